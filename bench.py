@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: YOLOv2-VOC dense fwd+bwd(+SGD step) images/sec at 416x416 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N = 1 runs in this process.  N > 1: when the process was started by a launcher (WORLD_SIZE in the environment, as the
 driver's `python -m torch.distributed.run ... bench.py --gpus N` does) it is one rank of N; started bare, it launches
@@ -13,9 +13,13 @@ One step = model(x) -> mean-of-logits loss -> backward (HIP engine) -> [gradient
 -> torch.optim.SGD step (lr 1e-5, momentum .9, weight_decay .0005*B: reference train.py:144-147)
 on one resident synthetic batch of B=64 images per GPU (BASELINE.json configs[1]).
 The TIMED step runs in the drop-in's default operand precision (`--precision auto` = "mixed": train-mode logits within
-north_star's 1e-3 of the reference's fp32 path); a second leg times the other precision of {mixed, fp16} and `parity` checks
-both against the oracle (`config.tolerance_mode`, `config.throughput_mode`).
-Prints ONE JSON line (rank 0).  The timed region is NOT instrumented; `roofline` comes from a separate pass of a few
+north_star's 1e-3 of the reference's fp32 path).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`value`, `ms_per_step`); `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs below).
+Everything else is measured with `--full` only (today's complete line): a second leg times the other precision of
+{mixed, fp16} and `parity` checks both against the oracle (`config.tolerance_mode`, `config.throughput_mode`), the
+`roofline` figures, `cpu_baseline`, and with N > 1 the all-reduce `overlap`.
+The timed region is NOT instrumented; `roofline` comes from a separate pass of a few
 more steps in which every convolution launch is bracketed by HIP events on the launch stream (medians per launch), for
 the dominant kernel: the implicit-GEMM MFMA convolution instance of the timed engine with the largest total time.
 `roofline_weight_gradient` is the same figure for the 9-tap weight-gradient kernel, whose total time is of the same size (it
@@ -143,6 +147,37 @@ def cpu_baseline(batch, steps):
                       "(oracle: fp32 PyTorch-CPU / oneDNN restatement of the reference; %d torch threads of the %d cores this "
                       "process may use -- more threads are slower, tools/cpu_threads_sweep.py)"
                       % (batch, steps, torch.get_num_threads(), ncpu)}
+
+
+def dump_outputs(d, model, out, loss):
+    """--dump-outputs DIR: what a caller of the timed step holds after the LAST timed step, as float32 .npy files --
+    logits.npy (region-layer logits of that step's forward), loss.npy, grad_sample.npy / weight_sample.npy (the parameters'
+    gradients and their values after the SGD update, concatenated in parameters() order) and bn_running_stats.npy (every
+    BatchNorm running_mean, then every running_var).  An array of more entries than its cap is a fixed sample: the sorted
+    distinct indices of a seeded draw, the same for every run and build, so that two builds compare entry for entry
+    (at most 4 M + 2 x 2 M float32 entries, 32 MB, plus the running statistics)."""
+    import numpy as np
+    import torch
+
+    def sample(t, cap, seed):
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            idx = np.unique(np.random.default_rng(seed).integers(0, t.numel(), cap))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return t.float().cpu().numpy()
+
+    params = list(model.parameters())
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    stats = [b for n, b in model.named_buffers() if n.endswith("running_mean")] + \
+            [b for n, b in model.named_buffers() if n.endswith("running_var")]
+    arrays = {"logits": sample(out, 1 << 22, 1),
+              "loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "grad_sample": sample(torch.cat([g.reshape(-1) for g in grads]), 1 << 21, 2),
+              "weight_sample": sample(torch.cat([p.detach().reshape(-1) for p in params]), 1 << 21, 2),
+              "bn_running_stats": torch.cat([b.reshape(-1).float() for b in stats]).cpu().numpy()}
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def spawn_ranks(n):
@@ -284,236 +319,18 @@ def bench_prune(args, model, dev):
     emit(res)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--batch", "--per-gpu-batch", dest="batch", type=int, default=64,
-                    help="images per GPU (BASELINE configs[3] = 256 over 8 GPUs: --per-gpu-batch 32)")
-    ap.add_argument("--loss", default="mean", choices=["mean", "region"],
-                    help="mean = mean of the logits (the headline line); region = the real train.py step: RegionLoss on "
-                         "synthetic boxes + the device-side overflow / non-finite policy (train.StepGuard), reference "
-                         "train.py:214-235")
-    ap.add_argument("--precision", default="auto", choices=["auto", "mixed", "fp16"],
-                    help="operand precision of the TIMED step: auto = the drop-in's training default (`mixed`: split hi/lo "
-                         "operands, train-mode logits within north_star's 1e-3); fp16 = plain operands, the throughput opt-in")
-    ap.add_argument("--no-tolerance-mode", "--no-second-precision", dest="no_tolerance_mode", action="store_true",
-                    help="skip the second timed leg (the OTHER precision of {mixed, fp16}) and the parity check")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-batch", type=int, default=64)
-    ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--profile-steps", type=int, default=5, help="instrumented steps (untimed) for the roofline entry")
-    ap.add_argument("--layer-table", default="", help="write the per-launch timing table to this file")
-    ap.add_argument("--transport", default=None, choices=["fp32", "fp16"], help="gradient all-reduce transport (N > 1)")
-    ap.add_argument("--workload", default="dense", choices=["dense", "filter40", "weight80", "slim60", "prune"],
-                    help="dense = BASELINE configs[1] (the default bench line); filter40 / weight80 = the retrain step of "
-                         "configs[2] / configs[3] with the reference's masks; slim60 = configs[4], eval forward of the "
-                         "physically slim 60 %% filter-pruned model (use --batch 128); prune = the mask computation itself")
-    args = ap.parse_args()
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(spawn_ranks(args.gpus))
-    claim_stdout()
-
+def roofline_pass(args, model, main_prec, step, fence, step_ms, rank):
+    """--full: per-kernel figures of the timed engine from an instrumented pass of a few more steps after the timed
+    region -- the `roofline` of the dominant kernel, `roofline_weight_gradient`, `event_pass`, the per-kernel fields
+    of `config` -- and the --layer-table file.  Returns those fields of the result line."""
     import torch
-    import torch.distributed as dist
-    from modelcompression_amd import nets, dp, YOLOV2_VOC_CFG, ops
-
-    # every pause of Python's cyclic garbage collector over the run (a host-side pause inside a step is a GPU-side gap once
-    # it outlasts the queued work): [generation, milliseconds, region] -- `region` is set around the timed loops
-    gc_log, gc_t0, region = [], [0.0], ["setup"]
-
-    def gc_watch(phase, info):
-        if phase == "start":
-            gc_t0[0] = time.perf_counter()
-        else:
-            gc_log.append((info.get("generation", -1), (time.perf_counter() - gc_t0[0]) * 1e3, region[0]))
-    gc.callbacks.append(gc_watch)
-    from modelcompression_amd import engine as engine_mod
-    from modelcompression_amd.synthetic import init_synthetic, synthetic_batch
-
-    # MCAMD_DP_BACKEND=gloo lets several ranks share one GPU (rehearsal of the N>1 path on a 1-GPU box)
-    backend = os.environ.get("MCAMD_DP_BACKEND") or None
-    ndev = max(torch.cuda.device_count(), 1)
-    os.environ["LOCAL_RANK"] = str(int(os.environ.get("LOCAL_RANK", "0")) % ndev)
-    rank, world = dp.init_from_env(backend)
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    assert world == args.gpus, "--gpus %d but WORLD_SIZE=%d" % (args.gpus, world)
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-
-    model = nets.Darknet(YOLOV2_VOC_CFG)
-    init_synthetic(model, seed=0)
-    model.to(dev).train()
-    if args.workload == "prune":
-        return bench_prune(args, model, dev)
-    # the timed precision: the drop-in's default unless asked otherwise; the other one of {mixed, fp16} is the second leg
-    main_prec = "fp16" if args.precision == "fp16" else "mixed"
-    other_prec = "mixed" if main_prec == "fp16" else "fp16"
-    model.precision = args.precision
-    B = args.batch
-    wl_name = "dense (0% prune)"
-    masks = None
-    if args.workload != "dense":
-        from modelcompression_amd.pruning.weightPruning.methods import weight_prune, quick_filter_prune
-        if args.workload == "weight80":
-            masks, wl_name = weight_prune(model, 80.0), "weight-pruned 80 % (magnitude masks)"
-        else:
-            perc = 40.0 if args.workload == "filter40" else 60.0
-            masks, wl_name = quick_filter_prune(model, perc), "filter-pruned %g %% (kept filters only)" % perc
-        if world > 1 or (dp.rehearsal() and dist.is_initialized()):
-            dp.broadcast_masks(masks, src=0)
-        model.set_masks(masks)
-    if args.workload == "slim60":
-        return bench_slim(args, model, dev, rank)
-    # same update rule as train.py:144-147; torch's fused multi-tensor implementation (one kernel per dtype/device)
-    opt = torch.optim.SGD(model.parameters(), lr=1e-5, momentum=0.9, dampening=0, weight_decay=0.0005 * B, fused=True)
-    reducer = None
-    dp_on = world > 1 or (dp.rehearsal() and dist.is_initialized())     # MCAMD_DP_REHEARSE=1: one-rank RCCL rehearsal
-    if dp_on:
-        # static weight masks (configs[3]): only the kept gradient entries travel
-        reducer = dp.attach(model, dp.GradReducer(transport=args.transport),
-                            masks=masks if args.workload == "weight80" else None)
-    x = synthetic_batch(B, 416, 416, seed=rank, device=dev)   # resident in HBM before the timed region
-    state0 = None
-    if not args.no_tolerance_mode and not args.no_cpu_baseline and not dp_on:
-        state0 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}   # for the parity check below
-    guard = target = None
-    if args.loss == "region":
-        # the real training step (reference train.py:214-235): RegionLoss on seeded synthetic boxes, resident in HBM, and
-        # train.py's skip policy -- decided on the device, read by the host one step late (no synchronisation in the step)
-        from modelcompression_amd.data import SyntheticDetection
-        from modelcompression_amd.train import StepGuard
-        ds = SyntheticDetection(B, shape=(416, 416), seed=100 + rank)
-        target = torch.stack([ds[i][1] for i in range(B)]).float().to(dev)
-        region_loss = model.loss
-        region_loss.seen = 0
-        guard = StepGuard(model, opt, dev)
-
-    steps_done = [0]
-
-    def step():
-        steps_done[0] += 1
-        out = model(x)
-        if guard is not None:
-            region_loss.seen = region_loss.seen + B * world
-            loss = region_loss(out, target)
-            opt.zero_grad()
-            loss.backward()
-            guard.decide(loss)
-            opt.step()
-            return
-        # mean of the logits: dL/dlogit = 1 / (B * 125 * 13 * 13).  (Rounds 1's sum-of-logits loss, dL/dlogit = 1, makes
-        # gradients of 1e3-1e5 that lr 1e-5 turns into O(1) weight updates: the run diverged within a few steps and
-        # only the fp16 saturation of the stored gradients kept it finite -- the overflow flag now shows that.)
-        loss = out.float().mean()
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-
-    def fence():
-        if dp_on:
-            dist.barrier(device_ids=[local]) if dist.get_backend() == "nccl" else dist.barrier()
-        torch.cuda.synchronize()
-
-    # fp16 gradient storage: the engine keeps grad_scale x gradient and saturates at +-65504 (flagged).  Settle the
-    # scale during warm-up the way train.py does per step (skip + reduce, all ranks together), then time with it fixed.
-    skipped_warm = 0
-    if guard is None:
-        for it in range(10):
-            step()
-            over = model.grad_overflowed()
-            if dp_on:
-                over = not dp.all_ranks_ok(not over, dev)
-            if not over:
-                break
-            model.grad_scale = model.grad_scale / 16.0
-    else:
-        for it in range(24):                  # StepGuard settles the scale itself (halving, one step late)
-            step()
-        guard.finish()
-        skipped_warm = guard.skipped
-    for _ in range(max(args.warmup, 1)):      # builds and warms the engine of the final scale
-        step()
-    if guard is not None:
-        guard.finish()
-        skipped_warm = guard.skipped
-    gc.collect()      # (a full collection now, so that none falls into the timed steps by accident of the allocation count)
-    fence()
-    region[0] = "timed"
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    dt = time.perf_counter() - t0
-    region[0] = "after"
-    flat = model._last_flat_grad
-    assert flat is not None and bool(torch.isfinite(flat).all()), "non-finite gradients in the timed run"
-    if guard is not None:
-        guard.finish()
-        assert guard.skipped == skipped_warm, "a step of the timed run was skipped (fp16 gradient overflow)"
-    else:
-        assert not model.grad_overflowed(), "a scaled gradient saturated the fp16 range in the timed run"
-    if reducer is not None:
-        assert not reducer.transport_overflowed(), "the fp16 all-reduce transport clamped a gradient in the timed run"
-    if dp_on:
-        t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-        # every rank must hold the same averaged gradient and the same weights after the same steps
-        sig = torch.stack([flat.double().sum(), flat.double().abs().sum(),
-                           sum(p.detach().double().sum() for p in model.parameters())])
-        lo, hi = sig.clone(), sig.clone()
-        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-        # (bit-identical is what a ring / tree all-reduce delivers; a last-bit difference between ranks would not
-        # invalidate the timing, a real divergence does)
-        spread = float(((hi - lo).abs() / hi.abs().clamp_min(1e-30)).max())
-        assert spread < 1e-6, "ranks diverged: gradient / weight checksums differ (%s vs %s)" % (lo.tolist(), hi.tolist())
-
-    # ---- how much of the gradient all-reduce is hidden under the backward pass (N > 1 / rehearsal): the same collectives
-    # alone on an idle GPU, and the same step without them (hooks detached; the ranks' weights drift apart from here on,
-    # which no later leg depends on)
-    overlap = None
-    red_steps = red_bytes = red_colls = 0
-    if dp_on:
-        red_steps, red_bytes, red_colls = steps_done[0], reducer.bytes_reduced, reducer.collectives
-        k = max(3, min(args.steps, 10))
-        tmp = torch.zeros_like(flat)
-        pre, reducer.prescaled = reducer.prescaled, True
-        reducer.reduce_flat(tmp)
-        fence()
-        ta = time.perf_counter()
-        for _ in range(k):
-            reducer.reduce_flat(tmp)
-        fence()
-        t_ar = (time.perf_counter() - ta) / k
-        reducer.prescaled = pre
-        hooks = (model._grad_ready_hook, model._grad_hook)
-        model._grad_ready_hook = model._grad_hook = None
-        step()
-        fence()
-        ta = time.perf_counter()
-        for _ in range(k):
-            step()
-        fence()
-        t_nodp = (time.perf_counter() - ta) / k
-        model._grad_ready_hook, model._grad_hook = hooks
-        tt = torch.tensor([t_ar, t_nodp], device=dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        t_ar, t_nodp = (float(v) for v in tt.tolist())
-        t_dp = dt / args.steps
-        overlap = {"allreduce_alone_ms": round(t_ar * 1e3, 3), "step_without_allreduce_ms": round(t_nodp * 1e3, 3),
-                   "step_ms": round(t_dp * 1e3, 3),
-                   "hidden_frac": round(max(0.0, min(1.0, (t_nodp + t_ar - t_dp) / t_ar)), 3) if t_ar > 0 else None}
-
+    from modelcompression_amd import ops
     # ---- roofline of the dominant kernel, from a SEPARATE instrumented pass (the timed region above carries no events):
     # every conv launch bracketed by HIP events on the launch stream
     eng = [e for e in model._engines.values() if e.precision == main_prec and e.grad_scale == float(model.grad_scale)][0]
     # One instrumented step at a time, harvested before the next: at most one step's events are alive (round 3 kept all
     # 5 x 138 timing events until the end), the event objects are reused, and the garbage collector is kept out of the
-    # pass (its pauses over the whole run are measured by `gc_watch` below and reported).  Per launch the MEDIAN over the
+    # pass (its pauses over the whole run are measured by main's `gc_watch` and reported).  Per launch the MEDIAN over the
     # instrumented steps is published -- one outlier pair (BENCH_r03: one 117 ms ('wgrad', layer) pair in 5 steps made
     # "wgrad 26.251 ms per step") cannot poison a figure -- and the slowest pair is reported with its host-side times.
     nprof = max(1, args.profile_steps)
@@ -599,13 +416,298 @@ def main():
                 traffic_source = tj.get("source", "profiles/dominant_kernel_traffic.json")
         except Exception:
             traffic = None
-    step_ms = dt / args.steps * 1e3
     if rank == 0 and args.layer_table:
         with open(args.layer_table, "w") as f:
             f.write("\n".join(rows) + "\n")
             for tag, (ms, fl) in tot.items():
                 f.write("TOTAL %-6s %8.3f ms/step  %8.1f TFLOP/s\n" % (tag, ms, fl / ms / 1e9 if ms else 0))
             f.write("step %.3f ms (uninstrumented); conv kernels %.3f ms\n" % (step_ms, sum(v[0] for v in tot.values())))
+    res = {"config": {"conv_kernel_ms_per_step": {k: round(v[0], 3) for k, v in tot.items()},
+                      "conv_kernel_tflops": {k: round(v[1] / v[0] / 1e9, 1) if v[0] else 0.0 for k, v in tot.items()}},
+        "roofline": {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
+                     "frac": round(achieved / PEAK_FP16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                     "algorithmic_gflop_per_launch": round(dom_flop / max(dom_n, 1) / 1e9, 2),
+                     # split-operand launches execute 3 MFMA products per algorithmic multiply -- one fp16 + two fp8 at twice
+                     # the rate (= 2 fp16-equivalent products) in the fp8-correction form: the rate the matrix cores actually
+                     # ran at, in fp16-equivalent flops (achieved counts the reference's 2 M N K only, as the contract asks)
+                     "mfma_tflops_executed": round(executed, 1), "mfma_frac_executed": round(executed / PEAK_FP16_TFLOPS, 4),
+                     "kernel": ("igemm_pp_kernel<%d,%d,%d,%s> %dx%dx%d ping-pong (%s launches of that instance)" % (
+                                    (dom_tile[4],) + dom_tile[:2] + ("32,true" if dom_tile[5] else "16",) + dom_tile[:3] +
+                                    (("split-operand conv forward with fp8 correction terms, fp32 raw output" if dom_tile[5] else
+                                      "split-operand conv forward, fp32 raw output") if dom_tile[4] == 3 else "conv fwd + dgrad",))
+                                if dom_tile[3] == 2 else
+                                "igemm_kernel<%d,%d,..,%d,2,%d> (conv launches of that instance)" % (dom_tile[:3] + (dom_tile[4],))),
+                     "launches_per_step": dom_n // nprof,
+                     "avg_launch_ms": round(dom_ms / max(dom_n, 1), 4),
+                     "measured": "HIP events around every launch in %d extra steps after the timed region; per launch the "
+                                 "median over those steps" % nprof},
+    }
+    if wg9:
+        wk = max(wg9, key=lambda k_: wg9[k_][0])
+        wms, wfl, wn = wg9[wk]
+        res["roofline_weight_gradient"] = {
+            "bound": "mfma", "achieved": round(wfl / (wms * 1e-3) / 1e12, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(wfl / (wms * 1e-3) / 1e12 / PEAK_FP16_TFLOPS, 4), "kernel": wk + " + its slab-reduction pass",
+            "launches_per_step": wn // nprof, "avg_launch_ms": round(wms / max(wn, 1), 4),
+            "ms_per_step": round(wms / nprof, 3), "dominant_conv_instance_ms_per_step": round(dom_ms / nprof, 3),
+            "note": "the weight-gradient kernel with the largest total time, same event pass (it runs on the second stream in "
+                    "the timed step); ALGORITHMIC flops 2 M Cout Cin 9 of the launches' layers"}
+    # the instrumented pass, as evidence: what the slowest single event pair was and what the host did inside it
+    # (seconds spent in [event record, library call, event record]); a per-step sum of kernel times cannot exceed ~1.5 steps
+    # (the timed step overlaps the weight gradients with the rest; serialised they add ~10 %)
+    res["event_pass"] = {"steps": nprof, "statistic": "median per launch",
+                         "max_pair_ms": round(worst[0], 3), "max_pair_at": {"tag": worst[1], "conv": worst[2] + 1, "step": worst[3]},
+                         "max_pair_host_ms": [round(v * 1e3, 3) for v in worst[4]]}
+    if rank != 0:
+        return res
+    ksum = sum(v[0] for v in tot.values())
+    assert ksum < 1.5 * step_ms, ("instrumented pass inconsistent with the timed step: conv kernels %.3f ms per step vs %.3f ms "
+                                 "per step; slowest pair %r" % (ksum, step_ms, worst))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", "--per-gpu-batch", dest="batch", type=int, default=64,
+                    help="images per GPU (BASELINE configs[3] = 256 over 8 GPUs: --per-gpu-batch 32)")
+    ap.add_argument("--loss", default="mean", choices=["mean", "region"],
+                    help="mean = mean of the logits (the headline line); region = the real train.py step: RegionLoss on "
+                         "synthetic boxes + the device-side overflow / non-finite policy (train.StepGuard), reference "
+                         "train.py:214-235")
+    ap.add_argument("--precision", default="auto", choices=["auto", "mixed", "fp16"],
+                    help="operand precision of the TIMED step: auto = the drop-in's training default (`mixed`: split hi/lo "
+                         "operands, train-mode logits within north_star's 1e-3); fp16 = plain operands, the throughput opt-in")
+    ap.add_argument("--no-tolerance-mode", "--no-second-precision", dest="no_tolerance_mode", action="store_true",
+                    help="skip the second timed leg (the OTHER precision of {mixed, fp16}) and the parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-batch", type=int, default=64)
+    ap.add_argument("--cpu-steps", type=int, default=3)
+    ap.add_argument("--profile-steps", type=int, default=5, help="instrumented steps (untimed) for the roofline entry")
+    ap.add_argument("--layer-table", default="", help="write the per-launch timing table to this file")
+    ap.add_argument("--transport", default=None, choices=["fp32", "fp16"], help="gradient all-reduce transport (N > 1)")
+    ap.add_argument("--workload", default="dense", choices=["dense", "filter40", "weight80", "slim60", "prune"],
+                    help="dense = BASELINE configs[1] (the default bench line); filter40 / weight80 = the retrain step of "
+                         "configs[2] / configs[3] with the reference's masks; slim60 = configs[4], eval forward of the "
+                         "physically slim 60 %% filter-pruned model (use --batch 128); prune = the mask computation itself")
+    ap.add_argument("--full", action="store_true",
+                    help="dense / filter40 / weight80: also measure and check what the headline figure does not need -- the "
+                         "second precision's leg, parity against the oracle, the instrumented roofline pass (--layer-table), "
+                         "cpu_baseline and, with N > 1, the all-reduce overlap legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)")
+    args = ap.parse_args()
+    if args.layer_table and not args.full:
+        ap.error("--layer-table comes from the instrumented pass of --full")
+    if args.dump_outputs and args.workload in ("prune", "slim60"):
+        ap.error("--dump-outputs: the training-step workloads only (dense, filter40, weight80)")
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(spawn_ranks(args.gpus))
+    claim_stdout()
+
+    import torch
+    import torch.distributed as dist
+    from modelcompression_amd import nets, dp, YOLOV2_VOC_CFG
+
+    # every pause of Python's cyclic garbage collector over the run (a host-side pause inside a step is a GPU-side gap once
+    # it outlasts the queued work): [generation, milliseconds, region] -- `region` is set around the timed loops
+    gc_log, gc_t0, region = [], [0.0], ["setup"]
+
+    def gc_watch(phase, info):
+        if phase == "start":
+            gc_t0[0] = time.perf_counter()
+        else:
+            gc_log.append((info.get("generation", -1), (time.perf_counter() - gc_t0[0]) * 1e3, region[0]))
+    gc.callbacks.append(gc_watch)
+    from modelcompression_amd import engine as engine_mod
+    from modelcompression_amd.synthetic import init_synthetic, synthetic_batch
+
+    # MCAMD_DP_BACKEND=gloo lets several ranks share one GPU (rehearsal of the N>1 path on a 1-GPU box)
+    backend = os.environ.get("MCAMD_DP_BACKEND") or None
+    ndev = max(torch.cuda.device_count(), 1)
+    os.environ["LOCAL_RANK"] = str(int(os.environ.get("LOCAL_RANK", "0")) % ndev)
+    rank, world = dp.init_from_env(backend)
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    assert world == args.gpus, "--gpus %d but WORLD_SIZE=%d" % (args.gpus, world)
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+
+    model = nets.Darknet(YOLOV2_VOC_CFG)
+    init_synthetic(model, seed=0)
+    model.to(dev).train()
+    if args.workload == "prune":
+        return bench_prune(args, model, dev)
+    # the timed precision: the drop-in's default unless asked otherwise; the other one of {mixed, fp16} is the second leg
+    main_prec = "fp16" if args.precision == "fp16" else "mixed"
+    other_prec = "mixed" if main_prec == "fp16" else "fp16"
+    model.precision = args.precision
+    B = args.batch
+    wl_name = "dense (0% prune)"
+    masks = None
+    if args.workload != "dense":
+        from modelcompression_amd.pruning.weightPruning.methods import weight_prune, quick_filter_prune
+        if args.workload == "weight80":
+            masks, wl_name = weight_prune(model, 80.0), "weight-pruned 80 % (magnitude masks)"
+        else:
+            perc = 40.0 if args.workload == "filter40" else 60.0
+            masks, wl_name = quick_filter_prune(model, perc), "filter-pruned %g %% (kept filters only)" % perc
+        if world > 1 or (dp.rehearsal() and dist.is_initialized()):
+            dp.broadcast_masks(masks, src=0)
+        model.set_masks(masks)
+    if args.workload == "slim60":
+        return bench_slim(args, model, dev, rank)
+    # same update rule as train.py:144-147; torch's fused multi-tensor implementation (one kernel per dtype/device)
+    opt = torch.optim.SGD(model.parameters(), lr=1e-5, momentum=0.9, dampening=0, weight_decay=0.0005 * B, fused=True)
+    reducer = None
+    dp_on = world > 1 or (dp.rehearsal() and dist.is_initialized())     # MCAMD_DP_REHEARSE=1: one-rank RCCL rehearsal
+    if dp_on:
+        # static weight masks (configs[3]): only the kept gradient entries travel
+        reducer = dp.attach(model, dp.GradReducer(transport=args.transport),
+                            masks=masks if args.workload == "weight80" else None)
+    x = synthetic_batch(B, 416, 416, seed=rank, device=dev)   # resident in HBM before the timed region
+    state0 = None
+    if args.full and not args.no_tolerance_mode and not args.no_cpu_baseline and not dp_on:
+        state0 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}   # for the parity check below
+    guard = target = None
+    if args.loss == "region":
+        # the real training step (reference train.py:214-235): RegionLoss on seeded synthetic boxes, resident in HBM, and
+        # train.py's skip policy -- decided on the device, read by the host one step late (no synchronisation in the step)
+        from modelcompression_amd.data import SyntheticDetection
+        from modelcompression_amd.train import StepGuard
+        ds = SyntheticDetection(B, shape=(416, 416), seed=100 + rank)
+        target = torch.stack([ds[i][1] for i in range(B)]).float().to(dev)
+        region_loss = model.loss
+        region_loss.seen = 0
+        guard = StepGuard(model, opt, dev)
+
+    steps_done = [0]
+    last = [None, None]     # (logits, loss) of the latest step: what --dump-outputs writes after the timed ones
+
+    def step():
+        steps_done[0] += 1
+        out = model(x)
+        if guard is not None:
+            region_loss.seen = region_loss.seen + B * world
+            loss = region_loss(out, target)
+            opt.zero_grad()
+            loss.backward()
+            guard.decide(loss)
+            opt.step()
+            last[0], last[1] = out, loss
+            return
+        # mean of the logits: dL/dlogit = 1 / (B * 125 * 13 * 13).  (Rounds 1's sum-of-logits loss, dL/dlogit = 1, makes
+        # gradients of 1e3-1e5 that lr 1e-5 turns into O(1) weight updates: the run diverged within a few steps and
+        # only the fp16 saturation of the stored gradients kept it finite -- the overflow flag now shows that.)
+        loss = out.float().mean()
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        last[0], last[1] = out, loss
+
+    def fence():
+        if dp_on:
+            dist.barrier(device_ids=[local]) if dist.get_backend() == "nccl" else dist.barrier()
+        torch.cuda.synchronize()
+
+    # fp16 gradient storage: the engine keeps grad_scale x gradient and saturates at +-65504 (flagged).  Settle the
+    # scale during warm-up the way train.py does per step (skip + reduce, all ranks together), then time with it fixed.
+    skipped_warm = 0
+    if guard is None:
+        for it in range(10):
+            step()
+            over = model.grad_overflowed()
+            if dp_on:
+                over = not dp.all_ranks_ok(not over, dev)
+            if not over:
+                break
+            model.grad_scale = model.grad_scale / 16.0
+    else:
+        for it in range(24):                  # StepGuard settles the scale itself (halving, one step late)
+            step()
+        guard.finish()
+        skipped_warm = guard.skipped
+    for _ in range(max(args.warmup, 1)):      # builds and warms the engine of the final scale
+        step()
+    if guard is not None:
+        guard.finish()
+        skipped_warm = guard.skipped
+    gc.collect()      # (a full collection now, so that none falls into the timed steps by accident of the allocation count)
+    fence()
+    region[0] = "timed"
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    fence()
+    dt = time.perf_counter() - t0
+    region[0] = "after"
+    flat = model._last_flat_grad
+    assert flat is not None and bool(torch.isfinite(flat).all()), "non-finite gradients in the timed run"
+    if guard is not None:
+        guard.finish()
+        assert guard.skipped == skipped_warm, "a step of the timed run was skipped (fp16 gradient overflow)"
+    else:
+        assert not model.grad_overflowed(), "a scaled gradient saturated the fp16 range in the timed run"
+    if reducer is not None:
+        assert not reducer.transport_overflowed(), "the fp16 all-reduce transport clamped a gradient in the timed run"
+    if dp_on:
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+        # every rank must hold the same averaged gradient and the same weights after the same steps
+        sig = torch.stack([flat.double().sum(), flat.double().abs().sum(),
+                           sum(p.detach().double().sum() for p in model.parameters())])
+        lo, hi = sig.clone(), sig.clone()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+        # (bit-identical is what a ring / tree all-reduce delivers; a last-bit difference between ranks would not
+        # invalidate the timing, a real divergence does)
+        spread = float(((hi - lo).abs() / hi.abs().clamp_min(1e-30)).max())
+        assert spread < 1e-6, "ranks diverged: gradient / weight checksums differ (%s vs %s)" % (lo.tolist(), hi.tolist())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last[0], last[1])
+
+    # ---- how much of the gradient all-reduce is hidden under the backward pass (N > 1 / rehearsal): the same collectives
+    # alone on an idle GPU, and the same step without them (hooks detached; the ranks' weights drift apart from here on,
+    # which no later leg depends on)
+    overlap = None
+    red_steps = red_bytes = red_colls = 0
+    if dp_on:
+        red_steps, red_bytes, red_colls = steps_done[0], reducer.bytes_reduced, reducer.collectives
+    if dp_on and args.full:
+        k = max(3, min(args.steps, 10))
+        tmp = torch.zeros_like(flat)
+        pre, reducer.prescaled = reducer.prescaled, True
+        reducer.reduce_flat(tmp)
+        fence()
+        ta = time.perf_counter()
+        for _ in range(k):
+            reducer.reduce_flat(tmp)
+        fence()
+        t_ar = (time.perf_counter() - ta) / k
+        reducer.prescaled = pre
+        hooks = (model._grad_ready_hook, model._grad_hook)
+        model._grad_ready_hook = model._grad_hook = None
+        step()
+        fence()
+        ta = time.perf_counter()
+        for _ in range(k):
+            step()
+        fence()
+        t_nodp = (time.perf_counter() - ta) / k
+        model._grad_ready_hook, model._grad_hook = hooks
+        tt = torch.tensor([t_ar, t_nodp], device=dev, dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        t_ar, t_nodp = (float(v) for v in tt.tolist())
+        t_dp = dt / args.steps
+        overlap = {"allreduce_alone_ms": round(t_ar * 1e3, 3), "step_without_allreduce_ms": round(t_nodp * 1e3, 3),
+                   "step_ms": round(t_dp * 1e3, 3),
+                   "hidden_frac": round(max(0.0, min(1.0, (t_nodp + t_ar - t_dp) / t_ar)), 3) if t_ar > 0 else None}
+
+    step_ms = dt / args.steps * 1e3
+    roof = roofline_pass(args, model, main_prec, step, fence, step_ms, rank) if args.full else None
 
     # ---- second timed leg: the OTHER precision of {mixed, fp16} -- same step, same batch, same barriers.  `mixed` (split
     # hi/lo operands on all but the costliest blocks, engine.py) meets north_star's 1e-3 on the region-layer logits; plain
@@ -625,7 +727,7 @@ def main():
             d["note"] = "plain fp16 MFMA operands everywhere: its train-mode logits do NOT meet 1e-3 (see `parity`)"
         return d
     legs = {main_prec: leg_info(main_prec, dt)}
-    if not args.no_tolerance_mode:
+    if args.full and not args.no_tolerance_mode:
         model.precision = other_prec
         for _ in range(max(2, min(args.warmup, 3))):
             step()
@@ -703,50 +805,16 @@ def main():
                    # (None: overlap off or probe disabled; False: no concurrent stream found, the step is serialised)
                    "second_stream_concurrent": next(iter(engine_mod.Engine._SIDE_STREAMS.values()), (None, None))[1],
                    "conv_tflops_whole_step": round(value * FWD_BWD_GFLOP_PER_IMG / 1e3, 1),
-                   "frac_of_fp16_mfma_peak_whole_step": round(value * FWD_BWD_GFLOP_PER_IMG / 1e3 / (PEAK_FP16_TFLOPS * world), 4),
-                   "conv_kernel_ms_per_step": {k: round(v[0], 3) for k, v in tot.items()},
-                   "conv_kernel_tflops": {k: round(v[1] / v[0] / 1e9, 1) if v[0] else 0.0 for k, v in tot.items()}},
-        "roofline": {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / PEAK_FP16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                     "algorithmic_gflop_per_launch": round(dom_flop / max(dom_n, 1) / 1e9, 2),
-                     # split-operand launches execute 3 MFMA products per algorithmic multiply -- one fp16 + two fp8 at twice
-                     # the rate (= 2 fp16-equivalent products) in the fp8-correction form: the rate the matrix cores actually
-                     # ran at, in fp16-equivalent flops (achieved counts the reference's 2 M N K only, as the contract asks)
-                     "mfma_tflops_executed": round(executed, 1), "mfma_frac_executed": round(executed / PEAK_FP16_TFLOPS, 4),
-                     "kernel": ("igemm_pp_kernel<%d,%d,%d,%s> %dx%dx%d ping-pong (%s launches of that instance)" % (
-                                    (dom_tile[4],) + dom_tile[:2] + ("32,true" if dom_tile[5] else "16",) + dom_tile[:3] +
-                                    (("split-operand conv forward with fp8 correction terms, fp32 raw output" if dom_tile[5] else
-                                      "split-operand conv forward, fp32 raw output") if dom_tile[4] == 3 else "conv fwd + dgrad",))
-                                if dom_tile[3] == 2 else
-                                "igemm_kernel<%d,%d,..,%d,2,%d> (conv launches of that instance)" % (dom_tile[:3] + (dom_tile[4],))),
-                     "launches_per_step": dom_n // nprof,
-                     "avg_launch_ms": round(dom_ms / max(dom_n, 1), 4),
-                     "measured": "HIP events around every launch in %d extra steps after the timed region; per launch the "
-                                 "median over those steps" % nprof},
+                   "frac_of_fp16_mfma_peak_whole_step": round(value * FWD_BWD_GFLOP_PER_IMG / 1e3 / (PEAK_FP16_TFLOPS * world), 4)},
     }
-    if wg9:
-        wk = max(wg9, key=lambda k_: wg9[k_][0])
-        wms, wfl, wn = wg9[wk]
-        res["roofline_weight_gradient"] = {
-            "bound": "mfma", "achieved": round(wfl / (wms * 1e-3) / 1e12, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
-            "frac": round(wfl / (wms * 1e-3) / 1e12 / PEAK_FP16_TFLOPS, 4), "kernel": wk + " + its slab-reduction pass",
-            "launches_per_step": wn // nprof, "avg_launch_ms": round(wms / max(wn, 1), 4),
-            "ms_per_step": round(wms / nprof, 3), "dominant_conv_instance_ms_per_step": round(dom_ms / nprof, 3),
-            "note": "the weight-gradient kernel with the largest total time, same event pass (it runs on the second stream in "
-                    "the timed step); ALGORITHMIC flops 2 M Cout Cin 9 of the launches' layers"}
-    # the instrumented pass, as evidence: what the slowest single event pair was and what the host did inside it
-    # (seconds spent in [event record, library call, event record]); a per-step sum of kernel times cannot exceed ~1.5 steps
-    # (the timed step overlaps the weight gradients with the rest; serialised they add ~10 %)
-    res["event_pass"] = {"steps": nprof, "statistic": "median per launch",
-                         "max_pair_ms": round(worst[0], 3), "max_pair_at": {"tag": worst[1], "conv": worst[2] + 1, "step": worst[3]},
-                         "max_pair_host_ms": [round(v * 1e3, 3) for v in worst[4]]}
+    if roof is not None:
+        res["config"].update(roof.pop("config"))
+        res.update(roof)
     gcs = [g for g in gc_log if g[2].startswith("timed")]
     res["host"] = {"gc_collections": len(gc_log), "gc_max_pause_ms": round(max([g[1] for g in gc_log] or [0.0]), 2),
                    "gc_pauses_in_timed_regions": [[g[0], round(g[1], 2), g[2]] for g in gcs]}
-    ksum = sum(v[0] for v in tot.values())
-    assert ksum < 1.5 * step_ms, ("instrumented pass inconsistent with the timed step: conv kernels %.3f ms per step vs %.3f ms "
-                                 "per step; slowest pair %r" % (ksum, step_ms, worst))
-    res["parity"] = parity
+    if args.full:
+        res["parity"] = parity
     if dp_on:
         res["cpu_baseline"] = None
         res["collective"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
@@ -755,7 +823,7 @@ def main():
                              "bytes_per_step_per_rank": red_bytes // max(1, red_steps),
                              "collectives_per_step": red_colls // max(1, red_steps),
                              "overlap": overlap}
-    elif not args.no_cpu_baseline:
+    elif args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(cpu_batch_for_host(args.cpu_batch), args.cpu_steps)
     emit(res)
 

@@ -42,7 +42,7 @@ def test_bench_two_rank_rehearsal_per_gpu_batch_32_region_loss(dev):
     env["MCAMD_DP_BACKEND"] = "gloo"
     env.setdefault("OMP_NUM_THREADS", "4")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--per-gpu-batch", "32", "--loss", "region",
-           "--workload", "weight80", "--steps", "2", "--warmup", "1", "--profile-steps", "1"]
+           "--workload", "weight80", "--steps", "2", "--warmup", "1", "--profile-steps", "1", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]

@@ -41,6 +41,33 @@ def test_smoke_entry(dev):
     g.smoke()
 
 
+def test_bench_plain_run_dumps_last_step(dev, tmp_path):
+    """A plain `bench.py` run prints the headline line only (the rest is `--full`'s) and `--dump-outputs` writes the last
+    timed step's results: float32 arrays, finite, the loss = the mean of the dumped logits (the headline loss)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--batch", "8", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0 and res["unit"] == "images/s"
+    assert res["higher_is_better"] is True and res["dtype"] == "fp16"
+    assert not {"roofline", "cpu_baseline", "parity"} & set(res) and res["config"]["throughput_mode"] is None
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert set(got) == {"logits", "loss", "grad_sample", "weight_sample", "bn_running_stats"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    assert got["logits"].size == 8 * 125 * 13 * 13 and got["grad_sample"].size == got["weight_sample"].size > 1 << 20
+    logits = got["logits"].astype(np.float64)
+    assert abs(logits.mean() - float(got["loss"][0])) <= 1e-5 * np.abs(logits).mean()
+
+
 def test_training_overfits_a_fixed_batch(dev):
     """End-to-end training dynamics (tools/soak.py): RegionLoss + engine backward + SGD on one fixed synthetic batch
     must drive the loss down by more than an order of magnitude -- a sign or scale error anywhere in the gradient

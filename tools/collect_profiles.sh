@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_final
 rm -rf $OUT && mkdir -p $OUT
 export MCAMD_OVERLAP_WGRAD=0
-CMD="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-tolerance-mode"
+CMD="python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-tolerance-mode"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $CMD --layer-table $OUT/layer_table.txt > $OUT/stats.log 2>&1
 echo "stats done"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > $OUT/fetch.log 2>&1
@@ -28,12 +28,12 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prune_stats -- pyth
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/prune_fetch -- python3 bench.py --workload prune --steps 10 --no-cpu-baseline > $OUT/prune_fetch.log 2>&1
 echo "prune done"
 unset MCAMD_OVERLAP_WGRAD
-python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
 python bench.py --workload prune > $OUT/bench_prune.json 2> $OUT/bench_prune.err
-python bench.py --loss region --no-cpu-baseline > $OUT/bench_region.json 2> $OUT/bench_region.err
-python bench.py --workload filter40 --no-cpu-baseline > $OUT/bench_filter40.json 2> $OUT/bench_filter40.err
-python bench.py --workload weight80 --per-gpu-batch 32 --loss region --no-cpu-baseline > $OUT/bench_weight80_b32_region.json 2> $OUT/bench_weight80_b32_region.err
+python bench.py --loss region --full --no-cpu-baseline > $OUT/bench_region.json 2> $OUT/bench_region.err
+python bench.py --workload filter40 --full --no-cpu-baseline > $OUT/bench_filter40.json 2> $OUT/bench_filter40.err
+python bench.py --workload weight80 --per-gpu-batch 32 --loss region --full --no-cpu-baseline > $OUT/bench_weight80_b32_region.json 2> $OUT/bench_weight80_b32_region.err
 python bench.py --workload slim60 --batch 128 > $OUT/bench_slim60.json 2> $OUT/bench_slim60.err
 echo "workload lines done"
 tail -c 600 $OUT/bench.json

@@ -54,8 +54,12 @@ reducer = dp.attach(model, dp.GradReducer(bucket_elems=2 << 20), masks=masks)   
 got = step()
 ok = torch.equal(got, expect)
 diff = float((got - expect).abs().max())
-print("rank %d: %s transport, %d collectives, max |dp - mean of locals| = %.3e -> %s" % (
-    rank, "packed" if masks is not None else "dense", reducer.collectives, diff, "OK" if ok else "MISMATCH"), flush=True)
+line = "rank %d: %s transport, %d collectives, max |dp - mean of locals| = %.3e -> %s\n" % (
+    rank, "packed" if masks is not None else "dense", reducer.collectives, diff, "OK" if ok else "MISMATCH")
+# the ranks share the launcher's stdout: one write per line (print() issues the text and the newline separately when stdout
+# is unbuffered, and the other rank's line can land between them)
+sys.stdout.flush()
+os.write(sys.stdout.fileno(), line.encode())
 t = torch.tensor([1 if ok else 0])
 dist.all_reduce(t, op=dist.ReduceOp.MIN)
 dist.destroy_process_group()

@@ -15,7 +15,7 @@ shutil.copy(os.path.join(src, "layer_table.txt"), "profiles/%s_layer_table.txt" 
 with open("profiles/%s_mixed_step_kernel_summary.txt" % tag, "w") as f:
     rows = list(csv.DictReader(open(st)))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
-    f.write("rocprofv3 --kernel-trace --stats of `bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-tolerance-mode` (default precision: mixed,\n"
+    f.write("rocprofv3 --kernel-trace --stats of `bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-tolerance-mode` (default precision: mixed,\n"
             "weight gradients serialised onto the launch stream); source: profiles/%s_kernel_stats.csv\n\n" % tag)
     f.write("%-110s %7s %10s %10s %6s\n" % ("kernel", "calls", "total ms", "avg us", "%"))
     for r in rows[:40]:
