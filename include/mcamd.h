@@ -514,6 +514,44 @@ int mcamd_region_loss(const mcamd_region_desc* d, float* loss, float* grad, int3
                       size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Training augmentation (reference src/dataloader.py:148-178 data_augmentation + ToTensor(), train=True): per image
+ * crop (outside the source reads 0) -> Pillow bicubic resize -> optional left-right flip -> Pillow RGB->HSV, three
+ * point LUTs, HSV->RGB -> out = u8 / 255.f.  Bit-equal to the reference's PIL chain: the host builds Pillow's
+ * fixed-point tables and the LUTs (modelcompression_amd/augment.py), the device only applies them.  Two launches
+ * (horizontal pass into tmp, then vertical pass + flip + HSV + store); no host synchronisation.
+ *   src  : uint8 RGB sources, HWC, rows of src_w * 3 bytes, image b at src + desc[b].src_off
+ *   coef : int32 resampling tables; a table for n outputs with k taps is n rows of (first, count, k[0..k-1]):
+ *          output o = clip8((2^21 + sum_t in[first + t] * k[t]) >> 22), t < count
+ *   lut  : uint8 [3][256] per image (H, S, V) at lut + desc[b].lut_off
+ *   tmp  : workspace (4-byte aligned), crop_h rows of W * 4 bytes (R, G, B, 0) per image at tmp + desc[b].tmp_off
+ *   out  : fp32 [B][3][H][W]
+ * Returns MCAMD_EINVAL for an empty crop (crop_w or crop_h < 1: the reference makes an image of no pixels there) and
+ * for any table / LUT / source / workspace extent outside its buffer; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+typedef struct mcamd_augment_desc {
+    int64_t src_off;            /* byte offset of the source in src */
+    int64_t tmp_off;            /* byte offset of this image's horizontal-pass rows in tmp, a multiple of 4 */
+    int32_t src_w, src_h;       /* source size, pixels */
+    int32_t crop_x, crop_y;     /* crop origin in source pixels (pleft, ptop; may be negative) */
+    int32_t crop_w, crop_h;     /* crop size (swidth - 1, sheight - 1: the reference's box is inclusive-exclusive) */
+    int32_t flip;               /* left-right flip after the resize */
+    int32_t hk, vk;             /* taps per row of the horizontal (W rows) and vertical (H rows) tables */
+    int32_t hcoef_off, vcoef_off; /* int32 offsets of the two tables in coef */
+    int32_t lut_off;            /* byte offset of the [3][256] LUTs in lut */
+} mcamd_augment_desc;
+typedef struct mcamd_augment_batch {
+    const mcamd_augment_desc* desc;      /* HOST array of B descriptors: validated */
+    const mcamd_augment_desc* desc_dev;  /* the same B descriptors in device memory: what the kernels read */
+    const uint8_t* src; int64_t src_bytes;
+    const int32_t* coef; int64_t coef_elems;
+    const uint8_t* lut; int64_t lut_bytes;
+    uint8_t* tmp; int64_t tmp_bytes;
+    float* out;
+    int32_t B, H, W;
+} mcamd_augment_batch;
+int mcamd_augment(const mcamd_augment_batch* a, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Launch plans: a whole forward or backward pass as ONE library call.
  * The reference executes Darknet.forward as one Python call per torch module (src/nets.py:720-774) and autograd
  * replays them; here the caller walks its layer list ONCE between mcamd_plan_begin and mcamd_plan_end: every

@@ -97,6 +97,25 @@ class FoldJob(C.Structure):
     _fields_ = [("d", FoldDesc), ("waug", C.c_void_p), ("first_block", C.c_int64)]
 
 
+class AugmentDesc(C.Structure):
+    """mcamd_augment_desc (include/mcamd.h)."""
+    _fields_ = [("src_off", C.c_int64), ("tmp_off", C.c_int64),
+                ("src_w", C.c_int32), ("src_h", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32),
+                ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("flip", C.c_int32),
+                ("hk", C.c_int32), ("vk", C.c_int32), ("hcoef_off", C.c_int32), ("vcoef_off", C.c_int32),
+                ("lut_off", C.c_int32)]
+
+
+class AugmentBatch(C.Structure):
+    """mcamd_augment_batch (include/mcamd.h)."""
+    _fields_ = [("desc", C.c_void_p), ("desc_dev", C.c_void_p),
+                ("src", C.c_void_p), ("src_bytes", C.c_int64),
+                ("coef", C.c_void_p), ("coef_elems", C.c_int64),
+                ("lut", C.c_void_p), ("lut_bytes", C.c_int64),
+                ("tmp", C.c_void_p), ("tmp_bytes", C.c_int64),
+                ("out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
 EPI_RAW_F16, EPI_NCHW_F32, EPI_PAD_F16, EPI_RAW_F32 = 0, 1, 2, 3
 DST_PLAIN, DST_POOL, DST_REORG = 0, 1, 2
 
@@ -141,6 +160,7 @@ SIGNATURES = {
     "mcamd_stem_conv_f32": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _P, _I32, _I32, _P]),
     "mcamd_region_loss_workspace_bytes": (_SZ, [_I32]),
     "mcamd_region_loss": (C.c_int, [C.POINTER(RegionDesc), _P, _P, _P, _P, _SZ, _P]),
+    "mcamd_augment": (C.c_int, [C.POINTER(AugmentBatch), _P]),
     "mcamd_plan_begin": (C.c_int, [C.POINTER(_P), _I32]),
     "mcamd_plan_mark": (_I32, []),
     "mcamd_plan_end": (_P, []),

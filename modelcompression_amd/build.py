@@ -34,6 +34,7 @@ SOURCES = {
     "plan.hip": [],
     "region_loss.hip": [],
     "prune.hip": ["-ffp-contract=off"],   # pinned fp32 arithmetic: no FMA contraction
+    "augment.hip": ["-ffp-contract=off"], # Pillow's float / double HSV arithmetic, operation by operation
 }
 
 

@@ -12,7 +12,10 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     raises instead);
   * when the image list is missing, a seeded synthetic detection set of the same shapes is
     used so the entry point can be exercised without VOC on disk;
-  * MAX_EPOCHS can be given to stop early (the reference hard-codes 135).
+  * MAX_EPOCHS can be given to stop early (the reference hard-codes 135);
+  * AUGMENT=True trains on the reference's train=True augmentation (dataloader.py:68-75): data.VOCAugment (or
+    data.SyntheticAugment without a list) decodes and draws parameters, augment.DeviceAugmenter does the pixels in
+    one HIP launch pair per batch on the training stream.  Off by default.
 """
 import os
 
@@ -25,7 +28,8 @@ import torch.distributed as dist  # noqa: E402
 import torch.optim as optim  # noqa: E402
 
 from . import dp  # noqa: E402
-from .data import VOCList, SyntheticDetection  # noqa: E402
+from .augment import DeviceAugmenter, collate_fn  # noqa: E402
+from .data import VOCList, SyntheticDetection, VOCAugment, SyntheticAugment  # noqa: E402
 from .nets import Darknet, parse_cfg  # noqa: E402
 from .pruning.weightPruning.methods import quick_filter_prune, weight_prune  # noqa: E402
 from .pruning.weightPruning.utils import prune_rate, are_masks_consistent  # noqa: E402
@@ -181,7 +185,7 @@ class YOLOv2Train():
               MODEL_CFG, MODEL_WEIGHT,
               BATCH_SIZE, SAVE_INTERNAL,
               LOGGER='', DEBUG_EPOCHS=-1, verbose=0, pruning_perc=0., pruning_method="weight",
-              MAX_EPOCHS=135, SYNTHETIC_SAMPLES=256, EVAL=False):
+              MAX_EPOCHS=135, SYNTHETIC_SAMPLES=256, EVAL=False, AUGMENT=False):
         rank, world = dp.init_from_env()
         local = int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(local)
@@ -202,12 +206,13 @@ class YOLOv2Train():
         # Step 2 - dataset
         self.trainlist, self.testlist = PASCAL_TRAIN, PASCAL_VALID
         self.init_width, self.init_height = self.model.width, self.model.height
+        shape = (self.init_width, self.init_height)
         if PASCAL_TRAIN and os.path.exists(PASCAL_TRAIN):
             nsamples = file_lines(self.trainlist)
-            dataset = VOCList(self.trainlist, shape=(self.init_width, self.init_height), train=True)
+            dataset = VOCAugment(self.trainlist, shape=shape) if AUGMENT else VOCList(self.trainlist, shape=shape, train=True)
         else:
             nsamples = SYNTHETIC_SAMPLES
-            dataset = SyntheticDetection(nsamples, shape=(self.init_width, self.init_height))
+            dataset = SyntheticAugment(nsamples, shape=shape) if AUGMENT else SyntheticDetection(nsamples, shape=shape)
             logging('train list %r not found: synthetic detection set of %d samples' % (PASCAL_TRAIN, nsamples))
         if TRAIN_LOGDIR and rank == 0 and not os.path.exists(TRAIN_LOGDIR):
             os.makedirs(TRAIN_LOGDIR, exist_ok=True)
@@ -243,23 +248,28 @@ class YOLOv2Train():
 
         per_rank = max(1, self.batch_size // world)
         sampler = torch.utils.data.distributed.DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 else None
+        augmenter = DeviceAugmenter(shape, dev) if AUGMENT else None
         loader = torch.utils.data.DataLoader(dataset, batch_size=per_rank, shuffle=(sampler is None), sampler=sampler,
-                                             num_workers=4 if isinstance(dataset, VOCList) else 0, pin_memory=True,
-                                             drop_last=True)
+                                             num_workers=4 if isinstance(dataset, (VOCList, VOCAugment, SyntheticAugment)) else 0,
+                                             pin_memory=True, drop_last=True,
+                                             collate_fn=collate_fn(shape) if AUGMENT else None)
         guard = StepGuard(self.model, optimizer, dev, log=logging if rank == 0 else None)
         epoch = init_epoch
         for epoch in range(init_epoch, min(MAX_EPOCHS, 135)):
             if sampler is not None:
                 sampler.set_epoch(epoch)
+            if AUGMENT:
+                dataset.set_epoch(epoch)       # before the loader's workers take their copy of the dataset
             if rank == 0:
                 print(' ---------------------------- EPOCH : ', epoch, ' (LR : ', LR, ') ---------------------------------- ')
             self.model.train()
             # the loss is accumulated on the device and read once per epoch; the skip policy lives in StepGuard
             train_loss_total, t0, steps_here = torch.zeros((), dtype=torch.float32, device=dev), time.time(), 0
             skipped_before = guard.skipped
-            for batch_idx, (data, target) in enumerate(loader):
+            for batch_idx, batch in enumerate(loader):
                 if DEBUG_EPOCHS > -1 and batch_idx > DEBUG_EPOCHS:
                     break
+                data, target = augmenter(batch) if AUGMENT else batch
                 data = data.to(dev, non_blocking=True)
                 target = target.float().to(dev, non_blocking=True)
                 output = self.model(data)
