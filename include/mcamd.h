@@ -331,16 +331,20 @@ typedef struct mcamd_act_bwd_desc {
     const void* act;           /* optional, PLAIN blocks without g2: the activation the forward pass stored for the consumer
                                   (fp16, padded NHWC / shared-halo form per act_pad, the hi plane of split storage) at channels
                                   [act_choff, act_choff + C) of rows of act_ld.  LeakyReLU is invertible: z = act > 0 ? act :
-                                  act / slope, xhat = (z - beta) / gamma -- so `y` (fp32, y_dtype 1, or NULL) is read only by
-                                  the threads that hold a channel with gamma == 0, where xhat cannot be recovered (NULL: the
-                                  dgamma of such a channel is written as 0).  With an fp32 `y` (split-operand precisions) the
+                                  act / slope, xhat = (z - beta) / gamma.  The fp16 rounding of act puts up to 2^-11 (|xhat| +
+                                  |beta / gamma|) into that xhat, so an ILL-CONDITIONED channel, |gamma| < 2^-5 max(|beta|, 1)
+                                  (gamma == 0 included; BN_ACT_T in csrc/bn_act.hip), takes xhat = (y - mean) invstd from `y`
+                                  (fp32, y_dtype 1) in both passes; `y` is read only by the threads that hold such a channel.
+                                  `y` NULL: those channels use the activation like all others (gamma == 0: dgamma written as
+                                  0; |gamma| small: xhat as recovered).  With an fp32 `y` (split-operand precisions) the
                                   two passes read half the bytes; the result carries the fp16 rounding of the stored
                                   activation, as every backward tensor does (nn.BatchNorm2d + nn.LeakyReLU backward,
                                   reference src/nets.py:802-809 under autograd).
                                   Mode MCAMD_DST_POOL (with or without g2): `act` is the FULL-RESOLUTION fp16 copy of the block's
                                   activation the forward pass wrote as mcamd_act_desc.pool_act (H x W, act_choff 0); the
                                   window's argmax is the maximum of the four stored values (strict by construction there)
-                                  and every element's LeakyReLU side is the sign of its stored value (nn.MaxPool2d(2, 2)
+                                  and every element's LeakyReLU side is the sign of its stored value (ill-conditioned channels
+                                  as above: xhat from `y`, argmax and side from the copy) (nn.MaxPool2d(2, 2)
                                   backward, reference src/nets.py:821). */
     int32_t act_ld, act_choff, act_pad;
 } mcamd_act_bwd_desc;

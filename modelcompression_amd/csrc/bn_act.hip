@@ -561,31 +561,54 @@ __global__ __launch_bounds__(256) void bn_plain_bwd_kernel(ActBwdArgs a) {
     }
 }
 
+// Backward passes from the stored activation (bn_plain_bwd_act_kernel, bn_pool_bwd_act_kernel): a channel is
+// ILL-CONDITIONED when |gamma| < BN_ACT_T max(|beta|, 1).  Recovering xhat = (z - beta) / gamma from an fp16 activation
+// costs up to 2^-11 (|xhat| + |beta / gamma|); on the other channels that is at most 2^-11 (1 / BN_ACT_T + |xhat|).  With
+// |gamma| = |scale| / invstd the test is |scale| < BN_ACT_T max(|beta|, 1) invstd (gamma == 0 always included).
+constexpr float BN_ACT_T = 0.03125f;     // 2^-5
+
+// Per channel, xhat = (u - off) mul with u = z from the activation (off = beta, mul = 1 / gamma), or with u = the saved
+// fp32 y (off = mean, mul = invstd) where the channel is ill-conditioned and `have_y`.  Returns whether any channel of the
+// thread reads y.
+__device__ __forceinline__ bool act_xhat_source(const float (&sc)[8], const float (&sh)[8], const float (&mu)[8],
+                                                const float (&is)[8], bool have_y, float (&off)[8], float (&mul)[8],
+                                                bool (&usey)[8]) {
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float beta = sh[i] + mu[i] * sc[i];                                       // shift = beta - mean scale
+        usey[i] = have_y && fabsf(sc[i]) < BN_ACT_T * fmaxf(fabsf(beta), 1.f) * is[i];  // scale = gamma invstd
+        off[i] = usey[i] ? mu[i] : beta;
+        mul[i] = usey[i] ? is[i] : (sc[i] != 0.f ? is[i] / sc[i] : 0.f);
+        any |= usey[i];
+    }
+    return any;
+}
+
 // The same two passes WITHOUT the saved raw output: LeakyReLU is invertible, so a PLAIN block's pre-activation is
 // recovered from the activation the forward pass stored for the consumer (fp16, the hi plane of split storage):
 // z = a > 0 ? a : a / slope, xhat = (z - beta) / gamma.  With the split-operand precisions the saved y is fp32: the two
 // passes read 2 instead of 4 bytes per element for it (0.89 -> 0.65 ms per "mixed" B=64 step), at the operand precision
 // every backward pass has anyway (G and dY are fp16).  With dm = gamma invstd (0 for a pruned filter):
 //     out = dm g_z - (P z + Q),   P = dm c2 / gamma,  Q = dm c1 - P beta     (per channel, hoisted)
-// A channel with gamma == 0 has no xhat to recover (its dY is 0 either way, dm = 0): the threads that hold such a channel
-// read the saved fp32 y for their dgamma sums in pass 0, as the y kernel does -- a branch nobody takes on a trained network.
+// The stored activation carries an fp16 rounding of up to 2^-11 |z|, so xhat = (z - beta) / gamma is off by up to
+// 2^-11 (|xhat| + |beta / gamma|): useless where |gamma| << |beta| (at gamma = 1e-4, beta = 1 every z rounds to beta).
+// Channels with |gamma| < BN_ACT_T max(|beta|, 1) (act_xhat_source, gamma = 0 included) take xhat = (y - mu) invstd from the
+// saved fp32 y in BOTH passes instead, with the y kernels' P = dm c2 invstd, Q = dm c1 - P mu; the LeakyReLU side stays
+// the sign of the stored activation.  Only the threads that hold such a channel read y: a healthy network's backward
+// pass reads what it read without the rule.  y = NULL: those channels use the activation as every other channel does
+// (gamma == 0: xhat 0, so dgamma 0; dY is 0 there either way, dm = 0).
 template <int PHASE>
 __global__ __launch_bounds__(256) void bn_plain_bwd_act_kernel(ActBwdArgs a) {
     const int CH = a.C >> 3, lg = __ffs(CH) - 1;        // C / 8 is a power of two (check_c)
     const int c8 = (threadIdx.x & (CH - 1)) * 8;
-    float sc[8], sh[8], mu[8], is[8], beta[8], rg[8], P[8], Q[8], dm[8];
+    float sc[8], sh[8], mu[8], is[8], off[8], mul[8], P[8], Q[8], dm[8];
+    bool usey[8];
     loadf8(a.scale + c8, sc);
     loadf8(a.shift + c8, sh);
     loadf8(a.mean + c8, mu);
     loadf8(a.invstd + c8, is);
-    bool need_y = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        beta[i] = sh[i] + mu[i] * sc[i];                 // shift = beta - mean scale
-        rg[i] = sc[i] != 0.f ? is[i] / sc[i] : 0.f;      // 1 / gamma (scale = gamma invstd)
-        need_y |= sc[i] == 0.f;
-    }
-    need_y = need_y && PHASE == 0 && a.y != nullptr;
+    const bool need_y = act_xhat_source(sc, sh, mu, is, a.y != nullptr, off, mul, usey);
     if (PHASE == 1) {
         float c1[8], c2[8];
         loadf8(a.coef + c8, c1);
@@ -601,8 +624,8 @@ __global__ __launch_bounds__(256) void bn_plain_bwd_act_kernel(ActBwdArgs a) {
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            P[i] = dm[i] * c2[i] * rg[i];
-            Q[i] = dm[i] * c1[i] - P[i] * beta[i];
+            P[i] = dm[i] * c2[i] * mul[i];
+            Q[i] = dm[i] * c1[i] - P[i] * off[i];
         }
     }
     float sb[8], sg[8];
@@ -622,20 +645,23 @@ __global__ __launch_bounds__(256) void bn_plain_bwd_act_kernel(ActBwdArgs a) {
         float av[8], gv[8];
         load8(a.act + pad_off(b, h, w, a.H, a.W, a.act_ld, a.act_pw) + a.act_choff + c8, av);
         load8(a.g + (long long)pix * a.g_ld + a.g_choff + c8, gv);
-        float out[8], yv[8];
-        if (need_y) load_y<true>(a.y, (long long)pix * a.y_ld + a.y_choff + c8, yv);
+        float out[8], z[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) z[i] = av[i] > 0.f ? av[i] : av[i] * inv_slope;
+        if (need_y) {                                    // ill-conditioned channels: the saved y in place of z
+            float yv[8];
+            load_y<true>(a.y, (long long)pix * a.y_ld + a.y_choff + c8, yv);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) z[i] = usey[i] ? yv[i] : z[i];
+        }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const bool pos = av[i] > 0.f;
-            const float z = pos ? av[i] : av[i] * inv_slope;
-            const float gz = pos ? gv[i] : gv[i] * a.slope;
+            const float gz = av[i] > 0.f ? gv[i] : gv[i] * a.slope;
             if (PHASE == 0) {
                 sb[i] += gz;
-                float xh = (z - beta[i]) * rg[i];
-                if (need_y && sc[i] == 0.f) xh = (yv[i] - mu[i]) * is[i];
-                sg[i] += gz * xh;
+                sg[i] += gz * ((z[i] - off[i]) * mul[i]);
             } else {
-                const float o = dm[i] * gz - (P[i] * z + Q[i]);
+                const float o = dm[i] * gz - (P[i] * z[i] + Q[i]);
                 out[i] = o;
                 satmax = fmaxf(satmax, fabsf(o));
             }
@@ -814,25 +840,20 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_kernel(ActBwdArgs a) {
 // the element it pooled (first maximum of the unrounded activations) is their strict maximum -- and the LeakyReLU side of
 // every element is the sign of its stored value (rounding keeps the sign).  Split-operand engines save y as fp32: the two passes read 2 instead of 4 bytes per
 // element (conv2 / 5 / 8 / 13 at B = 64: 0.66 GB less per step) for 2 bytes more written by the forward pass where the copy
-// did not exist.  out_k = [k == arg] dm g_z - (P z_k + Q) with P, Q of bn_plain_bwd_act_kernel; gamma == 0 channels read the
-// saved y for their dgamma sums (pass 0 only), as there.
+// did not exist.  out_k = [k == arg] dm g_z - (P z_k + Q) with P, Q of bn_plain_bwd_act_kernel; ill-conditioned channels
+// (act_xhat_source) take z_k from the saved fp32 y in both passes, as there, while the argmax and the LeakyReLU sides still come
+// from the stored activation.
 template <int PHASE, bool G2>
 __global__ __launch_bounds__(256) void bn_pool_bwd_act_kernel(ActBwdArgs a) {
     const int CH = a.C >> 3, lg = __ffs(CH) - 1;        // C / 8 is a power of two (check_c)
     const int c8 = (threadIdx.x & (CH - 1)) * 8;
-    float sc[8], sh[8], mu[8], is[8], beta[8], rg[8], P[8], Q[8], dm[8];
+    float sc[8], sh[8], mu[8], is[8], off[8], mul[8], P[8], Q[8], dm[8];
+    bool usey[8];
     loadf8(a.scale + c8, sc);
     loadf8(a.shift + c8, sh);
     loadf8(a.mean + c8, mu);
     loadf8(a.invstd + c8, is);
-    bool need_y = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        beta[i] = sh[i] + mu[i] * sc[i];                 // shift = beta - mean scale
-        rg[i] = sc[i] != 0.f ? is[i] / sc[i] : 0.f;      // 1 / gamma (scale = gamma invstd)
-        need_y |= sc[i] == 0.f;
-    }
-    need_y = need_y && PHASE == 0 && a.y != nullptr;
+    const bool need_y = act_xhat_source(sc, sh, mu, is, a.y != nullptr, off, mul, usey);
     if (PHASE == 1) {
         float c1[8], c2[8];
         loadf8(a.coef + c8, c1);
@@ -848,8 +869,8 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_act_kernel(ActBwdArgs a) {
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            P[i] = dm[i] * c2[i] * rg[i];
-            Q[i] = dm[i] * c1[i] - P[i] * beta[i];
+            P[i] = dm[i] * c2[i] * mul[i];
+            Q[i] = dm[i] * c1[i] - P[i] * off[i];
         }
     }
     float sb[8], sg[8];
@@ -884,21 +905,27 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_act_kernel(ActBwdArgs a) {
             load8(q0 + g2row, g2v[G2 ? 2 : 0]);
             load8(q0 + g2row + a.g2_ld, g2v[G2 ? 3 : 0]);
         }
-        float yv[4][8];
-        if (need_y) {
+        float z[4][8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) z[k][i] = av[k][i] > 0.f ? av[k][i] : av[k][i] * inv_slope;
+        if (need_y) {                                    // ill-conditioned channels: the saved y in place of z
             const float* yf = (const float*)a.y;
             const long long y0 = (((long long)b * a.H + 2 * ho) * a.W + 2 * wo) * a.y_ld + a.y_choff + c8;
+            float yv[4][8];
             loadf8(yf + y0, yv[0]);
             loadf8(yf + y0 + a.y_ld, yv[1]);
             loadf8(yf + y0 + yrow, yv[2]);
             loadf8(yf + y0 + yrow + a.y_ld, yv[3]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) z[k][i] = usey[i] ? yv[k][i] : z[k][i];
         }
         float out[4][8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            float z[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) z[k] = av[k][i] > 0.f ? av[k][i] : av[k][i] * inv_slope;
             // first maximum in (h, w) scan order of the activations as the forward pass stored them
             int arg = 0;
             float best = av[0][i];
@@ -914,11 +941,9 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_act_kernel(ActBwdArgs a) {
                     const float gzk = av[k][i] > 0.f ? ga : ga * a.slope;
                     if (PHASE == 0) {
                         sb[i] += gzk;
-                        float xh = (z[k] - beta[i]) * rg[i];
-                        if (need_y && sc[i] == 0.f) xh = (yv[k][i] - mu[i]) * is[i];
-                        sg[i] += gzk * xh;
+                        sg[i] += gzk * ((z[k][i] - off[i]) * mul[i]);
                     } else {
-                        const float o = dm[i] * gzk - (P[i] * z[k] + Q[i]);
+                        const float o = dm[i] * gzk - (P[i] * z[k][i] + Q[i]);
                         out[k][i] = o;
                         satmax = fmaxf(satmax, fabsf(o));
                     }
@@ -926,18 +951,16 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_act_kernel(ActBwdArgs a) {
             } else {
                 const float gz = best > 0.f ? gv[i] : gv[i] * a.slope;
                 if (PHASE == 0) {
-                    float zs = z[0], ys = need_y ? yv[0][i] : 0.f;
+                    float zs = z[0][i];
 #pragma unroll
-                    for (int k = 1; k < 4; ++k) zs = k == arg ? z[k] : zs, ys = (need_y && k == arg) ? yv[k][i] : ys;
+                    for (int k = 1; k < 4; ++k) zs = k == arg ? z[k][i] : zs;
                     sb[i] += gz;
-                    float xh = (zs - beta[i]) * rg[i];
-                    if (need_y && sc[i] == 0.f) xh = (ys - mu[i]) * is[i];
-                    sg[i] += gz * xh;
+                    sg[i] += gz * ((zs - off[i]) * mul[i]);
                 } else {
                     const float t = dm[i] * gz;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const float o = (k == arg ? t : 0.f) - (P[i] * z[k] + Q[i]);
+                        const float o = (k == arg ? t : 0.f) - (P[i] * z[k][i] + Q[i]);
                         out[k][i] = o;
                         satmax = fmaxf(satmax, fabsf(o));
                     }
@@ -1218,8 +1241,8 @@ extern "C" int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, si
                           (d->act_pad == 0 || d->act_pad == 1),
                       "bn_act_bwd: activation slice [%d, %d) does not fit act_ld %d", d->act_choff, d->act_choff + d->C, d->act_ld);
         MCAMD_REQUIRE(d->slope > 0.f, "bn_act_bwd: `act` needs an invertible activation (slope > 0)");
-        MCAMD_REQUIRE(!d->y || d->y_dtype == 1, "bn_act_bwd: with `act`, `y` is NULL or the fp32 raw output (read for channels "
-                                                "whose gamma is 0 only)");
+        MCAMD_REQUIRE(!d->y || d->y_dtype == 1, "bn_act_bwd: with `act`, `y` is NULL or the fp32 raw output (read for the "
+                                                "channels with |gamma| < %g max(|beta|, 1) only)", (double)BN_ACT_T);
     }
     long long pixels = (long long)d->B * d->H * d->W;
     double count = (double)pixels;
