@@ -209,6 +209,29 @@ int mcamd_pack_weights_many(const mcamd_pack_job* jobs_dev, int32_t njobs, int64
 int mcamd_conv_fwd(const mcamd_conv_geom* g, const void* x, const void* wp_fwd,
                    const mcamd_conv_epilogue* epi, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * 2:4 structured sparsity (an addition beyond the reference): inference forward on v_smfmac_f32_32x32x32_f16 for
+ * layers whose mask keeps at most 2 of every 4 consecutive input channels at each (filter, tap) -- nm_prune.
+ * ------------------------------------------------------------------------- */
+/* 1: mcamd_conv_fwd_sparse24 / mcamd_pack_sparse24 accept this geometry (stem == 0, ksize 1 or 3, cin % 4 == 0,
+ * cout % 8 == 0, x_wrap == 0, x_f8 == 0, the input slice of round_up(cin, 32) channels inside x_ld). */
+int32_t mcamd_conv_fwd_sparse24_ok(const mcamd_conv_geom* g);
+/* Sizes of the packed 2:4 operands: out[0] = fp16 kept values, out[1] = 16-bit index words. */
+int mcamd_sparse24_elems(const mcamd_conv_geom* g, int64_t out[2]);
+/* OIHW fp32 master (* mask, may be NULL) -> the 2:4 packing the sparse forward stages:
+ *   wsp: fp16 [Npad][ktot / 2], Npad = round_up(cout, 256), ktot = k*k * round_up(cin, 32): the dense forward row
+ *        (K order of mcamd_pack_weights) with each group of 4 consecutive k reduced to its 2 kept values, in k order;
+ *   idx: uint16 [ktot / 32][Npad][2]: word h of K32 chunk q of row n holds, for the 8 kept values of k [32 q + 16 h, +16),
+ *        the offset of kept value j inside its group of 4 at bits [2 j, 2 j + 2).
+ * The kept entries of a group are its non-zeros of w * mask (the first two when the mask does not conform); a group with
+ * fewer gets distinct indices with zero values.  Every row up to Npad is written. */
+int mcamd_pack_sparse24(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wsp, void* idx, void* stream);
+/* y = leaky(conv(x, w) * scale + shift) from the 2:4 packing: epilogue mode MCAMD_EPI_PAD_F16 only (with dst_mode PLAIN /
+ * POOL / REORG and y2 exactly as mcamd_conv_fwd), for geometries mcamd_conv_fwd_sparse24_ok() accepts, both `pad` forms of
+ * x.  The result equals mcamd_conv_fwd's on the same masked weights up to fp32 summation order. */
+int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, const void* wsp, const void* idx,
+                            const mcamd_conv_epilogue* epi, void* stream);
+
 /* dx = conv_transpose(dy, w) -- autograd's input gradient of the same call.
  * `dy` is padded NHWC fp16 [B][H+2][W+2][dy_ld] (zero halo); g->cin/cout keep their forward
  * meaning; the result has g->cin channels.  epi->mode 0 (fp16 [M][y_ld]) or 1 (fp32 NCHW). */
@@ -622,6 +645,15 @@ int mcamd_filter_mask(const int32_t* keep, int32_t cout, int64_t per_filter, flo
 int mcamd_count_zeros(const float* w, int64_t n, unsigned long long* out, void* stream);
 /* sum(p * |m - 1|) accumulated in fp32 into *out -- are_masks_consistent, utils.py:122-133. */
 int mcamd_masked_residual(const float* w, const float* mask, int64_t n, float* out, void* stream);
+
+/* N:M magnitude mask (nm_prune, an addition beyond the reference) of an OIHW tensor [cout][cin][khw], cin % 4 == 0:
+ * in every group of 4 consecutive input channels at a fixed (filter, tap) the 2 entries with the largest
+ * |w * old_mask| keep their old mask value (1 when old_mask is NULL), the others get 0; ties keep the lower channel.
+ * n = 2, m = 4 only. */
+int mcamd_nm_mask(const float* w, const float* old_mask, int32_t cout, int32_t cin, int32_t khw, int32_t n, int32_t m,
+                  float* mask, void* stream);
+/* number of such groups holding more than 2 non-zero mask entries, added to *count (device int32) */
+int mcamd_nm_violations(const float* mask, int32_t cout, int32_t cin, int32_t khw, int32_t* count, void* stream);
 
 #ifdef __cplusplus
 }

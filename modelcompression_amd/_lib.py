@@ -135,6 +135,10 @@ SIGNATURES = {
     "mcamd_pack_weights": (C.c_int, [C.POINTER(ConvGeom), _P, _P, C.POINTER(ChanMap), _P, _P, _P]),
     "mcamd_pack_weights_many": (C.c_int, [_P, _I32, _I64, _P]),
     "mcamd_conv_fwd": (C.c_int, [C.POINTER(ConvGeom), _P, _P, C.POINTER(ConvEpilogue), _P]),
+    "mcamd_conv_fwd_sparse24_ok": (_I32, [C.POINTER(ConvGeom)]),
+    "mcamd_sparse24_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
+    "mcamd_pack_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
+    "mcamd_conv_fwd_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_dgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _I32, _I32, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_wgrad_workspace_bytes": (_SZ, [C.POINTER(ConvGeom)]),
     "mcamd_conv_wgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _I32, _I32, _P, C.POINTER(ChanMap), _F, _P, _P, _P, _SZ, _P]),
@@ -180,6 +184,8 @@ SIGNATURES = {
     "mcamd_filter_mask": (C.c_int, [_P, _I32, _I64, _P, _P]),
     "mcamd_count_zeros": (C.c_int, [_P, _I64, _P, _P]),
     "mcamd_masked_residual": (C.c_int, [_P, _P, _I64, _P, _P]),
+    "mcamd_nm_mask": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "mcamd_nm_violations": (C.c_int, [_P, _I32, _I32, _I32, _P, _P]),
 }
 
 _lib = None

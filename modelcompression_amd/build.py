@@ -21,6 +21,7 @@ SOURCES = {
     "api.hip": [],
     "conv_igemm.hip": [],
     "conv_igemm_pp.hip": [],
+    "conv_sparse.hip": [],
     "conv_stem.hip": [],
     "conv_stem_block.hip": [],
     "conv_stem_f32.hip": [],

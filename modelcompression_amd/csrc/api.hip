@@ -572,6 +572,75 @@ extern "C" int mcamd_conv_fwd(const mcamd_conv_geom* g, const void* x, const voi
     return mcamd_igemm_launch(a, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------
+// 2:4 structured sparsity (conv_sparse.hip; an addition beyond the reference)
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_sparse24_ok(const mcamd_conv_geom* g) {
+    if (!g || g->stem || g->x_wrap != 0 || g->x_f8 != 0 || (g->ksize != 1 && g->ksize != 3)) return 0;
+    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->cin <= 0 || g->cout <= 0) return 0;
+    if (g->cin % 4 != 0 || g->cout % 8 != 0 || (long long)g->B * g->H * g->W >= (1ll << 31)) return 0;
+    if (g->pad != 0 && g->pad != 1) return 0;
+    if (g->x_ld % 8 != 0 || g->x_choff % 8 != 0 || g->x_choff + cin_tap_of(g) > g->x_ld) return 0;
+    return 1;
+}
+
+extern "C" int mcamd_sparse24_elems(const mcamd_conv_geom* g, int64_t out[2]) {
+    MCAMD_REQUIRE(g && out, "sparse24_elems: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_sparse24_ok(g), "sparse24_elems: geometry has no 2:4 form (mcamd_conv_fwd_sparse24_ok)");
+    const long long npad = round_up_int(g->cout, 256), ktot = (long long)ntaps_of(g) * cin_tap_of(g);
+    out[0] = npad * ktot / 2;      // kept fp16 values
+    out[1] = npad * ktot / 16;     // 16-bit index words
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_pack_sparse24(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wsp, void* idx,
+                                   void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "pack_sparse24: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_pack_sparse24(&g_, w_oihw, mask_oihw, wsp, idx, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_sparse24_ok(g), "pack_sparse24: geometry has no 2:4 form (mcamd_conv_fwd_sparse24_ok)");
+    MCAMD_REQUIRE(w_oihw && wsp && idx, "pack_sparse24: null pointer");
+    const int ct = cin_tap_of(g);
+    return mcamd_pack_sparse24_launch(w_oihw, mask_oihw, wsp, idx, g->cout, g->cin, ntaps_of(g), ct, kblock_of(ct),
+                                      (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, const void* wsp, const void* idx,
+                                       const mcamd_conv_epilogue* epi, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_sparse24: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_sparse24(&g_, x, wsp, idx, &e_, s); });
+    }
+    if (check_geom(g, "conv_fwd_sparse24")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_sparse24_ok(g), "conv_fwd_sparse24: geometry has no 2:4 form (mcamd_conv_fwd_sparse24_ok)");
+    MCAMD_REQUIRE(x && wsp && idx, "conv_fwd_sparse24: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_sparse24: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const half_t*)x;
+    a.w = (const half_t*)wsp;
+    a.x_ld = g->x_ld;
+    a.x_row_stride = (g->W + pw_of(g)) * g->x_ld;
+    a.x_img_stride = (long long)(g->H + pw_of(g)) * a.x_row_stride;
+    a.x_off = g->x_choff;
+    a.H = g->H, a.W = g->W, a.HW = g->H * g->W;
+    a.M = g->B * g->H * g->W;
+    a.N = g->cout;
+    a.cin_tap = cin_tap_of(g);
+    a.ntaps = ntaps_of(g);
+    a.kb = kblock_of(a.cin_tap);
+    a.ktot = a.ntaps * a.cin_tap;
+    a.wrap = 0x7fffffff;
+    a.f8_from = 0x7fffffff;
+    fill_taps(g->ksize, 0, a.x_row_stride, g->x_ld, a.tap_off);
+    if (fill_epilogue(a, epi, g->cout, a.M, a.cin_tap, a.ktot, "conv_fwd_sparse24")) return MCAMD_EINVAL;
+    return mcamd_sparse24_launch(a, idx, (hipStream_t)stream);
+}
+
 extern "C" int mcamd_conv_dgrad(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff,
                                 const void* wp_dgrad, const mcamd_conv_epilogue* epi, void* stream) {
     if (mcamd_recording()) {

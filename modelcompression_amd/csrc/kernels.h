@@ -80,6 +80,9 @@ int mcamd_igemm_pp_launch(const IgemmArgs& a, int bm, int bn, int rows, int ntil
 bool mcamd_igemm_f8_ok(long long M, int n, int cin_tap, int ktot);   // the fp8-correction form exists for the tile this shape takes
 int mcamd_igemm_rows(long long M, int n, int cin_tap, int ktot, bool raw_epilogue = true, bool concurrent = false);
 int mcamd_igemm_launch(IgemmArgs& a, hipStream_t st);
+int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);   // conv_sparse.hip: 2:4 weights, mode 2 epilogue
+int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
+                               int cin_tap, int kb, hipStream_t st);
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps);
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);

@@ -480,3 +480,75 @@ extern "C" int mcamd_masked_residual(const float* w, const float* mask, int64_t 
     MCAMD_LAUNCH_CHECK("masked_residual");
     return MCAMD_OK;
 }
+
+// ------------------------------------------------------------------------------------
+// N:M magnitude mask (nm_prune; an addition beyond the reference) and its conformance count
+// ------------------------------------------------------------------------------------
+// One thread per group of 4 consecutive input channels at a fixed (filter, tap) of an OIHW tensor: the 2 entries with the
+// largest |w * old_mask| keep their old mask value, the others get 0.  Rank of entry i = #{j: a_j > a_i} + #{j < i: a_j == a_i}:
+// the position of i in a stable argsort of -a, so ties keep the lower channel.
+__global__ __launch_bounds__(256) void nm_mask_kernel(const float* w, const float* old_mask, int cout, int cin, int khw,
+                                                      float* mask) {
+    const long long groups = (long long)cout * (cin / 4) * khw;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < groups; t += (long long)gridDim.x * 256) {
+        const int tap = (int)(t % khw);
+        const long long og = t / khw;
+        const int g = (int)(og % (cin / 4));
+        const long long o = og / (cin / 4);
+        const long long base = (o * cin + 4 * g) * khw + tap;
+        float a[4], m[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            m[e] = old_mask ? old_mask[base + e * khw] : 1.f;
+            a[e] = fabsf(w[base + e * khw] * m[e]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int rank = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rank += (a[j] > a[i]) || (j < i && a[j] == a[i]);
+            mask[base + i * khw] = rank < 2 ? m[i] : 0.f;
+        }
+    }
+}
+
+extern "C" int mcamd_nm_mask(const float* w, const float* old_mask, int32_t cout, int32_t cin, int32_t khw, int32_t n, int32_t m,
+                             float* mask, void* stream) {
+    MCAMD_REQUIRE(n == 2 && m == 4, "nm_mask: only the 2:4 pattern is supported (got %d:%d)", n, m);
+    MCAMD_REQUIRE(w && mask && cout > 0 && cin > 0 && khw > 0 && cin % 4 == 0, "nm_mask: bad argument (cin %d must be a multiple of 4)",
+                  cin);
+    const long long groups = (long long)cout * (cin / 4) * khw;
+    long long g = (groups + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(nm_mask_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, w, old_mask, cout, cin, khw, mask);
+    MCAMD_LAUNCH_CHECK("nm_mask");
+    return MCAMD_OK;
+}
+
+// groups of 4 consecutive input channels at a fixed (filter, tap) holding more than 2 non-zero mask entries, added to *count
+__global__ __launch_bounds__(256) void nm_violations_kernel(const float* mask, int cout, int cin, int khw, int* count) {
+    const long long groups = (long long)cout * (cin / 4) * khw;
+    int bad = 0;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < groups; t += (long long)gridDim.x * 256) {
+        const int tap = (int)(t % khw);
+        const long long og = t / khw;
+        const int g = (int)(og % (cin / 4));
+        const long long o = og / (cin / 4);
+        const long long base = (o * cin + 4 * g) * khw + tap;
+        int nz = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) nz += mask[base + e * khw] != 0.f;
+        bad += nz > 2;
+    }
+    if (bad) atomicAdd(count, bad);
+}
+
+extern "C" int mcamd_nm_violations(const float* mask, int32_t cout, int32_t cin, int32_t khw, int32_t* count, void* stream) {
+    MCAMD_REQUIRE(mask && count && cout > 0 && cin > 0 && khw > 0 && cin % 4 == 0, "nm_violations: bad argument");
+    const long long groups = (long long)cout * (cin / 4) * khw;
+    long long g = (groups + 255) / 256;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(nm_violations_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, mask, cout, cin, khw, count);
+    MCAMD_LAUNCH_CHECK("nm_violations");
+    return MCAMD_OK;
+}

@@ -166,6 +166,10 @@ class Engine:
         self._fwd_plans, self._bwd_plan, self._plan_epoch = {}, None, 0
         self._logits = self._gout = self._flat = None
         self._pack_on_side = False
+        # 2:4 sparse inference (Darknet.sparse = "2:4", plain-fp16 eval engines only): conv indices of the blocks that run
+        # mcamd_conv_fwd_sparse24, chosen when the masks change (_update_sparse); empty = every block dense
+        self.sparse_layers = []
+        self._sparse_mode, self._sparse_keys = None, None
         self.fold_dead = os.environ.get("MCAMD_FOLD_DEAD", "1") == "1"
         # "mixed": the two correction products of the split-operand forward from e4m3 copies on the block-scaled fp8 MFMAs
         # (csrc/conv_igemm_pp.hip, F8).  "fp16x3" keeps all three products on fp16 operands: it is the tests' tight reference.
@@ -656,8 +660,14 @@ class Engine:
                                  dst_fwd=lay.wp, dst_dgrad=lay.wd, split=split, f8_wexp=lay.f8_wexp_eff))
             self._pack_table = ops.pack_table(jobs, self.device) if jobs else None
             self._pack_key = tkey
+        skeys = (mkeys, self._sparse_mode)
+        if skeys != self._sparse_keys:
+            self._update_sparse()
+            self._sparse_keys = skeys
         for lay in self.layers:
             mask = lay.conv.mask.contiguous() if lay.conv.mask_flag else None
+            if lay.sp_on:
+                ops.pack_sparse24(lay.geom_act, lay.conv.weight.data, mask, lay.wsp, lay.widx)
             if lay.stem:
                 ops.pack_weights(lay.geom_act, lay.conv.weight.data, mask, True, False, lay.wp, None, rows=lay.g_rows)
             if getattr(lay, "stem_split", False):          # hi and lo stem packings of the split-operand fused first block
@@ -699,6 +709,46 @@ class Engine:
                 self._pack_on_side = True      # forward() makes the launch stream wait for the second one before block 2
         self._packed_sig = sig
         self.model._weights_dirty = False
+
+    # ------------------------------------------------------------------ 2:4 sparsity
+    def _fused_eval(self, lay):
+        """Does this block take the fused inference path (BN + LeakyReLU [+ pool / reorg] in the conv epilogue)?"""
+        return (self.fuse_eval and not self.precise and not lay.is_last and lay.perm is None and lay.border is None
+                and (lay.out2_t is None or lay.mode == L.DST_POOL)
+                and (lay.mode == L.DST_PLAIN or (lay.H % 2 == 0 and lay.W % 2 == 0)))
+
+    def _update_sparse(self):
+        """Which blocks run the 2:4 forward (called when the masks or Darknet.sparse change): a block does when its mask
+        keeps at most 2 of every 4 consecutive input channels at each (filter, tap) -- checked on the device, one host
+        read for all blocks --, it takes the fused inference path without filter compaction or folding, it is neither the
+        first nor the last block, and mcamd_conv_fwd_sparse24_ok accepts its geometry.  Every other block stays dense."""
+        self._plan_epoch += 1             # recorded forward plans name the dense or the sparse launch of a block
+        for lay in self.layers:
+            lay.sp_on = False
+        self.sparse_layers = []
+        if self._sparse_mode is None:
+            return
+        if self._sparse_mode != "2:4":
+            raise McamdError("sparse must be None or '2:4' (got %r)" % (self._sparse_mode,))
+        cand = [lay for lay in self.layers
+                if lay.li > 0 and not lay.stem and not lay.is_last and lay.conv.mask_flag and lay.fold is None
+                and lay.g_cols is None and lay.cin % 4 == 0 and self._fused_eval(lay)
+                and lay.conv.mask.shape == lay.conv.weight.shape and ops.conv_fwd_sparse24_ok(lay.geom_act)]
+        if not cand:
+            return
+        counts = torch.zeros(len(cand), dtype=torch.int32, device=self.device)
+        for i, lay in enumerate(cand):
+            ops.nm_violations(lay.conv.mask.contiguous(), counts[i:i + 1])
+        bad = counts.cpu().tolist()
+        for lay, b in zip(cand, bad):
+            if b:
+                continue
+            nv, ni = ops.sparse24_elems(lay.geom_act)
+            if getattr(lay, "wsp", None) is None or lay.wsp.numel() != nv:
+                lay.wsp = torch.zeros(nv, dtype=torch.float16, device=self.device)
+                lay.widx = torch.zeros(ni, dtype=torch.int16, device=self.device)
+            lay.sp_on = True
+            self.sparse_layers.append(lay.li + 1)      # conv number (conv1 = the first block)
 
     # ------------------------------------------------------------------ filter compaction
     def _set_geom_f(self, lay):
@@ -986,7 +1036,13 @@ class Engine:
                 if not lay.train_ok:
                     raise McamdError("conv block %d: training needs a BN channel count of 8 * (power of two), got %d"
                                      % (lay.index, lay.cout))
-        self.pack(force=training, training=training)
+        mode = None if training else getattr(self.model, "sparse", None)
+        if mode is not None and self.precise:
+            raise McamdError("sparse=%r runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r"
+                             % (mode, self.precision))
+        force = bool(training) or mode != self._sparse_mode
+        self._sparse_mode = mode
+        self.pack(force=force, training=training)
         self.serial += 1
         tin = self.layers[0].tin
         xs = x.detach().contiguous().float()
@@ -1101,6 +1157,12 @@ class Engine:
                 ops.bn_coeffs(None, lay.cout, lay.M, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, False,
                               lay.scale, lay.shift, lay.mean, lay.invstd, eps=bn.eps)
                 t, t2 = lay.out_t, lay.out2_t
+                if lay.sp_on:       # 2:4 weights on the sparse MFMA (Darknet.sparse, _update_sparse)
+                    self._timed('fwd', lay, ops.conv_fwd_sparse24, lay.geom_act, xin, lay.wsp, lay.widx, self.bufs[t.buf], t.ld,
+                                t.choff, lay.scale, lay.shift, lay.slope, dst_mode=lay.mode,
+                                y2=self.bufs[t2.buf] if t2 is not None else None,
+                                y2_ld=t2.ld if t2 is not None else 0, y2_choff=t2.choff if t2 is not None else 0)
+                    continue
                 self._timed('fwd', lay, ops.conv_fwd_padded, lay.geom_act, xin, lay.wp, self.bufs[t.buf], t.ld, t.choff,
                             lay.scale, lay.shift, lay.slope, dst_mode=lay.mode,
                             y2=self.bufs[t2.buf] if t2 is not None else None,

@@ -276,6 +276,10 @@ class Darknet(nn.Module):
         # a random-init network (3.2e-2 at B=64; the fp32 oracle with fp16-rounded storage: 3.7e-2) and is 1.35x faster:
         # `model.precision = "fp16"` / MCAMD_PRECISION=fp16 selects it explicitly (bench.py reports both).
         self.precision = os.environ.get("MCAMD_PRECISION", "auto")
+        # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
+        # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA
+        # (engine.Engine.sparse_layers).  Eval with precision "fp16" only -- other eval precisions raise; training ignores it.
+        self.sparse = None
 
     # ---- engine plumbing
     def _apply(self, fn, *args, **kwargs):

@@ -658,3 +658,61 @@ def masked_residual(ws, masks):
     for w, m in zip(ws, masks):
         check(L.lib().mcamd_masked_residual(ptr(w), ptr(m), w.numel(), ptr(out), stream_ptr()), "mcamd_masked_residual")
     return float(out.item())
+
+
+# ----------------------------------------------------------------------------- 2:4 structured sparsity
+def nm_mask(w, old_mask=None, n=2, m=4):
+    """N:M magnitude mask of an OIHW fp32 tensor (mcamd_nm_mask): per group of 4 consecutive input channels at a fixed
+    (filter, tap), the 2 largest |w * old_mask| keep their old mask value; ties keep the lower channel."""
+    _need_cuda(w, old_mask)
+    O, I = w.shape[0], w.shape[1]
+    khw = w.numel() // (O * I)
+    mask = torch.empty_like(w)
+    check(L.lib().mcamd_nm_mask(ptr(w), ptr(old_mask), O, I, khw, n, m, ptr(mask), stream_ptr()), "mcamd_nm_mask")
+    return mask
+
+
+def nm_violations(mask, out=None):
+    """Device int32 count of the mask's groups of 4 input channels with more than 2 non-zeros (added to `out`)."""
+    _need_cuda(mask)
+    O, I = mask.shape[0], mask.shape[1]
+    if out is None:
+        out = torch.zeros(1, dtype=torch.int32, device=mask.device)
+    check(L.lib().mcamd_nm_violations(ptr(mask), O, I, mask.numel() // (O * I), ptr(out), stream_ptr()), "mcamd_nm_violations")
+    return out
+
+
+def conv_fwd_sparse24_ok(g):
+    """Does mcamd_conv_fwd_sparse24 accept this geometry?  (Shared by the engine and the tests.)"""
+    return bool(L.lib().mcamd_conv_fwd_sparse24_ok(C.byref(g)))
+
+
+def sparse24_elems(g):
+    out = (C.c_int64 * 2)()
+    check(L.lib().mcamd_sparse24_elems(C.byref(g), out), "mcamd_sparse24_elems")
+    return int(out[0]), int(out[1])
+
+
+def pack_sparse24(g, w, mask=None, out_vals=None, out_idx=None):
+    """fp32 OIHW master (* mask) -> (fp16 kept values, int16 index words) of the 2:4 forward (mcamd_pack_sparse24)."""
+    _need_cuda(w, mask)
+    assert w.dtype == torch.float32 and w.is_contiguous()
+    nv, ni = sparse24_elems(g)
+    if out_vals is None:
+        out_vals = torch.empty(nv, dtype=HALF, device=w.device)
+    if out_idx is None:
+        out_idx = torch.empty(ni, dtype=torch.int16, device=w.device)
+    if out_vals.numel() < nv or out_idx.numel() < ni:
+        raise L.McamdError("pack_sparse24: destination too small")
+    check(L.lib().mcamd_pack_sparse24(C.byref(g), ptr(w), ptr(mask), ptr(out_vals), ptr(out_idx), stream_ptr()),
+          "mcamd_pack_sparse24")
+    return out_vals, out_idx
+
+
+def conv_fwd_sparse24(g, x, wsp, idx, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
+                      y2_choff=0):
+    """conv_fwd_padded on 2:4-packed weights (v_smfmac): the same inference epilogue, arguments and output."""
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff)
+    check(L.lib().mcamd_conv_fwd_sparse24(C.byref(g), ptr(x), ptr(wsp), ptr(idx), C.byref(e), stream_ptr()),
+          "mcamd_conv_fwd_sparse24")

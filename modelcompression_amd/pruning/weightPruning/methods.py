@@ -59,6 +59,34 @@ def weight_prune(model, pruning_perc):
     return [ops.magnitude_mask(w, thr) for w in ws]
 
 
+def nm_prune(model, n=2, m=4):
+    '''
+    N:M structured magnitude pruning -- an addition beyond the reference (which has only weight_prune and the filter
+    methods).  Same calling convention as weight_prune: one mask per `p.dim() != 1` parameter in model.parameters()
+    order, applied by the caller with model.set_masks(masks).  For a conv weight [O, I, kh, kw] with I % m == 0, every
+    group of m consecutive input channels at a fixed (o, tap) keeps its n entries of largest |w * old_mask| (ties: the
+    lower channel), old_mask being the layer's current mask (kept entries keep its value: composes with weight_prune)
+    or all ones; other parameters (conv1: 3 input channels) get their old mask unchanged, or all ones.  The 2:4 pattern
+    is what v_smfmac runs at twice the dense rate (Darknet.sparse = "2:4").  Only n=2, m=4.
+    '''
+    if (n, m) != (2, 4):
+        raise McamdError("nm_prune supports the 2:4 pattern only (got %s:%s)" % (n, m))
+    ps = _prunable(model)
+    owner = {}
+    for mod in model.modules():
+        if getattr(mod, "mask_flag", False) and hasattr(mod, "weight"):
+            owner[id(mod.weight)] = mod.mask
+    masks = []
+    for p in ps:
+        old = owner.get(id(p))
+        old = old.contiguous() if old is not None and old.shape == p.shape else None
+        if p.dim() == 4 and p.shape[1] % m == 0:
+            masks.append(ops.nm_mask(p.data.contiguous(), old, n, m))
+        else:
+            masks.append(old.clone() if old is not None else torch.ones_like(p.data))
+    return masks
+
+
 def _layer_scores(p):
     return ops.filter_scores(p.data.contiguous())
 
