@@ -114,7 +114,7 @@ typedef struct mcamd_conv_epilogue {
     float* stats;              /* modes 0 and 3, may be NULL: fp32 [stats_rows][2][stats_ld]; row p holds the
                                   per-channel sums (index 0) and sums of squares (index 1) over the pixels
                                   that persistent workgroup p processed (fixed order: deterministic) */
-    int32_t stats_rows;        /* must equal mcamd_conv_stats_rows(geom) */
+    int32_t stats_rows;        /* must equal mcamd_conv_stats_rows_mode(geom, mode) */
     int32_t stats_ld;          /* >= round_up(cout, 256) */
     const float* scale;        /* mode 2, may be NULL (=1) */
     const float* shift;        /* mode 2, may be NULL (=0) */
@@ -140,17 +140,20 @@ typedef struct mcamd_conv_epilogue {
 
 /* Rows of the BatchNorm partial-sum slab a forward launch of this geometry writes (epilogue mode 0). */
 int32_t mcamd_conv_stats_rows(const mcamd_conv_geom* g);
-/* The same for a given epilogue mode (MCAMD_EPI_RAW_F16 or MCAMD_EPI_RAW_F32: the fp32 epilogue only exists in
- * the LDS-staged implicit-GEMM kernels, so the slab shape differs for the layers that otherwise take a streaming kernel). */
+/* The same for a given epilogue mode (MCAMD_EPI_RAW_F16 or MCAMD_EPI_RAW_F32): the rows of the kernel mcamd_conv_fwd
+ * launches for (geometry, mode).  The queries below and the launch ask one route function, so a slab sized here is the
+ * slab the launch accepts. */
 int32_t mcamd_conv_stats_rows_mode(const mcamd_conv_geom* g, int32_t mode);
 
 /* Workgroup tile {BM, BN, BK, kernel} the forward (dgrad == 0) or dgrad launch (1; 2 = with epilogue.concurrent set) of
- * this geometry uses:
+ * this geometry uses, from the same route function as the launch.  Forward: a training launch (with a statistics slab),
+ * epilogue mode 3 for x_wrap / x_f8 geometries (they exist with the fp32 epilogues only), else mode 0; dgrad: mode 0.
  * kernel 0 = igemm_kernel<BM,BN,..,BK,..> (one tap per K chunk),
  * 2 = igemm_pp_kernel (ping-pong, one workgroup per CU), 1 = stem_fwd_kernel (first layer, no LDS staging),
  * 4 = small3x3_kernel (narrow 3x3 layers on huge images, no LDS staging), 5 = win3x3_kernel (rolling LDS window),
  * 6 = wres_kernel (3x3 layers with one 64-channel input block: weights resident in registers, one activation window per
- * M tile of 128 padded pixels). */
+ * M tile of 128 padded pixels), 7 = small3x3_split_kernel (the 32 -> <= 64 channel 3x3 layer on split operands at
+ * x_choff 0, fp32 output; BN = round_up(cout, 32), BK = the 96 K-concatenated channels). */
 int mcamd_conv_tile_info(const mcamd_conv_geom* g, int32_t dgrad, int32_t out[4]);
 
 /* Packed-weight sizes (elements of fp16) for a geometry. */

@@ -393,8 +393,31 @@ extern "C" int mcamd_pack_weights_many(const mcamd_pack_job* jobs_dev, int32_t n
 // ---------------------------------------------------------------------------------------
 // forward / dgrad
 // ---------------------------------------------------------------------------------------
-static int fill_epilogue(IgemmArgs& a, const mcamd_conv_epilogue* e, int n_out, long long M, int cin_tap, int ktot,
-                         const char* what, int expected_rows = -1) {
+// The operand side of a launch descriptor, shared by forward, 2:4 forward and dgrad: a padded NHWC operand `x` (`ld` elements per
+// pixel, slice at channel `choff`) with `ch_tap` channels per tap on the K side, `n` output columns.  No x_wrap / x_f8.
+static void fill_operand(IgemmArgs& a, const mcamd_conv_geom* g, const void* x, const void* w, int ld, int choff, int n,
+                         int ch_tap, int stem) {
+    memset(&a, 0, sizeof(a));
+    a.x = (const half_t*)x;
+    a.w = (const half_t*)w;
+    a.x_ld = ld;
+    a.x_row_stride = (g->W + pw_of(g)) * ld;
+    a.x_img_stride = (long long)(g->H + pw_of(g)) * a.x_row_stride;
+    a.x_off = choff;
+    a.H = g->H, a.W = g->W, a.HW = g->H * g->W;
+    a.M = g->B * g->H * g->W;
+    a.N = n;
+    a.cin_tap = ch_tap;
+    a.ntaps = stem ? 3 : g->ksize * g->ksize;
+    a.kb = kblock_of(ch_tap);
+    a.ktot = a.ntaps * ch_tap;
+    fill_taps(g->ksize, stem, a.x_row_stride, ld, a.tap_off);
+    a.wrap = 0x7fffffff;
+    a.f8_from = 0x7fffffff;
+}
+
+// `rows`: the statistics rows of the kernel the launch takes (ConvRoute.rows)
+static int fill_epilogue(IgemmArgs& a, const mcamd_conv_epilogue* e, int n_out, const char* what, int rows) {
     MCAMD_REQUIRE(e && e->y, "%s: null output", what);
     a.y = e->y;
     a.mode = e->mode;
@@ -414,7 +437,6 @@ static int fill_epilogue(IgemmArgs& a, const mcamd_conv_epilogue* e, int n_out, 
         MCAMD_REQUIRE(e->y_ld % 8 == 0 && e->y_choff % 8 == 0 && e->y_choff + n_out <= e->y_ld,
                       "%s: output slice [%d, %d) does not fit y_ld %d", what, e->y_choff, e->y_choff + n_out, e->y_ld);
         if (e->mode == MCAMD_EPI_RAW_F16 && e->stats) {
-            int rows = expected_rows >= 0 ? expected_rows : mcamd_igemm_rows(M, n_out, cin_tap, ktot);
             MCAMD_REQUIRE(e->stats_rows == rows, "%s: stats_rows must be mcamd_conv_stats_rows() = %d (got %d)", what, rows,
                           e->stats_rows);
             MCAMD_REQUIRE(e->stats_ld >= round_up_int(n_out, 256), "%s: stats_ld must be >= %d", what,
@@ -447,8 +469,6 @@ static int fill_epilogue(IgemmArgs& a, const mcamd_conv_epilogue* e, int n_out, 
         MCAMD_REQUIRE(e->y_ld % 4 == 0 && e->y_choff % 4 == 0 && e->y_choff + n_out <= e->y_ld,
                       "%s: fp32 output slice [%d, %d) does not fit y_ld %d", what, e->y_choff, e->y_choff + n_out, e->y_ld);
         if (e->stats) {
-            // the fp32 epilogue lives in the LDS-staged implicit-GEMM kernels only (mcamd_conv_stats_rows_mode)
-            int rows = expected_rows >= 0 ? expected_rows : mcamd_igemm_rows(M, n_out, cin_tap, ktot, false);
             MCAMD_REQUIRE(e->stats_rows == rows, "%s: stats_rows must be mcamd_conv_stats_rows_mode(g, 3) = %d (got %d)", what,
                           rows, e->stats_rows);
             MCAMD_REQUIRE(e->stats_ld >= round_up_int(n_out, 256), "%s: stats_ld must be >= %d", what,
@@ -462,55 +482,67 @@ static int fill_epilogue(IgemmArgs& a, const mcamd_conv_epilogue* e, int n_out, 
     return MCAMD_OK;
 }
 
-extern "C" int32_t mcamd_conv_stats_rows(const mcamd_conv_geom* g) {
-    if (!g) return 0;
-    if (mcamd_stem_direct_ok(g->stem, g->cout, MCAMD_EPI_RAW_F16)) return mcamd_stem_rows((long long)g->B * g->H * g->W);
-    if (g->pad == 0 && mcamd_wres_ok(g->ksize, g->stem, g->cout, cin_tap_of(g), ntaps_of(g) * cin_tap_of(g), g->B, g->H, g->W, MCAMD_EPI_RAW_F16))
-        return mcamd_wres_rows(g->cout, g->B, g->H, g->W);
-    return mcamd_igemm_rows((long long)g->B * g->H * g->W, g->cout, cin_tap_of(g), ntaps_of(g) * cin_tap_of(g));
+// The one place that decides which kernel a geometry takes, with which tile, and how many statistics rows it writes: the
+// size queries, mcamd_conv_tile_info and the launches all ask here, so they cannot disagree.  `dir` = the `dgrad` argument
+// of mcamd_conv_tile_info; `stats`: the epilogue writes BatchNorm partial sums.
+enum { DIR_FWD = 0, DIR_DGRAD = 1, DIR_DGRAD_CONCURRENT = 2 };
+static ConvRoute conv_route(const mcamd_conv_geom* g, int dir, int mode, int dst_mode, bool stats) {
+    const long long M = (long long)g->B * g->H * g->W;
+    const bool fwd = dir == DIR_FWD;
+    const int n = fwd ? g->cout : g->cin;
+    int ct = fwd ? cin_tap_of(g) : cout_p_of(g), ktot = (fwd ? ntaps_of(g) : g->ksize * g->ksize) * ct;
+    if (fwd && mcamd_stem_direct_ok(g->stem, n, mode))   // conv_stem.hip: weights in registers, image fragments straight from global memory
+        return {ROUTE_STEM, 32, n, 48, mcamd_stem_rows(M)};
+    if (fwd && dst_mode == MCAMD_DST_PLAIN && g->pad == 0 && g->x_f8 == 0 &&
+        mcamd_wres_ok(g->ksize, g->stem, n, ct, ktot, g->B, g->H, g->W, mode))   // conv_wres.hip: weights resident in registers
+        return {ROUTE_WRES, 128, 128, 64, mcamd_wres_rows(n, g->B, g->H, g->W)};
+    if (fwd && g->pad == 0 && !g->stem && g->x_choff == 0 && g->x_f8 == 0 &&
+        mcamd_small3x3_split_ok(M, n, ct, ktot, g->x_wrap, mode))   // conv_small.hip: weights resident, split operands
+        return {ROUTE_SMALL3X3_SPLIT, 32, round_up_int(n, 32), ct, mcamd_small3x3_rows(M)};
+    if (mcamd_win3x3_ok(mode, stats, M, n, ct, ktot, g->H, g->W))   // conv2 dgrad: rolling LDS window (conv_win.hip)
+        return {ROUTE_WIN3X3, 32, round_up_int(n, 16), 64, 0};
+    // (the fp8 correction form, mcamd_conv_geom.x_f8: K is 2/3 of the three-product problem's; the tile is chosen for that
+    // problem, so that a layer takes the same tile -- and the same statistics slab -- in either form)
+    if (fwd && g->x_f8 > 0 && mode == MCAMD_EPI_RAW_F32) ct = ct / 2 * 3, ktot = ktot / 2 * 3;   // (x_f8 launches with mode 3 only)
+    return mcamd_igemm_route(M, n, ct, ktot, mode == MCAMD_EPI_RAW_F16, dir == DIR_DGRAD_CONCURRENT);   // stats slabs only exist with RAW
+}
+
+static int launch_route(IgemmArgs& a, const ConvRoute& r, const mcamd_conv_geom* g, hipStream_t st) {
+    switch (r.kernel) {
+    case ROUTE_STEM: {
+        StemArgs q;
+        q.x = a.x, q.w = a.w, q.y = (half_t*)a.y, q.stats = a.stats;
+        q.y_ld = a.y_ld, q.y_choff = a.y_choff, q.stats_ld = a.stats_ld;
+        q.H = g->H, q.W = g->W, q.HW = a.HW, q.M = a.M;
+        return mcamd_stem_launch(q, g->cout, r.rows, st);
+    }
+    case ROUTE_WRES: return mcamd_wres_launch(a, g->B, r.rows, st);
+    case ROUTE_SMALL3X3_SPLIT: return mcamd_small3x3_split_launch(a, r.rows, st);
+    case ROUTE_SMALL3X3: return mcamd_small3x3_launch(a, r.rows, st);
+    case ROUTE_WIN3X3: return mcamd_win3x3_launch(a, st);
+    default: return mcamd_igemm_launch(a, r, st);   // ROUTE_IGEMM, ROUTE_PP
+    }
 }
 
 extern "C" int32_t mcamd_conv_stats_rows_mode(const mcamd_conv_geom* g, int32_t mode) {
     if (!g) return 0;
-    if (mode == MCAMD_EPI_RAW_F32) {
-        if (g->pad == 0 && mcamd_small3x3_split_ok((long long)g->B * g->H * g->W, g->cout, cin_tap_of(g), ntaps_of(g) * cin_tap_of(g),
-                                                   g->x_wrap, mode))
-            return mcamd_small3x3_rows((long long)g->B * g->H * g->W);
-        const int ct = g->x_f8 > 0 ? cin_tap_of(g) / 2 * 3 : cin_tap_of(g);      // (x_f8: the tile of the three-product problem)
-        return mcamd_igemm_rows((long long)g->B * g->H * g->W, g->cout, ct, ntaps_of(g) * ct, false);
-    }
-    return mcamd_conv_stats_rows(g);
+    return conv_route(g, DIR_FWD, mode == MCAMD_EPI_RAW_F32 ? MCAMD_EPI_RAW_F32 : MCAMD_EPI_RAW_F16, MCAMD_DST_PLAIN, true).rows;
 }
+
+extern "C" int32_t mcamd_conv_stats_rows(const mcamd_conv_geom* g) { return mcamd_conv_stats_rows_mode(g, MCAMD_EPI_RAW_F16); }
 
 extern "C" int32_t mcamd_conv_fwd_f8_ok(const mcamd_conv_geom* g) {
     if (!g || g->x_f8 <= 0 || g->x_f8 % 64 != 0 || g->cin != 2 * g->x_f8 || g->stem || g->x_wrap != 0 || g->x_choff != 0) return 0;
-    return mcamd_igemm_f8_ok((long long)g->B * g->H * g->W, g->cout, cin_tap_of(g), ntaps_of(g) * cin_tap_of(g)) ? 1 : 0;
+    return conv_route(g, DIR_FWD, MCAMD_EPI_RAW_F32, MCAMD_DST_PLAIN, true).kernel == ROUTE_PP ? 1 : 0;   // the three-product problem takes the ping-pong tile
 }
 
+// forward: with statistics, fp32 epilogue (mode 3) for the x_wrap / x_f8 forms, which only exist with it; dgrad: mode 0
 extern "C" int mcamd_conv_tile_info(const mcamd_conv_geom* g, int32_t dgrad, int32_t out[4]) {
     if (check_geom(g, "conv_tile_info")) return MCAMD_EINVAL;
     MCAMD_REQUIRE(out, "conv_tile_info: null output");
-    out[3] = 0;
-    if (!dgrad && g->x_f8 > 0) {
-        const int ct = cin_tap_of(g) / 2 * 3;
-        mcamd_igemm_tile((long long)g->B * g->H * g->W, g->cout, ct, ntaps_of(g) * ct, out, false);
-        return MCAMD_OK;
-    }
-    if (!dgrad && mcamd_stem_direct_ok(g->stem, g->cout, MCAMD_EPI_RAW_F16)) {
-        out[0] = 32, out[1] = g->cout, out[2] = 48, out[3] = 1;   // stem_fwd_kernel (conv_stem.hip)
-        return MCAMD_OK;
-    }
-    if (!dgrad && g->pad == 0 && mcamd_wres_ok(g->ksize, g->stem, g->cout, cin_tap_of(g), ntaps_of(g) * cin_tap_of(g), g->B, g->H, g->W, MCAMD_EPI_RAW_F16)) {
-        out[0] = 128, out[1] = 128, out[2] = 64, out[3] = 6;   // wres_kernel (conv_wres.hip): weights resident in registers
-        return MCAMD_OK;
-    }
-    if (dgrad && mcamd_win3x3_shape((long long)g->B * g->H * g->W, g->cin, cout_p_of(g), g->ksize * g->ksize * cout_p_of(g), g->W)) {
-        out[0] = 32, out[1] = round_up_int(g->cin, 16), out[2] = 64, out[3] = 5;   // win3x3_kernel (conv_win.hip)
-        return MCAMD_OK;
-    }
-    mcamd_igemm_tile((long long)g->B * g->H * g->W, dgrad ? g->cin : g->cout, dgrad ? cout_p_of(g) : cin_tap_of(g),
-                     dgrad ? g->ksize * g->ksize * cout_p_of(g) : ntaps_of(g) * cin_tap_of(g), out,
-                     dgrad == 2);
+    const bool f32 = !dgrad && (g->x_wrap > 0 || g->x_f8 > 0);
+    const ConvRoute r = conv_route(g, dgrad, f32 ? MCAMD_EPI_RAW_F32 : MCAMD_EPI_RAW_F16, MCAMD_DST_PLAIN, !dgrad);
+    out[0] = r.bm, out[1] = r.bn, out[2] = r.bk, out[3] = r.kernel;
     return MCAMD_OK;
 }
 
@@ -523,53 +555,22 @@ extern "C" int mcamd_conv_fwd(const mcamd_conv_geom* g, const void* x, const voi
         return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd(&g_, x, wp_fwd, &e_, s); });
     }
     if (check_geom(g, "conv_fwd")) return MCAMD_EINVAL;
-    MCAMD_REQUIRE(x && wp_fwd, "conv_fwd: null input");
+    MCAMD_REQUIRE(x && wp_fwd && epi, "conv_fwd: null input / epilogue");
     IgemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = (const half_t*)x;
-    a.w = (const half_t*)wp_fwd;
-    a.x_ld = g->x_ld;
-    a.x_row_stride = (g->W + pw_of(g)) * g->x_ld;
-    a.x_img_stride = (long long)(g->H + pw_of(g)) * a.x_row_stride;
-    a.x_off = g->x_choff;
-    a.H = g->H, a.W = g->W, a.HW = g->H * g->W;
-    a.M = g->B * g->H * g->W;
-    a.N = g->cout;
-    a.cin_tap = cin_tap_of(g);
-    a.ntaps = ntaps_of(g);
-    a.kb = kblock_of(a.cin_tap);
-    a.ktot = a.ntaps * a.cin_tap;
-    fill_taps(g->ksize, g->stem, a.x_row_stride, g->x_ld, a.tap_off);
-    a.wrap = g->x_wrap > 0 ? g->x_wrap : 0x7fffffff;
-    MCAMD_REQUIRE(g->x_wrap == 0 || (epi && (epi->mode == MCAMD_EPI_RAW_F32 || epi->mode == MCAMD_EPI_NCHW_F32)),
+    fill_operand(a, g, x, wp_fwd, g->x_ld, g->x_choff, g->cout, cin_tap_of(g), g->stem);
+    MCAMD_REQUIRE(g->x_wrap == 0 || epi->mode == MCAMD_EPI_RAW_F32 || epi->mode == MCAMD_EPI_NCHW_F32,
                   "conv_fwd: x_wrap goes with the fp32 epilogues (modes 3 and 1)");
+    if (g->x_wrap > 0) a.wrap = g->x_wrap;
     // x_f8: channel blocks [P, 2 P) of the slice are e4m3 bytes; K order [channel block][tap][kb] -> the fp8 chunks are the tail
-    a.f8_from = g->x_f8 > 0 ? (g->x_f8 / a.kb) * a.ntaps * (a.kb / 32) : 0x7fffffff;
+    if (g->x_f8 > 0) a.f8_from = (g->x_f8 / a.kb) * a.ntaps * (a.kb / 32);
     a.f8_sb = (127 - (MCAMD_F8_SXL + g->x_f8_wexp)) * 0x01010101;
+    const ConvRoute r = conv_route(g, DIR_FWD, epi->mode, epi->dst_mode, epi->stats != nullptr);
     if (g->x_f8 > 0) {
-        MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_RAW_F32, "conv_fwd: x_f8 goes with the fp32 epilogue (mode 3)");
-        MCAMD_REQUIRE(mcamd_igemm_f8_ok(a.M, g->cout, a.cin_tap, a.ktot), "conv_fwd: no fp8-correction kernel for this shape (mcamd_conv_fwd_f8_ok)");
+        MCAMD_REQUIRE(epi->mode == MCAMD_EPI_RAW_F32, "conv_fwd: x_f8 goes with the fp32 epilogue (mode 3)");
+        MCAMD_REQUIRE(r.kernel == ROUTE_PP, "conv_fwd: no fp8-correction kernel for this shape (mcamd_conv_fwd_f8_ok)");
     }
-    const bool stem_direct = epi && mcamd_stem_direct_ok(g->stem, g->cout, epi->mode);
-    const bool wres = epi && epi->dst_mode == MCAMD_DST_PLAIN && g->pad == 0 && g->x_f8 == 0 &&
-                      mcamd_wres_ok(g->ksize, g->stem, g->cout, a.cin_tap, a.ktot, g->B, g->H, g->W, epi->mode);
-    const bool small_split = epi && g->pad == 0 && !g->stem && g->x_choff == 0 && g->x_f8 == 0 &&
-                             mcamd_small3x3_split_ok(a.M, g->cout, a.cin_tap, a.ktot, g->x_wrap, epi->mode);
-    if (fill_epilogue(a, epi, g->cout, a.M, a.cin_tap, a.ktot, "conv_fwd",
-                      stem_direct ? mcamd_stem_rows(a.M) : (wres ? mcamd_wres_rows(g->cout, g->B, g->H, g->W)
-                                                                 : (small_split ? mcamd_small3x3_rows(a.M)
-                                                                                : (g->x_f8 > 0 ? mcamd_conv_stats_rows_mode(g, MCAMD_EPI_RAW_F32) : -1)))))
-        return MCAMD_EINVAL;
-    if (small_split) return mcamd_small3x3_split_launch(a, (hipStream_t)stream);   // conv_small.hip: weights resident, split operands
-    if (wres) return mcamd_wres_launch(a, g->B, (hipStream_t)stream);
-    if (stem_direct) {       // conv_stem.hip: weights in registers, image fragments straight from global memory
-        StemArgs q;
-        q.x = a.x, q.w = a.w, q.y = (half_t*)a.y, q.stats = a.stats;
-        q.y_ld = a.y_ld, q.y_choff = a.y_choff, q.stats_ld = a.stats_ld;
-        q.H = g->H, q.W = g->W, q.HW = a.HW, q.M = a.M;
-        return mcamd_stem_launch(q, g->cout, (hipStream_t)stream);
-    }
-    return mcamd_igemm_launch(a, (hipStream_t)stream);
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd", r.rows)) return MCAMD_EINVAL;
+    return launch_route(a, r, g, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -620,24 +621,8 @@ extern "C" int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, 
     MCAMD_REQUIRE(x && wsp && idx, "conv_fwd_sparse24: null input");
     MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_sparse24: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
     IgemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = (const half_t*)x;
-    a.w = (const half_t*)wsp;
-    a.x_ld = g->x_ld;
-    a.x_row_stride = (g->W + pw_of(g)) * g->x_ld;
-    a.x_img_stride = (long long)(g->H + pw_of(g)) * a.x_row_stride;
-    a.x_off = g->x_choff;
-    a.H = g->H, a.W = g->W, a.HW = g->H * g->W;
-    a.M = g->B * g->H * g->W;
-    a.N = g->cout;
-    a.cin_tap = cin_tap_of(g);
-    a.ntaps = ntaps_of(g);
-    a.kb = kblock_of(a.cin_tap);
-    a.ktot = a.ntaps * a.cin_tap;
-    a.wrap = 0x7fffffff;
-    a.f8_from = 0x7fffffff;
-    fill_taps(g->ksize, 0, a.x_row_stride, g->x_ld, a.tap_off);
-    if (fill_epilogue(a, epi, g->cout, a.M, a.cin_tap, a.ktot, "conv_fwd_sparse24")) return MCAMD_EINVAL;
+    fill_operand(a, g, x, wsp, g->x_ld, g->x_choff, g->cout, cin_tap_of(g), 0);
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_sparse24", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
     return mcamd_sparse24_launch(a, idx, (hipStream_t)stream);
 }
 
@@ -657,28 +642,13 @@ extern "C" int mcamd_conv_dgrad(const mcamd_conv_geom* g, const void* dy, int32_
     MCAMD_REQUIRE(dy_ld % 8 == 0 && dy_choff % 8 == 0 && dy_choff + cout_p <= dy_ld,
                   "conv_dgrad: dy slice [%d, %d) does not fit dy_ld %d", dy_choff, dy_choff + cout_p, dy_ld);
     IgemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = (const half_t*)dy;
-    a.w = (const half_t*)wp_dgrad;
-    a.x_ld = dy_ld;
-    a.x_row_stride = (g->W + pw_of(g)) * dy_ld;
-    a.x_img_stride = (long long)(g->H + pw_of(g)) * a.x_row_stride;
-    a.x_off = dy_choff;
-    a.H = g->H, a.W = g->W, a.HW = g->H * g->W;
-    a.M = g->B * g->H * g->W;
-    a.N = g->cin;
-    a.cin_tap = cout_p;
-    a.wrap = 0x7fffffff;
-    a.f8_from = 0x7fffffff;
-    a.ntaps = g->ksize * g->ksize;
-    a.kb = kblock_of(a.cin_tap);
-    a.ktot = a.ntaps * a.cin_tap;
-    fill_taps(g->ksize, 0, a.x_row_stride, dy_ld, a.tap_off);
+    fill_operand(a, g, dy, wp_dgrad, dy_ld, dy_choff, g->cin, cout_p, 0);
     MCAMD_REQUIRE(epi && epi->mode != MCAMD_EPI_PAD_F16 && !epi->stats && epi->dst_mode == 0 && !epi->y2,
                   "conv_dgrad: epilogue must be mode 0 (no stats) or 1");
-    if (fill_epilogue(a, epi, g->cin, a.M, a.cin_tap, a.ktot, "conv_dgrad")) return MCAMD_EINVAL;
     a.concurrent = epi->concurrent != 0;
-    return mcamd_igemm_launch(a, (hipStream_t)stream);
+    const ConvRoute r = conv_route(g, a.concurrent ? DIR_DGRAD_CONCURRENT : DIR_DGRAD, epi->mode, MCAMD_DST_PLAIN, false);
+    if (fill_epilogue(a, epi, g->cin, "conv_dgrad", r.rows)) return MCAMD_EINVAL;
+    return launch_route(a, r, g, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------

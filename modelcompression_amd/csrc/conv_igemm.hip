@@ -441,30 +441,19 @@ static TileCfg pick_tile(long long M, int n, int cin_tap, int ktot, bool raw_epi
     return t;
 }
 
-void mcamd_igemm_tile(long long M, int n, int cin_tap, int ktot, int out[4], bool concurrent) {
-    TileCfg t = pick_tile(M, n, cin_tap, ktot, true, concurrent);
-    out[0] = t.bm, out[1] = t.bn, out[2] = t.bk, out[3] = t.kind;
-}
-
-// x_f8 geometry (cin_tap = 2 P, ktot = ntaps * 2 P): the three-product problem of the same layer takes the ping-pong tile
-bool mcamd_igemm_f8_ok(long long M, int n, int cin_tap, int ktot) {
-    if (cin_tap % 128 != 0) return false;       // P % 64 == 0: whole 64-channel K blocks on either side of the fp16 / fp8 boundary
-    return pick_tile(M, n, cin_tap / 2 * 3, ktot / 2 * 3, false, false).kind == 2;
-}
-
 static int igemm_mtiles(long long M, int bm) { return (int)((M + bm - 1) / bm); }
 
-// Number of persistent workgroups along M (== rows of the BN-statistics slab).
-int mcamd_igemm_rows(long long M, int n, int cin_tap, int ktot, bool raw_epilogue, bool concurrent) {
-    TileCfg t = pick_tile(M, n, cin_tap, ktot, raw_epilogue, concurrent);
+// The tile and the number of persistent workgroups along M (== rows of the BN-statistics slab).
+ConvRoute mcamd_igemm_route(long long M, int n, int cin_tap, int ktot, bool raw_epilogue, bool concurrent) {
+    const TileCfg t = pick_tile(M, n, cin_tap, ktot, raw_epilogue, concurrent);
+    if (t.kind == ROUTE_SMALL3X3) return {t.kind, t.bm, t.bn, t.bk, mcamd_small3x3_rows(M)};
     int ntiles = (n + t.bn - 1) / t.bn;
     int mtiles = igemm_mtiles(M, t.bm);
-    if (t.kind == 4) return mcamd_small3x3_rows(M);
-    int target = t.kind == 2 ? 256 : 2048;   // ping-pong: one workgroup per CU, persistent
+    int target = t.kind == ROUTE_PP ? 256 : 2048;   // ping-pong: one workgroup per CU, persistent
     int p = target / ntiles;
     if (p < 1) p = 1;
     if (p > mtiles) p = mtiles;
-    return p;
+    return {t.kind, t.bm, t.bn, t.bk, p};
 }
 
 template <int BM, int BN, int WM, int WN, int BK, int NSTAGE, int EPI>
@@ -486,48 +475,32 @@ static void launch_one(const IgemmArgs& a, int rows, int ntiles, hipStream_t st)
     else launch_inst<BM, BN, WM, WN, BK, NSTAGE, MCAMD_EPI_RAW_F16>(a, rows, ntiles, st);
 }
 
-// a.* geometry fields must be filled by the caller; picks the tile and launches.
-int mcamd_igemm_launch(IgemmArgs& a, hipStream_t st) {
-    if (mcamd_win3x3_ok(a)) return mcamd_win3x3_launch(a, st);   // conv2 dgrad: rolling LDS window (conv_win.hip)
-    const bool conc = a.concurrent != 0;
-    const bool f8 = a.f8_from != 0x7fffffff;
-    // (the fp8 correction form, mcamd_conv_geom.x_f8: K is 2/3 of the three-product problem's; the tile is chosen for that
-    // problem, so that a layer takes the same tile -- and the same statistics slab -- in either form)
-    const int ktile = f8 ? a.ktot / 2 * 3 : a.ktot;
-    TileCfg t = pick_tile(a.M, a.N, f8 ? a.cin_tap / 2 * 3 : a.cin_tap, ktile, a.mode == MCAMD_EPI_RAW_F16, conc);   // stats slabs only exist with RAW
-    if (f8 && t.kind != 2) {
-        mcamd_set_error("igemm: no fp8-correction kernel for M %d N %d K %d (mcamd_conv_fwd_f8_ok)", a.M, a.N, a.ktot);
+// a.* geometry fields must be filled by the caller; r = the ROUTE_IGEMM / ROUTE_PP tile conv_route() chose for them.
+int mcamd_igemm_launch(IgemmArgs& a, const ConvRoute& r, hipStream_t st) {
+    if (a.cin_tap % r.bk != 0 || a.ktot % r.bk != 0) {
+        mcamd_set_error("igemm: K per tap (%d) must be a multiple of %d", a.cin_tap, r.bk);
         return MCAMD_EINVAL;
     }
-    if (t.kind == 4) return mcamd_small3x3_launch(a, st);
-    if (a.cin_tap % t.bk != 0 || a.ktot % t.bk != 0) {
-        mcamd_set_error("igemm: K per tap (%d) must be a multiple of %d", a.cin_tap, t.bk);
-        return MCAMD_EINVAL;
-    }
-    int ntiles = (a.N + t.bn - 1) / t.bn;
-    a.num_mtiles = igemm_mtiles(a.M, t.bm);
-    int rows = mcamd_igemm_rows(a.M, a.N, f8 ? a.cin_tap / 2 * 3 : a.cin_tap, ktile, a.mode == MCAMD_EPI_RAW_F16, conc);
+    const int rows = r.rows, ntiles = (a.N + r.bn - 1) / r.bn;
+    a.num_mtiles = igemm_mtiles(a.M, r.bm);
     a.num_pslots = rows;
     a.num_ntiles = ntiles;
     a.xcd_order = 1;
-    if (t.kind == 2) return mcamd_igemm_pp_launch(a, t.bm, t.bn, rows, ntiles, st);
-    const int stages = t.bk == 32 ? 3 : 2;
+    if (r.kernel == ROUTE_PP) return mcamd_igemm_pp_launch(a, r.bm, r.bn, rows, ntiles, st);
+    const int stages = r.bk == 32 ? 3 : 2;
 #define I_CASE(BN_, WM_, WN_, BK_, ST_)                              \
-    if (!done && t.bm == 128 && t.bn == BN_ && t.bk == BK_ && stages == ST_) { \
+    if (!done && r.bm == 128 && r.bn == BN_ && r.bk == BK_ && stages == ST_) { \
         launch_one<128, BN_, WM_, WN_, BK_, ST_>(a, rows, ntiles, st); \
         done = true;                                                  \
     }
     bool done = false;
-    if (t.bm == 192 && t.bn == 128 && t.bk == 64) { launch_one<192, 128, 96, 64, 64, 2>(a, rows, ntiles, st); done = true; }
-    I_CASE(128, 64, 64, 32, 2) I_CASE(128, 64, 64, 32, 3) I_CASE(128, 64, 64, 32, 4)
-    I_CASE(128, 64, 64, 64, 2) I_CASE(128, 64, 64, 64, 3)
-    I_CASE(64, 64, 32, 32, 2) I_CASE(64, 64, 32, 32, 3) I_CASE(64, 64, 32, 32, 4)
-    I_CASE(64, 64, 32, 64, 2) I_CASE(64, 64, 32, 64, 3)
-    I_CASE(32, 32, 32, 32, 2) I_CASE(32, 32, 32, 32, 3) I_CASE(32, 32, 32, 32, 4)
-    I_CASE(32, 32, 32, 64, 2) I_CASE(32, 32, 32, 64, 3)
+    if (r.bm == 192 && r.bn == 128 && r.bk == 64) { launch_one<192, 128, 96, 64, 64, 2>(a, rows, ntiles, st); done = true; }
+    I_CASE(128, 64, 64, 32, 3) I_CASE(128, 64, 64, 64, 2)
+    I_CASE(64, 64, 32, 32, 3) I_CASE(64, 64, 32, 64, 2)
+    I_CASE(32, 32, 32, 32, 3) I_CASE(32, 32, 32, 64, 2)
 #undef I_CASE
     if (!done) {
-        mcamd_set_error("igemm: no kernel instance for BN %d BK %d stages %d", t.bn, t.bk, stages);
+        mcamd_set_error("igemm: no kernel instance for BM %d BN %d BK %d stages %d", r.bm, r.bn, r.bk, stages);
         return MCAMD_EINVAL;
     }
     MCAMD_LAUNCH_CHECK("igemm");

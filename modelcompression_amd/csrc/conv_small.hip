@@ -283,8 +283,7 @@ bool mcamd_small3x3_split_ok(long long M, int n, int cin_tap, int ktot, int wrap
            M >= 4096;
 }
 
-int mcamd_small3x3_split_launch(const IgemmArgs& a, hipStream_t st) {
-    const int grid = mcamd_small3x3_rows(a.M);
+int mcamd_small3x3_split_launch(const IgemmArgs& a, int grid, hipStream_t st) {
     hipLaunchKernelGGL((small3x3_split_kernel<4>), dim3(grid), dim3(256), 0, st, a);
     MCAMD_LAUNCH_CHECK("small3x3_split");
     return MCAMD_OK;
@@ -316,8 +315,7 @@ static void launch_small(const IgemmArgs& a, int grid, hipStream_t st) {
     hipLaunchKernelGGL((small3x3_kernel<CT, NB, 2>), dim3(grid), dim3(256), 0, st, a);   // two 16-pixel groups in flight per wave (one: 0.186 vs 0.168 ms)
 }
 
-int mcamd_small3x3_launch(const IgemmArgs& a, hipStream_t st) {
-    const int grid = mcamd_small3x3_rows(a.M);
+int mcamd_small3x3_launch(const IgemmArgs& a, int grid, hipStream_t st) {
     const int nb = small_blocks(a.N);
     if (a.cin_tap == 32) {
         if (nb == 1) launch_small<32, 1>(a, grid, st);

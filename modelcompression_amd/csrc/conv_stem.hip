@@ -130,9 +130,8 @@ int mcamd_stem_rows(long long M) {
     return (int)(wgs < 2048 ? wgs : 2048);
 }
 
-int mcamd_stem_launch(const StemArgs& a, int cout, hipStream_t st) {
+int mcamd_stem_launch(const StemArgs& a, int cout, int grid, hipStream_t st) {
     // 4 groups in flight per wave: 1 / 2 / 4 / 8 measured 0.255 / 0.235 / 0.210 / 0.306 ms for conv1 at B=64
-    const int grid = mcamd_stem_rows(a.M);
     if (cout == 32) hipLaunchKernelGGL((stem_fwd_kernel<1, 4>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((stem_fwd_kernel<2, 4>), dim3(grid), dim3(256), 0, st, a);
     MCAMD_LAUNCH_CHECK("stem_fwd");

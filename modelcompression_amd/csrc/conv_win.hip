@@ -176,18 +176,10 @@ __global__ __launch_bounds__(256, 1) void win3x3_kernel(IgemmArgs a, int seg_row
     }
 }
 
-// dgrad-shaped problems: 3x3, 64 padded input channels, <= 32 outputs, raw fp16 epilogue without statistics
-static bool win_enabled() { return true; }
-
-bool mcamd_win3x3_ok(const IgemmArgs& a) {
-    if (!win_enabled()) return false;
-    if (a.mode != MCAMD_EPI_RAW_F16 || a.bias || a.kb != 64 || a.W < 32 || a.H < 8 || a.M % (a.H * a.W) != 0) return false;
-    return !a.stats && a.ktot == 9 * 64 && a.cin_tap == 64 && a.N % 8 == 0 && a.N <= 32 && a.W % 16 == 0 && a.M >= 65536;
-}
-
-bool mcamd_win3x3_shape(long long M, int n, int cin_tap, int ktot, int W) {   // for mcamd_conv_tile_info (dgrad)
-    if (!win_enabled()) return false;
-    return ktot == 9 * 64 && cin_tap == 64 && n % 8 == 0 && n <= 32 && W % 16 == 0 && W >= 32 && M >= 65536;
+// dgrad-shaped problems: 3x3, 64 padded input channels, <= 32 outputs, raw fp16 epilogue without statistics, M whole images
+bool mcamd_win3x3_ok(int mode, bool stats, long long M, int n, int cin_tap, int ktot, int H, int W) {
+    if (mode != MCAMD_EPI_RAW_F16 || stats || W < 32 || H < 8 || M % ((long long)H * W) != 0) return false;
+    return ktot == 9 * 64 && cin_tap == 64 && n % 8 == 0 && n <= 32 && W % 16 == 0 && M >= 65536;
 }
 
 template <int NB>

@@ -303,12 +303,12 @@ int mcamd_wres_rows(int n, int B, int H, int W) {
     return (int)p;
 }
 
-int mcamd_wres_launch(IgemmArgs& a, int B, hipStream_t st) {
+int mcamd_wres_launch(IgemmArgs& a, int B, int rows, hipStream_t st) {
     const int S = wres_S(a.W);
     const long long P = (long long)B * (a.H + 2) * (a.W + 2);
     a.num_ntiles = (a.N + BN - 1) / BN;
     a.num_mtiles = (int)((P + BM - 1) / BM);
-    a.num_pslots = mcamd_wres_rows(a.N, B, a.H, a.W);
+    a.num_pslots = rows;
     const size_t lds = 2 * (size_t)(BM + 2 * S) * RB + 2 * (size_t)BM * CTP * 2;
     const int grid = round_up_int(a.num_pslots, 8) * a.num_ntiles;
     if (a.mode == MCAMD_EPI_PAD_F16) {

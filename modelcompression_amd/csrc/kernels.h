@@ -75,11 +75,20 @@ struct WgradPlan {
     size_t bytes;
 };
 
-void mcamd_igemm_tile(long long M, int n, int cin_tap, int ktot, int out[4], bool concurrent = false);   // {BM, BN, BK, kind}: kind 0 igemm_kernel, 2 igemm_pp_kernel
+// Which kernel a forward / dgrad launch takes, its workgroup tile and the rows of the statistics slab it writes: decided
+// once per launch or query by conv_route() (api.hip).  `kernel` = the kinds of mcamd_conv_tile_info (mcamd.h).
+enum { ROUTE_IGEMM = 0, ROUTE_STEM = 1, ROUTE_PP = 2, ROUTE_SMALL3X3 = 4, ROUTE_WIN3X3 = 5, ROUTE_WRES = 6, ROUTE_SMALL3X3_SPLIT = 7 };
+struct ConvRoute {
+    int kernel;
+    int bm, bn, bk;
+    int rows;   // persistent workgroups along M
+};
+
+// conv_igemm.hip: pick_tile + the persistent-workgroup count for an implicit GEMM of M pixels x n channels (kernel
+// ROUTE_IGEMM, ROUTE_PP or ROUTE_SMALL3X3); mcamd_igemm_launch takes the first two as given
+ConvRoute mcamd_igemm_route(long long M, int n, int cin_tap, int ktot, bool raw_epilogue, bool concurrent);
 int mcamd_igemm_pp_launch(const IgemmArgs& a, int bm, int bn, int rows, int ntiles, hipStream_t st);
-bool mcamd_igemm_f8_ok(long long M, int n, int cin_tap, int ktot);   // the fp8-correction form exists for the tile this shape takes
-int mcamd_igemm_rows(long long M, int n, int cin_tap, int ktot, bool raw_epilogue = true, bool concurrent = false);
-int mcamd_igemm_launch(IgemmArgs& a, hipStream_t st);
+int mcamd_igemm_launch(IgemmArgs& a, const ConvRoute& r, hipStream_t st);
 int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);   // conv_sparse.hip: 2:4 weights, mode 2 epilogue
 int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
                                int cin_tap, int kb, hipStream_t st);
@@ -101,19 +110,19 @@ int mcamd_wgrad_finish_launch(const float* slab, const WgradPlan& p, int ktot, i
 int mcamd_colsum_launch(const half_t* dy, long long rows, int ld, int choff, int C, float inv_scale, float* out,
                         hipStream_t st, void* scratch, size_t scratch_bytes);   // scratch: reusable once the finish pass is enqueued
 
-bool mcamd_win3x3_ok(const IgemmArgs& a);                             // conv_win.hip
-bool mcamd_win3x3_shape(long long M, int n, int cin_tap, int ktot, int W);
+// the per-kernel eligibility rules and slab rows conv_route() asks, each once; the launches take `rows` from the route
+bool mcamd_win3x3_ok(int mode, bool stats, long long M, int n, int cin_tap, int ktot, int H, int W);   // conv_win.hip
 int mcamd_win3x3_launch(const IgemmArgs& a, hipStream_t st);
 bool mcamd_small3x3_ok(long long M, int n, int cin_tap, int ktot);   // conv_small.hip
 int mcamd_small3x3_rows(long long M);
-int mcamd_small3x3_launch(const IgemmArgs& a, hipStream_t st);
+int mcamd_small3x3_launch(const IgemmArgs& a, int rows, hipStream_t st);
 bool mcamd_small3x3_split_ok(long long M, int n, int cin_tap, int ktot, int wrap, int mode);   // split operands, fp32 output
-int mcamd_small3x3_split_launch(const IgemmArgs& a, hipStream_t st);
+int mcamd_small3x3_split_launch(const IgemmArgs& a, int rows, hipStream_t st);
 
 bool mcamd_wres_ok(int ksize, int stem, int n, int cin_tap, int ktot, int B, int H, int W, int mode);   // conv_wres.hip
 int mcamd_wres_rows(int n, int B, int H, int W);
-int mcamd_wres_launch(IgemmArgs& a, int B, hipStream_t st);
+int mcamd_wres_launch(IgemmArgs& a, int B, int rows, hipStream_t st);
 
 bool mcamd_stem_direct_ok(int stem, int cout, int mode);
 int mcamd_stem_rows(long long M);
-int mcamd_stem_launch(const StemArgs& a, int cout, hipStream_t st);
+int mcamd_stem_launch(const StemArgs& a, int cout, int rows, hipStream_t st);

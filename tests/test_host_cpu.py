@@ -165,6 +165,68 @@ def test_fp8_correction_geometry_query():
     assert ops.tile_info(ok) == ops.tile_info(three) and ops.tile_info(ok)[3] == 2
 
 
+def _route_table_tool():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("conv_route_table", os.path.join(ROOT, "tools", "conv_route_table.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_conv_route_table_is_frozen():
+    """tests/golden/conv_route_table.json holds what the host queries (statistics rows in modes 0 and 3, conv_fwd_f8_ok,
+    tile_info forward / dgrad / dgrad-concurrent) answered BEFORE forward and dgrad got their single route function
+    (api.hip conv_route): every YOLOv2-VOC and mini-cfg convolution at six batch sizes, three input sizes, both halo forms,
+    in the plain, split, fp8, channel-offset and split + channel-offset operand forms, filter-pruned widths, and a reduced
+    list under each MCAMD_* tile switch.  Every row must still be answered the same, except the two corrections below --
+    both on the conv2 shape of the split-operand precision, which small3x3_split_kernel serves only at x_choff == 0:
+      1. x_choff == 0: tile_info reported the LDS-staged tile although conv_fwd launches small3x3_split_kernel; now
+         (32, round_up(cout, 32), 96, 7).
+      2. x_choff != 0: stats_rows(mode 3) answered small3x3_rows(M) although conv_fwd launches igemm_kernel there (and
+         refused the slab so sized); now the rows of that kernel's tile: min(ceil(M / BM), 2048 / ceil(cout / BN)).
+    Nothing else may move: 27 + 27 rows of 4 677."""
+    tool = _route_table_tool()
+    old, new = _gold("conv_route_table.json"), tool.table()
+    assert old["cols"] == new["cols"] == tool.COLS
+    assert [s["env"] for s in old["sections"]] == [s["env"] for s in new["sections"]]
+    total, moved = 0, [0, 0]
+    for so, sn in zip(old["sections"], new["sections"]):
+        assert [r[:12] for r in so["rows"]] == [r[:12] for r in sn["rows"]], so["env"]
+        for ro, rn in zip(so["rows"], sn["rows"]):
+            g = dict(zip(old["cols"], ro))
+            was, now = list(old["results"][ro[12]]), list(new["results"][rn[12]])
+            M = g["B"] * g["H"] * g["W"]
+            split_conv2 = (g["ksize"] == 3 and g["cin"] == 96 and g["x_wrap"] == 64 and g["pad"] == 0 and 32 < g["cout"] <= 64
+                           and g["cout"] % 8 == 0 and M >= 4096 and so["env"].get("MCAMD_SMALL3X3") != "0")
+            total += 1
+            if split_conv2 and g["x_choff"] == 0:
+                assert was[3:7] != now[3:7] and now[3:7] == [32, -(-g["cout"] // 32) * 32, 96, 7], (so["env"], g, was, now)
+                was[3:7] = now[3:7]
+                moved[0] += 1
+            elif split_conv2:
+                bm, bn, _, kind = was[3:7]
+                assert kind == 0 and was[1] == min(256, -(-(-(-M // 32)) // 8)), (so["env"], g, was)
+                assert now[1] == min(-(-M // bm), 2048 // -(-g["cout"] // bn)) != was[1], (so["env"], g, was, now)
+                was[1] = now[1]
+                moved[1] += 1
+            assert was == now, (so["env"], g, was, now)
+    assert total == 4677 and moved == [27, 27]
+
+
+def test_stats_rows_query_names_the_launched_kernel():
+    """The slab a caller sizes with stats_rows() is the one conv_fwd accepts: the split conv2 geometry read at a channel
+    offset goes to igemm_kernel (small3x3_split_kernel reads at x_choff == 0 only), so its mode-3 row count is that tile's,
+    not small3x3_rows (256 here).  tile_info names small3x3_split_kernel (kind 7) where it is launched."""
+    from modelcompression_amd import ops
+    L = _lib
+    g0 = ops.geom(64, 208, 208, 3, 96, 64, 64, x_wrap=64)
+    assert ops.stats_rows(g0, L.EPI_RAW_F32) == 256 and ops.tile_info(g0) == (32, 64, 96, 7)
+    assert ops.tile_info(ops.geom(1, 208, 208, 3, 96, 64, 64, x_wrap=64)) == (32, 64, 96, 7)
+    g = ops.geom(64, 208, 208, 3, 96, 64, 128, x_choff=64, x_wrap=64)
+    assert ops.tile_info(g) == (128, 64, 32, 0)
+    assert ops.stats_rows(g, L.EPI_RAW_F32) == min(-(-64 * 208 * 208 // 128), 2048) == 2048
+
+
 def test_few_tile_launches_take_64_column_tiles():
     """Tile rule of the LDS-staged implicit GEMM (no GPU needed: a host-side query): a launch whose 128 x 128 tiles would
     fill less than one round of the 256 CUs takes 64-column tiles -- also when the channel count is ragged but pads to the

@@ -537,6 +537,45 @@ def test_small3x3_split_kernel(dev, setenv, B, H, W, cout):
     assert rel_l2(outs[0][0], outs[1][0]) < 1e-6
 
 
+def test_split_conv2_at_channel_offset(dev, setenv):
+    """The conv2 shape on split operands read from a slice at channel 64 of a wider buffer: small3x3_split_kernel reads at
+    x_choff == 0 only, so the launch goes to igemm_kernel -- with the slab that stats_rows() sizes (the query once answered
+    small3x3_rows here and the launch refused that slab).  Against float64 torch (2e-6), the statistics against the sums of
+    the output, and against the same kernel on the offset-free buffer (MCAMD_SMALL3X3=0, 1e-6)."""
+    B, H, W, C_, cout, off = 2, 56, 56, 32, 64, 64
+    gen = torch.Generator().manual_seed(7)
+    x = torch.randn(B, C_, H, W, generator=gen)
+    w = torch.randn(cout, C_, 3, 3, generator=gen) * (2.0 / (C_ * 9)) ** 0.5
+    hi = x.half().float()
+    lo = (x - hi).half().float()
+    ref = F.conv2d(x.double(), w.double(), None, 1, 1)
+    outs = []
+    for choff, sw in ((off, "1"), (0, "0")):
+        setenv("MCAMD_SMALL3X3", sw)
+        ld = 2 * C_ + choff
+        xb = ops.alloc_padded(B, H, W, ld, dev)
+        ops.nchw_to_padded(hi.to(dev).contiguous(), xb, ld, choff)
+        ops.nchw_to_padded(lo.to(dev).contiguous(), xb, ld, choff + C_)
+        g = ops.geom(B, H, W, 3, 3 * C_, cout, ld, x_choff=choff, x_wrap=2 * C_)
+        wp = torch.zeros(ops.packed_elems(g)[0], dtype=torch.float16, device=dev)
+        ops.pack_many(*ops.pack_table([dict(w=w.to(dev).contiguous(), mask=None, rows=None, cols=None, cout=cout, cin=C_,
+                                            ksize=3, dst_fwd=wp, dst_dgrad=None, split=True)], dev))
+        assert ops.tile_info(g)[3] == 0
+        rows = ops.stats_rows(g, L.EPI_RAW_F32)
+        assert rows == -(-B * H * W // ops.tile_info(g)[0])         # one persistent workgroup per M tile at this size
+        y = torch.full((B * H * W * cout,), float("nan"), device=dev)
+        stats = torch.full((rows, 2, ops.round_up(cout, 256)), float("nan"), device=dev)
+        stats[:, :, cout:] = 0
+        ops.conv_fwd_raw32(g, xb, wp, y, cout, 0, stats)
+        got = y.view(B, H, W, cout).permute(0, 3, 1, 2).cpu()
+        assert rel_l2(got, ref) < 2e-6
+        yd = y.view(-1, cout).double()
+        assert torch.allclose(stats[:, 0, :cout].double().sum(0), yd.sum(0), rtol=1e-5, atol=1e-3)
+        assert torch.allclose(stats[:, 1, :cout].double().sum(0), (yd * yd).sum(0), rtol=1e-5)
+        outs.append(got)
+    assert rel_l2(outs[0], outs[1]) < 1e-6
+
+
 def test_step_flags_kernel(dev):
     """mcamd_step_flags (train.StepGuard's device-side decision in one launch): [any engine overflow, loss not finite,
     transport overflow], found_inf = EXACTLY 1.0 when any of them fired (torch's fused SGD tests `== 1`: a sum of two
