@@ -255,6 +255,30 @@ int mcamd_conv_wgrad(const mcamd_conv_geom* g, const void* x, const void* dy, in
                      float grad_scale, float* dw_oihw, float* dbias, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* Which kernels mcamd_conv_wgrad launches for this geometry (has_cmap != 0: with map->cols), from the plan and decision
+ * functions the launch itself calls; works without a GPU.  out[]:
+ *   0     family: MCAMD_WGRAD_GENERIC wgrad_kernel<TMo, TNc, TAPS, KP, NS>, _STEM wgrad_stem_kernel<NS>, _WIN
+ *         wgrad_win_kernel<TMo / 32, NS>, _NINE wgrad9_kernel<KP>, _NINE_WIDE wgrad9w_kernel<KP, NS>
+ *   1-5   TMo, TNc, TAPS, KP, NS: filters x input channels x taps of a workgroup, pixels per step, LDS ring stages
+ *   6-8   nsplit (pixel splits = fp32 slabs), pix_per_split (0: the stem / win kernels divide the steps themselves),
+ *         rows_pad (filter rows of a slab; the dy slice that is read is that wide)
+ *   9-10  finish kernel: MCAMD_WFIN_ROW wgrad_finish_row_kernel<k*k> (SG 0), _VEC wgrad_finish_vec_kernel<k*k, SG>,
+ *         _GENERIC wgrad_finish_kernel<SG>; and SG (1 / 8 / 32)
+ *   11-12 tiles (workgroups per split) and workgroups launched (tiles * nsplit, rounded up to 8 where the kernel asks it) */
+#define MCAMD_WGRAD_GENERIC 0
+#define MCAMD_WGRAD_STEM 1
+#define MCAMD_WGRAD_WIN 2
+#define MCAMD_WGRAD_NINE 3
+#define MCAMD_WGRAD_NINE_WIDE 4
+#define MCAMD_WFIN_ROW 0
+#define MCAMD_WFIN_VEC 1
+#define MCAMD_WFIN_GENERIC 2
+#define MCAMD_WGRAD_PLAN_INFO_N 13
+int mcamd_conv_wgrad_plan_info(const mcamd_conv_geom* g, int32_t has_cmap, int32_t out[MCAMD_WGRAD_PLAN_INFO_N]);
+/* The (TMo, TNc, TAPS, KP) of every wgrad_kernel instance the library holds, 4 values each; at most `cap` tuples are
+ * written (out may be NULL with cap 0); returns their number.  Any other tuple is an MCAMD_EINVAL of the launch. */
+int32_t mcamd_wgrad_generic_instances(int32_t* out, int32_t cap);
+
 /* ------------------------------------------------------------------------- *
  * BatchNorm2d (eps, momentum as given; torch defaults 1e-5 / 0.1 at nets.py:802)
  * + LeakyReLU(0.1) (nets.py:809) + MaxPool2d(2,2) (nets.py:821) + Reorg(2)

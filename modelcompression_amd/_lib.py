@@ -118,6 +118,9 @@ class AugmentBatch(C.Structure):
 
 EPI_RAW_F16, EPI_NCHW_F32, EPI_PAD_F16, EPI_RAW_F32 = 0, 1, 2, 3
 DST_PLAIN, DST_POOL, DST_REORG = 0, 1, 2
+WGRAD_GENERIC, WGRAD_STEM, WGRAD_WIN, WGRAD_NINE, WGRAD_NINE_WIDE = 0, 1, 2, 3, 4      # mcamd_conv_wgrad_plan_info: family
+WFIN_ROW, WFIN_VEC, WFIN_GENERIC = 0, 1, 2                                             # ... and finish kernel
+WGRAD_PLAN_INFO_N = 13
 
 # name -> (restype, argtypes); the complete list of symbols include/mcamd.h declares.
 _P, _I32, _I64, _F, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -142,6 +145,8 @@ SIGNATURES = {
     "mcamd_conv_dgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _I32, _I32, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_wgrad_workspace_bytes": (_SZ, [C.POINTER(ConvGeom)]),
     "mcamd_conv_wgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _I32, _I32, _P, C.POINTER(ChanMap), _F, _P, _P, _P, _SZ, _P]),
+    "mcamd_conv_wgrad_plan_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I32)]),
+    "mcamd_wgrad_generic_instances": (_I32, [C.POINTER(_I32), _I32]),
     "mcamd_bn_coeffs": (C.c_int, [_P, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _F, _F, _I32, _P, _P, _P, _P, _P, _P]),
     "mcamd_bn_coeffs_ex": (C.c_int, [_P, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _F, _F, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "mcamd_fold_weights": (C.c_int, [C.POINTER(FoldDesc), _P, _P]),

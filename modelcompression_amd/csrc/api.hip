@@ -669,6 +669,29 @@ extern "C" size_t mcamd_conv_wgrad_workspace_bytes(const mcamd_conv_geom* g) {
     return wgrad_plan_for(g).bytes;
 }
 
+// out: see include/mcamd.h.  The plan, the ring depth and the finish kernel come from the functions the launch calls.
+extern "C" int mcamd_conv_wgrad_plan_info(const mcamd_conv_geom* g, int32_t has_cmap, int32_t out[MCAMD_WGRAD_PLAN_INFO_N]) {
+    if (check_geom(g, "conv_wgrad_plan_info")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(out, "conv_wgrad_plan_info: null output");
+    MCAMD_REQUIRE(!(g->stem && has_cmap), "conv_wgrad_plan_info: the stem layer takes no input-channel map");
+    const WgradPlan p = wgrad_plan_for(g);
+    const WgradFinish f = mcamd_wgrad_finish_pick(p.nsplit, g->stem, g->cin, g->ksize, has_cmap != 0);
+    const int tiles = p.n_otiles * p.n_tapgroups * p.n_ctiles;
+    out[0] = p.nine == 2 ? MCAMD_WGRAD_NINE_WIDE : p.nine ? MCAMD_WGRAD_NINE : p.stemw == 1 ? MCAMD_WGRAD_STEM
+             : p.stemw == 2 ? MCAMD_WGRAD_WIN : MCAMD_WGRAD_GENERIC;
+    out[1] = p.tmo, out[2] = p.tnc, out[3] = p.taps, out[4] = p.kp, out[5] = p.ns;
+    out[6] = p.nsplit, out[7] = p.pix_per_split, out[8] = p.rows_pad;
+    out[9] = f.kernel, out[10] = f.sg;
+    out[11] = tiles;
+    out[12] = p.stemw ? p.nsplit : round_up_int(tiles * p.nsplit, 8);
+    return MCAMD_OK;
+}
+
+extern "C" int32_t mcamd_wgrad_generic_instances(int32_t* out, int32_t cap) {
+    static_assert(sizeof(int32_t) == sizeof(int), "instance tuples are copied as int");
+    return mcamd_wgrad_instances((int (*)[4])out, out ? cap : 0);
+}
+
 extern "C" int mcamd_conv_wgrad(const mcamd_conv_geom* g, const void* x, const void* dy, int32_t dy_ld, int32_t dy_choff,
                                 const float* mask_oihw, const mcamd_chan_map* map, float grad_scale, float* dw_oihw,
                                 float* dbias, void* workspace, size_t workspace_bytes, void* stream) {

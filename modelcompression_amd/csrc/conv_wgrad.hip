@@ -750,7 +750,20 @@ static int pick_kp(int tmo, int tnc, int taps) {
     return 32;
 }
 
+// LDS ring stages of wgrad_kernel<TMo, TNc, TAPS, KP, NS>: three where three workgroups of them still fit a CU's 160 KB
+// (the 1x1 layers: 16-24 KB stages)
+static constexpr size_t wgrad_stage(int tmo, int tnc, int taps, int kp) {
+    return (size_t)(kp * (tmo / 8) + taps * kp * (tnc / 8)) * 16;
+}
+static constexpr int wgrad_ring(int tmo, int tnc, int taps, int kp) {
+    return 3 * wgrad_stage(tmo, tnc, taps, kp) * 3 <= 156 * 1024 ? 3 : 2;
+}
+
 static int wgrad9_S(int pitch) { return round_up_int(pitch + 1, 4); }   // pitch = padded pixels per image row (W + 2, or W + 1 in the shared-halo form)
+
+// bytes of one ring stage of the wide form (64 pixels of dY x 128 filters + the X window), and how many stages fit the LDS
+static size_t wgrad9w_stage(int pitch) { return (size_t)64 * 256 + (size_t)(64 + 2 * wgrad9_S(pitch)) * 128; }
+static int wgrad9w_ring(int pitch) { return 3 * wgrad9w_stage(pitch) <= 160 * 1024 ? 3 : 2; }
 
 // plan of the padded-pixel 9-tap kernel (see wgrad9_kernel); P = padded pixels
 static WgradPlan wgrad9_plan(long long P, int cout, int cin_tap, int W, int pitch, int B) {
@@ -763,11 +776,9 @@ static WgradPlan wgrad9_plan(long long P, int cout, int cin_tap, int W, int pitc
     // 64 pixels per step (half the barriers, 17-25 % fewer staged bytes per flop) while two double-buffered
     // workgroups still fit the LDS; the big-image layers (window of 64 + 2(W+3) rows) stay at 32
     p.kp = 32;
-    {
-        const int want = 64;   // 128 (13x13 layers only) measured 1.8x SLOWER
-        for (int kp = 64; kp <= want && kp <= 128; kp *= 2)
-            if (2 * (size_t)(kp + kp + 2 * wgrad9_S(pitch)) * 128 <= 72 * 1024) p.kp = kp;   // two workgroups per CU: 2 x 72 KB
-    }
+    p.ns = 2;
+    // 128 pixels per step (13x13 layers only) measured 1.8x SLOWER: wgrad9_kernel exists for 32 and 64
+    if (2 * (size_t)(64 + 64 + 2 * wgrad9_S(pitch)) * 128 <= 72 * 1024) p.kp = 64;   // two workgroups per CU: 2 x 72 KB
     p.rows_pad = round_up_int(cout, 64);
     p.n_otiles = p.rows_pad / 64;
     p.n_ctiles = cin_tap / 64;
@@ -778,11 +789,12 @@ static WgradPlan wgrad9_plan(long long P, int cout, int cin_tap, int W, int pitc
     // narrow kernel already executes ~1.1 PFLOP/s of padded-pixel MFMAs there: 33 % of the rows are halo at 13x13)
     // and conv22 (20 channel tiles) is 35 % slower, so the wide form is used from 40 pixels per row up
     const bool wide = cout % 128 == 0 && MCAMD_ENV_INT("MCAMD_WGRAD9W", 1) && W >= MCAMD_ENV_INT("MCAMD_WGRAD9W_MINW", 40) &&
-                      2 * (size_t)(64 * 256 + (64 + 2 * wgrad9_S(pitch)) * 128) <= 160 * 1024;
+                      2 * wgrad9w_stage(pitch) <= 160 * 1024;
     if (wide) {
         p.nine = 2;
         p.tmo = 128;
         p.kp = 64;
+        p.ns = wgrad9w_ring(pitch);
         p.n_otiles = p.rows_pad / 128;
     }
     long long tiles = (long long)p.n_otiles * p.n_ctiles;
@@ -841,23 +853,21 @@ int mcamd_wgrad9_launch(const WgradArgs& w, const WgradPlan& p, int pitch, long 
     a.nsteps_total = (int)((P + 31) / 32);
     const int R = 32 + 2 * a.S;
     const int grid = round_up_int(p.n_otiles * p.n_ctiles * p.nsplit, 8);
-    if (p.nine == 2) {
-        const size_t stage = (size_t)64 * 256 + (size_t)(64 + 2 * a.S) * 128;
-        const int ns = 3 * stage <= 160 * 1024 ? 3 : 2;
+    if (p.nine == 2 && p.kp == 64 && (p.ns == 2 || p.ns == 3)) {
+        const size_t stage = wgrad9w_stage(pitch);
         MCAMD_LDS_OPT_IN((wgrad9w_kernel<64, 2>), 160 * 1024);
         MCAMD_LDS_OPT_IN((wgrad9w_kernel<64, 3>), 160 * 1024);
-        if (ns == 3) hipLaunchKernelGGL((wgrad9w_kernel<64, 3>), dim3(grid), dim3(512), 3 * stage, st, a);
+        if (p.ns == 3) hipLaunchKernelGGL((wgrad9w_kernel<64, 3>), dim3(grid), dim3(512), 3 * stage, st, a);
         else hipLaunchKernelGGL((wgrad9w_kernel<64, 2>), dim3(grid), dim3(512), 2 * stage, st, a);
-    } else if (p.kp == 128) {
-        const size_t lds = 2 * (size_t)(128 * 128 + (R + 96) * 128);
-        if (lds > 64 * 1024) MCAMD_LDS_OPT_IN(wgrad9_kernel<128>, 72 * 1024);
-        hipLaunchKernelGGL(wgrad9_kernel<128>, dim3(grid), dim3(256), lds, st, a);
-    } else if (p.kp == 64) {
+    } else if (p.nine == 1 && p.kp == 64) {
         const size_t lds = 2 * (size_t)(64 * 128 + (R + 32) * 128);
         hipLaunchKernelGGL(wgrad9_kernel<64>, dim3(grid), dim3(256), lds, st, a);
-    } else {
+    } else if (p.nine == 1 && p.kp == 32) {
         const size_t lds = 2 * (size_t)(32 * 128 + R * 128);
         hipLaunchKernelGGL(wgrad9_kernel<32>, dim3(grid), dim3(256), lds, st, a);
+    } else {
+        mcamd_set_error("wgrad9: no kernel instance for form %d kp %d stages %d", p.nine, p.kp, p.ns);
+        return MCAMD_EINVAL;
     }
     MCAMD_LAUNCH_CHECK("wgrad9");
     return MCAMD_OK;
@@ -871,6 +881,7 @@ WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps) {
     p.tnc = pick_t(cin_tap);
     p.taps = pick_taps(p.tmo, p.tnc, ntaps);
     p.kp = pick_kp(p.tmo, p.tnc, p.taps);
+    p.ns = wgrad_ring(p.tmo, p.tnc, p.taps, p.kp);
     p.rows_pad = round_up_int(cout, p.tmo);
     p.n_otiles = p.rows_pad / p.tmo;
     p.n_ctiles = cin_tap / p.tnc;
@@ -904,12 +915,33 @@ WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps) {
 
 template <int TMo, int TNc, int TAPS, int KP>
 static void launch_w(const WgradArgs& a, int grid, hipStream_t st) {
-    constexpr size_t stage = (size_t)(KP * (TMo / 8) + TAPS * KP * (TNc / 8)) * 16;
-    // three stages where three workgroups of them still fit a CU's 160 KB (the 1x1 layers: 16-24 KB stages)
-    constexpr int NS = (3 * stage * 3 <= 156 * 1024) ? 3 : 2;
-    constexpr size_t lds = NS * stage;
+    constexpr int NS = wgrad_ring(TMo, TNc, TAPS, KP);
+    constexpr size_t lds = NS * wgrad_stage(TMo, TNc, TAPS, KP);
     if (lds > 64 * 1024) MCAMD_LDS_OPT_IN((wgrad_kernel<TMo, TNc, TAPS, KP, NS>), lds);   // lds is a per-instance constant
     hipLaunchKernelGGL((wgrad_kernel<TMo, TNc, TAPS, KP, NS>), dim3(grid), dim3(256), lds, st, a);
+}
+
+// Every (TMo, TNc, TAPS, KP) that pick_t x pick_t x pick_taps x pick_kp can produce: the instances that exist, for the
+// launch below and for mcamd_wgrad_generic_instances.  KP follows from the other three.  tests/test_host_cpu.py
+// (test_wgrad_instances_are_the_reachable_set) enumerates the pick rules through mcamd_conv_wgrad_plan_info against it.
+#define W_INSTANCES(X)                                             \
+    X(32, 32, 9, 32) X(32, 32, 3, 64) X(32, 32, 1, 128)             \
+    X(32, 64, 9, 32) X(32, 64, 1, 128)                              \
+    X(32, 128, 3, 32) X(32, 128, 1, 64)                             \
+    X(64, 32, 9, 32) X(64, 32, 3, 64) X(64, 32, 1, 128)             \
+    X(64, 64, 3, 32) X(64, 64, 1, 64)                               \
+    X(64, 128, 3, 32) X(64, 128, 1, 64)                             \
+    X(128, 32, 3, 32) X(128, 32, 1, 64)                             \
+    X(128, 64, 3, 32) X(128, 64, 1, 64)                             \
+    X(128, 128, 1, 32)
+
+int mcamd_wgrad_instances(int (*out)[4], int cap) {
+#define W_ROW(TM_, TN_, TP_, KP_) {TM_, TN_, TP_, KP_},
+    static const int list[][4] = {W_INSTANCES(W_ROW)};
+#undef W_ROW
+    const int n = (int)(sizeof(list) / sizeof(list[0]));
+    for (int i = 0; i < n && i < cap; ++i) memcpy(out[i], list[i], sizeof(list[i]));
+    return n;
 }
 
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st) {
@@ -927,17 +959,7 @@ int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st) {
         launch_w<TM_, TN_, TP_, KP_>(a, grid, st);                              \
         done = true;                                                            \
     }
-#define W_KPS(TM_, TN_, TP_) W_CASE(TM_, TN_, TP_, 32) W_CASE(TM_, TN_, TP_, 64) W_CASE(TM_, TN_, TP_, 128)
-    W_KPS(32, 32, 9) W_KPS(32, 32, 3) W_KPS(32, 32, 1)
-    W_KPS(32, 64, 9) W_KPS(32, 64, 3) W_KPS(32, 64, 1)
-    W_KPS(32, 128, 3) W_KPS(32, 128, 1)
-    W_KPS(64, 32, 9) W_KPS(64, 32, 3) W_KPS(64, 32, 1)
-    W_KPS(64, 64, 3) W_KPS(64, 64, 1)
-    W_KPS(64, 128, 3) W_KPS(64, 128, 1)
-    W_KPS(128, 32, 3) W_KPS(128, 32, 1)
-    W_KPS(128, 64, 3) W_KPS(128, 64, 1)
-    W_KPS(128, 128, 1)
-#undef W_KPS
+    W_INSTANCES(W_CASE)
 #undef W_CASE
     if (!done) {
         mcamd_set_error("wgrad: no kernel instance for tile %dx%d taps %d kp %d", p.tmo, p.tnc, p.taps, p.kp);
@@ -960,12 +982,21 @@ static void launch_finish_vec(int sg, long long total, const float* slab, const 
 #undef F_CASE
 }
 
+// Row kernel: one workgroup per filter gathers the row through the column map in LDS (<= 16 splits, a row of <= 60 KB);
+// vector kernel: four input channels per lane group; generic kernel: any Cin, and the stem's slab layout.
+WgradFinish mcamd_wgrad_finish_pick(int nsplit, int stem, int Cin, int ksize, bool has_cmap) {
+    const int sg = nsplit <= 4 ? 1 : (nsplit <= 64 ? 8 : 32);
+    const bool vec_ok = !stem && Cin % 4 == 0 && (ksize == 1 || ksize == 3);
+    if (has_cmap && vec_ok && nsplit <= 16 && (size_t)Cin * ksize * ksize * sizeof(float) <= 60 * 1024) return {MCAMD_WFIN_ROW, 0};
+    return {vec_ok ? MCAMD_WFIN_VEC : MCAMD_WFIN_GENERIC, sg};
+}
+
 int mcamd_wgrad_finish_launch(const float* slab, const WgradPlan& p, int ktot, int cin_tap, int stem, int Cout, int Cin,
                               int ksize, const float* mask, float inv_scale, float* dw, const int* rmap, const int* cmap,
                               hipStream_t st) {
-    const int sg = p.nsplit <= 4 ? 1 : (p.nsplit <= 64 ? 8 : 32);
-    if (cmap && !stem && Cin % 4 == 0 && (ksize == 1 || ksize == 3) && p.nsplit <= 16 &&
-        (size_t)Cin * ksize * ksize * sizeof(float) <= 60 * 1024) {
+    const WgradFinish f = mcamd_wgrad_finish_pick(p.nsplit, stem, Cin, ksize, cmap != nullptr);
+    const int sg = f.sg;
+    if (f.kernel == MCAMD_WFIN_ROW) {
         const size_t lds = (size_t)Cin * ksize * ksize * sizeof(float);
         if (ksize == 3)
             hipLaunchKernelGGL(wgrad_finish_row_kernel<9>, dim3(Cout), dim3(256), lds, st, slab, p.nsplit, p.rows_pad, ktot,
@@ -973,7 +1004,7 @@ int mcamd_wgrad_finish_launch(const float* slab, const WgradPlan& p, int ktot, i
         else
             hipLaunchKernelGGL(wgrad_finish_row_kernel<1>, dim3(Cout), dim3(256), lds, st, slab, p.nsplit, p.rows_pad, ktot,
                                cin_tap, Cin, mask, inv_scale, dw, rmap, cmap);
-    } else if (!stem && Cin % 4 == 0 && (ksize == 1 || ksize == 3)) {
+    } else if (f.kernel == MCAMD_WFIN_VEC) {
         long long total = (long long)Cout * (Cin / 4);
         if (ksize == 3) launch_finish_vec<9>(sg, total, slab, p, ktot, cin_tap, Cout, Cin, mask, inv_scale, dw, rmap, cmap, st);
         else launch_finish_vec<1>(sg, total, slab, p, ktot, cin_tap, Cout, Cin, mask, inv_scale, dw, rmap, cmap, st);

@@ -144,6 +144,8 @@ __global__ __launch_bounds__(256) void wgrad_stem_kernel(WgradArgs a) {
     }
 }
 
+constexpr int WGRAD_STEM_NS = 4;
+
 bool mcamd_wgrad_stem_ok(int stem, int cout, int W, long long M) {
     return stem && cout == 32 && W % 32 == 0 && M >= 4096;
 }
@@ -153,6 +155,7 @@ WgradPlan mcamd_wgrad_stem_plan(long long M) {
     memset(&p, 0, sizeof(p));
     p.stemw = 1;
     p.tmo = 32, p.tnc = 16, p.taps = 3, p.kp = 32;
+    p.ns = WGRAD_STEM_NS;
     p.rows_pad = 32;
     p.n_otiles = p.n_ctiles = p.n_tapgroups = 1;
     long long steps = M / 32, wgs = (steps + 31) / 32;     // at least 8 steps per wave
@@ -169,7 +172,7 @@ int mcamd_wgrad_stem_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st) {
     }
     a.rows_pad = p.rows_pad;
     a.nsplit = p.nsplit;
-    hipLaunchKernelGGL(wgrad_stem_kernel<4>, dim3(p.nsplit), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(wgrad_stem_kernel<WGRAD_STEM_NS>, dim3(p.nsplit), dim3(256), 0, st, a);
     MCAMD_LAUNCH_CHECK("wgrad_stem");
     return MCAMD_OK;
 }
@@ -326,6 +329,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_win_kernel(WgradArgs a) {
         }
 }
 
+constexpr int WGRAD_WIN_NS = 6;                              // 5 stages (27 KB per wave) in flight: latency-bound below that
+
 bool mcamd_wgrad_win_ok(int ksize, int stem, int cout, int cin_tap, int W, long long M) {
     return ksize == 3 && !stem && cin_tap == 32 && round_up_int(cout, 32) <= 64 && W % 16 == 0 && M >= 4096;
 }
@@ -336,6 +341,7 @@ WgradPlan mcamd_wgrad_win_plan(long long M, int cout) {
     p.stemw = 2;
     p.rows_pad = round_up_int(cout, 32);
     p.tmo = p.rows_pad, p.tnc = 32, p.taps = 9, p.kp = 16;
+    p.ns = WGRAD_WIN_NS;
     p.n_otiles = p.n_ctiles = p.n_tapgroups = 1;
     long long steps = M / 16, wgs = (steps + 31) / 32;     // at least 8 steps per wave
     p.nsplit = (int)(wgs < 256 ? wgs : 256);                // one workgroup per CU
@@ -345,7 +351,7 @@ WgradPlan mcamd_wgrad_win_plan(long long M, int cout) {
 
 template <int NI>
 static void launch_win(const WgradArgs& a, int grid, hipStream_t st) {
-    constexpr int NS = 6;                                     // 5 stages (27 KB per wave) in flight: latency-bound below that
+    constexpr int NS = WGRAD_WIN_NS;
     const size_t lds = 4 * NS * (16 * NI * 64 + 4096);
     MCAMD_LDS_OPT_IN((wgrad_win_kernel<NI, NS>), lds);   // lds is a per-instance constant
     hipLaunchKernelGGL((wgrad_win_kernel<NI, NS>), dim3(grid), dim3(256), lds, st, a);

@@ -72,7 +72,14 @@ struct WgradPlan {
     int tmo, tnc, taps, kp, rows_pad, n_otiles, n_ctiles, n_tapgroups, nsplit, pix_per_split;
     int nine;   // 1: padded-pixel 9-tap kernel (wgrad9_kernel), 2: its wide form (wgrad9w_kernel)
     int stemw;  // 1: raw-window first-layer kernel (wgrad_stem_kernel), 2: raw-window 32-channel kernel (wgrad_win_kernel)
+    int ns;     // LDS ring stages of the kernel instance (the NS template argument where the kernel has one)
     size_t bytes;
+};
+
+// Which kernel sums the split-K slabs into dW (mcamd_wgrad_finish_launch) and how many lanes share one sum.
+struct WgradFinish {
+    int kernel;   // MCAMD_WFIN_ROW: wgrad_finish_row_kernel, _VEC: wgrad_finish_vec_kernel, _GENERIC: wgrad_finish_kernel
+    int sg;       // the SG template argument (1 / 8 / 32); 0 for the row kernel, which has none
 };
 
 // Which kernel a forward / dgrad launch takes, its workgroup tile and the rows of the statistics slab it writes: decided
@@ -104,6 +111,8 @@ int mcamd_wgrad_win_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);
 bool mcamd_wgrad_use9(int ksize, int stem, int cout, int cin_tap, int W);
 WgradPlan mcamd_wgrad_plan9(long long P, int cout, int cin_tap, int W, int pitch, int B);
 int mcamd_wgrad9_launch(const WgradArgs& w, const WgradPlan& p, int pitch, long long P, hipStream_t st);
+WgradFinish mcamd_wgrad_finish_pick(int nsplit, int stem, int Cin, int ksize, bool has_cmap);
+int mcamd_wgrad_instances(int (*out)[4], int cap);   // the (TMo, TNc, TAPS, KP) of every wgrad_kernel instance; returns their number
 int mcamd_wgrad_finish_launch(const float* slab, const WgradPlan& p, int ktot, int cin_tap, int stem, int Cout, int Cin,
                               int ksize, const float* mask, float inv_scale, float* dw, const int* rmap, const int* cmap,
                               hipStream_t st);

@@ -3,6 +3,7 @@
 Tensors are only containers for device memory here (allocation + stream come
 from PyTorch-ROCm); every compute call goes to libmcamd.so.
 """
+import collections
 import ctypes as C
 import weakref
 
@@ -226,6 +227,25 @@ def conv_dgrad_nchw(g, dy, dy_ld, dy_choff, wpd, out):
 
 def wgrad_workspace_bytes(g):
     return int(L.lib().mcamd_conv_wgrad_workspace_bytes(C.byref(g)))
+
+
+WgradPlanInfo = collections.namedtuple("WgradPlanInfo", "family tmo tnc taps kp ns nsplit pix_per_split rows_pad finish sg tiles grid")
+
+
+def wgrad_plan_info(g, has_cmap=False):
+    """The kernels mcamd_conv_wgrad launches for `g` (with a column map or without): mcamd_conv_wgrad_plan_info.  Needs no GPU."""
+    out = (C.c_int32 * L.WGRAD_PLAN_INFO_N)()
+    check(L.lib().mcamd_conv_wgrad_plan_info(C.byref(g), 1 if has_cmap else 0, out), "mcamd_conv_wgrad_plan_info")
+    return WgradPlanInfo(*out)
+
+
+def wgrad_generic_instances():
+    """(TMo, TNc, TAPS, KP) of every wgrad_kernel instance in the library."""
+    lib = L.lib()
+    n = int(lib.mcamd_wgrad_generic_instances(None, 0))
+    out = (C.c_int32 * (4 * n))()
+    lib.mcamd_wgrad_generic_instances(out, n)
+    return [tuple(out[4 * i:4 * i + 4]) for i in range(n)]
 
 
 def conv_wgrad(g, x, dy, dy_ld, dy_choff, dw, mask=None, grad_scale=1.0, dbias=None, workspace=None, rows=None, cols=None):

@@ -239,6 +239,77 @@ def test_few_tile_launches_take_64_column_tiles():
     assert tuple(ops.tile_info(ops.geom(64, 52, 52, 1, 256, 125, 256))[:2]) == (128, 128)       # ragged, but 1 352 tiles
 
 
+def test_wgrad_instances_are_the_reachable_set(setenv):
+    """The wgrad_kernel<TMo, TNc, TAPS, KP, NS> instances the library holds (mcamd_wgrad_generic_instances) are exactly the
+    tuples its pick rules can produce.  The tuple is a function of (cout, padded cin, taps) alone, so every cout and cin
+    from 8 to 1344, both kernel sizes and the stem form are asked through mcamd_conv_wgrad_plan_info on a one-tile image
+    (no raw-window kernel), with the 9-tap kernels on and off (off, the 3x3 layers with 64-multiple inputs reach the
+    generic kernel too).  An instance nobody can launch, or a tuple without an instance, fails here."""
+    from modelcompression_amd import ops
+    import wgrad_cases as WC
+    seen = set()
+    for w9 in ("1", "0"):
+        setenv("MCAMD_WGRAD9", w9)
+        for cout in range(8, 1345, 8):
+            p = ops.wgrad_plan_info(ops.geom(1, 8, 8, 3, 3, cout, 4, 0, stem=1))
+            assert p.family == _lib.WGRAD_GENERIC
+            seen.add((p.tmo, p.tnc, p.taps, p.kp))
+            for cin in range(8, 1345, 8):
+                for k in (1, 3):
+                    p = ops.wgrad_plan_info(ops.geom(1, 8, 8, k, cin, cout, ops.round_up(cin, 32)))
+                    if p.family == _lib.WGRAD_GENERIC:
+                        seen.add((p.tmo, p.tnc, p.taps, p.kp))
+                    else:
+                        assert w9 == "1" and k == 3 and p.family == _lib.WGRAD_NINE
+    have = ops.wgrad_generic_instances()
+    assert len(have) == len(set(have)) == 19
+    assert seen == set(have), seen ^ set(have)
+    # the other families over images and switches (WC.reachable): nothing outside the instances their launchers hold
+    comp, fin = WC.reachable(setenv)
+    assert {c for c in comp if c[0] != "wgrad_kernel"} == {
+        ("wgrad_stem_kernel", 4), ("wgrad_win_kernel", 1, 6), ("wgrad_win_kernel", 2, 6), ("wgrad9_kernel", 32),
+        ("wgrad9_kernel", 64), ("wgrad9w_kernel", 64, 2), ("wgrad9w_kernel", 64, 3)}
+    assert {c[1:5] for c in comp if c[0] == "wgrad_kernel"} == set(have)
+    assert fin == ({("wgrad_finish_row_kernel", kk) for kk in (1, 9)}
+                   | {("wgrad_finish_vec_kernel", kk, sg) for kk in (1, 9) for sg in (1, 8, 32)}
+                   | {("wgrad_finish_kernel", sg) for sg in (1, 8, 32)})
+
+
+def test_wgrad_cases_reach_every_instance_and_boundary(setenv):
+    """Coverage of tests/test_wgrad_instances_gpu.py, proved without a GPU: the cases reach every compute-kernel instance
+    and every finish-kernel instance (with every SG) that the plan rules can name, and every named boundary condition,
+    each read from the library's own answer.  A changed pick rule that makes a new instance reachable fails here until a
+    case is added; each case also still names the instance it was written for."""
+    import wgrad_cases as WC
+    comp, fin, tags = set(), set(), set()
+    for c in WC.WGRAD_CASES:
+        WC.apply_env(c, setenv)
+        p = WC.plan_of(c)
+        got = (WC.compute_of(p), WC.finish_of(p, c.k, c.stem))
+        assert got == c.expect, (c.name, p)
+        t = WC.boundary_tags(c, p)
+        assert set(c.tags) <= t, (c.name, p, t)
+        assert c.vmax ** 2 * WC.pixels_enumerated(c) < 2 ** 24, c.name          # the condition of exactness
+        comp.add(got[0]), fin.add(got[1])
+        tags |= t
+    assert len({c.name for c in WC.WGRAD_CASES}) == len(WC.WGRAD_CASES)
+    want_comp, want_fin = WC.reachable(setenv)
+    assert comp == want_comp, comp ^ want_comp
+    assert fin == want_fin, fin ^ want_fin
+    assert tags >= set(WC.BOUNDARIES), set(WC.BOUNDARIES) - tags
+    # the operand forms, spread over the list
+    cs = WC.WGRAD_CASES
+    nine = [c for c in cs if c.expect[0][0] in ("wgrad9_kernel", "wgrad9w_kernel")]
+    assert {c.expect[0] for c in nine if c.pad} == {c.expect[0] for c in nine}, "every 9-tap instance in the shared-halo form"
+    assert {c.expect[0] for c in nine if not c.pad} == {c.expect[0] for c in nine}
+    for what in (lambda c: c.x_choff > 0 and c.x_ld > c.x_choff + 32, lambda c: c.dy_choff > 0, lambda c: c.cout_full > c.cout,
+                 lambda c: c.perm_cols, lambda c: c.mask, lambda c: not c.mask, lambda c: c.grad_scale == 1.0,
+                 lambda c: c.grad_scale == 256.0, lambda c: c.dbias, lambda c: not c.dbias):
+        assert sum(1 for c in cs if what(c)) >= 1
+    for name in WC.DETERMINISM_CASES:
+        assert sum(1 for c in cs if c.name == name) == 1
+
+
 def test_region_loss_runs_and_has_reference_quirks():
     from modelcompression_amd.region_loss import RegionLoss
     loss = RegionLoss()
