@@ -397,6 +397,22 @@ typedef struct mcamd_act_bwd_desc {
                                   as above: xhat from `y`, argmax and side from the copy) (nn.MaxPool2d(2, 2)
                                   backward, reference src/nets.py:821). */
     int32_t act_ld, act_choff, act_pad;
+    const void* pool_out;      /* optional (mode MCAMD_DST_POOL, no g2, with `act` or an fp32 `y`), NULL = none: the POOLED activation the forward
+                                  pass stored for the consumer (fp16, H/2 x W/2, padded NHWC / shared-halo form per
+                                  pool_out_pad, the hi plane of split storage) at channels [pool_out_choff, pool_out_choff + C)
+                                  of rows of pool_out_ld.  Only the pooled element of a window has a gradient, and its stored
+                                  value -- the strict maximum of the window's four `act` values -- is this tensor bit for
+                                  bit (both are the saturated fp16 rounding of the same maximum), so the pass that forms
+                                  the two per-channel sums reads it and `g` (4 bytes per window) instead of the four `act`
+                                  values and `g` (10 bytes).  The threads that hold an ill-conditioned channel (see `act`)
+                                  still read the window of `act` for the argmax and `y` at it.  dY is formed as without
+                                  it.  WITHOUT `act` (fp32 `y`, y_dtype 1): the pass reads 4 bytes per window instead of the
+                                  four fp32 `y` values and `g` (18 bytes); xhat = (z - beta) / gamma then comes from the fp16
+                                  pooled activation, as `act` gives it for a PLAIN block, and the ill-conditioned channels
+                                  take the argmax from the unrounded activations of `y`.  An fp16 `y` is refused: it is the
+                                  tensor whose statistics the forward pass took, its xhat is exact.
+                                  MCAMD_BN_POOL_SUMS_POOLED=0 ignores the pointer. */
+    int32_t pool_out_ld, pool_out_choff, pool_out_pad;
 } mcamd_act_bwd_desc;
 size_t mcamd_bn_act_bwd_workspace_bytes(const mcamd_act_bwd_desc* d);
 int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, size_t workspace_bytes, void* stream);

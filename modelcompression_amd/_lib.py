@@ -62,7 +62,9 @@ class ActBwdDesc(C.Structure):
                 ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("grad_scale", C.c_float),
                 ("dy_keep", C.c_void_p), ("chan_perm", C.c_void_p), ("y_dtype", C.c_int32),
                 ("overflow", C.c_void_p), ("dy_pad", C.c_int32), ("skip_dead_param_grads", C.c_int32),
-                ("act", C.c_void_p), ("act_ld", C.c_int32), ("act_choff", C.c_int32), ("act_pad", C.c_int32)]
+                ("act", C.c_void_p), ("act_ld", C.c_int32), ("act_choff", C.c_int32), ("act_pad", C.c_int32),
+                ("pool_out", C.c_void_p), ("pool_out_ld", C.c_int32), ("pool_out_choff", C.c_int32),
+                ("pool_out_pad", C.c_int32)]
 
 
 class FoldDesc(C.Structure):

@@ -326,6 +326,8 @@ struct ActBwdArgs {
     int dy_pw;             // 2: dy in the padded form, 1: shared-halo form
     const half_t* act;     // optional (bn_plain_bwd_act_kernel): the block's stored activation, padded NHWC fp16
     int act_ld, act_choff, act_pw;
+    const half_t* pool_out;  // optional (bn_pool_sums_kernel): the block's POOLED activation, padded NHWC fp16 at H/2 x W/2
+    int pool_out_ld, pool_out_choff, pool_out_pw;
 };
 
 // PHASE 0: per-channel sums of g_z and g_z*xhat -> slab.  PHASE 1: dy -> padded NHWC.
@@ -987,6 +989,151 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_act_kernel(ActBwdArgs a) {
     }
 }
 
+// Pass 0 of a MaxPool block without a second gradient, from the POOLED tensors (mcamd_act_bwd_desc.pool_out).  Only the
+// pooled element of a window has a g_z, so the two sums need that element's activation and nothing of the other three.
+// bn_act_fwd_kernel writes it twice: as the pooled output, sat_half(max of the four unrounded activations), and into the
+// full-resolution copy as the window's strict maximum, sat_half of the same value.  max(av[0..3]) of
+// bn_pool_bwd_act_kernel<0, false> is therefore the pooled value bit for bit (tests/test_bn_pool_sums_gpu.py pins it), and
+// this pass reads pooled G + pooled activation, 4 bytes per window and channel, where that one reads 10.  The terms are
+// the same fp32 values and a thread adds them in the same order (its windows pix, pix + stride, ...; two per loop trip,
+// four 16-byte loads in flight), so at the same grid the slab is bit-equal to that pass's.  conv2 / 5 / 8 at B = 64:
+// 61 -> 22 us per launch, FETCH_SIZE 2.5 : 1.
+// Threads that hold an ill-conditioned channel (act_xhat_source) need z from the saved fp32 y AT THE ARGMAX, which the
+// pooled tensor does not locate: they load the window of the copy and of y as the other kernel does, one window per
+// trip.  A healthy network has no such thread.
+// ACT == false: an engine without the copy (filter compaction) -- pass 0 read the four fp32 y values of a window, 18 bytes
+// with G.  The pooled activation gives xhat = (z - beta) / gamma at fp16 accuracy, the trade bn_plain_bwd_act_kernel made;
+// the ill-conditioned channels take the argmax from the unrounded activations of y, as bn_pool_bwd_kernel<., true, .>.
+struct PoolPos {
+    unsigned pix;
+    int b, ho, wo;
+};
+__device__ __forceinline__ PoolPos pool_pos(unsigned pix, int HoWo, int Wo) {
+    PoolPos p;
+    p.pix = pix;
+    p.b = (int)(pix / (unsigned)HoWo);
+    const int rem = (int)(pix - (unsigned)p.b * (unsigned)HoWo);
+    p.ho = rem / Wo, p.wo = rem - p.ho * Wo;
+    return p;
+}
+// p += s (s.pix pixels, decomposed once), without a division
+__device__ __forceinline__ void pool_pos_step(PoolPos& p, const PoolPos& s, int Ho, int Wo) {
+    p.pix += s.pix;
+    p.wo += s.wo;
+    if (p.wo >= Wo) p.wo -= Wo, ++p.ho;
+    p.ho += s.ho;
+    if (p.ho >= Ho) p.ho -= Ho, ++p.b;
+    p.b += s.b;
+}
+// z of the argmax element from the saved y, for the ill-conditioned channels of one window (one image row of the window at
+// a time: 32 values in flight)
+template <bool ACT>
+__device__ __forceinline__ void pool_sums_z_from_y(const ActBwdArgs& a, const PoolPos& p, int c8, const bool (&usey)[8],
+                                                   const float (&sc)[8], const float (&sh)[8], float (&z)[8]) {
+    const half_t* ap = ACT ? a.act + pad_off(p.b, 2 * p.ho, 2 * p.wo, a.H, a.W, a.act_ld, a.act_pw) + a.act_choff + c8 : nullptr;
+    const long long arow = (long long)(a.W + a.act_pw) * a.act_ld;
+    const float* yf = (const float*)a.y + (((long long)p.b * a.H + 2 * p.ho) * a.W + 2 * p.wo) * a.y_ld + a.y_choff + c8;
+    const long long yrow = (long long)a.W * a.y_ld;
+    float best[8], ys[8];
+#pragma unroll 1
+    for (int r = 0; r < 2; ++r) {
+        float av[2][8], yv[2][8];
+        loadf8(yf + r * yrow, yv[0]);
+        loadf8(yf + r * yrow + a.y_ld, yv[1]);
+        if (ACT) {
+            load8(ap + r * arow, av[0]);
+            load8(ap + r * arow + a.act_ld, av[1]);
+        } else {                                         // no copy: the unrounded activations, as bn_pool_bwd_kernel<., true, .>
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const float zk = yv[k][i] * sc[i] + sh[i];
+                    av[k][i] = zk > 0.f ? zk : zk * a.slope;
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            // first maximum in (h, w) scan order of the activations as the forward pass stored them
+            if (r == 0) best[i] = av[0][i], ys[i] = yv[0][i];
+#pragma unroll
+            for (int k = r == 0 ? 1 : 0; k < 2; ++k) {
+                const bool gt = av[k][i] > best[i];
+                best[i] = gt ? av[k][i] : best[i], ys[i] = gt ? yv[k][i] : ys[i];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z[i] = usey[i] ? ys[i] : z[i];
+}
+template <bool ACT>
+__global__ __launch_bounds__(256) void bn_pool_sums_kernel(ActBwdArgs a) {
+    const int CH = a.C >> 3, lg = __ffs(CH) - 1;        // C / 8 is a power of two (check_c)
+    const int c8 = (threadIdx.x & (CH - 1)) * 8;
+    float sc[8], sh[8], mu[8], is[8], off[8], mul[8];
+    bool usey[8];
+    loadf8(a.scale + c8, sc);
+    loadf8(a.shift + c8, sh);
+    loadf8(a.mean + c8, mu);
+    loadf8(a.invstd + c8, is);
+    const bool need_y = act_xhat_source(sc, sh, mu, is, a.y != nullptr, off, mul, usey);
+    float sb[8], sg[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sb[i] = sg[i] = 0.f;
+    const float inv_slope = 1.0f / a.slope;
+    const int Ho = a.H >> 1, Wo = a.W >> 1, HoWo = Ho * Wo;
+    const unsigned npix = (unsigned)(a.items >> lg);                       // pooled pixels
+    const unsigned stride = (gridDim.x * 256u) >> lg;                      // pooled pixels per grid stride
+    PoolPos p0 = pool_pos((blockIdx.x * 256u + threadIdx.x) >> lg, HoWo, Wo);
+    const half_t* pout = a.pool_out + a.pool_out_choff + c8;
+    const half_t* gp = a.g + a.g_choff + c8;
+    auto add = [&](const float (&z)[8], const float (&pv)[8], const float (&gv)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float gz = pv[i] > 0.f ? gv[i] : gv[i] * a.slope;
+            sb[i] += gz;
+            sg[i] += gz * ((z[i] - off[i]) * mul[i]);
+        }
+    };
+    auto window = [&](const PoolPos& p, float (&pv)[8], float (&gv)[8]) {
+        load8(pout + pad_off(p.b, p.ho, p.wo, Ho, Wo, a.pool_out_ld, a.pool_out_pw), pv);
+        load8(gp + (long long)p.pix * a.g_ld, gv);
+    };
+    auto z_of = [&](const float (&pv)[8], float (&z)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) z[i] = pv[i] > 0.f ? pv[i] : pv[i] * inv_slope;
+    };
+    if (need_y) {                                        // a thread with an ill-conditioned channel: one window per trip
+        const PoolPos step = pool_pos(stride, HoWo, Wo);
+        for (; p0.pix < npix; pool_pos_step(p0, step, Ho, Wo)) {
+            float pv[8], gv[8], z[8];
+            window(p0, pv, gv);
+            z_of(pv, z);
+            pool_sums_z_from_y<ACT>(a, p0, c8, usey, sc, sh, z);
+            add(z, pv, gv);
+        }
+    } else {
+        const PoolPos step2 = pool_pos(2u * stride, HoWo, Wo);
+        PoolPos p1 = pool_pos(p0.pix + stride, HoWo, Wo);
+        for (; p1.pix < npix; pool_pos_step(p0, step2, Ho, Wo), pool_pos_step(p1, step2, Ho, Wo)) {
+            float pv0[8], gv0[8], pv1[8], gv1[8], z[8];
+            window(p0, pv0, gv0);
+            window(p1, pv1, gv1);
+            z_of(pv0, z);
+            add(z, pv0, gv0);
+            z_of(pv1, z);
+            add(z, pv1, gv1);
+        }
+        if (p0.pix < npix) {
+            float pv[8], gv[8], z[8];
+            window(p0, pv, gv);
+            z_of(pv, z);
+            add(z, pv, gv);
+        }
+    }
+    block_partials_to_slab(sb, sg, CH, a.slab, a.C);
+}
+
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* slab, int nblocks, int C, double count,
                                                                float inv_scale, float* dgamma, float* dbeta,
                                                                float* coef, const int* perm, int skip_from) {
@@ -1244,12 +1391,28 @@ extern "C" int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, si
         MCAMD_REQUIRE(!d->y || d->y_dtype == 1, "bn_act_bwd: with `act`, `y` is NULL or the fp32 raw output (read for the "
                                                 "channels with |gamma| < %g max(|beta|, 1) only)", (double)BN_ACT_T);
     }
+    // MCAMD_BN_POOL_SUMS_POOLED=0: the sums of a MaxPool block from the full-resolution copy although pool_out is given
+    a.pool_out = MCAMD_ENV_INT("MCAMD_BN_POOL_SUMS_POOLED", 1) != 0 ? (const half_t*)d->pool_out : nullptr;
+    a.pool_out_ld = d->pool_out_ld, a.pool_out_choff = d->pool_out_choff;
+    a.pool_out_pw = d->pool_out_pad ? 1 : 2;
+    if (d->pool_out) {
+        MCAMD_REQUIRE(d->mode == MCAMD_DST_POOL && !d->g2 && (d->act || (d->y && y32)) && d->slope > 0.f,
+                      "bn_act_bwd: `pool_out` (sums from the pooled activation) is for MaxPool blocks without a second gradient, "
+                      "with `act` or an fp32 `y`, and an invertible activation (slope > 0)");
+        MCAMD_REQUIRE(d->pool_out_ld % 8 == 0 && d->pool_out_choff % 8 == 0 && d->pool_out_choff + d->C <= d->pool_out_ld &&
+                          (d->pool_out_pad == 0 || d->pool_out_pad == 1),
+                      "bn_act_bwd: pooled activation slice [%d, %d) does not fit pool_out_ld %d", d->pool_out_choff,
+                      d->pool_out_choff + d->C, d->pool_out_ld);
+    }
     long long pixels = (long long)d->B * d->H * d->W;
     double count = (double)pixels;
     if (d->mode != MCAMD_DST_PLAIN) pixels /= 4;
     a.items = pixels * (d->C / 8);
     int grid = stream_grid(a.items);
+    // MCAMD_BN_BWD_BLOCKS: fewer workgroups than the slab has rows (tests: the same sums in another summation order)
+    const int max_blocks = MCAMD_ENV_INT("MCAMD_BN_BWD_BLOCKS", kBwdBlocks);
     if (grid > kBwdBlocks) grid = kBwdBlocks;
+    if (max_blocks >= 1 && grid > max_blocks) grid = max_blocks;
     hipStream_t st = (hipStream_t)stream;
 #define BWD_INST(MODE_, PHASE)                                                                                     \
     do {                                                                                                          \
@@ -1291,7 +1454,9 @@ extern "C" int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, si
         else if (y32) hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE, true>), dim3(grid), dim3(256), 0, st, a);    \
         else hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE, false>), dim3(grid), dim3(256), 0, st, a);            \
     } while (0)
-    if (pool_fast) POOL_LAUNCH(0);
+    if (pool_fast && a.pool_out && a.act) hipLaunchKernelGGL(bn_pool_sums_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+    else if (pool_fast && a.pool_out) hipLaunchKernelGGL(bn_pool_sums_kernel<false>, dim3(grid), dim3(256), 0, st, a);
+    else if (pool_fast) POOL_LAUNCH(0);
     else if (plain_fast) PLAIN_LAUNCH(0);
     else {
         BWD_LAUNCH(0)

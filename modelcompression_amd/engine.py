@@ -1208,6 +1208,13 @@ class Engine:
             # ... and a MaxPool block's read the full-resolution fp16 copy of its activation (mcamd_act_desc.pool_act)
             if self.pool_act_on and getattr(lay, "act_full", None) is not None:
                 act = dict(act=lay.act_full, act_ld=ops.round_up(lay.cout, 8), act_choff=0, act_pad=self._pad_for(lay.W))
+            if g2 is None and lay.y is not None:
+                # ... and the pass that forms the sums needs the pooled element only: the hi plane of the consumer's
+                # input buffer, a quarter of the copy (mcamd_act_bwd_desc.pool_out) -- also where there is no copy (filter
+                # compaction): 4 bytes per window instead of the 18 of four fp32 y values and G
+                t = lay.out_t
+                act.update(pool_out=self.bufs[t.buf], pool_out_ld=t.ld, pool_out_choff=t.choff,
+                           pool_out_pad=self._pad_for(t.W))
         ops.bn_act_bwd(self.B, lay.H, lay.W, cb, lay.y, lay.cout, 0, lay.scale, lay.shift, lay.mean,
                        lay.invstd, lay.slope, lay.mode, g, g_ld, g_choff, dy, lay.cout_p, 0,
                        dgamma, dbeta, grad_scale, g2, g2_ld, g2_choff,

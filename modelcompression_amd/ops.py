@@ -356,15 +356,20 @@ def bn_act_fwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, ds
 
 def bn_act_bwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, mean, invstd, slope, mode, g, g_ld, g_choff, dy, dy_ld,
                dy_choff, dgamma, dbeta, grad_scale=1.0, g2=None, g2_ld=0, g2_choff=0, workspace=None, dy_keep=None,
-               perm=None, overflow=None, skip_dead_from=0, dy_pad=0, act=None, act_ld=0, act_choff=0, act_pad=0):
+               perm=None, overflow=None, skip_dead_from=0, dy_pad=0, act=None, act_ld=0, act_choff=0, act_pad=0,
+               pool_out=None, pool_out_ld=0, pool_out_choff=0, pool_out_pad=0):
     """`act` (PLAIN blocks): the stored fp16 activation in its padded buffer -- the pre-activation is recovered from it
-    and `y` is not read (mcamd_act_bwd_desc.act)."""
+    and `y` is not read (mcamd_act_bwd_desc.act).
+    `pool_out` (MaxPool blocks with `act` or an fp32 `y`, no g2): the pooled fp16 activation in the consumer's padded buffer -- the pass
+    that forms the per-channel sums reads it instead of the full-resolution copy or `y` (mcamd_act_bwd_desc.pool_out)."""
     d = ActBwdDesc()
     d.skip_dead_param_grads = int(skip_dead_from)
     d.dy_pad = dy_pad
     d.B, d.H, d.W, d.C = B, H, W, C_
     if act is not None:
         d.act, d.act_ld, d.act_choff, d.act_pad = act.data_ptr(), act_ld, act_choff, act_pad
+    if pool_out is not None:
+        d.pool_out, d.pool_out_ld, d.pool_out_choff, d.pool_out_pad = pool_out.data_ptr(), pool_out_ld, pool_out_choff, pool_out_pad
     d.y, d.y_ld, d.y_choff = (y.data_ptr() if y is not None else None), y_ld, y_choff
     d.scale, d.shift, d.mean, d.invstd = scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr()
     d.slope, d.mode = slope, mode
