@@ -235,6 +235,36 @@ int mcamd_pack_sparse24(const mcamd_conv_geom* g, const float* w_oihw, const flo
 int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, const void* wsp, const void* idx,
                             const mcamd_conv_epilogue* epi, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * fp8 (OCP e4m3) quantised inference (an addition beyond the reference; conv_q8.hip, Darknet.precision = "fp8").
+ *   q(v) = round-to-nearest-even to e4m3 of v clamped to [-448, 448].
+ *   activations: bytes q(2 x) in a padded NHWC BYTE buffer [B][H+2][W+2][ld] (or the shared-halo form), halo bytes 0x00;
+ *   weights, per filter f: a = max |w * mask|, (m, x) = frexp(a), e_f = 9 - x if m <= 0.875 else 8 - x (0 for an all-zero
+ *   filter), bytes q(w * mask * 2^e_f): the filter's largest weight lands in (224, 448];
+ *   output: v = leaky(scale_f * 2^-(e_f + 1) * S + shift_f), S = the fp32-accumulated sum of byte products.
+ *   S is an fp32 sum of the exact products (fp16 MFMAs on the bytes converted in registers).  MCAMD_Q8_MFMA=1 multiplies the
+ *   bytes on the block-scaled fp8 MFMA instead: 1.41x instead of 1.01x the fp16 forward of YOLOv2-VOC at B = 128, but that instruction truncates
+ *   inside groups of 8 products and a few 1e-4 of the output bytes come out one code off.
+ * ------------------------------------------------------------------------- */
+/* 1: mcamd_conv_fwd_q8 / mcamd_pack_q8 accept this geometry: stem == 0, ksize 1 or 3, cin % 64 == 0, cout % 8 == 0,
+ * x_wrap == 0, x_f8 == 0, x_ld % 16 == 0, x_choff % 16 == 0, the slice of cin channels inside x_ld.  Any batch size. */
+int32_t mcamd_conv_fwd_q8_ok(const mcamd_conv_geom* g);
+/* Sizes of the packed operands: out[0] = weight bytes (Npad * k*k * cin, Npad = round_up(cout, 256)), out[1] = int32
+ * exponents (Npad). */
+int mcamd_q8_elems(const mcamd_conv_geom* g, int64_t out[2]);
+/* OIHW fp32 master (* mask, may be NULL) -> wq: bytes [Npad][kpos], kpos(t, c) = (c / 64) * k*k*64 + t * 64 + c % 64;
+ * wexp: int32 [Npad] (e_f; pad rows: zero bytes, exponent 0).  Exponents are computed on the device. */
+int mcamd_pack_q8(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wq, int32_t* wexp, void* stream);
+/* The quantised block: epilogue mode MCAMD_EPI_PAD_F16 only, dst_mode PLAIN / POOL / REORG and y2 as mcamd_conv_fwd.
+ * y_f8 / y2_f8 != 0: that destination is a padded NHWC BYTE buffer and receives q(2 v) (y_ld / y_choff count bytes);
+ * 0: fp16 as mcamd_conv_fwd writes it.  Both `pad` forms of x. */
+int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
+                      const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream);
+/* The cast pass of an fp16 -> fp8 edge: fp16 [pixels][src_ld] channels [src_choff, +C) -> bytes q(2 x) [pixels][dst_ld]
+ * channels [dst_choff, +C); C, the leading dimensions and offsets multiples of 8.  Halo pixels are pixels like any other. */
+int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst, int32_t dst_ld,
+                  int32_t dst_choff, void* stream);
+
 /* dx = conv_transpose(dy, w) -- autograd's input gradient of the same call.
  * `dy` is padded NHWC fp16 [B][H+2][W+2][dy_ld] (zero halo); g->cin/cout keep their forward
  * meaning; the result has g->cin channels.  epi->mode 0 (fp16 [M][y_ld]) or 1 (fp32 NCHW). */

@@ -22,6 +22,7 @@ SOURCES = {
     "conv_igemm.hip": [],
     "conv_igemm_pp.hip": [],
     "conv_sparse.hip": [],
+    "conv_q8.hip": [],
     "conv_stem.hip": [],
     "conv_stem_block.hip": [],
     "conv_stem_f32.hip": [],

@@ -626,6 +626,68 @@ extern "C" int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, 
     return mcamd_sparse24_launch(a, idx, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------
+// fp8 (e4m3) quantised inference (conv_q8.hip; an addition beyond the reference)
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_q8_ok(const mcamd_conv_geom* g) {
+    if (!g || g->stem || g->x_wrap != 0 || g->x_f8 != 0 || (g->ksize != 1 && g->ksize != 3)) return 0;
+    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->cin <= 0 || g->cout <= 0) return 0;
+    if (g->cin % 64 != 0 || g->cout % 8 != 0 || (long long)g->B * g->H * g->W >= (1ll << 31)) return 0;
+    if (g->pad != 0 && g->pad != 1) return 0;
+    if (g->x_ld % 16 != 0 || g->x_choff % 16 != 0 || g->x_choff < 0 || g->x_choff + g->cin > g->x_ld) return 0;
+    return 1;
+}
+
+extern "C" int mcamd_q8_elems(const mcamd_conv_geom* g, int64_t out[2]) {
+    MCAMD_REQUIRE(g && out, "q8_elems: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_ok(g), "q8_elems: geometry has no fp8 form (mcamd_conv_fwd_q8_ok)");
+    const long long npad = round_up_int(g->cout, 256);
+    out[0] = npad * ntaps_of(g) * g->cin;
+    out[1] = npad;
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_pack_q8(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wq, int32_t* wexp,
+                             void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "pack_q8: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_pack_q8(&g_, w_oihw, mask_oihw, wq, wexp, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_ok(g), "pack_q8: geometry has no fp8 form (mcamd_conv_fwd_q8_ok)");
+    MCAMD_REQUIRE(w_oihw && wq && wexp, "pack_q8: null pointer");
+    return mcamd_pack_q8_launch(w_oihw, mask_oihw, wq, wexp, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
+                                 const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_q8(&g_, x8, wq, wexp, &e_, y_f8, y2_f8, s); });
+    }
+    if (check_geom(g, "conv_fwd_q8")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_ok(g), "conv_fwd_q8: geometry has no fp8 form (mcamd_conv_fwd_q8_ok)");
+    MCAMD_REQUIRE(x8 && wq && wexp, "conv_fwd_q8: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x8, wq, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    return mcamd_conv_q8_launch(a, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst,
+                             int32_t dst_ld, int32_t dst_choff, void* stream) {
+    if (mcamd_recording())
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_cast_q8(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, s); });
+    MCAMD_REQUIRE(src && dst && pixels > 0 && C > 0, "cast_q8: null pointer / empty");
+    MCAMD_REQUIRE(C % 8 == 0 && src_ld % 8 == 0 && src_choff % 8 == 0 && dst_ld % 8 == 0 && dst_choff % 8 == 0 &&
+                      src_choff >= 0 && dst_choff >= 0 && src_choff + C <= src_ld && dst_choff + C <= dst_ld,
+                  "cast_q8: channel slices must be multiples of 8 inside their leading dimensions");
+    return mcamd_cast_q8_launch(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, (hipStream_t)stream);
+}
+
 extern "C" int mcamd_conv_dgrad(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff,
                                 const void* wp_dgrad, const mcamd_conv_epilogue* epi, void* stream) {
     if (mcamd_recording()) {

@@ -1,0 +1,467 @@
+// fp8 (OCP e4m3) implicit-GEMM convolution forward for gfx950 (MI355X), inference epilogue (an addition beyond the
+// reference: post-training quantised inference, Darknet.precision = "fp8").
+//
+//   S[n][m] = sum_{tap, c} W8[n][kpos(tap, c)] * X8[pixel(m) + tap][c]        (fp32 accumulation of exact products)
+//   v       = leaky(scale[n] * 2^-(e[n] + 1) * S + shift[n])
+//
+// X8 = e4m3(2 x) bytes in a padded NHWC BYTE buffer (halo bytes 0x00), W8 = e4m3(w * 2^e[n]) with one exponent per
+// filter (mcamd_pack_q8 below).  The MFMA: by default v_mfma_f32_32x32x16_f16 on the bytes converted to fp16 in registers
+// (byte-exact against the contract), or v_mfma_scale_f32_32x32x64_f8f6f4 with both e8m0 scales 1.0 (MCAMD_Q8_MFMA=1: half
+// the MFMA time, not byte-exact; see conv_q8_kernel).  The power of two goes into the epilogue's per-filter scale (exact).
+// As in conv_sparse.hip the weights are the A operand (rows = output channels)
+// and the pixels the columns, so that a lane's four accumulator rows are four consecutive channels of one pixel: one
+// 32-bit word of output bytes.
+//
+// Operand form: K order [channel block of 64][tap][64 channels]; one K chunk = 64 k = one 64-byte LDS row per weight row /
+// pixel, staged by global_load_lds_dwordx4 (source address swizzled as in conv_igemm.hip).  Lane (r, h) of an MFMA reads
+// bytes [16 h, 16 h + 16) and [32 + 16 h, 32 + 16 h + 16) of row r for BOTH operands: a k permutation common to A and B
+// (tools/f8_probe.hip; the F8 phase of conv_igemm_pp.hip reads the same way).  Against the fp16 kernels a chunk carries
+// twice the k per staged byte (and, with the fp8 MFMA, per MFMA cycle).
+//
+// Epilogue: the tile is laid down in LDS as [pixel][channel] in the format of each destination -- e4m3(2 v) bytes for a
+// destination an fp8 block reads (ONE rounding from fp32), fp16 otherwise -- and stored PLAIN / POOL (+ the optional
+// full-resolution copy y2) / REORG as epi_pool.h does for fp16.  MaxPool of bytes is taken on the order-preserving key
+// of the code (q is monotone: the maximum of the bytes is the byte of the maximum; -0 sorts below +0).
+#include "kernels.h"
+#include "epi_pool.h"
+
+namespace {
+
+typedef int i32x8_t __attribute__((ext_vector_type(8)));
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef int i32x2_t __attribute__((ext_vector_type(2)));
+
+template <int N>
+__device__ __forceinline__ void q8_wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// e4m3(2 v) of four values, clamped to +-448 first (the conversion returns NaN above the format's maximum)
+__device__ __forceinline__ int q8_bytes4(const float* v) {
+    float c[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) c[e] = fminf(fmaxf(v[e] * 2.f, -448.f), 448.f);
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
+    return __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], w, true);
+}
+
+// order-preserving key of four e4m3 codes (unsigned byte order = value order, -0 below +0) and back
+__device__ __forceinline__ unsigned q8_key(unsigned b) { return b ^ ((((b >> 7) & 0x01010101u) * 0xffu) | 0x80808080u); }
+__device__ __forceinline__ unsigned q8_unkey(unsigned k) { return k ^ ((((~k >> 7) & 0x01010101u) * 0xffu) | 0x80808080u); }
+__device__ __forceinline__ unsigned q8_max4(unsigned a, unsigned b) {
+    unsigned r = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const unsigned x = (a >> (8 * e)) & 0xffu, y = (b >> (8 * e)) & 0xffu;
+        r |= (x > y ? x : y) << (8 * e);
+    }
+    return r;
+}
+
+// padded NHWC element offset of pixel (b, h, w) of an H x W image, ld channels per pixel
+__device__ __forceinline__ long long q8_pix(int b, int h, int w, int H, int W, int ld) {
+    return (((long long)b * (H + 2) + h + 1) * (W + 2) + w + 1) * ld;
+}
+
+// 8 channels of one tile row to one destination in its format: T = 1 byte (from the byte tile) or 2 (from the fp16 tile)
+__device__ __forceinline__ void q8_put8(void* y, bool f8, long long off, const char* bt, const half_t* ht, int tile_off) {
+    if (f8) *(i32x2_t*)((char*)y + off) = *(const i32x2_t*)(bt + tile_off);
+    else *(h8_t*)((half_t*)y + off) = *(const h8_t*)(ht + tile_off);
+}
+
+// eight e4m3 codes -> eight fp16 values (exact: every e4m3 value is an fp16 value)
+__device__ __forceinline__ h8_t q8_to_f16(int lo, int hi) {
+    const h2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true);
+    const h2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true);
+    const h4_t a = __builtin_shufflevector(p0, p1, 0, 1, 2, 3), b = __builtin_shufflevector(p2, p3, 0, 1, 2, 3);
+    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+}  // namespace
+
+// F8MFMA = false (the default): the staged bytes are converted to fp16 in registers and multiplied by
+// v_mfma_f32_32x32x16_f16, whose sum of the (exact) products is an fp32 sum -- the arithmetic of the contract, byte for
+// byte.  F8MFMA = true (MCAMD_Q8_MFMA=1): one v_mfma_scale_f32_32x32x64_f8f6f4 per block and chunk, half the MFMA time --
+// but that instruction (and the non-scaled fp8 one) drops products more than ~14 bits below the largest of their group
+// of 8, which flips ~6e-4 of the output bytes to the adjacent code.
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
+void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8) {
+    constexpr int WAVES_N = BNP / WN;
+    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
+    constexpr int BK = 64, CPR = 4;                // 64 e4m3 k per 64-byte LDS row: four 16-byte chunks
+    constexpr int A_SLOTS = BMW * CPR, B_SLOTS = BNP * CPR;
+    constexpr int A_IT = A_SLOTS / NT, B_IT = B_SLOTS / NT;
+    constexpr int TM = WM / 32, TN = WN / 32;
+    constexpr int STAGE_BYTES = (A_SLOTS + B_SLOTS) * 16;
+    constexpr int DPS = A_IT + B_IT;               // DMA instructions per stage and wave
+    static_assert(A_SLOTS % NT == 0 && B_SLOTS % NT == 0, "whole workgroups per DMA round");
+    static_assert(NSTAGE >= 2 && NSTAGE <= 3, "LDS ring depth");
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    // all channel tiles of a pixel tile on one XCD (its activation rows stay in that XCD's L2)
+    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
+    const int nt = jb % a.num_ntiles;
+    const int mt = (jb / a.num_ntiles) * 8 + xcd;
+    if (mt >= a.num_mtiles) return;
+    const int nchunks = a.ktot / BK;
+    const char* xg = (const char*)a.x;             // byte operands: every stride of `a` counts bytes
+    const char* wg = (const char*)a.w;
+
+    long long wbase[A_IT];
+#pragma unroll
+    for (int it = 0; it < A_IT; ++it) {
+        const int slot = it * NT + tid;
+        const int row = slot / CPR, phys = slot % CPR;
+        wbase[it] = (long long)(nt * BMW + row) * a.ktot + (phys ^ swz<CPR>(row)) * 16;   // rows < Npad = round_up(N, 256)
+    }
+    long long xbase[B_IT];
+#pragma unroll
+    for (int it = 0; it < B_IT; ++it) {
+        const int slot = it * NT + tid;
+        const int row = slot / CPR, phys = slot % CPR;
+        int m = mt * BNP + row;
+        if (m > a.M - 1) m = a.M - 1;              // tail columns re-read the last pixel; their results are not stored
+        int b, h, w;
+        if (a.dst_mode != 0) {
+            pooled_pixel(a, m, b, h, w);
+        } else {
+            b = m / a.HW;
+            const int rem = m - b * a.HW;
+            h = rem / a.W;
+            w = rem - h * a.W;
+        }
+        xbase[it] = (long long)b * a.x_img_stride + (long long)h * a.x_row_stride + (long long)w * a.x_ld + a.x_off +
+                    (phys ^ swz<CPR>(row)) * 16;
+    }
+
+    f32x16_t acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    auto stage = [&](int q, int buf) {
+        const int cb = q / a.ntaps, tap = q - cb * a.ntaps;      // one chunk per tap of a 64-channel block
+        const int koff = a.tap_off[tap] + cb * BK;
+        char* sa = smem + buf * STAGE_BYTES;
+        char* sb = sa + A_SLOTS * 16;
+#pragma unroll
+        for (int it = 0; it < A_IT; ++it) glds16(wg + wbase[it] + (long long)q * BK, sa + (it * NT + wave * 64) * 16);
+#pragma unroll
+        for (int it = 0; it < B_IT; ++it) glds16(xg + xbase[it] + koff, sb + (it * NT + wave * 64) * 16);
+    };
+
+    // fragment addresses: row = block row + (lane & 31), 16-byte chunks h and 2 + h of the row (swizzled)
+    const int lrow = lane & 31, hh = lane >> 5;
+    const int SC = 127 * 0x01010101;               // e8m0 1.0 in all four scale bytes
+
+#pragma unroll
+    for (int p = 0; p < NSTAGE - 1; ++p)
+        if (p < nchunks) stage(p, p);
+    int sidx = 0;
+    for (int q = 0; q < nchunks; ++q) {
+        int issued = q + NSTAGE - 1;
+        if (issued > nchunks) issued = nchunks;
+        const int inflight = issued - q - 1;
+        if (NSTAGE == 2 || inflight == 0) q8_wait_vmcnt<0>();
+        else q8_wait_vmcnt<DPS>();
+        __builtin_amdgcn_s_barrier();              // chunk q landed for every wave; every wave is done with chunk q-1
+        if (q + NSTAGE - 1 < nchunks) {
+            int ns = sidx + NSTAGE - 1;
+            if (ns >= NSTAGE) ns -= NSTAGE;
+            stage(q + NSTAGE - 1, ns);
+        }
+        const char* sa = smem + sidx * STAGE_BYTES;
+        const char* sb = sa + A_SLOTS * 16;
+        sidx = sidx + 1 == NSTAGE ? 0 : sidx + 1;
+        i32x8_t af[TM], bf[TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int row = wm * WM + i * 32 + lrow;
+            const i32x4_t lo = *(const i32x4_t*)(sa + (row * CPR + (hh ^ swz<CPR>(row))) * 16);
+            const i32x4_t hi = *(const i32x4_t*)(sa + (row * CPR + ((2 + hh) ^ swz<CPR>(row))) * 16);
+            af[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int row = wn * WN + j * 32 + lrow;
+            const i32x4_t lo = *(const i32x4_t*)(sb + (row * CPR + (hh ^ swz<CPR>(row))) * 16);
+            const i32x4_t hi = *(const i32x4_t*)(sb + (row * CPR + ((2 + hh) ^ swz<CPR>(row))) * 16);
+            bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+        // Inline assembly as in conv_igemm_pp.hip (through the builtin hipcc does not accumulate in place).  The operands
+        // come from LDS reads the compiler waits for; the blocks are independent; the epilogue's reads are padded below.
+        if constexpr (F8MFMA) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"
+                                 : "+v"(acc[i][j])
+                                 : "v"(af[i]), "v"(bf[j]), "v"(SC), "v"(SC));
+        } else {
+            // four 16-k steps: 8-byte piece s of the lane's 32 bytes of both operands (lanes h = 0 / 1 hold disjoint k)
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                h8_t a16[TM], b16[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) a16[i] = q8_to_f16(af[i][2 * s4], af[i][2 * s4 + 1]);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) b16[j] = q8_to_f16(bf[j][2 * s4], bf[j][2 * s4 + 1]);
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a16[i], b16[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    }
+    if constexpr (F8MFMA) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // last (assembly) MFMA -> VALU reads of the accumulators
+
+    // ------------------------------- epilogue -------------------------------
+    __syncthreads();                               // every wave is done with the stage buffers
+    const bool has2 = a.y2 != nullptr;
+    const bool need_b = y_f8 || (has2 && y2_f8), need_h = !y_f8 || (has2 && !y2_f8);
+    // tile rows are PB = BMW + 8 elements apart: the 32 pixels of a wave's write then fall on 32 different LDS banks (a
+    // pitch of BMW puts them all on one or two)
+    constexpr int PB = BMW + 8;
+    char* bt = smem;                               // [BNP][PB] e4m3 tile
+    half_t* ht = (half_t*)(smem + (need_b ? BNP * PB : 0));   // [BNP][PB] fp16 tile
+    bool sat = false;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {              // accumulator rows 4 g .. 4 g + 3: four consecutive channels
+            const int ch0 = wm * WM + i * 32 + 8 * g + 4 * (lane >> 5);
+            float sc[4], sh[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int n = nt * BMW + ch0 + e;
+                sc[e] = 1.f, sh[e] = 0.f;
+                if (n < a.N) {
+                    sc[e] = ldexpf(a.scale ? a.scale[n] : 1.f, -(wexp[n] + 1));
+                    if (a.shift) sh[e] = a.shift[n];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int pix = wn * WN + j * 32 + (lane & 31);
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = acc[i][j][4 * g + e] * sc[e] + sh[e];
+                    v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope;
+                }
+                if (need_b) *(int*)(bt + pix * PB + ch0) = q8_bytes4(v);
+                if (need_h) {
+                    h4_t hv;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        sat |= fabsf(v[e]) > 65504.f;
+                        hv[e] = (half_t)fminf(fmaxf(v[e], -65504.f), 65504.f);   // saturate, never inf
+                    }
+                    *(h4_t*)(ht + pix * PB + ch0) = hv;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    constexpr int CH = BMW / 8;
+    const int Wo = a.W >> 1, Ho = a.H >> 1, HWo = Ho * Wo;
+    if (a.dst_mode == MCAMD_DST_POOL) {
+        for (int slot = tid; slot < (BNP / 4) * CH; slot += NT) {
+            const int pr = slot / CH, ch = slot - pr * CH;
+            const int idx = mt * (BNP / 4) + pr;   // pooled pixel
+            const int n0 = nt * BMW + ch * 8;
+            if (4 * idx < a.M && n0 < a.N) {
+                const int b = idx / HWo, r = idx - b * HWo;
+                const int ho = r / Wo, wo = r - ho * Wo;
+                const long long off = q8_pix(b, ho, wo, Ho, Wo, a.y_ld) + a.y_choff + n0;
+                if (y_f8) {
+                    unsigned k0 = 0, k1 = 0;       // keys >= 0x00: the first window pixel always replaces them
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const i32x2_t v = *(const i32x2_t*)(bt + (4 * pr + q) * PB + ch * 8);
+                        k0 = q8_max4(k0, q8_key((unsigned)v[0]));
+                        k1 = q8_max4(k1, q8_key((unsigned)v[1]));
+                    }
+                    i32x2_t mx;
+                    mx[0] = (int)q8_unkey(k0), mx[1] = (int)q8_unkey(k1);
+                    *(i32x2_t*)((char*)a.y + off) = mx;
+                } else {
+                    h8_t v[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = *(const h8_t*)(ht + (4 * pr + q) * PB + ch * 8);
+                    h8_t mx;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const half_t m01 = v[0][e] > v[1][e] ? v[0][e] : v[1][e], m23 = v[2][e] > v[3][e] ? v[2][e] : v[3][e];
+                        mx[e] = m01 > m23 ? m01 : m23;
+                    }
+                    *(h8_t*)((half_t*)a.y + off) = mx;
+                }
+                if (has2) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int h = 2 * ho + (q >> 1), w = 2 * wo + (q & 1);
+                        q8_put8(a.y2, y2_f8 != 0, q8_pix(b, h, w, a.H, a.W, a.y2_ld) + a.y2_choff + n0, bt, ht,
+                                (4 * pr + q) * PB + ch * 8);
+                    }
+                }
+            }
+        }
+    } else {
+        for (int slot = tid; slot < BNP * CH; slot += NT) {
+            const int row = slot / CH, ch = slot - row * CH;
+            const int m = mt * BNP + row;
+            const int n0 = nt * BMW + ch * 8;
+            if (m < a.M && n0 < a.N) {
+                long long off;
+                if (a.dst_mode == MCAMD_DST_REORG) {   // out channel = (dy * 2 + dx) * N + n at the pooled pixel
+                    const int idx = m >> 2, q = m & 3;
+                    const int b = idx / HWo, r = idx - b * HWo;
+                    const int ho = r / Wo, wo = r - ho * Wo;
+                    off = q8_pix(b, ho, wo, Ho, Wo, a.y_ld) + a.y_choff + q * a.N + n0;
+                } else {
+                    const int b = m / a.HW;
+                    const int rem = m - b * a.HW;
+                    const int h = rem / a.W;
+                    off = q8_pix(b, h, rem - h * a.W, a.H, a.W, a.y_ld) + a.y_choff + n0;
+                }
+                q8_put8(a.y, y_f8 != 0, off, bt, ht, row * PB + ch * 8);
+            }
+        }
+    }
+    if (sat && a.overflow) atomicOr(a.overflow, 1);
+}
+
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, hipStream_t st) {
+    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
+    constexpr int RING = NSTAGE * (BMW + BNP) * 64;
+    constexpr int PB = BMW + 8;                    // tile row pitch (conv_q8_kernel)
+    constexpr int TILES = BNP * PB * 3;            // a byte and an fp16 tile (destinations of both formats)
+    constexpr int LDS = RING > TILES ? RING : TILES;
+    const bool has2 = a.y2 != nullptr;
+    const bool mixed = (y_f8 || (has2 && y2_f8)) && (!y_f8 || (has2 && !y2_f8));
+    const int lds = mixed ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);
+    auto kern = conv_q8_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
+    MCAMD_LDS_OPT_IN(kern, LDS);
+    a.num_mtiles = (a.M + BNP - 1) / BNP;
+    a.num_ntiles = (a.N + BMW - 1) / BMW;
+    const int grid = (a.num_mtiles + 7) / 8 * 8 * a.num_ntiles;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8);
+    MCAMD_LAUNCH_CHECK("conv_fwd_q8");
+    return MCAMD_OK;
+}
+
+// Tiles as conv_sparse.hip's: 256 channels x 128 pixels (8 waves of 64 x 64) from 256 filters, 128 x 128 (4 waves) from
+// 128, 64 x 128 below; a 3-deep ring of 64-byte rows (72 / 48 / 36 KB: two workgroups per CU).
+// MCAMD_Q8_MFMA: 0 = fp16 MFMAs on converted bytes, 1 = the block-scaled fp8 MFMA.
+int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st) {
+    const int* we = (const int*)wexp;
+    if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {       // the fp8 MFMA: faster, not byte-exact (see the kernel's comment)
+        if (a.N >= 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st);
+        if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st);
+        return conv_q8_launch_t<64, 128, 32, 64, 3, true>(a, we, y_f8, y2_f8, st);
+    }
+    // (no 256-channel tile here: with the converted fragments it needs 136 registers, one workgroup per CU, and measured
+    // 0.87-0.92 x the fp16 kernels on the 256- and 512-filter layers)
+    if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false>(a, we, y_f8, y2_f8, st);
+    return conv_q8_launch_t<64, 128, 32, 64, 3, false>(a, we, y_f8, y2_f8, st);
+}
+
+// ---------------------------------------------------------------------------------------
+// packer: fp32 OIHW master * mask -> e4m3 bytes [Npad][ktot] in the kernel's K order + one exponent per filter
+// ---------------------------------------------------------------------------------------
+// One workgroup per row n < Npad.  a = max |w * mask| of the filter, (m, x) = frexp(a), e = 9 - x if m <= 0.875 else 8 - x
+// (a 2^e in (224, 448]; e = 0 for an all-zero filter): integer steps only, so the host emulation cannot disagree at a
+// power of two.  Then w8 = e4m3(clamp(ldexp(w * mask, e))), four k per thread and store.  Pad rows: zero bytes, e = 0.
+__global__ __launch_bounds__(256) void pack_q8_kernel(const float* __restrict__ w, const float* __restrict__ mask,
+                                                      char* __restrict__ wq, int* __restrict__ wexp, int cout, int cin,
+                                                      int ntaps) {
+    __shared__ float red[256];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int ktot = cin * ntaps;
+    float amax = 0.f;
+    if (n < cout)
+        for (int o = tid; o < ktot; o += 256) {
+            const long long s = (long long)n * ktot + o;
+            amax = fmaxf(amax, fabsf(w[s] * (mask ? mask[s] : 1.f)));
+        }
+    red[tid] = amax;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    amax = red[0];
+    int e = 0;
+    if (amax > 0.f) {
+        int x;
+        const float m = frexpf(amax, &x);
+        e = m <= 0.875f ? 9 - x : 8 - x;
+    }
+    if (tid == 0) wexp[n] = e;
+    for (int k4 = tid; k4 < ktot / 4; k4 += 256) {
+        const int kp = 4 * k4;                                   // position in the packed order [cb][tap][64]
+        const int cb = kp / (ntaps * 64), r = kp - cb * ntaps * 64;
+        const int tap = r / 64, c0 = cb * 64 + (r - tap * 64);
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] = 0.f;
+            if (n < cout) {
+                const long long s = ((long long)n * cin + c0 + i) * ntaps + tap;
+                v[i] = fminf(fmaxf(ldexpf(w[s] * (mask ? mask[s] : 1.f), e), -448.f), 448.f);
+            }
+        }
+        int b = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+        b = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], b, true);
+        *(int*)(wq + (long long)n * ktot + kp) = b;
+    }
+}
+
+int mcamd_pack_q8_launch(const float* w, const float* mask, void* wq, void* wexp, int cout, int cin, int ntaps, hipStream_t st) {
+    hipLaunchKernelGGL(pack_q8_kernel, dim3(round_up_int(cout, 256)), dim3(256), 0, st, w, mask, (char*)wq, (int*)wexp, cout,
+                       cin, ntaps);
+    MCAMD_LAUNCH_CHECK("pack_q8");
+    return MCAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// cast pass of an fp16 -> fp8 edge: fp16 [pixels][src_ld] channels [src_choff, +C) -> e4m3(2 x) bytes [pixels][dst_ld]
+// channels [dst_choff, +C), halo pixels included (0 -> 0x00).  8 channels per thread.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cast_q8_kernel(const half_t* __restrict__ src, long long pixels, int src_ld, int src_choff,
+                                                      int C, char* __restrict__ dst, int dst_ld, int dst_choff) {
+    const int c8 = C / 8;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= pixels * c8) return;
+    const long long p = t / c8;
+    const int c = (int)(t - p * c8) * 8;
+    const h8_t h = *(const h8_t*)(src + p * src_ld + src_choff + c);
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
+    i32x2_t o;
+    o[0] = q8_bytes4(v), o[1] = q8_bytes4(v + 4);
+    *(i32x2_t*)(dst + p * dst_ld + dst_choff + c) = o;
+}
+
+int mcamd_cast_q8_launch(const void* src, long long pixels, int src_ld, int src_choff, int C, void* dst, int dst_ld,
+                         int dst_choff, hipStream_t st) {
+    const long long total = pixels * (C / 8);
+    hipLaunchKernelGGL(cast_q8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const half_t*)src, pixels, src_ld,
+                       src_choff, C, (char*)dst, dst_ld, dst_choff);
+    MCAMD_LAUNCH_CHECK("cast_q8");
+    return MCAMD_OK;
+}

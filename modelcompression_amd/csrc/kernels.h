@@ -99,6 +99,11 @@ int mcamd_igemm_launch(IgemmArgs& a, const ConvRoute& r, hipStream_t st);
 int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);   // conv_sparse.hip: 2:4 weights, mode 2 epilogue
 int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
                                int cin_tap, int kb, hipStream_t st);
+// conv_q8.hip: e4m3 operands (byte strides in `a`), mode 2 epilogue with a format per destination; packer; cast pass
+int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
+int mcamd_pack_q8_launch(const float* w, const float* mask, void* wq, void* wexp, int cout, int cin, int ntaps, hipStream_t st);
+int mcamd_cast_q8_launch(const void* src, long long pixels, int src_ld, int src_choff, int C, void* dst, int dst_ld,
+                         int dst_choff, hipStream_t st);
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps);
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);

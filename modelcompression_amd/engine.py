@@ -140,14 +140,22 @@ class Engine:
         multiply, ~2^-21 operand precision), activations are stored as hi | lo pairs and the raw conv output as fp32;
         "mixed" -- split operands except on the costliest blocks that the 1e-3 logit budget can afford to leave
         plain (MIXED_BUDGET; `for_training`: the budget of the training-mode forward, MIXED_BUDGET_TRAIN, under which the
-        first block is split as well).  The backward pass uses plain fp16 operands in every mode."""
-        if precision not in ("fp16", "fp16x3", "mixed"):
-            raise McamdError("precision must be 'fp16', 'fp16x3' or 'mixed' (got %r)" % (precision,))
+        first block is split as well).  The backward pass uses plain fp16 operands in every mode.
+        "fp8" -- inference only: the "fp16" engine with every eligible block on e4m3 activations and weights
+        (csrc/conv_q8.hip, `fp8_layers`, _update_q8); a training-mode forward raises."""
+        if precision not in ("fp16", "fp16x3", "mixed", "fp8"):
+            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed' or 'fp8' (got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision != "fp16"
+        self.precise = precision not in ("fp16", "fp8")
+        # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
+        # when the masks change (_update_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
+        self.q8 = precision == "fp8"
+        self.fp8_layers = []
+        self.qbufs = {}
+        self._q8_keys = None
         self.grad_scale = float(grad_scale)
         self.serial = 0
         self._packed_sig = None
@@ -664,10 +672,15 @@ class Engine:
         if skeys != self._sparse_keys:
             self._update_sparse()
             self._sparse_keys = skeys
+        if self.q8 and mkeys != self._q8_keys:
+            self._update_q8()
+            self._q8_keys = mkeys
         for lay in self.layers:
             mask = lay.conv.mask.contiguous() if lay.conv.mask_flag else None
             if lay.sp_on:
                 ops.pack_sparse24(lay.geom_act, lay.conv.weight.data, mask, lay.wsp, lay.widx)
+            if self.q8 and lay.q8_on:      # e4m3 bytes + one exponent per filter, computed on the device
+                ops.pack_q8(lay.geom_act, lay.conv.weight.data, mask, lay.wq, lay.wexp)
             if lay.stem:
                 ops.pack_weights(lay.geom_act, lay.conv.weight.data, mask, True, False, lay.wp, None, rows=lay.g_rows)
             if getattr(lay, "stem_split", False):          # hi and lo stem packings of the split-operand fused first block
@@ -749,6 +762,88 @@ class Engine:
                 lay.widx = torch.zeros(ni, dtype=torch.int16, device=self.device)
             lay.sp_on = True
             self.sparse_layers.append(lay.li + 1)      # conv number (conv1 = the first block)
+
+    # ------------------------------------------------------------------ fp8 quantised inference
+    def _update_q8(self):
+        """Which blocks run the fp8 forward (called when the masks change): a block does when it is neither the first nor
+        the last one, has a multiple of 64 input channels, takes the fused inference path without filter compaction,
+        folding or a border table, and mcamd_conv_fwd_q8_ok accepts its geometry.  Every other block runs what the "fp16"
+        engine runs.  An activation buffer holds e4m3 bytes when EVERY block that reads it (a concat member can have a
+        reader of its own beside the concat's) and every block that writes into it are fp8 blocks: one format per tensor.
+        Otherwise the buffer stays fp16 and an fp8 block that reads it takes a private byte copy that a cast pass
+        (mcamd_cast_q8) writes in front of it."""
+        self._plan_epoch += 1             # recorded forward plans name the fp16 or the fp8 launch of a block
+        for lay in self.layers:
+            lay.q8_on, lay.q8_y, lay.q8_y2, lay.xq = False, False, False, None
+        self.fp8_layers = []
+        dev = self.device
+        for lay in self.layers:
+            if (lay.li > 0 and not lay.stem and not lay.is_last and lay.cin % 64 == 0 and lay.fold is None
+                    and lay.g_cols is None and lay.g_rows is None and lay.n_act == lay.cout and not lay.pad
+                    and self._fused_eval(lay) and ops.conv_fwd_q8_ok(lay.geom_act)):
+                lay.q8_on = True
+                self.fp8_layers.append(lay.li + 1)     # conv number (conv1 = the first block)
+        writers = {}                      # buffer id -> the blocks that write into it
+        for lay in self.layers:
+            if not lay.is_last:
+                for t in (lay.out_t, lay.out2_t):
+                    if t is not None:
+                        writers.setdefault(t.buf, []).append(lay)
+        readers = {}                      # buffer id -> the blocks that read it (a concat member may have a reader of its own)
+        for lay in self.layers:
+            readers.setdefault(lay.tin.buf, []).append(lay)
+        live = set()
+        for lay in self.layers:
+            if not lay.q8_on:
+                continue
+            nw, ne = ops.q8_elems(lay.geom_act)
+            if getattr(lay, "wq", None) is None or lay.wq.numel() != nw:
+                lay.wq = torch.zeros(nw, dtype=torch.uint8, device=dev)
+                lay.wexp = torch.zeros(ne, dtype=torch.int32, device=dev)
+            t = lay.tin
+            ws = writers.get(t.buf, [])
+            if ws and all(w.q8_on for w in ws) and all(r.q8_on for r in readers[t.buf]):
+                live.add(t.buf)
+                if t.buf not in self.qbufs:
+                    self.qbufs[t.buf] = ops.alloc_padded_q8(self.B, t.H, t.W, t.ld, dev)
+            else:
+                key = (self.B, t.H, t.W, t.ld)
+                if getattr(lay, "_xq_key", None) != key:
+                    lay._xq, lay._xq_key = ops.alloc_padded_q8(self.B, t.H, t.W, t.ld, dev), key
+                lay.xq = lay._xq
+        for b in [b for b in self.qbufs if b not in live]:
+            del self.qbufs[b]
+        for lay in self.layers:
+            if lay.q8_on:
+                lay.q8_y = lay.out_t.buf in self.qbufs
+                lay.q8_y2 = lay.out2_t is not None and lay.out2_t.buf in self.qbufs
+
+    def q8_block_io(self, conv_number):
+        """Debug accessor: what fp8 block `conv_number` read and wrote in the last forward, from the engine's own buffers,
+        as CPU NCHW tensors -- `x8` e4m3 codes of the input; `y` (and `y2`, the full-resolution copy, or None) as codes
+        (uint8) where `y_f8` (`y2_f8`) else fp16 values; `dst` "plain" / "pool" / "reorg"; the epilogue's `scale`, `shift`,
+        `slope`."""
+        lay = self.layers[conv_number - 1]
+        if not getattr(lay, "q8_on", False):
+            raise McamdError("conv%d is not an fp8 block (fp8_layers = %r)" % (conv_number, self.fp8_layers))
+        B = self.B
+
+        def read(buf, f8, t, C):
+            if f8:
+                v = buf[: B * (t.H + 2) * (t.W + 2) * t.ld].view(B, t.H + 2, t.W + 2, t.ld)
+            else:
+                v = ops.padded_view(buf, B, t.H, t.W, t.ld)
+            v = v[:, 1:-1, 1:-1, t.choff:t.choff + C].permute(0, 3, 1, 2).contiguous().cpu()
+            return v if f8 else v.float()
+        t, t2, ti = lay.out_t, lay.out2_t, lay.tin
+        cdst = 4 * lay.cout if lay.mode == L.DST_REORG else lay.cout
+        out = dict(x8=read(lay.xq if lay.xq is not None else self.qbufs[ti.buf], True, ti, lay.cin),
+                   y=read(self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf], lay.q8_y, t, cdst), y_f8=lay.q8_y,
+                   y2=None, y2_f8=lay.q8_y2, dst={L.DST_PLAIN: "plain", L.DST_POOL: "pool", L.DST_REORG: "reorg"}[lay.mode],
+                   scale=lay.scale.cpu(), shift=lay.shift.cpu(), slope=lay.slope)
+        if t2 is not None:
+            out["y2"] = read(self.qbufs[t2.buf] if lay.q8_y2 else self.bufs[t2.buf], lay.q8_y2, t2, lay.cout)
+        return out
 
     # ------------------------------------------------------------------ filter compaction
     def _set_geom_f(self, lay):
@@ -1036,8 +1131,11 @@ class Engine:
                 if not lay.train_ok:
                     raise McamdError("conv block %d: training needs a BN channel count of 8 * (power of two), got %d"
                                      % (lay.index, lay.cout))
+        if training and self.q8:
+            raise McamdError("precision 'fp8' is inference only (there is no fp8 training path): call model.eval() or "
+                             "pick another precision for training")
         mode = None if training else getattr(self.model, "sparse", None)
-        if mode is not None and self.precise:
+        if mode is not None and (self.precise or self.q8):
             raise McamdError("sparse=%r runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r"
                              % (mode, self.precision))
         force = bool(training) or mode != self._sparse_mode
@@ -1157,6 +1255,19 @@ class Engine:
                 ops.bn_coeffs(None, lay.cout, lay.M, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, False,
                               lay.scale, lay.shift, lay.mean, lay.invstd, eps=bn.eps)
                 t, t2 = lay.out_t, lay.out2_t
+                if self.q8 and lay.q8_on:   # e4m3 activations x e4m3 weights (Darknet.precision = "fp8", _update_q8)
+                    x8 = self.qbufs.get(lay.tin.buf)
+                    if lay.xq is not None:  # the fp16 -> fp8 edge: cast pass over the padded input slice
+                        ti, x8 = lay.tin, lay.xq
+                        self._timed('cast', lay, ops.cast_q8, xin, B * (ti.H + 2) * (ti.W + 2), ti.ld, ti.choff, lay.cin,
+                                    x8, ti.ld, ti.choff)
+                    self._timed('fwd', lay, ops.conv_fwd_q8, lay.geom_act, x8, lay.wq, lay.wexp,
+                                self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf], t.ld, t.choff, lay.scale, lay.shift,
+                                lay.slope, dst_mode=lay.mode,
+                                y2=(self.qbufs[t2.buf] if lay.q8_y2 else self.bufs[t2.buf]) if t2 is not None else None,
+                                y2_ld=t2.ld if t2 is not None else 0, y2_choff=t2.choff if t2 is not None else 0,
+                                y_f8=lay.q8_y, y2_f8=lay.q8_y2)
+                    continue
                 if lay.sp_on:       # 2:4 weights on the sparse MFMA (Darknet.sparse, _update_sparse)
                     self._timed('fwd', lay, ops.conv_fwd_sparse24, lay.geom_act, xin, lay.wsp, lay.widx, self.bufs[t.buf], t.ld,
                                 t.choff, lay.scale, lay.shift, lay.slope, dst_mode=lay.mode,

@@ -275,6 +275,10 @@ class Darknet(nn.Module):
         # fp32 end to end (layers.py:59-64, train.py:224-235).  Training in plain fp16 does NOT meet 1e-3 end to end on
         # a random-init network (3.2e-2 at B=64; the fp32 oracle with fp16-rounded storage: 3.7e-2) and is 1.35x faster:
         # `model.precision = "fp16"` / MCAMD_PRECISION=fp16 selects it explicitly (bench.py reports both).
+        # "fp8" (an addition beyond the reference, eval only): post-training quantised inference -- the "fp16" engine with every
+        # eligible block (engine.Engine.fp8_layers: conv3-conv22 of YOLOv2-VOC) on e4m3 activations and weights, fp32
+        # accumulation, no calibration data (csrc/conv_q8.hip; MCAMD_Q8_MFMA picks the MFMA form).  A training-mode
+        # forward raises.
         self.precision = os.environ.get("MCAMD_PRECISION", "auto")
         # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA

@@ -741,3 +741,51 @@ def conv_fwd_sparse24(g, x, wsp, idx, y, y_ld, y_choff=0, scale=None, shift=None
              y2_choff=y2_choff)
     check(L.lib().mcamd_conv_fwd_sparse24(C.byref(g), ptr(x), ptr(wsp), ptr(idx), C.byref(e), stream_ptr()),
           "mcamd_conv_fwd_sparse24")
+
+
+# ----------------------------------------------------------------------------- fp8 (e4m3) quantised inference
+def conv_fwd_q8_ok(g):
+    """Does mcamd_conv_fwd_q8 accept this geometry?  (Shared by the engine and the tests.)"""
+    return bool(L.lib().mcamd_conv_fwd_q8_ok(C.byref(g)))
+
+
+def q8_elems(g):
+    out = (C.c_int64 * 2)()
+    check(L.lib().mcamd_q8_elems(C.byref(g), out), "mcamd_q8_elems")
+    return int(out[0]), int(out[1])
+
+
+def alloc_padded_q8(B, H, W, ld, device):
+    """Zeroed padded-NHWC BYTE buffer [B][H+2][W+2][ld] of e4m3 activations (halo bytes 0x00 = +0), flat."""
+    return torch.zeros(B * (H + 2) * (W + 2) * ld, dtype=torch.uint8, device=device)
+
+
+def pack_q8(g, w, mask=None, out_w=None, out_exp=None):
+    """fp32 OIHW master (* mask) -> (e4m3 weight bytes in the kernel's K order, int32 exponent per filter) (mcamd_pack_q8)."""
+    _need_cuda(w, mask)
+    assert w.dtype == torch.float32 and w.is_contiguous()
+    nw, ne = q8_elems(g)
+    if out_w is None:
+        out_w = torch.empty(nw, dtype=torch.uint8, device=w.device)
+    if out_exp is None:
+        out_exp = torch.empty(ne, dtype=torch.int32, device=w.device)
+    if out_w.numel() < nw or out_exp.numel() < ne:
+        raise L.McamdError("pack_q8: destination too small")
+    check(L.lib().mcamd_pack_q8(C.byref(g), ptr(w), ptr(mask), ptr(out_w), ptr(out_exp), stream_ptr()), "mcamd_pack_q8")
+    return out_w, out_exp
+
+
+def conv_fwd_q8(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
+                y2_choff=0, y_f8=False, y2_f8=False):
+    """The quantised block (mcamd_conv_fwd_q8): e4m3 activations x e4m3 weights, the inference epilogue of conv_fwd_padded
+    with `y` / `y2` written as e4m3 bytes (y_f8 / y2_f8) or fp16."""
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff)
+    check(L.lib().mcamd_conv_fwd_q8(C.byref(g), ptr(x8), ptr(wq), ptr(wexp), C.byref(e), int(bool(y_f8)), int(bool(y2_f8)),
+                                    stream_ptr()), "mcamd_conv_fwd_q8")
+
+
+def cast_q8(src, pixels, src_ld, src_choff, C_, dst, dst_ld, dst_choff=0):
+    """fp16 channel slice of `pixels` pixels -> e4m3(2 x) bytes (mcamd_cast_q8): the fp16 -> fp8 edge of the fp8 engine."""
+    check(L.lib().mcamd_cast_q8(ptr(src), pixels, src_ld, src_choff, C_, ptr(dst), dst_ld, dst_choff, stream_ptr()),
+          "mcamd_cast_q8")
