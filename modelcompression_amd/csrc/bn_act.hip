@@ -189,10 +189,6 @@ __device__ __forceinline__ void store_act2(int pl2, half_t* p, int plane, const 
     else if (pl2 == 2) store_act<2>(p, plane, v, ci);
     else store_act<1>(p, plane, v, ci);
 }
-// offset of pixel (b, h, w) from the buffer pointer; pw = 2: padded NHWC, pw = 1: shared-halo form (include/mcamd.h)
-__device__ __forceinline__ long long pad_off(int b, int h, int w, int H, int W, int ld, int pw = 2) {
-    return (((long long)b * (H + pw) + h + 1) * (W + pw) + w + 1) * ld;
-}
 
 // Border class of pixel (h, w): which 3x3 taps fall into the zero padding (bit 0 top, 1 bottom, 2 left, 3 right).
 __device__ __forceinline__ int border_class(int h, int w, int H, int W) {

@@ -15,6 +15,9 @@ typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
+typedef int i32x8_t __attribute__((ext_vector_type(8)));
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef int i32x2_t __attribute__((ext_vector_type(2)));
 
 #define MCAMD_WAVE 64
 
@@ -79,6 +82,17 @@ __device__ __forceinline__ int mfma32_row(int reg, int lane) { return (reg & 3) 
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+// Counted wait: at most N of this wave's vector-memory operations (LDS-DMA pieces included) still in flight.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// offset of pixel (b, h, w) from the buffer pointer; pw = 2: padded NHWC, pw = 1: shared-halo form (include/mcamd.h)
+__device__ __forceinline__ long long pad_off(int b, int h, int w, int H, int W, int ld, int pw = 2) {
+    return (((long long)b * (H + pw) + h + 1) * (W + pw) + w + 1) * ld;
 }
 
 // XOR swizzle of the 16-byte chunks of an LDS row of CPR chunks (ds_read_b128 operand tiles).

@@ -1,0 +1,230 @@
+// Addressing and epilogues shared by the forward implicit-GEMM kernels (conv_igemm.hip, conv_igemm_pp.hip,
+// conv_sparse.hip, conv_q8.hip): GEMM row -> pixel, the store of a finished LDS tile into the consumer's padded buffer,
+// and the accumulators -> LDS tile step of the two weights-as-A kernels.
+//
+// Inference blocks whose activation pass is fused with MaxPool(2,2) / Reorg(2) (reference src/nets.py:802-821 conv ->
+// BatchNorm -> LeakyReLU -> MaxPool, nets.py:648-667 Reorg): the conv epilogue has applied leaky(acc * scale + shift) and
+// laid the tile [pixel][channel] down in LDS; with the M tile enumerated in POOLED order -- m = 4 * pooled pixel +
+// (dy * 2 + dx) -- four consecutive rows are one 2x2 window, so the pooled output (or the reorg'ed one, or the pooled one
+// plus a full-resolution copy for the route that reads conv13 beside its pool) is written straight into the consumer's
+// padded buffer: the raw output never exists and no activation pass runs.
+#pragma once
+#include "kernels.h"
+
+// row-major pixel index p of images of HW = H * W pixels -> (image b, pixel hw of it) -> (b, h, w)
+__device__ __forceinline__ void split_image(int p, int HW, int& b, int& hw) {
+    b = p / HW;
+    hw = p - b * HW;
+}
+__device__ __forceinline__ void split_pixel(int p, int HW, int W, int& b, int& h, int& w) {
+    int r;
+    split_image(p, HW, b, r);
+    h = r / W;
+    w = r - h * W;
+}
+
+// pixel of GEMM row m: row-major, or in pooled order (four consecutive rows = one 2x2 window)
+__device__ __forceinline__ void tile_pixel(const IgemmArgs& __restrict__ a, bool pooled, int m, int& b, int& h, int& w) {
+    if (pooled) {
+        const int Wo = a.W >> 1, q = m & 3;
+        int ho, wo;
+        split_pixel(m >> 2, (a.H >> 1) * Wo, Wo, b, ho, wo);
+        h = 2 * ho + (q >> 1);
+        w = 2 * wo + (q & 1);
+    } else {
+        split_pixel(m, a.HW, a.W, b, h, w);
+    }
+}
+
+// offset in x (in the units of a's strides) of the top-left tap of GEMM row m; rows past the last pixel re-read it
+// (their results are masked or not stored)
+__device__ __forceinline__ long long tile_x_base(const IgemmArgs& __restrict__ a, bool pooled, int m) {
+    if (m > a.M - 1) m = a.M - 1;
+    int b, h, w;
+    tile_pixel(a, pooled, m, b, h, w);
+    return (long long)b * a.x_img_stride + (long long)h * a.x_row_stride + (long long)w * a.x_ld + a.x_off;
+}
+
+// All channel tiles of a pixel tile (or of a persistent M slot) on one XCD -- its activation rows stay in that XCD's
+// L2: blocks are dealt round-robin to the 8 XCDs.  False for the blocks that pad the grid.
+__device__ __forceinline__ bool xcd_tile(int num_ntiles, int num_slots, int& nt, int& slot) {
+    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
+    nt = jb % num_ntiles;
+    slot = (jb / num_ntiles) * 8 + xcd;
+    return slot < num_slots;
+}
+
+// ---------------------------------------------------------------------------------------
+// Destinations in either format: fp16, or the e4m3 bytes an fp8 block reads
+// ---------------------------------------------------------------------------------------
+// e4m3(2 v) of four values, clamped to +-448 first (the conversion returns NaN above the format's maximum)
+__device__ __forceinline__ int e4m3_bytes4(const float* v) {
+    float c[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) c[e] = fminf(fmaxf(v[e] * 2.f, -448.f), 448.f);
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
+    return __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], w, true);
+}
+
+// order-preserving key of four e4m3 codes (unsigned byte order = value order, -0 below +0) and back: MaxPool of bytes is
+// taken on the key (e4m3 is monotone: the maximum of the bytes is the byte of the maximum)
+__device__ __forceinline__ unsigned e4m3_key(unsigned b) { return b ^ ((((b >> 7) & 0x01010101u) * 0xffu) | 0x80808080u); }
+__device__ __forceinline__ unsigned e4m3_unkey(unsigned k) { return k ^ ((((~k >> 7) & 0x01010101u) * 0xffu) | 0x80808080u); }
+__device__ __forceinline__ unsigned e4m3_max4(unsigned a, unsigned b) {
+    unsigned r = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const unsigned x = (a >> (8 * e)) & 0xffu, y = (b >> (8 * e)) & 0xffu;
+        r |= (x > y ? x : y) << (8 * e);
+    }
+    return r;
+}
+
+// 8 channels of one tile row to one destination in its format: bytes from the byte tile or fp16 from the fp16 tile
+__device__ __forceinline__ void put8(void* y, bool f8, long long off, const char* bt, const half_t* ht, int tile_off) {
+    if (f8) *(i32x2_t*)((char*)y + off) = *(const i32x2_t*)(bt + tile_off);
+    else *(h8_t*)((half_t*)y + off) = *(const h8_t*)(ht + tile_off);
+}
+
+// ---------------------------------------------------------------------------------------
+// The store of a finished tile (MCAMD_EPI_PAD_F16): ROWS pixels x COLS channels in LDS, rows PITCH elements apart, as
+// fp16 (ht) and / or e4m3 bytes (bt), into the padded NHWC destination(s) -- PLAIN, POOL (+ the optional full-resolution
+// copy y2) or REORG by a.dst_mode, each destination in its own format (y_f8 / y2_f8: bytes; the fp16 kernels pass
+// nullptr, false, false and those branches fold away).  Nothing outside the interior pixels x [choff, choff + N) is
+// written.
+// ---------------------------------------------------------------------------------------
+template <int ROWS, int COLS, int PITCH, int NT>
+__device__ __forceinline__ void store_pad_tile(const IgemmArgs& __restrict__ a, const char* bt, const half_t* ht, bool y_f8, bool y2_f8,
+                                               int mt, int nt, int tid) {
+    constexpr int CH = COLS / 8;   // 8-channel pieces per tile row
+    if (a.dst_mode == MCAMD_DST_PLAIN) {
+        for (int slot = tid; slot < ROWS * CH; slot += NT) {
+            const int row = slot / CH, ch = slot - row * CH;
+            const int m = mt * ROWS + row;
+            const int n0 = nt * COLS + ch * 8;
+            if (m < a.M && n0 < a.N) {
+                int b, h, w;
+                split_pixel(m, a.HW, a.W, b, h, w);
+                put8(a.y, y_f8, pad_off(b, h, w, a.H, a.W, a.y_ld) + a.y_choff + n0, bt, ht, row * PITCH + ch * 8);
+            }
+        }
+        return;
+    }
+    const int Wo = a.W >> 1, Ho = a.H >> 1, HWo = Ho * Wo;
+    if (a.dst_mode == MCAMD_DST_POOL) {
+        const bool has2 = a.y2 != nullptr;
+        for (int slot = tid; slot < (ROWS / 4) * CH; slot += NT) {
+            const int pr = slot / CH, ch = slot - pr * CH;
+            const int idx = mt * (ROWS / 4) + pr;   // pooled pixel
+            const int n0 = nt * COLS + ch * 8;
+            if (4 * idx < a.M && n0 < a.N) {
+                int b, ho, wo;
+                split_pixel(idx, HWo, Wo, b, ho, wo);
+                const long long off = pad_off(b, ho, wo, Ho, Wo, a.y_ld) + a.y_choff + n0;
+                if (y_f8) {
+                    unsigned k0 = 0, k1 = 0;       // keys >= 0x00: the first window pixel always replaces them
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const i32x2_t v = *(const i32x2_t*)(bt + (4 * pr + q) * PITCH + ch * 8);
+                        k0 = e4m3_max4(k0, e4m3_key((unsigned)v[0]));
+                        k1 = e4m3_max4(k1, e4m3_key((unsigned)v[1]));
+                    }
+                    i32x2_t mx;
+                    mx[0] = (int)e4m3_unkey(k0), mx[1] = (int)e4m3_unkey(k1);
+                    *(i32x2_t*)((char*)a.y + off) = mx;
+                } else {
+                    h8_t v[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = *(const h8_t*)(ht + (4 * pr + q) * PITCH + ch * 8);
+                    h8_t mx;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const half_t m01 = v[0][e] > v[1][e] ? v[0][e] : v[1][e], m23 = v[2][e] > v[3][e] ? v[2][e] : v[3][e];
+                        mx[e] = m01 > m23 ? m01 : m23;
+                    }
+                    *(h8_t*)((half_t*)a.y + off) = mx;
+                }
+                if (has2) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        put8(a.y2, y2_f8, pad_off(b, 2 * ho + (q >> 1), 2 * wo + (q & 1), a.H, a.W, a.y2_ld) + a.y2_choff + n0,
+                             bt, ht, (4 * pr + q) * PITCH + ch * 8);
+                }
+            }
+        }
+    } else {   // MCAMD_DST_REORG: out channel = (dy * 2 + dx) * N + n at the pooled pixel
+        for (int slot = tid; slot < ROWS * CH; slot += NT) {
+            const int row = slot / CH, ch = slot - row * CH;
+            const int m = mt * ROWS + row;
+            const int n0 = nt * COLS + ch * 8;
+            if (m < a.M && n0 < a.N) {
+                int b, ho, wo;
+                split_pixel(m >> 2, HWo, Wo, b, ho, wo);
+                put8(a.y, y_f8, pad_off(b, ho, wo, Ho, Wo, a.y_ld) + a.y_choff + (m & 3) * a.N + n0, bt, ht, row * PITCH + ch * 8);
+            }
+        }
+    }
+}
+
+// The sibling for MCAMD_EPI_RAW_F16: the fp16 tile [ROWS][COLS] to the raw output [M][y_ld].
+template <int ROWS, int COLS, int NT>
+__device__ __forceinline__ void store_raw_tile(const IgemmArgs& __restrict__ a, const half_t* ct, int mt, int nt, int tid) {
+    constexpr int CH = COLS / 8;   // 16-byte chunks per output row
+    half_t* y = (half_t*)a.y;
+    for (int slot = tid; slot < ROWS * CH; slot += NT) {
+        const int row = slot / CH, ch = slot - row * CH;
+        const int m = mt * ROWS + row;
+        const int n0 = nt * COLS + ch * 8;
+        if (m < a.M && n0 < a.N) *(h8_t*)(y + (long long)m * a.y_ld + a.y_choff + n0) = *(const h8_t*)(ct + row * COLS + ch * 8);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Accumulators -> LDS tile of the weights-as-A kernels (conv_sparse.hip, conv_q8.hip): there the rows of a 32x32 block
+// are output channels and the columns pixels, so a lane's accumulator rows 4 g .. 4 g + 3 are four consecutive channels
+// of one pixel.  leaky(acc * scale_of(n) + shift[n]) goes down as [pixel][channel], rows PITCH elements apart, as e4m3(2 v)
+// bytes (need_b) and / or saturated fp16 (need_h).  Returns whether an fp16 value was clamped.
+// ---------------------------------------------------------------------------------------
+template <int BMW, int PITCH, int WM, int WN, int TM, int TN, class ScaleOf>
+__device__ __forceinline__ bool write_ch_tile(const IgemmArgs& __restrict__ a, const f32x16_t (&acc)[TM][TN], ScaleOf scale_of, bool need_b,
+                                              bool need_h, char* bt, half_t* ht, int nt, int wm, int wn, int lane) {
+    bool sat = false;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int ch0 = wm * WM + i * 32 + 8 * g + 4 * (lane >> 5);
+            float sc[4], sh[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int n = nt * BMW + ch0 + e;
+                sc[e] = 1.f, sh[e] = 0.f;
+                if (n < a.N) {
+                    sc[e] = scale_of(n);
+                    if (a.shift) sh[e] = a.shift[n];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int pix = wn * WN + j * 32 + (lane & 31);
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = acc[i][j][4 * g + e] * sc[e] + sh[e];
+                    v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope;
+                }
+                if (need_b) *(int*)(bt + pix * PITCH + ch0) = e4m3_bytes4(v);
+                if (need_h) {
+                    h4_t hv;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        sat |= fabsf(v[e]) > 65504.f;
+                        hv[e] = (half_t)fminf(fmaxf(v[e], -65504.f), 65504.f);   // saturate, never inf
+                    }
+                    *(h4_t*)(ht + pix * PITCH + ch0) = hv;
+                }
+            }
+        }
+    }
+    return sat;
+}

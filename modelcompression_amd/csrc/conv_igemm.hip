@@ -21,14 +21,9 @@
 // Replaces F.conv2d at reference src/pruning/weightPruning/layers.py:60-64 and its autograd
 // input gradient.
 #include "kernels.h"
-#include "epi_pool.h"
+#include "conv_epi.h"
 #include <stdlib.h>
 
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int BM, int BN, int WM, int WN, int BK, int NSTAGE, int EPI>
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64,
@@ -67,10 +62,7 @@ void igemm_kernel(IgemmArgs a) {
         nt = item / a.num_pslots;
         pslot = item - nt * a.num_pslots;
     } else {
-        const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-        nt = jb % a.num_ntiles;
-        pslot = (jb / a.num_ntiles) * 8 + xcd;
-        if (pslot >= a.num_pslots) return;
+        if (!xcd_tile(a.num_ntiles, a.num_pslots, nt, pslot)) return;
     }
     const int nchunks = a.ktot / BK;
     const int cpt = a.cin_tap / BK;  // chunks per tap
@@ -98,19 +90,8 @@ void igemm_kernel(IgemmArgs a) {
             int slot = it * NT + tid;
             int row = slot / CPR, phys = slot % CPR;
             int logical = phys ^ swz<CPR>(row);
-            int m = mt * BM + row;
-            if (m > a.M - 1) m = a.M - 1;  // tail rows re-read the last pixel; their results are masked
-            int b, h, w;
-            if (EPI == MCAMD_EPI_PAD_F16 && a.dst_mode != 0) {   // pooled order: four consecutive rows = one 2x2 window
-                pooled_pixel(a, m, b, h, w);
-            } else {
-                b = m / a.HW;
-                const int rem = m - b * a.HW;
-                h = rem / a.W;
-                w = rem - h * a.W;
-            }
-            abase[it] = (long long)b * a.x_img_stride + (long long)h * a.x_row_stride + (long long)w * a.x_ld +
-                        a.x_off + logical * 8;
+            // (pooled order when the epilogue pools: four consecutive rows = one 2x2 window)
+            abase[it] = tile_x_base(a, EPI == MCAMD_EPI_PAD_F16 && a.dst_mode != 0, mt * BM + row) + logical * 8;
         }
 
         f32x16_t acc[TM][TN];
@@ -213,8 +194,8 @@ void igemm_kernel(IgemmArgs a) {
                 for (int r = 0; r < 16; ++r) {
                     int m = mt * BM + wm * WM + i * 32 + mfma32_row(r, lane);
                     if (m < a.M) {
-                        int b = m / a.HW;
-                        int hw = m - b * a.HW;
+                        int b, hw;
+                        split_image(m, a.HW, b, hw);
 #pragma unroll
                         for (int j = 0; j < TN; ++j) {
                             int n = nt * BN + wn * WN + j * 32 + (lane & 31);
@@ -283,30 +264,8 @@ void igemm_kernel(IgemmArgs a) {
                     }
             }
             __syncthreads();
-            constexpr int CH = BN / 8;  // 16-byte chunks per output row
-            half_t* y = (half_t*)a.y;
-            if (EPI == MCAMD_EPI_PAD_F16 && a.dst_mode != 0) {
-                store_pad_pooled<BM, BN, NT>(a, ct, mt, nt, tid);
-                continue;
-            }
-            for (int slot = tid; slot < BM * CH; slot += NT) {
-                int row = slot / CH, ch = slot - row * CH;
-                int m = mt * BM + row;
-                int n0 = nt * BN + ch * 8;
-                if (m < a.M && n0 < a.N) {
-                    long long off;
-                    if constexpr (EPI == MCAMD_EPI_PAD_F16) {
-                        int b = m / a.HW;
-                        int rem = m - b * a.HW;
-                        int h = rem / a.W;
-                        int w = rem - h * a.W;
-                        off = (((long long)b * (a.H + 2) + h + 1) * (a.W + 2) + w + 1) * a.y_ld;
-                    } else {
-                        off = (long long)m * a.y_ld;
-                    }
-                    *(h8_t*)(y + off + a.y_choff + n0) = *(const h8_t*)(ct + row * BN + ch * 8);
-                }
-            }
+            if constexpr (EPI == MCAMD_EPI_PAD_F16) store_pad_tile<BM, BN, BN, NT>(a, nullptr, ct, false, false, mt, nt, tid);
+            else store_raw_tile<BM, BN, NT>(a, ct, mt, nt, tid);
         }
     }
 

@@ -46,11 +46,11 @@
 // MFMA time and of staged bytes.  Residual: the e4m3 rounding of the bracket's operands, ~4 % of what plain fp16
 // operands lose (measured per kernel and per block: DESIGN.md 3d).
 //
-// Operand addressing, LDS swizzle (on the DMA source), persistent M tiles per N tile, BatchNorm partial
-// sums and the epilogues are those of conv_igemm.hip.  Replaces F.conv2d at reference
+// Operand addressing, LDS swizzle (on the DMA source), persistent M tiles per N tile, BatchNorm partial sums and the
+// epilogues are those of conv_igemm.hip (row -> pixel and the tile stores: conv_epi.h).  Replaces F.conv2d at reference
 // src/pruning/weightPruning/layers.py:60-64 and its autograd input gradient.
 #include "kernels.h"
-#include "epi_pool.h"
+#include "conv_epi.h"
 #include <stdlib.h>
 
 namespace {
@@ -88,8 +88,6 @@ template <> struct Shape<16> {
     }
 };
 
-typedef int i32x8_t __attribute__((ext_vector_type(8)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 // F8 kernels keep the two k16-step fragments of a 64-byte row as ONE 8-register value from the moment they are read: it is
 // the 32-byte operand of the 64-k fp8 instruction as it stands, and its halves are the operands of the fp16 instruction
 // (built at the use instead -- concatenating two h8_t values in the matrix phase -- hipcc copies every fragment: +56
@@ -101,11 +99,6 @@ __device__ __forceinline__ i32x8_t read_pair(const char* p0, const char* p1) {
 __device__ __forceinline__ h8_t half_of(i32x8_t v, int s) {
     const i32x4_t q = s ? __builtin_shufflevector(v, v, 4, 5, 6, 7) : __builtin_shufflevector(v, v, 0, 1, 2, 3);
     return __builtin_bit_cast(h8_t, q);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 }  // namespace
@@ -138,20 +131,18 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
     // counted waits: "at most n chunks' worth of this wave's DMA instructions still in flight"
     auto wait_chunks = [&](int n) {
         if (RAGGED && group == 1) {
-            if (n == 2) wait_vm<2 * (DPC - 1)>();
-            else if (n == 1) wait_vm<DPC - 1>();
-            else wait_vm<0>();
+            if (n == 2) wait_vmcnt<2 * (DPC - 1)>();
+            else if (n == 1) wait_vmcnt<DPC - 1>();
+            else wait_vmcnt<0>();
         } else {
-            if (n == 2) wait_vm<2 * DPC>();
-            else if (n == 1) wait_vm<DPC>();
-            else wait_vm<0>();
+            if (n == 2) wait_vmcnt<2 * DPC>();
+            else if (n == 1) wait_vmcnt<DPC>();
+            else wait_vmcnt<0>();
         }
     };
 
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nt = jb % a.num_ntiles;
-    const int pslot = (jb / a.num_ntiles) * 8 + xcd;
-    if (pslot >= a.num_pslots) return;
+    int nt, pslot;
+    if (!xcd_tile(a.num_ntiles, a.num_pslots, nt, pslot)) return;
     const int nchunks = a.ktot / BK;
     const int cpt = a.cin_tap / BK;
 
@@ -174,19 +165,8 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
         for (int it = 0; it < A_IT; ++it) {
             const int slot = it * NT + tid;
             const int row = (slot / CPR) % BM, phys = slot % CPR;   // (slots beyond the tile, BM = 192: never issued)
-            int m = mt * BM + row;
-            if (m > a.M - 1) m = a.M - 1;   // tail rows re-read the last pixel; their results are masked
-            int b, h, w;
-            if (EPI == MCAMD_EPI_PAD_F16 && a.dst_mode != 0) {   // pooled order: four consecutive rows = one 2x2 window
-                pooled_pixel(a, m, b, h, w);
-            } else {
-                b = m / a.HW;
-                const int rem = m - b * a.HW;
-                h = rem / a.W;
-                w = rem - h * a.W;
-            }
-            abase[it] = (long long)b * a.x_img_stride + (long long)h * a.x_row_stride + (long long)w * a.x_ld + a.x_off +
-                        (phys ^ SH::swz4(row)) * 8;
+            // (pooled order when the epilogue pools: four consecutive rows = one 2x2 window)
+            abase[it] = tile_x_base(a, EPI == MCAMD_EPI_PAD_F16 && a.dst_mode != 0, mt * BM + row) + (phys ^ SH::swz4(row)) * 8;
         }
 
         acc_v acc[TM][TN];
@@ -365,7 +345,9 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
         if (group == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last barrier: both groups aligned again
         if constexpr (F8) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // last (assembly) MFMA -> VALU reads of the accumulators
 
-        // ------------------------------- epilogue (as conv_igemm.hip) -------------------------------
+        // ------------------------------- epilogue -------------------------------
+        // (conv_igemm.hip's three forms and statistics tail on the rows of Shape<MS>.  Both stay in the kernels: as functions
+        // shared with igemm_kernel hipcc compiles the training instances differently)
         if constexpr (EPI == MCAMD_EPI_NCHW_F32) {
             float* y = (float*)a.y;
 #pragma unroll
@@ -374,8 +356,8 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
                 for (int r = 0; r < AR; ++r) {
                     const int m = mt * BM + wm * WM + i * MS + SH::rowof(r, lane);
                     if (m < a.M) {
-                        const int b = m / a.HW;
-                        const int hw = m - b * a.HW;
+                        int b, hw;
+                        split_image(m, a.HW, b, hw);
 #pragma unroll
                         for (int j = 0; j < TN; ++j) {
                             const int n = nt * BN + wn * WN + j * MS + (lane & (MS - 1));
@@ -443,30 +425,8 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
                     }
             }
             __syncthreads();
-            constexpr int CH = BN / 8;
-            half_t* y = (half_t*)a.y;
-            if (EPI == MCAMD_EPI_PAD_F16 && a.dst_mode != 0) {
-                store_pad_pooled<BM, BN, NT>(a, ct, mt, nt, tid);
-                continue;
-            }
-            for (int slot = tid; slot < BM * CH; slot += NT) {
-                const int row = slot / CH, ch = slot - row * CH;
-                const int m = mt * BM + row;
-                const int n0 = nt * BN + ch * 8;
-                if (m < a.M && n0 < a.N) {
-                    long long off;
-                    if constexpr (EPI == MCAMD_EPI_PAD_F16) {
-                        const int b = m / a.HW;
-                        const int rem = m - b * a.HW;
-                        const int h = rem / a.W;
-                        const int w = rem - h * a.W;
-                        off = (((long long)b * (a.H + 2) + h + 1) * (a.W + 2) + w + 1) * a.y_ld;
-                    } else {
-                        off = (long long)m * a.y_ld;
-                    }
-                    *(h8_t*)(y + off + a.y_choff + n0) = *(const h8_t*)(ct + row * BN + ch * 8);
-                }
-            }
+            if constexpr (EPI == MCAMD_EPI_PAD_F16) store_pad_tile<BM, BN, BN, NT>(a, nullptr, ct, false, false, mt, nt, tid);
+            else store_raw_tile<BM, BN, NT>(a, ct, mt, nt, tid);
         }
     }
 

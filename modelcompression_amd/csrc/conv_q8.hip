@@ -19,55 +19,14 @@
 // twice the k per staged byte (and, with the fp8 MFMA, per MFMA cycle).
 //
 // Epilogue: the tile is laid down in LDS as [pixel][channel] in the format of each destination -- e4m3(2 v) bytes for a
-// destination an fp8 block reads (ONE rounding from fp32), fp16 otherwise -- and stored PLAIN / POOL (+ the optional
-// full-resolution copy y2) / REORG as epi_pool.h does for fp16.  MaxPool of bytes is taken on the order-preserving key
-// of the code (q is monotone: the maximum of the bytes is the byte of the maximum; -0 sorts below +0).
+// destination an fp8 block reads (ONE rounding from fp32), fp16 otherwise (conv_epi.h: write_ch_tile) -- and stored PLAIN /
+// POOL (+ the optional full-resolution copy y2) / REORG by the store every forward implicit-GEMM kernel uses
+// (store_pad_tile).  MaxPool of bytes is taken on the order-preserving key of the code (q is monotone: the maximum of the
+// bytes is the byte of the maximum; -0 sorts below +0).
 #include "kernels.h"
-#include "epi_pool.h"
+#include "conv_epi.h"
 
 namespace {
-
-typedef int i32x8_t __attribute__((ext_vector_type(8)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef int i32x2_t __attribute__((ext_vector_type(2)));
-
-template <int N>
-__device__ __forceinline__ void q8_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// e4m3(2 v) of four values, clamped to +-448 first (the conversion returns NaN above the format's maximum)
-__device__ __forceinline__ int q8_bytes4(const float* v) {
-    float c[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c[e] = fminf(fmaxf(v[e] * 2.f, -448.f), 448.f);
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], w, true);
-}
-
-// order-preserving key of four e4m3 codes (unsigned byte order = value order, -0 below +0) and back
-__device__ __forceinline__ unsigned q8_key(unsigned b) { return b ^ ((((b >> 7) & 0x01010101u) * 0xffu) | 0x80808080u); }
-__device__ __forceinline__ unsigned q8_unkey(unsigned k) { return k ^ ((((~k >> 7) & 0x01010101u) * 0xffu) | 0x80808080u); }
-__device__ __forceinline__ unsigned q8_max4(unsigned a, unsigned b) {
-    unsigned r = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const unsigned x = (a >> (8 * e)) & 0xffu, y = (b >> (8 * e)) & 0xffu;
-        r |= (x > y ? x : y) << (8 * e);
-    }
-    return r;
-}
-
-// padded NHWC element offset of pixel (b, h, w) of an H x W image, ld channels per pixel
-__device__ __forceinline__ long long q8_pix(int b, int h, int w, int H, int W, int ld) {
-    return (((long long)b * (H + 2) + h + 1) * (W + 2) + w + 1) * ld;
-}
-
-// 8 channels of one tile row to one destination in its format: T = 1 byte (from the byte tile) or 2 (from the fp16 tile)
-__device__ __forceinline__ void q8_put8(void* y, bool f8, long long off, const char* bt, const half_t* ht, int tile_off) {
-    if (f8) *(i32x2_t*)((char*)y + off) = *(const i32x2_t*)(bt + tile_off);
-    else *(h8_t*)((half_t*)y + off) = *(const h8_t*)(ht + tile_off);
-}
 
 // eight e4m3 codes -> eight fp16 values (exact: every e4m3 value is an fp16 value)
 __device__ __forceinline__ h8_t q8_to_f16(int lo, int hi) {
@@ -104,11 +63,8 @@ void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    // all channel tiles of a pixel tile on one XCD (its activation rows stay in that XCD's L2)
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nt = jb % a.num_ntiles;
-    const int mt = (jb / a.num_ntiles) * 8 + xcd;
-    if (mt >= a.num_mtiles) return;
+    int nt, mt;
+    if (!xcd_tile(a.num_ntiles, a.num_mtiles, nt, mt)) return;
     const int nchunks = a.ktot / BK;
     const char* xg = (const char*)a.x;             // byte operands: every stride of `a` counts bytes
     const char* wg = (const char*)a.w;
@@ -125,19 +81,7 @@ void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_
     for (int it = 0; it < B_IT; ++it) {
         const int slot = it * NT + tid;
         const int row = slot / CPR, phys = slot % CPR;
-        int m = mt * BNP + row;
-        if (m > a.M - 1) m = a.M - 1;              // tail columns re-read the last pixel; their results are not stored
-        int b, h, w;
-        if (a.dst_mode != 0) {
-            pooled_pixel(a, m, b, h, w);
-        } else {
-            b = m / a.HW;
-            const int rem = m - b * a.HW;
-            h = rem / a.W;
-            w = rem - h * a.W;
-        }
-        xbase[it] = (long long)b * a.x_img_stride + (long long)h * a.x_row_stride + (long long)w * a.x_ld + a.x_off +
-                    (phys ^ swz<CPR>(row)) * 16;
+        xbase[it] = tile_x_base(a, a.dst_mode != 0, mt * BNP + row) + (phys ^ swz<CPR>(row)) * 16;
     }
 
     f32x16_t acc[TM][TN];
@@ -171,8 +115,8 @@ void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_
         int issued = q + NSTAGE - 1;
         if (issued > nchunks) issued = nchunks;
         const int inflight = issued - q - 1;
-        if (NSTAGE == 2 || inflight == 0) q8_wait_vmcnt<0>();
-        else q8_wait_vmcnt<DPS>();
+        if (NSTAGE == 2 || inflight == 0) wait_vmcnt<0>();
+        else wait_vmcnt<DPS>();
         __builtin_amdgcn_s_barrier();              // chunk q landed for every wave; every wave is done with chunk q-1
         if (q + NSTAGE - 1 < nchunks) {
             int ns = sidx + NSTAGE - 1;
@@ -235,111 +179,12 @@ void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_
     constexpr int PB = BMW + 8;
     char* bt = smem;                               // [BNP][PB] e4m3 tile
     half_t* ht = (half_t*)(smem + (need_b ? BNP * PB : 0));   // [BNP][PB] fp16 tile
-    bool sat = false;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {              // accumulator rows 4 g .. 4 g + 3: four consecutive channels
-            const int ch0 = wm * WM + i * 32 + 8 * g + 4 * (lane >> 5);
-            float sc[4], sh[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int n = nt * BMW + ch0 + e;
-                sc[e] = 1.f, sh[e] = 0.f;
-                if (n < a.N) {
-                    sc[e] = ldexpf(a.scale ? a.scale[n] : 1.f, -(wexp[n] + 1));
-                    if (a.shift) sh[e] = a.shift[n];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int pix = wn * WN + j * 32 + (lane & 31);
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = acc[i][j][4 * g + e] * sc[e] + sh[e];
-                    v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope;
-                }
-                if (need_b) *(int*)(bt + pix * PB + ch0) = q8_bytes4(v);
-                if (need_h) {
-                    h4_t hv;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        sat |= fabsf(v[e]) > 65504.f;
-                        hv[e] = (half_t)fminf(fmaxf(v[e], -65504.f), 65504.f);   // saturate, never inf
-                    }
-                    *(h4_t*)(ht + pix * PB + ch0) = hv;
-                }
-            }
-        }
-    }
+    // the per-filter scale with the power of two of the packed weights and of the 2 x activations taken back (exact)
+    const float* scale = a.scale;
+    const bool sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale, wexp](int n) { return ldexpf(scale ? scale[n] : 1.f, -(wexp[n] + 1)); },
+                                                    need_b, need_h, bt, ht, nt, wm, wn, lane);
     __syncthreads();
-    constexpr int CH = BMW / 8;
-    const int Wo = a.W >> 1, Ho = a.H >> 1, HWo = Ho * Wo;
-    if (a.dst_mode == MCAMD_DST_POOL) {
-        for (int slot = tid; slot < (BNP / 4) * CH; slot += NT) {
-            const int pr = slot / CH, ch = slot - pr * CH;
-            const int idx = mt * (BNP / 4) + pr;   // pooled pixel
-            const int n0 = nt * BMW + ch * 8;
-            if (4 * idx < a.M && n0 < a.N) {
-                const int b = idx / HWo, r = idx - b * HWo;
-                const int ho = r / Wo, wo = r - ho * Wo;
-                const long long off = q8_pix(b, ho, wo, Ho, Wo, a.y_ld) + a.y_choff + n0;
-                if (y_f8) {
-                    unsigned k0 = 0, k1 = 0;       // keys >= 0x00: the first window pixel always replaces them
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const i32x2_t v = *(const i32x2_t*)(bt + (4 * pr + q) * PB + ch * 8);
-                        k0 = q8_max4(k0, q8_key((unsigned)v[0]));
-                        k1 = q8_max4(k1, q8_key((unsigned)v[1]));
-                    }
-                    i32x2_t mx;
-                    mx[0] = (int)q8_unkey(k0), mx[1] = (int)q8_unkey(k1);
-                    *(i32x2_t*)((char*)a.y + off) = mx;
-                } else {
-                    h8_t v[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = *(const h8_t*)(ht + (4 * pr + q) * PB + ch * 8);
-                    h8_t mx;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const half_t m01 = v[0][e] > v[1][e] ? v[0][e] : v[1][e], m23 = v[2][e] > v[3][e] ? v[2][e] : v[3][e];
-                        mx[e] = m01 > m23 ? m01 : m23;
-                    }
-                    *(h8_t*)((half_t*)a.y + off) = mx;
-                }
-                if (has2) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int h = 2 * ho + (q >> 1), w = 2 * wo + (q & 1);
-                        q8_put8(a.y2, y2_f8 != 0, q8_pix(b, h, w, a.H, a.W, a.y2_ld) + a.y2_choff + n0, bt, ht,
-                                (4 * pr + q) * PB + ch * 8);
-                    }
-                }
-            }
-        }
-    } else {
-        for (int slot = tid; slot < BNP * CH; slot += NT) {
-            const int row = slot / CH, ch = slot - row * CH;
-            const int m = mt * BNP + row;
-            const int n0 = nt * BMW + ch * 8;
-            if (m < a.M && n0 < a.N) {
-                long long off;
-                if (a.dst_mode == MCAMD_DST_REORG) {   // out channel = (dy * 2 + dx) * N + n at the pooled pixel
-                    const int idx = m >> 2, q = m & 3;
-                    const int b = idx / HWo, r = idx - b * HWo;
-                    const int ho = r / Wo, wo = r - ho * Wo;
-                    off = q8_pix(b, ho, wo, Ho, Wo, a.y_ld) + a.y_choff + q * a.N + n0;
-                } else {
-                    const int b = m / a.HW;
-                    const int rem = m - b * a.HW;
-                    const int h = rem / a.W;
-                    off = q8_pix(b, h, rem - h * a.W, a.H, a.W, a.y_ld) + a.y_choff + n0;
-                }
-                q8_put8(a.y, y_f8 != 0, off, bt, ht, row * PB + ch * 8);
-            }
-        }
-    }
+    store_pad_tile<BNP, BMW, PB, NT>(a, bt, ht, y_f8 != 0, y2_f8 != 0, mt, nt, tid);
     if (sat && a.overflow) atomicOr(a.overflow, 1);
 }
 
@@ -453,7 +298,7 @@ __global__ __launch_bounds__(256) void cast_q8_kernel(const half_t* __restrict__
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
     i32x2_t o;
-    o[0] = q8_bytes4(v), o[1] = q8_bytes4(v + 4);
+    o[0] = e4m3_bytes4(v), o[1] = e4m3_bytes4(v + 4);
     *(i32x2_t*)(dst + p * dst_ld + dst_choff + c) = o;
 }
 

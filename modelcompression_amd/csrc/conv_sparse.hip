@@ -19,14 +19,10 @@
 // dense kernel the weight bytes and the MFMA count halve; the activation bytes do not change.
 //
 // Epilogue: MCAMD_EPI_PAD_F16 (leaky(acc * scale + shift), the inference form of mcamd_conv_fwd mode 2), the tile laid
-// down in LDS as [pixel][channel] so that the plain store and epi_pool.h's POOL / REORG stores are shared.
+// down in LDS as [pixel][channel] (conv_epi.h: write_ch_tile) and stored PLAIN / POOL / REORG by the store every forward
+// implicit-GEMM kernel uses (store_pad_tile).
 #include "kernels.h"
-#include "epi_pool.h"
-
-template <int N>
-__device__ __forceinline__ void sp_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+#include "conv_epi.h"
 
 typedef _Float16 h16_t __attribute__((ext_vector_type(16)));
 
@@ -55,11 +51,8 @@ void sparse24_kernel(IgemmArgs a, const unsigned short* __restrict__ idx, int np
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    // all channel tiles of a pixel tile on one XCD (its activation rows stay in that XCD's L2)
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nt = jb % a.num_ntiles;
-    const int mt = (jb / a.num_ntiles) * 8 + xcd;
-    if (mt >= a.num_mtiles) return;
+    int nt, mt;
+    if (!xcd_tile(a.num_ntiles, a.num_mtiles, nt, mt)) return;
     const int nchunks = a.ktot / BK;
     const int krow = a.ktot / 2;                   // compressed row length (fp16)
 
@@ -77,18 +70,7 @@ void sparse24_kernel(IgemmArgs a, const unsigned short* __restrict__ idx, int np
         const int slot = it * NT + tid;
         const int row = slot / CPRB, phys = slot % CPRB;
         const int logical = phys ^ swz<CPRB>(row);
-        int m = mt * BNP + row;
-        if (m > a.M - 1) m = a.M - 1;              // tail columns re-read the last pixel; their results are not stored
-        int b, h, w;
-        if (a.dst_mode != 0) {
-            pooled_pixel(a, m, b, h, w);
-        } else {
-            b = m / a.HW;
-            const int rem = m - b * a.HW;
-            h = rem / a.W;
-            w = rem - h * a.W;
-        }
-        xbase[it] = (long long)b * a.x_img_stride + (long long)h * a.x_row_stride + (long long)w * a.x_ld + a.x_off + logical * 8;
+        xbase[it] = tile_x_base(a, a.dst_mode != 0, mt * BNP + row) + logical * 8;
     }
     // index DMA (waves 0 .. I_WAVES-1): slot l fetches 16 bytes = 4 rows of K32 step s = l / (BMW / 4) of the chunk
     const int islot = wave * 64 + lane;
@@ -131,8 +113,8 @@ void sparse24_kernel(IgemmArgs a, const unsigned short* __restrict__ idx, int np
         int issued = q + NSTAGE - 1;
         if (issued > nchunks) issued = nchunks;
         const int inflight = issued - q - 1;
-        if (NSTAGE == 2 || inflight == 0) sp_wait_vmcnt<0>();
-        else sp_wait_vmcnt<DMIN>();
+        if (NSTAGE == 2 || inflight == 0) wait_vmcnt<0>();
+        else wait_vmcnt<DMIN>();
         __builtin_amdgcn_s_barrier();              // chunk q landed for every wave; every wave is done with chunk q-1
         if (q + NSTAGE - 1 < nchunks) {
             int ns = sidx + NSTAGE - 1;
@@ -175,57 +157,11 @@ void sparse24_kernel(IgemmArgs a, const unsigned short* __restrict__ idx, int np
     // ------------------------------- epilogue -------------------------------
     __syncthreads();                               // every wave is done with the stage buffers
     half_t* ct = (half_t*)smem;                    // [BNP][BMW] fp16 output tile: pixel rows, channel columns
-    bool sat = false;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {              // accumulator rows 4 g .. 4 g + 3: four consecutive channels
-            const int ch0 = wm * WM + i * 32 + 8 * g + 4 * (lane >> 5);
-            float sc[4], sh[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int n = nt * BMW + ch0 + e;
-                sc[e] = 1.f, sh[e] = 0.f;
-                if (n < a.N) {
-                    if (a.scale) sc[e] = a.scale[n];
-                    if (a.shift) sh[e] = a.shift[n];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int pix = wn * WN + j * 32 + (lane & 31);
-                h4_t hv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float v = acc[i][j][4 * g + e] * sc[e] + sh[e];
-                    v = v > 0.f ? v : v * a.slope;
-                    sat |= fabsf(v) > 65504.f;
-                    hv[e] = (half_t)fminf(fmaxf(v, -65504.f), 65504.f);   // saturate, never inf
-                }
-                *(h4_t*)(ct + pix * BMW + ch0) = hv;
-            }
-        }
-    }
+    const float* scale = a.scale;
+    const bool sat = write_ch_tile<BMW, BMW, WM, WN>(a, acc, [scale](int n) { return scale ? scale[n] : 1.f; }, false, true, nullptr,
+                                                     ct, nt, wm, wn, lane);
     __syncthreads();
-    if (a.dst_mode != 0) {
-        store_pad_pooled<BNP, BMW, NT>(a, ct, mt, nt, tid);
-    } else {
-        constexpr int CH = BMW / 8;
-        half_t* y = (half_t*)a.y;
-        for (int slot = tid; slot < BNP * CH; slot += NT) {
-            const int row = slot / CH, ch = slot - row * CH;
-            const int m = mt * BNP + row;
-            const int n0 = nt * BMW + ch * 8;
-            if (m < a.M && n0 < a.N) {
-                const int b = m / a.HW;
-                const int rem = m - b * a.HW;
-                const int h = rem / a.W;
-                const int w = rem - h * a.W;
-                const long long off = (((long long)b * (a.H + 2) + h + 1) * (a.W + 2) + w + 1) * a.y_ld;
-                *(h8_t*)(y + off + a.y_choff + n0) = *(const h8_t*)(ct + row * BMW + ch * 8);
-            }
-        }
-    }
+    store_pad_tile<BNP, BMW, BMW, NT>(a, nullptr, ct, false, false, mt, nt, tid);
     if (sat && a.overflow) atomicOr(a.overflow, 1);
 }
 

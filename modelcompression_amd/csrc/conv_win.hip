@@ -22,11 +22,6 @@ namespace {
 constexpr int NR = 6;                 // ring rows: 3 under the taps + 2 in flight + 1 being overwritten
 constexpr int ROW_BYTES = 5 * 1024;   // 34 pixels x 128 bytes = 272 pieces, staged by 5 DMA instructions (320 slots)
 constexpr int LA = 2;                 // rows staged ahead of the row being multiplied
-
-template <int N>
-__device__ __forceinline__ void wait_vmc() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 }  // namespace
 
 // Every wave has its own units and computes all (<= 32) output channels: the input gradient of conv2.  (A four-wave form
@@ -102,13 +97,13 @@ __global__ __launch_bounds__(256, 1) void win3x3_kernel(IgemmArgs a, int seg_row
             // before the row is in: wrong results under load, B = 64.)
             static_assert(LA == 2, "the three cases below are written out for LA = 2");
             const int k = h - h_lo;
-            if (k == 0) wait_vmc<10>();
+            if (k == 0) wait_vmcnt<10>();
             else if (k == 1) {
-                if (ngroups == 2) wait_vmc<12>();
-                else wait_vmc<11>();
+                if (ngroups == 2) wait_vmcnt<12>();
+                else wait_vmcnt<11>();
             } else {
-                if (ngroups == 2) wait_vmc<14>();
-                else wait_vmc<12>();
+                if (ngroups == 2) wait_vmcnt<14>();
+                else wait_vmcnt<12>();
             }
             int s1 = slot0 + 1, s2 = slot0 + 2;
             if (s1 >= NR) s1 -= NR;
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(256, 1) void win3x3_kernel(IgemmArgs a, int seg_row
             yrow += (long long)a.W * a.y_ld;
             slot0 = slot0 + 1 == NR ? 0 : slot0 + 1;
         }
-        wait_vmc<0>();     // the look-ahead rows of this unit must not land in the next unit's ring
+        wait_vmcnt<0>();     // the look-ahead rows of this unit must not land in the next unit's ring
     }
 }
 

@@ -1246,16 +1246,19 @@ class Engine:
                                pool_act=af, pool_act_ld=ops.round_up(lay.cout, 8) if af is not None else 0,
                                pool_act_pad=self._pad_for(lay.W) if af is not None else 0)
                 continue
-            if (not training and self.fuse_eval and lay.perm is None and lay.border is None
-                    and (lay.out2_t is None or lay.mode == L.DST_POOL)
-                    and (lay.mode == L.DST_PLAIN or (lay.H % 2 == 0 and lay.W % 2 == 0))):
+            if not training and self._fused_eval(lay):
                 # inference: BN (running statistics) + LeakyReLU -- and the MaxPool / Reorg that follows the block -- in the
                 # conv epilogue, written straight into the consumer's padded buffer: the raw output is never stored (one
                 # fp16 rounding per layer, no second pass)
                 ops.bn_coeffs(None, lay.cout, lay.M, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, False,
                               lay.scale, lay.shift, lay.mean, lay.invstd, eps=bn.eps)
                 t, t2 = lay.out_t, lay.out2_t
-                if self.q8 and lay.q8_on:   # e4m3 activations x e4m3 weights (Darknet.precision = "fp8", _update_q8)
+                q8 = self.q8 and lay.q8_on
+                # destination form of the epilogue: plain / pool (+ the full-resolution copy y2, bytes or fp16) / reorg
+                y2 = None if t2 is None else (self.qbufs if q8 and lay.q8_y2 else self.bufs)[t2.buf]
+                dst = dict(dst_mode=lay.mode, y2=y2, y2_ld=t2.ld if t2 is not None else 0,
+                           y2_choff=t2.choff if t2 is not None else 0)
+                if q8:                      # e4m3 activations x e4m3 weights (Darknet.precision = "fp8", _update_q8)
                     x8 = self.qbufs.get(lay.tin.buf)
                     if lay.xq is not None:  # the fp16 -> fp8 edge: cast pass over the padded input slice
                         ti, x8 = lay.tin, lay.xq
@@ -1263,21 +1266,14 @@ class Engine:
                                     x8, ti.ld, ti.choff)
                     self._timed('fwd', lay, ops.conv_fwd_q8, lay.geom_act, x8, lay.wq, lay.wexp,
                                 self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf], t.ld, t.choff, lay.scale, lay.shift,
-                                lay.slope, dst_mode=lay.mode,
-                                y2=(self.qbufs[t2.buf] if lay.q8_y2 else self.bufs[t2.buf]) if t2 is not None else None,
-                                y2_ld=t2.ld if t2 is not None else 0, y2_choff=t2.choff if t2 is not None else 0,
-                                y_f8=lay.q8_y, y2_f8=lay.q8_y2)
+                                lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
                     continue
                 if lay.sp_on:       # 2:4 weights on the sparse MFMA (Darknet.sparse, _update_sparse)
                     self._timed('fwd', lay, ops.conv_fwd_sparse24, lay.geom_act, xin, lay.wsp, lay.widx, self.bufs[t.buf], t.ld,
-                                t.choff, lay.scale, lay.shift, lay.slope, dst_mode=lay.mode,
-                                y2=self.bufs[t2.buf] if t2 is not None else None,
-                                y2_ld=t2.ld if t2 is not None else 0, y2_choff=t2.choff if t2 is not None else 0)
+                                t.choff, lay.scale, lay.shift, lay.slope, **dst)
                     continue
                 self._timed('fwd', lay, ops.conv_fwd_padded, lay.geom_act, xin, lay.wp, self.bufs[t.buf], t.ld, t.choff,
-                            lay.scale, lay.shift, lay.slope, dst_mode=lay.mode,
-                            y2=self.bufs[t2.buf] if t2 is not None else None,
-                            y2_ld=t2.ld if t2 is not None else 0, y2_choff=t2.choff if t2 is not None else 0)
+                            lay.scale, lay.shift, lay.slope, **dst)
                 continue
             self._timed('fwd', lay, ops.conv_fwd_raw, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0, lay.stats if training else None)
             ops.bn_coeffs(lay.stats if training else None, lay.cout, lay.M, bn.weight.data, bn.bias.data,
