@@ -265,6 +265,35 @@ int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const void* wq, 
 int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst, int32_t dst_ld,
                   int32_t dst_choff, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * 2:4-sparse fp8 quantised inference (an addition beyond the reference; conv_q8_sparse.hip, Darknet.precision =
+ * "fp8-2:4"): the fp8 block above -- same activations, exponents, q(), output formula and destinations -- for weights
+ * whose mask keeps at most 2 of every 4 consecutive input channels at each (filter, tap), on the sparse MFMA.  S is an fp32
+ * sum of the exact products (v_smfmac_f32_32x32x32_f16 on the bytes converted in registers); MCAMD_Q8_MFMA=1 multiplies on
+ * v_smfmac_f32_32x32x64_fp8_fp8 instead, which like the dense fp8 MFMA truncates inside groups of 8 products.
+ * ------------------------------------------------------------------------- */
+/* mcamd_conv_fwd_q8_ok's predicate (cin % 64 == 0 implies whole groups of 4). */
+int32_t mcamd_conv_fwd_q8_sparse24_ok(const mcamd_conv_geom* g);
+/* Sizes of the packed operands: out[0] = kept bytes (Npad * ktot / 2; Npad = round_up(cout, 256), ktot = k*k * cin),
+ * out[1] = 32-bit index words (Npad * ktot / 32), out[2] = int32 exponents (Npad). */
+int mcamd_q8_sparse24_elems(const mcamd_conv_geom* g, int64_t out[3]);
+/* OIHW fp32 master (* mask, may be NULL) -> the 2:4 fp8 packing:
+ *   wexp: int32 [Npad], e_f of mcamd_pack_q8 (from max |w * mask| over the WHOLE filter; pad rows 0);
+ *   wq:   bytes [Npad][ktot / 2]: the dense row of mcamd_pack_q8 (position kpos(t, c) = (c / 64) * k*k*64 + t * 64 + c % 64)
+ *         with every group of 4 consecutive positions [4 G, 4 G + 4) -- 4 consecutive input channels at one tap -- reduced
+ *         to its 2 kept bytes: kept byte j of the row (j < ktot / 2) belongs to group G = j / 2; pad rows zero bytes;
+ *   idx:  uint32 [ktot / 64][Npad][2]: word idx[(q * Npad + n) * 2 + h] describes kept bytes j in [32 q + 16 h, +16) of row
+ *         n; bits [2 i, 2 i + 2), i = j - 32 q - 16 h, hold the offset o of kept byte j inside its group: its dense position
+ *         is 4 (j / 2) + o.  The two offsets of a group are distinct and ascending.
+ * The kept entries of a group are the non-zeros of the fp32 product w * mask in channel order (the first two when the mask
+ * does not conform); a group with fewer gets distinct ascending offsets with zero values (none: 0, 1; one at offset o: (o, o
+ * + 1) if o == 0 else (0, o)).  The bytes are q(kept value * 2^e_f).  Every row up to Npad is written. */
+int mcamd_pack_q8_sparse24(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wq, void* idx,
+                           int32_t* wexp, void* stream);
+/* mcamd_conv_fwd_q8 from that packing (the same arguments plus `idx`). */
+int mcamd_conv_fwd_q8_sparse24(const mcamd_conv_geom* g, const void* x8, const void* wq, const void* idx, const int32_t* wexp,
+                               const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream);
+
 /* dx = conv_transpose(dy, w) -- autograd's input gradient of the same call.
  * `dy` is padded NHWC fp16 [B][H+2][W+2][dy_ld] (zero halo); g->cin/cout keep their forward
  * meaning; the result has g->cin channels.  epi->mode 0 (fp16 [M][y_ld]) or 1 (fp32 NCHW). */

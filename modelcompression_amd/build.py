@@ -23,6 +23,7 @@ SOURCES = {
     "conv_igemm_pp.hip": [],
     "conv_sparse.hip": [],
     "conv_q8.hip": [],
+    "conv_q8_sparse.hip": [],
     "conv_stem.hip": [],
     "conv_stem_block.hip": [],
     "conv_stem_f32.hip": [],

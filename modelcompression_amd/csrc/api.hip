@@ -677,6 +677,54 @@ extern "C" int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const
     return mcamd_conv_q8_launch(a, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------
+// 2:4-sparse fp8 quantised inference (conv_q8_sparse.hip; an addition beyond the reference)
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_q8_sparse24_ok(const mcamd_conv_geom* g) {
+    return mcamd_conv_fwd_q8_ok(g);                // (cin % 64 == 0: whole groups of 4)
+}
+
+extern "C" int mcamd_q8_sparse24_elems(const mcamd_conv_geom* g, int64_t out[3]) {
+    MCAMD_REQUIRE(g && out, "q8_sparse24_elems: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_sparse24_ok(g), "q8_sparse24_elems: geometry has no 2:4 fp8 form (mcamd_conv_fwd_q8_sparse24_ok)");
+    const long long npad = round_up_int(g->cout, 256), ktot = (long long)ntaps_of(g) * g->cin;
+    out[0] = npad * ktot / 2;      // kept bytes
+    out[1] = npad * ktot / 32;     // 32-bit index words
+    out[2] = npad;                 // int32 exponents
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_pack_q8_sparse24(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wq, void* idx,
+                                      int32_t* wexp, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "pack_q8_sparse24: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_pack_q8_sparse24(&g_, w_oihw, mask_oihw, wq, idx, wexp, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_sparse24_ok(g), "pack_q8_sparse24: geometry has no 2:4 fp8 form (mcamd_conv_fwd_q8_sparse24_ok)");
+    MCAMD_REQUIRE(w_oihw && wq && idx && wexp, "pack_q8_sparse24: null pointer");
+    return mcamd_pack_q8_sparse24_launch(w_oihw, mask_oihw, wq, idx, wexp, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_q8_sparse24(const mcamd_conv_geom* g, const void* x8, const void* wq, const void* idx,
+                                          const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8,
+                                          void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_sparse24: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_q8_sparse24(&g_, x8, wq, idx, wexp, &e_, y_f8, y2_f8, s); });
+    }
+    if (check_geom(g, "conv_fwd_q8_sparse24")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_sparse24_ok(g), "conv_fwd_q8_sparse24: geometry has no 2:4 fp8 form (mcamd_conv_fwd_q8_sparse24_ok)");
+    MCAMD_REQUIRE(x8 && wq && idx && wexp, "conv_fwd_q8_sparse24: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8_sparse24: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x8, wq, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_sparse24", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    return mcamd_conv_q8_sparse_launch(a, idx, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
+}
+
 extern "C" int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst,
                              int32_t dst_ld, int32_t dst_choff, void* stream) {
     if (mcamd_recording())

@@ -66,6 +66,14 @@ __device__ __forceinline__ int e4m3_bytes4(const float* v) {
     return __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], w, true);
 }
 
+// ... and back: eight e4m3 codes -> eight fp16 values (exact: every e4m3 value is an fp16 value)
+__device__ __forceinline__ h8_t q8_to_f16(int lo, int hi) {
+    const h2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true);
+    const h2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true);
+    const h4_t a = __builtin_shufflevector(p0, p1, 0, 1, 2, 3), b = __builtin_shufflevector(p2, p3, 0, 1, 2, 3);
+    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 // order-preserving key of four e4m3 codes (unsigned byte order = value order, -0 below +0) and back: MaxPool of bytes is
 // taken on the key (e4m3 is monotone: the maximum of the bytes is the byte of the maximum)
 __device__ __forceinline__ unsigned e4m3_key(unsigned b) { return b ^ ((((b >> 7) & 0x01010101u) * 0xffu) | 0x80808080u); }

@@ -26,18 +26,6 @@
 #include "kernels.h"
 #include "conv_epi.h"
 
-namespace {
-
-// eight e4m3 codes -> eight fp16 values (exact: every e4m3 value is an fp16 value)
-__device__ __forceinline__ h8_t q8_to_f16(int lo, int hi) {
-    const h2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true);
-    const h2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true);
-    const h4_t a = __builtin_shufflevector(p0, p1, 0, 1, 2, 3), b = __builtin_shufflevector(p2, p3, 0, 1, 2, 3);
-    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-}  // namespace
-
 // F8MFMA = false (the default): the staged bytes are converted to fp16 in registers and multiplied by
 // v_mfma_f32_32x32x16_f16, whose sum of the (exact) products is an fp32 sum -- the arithmetic of the contract, byte for
 // byte.  F8MFMA = true (MCAMD_Q8_MFMA=1): one v_mfma_scale_f32_32x32x64_f8f6f4 per block and chunk, half the MFMA time --

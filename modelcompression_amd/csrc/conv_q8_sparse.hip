@@ -1,0 +1,315 @@
+// 2:4-sparse fp8 (OCP e4m3) implicit-GEMM convolution forward for gfx950 (MI355X), inference epilogue (an addition beyond
+// the reference: the nm_prune masks on the fp8 engine, Darknet.precision = "fp8-2:4").
+//
+//   S[n][m] = sum_{tap, c} W8[n][kpos(tap, c)] * X8[pixel(m) + tap][c]        (W8 2:4 along c; fp32 accumulation)
+//   v       = leaky(scale[n] * 2^-(e[n] + 1) * S + shift[n])
+//
+// The arithmetic, the byte buffers and the epilogue are conv_q8.hip's; the weights are its packed rows with every group
+// of 4 consecutive k reduced to its 2 kept bytes (mcamd_pack_q8_sparse24 below), multiplied on the sparse MFMA with the
+// weights as the (sparse) A operand as in conv_sparse.hip.
+//
+// One K chunk = 64 dense k: per weight row 32 kept bytes + 8 index bytes, per pixel one 64-byte row, all staged by
+// global_load_lds_dwordx4 (pixel rows swizzled as in conv_q8.hip; the 32-byte weight rows are read 16 bytes per lane,
+// contiguously over the wave, and need no swizzle).  Lane (r, h), r = lane & 31, h = lane >> 5, holds
+//   A: the 16 kept bytes of dense k [32 h, 32 h + 32) of row r, and index word h of the row's chunk: kept byte j lies in
+//      group j / 2 of those 32 k at offset bits [2 j, 2 j + 2);
+//   B: bytes [16 h, 16 h + 16) and [32 + 16 h, 32 + 16 h + 16) of pixel row r
+// which IS the operand layout of v_smfmac_f32_32x32x64_fp8_fp8 (tools/smfmac_f8_probe.hip): MCAMD_Q8_MFMA=1 issues one per
+// 32x32 block and chunk.  The default form converts the bytes to fp16 in registers and issues two
+// v_smfmac_f32_32x32x32_f16 (layout: conv_sparse.hip); step s takes, of the same registers,
+//   A: kept bytes [4 s, 4 s + 4) and [8 + 4 s, 8 + 4 s + 4) with their index bits [8 s, 8 s + 8) and [16 + 8 s, 16 + 8 s + 8),
+//   B: bytes [8 s, 8 s + 8) of each of the lane's two 16-byte pieces,
+// a k permutation common to both operands under which that instruction's lanes (A: k [16 h, 16 h + 16), B: k 16 (e >> 3) +
+// 8 h + (e & 7)) meet exactly the registers above.  Its products are exact and its sum is an fp32 sum: the byte contract.
+#include "kernels.h"
+#include "conv_epi.h"
+
+typedef _Float16 h16_t __attribute__((ext_vector_type(16)));
+
+// F8MFMA as in conv_q8_kernel: false = fp16 sparse MFMAs on converted bytes (byte-exact), true = the fp8 sparse MFMA, which
+// like the dense fp8 MFMAs sums groups of 8 products on a grid 14 bits below the group's largest.
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
+void conv_q8_sparse_kernel(IgemmArgs a, const unsigned* __restrict__ idx, int npad, const int* __restrict__ wexp, int y_f8,
+                           int y2_f8) {
+    constexpr int WAVES_N = BNP / WN;
+    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
+    constexpr int BK = 64, CPRA = 2, CPRB = 4;     // 16-byte chunks per compressed weight row / per pixel row
+    constexpr int A_SLOTS = BMW * CPRA, B_SLOTS = BNP * CPRB;
+    constexpr int A_IT = (A_SLOTS + NT - 1) / NT, B_IT = B_SLOTS / NT;
+    constexpr int I_BYTES = BMW * 8 > 1024 ? BMW * 8 : 1024;     // index region: whole wave-wide DMAs
+    constexpr int I_WAVES = I_BYTES / 1024;
+    constexpr int TM = WM / 32, TN = WN / 32;
+    constexpr int STAGE_BYTES = (A_SLOTS + B_SLOTS) * 16 + I_BYTES;
+    constexpr int DMIN = A_SLOTS / NT + B_IT;      // DMA instructions every wave issues per stage
+    static_assert(A_SLOTS % 64 == 0 && B_SLOTS % NT == 0, "whole waves per DMA instruction");
+    static_assert(I_WAVES <= NT / 64, "index region");
+    static_assert(NSTAGE >= 2 && NSTAGE <= 3, "LDS ring depth");
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    int nt, mt;
+    if (!xcd_tile(a.num_ntiles, a.num_mtiles, nt, mt)) return;
+    const int nchunks = a.ktot / BK;
+    const int krow = a.ktot / 2;                   // compressed row length (bytes)
+    const char* xg = (const char*)a.x;             // byte operands: every stride of `a` counts bytes
+    const char* wg = (const char*)a.w;
+    const char* ig = (const char*)idx;
+
+    long long wbase[A_IT];
+#pragma unroll
+    for (int it = 0; it < A_IT; ++it) {
+        const int slot = (it * NT + tid) % A_SLOTS;              // (a wave past A_SLOTS issues nothing: stage())
+        wbase[it] = (long long)(nt * BMW + slot / CPRA) * krow + (slot % CPRA) * 16;   // rows < Npad = round_up(N, 256)
+    }
+    long long xbase[B_IT];
+#pragma unroll
+    for (int it = 0; it < B_IT; ++it) {
+        const int slot = it * NT + tid;
+        const int row = slot / CPRB, phys = slot % CPRB;
+        xbase[it] = tile_x_base(a, a.dst_mode != 0, mt * BNP + row) + (phys ^ swz<CPRB>(row)) * 16;
+    }
+    // index DMA (waves 0 .. I_WAVES-1): slot l fetches 16 bytes = the two words of 2 rows (a 64-row tile: lanes 32-63 repeat)
+    const long long ibase = ((long long)nt * BMW + 2 * ((wave * 64 + lane) % (BMW / 2))) * 8;
+
+    f32x16_t acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    auto stage = [&](int q, int buf) {
+        const int cb = q / a.ntaps, tap = q - cb * a.ntaps;      // one chunk per tap of a 64-channel block
+        const int koff = a.tap_off[tap] + cb * BK;
+        char* sa = smem + buf * STAGE_BYTES;
+        char* si = sa + A_SLOTS * 16;
+        char* sb = si + I_BYTES;
+#pragma unroll
+        for (int it = 0; it < A_IT; ++it) {
+            const int wslot = it * NT + wave * 64;
+            if (wslot < A_SLOTS) glds16(wg + wbase[it] + (long long)q * (BK / 2), sa + wslot * 16);
+        }
+        if (wave < I_WAVES) glds16(ig + ibase + (long long)q * npad * 8, si + wave * 1024);
+#pragma unroll
+        for (int it = 0; it < B_IT; ++it) glds16(xg + xbase[it] + koff, sb + (it * NT + wave * 64) * 16);
+    };
+
+    const int lrow = lane & 31, hh = lane >> 5;
+
+#pragma unroll
+    for (int p = 0; p < NSTAGE - 1; ++p)
+        if (p < nchunks) stage(p, p);
+    int sidx = 0;
+    for (int q = 0; q < nchunks; ++q) {
+        int issued = q + NSTAGE - 1;
+        if (issued > nchunks) issued = nchunks;
+        const int inflight = issued - q - 1;
+        if (NSTAGE == 2 || inflight == 0) wait_vmcnt<0>();
+        else wait_vmcnt<DMIN>();
+        __builtin_amdgcn_s_barrier();              // chunk q landed for every wave; every wave is done with chunk q-1
+        if (q + NSTAGE - 1 < nchunks) {
+            int ns = sidx + NSTAGE - 1;
+            if (ns >= NSTAGE) ns -= NSTAGE;
+            stage(q + NSTAGE - 1, ns);
+        }
+        const char* sa = smem + sidx * STAGE_BYTES;
+        const char* si = sa + A_SLOTS * 16;
+        const char* sb = si + I_BYTES;
+        sidx = sidx + 1 == NSTAGE ? 0 : sidx + 1;
+        i32x4_t af[TM];
+        int ix[TM];
+        i32x8_t bf[TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int row = wm * WM + i * 32 + lrow;
+            af[i] = *(const i32x4_t*)(sa + (row * CPRA + hh) * 16);
+            ix[i] = *(const int*)(si + row * 8 + hh * 4);
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int row = wn * WN + j * 32 + lrow;
+            const i32x4_t lo = *(const i32x4_t*)(sb + (row * CPRB + (hh ^ swz<CPRB>(row))) * 16);
+            const i32x4_t hi = *(const i32x4_t*)(sb + (row * CPRB + ((2 + hh) ^ swz<CPRB>(row))) * 16);
+            bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+        if constexpr (F8MFMA) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_smfmac_f32_32x32x64_fp8_fp8(af[i], bf[j], acc[i][j], ix[i], 0, 0);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                h8_t a16[TM];
+                int i16[TM];
+                h16_t b16[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    a16[i] = q8_to_f16(af[i][s], af[i][2 + s]);
+                    const unsigned w = (unsigned)ix[i];
+                    i16[i] = (int)(((w >> (8 * s)) & 0xffu) | (((w >> (16 + 8 * s)) & 0xffu) << 8));
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const h8_t lo = q8_to_f16(bf[j][2 * s], bf[j][2 * s + 1]), hi = q8_to_f16(bf[j][4 + 2 * s], bf[j][4 + 2 * s + 1]);
+                    b16[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+                }
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_smfmac_f32_32x32x32_f16(a16[i], b16[j], acc[i][j], i16[i], 0, 0);
+            }
+        }
+    }
+
+    // ------------------------------- epilogue (conv_q8_kernel's) -------------------------------
+    __syncthreads();                               // every wave is done with the stage buffers
+    const bool has2 = a.y2 != nullptr;
+    const bool need_b = y_f8 || (has2 && y2_f8), need_h = !y_f8 || (has2 && !y2_f8);
+    constexpr int PB = BMW + 8;                    // tile row pitch: a wave's 32 pixels on 32 LDS banks
+    char* bt = smem;                               // [BNP][PB] e4m3 tile
+    half_t* ht = (half_t*)(smem + (need_b ? BNP * PB : 0));   // [BNP][PB] fp16 tile
+    const float* scale = a.scale;
+    const bool sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale, wexp](int n) { return ldexpf(scale ? scale[n] : 1.f, -(wexp[n] + 1)); },
+                                                    need_b, need_h, bt, ht, nt, wm, wn, lane);
+    __syncthreads();
+    store_pad_tile<BNP, BMW, PB, NT>(a, bt, ht, y_f8 != 0, y2_f8 != 0, mt, nt, tid);
+    if (sat && a.overflow) atomicOr(a.overflow, 1);
+}
+
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+static int conv_q8_sparse_launch_t(IgemmArgs& a, const unsigned* idx, int npad, const int* wexp, int y_f8, int y2_f8, hipStream_t st) {
+    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
+    constexpr int I_BYTES = BMW * 8 > 1024 ? BMW * 8 : 1024;
+    constexpr int RING = NSTAGE * (BMW * 32 + BNP * 64 + I_BYTES);
+    constexpr int PB = BMW + 8;                    // tile row pitch (conv_q8_sparse_kernel)
+    constexpr int TILES = BNP * PB * 3;            // a byte and an fp16 tile (destinations of both formats)
+    constexpr int LDS = RING > TILES ? RING : TILES;
+    const bool has2 = a.y2 != nullptr;
+    const bool mixed = (y_f8 || (has2 && y2_f8)) && (!y_f8 || (has2 && !y2_f8));
+    const int lds = mixed ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);
+    auto kern = conv_q8_sparse_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
+    MCAMD_LDS_OPT_IN(kern, LDS);
+    a.num_mtiles = (a.M + BNP - 1) / BNP;
+    a.num_ntiles = (a.N + BMW - 1) / BMW;
+    const int grid = (a.num_mtiles + 7) / 8 * 8 * a.num_ntiles;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a, idx, npad, wexp, y_f8, y2_f8);
+    MCAMD_LAUNCH_CHECK("conv_fwd_q8_sparse24");
+    return MCAMD_OK;
+}
+
+// Tiles as conv_q8.hip's: 256 channels x 128 pixels (8 waves of 64 x 64) from 256 filters with the fp8 MFMA, 128 x 128
+// (4 waves) from 128, 64 x 128 below; a 3-deep ring (54 / 39 / 33 KB).
+// MCAMD_Q8_MFMA: 0 = fp16 sparse MFMAs on converted bytes, 1 = the fp8 sparse MFMA.
+int mcamd_conv_q8_sparse_launch(IgemmArgs& a, const void* idx, const void* wexp, int y_f8, int y2_f8, hipStream_t st) {
+    const int* we = (const int*)wexp;
+    const unsigned* ix = (const unsigned*)idx;
+    const int npad = round_up_int(a.N, 256);
+    if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {       // the fp8 sparse MFMA: faster, not byte-exact (see the kernel's comment)
+        if (a.N >= 256) return conv_q8_sparse_launch_t<256, 128, 64, 64, 3, true>(a, ix, npad, we, y_f8, y2_f8, st);
+        if (a.N >= 128) return conv_q8_sparse_launch_t<128, 128, 64, 64, 3, true>(a, ix, npad, we, y_f8, y2_f8, st);
+        return conv_q8_sparse_launch_t<64, 128, 32, 64, 3, true>(a, ix, npad, we, y_f8, y2_f8, st);
+    }
+    // (no 256-channel tile here either: the A fragments are half the dense ones, but with the converted fragments it still
+    // needs 133 registers -- one workgroup per CU; held to 128 it spills -- and measured 0.94 x the 128 x 128 tile over the
+    // whole forward, 0.73-0.84 x on the 256- and 512-filter layers: DESIGN.md 3k)
+    if (a.N >= 128) return conv_q8_sparse_launch_t<128, 128, 64, 64, 3, false>(a, ix, npad, we, y_f8, y2_f8, st);
+    return conv_q8_sparse_launch_t<64, 128, 32, 64, 3, false>(a, ix, npad, we, y_f8, y2_f8, st);
+}
+
+// ---------------------------------------------------------------------------------------
+// packer: fp32 OIHW master * mask -> kept e4m3 bytes [Npad][ktot / 2] + index words [ktot / 64][Npad][2] + exponents
+// ---------------------------------------------------------------------------------------
+// One workgroup per row n < Npad.  The exponent is pack_q8_kernel's (max |w * mask| of the whole filter, integer steps).
+// Then one thread per 32 dense k of the packed order [cb][tap][64]: 8 groups of 4 consecutive input channels at one tap ->
+// 16 kept bytes and one index word.  The kept entries of a group are pack_sparse24_kernel's: the non-zeros of the fp32
+// w * mask in channel order (the first two when the mask does not conform); a group with fewer gets distinct ascending
+// indices with zero values.  Pad rows: zero bytes, e = 0.
+__global__ __launch_bounds__(256) void pack_q8_sparse24_kernel(const float* __restrict__ w, const float* __restrict__ mask,
+                                                               char* __restrict__ wq, unsigned* __restrict__ idx,
+                                                               int* __restrict__ wexp, int cout, int cin, int ntaps, int npad) {
+    __shared__ float red[256];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int ktot = cin * ntaps;
+    float amax = 0.f;
+    if (n < cout)
+        for (int o = tid; o < ktot; o += 256) {
+            const long long s = (long long)n * ktot + o;
+            amax = fmaxf(amax, fabsf(w[s] * (mask ? mask[s] : 1.f)));
+        }
+    red[tid] = amax;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    amax = red[0];
+    int e = 0;
+    if (amax > 0.f) {
+        int x;
+        const float m = frexpf(amax, &x);
+        e = m <= 0.875f ? 9 - x : 8 - x;
+    }
+    if (tid == 0) wexp[n] = e;
+    for (int u = tid; u < ktot / 32; u += 256) {
+        i32x4_t kept;
+        unsigned field = 0;
+#pragma unroll
+        for (int g2 = 0; g2 < 4; ++g2) {           // two groups -> four kept bytes -> one 32-bit word
+            float kv[4];
+#pragma unroll
+            for (int gg = 0; gg < 2; ++gg) {
+                const int g = 2 * g2 + gg;
+                const int kp = 32 * u + 4 * g;                       // first k of the group in the packed order
+                const int cb = kp / (ntaps * 64), r = kp - cb * ntaps * 64;
+                const int tap = r / 64, c0 = cb * 64 + (r - tap * 64);
+                float v[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    v[i] = 0.f;
+                    if (n < cout) {
+                        const long long s = ((long long)n * cin + c0 + i) * ntaps + tap;
+                        v[i] = w[s] * (mask ? mask[s] : 1.f);
+                    }
+                }
+                int p[2], np = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (v[i] != 0.f && np < 2) p[np++] = i;
+                if (np == 0) { p[0] = 0; p[1] = 1; }
+                else if (np == 1) { if (p[0] == 0) p[1] = 1; else { p[1] = p[0]; p[0] = 0; } }
+                float k0 = 0.f, k1 = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {      // (selects, not indexed reads: v stays in registers)
+                    k0 = p[0] == i ? v[i] : k0;
+                    k1 = p[1] == i ? v[i] : k1;
+                }
+                kv[2 * gg] = fminf(fmaxf(ldexpf(k0, e), -448.f), 448.f);
+                kv[2 * gg + 1] = fminf(fmaxf(ldexpf(k1, e), -448.f), 448.f);
+                field |= (unsigned)p[0] << (4 * g) | (unsigned)p[1] << (4 * g + 2);
+            }
+            int b = __builtin_amdgcn_cvt_pk_fp8_f32(kv[0], kv[1], 0, false);
+            b = __builtin_amdgcn_cvt_pk_fp8_f32(kv[2], kv[3], b, true);
+            kept[g2] = b;
+        }
+        *(i32x4_t*)(wq + (long long)n * (ktot / 2) + 16 * u) = kept;
+        idx[((long long)(u >> 1) * npad + n) * 2 + (u & 1)] = field;
+    }
+}
+
+int mcamd_pack_q8_sparse24_launch(const float* w, const float* mask, void* wq, void* idx, void* wexp, int cout, int cin,
+                                  int ntaps, hipStream_t st) {
+    const int npad = round_up_int(cout, 256);
+    hipLaunchKernelGGL(pack_q8_sparse24_kernel, dim3(npad), dim3(256), 0, st, w, mask, (char*)wq, (unsigned*)idx, (int*)wexp, cout,
+                       cin, ntaps, npad);
+    MCAMD_LAUNCH_CHECK("pack_q8_sparse24");
+    return MCAMD_OK;
+}

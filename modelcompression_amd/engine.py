@@ -142,18 +142,23 @@ class Engine:
         plain (MIXED_BUDGET; `for_training`: the budget of the training-mode forward, MIXED_BUDGET_TRAIN, under which the
         first block is split as well).  The backward pass uses plain fp16 operands in every mode.
         "fp8" -- inference only: the "fp16" engine with every eligible block on e4m3 activations and weights
-        (csrc/conv_q8.hip, `fp8_layers`, _update_q8); a training-mode forward raises."""
-        if precision not in ("fp16", "fp16x3", "mixed", "fp8"):
-            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed' or 'fp8' (got %r)" % (precision,))
+        (csrc/conv_q8.hip, `fp8_layers`, _update_q8); a training-mode forward raises.
+        "fp8-2:4" -- the "fp8" engine with every fp8 block whose mask conforms to 2:4 on the sparse fp8 kernel
+        (csrc/conv_q8_sparse.hip, `fp8_sparse_layers`); every other block runs what "fp8" runs."""
+        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4"):
+            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8' or 'fp8-2:4' (got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision not in ("fp16", "fp8")
+        self.precise = precision not in ("fp16", "fp8", "fp8-2:4")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_update_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision == "fp8"
+        self.q8 = precision in ("fp8", "fp8-2:4")
         self.fp8_layers = []
+        # "fp8-2:4": the subset of fp8_layers whose masks conform to 2:4 and that run mcamd_conv_fwd_q8_sparse24
+        self.q8_sparse = precision == "fp8-2:4"
+        self.fp8_sparse_layers = []
         self.qbufs = {}
         self._q8_keys = None
         self.grad_scale = float(grad_scale)
@@ -680,7 +685,10 @@ class Engine:
             if lay.sp_on:
                 ops.pack_sparse24(lay.geom_act, lay.conv.weight.data, mask, lay.wsp, lay.widx)
             if self.q8 and lay.q8_on:      # e4m3 bytes + one exponent per filter, computed on the device
-                ops.pack_q8(lay.geom_act, lay.conv.weight.data, mask, lay.wq, lay.wexp)
+                if lay.q8s_on:             # ... 2:4-compressed, with their index words
+                    ops.pack_q8_sparse24(lay.geom_act, lay.conv.weight.data, mask, lay.wqs, lay.widx8, lay.wexp)
+                else:
+                    ops.pack_q8(lay.geom_act, lay.conv.weight.data, mask, lay.wq, lay.wexp)
             if lay.stem:
                 ops.pack_weights(lay.geom_act, lay.conv.weight.data, mask, True, False, lay.wp, None, rows=lay.g_rows)
             if getattr(lay, "stem_split", False):          # hi and lo stem packings of the split-operand fused first block
@@ -771,11 +779,14 @@ class Engine:
         engine runs.  An activation buffer holds e4m3 bytes when EVERY block that reads it (a concat member can have a
         reader of its own beside the concat's) and every block that writes into it are fp8 blocks: one format per tensor.
         Otherwise the buffer stays fp16 and an fp8 block that reads it takes a private byte copy that a cast pass
-        (mcamd_cast_q8) writes in front of it."""
-        self._plan_epoch += 1             # recorded forward plans name the fp16 or the fp8 launch of a block
+        (mcamd_cast_q8) writes in front of it.
+        Precision "fp8-2:4": an fp8 block whose mask is present with the weight's shape and keeps at most 2 of every 4
+        consecutive input channels at each (filter, tap) -- checked on the device, one host read for all blocks -- runs
+        the sparse fp8 kernel (`fp8_sparse_layers`); formats and buffers do not depend on that."""
+        self._plan_epoch += 1             # recorded forward plans name the fp16, the fp8 or the sparse fp8 launch of a block
         for lay in self.layers:
-            lay.q8_on, lay.q8_y, lay.q8_y2, lay.xq = False, False, False, None
-        self.fp8_layers = []
+            lay.q8_on, lay.q8_y, lay.q8_y2, lay.xq, lay.q8s_on = False, False, False, None, False
+        self.fp8_layers, self.fp8_sparse_layers = [], []
         dev = self.device
         for lay in self.layers:
             if (lay.li > 0 and not lay.stem and not lay.is_last and lay.cin % 64 == 0 and lay.fold is None
@@ -783,6 +794,17 @@ class Engine:
                     and self._fused_eval(lay) and ops.conv_fwd_q8_ok(lay.geom_act)):
                 lay.q8_on = True
                 self.fp8_layers.append(lay.li + 1)     # conv number (conv1 = the first block)
+        cand = [lay for lay in self.layers
+                if self.q8_sparse and lay.q8_on and lay.conv.mask_flag and lay.conv.mask.shape == lay.conv.weight.shape
+                and ops.conv_fwd_q8_sparse24_ok(lay.geom_act)]
+        if cand:
+            counts = torch.zeros(len(cand), dtype=torch.int32, device=dev)
+            for i, lay in enumerate(cand):
+                ops.nm_violations(lay.conv.mask.contiguous(), counts[i:i + 1])
+            for lay, bad in zip(cand, counts.cpu().tolist()):
+                if not bad:
+                    lay.q8s_on = True
+                    self.fp8_sparse_layers.append(lay.li + 1)
         writers = {}                      # buffer id -> the blocks that write into it
         for lay in self.layers:
             if not lay.is_last:
@@ -796,9 +818,16 @@ class Engine:
         for lay in self.layers:
             if not lay.q8_on:
                 continue
-            nw, ne = ops.q8_elems(lay.geom_act)
-            if getattr(lay, "wq", None) is None or lay.wq.numel() != nw:
-                lay.wq = torch.zeros(nw, dtype=torch.uint8, device=dev)
+            if lay.q8s_on:
+                nw, ni, ne = ops.q8_sparse24_elems(lay.geom_act)
+                if getattr(lay, "wqs", None) is None or lay.wqs.numel() != nw:
+                    lay.wqs = torch.zeros(nw, dtype=torch.uint8, device=dev)
+                    lay.widx8 = torch.zeros(ni, dtype=torch.int32, device=dev)
+            else:
+                nw, ne = ops.q8_elems(lay.geom_act)
+                if getattr(lay, "wq", None) is None or lay.wq.numel() != nw:
+                    lay.wq = torch.zeros(nw, dtype=torch.uint8, device=dev)
+            if getattr(lay, "wexp", None) is None or lay.wexp.numel() != ne:
                 lay.wexp = torch.zeros(ne, dtype=torch.int32, device=dev)
             t = lay.tin
             ws = writers.get(t.buf, [])
@@ -1132,12 +1161,13 @@ class Engine:
                     raise McamdError("conv block %d: training needs a BN channel count of 8 * (power of two), got %d"
                                      % (lay.index, lay.cout))
         if training and self.q8:
-            raise McamdError("precision 'fp8' is inference only (there is no fp8 training path): call model.eval() or "
-                             "pick another precision for training")
+            raise McamdError("precision %r is inference only (there is no fp8 training path): call model.eval() or "
+                             "pick another precision for training" % (self.precision,))
         mode = None if training else getattr(self.model, "sparse", None)
         if mode is not None and (self.precise or self.q8):
-            raise McamdError("sparse=%r runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r"
-                             % (mode, self.precision))
+            raise McamdError("sparse=%r runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r%s"
+                             % (mode, self.precision, "; 2:4 masks on the fp8 engine: model.precision = 'fp8-2:4' with "
+                                "model.sparse = None" if self.q8 else ""))
         force = bool(training) or mode != self._sparse_mode
         self._sparse_mode = mode
         self.pack(force=force, training=training)
@@ -1264,9 +1294,13 @@ class Engine:
                         ti, x8 = lay.tin, lay.xq
                         self._timed('cast', lay, ops.cast_q8, xin, B * (ti.H + 2) * (ti.W + 2), ti.ld, ti.choff, lay.cin,
                                     x8, ti.ld, ti.choff)
-                    self._timed('fwd', lay, ops.conv_fwd_q8, lay.geom_act, x8, lay.wq, lay.wexp,
-                                self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf], t.ld, t.choff, lay.scale, lay.shift,
-                                lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
+                    y = self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf]
+                    if lay.q8s_on:          # ... 2:4-compressed weights on the sparse MFMA ("fp8-2:4")
+                        self._timed('fwd', lay, ops.conv_fwd_q8_sparse24, lay.geom_act, x8, lay.wqs, lay.widx8, lay.wexp, y,
+                                    t.ld, t.choff, lay.scale, lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
+                        continue
+                    self._timed('fwd', lay, ops.conv_fwd_q8, lay.geom_act, x8, lay.wq, lay.wexp, y, t.ld, t.choff, lay.scale,
+                                lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
                     continue
                 if lay.sp_on:       # 2:4 weights on the sparse MFMA (Darknet.sparse, _update_sparse)
                     self._timed('fwd', lay, ops.conv_fwd_sparse24, lay.geom_act, xin, lay.wsp, lay.widx, self.bufs[t.buf], t.ld,

@@ -278,7 +278,8 @@ class Darknet(nn.Module):
         # "fp8" (an addition beyond the reference, eval only): post-training quantised inference -- the "fp16" engine with every
         # eligible block (engine.Engine.fp8_layers: conv3-conv22 of YOLOv2-VOC) on e4m3 activations and weights, fp32
         # accumulation, no calibration data (csrc/conv_q8.hip; MCAMD_Q8_MFMA picks the MFMA form).  A training-mode
-        # forward raises.
+        # forward raises.  "fp8-2:4": the "fp8" engine with every fp8 block whose mask conforms to 2:4 (nm_prune) on the sparse
+        # fp8 MFMA kernel (engine.Engine.fp8_sparse_layers, csrc/conv_q8_sparse.hip); `sparse` stays None with it.
         self.precision = os.environ.get("MCAMD_PRECISION", "auto")
         # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA

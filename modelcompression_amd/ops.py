@@ -789,3 +789,45 @@ def cast_q8(src, pixels, src_ld, src_choff, C_, dst, dst_ld, dst_choff=0):
     """fp16 channel slice of `pixels` pixels -> e4m3(2 x) bytes (mcamd_cast_q8): the fp16 -> fp8 edge of the fp8 engine."""
     check(L.lib().mcamd_cast_q8(ptr(src), pixels, src_ld, src_choff, C_, ptr(dst), dst_ld, dst_choff, stream_ptr()),
           "mcamd_cast_q8")
+
+
+# ----------------------------------------------------------------------------- 2:4-sparse fp8 quantised inference
+def conv_fwd_q8_sparse24_ok(g):
+    """Does mcamd_conv_fwd_q8_sparse24 accept this geometry?  (Shared by the engine and the tests.)"""
+    return bool(L.lib().mcamd_conv_fwd_q8_sparse24_ok(C.byref(g)))
+
+
+def q8_sparse24_elems(g):
+    """(kept bytes, 32-bit index words, int32 exponents) of the 2:4 fp8 packing."""
+    out = (C.c_int64 * 3)()
+    check(L.lib().mcamd_q8_sparse24_elems(C.byref(g), out), "mcamd_q8_sparse24_elems")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def pack_q8_sparse24(g, w, mask=None, out_w=None, out_idx=None, out_exp=None):
+    """fp32 OIHW master (* mask) -> (kept e4m3 bytes, int32 index words, int32 exponent per filter) of the 2:4 fp8 forward
+    (mcamd_pack_q8_sparse24)."""
+    _need_cuda(w, mask)
+    assert w.dtype == torch.float32 and w.is_contiguous()
+    nw, ni, ne = q8_sparse24_elems(g)
+    if out_w is None:
+        out_w = torch.empty(nw, dtype=torch.uint8, device=w.device)
+    if out_idx is None:
+        out_idx = torch.empty(ni, dtype=torch.int32, device=w.device)
+    if out_exp is None:
+        out_exp = torch.empty(ne, dtype=torch.int32, device=w.device)
+    if out_w.numel() < nw or out_idx.numel() < ni or out_exp.numel() < ne:
+        raise L.McamdError("pack_q8_sparse24: destination too small")
+    check(L.lib().mcamd_pack_q8_sparse24(C.byref(g), ptr(w), ptr(mask), ptr(out_w), ptr(out_idx), ptr(out_exp), stream_ptr()),
+          "mcamd_pack_q8_sparse24")
+    return out_w, out_idx, out_exp
+
+
+def conv_fwd_q8_sparse24(g, x8, wq, idx, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None,
+                         y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False):
+    """conv_fwd_q8 on 2:4-compressed e4m3 weights (mcamd_conv_fwd_q8_sparse24): the same arguments plus the index words,
+    the same arithmetic and output."""
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff)
+    check(L.lib().mcamd_conv_fwd_q8_sparse24(C.byref(g), ptr(x8), ptr(wq), ptr(idx), ptr(wexp), C.byref(e), int(bool(y_f8)),
+                                             int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q8_sparse24")

@@ -2,7 +2,9 @@
 Prints the per-layer forward kernel times of both engines (HIP events around every launch, median of the instrumented
 passes; the cast pass of the fp16 -> fp8 edge is charged to its block), the whole forward of both engines alternated --
 three pairs of windows of at least 100 forwards each -- and the logits rel-L2 between them.
-usage: python tools/q8_bench.py [batch] [forwards per window] [--json PATH]"""
+--sparse: the model is nm_prune'd (2:4 masks) and four engines are measured the same way on the same masked weights: fp16,
+fp16 with sparse = "2:4", fp8 and fp8-2:4 (windows alternated over all four).
+usage: python tools/q8_bench.py [batch] [forwards per window] [--sparse] [--json PATH]"""
 import json
 import os
 import sys
@@ -18,11 +20,11 @@ def parse(argv):
     out_json = argv[argv.index("--json") + 1] if "--json" in argv else None
     if B < 1 or K < 1:
         raise SystemExit("q8_bench: batch and forwards per window must be positive")
-    return B, K, out_json
+    return B, K, out_json, "--sparse" in argv
 
 
 def main(argv):
-    B, K, out_json = parse(argv)
+    B, K, out_json, sparse = parse(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("q8_bench needs the GPU")
@@ -33,9 +35,16 @@ def main(argv):
     m.eval()
     x = synthetic_batch(B, 416, 416, seed=0, device=dev)
     modes = ("fp16", "fp8")
+    if sparse:
+        from modelcompression_amd.pruning.weightPruning.methods import nm_prune
+        m.set_masks(nm_prune(m))
+        modes = ("fp16", "fp16+2:4", "fp8", "fp8-2:4")
 
-    def engine(prec):
-        return [e for k, e in m._engines.items() if k[3] == prec and not e.train_layout][0]
+    def select(mode):
+        m.precision, m.sparse = mode.split("+")[0], "2:4" if mode.endswith("+2:4") else None
+
+    def engine(mode):
+        return [e for k, e in m._engines.items() if k[3] == mode.split("+")[0] and not e.train_layout][0]
 
     def layer_times(prec, passes=5):
         eng = engine(prec)
@@ -55,16 +64,18 @@ def main(argv):
     with torch.no_grad():
         res = {}
         for prec in modes:
-            m.precision = prec
+            select(prec)
             for _ in range(3):
                 y = m(x)
             torch.cuda.synchronize()
             res[prec] = {"logits": y.clone(), "layers": layer_times(prec)}
+            if prec == "fp16+2:4":
+                sparse_layers = list(engine(prec).sparse_layers)
         fp8_layers = list(engine("fp8").fp8_layers)
         rates = {p: [] for p in modes}
         for rep in range(3):                   # alternated: the two engines see the same host / GPU conditions
             for prec in modes:
-                m.precision = prec
+                select(prec)
                 for _ in range(5):
                     m(x)
                 torch.cuda.synchronize()
@@ -74,6 +85,8 @@ def main(argv):
                 torch.cuda.synchronize()
                 rates[prec].append(B * K / (time.perf_counter() - t0))
 
+    if sparse:
+        return report_sparse(B, K, out_json, modes, res, rates, fp8_layers, list(engine("fp8-2:4").fp8_sparse_layers), sparse_layers)
     d, s = res["fp16"], res["fp8"]
     rel = float((s["logits"].double() - d["logits"].double()).norm() / d["logits"].double().norm())
     print("fp8 layers (conv numbers): %s" % fp8_layers)
@@ -91,6 +104,34 @@ def main(argv):
         with open(out_json, "w") as f:
             json.dump({"B": B, "forwards_per_window": K, "fp8_layers": fp8_layers, "fp16_ms": d["layers"], "fp8_ms": s["layers"],
                        "fp16_img_s": rates["fp16"], "fp8_img_s": rates["fp8"], "pairs": pairs, "rel_l2": rel}, f, indent=1)
+
+
+def report_sparse(B, K, out_json, modes, res, rates, fp8_layers, fp8_sparse_layers, sparse_layers):
+    def rel(a, b):
+        return float((a.double() - b.double()).norm() / b.double().norm())
+    print("2:4 fp16 layers: %s\nfp8 layers: %s\n2:4 fp8 layers: %s" % (sparse_layers, fp8_layers, fp8_sparse_layers))
+    print("%-6s " % "conv" + " ".join("%12s" % (p + " ms") for p in modes) + "  fp8-2:4: /fp8  /fp16+2:4  /fp16")
+    ms = {p: res[p]["layers"] for p in modes}
+    for k in sorted(ms["fp16"]):
+        t = [ms[p].get(k, float("nan")) for p in modes]
+        print("%-6s " % ("conv%d" % k) + " ".join("%12.3f" % v for v in t)
+              + "  %12.2f %10.2f %6.2f" % (t[2] / t[3], t[1] / t[3], t[0] / t[3]))
+    tot = [sum(ms[p].values()) for p in modes]
+    print("%-6s " % "sum" + " ".join("%12.3f" % v for v in tot) + "  %12.2f %10.2f %6.2f" % (tot[2] / tot[3], tot[1] / tot[3], tot[0] / tot[3]))
+    for p in modes:
+        r = rates[p]
+        print("whole forward B=%d, %d forwards per window, %-9s %s img/s (spread %.2f %%)"
+              % (B, K, p + ":", ["%.0f" % v for v in r], 100.0 * (max(r) - min(r)) / min(r)))
+    pairs = {q: [b / a for a, b in zip(rates[q], rates["fp8-2:4"])] for q in modes[:3]}
+    for q in modes[:3]:
+        print("pairs fp8-2:4 / %s: %s" % (q, ["%.3f" % v for v in pairs[q]]))
+    rels = {p: rel(res[p]["logits"], res["fp16"]["logits"]) for p in modes[1:]}
+    print("logits rel-L2 against the fp16 engine (same masked weights): %s" % {p: "%.3e" % v for p, v in rels.items()})
+    if out_json:
+        with open(out_json, "w") as f:
+            json.dump({"B": B, "forwards_per_window": K, "mfma": os.environ.get("MCAMD_Q8_MFMA", "0"), "modes": list(modes),
+                       "sparse_layers": sparse_layers, "fp8_layers": fp8_layers, "fp8_sparse_layers": fp8_sparse_layers,
+                       "ms": ms, "img_s": rates, "pairs_fp8_2_4_over": pairs, "rel_l2_vs_fp16": rels}, f, indent=1)
 
 
 if __name__ == "__main__":
