@@ -255,7 +255,7 @@ int mcamd_q8_elems(const mcamd_conv_geom* g, int64_t out[2]);
 /* OIHW fp32 master (* mask, may be NULL) -> wq: bytes [Npad][kpos], kpos(t, c) = (c / 64) * k*k*64 + t * 64 + c % 64;
  * wexp: int32 [Npad] (e_f; pad rows: zero bytes, exponent 0).  Exponents are computed on the device. */
 int mcamd_pack_q8(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wq, int32_t* wexp, void* stream);
-/* The quantised block: epilogue mode MCAMD_EPI_PAD_F16 only, dst_mode PLAIN / POOL / REORG and y2 as mcamd_conv_fwd.
+/* The quantised block: epilogue mode MCAMD_EPI_PAD_F16 (inference; MCAMD_EPI_RAW_F32: the training form below), dst_mode PLAIN / POOL / REORG and y2 as mcamd_conv_fwd.
  * y_f8 / y2_f8 != 0: that destination is a padded NHWC BYTE buffer and receives q(2 v) (y_ld / y_choff count bytes);
  * 0: fp16 as mcamd_conv_fwd writes it.  Both `pad` forms of x. */
 int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
@@ -264,6 +264,41 @@ int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const void* wq, 
  * channels [dst_choff, +C); C, the leading dimensions and offsets multiples of 8.  Halo pixels are pixels like any other. */
 int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst, int32_t dst_ld,
                   int32_t dst_choff, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * fp8 quantisation-aware training (an addition beyond the reference; Darknet.precision = "fp8-qat"): the
+ * training-mode forward of an fp8 block runs in the deployment arithmetic above, its backward is straight-through.
+ *   forward   a8 = q(2 x) input codes, (w8, e_f) re-quantised from w = weight * mask every step (mcamd_pack_q8);
+ *             raw output y[m][f] = 2^-(e_f + 1) * sum a8 * w8, fp32 [B*H*W][y_ld] -- the convolution of x_q = deq(a8) / 2
+ *             with w_q = deq(w8) * 2^-e_f (the power of two is exact);
+ *             BatchNorm takes batch statistics of those fp32 values (biased variance; running statistics updated as
+ *             nn.BatchNorm2d does: mcamd_bn_coeffs on the slab below); v = leaky(scale_f * y + shift_f);
+ *             a destination the engine holds as bytes receives q(2 v) (POOL: q of 2 x the window maximum; REORG and the
+ *             full-resolution copy mapped as in inference), ONE rounding from fp32, and the fp16 buffer of the same tensor
+ *             deq(that byte) / 2, exact in fp16 (mcamd_act_desc.dst_q8 / dst2_q8); a destination a non-fp8 block reads
+ *             receives fp16(v);
+ *             at an fp16 -> fp8 edge the consumer's codes are q(2 x16) and mcamd_cast_q8_train writes deq(code) / 2 back
+ *             over the fp16 slice: the values the consumer's weight gradient multiplies.
+ *   backward  both quantisers are the identity (straight-through), WITHOUT a clipping mask: after BatchNorm |2 v| > 448
+ *             does not occur in practice.  G -> pool / reorg / route, LeakyReLU and BatchNorm backward from the saved fp32 y
+ *             (mcamd_bn_act_bwd, y_dtype 1: the pooled argmax is the forward's, taken on the unrounded activations) -> dY;
+ *             dX = dgrad(dY, fp16(w_q)), dW = wgrad(dY, x_q) * mask; master weights fp32.  fp16(w_q) is exact for
+ *             initialisation-sized weights (e4m3 has 4 significant bits; w_q leaves fp16's normal range only below 2^-14).
+ *   An inference-mode forward under "fp8-qat" is the "fp8" engine's, bit for bit.
+ * ------------------------------------------------------------------------- */
+/* mcamd_conv_fwd_q8 also takes epilogue mode MCAMD_EPI_RAW_F32 (y_f8 / y2_f8 ignored, no dst_mode / y2): y as above, and with
+ * epi->stats the per-channel sums and sums of squares of the fp32 values, row p over the pixels [128 p, 128 p + 128) --
+ * every row written, fixed summation order, no atomics; stats_rows must equal the query below, stats_ld >= round_up(cout,
+ * 256).  Both MCAMD_Q8_MFMA forms, both `pad` forms of x, any batch size. */
+int32_t mcamd_conv_fwd_q8_stats_rows(const mcamd_conv_geom* g);   /* 0 when the geometry has no fp8 form */
+/* w_q = deq(q(w * mask * 2^e_f)) * 2^-e_f as fp32 OIHW [cout][cin][k][k], e_f = wexp[f] as mcamd_pack_q8 wrote it for the same
+ * weights and mask: the values the forward's weight bytes stand for.  mcamd_pack_weights(_many) builds the dgrad operand
+ * from it (with no mask). */
+int mcamd_fakequant_q8(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, const int32_t* wexp,
+                       float* wq_oihw, void* stream);
+/* mcamd_cast_q8 that also writes deq(code) / 2 (exact in fp16) back over the source slice. */
+int mcamd_cast_q8_train(void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst, int32_t dst_ld,
+                        int32_t dst_choff, void* stream);
 
 /* ---------------------------------------------------------------------------
  * 2:4-sparse fp8 quantised inference (an addition beyond the reference; conv_q8_sparse.hip, Darknet.precision =
@@ -410,6 +445,13 @@ typedef struct mcamd_act_desc {
                                   the same fp16 value is written one fp16 step lower (~6e-4 of the elements of a random
                                   tensor), so that the backward pass routes the gradient where the fp32 forward did. */
     int32_t pool_act_ld, pool_act_pad;
+    void* dst_q8;              /* optional, NULL = none (fp32 y, planes 1, no pool_act): a BYTE twin of dst -- the same padded form,
+                                  resolution, dst_ld (bytes per pixel) and dst_choff, halo bytes 0x00 and never written.  It
+                                  receives the e4m3 codes q(2 v) of mcamd_conv_fwd_q8's contract (mode POOL: q of 2 x the window
+                                  maximum; REORG: mapped as dst), ONE rounding from fp32, and dst then receives deq(code) / 2
+                                  (exact in fp16) instead of fp16(v): the training-mode forward of an fp8 block
+                                  (Darknet.precision = "fp8-qat"), whose backward multiplies what the consumer's forward did. */
+    void* dst2_q8;             /* the same for dst2 (needs dst2) */
 } mcamd_act_desc;
 int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream);
 

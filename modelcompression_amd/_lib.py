@@ -37,7 +37,8 @@ class ActDesc(C.Structure):
                 ("dst2", C.c_void_p), ("dst2_ld", C.c_int32), ("dst2_choff", C.c_int32),
                 ("y_dtype", C.c_int32), ("planes", C.c_int32), ("dst_plane", C.c_int32), ("dst2_plane", C.c_int32),
                 ("dst_pad", C.c_int32), ("dst2_pad", C.c_int32), ("border", C.c_void_p), ("planes2", C.c_int32),
-                ("pool_act", C.c_void_p), ("pool_act_ld", C.c_int32), ("pool_act_pad", C.c_int32)]
+                ("pool_act", C.c_void_p), ("pool_act_ld", C.c_int32), ("pool_act_pad", C.c_int32),
+                ("dst_q8", C.c_void_p), ("dst2_q8", C.c_void_p)]
 
 
 class ChanMap(C.Structure):
@@ -153,6 +154,9 @@ SIGNATURES = {
     "mcamd_pack_q8_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P, _P]),
     "mcamd_conv_fwd_q8_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _P]),
     "mcamd_cast_q8": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "mcamd_conv_fwd_q8_stats_rows": (_I32, [C.POINTER(ConvGeom)]),
+    "mcamd_fakequant_q8": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
+    "mcamd_cast_q8_train": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _I32, _I32, _P]),
     "mcamd_conv_dgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _I32, _I32, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_wgrad_workspace_bytes": (_SZ, [C.POINTER(ConvGeom)]),
     "mcamd_conv_wgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _I32, _I32, _P, C.POINTER(ChanMap), _F, _P, _P, _P, _SZ, _P]),

@@ -469,7 +469,7 @@ static int fill_epilogue(IgemmArgs& a, const mcamd_conv_epilogue* e, int n_out, 
         MCAMD_REQUIRE(e->y_ld % 4 == 0 && e->y_choff % 4 == 0 && e->y_choff + n_out <= e->y_ld,
                       "%s: fp32 output slice [%d, %d) does not fit y_ld %d", what, e->y_choff, e->y_choff + n_out, e->y_ld);
         if (e->stats) {
-            MCAMD_REQUIRE(e->stats_rows == rows, "%s: stats_rows must be mcamd_conv_stats_rows_mode(g, 3) = %d (got %d)", what,
+            MCAMD_REQUIRE(e->stats_rows == rows, "%s: stats_rows must be %d, what the row query of this launch returns (got %d)", what,
                           rows, e->stats_rows);
             MCAMD_REQUIRE(e->stats_ld >= round_up_int(n_out, 256), "%s: stats_ld must be >= %d", what,
                           round_up_int(n_out, 256));
@@ -670,11 +670,31 @@ extern "C" int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const
     if (check_geom(g, "conv_fwd_q8")) return MCAMD_EINVAL;
     MCAMD_REQUIRE(mcamd_conv_fwd_q8_ok(g), "conv_fwd_q8: geometry has no fp8 form (mcamd_conv_fwd_q8_ok)");
     MCAMD_REQUIRE(x8 && wq && wexp, "conv_fwd_q8: null input");
-    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    MCAMD_REQUIRE(epi && (epi->mode == MCAMD_EPI_PAD_F16 || epi->mode == MCAMD_EPI_RAW_F32),
+                  "conv_fwd_q8: epilogue modes 2 (MCAMD_EPI_PAD_F16) and 3 (MCAMD_EPI_RAW_F32) only");
     IgemmArgs a;
     fill_operand(a, g, x8, wq, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
-    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    // (mode 2: no statistics; mode 3, the training form: one slab row per pixel tile)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8", epi->mode == MCAMD_EPI_RAW_F32 ? mcamd_conv_fwd_q8_stats_rows(g) : 0))
+        return MCAMD_EINVAL;
     return mcamd_conv_q8_launch(a, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
+}
+
+extern "C" int32_t mcamd_conv_fwd_q8_stats_rows(const mcamd_conv_geom* g) {
+    if (!mcamd_conv_fwd_q8_ok(g)) return 0;
+    return (int32_t)(((long long)g->B * g->H * g->W + MCAMD_Q8_TILE_M - 1) / MCAMD_Q8_TILE_M);
+}
+
+extern "C" int mcamd_fakequant_q8(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, const int32_t* wexp,
+                                  float* wq_oihw, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "fakequant_q8: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_fakequant_q8(&g_, w_oihw, mask_oihw, wexp, wq_oihw, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_ok(g), "fakequant_q8: geometry has no fp8 form (mcamd_conv_fwd_q8_ok)");
+    MCAMD_REQUIRE(w_oihw && wexp && wq_oihw, "fakequant_q8: null pointer");
+    return mcamd_fakequant_q8_launch(w_oihw, mask_oihw, wexp, wq_oihw, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -725,15 +745,27 @@ extern "C" int mcamd_conv_fwd_q8_sparse24(const mcamd_conv_geom* g, const void* 
     return mcamd_conv_q8_sparse_launch(a, idx, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
 }
 
-extern "C" int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst,
-                             int32_t dst_ld, int32_t dst_choff, void* stream) {
-    if (mcamd_recording())
-        return mcamd_rec_push(stream, [=](void* s) { return mcamd_cast_q8(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, s); });
+static int cast_q8_any(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst, int32_t dst_ld,
+                       int32_t dst_choff, int back, void* stream) {
     MCAMD_REQUIRE(src && dst && pixels > 0 && C > 0, "cast_q8: null pointer / empty");
     MCAMD_REQUIRE(C % 8 == 0 && src_ld % 8 == 0 && src_choff % 8 == 0 && dst_ld % 8 == 0 && dst_choff % 8 == 0 &&
                       src_choff >= 0 && dst_choff >= 0 && src_choff + C <= src_ld && dst_choff + C <= dst_ld,
                   "cast_q8: channel slices must be multiples of 8 inside their leading dimensions");
-    return mcamd_cast_q8_launch(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, (hipStream_t)stream);
+    return mcamd_cast_q8_launch(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, back, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst,
+                             int32_t dst_ld, int32_t dst_choff, void* stream) {
+    if (mcamd_recording())
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_cast_q8(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, s); });
+    return cast_q8_any(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, 0, stream);
+}
+
+extern "C" int mcamd_cast_q8_train(void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst,
+                                   int32_t dst_ld, int32_t dst_choff, void* stream) {
+    if (mcamd_recording())
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_cast_q8_train(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, s); });
+    return cast_q8_any(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, 1, stream);
 }
 
 extern "C" int mcamd_conv_dgrad(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff,

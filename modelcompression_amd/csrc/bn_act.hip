@@ -6,6 +6,7 @@
 // nn.LeakyReLU(0.1) (nets.py:809), nn.MaxPool2d(2,2) (nets.py:821), Reorg (nets.py:648-667),
 // torch.cat route (nets.py:738-746), and their autograd backward.
 #include "common.h"
+#include "conv_epi.h"   // e4m3_bytes4 / q8_to_f16: the byte destinations of the fp8 quantisation-aware training blocks
 
 // ------------------------------------------------------------------------------------
 // batch statistics -> affine coefficients
@@ -106,6 +107,8 @@ struct ActArgs {
     int dst2_pl;                // storage form of dst2 (mcamd_act_desc.planes2)
     half_t* pool_act;           // optional (pool): full-resolution fp16 activation for the backward pass (mcamd_act_desc.pool_act)
     int pool_act_ld, pool_act_pw;
+    char* dst_q8;               // optional (kernel form Q8): BYTE twins of dst / dst2, same geometry (mcamd_act_desc.dst_q8)
+    char* dst2_q8;
 };
 
 __device__ __forceinline__ void load8(const half_t* p, float* v) {
@@ -175,6 +178,22 @@ __device__ __forceinline__ void store_act(half_t* p, int plane, const float* v, 
         if (PL == 3) *(h8_t*)(p + 2 * plane) = hi;      // (PL == 2: the consumer wraps its third K part onto the hi plane)
     }
 }
+// One destination of an fp8 quantisation-aware training block (mcamd_act_desc.dst_q8): with a byte twin `q`
+// of the buffer, the codes e4m3(2 v) -- one rounding from fp32 -- go there and the fp16 buffer receives their values / 2
+// (exact in fp16), so that the backward pass multiplies what the consumer's forward multiplied; without one, fp16(v).
+__device__ __forceinline__ void store_act_q8(half_t* p, char* q, long long off, const float* v) {
+    if (!q) {
+        store_act<1>(p + off, 0, v);
+        return;
+    }
+    i32x2_t o;
+    o[0] = e4m3_bytes4(v), o[1] = e4m3_bytes4(v + 4);
+    *(i32x2_t*)(q + off) = o;
+    h8_t h = q8_to_f16(o[0], o[1]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = h[i] * (half_t)0.5f;
+    *(h8_t*)(p + off) = h;
+}
 // the largest fp16 value below h (bit pattern; h finite, not the most negative value)
 __device__ __forceinline__ unsigned short half_prev_bits(unsigned short b) {
     if (b == 0x0000 || b == 0x8000) return 0x8001;          // +-0 -> the smallest negative subnormal
@@ -197,7 +216,8 @@ __device__ __forceinline__ int border_class(int h, int w, int H, int W) {
 
 // FIXED: C/8 divides 256, so a thread keeps one channel group for the whole grid-stride loop and its BN
 // coefficients stay in registers.  !FIXED: any C % 8 == 0 (slim models), coefficients re-read per item (L1/L2 hits).
-template <int MODE, bool FIXED, bool Y32, int PL>
+// Q8 (fp32 y, one plane): the destinations may have byte twins (store_act_q8).
+template <int MODE, bool FIXED, bool Y32, int PL, bool Q8 = false>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(ActArgs a) {
     const int CH = a.C >> 3;
     int c8 = (threadIdx.x % CH) * 8;
@@ -231,7 +251,8 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(ActArgs a) {
                 float z = v[i] * sc[i] + sh[i];
                 v[i] = z > 0.f ? z : z * a.slope;
             }
-            store_act<PL>(a.dst + pad_off(b, h, w, a.H, a.W, a.dst_ld, a.dst_pw) + a.dst_choff + c8, a.dst_plane, v, a.dst_choff + c8);
+            if (Q8) store_act_q8(a.dst, a.dst_q8, pad_off(b, h, w, a.H, a.W, a.dst_ld, a.dst_pw) + a.dst_choff + c8, v);
+            else store_act<PL>(a.dst + pad_off(b, h, w, a.H, a.W, a.dst_ld, a.dst_pw) + a.dst_choff + c8, a.dst_plane, v, a.dst_choff + c8);
         } else {
             int b = (int)(pix / (Ho * Wo));
             int rem = (int)(pix - (long long)b * Ho * Wo);
@@ -253,15 +274,18 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(ActArgs a) {
                     float z = act[k][i] * sc[i] + sh[i];
                     act[k][i] = z > 0.f ? z : z * a.slope;
                 }
-                if (a.dst2) store_act2<PL>(a.dst2_pl, a.dst2 + pad_off(b, h, w, a.H, a.W, a.dst2_ld, a.dst2_pw) + a.dst2_choff + c8, a.dst2_plane, act[k], a.dst2_choff + c8);
+                if (Q8) {
+                    if (a.dst2) store_act_q8(a.dst2, a.dst2_q8, pad_off(b, h, w, a.H, a.W, a.dst2_ld, a.dst2_pw) + a.dst2_choff + c8, act[k]);
+                } else if (a.dst2) store_act2<PL>(a.dst2_pl, a.dst2 + pad_off(b, h, w, a.H, a.W, a.dst2_ld, a.dst2_pw) + a.dst2_choff + c8, a.dst2_plane, act[k], a.dst2_choff + c8);
             }
             long long dp = pad_off(b, ho, wo, Ho, Wo, a.dst_ld, a.dst_pw) + a.dst_choff;
             if (MODE == MCAMD_DST_POOL) {
                 float m[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) m[i] = fmaxf(fmaxf(act[0][i], act[1][i]), fmaxf(act[2][i], act[3][i]));
-                store_act<PL>(a.dst + dp + c8, a.dst_plane, m, a.dst_choff + c8);
-                if (a.pool_act) {
+                if (Q8) store_act_q8(a.dst, a.dst_q8, dp + c8, m);      // e4m3 of the window maximum
+                else store_act<PL>(a.dst + dp + c8, a.dst_plane, m, a.dst_choff + c8);
+                if (!Q8 && a.pool_act) {
                     // the four activations rounded to fp16, with the window's argmax (first maximum of the UNROUNDED values,
                     // what was just pooled) as their strict maximum: a neighbour that rounds to the same fp16 value is stored
                     // one step lower, so the backward pass finds the argmax the forward pass took from the stored values alone
@@ -293,7 +317,10 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(ActArgs a) {
                 }
             } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) store_act<PL>(a.dst + dp + k * a.C + c8, a.dst_plane, act[k], a.dst_choff + k * a.C + c8);
+                for (int k = 0; k < 4; ++k) {
+                    if (Q8) store_act_q8(a.dst, a.dst_q8, dp + k * a.C + c8, act[k]);
+                    else store_act<PL>(a.dst + dp + k * a.C + c8, a.dst_plane, act[k], a.dst_choff + k * a.C + c8);
+                }
             }
         }
     }
@@ -1305,9 +1332,14 @@ extern "C" int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream) {
     const bool fixed = CH <= 256 && 256 % CH == 0;
     const bool y32 = d->y_dtype == 1;
     MCAMD_REQUIRE(planes != 4 || y32, "bn_act_fwd: planes 4 (e4m3 corrections) goes with an fp32 y");
+    const bool q8 = d->dst_q8 || d->dst2_q8;
+    MCAMD_REQUIRE(!q8 || (y32 && planes == 1 && planes2 == 1 && !d->pool_act && (!d->dst2_q8 || d->dst2)),
+                  "bn_act_fwd: byte destinations (dst_q8 / dst2_q8) go with an fp32 y, one plane, no pool_act, and dst2_q8 with dst2");
+    a.dst_q8 = (char*)d->dst_q8, a.dst2_q8 = (char*)d->dst2_q8;
 #define ACT_INST(MODE_, FIXED_)                                                                                         \
     do {                                                                                                                \
-        if (y32 && planes == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<MODE_, FIXED_, true, 4>), dim3(grid), dim3(256), 0, st, a);       \
+        if (q8) hipLaunchKernelGGL((bn_act_fwd_kernel<MODE_, FIXED_, true, 1, true>), dim3(grid), dim3(256), 0, st, a);                 \
+        else if (y32 && planes == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<MODE_, FIXED_, true, 4>), dim3(grid), dim3(256), 0, st, a);       \
         else if (y32 && planes == 3) hipLaunchKernelGGL((bn_act_fwd_kernel<MODE_, FIXED_, true, 3>), dim3(grid), dim3(256), 0, st, a);  \
         else if (y32 && planes == 2) hipLaunchKernelGGL((bn_act_fwd_kernel<MODE_, FIXED_, true, 2>), dim3(grid), dim3(256), 0, st, a);  \
         else if (y32) hipLaunchKernelGGL((bn_act_fwd_kernel<MODE_, FIXED_, true, 1>), dim3(grid), dim3(256), 0, st, a);                 \

@@ -1,5 +1,7 @@
 // fp8 (OCP e4m3) implicit-GEMM convolution forward for gfx950 (MI355X), inference epilogue (an addition beyond the
-// reference: post-training quantised inference, Darknet.precision = "fp8").
+// reference: post-training quantised inference, Darknet.precision = "fp8") -- and, for quantisation-aware
+// training (Darknet.precision = "fp8-qat"), the same kernel with a raw fp32 epilogue + BatchNorm partial sums,
+// the fake quantisation of the weights and the training form of the cast pass.
 //
 //   S[n][m] = sum_{tap, c} W8[n][kpos(tap, c)] * X8[pixel(m) + tap][c]        (fp32 accumulation of exact products)
 //   v       = leaky(scale[n] * 2^-(e[n] + 1) * S + shift[n])
@@ -31,7 +33,14 @@
 // byte.  F8MFMA = true (MCAMD_Q8_MFMA=1): one v_mfma_scale_f32_32x32x64_f8f6f4 per block and chunk, half the MFMA time --
 // but that instruction (and the non-scaled fp8 one) drops products more than ~14 bits below the largest of their group
 // of 8, which flips ~6e-4 of the output bytes to the adjacent code.
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+//
+// RAW (training, Darknet.precision = "fp8-qat"): the same main loop with the MCAMD_EPI_RAW_F32 epilogue --
+// y[m][n] = 2^-(e[n] + 1) * S as fp32 [M][y_ld] (the power of two is exact) plus, per channel, the sum and the sum of squares
+// of those fp32 values over the workgroup's pixel tile: slab row = the pixel tile mt, every row written, fixed order, no
+// atomics.  Each wave transposes its accumulators through a private LDS region, 32 pixels at a time ([pixel][channel], rows
+// WM + 4 floats apart: the 16-byte writes of 8 pixels fall on 8 different bank slots), stores whole channel runs and adds
+// the 32 rows of a column in order; pixels past M go down as zeros and are not stored.
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW>
 __global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
 void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8) {
     constexpr int WAVES_N = BNP / WN;
@@ -160,6 +169,65 @@ void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_
 
     // ------------------------------- epilogue -------------------------------
     __syncthreads();                               // every wave is done with the stage buffers
+    if constexpr (RAW) {
+        constexpr int PF = WM + 4, C4 = WM / 4;    // floats between the pixel rows of a wave's region; float4 pieces per row
+        constexpr int REGION = 32 * PF;            // floats per wave
+        static_assert((NT / 64) * REGION * 4 + WAVES_N * BMW * 2 * 4 <= NSTAGE * STAGE_BYTES, "raw epilogue inside the ring");
+        float* tile = (float*)smem + wave * REGION;
+        float* comb = (float*)smem + (NT / 64) * REGION;          // [WAVES_N][BMW][2] partial sums of the pixel waves
+        float* y = (float*)a.y;
+        float s1 = 0.f, s2 = 0.f;                  // lane c < WM: channel wm * WM + c over this wave's WN pixels
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int m0 = mt * BNP + wn * WN + j * 32;
+            const bool live = m0 + (lane & 31) < a.M;
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int ch0 = i * 32 + 8 * g + 4 * (lane >> 5);
+                    f32x4_t v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)    // (rows up to Npad = round_up(N, 256) exist: zero bytes, exponent 0)
+                        v[e] = live ? ldexpf(acc[i][j][4 * g + e], -(wexp[nt * BMW + wm * WM + ch0 + e] + 1)) : 0.f;
+                    *(f32x4_t*)(tile + (lane & 31) * PF + ch0) = v;
+                }
+            __syncthreads();
+            for (int slot = lane; slot < 32 * C4; slot += 64) {
+                const int row = slot / C4, c4 = slot - row * C4;
+                const int m = m0 + row, n0 = nt * BMW + wm * WM + c4 * 4;
+                if (m < a.M && n0 < a.N) *(f32x4_t*)(y + (long long)m * a.y_ld + a.y_choff + n0) = *(const f32x4_t*)(tile + row * PF + c4 * 4);
+            }
+            if (a.stats && lane < WM) {
+#pragma unroll 8
+                for (int p = 0; p < 32; ++p) {
+                    const float v = tile[p * PF + lane];
+                    s1 += v;
+                    s2 += v * v;
+                }
+            }
+            __syncthreads();
+        }
+        if (a.stats) {                             // (wave-uniform)
+            if (lane < WM) {
+                comb[(wn * BMW + wm * WM + lane) * 2] = s1;
+                comb[(wn * BMW + wm * WM + lane) * 2 + 1] = s2;
+            }
+            __syncthreads();
+            if (tid < BMW) {
+                float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+                for (int k = 0; k < WAVES_N; ++k) {
+                    t1 += comb[(k * BMW + tid) * 2];
+                    t2 += comb[(k * BMW + tid) * 2 + 1];
+                }
+                // channels in [N, round_up(N, BMW)) come out as zeros: stats_ld >= round_up(N, 256) holds them
+                a.stats[((long long)mt * 2 + 0) * a.stats_ld + nt * BMW + tid] = t1;
+                a.stats[((long long)mt * 2 + 1) * a.stats_ld + nt * BMW + tid] = t2;
+            }
+        }
+        return;
+    }
     const bool has2 = a.y2 != nullptr;
     const bool need_b = y_f8 || (has2 && y2_f8), need_h = !y_f8 || (has2 && !y2_f8);
     // tile rows are PB = BMW + 8 elements apart: the 32 pixels of a wave's write then fall on 32 different LDS banks (a
@@ -176,7 +244,7 @@ void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_
     if (sat && a.overflow) atomicOr(a.overflow, 1);
 }
 
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW = false>
 static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, hipStream_t st) {
     constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
     constexpr int RING = NSTAGE * (BMW + BNP) * 64;
@@ -185,8 +253,8 @@ static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, 
     constexpr int LDS = RING > TILES ? RING : TILES;
     const bool has2 = a.y2 != nullptr;
     const bool mixed = (y_f8 || (has2 && y2_f8)) && (!y_f8 || (has2 && !y2_f8));
-    const int lds = mixed ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);
-    auto kern = conv_q8_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
+    const int lds = (mixed && !RAW) ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);   // (RAW: its tiles lie inside the ring)
+    auto kern = conv_q8_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA, RAW>;
     MCAMD_LDS_OPT_IN(kern, LDS);
     a.num_mtiles = (a.M + BNP - 1) / BNP;
     a.num_ntiles = (a.N + BMW - 1) / BMW;
@@ -201,6 +269,15 @@ static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, 
 // MCAMD_Q8_MFMA: 0 = fp16 MFMAs on converted bytes, 1 = the block-scaled fp8 MFMA.
 int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st) {
     const int* we = (const int*)wexp;
+    if (a.mode == MCAMD_EPI_RAW_F32) {             // training: fp32 y + statistics, the same tile per filter count
+        if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {
+            if (a.N >= 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true, true>(a, we, 0, 0, st);
+            if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true, true>(a, we, 0, 0, st);
+            return conv_q8_launch_t<64, 128, 32, 64, 3, true, true>(a, we, 0, 0, st);
+        }
+        if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false, true>(a, we, 0, 0, st);
+        return conv_q8_launch_t<64, 128, 32, 64, 3, false, true>(a, we, 0, 0, st);
+    }
     if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {       // the fp8 MFMA: faster, not byte-exact (see the kernel's comment)
         if (a.N >= 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st);
         if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st);
@@ -274,7 +351,10 @@ int mcamd_pack_q8_launch(const float* w, const float* mask, void* wq, void* wexp
 // cast pass of an fp16 -> fp8 edge: fp16 [pixels][src_ld] channels [src_choff, +C) -> e4m3(2 x) bytes [pixels][dst_ld]
 // channels [dst_choff, +C), halo pixels included (0 -> 0x00).  8 channels per thread.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cast_q8_kernel(const half_t* __restrict__ src, long long pixels, int src_ld, int src_choff,
+// BACK (training): the values the codes stand for, deq(code) / 2 (exact in fp16), are written back over the
+// fp16 source, so that the consumer's weight gradient multiplies what its forward multiplied.
+template <bool BACK>
+__global__ __launch_bounds__(256) void cast_q8_kernel(half_t* __restrict__ src, long long pixels, int src_ld, int src_choff,
                                                       int C, char* __restrict__ dst, int dst_ld, int dst_choff) {
     const int c8 = C / 8;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -288,13 +368,57 @@ __global__ __launch_bounds__(256) void cast_q8_kernel(const half_t* __restrict__
     i32x2_t o;
     o[0] = e4m3_bytes4(v), o[1] = e4m3_bytes4(v + 4);
     *(i32x2_t*)(dst + p * dst_ld + dst_choff + c) = o;
+    if (BACK) {
+        h8_t r = q8_to_f16(o[0], o[1]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) r[i] = r[i] * (half_t)0.5f;
+        *(h8_t*)(src + p * src_ld + src_choff + c) = r;
+    }
 }
 
 int mcamd_cast_q8_launch(const void* src, long long pixels, int src_ld, int src_choff, int C, void* dst, int dst_ld,
-                         int dst_choff, hipStream_t st) {
+                         int dst_choff, int back, hipStream_t st) {
     const long long total = pixels * (C / 8);
-    hipLaunchKernelGGL(cast_q8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const half_t*)src, pixels, src_ld,
-                       src_choff, C, (char*)dst, dst_ld, dst_choff);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (back) hipLaunchKernelGGL(cast_q8_kernel<true>, grid, dim3(256), 0, st, (half_t*)src, pixels, src_ld, src_choff, C, (char*)dst, dst_ld, dst_choff);
+    else hipLaunchKernelGGL(cast_q8_kernel<false>, grid, dim3(256), 0, st, (half_t*)src, pixels, src_ld, src_choff, C, (char*)dst, dst_ld, dst_choff);
     MCAMD_LAUNCH_CHECK("cast_q8");
+    return MCAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// fake quantisation of the weights (training): w_q = deq(e4m3(clamp(w * mask * 2^e))) * 2^-e as fp32 OIHW, e =
+// the exponent table pack_q8_kernel wrote for the same weights -- the values the forward's weight bytes stand for.  The fp16
+// packers build the dgrad operand from it.  Four consecutive weights per thread (cin * taps is a multiple of 64).
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fakequant_q8_kernel(const float* __restrict__ w, const float* __restrict__ mask,
+                                                           const int* __restrict__ wexp, float* __restrict__ out,
+                                                           long long total4, int per_filter) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total4) return;
+    const long long s = 4 * t;
+    const int e = wexp[s / per_filter];
+    f32x4_t v = *(const f32x4_t*)(w + s);
+    if (mask) {
+        const f32x4_t m = *(const f32x4_t*)(mask + s);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] *= m[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = fminf(fmaxf(ldexpf(v[i], e), -448.f), 448.f);
+    int b = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+    b = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], b, true);
+    f32x4_t r;
+    r[0] = ldexpf(__builtin_amdgcn_cvt_f32_fp8(b, 0), -e), r[1] = ldexpf(__builtin_amdgcn_cvt_f32_fp8(b, 1), -e);
+    r[2] = ldexpf(__builtin_amdgcn_cvt_f32_fp8(b, 2), -e), r[3] = ldexpf(__builtin_amdgcn_cvt_f32_fp8(b, 3), -e);
+    *(f32x4_t*)(out + s) = r;
+}
+
+int mcamd_fakequant_q8_launch(const float* w, const float* mask, const void* wexp, float* out, int cout, int cin, int ntaps,
+                              hipStream_t st) {
+    const long long total4 = (long long)cout * cin * ntaps / 4;
+    hipLaunchKernelGGL(fakequant_q8_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, w, mask, (const int*)wexp, out,
+                       total4, cin * ntaps);
+    MCAMD_LAUNCH_CHECK("fakequant_q8");
     return MCAMD_OK;
 }

@@ -102,8 +102,12 @@ int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, vo
 // conv_q8.hip: e4m3 operands (byte strides in `a`), mode 2 epilogue with a format per destination; packer; cast pass
 int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
 int mcamd_pack_q8_launch(const float* w, const float* mask, void* wq, void* wexp, int cout, int cin, int ntaps, hipStream_t st);
+// (a.mode MCAMD_EPI_RAW_F32: the training form, fp32 y + one statistics row per pixel tile of MCAMD_Q8_TILE_M pixels)
+#define MCAMD_Q8_TILE_M 128
 int mcamd_cast_q8_launch(const void* src, long long pixels, int src_ld, int src_choff, int C, void* dst, int dst_ld,
-                         int dst_choff, hipStream_t st);
+                         int dst_choff, int back, hipStream_t st);
+int mcamd_fakequant_q8_launch(const float* w, const float* mask, const void* wexp, float* out, int cout, int cin, int ntaps,
+                              hipStream_t st);
 // conv_q8_sparse.hip: conv_q8.hip's block on 2:4-compressed e4m3 weights (sparse MFMA); packer
 int mcamd_conv_q8_sparse_launch(IgemmArgs& a, const void* idx, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
 int mcamd_pack_q8_sparse24_launch(const float* w, const float* mask, void* wq, void* idx, void* wexp, int cout, int cin,

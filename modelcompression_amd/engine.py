@@ -144,17 +144,22 @@ class Engine:
         "fp8" -- inference only: the "fp16" engine with every eligible block on e4m3 activations and weights
         (csrc/conv_q8.hip, `fp8_layers`, _update_q8); a training-mode forward raises.
         "fp8-2:4" -- the "fp8" engine with every fp8 block whose mask conforms to 2:4 on the sparse fp8 kernel
-        (csrc/conv_q8_sparse.hip, `fp8_sparse_layers`); every other block runs what "fp8" runs."""
-        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4"):
-            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8' or 'fp8-2:4' (got %r)" % (precision,))
+        (csrc/conv_q8_sparse.hip, `fp8_sparse_layers`); every other block runs what "fp8" runs.
+        "fp8-qat" -- fp8 quantisation-aware training: in training mode every block of `fp8_layers` runs its
+        forward in the "fp8" arithmetic on batch statistics (mcamd_conv_fwd_q8 with the fp32 raw epilogue, byte + dequantised
+        fp16 destinations) and a straight-through backward on the fp16 kernels; every other block trains as in "fp16".  An
+        inference-mode forward is the "fp8" engine's, bit for bit."""
+        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-qat"):
+            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4' or 'fp8-qat' (got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision not in ("fp16", "fp8", "fp8-2:4")
+        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-qat")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_update_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision in ("fp8", "fp8-2:4")
+        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-qat")
+        self.qat = precision == "fp8-qat"      # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
         # "fp8-2:4": the subset of fp8_layers whose masks conform to 2:4 and that run mcamd_conv_fwd_q8_sparse24
         self.q8_sparse = precision == "fp8-2:4"
@@ -651,6 +656,10 @@ class Engine:
         # Split-operand engines: forward = fp16 of [w_hi | w_hi | w_lo] along the input channels (w_hi = fp16(w * mask),
         # w_lo = fp16(w * mask - w_hi)), matching the [x_hi | x_lo | x_hi] activation planes, written by the one-launch
         # packer itself (mcamd_pack_job.split); dgrad = the plain fp16 packing (the backward pass multiplies plain operands)
+        if self.q8 and mkeys != self._q8_keys:      # (in front of the job table: it names the fp8 blocks' w_q)
+            self._update_q8()
+            self._q8_keys = mkeys
+            self._pack_key = None
         tkey = tuple((s_[0], None if s_[2] is None else s_[2][0]) for s_ in sig)
         if tkey != self._pack_key:          # weight / mask storage moved, or the compaction changed: new job table
             jobs, self._pack_keep = [], []
@@ -669,6 +678,10 @@ class Engine:
                     jobs.append(dict(w=lay.waug, mask=None, rows=None, cols=None, cout=lay.n_act, cin=lay.fold_aug,
                                      ksize=lay.k, dst_fwd=lay.wp, dst_dgrad=lay.wd, split=split, f8_wexp=lay.f8_wexp_eff))
                     continue
+                if self._qat_train(lay):     # straight-through backward: the dgrad operand is fp16(w_q) (no mask: it is in w_q)
+                    jobs.append(dict(w=lay.w_q, mask=None, rows=None, cols=None, cout=lay.cout, cin=lay.cin, ksize=lay.k,
+                                     dst_fwd=None, dst_dgrad=lay.wd, split=0))
+                    continue
                 jobs.append(dict(w=w, mask=mask, rows=lay.g_rows, cols=lay.g_cols, cout=lay.n_act, cin=lay.cin, ksize=lay.k,
                                  dst_fwd=lay.wp, dst_dgrad=lay.wd, split=split, f8_wexp=lay.f8_wexp_eff))
             self._pack_table = ops.pack_table(jobs, self.device) if jobs else None
@@ -677,9 +690,6 @@ class Engine:
         if skeys != self._sparse_keys:
             self._update_sparse()
             self._sparse_keys = skeys
-        if self.q8 and mkeys != self._q8_keys:
-            self._update_q8()
-            self._q8_keys = mkeys
         for lay in self.layers:
             mask = lay.conv.mask.contiguous() if lay.conv.mask_flag else None
             if lay.sp_on:
@@ -689,6 +699,8 @@ class Engine:
                     ops.pack_q8_sparse24(lay.geom_act, lay.conv.weight.data, mask, lay.wqs, lay.widx8, lay.wexp)
                 else:
                     ops.pack_q8(lay.geom_act, lay.conv.weight.data, mask, lay.wq, lay.wexp)
+                    if self._qat_train(lay):   # the values those bytes stand for, fp32 OIHW: the dgrad packing's source
+                        ops.fakequant_q8(lay.geom_act, lay.conv.weight.data, mask, lay.wexp, lay.w_q)
             if lay.stem:
                 ops.pack_weights(lay.geom_act, lay.conv.weight.data, mask, True, False, lay.wp, None, rows=lay.g_rows)
             if getattr(lay, "stem_split", False):          # hi and lo stem packings of the split-operand fused first block
@@ -786,11 +798,16 @@ class Engine:
         self._plan_epoch += 1             # recorded forward plans name the fp16, the fp8 or the sparse fp8 launch of a block
         for lay in self.layers:
             lay.q8_on, lay.q8_y, lay.q8_y2, lay.xq, lay.q8s_on = False, False, False, None, False
+            if getattr(lay, "y_f16", None) is not None:
+                lay.y, lay.stats = lay.y_f16, lay.stats_f16
         self.fp8_layers, self.fp8_sparse_layers = [], []
         dev = self.device
+        # "fp8-qat" training engines keep their small images in the shared-halo form (both kernels read it); the set of
+        # blocks is the inference engine's: the same predicate on everything that does not depend on the layout
+        qat_train = self.qat and self.train_layout
         for lay in self.layers:
             if (lay.li > 0 and not lay.stem and not lay.is_last and lay.cin % 64 == 0 and lay.fold is None
-                    and lay.g_cols is None and lay.g_rows is None and lay.n_act == lay.cout and not lay.pad
+                    and lay.g_cols is None and lay.g_rows is None and lay.n_act == lay.cout and (qat_train or not lay.pad)
                     and self._fused_eval(lay) and ops.conv_fwd_q8_ok(lay.geom_act)):
                 lay.q8_on = True
                 self.fp8_layers.append(lay.li + 1)     # conv number (conv1 = the first block)
@@ -834,18 +851,73 @@ class Engine:
             if ws and all(w.q8_on for w in ws) and all(r.q8_on for r in readers[t.buf]):
                 live.add(t.buf)
                 if t.buf not in self.qbufs:
-                    self.qbufs[t.buf] = ops.alloc_padded_q8(self.B, t.H, t.W, t.ld, dev)
+                    self.qbufs[t.buf] = ops.alloc_padded_q8(self.B, t.H, t.W, t.ld, dev, pad=self._pad_for(t.W))
             else:
+                if qat_train and readers[t.buf] != [lay]:
+                    # the training cast writes the dequantised values back over the fp16 slice, which is safe only when
+                    # this block is the buffer's one reader (forward and weight gradient)
+                    raise NotImplementedError("fp8-qat: conv%d reads an fp16 tensor that another block reads too"
+                                              % (lay.li + 1))
                 key = (self.B, t.H, t.W, t.ld)
                 if getattr(lay, "_xq_key", None) != key:
-                    lay._xq, lay._xq_key = ops.alloc_padded_q8(self.B, t.H, t.W, t.ld, dev), key
+                    lay._xq, lay._xq_key = ops.alloc_padded_q8(self.B, t.H, t.W, t.ld, dev, pad=self._pad_for(t.W)), key
                 lay.xq = lay._xq
+            if qat_train:
+                # fp32 raw output + its statistics slab (the fp16 ones come back when the block leaves the set), and w_q
+                if getattr(lay, "y_f16", None) is None:
+                    lay.y_f16, lay.stats_f16 = lay.y, lay.stats
+                    lay.y_f32 = torch.zeros(lay.M * lay.cout, dtype=torch.float32, device=dev)
+                    lay.stats_q8 = torch.zeros(ops.conv_fwd_q8_stats_rows(lay.geom_act), 2, ops.round_up(lay.cout, 256),
+                                               dtype=torch.float32, device=dev)
+                    lay.w_q = torch.zeros_like(lay.conv.weight.data)
+                lay.y, lay.stats = lay.y_f32, lay.stats_q8
         for b in [b for b in self.qbufs if b not in live]:
             del self.qbufs[b]
         for lay in self.layers:
             if lay.q8_on:
                 lay.q8_y = lay.out_t.buf in self.qbufs
                 lay.q8_y2 = lay.out2_t is not None and lay.out2_t.buf in self.qbufs
+
+    def _qat_train(self, lay):
+        """Does this block train in the fp8 arithmetic (a block of fp8_layers in an "fp8-qat" training engine)?"""
+        return self.qat and self.train_layout and getattr(lay, "q8_on", False)
+
+    def qat_block_io(self, conv_number):
+        """Debug accessor of an "fp8-qat" training engine: what fp8 block `conv_number` read and wrote in the last training
+        step, from the engine's own buffers, as CPU tensors (NCHW) -- `x8` input codes and `x16` the fp16 values beside them;
+        `y` the fp32 raw output; batch `scale` / `shift` / `mean` / `invstd`; `out8` (`out2_8`) output codes where the
+        destination is held as bytes, else None, and `out16` (`out2_16`) the fp16 buffer of the same tensor; `dst`;
+        `dy` the gradient wrt y times grad_scale (after a backward); `w_q` the weights the dgrad operand was packed from,
+        `wexp` their exponents; `gin` the gradient wrt the block's input slice times grad_scale."""
+        lay = self.layers[conv_number - 1]
+        if not self._qat_train(lay):
+            raise McamdError("conv%d is not an fp8 block of an fp8-qat training engine (fp8_layers = %r)"
+                             % (conv_number, self.fp8_layers))
+        B = self.B
+
+        def interior(buf, f8, t, C):
+            pad = self._pad_for(t.W)
+            v = ops.padded_view_q8(buf, B, t.H, t.W, t.ld, pad) if f8 else ops.padded_view(buf, B, t.H, t.W, t.ld, pad)
+            v = v[:, 1:-1, 1:-1, t.choff:t.choff + C].permute(0, 3, 1, 2).contiguous().cpu()
+            return v if f8 else v.float()
+        t, t2, ti = lay.out_t, lay.out2_t, lay.tin
+        cdst = 4 * lay.cout if lay.mode == L.DST_REORG else lay.cout
+        out = dict(x8=interior(lay.xq if lay.xq is not None else self.qbufs[ti.buf], True, ti, lay.cin),
+                   x16=interior(self.bufs[ti.buf], False, ti, lay.cin),
+                   y=lay.y.view(B, lay.H, lay.W, lay.cout).permute(0, 3, 1, 2).contiguous().cpu(),
+                   scale=lay.scale.cpu(), shift=lay.shift.cpu(), mean=lay.mean.cpu(), invstd=lay.invstd.cpu(), slope=lay.slope,
+                   out8=interior(self.qbufs[t.buf], True, t, cdst) if lay.q8_y else None,
+                   out16=interior(self.bufs[t.buf], False, t, cdst), out2_8=None, out2_16=None,
+                   dst={L.DST_PLAIN: "plain", L.DST_POOL: "pool", L.DST_REORG: "reorg"}[lay.mode],
+                   dy=ops.padded_view(lay.dy, B, lay.H, lay.W, lay.cout_p, lay.pad)[:, 1:-1, 1:-1, :lay.cout]
+                   .permute(0, 3, 1, 2).contiguous().float().cpu(),
+                   w_q=lay.w_q.cpu(), wexp=lay.wexp[:lay.cout].cpu(),
+                   gin=lay.gin.view(B, lay.H, lay.W, ti.ld)[..., ti.choff:ti.choff + lay.cin].permute(0, 3, 1, 2)
+                   .contiguous().float().cpu())
+        if t2 is not None:
+            out["out2_8"] = interior(self.qbufs[t2.buf], True, t2, lay.cout) if lay.q8_y2 else None
+            out["out2_16"] = interior(self.bufs[t2.buf], False, t2, lay.cout)
+        return out
 
     def q8_block_io(self, conv_number):
         """Debug accessor: what fp8 block `conv_number` read and wrote in the last forward, from the engine's own buffers,
@@ -1160,7 +1232,7 @@ class Engine:
                 if not lay.train_ok:
                     raise McamdError("conv block %d: training needs a BN channel count of 8 * (power of two), got %d"
                                      % (lay.index, lay.cout))
-        if training and self.q8:
+        if training and self.q8 and not self.qat:
             raise McamdError("precision %r is inference only (there is no fp8 training path): call model.eval() or "
                              "pick another precision for training" % (self.precision,))
         mode = None if training else getattr(self.model, "sparse", None)
@@ -1309,6 +1381,9 @@ class Engine:
                 self._timed('fwd', lay, ops.conv_fwd_padded, lay.geom_act, xin, lay.wp, self.bufs[t.buf], t.ld, t.choff,
                             lay.scale, lay.shift, lay.slope, **dst)
                 continue
+            if training and self._qat_train(lay):
+                self._qat_forward(lay, xin)
+                continue
             self._timed('fwd', lay, ops.conv_fwd_raw, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0, lay.stats if training else None)
             ops.bn_coeffs(lay.stats if training else None, lay.cout, lay.M, bn.weight.data, bn.bias.data,
                           bn.running_mean, bn.running_var, training, lay.scale, lay.shift, lay.mean, lay.invstd,
@@ -1320,6 +1395,29 @@ class Engine:
                            self.bufs[t2.buf] if t2 is not None else None,
                            t2.ld if t2 is not None else 0, t2.choff if t2 is not None else 0, border=lay.border,
                            dst_pad=self._pad_for(t.W), dst2_pad=self._pad_for(t2.W) if t2 is not None else 0)
+
+    def _qat_forward(self, lay, xin):
+        """Training-mode forward of an fp8 block ("fp8-qat"): the fp8 convolution's fp32 raw output and its
+        batch statistics, coefficients, then BatchNorm + LeakyReLU (+ pool / reorg / route) written as e4m3 codes into the
+        tensors the engine holds as bytes -- with the dequantised values in their fp16 buffers, which the backward pass
+        reads -- and as fp16 elsewhere."""
+        B, bn = self.B, lay.bn
+        x8 = self.qbufs.get(lay.tin.buf)
+        if lay.xq is not None:          # the fp16 -> fp8 edge: codes of the padded input slice, dequantised values written back
+            ti, x8 = lay.tin, lay.xq
+            self._timed('cast', lay, ops.cast_q8, xin, ops.padded_pixels(B, ti.H, ti.W, self._pad_for(ti.W)), ti.ld, ti.choff,
+                        lay.cin, x8, ti.ld, ti.choff, write_back=True)
+        self._timed('fwd', lay, ops.conv_fwd_q8_raw, lay.geom_act, x8, lay.wq, lay.wexp, lay.y, lay.cout, 0, lay.stats)
+        ops.bn_coeffs(lay.stats, lay.cout, lay.M, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, True,
+                      lay.scale, lay.shift, lay.mean, lay.invstd, momentum=bn.momentum if bn.momentum is not None else 0.1,
+                      eps=bn.eps)
+        t, t2 = lay.out_t, lay.out2_t
+        ops.bn_act_fwd(B, lay.H, lay.W, lay.cout, lay.y, lay.cout, 0, lay.scale, lay.shift, lay.slope, lay.mode,
+                       self.bufs[t.buf], t.ld, t.choff, self.bufs[t2.buf] if t2 is not None else None,
+                       t2.ld if t2 is not None else 0, t2.choff if t2 is not None else 0,
+                       dst_pad=self._pad_for(t.W), dst2_pad=self._pad_for(t2.W) if t2 is not None else 0,
+                       dst_q8=self.qbufs[t.buf] if lay.q8_y else None,
+                       dst2_q8=self.qbufs[t2.buf] if (t2 is not None and lay.q8_y2) else None)
 
     def _stem_split_forward(self, lay):
         """The first block of the "mixed" training precision: batch statistics of the split-operand conv output (nothing

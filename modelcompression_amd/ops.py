@@ -329,8 +329,10 @@ def unfold_wgrad(w, mask, rows, cols, beta, slope, n, cin_k, dwaug, dw, prod_dbe
 
 def bn_act_fwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, dst_ld, dst_choff=0, dst2=None,
                dst2_ld=0, dst2_choff=0, border=None, planes=1, dst_plane=0, dst2_plane=0, dst_pad=0, dst2_pad=0, planes2=0,
-               pool_act=None, pool_act_ld=0, pool_act_pad=0):
-    """`border`: optional fp32 [16, C] table added to the raw conv output by border class (slim models).
+               pool_act=None, pool_act_ld=0, pool_act_pad=0, dst_q8=None, dst2_q8=None):
+    """`dst_q8` / `dst2_q8`: byte twins of dst / dst2 (same geometry) that receive the e4m3 codes q(2 v) while the fp16
+    buffer receives deq(code) / 2 (mcamd_act_desc.dst_q8: the fp8 quantisation-aware training forward; fp32 y, planes 1).
+    `border`: optional fp32 [16, C] table added to the raw conv output by border class (slim models).
     `pool_act` (mode pool): padded fp16 buffer that receives the full-resolution activation for the block's backward pass
     (mcamd_act_desc.pool_act; bn_act_bwd(..., act=pool_act)).
     `y` may be fp16 or fp32 (conv_fwd_raw / conv_fwd_raw32).  planes=3: split (hi | lo | hi) activation storage of
@@ -351,6 +353,8 @@ def bn_act_fwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, ds
         d.border = border.data_ptr()
     if pool_act is not None:
         d.pool_act, d.pool_act_ld, d.pool_act_pad = pool_act.data_ptr(), pool_act_ld, pool_act_pad
+    d.dst_q8 = dst_q8.data_ptr() if dst_q8 is not None else None
+    d.dst2_q8 = dst2_q8.data_ptr() if dst2_q8 is not None else None
     check(L.lib().mcamd_bn_act_fwd(C.byref(d), stream_ptr()), "mcamd_bn_act_fwd")
 
 
@@ -755,9 +759,22 @@ def q8_elems(g):
     return int(out[0]), int(out[1])
 
 
-def alloc_padded_q8(B, H, W, ld, device):
-    """Zeroed padded-NHWC BYTE buffer [B][H+2][W+2][ld] of e4m3 activations (halo bytes 0x00 = +0), flat."""
-    return torch.zeros(B * (H + 2) * (W + 2) * ld, dtype=torch.uint8, device=device)
+def alloc_padded_q8(B, H, W, ld, device, pad=0):
+    """Zeroed padded-NHWC BYTE buffer [B][H+2][W+2][ld] of e4m3 activations (halo bytes 0x00 = +0), flat.
+    pad=1: the shared-halo form, B (H+1) (W+1) + W + 2 pixels from pixel (0, -1, -1) (training engines, W <= 26)."""
+    return torch.zeros(padded_pixels(B, H, W, pad) * ld, dtype=torch.uint8, device=device)
+
+
+def padded_pixels(B, H, W, pad=0):
+    """Pixels (halo included) of a padded activation buffer in the padded (0) / shared-halo (1) form."""
+    return B * (H + 1) * (W + 1) + W + 2 if pad else B * (H + 2) * (W + 2)
+
+
+def padded_view_q8(buf, B, H, W, ld, pad=0):
+    """[B][H+2][W+2][ld] view of a byte buffer from alloc_padded_q8 (shared-halo form: overlapping, as padded_view)."""
+    if pad:
+        return torch.as_strided(buf, (B, H + 2, W + 2, ld), ((H + 1) * (W + 1) * ld, (W + 1) * ld, ld, 1))
+    return buf[: B * (H + 2) * (W + 2) * ld].view(B, H + 2, W + 2, ld)
 
 
 def pack_q8(g, w, mask=None, out_w=None, out_exp=None):
@@ -785,10 +802,36 @@ def conv_fwd_q8(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slo
                                     stream_ptr()), "mcamd_conv_fwd_q8")
 
 
-def cast_q8(src, pixels, src_ld, src_choff, C_, dst, dst_ld, dst_choff=0):
-    """fp16 channel slice of `pixels` pixels -> e4m3(2 x) bytes (mcamd_cast_q8): the fp16 -> fp8 edge of the fp8 engine."""
-    check(L.lib().mcamd_cast_q8(ptr(src), pixels, src_ld, src_choff, C_, ptr(dst), dst_ld, dst_choff, stream_ptr()),
-          "mcamd_cast_q8")
+def cast_q8(src, pixels, src_ld, src_choff, C_, dst, dst_ld, dst_choff=0, write_back=False):
+    """fp16 channel slice of `pixels` pixels -> e4m3(2 x) bytes (mcamd_cast_q8): the fp16 -> fp8 edge of the fp8 engine.
+    `write_back` (training, mcamd_cast_q8_train): the fp16 slice is overwritten with deq(code) / 2."""
+    fn = L.lib().mcamd_cast_q8_train if write_back else L.lib().mcamd_cast_q8
+    check(fn(ptr(src), pixels, src_ld, src_choff, C_, ptr(dst), dst_ld, dst_choff, stream_ptr()),
+          "mcamd_cast_q8_train" if write_back else "mcamd_cast_q8")
+
+
+def conv_fwd_q8_stats_rows(g):
+    """Rows of the statistics slab conv_fwd_q8_raw writes for `g` (mcamd_conv_fwd_q8_stats_rows)."""
+    return int(L.lib().mcamd_conv_fwd_q8_stats_rows(C.byref(g)))
+
+
+def conv_fwd_q8_raw(g, x8, wq, wexp, y, y_ld, y_choff=0, stats=None):
+    """The training form of the quantised block (mcamd_conv_fwd_q8, MCAMD_EPI_RAW_F32): y[M][y_ld] fp32 = 2^-(e_f + 1) x
+    the sum of byte products; `stats`: fp32 [conv_fwd_q8_stats_rows(g)][2][stats_ld] slab of the fp32 values, or None."""
+    e = _epi(L.EPI_RAW_F32, y, y_ld, y_choff, stats=stats,
+             stats_rows_=stats.shape[0] if stats is not None else 0,
+             stats_ld=stats.shape[2] if stats is not None else 0)
+    check(L.lib().mcamd_conv_fwd_q8(C.byref(g), ptr(x8), ptr(wq), ptr(wexp), C.byref(e), 0, 0, stream_ptr()), "mcamd_conv_fwd_q8")
+
+
+def fakequant_q8(g, w, mask, wexp, out=None):
+    """fp32 OIHW w_q = deq(q(w * mask * 2^e_f)) * 2^-e_f from the exponents pack_q8 wrote (mcamd_fakequant_q8)."""
+    _need_cuda(w, mask, wexp)
+    assert w.dtype == torch.float32 and w.is_contiguous()
+    if out is None:
+        out = torch.empty_like(w)
+    check(L.lib().mcamd_fakequant_q8(C.byref(g), ptr(w), ptr(mask), ptr(wexp), ptr(out), stream_ptr()), "mcamd_fakequant_q8")
+    return out
 
 
 # ----------------------------------------------------------------------------- 2:4-sparse fp8 quantised inference
