@@ -335,6 +335,34 @@ int mcamd_conv_fwd_q8_sparse24(const mcamd_conv_geom* g, const void* x8, const v
 int mcamd_conv_dgrad(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff,
                      const void* wp_dgrad, const mcamd_conv_epilogue* epi, void* stream);
 
+/* The same launch, also taking the sums of the BatchNorm backward of the PLAIN block (BatchNorm + LeakyReLU, nothing
+ * pooled or reorg'ed behind it; nn.BatchNorm2d + nn.LeakyReLU under autograd, reference src/nets.py:802-809) whose
+ * output gradient G it stores: the tile is in LDS as fp16 on its way out, the block's stored activation at the same pixel
+ * and channel is this convolution's own forward input, so sum g_z and sum g_z xhat per channel -- the first pass of
+ * mcamd_bn_act_bwd with mcamd_act_bwd_desc.act, same formulas, same ill-conditioned-channel rule, on G AS STORED -- are
+ * formed here and mcamd_bn_act_bwd (mcamd_act_bwd_desc.sums) skips that pass.  Fixed summation order, no atomics.
+ * `sums` NULL (or sums->slab NULL): exactly mcamd_conv_dgrad. */
+typedef struct mcamd_dgrad_sums {
+    float* slab;               /* out: fp32 [rows][2][ld]; every row and every producer channel is written */
+    int32_t rows;              /* must equal mcamd_conv_dgrad_sums_rows(geom, epilogue.concurrent) */
+    int32_t ld;                /* >= C */
+    const void* act;           /* the producer's stored fp16 activation, as mcamd_act_bwd_desc.act: padded NHWC (act_pad 1:
+                                  shared-halo form) at this geometry's B, H, W, producer channel c at act_choff + c of act_ld */
+    int32_t act_ld, act_choff, act_pad;
+    const float* scale; const float* shift; const float* mean; const float* invstd;   /* the producer's, [C] */
+    float slope;               /* the producer's negative-side slope (> 0) */
+    const float* y;            /* the producer's saved fp32 raw output [B*H*W][y_ld] (channels from y_choff) or NULL: read
+                                  for ill-conditioned channels only, as mcamd_act_bwd_desc.y with `act` */
+    int32_t y_ld, y_choff;
+    int32_t ch_lo, C;          /* the producer's C channels are channels [ch_lo, ch_lo + C) of this launch's output
+                                  (multiples of 8; a concat member: its offset inside the consumer's input slice) */
+} mcamd_dgrad_sums;
+/* Slab rows such a launch writes, from the route function the launch asks; 0: the kernel this geometry gets cannot take
+ * sums (the caller keeps the two-pass mcamd_bn_act_bwd). */
+int32_t mcamd_conv_dgrad_sums_rows(const mcamd_conv_geom* g, int32_t concurrent);
+int mcamd_conv_dgrad_sums(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff,
+                          const void* wp_dgrad, const mcamd_conv_epilogue* epi, const mcamd_dgrad_sums* sums, void* stream);
+
 /* dW = wgrad(x, dy) * mask / grad_scale, written as fp32 OIHW -- autograd's weight gradient of
  * `self.weight * mask_var` followed by F.conv2d.  Deterministic (slab reduction, no atomics).
  * Fully pruned filters are skipped through `map` (may be NULL): the caller keeps the surviving filters first
@@ -514,6 +542,12 @@ typedef struct mcamd_act_bwd_desc {
                                   tensor whose statistics the forward pass took, its xhat is exact.
                                   MCAMD_BN_POOL_SUMS_POOLED=0 ignores the pointer. */
     int32_t pool_out_ld, pool_out_choff, pool_out_pad;
+    const float* sums;         /* optional (PLAIN blocks without g2, with `act`), NULL = none: the per-channel sums of the pass
+                                  that forms them are ALREADY in this slab -- fp32 [sums_rows][2][sums_ld], row p holding sum g_z
+                                  (index 0) and sum g_z xhat (index 1) of a part of the pixels -- written by the dgrad launch
+                                  that stored `g` (mcamd_conv_dgrad_sums below).  The call then runs the coefficient kernel and
+                                  the dY pass only: one read of `g` and `act` less. */
+    int32_t sums_rows, sums_ld;
 } mcamd_act_bwd_desc;
 size_t mcamd_bn_act_bwd_workspace_bytes(const mcamd_act_bwd_desc* d);
 int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, size_t workspace_bytes, void* stream);

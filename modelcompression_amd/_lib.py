@@ -65,7 +65,17 @@ class ActBwdDesc(C.Structure):
                 ("overflow", C.c_void_p), ("dy_pad", C.c_int32), ("skip_dead_param_grads", C.c_int32),
                 ("act", C.c_void_p), ("act_ld", C.c_int32), ("act_choff", C.c_int32), ("act_pad", C.c_int32),
                 ("pool_out", C.c_void_p), ("pool_out_ld", C.c_int32), ("pool_out_choff", C.c_int32),
-                ("pool_out_pad", C.c_int32)]
+                ("pool_out_pad", C.c_int32),
+                ("sums", C.c_void_p), ("sums_rows", C.c_int32), ("sums_ld", C.c_int32)]
+
+
+class DgradSums(C.Structure):
+    """mcamd_dgrad_sums (include/mcamd.h)."""
+    _fields_ = [("slab", C.c_void_p), ("rows", C.c_int32), ("ld", C.c_int32),
+                ("act", C.c_void_p), ("act_ld", C.c_int32), ("act_choff", C.c_int32), ("act_pad", C.c_int32),
+                ("scale", C.c_void_p), ("shift", C.c_void_p), ("mean", C.c_void_p), ("invstd", C.c_void_p),
+                ("slope", C.c_float), ("y", C.c_void_p), ("y_ld", C.c_int32), ("y_choff", C.c_int32),
+                ("ch_lo", C.c_int32), ("C", C.c_int32)]
 
 
 class FoldDesc(C.Structure):
@@ -158,6 +168,8 @@ SIGNATURES = {
     "mcamd_fakequant_q8": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
     "mcamd_cast_q8_train": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _I32, _I32, _P]),
     "mcamd_conv_dgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _I32, _I32, _P, C.POINTER(ConvEpilogue), _P]),
+    "mcamd_conv_dgrad_sums_rows": (_I32, [C.POINTER(ConvGeom), _I32]),
+    "mcamd_conv_dgrad_sums": (C.c_int, [C.POINTER(ConvGeom), _P, _I32, _I32, _P, C.POINTER(ConvEpilogue), C.POINTER(DgradSums), _P]),
     "mcamd_conv_wgrad_workspace_bytes": (_SZ, [C.POINTER(ConvGeom)]),
     "mcamd_conv_wgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _I32, _I32, _P, C.POINTER(ChanMap), _F, _P, _P, _P, _SZ, _P]),
     "mcamd_conv_wgrad_plan_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I32)]),

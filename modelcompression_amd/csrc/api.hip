@@ -768,13 +768,27 @@ extern "C" int mcamd_cast_q8_train(void* src, int64_t pixels, int32_t src_ld, in
     return cast_q8_any(src, pixels, src_ld, src_choff, C, dst, dst_ld, dst_choff, 1, stream);
 }
 
-extern "C" int mcamd_conv_dgrad(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff,
-                                const void* wp_dgrad, const mcamd_conv_epilogue* epi, void* stream) {
+// dgrad: the route of a launch with epilogue mode `mode` (0 or 1)
+static ConvRoute dgrad_route(const mcamd_conv_geom* g, bool concurrent, int mode) {
+    return conv_route(g, concurrent ? DIR_DGRAD_CONCURRENT : DIR_DGRAD, mode, MCAMD_DST_PLAIN, false);
+}
+
+extern "C" int32_t mcamd_conv_dgrad_sums_rows(const mcamd_conv_geom* g, int32_t concurrent) {
+    if (!g || g->stem) return 0;
+    const ConvRoute r = dgrad_route(g, concurrent != 0, MCAMD_EPI_RAW_F16);
+    return mcamd_igemm_sums_ok(r) ? r.rows : 0;
+}
+
+extern "C" int mcamd_conv_dgrad_sums(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff,
+                                     const void* wp_dgrad, const mcamd_conv_epilogue* epi, const mcamd_dgrad_sums* sums,
+                                     void* stream) {
     if (mcamd_recording()) {
         MCAMD_REQUIRE(g && epi, "conv_dgrad: null geometry / epilogue");
         const mcamd_conv_geom g_ = *g;
         const mcamd_conv_epilogue e_ = *epi;
-        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_dgrad(&g_, dy, dy_ld, dy_choff, wp_dgrad, &e_, s); });
+        if (!sums) return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_dgrad_sums(&g_, dy, dy_ld, dy_choff, wp_dgrad, &e_, nullptr, s); });
+        const mcamd_dgrad_sums s_ = *sums;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_dgrad_sums(&g_, dy, dy_ld, dy_choff, wp_dgrad, &e_, &s_, s); });
     }
     if (check_geom(g, "conv_dgrad")) return MCAMD_EINVAL;
     MCAMD_REQUIRE(g->x_wrap == 0 && g->x_f8 == 0, "conv_dgrad: x_wrap / x_f8 are forward-only fields");
@@ -788,9 +802,38 @@ extern "C" int mcamd_conv_dgrad(const mcamd_conv_geom* g, const void* dy, int32_
     MCAMD_REQUIRE(epi && epi->mode != MCAMD_EPI_PAD_F16 && !epi->stats && epi->dst_mode == 0 && !epi->y2,
                   "conv_dgrad: epilogue must be mode 0 (no stats) or 1");
     a.concurrent = epi->concurrent != 0;
-    const ConvRoute r = conv_route(g, a.concurrent ? DIR_DGRAD_CONCURRENT : DIR_DGRAD, epi->mode, MCAMD_DST_PLAIN, false);
+    const ConvRoute r = dgrad_route(g, a.concurrent, epi->mode);
     if (fill_epilogue(a, epi, g->cin, "conv_dgrad", r.rows)) return MCAMD_EINVAL;
+    if (sums && sums->slab) {
+        const mcamd_dgrad_sums* s = sums;
+        MCAMD_REQUIRE(epi->mode == MCAMD_EPI_RAW_F16, "conv_dgrad: producer sums go with epilogue mode 0");
+        MCAMD_REQUIRE(mcamd_igemm_sums_ok(r) && s->rows == r.rows,
+                      "conv_dgrad: sums.rows must be mcamd_conv_dgrad_sums_rows() = %d (got %d; 0: this launch cannot take sums)",
+                      mcamd_igemm_sums_ok(r) ? r.rows : 0, s->rows);
+        MCAMD_REQUIRE(s->act && s->scale && s->shift && s->mean && s->invstd, "conv_dgrad: sums: null argument");
+        MCAMD_REQUIRE(s->C > 0 && s->C % 8 == 0 && s->ch_lo >= 0 && s->ch_lo % 8 == 0 && s->ch_lo + s->C <= g->cin,
+                      "conv_dgrad: sums: producer columns [%d, %d) must be whole groups of 8 inside the %d channels of G",
+                      s->ch_lo, s->ch_lo + s->C, g->cin);
+        MCAMD_REQUIRE(s->ld >= s->C, "conv_dgrad: sums.ld (%d) must be >= C (%d)", s->ld, s->C);
+        MCAMD_REQUIRE(s->act_ld % 8 == 0 && s->act_choff % 8 == 0 && s->act_choff >= 0 && s->act_choff + s->C <= s->act_ld &&
+                          (s->act_pad == 0 || s->act_pad == 1),
+                      "conv_dgrad: sums: activation slice [%d, %d) does not fit act_ld %d", s->act_choff, s->act_choff + s->C, s->act_ld);
+        MCAMD_REQUIRE(!s->y || (s->y_ld % 4 == 0 && s->y_choff % 4 == 0 && s->y_choff >= 0 && s->y_choff + s->C <= s->y_ld),
+                      "conv_dgrad: sums: fp32 y slice [%d, %d) does not fit y_ld %d", s->y_choff, s->y_choff + s->C, s->y_ld);
+        MCAMD_REQUIRE(s->slope > 0.f, "conv_dgrad: sums need an invertible activation (slope > 0)");
+        a.bsum.slab = s->slab, a.bsum.ld = s->ld;
+        a.bsum.act = (const half_t*)s->act, a.bsum.act_ld = s->act_ld, a.bsum.act_choff = s->act_choff, a.bsum.act_pw = s->act_pad ? 1 : 2;
+        a.bsum.scale = s->scale, a.bsum.shift = s->shift, a.bsum.mean = s->mean, a.bsum.invstd = s->invstd;
+        a.bsum.y = s->y, a.bsum.y_ld = s->y_ld, a.bsum.y_choff = s->y_choff;
+        a.bsum.ch_lo = s->ch_lo, a.bsum.C = s->C;
+        a.bsum.slope = s->slope;
+    }
     return launch_route(a, r, g, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_dgrad(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff,
+                                const void* wp_dgrad, const mcamd_conv_epilogue* epi, void* stream) {
+    return mcamd_conv_dgrad_sums(g, dy, dy_ld, dy_choff, wp_dgrad, epi, nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -590,25 +590,7 @@ __global__ __launch_bounds__(256) void bn_plain_bwd_kernel(ActBwdArgs a) {
 // ILL-CONDITIONED when |gamma| < BN_ACT_T max(|beta|, 1).  Recovering xhat = (z - beta) / gamma from an fp16 activation
 // costs up to 2^-11 (|xhat| + |beta / gamma|); on the other channels that is at most 2^-11 (1 / BN_ACT_T + |xhat|).  With
 // |gamma| = |scale| / invstd the test is |scale| < BN_ACT_T max(|beta|, 1) invstd (gamma == 0 always included).
-constexpr float BN_ACT_T = 0.03125f;     // 2^-5
-
-// Per channel, xhat = (u - off) mul with u = z from the activation (off = beta, mul = 1 / gamma), or with u = the saved
-// fp32 y (off = mean, mul = invstd) where the channel is ill-conditioned and `have_y`.  Returns whether any channel of the
-// thread reads y.
-__device__ __forceinline__ bool act_xhat_source(const float (&sc)[8], const float (&sh)[8], const float (&mu)[8],
-                                                const float (&is)[8], bool have_y, float (&off)[8], float (&mul)[8],
-                                                bool (&usey)[8]) {
-    bool any = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float beta = sh[i] + mu[i] * sc[i];                                       // shift = beta - mean scale
-        usey[i] = have_y && fabsf(sc[i]) < BN_ACT_T * fmaxf(fabsf(beta), 1.f) * is[i];  // scale = gamma invstd
-        off[i] = usey[i] ? mu[i] : beta;
-        mul[i] = usey[i] ? is[i] : (sc[i] != 0.f ? is[i] / sc[i] : 0.f);
-        any |= usey[i];
-    }
-    return any;
-}
+// (BN_ACT_T and act_xhat_source: common.h -- the dgrad epilogue that takes a PLAIN block's sums applies the same rule)
 
 // The same two passes WITHOUT the saved raw output: LeakyReLU is invertible, so a PLAIN block's pre-activation is
 // recovered from the activation the forward pass stored for the consumer (fp16, the hi plane of split storage):
@@ -1157,7 +1139,7 @@ __global__ __launch_bounds__(256) void bn_pool_sums_kernel(ActBwdArgs a) {
     block_partials_to_slab(sb, sg, CH, a.slab, a.C);
 }
 
-__global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* slab, int nblocks, int C, double count,
+__global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* slab, int nblocks, int ld, int C, double count,
                                                                float inv_scale, float* dgamma, float* dbeta,
                                                                float* coef, const int* perm, int skip_from) {
     __shared__ double red[2][16][RED_CPB];
@@ -1166,8 +1148,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* slab
     double sb = 0.0, sg = 0.0;
     if (c < C) {
         for (int p = ry; p < nblocks; p += RED_RG) {
-            sb += (double)slab[((long long)p * 2 + 0) * C + c];
-            sg += (double)slab[((long long)p * 2 + 1) * C + c];
+            sb += (double)slab[((long long)p * 2 + 0) * ld + c];
+            sg += (double)slab[((long long)p * 2 + 1) * ld + c];
         }
     }
     block_reduce2(sb, sg, red);
@@ -1482,7 +1464,17 @@ extern "C" int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, si
         else if (y32) hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE, true>), dim3(grid), dim3(256), 0, st, a);    \
         else hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE, false>), dim3(grid), dim3(256), 0, st, a);            \
     } while (0)
-    if (pool_fast && a.pool_out && a.act) hipLaunchKernelGGL(bn_pool_sums_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+    // sums already taken (mcamd_act_bwd_desc.sums: the dgrad launch that wrote G formed them, mcamd_conv_dgrad_sums): no pass 0
+    const float* fin_slab = (const float*)a.slab;
+    int fin_rows = grid, fin_ld = d->C;
+    if (d->sums) {
+        MCAMD_REQUIRE(plain_fast && a.act, "bn_act_bwd: `sums` is for PLAIN blocks without a second gradient, with `act`");
+        MCAMD_REQUIRE(d->sums_rows > 0 && d->sums_ld >= d->C, "bn_act_bwd: sums_rows (%d) must be positive and sums_ld (%d) >= C",
+                      d->sums_rows, d->sums_ld);
+        fin_slab = d->sums, fin_rows = d->sums_rows, fin_ld = d->sums_ld;
+    }
+    if (d->sums) {   // pass 0 ran in that dgrad's epilogue
+    } else if (pool_fast && a.pool_out && a.act) hipLaunchKernelGGL(bn_pool_sums_kernel<true>, dim3(grid), dim3(256), 0, st, a);
     else if (pool_fast && a.pool_out) hipLaunchKernelGGL(bn_pool_sums_kernel<false>, dim3(grid), dim3(256), 0, st, a);
     else if (pool_fast) POOL_LAUNCH(0);
     else if (plain_fast) PLAIN_LAUNCH(0);
@@ -1490,7 +1482,7 @@ extern "C" int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, si
         BWD_LAUNCH(0)
     }
     MCAMD_LAUNCH_CHECK("bn_act_bwd reduce");
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((d->C + RED_CPB - 1) / RED_CPB), dim3(1024), 0, st, (const float*)a.slab, grid, d->C,
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((d->C + RED_CPB - 1) / RED_CPB), dim3(1024), 0, st, fin_slab, fin_rows, fin_ld, d->C,
                        count, 1.0f / d->grad_scale, d->dgamma, d->dbeta, coef, (const int*)d->chan_perm,
                        d->skip_dead_param_grads);
     MCAMD_LAUNCH_CHECK("bn_act_bwd finalize");

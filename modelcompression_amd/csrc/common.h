@@ -95,6 +95,28 @@ __device__ __forceinline__ long long pad_off(int b, int h, int w, int H, int W, 
     return (((long long)b * (H + pw) + h + 1) * (W + pw) + w + 1) * ld;
 }
 
+// BatchNorm backward from the stored activation (bn_act.hip; conv_epi.h store_raw_tile_sums): a channel is ILL-CONDITIONED
+// when |gamma| < BN_ACT_T max(|beta|, 1), see bn_act.hip.
+constexpr float BN_ACT_T = 0.03125f;     // 2^-5
+
+// Per channel, xhat = (u - off) mul with u = z from the activation (off = beta, mul = 1 / gamma), or with u = the saved
+// fp32 y (off = mean, mul = invstd) where the channel is ill-conditioned and `have_y`.  Returns whether any channel of the
+// thread reads y.
+__device__ __forceinline__ bool act_xhat_source(const float (&sc)[8], const float (&sh)[8], const float (&mu)[8],
+                                                const float (&is)[8], bool have_y, float (&off)[8], float (&mul)[8],
+                                                bool (&usey)[8]) {
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float beta = sh[i] + mu[i] * sc[i];                                       // shift = beta - mean scale
+        usey[i] = have_y && fabsf(sc[i]) < BN_ACT_T * fmaxf(fabsf(beta), 1.f) * is[i];  // scale = gamma invstd
+        off[i] = usey[i] ? mu[i] : beta;
+        mul[i] = usey[i] ? is[i] : (sc[i] != 0.f ? is[i] / sc[i] : 0.f);
+        any |= usey[i];
+    }
+    return any;
+}
+
 // XOR swizzle of the 16-byte chunks of an LDS row of CPR chunks (ds_read_b128 operand tiles).
 template <int CPR>
 __device__ __forceinline__ int swz(int row) {

@@ -188,6 +188,172 @@ __device__ __forceinline__ void store_raw_tile(const IgemmArgs& __restrict__ a, 
 }
 
 // ---------------------------------------------------------------------------------------
+// store_raw_tile for a dgrad launch whose output is the gradient G of a PLAIN BatchNorm + LeakyReLU block (a.bsum,
+// MCAMD_EPI_RAW_F16_SUMS instances): while the tile goes out, pass 0 of that block's BatchNorm backward
+// (bn_plain_bwd_act_kernel<0>, bn_act.hip) is taken on it -- per producer channel sum g_z and sum g_z xhat, from G AS
+// STORED (fp16, saturated: what pass 1 reads) and the 16 bytes of the producer's stored activation at the same pixel and
+// channels.  Same element formulas, same ill-conditioned-channel rule (act_xhat_source: only threads that hold such a
+// channel read the saved fp32 y).  Rows >= M and columns outside [ch_lo, ch_lo + C) contribute nothing.
+//
+// NT % (COLS / 8) == 0: a thread keeps the same 8 channels for all its slots, so the hoisted per-channel values are
+// computed once per tile, and its pixels advance by NT / CH rows (stepped, no division per slot).  The threads' partials
+// are reduced over the NT / CH threads that share a channel through LDS in a fixed order (layout of
+// block_partials_to_slab, bn_act.hip) into tot[]: ONE register per thread and value (2 COLS values on NT threads) lives
+// across the K loops of a persistent slot's M tiles; store_tile_sums_slab writes it to the slot's slab row at the end.  No
+// atomics: the sums do not depend on scheduling.
+//
+// The coefficient pointers are taken through an empty volatile asm: inlined without it, hipcc hoists the coefficient
+// loads and the address arithmetic above the K loop and every instance goes over its register budget.
+// `smem`: the tile ct = [ROWS][COLS] fp16 at its start; at least 16 (NT + 8) floats long (sums_lds_bytes).
+// ---------------------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ const T* pin_here(const T* p) {
+    asm volatile("" : "+s"(p));
+    return p;
+}
+__host__ __device__ constexpr int sums_vals(int cols, int nt) { return (2 * cols + nt - 1) / nt; }
+__host__ __device__ constexpr size_t sums_lds_bytes(int nt) { return (size_t)16 * (nt + 8) * sizeof(float); }
+
+__host__ __device__ constexpr int sums_slots(int rows, int cols, int nt) { return rows * (cols / 8) / nt; }
+// ... of which this many are fetched early: all, except in the 256 x 256 ping-pong tile, whose 128 accumulator registers
+// leave room for 8 of its 16 pieces (all 16: 192 bytes of scratch per lane)
+__host__ __device__ constexpr int sums_early(int rows, int cols, int nt) {
+    return rows * cols >= 256 * 256 && sums_slots(rows, cols, nt) > 8 ? 8 : sums_slots(rows, cols, nt);
+}
+
+// Step 1, BEFORE the accumulators go to LDS: the thread's activation pieces of the tile, all in flight while the tile is
+// transposed (issued slot by slot next to the stores they cost about what the pass they replace cost: the early 1x1 dgrads
+// are store-bound and the ping-pong dgrads run one tile per CU with nothing else to hide a load behind).
+template <int ROWS, int COLS, int NT>
+__device__ __forceinline__ void sums_prefetch(const IgemmArgs& __restrict__ a, int mt, int nt, int tid,
+                                              h8_t (&aq)[sums_early(ROWS, COLS, NT)]) {
+    constexpr int CH = COLS / 8, RSTEP = NT / CH, NSLOT = sums_early(ROWS, COLS, NT);
+    static_assert(NT % CH == 0 && (ROWS * CH) % NT == 0, "a thread keeps its 8 channels for all its slots");
+    const int ch = tid % CH, row0 = tid / CH;
+    const int n0 = nt * COLS + ch * 8;
+    const int c = n0 - a.bsum.ch_lo;                        // producer channel of this thread's first column
+    const bool live = n0 < a.N && c >= 0 && c < a.bsum.C;   // (ch_lo and C are multiples of 8: all 8 channels or none)
+    const half_t* act = pin_here(a.bsum.act) + a.bsum.act_choff + c;
+    // pixel of this thread's first row, and the step of RSTEP rows (no division per slot)
+    int m = mt * ROWS + row0;
+    int b, h, w;
+    split_pixel(m, a.HW, a.W, b, h, w);
+    const int sb_ = RSTEP / a.HW, srem = RSTEP - sb_ * a.HW;
+    const int sh_ = srem / a.W, sw_ = srem - sh_ * a.W;
+#pragma unroll
+    for (int k = 0; k < NSLOT; ++k) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) aq[k][i] = (half_t)0.f;
+        if (live && m < a.M) aq[k] = *(const h8_t*)(act + pad_off(b, h, w, a.H, a.W, a.bsum.act_ld, a.bsum.act_pw));
+        m += RSTEP;
+        w += sw_;
+        if (w >= a.W) w -= a.W, ++h;
+        h += sh_;
+        if (h >= a.H) h -= a.H, ++b;
+        b += sb_;
+    }
+}
+
+// Step 2, with the tile in LDS: store it and accumulate.
+template <int ROWS, int COLS, int NT>
+__device__ __forceinline__ void store_raw_tile_sums(const IgemmArgs& __restrict__ a, char* smem, int mt, int nt, int tid,
+                                                    const h8_t (&aq)[sums_early(ROWS, COLS, NT)],
+                                                    float (&tot)[sums_vals(COLS, NT)]) {
+    constexpr int CH = COLS / 8, RSTEP = NT / CH, NSLOT = sums_slots(ROWS, COLS, NT), PITCH = NT + 8;
+    constexpr int EARLY = sums_early(ROWS, COLS, NT);
+    const half_t* ct = (const half_t*)smem;
+    half_t* y = (half_t*)a.y;
+    const int ch = tid % CH, row0 = tid / CH;
+    const int n0 = nt * COLS + ch * 8;
+    const int c = n0 - a.bsum.ch_lo;
+    const bool col_ok = n0 < a.N;
+    const bool live = col_ok && c >= 0 && c < a.bsum.C;
+    float sb[8], sg[8], off[8], mul[8];
+    bool usey[8];
+    bool need_y = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sb[i] = sg[i] = 0.f, off[i] = 0.f, mul[i] = 0.f, usey[i] = false;
+    if (live) {
+        const float *scp = pin_here(a.bsum.scale) + c, *shp = pin_here(a.bsum.shift) + c;
+        const float *mup = pin_here(a.bsum.mean) + c, *isp = pin_here(a.bsum.invstd) + c;
+        float sc[8], sh[8], mu[8], is[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sc[i] = scp[i], sh[i] = shp[i], mu[i] = mup[i], is[i] = isp[i];
+        need_y = act_xhat_source(sc, sh, mu, is, a.bsum.y != nullptr, off, mul, usey);
+    }
+    const float slope = a.bsum.slope, inv_slope = 1.0f / slope;
+#pragma unroll
+    for (int k = 0; k < NSLOT; ++k) {
+        const int row = row0 + k * RSTEP, m = mt * ROWS + row;
+        if (!col_ok || m >= a.M) continue;
+        const h8_t gq = *(const h8_t*)(ct + row * COLS + ch * 8);
+        *(h8_t*)(y + (long long)m * a.y_ld + a.y_choff + n0) = gq;
+        if (!live) continue;
+        h8_t av8;
+        if (k < EARLY) {
+            av8 = aq[k];
+        } else {   // (the late pieces of the 256 x 256 tile)
+            int b, h, w;
+            split_pixel(m, a.HW, a.W, b, h, w);
+            av8 = *(const h8_t*)(a.bsum.act + pad_off(b, h, w, a.H, a.W, a.bsum.act_ld, a.bsum.act_pw) + a.bsum.act_choff + c);
+        }
+        float z[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float av = (float)av8[i];
+            z[i] = av > 0.f ? av : av * inv_slope;
+        }
+        if (need_y) {                                // ill-conditioned channels: the saved y in place of z
+            const float* yp = a.bsum.y + (long long)m * a.bsum.y_ld + a.bsum.y_choff + c;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) z[i] = usey[i] ? yp[i] : z[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float gv = (float)gq[i];
+            const float gz = (float)av8[i] > 0.f ? gv : gv * slope;
+            sb[i] += gz;
+            sg[i] += gz * ((z[i] - off[i]) * mul[i]);
+        }
+    }
+    __syncthreads();   // every thread is done with the tile: its LDS takes the partials, [16 values][NT threads]
+    float* red = (float*)smem;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        red[i * PITCH + tid] = sb[i];
+        red[(8 + i) * PITCH + tid] = sg[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < sums_vals(COLS, NT); ++k) {
+        const int t = tid + k * NT;
+        if (t < 2 * COLS) {
+            const int which = t / COLS, col = t - which * COLS;
+            const int v = which * 8 + (col & 7), chq = col >> 3;
+            float s = 0.f;
+            for (int r = 0; r < RSTEP; ++r) s += red[v * PITCH + r * CH + chq];   // the threads r CH + chq, in order
+            tot[k] += s;
+        }
+    }
+    // (the next tile's K loop, or nothing that touches LDS, follows behind the kernels' own barrier)
+}
+
+// ... and the slot's sums to its slab row [2][ld] once its M tiles are done
+template <int COLS, int NT>
+__device__ __forceinline__ void store_tile_sums_slab(const IgemmArgs& __restrict__ a, int pslot, int nt, int tid,
+                                                     const float (&tot)[sums_vals(COLS, NT)]) {
+#pragma unroll
+    for (int k = 0; k < sums_vals(COLS, NT); ++k) {
+        const int t = tid + k * NT;
+        if (t < 2 * COLS) {
+            const int which = t / COLS, col = t - which * COLS;
+            const int n = nt * COLS + col, c = n - a.bsum.ch_lo;
+            if (n < a.N && c >= 0 && c < a.bsum.C) a.bsum.slab[((long long)pslot * 2 + which) * a.bsum.ld + c] = tot[k];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Accumulators -> LDS tile of the weights-as-A kernels (conv_sparse.hip, conv_q8.hip): there the rows of a 32x32 block
 // are output channels and the columns pixels, so a lane's accumulator rows 4 g .. 4 g + 3 are four consecutive channels
 // of one pixel.  leaky(acc * scale_of(n) + shift[n]) goes down as [pixel][channel], rows PITCH elements apart, as e4m3(2 v)

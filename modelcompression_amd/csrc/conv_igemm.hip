@@ -81,6 +81,10 @@ void igemm_kernel(IgemmArgs a) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) s1[j] = s2[j] = 0.f;
     bool sat = false;   // an fp16 output was clamped (reported through a.overflow)
+    constexpr bool SUMS = EPI == MCAMD_EPI_RAW_F16_SUMS;   // dgrad: BatchNorm-backward sums of the producer (conv_epi.h)
+    float tot[SUMS ? sums_vals(BN, NT) : 1];
+#pragma unroll
+    for (int k = 0; k < (SUMS ? sums_vals(BN, NT) : 1); ++k) tot[k] = 0.f;
 
     for (int mt = pslot; mt < a.num_mtiles; mt += a.num_pslots) {
         // ---- per-tile A row bases (top-left tap of each output pixel, swizzled chunk) ----
@@ -229,6 +233,8 @@ void igemm_kernel(IgemmArgs a) {
                     }
             }
         } else {
+            h8_t aq[SUMS ? sums_early(BM, BN, NT) : 1];   // the producer's activation pieces: in flight while the tile is transposed
+            if constexpr (SUMS) sums_prefetch<BM, BN, NT>(a, mt, nt, tid, aq);
             __syncthreads();  // every wave is done with the stage buffers
             half_t* ct = (half_t*)smem;  // [BM][BN] fp16 output tile
             const int mlim = a.M - mt * BM;  // rows of this tile that are real pixels
@@ -265,11 +271,13 @@ void igemm_kernel(IgemmArgs a) {
             }
             __syncthreads();
             if constexpr (EPI == MCAMD_EPI_PAD_F16) store_pad_tile<BM, BN, BN, NT>(a, nullptr, ct, false, false, mt, nt, tid);
+            else if constexpr (SUMS) store_raw_tile_sums<BM, BN, NT>(a, smem, mt, nt, tid, aq, tot);
             else store_raw_tile<BM, BN, NT>(a, ct, mt, nt, tid);
         }
     }
 
     if (sat && a.overflow) atomicOr(a.overflow, 1);
+    if constexpr (SUMS) store_tile_sums_slab<BN, NT>(a, pslot, nt, tid, tot);
     if ((EPI == MCAMD_EPI_RAW_F16 || EPI == MCAMD_EPI_RAW_F32) && a.stats) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -422,6 +430,7 @@ static void launch_inst(const IgemmArgs& a, int rows, int ntiles, hipStream_t st
     size_t lds = NSTAGE * STAGE_BYTES;
     if (lds < (size_t)BM * BN * 2) lds = (size_t)BM * BN * 2;
     if (lds < (size_t)(BM / WM) * 2 * BN * 4) lds = (size_t)(BM / WM) * 2 * BN * 4;
+    if (EPI == MCAMD_EPI_RAW_F16_SUMS && lds < sums_lds_bytes(NT)) lds = sums_lds_bytes(NT);
     if (lds > 64 * 1024) MCAMD_LDS_OPT_IN((igemm_kernel<BM, BN, WM, WN, BK, NSTAGE, EPI>), lds);   // lds is a per-instance constant
     hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, BK, NSTAGE, EPI>), dim3(round_up_int(rows, 8) * ntiles + 8), dim3(NT), lds, st, a);
 }
@@ -431,7 +440,18 @@ static void launch_one(const IgemmArgs& a, int rows, int ntiles, hipStream_t st)
     if (a.mode == MCAMD_EPI_NCHW_F32) launch_inst<BM, BN, WM, WN, BK, NSTAGE, MCAMD_EPI_NCHW_F32>(a, rows, ntiles, st);
     else if (a.mode == MCAMD_EPI_RAW_F32) launch_inst<BM, BN, WM, WN, BK, NSTAGE, MCAMD_EPI_RAW_F32>(a, rows, ntiles, st);
     else if (a.mode == MCAMD_EPI_PAD_F16) launch_inst<BM, BN, WM, WN, BK, NSTAGE, MCAMD_EPI_PAD_F16>(a, rows, ntiles, st);
+    else if (a.bsum.slab) {
+        // the sums-taking dgrad instances exist for the tiles the dense training step's plain producers get (128 and 64
+        // columns); mcamd_igemm_sums_ok() says so before the launch
+        if constexpr (BN >= 64) launch_inst<BM, BN, WM, WN, BK, NSTAGE, MCAMD_EPI_RAW_F16_SUMS>(a, rows, ntiles, st);
+    }
     else launch_inst<BM, BN, WM, WN, BK, NSTAGE, MCAMD_EPI_RAW_F16>(a, rows, ntiles, st);
+}
+
+// The kernels that can take a producer's BatchNorm-backward sums in their epilogue (IgemmArgs.bsum): the ping-pong tiles
+// and igemm_kernel's 128- and 64-column tiles.
+bool mcamd_igemm_sums_ok(const ConvRoute& r) {
+    return r.kernel == ROUTE_PP || (r.kernel == ROUTE_IGEMM && r.bn >= 64);
 }
 
 // a.* geometry fields must be filled by the caller; r = the ROUTE_IGEMM / ROUTE_PP tile conv_route() chose for them.

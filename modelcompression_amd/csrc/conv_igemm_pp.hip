@@ -158,6 +158,10 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) s1[j] = s2[j] = 0.f;
     bool sat = false;   // an fp16 output was clamped (reported through a.overflow)
+    constexpr bool SUMS = EPI == MCAMD_EPI_RAW_F16_SUMS;   // dgrad: BatchNorm-backward sums of the producer (conv_epi.h)
+    float tot[SUMS ? sums_vals(BN, NT) : 1];
+#pragma unroll
+    for (int k = 0; k < (SUMS ? sums_vals(BN, NT) : 1); ++k) tot[k] = 0.f;
 
     for (int mt = pslot; mt < a.num_mtiles; mt += a.num_pslots) {
         long long abase[A_IT];
@@ -390,6 +394,8 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
                     }
             }
         } else {
+            h8_t aq[SUMS ? sums_early(BM, BN, NT) : 1];   // the producer's activation pieces: in flight while the tile is transposed
+            if constexpr (SUMS) sums_prefetch<BM, BN, NT>(a, mt, nt, tid, aq);
             __syncthreads();   // every wave is done with the stage buffers
             half_t* ct = (half_t*)smem;   // [BM][BN] fp16 output tile (128 KB)
             const int mlim = a.M - mt * BM;
@@ -426,11 +432,13 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
             }
             __syncthreads();
             if constexpr (EPI == MCAMD_EPI_PAD_F16) store_pad_tile<BM, BN, BN, NT>(a, nullptr, ct, false, false, mt, nt, tid);
+            else if constexpr (SUMS) store_raw_tile_sums<BM, BN, NT>(a, smem, mt, nt, tid, aq, tot);
             else store_raw_tile<BM, BN, NT>(a, ct, mt, nt, tid);
         }
     }
 
     if (sat && a.overflow) atomicOr(a.overflow, 1);
+    if constexpr (SUMS) store_tile_sums_slab<BN, NT>(a, pslot, nt, tid, tot);
     if ((EPI == MCAMD_EPI_RAW_F16 || EPI == MCAMD_EPI_RAW_F32) && a.stats) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {   // lanes that hold the same column: l ^ 32 (and l ^ 16 for 16x16 blocks)
@@ -464,7 +472,7 @@ __global__ __launch_bounds__(512, 1) void igemm_pp_kernel(IgemmArgs a) {
 template <int EPI, int BM, int BN, int MS, bool F8 = false>
 static void launch_pp(const IgemmArgs& a, int rows, int ntiles, hipStream_t st) {
     constexpr size_t ring = (size_t)NST * (BM + BN) * CPR * 16;   // <= 128 KB: the ring, then the fp16 output tile
-    static_assert((size_t)BM * BN * 2 <= ring, "output tile fits the ring");
+    static_assert((size_t)BM * BN * 2 <= ring && sums_lds_bytes(NT) <= ring, "output tile (and the partials of the sums form) fit the ring");
     MCAMD_LDS_OPT_IN((igemm_pp_kernel<EPI, BM, BN, MS, F8>), ring);
     hipLaunchKernelGGL((igemm_pp_kernel<EPI, BM, BN, MS, F8>), dim3(round_up_int(rows, 8) * ntiles + 8), dim3(NT), ring, st, a);
 }
@@ -504,6 +512,7 @@ int mcamd_igemm_pp_launch(const IgemmArgs& a, int bm, int bn, int rows, int ntil
     if (a.mode == MCAMD_EPI_NCHW_F32) PP_CASE(MCAMD_EPI_NCHW_F32);
     else if (a.mode == MCAMD_EPI_RAW_F32) PP_CASE(MCAMD_EPI_RAW_F32);
     else if (a.mode == MCAMD_EPI_PAD_F16) PP_CASE(MCAMD_EPI_PAD_F16);
+    else if (a.bsum.slab) PP_CASE(MCAMD_EPI_RAW_F16_SUMS);
     else PP_CASE(MCAMD_EPI_RAW_F16);
 #undef PP_CASE
 #undef PP_SHAPE

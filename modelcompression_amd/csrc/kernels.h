@@ -2,6 +2,25 @@
 #pragma once
 #include "common.h"
 
+// BatchNorm-backward sums of the PLAIN block whose output gradient G a dgrad launch stores (mcamd_dgrad_sums, mcamd.h;
+// conv_epi.h store_raw_tile_sums): pass 0 of bn_plain_bwd_act_kernel taken on the fp16 tile on its way out.
+struct DgradSums {
+    float* slab;             // [num_pslots][2][ld]: sum g_z, sum g_z xhat per producer channel; NULL = none
+    const half_t* act;       // the producer's stored activation (padded NHWC / shared-halo form per act_pw)
+    const float* scale;
+    const float* shift;
+    const float* mean;
+    const float* invstd;
+    const float* y;          // the producer's saved fp32 raw output [M][y_ld] (ill-conditioned channels only) or NULL
+    int act_ld, act_choff, act_pw;   // producer channel c of a pixel: act[pad_off(..) + act_choff + c]
+    int y_ld, y_choff;
+    int ch_lo, C;            // the producer's channels are the G columns [ch_lo, ch_lo + C)
+    int ld;
+    float slope;
+};
+// Kernel-instance selector beside the MCAMD_EPI_* modes (never in IgemmArgs.mode): MCAMD_EPI_RAW_F16 with a.bsum taken
+#define MCAMD_EPI_RAW_F16_SUMS 4
+
 struct IgemmArgs {
     const half_t* x;
     const half_t* w;
@@ -38,6 +57,7 @@ struct IgemmArgs {
     int wrap;        // mcamd_conv_geom.x_wrap (INT_MAX = none): channel blocks >= wrap are read `wrap` channels lower
     int f8_from;     // mcamd_conv_geom.x_f8: first K chunk (of 32 fp16 = 64 e4m3 values) of the fp8 correction part; INT_MAX = none
     int f8_sb;       // e8m0 scale of the B operand of the fp8 MFMAs in all four bytes: 2^-(F8_SXL + x_f8_wexp) (A: 1.0)
+    DgradSums bsum;  // dgrad, mode MCAMD_EPI_RAW_F16: bsum.slab != NULL selects the MCAMD_EPI_RAW_F16_SUMS instances
 };
 
 
@@ -96,6 +116,7 @@ struct ConvRoute {
 ConvRoute mcamd_igemm_route(long long M, int n, int cin_tap, int ktot, bool raw_epilogue, bool concurrent);
 int mcamd_igemm_pp_launch(const IgemmArgs& a, int bm, int bn, int rows, int ntiles, hipStream_t st);
 int mcamd_igemm_launch(IgemmArgs& a, const ConvRoute& r, hipStream_t st);
+bool mcamd_igemm_sums_ok(const ConvRoute& r);   // the route's kernel has a MCAMD_EPI_RAW_F16_SUMS instance (IgemmArgs.bsum)
 int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);   // conv_sparse.hip: 2:4 weights, mode 2 epilogue
 int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
                                int cin_tap, int kb, hipStream_t st);

@@ -195,6 +195,10 @@ class Engine:
         self.bn_narrow_on = True      # BatchNorm / activation passes of a folded producer on its kept channels only
         self.bwd_from_act = True      # split-operand engines: BatchNorm backward of PLAIN blocks from the stored activation
         self.pool_act_on = True       # ... and of MaxPool blocks from a full-resolution copy (off with filter compaction)
+        # ... and the sums of a PLAIN block's BatchNorm backward in the epilogue of the dgrad launch that stores its G
+        # (mcamd_conv_dgrad_sums; MCAMD_DGRAD_BN_SUMS=0: the two-pass mcamd_bn_act_bwd everywhere)
+        self.dgrad_bn_sums = os.environ.get("MCAMD_DGRAD_BN_SUMS", "1") == "1"
+        self._dgrad_sums_cache = {}
         self._side_stream = None
         self._side_concurrent = True
         self._side_ws = None
@@ -1432,10 +1436,53 @@ class Engine:
                            eps=bn.eps, cout=lay.cout, planes=self.act_planes, x_lo=lay.sh_img_lo, wp_lo=lay.sh_wp_lo)
 
     # ------------------------------------------------------------------ backward
-    def bn_act_bwd_layer(self, lay, g, g_ld, g_choff, g2, g2_ld, g2_choff, dy, dgamma, dbeta, grad_scale):
+    def _dgrad_sums(self, lay, concurrent):
+        """(descriptor, slab, producer) when the dgrad launch of block `lay` can take the BatchNorm-backward sums of the
+        block that produced its input (ops.dgrad_sums), else None.  The producer must be a PLAIN block of a split-operand
+        engine read from its stored activation (bwd_from_act), with this block as its only consumer and none of keep / perm /
+        fold / skip_dead / a narrowed BatchNorm pass; this block must run its dense geometry (no gather / fold of its own),
+        and the kernel its dgrad gets must have the sums-taking form (ops.dgrad_sums_rows > 0)."""
+        if not (self.dgrad_bn_sums and self.bwd_from_act and self.precise) or lay.gin is None:
+            return None
+        key = (lay.li, bool(concurrent), self._plan_epoch)
+        hit = self._dgrad_sums_cache.get(key, False)
+        if hit is not False:
+            return hit
+        res = None
+        if lay.fold is None and not lay.gather and lay.in_perm is None and lay.geom_act is lay.geom:
+            for prod in self.layers:
+                if prod.is_last or prod.fused_stem or prod.stem_shadow or prod.bn is None or prod.out_t is None:
+                    continue
+                if self.consumer_of.get(prod.out_id) is not lay or prod.mode != L.DST_PLAIN or prod.slope <= 0.0:
+                    continue
+                if prod.out2_id is not None and prod.out2_id in self.consumer_of:
+                    continue              # a second consumer: its G arrives in two tensors
+                if (prod.keep is not None or prod.perm is not None or prod.fold is not None or prod.skip_dead or prod.fold_consumers
+                        or prod.bn_width or prod.border is not None or prod.cout % 8 != 0):
+                    continue
+                t = prod.out_t
+                ch_lo = t.choff - lay.tin.choff
+                if t.buf != lay.tin.buf or t.ld != lay.tin.ld or ch_lo < 0 or ch_lo % 8 != 0 or ch_lo + prod.cout > lay.geom.cin:
+                    continue
+                rows = ops.dgrad_sums_rows(lay.geom_act, concurrent)
+                if rows <= 0:
+                    continue
+                slab = torch.empty(rows, 2, prod.cout, dtype=torch.float32, device=self.device)
+                y = prod.y if (prod.y is not None and prod.y.dtype == torch.float32) else None
+                desc = ops.dgrad_sums(slab, self.bufs[t.buf], t.ld, t.choff, self._pad_for(t.W), prod.scale, prod.shift, prod.mean,
+                                      prod.invstd, prod.slope, prod.cout, ch_lo=ch_lo, y=y, y_ld=prod.cout, y_choff=0)
+                res = (desc, slab, prod)
+                break
+        self._dgrad_sums_cache = {k: v for k, v in self._dgrad_sums_cache.items() if k[2] == self._plan_epoch}
+        self._dgrad_sums_cache[key] = res
+        return res
+
+    def bn_act_bwd_layer(self, lay, g, g_ld, g_choff, g2, g2_ld, g2_choff, dy, dgamma, dbeta, grad_scale, sums=None):
         """pool / reorg / route + LeakyReLU + BatchNorm backward of one block: G (gradient wrt the block's output, at the
         consumer's channel slice) -> dY (padded NHWC), dgamma, dbeta.  One place for the launch arguments (narrowed to the
-        kept channels for a folded producer); tests re-issue it with a substitute G."""
+        kept channels for a folded producer); tests re-issue it with a substitute G.
+        `sums`: the slab the dgrad launch that wrote G left the block's sums in (_dgrad_sums) -- only the backward walk,
+        which has just issued that launch, passes it."""
         cb = lay.bn_width or lay.cout
         act = {}
         if self.bwd_from_act and self.precise and lay.mode == L.DST_PLAIN and g2 is None:
@@ -1454,6 +1501,8 @@ class Engine:
                 t = lay.out_t
                 act.update(pool_out=self.bufs[t.buf], pool_out_ld=t.ld, pool_out_choff=t.choff,
                            pool_out_pad=self._pad_for(t.W))
+        if sums is not None:
+            act["sums"] = sums
         ops.bn_act_bwd(self.B, lay.H, lay.W, cb, lay.y, lay.cout, 0, lay.scale, lay.shift, lay.mean,
                        lay.invstd, lay.slope, lay.mode, g, g_ld, g_choff, dy, lay.cout_p, 0,
                        dgamma, dbeta, grad_scale, g2, g2_ld, g2_choff,
@@ -1563,6 +1612,7 @@ class Engine:
         # late start costs more overlap than the saved events).  dY and the block inputs stay in place until the next
         # forward, so a late start is safe.
         pending, chunk = [], self.wgrad_chunk
+        sums_of = {}      # block -> slab its consumer's dgrad launch (issued earlier in this walk) left its sums in
 
         def flush():
             if not pending:
@@ -1610,7 +1660,7 @@ class Engine:
                     c2, t2 = self.consumer_of[lay.out2_id], lay.out2_t
                     g2, g2_ld, g2_choff = c2.gin, c2.tin.ld, t2.choff
                 self.bn_act_bwd_layer(lay, cons.gin, cons.tin.ld, t.choff, g2, g2_ld or 0, g2_choff or 0, lay.dy,
-                                      gmap[id(lay.bn.weight)], gmap[id(lay.bn.bias)], D)
+                                      gmap[id(lay.bn.weight)], gmap[id(lay.bn.bias)], D, sums=sums_of.pop(lay.li, None))
             mask = lay.conv.mask.contiguous() if lay.conv.mask_flag else None
             dbias = gmap[id(lay.conv.bias)] if lay.conv.bias is not None else None
             def wgrad_of(ws, lay=lay, mask=mask, dbias=dbias):
@@ -1652,9 +1702,14 @@ class Engine:
                 # (concurrent: the weight gradients run beside this launch and take the CUs it leaves idle, so the library
                 # picks the tile with the least CU-time.  Not in the per-kernel timing mode, where every launch has the GPU
                 # to itself: the layer table then shows the tile that is fastest alone -- three launches differ)
+                # (... and where the input comes from a PLAIN block, the launch takes that block's BatchNorm-backward sums
+                # from the tile it stores: _dgrad_sums)
+                conc = side is not None and self._side_concurrent
+                ds = self._dgrad_sums(lay, conc)
+                if ds is not None:
+                    sums_of[ds[2].li] = ds[1]
                 self._timed('dgrad', lay, ops.conv_dgrad_raw, lay.geom_act, lay.dy, lay.cout_p, 0, lay.wd, lay.gin, lay.tin.ld,
-                            lay.tin.choff, overflow=self.overflow,
-                            concurrent=side is not None and self._side_concurrent)
+                            lay.tin.choff, overflow=self.overflow, concurrent=conc, sums=ds[0] if ds is not None else None)
         if side is not None:
             flush()
             ops.stream_wait(main, side)

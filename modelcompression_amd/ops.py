@@ -10,7 +10,7 @@ import weakref
 import torch
 
 from . import _lib as L
-from ._lib import (ConvGeom, ConvEpilogue, ActDesc, ActBwdDesc, ChanMap, PackJob, StemBlockDesc, FoldDesc, FoldJob, check, ptr,
+from ._lib import (ConvGeom, ConvEpilogue, ActDesc, ActBwdDesc, DgradSums, ChanMap, PackJob, StemBlockDesc, FoldDesc, FoldJob, check, ptr,
                    stream_ptr)
 
 HALF = torch.float16
@@ -210,11 +210,40 @@ def conv_fwd_padded(g, x, wp, y, y_ld, y_choff=0, scale=None, shift=None, slope=
     check(L.lib().mcamd_conv_fwd(C.byref(g), ptr(x), ptr(wp), C.byref(e), stream_ptr()), "mcamd_conv_fwd")
 
 
-def conv_dgrad_raw(g, dy, dy_ld, dy_choff, wpd, out, out_ld, out_choff=0, overflow=None, concurrent=False):
+def dgrad_sums_rows(g, concurrent=False):
+    """Slab rows a conv_dgrad_raw launch of `g` writes when it takes its producer's BatchNorm-backward sums (dgrad_sums);
+    0: the kernel that geometry gets cannot take them."""
+    return int(L.lib().mcamd_conv_dgrad_sums_rows(C.byref(g), 1 if concurrent else 0))
+
+
+def dgrad_sums(slab, act, act_ld, act_choff, act_pad, scale, shift, mean, invstd, slope, C_, ch_lo=0, y=None, y_ld=0, y_choff=0):
+    """mcamd_dgrad_sums for conv_dgrad_raw(..., sums=): the PLAIN block whose C_ channels are the columns [ch_lo, ch_lo + C_)
+    of the launch's output G; `slab` fp32 [dgrad_sums_rows(g, concurrent)][2][ld >= C_] receives sum g_z and sum g_z xhat,
+    which bn_act_bwd(..., sums=slab) then takes instead of running its first pass.  The tensors must stay alive."""
+    _need_cuda(slab, act, scale, shift, mean, invstd, y)
+    assert slab.dtype == torch.float32 and slab.dim() == 3 and slab.shape[1] == 2 and slab.is_contiguous()
+    assert y is None or y.dtype == torch.float32
+    d = DgradSums()
+    d.slab, d.rows, d.ld = slab.data_ptr(), slab.shape[0], slab.shape[2]
+    d.act, d.act_ld, d.act_choff, d.act_pad = act.data_ptr(), act_ld, act_choff, act_pad
+    d.scale, d.shift, d.mean, d.invstd = scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr()
+    d.slope = slope
+    d.y, d.y_ld, d.y_choff = (y.data_ptr() if y is not None else None), y_ld, y_choff
+    d.ch_lo, d.C = ch_lo, C_
+    return d
+
+
+def conv_dgrad_raw(g, dy, dy_ld, dy_choff, wpd, out, out_ld, out_choff=0, overflow=None, concurrent=False, sums=None):
     """`overflow`: optional int32[1] device flag, set when a (scaled) gradient was clamped to the fp16 range.
-    `concurrent`: another stream has work for the CUs this launch leaves idle (mcamd_conv_epilogue.concurrent)."""
+    `concurrent`: another stream has work for the CUs this launch leaves idle (mcamd_conv_epilogue.concurrent).
+    `sums`: optional dgrad_sums(...) descriptor -- the launch also forms the BatchNorm-backward sums of the producer whose
+    output gradient it stores (mcamd_conv_dgrad_sums)."""
     e = _epi(L.EPI_RAW_F16, out, out_ld, out_choff, overflow=overflow)
     e.concurrent = 1 if concurrent else 0
+    if sums is not None:
+        check(L.lib().mcamd_conv_dgrad_sums(C.byref(g), ptr(dy), dy_ld, dy_choff, ptr(wpd), C.byref(e), C.byref(sums), stream_ptr()),
+              "mcamd_conv_dgrad_sums")
+        return
     check(L.lib().mcamd_conv_dgrad(C.byref(g), ptr(dy), dy_ld, dy_choff, ptr(wpd), C.byref(e), stream_ptr()),
           "mcamd_conv_dgrad")
 
@@ -361,12 +390,17 @@ def bn_act_fwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, ds
 def bn_act_bwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, mean, invstd, slope, mode, g, g_ld, g_choff, dy, dy_ld,
                dy_choff, dgamma, dbeta, grad_scale=1.0, g2=None, g2_ld=0, g2_choff=0, workspace=None, dy_keep=None,
                perm=None, overflow=None, skip_dead_from=0, dy_pad=0, act=None, act_ld=0, act_choff=0, act_pad=0,
-               pool_out=None, pool_out_ld=0, pool_out_choff=0, pool_out_pad=0):
+               pool_out=None, pool_out_ld=0, pool_out_choff=0, pool_out_pad=0, sums=None):
     """`act` (PLAIN blocks): the stored fp16 activation in its padded buffer -- the pre-activation is recovered from it
     and `y` is not read (mcamd_act_bwd_desc.act).
     `pool_out` (MaxPool blocks with `act` or an fp32 `y`, no g2): the pooled fp16 activation in the consumer's padded buffer -- the pass
-    that forms the per-channel sums reads it instead of the full-resolution copy or `y` (mcamd_act_bwd_desc.pool_out)."""
+    that forms the per-channel sums reads it instead of the full-resolution copy or `y` (mcamd_act_bwd_desc.pool_out).
+    `sums` (PLAIN blocks with `act`, no g2): fp32 [rows][2][ld] slab that already holds the per-channel sums -- written by the
+    conv_dgrad_raw(..., sums=) launch that stored `g` -- so the pass that forms them is skipped (mcamd_act_bwd_desc.sums)."""
     d = ActBwdDesc()
+    if sums is not None:
+        assert sums.dtype == torch.float32 and sums.dim() == 3 and sums.shape[1] == 2 and sums.is_contiguous()
+        d.sums, d.sums_rows, d.sums_ld = sums.data_ptr(), sums.shape[0], sums.shape[2]
     d.skip_dead_param_grads = int(skip_dead_from)
     d.dy_pad = dy_pad
     d.B, d.H, d.W, d.C = B, H, W, C_
