@@ -266,6 +266,34 @@ int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_c
                   int32_t dst_choff, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * fp8 inference of slim_export models (an addition beyond the reference): the fp8 block above for an input
+ * channel count that is a multiple of 8 only, and with the border table of a conv that lost input channels (slim.py) in
+ * the epilogue.  With cin_pad = round_up(cin, 64):
+ *   weights   rows of cin_pad channels per tap, kpos(t, c) as above over cin_pad channels; the bytes of the channels
+ *             [cin, cin_pad) are 0x00; e_f from max |w * mask| over the real channels;
+ *   K loop    the one of mcamd_conv_fwd_q8 over cin_pad channels: the bytes it reads behind the slice, channels [x_choff +
+ *             cin, x_choff + cin_pad) of the same pixel, must lie inside x_ld; they may hold anything a byte buffer holds
+ *             (never-written 0x00, or another tensor's codes: q() never stores a NaN code) -- every such product is an
+ *             exact 0, so the result is bit-identical to mcamd_conv_fwd_q8 on the weights zero-extended to cin_pad channels;
+ *   output    v = leaky(scale_f * (2^-(e_f + 1) * S + border[cls(h, w)][f]) + shift_f), evaluated in fp32; cls has bit 0
+ *             for h == 0, bit 1 for h == H - 1, bit 2 for w == 0, bit 3 for w == W - 1 (mcamd_act_desc.border); the entries
+ *             are used as given (fp32, not quantised); border == NULL: no term.
+ * ------------------------------------------------------------------------- */
+/* mcamd_conv_fwd_q8_ok's predicate with cin % 8 == 0 in place of cin % 64 == 0 and x_choff + round_up(cin, 64) <= x_ld in
+ * place of x_choff + cin <= x_ld.  Needs no device. */
+int32_t mcamd_conv_fwd_q8_slim_ok(const mcamd_conv_geom* g);
+/* out[0] = weight bytes (Npad * k*k * round_up(cin, 64), Npad = round_up(cout, 256)), out[1] = int32 exponents (Npad). */
+int mcamd_q8_slim_elems(const mcamd_conv_geom* g, int64_t out[2]);
+/* mcamd_pack_q8 into rows of round_up(cin, 64) channels per tap (pad channels 0x00; every row up to Npad is written). */
+int mcamd_pack_q8_slim(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wq, int32_t* wexp,
+                       void* stream);
+/* The block: epi->mode MCAMD_EPI_PAD_F16 only; dst_mode, y2, y_f8 / y2_f8 as mcamd_conv_fwd_q8.  border: fp32 [16][border_ld]
+ * or NULL; border_ld >= cout, border_ld % 4 == 0.  Both MCAMD_Q8_MFMA forms, both `pad` forms of x, any batch size. */
+int mcamd_conv_fwd_q8_slim(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
+                           const mcamd_conv_epilogue* epi, const float* border, int32_t border_ld, int32_t y_f8, int32_t y2_f8,
+                           void* stream);
+
+/* ---------------------------------------------------------------------------
  * fp8 quantisation-aware training (an addition beyond the reference; Darknet.precision = "fp8-qat"): the
  * training-mode forward of an fp8 block runs in the deployment arithmetic above, its backward is straight-through.
  *   forward   a8 = q(2 x) input codes, (w8, e_f) re-quantised from w = weight * mask every step (mcamd_pack_q8);

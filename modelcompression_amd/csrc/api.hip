@@ -680,6 +680,62 @@ extern "C" int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const
     return mcamd_conv_q8_launch(a, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------
+// fp8 inference of slim_export models: cin a multiple of 8 on zero-padded weight rows, border tables
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_q8_slim_ok(const mcamd_conv_geom* g) {
+    if (!g || g->stem || g->x_wrap != 0 || g->x_f8 != 0 || (g->ksize != 1 && g->ksize != 3)) return 0;
+    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->cin <= 0 || g->cout <= 0) return 0;
+    if (g->cin % 8 != 0 || g->cout % 8 != 0 || (long long)g->B * g->H * g->W >= (1ll << 31)) return 0;
+    if (g->pad != 0 && g->pad != 1) return 0;
+    // the K loop reads round_up(cin, 64) channels of every pixel: they must lie inside the pixel's row
+    if (g->x_ld % 16 != 0 || g->x_choff % 16 != 0 || g->x_choff < 0 || (long long)g->x_choff + round_up_int(g->cin, 64) > g->x_ld) return 0;
+    return 1;
+}
+
+extern "C" int mcamd_q8_slim_elems(const mcamd_conv_geom* g, int64_t out[2]) {
+    MCAMD_REQUIRE(g && out, "q8_slim_elems: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_slim_ok(g), "q8_slim_elems: geometry has no slim fp8 form (mcamd_conv_fwd_q8_slim_ok)");
+    const long long npad = round_up_int(g->cout, 256);
+    out[0] = npad * ntaps_of(g) * round_up_int(g->cin, 64);
+    out[1] = npad;
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_pack_q8_slim(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wq, int32_t* wexp,
+                                  void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "pack_q8_slim: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_pack_q8_slim(&g_, w_oihw, mask_oihw, wq, wexp, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_slim_ok(g), "pack_q8_slim: geometry has no slim fp8 form (mcamd_conv_fwd_q8_slim_ok)");
+    MCAMD_REQUIRE(w_oihw && wq && wexp, "pack_q8_slim: null pointer");
+    return mcamd_pack_q8_slim_launch(w_oihw, mask_oihw, wq, wexp, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_q8_slim(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
+                                      const mcamd_conv_epilogue* epi, const float* border, int32_t border_ld, int32_t y_f8,
+                                      int32_t y2_f8, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_slim: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_q8_slim(&g_, x8, wq, wexp, &e_, border, border_ld, y_f8, y2_f8, s); });
+    }
+    if (check_geom(g, "conv_fwd_q8_slim")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_slim_ok(g), "conv_fwd_q8_slim: geometry has no slim fp8 form (mcamd_conv_fwd_q8_slim_ok)");
+    MCAMD_REQUIRE(x8 && wq && wexp, "conv_fwd_q8_slim: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8_slim: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    MCAMD_REQUIRE(!border || (border_ld >= g->cout && border_ld % 4 == 0),
+                  "conv_fwd_q8_slim: border_ld %d must be a multiple of 4 and >= cout %d", border_ld, g->cout);
+    IgemmArgs a;
+    // the unchanged K loop over round_up(cin, 64) channels per tap: the weight bytes of the extra ones are 0x00
+    fill_operand(a, g, x8, wq, g->x_ld, g->x_choff, g->cout, round_up_int(g->cin, 64), 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_slim", 0)) return MCAMD_EINVAL;           // (mode 2: no statistics)
+    return mcamd_conv_q8_launch(a, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream, border, border ? border_ld : 0);
+}
+
 extern "C" int32_t mcamd_conv_fwd_q8_stats_rows(const mcamd_conv_geom* g) {
     if (!mcamd_conv_fwd_q8_ok(g)) return 0;
     return (int32_t)(((long long)g->B * g->H * g->W + MCAMD_Q8_TILE_M - 1) / MCAMD_Q8_TILE_M);

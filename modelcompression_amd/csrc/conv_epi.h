@@ -358,11 +358,43 @@ __device__ __forceinline__ void store_tile_sums_slab(const IgemmArgs& __restrict
 // are output channels and the columns pixels, so a lane's accumulator rows 4 g .. 4 g + 3 are four consecutive channels
 // of one pixel.  leaky(acc * scale_of(n) + shift[n]) goes down as [pixel][channel], rows PITCH elements apart, as e4m3(2 v)
 // bytes (need_b) and / or saturated fp16 (need_h).  Returns whether an fp16 value was clamped.
+//
+// BorderOf (slim models; NoBorder: none, the code below is what it was): a per-pixel-class constant joins the
+// raw value in front of the affine step, leaky((acc * pre(n) + table[cls][n]) * scale_of(n) + shift[n]) -- pre(n) = the
+// power of two that scale_of(n) carries for the other kernels.  The class of an accumulator column is taken ONCE per
+// column (TN registers), from the pixel the launch's enumeration gives it (tile_pixel: each pixel of a POOL / REORG
+// window has its own); a lane then reads one 16-byte table piece per (pixel, four channels).
 // ---------------------------------------------------------------------------------------
-template <int BMW, int PITCH, int WM, int WN, int TM, int TN, class ScaleOf>
+struct NoBorder {
+    static constexpr bool on = false;
+};
+// table: fp32 [16][ld], class bits: 0 top row, 1 bottom row, 2 left column, 3 right column (bn_act.hip border_class);
+// wexp: the per-filter exponents of the packed fp8 weights; m0: GEMM row (pixel) of the tile's first column
+struct Q8Border {
+    static constexpr bool on = true;
+    const float* table;
+    const int* wexp;
+    int ld, m0;
+    __device__ __forceinline__ int cls(const IgemmArgs& __restrict__ a, int pix) const {
+        int m = m0 + pix, b, h, w;
+        if (m > a.M - 1) m = a.M - 1;              // (columns past the last pixel are not stored)
+        tile_pixel(a, a.dst_mode != 0, m, b, h, w);
+        return (h == 0 ? 1 : 0) | (h == a.H - 1 ? 2 : 0) | (w == 0 ? 4 : 0) | (w == a.W - 1 ? 8 : 0);
+    }
+    __device__ __forceinline__ float pre(int n) const { return ldexpf(1.f, -(wexp[n] + 1)); }
+    __device__ __forceinline__ f32x4_t row(int c, int n0) const { return *(const f32x4_t*)(table + c * ld + n0); }
+};
+
+template <int BMW, int PITCH, int WM, int WN, int TM, int TN, class ScaleOf, class BorderOf = NoBorder>
 __device__ __forceinline__ bool write_ch_tile(const IgemmArgs& __restrict__ a, const f32x16_t (&acc)[TM][TN], ScaleOf scale_of, bool need_b,
-                                              bool need_h, char* bt, half_t* ht, int nt, int wm, int wn, int lane) {
+                                              bool need_h, char* bt, half_t* ht, int nt, int wm, int wn, int lane,
+                                              BorderOf border_of = BorderOf()) {
     bool sat = false;
+    int cls[BorderOf::on ? TN : 1];
+    if constexpr (BorderOf::on) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) cls[j] = border_of.cls(a, wn * WN + j * 32 + (lane & 31));
+    }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -378,15 +410,26 @@ __device__ __forceinline__ bool write_ch_tile(const IgemmArgs& __restrict__ a, c
                     if (a.shift) sh[e] = a.shift[n];
                 }
             }
+            float pre[BorderOf::on ? 4 : 1];
+            if constexpr (BorderOf::on) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pre[e] = nt * BMW + ch0 + e < a.N ? border_of.pre(nt * BMW + ch0 + e) : 1.f;
+            }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int pix = wn * WN + j * 32 + (lane & 31);
                 float v[4];
+                if constexpr (BorderOf::on) {
+                    f32x4_t bb = {0.f, 0.f, 0.f, 0.f};
+                    if (nt * BMW + ch0 < a.N) bb = border_of.row(cls[j], nt * BMW + ch0);   // (N % 4 == 0: all four or none)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = acc[i][j][4 * g + e] * sc[e] + sh[e];
-                    v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope;
+                    for (int e = 0; e < 4; ++e) v[e] = (acc[i][j][4 * g + e] * pre[e] + bb[e]) * sc[e] + sh[e];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * g + e] * sc[e] + sh[e];
                 }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope;
                 if (need_b) *(int*)(bt + pix * PITCH + ch0) = e4m3_bytes4(v);
                 if (need_h) {
                     h4_t hv;

@@ -40,9 +40,12 @@
 // atomics.  Each wave transposes its accumulators through a private LDS region, 32 pixels at a time ([pixel][channel], rows
 // WM + 4 floats apart: the 16-byte writes of 8 pixels fall on 8 different bank slots), stores whole channel runs and adds
 // the 32 rows of a column in order; pixels past M go down as zeros and are not stored.
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW>
-__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
-void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8) {
+//
+// BORDER (slim models; conv_q8_border_kernel below): the epilogue adds the fp32 table entry of the pixel's
+// border class to the raw value 2^-(e[n] + 1) * S in front of the affine step (conv_epi.h: Q8Border).
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW, bool BORDER>
+__device__ __forceinline__ void conv_q8_block(const IgemmArgs& __restrict__ a, const int* __restrict__ wexp, int y_f8, int y2_f8,
+                                              const float* __restrict__ border, int border_ld) {
     constexpr int WAVES_N = BNP / WN;
     constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
     constexpr int BK = 64, CPR = 4;                // 64 e4m3 k per 64-byte LDS row: four 16-byte chunks
@@ -237,15 +240,35 @@ void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_
     half_t* ht = (half_t*)(smem + (need_b ? BNP * PB : 0));   // [BNP][PB] fp16 tile
     // the per-filter scale with the power of two of the packed weights and of the 2 x activations taken back (exact)
     const float* scale = a.scale;
-    const bool sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale, wexp](int n) { return ldexpf(scale ? scale[n] : 1.f, -(wexp[n] + 1)); },
-                                                    need_b, need_h, bt, ht, nt, wm, wn, lane);
+    bool sat;
+    if constexpr (BORDER)
+        sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale](int n) { return scale ? scale[n] : 1.f; }, need_b, need_h, bt, ht, nt, wm,
+                                             wn, lane, Q8Border{border, wexp, border_ld, mt * BNP});
+    else
+        sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale, wexp](int n) { return ldexpf(scale ? scale[n] : 1.f, -(wexp[n] + 1)); },
+                                             need_b, need_h, bt, ht, nt, wm, wn, lane);
     __syncthreads();
     store_pad_tile<BNP, BMW, PB, NT>(a, bt, ht, y_f8 != 0, y2_f8 != 0, mt, nt, tid);
     if (sat && a.overflow) atomicOr(a.overflow, 1);
 }
 
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW>
+__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
+void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8) {
+    conv_q8_block<BMW, BNP, WM, WN, NSTAGE, F8MFMA, RAW, false>(a, wexp, y_f8, y2_f8, nullptr, 0);
+}
+
+// ... with a border table (inference epilogue only)
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
+void conv_q8_border_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8, const float* __restrict__ border,
+                           int border_ld) {
+    conv_q8_block<BMW, BNP, WM, WN, NSTAGE, F8MFMA, false, true>(a, wexp, y_f8, y2_f8, border, border_ld);
+}
+
 template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW = false>
-static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, hipStream_t st) {
+static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, hipStream_t st, const float* border = nullptr,
+                            int border_ld = 0) {
     constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
     constexpr int RING = NSTAGE * (BMW + BNP) * 64;
     constexpr int PB = BMW + 8;                    // tile row pitch (conv_q8_kernel)
@@ -254,11 +277,20 @@ static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, 
     const bool has2 = a.y2 != nullptr;
     const bool mixed = (y_f8 || (has2 && y2_f8)) && (!y_f8 || (has2 && !y2_f8));
     const int lds = (mixed && !RAW) ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);   // (RAW: its tiles lie inside the ring)
-    auto kern = conv_q8_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA, RAW>;
-    MCAMD_LDS_OPT_IN(kern, LDS);
     a.num_mtiles = (a.M + BNP - 1) / BNP;
     a.num_ntiles = (a.N + BMW - 1) / BMW;
     const int grid = (a.num_mtiles + 7) / 8 * 8 * a.num_ntiles;
+    if constexpr (!RAW) {
+        if (border) {                              // (the same tile, ring and LDS as the launch without a table)
+            auto kern = conv_q8_border_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
+            MCAMD_LDS_OPT_IN(kern, LDS);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8, border, border_ld);
+            MCAMD_LAUNCH_CHECK("conv_fwd_q8_slim");
+            return MCAMD_OK;
+        }
+    }
+    auto kern = conv_q8_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA, RAW>;
+    MCAMD_LDS_OPT_IN(kern, LDS);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8);
     MCAMD_LAUNCH_CHECK("conv_fwd_q8");
     return MCAMD_OK;
@@ -267,7 +299,8 @@ static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, 
 // Tiles as conv_sparse.hip's: 256 channels x 128 pixels (8 waves of 64 x 64) from 256 filters, 128 x 128 (4 waves) from
 // 128, 64 x 128 below; a 3-deep ring of 64-byte rows (72 / 48 / 36 KB: two workgroups per CU).
 // MCAMD_Q8_MFMA: 0 = fp16 MFMAs on converted bytes, 1 = the block-scaled fp8 MFMA.
-int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st) {
+// `border` (mcamd_conv_fwd_q8_slim; inference epilogue only): fp32 [16][border_ld] table added by pixel class, or NULL.
+int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st, const float* border, int border_ld) {
     const int* we = (const int*)wexp;
     if (a.mode == MCAMD_EPI_RAW_F32) {             // training: fp32 y + statistics, the same tile per filter count
         if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {
@@ -279,14 +312,14 @@ int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hi
         return conv_q8_launch_t<64, 128, 32, 64, 3, false, true>(a, we, 0, 0, st);
     }
     if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {       // the fp8 MFMA: faster, not byte-exact (see the kernel's comment)
-        if (a.N >= 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st);
-        if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st);
-        return conv_q8_launch_t<64, 128, 32, 64, 3, true>(a, we, y_f8, y2_f8, st);
+        if (a.N >= 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st, border, border_ld);
+        if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st, border, border_ld);
+        return conv_q8_launch_t<64, 128, 32, 64, 3, true>(a, we, y_f8, y2_f8, st, border, border_ld);
     }
     // (no 256-channel tile here: with the converted fragments it needs 136 registers, one workgroup per CU, and measured
     // 0.87-0.92 x the fp16 kernels on the 256- and 512-filter layers)
-    if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false>(a, we, y_f8, y2_f8, st);
-    return conv_q8_launch_t<64, 128, 32, 64, 3, false>(a, we, y_f8, y2_f8, st);
+    if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false>(a, we, y_f8, y2_f8, st, border, border_ld);
+    return conv_q8_launch_t<64, 128, 32, 64, 3, false>(a, we, y_f8, y2_f8, st, border, border_ld);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -295,12 +328,15 @@ int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hi
 // One workgroup per row n < Npad.  a = max |w * mask| of the filter, (m, x) = frexp(a), e = 9 - x if m <= 0.875 else 8 - x
 // (a 2^e in (224, 448]; e = 0 for an all-zero filter): integer steps only, so the host emulation cannot disagree at a
 // power of two.  Then w8 = e4m3(clamp(ldexp(w * mask, e))), four k per thread and store.  Pad rows: zero bytes, e = 0.
-__global__ __launch_bounds__(256) void pack_q8_kernel(const float* __restrict__ w, const float* __restrict__ mask,
-                                                      char* __restrict__ wq, int* __restrict__ wexp, int cout, int cin,
-                                                      int ntaps) {
+// PITCH (mcamd_pack_q8_slim): cin % 8 == 0 only; the row is laid out for cin_pad = round_up(cin, 64) channels
+// and the bytes of the channels [cin, cin_pad) are 0x00 -- the exponent comes from the real weights.
+template <bool PITCH>
+__device__ __forceinline__ void pack_q8_row(const float* __restrict__ w, const float* __restrict__ mask, char* __restrict__ wq,
+                                            int* __restrict__ wexp, int cout, int cin, int ntaps) {
     __shared__ float red[256];
     const int n = blockIdx.x, tid = threadIdx.x;
     const int ktot = cin * ntaps;
+    const int cin_pad = PITCH ? (cin + 63) / 64 * 64 : cin, kpad = cin_pad * ntaps;
     float amax = 0.f;
     if (n < cout)
         for (int o = tid; o < ktot; o += 256) {
@@ -321,7 +357,7 @@ __global__ __launch_bounds__(256) void pack_q8_kernel(const float* __restrict__ 
         e = m <= 0.875f ? 9 - x : 8 - x;
     }
     if (tid == 0) wexp[n] = e;
-    for (int k4 = tid; k4 < ktot / 4; k4 += 256) {
+    for (int k4 = tid; k4 < kpad / 4; k4 += 256) {
         const int kp = 4 * k4;                                   // position in the packed order [cb][tap][64]
         const int cb = kp / (ntaps * 64), r = kp - cb * ntaps * 64;
         const int tap = r / 64, c0 = cb * 64 + (r - tap * 64);
@@ -329,15 +365,34 @@ __global__ __launch_bounds__(256) void pack_q8_kernel(const float* __restrict__ 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             v[i] = 0.f;
-            if (n < cout) {
+            if (n < cout && (!PITCH || c0 < cin)) {              // (cin % 4 == 0: all four channels or none)
                 const long long s = ((long long)n * cin + c0 + i) * ntaps + tap;
                 v[i] = fminf(fmaxf(ldexpf(w[s] * (mask ? mask[s] : 1.f), e), -448.f), 448.f);
             }
         }
         int b = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
         b = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], b, true);
-        *(int*)(wq + (long long)n * ktot + kp) = b;
+        *(int*)(wq + (long long)n * kpad + kp) = b;
     }
+}
+
+__global__ __launch_bounds__(256) void pack_q8_kernel(const float* __restrict__ w, const float* __restrict__ mask,
+                                                      char* __restrict__ wq, int* __restrict__ wexp, int cout, int cin,
+                                                      int ntaps) {
+    pack_q8_row<false>(w, mask, wq, wexp, cout, cin, ntaps);
+}
+
+__global__ __launch_bounds__(256) void pack_q8_slim_kernel(const float* __restrict__ w, const float* __restrict__ mask,
+                                                           char* __restrict__ wq, int* __restrict__ wexp, int cout, int cin,
+                                                           int ntaps) {
+    pack_q8_row<true>(w, mask, wq, wexp, cout, cin, ntaps);
+}
+
+int mcamd_pack_q8_slim_launch(const float* w, const float* mask, void* wq, void* wexp, int cout, int cin, int ntaps, hipStream_t st) {
+    hipLaunchKernelGGL(pack_q8_slim_kernel, dim3(round_up_int(cout, 256)), dim3(256), 0, st, w, mask, (char*)wq, (int*)wexp, cout,
+                       cin, ntaps);
+    MCAMD_LAUNCH_CHECK("pack_q8_slim");
+    return MCAMD_OK;
 }
 
 int mcamd_pack_q8_launch(const float* w, const float* mask, void* wq, void* wexp, int cout, int cin, int ntaps, hipStream_t st) {

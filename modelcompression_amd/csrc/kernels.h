@@ -121,8 +121,12 @@ int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);   // c
 int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
                                int cin_tap, int kb, hipStream_t st);
 // conv_q8.hip: e4m3 operands (byte strides in `a`), mode 2 epilogue with a format per destination; packer; cast pass
-int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
+// (`border`: fp32 [16][border_ld] table the inference epilogue adds by pixel class, mcamd_conv_fwd_q8_slim; NULL = none)
+int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st, const float* border = nullptr,
+                         int border_ld = 0);
 int mcamd_pack_q8_launch(const float* w, const float* mask, void* wq, void* wexp, int cout, int cin, int ntaps, hipStream_t st);
+// ... rows of round_up(cin, 64) channels per tap, zero bytes behind the real ones (cin % 8 == 0)
+int mcamd_pack_q8_slim_launch(const float* w, const float* mask, void* wq, void* wexp, int cout, int cin, int ntaps, hipStream_t st);
 // (a.mode MCAMD_EPI_RAW_F32: the training form, fp32 y + one statistics row per pixel tile of MCAMD_Q8_TILE_M pixels)
 #define MCAMD_Q8_TILE_M 128
 int mcamd_cast_q8_launch(const void* src, long long pixels, int src_ld, int src_choff, int C, void* dst, int dst_ld,

@@ -165,6 +165,7 @@ class Engine:
         self.q8_sparse = precision == "fp8-2:4"
         self.fp8_sparse_layers = []
         self.qbufs = {}
+        self._qld = {}                         # buffer id -> bytes per pixel of its byte buffer (_update_q8)
         self._q8_keys = None
         self.grad_scale = float(grad_scale)
         self.serial = 0
@@ -700,9 +701,11 @@ class Engine:
                 ops.pack_sparse24(lay.geom_act, lay.conv.weight.data, mask, lay.wsp, lay.widx)
             if self.q8 and lay.q8_on:      # e4m3 bytes + one exponent per filter, computed on the device
                 if lay.q8s_on:             # ... 2:4-compressed, with their index words
-                    ops.pack_q8_sparse24(lay.geom_act, lay.conv.weight.data, mask, lay.wqs, lay.widx8, lay.wexp)
+                    ops.pack_q8_sparse24(lay.geom_q8, lay.conv.weight.data, mask, lay.wqs, lay.widx8, lay.wexp)
+                elif lay.q8_slim:          # ... rows of round_up(cin, 64) channels, zero bytes behind the real ones
+                    ops.pack_q8_slim(lay.geom_q8, lay.conv.weight.data, mask, lay.wq, lay.wexp)
                 else:
-                    ops.pack_q8(lay.geom_act, lay.conv.weight.data, mask, lay.wq, lay.wexp)
+                    ops.pack_q8(lay.geom_q8, lay.conv.weight.data, mask, lay.wq, lay.wexp)
                     if self._qat_train(lay):   # the values those bytes stand for, fp32 OIHW: the dgrad packing's source
                         ops.fakequant_q8(lay.geom_act, lay.conv.weight.data, mask, lay.wexp, lay.w_q)
             if lay.stem:
@@ -748,9 +751,11 @@ class Engine:
         self.model._weights_dirty = False
 
     # ------------------------------------------------------------------ 2:4 sparsity
-    def _fused_eval(self, lay):
-        """Does this block take the fused inference path (BN + LeakyReLU [+ pool / reorg] in the conv epilogue)?"""
-        return (self.fuse_eval and not self.precise and not lay.is_last and lay.perm is None and lay.border is None
+    def _fused_eval(self, lay, border_ok=False):
+        """Does this block take the fused inference path (BN + LeakyReLU [+ pool / reorg] in the conv epilogue)?
+        `border_ok`: also with a border table (slim models) -- the fp8 epilogue adds it (_update_q8), the fp16 ones do not."""
+        return (self.fuse_eval and not self.precise and not lay.is_last and lay.perm is None
+                and (border_ok or lay.border is None)
                 and (lay.out2_t is None or lay.mode == L.DST_POOL)
                 and (lay.mode == L.DST_PLAIN or (lay.H % 2 == 0 and lay.W % 2 == 0)))
 
@@ -798,10 +803,18 @@ class Engine:
         (mcamd_cast_q8) writes in front of it.
         Precision "fp8-2:4": an fp8 block whose mask is present with the weight's shape and keeps at most 2 of every 4
         consecutive input channels at each (filter, tap) -- checked on the device, one host read for all blocks -- runs
-        the sparse fp8 kernel (`fp8_sparse_layers`); formats and buffers do not depend on that."""
+        the sparse fp8 kernel (`fp8_sparse_layers`); formats and buffers do not depend on that.
+        Slim models (a model some conv of which carries a border table; not under "fp8-qat"): a block with a
+        border table and / or an input channel count that is
+        no multiple of 64 becomes an fp8 block on mcamd_conv_fwd_q8_slim when it meets the other conditions above,
+        mcamd_conv_fwd_q8_slim_ok accepts it and round_up(cin, 64) <= 2 cin; it always runs the dense fp8 kernel.  Its K
+        loop reads round_up(cin, 64) bytes per pixel and tap, so a byte buffer's leading dimension (`_qld`, the private
+        copies' too) is raised until that span lies inside it for every fp8 reader; the bytes behind a tensor's channels are
+        allocated 0x00 and never written."""
         self._plan_epoch += 1             # recorded forward plans name the fp16, the fp8 or the sparse fp8 launch of a block
         for lay in self.layers:
             lay.q8_on, lay.q8_y, lay.q8_y2, lay.xq, lay.q8s_on = False, False, False, None, False
+            lay.q8_slim, lay.geom_q8 = False, lay.geom_act
             if getattr(lay, "y_f16", None) is not None:
                 lay.y, lay.stats = lay.y_f16, lay.stats_f16
         self.fp8_layers, self.fp8_sparse_layers = [], []
@@ -809,14 +822,23 @@ class Engine:
         # "fp8-qat" training engines keep their small images in the shared-halo form (both kernels read it); the set of
         # blocks is the inference engine's: the same predicate on everything that does not depend on the layout
         qat_train = self.qat and self.train_layout
+        # the slim form is for slim_export models (some conv carries a border table): every other model keeps the set it
+        # had -- conv2 of the dense YOLOv2 (32 input channels, no table) stays an fp16 block
+        slim_model = not self.qat and any(lay.border is not None for lay in self.layers)
         for lay in self.layers:
-            if (lay.li > 0 and not lay.stem and not lay.is_last and lay.cin % 64 == 0 and lay.fold is None
-                    and lay.g_cols is None and lay.g_rows is None and lay.n_act == lay.cout and (qat_train or not lay.pad)
-                    and self._fused_eval(lay) and ops.conv_fwd_q8_ok(lay.geom_act)):
+            if not (lay.li > 0 and not lay.stem and not lay.is_last and lay.fold is None and lay.g_cols is None
+                    and lay.g_rows is None and lay.n_act == lay.cout and (qat_train or not lay.pad)):
+                continue
+            if lay.cin % 64 == 0 and self._fused_eval(lay) and ops.conv_fwd_q8_ok(lay.geom_act):
                 lay.q8_on = True
+            elif (slim_model and (lay.border is not None or lay.cin % 64 != 0) and self._fused_eval(lay, border_ok=True)
+                  and ops.round_up(lay.cin, 64) <= 2 * lay.cin and ops.conv_fwd_q8_slim_ok(self._q8_geom(lay))):
+                lay.q8_on = lay.q8_slim = True
+            if lay.q8_on:
                 self.fp8_layers.append(lay.li + 1)     # conv number (conv1 = the first block)
         cand = [lay for lay in self.layers
-                if self.q8_sparse and lay.q8_on and lay.conv.mask_flag and lay.conv.mask.shape == lay.conv.weight.shape
+                if self.q8_sparse and lay.q8_on and not lay.q8_slim and lay.conv.mask_flag
+                and lay.conv.mask.shape == lay.conv.weight.shape
                 and ops.conv_fwd_q8_sparse24_ok(lay.geom_act)]
         if cand:
             counts = torch.zeros(len(cand), dtype=torch.int32, device=dev)
@@ -839,32 +861,39 @@ class Engine:
         for lay in self.layers:
             if not lay.q8_on:
                 continue
+            t = lay.tin
+            ws = writers.get(t.buf, [])
+            shared = bool(ws) and all(w.q8_on for w in ws) and all(r.q8_on for r in readers[t.buf])
+            # bytes per pixel of the buffer this block reads: wide enough for every fp8 reader's K loop (t.ld unless a
+            # reader's round_up(cin, 64) channels reach past it)
+            qld = max(self._q8_ld(r) for r in readers[t.buf]) if shared else self._q8_ld(lay)
+            if qld != t.ld or lay.q8_slim:
+                lay.geom_q8 = self._q8_geom(lay, qld)
             if lay.q8s_on:
-                nw, ni, ne = ops.q8_sparse24_elems(lay.geom_act)
+                nw, ni, ne = ops.q8_sparse24_elems(lay.geom_q8)
                 if getattr(lay, "wqs", None) is None or lay.wqs.numel() != nw:
                     lay.wqs = torch.zeros(nw, dtype=torch.uint8, device=dev)
                     lay.widx8 = torch.zeros(ni, dtype=torch.int32, device=dev)
             else:
-                nw, ne = ops.q8_elems(lay.geom_act)
+                nw, ne = ops.q8_slim_elems(lay.geom_q8) if lay.q8_slim else ops.q8_elems(lay.geom_q8)
                 if getattr(lay, "wq", None) is None or lay.wq.numel() != nw:
                     lay.wq = torch.zeros(nw, dtype=torch.uint8, device=dev)
             if getattr(lay, "wexp", None) is None or lay.wexp.numel() != ne:
                 lay.wexp = torch.zeros(ne, dtype=torch.int32, device=dev)
-            t = lay.tin
-            ws = writers.get(t.buf, [])
-            if ws and all(w.q8_on for w in ws) and all(r.q8_on for r in readers[t.buf]):
+            if shared:
                 live.add(t.buf)
-                if t.buf not in self.qbufs:
-                    self.qbufs[t.buf] = ops.alloc_padded_q8(self.B, t.H, t.W, t.ld, dev, pad=self._pad_for(t.W))
+                if t.buf not in self.qbufs or self._qld.get(t.buf) != qld:
+                    self.qbufs[t.buf] = ops.alloc_padded_q8(self.B, t.H, t.W, qld, dev, pad=self._pad_for(t.W))
+                    self._qld[t.buf] = qld
             else:
                 if qat_train and readers[t.buf] != [lay]:
                     # the training cast writes the dequantised values back over the fp16 slice, which is safe only when
                     # this block is the buffer's one reader (forward and weight gradient)
                     raise NotImplementedError("fp8-qat: conv%d reads an fp16 tensor that another block reads too"
                                               % (lay.li + 1))
-                key = (self.B, t.H, t.W, t.ld)
+                key = (self.B, t.H, t.W, qld)
                 if getattr(lay, "_xq_key", None) != key:
-                    lay._xq, lay._xq_key = ops.alloc_padded_q8(self.B, t.H, t.W, t.ld, dev, pad=self._pad_for(t.W)), key
+                    lay._xq, lay._xq_key = ops.alloc_padded_q8(self.B, t.H, t.W, qld, dev, pad=self._pad_for(t.W)), key
                 lay.xq = lay._xq
             if qat_train:
                 # fp32 raw output + its statistics slab (the fp16 ones come back when the block leaves the set), and w_q
@@ -877,10 +906,25 @@ class Engine:
                 lay.y, lay.stats = lay.y_f32, lay.stats_q8
         for b in [b for b in self.qbufs if b not in live]:
             del self.qbufs[b]
+            self._qld.pop(b, None)
         for lay in self.layers:
             if lay.q8_on:
                 lay.q8_y = lay.out_t.buf in self.qbufs
                 lay.q8_y2 = lay.out2_t is not None and lay.out2_t.buf in self.qbufs
+
+    def _q8_ld(self, lay):
+        """Bytes per pixel a byte buffer needs for this block to read its input from it: the fp16 buffer's leading dimension,
+        or more when the round_up(cin, 64) channels of the block's K loop (slim models) reach past it."""
+        return max(lay.tin.ld, ops.round_up(lay.tin.choff + ops.round_up(lay.cin, 64), 16))
+
+    def _q8_geom(self, lay, ld=None):
+        """Geometry of this block's fp8 launch on a byte buffer of `ld` bytes per pixel (default: _q8_ld)."""
+        return ops.geom(self.B, lay.H, lay.W, lay.k, lay.cin, lay.cout, ld if ld is not None else self._q8_ld(lay),
+                        lay.tin.choff, 0, lay.pad)
+
+    def _q8_tld(self, t, f8):
+        """Leading dimension of tensor `t` in the buffer a launch addresses: the byte buffer's (`f8`) or the fp16 one's."""
+        return self._qld[t.buf] if f8 else t.ld
 
     def _qat_train(self, lay):
         """Does this block train in the fp8 arithmetic (a block of fp8_layers in an "fp8-qat" training engine)?"""
@@ -933,16 +977,17 @@ class Engine:
             raise McamdError("conv%d is not an fp8 block (fp8_layers = %r)" % (conv_number, self.fp8_layers))
         B = self.B
 
-        def read(buf, f8, t, C):
+        def read(buf, f8, t, C, ld=None):
             if f8:
-                v = buf[: B * (t.H + 2) * (t.W + 2) * t.ld].view(B, t.H + 2, t.W + 2, t.ld)
+                ld = ld or self._qld[t.buf]
+                v = buf[: B * (t.H + 2) * (t.W + 2) * ld].view(B, t.H + 2, t.W + 2, ld)
             else:
                 v = ops.padded_view(buf, B, t.H, t.W, t.ld)
             v = v[:, 1:-1, 1:-1, t.choff:t.choff + C].permute(0, 3, 1, 2).contiguous().cpu()
             return v if f8 else v.float()
         t, t2, ti = lay.out_t, lay.out2_t, lay.tin
         cdst = 4 * lay.cout if lay.mode == L.DST_REORG else lay.cout
-        out = dict(x8=read(lay.xq if lay.xq is not None else self.qbufs[ti.buf], True, ti, lay.cin),
+        out = dict(x8=read(lay.xq if lay.xq is not None else self.qbufs[ti.buf], True, ti, lay.cin, lay.geom_q8.x_ld),
                    y=read(self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf], lay.q8_y, t, cdst), y_f8=lay.q8_y,
                    y2=None, y2_f8=lay.q8_y2, dst={L.DST_PLAIN: "plain", L.DST_POOL: "pool", L.DST_REORG: "reorg"}[lay.mode],
                    scale=lay.scale.cpu(), shift=lay.shift.cpu(), slope=lay.slope)
@@ -1352,7 +1397,7 @@ class Engine:
                                pool_act=af, pool_act_ld=ops.round_up(lay.cout, 8) if af is not None else 0,
                                pool_act_pad=self._pad_for(lay.W) if af is not None else 0)
                 continue
-            if not training and self._fused_eval(lay):
+            if not training and (self._fused_eval(lay) or (self.q8 and lay.q8_on)):
                 # inference: BN (running statistics) + LeakyReLU -- and the MaxPool / Reorg that follows the block -- in the
                 # conv epilogue, written straight into the consumer's padded buffer: the raw output is never stored (one
                 # fp16 rounding per layer, no second pass)
@@ -1362,20 +1407,25 @@ class Engine:
                 q8 = self.q8 and lay.q8_on
                 # destination form of the epilogue: plain / pool (+ the full-resolution copy y2, bytes or fp16) / reorg
                 y2 = None if t2 is None else (self.qbufs if q8 and lay.q8_y2 else self.bufs)[t2.buf]
-                dst = dict(dst_mode=lay.mode, y2=y2, y2_ld=t2.ld if t2 is not None else 0,
+                dst = dict(dst_mode=lay.mode, y2=y2, y2_ld=self._q8_tld(t2, q8 and lay.q8_y2) if t2 is not None else 0,
                            y2_choff=t2.choff if t2 is not None else 0)
                 if q8:                      # e4m3 activations x e4m3 weights (Darknet.precision = "fp8", _update_q8)
                     x8 = self.qbufs.get(lay.tin.buf)
                     if lay.xq is not None:  # the fp16 -> fp8 edge: cast pass over the padded input slice
                         ti, x8 = lay.tin, lay.xq
                         self._timed('cast', lay, ops.cast_q8, xin, B * (ti.H + 2) * (ti.W + 2), ti.ld, ti.choff, lay.cin,
-                                    x8, ti.ld, ti.choff)
-                    y = self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf]
+                                    x8, lay.geom_q8.x_ld, ti.choff)
+                    y, y_ld = (self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf]), self._q8_tld(t, lay.q8_y)
                     if lay.q8s_on:          # ... 2:4-compressed weights on the sparse MFMA ("fp8-2:4")
-                        self._timed('fwd', lay, ops.conv_fwd_q8_sparse24, lay.geom_act, x8, lay.wqs, lay.widx8, lay.wexp, y,
-                                    t.ld, t.choff, lay.scale, lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
+                        self._timed('fwd', lay, ops.conv_fwd_q8_sparse24, lay.geom_q8, x8, lay.wqs, lay.widx8, lay.wexp, y,
+                                    y_ld, t.choff, lay.scale, lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
                         continue
-                    self._timed('fwd', lay, ops.conv_fwd_q8, lay.geom_act, x8, lay.wq, lay.wexp, y, t.ld, t.choff, lay.scale,
+                    if lay.q8_slim:         # ... a slim model's block: zero-padded K, border table in the epilogue
+                        self._timed('fwd', lay, ops.conv_fwd_q8_slim, lay.geom_q8, x8, lay.wq, lay.wexp, y, y_ld, t.choff,
+                                    lay.scale, lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, border=lay.border,
+                                    border_ld=lay.cout, **dst)
+                        continue
+                    self._timed('fwd', lay, ops.conv_fwd_q8, lay.geom_q8, x8, lay.wq, lay.wexp, y, y_ld, t.choff, lay.scale,
                                 lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
                     continue
                 if lay.sp_on:       # 2:4 weights on the sparse MFMA (Darknet.sparse, _update_sparse)

@@ -836,6 +836,46 @@ def conv_fwd_q8(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slo
                                     stream_ptr()), "mcamd_conv_fwd_q8")
 
 
+# ... of slim_export models: cin a multiple of 8 on zero-padded weight rows, border table in the epilogue
+def conv_fwd_q8_slim_ok(g):
+    """Does mcamd_conv_fwd_q8_slim accept this geometry?  (Shared by the engine and the tests; needs no device.)"""
+    return bool(L.lib().mcamd_conv_fwd_q8_slim_ok(C.byref(g)))
+
+
+def q8_slim_elems(g):
+    out = (C.c_int64 * 2)()
+    check(L.lib().mcamd_q8_slim_elems(C.byref(g), out), "mcamd_q8_slim_elems")
+    return int(out[0]), int(out[1])
+
+
+def pack_q8_slim(g, w, mask=None, out_w=None, out_exp=None):
+    """pack_q8 into rows of round_up(cin, 64) channels per tap, pad channels 0x00 (mcamd_pack_q8_slim)."""
+    _need_cuda(w, mask)
+    assert w.dtype == torch.float32 and w.is_contiguous()
+    nw, ne = q8_slim_elems(g)
+    if out_w is None:
+        out_w = torch.empty(nw, dtype=torch.uint8, device=w.device)
+    if out_exp is None:
+        out_exp = torch.empty(ne, dtype=torch.int32, device=w.device)
+    if out_w.numel() < nw or out_exp.numel() < ne:
+        raise L.McamdError("pack_q8_slim: destination too small")
+    check(L.lib().mcamd_pack_q8_slim(C.byref(g), ptr(w), ptr(mask), ptr(out_w), ptr(out_exp), stream_ptr()), "mcamd_pack_q8_slim")
+    return out_w, out_exp
+
+
+def conv_fwd_q8_slim(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
+                     y2_choff=0, y_f8=False, y2_f8=False, border=None, border_ld=0):
+    """conv_fwd_q8 for cin % 8 == 0 from pack_q8_slim's rows, with the fp32 [16][border_ld] table `border` (or None) added to
+    the raw value by pixel class in the epilogue (mcamd_conv_fwd_q8_slim)."""
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff)
+    if border is not None:
+        assert border.dtype == torch.float32 and border.is_contiguous()
+        border_ld = border_ld or border.shape[-1]
+    check(L.lib().mcamd_conv_fwd_q8_slim(C.byref(g), ptr(x8), ptr(wq), ptr(wexp), C.byref(e), ptr(border), int(border_ld),
+                                         int(bool(y_f8)), int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q8_slim")
+
+
 def cast_q8(src, pixels, src_ld, src_choff, C_, dst, dst_ld, dst_choff=0, write_back=False):
     """fp16 channel slice of `pixels` pixels -> e4m3(2 x) bytes (mcamd_cast_q8): the fp16 -> fp8 edge of the fp8 engine.
     `write_back` (training, mcamd_cast_q8_train): the fp16 slice is overwritten with deq(code) / 2."""

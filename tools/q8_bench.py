@@ -4,7 +4,11 @@ passes; the cast pass of the fp16 -> fp8 edge is charged to its block), the whol
 three pairs of windows of at least 100 forwards each -- and the logits rel-L2 between them.
 --sparse: the model is nm_prune'd (2:4 masks) and four engines are measured the same way on the same masked weights: fp16,
 fp16 with sparse = "2:4", fp8 and fp8-2:4 (windows alternated over all four).
-usage: python tools/q8_bench.py [batch] [forwards per window] [--sparse] [--json PATH]"""
+--slim PCT: the model is quick_filter_prune(PCT)'d and slim_export'ed; the slim model is measured in fp16 (its
+unfused border path) and fp8 the same way, and the table names per layer cin -> round_up(cin, 64), which blocks are fp8
+blocks (`slim`: on mcamd_conv_fwd_q8_slim, `table`: with a border table) and the time of each cast pass.  Run it once
+without and once with MCAMD_Q8_MFMA=1 for the two forms of the fp8 kernel.
+usage: python tools/q8_bench.py [batch] [forwards per window] [--sparse | --slim PCT] [--json PATH]"""
 import json
 import os
 import sys
@@ -14,17 +18,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def parse(argv):
-    args = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] != "--json")]
+    args = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] not in ("--json", "--slim"))]
     B = int(args[0]) if len(args) > 0 else 128
     K = int(args[1]) if len(args) > 1 else 100
     out_json = argv[argv.index("--json") + 1] if "--json" in argv else None
+    slim_pct = float(argv[argv.index("--slim") + 1]) if "--slim" in argv else None
     if B < 1 or K < 1:
         raise SystemExit("q8_bench: batch and forwards per window must be positive")
-    return B, K, out_json, "--sparse" in argv
+    if slim_pct is not None and ("--sparse" in argv or not 0.0 < slim_pct < 100.0):
+        raise SystemExit("q8_bench: --slim takes a percentage in (0, 100) and does not combine with --sparse")
+    return B, K, out_json, "--sparse" in argv, slim_pct
 
 
 def main(argv):
-    B, K, out_json, sparse = parse(argv)
+    B, K, out_json, sparse, slim_pct = parse(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("q8_bench needs the GPU")
@@ -35,6 +42,13 @@ def main(argv):
     m.eval()
     x = synthetic_batch(B, 416, 416, seed=0, device=dev)
     modes = ("fp16", "fp8")
+    if slim_pct is not None:
+        import tempfile
+        from modelcompression_amd import slim
+        from modelcompression_amd.pruning.weightPruning.methods import quick_filter_prune
+        m.set_masks(quick_filter_prune(m, slim_pct))
+        with tempfile.TemporaryDirectory() as tmp:
+            m = slim.slim_export(m, os.path.join(tmp, "slim.cfg"))
     if sparse:
         from modelcompression_amd.pruning.weightPruning.methods import nm_prune
         m.set_masks(nm_prune(m))
@@ -46,7 +60,8 @@ def main(argv):
     def engine(mode):
         return [e for k, e in m._engines.items() if k[3] == mode.split("+")[0] and not e.train_layout][0]
 
-    def layer_times(prec, passes=5):
+    def layer_times(prec, passes=5, only=None):
+        """conv number -> median ms of the block's launches (`only`: of the launches with that tag, e.g. 'cast')"""
         eng = engine(prec)
         per = {}
         for _ in range(passes):
@@ -55,7 +70,8 @@ def main(argv):
             torch.cuda.synchronize()
             once = {}
             for tag, lay, e0, e1, _host in eng.events:
-                once[lay.li + 1] = once.get(lay.li + 1, 0.0) + e0.elapsed_time(e1)
+                if only is None or tag == only:
+                    once[lay.li + 1] = once.get(lay.li + 1, 0.0) + e0.elapsed_time(e1)
             for k, v in once.items():
                 per.setdefault(k, []).append(v)
             eng.events = None
@@ -69,6 +85,8 @@ def main(argv):
                 y = m(x)
             torch.cuda.synchronize()
             res[prec] = {"logits": y.clone(), "layers": layer_times(prec)}
+            if slim_pct is not None and prec == "fp8":
+                res[prec]["casts"] = layer_times(prec, only="cast")
             if prec == "fp16+2:4":
                 sparse_layers = list(engine(prec).sparse_layers)
         fp8_layers = list(engine("fp8").fp8_layers)
@@ -85,6 +103,8 @@ def main(argv):
                 torch.cuda.synchronize()
                 rates[prec].append(B * K / (time.perf_counter() - t0))
 
+    if slim_pct is not None:
+        return report_slim(B, K, out_json, slim_pct, engine("fp8"), res, rates)
     if sparse:
         return report_sparse(B, K, out_json, modes, res, rates, fp8_layers, list(engine("fp8-2:4").fp8_sparse_layers), sparse_layers)
     d, s = res["fp16"], res["fp8"]
@@ -103,6 +123,39 @@ def main(argv):
     if out_json:
         with open(out_json, "w") as f:
             json.dump({"B": B, "forwards_per_window": K, "fp8_layers": fp8_layers, "fp16_ms": d["layers"], "fp8_ms": s["layers"],
+                       "fp16_img_s": rates["fp16"], "fp8_img_s": rates["fp8"], "pairs": pairs, "rel_l2": rel}, f, indent=1)
+
+
+def report_slim(B, K, out_json, pct, eng, res, rates):
+    d, s = res["fp16"], res["fp8"]
+    rel = float((s["logits"].double() - d["logits"].double()).norm() / d["logits"].double().norm())
+    mfma = os.environ.get("MCAMD_Q8_MFMA", "0")
+    fp8_layers = list(eng.fp8_layers)
+    print("slim %g %%, MCAMD_Q8_MFMA=%s; fp8 layers (conv numbers): %s" % (pct, mfma, fp8_layers))
+    print("%-6s %5s %8s %10s %10s %9s %7s  %s" % ("conv", "cin", "cin_pad", "fp16 ms", "fp8 ms", "(cast ms)", "ratio", "block"))
+    rows = []
+    for lay in eng.layers:
+        k = lay.li + 1
+        dm, sm, cm = d["layers"].get(k, float("nan")), s["layers"].get(k, float("nan")), s["casts"].get(k)
+        on = k in fp8_layers
+        kind = "fp16" if not on else "fp8" + (" slim" if lay.q8_slim else "") + (" table" if lay.border is not None else "")
+        if not on and lay.border is not None:
+            kind += " table (unfused)"
+        cp = (lay.cin + 63) // 64 * 64 if on else lay.cin
+        rows.append({"conv": k, "cin": lay.cin, "cin_pad": cp, "cout": lay.cout, "fp16_ms": dm, "fp8_ms": sm, "cast_ms": cm, "block": kind})
+        print("%-6s %5d %8d %10.3f %10.3f %9s %7.2f  %s" % ("conv%d" % k, lay.cin, cp, dm, sm, "" if cm is None else "%.3f" % cm, dm / sm, kind))
+    td, ts = sum(d["layers"].values()), sum(s["layers"].values())
+    print("%-6s %5s %8s %10.3f %10.3f %9.3f %7.2f" % ("sum", "", "", td, ts, sum(s["casts"].values()), td / ts))
+    for p in ("fp16", "fp8"):
+        r = rates[p]
+        print("whole forward B=%d, %d forwards per window, %-5s %s img/s (spread %.2f %%)"
+              % (B, K, p + ":", ["%.0f" % v for v in r], 100.0 * (max(r) - min(r)) / min(r)))
+    pairs = [b / a for a, b in zip(rates["fp16"], rates["fp8"])]
+    print("pairs fp8 / fp16: %s" % ["%.3f" % p for p in pairs])
+    print("logits rel-L2 (fp8 vs fp16 engine, same slim weights): %.3e" % rel)
+    if out_json:
+        with open(out_json, "w") as f:
+            json.dump({"B": B, "forwards_per_window": K, "slim_pct": pct, "mfma": mfma, "fp8_layers": fp8_layers, "layers": rows,
                        "fp16_img_s": rates["fp16"], "fp8_img_s": rates["fp8"], "pairs": pairs, "rel_l2": rel}, f, indent=1)
 
 
