@@ -747,6 +747,40 @@ int mcamd_region_loss(const mcamd_region_desc* d, float* loss, float* grad, int3
                       size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Detection post-processing of the eval path (reference src/nets2_utils.py:141-259 get_region_boxes + nms, chained as
+ * predict.py:148-173 does).  N = H * W * num_anchors rows per image in the reference's (cy, cx, anchor) order,
+ * N <= 2048, num_anchors <= 8, num_classes <= 80; anything else returns MCAMD_EINVAL and launches nothing.
+ * None of the three allocates, synchronises or can be recorded into a launch plan.
+ *   output  : fp32 [B][num_anchors * (5 + num_classes)][H][W] -- what Darknet.forward returns
+ *   anchors : num_anchors (w, h) pairs in grid units
+ *
+ * mcamd_region_decode: head [B][N][7] = x, y, w, h (network-relative), box_conf, cls_max_conf, cls_max_id (as float;
+ *   the first maximum), cls_conf [B][N][num_classes] = the softmax class confidences.
+ *
+ * mcamd_nms: greedy suppression of nets2_utils.py:236-259 for B images of n <= 2048 boxes (cx, cy, w, h), 16-byte
+ *   aligned.  order [B][n]: the stable ascending sort of the fp32 key 1.0f - conf (ties by lower index) over all n
+ *   entries; kept [B][n]: whether the r-th box of that order survives.  Candidates are conf > 0; a candidate is kept iff
+ *   no KEPT box before it in the order has iou > nms_thresh with it (bbox_iou, x1y1x2y2=False, strict).
+ *
+ * mcamd_detect: decode, candidates box_conf * cls_max_conf > conf_thresh, sort by 1 - box_conf, suppression and
+ *   compaction in one launch.  rows [B][N][8]: the kept boxes by descending confidence, the seven head values and the
+ *   row index n (as float); probs [B][N][num_classes] = box_conf * cls_conf of the same rows; nkept [B] = kept boxes per
+ *   image.  Rows at or beyond nkept[b] are unspecified.  head_out / cls_out (each may be NULL) receive the full decode,
+ *   bit-equal to mcamd_region_decode's.
+ * ------------------------------------------------------------------------- */
+typedef struct mcamd_detect_desc {
+    const float* output;
+    int32_t B, H, W, num_anchors, num_classes;
+    float anchors[16];
+    float conf_thresh, nms_thresh;                            /* mcamd_detect only */
+} mcamd_detect_desc;
+int mcamd_region_decode(const mcamd_detect_desc* d, float* head, float* cls_conf, void* stream);
+int mcamd_nms(const float* boxes, const float* conf, int32_t B, int32_t n, float nms_thresh, int32_t* order,
+              uint8_t* kept, void* stream);
+int mcamd_detect(const mcamd_detect_desc* d, float* rows, float* probs, int32_t* nkept, float* head_out,
+                 float* cls_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Training augmentation (reference src/dataloader.py:148-178 data_augmentation + ToTensor(), train=True): per image
  * crop (outside the source reads 0) -> Pillow bicubic resize -> optional left-right flip -> Pillow RGB->HSV, three
  * point LUTs, HSV->RGB -> out = u8 / 255.f.  Bit-equal to the reference's PIL chain: the host builds Pillow's

@@ -348,6 +348,19 @@ class Darknet(nn.Module):
             return eng.forward(x, self.training)
         return _DarknetFn.apply(self, eng, self.training, x, self._anchor)
 
+    def detect(self, images, conf_thresh=0.25, nms_thresh=0.45):
+        """Eval forward plus the fused post-processing (nets2_utils.detections_device): device tensors
+        (rows [B, N, 8], probs [B, N, C], nkept [B]) with no host synchronisation, in every eval precision."""
+        from .nets2_utils import detections_device
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                out = self(images)
+            return detections_device(out, conf_thresh, nms_thresh, self.num_classes, self.anchors, self.num_anchors)
+        finally:
+            self.train(was_training)
+
     def print_network(self):
         print_cfg(self.blocks)
 

@@ -210,6 +210,38 @@ def detections(output, CONF_THRESH, NMS_THRESH, num_classes, anchors_list, ancho
     return res
 
 
+def detections_device(output, CONF_THRESH, NMS_THRESH, num_classes, anchors_list, anchors_cell):
+    """The device half of `detections` as ONE HIP launch (csrc/detect.hip, mcamd_detect) and no host synchronisation:
+        rows  [B, N, 8]  the kept boxes of each image by descending objectness: x, y, w, h, box_conf, cls_max_conf,
+                         cls_max_id and the row index (cy, cx, anchor order) of the box
+        probs [B, N, C]  box_conf * cls_conf of the same rows
+        nkept [B] int32  kept boxes per image; rows at or beyond nkept[b] are unspecified
+    More than ops.DETECT_MAX_ROWS rows per image (the kernel holds them in LDS) raise McamdError."""
+    from . import ops
+    if output.dim() == 3:
+        output = output.unsqueeze(0)
+    return ops.detect(output.detach().float().contiguous(), anchors_list, anchors_cell, num_classes, CONF_THRESH, NMS_THRESH)
+
+
+def detections_fused(output, CONF_THRESH, NMS_THRESH, num_classes, anchors_list, anchors_cell):
+    """`detections` through `detections_device`: the same list format, one read of nkept and one copy of the kept rows."""
+    rows, probs, nkept = detections_device(output, CONF_THRESH, NMS_THRESH, num_classes, anchors_list, anchors_cell)
+    nk = nkept.cpu().tolist()
+    top = max(nk)
+    both = torch.cat((rows[:, :top], probs[:, :top]), 2).cpu()
+    rows_c, probs_c = both[..., :8], both[..., 8:]
+    emit_c = probs_c > CONF_THRESH
+    res = []
+    for b, k in enumerate(nk):
+        dets = []
+        for r in range(k):
+            top_c = int(rows_c[b, r, 6])
+            cls = [top_c] + [c for c in torch.nonzero(emit_c[b, r]).flatten().tolist() if c != top_c]
+            dets.append((rows_c[b, r, :4], [(c, probs_c[b, r, c]) for c in cls]))
+        res.append(dets)
+    return res
+
+
 def get_image_size(fname):
     """Width, height of a PNG / GIF / JPEG without decoding it (nets2_utils.py:502-535)."""
     with open(fname, 'rb') as fh:

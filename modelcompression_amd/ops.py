@@ -591,6 +591,63 @@ def region_loss(output, target, anchors, num_anchors, num_classes, coord_scale, 
     return loss, grad, counts
 
 
+# ------------------------------------------------------------------ detection post-processing (csrc/detect.hip)
+DETECT_MAX_ROWS = 2048      # rows (cells x anchors) per image the kernels hold in LDS
+
+
+def _detect_desc(output, anchors, num_anchors, num_classes, conf_thresh=0.0, nms_thresh=0.0):
+    _need_cuda(output)
+    assert output.dtype == torch.float32 and output.is_contiguous() and output.dim() == 4
+    B, ch, H, W = output.shape
+    if ch != num_anchors * (5 + num_classes):
+        raise L.McamdError("detect: %d channels, expected %d anchors x (5 + %d classes)" % (ch, num_anchors, num_classes))
+    if num_anchors < 1 or len(anchors) < 2 * num_anchors:
+        raise L.McamdError("detect: %d anchor values for %d anchors" % (len(anchors), num_anchors))
+    d = L.DetectDesc()
+    d.output = output.data_ptr()
+    d.B, d.H, d.W, d.num_anchors, d.num_classes = B, H, W, num_anchors, num_classes
+    step = len(anchors) // num_anchors
+    for n in range(min(num_anchors, 8)):
+        d.anchors[2 * n], d.anchors[2 * n + 1] = float(anchors[step * n]), float(anchors[step * n + 1])
+    d.conf_thresh, d.nms_thresh = float(conf_thresh), float(nms_thresh)
+    return d, B, H * W * num_anchors
+
+
+def region_decode(output, anchors, num_anchors, num_classes):
+    """head [B, N, 7], cls_conf [B, N, C] of nets2_utils.region_boxes_tensors in one library call (mcamd_region_decode)."""
+    d, B, N = _detect_desc(output, anchors, num_anchors, num_classes)
+    head = torch.empty(B, N, 7, dtype=torch.float32, device=output.device)
+    cls = torch.empty(B, N, num_classes, dtype=torch.float32, device=output.device)
+    check(L.lib().mcamd_region_decode(C.byref(d), ptr(head), ptr(cls), stream_ptr()), "mcamd_region_decode")
+    return head, cls
+
+
+def nms(boxes, conf, nms_thresh):
+    """(order int32 [B, n], kept uint8 [B, n]) of nets2_utils.nms_tensors in one library call (mcamd_nms)."""
+    _need_cuda(boxes, conf)
+    boxes, conf = boxes.detach().float().contiguous(), conf.detach().float().contiguous()
+    assert boxes.dim() == 3 and boxes.shape[2] == 4 and conf.shape == boxes.shape[:2]
+    B, n = conf.shape
+    order = torch.empty(B, n, dtype=torch.int32, device=boxes.device)
+    kept = torch.empty(B, n, dtype=torch.uint8, device=boxes.device)
+    check(L.lib().mcamd_nms(ptr(boxes), ptr(conf), B, n, float(nms_thresh), ptr(order), ptr(kept), stream_ptr()), "mcamd_nms")
+    return order, kept
+
+
+def detect(output, anchors, num_anchors, num_classes, conf_thresh, nms_thresh, want_decode=False):
+    """Decode, threshold, sort, greedy NMS and compaction in one launch (mcamd_detect): rows [B, N, 8], probs [B, N, C],
+    nkept int32 [B]; rows at or beyond nkept[b] are unspecified.  want_decode adds the full (head, cls_conf)."""
+    d, B, N = _detect_desc(output, anchors, num_anchors, num_classes, conf_thresh, nms_thresh)
+    dev = output.device
+    rows = torch.empty(B, N, 8, dtype=torch.float32, device=dev)
+    probs = torch.empty(B, N, num_classes, dtype=torch.float32, device=dev)
+    nkept = torch.empty(B, dtype=torch.int32, device=dev)
+    head = torch.empty(B, N, 7, dtype=torch.float32, device=dev) if want_decode else None
+    cls = torch.empty(B, N, num_classes, dtype=torch.float32, device=dev) if want_decode else None
+    check(L.lib().mcamd_detect(C.byref(d), ptr(rows), ptr(probs), ptr(nkept), ptr(head), ptr(cls), stream_ptr()), "mcamd_detect")
+    return (rows, probs, nkept, head, cls) if want_decode else (rows, probs, nkept)
+
+
 # ------------------------------------------------------------------ launch plans
 class Plan:
     """A recorded sequence of library calls (include/mcamd.h, "Launch plans"), replayed with one call per segment."""

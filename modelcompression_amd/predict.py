@@ -15,10 +15,15 @@ import torch
 
 from .data import VOCList, SyntheticDetection
 from .nets import getYOLOv2
-from .nets2_utils import get_region_boxes, nms, detections, get_image_size  # noqa: F401
+from .nets2_utils import get_region_boxes, nms, detections, detections_fused, get_image_size  # noqa: F401
+from .ops import DETECT_MAX_ROWS
 
 
 class PASCALVOCEval():
+    # True: CUDA logits go through the one-launch HIP post-processing (csrc/detect.hip, nets2_utils.detections_fused);
+    # False: the batched torch restatement (nets2_utils.detections), which also serves grids of more rows per image than
+    # the kernel holds.  Off until tools/detect_bench.py has measured the fused path faster.
+    fused = False
 
     def __init__(self, MODEL, MODEL_CFGFILE, MODEL_WEIGHTFILE, MODEL_LOSS,
                  PASCAL_DIR, EVAL_IMAGELIST, EVAL_OUTPUTDIR, EVAL_PREFIX, EVAL_OUTPUTDIR_PKL,
@@ -65,8 +70,10 @@ class PASCALVOCEval():
                     val_loss_total += float(self.MODEL_LOSS(output, target.float().to(dev)))
                 # predict.py:148-173 (get_region_boxes(.., 0, 1) -> nms -> one line per class above the threshold) as one
                 # batched device computation; only the surviving detections come to the host
-                batch_dets = detections(output, CONF_THRESH, NMS_THRESH, self.MODEL.num_classes, self.MODEL.anchors,
-                                        self.MODEL.num_anchors)
+                rows = output.size(2) * output.size(3) * self.MODEL.num_anchors
+                post = detections_fused if self.fused and output.is_cuda and rows <= DETECT_MAX_ROWS else detections
+                batch_dets = post(output, CONF_THRESH, NMS_THRESH, self.MODEL.num_classes, self.MODEL.anchors,
+                                  self.MODEL.num_anchors)
                 for i in range(output.size(0)):
                     lineId += 1
                     fileId = os.path.basename(valid_files[lineId]).split('.')[0]
