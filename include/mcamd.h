@@ -781,6 +781,56 @@ int mcamd_detect(const mcamd_detect_desc* d, float* rows, float* probs, int32_t*
                  float* cls_out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * VOC07 evaluation on the device (reference src/predict.py:250-437, voc_eval + voc_ap with use_07_metric=True), fed by
+ * what mcamd_detect writes.  The per-class AP values are the float64 values that the reference's file path computes
+ * from the same detections: it prints every fp32 score and coordinate with "%f" and parses the text as a double, which
+ * is q(v) = rint((double)v * 1e6) / 1e6 exactly.  Neither call allocates, synchronises or can be recorded into a launch
+ * plan; every limit is checked before the launch (MCAMD_EINVAL, nothing launched).
+ *
+ * mcamd_voc_match: for image b of the batch, row r < nkept[b] and class c, a record is emitted when
+ *   probs[b][r][c] > conf_thresh or c == cls_max_id of the row (rows[b][r][6]); rows at or beyond nkept[b] are never
+ *   read.  Its box is x1 = q(fl32(fl32(x - fl32(w / 2)) * W)), y1, x2 (+), y2 likewise with the image's (W, H) as fp32.
+ *   Per (image, class) the records are matched in the order (descending q(score), ascending r) against the image's
+ *   ground-truth objects of that class in table order, in float64 term by term as voc_eval writes it:
+ *   iw = max((min(g2, b2) - max(g0, b0)) + 1., 0.), ih likewise, uni = ((b2 - b0 + 1.) * (b3 - b1 + 1.) +
+ *   (g2 - g0 + 1.) * (g3 - g1 + 1.)) - iw * ih; the first maximum of iw * ih / uni wins; with no object of the class the
+ *   maximum is -inf.  flag = 1 (tp) when the maximum > ovthresh and its object is neither difficult nor matched yet (it
+ *   is matched from then on), 0 (neither) when that object is difficult, 2 (fp) otherwise.
+ *   Every record takes a slot from counters[0] (atomically; slot order is arbitrary) and writes keys[slot], flags[slot];
+ *   a record whose slot is >= capacity is counted in counters[1] and not written.  The caller zeroes counters before the
+ *   first batch.  The 64-bit key is a total order, class, then descending q(score), then image, then row:
+ *       bit 63      0 (the keys also sort as signed 64-bit integers)
+ *       bits 62-56  class
+ *       bits 55-36  1000000 - rint(score * 1e6)
+ *       bits 35-11  first_image + b              (first_image + B <= 2^25)
+ *       bits 10-0   r
+ *   Limits: N <= 2048, C <= 80, G <= 64.
+ *     rows, probs, nkept : [B][N][8], [B][N][C], [B] as mcamd_detect writes them
+ *     gt_box             : int32 [B][G][4] xmin, ymin, xmax, ymax;  gt_cls, gt_difficult: uint8 [B][G];
+ *     gt_count           : int32 [B] objects per image (<= G);  image_size: int32 [B][2] width, height
+ *
+ * mcamd_voc_ap: keys / flags are the records SORTED by key (flags permuted alike), n = min(counters[0], capacity) of
+ *   them; npos [C] = non-difficult objects per class.  Per class, over its records in order:
+ *   rec = tp_cum / (double)max(npos, 1), prec = tp_cum / max(tp_cum + fp_cum, DBL_EPSILON), p_i = the maximum of prec
+ *   where rec >= i * 0.1 (0 when nowhere), ap = the sequential sum of p_i / 11., i = 0 .. 10; 0.0 without records.
+ *   ap [C]; rec, prec (each may be NULL) receive the curves at the records' sorted positions.
+ * ------------------------------------------------------------------------- */
+typedef struct mcamd_voc_match_desc {
+    const float* rows; const float* probs; const int32_t* nkept;
+    int32_t B, N, C, G;
+    float conf_thresh;
+    int32_t first_image;
+    double ovthresh;
+    const int32_t* gt_box; const uint8_t* gt_cls; const uint8_t* gt_difficult; const int32_t* gt_count;
+    const int32_t* image_size;
+    uint64_t* keys; uint8_t* flags; int64_t capacity;
+    uint64_t* counters;                                       /* [0] records, [1] records lost to the capacity */
+} mcamd_voc_match_desc;
+int mcamd_voc_match(const mcamd_voc_match_desc* d, void* stream);
+int mcamd_voc_ap(const uint64_t* keys, const uint8_t* flags, const uint64_t* counters, int64_t capacity,
+                 const int32_t* npos, int32_t C, double* ap, double* rec, double* prec, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Training augmentation (reference src/dataloader.py:148-178 data_augmentation + ToTensor(), train=True): per image
  * crop (outside the source reads 0) -> Pillow bicubic resize -> optional left-right flip -> Pillow RGB->HSV, three
  * point LUTs, HSV->RGB -> out = u8 / 255.f.  Bit-equal to the reference's PIL chain: the host builds Pillow's

@@ -113,6 +113,16 @@ class DetectDesc(C.Structure):
                 ("anchors", C.c_float * 16), ("conf_thresh", C.c_float), ("nms_thresh", C.c_float)]
 
 
+class VocMatchDesc(C.Structure):
+    """mcamd_voc_match_desc (include/mcamd.h)."""
+    _fields_ = [("rows", C.c_void_p), ("probs", C.c_void_p), ("nkept", C.c_void_p),
+                ("B", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("G", C.c_int32),
+                ("conf_thresh", C.c_float), ("first_image", C.c_int32), ("ovthresh", C.c_double),
+                ("gt_box", C.c_void_p), ("gt_cls", C.c_void_p), ("gt_difficult", C.c_void_p), ("gt_count", C.c_void_p),
+                ("image_size", C.c_void_p),
+                ("keys", C.c_void_p), ("flags", C.c_void_p), ("capacity", C.c_int64), ("counters", C.c_void_p)]
+
+
 class FoldJob(C.Structure):
     _fields_ = [("d", FoldDesc), ("waug", C.c_void_p), ("first_block", C.c_int64)]
 
@@ -210,6 +220,8 @@ SIGNATURES = {
     "mcamd_region_decode": (C.c_int, [C.POINTER(DetectDesc), _P, _P, _P]),
     "mcamd_nms": (C.c_int, [_P, _P, _I32, _I32, _F, _P, _P, _P]),
     "mcamd_detect": (C.c_int, [C.POINTER(DetectDesc), _P, _P, _P, _P, _P, _P]),
+    "mcamd_voc_match": (C.c_int, [C.POINTER(VocMatchDesc), _P]),
+    "mcamd_voc_ap": (C.c_int, [_P, _P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
     "mcamd_augment": (C.c_int, [C.POINTER(AugmentBatch), _P]),
     "mcamd_plan_begin": (C.c_int, [C.POINTER(_P), _I32]),
     "mcamd_plan_mark": (_I32, []),

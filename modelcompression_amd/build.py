@@ -39,6 +39,7 @@ SOURCES = {
     "prune.hip": ["-ffp-contract=off"],   # pinned fp32 arithmetic: no FMA contraction
     "augment.hip": ["-ffp-contract=off"], # Pillow's float / double HSV arithmetic, operation by operation
     "detect.hip": ["-ffp-contract=off"],  # suppression decisions are pinned fp32 comparisons; one decode, bit for bit
+    "voc_eval.hip": ["-ffp-contract=off"],  # voc_eval's float64 arithmetic, operation by operation
 }
 
 

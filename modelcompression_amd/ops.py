@@ -648,6 +648,63 @@ def detect(output, anchors, num_anchors, num_classes, conf_thresh, nms_thresh, w
     return (rows, probs, nkept, head, cls) if want_decode else (rows, probs, nkept)
 
 
+# ------------------------------------------------------------------ VOC07 evaluation (csrc/voc_eval.hip)
+VOC_MAX_OBJECTS = 64        # ground-truth objects per image: one lane of a wave each
+VOC_KEY_CLASS_SHIFT, VOC_KEY_SCORE_SHIFT, VOC_KEY_IMAGE_SHIFT = 56, 36, 11      # key layout, include/mcamd.h
+
+
+def _voc_tensor(t, dtype, shape, name):
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise L.McamdError("voc_match: `%s` must be a contiguous %s tensor of shape %s, got %s %s"
+                           % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+
+
+def voc_match(rows, probs, nkept, conf_thresh, ovthresh, first_image, gt_box, gt_cls, gt_difficult, gt_count, image_size,
+              keys, flags, counters):
+    """Append the batch's detection records (64-bit sort key, tp / fp / neither flag) to keys / flags (mcamd_voc_match);
+    counters int64 [2] = records so far, records lost to the capacity.  No allocation, no host synchronisation."""
+    _need_cuda(rows, probs, nkept, gt_box, gt_cls, gt_difficult, gt_count, image_size, keys, flags, counters)
+    if rows.dim() != 3 or probs.dim() != 3 or gt_box.dim() != 3:
+        raise L.McamdError("voc_match: rows [B, N, 8], probs [B, N, C] and gt_box [B, G, 4] expected")
+    B, N, C_ = probs.shape
+    G = gt_box.shape[1]
+    _voc_tensor(rows, torch.float32, (B, N, 8), "rows")
+    _voc_tensor(probs, torch.float32, (B, N, C_), "probs")
+    _voc_tensor(nkept, torch.int32, (B,), "nkept")
+    _voc_tensor(gt_box, torch.int32, (B, G, 4), "gt_box")
+    _voc_tensor(gt_cls, torch.uint8, (B, G), "gt_cls")
+    _voc_tensor(gt_difficult, torch.uint8, (B, G), "gt_difficult")
+    _voc_tensor(gt_count, torch.int32, (B,), "gt_count")
+    _voc_tensor(image_size, torch.int32, (B, 2), "image_size")
+    _voc_tensor(keys, torch.int64, (keys.numel(),), "keys")
+    _voc_tensor(flags, torch.uint8, (keys.numel(),), "flags")
+    _voc_tensor(counters, torch.int64, (2,), "counters")
+    d = L.VocMatchDesc()
+    d.rows, d.probs, d.nkept = rows.data_ptr(), probs.data_ptr(), nkept.data_ptr()
+    d.B, d.N, d.C, d.G = B, N, C_, G
+    d.conf_thresh, d.ovthresh, d.first_image = float(conf_thresh), float(ovthresh), int(first_image)
+    d.gt_box, d.gt_cls, d.gt_difficult = gt_box.data_ptr(), gt_cls.data_ptr(), gt_difficult.data_ptr()
+    d.gt_count, d.image_size = gt_count.data_ptr(), image_size.data_ptr()
+    d.keys, d.flags, d.capacity, d.counters = keys.data_ptr(), flags.data_ptr(), keys.numel(), counters.data_ptr()
+    check(L.lib().mcamd_voc_match(C.byref(d), stream_ptr()), "mcamd_voc_match")
+
+
+def voc_ap(keys, flags, counters, npos, want_curves=False):
+    """Per-class VOC07 AP (float64 [C]) of the records SORTED by key (mcamd_voc_ap); want_curves adds rec and prec at the
+    records' sorted positions (float64, the capacity long)."""
+    _need_cuda(keys, flags, counters, npos)
+    _voc_tensor(keys, torch.int64, (keys.numel(),), "keys")
+    _voc_tensor(flags, torch.uint8, (keys.numel(),), "flags")
+    _voc_tensor(counters, torch.int64, (2,), "counters")
+    _voc_tensor(npos, torch.int32, (npos.numel(),), "npos")
+    ap = torch.empty(npos.numel(), dtype=torch.float64, device=keys.device)
+    rec = torch.zeros(keys.numel(), dtype=torch.float64, device=keys.device) if want_curves else None
+    prec = torch.zeros(keys.numel(), dtype=torch.float64, device=keys.device) if want_curves else None
+    check(L.lib().mcamd_voc_ap(ptr(keys), ptr(flags), ptr(counters), keys.numel(), ptr(npos), npos.numel(), ptr(ap), ptr(rec),
+                               ptr(prec), stream_ptr()), "mcamd_voc_ap")
+    return (ap, rec, prec) if want_curves else ap
+
+
 # ------------------------------------------------------------------ launch plans
 class Plan:
     """A recorded sequence of library calls (include/mcamd.h, "Launch plans"), replayed with one call per segment."""

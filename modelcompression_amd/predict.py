@@ -15,8 +15,10 @@ import torch
 
 from .data import VOCList, SyntheticDetection
 from .nets import getYOLOv2
-from .nets2_utils import get_region_boxes, nms, detections, detections_fused, get_image_size  # noqa: F401
+from ._lib import McamdError
+from .nets2_utils import get_region_boxes, nms, detections, detections_device, detections_fused, get_image_size  # noqa: F401
 from .ops import DETECT_MAX_ROWS
+from .voc_eval import VOCGroundTruth, DeviceVOCEval
 
 
 class PASCALVOCEval():
@@ -44,11 +46,17 @@ class PASCALVOCEval():
                             "train", "tvmonitor")
         self.VOC_YEAR = '2007'
         self.mAP = None
+        self.aps = None
 
-    def predict(self, BATCH_SIZE=2, CONF_THRESH=0.005, NMS_THRESH=0.45):
+    def predict(self, BATCH_SIZE=2, CONF_THRESH=0.005, NMS_THRESH=0.45, DEVICE_EVAL=False):
+        """DEVICE_EVAL=True: detections, their matching to the ground truth and the per-class AP stay on the device
+        (mcamd_detect, mcamd_voc_match, mcamd_voc_ap); no detection files are written and self.aps / self.mAP
+        are the float64 values the file path computes from the same detections."""
         if self.MODEL == '' or self.MODEL is None:
             self.MODEL = getYOLOv2(self.MODEL_CFGFILE, self.MODEL_WEIGHTFILE)
         self.MODEL.eval()
+        if DEVICE_EVAL:
+            return self._predict_device(BATCH_SIZE, CONF_THRESH, NMS_THRESH)
         dev = next(self.MODEL.parameters()).device
         have_list = bool(self.EVAL_IMAGELIST) and os.path.exists(self.EVAL_IMAGELIST)
         if have_list:
@@ -92,6 +100,59 @@ class PASCALVOCEval():
         self.num_detections = ndet
         if have_list and os.path.isdir(os.path.join(self.PASCAL_DIR or '', 'VOC' + self.VOC_YEAR, 'Annotations')):
             self._do_python_eval()
+        return self.mAP
+
+    # records the device evaluation holds (DeviceVOCEval: 9 bytes each, and the sort's workspace).  More make predict
+    # raise McamdError naming this capacity; a set that emits more at the reference's CONF_THRESH 0.005 raises it here.
+    DEVICE_EVAL_CAPACITY = 1 << 22
+
+    def _predict_device(self, BATCH_SIZE, CONF_THRESH, NMS_THRESH):
+        if not (bool(self.EVAL_IMAGELIST) and os.path.exists(self.EVAL_IMAGELIST)):
+            raise McamdError("predict(DEVICE_EVAL=True) needs an image list, got `%s`" % self.EVAL_IMAGELIST)
+        base = os.path.join(self.PASCAL_DIR or '', 'VOC' + self.VOC_YEAR)
+        if not os.path.isdir(os.path.join(base, 'Annotations')):
+            raise McamdError("predict(DEVICE_EVAL=True) needs the annotations, %s is missing" % os.path.join(base, 'Annotations'))
+        dev = next(self.MODEL.parameters()).device
+        if dev.type != 'cuda':
+            raise McamdError("predict(DEVICE_EVAL=True) needs the model on the GPU, it is on `%s`" % dev)
+        with open(self.EVAL_IMAGELIST) as fp:
+            valid_files = [item.rstrip() for item in fp.readlines()]
+        classes = self.VOC_CLASSES[:self.MODEL.num_classes]
+        gt = VOCGroundTruth(self.parse_rec, os.path.join(base, 'Annotations', '{:s}.xml'),
+                            os.path.join(base, 'ImageSets', 'Main', 'test.txt'), valid_files, classes, dev,
+                            default_size=(self.MODEL.width, self.MODEL.height))
+        acc = DeviceVOCEval(gt, len(classes), capacity=self.DEVICE_EVAL_CAPACITY)
+        ds = VOCList(self.EVAL_IMAGELIST, shape=(self.MODEL.width, self.MODEL.height), train=False)
+        loader = torch.utils.data.DataLoader(ds, batch_size=BATCH_SIZE, shuffle=False, num_workers=1, pin_memory=True)
+        first, val_loss_total = 0, 0.0
+        with torch.no_grad():
+            for data, target in loader:
+                output = self.MODEL(data.to(dev))
+                if self.LOGGER != '' and self.MODEL_LOSS is not None and bool((target != 0).any()):
+                    val_loss_total += float(self.MODEL_LOSS(output, target.float().to(dev)))
+                if not output.is_cuda:
+                    raise McamdError("predict(DEVICE_EVAL=True): the logits are not on the GPU")
+                rows = output.size(2) * output.size(3) * self.MODEL.num_anchors
+                if rows > DETECT_MAX_ROWS:
+                    raise McamdError("predict(DEVICE_EVAL=True): %d rows per image, at most %d" % (rows, DETECT_MAX_ROWS))
+                acc.add(*detections_device(output, CONF_THRESH, NMS_THRESH, self.MODEL.num_classes, self.MODEL.anchors,
+                                           self.MODEL.num_anchors), first, CONF_THRESH)
+                first += output.size(0)
+        if self.LOGGER != '' and self.MODEL_LOSS is not None:
+            self.LOGGER.save_value('Total Loss', 'Val Loss', self.LOGGER_EPOCH + 1, val_loss_total / max(len(loader), 1))
+        aps, mAP = acc.finish()
+        self.num_detections = acc.num_records
+        return self._report(classes, aps)
+
+    def _report(self, classes, aps):
+        """The lines and the LOGGER value of _do_python_eval."""
+        for cls, ap in zip(classes, aps):
+            print('AP for {} = {:.4f}'.format(cls, ap))
+        self.aps = np.asarray(aps, dtype=np.float64)
+        self.mAP = float(np.mean(aps))
+        print('Mean AP = {:.4f}'.format(self.mAP))
+        if self.LOGGER != '':
+            self.LOGGER.save_value('mAP', 'Val mAP', self.LOGGER_EPOCH + 1, self.mAP)
         return self.mAP
 
     def parse_rec(self, filename):
@@ -187,6 +248,7 @@ class PASCALVOCEval():
             rec, prec, ap = self.voc_eval(detpath, annopath, imagesetfile, cls, self.EVAL_OUTPUTDIR_PKL, 0.5, True)
             aps.append(ap)
             print('AP for {} = {:.4f}'.format(cls, ap))
+        self.aps = np.asarray(aps, dtype=np.float64)
         self.mAP = float(np.mean(aps))
         print('Mean AP = {:.4f}'.format(self.mAP))
         if self.LOGGER != '':
