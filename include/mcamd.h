@@ -235,6 +235,34 @@ int mcamd_pack_sparse24(const mcamd_conv_geom* g, const float* w_oihw, const flo
 int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, const void* wsp, const void* idx,
                             const mcamd_conv_epilogue* epi, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Split-K forward for low-batch fp16 inference (an addition beyond the reference; conv_splitk.hip, Darknet.splitk).
+ * A layer of few output pixels gives mcamd_conv_fwd a handful of workgroups that each walk the whole K axis; here
+ * workgroup (tile, slice s) of a first launch multiplies the K chunks [floor(s n / S), floor((s + 1) n / S)) of the
+ * tile's n = ktot / bk chunks and stores its unrounded fp32 accumulators to slab s of `workspace`; a second launch on
+ * the same stream sums the S slabs of every element in slice order in fp32 and applies mcamd_conv_fwd's epilogue.  The
+ * result is a function of the operands and S only (no atomics, no workgroup waits for another); with S = 1 it is
+ * mcamd_conv_fwd's igemm result bit for bit.
+ *
+ * Geometries: stem == 0, pad == 0, x_wrap == 0, x_f8 == 0, ksize 1 or 3.  Epilogues: MCAMD_EPI_PAD_F16 (dst_mode
+ * PLAIN / POOL (+ y2) / REORG) and MCAMD_EPI_RAW_F16 with stats == NULL.  Same packed weights as mcamd_conv_fwd.
+ * ------------------------------------------------------------------------- */
+typedef struct mcamd_splitk_info {
+    int32_t slices;          /* 1 = the policy does not split this launch */
+    int32_t bm, bn, bk;      /* workgroup tile of the partial kernel */
+    int32_t chunks;          /* ktot / bk */
+    int32_t tiles;           /* M tiles x N tiles */
+    int64_t workspace_bytes; /* what mcamd_conv_fwd_splitk needs for `slices` */
+} mcamd_splitk_info;
+/* Host logic only.  slices = 0 asks the policy (the largest S <= MCAMD_SPLITK_CUS / tiles that leaves every slice at
+ * least MCAMD_SPLITK_MIN_CHUNKS chunks, clamped to [1, 16]); slices > 0 sizes a forced count in [1, chunks]. */
+int mcamd_conv_fwd_splitk_info(const mcamd_conv_geom* g, int32_t mode, int32_t dst_mode, int32_t slices,
+                               mcamd_splitk_info* out);
+/* The two launches.  slices as above; workspace: at least the workspace_bytes the query returns for the same
+ * arguments, 16-byte aligned, free again once the call's launches have run. */
+int mcamd_conv_fwd_splitk(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const mcamd_conv_epilogue* epi,
+                          int32_t slices, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------
  * fp8 (OCP e4m3) quantised inference (an addition beyond the reference; conv_q8.hip, Darknet.precision = "fp8").
  *   q(v) = round-to-nearest-even to e4m3 of v clamped to [-448, 448].

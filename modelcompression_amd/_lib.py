@@ -78,6 +78,12 @@ class DgradSums(C.Structure):
                 ("ch_lo", C.c_int32), ("C", C.c_int32)]
 
 
+class SplitkInfo(C.Structure):
+    """mcamd_splitk_info (include/mcamd.h)."""
+    _fields_ = [("slices", C.c_int32), ("bm", C.c_int32), ("bn", C.c_int32), ("bk", C.c_int32),
+                ("chunks", C.c_int32), ("tiles", C.c_int32), ("workspace_bytes", C.c_int64)]
+
+
 class FoldDesc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("mask", C.c_void_p), ("rows", C.c_void_p), ("cols", C.c_void_p),
                 ("beta", C.c_void_p), ("slope", C.c_float),
@@ -172,6 +178,8 @@ SIGNATURES = {
     "mcamd_sparse24_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
     "mcamd_pack_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
     "mcamd_conv_fwd_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
+    "mcamd_conv_fwd_splitk_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, _I32, C.POINTER(SplitkInfo)]),
+    "mcamd_conv_fwd_splitk": (C.c_int, [C.POINTER(ConvGeom), _P, _P, C.POINTER(ConvEpilogue), _I32, _P, _SZ, _P]),
     "mcamd_conv_fwd_q8_ok": (_I32, [C.POINTER(ConvGeom)]),
     "mcamd_q8_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
     "mcamd_pack_q8": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),

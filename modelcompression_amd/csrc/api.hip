@@ -627,6 +627,66 @@ extern "C" int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, 
 }
 
 // ---------------------------------------------------------------------------------------
+// split-K forward for low-batch inference (conv_splitk.hip; an addition beyond the reference)
+// ---------------------------------------------------------------------------------------
+// what both entries refuse, then the plan for `slices` (0 = the policy)
+static int splitk_plan_for(const mcamd_conv_geom* g, int mode, int dst_mode, int slices, const char* what, SplitkPlan* p) {
+    MCAMD_REQUIRE(g, "%s: null geometry", what);
+    MCAMD_REQUIRE(g->stem == 0, "%s: stem %d: the first layer has no split-K form", what, g->stem);
+    MCAMD_REQUIRE(g->pad == 0, "%s: pad %d: the shared-halo form is not accepted (pad must be 0)", what, g->pad);
+    MCAMD_REQUIRE(g->x_wrap == 0, "%s: x_wrap %d: split operands have no split-K form", what, g->x_wrap);
+    MCAMD_REQUIRE(g->x_f8 == 0, "%s: x_f8 %d: the fp8 correction form has no split-K form", what, g->x_f8);
+    if (check_geom(g, what)) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mode == MCAMD_EPI_PAD_F16 || mode == MCAMD_EPI_RAW_F16,
+                  "%s: epilogue mode %d: modes 2 (MCAMD_EPI_PAD_F16) and 0 (MCAMD_EPI_RAW_F16) only", what, mode);
+    MCAMD_REQUIRE(dst_mode == MCAMD_DST_PLAIN || (mode == MCAMD_EPI_PAD_F16 && (dst_mode == MCAMD_DST_POOL || dst_mode == MCAMD_DST_REORG)),
+                  "%s: bad dst_mode %d for epilogue mode %d", what, dst_mode, mode);
+    MCAMD_REQUIRE(slices >= 0, "%s: slices %d is negative", what, slices);
+    const int ct = cin_tap_of(g);
+    *p = mcamd_splitk_plan((long long)g->B * g->H * g->W, g->cout, ct, ntaps_of(g) * ct, slices);
+    MCAMD_REQUIRE(p->slices >= 1 && p->slices <= p->chunks, "%s: slices %d outside [1, chunks = %d]", what, p->slices, p->chunks);
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_conv_fwd_splitk_info(const mcamd_conv_geom* g, int32_t mode, int32_t dst_mode, int32_t slices,
+                                          mcamd_splitk_info* out) {
+    MCAMD_REQUIRE(out, "conv_fwd_splitk_info: null output");
+    SplitkPlan p;
+    if (splitk_plan_for(g, mode, dst_mode, slices, "conv_fwd_splitk_info", &p)) return MCAMD_EINVAL;
+    out->slices = p.slices;
+    out->bm = p.bm, out->bn = p.bn, out->bk = p.bk;
+    out->chunks = p.chunks;
+    out->tiles = p.tiles;
+    out->workspace_bytes = (int64_t)p.slices * p.slab_elems * (int64_t)sizeof(float);
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_conv_fwd_splitk(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const mcamd_conv_epilogue* epi,
+                                     int32_t slices, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_splitk: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_splitk(&g_, x, wp_fwd, &e_, slices, workspace, workspace_bytes, s); });
+    }
+    MCAMD_REQUIRE(g, "conv_fwd_splitk: null geometry");
+    MCAMD_REQUIRE(epi, "conv_fwd_splitk: null epilogue");
+    SplitkPlan p;
+    if (splitk_plan_for(g, epi->mode, epi->dst_mode, slices, "conv_fwd_splitk", &p)) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(epi->stats == nullptr, "conv_fwd_splitk: stats must be NULL (no statistics slab in the split-K form)");
+    MCAMD_REQUIRE(x && wp_fwd, "conv_fwd_splitk: null input");
+    const size_t need = (size_t)p.slices * (size_t)p.slab_elems * sizeof(float);
+    MCAMD_REQUIRE(workspace, "conv_fwd_splitk: null workspace (%zu bytes needed)", need);
+    MCAMD_REQUIRE(workspace_bytes >= need, "conv_fwd_splitk: workspace_bytes %zu is short of the %zu bytes %d slices need",
+                  workspace_bytes, need, p.slices);
+    MCAMD_REQUIRE(((uintptr_t)workspace & 15) == 0, "conv_fwd_splitk: workspace must be 16-byte aligned");
+    IgemmArgs a;
+    fill_operand(a, g, x, wp_fwd, g->x_ld, g->x_choff, g->cout, cin_tap_of(g), 0);
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_splitk", 0)) return MCAMD_EINVAL;
+    return mcamd_splitk_launch(a, p, (float*)workspace, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------
 // fp8 (e4m3) quantised inference (conv_q8.hip; an addition beyond the reference)
 // ---------------------------------------------------------------------------------------
 extern "C" int32_t mcamd_conv_fwd_q8_ok(const mcamd_conv_geom* g) {

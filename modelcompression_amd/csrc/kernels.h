@@ -117,6 +117,14 @@ ConvRoute mcamd_igemm_route(long long M, int n, int cin_tap, int ktot, bool raw_
 int mcamd_igemm_pp_launch(const IgemmArgs& a, int bm, int bn, int rows, int ntiles, hipStream_t st);
 int mcamd_igemm_launch(IgemmArgs& a, const ConvRoute& r, hipStream_t st);
 bool mcamd_igemm_sums_ok(const ConvRoute& r);   // the route's kernel has a MCAMD_EPI_RAW_F16_SUMS instance (IgemmArgs.bsum)
+// conv_splitk.hip: split-K forward (partial + finish launch).  mcamd_splitk_plan is the tile and the slice policy
+// (forced > 0: that slice count instead of the policy's); slab_elems = floats per slice of the workspace
+struct SplitkPlan {
+    int bm, bn, bk, chunks, mtiles, ntiles, tiles, slices;
+    long long slab_elems;
+};
+SplitkPlan mcamd_splitk_plan(long long M, int n, int cin_tap, int ktot, int forced);
+int mcamd_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, float* ws, hipStream_t st);
 int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);   // conv_sparse.hip: 2:4 weights, mode 2 epilogue
 int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
                                int cin_tap, int kb, hipStream_t st);

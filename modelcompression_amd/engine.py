@@ -189,6 +189,10 @@ class Engine:
         # mcamd_conv_fwd_sparse24, chosen when the masks change (_update_sparse); empty = every block dense
         self.sparse_layers = []
         self._sparse_mode, self._sparse_keys = None, None
+        # split-K low-batch inference (Darknet.splitk, plain-fp16 eval engines only): conv numbers of the blocks that run
+        # mcamd_conv_fwd_splitk, chosen when the flag or the masks change (_update_splitk); one workspace for all of them
+        self.splitk_layers = []
+        self._splitk_on, self._splitk_keys, self._splitk_ws = False, None, None
         self.fold_dead = os.environ.get("MCAMD_FOLD_DEAD", "1") == "1"
         # "mixed": the two correction products of the split-operand forward from e4m3 copies on the block-scaled fp8 MFMAs
         # (csrc/conv_igemm_pp.hip, F8).  "fp16x3" keeps all three products on fp16 operands: it is the tests' tight reference.
@@ -695,6 +699,10 @@ class Engine:
         if skeys != self._sparse_keys:
             self._update_sparse()
             self._sparse_keys = skeys
+        kkeys = (mkeys, self._sparse_mode, self._splitk_on)      # (behind _update_sparse: sparse blocks are never split)
+        if kkeys != self._splitk_keys:
+            self._update_splitk()
+            self._splitk_keys = kkeys
         for lay in self.layers:
             mask = lay.conv.mask.contiguous() if lay.conv.mask_flag else None
             if lay.sp_on:
@@ -791,6 +799,37 @@ class Engine:
                 lay.widx = torch.zeros(ni, dtype=torch.int16, device=self.device)
             lay.sp_on = True
             self.sparse_layers.append(lay.li + 1)      # conv number (conv1 = the first block)
+
+    # ------------------------------------------------------------------ split-K low-batch inference
+    def _splitk_form(self, lay):
+        """(epilogue mode, dst_mode) of the eval-mode launch of a block the split-K pair can stand in for, or None: the fused
+        inference launch (ops.conv_fwd_padded) or the raw one without statistics (ops.conv_fwd_raw: blocks with a border
+        table, a permutation or folding -- how slim_export models run in fp16)."""
+        if (lay.li == 0 or lay.stem or lay.is_last or lay.sp_on or self.precise or self.q8
+                or lay.fused_stem or lay.fused_stem_eval or getattr(lay, "stem_split", False)):
+            return None
+        return (L.EPI_PAD_F16, lay.mode) if self._fused_eval(lay) else (L.EPI_RAW_F16, L.DST_PLAIN)
+
+    def _update_splitk(self):
+        """Which blocks run the split-K forward (called when Darknet.splitk, Darknet.sparse or the masks change, and when
+        the engine is built): a block does when the library's policy gives its eval-mode launch two slices or more
+        (mcamd_conv_fwd_splitk_info); blocks on the 2:4 kernel, the first and the last block never do."""
+        self._plan_epoch += 1             # recorded forward plans name the unsplit or the split launch of a block
+        self.splitk_layers = []
+        need = 0
+        for lay in self.layers:
+            lay.sk_on, lay.sk_slices = False, 1
+            form = self._splitk_form(lay) if self._splitk_on else None
+            if form is None or lay.geom_act.pad:
+                continue
+            info = ops.conv_fwd_splitk_info(lay.geom_act, form[0], form[1])
+            if info.slices >= 2:
+                lay.sk_on, lay.sk_slices = True, info.slices
+                need = max(need, info.workspace_bytes)
+                self.splitk_layers.append(lay.li + 1)      # conv number (conv1 = the first block)
+        # one workspace of the largest requirement: the layers run one after another on the launch stream
+        if need and (self._splitk_ws is None or self._splitk_ws.numel() * 4 < need):
+            self._splitk_ws = torch.empty(need // 4, dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------ fp8 quantised inference
     def _update_q8(self):
@@ -1289,8 +1328,12 @@ class Engine:
             raise McamdError("sparse=%r runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r%s"
                              % (mode, self.precision, "; 2:4 masks on the fp8 engine: model.precision = 'fp8-2:4' with "
                                 "model.sparse = None" if self.q8 else ""))
-        force = bool(training) or mode != self._sparse_mode
-        self._sparse_mode = mode
+        splitk = bool(getattr(self.model, "splitk", False)) and not training
+        if splitk and (self.precise or self.q8):
+            raise McamdError("splitk=True runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r"
+                             % (self.precision,))
+        force = bool(training) or mode != self._sparse_mode or splitk != self._splitk_on
+        self._sparse_mode, self._splitk_on = mode, splitk
         self.pack(force=force, training=training)
         self.serial += 1
         tin = self.layers[0].tin
@@ -1432,13 +1475,21 @@ class Engine:
                     self._timed('fwd', lay, ops.conv_fwd_sparse24, lay.geom_act, xin, lay.wsp, lay.widx, self.bufs[t.buf], t.ld,
                                 t.choff, lay.scale, lay.shift, lay.slope, **dst)
                     continue
+                if lay.sk_on:       # few pixels: K cut into slices over the whole chip (Darknet.splitk, _update_splitk)
+                    self._timed('fwd', lay, ops.conv_fwd_splitk, lay.geom_act, xin, lay.wp, self.bufs[t.buf], t.ld, t.choff,
+                                lay.scale, lay.shift, lay.slope, slices=lay.sk_slices, workspace=self._splitk_ws, **dst)
+                    continue
                 self._timed('fwd', lay, ops.conv_fwd_padded, lay.geom_act, xin, lay.wp, self.bufs[t.buf], t.ld, t.choff,
                             lay.scale, lay.shift, lay.slope, **dst)
                 continue
             if training and self._qat_train(lay):
                 self._qat_forward(lay, xin)
                 continue
-            self._timed('fwd', lay, ops.conv_fwd_raw, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0, lay.stats if training else None)
+            if lay.sk_on and not training:
+                self._timed('fwd', lay, ops.conv_fwd_raw_splitk, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0,
+                            slices=lay.sk_slices, workspace=self._splitk_ws)
+            else:
+                self._timed('fwd', lay, ops.conv_fwd_raw, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0, lay.stats if training else None)
             ops.bn_coeffs(lay.stats if training else None, lay.cout, lay.M, bn.weight.data, bn.bias.data,
                           bn.running_mean, bn.running_var, training, lay.scale, lay.shift, lay.mean, lay.invstd,
                           momentum=bn.momentum if bn.momentum is not None else 0.1, eps=bn.eps, perm=lay.perm32,

@@ -289,6 +289,11 @@ class Darknet(nn.Module):
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA
         # (engine.Engine.sparse_layers).  Eval with precision "fp16" only -- other eval precisions raise; training ignores it.
         self.sparse = None
+        # Low-batch inference (an addition beyond the reference): True runs every block whose forward launch would leave most
+        # CUs idle -- the 13x13 and 26x26 layers at B = 1 -- as a split-K pair (csrc/conv_splitk.hip, DESIGN.md 3p,
+        # engine.Engine.splitk_layers); batches the policy does not split run exactly what they run without it.  Eval with
+        # precision "fp16" only -- other eval precisions raise; training ignores it.  MCAMD_SPLITK=1 sets the default.
+        self.splitk = os.environ.get("MCAMD_SPLITK", "0") == "1"
 
     # ---- engine plumbing
     def _apply(self, fn, *args, **kwargs):

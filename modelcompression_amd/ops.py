@@ -10,7 +10,7 @@ import weakref
 import torch
 
 from . import _lib as L
-from ._lib import (ConvGeom, ConvEpilogue, ActDesc, ActBwdDesc, DgradSums, ChanMap, PackJob, StemBlockDesc, FoldDesc, FoldJob, check, ptr,
+from ._lib import (ConvGeom, ConvEpilogue, SplitkInfo, ActDesc, ActBwdDesc, DgradSums, ChanMap, PackJob, StemBlockDesc, FoldDesc, FoldJob, check, ptr,
                    stream_ptr)
 
 HALF = torch.float16
@@ -893,6 +893,39 @@ def conv_fwd_sparse24(g, x, wsp, idx, y, y_ld, y_choff=0, scale=None, shift=None
              y2_choff=y2_choff)
     check(L.lib().mcamd_conv_fwd_sparse24(C.byref(g), ptr(x), ptr(wsp), ptr(idx), C.byref(e), stream_ptr()),
           "mcamd_conv_fwd_sparse24")
+
+
+# ----------------------------------------------------------------------------- split-K forward (low-batch inference)
+def conv_fwd_splitk_info(g, mode, dst_mode=0, slices=0):
+    """mcamd_splitk_info of a split-K forward of `g` with epilogue `mode` (L.EPI_PAD_F16 / L.EPI_RAW_F16): host logic only.
+    slices = 0 asks the policy (info.slices == 1: it does not split this launch); > 0 sizes a forced slice count."""
+    info = SplitkInfo()
+    check(L.lib().mcamd_conv_fwd_splitk_info(C.byref(g), mode, dst_mode, slices, C.byref(info)), "mcamd_conv_fwd_splitk_info")
+    return info
+
+
+def _splitk(g, x, wp, e, slices, workspace):
+    if workspace is None:
+        info = conv_fwd_splitk_info(g, e.mode, e.dst_mode, slices)
+        workspace = torch.empty(info.workspace_bytes // 4, dtype=torch.float32, device=x.device)
+    _need_cuda(x, workspace)
+    check(L.lib().mcamd_conv_fwd_splitk(C.byref(g), ptr(x), ptr(wp), C.byref(e), slices, ptr(workspace),
+                                        workspace.numel() * workspace.element_size(), stream_ptr()), "mcamd_conv_fwd_splitk")
+    return workspace
+
+
+def conv_fwd_splitk(g, x, wp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0, y2_choff=0,
+                    slices=0, workspace=None):
+    """conv_fwd_padded with the K axis cut into `slices` slices (0 = the policy's count): a partial launch into `workspace`
+    (fp32, conv_fwd_splitk_info(...).workspace_bytes; None allocates one) and a finish launch with the same epilogue."""
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff)
+    return _splitk(g, x, wp, e, slices, workspace)
+
+
+def conv_fwd_raw_splitk(g, x, wp, y, y_ld, y_choff=0, slices=0, workspace=None):
+    """conv_fwd_raw(..., stats=None) with the K axis cut into `slices` slices: y[M][y_ld] fp16 raw conv output."""
+    return _splitk(g, x, wp, _epi(L.EPI_RAW_F16, y, y_ld, y_choff), slices, workspace)
 
 
 # ----------------------------------------------------------------------------- fp8 (e4m3) quantised inference
