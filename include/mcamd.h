@@ -155,6 +155,11 @@ int32_t mcamd_conv_stats_rows_mode(const mcamd_conv_geom* g, int32_t mode);
  * M tile of 128 padded pixels), 7 = small3x3_split_kernel (the 32 -> <= 64 channel 3x3 layer on split operands at
  * x_choff 0, fp32 output; BN = round_up(cout, 32), BK = the 96 K-concatenated channels). */
 int mcamd_conv_tile_info(const mcamd_conv_geom* g, int32_t dgrad, int32_t out[4]);
+/* The same route function's whole answer {BM, BN, BK, kernel, rows} for any launch: dir 0 = mcamd_conv_fwd, 1 = mcamd_conv_dgrad,
+ * 2 = mcamd_conv_dgrad with epilogue.concurrent set; `mode` / `dst_mode` = the epilogue's; stats != 0: the epilogue has a
+ * statistics slab.  rows = the persistent workgroups along M (the rows of that slab; 0 for win3x3_kernel).  Host logic
+ * only: no device is touched.  It answers for the combination given, whether or not the launch entry accepts it. */
+int mcamd_conv_route_info(const mcamd_conv_geom* g, int32_t dir, int32_t mode, int32_t dst_mode, int32_t stats, int32_t out[5]);
 
 /* Packed-weight sizes (elements of fp16) for a geometry. */
 int64_t mcamd_packed_elems_fwd(const mcamd_conv_geom* g);

@@ -169,6 +169,7 @@ SIGNATURES = {
     "mcamd_conv_stats_rows_mode": (_I32, [C.POINTER(ConvGeom), _I32]),
     "mcamd_conv_fwd_f8_ok": (_I32, [C.POINTER(ConvGeom)]),
     "mcamd_conv_tile_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I32)]),
+    "mcamd_conv_route_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mcamd_packed_elems_fwd": (_I64, [C.POINTER(ConvGeom)]),
     "mcamd_packed_elems_dgrad": (_I64, [C.POINTER(ConvGeom)]),
     "mcamd_pack_weights": (C.c_int, [C.POINTER(ConvGeom), _P, _P, C.POINTER(ChanMap), _P, _P, _P]),

@@ -546,6 +546,20 @@ extern "C" int mcamd_conv_tile_info(const mcamd_conv_geom* g, int32_t dgrad, int
     return MCAMD_OK;
 }
 
+// conv_route()'s answer for any (direction, epilogue mode, destination form, statistics) a launch can have
+extern "C" int mcamd_conv_route_info(const mcamd_conv_geom* g, int32_t dir, int32_t mode, int32_t dst_mode, int32_t stats,
+                                     int32_t out[5]) {
+    if (check_geom(g, "conv_route_info")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(out, "conv_route_info: null output");
+    MCAMD_REQUIRE(dir == DIR_FWD || dir == DIR_DGRAD || dir == DIR_DGRAD_CONCURRENT, "conv_route_info: bad direction %d", dir);
+    MCAMD_REQUIRE(mode >= MCAMD_EPI_RAW_F16 && mode <= MCAMD_EPI_RAW_F32, "conv_route_info: bad epilogue mode %d", mode);
+    MCAMD_REQUIRE(dst_mode == MCAMD_DST_PLAIN || dst_mode == MCAMD_DST_POOL || dst_mode == MCAMD_DST_REORG,
+                  "conv_route_info: bad dst_mode %d", dst_mode);
+    const ConvRoute r = conv_route(g, dir, mode, dst_mode, stats != 0);
+    out[0] = r.bm, out[1] = r.bn, out[2] = r.bk, out[3] = r.kernel, out[4] = r.rows;
+    return MCAMD_OK;
+}
+
 extern "C" int mcamd_conv_fwd(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const mcamd_conv_epilogue* epi,
                               void* stream) {
     if (mcamd_recording()) {

@@ -157,6 +157,19 @@ def tile_info(g, dgrad=False, concurrent=False):
     return tuple(out)
 
 
+ConvRouteInfo = collections.namedtuple("ConvRouteInfo", "bm bn bk kernel rows")
+DIR_FWD, DIR_DGRAD, DIR_DGRAD_CONCURRENT = 0, 1, 2      # `dir` of conv_route_info
+ROUTE_IGEMM, ROUTE_STEM, ROUTE_PP, ROUTE_SMALL3X3, ROUTE_WIN3X3, ROUTE_WRES, ROUTE_SMALL3X3_SPLIT = 0, 1, 2, 4, 5, 6, 7
+
+
+def conv_route_info(g, dir=DIR_FWD, mode=L.EPI_RAW_F16, dst_mode=L.DST_PLAIN, stats=False):
+    """The kernel, tile and slab rows a forward / dgrad launch of `g` with this epilogue takes: mcamd_conv_route_info, the
+    launches' own route function.  Needs no GPU."""
+    out = (C.c_int32 * 5)()
+    check(L.lib().mcamd_conv_route_info(C.byref(g), dir, mode, dst_mode, 1 if stats else 0, out), "mcamd_conv_route_info")
+    return ConvRouteInfo(*out)
+
+
 def stats_rows(g, mode=L.EPI_RAW_F16):
     """Rows of the BN partial-sum slab a forward launch of `g` writes with epilogue `mode` (RAW_F16 or RAW_F32)."""
     return int(L.lib().mcamd_conv_stats_rows_mode(C.byref(g), mode))

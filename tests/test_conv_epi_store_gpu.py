@@ -24,7 +24,7 @@ B, H, W, CIN = 2, 6, 10, 64
 OFF, OFF2 = 8, 32                   # channel offsets of the slices in y and y2
 SENT16, SENT8 = 7.0, 0x5a           # fp16 7.0; a non-zero e4m3 code
 DSTS = ["plain", "pool", "pool+y2", "reorg"]
-ROUTE_PP = 2                        # mcamd_conv_tile_info: the ping-pong kernel
+ROUTE_PP = ops.ROUTE_PP              # mcamd_conv_route_info: the ping-pong kernel
 
 
 def whole(buf):
@@ -134,9 +134,6 @@ def test_store_pingpong_tile(dev):
     192 x 256 ping-pong tiles, the last one ragged in M)."""
     shape = (58, 26, 26, 128)
     g = operands(dev, "padded", *shape, 256, 3)[0]
-    # tile_info answers for the raw fp16 epilogue into a plain destination, this launch is the padded one with POOL:
-    # conv_route (csrc/api.hip) and pick_tile (csrc/conv_igemm.hip) tell the two apart only in the resident-weight branch
-    # (64 input channels, plain destinations) and the small-3x3 one (at most 64 filters); neither takes 128 -> 256
-    # channels, so the answer holds for this launch as well
-    assert ops.tile_info(g)[3] == ROUTE_PP
+    # (asked for this launch's own epilogue: the padded one with POOL)
+    assert ops.conv_route_info(g, ops.DIR_FWD, L.EPI_PAD_F16, L.DST_POOL).kernel == ROUTE_PP
     check(dev, "padded", shape, 256, 3, "pool+y2")

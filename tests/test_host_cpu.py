@@ -310,6 +310,101 @@ def test_wgrad_cases_reach_every_instance_and_boundary(setenv):
         assert sum(1 for c in cs if c.name == name) == 1
 
 
+def test_conv_routes_are_the_expected_set(setenv):
+    """What mcamd_conv_fwd and mcamd_conv_dgrad can launch, asked from their own route function (mcamd_conv_route_info) over
+    M from one ragged tile to the training batch at 208 x 208, column and K-side channel counts from 8 to 1344, both kernel
+    sizes and the stem, every direction / epilogue mode / destination form / statistics combination the entries accept and
+    every setting of the route switches (conv_cases.reachable): the set of (kernel, bm, bn, bk) per epilogue is exactly the
+    literal one below.  A changed rule that makes a new tile reachable, or a tile nobody can reach any more, fails here.
+    mcamd_conv_tile_info, which answers for the raw epilogues only, agrees with the new query on those."""
+    from modelcompression_amd import ops
+    import conv_cases as CC
+    L = _lib
+    reach = CC.reachable_cached(setenv)
+    igemm = {(0, 128, 32, 32), (0, 128, 32, 64), (0, 128, 64, 32), (0, 128, 64, 64), (0, 128, 128, 32), (0, 128, 128, 64), (0, 192, 128, 64)}
+    pp = {(2, 256, 256, 32), (2, 192, 256, 32), (2, 256, 128, 32), (2, 192, 128, 32)}
+    small = {(4, 32, 32, 32), (4, 32, 64, 32), (4, 32, 32, 64)}         # small3x3_kernel<32, 1 | 2>, <32, 4>, <64, 1 | 2>
+    win = {(5, 32, 16, 64), (5, 32, 32, 64)}                           # win3x3_kernel<1>, <2>
+    wres, stem = {(6, 128, 128, 64)}, {(1, 32, 32, 48), (1, 32, 64, 48)}
+    want = {"fwd-raw16-stats": igemm | pp | small | wres | stem, "fwd-raw16": igemm | pp | small | wres | stem | win,
+            "fwd-raw32-stats": igemm | pp, "fwd-raw32": igemm | pp, "fwd-nchw": igemm | pp,
+            "fwd-pad": igemm | pp | wres, "fwd-pad-pool": igemm | pp, "fwd-pad-reorg": igemm | pp,
+            "dgrad-raw16": igemm | pp | small | win, "dgrad-nchw": igemm | pp,
+            "dgradc-raw16": igemm | pp | small | win, "dgradc-nchw": igemm | pp}
+    assert set(reach) == set(want)
+    for e in want:
+        assert reach[e] == want[e], (e, reach[e] ^ want[e])
+    # the two queries agree where tile_info answers: forward with statistics (mode 0), dgrad and dgrad-concurrent (mode 0)
+    for env in CC.SWEEP_ENVS:
+        for name, default in CC.ENV_DEFAULTS.items():
+            setenv(name, env.get(name, default))
+        for (B, H, W) in CC.SWEEP_IMAGES:
+            for n in (8, 32, 64, 128, 256, 1024):
+                for kch in (32, 64, 96, 256):
+                    for k in (1, 3):
+                        g = ops.geom(B, H, W, k, kch, n, ops.round_up(kch, 32))
+                        assert ops.tile_info(g) == tuple(ops.conv_route_info(g, ops.DIR_FWD, L.EPI_RAW_F16, L.DST_PLAIN, True))[:4]
+                        g = ops.geom(B, H, W, k, n, kch, ops.round_up(n, 32))
+                        for conc in (False, True):
+                            d = ops.DIR_DGRAD_CONCURRENT if conc else ops.DIR_DGRAD
+                            assert ops.tile_info(g, True, conc) == tuple(ops.conv_route_info(g, d, L.EPI_RAW_F16, L.DST_PLAIN, False))[:4]
+            g = ops.geom(B, H, W, 3, 3, 32, 4, 0, stem=1)
+            assert ops.tile_info(g) == tuple(ops.conv_route_info(g, ops.DIR_FWD, L.EPI_RAW_F16, L.DST_PLAIN, True))[:4]
+            assert ops.stats_rows(g) == ops.conv_route_info(g, ops.DIR_FWD, L.EPI_RAW_F16, L.DST_PLAIN, True).rows
+    with pytest.raises(_lib.McamdError):
+        ops.conv_route_info(ops.geom(1, 8, 8, 3, 32, 32, 32), 3)
+
+
+def test_conv_cases_reach_every_instance_and_boundary(setenv):
+    """Coverage of tests/test_conv_instances_gpu.py, proved without a GPU: the cases reach every (kernel, tile) the route
+    rules can name under each of the six epilogues (and win3x3_kernel from a forward launch without statistics, the one
+    kernel the statistics argument decides), and every named boundary condition on an igemm_kernel tile and on a ping-pong
+    tile where it applies, each read from the library's own answer; every case still names the instance it was written
+    for; and every case's operands and reference meet the conditions of exactness (conv_cases.exactness), so that EQUAL
+    is the right comparison on the GPU."""
+    import conv_cases as CC
+    reach = CC.reachable_cached(setenv)
+    inst, tags_of = set(), {CC.IGEMM: set(), CC.PP: set()}
+    for c in CC.CONV_CASES:
+        CC.apply_env(c, setenv)
+        r = CC.route_of(c)
+        assert (r.kernel, r.bm, r.bn, r.bk) == c.expect, (c.name, r)
+        t = CC.boundary_tags(c, r)
+        assert set(c.tags) <= t, (c.name, r, t)
+        inst.add(CC.instance_of(c, r))
+        if r.kernel in tags_of:
+            tags_of[r.kernel] |= t
+        o = CC.operands(c)
+        assert CC.exactness(c, o, CC.reference(c, o)) == [], c.name
+        if c.overflow:
+            o = CC.operands(c, plant=False)
+            assert CC.exactness(c, o, CC.reference(c, o)) == [] and not o.planted
+    assert len({c.name for c in CC.CONV_CASES}) == len(CC.CONV_CASES)
+    for e in CC.CASE_EPILOGUES[:6]:
+        want = reach[e] | (reach["dgradc-" + e[6:]] if e.startswith("dgrad") else set())
+        got = {i[1] for i in inst if i[0] == e}
+        assert got == want, (e, got ^ want)
+    assert {i[1] for i in inst if i[0] == "fwd-raw16"} == reach["fwd-raw16"] - reach["fwd-raw16-stats"]
+    assert len(inst) == 80
+    assert tags_of[CC.IGEMM] >= set(CC.BOUNDARIES_BOTH + CC.BOUNDARIES_IGEMM), set(CC.BOUNDARIES_BOTH + CC.BOUNDARIES_IGEMM) - tags_of[CC.IGEMM]
+    assert tags_of[CC.PP] >= set(CC.BOUNDARIES_BOTH + CC.BOUNDARIES_PP), set(CC.BOUNDARIES_BOTH + CC.BOUNDARIES_PP) - tags_of[CC.PP]
+    cs = CC.CONV_CASES
+    # the destination forms of the padded epilogue: all four on one igemm_kernel tile and one ping-pong tile; wres_kernel
+    # takes plain destinations only (conv_route)
+    for tile in ((CC.IGEMM, 128, 64, 32), (CC.PP, 256, 256, 32)):
+        assert {c.dst for c in cs if c.expect == tile and c.epi == "fwd-pad"} == set(CC.DSTS)
+    assert {c.dst for c in cs if c.expect[0] == CC.WRES and c.epi == "fwd-pad"} == {"plain"}
+    # small3x3_kernel<CT, NB>: the route names CT and round_up(n, 32); every NB needs its own column count
+    for epi in ("fwd-raw16-stats", "dgrad-raw16"):
+        nb = {(c.expect[3], 1 if c.n <= 16 else 2 if c.n <= 32 else 4) for c in cs if c.expect[0] == CC.SMALL and c.epi == epi}
+        assert nb == {(32, 1), (32, 2), (32, 4), (64, 1), (64, 2)}, (epi, nb)
+    assert sum(1 for c in cs if c.overflow) == 1
+    assert sum(1 for c in cs if c.stem and c.expect[0] == CC.IGEMM) >= 1          # the first layer's form on igemm_kernel
+    for name in CC.DETERMINISM_CASES:
+        assert sum(1 for c in cs if c.name == name) == 1
+    assert {next(c for c in cs if c.name == n).expect[0] for n in CC.DETERMINISM_CASES} == {CC.IGEMM, CC.SMALL, CC.WIN, CC.WRES, CC.STEM}
+
+
 def test_region_loss_runs_and_has_reference_quirks():
     from modelcompression_amd.region_loss import RegionLoss
     loss = RegionLoss()
