@@ -875,6 +875,8 @@ int mcamd_voc_ap(const uint64_t* keys, const uint8_t* flags, const uint64_t* cou
  *   lut  : uint8 [3][256] per image (H, S, V) at lut + desc[b].lut_off
  *   tmp  : workspace (4-byte aligned), crop_h rows of W * 4 bytes (R, G, B, 0) per image at tmp + desc[b].tmp_off
  *   out  : fp32 [B][3][H][W]
+ * A descriptor with lut_off == -1 has no HSV step: out = u8 / 255.f of the resampled pixel (Image.resize +
+ * ToTensor()); lut may be NULL when no image has LUTs.  Every other negative lut_off is refused.
  * Returns MCAMD_EINVAL for an empty crop (crop_w or crop_h < 1: the reference makes an image of no pixels there) and
  * for any table / LUT / source / workspace extent outside its buffer; nothing is launched then.
  * ------------------------------------------------------------------------- */
@@ -887,7 +889,7 @@ typedef struct mcamd_augment_desc {
     int32_t flip;               /* left-right flip after the resize */
     int32_t hk, vk;             /* taps per row of the horizontal (W rows) and vertical (H rows) tables */
     int32_t hcoef_off, vcoef_off; /* int32 offsets of the two tables in coef */
-    int32_t lut_off;            /* byte offset of the [3][256] LUTs in lut */
+    int32_t lut_off;            /* byte offset of the [3][256] LUTs in lut; -1: no HSV distortion */
 } mcamd_augment_desc;
 typedef struct mcamd_augment_batch {
     const mcamd_augment_desc* desc;      /* HOST array of B descriptors: validated */
@@ -900,6 +902,21 @@ typedef struct mcamd_augment_batch {
     int32_t B, H, W;
 } mcamd_augment_batch;
 int mcamd_augment(const mcamd_augment_batch* a, void* stream);
+/* The tables and LUTs of a batch built on the device, for sources that already live there: for every image the
+ * horizontal table (crop_w -> W) at coef + hcoef_off, the vertical table (crop_h -> H) at coef + vcoef_off and, when
+ * lut_off >= 0, the LUTs of hsv_dev[b] = (dhue, dsat, dexp) at lut + lut_off.  The contract is augment.resample_table
+ * and augment.point_luts (modelcompression_amd/augment.py) bit for bit, in the row format above: float64 throughout,
+ * the same operations in the same order, the row sum in tap order, truncation toward zero, round-half-even for the
+ * LUTs, the hue wrap at 255, the identity table (k = 1) where the sizes are equal.  One launch, no host
+ * synchronisation; mcamd_augment on the same stream then reads what this wrote.
+ *   desc_host / desc_dev : the B descriptors of mcamd_augment_batch (host copy validated, device copy read)
+ *   hsv_dev              : float64 [B][3] in device memory; may be NULL when every lut_off is -1 (lut too)
+ * Returns MCAMD_EINVAL, before anything is launched, when a table or LUT extent lies outside its buffer, when hk or vk
+ * is not the tap count of its table (1 for equal sizes, else 2 * ceil(2 * max(float(n_in) / n_out, 1)) + 1), or when a
+ * crop is empty. */
+int mcamd_augment_tables(const mcamd_augment_desc* desc_host, const mcamd_augment_desc* desc_dev, const double* hsv_dev,
+                         int32_t B, int32_t H, int32_t W, int32_t* coef, int64_t coef_elems, uint8_t* lut,
+                         int64_t lut_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Launch plans: a whole forward or backward pass as ONE library call.

@@ -232,6 +232,7 @@ SIGNATURES = {
     "mcamd_voc_match": (C.c_int, [C.POINTER(VocMatchDesc), _P]),
     "mcamd_voc_ap": (C.c_int, [_P, _P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
     "mcamd_augment": (C.c_int, [C.POINTER(AugmentBatch), _P]),
+    "mcamd_augment_tables": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I64, _P, _I64, _P]),
     "mcamd_plan_begin": (C.c_int, [C.POINTER(_P), _I32]),
     "mcamd_plan_mark": (_I32, []),
     "mcamd_plan_end": (_P, []),

@@ -8,8 +8,12 @@
 //   augment_hpass_kernel  crop + horizontal resampling pass, uint8 RGBX rows into the workspace (Pillow rounds and
 //                         clips to uint8 between its two passes, so the intermediate is uint8 by definition);
 //   augment_vpass_kernel  vertical pass + flip + RGB->HSV -> LUTs -> HSV->RGB, one coalesced fp32 store per channel.
-// The resampling tables and LUTs come from the host (modelcompression_amd/augment.py); the kernels clamp every table
-// entry to the crop, so a corrupt table can give wrong pixels but never an out-of-bounds access.
+// The resampling tables and LUTs come from the host (modelcompression_amd/augment.py) or from
+//   augment_tables_kernel  augment.resample_table and augment.point_luts restated in float64, operation by operation,
+//                          one block per (image, axis) and one per image's LUTs (mcamd_augment_tables);
+// the pixel kernels clamp every table entry to the crop, so a corrupt table can give wrong pixels but never an
+// out-of-bounds access.  A descriptor with lut_off == -1 has no HSV step: the resampled pixel is stored as u8 / 255.f
+// (Image.resize + ToTensor(), the evaluation loader).
 #include "common.h"
 
 namespace {
@@ -112,8 +116,11 @@ __global__ __launch_bounds__(NTHR) void augment_vpass_kernel(const mcamd_augment
     __shared__ uint8_t L[768];
     const int b = blockIdx.y, y = blockIdx.x;
     const mcamd_augment_desc d = descs[b];
-    for (int i = threadIdx.x; i < 768; i += NTHR) L[i] = lut[d.lut_off + i];
-    __syncthreads();
+    const bool distort = d.lut_off >= 0;         // block-uniform: one block per (row, image)
+    if (distort) {
+        for (int i = threadIdx.x; i < 768; i += NTHR) L[i] = lut[d.lut_off + i];
+        __syncthreads();
+    }
     const int32_t* k = coef + d.vcoef_off + (long long)y * (d.vk + 2);
     const int first = min(max(k[0], 0), d.crop_h);
     const int cnt = min(max(k[1], 0), min(d.vk, d.crop_h - first));
@@ -129,9 +136,12 @@ __global__ __launch_bounds__(NTHR) void augment_vpass_kernel(const mcamd_augment
             const int c = k[2 + j];
             a0 += (int)(p & 255) * c, a1 += (int)((p >> 8) & 255) * c, a2 += (int)((p >> 16) & 255) * c;
         }
-        int h, s, v, r, g, bl;
-        rgb2hsv(clip8(a0), clip8(a1), clip8(a2), h, s, v);
-        hsv2rgb(L[h], L[256 + s], L[512 + v], r, g, bl);
+        int r = clip8(a0), g = clip8(a1), bl = clip8(a2);
+        if (distort) {
+            int h, s, v;
+            rgb2hsv(r, g, bl, h, s, v);
+            hsv2rgb(L[h], L[256 + s], L[512 + v], r, g, bl);
+        }
         o[x] = (float)r / 255.0f;
         o[plane + x] = (float)g / 255.0f;
         o[2 * plane + x] = (float)bl / 255.0f;
@@ -141,10 +151,78 @@ __global__ __launch_bounds__(NTHR) void augment_vpass_kernel(const mcamd_augment
 constexpr int MAX_DIM = 1 << 16;
 constexpr int MAX_TAPS = 4096;
 
+// Pillow's bicubic_filter (a = -0.5) as augment._bicubic writes it.
+__device__ __forceinline__ double bicubic(double x) {
+    x = fabs(x);
+    if (x < 1.0) return ((-0.5 + 2.0) * x - (-0.5 + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * -0.5;
+    return 0.0;
+}
+
+// augment.resample_table(n_in, n_out) into n_out rows of (first, count, k[0..ksize)), one thread per row.
+__device__ void resample_table(int n_in, int n_out, int ksize, int32_t* __restrict__ t) {
+    if (n_in == n_out) {                          // the pass Pillow skips: ksize is 1 (validated on the host)
+        for (int o = threadIdx.x; o < n_out; o += NTHR) {
+            int32_t* row = t + (long long)o * 3;
+            row[0] = o, row[1] = 1, row[2] = 1 << PREC;
+        }
+        return;
+    }
+    const double scale = (double)(float)n_in / n_out;
+    const double filterscale = fmax(scale, 1.0);
+    const double support = 2.0 * filterscale;
+    const double ss = 1.0 / filterscale;
+    for (int o = threadIdx.x; o < n_out; o += NTHR) {
+        const double center = 0.0 + (o + 0.5) * scale;
+        const long long xmin = (long long)fmax(trunc(center - support + 0.5), 0.0);
+        const long long xmax = min((long long)trunc(center + support + 0.5), (long long)n_in) - xmin;
+        double ww = 0.0;                           // the row sum, in tap order
+        for (int j = 0; j < ksize; ++j)
+            ww = ww + (j < xmax ? bicubic((((double)(j + xmin) - center) + 0.5) * ss) : 0.0);
+        int32_t* row = t + (long long)o * (ksize + 2);
+        row[0] = (int32_t)xmin, row[1] = (int32_t)xmax;
+        for (int j = 0; j < ksize; ++j) {
+            double w = j < xmax ? bicubic((((double)(j + xmin) - center) + 0.5) * ss) : 0.0;
+            if (ww != 0.0) w = w / ww;
+            row[2 + j] = (int32_t)(w < 0 ? trunc(-0.5 + w * (double)(1 << PREC)) : trunc(0.5 + w * (double)(1 << PREC)));
+        }
+    }
+}
+
+// blockIdx.x: 0 the horizontal table, 1 the vertical table, 2 augment.point_luts(dhue, dsat, dexp); blockIdx.y: image.
+__global__ __launch_bounds__(NTHR) void augment_tables_kernel(const mcamd_augment_desc* __restrict__ descs,
+                                                              const double* __restrict__ hsv, int32_t* __restrict__ coef,
+                                                              uint8_t* __restrict__ lut, int H, int W) {
+    const int b = blockIdx.y;
+    const mcamd_augment_desc d = descs[b];
+    if (blockIdx.x == 0) {
+        resample_table(d.crop_w, W, d.hk, coef + d.hcoef_off);
+    } else if (blockIdx.x == 1) {
+        resample_table(d.crop_h, H, d.vk, coef + d.vcoef_off);
+    } else if (d.lut_off >= 0) {
+        const double dhue = hsv[3 * b], dsat = hsv[3 * b + 1], dexp = hsv[3 * b + 2];
+        for (int n = threadIdx.x; n < 256; n += NTHR) {
+            const double i = (double)n;
+            double h = i + dhue * 255;
+            if (h > 255) h = h - 255;             // change_hue wraps at 255, not 256
+            if (h < 0) h = h + 255;
+            const double v[3] = {h, i * dsat, i * dexp};
+            for (int c = 0; c < 3; ++c)            // Python's round: half to even
+                lut[d.lut_off + 256 * c + n] = (uint8_t)fmin(fmax(rint(v[c]), 0.0), 255.0);
+        }
+    }
+}
+
+// ksize of augment.resample_table(n_in, n_out)
+int table_taps(int n_in, int n_out) {
+    if (n_in == n_out) return 1;
+    return (int)ceil(2.0 * fmax((double)(float)n_in / n_out, 1.0)) * 2 + 1;
+}
+
 }  // namespace
 
 extern "C" int mcamd_augment(const mcamd_augment_batch* a, void* stream) {
-    MCAMD_REQUIRE(a && a->desc && a->desc_dev && a->src && a->coef && a->lut && a->tmp && a->out, "augment: null argument");
+    MCAMD_REQUIRE(a && a->desc && a->desc_dev && a->src && a->coef && a->tmp && a->out, "augment: null argument");
     MCAMD_REQUIRE(!mcamd_recording(), "augment: not recordable into a launch plan");
     MCAMD_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0 && a->H <= MAX_DIM && a->W <= MAX_DIM && a->B <= 65535 &&
                       ((uintptr_t)a->tmp & 3) == 0,
@@ -171,7 +249,9 @@ extern "C" int mcamd_augment(const mcamd_augment_batch* a, void* stream) {
         MCAMD_REQUIRE(d.hcoef_off >= 0 && d.hcoef_off + (int64_t)a->W * (d.hk + 2) <= a->coef_elems &&
                           d.vcoef_off >= 0 && d.vcoef_off + (int64_t)a->H * (d.vk + 2) <= a->coef_elems,
                       "augment: image %d: resampling table outside coef (%lld entries)", b, (long long)a->coef_elems);
-        MCAMD_REQUIRE(d.lut_off >= 0 && d.lut_off + 768 <= a->lut_bytes, "augment: image %d: LUTs outside lut", b);
+        // lut_off == -1: no HSV distortion for this image (and no LUTs: lut may then be NULL)
+        MCAMD_REQUIRE(d.lut_off == -1 || (d.lut_off >= 0 && a->lut && d.lut_off + 768 <= a->lut_bytes),
+                      "augment: image %d: LUTs outside lut (lut_off %d)", b, d.lut_off);
         max_rows = max(max_rows, d.crop_h);
     }
     hipStream_t st = (hipStream_t)stream;
@@ -180,5 +260,34 @@ extern "C" int mcamd_augment(const mcamd_augment_batch* a, void* stream) {
     hipLaunchKernelGGL(augment_vpass_kernel, dim3(a->H, a->B), dim3(NTHR), 0, st, a->desc_dev, a->coef, a->lut,
                        (const uint32_t*)a->tmp, a->out, a->H, a->W);
     MCAMD_LAUNCH_CHECK("augment");
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_augment_tables(const mcamd_augment_desc* desc_host, const mcamd_augment_desc* desc_dev,
+                                    const double* hsv_dev, int32_t B, int32_t H, int32_t W, int32_t* coef,
+                                    int64_t coef_elems, uint8_t* lut, int64_t lut_bytes, void* stream) {
+    MCAMD_REQUIRE(desc_host && desc_dev && coef, "augment_tables: null argument");
+    MCAMD_REQUIRE(!mcamd_recording(), "augment_tables: not recordable into a launch plan");
+    MCAMD_REQUIRE(B > 0 && H > 0 && W > 0 && H <= MAX_DIM && W <= MAX_DIM && B <= 65535,
+                  "augment_tables: bad batch shape (B %d, %d x %d)", B, H, W);
+    MCAMD_REQUIRE(coef_elems >= 0 && lut_bytes >= 0, "augment_tables: negative buffer size");
+    for (int b = 0; b < B; ++b) {
+        const mcamd_augment_desc& d = desc_host[b];
+        MCAMD_REQUIRE(d.crop_w >= 1 && d.crop_h >= 1, "augment_tables: image %d: empty crop (%d x %d)", b, d.crop_w, d.crop_h);
+        MCAMD_REQUIRE(d.crop_w <= MAX_DIM && d.crop_h <= MAX_DIM, "augment_tables: image %d: crop %d x %d out of range", b,
+                      d.crop_w, d.crop_h);
+        const int hk = table_taps(d.crop_w, W), vk = table_taps(d.crop_h, H);
+        MCAMD_REQUIRE(d.hk == hk && d.vk == vk && hk <= MAX_TAPS && vk <= MAX_TAPS,
+                      "augment_tables: image %d: tap counts %d, %d, the tables of %d -> %d and %d -> %d have %d, %d", b, d.hk,
+                      d.vk, d.crop_w, W, d.crop_h, H, hk, vk);
+        MCAMD_REQUIRE(d.hcoef_off >= 0 && d.hcoef_off + (int64_t)W * (hk + 2) <= coef_elems && d.vcoef_off >= 0 &&
+                          d.vcoef_off + (int64_t)H * (vk + 2) <= coef_elems,
+                      "augment_tables: image %d: resampling table outside coef (%lld entries)", b, (long long)coef_elems);
+        MCAMD_REQUIRE(d.lut_off == -1 || (d.lut_off >= 0 && lut && hsv_dev && d.lut_off + 768 <= lut_bytes),
+                      "augment_tables: image %d: LUTs outside lut, or no hsv / lut buffer (lut_off %d)", b, d.lut_off);
+    }
+    hipLaunchKernelGGL(augment_tables_kernel, dim3(3, B), dim3(NTHR), 0, (hipStream_t)stream, desc_dev, hsv_dev, coef, lut,
+                       H, W);
+    MCAMD_LAUNCH_CHECK("augment_tables");
     return MCAMD_OK;
 }

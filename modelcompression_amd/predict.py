@@ -13,12 +13,28 @@ import xml.etree.ElementTree as ET
 import numpy as np
 import torch
 
-from .data import VOCList, SyntheticDetection
+from .augment import DeviceAugmenter
+from .data import VOCList, SyntheticDetection, ResidentImages, ResidentList, label_path_for
 from .nets import getYOLOv2
 from ._lib import McamdError
 from .nets2_utils import get_region_boxes, nms, detections, detections_device, detections_fused, get_image_size  # noqa: F401
 from .ops import DETECT_MAX_ROWS
 from .voc_eval import VOCGroundTruth, DeviceVOCEval
+
+
+class _DeviceBatches:
+    """A loader of pack_resident batches as the (data, target) batches predict() iterates."""
+
+    def __init__(self, loader, augmenter):
+        self.loader, self.augmenter = loader, augmenter
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for batch in self.loader:
+            data, _ = self.augmenter(batch)
+            yield data, batch.target
 
 
 class PASCALVOCEval():
@@ -48,26 +64,30 @@ class PASCALVOCEval():
         self.mAP = None
         self.aps = None
 
-    def predict(self, BATCH_SIZE=2, CONF_THRESH=0.005, NMS_THRESH=0.45, DEVICE_EVAL=False):
+    def predict(self, BATCH_SIZE=2, CONF_THRESH=0.005, NMS_THRESH=0.45, DEVICE_EVAL=False, RESIDENT=None):
         """DEVICE_EVAL=True: detections, their matching to the ground truth and the per-class AP stay on the device
         (mcamd_detect, mcamd_voc_match, mcamd_voc_ap); no detection files are written and self.aps / self.mAP
-        are the float64 values the file path computes from the same detections."""
+        are the float64 values the file path computes from the same detections.
+        RESIDENT: the pictures of EVAL_IMAGELIST come from a data.ResidentImages on the model's device instead of a
+        loader worker: True builds it from the list once per instance, or pass one built before.  The
+        batches are the same bytes (Image.resize + /255 on the device), so are the detections."""
         if self.MODEL == '' or self.MODEL is None:
             self.MODEL = getYOLOv2(self.MODEL_CFGFILE, self.MODEL_WEIGHTFILE)
         self.MODEL.eval()
         if DEVICE_EVAL:
-            return self._predict_device(BATCH_SIZE, CONF_THRESH, NMS_THRESH)
+            return self._predict_device(BATCH_SIZE, CONF_THRESH, NMS_THRESH, RESIDENT)
         dev = next(self.MODEL.parameters()).device
         have_list = bool(self.EVAL_IMAGELIST) and os.path.exists(self.EVAL_IMAGELIST)
         if have_list:
             with open(self.EVAL_IMAGELIST) as fp:
                 valid_files = [item.rstrip() for item in fp.readlines()]
-            ds = VOCList(self.EVAL_IMAGELIST, shape=(self.MODEL.width, self.MODEL.height), train=False)
+            loader = self._list_loader(BATCH_SIZE, dev, RESIDENT)
         else:
+            if RESIDENT is not None and RESIDENT is not False:
+                raise McamdError("predict(RESIDENT=...) needs an image list, got `%s`" % self.EVAL_IMAGELIST)
             ds = SyntheticDetection(4 * BATCH_SIZE, shape=(self.MODEL.width, self.MODEL.height), seed=1)
             valid_files = ['synthetic_%06d.jpg' % i for i in range(len(ds))]
-        loader = torch.utils.data.DataLoader(ds, batch_size=BATCH_SIZE, shuffle=False, num_workers=1 if have_list else 0,
-                                             pin_memory=True)
+            loader = torch.utils.data.DataLoader(ds, batch_size=BATCH_SIZE, shuffle=False, num_workers=0, pin_memory=True)
         os.makedirs(self.EVAL_OUTPUTDIR, exist_ok=True)
         fps = [open('%s/%s%s.txt' % (self.EVAL_OUTPUTDIR, self.EVAL_PREFIX, c), 'w') for c in self.VOC_CLASSES[:self.MODEL.num_classes]]
         lineId, val_loss_total, ndet = -1, 0.0, 0
@@ -102,11 +122,37 @@ class PASCALVOCEval():
             self._do_python_eval()
         return self.mAP
 
+    def _list_loader(self, BATCH_SIZE, dev, resident):
+        """The (data, target) batches of EVAL_IMAGELIST, in list order: VOCList through one loader worker, or, with
+        RESIDENT, ResidentList batches resampled on the device from the resident pictures."""
+        shape = (self.MODEL.width, self.MODEL.height)
+        if resident is None or resident is False:
+            ds = VOCList(self.EVAL_IMAGELIST, shape=shape, train=False)
+            return torch.utils.data.DataLoader(ds, batch_size=BATCH_SIZE, shuffle=False, num_workers=1, pin_memory=True)
+        if dev.type != 'cuda':
+            raise McamdError("predict(RESIDENT=...) needs the model on the GPU, it is on `%s`" % dev)
+        lines = VOCList(self.EVAL_IMAGELIST, shape=shape, train=False).lines
+        if resident is True:
+            if getattr(self, '_resident', None) is None:
+                self._resident = ResidentImages(lines, dev)
+            resident = self._resident
+        if len(resident) != len(lines):
+            raise McamdError("predict(RESIDENT=...): %d resident pictures, %d lines in `%s`"
+                             % (len(resident), len(lines), self.EVAL_IMAGELIST))
+        if resident.device != dev:
+            raise McamdError("predict(RESIDENT=...): the pictures are on `%s`, the model on `%s`" % (resident.device, dev))
+        if getattr(self, '_resident_list', (None,))[0] is not resident:
+            self._resident_list = (resident, ResidentList(resident, [label_path_for(p) for p in lines], shape))
+        rl = self._resident_list[1]
+        loader = torch.utils.data.DataLoader(rl, batch_size=BATCH_SIZE, shuffle=False, num_workers=0, pin_memory=True,
+                                             collate_fn=rl.collate)
+        return _DeviceBatches(loader, DeviceAugmenter(shape, dev, resident))
+
     # records the device evaluation holds (DeviceVOCEval: 9 bytes each, and the sort's workspace).  More make predict
     # raise McamdError naming this capacity; a set that emits more at the reference's CONF_THRESH 0.005 raises it here.
     DEVICE_EVAL_CAPACITY = 1 << 22
 
-    def _predict_device(self, BATCH_SIZE, CONF_THRESH, NMS_THRESH):
+    def _predict_device(self, BATCH_SIZE, CONF_THRESH, NMS_THRESH, RESIDENT=None):
         if not (bool(self.EVAL_IMAGELIST) and os.path.exists(self.EVAL_IMAGELIST)):
             raise McamdError("predict(DEVICE_EVAL=True) needs an image list, got `%s`" % self.EVAL_IMAGELIST)
         base = os.path.join(self.PASCAL_DIR or '', 'VOC' + self.VOC_YEAR)
@@ -122,8 +168,7 @@ class PASCALVOCEval():
                             os.path.join(base, 'ImageSets', 'Main', 'test.txt'), valid_files, classes, dev,
                             default_size=(self.MODEL.width, self.MODEL.height))
         acc = DeviceVOCEval(gt, len(classes), capacity=self.DEVICE_EVAL_CAPACITY)
-        ds = VOCList(self.EVAL_IMAGELIST, shape=(self.MODEL.width, self.MODEL.height), train=False)
-        loader = torch.utils.data.DataLoader(ds, batch_size=BATCH_SIZE, shuffle=False, num_workers=1, pin_memory=True)
+        loader = self._list_loader(BATCH_SIZE, dev, RESIDENT)
         first, val_loss_total = 0, 0.0
         with torch.no_grad():
             for data, target in loader:

@@ -16,6 +16,9 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
   * AUGMENT=True trains on the reference's train=True augmentation (dataloader.py:68-75): data.VOCAugment (or
     data.SyntheticAugment without a list) decodes and draws parameters, augment.DeviceAugmenter does the pixels in
     one HIP launch pair per batch on the training stream.  Off by default.
+  * RESIDENT=True decodes the train list once into device memory (data.ResidentImages; every rank keeps the whole
+    set) and trains from it with no loader workers: data.ResidentAugment with AUGMENT, data.ResidentList without;
+    with EVAL the evaluation pictures are made resident once, for every epoch's predict.  Off by default.
 """
 import os
 
@@ -29,7 +32,8 @@ import torch.optim as optim  # noqa: E402
 
 from . import dp  # noqa: E402
 from .augment import DeviceAugmenter, collate_fn  # noqa: E402
-from .data import VOCList, SyntheticDetection, VOCAugment, SyntheticAugment  # noqa: E402
+from .data import (VOCList, SyntheticDetection, VOCAugment, SyntheticAugment, ResidentImages, ResidentAugment,  # noqa: E402
+                   ResidentList, label_path_for, read_boxes)
 from .nets import Darknet, parse_cfg  # noqa: E402
 from .pruning.weightPruning.methods import quick_filter_prune, weight_prune  # noqa: E402
 from .pruning.weightPruning.utils import prune_rate, are_masks_consistent  # noqa: E402
@@ -185,7 +189,7 @@ class YOLOv2Train():
               MODEL_CFG, MODEL_WEIGHT,
               BATCH_SIZE, SAVE_INTERNAL,
               LOGGER='', DEBUG_EPOCHS=-1, verbose=0, pruning_perc=0., pruning_method="weight",
-              MAX_EPOCHS=135, SYNTHETIC_SAMPLES=256, EVAL=False, AUGMENT=False):
+              MAX_EPOCHS=135, SYNTHETIC_SAMPLES=256, EVAL=False, AUGMENT=False, RESIDENT=False):
         rank, world = dp.init_from_env()
         local = int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(local)
@@ -207,13 +211,35 @@ class YOLOv2Train():
         self.trainlist, self.testlist = PASCAL_TRAIN, PASCAL_VALID
         self.init_width, self.init_height = self.model.width, self.model.height
         shape = (self.init_width, self.init_height)
+        resident = None
         if PASCAL_TRAIN and os.path.exists(PASCAL_TRAIN):
             nsamples = file_lines(self.trainlist)
             dataset = VOCAugment(self.trainlist, shape=shape) if AUGMENT else VOCList(self.trainlist, shape=shape, train=True)
+            if RESIDENT:
+                t0 = time.time()
+                resident = ResidentImages(dataset.lines, dev)
+                labels = [label_path_for(p) for p in dataset.lines]
+                dataset = (ResidentAugment(resident, [read_boxes(lp) for lp in labels], shape) if AUGMENT
+                           else ResidentList(resident, labels, shape))
         else:
             nsamples = SYNTHETIC_SAMPLES
             dataset = SyntheticAugment(nsamples, shape=shape) if AUGMENT else SyntheticDetection(nsamples, shape=shape)
             logging('train list %r not found: synthetic detection set of %d samples' % (PASCAL_TRAIN, nsamples))
+            if RESIDENT:
+                # the uint8 sources of SyntheticAugment either way (SyntheticDetection's float pictures have no uint8 form)
+                t0 = time.time()
+                items = [SyntheticAugment(nsamples, shape=shape)[i] for i in range(nsamples)]
+                resident = ResidentImages.from_sources([src for src, _, _ in items], dev)
+                if AUGMENT:
+                    dataset = ResidentAugment(resident, [boxes for _, boxes, _ in items], shape)
+                else:
+                    targets = torch.zeros(nsamples, 250)
+                    for i, (_, boxes, _) in enumerate(items):
+                        targets[i, :boxes.size] = torch.from_numpy(boxes.astype('float32').reshape(-1))
+                    dataset = ResidentList(resident, targets, shape)
+        if resident is not None and rank == 0:
+            logging('%d pictures resident on %s: %d bytes, built in %.2f s' % (len(resident), dev, resident.nbytes,
+                                                                               time.time() - t0))
         if TRAIN_LOGDIR and rank == 0 and not os.path.exists(TRAIN_LOGDIR):
             os.makedirs(TRAIN_LOGDIR, exist_ok=True)
 
@@ -248,11 +274,15 @@ class YOLOv2Train():
 
         per_rank = max(1, self.batch_size // world)
         sampler = torch.utils.data.distributed.DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 else None
-        augmenter = DeviceAugmenter(shape, dev) if AUGMENT else None
+        augmenter = DeviceAugmenter(shape, dev, resident) if AUGMENT or resident is not None else None
         loader = torch.utils.data.DataLoader(dataset, batch_size=per_rank, shuffle=(sampler is None), sampler=sampler,
                                              num_workers=4 if isinstance(dataset, (VOCList, VOCAugment, SyntheticAugment)) else 0,
                                              pin_memory=True, drop_last=True,
-                                             collate_fn=collate_fn(shape) if AUGMENT else None)
+                                             collate_fn=dataset.collate if resident is not None
+                                             else collate_fn(shape) if AUGMENT else None)
+        eval_resident = None
+        if RESIDENT and EVAL and rank == 0 and PASCAL_VALID and os.path.exists(PASCAL_VALID):
+            eval_resident = ResidentImages(VOCList(PASCAL_VALID, shape=shape, train=False).lines, dev)
         guard = StepGuard(self.model, optimizer, dev, log=logging if rank == 0 else None)
         epoch = init_epoch
         for epoch in range(init_epoch, min(MAX_EPOCHS, 135)):
@@ -269,7 +299,7 @@ class YOLOv2Train():
             for batch_idx, batch in enumerate(loader):
                 if DEBUG_EPOCHS > -1 and batch_idx > DEBUG_EPOCHS:
                     break
-                data, target = augmenter(batch) if AUGMENT else batch
+                data, target = augmenter(batch) if augmenter is not None else batch
                 data = data.to(dev, non_blocking=True)
                 target = target.float().to(dev, non_blocking=True)
                 output = self.model(data)
@@ -306,7 +336,7 @@ class YOLOv2Train():
             if EVAL and rank == 0:
                 from .predict import PASCALVOCEval
                 PASCALVOCEval(self.model, MODEL_CFG, MODEL_WEIGHT, region_loss, PASCAL_DIR, PASCAL_VALID, VAL_LOGDIR,
-                              VAL_PREFIX, VAL_OUTPUTDIR_PKL, LOGGER, epoch).predict(BATCH_SIZE)
+                              VAL_PREFIX, VAL_OUTPUTDIR_PKL, LOGGER, epoch).predict(BATCH_SIZE, RESIDENT=eval_resident)
         if TRAIN_LOGDIR and rank == 0:
             name = '%s/%s-pruned-%s-retrained-final_%06d.weights' % (TRAIN_LOGDIR, pruning_method, pruning_perc, epoch + 1)
             logging('save weights to %s' % name)

@@ -3,9 +3,12 @@
   * device time of mcamd_augment per B=64 batch of VOC-sized sources (HIP events, warmed up), bytes moved, HBM share;
   * loader images/s with 16 workers over synthetic JPEGs in a temp dir: VOCList (PIL resize, no augmentation) and
     VOCAugment + collate + DeviceAugmenter;
-  * train(..., AUGMENT=True) samples/s over 20 steps on the synthetic ragged source, next to AUGMENT=False.
+  * train(..., AUGMENT=True) samples/s over 20 steps on the synthetic ragged source, next to AUGMENT=False;
+  * --resident instead: the same JPEG list made resident on the device (build seconds, bytes), then, taken
+    alternately in this process for --rounds rounds, images/s of the two loaders above (16 workers) and of ResidentList /
+    ResidentAugment + DeviceAugmenter with 0, 4 and 16 loader workers; the median of the rounds is reported.
 
-    python tools/augment_bench.py [--iters 50] [--images 512] [--skip-train] [--device-only]
+    python tools/augment_bench.py [--iters 50] [--images 512] [--skip-train] [--device-only] [--resident [--rounds 3]]
 """
 import argparse
 import contextlib
@@ -14,6 +17,7 @@ import json
 import os
 import random
 import re
+import statistics
 import sys
 import tempfile
 import time
@@ -23,7 +27,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from modelcompression_amd import YOLOV2_VOC_CFG, augment as A  # noqa: E402
-from modelcompression_amd.data import VOCAugment, VOCList  # noqa: E402
+from modelcompression_amd.data import (ResidentAugment, ResidentImages, ResidentList, VOCAugment, VOCList,  # noqa: E402
+                                       label_path_for, read_boxes)
 
 HBM_BPS = 6.3e12      # achievable copy rate, MI355X_MICROARCH
 
@@ -102,6 +107,48 @@ def loader_rate(dev, listfile, augment):
     return round(n / (time.time() - t0), 1)
 
 
+def resident_rate(dev, ds, resident, workers, passes=4):
+    """images/s of a resident set's loader + DeviceAugmenter over `passes` passes (the first batch is not timed)."""
+    loader = torch.utils.data.DataLoader(ds, batch_size=64, shuffle=False, num_workers=workers, pin_memory=True,
+                                         drop_last=True, collate_fn=ds.collate)
+    aug = A.DeviceAugmenter(ds.shape, dev, resident)
+    n, t0 = 0, None
+    for epoch in range(passes):
+        for i, batch in enumerate(loader):
+            if epoch == 0 and i == 1:
+                torch.cuda.synchronize()
+                t0, n = time.time(), 0
+            x, _ = aug(batch)
+            n += x.shape[0]
+    torch.cuda.synchronize()
+    return round(n / (time.time() - t0), 1)
+
+
+def resident_figures(dev, listfile, rounds):
+    shape = (416, 416)
+    lines = VOCList(listfile, shape).lines
+    res = {}
+    for workers in (4, 16):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        resident = ResidentImages(lines, dev, num_workers=workers)
+        res["resident_build_s_%d_threads" % workers] = round(time.time() - t0, 3)
+    res["resident_images"], res["resident_bytes"] = len(resident), resident.nbytes
+    labels = [label_path_for(p) for p in lines]
+    sets = {"list": ResidentList(resident, labels, shape),
+            "augment": ResidentAugment(resident, [read_boxes(lp) for lp in labels], shape)}
+    runs = {}
+    for _ in range(rounds):                      # old and new alternately: drift of the machine hits both
+        for name, augment in (("list", False), ("augment", True)):
+            runs.setdefault("loader_%s_files_16w_img_s" % name, []).append(loader_rate(dev, listfile, augment))
+            for workers in (0, 4, 16):
+                runs.setdefault("loader_%s_resident_%dw_img_s" % (name, workers), []).append(
+                    resident_rate(dev, sets[name], resident, workers))
+    for k, v in runs.items():
+        res[k] = {"median": statistics.median(v), "runs": v}
+    return res
+
+
 def train_rate(augment, steps=20):
     from modelcompression_amd.train import YOLOv2Train
     buf = io.StringIO()
@@ -117,9 +164,17 @@ def main():
     ap.add_argument("--images", type=int, default=512)
     ap.add_argument("--skip-train", action="store_true")
     ap.add_argument("--device-only", action="store_true", help="only the device time (for a profiler run)")
+    ap.add_argument("--resident", action="store_true", help="file loaders against the resident loaders, alternately")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     res = {"metric": "augment", "pil": __import__("PIL").__version__}
+    if a.resident:
+        res["metric"] = "augment_resident"
+        with tempfile.TemporaryDirectory() as root:
+            res.update(resident_figures(dev, write_jpegs(root, a.images), a.rounds))
+        print(json.dumps(res))
+        return
     res.update(device_time(dev, a.iters))
     if a.device_only:
         print(json.dumps(res))

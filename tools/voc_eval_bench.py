@@ -5,7 +5,10 @@ module that replays stored 13x13 logits randn * 1.5 (the spread of tests/golden/
 evaluation and the image loader that both paths share (timed alone as `loader`).  mAP is meaningless here; the two paths
 report the same one unless scores tie after the six-decimal rounding (numpy's argsort is not stable).
 Thresholds (0.005, 0.45) -- the reference's evaluation -- and (0.25, 0.45).  Median of five runs.
-usage: python tools/voc_eval_bench.py [images] [batch] [--json]"""
+--resident instead: the pictures made resident on the device once (build seconds, bytes), then, run by run
+alternately, the loader alone from files (one worker, as predict starts it) and from the resident set (0, 4 and 16 loader
+workers), and both paths of predict at (0.005, 0.45) with RESIDENT=None and RESIDENT=True.
+usage: python tools/voc_eval_bench.py [images] [batch] [--json] [--resident]"""
 import contextlib
 import io
 import json
@@ -21,7 +24,8 @@ import numpy as np
 import torch
 from PIL import Image
 from modelcompression_amd import nets, YOLOV2_VOC_CFG
-from modelcompression_amd.data import VOCList
+from modelcompression_amd.augment import DeviceAugmenter
+from modelcompression_amd.data import ResidentImages, ResidentList, VOCList, label_path_for
 from modelcompression_amd.predict import PASCALVOCEval
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -99,10 +103,10 @@ ev.fused = True
 res = {"tool": "voc_eval_bench", "images": IMAGES, "batch": B, "repeats": REPEATS, "grid": [13, 13], "logits": "randn * 1.5"}
 
 
-def run(ct, nt, device_eval):
+def run(ct, nt, device_eval, resident=None):
     model.calls = 0
     with contextlib.redirect_stdout(io.StringIO()):
-        return ev.predict(BATCH_SIZE=B, CONF_THRESH=ct, NMS_THRESH=nt, DEVICE_EVAL=device_eval)
+        return ev.predict(BATCH_SIZE=B, CONF_THRESH=ct, NMS_THRESH=nt, DEVICE_EVAL=device_eval, RESIDENT=resident)
 
 
 def loader_only():
@@ -111,6 +115,56 @@ def loader_only():
         data.to(dev)
 
 
+def alternately(fns):
+    """{name: fn} -> {name: median / min / max seconds}: one warm-up each, then REPEATS rounds that run every fn once."""
+    v = {k: [] for k in fns}
+    for k, fn in fns.items():
+        fn()
+    for _ in range(REPEATS):
+        for k, fn in fns.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            v[k].append(time.perf_counter() - t0)
+    return {k: {"s": round(statistics.median(t), 4), "min": round(min(t), 4), "max": round(max(t), 4)} for k, t in v.items()}
+
+
+def resident_bench():
+    shape = (like.width, like.height)
+    lines = VOCList(listfile, shape=shape, train=False).lines
+    for workers in (4, 16):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        resident = ResidentImages(lines, dev, num_workers=workers)
+        res["resident_build_s_%d_threads" % workers] = round(time.perf_counter() - t0, 3)
+    res["resident_bytes"] = resident.nbytes
+    rl = ResidentList(resident, [label_path_for(p) for p in lines], shape)
+    aug = DeviceAugmenter(shape, dev, resident)
+
+    def resident_loader(workers):
+        for batch in torch.utils.data.DataLoader(rl, batch_size=B, shuffle=False, num_workers=workers, pin_memory=True,
+                                                 collate_fn=rl.collate):
+            aug(batch)
+    fns = {"loader_files_1w": loader_only}
+    for workers in (0, 4, 16):
+        fns["loader_resident_%dw" % workers] = lambda w=workers: resident_loader(w)
+    res["loader"] = alternately(fns)
+    r = alternately({"device_path_files": lambda: run(0.005, 0.45, True), "device_path_resident": lambda: run(0.005, 0.45, True, resident),
+                     "file_path_files": lambda: run(0.005, 0.45, False), "file_path_resident": lambda: run(0.005, 0.45, False, resident)})
+    run(0.005, 0.45, True)
+    r["mAP_files"] = ev.mAP
+    run(0.005, 0.45, True, resident)
+    r["mAP_resident"] = ev.mAP
+    res["conf_0.005_nms_0.45"] = r
+
+
+if "--resident" in sys.argv:
+    res["tool"] = "voc_eval_bench --resident"
+    resident_bench()
+    shutil.rmtree(root, ignore_errors=True)
+    print(json.dumps(res))
+    sys.exit(0)
 res["loader"] = median_seconds(loader_only, "loader")
 for ct, nt in ((0.005, 0.45), (0.25, 0.45)):
     r = {"device_path": median_seconds(lambda: run(ct, nt, True), "device_path %g" % ct)}
