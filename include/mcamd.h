@@ -544,6 +544,30 @@ typedef struct mcamd_act_desc {
 } mcamd_act_desc;
 int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream);
 
+/* mcamd_bn_act_fwd(d) followed by mcamd_conv_fwd(g, d->dst, wp_fwd, epi) in ONE launch, for a PLAIN block whose only
+ * consumer is a 1x1 convolution on split operands (csrc/bn_conv1x1.hip): a workgroup reads the producer's fp32 raw output
+ * d->y once, applies leaky(y * scale + shift), splits into hi = fp16(v) saturated and lo = fp16(v - hi) in registers and
+ * multiplies x_hi w_hi + x_lo w_hi + x_hi w_lo with the packed weights [w_hi | w_hi | w_lo] (mcamd_pack_job.split 1) on the
+ * fp16 MFMAs -- the same instructions in the same K order as the launches it replaces, so epi->y and epi->stats are
+ * BIT-EQUAL to theirs.  The hi plane is still written, to channels [d->dst_choff, d->dst_choff + d->C) of the interior
+ * pixels of d->dst (the backward pass reads it); the lo plane and the halo are not touched.  Replaces nn.BatchNorm2d +
+ * nn.LeakyReLU + F.conv2d (reference src/nets.py:802-809, src/pruning/weightPruning/layers.py:60-64) for such a pair.
+ *   d   : the activation pass as mcamd_bn_act_fwd would get it: mode MCAMD_DST_PLAIN, fp32 y (y_dtype 1), planes 2 with
+ *         dst_plane == C, dst_pad 0, no dst2 / border / pool_act / dst_q8
+ *   g   : the consumer's forward geometry as mcamd_conv_fwd would get it: ksize 1, cin = 3 C, x_wrap = 2 C, pad 0, no x_f8,
+ *         x_ld == d->dst_ld, x_choff == d->dst_choff, the producer's B x H x W
+ *   epi : mode MCAMD_EPI_RAW_F32; stats may be NULL (no slab is written), else stats_rows ==
+ *         mcamd_bn_act_conv1x1_stats_rows(d, g) (== mcamd_conv_stats_rows_mode(g, MCAMD_EPI_RAW_F32))
+ * mcamd_bn_act_conv1x1_ok (host logic only, pointers are not read): 1 when the pair has a fused launch -- the above, C % 64
+ * == 0, cout % 8 == 0 within one column tile (<= 128), C <= 128 (cout <= 64) or 256 (a thread keeps its converted values in
+ * registers across the three parts), and a consumer whose own forward takes igemm_kernel's 128-pixel tiles of 64 or 128
+ * columns (the persistent slots and the wave rows of 64 pixels, hence the slab and its summation order, are that launch's;
+ * cout <= 32 takes the 32-column tile there and is refused).  Everything else is refused, by the launch entry too (MCAMD_EINVAL). */
+int32_t mcamd_bn_act_conv1x1_ok(const mcamd_act_desc* d, const mcamd_conv_geom* g);
+int32_t mcamd_bn_act_conv1x1_stats_rows(const mcamd_act_desc* d, const mcamd_conv_geom* g);   /* 0 when refused */
+int mcamd_bn_act_conv1x1_fwd(const mcamd_act_desc* d, const mcamd_conv_geom* g, const void* wp_fwd,
+                             const mcamd_conv_epilogue* epi, void* stream);
+
 typedef struct mcamd_act_bwd_desc {
     int32_t B, H, W, C;
     const void* y; int32_t y_ld, y_choff;   /* saved raw conv output */

@@ -210,6 +210,9 @@ SIGNATURES = {
     "mcamd_fold_weights_many": (C.c_int, [_P, _I32, _I64, _P]),
     "mcamd_unfold_wgrad": (C.c_int, [C.POINTER(FoldDesc), _P, _P, _P, _P, _I32, _P]),
     "mcamd_bn_act_fwd": (C.c_int, [C.POINTER(ActDesc), _P]),
+    "mcamd_bn_act_conv1x1_ok": (_I32, [C.POINTER(ActDesc), C.POINTER(ConvGeom)]),
+    "mcamd_bn_act_conv1x1_stats_rows": (_I32, [C.POINTER(ActDesc), C.POINTER(ConvGeom)]),
+    "mcamd_bn_act_conv1x1_fwd": (C.c_int, [C.POINTER(ActDesc), C.POINTER(ConvGeom), _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_bn_act_bwd_workspace_bytes": (_SZ, [C.POINTER(ActBwdDesc)]),
     "mcamd_bn_act_bwd": (C.c_int, [C.POINTER(ActBwdDesc), _P, _SZ, _P]),
     "mcamd_stem_block_workspace_bytes": (_SZ, []),

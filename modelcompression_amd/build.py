@@ -34,6 +34,7 @@ SOURCES = {
     "conv_wgrad.hip": [],
     "conv_wgrad_stem.hip": [],
     "bn_act.hip": [],
+    "bn_conv1x1.hip": [],
     "fold.hip": [],
     "plan.hip": [],
     "region_loss.hip": [],

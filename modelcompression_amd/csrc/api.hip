@@ -4,6 +4,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <string>
+
 #include "kernels.h"
 
 static thread_local char g_err[512] = "";
@@ -585,6 +587,69 @@ extern "C" int mcamd_conv_fwd(const mcamd_conv_geom* g, const void* x, const voi
     }
     if (fill_epilogue(a, epi, g->cout, "conv_fwd", r.rows)) return MCAMD_EINVAL;
     return launch_route(a, r, g, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// BatchNorm + LeakyReLU fused into the 1x1 split-operand forward behind it (bn_conv1x1.hip)
+// ---------------------------------------------------------------------------------------
+// Host logic only.  NULL = the pair (activation pass `d`, consumer forward `g`) has a fused launch; else why not.  *r: the
+// route of the consumer's own forward, whose persistent slots (statistics rows) the fused launch keeps.
+static const char* bn_conv1x1_refusal(const mcamd_act_desc* d, const mcamd_conv_geom* g, ConvRoute* r) {
+    if (!d || !g) return "null descriptor";
+    if (check_geom(g, "bn_act_conv1x1")) return mcamd_last_error();
+    if (g->ksize != 1 || g->stem) return "the consumer is not a 1x1 convolution";
+    if (g->x_f8 != 0) return "fp8 correction operands (x_f8)";
+    if (g->pad != 0 || d->dst_pad != 0) return "shared-halo destination";
+    const int P = g->x_wrap / 2;
+    if (g->x_wrap <= 0 || g->cin != 3 * P) return "the consumer does not multiply split operands on two planes (x_wrap)";
+    if (P % 64 != 0) return "input channels must be a multiple of 64";
+    if (!mcamd_bn_conv1x1_shape_ok(P, g->cout)) return "no kernel instance: cout <= 128 in steps of 8, cin <= 128 (cout <= 64) or 256";
+    if (d->mode != MCAMD_DST_PLAIN || d->dst2 || d->pool_act || d->dst_q8 || d->dst2_q8) return "the producer is not a PLAIN block with one destination";
+    if (d->border) return "border table";
+    if (d->B != g->B || d->H != g->H || d->W != g->W) return "producer and consumer differ in B x H x W";
+    if (d->C != P || d->planes != 2 || d->dst_plane != P || d->dst_ld != g->x_ld || d->dst_choff != g->x_choff)
+        return "the producer's hi | lo planes are not the consumer's input slice";
+    if (d->y_dtype != 1 || d->y_ld % 4 != 0 || d->y_choff % 4 != 0 || d->y_choff + P > d->y_ld) return "the raw output must be an fp32 slice in steps of 4 channels";
+    *r = conv_route(g, DIR_FWD, MCAMD_EPI_RAW_F32, MCAMD_DST_PLAIN, true);
+    // (igemm_kernel's 32-column tile has wave rows of 32 pixels, the wider ones of 64: another order of the partial sums)
+    if (r->kernel != ROUTE_IGEMM || r->bm != 128 || r->bn < 64) return "the consumer's own forward does not take 128-pixel igemm tiles in wave rows of 64";
+    return nullptr;
+}
+
+extern "C" int32_t mcamd_bn_act_conv1x1_ok(const mcamd_act_desc* d, const mcamd_conv_geom* g) {
+    ConvRoute r;
+    return bn_conv1x1_refusal(d, g, &r) ? 0 : 1;
+}
+
+extern "C" int32_t mcamd_bn_act_conv1x1_stats_rows(const mcamd_act_desc* d, const mcamd_conv_geom* g) {
+    ConvRoute r;
+    return bn_conv1x1_refusal(d, g, &r) ? 0 : r.rows;
+}
+
+extern "C" int mcamd_bn_act_conv1x1_fwd(const mcamd_act_desc* d, const mcamd_conv_geom* g, const void* wp_fwd,
+                                        const mcamd_conv_epilogue* epi, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(d && g && epi, "bn_act_conv1x1_fwd: null descriptor / geometry / epilogue");
+        const mcamd_act_desc d_ = *d;
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_bn_act_conv1x1_fwd(&d_, &g_, wp_fwd, &e_, s); });
+    }
+    ConvRoute r;
+    const char* why = bn_conv1x1_refusal(d, g, &r);
+    if (why) {
+        const std::string w(why);   // (may be the error buffer itself)
+        mcamd_set_error("bn_act_conv1x1_fwd: %s (mcamd_bn_act_conv1x1_ok)", w.c_str());
+        return MCAMD_EINVAL;
+    }
+    MCAMD_REQUIRE(d->y && d->scale && d->shift && d->dst && wp_fwd && epi, "bn_act_conv1x1_fwd: null input / epilogue");
+    MCAMD_REQUIRE(epi->mode == MCAMD_EPI_RAW_F32, "bn_act_conv1x1_fwd: epilogue mode 3 (MCAMD_EPI_RAW_F32) only");
+    IgemmArgs a;
+    fill_operand(a, g, d->dst, wp_fwd, g->x_ld, g->x_choff, g->cout, cin_tap_of(g), 0);
+    a.wrap = g->x_wrap;
+    if (fill_epilogue(a, epi, g->cout, "bn_act_conv1x1_fwd", r.rows)) return MCAMD_EINVAL;
+    a.scale = d->scale, a.shift = d->shift, a.slope = d->slope;
+    return mcamd_bn_conv1x1_launch(a, (const float*)d->y, d->y_ld, d->y_choff, g->x_wrap / 2, r.rows, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------

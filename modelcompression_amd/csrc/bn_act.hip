@@ -116,9 +116,7 @@ __device__ __forceinline__ void load8(const half_t* p, float* v) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
 }
-__device__ __forceinline__ half_t sat_half(float v) {  // saturate instead of overflowing to inf (inf * 0 = NaN downstream)
-    return (half_t)fminf(fmaxf(v, -65504.f), 65504.f);
-}
+// (sat_half, bn_leaky, split_hi_lo: conv_epi.h -- shared with the fused 1x1 forward, bn_conv1x1.hip)
 __device__ __forceinline__ void store8(half_t* p, const float* v) {
     h8_t h;
 #pragma unroll
@@ -147,9 +145,8 @@ __device__ __forceinline__ void load_y(const void* y, long long idx, float* v) {
 // e4m3 strings too).  The conversion instruction returns NaN above 448: clamped first.
 template <int PL>
 __device__ __forceinline__ void store_act(half_t* p, int plane, const float* v, int ci = 0) {
-    h8_t hi;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hi[i] = sat_half(v[i]);
+    h8_t hi, lo;
+    split_hi_lo(v, hi, lo);
     *(h8_t*)p = hi;
     if (PL == 4) {
         float ql[8], q8[8];
@@ -171,9 +168,6 @@ __device__ __forceinline__ void store_act(half_t* p, int plane, const float* v, 
         *(i32x2_t*)b = i32x2_t{wl[0], wl[1]};
         *(i32x2_t*)(b + plane) = i32x2_t{w8[0], w8[1]};
     } else if (PL >= 2) {
-        h8_t lo;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) lo[i] = (half_t)(v[i] - (float)hi[i]);   // exact difference, one rounding; |lo| <= ulp(hi)/2
         *(h8_t*)(p + plane) = lo;
         if (PL == 3) *(h8_t*)(p + 2 * plane) = hi;      // (PL == 2: the consumer wraps its third K part onto the hi plane)
     }
@@ -247,10 +241,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(ActArgs a) {
                 for (int i = 0; i < 8; ++i) v[i] += bb[i];
             }
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                float z = v[i] * sc[i] + sh[i];
-                v[i] = z > 0.f ? z : z * a.slope;
-            }
+            for (int i = 0; i < 8; ++i) v[i] = bn_leaky(v[i], sc[i], sh[i], a.slope);
             if (Q8) store_act_q8(a.dst, a.dst_q8, pad_off(b, h, w, a.H, a.W, a.dst_ld, a.dst_pw) + a.dst_choff + c8, v);
             else store_act<PL>(a.dst + pad_off(b, h, w, a.H, a.W, a.dst_ld, a.dst_pw) + a.dst_choff + c8, a.dst_plane, v, a.dst_choff + c8);
         } else {
@@ -270,10 +261,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(ActArgs a) {
                     for (int i = 0; i < 8; ++i) act[k][i] += bb[i];
                 }
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    float z = act[k][i] * sc[i] + sh[i];
-                    act[k][i] = z > 0.f ? z : z * a.slope;
-                }
+                for (int i = 0; i < 8; ++i) act[k][i] = bn_leaky(act[k][i], sc[i], sh[i], a.slope);
                 if (Q8) {
                     if (a.dst2) store_act_q8(a.dst2, a.dst2_q8, pad_off(b, h, w, a.H, a.W, a.dst2_ld, a.dst2_pw) + a.dst2_choff + c8, act[k]);
                 } else if (a.dst2) store_act2<PL>(a.dst2_pl, a.dst2 + pad_off(b, h, w, a.H, a.W, a.dst2_ld, a.dst2_pw) + a.dst2_choff + c8, a.dst2_plane, act[k], a.dst2_choff + c8);

@@ -188,6 +188,85 @@ __device__ __forceinline__ void store_raw_tile(const IgemmArgs& __restrict__ a, 
 }
 
 // ---------------------------------------------------------------------------------------
+// MCAMD_EPI_RAW_F32 of the kernels whose waves hold (WM / 32) x (WN / 32) accumulator blocks of 32 x 32 (igemm_kernel,
+// bn_conv1x1_kernel): the unrounded accumulators to fp32 [M][y_ld] -- a store instruction writes two rows x 32
+// consecutive floats, whole 128-byte lines straight from the registers -- and the BatchNorm partial sums of the lane's
+// column taken from the same fp32 values (rows >= M contribute nothing).
+// ---------------------------------------------------------------------------------------
+template <int BM, int BN, int WM, int WN>
+__device__ __forceinline__ void store_raw32_tile(const IgemmArgs& __restrict__ a, const f32x16_t (&acc)[WM / 32][WN / 32], int mt, int nt,
+                                                 int wm, int wn, int lane, float (&s1)[WN / 32], float (&s2)[WN / 32]) {
+    constexpr int TM = WM / 32, TN = WN / 32;
+    float* y = (float*)a.y;
+    const int mlim = a.M - mt * BM;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = nt * BN + wn * WN + j * 32 + (lane & 31);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = wm * WM + i * 32 + mfma32_row(r, lane);
+                const float v = acc[i][j][r];
+                if (row < mlim) {
+                    if (n < a.N) y[(long long)(mt * BM + row) * a.y_ld + a.y_choff + n] = v;
+                    s1[j] += v;
+                    s2[j] += v * v;
+                }
+            }
+    }
+}
+
+// ... and a persistent workgroup's sums to its slab row [2][stats_ld] once its M tiles are done: the two lane halves, then
+// the BM / WM wave rows in order (deterministic).  `smem`: (BM / WM) * 2 * BN floats.
+template <int BM, int BN, int WM, int WN, int NT>
+__device__ __forceinline__ void store_stats_slab(const IgemmArgs& __restrict__ a, char* smem, float (&s1)[WN / 32], float (&s2)[WN / 32],
+                                                 int pslot, int nt, int wm, int wn, int lane, int tid) {
+    constexpr int TN = WN / 32;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        s1[j] += __shfl_xor(s1[j], 32);
+        s2[j] += __shfl_xor(s2[j], 32);
+    }
+    __syncthreads();
+    float* red = (float*)smem;  // [BM/WM][2][BN]
+    if (lane < 32) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            red[(wm * 2 + 0) * BN + wn * WN + j * 32 + lane] = s1[j];
+            red[(wm * 2 + 1) * BN + wn * WN + j * 32 + lane] = s2[j];
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < 2 * BN; t += NT) {
+        int which = t / BN, col = t - which * BN;
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < BM / WM; ++k) v += red[(k * 2 + which) * BN + col];
+        a.stats[((long long)pslot * 2 + which) * a.stats_ld + nt * BN + col] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// BatchNorm + LeakyReLU of one raw value, and the split storage of an activation v: hi = fp16(v) saturated (never inf:
+// inf * 0 = NaN downstream), lo = fp16(v - hi) -- exact difference, one rounding; |lo| <= ulp(hi) / 2.  The activation pass
+// (bn_act.hip) and the fused 1x1 forward (bn_conv1x1.hip) share these expressions, so they produce the same bits.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ float bn_leaky(float y, float sc, float sh, float slope) {
+    const float z = y * sc + sh;
+    return z > 0.f ? z : z * slope;
+}
+__device__ __forceinline__ half_t sat_half(float v) {
+    return (half_t)fminf(fmaxf(v, -65504.f), 65504.f);
+}
+__device__ __forceinline__ void split_hi_lo(const float* v, h8_t& hi, h8_t& lo) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) hi[i] = sat_half(v[i]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) lo[i] = (half_t)(v[i] - (float)hi[i]);
+}
+
+// ---------------------------------------------------------------------------------------
 // store_raw_tile for a dgrad launch whose output is the gradient G of a PLAIN BatchNorm + LeakyReLU block (a.bsum,
 // MCAMD_EPI_RAW_F16_SUMS instances): while the tile goes out, pass 0 of that block's BatchNorm backward
 // (bn_plain_bwd_act_kernel<0>, bn_act.hip) is taken on it -- per producer channel sum g_z and sum g_z xhat, from G AS

@@ -212,26 +212,7 @@ void igemm_kernel(IgemmArgs a) {
                     }
                 }
         } else if constexpr (EPI == MCAMD_EPI_RAW_F32) {
-            // unrounded accumulators, fp32 [M][y_ld]: a store instruction writes two rows x 32 consecutive floats
-            // (whole 128-byte lines straight from the registers); BN partial sums from the same fp32 values
-            float* y = (float*)a.y;
-            const int mlim = a.M - mt * BM;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = nt * BN + wn * WN + j * 32 + (lane & 31);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = wm * WM + i * 32 + mfma32_row(r, lane);
-                        const float v = acc[i][j][r];
-                        if (row < mlim) {
-                            if (n < a.N) y[(long long)(mt * BM + row) * a.y_ld + a.y_choff + n] = v;
-                            s1[j] += v;
-                            s2[j] += v * v;
-                        }
-                    }
-            }
+            store_raw32_tile<BM, BN, WM, WN>(a, acc, mt, nt, wm, wn, lane, s1, s2);
         } else {
             h8_t aq[SUMS ? sums_early(BM, BN, NT) : 1];   // the producer's activation pieces: in flight while the tile is transposed
             if constexpr (SUMS) sums_prefetch<BM, BN, NT>(a, mt, nt, tid, aq);
@@ -278,30 +259,8 @@ void igemm_kernel(IgemmArgs a) {
 
     if (sat && a.overflow) atomicOr(a.overflow, 1);
     if constexpr (SUMS) store_tile_sums_slab<BN, NT>(a, pslot, nt, tid, tot);
-    if ((EPI == MCAMD_EPI_RAW_F16 || EPI == MCAMD_EPI_RAW_F32) && a.stats) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            s1[j] += __shfl_xor(s1[j], 32);
-            s2[j] += __shfl_xor(s2[j], 32);
-        }
-        __syncthreads();
-        float* red = (float*)smem;  // [BM/WM][2][BN]
-        if (lane < 32) {
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                red[(wm * 2 + 0) * BN + wn * WN + j * 32 + lane] = s1[j];
-                red[(wm * 2 + 1) * BN + wn * WN + j * 32 + lane] = s2[j];
-            }
-        }
-        __syncthreads();
-        for (int t = tid; t < 2 * BN; t += NT) {
-            int which = t / BN, col = t - which * BN;
-            float v = 0.f;
-#pragma unroll
-            for (int k = 0; k < BM / WM; ++k) v += red[(k * 2 + which) * BN + col];
-            a.stats[((long long)pslot * 2 + which) * a.stats_ld + nt * BN + col] = v;
-        }
-    }
+    if ((EPI == MCAMD_EPI_RAW_F16 || EPI == MCAMD_EPI_RAW_F32) && a.stats)
+        store_stats_slab<BM, BN, WM, WN, NT>(a, smem, s1, s2, pslot, nt, wm, wn, lane, tid);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -174,6 +174,12 @@ int mcamd_small3x3_launch(const IgemmArgs& a, int rows, hipStream_t st);
 bool mcamd_small3x3_split_ok(long long M, int n, int cin_tap, int ktot, int wrap, int mode);   // split operands, fp32 output
 int mcamd_small3x3_split_launch(const IgemmArgs& a, int rows, hipStream_t st);
 
+// bn_conv1x1.hip: a PLAIN block's BatchNorm + LeakyReLU fused into the split-operand 1x1 forward behind it.  Not a route of
+// conv_route(): its own entry point (mcamd_bn_act_conv1x1_fwd).  `a` as for the consumer's igemm launch + the producer's
+// scale / shift / slope; py = the producer's fp32 raw output, P its channels
+bool mcamd_bn_conv1x1_shape_ok(int P, int cout);
+int mcamd_bn_conv1x1_launch(IgemmArgs& a, const float* py, int py_ld, int py_choff, int P, int rows, hipStream_t st);
+
 bool mcamd_wres_ok(int ksize, int stem, int n, int cin_tap, int ktot, int B, int H, int W, int mode);   // conv_wres.hip
 int mcamd_wres_rows(int n, int B, int H, int W);
 int mcamd_wres_launch(IgemmArgs& a, int B, int rows, hipStream_t st);

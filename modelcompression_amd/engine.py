@@ -203,6 +203,12 @@ class Engine:
         # ... and the sums of a PLAIN block's BatchNorm backward in the epilogue of the dgrad launch that stores its G
         # (mcamd_conv_dgrad_sums; MCAMD_DGRAD_BN_SUMS=0: the two-pass mcamd_bn_act_bwd everywhere)
         self.dgrad_bn_sums = os.environ.get("MCAMD_DGRAD_BN_SUMS", "1") == "1"
+        # ... and a PLAIN block's BatchNorm + LeakyReLU inside the forward launch of the split-operand 1x1 block behind it
+        # (mcamd_bn_act_conv1x1_fwd, _fused_1x1; MCAMD_FUSE_BN_1X1=0: activation pass + forward launch).  The counter says how
+        # many such launches the layer walk has issued (recorded ones count once, when the plan is recorded).
+        self.fuse_bn_1x1 = os.environ.get("MCAMD_FUSE_BN_1X1", "1") == "1"
+        self.fused_1x1_launches = 0
+        self._fused_1x1_cache = {}
         self._dgrad_sums_cache = {}
         self._side_stream = None
         self._side_concurrent = True
@@ -1387,6 +1393,7 @@ class Engine:
         """The layer walk of the forward pass: library calls only (every one of them recordable)."""
         B = self.B
         out = self._logits
+        fused_done = set()      # blocks whose forward launch ran inside their producer's (_fused_1x1)
         for lay in self.layers:
             xin = self.bufs[lay.tin.buf]
             if lay.li == 1 and side is not None:
@@ -1421,7 +1428,7 @@ class Engine:
             if self.precise:
                 # unrounded fp32 raw output (+ batch statistics from the fp32 values), then BN + LeakyReLU
                 # (+ pool / reorg / route) written as hi | lo | hi planes
-                if not lay.stem_f32:        # (the fp32 first convolution ran in forward(), from the caller's image)
+                if not lay.stem_f32 and lay.li not in fused_done:   # (the fp32 first convolution ran in forward(), from the caller's image)
                     self._timed('fwd', lay, ops.conv_fwd_raw32, lay.geom_f, xin, lay.wp, lay.y, lay.cout, 0,
                                 lay.stats if training else None)
                 ops.bn_coeffs(lay.stats if training else None, lay.cout, lay.M, bn.weight.data, bn.bias.data,
@@ -1429,6 +1436,14 @@ class Engine:
                               momentum=bn.momentum if bn.momentum is not None else 0.1, eps=bn.eps, perm=lay.perm32,
                               ones_channel=lay.ones_idx)
                 t, t2 = lay.out_t, lay.out2_t
+                cons = self._fused_1x1(lay)
+                if cons is not None:
+                    # the activation goes straight into the 1x1 forward behind this block: only its hi plane is stored
+                    self._timed('fwd', cons, ops.bn_act_conv1x1_fwd, *self._fused_1x1_act(lay), cons.geom_f, cons.wp, cons.y,
+                                cons.cout, 0, cons.stats if training else None)
+                    fused_done.add(cons.li)
+                    self.fused_1x1_launches += 1
+                    continue
                 af = getattr(lay, "act_full", None) if (training and self.pool_act_on) else None
                 ops.bn_act_fwd(B, lay.H, lay.W, lay.bn_width or lay.cout, lay.y, lay.cout, 0, lay.scale, lay.shift,
                                lay.slope, lay.mode, self.bufs[t.buf], t.ld, t.choff,
@@ -1500,6 +1515,47 @@ class Engine:
                            self.bufs[t2.buf] if t2 is not None else None,
                            t2.ld if t2 is not None else 0, t2.choff if t2 is not None else 0, border=lay.border,
                            dst_pad=self._pad_for(t.W), dst2_pad=self._pad_for(t2.W) if t2 is not None else 0)
+
+    def _fused_1x1_act(self, lay):
+        """(positional, keyword) arguments of the activation pass of the PLAIN block `lay` in hi | lo storage, as
+        ops.bn_act_fwd takes them."""
+        t = lay.out_t
+        return ((self.B, lay.H, lay.W, lay.cout, lay.y, lay.cout, 0, lay.scale, lay.shift, lay.slope, lay.mode,
+                 self.bufs[t.buf], t.ld, t.choff),
+                dict(planes=self._planes_for(lay.out_id), dst_plane=t.ps, dst_pad=self._pad_for(t.W)))
+
+    def _fused_1x1(self, lay):
+        """The block whose forward launch takes the BatchNorm + LeakyReLU of block `lay` (ops.bn_act_conv1x1_fwd), or None.
+        `lay` must be a PLAIN block of a split-operand engine with one destination and none of keep / perm / fold /
+        fold_consumers / a narrowed BatchNorm pass / a border table; its one consumer a BatchNorm 1x1 block on three fp16
+        operand terms (level 3, no fp8 correction form) that runs its dense geometry (no fold / gather / in_perm) on exactly
+        the producer's channel slice; and the library must have a kernel for the pair (mcamd_bn_act_conv1x1_ok)."""
+        if not (self.fuse_bn_1x1 and self.precise):
+            return None
+        key = (lay.li, self._plan_epoch)
+        hit = self._fused_1x1_cache.get(key, False)
+        if hit is not False:
+            return hit
+        res = None
+        cons = self.consumer_of.get(lay.out_id)
+        t = lay.out_t
+        if (cons is not None and t is not None and lay.mode == L.DST_PLAIN and lay.out2_id is None and lay.out2_t is None
+                and not lay.stem and not lay.fused_stem and not lay.stem_split and not lay.stem_f32
+                and lay.keep is None and lay.perm is None and lay.fold is None and not lay.fold_consumers and not lay.bn_width
+                and not lay.skip_dead and lay.ones_idx < 0 and lay.border is None
+                and lay.y is not None and lay.y.dtype == torch.float32
+                and cons.bn is not None and not cons.is_last and cons.k == 1 and cons.level == 3 and not cons.f8
+                and cons.fold is None and not cons.gather and cons.in_perm is None and cons.geom_act is cons.geom
+                and cons.src == lay.out_id
+                and cons.tin.buf == t.buf and cons.tin.ld == t.ld and cons.tin.choff == t.choff and cons.cin == lay.cout
+                and cons.y is not None and cons.y.dtype == torch.float32):
+            args, kw = self._fused_1x1_act(lay)
+            d = ops.act_geom(self.B, lay.H, lay.W, lay.cout, lay.cout, 0, lay.slope, lay.mode, t.ld, t.choff, **kw)
+            if ops.bn_act_conv1x1_ok(d, cons.geom_f):
+                res = cons
+        self._fused_1x1_cache = {k: v for k, v in self._fused_1x1_cache.items() if k[1] == self._plan_epoch}
+        self._fused_1x1_cache[key] = res
+        return res
 
     def _qat_forward(self, lay, xin):
         """Training-mode forward of an fp8 block ("fp8-qat"): the fp8 convolution's fp32 raw output and its

@@ -369,16 +369,10 @@ def unfold_wgrad(w, mask, rows, cols, beta, slope, n, cin_k, dwaug, dw, prod_dbe
                                      stream_ptr()), "mcamd_unfold_wgrad")
 
 
-def bn_act_fwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, dst_ld, dst_choff=0, dst2=None,
-               dst2_ld=0, dst2_choff=0, border=None, planes=1, dst_plane=0, dst2_plane=0, dst_pad=0, dst2_pad=0, planes2=0,
-               pool_act=None, pool_act_ld=0, pool_act_pad=0, dst_q8=None, dst2_q8=None):
-    """`dst_q8` / `dst2_q8`: byte twins of dst / dst2 (same geometry) that receive the e4m3 codes q(2 v) while the fp16
-    buffer receives deq(code) / 2 (mcamd_act_desc.dst_q8: the fp8 quantisation-aware training forward; fp32 y, planes 1).
-    `border`: optional fp32 [16, C] table added to the raw conv output by border class (slim models).
-    `pool_act` (mode pool): padded fp16 buffer that receives the full-resolution activation for the block's backward pass
-    (mcamd_act_desc.pool_act; bn_act_bwd(..., act=pool_act)).
-    `y` may be fp16 or fp32 (conv_fwd_raw / conv_fwd_raw32).  planes=3: split (hi | lo | hi) activation storage of
-    the "fp16x3" precision mode with plane strides dst_plane / dst2_plane (include/mcamd.h, mcamd_act_desc.planes)."""
+def _act_desc(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, dst_ld, dst_choff=0, dst2=None,
+              dst2_ld=0, dst2_choff=0, border=None, planes=1, dst_plane=0, dst2_plane=0, dst_pad=0, dst2_pad=0, planes2=0,
+              pool_act=None, pool_act_ld=0, pool_act_pad=0, dst_q8=None, dst2_q8=None):
+    """mcamd_act_desc of bn_act_fwd's arguments."""
     d = ActDesc()
     d.y_dtype = 1 if y.dtype == torch.float32 else 0
     d.planes, d.dst_plane, d.dst2_plane, d.planes2 = planes, dst_plane, dst2_plane, planes2
@@ -397,7 +391,57 @@ def bn_act_fwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, ds
         d.pool_act, d.pool_act_ld, d.pool_act_pad = pool_act.data_ptr(), pool_act_ld, pool_act_pad
     d.dst_q8 = dst_q8.data_ptr() if dst_q8 is not None else None
     d.dst2_q8 = dst2_q8.data_ptr() if dst2_q8 is not None else None
+    return d
+
+
+def bn_act_fwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, dst_ld, dst_choff=0, dst2=None,
+               dst2_ld=0, dst2_choff=0, border=None, planes=1, dst_plane=0, dst2_plane=0, dst_pad=0, dst2_pad=0, planes2=0,
+               pool_act=None, pool_act_ld=0, pool_act_pad=0, dst_q8=None, dst2_q8=None):
+    """`dst_q8` / `dst2_q8`: byte twins of dst / dst2 (same geometry) that receive the e4m3 codes q(2 v) while the fp16
+    buffer receives deq(code) / 2 (mcamd_act_desc.dst_q8: the fp8 quantisation-aware training forward; fp32 y, planes 1).
+    `border`: optional fp32 [16, C] table added to the raw conv output by border class (slim models).
+    `pool_act` (mode pool): padded fp16 buffer that receives the full-resolution activation for the block's backward pass
+    (mcamd_act_desc.pool_act; bn_act_bwd(..., act=pool_act)).
+    `y` may be fp16 or fp32 (conv_fwd_raw / conv_fwd_raw32).  planes=3: split (hi | lo | hi) activation storage of
+    the "fp16x3" precision mode with plane strides dst_plane / dst2_plane (include/mcamd.h, mcamd_act_desc.planes)."""
+    d = _act_desc(**locals())
     check(L.lib().mcamd_bn_act_fwd(C.byref(d), stream_ptr()), "mcamd_bn_act_fwd")
+
+
+class _NoPtr:
+    """Stands for a device buffer where only the geometry is asked (bn_act_conv1x1_ok needs no GPU)."""
+    dtype = torch.float32
+
+    @staticmethod
+    def data_ptr():
+        return None
+
+
+def act_geom(B, H, W, C_, y_ld, y_choff, slope, mode, dst_ld, dst_choff=0, **kw):
+    """The geometry half of bn_act_fwd's arguments as a descriptor without pointers (fp32 y): for bn_act_conv1x1_ok."""
+    return _act_desc(B, H, W, C_, _NoPtr, y_ld, y_choff, _NoPtr, _NoPtr, slope, mode, _NoPtr, dst_ld, dst_choff, **kw)
+
+
+def bn_act_conv1x1_ok(d, g):
+    """Whether the activation pass `d` (act_geom(...) / the arguments of bn_act_fwd) and the 1x1 forward `g` behind it have
+    a fused launch (mcamd_bn_act_conv1x1_ok: host logic only)."""
+    return bool(L.lib().mcamd_bn_act_conv1x1_ok(C.byref(d), C.byref(g)))
+
+
+def bn_act_conv1x1_stats_rows(d, g):
+    """Rows of the statistics slab bn_act_conv1x1_fwd writes (0 when the pair is refused)."""
+    return int(L.lib().mcamd_bn_act_conv1x1_stats_rows(C.byref(d), C.byref(g)))
+
+
+def bn_act_conv1x1_fwd(act_args, act_kw, g, wp, y, y_ld, y_choff=0, stats=None):
+    """bn_act_fwd(*act_args, **act_kw) and conv_fwd_raw32(g, dst, wp, y, y_ld, y_choff, stats) in one launch
+    (mcamd_bn_act_conv1x1_fwd): bit-equal y and stats; of the activation only the hi plane is stored."""
+    d = _act_desc(*act_args, **act_kw)
+    e = _epi(L.EPI_RAW_F32, y, y_ld, y_choff, stats=stats,
+             stats_rows_=stats.shape[0] if stats is not None else 0,
+             stats_ld=stats.shape[2] if stats is not None else 0)
+    check(L.lib().mcamd_bn_act_conv1x1_fwd(C.byref(d), C.byref(g), ptr(wp), C.byref(e), stream_ptr()),
+          "mcamd_bn_act_conv1x1_fwd")
 
 
 def bn_act_bwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, mean, invstd, slope, mode, g, g_ld, g_choff, dy, dy_ld,
