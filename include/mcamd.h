@@ -804,6 +804,30 @@ int mcamd_region_loss(const mcamd_region_desc* d, float* loss, float* grad, int3
                       size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Objectness-scaled distillation loss of a YOLOv2 head against a frozen teacher's logits (Mehta and Ozturk, "Object
+ * detection at 200 FPS"; Chen et al., NeurIPS 2017): loss AND d(loss)/d(student) in one pass, no gradient for the teacher.
+ *   student, teacher : fp32 [B][num_anchors * (5 + num_classes)][H][W] -- what Darknet.forward returns; per prediction
+ *                      (x, y, w, h, obj, classes) with student values s_k and teacher values t_k:
+ *     q   = sig(t_4)                                        (a weight, never differentiated)
+ *     L_o = 1/2 (sig(s_4) - q)^2
+ *     L_b = 1/2 [(sig(s_0) - sig(t_0))^2 + (sig(s_1) - sig(t_1))^2 + (s_2 - t_2)^2 + (s_3 - t_3)^2]
+ *     L_c = temperature^2 * KL(softmax(t_5.. / temperature) || softmax(s_5.. / temperature))
+ *     loss = 1/B sum [obj_scale L_o + q (box_scale L_b + cls_scale L_c)]
+ *   loss : device fp32 scalar;  grad : device fp32, shaped like student: d(loss)/d(student)
+ *   workspace : mcamd_distill_loss_workspace_bytes(B, num_anchors) bytes, one partial sum per (image, anchor)
+ * Deterministic (no atomics); bit-equal operands give loss == 0 and grad == 0 exactly; a NaN or Inf logit in either
+ * operand gives a non-finite loss.  num_anchors in [1, 8], num_classes >= 1, temperature > 0.
+ * ------------------------------------------------------------------------- */
+typedef struct mcamd_distill_desc {
+    const float* student; const float* teacher;
+    int32_t B, H, W, num_anchors, num_classes;
+    float obj_scale, box_scale, cls_scale, temperature;
+} mcamd_distill_desc;
+size_t mcamd_distill_loss_workspace_bytes(int32_t B, int32_t num_anchors);
+int mcamd_distill_loss(const mcamd_distill_desc* d, float* loss, float* grad, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Detection post-processing of the eval path (reference src/nets2_utils.py:141-259 get_region_boxes + nms, chained as
  * predict.py:148-173 does).  N = H * W * num_anchors rows per image in the reference's (cy, cx, anchor) order,
  * N <= 2048, num_anchors <= 8, num_classes <= 80; anything else returns MCAMD_EINVAL and launches nothing.

@@ -112,6 +112,13 @@ class RegionDesc(C.Structure):
                 ("class_scale", C.c_float), ("thresh", C.c_float)]
 
 
+class DistillDesc(C.Structure):
+    """mcamd_distill_desc (include/mcamd.h)."""
+    _fields_ = [("student", C.c_void_p), ("teacher", C.c_void_p),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("num_anchors", C.c_int32), ("num_classes", C.c_int32),
+                ("obj_scale", C.c_float), ("box_scale", C.c_float), ("cls_scale", C.c_float), ("temperature", C.c_float)]
+
+
 class DetectDesc(C.Structure):
     """mcamd_detect_desc (include/mcamd.h)."""
     _fields_ = [("output", C.c_void_p),
@@ -229,6 +236,8 @@ SIGNATURES = {
     "mcamd_stem_conv_f32": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _P, _I32, _I32, _P]),
     "mcamd_region_loss_workspace_bytes": (_SZ, [_I32]),
     "mcamd_region_loss": (C.c_int, [C.POINTER(RegionDesc), _P, _P, _P, _P, _SZ, _P]),
+    "mcamd_distill_loss_workspace_bytes": (_SZ, [_I32, _I32]),
+    "mcamd_distill_loss": (C.c_int, [C.POINTER(DistillDesc), _P, _P, _P, _SZ, _P]),
     "mcamd_region_decode": (C.c_int, [C.POINTER(DetectDesc), _P, _P, _P]),
     "mcamd_nms": (C.c_int, [_P, _P, _I32, _I32, _F, _P, _P, _P]),
     "mcamd_detect": (C.c_int, [C.POINTER(DetectDesc), _P, _P, _P, _P, _P, _P]),

@@ -38,6 +38,7 @@ SOURCES = {
     "fold.hip": [],
     "plan.hip": [],
     "region_loss.hip": [],
+    "distill_loss.hip": [],
     "prune.hip": ["-ffp-contract=off"],   # pinned fp32 arithmetic: no FMA contraction
     "augment.hip": ["-ffp-contract=off"], # Pillow's float / double HSV arithmetic, operation by operation
     "detect.hip": ["-ffp-contract=off"],  # suppression decisions are pinned fp32 comparisons; one decode, bit for bit

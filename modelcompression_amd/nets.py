@@ -61,47 +61,67 @@ def parse_cfg(cfgfile, verbose=0):
     return blocks
 
 
-def print_cfg(blocks):
-    """Layer table like nets.py:75-190 (index, type, filters, size, input -> output)."""
-    print('layer     filters    size              input                output')
+def cfg_shapes(blocks):
+    """(input w, h, channels, output w, h, channels) of every non-[net] block of a parsed cfg, by the rules of the layer
+    table (nets.py:75-190): the one place that walks a cfg's geometry (print_cfg, train's teacher check)."""
     prev_w = prev_h = prev_f = 0
-    out_f, out_w, out_h = [], [], []
-    ind = -2
+    shapes = []
     for block in blocks:
-        ind += 1
         t = block['type']
         if t == 'net':
             prev_w, prev_h, prev_f = int(block['width']), int(block['height']), int(block['channels'])
             continue
+        ind = len(shapes)
+        w, h, f = prev_w, prev_h, prev_f
         if t == 'convolutional':
             f, k, s = int(block['filters']), int(block['size']), int(block['stride'])
             pad = (k - 1) // 2 if int(block['pad']) else 0
             w, h = (prev_w + 2 * pad - k) // s + 1, (prev_h + 2 * pad - k) // s + 1
-            print('%5d %-6s %4d  %d x %d / %d   %3d x %3d x%4d   ->   %3d x %3d x%4d' % (
-                ind, 'conv', f, k, k, s, prev_w, prev_h, prev_f, w, h, f))
-            prev_w, prev_h, prev_f = w, h, f
         elif t == 'maxpool':
-            k, s = int(block['size']), int(block['stride'])
+            s = int(block['stride'])
             w, h = prev_w // s, prev_h // s
-            print('%5d %-6s       %d x %d / %d   %3d x %3d x%4d   ->   %3d x %3d x%4d' % (
-                ind, 'max', k, k, s, prev_w, prev_h, prev_f, w, h, prev_f))
-            prev_w, prev_h = w, h
         elif t == 'reorg':
             s = int(block['stride'])
             f, w, h = s * s * prev_f, prev_w // s, prev_h // s
+        elif t == 'route':
+            layers = [int(i) if int(i) > 0 else int(i) + ind for i in block['layers'].split(',')]
+            prev_w, prev_h = w, h = shapes[layers[0]][3], shapes[layers[0]][4]
+            prev_f = f = sum(shapes[l][5] for l in layers)
+        shapes.append((prev_w, prev_h, prev_f, w, h, f))
+        prev_w, prev_h, prev_f = w, h, f
+    return shapes
+
+
+def print_cfg(blocks):
+    """Layer table like nets.py:75-190 (index, type, filters, size, input -> output)."""
+    print('layer     filters    size              input                output')
+    shapes = cfg_shapes(blocks)
+    ind = -1
+    for block in blocks:
+        t = block['type']
+        if t == 'net':
+            continue
+        ind += 1
+        prev_w, prev_h, prev_f, w, h, f = shapes[ind]
+        if t == 'convolutional':
+            k, s = int(block['size']), int(block['stride'])
+            print('%5d %-6s %4d  %d x %d / %d   %3d x %3d x%4d   ->   %3d x %3d x%4d' % (
+                ind, 'conv', f, k, k, s, prev_w, prev_h, prev_f, w, h, f))
+        elif t == 'maxpool':
+            k, s = int(block['size']), int(block['stride'])
+            print('%5d %-6s       %d x %d / %d   %3d x %3d x%4d   ->   %3d x %3d x%4d' % (
+                ind, 'max', k, k, s, prev_w, prev_h, prev_f, w, h, prev_f))
+        elif t == 'reorg':
+            s = int(block['stride'])
             print('%5d %-6s              / %d   %3d x %3d x%4d   ->   %3d x %3d x%4d' % (
                 ind, 'reorg', s, prev_w, prev_h, prev_f, w, h, f))
-            prev_w, prev_h, prev_f = w, h, f
         elif t == 'route':
             layers = [int(i) if int(i) > 0 else int(i) + ind for i in block['layers'].split(',')]
             print('%5d %-6s %s' % (ind, 'route', ' '.join(str(l) for l in layers)))
-            prev_w, prev_h = out_w[layers[0]], out_h[layers[0]]
-            prev_f = sum(out_f[l] for l in layers)
         elif t == 'region':
             print('%5d %-6s' % (ind, 'detection'))
         else:
             print('unknown type %s' % t)
-        out_f.append(prev_f), out_w.append(prev_w), out_h.append(prev_h)
 
 
 # ----------------------------------------------------------------------------- weight files

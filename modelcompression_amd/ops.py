@@ -648,6 +648,31 @@ def region_loss(output, target, anchors, num_anchors, num_classes, coord_scale, 
     return loss, grad, counts
 
 
+def distill_loss(student, teacher, num_anchors, num_classes, obj_scale=1.0, box_scale=1.0, cls_scale=1.0, temperature=1.0):
+    """(loss, grad): the objectness-scaled distillation loss of the student's logits against the teacher's (0-dim fp32
+    tensor) and d(loss)/d(student), in one library call (include/mcamd.h, mcamd_distill_desc; csrc/distill_loss.hip)."""
+    if student.device != teacher.device:
+        raise L.McamdError("distill_loss: student on %s, teacher on %s" % (student.device, teacher.device))
+    _need_cuda(student, teacher)
+    if tuple(student.shape) != tuple(teacher.shape) or student.dim() != 4:
+        raise L.McamdError("distill_loss: student logits %s, teacher logits %s: both must be one [B, A*(5+C), H, W] shape"
+                           % (tuple(student.shape), tuple(teacher.shape)))
+    B, ch, H, W = student.shape
+    if ch != num_anchors * (5 + num_classes):
+        raise L.McamdError("distill_loss: %d channels, expected %d anchors x (5 + %d classes)" % (ch, num_anchors, num_classes))
+    s = student.detach().contiguous().float()
+    t = teacher.detach().contiguous().float()
+    d = L.DistillDesc()
+    d.student, d.teacher = s.data_ptr(), t.data_ptr()
+    d.B, d.H, d.W, d.num_anchors, d.num_classes = B, H, W, num_anchors, num_classes
+    d.obj_scale, d.box_scale, d.cls_scale, d.temperature = float(obj_scale), float(box_scale), float(cls_scale), float(temperature)
+    loss = torch.empty((), dtype=torch.float32, device=s.device)
+    grad = torch.empty_like(s)
+    ws = torch.empty(int(L.lib().mcamd_distill_loss_workspace_bytes(B, num_anchors)), dtype=torch.uint8, device=s.device)
+    check(L.lib().mcamd_distill_loss(C.byref(d), ptr(loss), ptr(grad), ptr(ws), ws.numel(), stream_ptr()), "mcamd_distill_loss")
+    return loss, grad
+
+
 # ------------------------------------------------------------------ detection post-processing (csrc/detect.hip)
 DETECT_MAX_ROWS = 2048      # rows (cells x anchors) per image the kernels hold in LDS
 

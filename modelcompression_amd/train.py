@@ -19,6 +19,14 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
   * RESIDENT=True decodes the train list once into device memory (data.ResidentImages; every rank keeps the whole
     set) and trains from it with no loader workers: data.ResidentAugment with AUGMENT, data.ResidentList without;
     with EVAL the evaluation pictures are made resident once, for every epoch's predict.  Off by default.
+  * TEACHER adds knowledge distillation to the retraining (distill.py): True = a frozen copy of the model as loaded, taken
+    before pruning (the common case: `pruning_perc=80, TEACHER=True`), a path = a Darknet of MODEL_CFG with those weights,
+    or a Darknet of the caller's (its own cfg and eval `precision`; that object itself is used: it is moved to the
+    device, put in eval mode and frozen with requires_grad_(False), in place).  Anything else, False included, raises.
+    The teacher stays in eval mode without masks,
+    optimizer entry or gradient hook; every step runs its forward under no_grad in front of the student's and adds
+    DISTILL(output, teacher_output) -- a distill.DistillLoss, by default DistillLoss.from_model(model) -- to the region
+    loss.  Off by default: the same launches and results as without the keywords.
 """
 import os
 
@@ -32,9 +40,10 @@ import torch.optim as optim  # noqa: E402
 
 from . import dp  # noqa: E402
 from .augment import DeviceAugmenter, collate_fn  # noqa: E402
+from .distill import DistillLoss  # noqa: E402
 from .data import (VOCList, SyntheticDetection, VOCAugment, SyntheticAugment, ResidentImages, ResidentAugment,  # noqa: E402
                    ResidentList, label_path_for, read_boxes)
-from .nets import Darknet, parse_cfg  # noqa: E402
+from .nets import Darknet, cfg_shapes, parse_cfg  # noqa: E402
 from .pruning.weightPruning.methods import quick_filter_prune, weight_prune  # noqa: E402
 from .pruning.weightPruning.utils import prune_rate, are_masks_consistent  # noqa: E402
 
@@ -46,6 +55,11 @@ def logging(message):
 def file_lines(thefilepath):
     with open(thefilepath, 'rb') as f:
         return sum(buf.count(b'\n') for buf in iter(lambda: f.read(1 << 20), b''))
+
+
+def _logit_grid(model):
+    """(width, height) of the grid a Darknet maps its cfg's input size to, from the cfg alone (no forward)."""
+    return cfg_shapes(model.blocks)[-1][3:5]
 
 
 class StepGuard:
@@ -184,12 +198,17 @@ class YOLOv2Train():
         self.init_width = ''
         self.init_height = ''
         self.batch_size = ''
+        self.teacher = None       # train(TEACHER=...): the frozen Darknet and the distill.DistillLoss of the last call
+        self.distill = None
 
     def train(self, PASCAL_DIR, PASCAL_TRAIN, PASCAL_VALID, TRAIN_LOGDIR, VAL_LOGDIR, VAL_OUTPUTDIR_PKL, VAL_PREFIX,
               MODEL_CFG, MODEL_WEIGHT,
               BATCH_SIZE, SAVE_INTERNAL,
               LOGGER='', DEBUG_EPOCHS=-1, verbose=0, pruning_perc=0., pruning_method="weight",
-              MAX_EPOCHS=135, SYNTHETIC_SAMPLES=256, EVAL=False, AUGMENT=False, RESIDENT=False):
+              MAX_EPOCHS=135, SYNTHETIC_SAMPLES=256, EVAL=False, AUGMENT=False, RESIDENT=False, TEACHER=None,
+              DISTILL=None):
+        if DISTILL is not None and TEACHER is None:
+            raise ValueError("train: DISTILL needs a TEACHER (True, a .weights path or a Darknet)")
         rank, world = dp.init_from_env()
         local = int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(local)
@@ -206,6 +225,7 @@ class YOLOv2Train():
             logging('weights file %r not found: seeded synthetic initialisation' % (MODEL_WEIGHT,))
         self.model = self.model.to(dev)
         dp.broadcast_parameters(self.model, src=0)
+        self.teacher, self.distill = self._make_teacher(TEACHER, DISTILL, MODEL_CFG, dev)
 
         # Step 2 - dataset
         self.trainlist, self.testlist = PASCAL_TRAIN, PASCAL_VALID
@@ -296,15 +316,23 @@ class YOLOv2Train():
             # the loss is accumulated on the device and read once per epoch; the skip policy lives in StepGuard
             train_loss_total, t0, steps_here = torch.zeros((), dtype=torch.float32, device=dev), time.time(), 0
             skipped_before = guard.skipped
+            distill_loss_total = torch.zeros((), dtype=torch.float32, device=dev) if self.teacher is not None else None
             for batch_idx, batch in enumerate(loader):
                 if DEBUG_EPOCHS > -1 and batch_idx > DEBUG_EPOCHS:
                     break
                 data, target = augmenter(batch) if augmenter is not None else batch
                 data = data.to(dev, non_blocking=True)
                 target = target.float().to(dev, non_blocking=True)
+                if self.teacher is not None:
+                    with torch.no_grad():
+                        t_out = self.teacher(data)
                 output = self.model(data)
                 region_loss.seen = region_loss.seen + data.size(0) * world
                 train_loss = region_loss(output, target)
+                if self.teacher is not None:
+                    distill_loss = self.distill(output, t_out)
+                    train_loss = train_loss + distill_loss
+                    distill_loss_total += distill_loss.detach()
                 train_loss_total += train_loss.detach()
                 optimizer.zero_grad()
                 train_loss.backward()
@@ -320,8 +348,10 @@ class YOLOv2Train():
             seen_here = (steps_here - (guard.skipped - skipped_before)) * per_rank * world
             train_loss_total = float(train_loss_total)
             if rank == 0:
-                logging('training with %f samples/s, mean loss %.4f' % (seen_here / max(time.time() - t0, 1e-9),
-                                                                         train_loss_total / max(len(loader), 1)))
+                logging('training with %f samples/s, mean loss %.4f%s' % (
+                    seen_here / max(time.time() - t0, 1e-9), train_loss_total / max(len(loader), 1),
+                    '' if distill_loss_total is None else
+                    ', of it distillation %.4f' % (float(distill_loss_total) / max(len(loader), 1))))
             dp.sync_buffers(self.model)     # BatchNorm running statistics are rank-local: average before checkpoint / eval
             if pruning_perc > 0 and rank == 0:
                 print(' pruned: %s' % prune_rate(self.model, False))
@@ -342,6 +372,40 @@ class YOLOv2Train():
             logging('save weights to %s' % name)
             self.model.save_weights(name)
         return self.model
+
+    def _make_teacher(self, TEACHER, DISTILL, MODEL_CFG, dev):
+        """(teacher, loss) of the TEACHER / DISTILL keywords, (None, None) without a teacher.  Called after the model is
+        loaded and broadcast and BEFORE pruning: TEACHER=True freezes the weights the student starts from."""
+        if TEACHER is None:
+            return None, None
+        if isinstance(TEACHER, Darknet):
+            teacher = TEACHER.to(dev)
+        else:
+            # a fresh Darknet, not copy.deepcopy: a Darknet carries engines with device pointers
+            teacher = Darknet(MODEL_CFG)
+            if TEACHER is True:
+                teacher.load_state_dict(self.model.state_dict())
+            elif isinstance(TEACHER, (str, os.PathLike)) and os.path.exists(TEACHER):
+                teacher.load_weights(os.fspath(TEACHER))
+            else:
+                raise ValueError("train: TEACHER must be True, an existing .weights file or a Darknet, got %r" % (TEACHER,))
+            teacher = teacher.to(dev)
+        teacher.eval()
+        teacher.requires_grad_(False)
+        distill = DistillLoss.from_model(self.model) if DISTILL is None else DISTILL
+        if not isinstance(distill, DistillLoss):
+            raise ValueError("train: DISTILL must be a distill.DistillLoss, got %r" % (DISTILL,))
+        head = (self.model.num_anchors, self.model.num_classes)
+        if (teacher.num_anchors, teacher.num_classes) != head or (distill.num_anchors, distill.num_classes) != head:
+            raise ValueError("train: the student's region layer has %d anchors x %d classes, the teacher's %d x %d, the "
+                             "distillation loss %d x %d" % (head + (teacher.num_anchors, teacher.num_classes,
+                                                                    distill.num_anchors, distill.num_classes)))
+        shapes = [_logit_grid(m) for m in (self.model, teacher)]
+        if shapes[0] != shapes[1] or (self.model.width, self.model.height) != (teacher.width, teacher.height):
+            raise ValueError("train: the student maps %dx%d pictures to a %dx%d grid, the teacher %dx%d to %dx%d"
+                             % (self.model.width, self.model.height, shapes[0][0], shapes[0][1],
+                                teacher.width, teacher.height, shapes[1][0], shapes[1][1]))
+        return teacher, distill.to(dev)
 
     def adjust_learning_rate(self, optimizer, batch, learning_rate, steps, scales, batch_size):
         """train.py:277-290 (never called by the reference's loop either)."""
