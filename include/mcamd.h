@@ -1043,6 +1043,79 @@ int mcamd_nm_mask(const float* w, const float* old_mask, int32_t cout, int32_t c
 /* number of such groups holding more than 2 non-zero mask entries, added to *count (device int32) */
 int mcamd_nm_violations(const float* mask, int32_t cout, int32_t cin, int32_t khw, int32_t* count, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Compressed model files (.mcz; an addition beyond the reference): the two device passes around the file.
+ * ------------------------------------------------------------------------- */
+/* The file (little-endian, every array zero-padded to a multiple of 8 bytes):
+ *   header   char magic[4] = "MCZW"; uint32 version = 1; uint32 payload (value kind the file was asked for);
+ *            uint32 nrec; int64 seen
+ *   record   int32 cout, cin, kh, kw; uint32 flags; uint32 0; uint64 kept;
+ *            float32 bn.bias[cout], bn.weight[cout], running_mean[cout], running_var[cout]   (MCAMD_WZ_F_BN)
+ *            or float32 conv.bias[cout];
+ *            int32 exponent[cout]                                                            (value kind MCAMD_WZ_FP8)
+ *            uint64 word[ceil(n / 64)], n = cout cin kh kw                                   (MCAMD_WZ_F_BITS)
+ *            kept values (MCAMD_WZ_F_BITS) or all n values, in flat OIHW order
+ *   flags    MCAMD_WZ_F_BN | MCAMD_WZ_F_BITS | value kind << 8
+ * Bit i of word j stands for weight 64 j + i; the tail bits of the last word are 0.  A weight is KEPT iff its stored
+ * value is non-zero: any bit outside the sign bit set in the code of weight * mask, the code being
+ *   MCAMD_WZ_FP32  the fp32 pattern,            4 bytes
+ *   MCAMD_WZ_FP16  its round-to-nearest-even fp16 pattern (what the fp16 packers store),   2 bytes
+ *   MCAMD_WZ_FP8   the e4m3 code mcamd_pack_q8 stores, with that packer's exponent per filter,   1 byte
+ * and every other weight reads back as +0.  A record has bit words iff 8 ceil(n / 64) + kept elem < n elem; otherwise
+ * all n values are stored (0 for a weight that is not kept).  Reading: fp32 as is, fp16 widened, e4m3 as
+ * value(code) 2^-exponent (exact in fp32 whenever that is a normal number). */
+#define MCAMD_WZ_FP32 0
+#define MCAMD_WZ_FP16 1
+#define MCAMD_WZ_FP8 2
+#define MCAMD_WZ_F_BN 1u
+#define MCAMD_WZ_F_BITS 2u
+#define MCAMD_WZ_BLOCK_WORDS 64 /* bit words (of 64 weights) per workgroup of both passes */
+
+/* One weight tensor of a pass.  All tensors of a model go through ONE table: a HOST array for the checks and the grid
+ * sizes and its DEVICE copy for the kernels.  Running sums over the table, in order (checked):
+ *   block0  += ceil(ceil(n / 64) / MCAMD_WZ_BLOCK_WORDS)
+ *   word0   += ceil(n / 64)     pack only
+ *   exp0    += cout             pack only, the segments of kind MCAMD_WZ_FP8
+ * Unpack reads the bit words, exponents and values where the caller has them: word0 (dense == 0), exp0 (MCAMD_WZ_FP8)
+ * and val0 are any offsets whose range lies inside the arrays given (checked).  All three arrays may be one buffer
+ * holding the file as it is, since every array of a record starts at a multiple of 8 bytes. */
+typedef struct mcamd_wz_seg {
+    void* w;         /* fp32 OIHW [cout][n / cout]: the master (pack, read) or the weights to fill (unpack, written) */
+    void* mask;      /* fp32 0/1 mask: read by pack (NULL = all ones); written by unpack unless NULL */
+    int64_t n;       /* weights, > 0, a multiple of cout */
+    int64_t word0;   /* first bit word of the segment in `words` */
+    int64_t val0;    /* unpack: byte offset of the segment's values in `values`, a multiple of 8.  pack: unused */
+    int64_t kept;    /* unpack, dense == 0: number of values stored (<= n).  pack: unused */
+    int32_t cout;
+    int32_t kind;    /* MCAMD_WZ_FP32 / _FP16 / _FP8 */
+    int32_t exp0;    /* first exponent of the segment in `exps` */
+    int32_t dense;   /* unpack: 1 = the record has no bit words, all n values are stored.  pack: unused */
+    int32_t block0;  /* first workgroup of the segment */
+    int32_t reserved;
+} mcamd_wz_seg;
+
+/* workspace of either pass for a table of `nseg` segments and `nblocks` workgroups (the final block0 sum) */
+size_t mcamd_wz_workspace_bytes(int64_t nblocks, int32_t nseg);
+
+/* Pack: for every segment the bit words (words[word0 ...]), the kept count (counts[segment], uint64), the exponents of an
+ * MCAMD_WZ_FP8 segment (exps[exp0 ...]) and the values.  The values of segment s begin at byte
+ *   base(s) = sum over t < s of round_up(bytes(t), 8),  bytes(t) = (record t has bit words ? kept : n) * elem
+ * of `values`, by the rule above -- exactly the value arrays of the file, padding included (the padding bytes are not
+ * written: zero `values` first).  values_bytes >= sum of round_up(n elem, 8) (checked).  One wave per word: the ballot of
+ * "my weight is kept" IS the word, a lane's rank is the population count of the word below the lane; positions come
+ * from a scan of the per-workgroup counts -- no atomics, the output bytes depend on the inputs only.
+ * Not recordable into a launch plan (refused while a recording is open). */
+int mcamd_wz_pack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, uint64_t* words, int64_t words_cap,
+                  uint64_t* counts, int32_t* exps, int64_t exps_cap, void* values, int64_t values_bytes, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/* Unpack: the reverse, next to the weights: w[i] = the value bit i selects (+0 where the bit is clear), mask[i] = the bit
+ * as 0.f / 1.f (all ones for a dense segment).  A bit whose position is past `kept` reads as +0 (a damaged file cannot
+ * make the pass read outside `values`; val0 + stored bytes <= values_bytes is checked).  Not recordable. */
+int mcamd_wz_unpack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, const uint64_t* words,
+                    int64_t words_cap, const int32_t* exps, int64_t exps_cap, const void* values, int64_t values_bytes,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,11 +159,21 @@ class AugmentBatch(C.Structure):
                 ("out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
 
 
+class WzSeg(C.Structure):
+    """mcamd_wz_seg (include/mcamd.h)."""
+    _fields_ = [("w", C.c_void_p), ("mask", C.c_void_p), ("n", C.c_int64), ("word0", C.c_int64), ("val0", C.c_int64),
+                ("kept", C.c_int64), ("cout", C.c_int32), ("kind", C.c_int32), ("exp0", C.c_int32), ("dense", C.c_int32),
+                ("block0", C.c_int32), ("reserved", C.c_int32)]
+
+
 EPI_RAW_F16, EPI_NCHW_F32, EPI_PAD_F16, EPI_RAW_F32 = 0, 1, 2, 3
 DST_PLAIN, DST_POOL, DST_REORG = 0, 1, 2
 WGRAD_GENERIC, WGRAD_STEM, WGRAD_WIN, WGRAD_NINE, WGRAD_NINE_WIDE = 0, 1, 2, 3, 4      # mcamd_conv_wgrad_plan_info: family
 WFIN_ROW, WFIN_VEC, WFIN_GENERIC = 0, 1, 2                                             # ... and finish kernel
 WGRAD_PLAN_INFO_N = 13
+WZ_FP32, WZ_FP16, WZ_FP8 = 0, 1, 2                                                     # mcamd_wz_seg.kind
+WZ_F_BN, WZ_F_BITS = 1, 2                                                              # record flags of a .mcz file
+WZ_BLOCK_WORDS = 64
 
 # name -> (restype, argtypes); the complete list of symbols include/mcamd.h declares.
 _P, _I32, _I64, _F, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -266,6 +276,9 @@ SIGNATURES = {
     "mcamd_masked_residual": (C.c_int, [_P, _P, _I64, _P, _P]),
     "mcamd_nm_mask": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "mcamd_nm_violations": (C.c_int, [_P, _I32, _I32, _I32, _P, _P]),
+    "mcamd_wz_workspace_bytes": (_SZ, [_I64, _I32]),
+    "mcamd_wz_pack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "mcamd_wz_unpack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -43,6 +43,7 @@ SOURCES = {
     "augment.hip": ["-ffp-contract=off"], # Pillow's float / double HSV arithmetic, operation by operation
     "detect.hip": ["-ffp-contract=off"],  # suppression decisions are pinned fp32 comparisons; one decode, bit for bit
     "voc_eval.hip": ["-ffp-contract=off"],  # voc_eval's float64 arithmetic, operation by operation
+    "wpack.hip": ["-ffp-contract=off"],   # compressed model files: the stored codes are pinned conversions of weight * mask
 }
 
 

@@ -27,6 +27,7 @@
 // bytes is the byte of the maximum; -0 sorts below +0).
 #include "kernels.h"
 #include "conv_epi.h"
+#include "q8_exp.h"
 
 // F8MFMA = false (the default): the staged bytes are converted to fp16 in registers and multiplied by
 // v_mfma_f32_32x32x16_f16, whose sum of the (exact) products is an fp32 sum -- the arithmetic of the contract, byte for
@@ -350,12 +351,7 @@ __device__ __forceinline__ void pack_q8_row(const float* __restrict__ w, const f
         __syncthreads();
     }
     amax = red[0];
-    int e = 0;
-    if (amax > 0.f) {
-        int x;
-        const float m = frexpf(amax, &x);
-        e = m <= 0.875f ? 9 - x : 8 - x;
-    }
+    const int e = q8_filter_exponent(amax);
     if (tid == 0) wexp[n] = e;
     for (int k4 = tid; k4 < kpad / 4; k4 += 256) {
         const int kp = 4 * k4;                                   // position in the packed order [cb][tap][64]
@@ -367,7 +363,7 @@ __device__ __forceinline__ void pack_q8_row(const float* __restrict__ w, const f
             v[i] = 0.f;
             if (n < cout && (!PITCH || c0 < cin)) {              // (cin % 4 == 0: all four channels or none)
                 const long long s = ((long long)n * cin + c0 + i) * ntaps + tap;
-                v[i] = fminf(fmaxf(ldexpf(w[s] * (mask ? mask[s] : 1.f), e), -448.f), 448.f);
+                v[i] = q8_weight_scaled(w[s] * (mask ? mask[s] : 1.f), e);
             }
         }
         int b = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);

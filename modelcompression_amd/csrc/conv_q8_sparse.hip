@@ -23,6 +23,7 @@
 // 8 h + (e & 7)) meet exactly the registers above.  Its products are exact and its sum is an fp32 sum: the byte contract.
 #include "kernels.h"
 #include "conv_epi.h"
+#include "q8_exp.h"
 
 typedef _Float16 h16_t __attribute__((ext_vector_type(16)));
 
@@ -252,12 +253,7 @@ __global__ __launch_bounds__(256) void pack_q8_sparse24_kernel(const float* __re
         __syncthreads();
     }
     amax = red[0];
-    int e = 0;
-    if (amax > 0.f) {
-        int x;
-        const float m = frexpf(amax, &x);
-        e = m <= 0.875f ? 9 - x : 8 - x;
-    }
+    const int e = q8_filter_exponent(amax);
     if (tid == 0) wexp[n] = e;
     for (int u = tid; u < ktot / 32; u += 256) {
         i32x4_t kept;
@@ -292,8 +288,8 @@ __global__ __launch_bounds__(256) void pack_q8_sparse24_kernel(const float* __re
                     k0 = p[0] == i ? v[i] : k0;
                     k1 = p[1] == i ? v[i] : k1;
                 }
-                kv[2 * gg] = fminf(fmaxf(ldexpf(k0, e), -448.f), 448.f);
-                kv[2 * gg + 1] = fminf(fmaxf(ldexpf(k1, e), -448.f), 448.f);
+                kv[2 * gg] = q8_weight_scaled(k0, e);
+                kv[2 * gg + 1] = q8_weight_scaled(k1, e);
                 field |= (unsigned)p[0] << (4 * g) | (unsigned)p[1] << (4 * g + 2);
             }
             int b = __builtin_amdgcn_cvt_pk_fp8_f32(kv[0], kv[1], 0, false);

@@ -462,7 +462,13 @@ class Darknet(nn.Module):
 
     def load_weights(self, weightfile):
         """nets.py:897-948: 3 x int32 major/minor/revision, `seen` as int64 when
-        major*10+minor >= 2 (both < 1000) else int32, then the conv blocks in order."""
+        major*10+minor >= 2 (both < 1000) else int32, then the conv blocks in order.
+        A file that begins with the magic of a compressed model file (compress.py) goes to load_compressed:
+        a Darknet file cannot begin with it, its first int32 is a small version number."""
+        from . import compress
+        if compress.is_compressed(weightfile):
+            compress.load_compressed(self, weightfile)
+            return
         with open(weightfile, mode='rb') as f:
             major = int(np.fromfile(f, dtype=np.int32, count=1)[0])
             minor = int(np.fromfile(f, dtype=np.int32, count=1)[0])
@@ -533,6 +539,16 @@ class Darknet(nn.Module):
                 elif block['type'] == 'connected':
                     model = self.models[ind]
                     save_fc(fp, model[0] if block['activation'] != 'linear' else model)
+
+    def save_compressed(self, outfile, payload="fp16", layers=None):
+        """Write a compressed model file (an addition beyond the reference; compress.save_compressed)."""
+        from . import compress
+        compress.save_compressed(self, outfile, payload, layers)
+
+    def load_compressed(self, weightfile, set_masks=True):
+        """Read a compressed model file; returns the kept-bit masks (compress.load_compressed)."""
+        from . import compress
+        return compress.load_compressed(self, weightfile, set_masks)
 
     def set_masks(self, masks):
         """nets.py:1053-1061: hand masks[count] to every MaskedConv2d in module order.  Like the

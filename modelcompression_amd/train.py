@@ -27,6 +27,12 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     optimizer entry or gradient hook; every step runs its forward under no_grad in front of the student's and adds
     DISTILL(output, teacher_output) -- a distill.DistillLoss, by default DistillLoss.from_model(model) -- to the region
     loss.  Off by default: the same launches and results as without the keywords.
+  * YOLOv2Train.SAVE_COMPRESSED = "fp32" / "fp16" / "fp8" (an attribute, set on the class or on the object before
+    train() is called: the signature of train() stays the reference's plus the keywords above) writes a compressed model
+    file of that payload (compress.py) beside every .weights file saved, with the extension .mcz.
+    MODEL_WEIGHT and a TEACHER path may name such a file: Darknet.load_weights recognises it, and train() resumes at the
+    epoch the file's `seen` stands for (a .weights file drops `seen`, as in the reference).  None by default: the same
+    files as before.
 """
 import os
 
@@ -189,6 +195,9 @@ class StepGuard:
 
 
 class YOLOv2Train():
+    # "fp32" / "fp16" / "fp8": train() writes a compressed model file of that payload (compress.py) beside every .weights file
+    # it saves.  An attribute, like PASCALVOCEval.fused, not a keyword: train() keeps its signature.
+    SAVE_COMPRESSED = None
 
     def __init__(self):
         self.model = ''
@@ -207,6 +216,9 @@ class YOLOv2Train():
               LOGGER='', DEBUG_EPOCHS=-1, verbose=0, pruning_perc=0., pruning_method="weight",
               MAX_EPOCHS=135, SYNTHETIC_SAMPLES=256, EVAL=False, AUGMENT=False, RESIDENT=False, TEACHER=None,
               DISTILL=None):
+        SAVE_COMPRESSED = self.SAVE_COMPRESSED
+        if SAVE_COMPRESSED not in (None, "fp32", "fp16", "fp8"):
+            raise ValueError('train: SAVE_COMPRESSED must be None, "fp32", "fp16" or "fp8", got %r' % (SAVE_COMPRESSED,))
         if DISTILL is not None and TEACHER is None:
             raise ValueError("train: DISTILL needs a TEACHER (True, a .weights path or a Darknet)")
         rank, world = dp.init_from_env()
@@ -360,6 +372,7 @@ class YOLOv2Train():
                     name = '%s/%s-pruned-%s-retrained_%06d.weights' % (TRAIN_LOGDIR, pruning_method, pruning_perc, epoch + 1)
                     logging('save weights to %s' % name)
                     self.model.save_weights(name)
+                    self._save_compressed(name, SAVE_COMPRESSED)
             if LOGGER != '' and rank == 0:
                 LOGGER.save_value('Total Loss', 'Train Loss', epoch + 1, train_loss_total / max(len(loader), 1))
             self.model.seen = (epoch + 1) * nsamples
@@ -371,7 +384,16 @@ class YOLOv2Train():
             name = '%s/%s-pruned-%s-retrained-final_%06d.weights' % (TRAIN_LOGDIR, pruning_method, pruning_perc, epoch + 1)
             logging('save weights to %s' % name)
             self.model.save_weights(name)
+            self._save_compressed(name, SAVE_COMPRESSED)
         return self.model
+
+    def _save_compressed(self, weights_name, payload):
+        """YOLOv2Train.SAVE_COMPRESSED = payload: the compressed model file (compress.py) beside a .weights file just saved."""
+        if payload is None:
+            return
+        name = os.path.splitext(weights_name)[0] + '.mcz'
+        logging('save compressed weights (%s) to %s' % (payload, name))
+        self.model.save_compressed(name, payload)
 
     def _make_teacher(self, TEACHER, DISTILL, MODEL_CFG, dev):
         """(teacher, loss) of the TEACHER / DISTILL keywords, (None, None) without a teacher.  Called after the model is

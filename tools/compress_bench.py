@@ -1,0 +1,107 @@
+"""Compressed model files (modelcompression_amd/compress.py) of a seeded YOLOv2-VOC: bytes on disk and the
+time to write and read them.
+
+  bytes  for the dense model, weight_prune(80) and nm_prune, and each payload (fp32, fp16, fp8 with the default layers):
+         the size of the .mcz file and its ratio against the dense float32 .weights file.  Exact, not timed: the sizes follow
+         from the kept counts.
+  time   on the weight_prune(80) model, fp16 payload: save_compressed against save_weights, and load-to-device
+         (a fresh Darknet on the device + load_compressed, the device expanding the file's bytes) against the Darknet path
+         (load_weights on the host + .to(device)).  The four legs alternate in one process, ROUNDS rounds after one warm-up
+         round; every sample is wall time around the call with a device synchronise on both sides, files in a temporary
+         directory (page cache warm for every leg alike).  Quoted: the median of the samples and their spread.
+
+usage: python tools/compress_bench.py [--json]
+--json writes the result to profiles/compress_bench.json."""
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+JSON_PATH = os.path.join(ROOT, "profiles", "compress_bench.json")
+ROUNDS = 5
+PAYLOADS = ("fp32", "fp16", "fp8")
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+
+
+def spread(v):
+    return 100.0 * (max(v) - min(v)) / min(v)
+
+
+def main(argv):
+    import torch
+    from modelcompression_amd import compress, nets, YOLOV2_VOC_CFG
+    from modelcompression_amd.pruning.weightPruning.methods import nm_prune, weight_prune
+    from modelcompression_amd.synthetic import init_synthetic
+
+    dev = torch.device("cuda", 0)
+
+    def fresh():
+        return init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), seed=0).to(dev)
+
+    result = {"model": "YOLOv2-VOC, seeded synthetic weights", "bytes": {}, "time": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        models = {}
+        for name, prune in (("dense", None), ("weight_prune(80)", lambda m: weight_prune(m, 80.0)), ("nm_prune", nm_prune)):
+            m = fresh()
+            if prune is not None:
+                m.set_masks(prune(m))
+            models[name] = m
+            plain = os.path.join(tmp, "m.weights")
+            m.save_weights(plain)
+            row = {"float32 .weights": os.path.getsize(plain)}
+            for payload in PAYLOADS:
+                path = os.path.join(tmp, "m.mcz")
+                m.save_compressed(path, payload)
+                info = compress.compressed_info(path)
+                assert info["bytes"] == os.path.getsize(path) and info["dense_bytes"] == row["float32 .weights"]
+                row[payload] = {"bytes": info["bytes"], "ratio": round(info["ratio"], 3), "kept": info["kept"],
+                                "weights": info["weights"]}
+            result["bytes"][name] = row
+            print("%-18s %12d bytes dense float32; " % (name, row["float32 .weights"])
+                  + ", ".join("%s %d (%.2fx)" % (p, row[p]["bytes"], row[p]["ratio"]) for p in PAYLOADS))
+
+        m = models["weight_prune(80)"]
+        plain, packed = os.path.join(tmp, "t.weights"), os.path.join(tmp, "t.mcz")
+
+        def load_plain():
+            r = nets.Darknet(YOLOV2_VOC_CFG)
+            r.load_weights(plain)
+            return r.to(dev)
+
+        def load_packed():
+            r = nets.Darknet(YOLOV2_VOC_CFG).to(dev)
+            r.load_weights(packed)
+            return r
+
+        legs = {"save_weights": lambda: m.save_weights(plain), "save_compressed fp16": lambda: m.save_compressed(packed, "fp16"),
+                "load_weights + to(device)": load_plain, "load_compressed on the device": load_packed}
+        samples = {k: [] for k in legs}
+        for rnd in range(ROUNDS + 1):
+            for k, fn in legs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if rnd:
+                    samples[k].append(1e3 * (time.perf_counter() - t0))
+        for k, v in samples.items():
+            result["time"][k] = {"ms": v, "median_ms": median(v), "spread_percent": spread(v)}
+            print("%-32s median %9.1f ms (spread %.0f %%)" % (k, median(v), spread(v)))
+        result["time"]["rounds"] = ROUNDS
+        result["time"]["model"] = "weight_prune(80), fp16 payload, %d bytes against %d" % (os.path.getsize(packed), os.path.getsize(plain))
+    if "--json" in argv:
+        with open(JSON_PATH, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print("wrote", JSON_PATH)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
