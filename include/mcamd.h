@@ -241,6 +241,30 @@ int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, const void*
                             const mcamd_conv_epilogue* epi, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Block-sparse fp16 inference forward (an addition beyond the reference; conv_bsparse.hip, Darknet.sparse = "block").
+ * The packed K axis of mcamd_pack_weights runs [channel block][tap][kb channels], so K chunk q of kb columns is one
+ * (channel block, tap) pair.  For every N tile of 64 filters a list names the chunks the tile multiplies, in ascending
+ * q; a chunk whose 64 x kb weights are all zero adds exactly +0 to every accumulator, so a launch on the lists of
+ * mcamd_bsparse_lists equals the same launch on full lists bit for bit, and that one walks mcamd_conv_fwd's igemm MFMA
+ * sequence.  The weights are the dense packing of mcamd_pack_weights: no second format.
+ * ------------------------------------------------------------------------- */
+/* 1: the entries below accept this geometry (stem == 0, ksize 1 or 3, cin % 32 == 0 -- cin_tap == cin --, cout % 8 == 0,
+ * x_wrap == 0, x_f8 == 0, the input slice inside x_ld). */
+int32_t mcamd_conv_fwd_bsparse_ok(const mcamd_conv_geom* g);
+/* Sizes of the lists (int32 entries): out[0] = ntiles = ceil(cout / 64) counts, out[1] = ntiles * nchunks list entries,
+ * nchunks = k*k * cin / kb. */
+int mcamd_bsparse_elems(const mcamd_conv_geom* g, int64_t out[2]);
+/* count[nt] and list[nt][0 .. count[nt]) from the packed forward weights: the chunks q with any non-zero fp16 value
+ * (-0 counts as zero) in rows [64 nt, 64 nt + 64), columns [q kb, q kb + kb), ascending.  One wave ballot per (tile,
+ * chunk) and a scan in q order: no atomics, no host synchronisation.  Entries behind the count are written as 0. */
+int mcamd_bsparse_lists(const mcamd_conv_geom* g, const void* wp_fwd, int32_t* count, int32_t* list, void* stream);
+/* y = leaky(conv(x, w) * scale + shift) over the listed chunks: epilogue mode MCAMD_EPI_PAD_F16 only (dst_mode PLAIN /
+ * POOL / REORG, y2, channel offsets and the overflow flag exactly as mcamd_conv_fwd), both `pad` forms of x.  A count
+ * outside [0, nchunks] or an index outside [0, nchunks) is clamped into its range. */
+int mcamd_conv_fwd_bsparse(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const int32_t* count,
+                           const int32_t* list, const mcamd_conv_epilogue* epi, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Split-K forward for low-batch fp16 inference (an addition beyond the reference; conv_splitk.hip, Darknet.splitk).
  * A layer of few output pixels gives mcamd_conv_fwd a handful of workgroups that each walk the whole K axis; here
  * workgroup (tile, slice s) of a first launch multiplies the K chunks [floor(s n / S), floor((s + 1) n / S)) of the
@@ -1042,6 +1066,18 @@ int mcamd_nm_mask(const float* w, const float* old_mask, int32_t cout, int32_t c
                   float* mask, void* stream);
 /* number of such groups holding more than 2 non-zero mask entries, added to *count (device int32) */
 int mcamd_nm_violations(const float* mask, int32_t cout, int32_t cin, int32_t khw, int32_t* count, void* stream);
+
+/* Block magnitude scores (block_prune, an addition beyond the reference) of an OIHW tensor [cout][cin][khw], cin % 32 == 0.
+ * Block (fb, cb, tap): filters [64 fb, min(64 fb + 64, cout)) x input channels [kb cb, kb cb + kb) at one tap, kb = 64 when
+ * cin % 64 == 0 else 32 -- one K chunk of one N tile of mcamd_conv_fwd_bsparse; block index (fb * (cin / kb) + cb) * khw + tap.
+ * scores[block] = the float64 mean over the block of (double)(w * old_mask)^2 (old_mask may be NULL = ones; the product
+ * in fp32).  Fixed summation order, no atomics: with the block's elements numbered e = r * kb + c, lane l of one wave adds
+ * e = l, l + 64, ... in ascending order; the 64 lane sums are combined by s[l] += s[l ^ d], d = 32, 16, 8, 4, 2, 1. */
+int mcamd_block_scores(const float* w, const float* old_mask, int32_t cout, int32_t cin, int32_t khw, double* scores,
+                       void* stream);
+/* mask = old_mask (NULL = ones) with every block whose keep[block index] is 0 zeroed. */
+int mcamd_block_mask(const int32_t* keep, const float* old_mask, int32_t cout, int32_t cin, int32_t khw, float* mask,
+                     void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Compressed model files (.mcz; an addition beyond the reference): the two device passes around the file.

@@ -196,6 +196,10 @@ SIGNATURES = {
     "mcamd_sparse24_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
     "mcamd_pack_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
     "mcamd_conv_fwd_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
+    "mcamd_conv_fwd_bsparse_ok": (_I32, [C.POINTER(ConvGeom)]),
+    "mcamd_bsparse_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
+    "mcamd_bsparse_lists": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P]),
+    "mcamd_conv_fwd_bsparse": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_fwd_splitk_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, _I32, C.POINTER(SplitkInfo)]),
     "mcamd_conv_fwd_splitk": (C.c_int, [C.POINTER(ConvGeom), _P, _P, C.POINTER(ConvEpilogue), _I32, _P, _SZ, _P]),
     "mcamd_conv_fwd_q8_ok": (_I32, [C.POINTER(ConvGeom)]),
@@ -276,6 +280,8 @@ SIGNATURES = {
     "mcamd_masked_residual": (C.c_int, [_P, _P, _I64, _P, _P]),
     "mcamd_nm_mask": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "mcamd_nm_violations": (C.c_int, [_P, _I32, _I32, _I32, _P, _P]),
+    "mcamd_block_scores": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    "mcamd_block_mask": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "mcamd_wz_workspace_bytes": (_SZ, [_I64, _I32]),
     "mcamd_wz_pack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P, _SZ, _P]),
     "mcamd_wz_unpack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),

@@ -22,6 +22,7 @@ SOURCES = {
     "conv_igemm.hip": [],
     "conv_igemm_pp.hip": [],
     "conv_sparse.hip": [],
+    "conv_bsparse.hip": [],
     "conv_splitk.hip": [],
     "conv_q8.hip": [],
     "conv_q8_sparse.hip": [],

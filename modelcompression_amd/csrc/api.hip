@@ -706,6 +706,58 @@ extern "C" int mcamd_conv_fwd_sparse24(const mcamd_conv_geom* g, const void* x, 
 }
 
 // ---------------------------------------------------------------------------------------
+// block sparsity (conv_bsparse.hip; an addition beyond the reference)
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_bsparse_ok(const mcamd_conv_geom* g) {
+    if (!g || g->stem || g->x_wrap != 0 || g->x_f8 != 0 || (g->ksize != 1 && g->ksize != 3)) return 0;
+    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->cin <= 0 || g->cout <= 0) return 0;
+    if (g->cin % 32 != 0 || g->cout % 8 != 0 || (long long)g->B * g->H * g->W >= (1ll << 31)) return 0;
+    if (g->pad != 0 && g->pad != 1) return 0;
+    if (g->x_ld % 8 != 0 || g->x_choff % 8 != 0 || g->x_choff + g->cin > g->x_ld) return 0;
+    return 1;
+}
+
+extern "C" int mcamd_bsparse_elems(const mcamd_conv_geom* g, int64_t out[2]) {
+    MCAMD_REQUIRE(g && out, "bsparse_elems: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_bsparse_ok(g), "bsparse_elems: geometry has no block-sparse form (mcamd_conv_fwd_bsparse_ok)");
+    const int ct = cin_tap_of(g);
+    const long long ntiles = (g->cout + 63) / 64, nchunks = (long long)ntaps_of(g) * ct / kblock_of(ct);
+    out[0] = ntiles;             // counts
+    out[1] = ntiles * nchunks;   // list entries
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_bsparse_lists(const mcamd_conv_geom* g, const void* wp_fwd, int32_t* count, int32_t* list, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "bsparse_lists: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_bsparse_lists(&g_, wp_fwd, count, list, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_bsparse_ok(g), "bsparse_lists: geometry has no block-sparse form (mcamd_conv_fwd_bsparse_ok)");
+    MCAMD_REQUIRE(wp_fwd && count && list, "bsparse_lists: null pointer");
+    MCAMD_REQUIRE(((uintptr_t)wp_fwd & 15) == 0, "bsparse_lists: packed weights must be 16-byte aligned");
+    return mcamd_bsparse_lists_launch(wp_fwd, g->cout, cin_tap_of(g), ntaps_of(g), count, list, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_bsparse(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const int32_t* count,
+                                      const int32_t* list, const mcamd_conv_epilogue* epi, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_bsparse: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_bsparse(&g_, x, wp_fwd, count, list, &e_, s); });
+    }
+    if (check_geom(g, "conv_fwd_bsparse")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_bsparse_ok(g), "conv_fwd_bsparse: geometry has no block-sparse form (mcamd_conv_fwd_bsparse_ok)");
+    MCAMD_REQUIRE(x && wp_fwd && count && list, "conv_fwd_bsparse: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_bsparse: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x, wp_fwd, g->x_ld, g->x_choff, g->cout, cin_tap_of(g), 0);
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_bsparse", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    return mcamd_bsparse_launch(a, count, list, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------
 // split-K forward for low-batch inference (conv_splitk.hip; an addition beyond the reference)
 // ---------------------------------------------------------------------------------------
 // what both entries refuse, then the plan for `slices` (0 = the policy)

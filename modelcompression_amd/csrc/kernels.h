@@ -125,6 +125,11 @@ struct SplitkPlan {
 };
 SplitkPlan mcamd_splitk_plan(long long M, int n, int cin_tap, int ktot, int forced);
 int mcamd_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, float* ws, hipStream_t st);
+// conv_bsparse.hip: the K chunks of each 64-filter N tile from a list (count[ntiles], list[ntiles][ktot / kb]), mode 2
+// epilogue; and the lists of a packed forward weight matrix
+#define MCAMD_BSPARSE_BM_DEFAULT 128
+int mcamd_bsparse_launch(IgemmArgs& a, const int* count, const int* list, hipStream_t st);
+int mcamd_bsparse_lists_launch(const void* wp, int cout, int cin_tap, int ntaps, int* count, int* list, hipStream_t st);
 int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);   // conv_sparse.hip: 2:4 weights, mode 2 epilogue
 int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
                                int cin_tap, int kb, hipStream_t st);

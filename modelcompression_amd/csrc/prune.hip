@@ -552,3 +552,80 @@ extern "C" int mcamd_nm_violations(const float* mask, int32_t cout, int32_t cin,
     MCAMD_LAUNCH_CHECK("nm_violations");
     return MCAMD_OK;
 }
+
+// ------------------------------------------------------------------------------------
+// Block magnitude scores and masks (block_prune; an addition beyond the reference)
+// ------------------------------------------------------------------------------------
+// Block (fb, cb, tap) of an OIHW tensor [cout][cin][khw], cin % 32 == 0, kb = 64 when cin % 64 == 0 else 32 (the channel
+// block of the packed K axis, include/mcamd.h): filters [64 fb, min(64 fb + 64, cout)) x input channels [kb cb, kb cb + kb)
+// at one tap -- one K chunk of one 64-filter N tile of the forward kernels.  Block index = (fb * (cin / kb) + cb) * khw + tap.
+//
+// score = (sum over the block of (double)(w * old_mask)^2) / (elements of the block), w * old_mask taken in fp32.
+// Summation order (tests/bsparse_ref.py restates it): one wave per block; with the block's elements numbered
+// e = r * kb + c (r = filter inside the block, c = channel inside the block), lane l adds e = l, l + 64, l + 128, ... in
+// ascending order into its own double; the 64 lane sums are then combined by the butterfly s[l] = s[l] + s[l ^ d] for
+// d = 32, 16, 8, 4, 2, 1 (each step adds the same two numbers in both lanes of a pair, so all lanes agree); one division.
+// No atomics: the score is a function of the tensor alone.
+__global__ __launch_bounds__(256) void block_scores_kernel(const float* w, const float* old_mask, int cout, int cin, int khw, int kb,
+                                                           double* scores) {
+    const int ncb = cin / kb, nfb = (cout + 63) / 64;
+    const int lane = threadIdx.x & 63;
+    const long long pair = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // (fb, cb)
+    if (pair >= (long long)nfb * ncb) return;
+    const int fb = (int)(pair / ncb), cb = (int)(pair - (long long)fb * ncb);
+    const int rows = cout - 64 * fb < 64 ? cout - 64 * fb : 64;
+    const int n = rows * kb;
+    for (int tap = 0; tap < khw; ++tap) {
+        double s = 0.0;
+        for (int e = lane; e < n; e += 64) {
+            const int r = e / kb, c = e - r * kb;
+            const long long idx = ((long long)(64 * fb + r) * cin + cb * kb + c) * khw + tap;
+            const float v = w[idx] * (old_mask ? old_mask[idx] : 1.f);
+            const double d = (double)v;
+            s += d * d;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+        if (lane == 0) scores[pair * khw + tap] = s / (double)n;
+    }
+}
+
+extern "C" int mcamd_block_scores(const float* w, const float* old_mask, int32_t cout, int32_t cin, int32_t khw, double* scores,
+                                  void* stream) {
+    MCAMD_REQUIRE(w && scores && cout > 0 && cin > 0 && khw > 0 && cin % 32 == 0,
+                  "block_scores: bad argument (cin %d must be a multiple of 32)", cin);
+    const int kb = cin % 64 == 0 ? 64 : 32;
+    const long long pairs = (long long)((cout + 63) / 64) * (cin / kb);
+    hipLaunchKernelGGL(block_scores_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, w, old_mask, cout,
+                       cin, khw, kb, scores);
+    MCAMD_LAUNCH_CHECK("block_scores");
+    return MCAMD_OK;
+}
+
+// mask = old_mask (ones when NULL) with the blocks whose keep flag is 0 zeroed; keep[block index] as above
+__global__ __launch_bounds__(256) void block_mask_kernel(const int* keep, const float* old_mask, int cout, int cin, int khw, int kb,
+                                                         float* mask) {
+    const long long n = (long long)cout * cin * khw;
+    const int ncb = cin / kb;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int tap = (int)(i % khw);
+        const long long oc = i / khw;
+        const int c = (int)(oc % cin);
+        const long long o = oc / cin;
+        const long long blk = ((o / 64) * ncb + c / kb) * khw + tap;
+        mask[i] = keep[blk] ? (old_mask ? old_mask[i] : 1.f) : 0.f;
+    }
+}
+
+extern "C" int mcamd_block_mask(const int32_t* keep, const float* old_mask, int32_t cout, int32_t cin, int32_t khw, float* mask,
+                                void* stream) {
+    MCAMD_REQUIRE(keep && mask && cout > 0 && cin > 0 && khw > 0 && cin % 32 == 0,
+                  "block_mask: bad argument (cin %d must be a multiple of 32)", cin);
+    const long long n = (long long)cout * cin * khw;
+    long long g = (n + 256 * 8 - 1) / (256 * 8);
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(block_mask_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, keep, old_mask, cout, cin, khw,
+                       cin % 64 == 0 ? 64 : 32, mask);
+    MCAMD_LAUNCH_CHECK("block_mask");
+    return MCAMD_OK;
+}

@@ -85,6 +85,12 @@ MIXED_BUDGET = 5.5e-4
 # form stays on everywhere: the step meets 12.0 ms with it and the bar is 1e-3.)
 MIXED_BUDGET_TRAIN = 7.0e-4
 TRAIN_GAIN = 1.1
+# Darknet.sparse = "block": a masked block leaves the dense fp16 launch for the block-sparse kernel (csrc/conv_bsparse.hip)
+# when the kept fraction of its (64-filter tile, K chunk) pairs is at most this -- the default of Darknet.sparse_max_kept.
+# Measured (tools/bsparse_bench.py, profiles/bsparse_bench.json): the largest kept fraction at which the kernel
+# is at least 10 % faster than the dense launch on every layer of conv9 .. conv22 at B = 128 (worst layer 1.15x at 0.375;
+# at 0.5 conv9 / 11 / 13 gain 4-9 % only, and from 0.625 up the 3x3 layers lose).
+BSPARSE_MAX_KEPT = 0.375
 
 
 def _probe_side_stream(device, tries=8):
@@ -189,6 +195,12 @@ class Engine:
         # mcamd_conv_fwd_sparse24, chosen when the masks change (_update_sparse); empty = every block dense
         self.sparse_layers = []
         self._sparse_mode, self._sparse_keys = None, None
+        # block-sparse inference (Darknet.sparse = "block", plain-fp16 eval engines only): conv numbers of the blocks that run
+        # mcamd_conv_fwd_bsparse, chosen when the masks, the weights or Darknet.sparse_max_kept change (_refresh_bsparse)
+        self.bsparse_layers = []
+        self.bsparse_kept = {}           # conv number -> kept-chunk fraction of every candidate block
+        self._bs_max_kept = None
+        self._bs_exempt = frozenset()    # layer indices the policy chose: their filters are not compacted (_plan_bsparse)
         # split-K low-batch inference (Darknet.splitk, plain-fp16 eval engines only): conv numbers of the blocks that run
         # mcamd_conv_fwd_splitk, chosen when the flag or the masks change (_update_splitk); one workspace for all of them
         self.splitk_layers = []
@@ -659,9 +671,13 @@ class Engine:
             self._refresh_f8_wexp()
         mkeys = tuple(None if not lay.conv.mask_flag else (lay.conv.mask.data_ptr(), lay.conv.mask._version)
                       for lay in self.layers)
-        if mkeys != self._mask_keys:         # masks are static during retraining: planned once
+        # (Darknet.sparse = "block": the blocks the policy chose keep their dense filter layout, so the compaction plan
+        # depends on that choice too; it is the empty set in every other mode)
+        exempt = self._plan_bsparse() if self._sparse_mode == "block" else frozenset()
+        if (mkeys, exempt) != self._mask_keys:         # masks are static during retraining: planned once
+            self._bs_exempt = exempt
             self._update_compaction()
-            self._mask_keys = mkeys
+            self._mask_keys = (mkeys, exempt)
             self._pack_key = None
             for lay in self.layers:          # the packed shapes may have shrunk: stale entries must not survive
                 lay.wp.zero_()
@@ -761,6 +777,8 @@ class Engine:
                 ops.pack_many(*self._pack_table)
             if side is not None:
                 self._pack_on_side = True      # forward() makes the launch stream wait for the second one before block 2
+        if self._sparse_mode == "block":       # (eval only: a training-mode forward has _sparse_mode None)
+            self._refresh_bsparse()
         self._packed_sig = sig
         self.model._weights_dirty = False
 
@@ -780,12 +798,16 @@ class Engine:
         first nor the last block, and mcamd_conv_fwd_sparse24_ok accepts its geometry.  Every other block stays dense."""
         self._plan_epoch += 1             # recorded forward plans name the dense or the sparse launch of a block
         for lay in self.layers:
-            lay.sp_on = False
-        self.sparse_layers = []
+            lay.sp_on = lay.bs_on = False
+        self.sparse_layers, self.bsparse_layers = [], []
+        if self._sparse_mode != "block":
+            self.bsparse_kept = {}
         if self._sparse_mode is None:
             return
+        if self._sparse_mode == "block":
+            return                        # (chosen per re-pack: _plan_bsparse / _refresh_bsparse)
         if self._sparse_mode != "2:4":
-            raise McamdError("sparse must be None or '2:4' (got %r)" % (self._sparse_mode,))
+            raise McamdError("sparse must be None, '2:4' or 'block' (got %r)" % (self._sparse_mode,))
         cand = [lay for lay in self.layers
                 if lay.li > 0 and not lay.stem and not lay.is_last and lay.conv.mask_flag and lay.fold is None
                 and lay.g_cols is None and lay.cin % 4 == 0 and self._fused_eval(lay)
@@ -806,12 +828,72 @@ class Engine:
             lay.sp_on = True
             self.sparse_layers.append(lay.li + 1)      # conv number (conv1 = the first block)
 
+    # ------------------------------------------------------------------ block sparsity
+    def _bsparse_candidate(self, lay):
+        """Could this block run mcamd_conv_fwd_bsparse?  It has a mask of its weight's shape, is neither the first nor the
+        last block, takes the fused inference path when its filters are not compacted, has no border table (slim_export
+        models) and a geometry mcamd_conv_fwd_bsparse_ok accepts."""
+        m = lay.conv.mask if lay.conv.mask_flag else None
+        return (m is not None and m.is_cuda and m.dtype == torch.float32 and m.shape == lay.conv.weight.shape
+                and lay.li > 0 and not lay.stem and not lay.is_last and lay.bn is not None and lay.border is None
+                and self.fuse_eval and not self.precise and not self.q8
+                and (lay.out2_t is None or lay.mode == L.DST_POOL)
+                and (lay.mode == L.DST_PLAIN or (lay.H % 2 == 0 and lay.W % 2 == 0))
+                and ops.conv_fwd_bsparse_ok(lay.geom))
+
+    def _plan_bsparse(self):
+        """The policy of Darknet.sparse = "block", taken in front of every re-pack (masks, weights, the mode or
+        Darknet.sparse_max_kept changed): every candidate's chunk lists from its packed weights in their own filter and
+        channel order (mcamd_bsparse_lists on a temporary packing), ONE host read of all counts, and a candidate is chosen
+        when its kept-chunk fraction, sum(count) / (tiles x chunks), is at most sparse_max_kept.  Returns the chosen
+        layer indices: pack() keeps those blocks out of the filter compaction, whose physical channel order would scatter
+        the zero blocks over the K chunks."""
+        cand = [lay for lay in self.layers if self._bsparse_candidate(lay)]
+        sums = []
+        for lay in cand:
+            wp, _ = ops.pack_weights(lay.geom, lay.conv.weight.data, lay.conv.mask.contiguous(), want_dgrad=False)
+            sums.append(ops.bsparse_lists(lay.geom, wp)[0].sum())
+        self.bsparse_kept = {}
+        if not cand:
+            return frozenset()
+        chosen = []
+        for lay, s_ in zip(cand, torch.stack(sums).cpu().tolist()):
+            kept = s_ / float(ops.bsparse_elems(lay.geom)[1])
+            self.bsparse_kept[lay.li + 1] = kept       # conv number (conv1 = the first block)
+            if kept <= self._bs_max_kept:
+                chosen.append(lay.li)
+        return frozenset(chosen)
+
+    def _refresh_bsparse(self):
+        """Behind every re-pack under Darknet.sparse = "block": the chunk lists of the chosen blocks from the weights the
+        forward launch reads.  A chosen block whose producer was compacted after all (its input channels are permuted)
+        stays on the dense launch."""
+        on = []
+        for lay in self.layers:
+            lay_on = (lay.li in self._bs_exempt and lay.perm is None and lay.g_cols is None and lay.fold is None
+                      and self._fused_eval(lay))
+            if lay_on:
+                nc, nl = ops.bsparse_elems(lay.geom_act)
+                if getattr(lay, "bs_count", None) is None or lay.bs_count.numel() != nc or lay.bs_list.numel() != nl:
+                    lay.bs_count = torch.zeros(nc, dtype=torch.int32, device=self.device)
+                    lay.bs_list = torch.zeros(nc, nl // nc, dtype=torch.int32, device=self.device)
+                    self._plan_epoch += 1     # recorded forward plans hold the lists' addresses
+                ops.bsparse_lists(lay.geom_act, lay.wp, lay.bs_count, lay.bs_list)
+                on.append(lay.li + 1)
+            if lay_on != lay.bs_on:
+                self._plan_epoch += 1         # recorded forward plans name the dense or the block-sparse launch of a block
+                lay.bs_on = lay_on
+        if on != self.bsparse_layers:
+            self.bsparse_layers = on
+            if self._splitk_on:
+                self._update_splitk()         # block-sparse blocks are never split
+
     # ------------------------------------------------------------------ split-K low-batch inference
     def _splitk_form(self, lay):
         """(epilogue mode, dst_mode) of the eval-mode launch of a block the split-K pair can stand in for, or None: the fused
         inference launch (ops.conv_fwd_padded) or the raw one without statistics (ops.conv_fwd_raw: blocks with a border
         table, a permutation or folding -- how slim_export models run in fp16)."""
-        if (lay.li == 0 or lay.stem or lay.is_last or lay.sp_on or self.precise or self.q8
+        if (lay.li == 0 or lay.stem or lay.is_last or lay.sp_on or lay.bs_on or self.precise or self.q8
                 or lay.fused_stem or lay.fused_stem_eval or getattr(lay, "stem_split", False)):
             return None
         return (L.EPI_PAD_F16, lay.mode) if self._fused_eval(lay) else (L.EPI_RAW_F16, L.DST_PLAIN)
@@ -1133,7 +1215,9 @@ class Engine:
                     # exist for 32 and 64 filters only, and a ragged count falls back to the generic kernels:
                     # measured 0.22 -> 0.33 ms forward, 0.19 -> 0.32 ms weight gradient at 40 % pruning)
                     # (... nor does the first block of a split-operand engine: its fused / fp32 kernels want all 32 filters)
-                    if self.compact and lay.bn is not None and not lay.stem and not (self.precise and lay.li == 0):
+                    # (... nor does a block that runs the block-sparse kernel: it skips the dead filters' tiles itself)
+                    if (self.compact and lay.bn is not None and not lay.stem and not (self.precise and lay.li == 0)
+                            and lay.li not in self._bs_exempt):
                         # kept count rounded up so the kernels keep their tile shapes: whole 64-filter tiles
                         # (the 9-tap wgrad and the 128-wide igemm tiles) where the layer has them
                         gran = self.compact_gran or (64 if lay.cout >= 128 else 8)
@@ -1333,13 +1417,14 @@ class Engine:
         if mode is not None and (self.precise or self.q8):
             raise McamdError("sparse=%r runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r%s"
                              % (mode, self.precision, "; 2:4 masks on the fp8 engine: model.precision = 'fp8-2:4' with "
-                                "model.sparse = None" if self.q8 else ""))
+                                "model.sparse = None" if self.q8 and mode == "2:4" else ""))
         splitk = bool(getattr(self.model, "splitk", False)) and not training
         if splitk and (self.precise or self.q8):
             raise McamdError("splitk=True runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r"
                              % (self.precision,))
-        force = bool(training) or mode != self._sparse_mode or splitk != self._splitk_on
-        self._sparse_mode, self._splitk_on = mode, splitk
+        max_kept = float(getattr(self.model, "sparse_max_kept", BSPARSE_MAX_KEPT)) if mode == "block" else None
+        force = bool(training) or mode != self._sparse_mode or splitk != self._splitk_on or max_kept != self._bs_max_kept
+        self._sparse_mode, self._splitk_on, self._bs_max_kept = mode, splitk, max_kept
         self.pack(force=force, training=training)
         self.serial += 1
         tin = self.layers[0].tin
@@ -1489,6 +1574,10 @@ class Engine:
                 if lay.sp_on:       # 2:4 weights on the sparse MFMA (Darknet.sparse, _update_sparse)
                     self._timed('fwd', lay, ops.conv_fwd_sparse24, lay.geom_act, xin, lay.wsp, lay.widx, self.bufs[t.buf], t.ld,
                                 t.choff, lay.scale, lay.shift, lay.slope, **dst)
+                    continue
+                if lay.bs_on:       # the non-zero K chunks of each 64-filter tile only (Darknet.sparse = "block", _refresh_bsparse)
+                    self._timed('fwd', lay, ops.conv_fwd_bsparse, lay.geom_act, xin, lay.wp, lay.bs_count, lay.bs_list,
+                                self.bufs[t.buf], t.ld, t.choff, lay.scale, lay.shift, lay.slope, **dst)
                     continue
                 if lay.sk_on:       # few pixels: K cut into slices over the whole chip (Darknet.splitk, _update_splitk)
                     self._timed('fwd', lay, ops.conv_fwd_splitk, lay.geom_act, xin, lay.wp, self.bufs[t.buf], t.ld, t.choff,

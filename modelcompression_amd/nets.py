@@ -307,8 +307,14 @@ class Darknet(nn.Module):
         self.precision = os.environ.get("MCAMD_PRECISION", "auto")
         # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA
-        # (engine.Engine.sparse_layers).  Eval with precision "fp16" only -- other eval precisions raise; training ignores it.
+        # (engine.Engine.sparse_layers).  "block" runs every eligible masked block on the block-sparse kernel
+        # (csrc/conv_bsparse.hip): per 64-filter tile it multiplies only the K chunks of the packed weights that
+        # hold a non-zero value -- what pruning.weightPruning.methods.block_prune zeroes is skipped, bit-identically to
+        # multiplying it -- provided the layer's kept-chunk fraction is at most `sparse_max_kept`
+        # (engine.Engine.bsparse_layers).  Eval with precision "fp16" only -- other eval precisions raise; training ignores it.
         self.sparse = None
+        from .engine import BSPARSE_MAX_KEPT
+        self.sparse_max_kept = BSPARSE_MAX_KEPT      # the measured policy constant (engine.py)
         # Low-batch inference (an addition beyond the reference): True runs every block whose forward launch would leave most
         # CUs idle -- the 13x13 and 26x26 layers at B = 1 -- as a split-K pair (csrc/conv_splitk.hip, DESIGN.md 3p,
         # engine.Engine.splitk_layers); batches the policy does not split run exactly what they run without it.  Eval with

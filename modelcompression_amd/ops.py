@@ -977,6 +977,87 @@ def conv_fwd_sparse24(g, x, wsp, idx, y, y_ld, y_choff=0, scale=None, shift=None
           "mcamd_conv_fwd_sparse24")
 
 
+# ----------------------------------------------------------------------------- block sparsity
+BLOCK_FILTERS = 64      # filters per block of block_prune = the N tile of conv_fwd_bsparse
+
+
+def block_kb(cin):
+    """Channels per block: the channel block of the packed K axis (include/mcamd.h), for cin % 32 == 0."""
+    return 64 if cin % 64 == 0 else 32
+
+
+def block_scores(w, old_mask=None):
+    """float64 mean of (w * old_mask)^2 per block [fb][cb][tap] of an OIHW fp32 tensor with cin % 32 == 0
+    (mcamd_block_scores: fixed summation order, no atomics)."""
+    _need_cuda(w, old_mask)
+    assert w.dtype == torch.float32 and w.is_contiguous() and (old_mask is None or old_mask.is_contiguous())
+    O, I = w.shape[0], w.shape[1]
+    khw = w.numel() // (O * I)
+    scores = torch.empty(((O + BLOCK_FILTERS - 1) // BLOCK_FILTERS) * (I // block_kb(I)) * khw, dtype=torch.float64, device=w.device)
+    check(L.lib().mcamd_block_scores(ptr(w), ptr(old_mask), O, I, khw, ptr(scores), stream_ptr()), "mcamd_block_scores")
+    return scores
+
+
+def block_mask(keep_i32, shape, old_mask=None):
+    """old_mask (ones when None) with the blocks whose keep flag is 0 zeroed (mcamd_block_mask)."""
+    _need_cuda(keep_i32, old_mask)
+    O, I = shape[0], shape[1]
+    khw = 1
+    for s in shape[2:]:
+        khw *= s
+    nblocks = ((O + BLOCK_FILTERS - 1) // BLOCK_FILTERS) * (I // block_kb(I)) * khw
+    if keep_i32.dtype != torch.int32 or not keep_i32.is_contiguous() or keep_i32.numel() != nblocks:
+        raise L.McamdError("block_mask: keep must be a contiguous CUDA int32 vector of %d entries" % nblocks)
+    mask = torch.empty(tuple(shape), dtype=torch.float32, device=keep_i32.device)
+    check(L.lib().mcamd_block_mask(ptr(keep_i32), ptr(old_mask), O, I, khw, ptr(mask), stream_ptr()), "mcamd_block_mask")
+    return mask
+
+
+def conv_fwd_bsparse_ok(g):
+    """Does mcamd_conv_fwd_bsparse accept this geometry?  (Shared by the engine and the tests.)"""
+    return bool(L.lib().mcamd_conv_fwd_bsparse_ok(C.byref(g)))
+
+
+def bsparse_elems(g):
+    """(ntiles, ntiles * nchunks): int32 entries of the counts and of the lists."""
+    out = (C.c_int64 * 2)()
+    check(L.lib().mcamd_bsparse_elems(C.byref(g), out), "mcamd_bsparse_elems")
+    return int(out[0]), int(out[1])
+
+
+def bsparse_lists(g, wp, out_count=None, out_list=None):
+    """Packed fp16 forward weights -> (count int32[ntiles], list int32[ntiles][nchunks]): per 64-filter tile the K chunks
+    holding a non-zero weight, ascending (mcamd_bsparse_lists; no host synchronisation)."""
+    _need_cuda(wp)
+    nc, nl = bsparse_elems(g)
+    if out_count is None:
+        out_count = torch.empty(nc, dtype=torch.int32, device=wp.device)
+    if out_list is None:
+        out_list = torch.empty(nc, nl // nc, dtype=torch.int32, device=wp.device)
+    if out_count.numel() != nc or out_list.numel() != nl or wp.numel() < packed_elems(g)[0]:
+        raise L.McamdError("bsparse_lists: operand sizes do not fit the geometry")
+    check(L.lib().mcamd_bsparse_lists(C.byref(g), ptr(wp), ptr(out_count), ptr(out_list), stream_ptr()), "mcamd_bsparse_lists")
+    return out_count, out_list
+
+
+def conv_fwd_bsparse(g, x, wp, count, lst, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
+                     y2_choff=0, all_chunks=False):
+    """conv_fwd_padded over the listed K chunks of each 64-filter tile (bsparse_lists): the same inference epilogue,
+    arguments and output.  all_chunks=True (tests, tools/bsparse_bench.py) runs the same launch with full lists."""
+    nc, nl = bsparse_elems(g)
+    if all_chunks:
+        nch = nl // nc
+        count = torch.full((nc,), nch, dtype=torch.int32, device=x.device)
+        lst = torch.arange(nch, dtype=torch.int32, device=x.device).repeat(nc, 1).contiguous()
+    _need_cuda(x, count, lst)
+    if count.dtype != torch.int32 or lst.dtype != torch.int32 or count.numel() != nc or lst.numel() != nl or not lst.is_contiguous():
+        raise L.McamdError("conv_fwd_bsparse: count / list must be contiguous int32 of %d / %d entries" % (nc, nl))
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff)
+    check(L.lib().mcamd_conv_fwd_bsparse(C.byref(g), ptr(x), ptr(wp), ptr(count), ptr(lst), C.byref(e), stream_ptr()),
+          "mcamd_conv_fwd_bsparse")
+
+
 # ----------------------------------------------------------------------------- split-K forward (low-batch inference)
 def conv_fwd_splitk_info(g, mode, dst_mode=0, slices=0):
     """mcamd_splitk_info of a split-K forward of `g` with epilogue `mode` (L.EPI_PAD_F16 / L.EPI_RAW_F16): host logic only.

@@ -101,6 +101,63 @@ def _percentile_f64(values, perc):
     return _lerp(np.float64(s[k]), np.float64(s[k + 1]), gamma)
 
 
+def _block_keep(scores, pruning_perc, per_layer=False):
+    """Keep flags (int32, one array per layer) from the layers' float64 block scores: a block goes when its score is
+    strictly below the `pruning_perc` percentile of all scores (of its own layer's with per_layer); the highest-scoring
+    block of every layer stays whatever the threshold, ties to the lowest block index."""
+    allv = np.concatenate([np.zeros(0, np.float64)] + list(scores))
+    if not per_layer and allv.shape[0]:
+        threshold = _percentile_f64(allv, pruning_perc)
+    keeps = []
+    for s in scores:
+        if per_layer:
+            threshold = _percentile_f64(s, pruning_perc)
+        keep = (~(s < threshold)).astype(np.int32)
+        keep[int(np.argmax(s))] = 1           # (argmax: the first of equal maxima)
+        keeps.append(keep)
+    return keeps
+
+
+def block_prune(model, pruning_perc, per_layer=False):
+    '''
+    Block magnitude pruning (Narang et al. 2017, arXiv:1711.02782; Mao et al. 2017, arXiv:1705.08922) -- an addition
+    beyond the reference.  Same calling convention as weight_prune / nm_prune: one mask per `p.dim() != 1` parameter in
+    model.parameters() order, applied by the caller with model.set_masks(masks).  For a conv weight [O, I, kh, kw] with
+    I % 32 == 0 a block is filters [64 f, min(64 f + 64, O)) x input channels [kb c, kb c + kb) at one tap, kb = 64 when
+    I % 64 == 0 else 32: one K chunk of one 64-filter tile of the forward kernels, so Darknet.sparse = "block" skips it.
+    A block's score is the float64 mean of (w * old_mask)^2 (mcamd_block_scores: fixed summation order), old_mask being
+    the layer's current mask or all ones; blocks scoring strictly below the pruning_perc percentile of all eligible blocks
+    of the model (per_layer=True: of their own layer) are zeroed, except that every layer keeps its highest-scoring block
+    (ties: the lowest block index).  mask = old_mask * keep, so the method composes with weight_prune / nm_prune.  Other
+    parameters (conv1: 3 input channels) get their old mask unchanged, or all ones.
+    '''
+    ps = _prunable(model)
+    owner = {}
+    for mod in model.modules():
+        if getattr(mod, "mask_flag", False) and hasattr(mod, "weight"):
+            owner[id(mod.weight)] = mod.mask
+    olds, elig = [], []
+    for p in ps:
+        old = owner.get(id(p))
+        olds.append(old.contiguous() if old is not None and old.shape == p.shape else None)
+        elig.append(p.dim() == 4 and p.shape[1] % 32 == 0)
+    scores = [ops.block_scores(p.data.contiguous(), old) for p, old, e in zip(ps, olds, elig) if e]
+    keeps = iter(())
+    if scores:
+        # one device->host read of all scores (12 367 for YOLOv2-VOC), one host->device write of the keep flags
+        sizes = [s.numel() for s in scores]
+        host = np.split(torch.cat(scores).cpu().numpy(), np.cumsum(sizes)[:-1])
+        keep_all = torch.from_numpy(np.concatenate(_block_keep(host, pruning_perc, per_layer))).to(ps[0].device)
+        keeps = iter(torch.split(keep_all, sizes))
+    masks = []
+    for p, old, e in zip(ps, olds, elig):
+        if e:
+            masks.append(ops.block_mask(next(keeps).contiguous(), tuple(p.shape), old))
+        else:
+            masks.append(old.clone() if old is not None else torch.ones_like(p.data))
+    return masks
+
+
 def quick_filter_prune(model, pruning_perc):
     '''
     Prune pruning_perc% filters globally                   (reference methods.py:28-78)

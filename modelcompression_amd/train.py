@@ -50,7 +50,7 @@ from .distill import DistillLoss  # noqa: E402
 from .data import (VOCList, SyntheticDetection, VOCAugment, SyntheticAugment, ResidentImages, ResidentAugment,  # noqa: E402
                    ResidentList, label_path_for, read_boxes)
 from .nets import Darknet, cfg_shapes, parse_cfg  # noqa: E402
-from .pruning.weightPruning.methods import quick_filter_prune, weight_prune  # noqa: E402
+from .pruning.weightPruning.methods import block_prune, quick_filter_prune, weight_prune  # noqa: E402
 from .pruning.weightPruning.utils import prune_rate, are_masks_consistent  # noqa: E402
 
 
@@ -292,6 +292,8 @@ class YOLOv2Train():
         if pruning_perc > 0:
             if pruning_method == "filter":
                 masks = quick_filter_prune(self.model, pruning_perc)
+            elif pruning_method == "block":
+                masks = block_prune(self.model, pruning_perc)
             else:
                 masks = weight_prune(self.model, pruning_perc)
             dp.broadcast_masks(masks, src=0)
