@@ -766,6 +766,21 @@ int mcamd_stem_block_bwd(const mcamd_stem_block_desc* d, void* workspace, size_t
  * mcamd_bn_coeffs takes, as mcamd_conv_epilogue.stats.  nn.BatchNorm2d's batch statistics (src/nets.py:802). */
 int32_t mcamd_stem_block_stats_rows(const mcamd_stem_block_desc* d);
 int mcamd_stem_block_stats(const mcamd_stem_block_desc* d, float* stats, int32_t stats_rows, int32_t stats_ld, void* stream);
+/* How the block's five persistent launches divide a B x H x W problem (only d->B, H, W are read), from the function the
+ * launches themselves ask; works without a GPU.  A work item is a unit (32 columns x 2 conv rows = 16 pooled pixels) or,
+ * for the Gram pass, a step (32 columns x 1 row).  out[4 * launch + i], launch = MCAMD_STEM_PLAN_*:
+ *   0 workgroups launched   1 work items   2 items all workgroups take in one pass (passes = ceil(items / this))
+ *   3 items the busiest wave takes over all passes: the length of its fp32 accumulation chain
+ * _FWD: the plain forward pass; _FWD_PLANES: the forward pass with planes >= 2 or split operands; _STATS:
+ * mcamd_stem_block_stats (its grid is mcamd_stem_block_stats_rows); _GRAM: the Gram pass of training != 0; _BWD. */
+#define MCAMD_STEM_PLAN_FWD 0
+#define MCAMD_STEM_PLAN_FWD_PLANES 1
+#define MCAMD_STEM_PLAN_STATS 2
+#define MCAMD_STEM_PLAN_GRAM 3
+#define MCAMD_STEM_PLAN_BWD 4
+#define MCAMD_STEM_PLAN_LAUNCHES 5
+#define MCAMD_STEM_PLAN_INFO_N 20
+int mcamd_stem_block_plan_info(const mcamd_stem_block_desc* d, int32_t out[MCAMD_STEM_PLAN_INFO_N]);
 
 /* ------------------------------------------------------------------------- *
  * Layout conversion at the model boundary (Darknet.forward takes/returns NCHW fp32,

@@ -171,6 +171,8 @@ DST_PLAIN, DST_POOL, DST_REORG = 0, 1, 2
 WGRAD_GENERIC, WGRAD_STEM, WGRAD_WIN, WGRAD_NINE, WGRAD_NINE_WIDE = 0, 1, 2, 3, 4      # mcamd_conv_wgrad_plan_info: family
 WFIN_ROW, WFIN_VEC, WFIN_GENERIC = 0, 1, 2                                             # ... and finish kernel
 WGRAD_PLAN_INFO_N = 13
+STEM_PLAN_FWD, STEM_PLAN_FWD_PLANES, STEM_PLAN_STATS, STEM_PLAN_GRAM, STEM_PLAN_BWD = 0, 1, 2, 3, 4    # mcamd_stem_block_plan_info
+STEM_PLAN_INFO_N = 20
 WZ_FP32, WZ_FP16, WZ_FP8 = 0, 1, 2                                                     # mcamd_wz_seg.kind
 WZ_F_BN, WZ_F_BITS = 1, 2                                                              # record flags of a .mcz file
 WZ_BLOCK_WORDS = 64
@@ -241,6 +243,7 @@ SIGNATURES = {
     "mcamd_stem_block_bwd": (C.c_int, [C.POINTER(StemBlockDesc), _P, _SZ, _P]),
     "mcamd_stem_block_stats_rows": (_I32, [C.POINTER(StemBlockDesc)]),
     "mcamd_stem_block_stats": (C.c_int, [C.POINTER(StemBlockDesc), _P, _I32, _I32, _P]),
+    "mcamd_stem_block_plan_info": (C.c_int, [C.POINTER(StemBlockDesc), C.POINTER(_I32)]),
     "mcamd_nchw_f32_to_nhwc4_split": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
     "mcamd_pack_stem_split": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
     "mcamd_nchw_f32_to_padded_nhwc_f16": (C.c_int, [_P, _I32, _I32, _I32, _I32, _F, _P, _I32, _I32, _P, _P]),

@@ -12,7 +12,7 @@
 //   C        = sum_m v_m v_m^T,   S = sum_m v_m                  (stem_gram_kernel: image only, MFMA F^T F)
 //   mean_n   = W[n] . S / M,      E[y^2]_n = W[n]^T C W[n] / M   (stem_coeffs_kernel, double)
 //   forward  : image -> y (registers) -> scale/shift -> 2x2 max -> LeakyReLU -> pooled fp16 output   (one pass)
-//   backward : recompute y and the window argmax from the image, g_z = G * leaky'(z) at the argmax position,
+//   backward : recompute y and the window argmax from the image, g_z = fp16(G * leaky'(z)) at the argmax position,
 //              T[n][k] = sum_m g_z[m][n] v_m[k] (MFMA), dbeta_n = sum_m g_z[m][n]                     (one pass)
 //              dgamma_n = invstd_n (W[n] . T[n] - mean_n dbeta_n)
 //              dW[n][k] = gamma_n invstd_n (T[n][k] - dbeta_n/M S[k] - dgamma_n/M invstd_n ((W C)[n][k] - mean_n S[k]))
@@ -564,9 +564,12 @@ __global__ __launch_bounds__(512) void stem_block_bwd_kernel(StemBlockArgs a) {
             const float z10 = __builtin_fmaf(acc1[2 * q], sc, sh), z11 = __builtin_fmaf(acc1[2 * q + 1], sc, sh);
             const float m0 = fmaxf(z00, z01), m1 = fmaxf(z10, z11);
             const float best = fmaxf(m0, m1);
-            const float gz = (float)gq[q] * (best > 0.f ? 1.f : a.slope);
-            sb += gz;
-            const unsigned gh = (unsigned)__builtin_bit_cast(unsigned short, (half_t)gz);
+            // g_z is rounded to fp16 ONCE and that value enters both T and dbeta: dgamma and dW subtract mean * dbeta and
+            // dbeta / M * S from W . T and T, and with the unrounded product in dbeta the rounding errors of T no longer
+            // cancel in those differences (they were amplified by mean / std of the channel and of the image)
+            const half_t gzh = (half_t)((float)gq[q] * (best > 0.f ? 1.f : a.slope));
+            sb += (float)gzh;
+            const unsigned gh = (unsigned)__builtin_bit_cast(unsigned short, gzh);
             const unsigned w0 = z00 >= z01 ? gh : gh << 16, w1 = z10 >= z11 ? gh : gh << 16;
             g0[q] = m0 >= m1 ? w0 : 0u;
             g1[q] = m0 >= m1 ? 0u : w1;
@@ -715,13 +718,46 @@ __global__ __launch_bounds__(256) void nhwc4_split_kernel(const float* src, int 
     }
 }
 
-int stats_grid(const mcamd_stem_block_desc* d) {
-    const long long nunits = (long long)d->B * (d->H / 2) * (d->W / 32);
-    const long long want = (nunits + 7) / 8;      // >= one pass of 2 units per wave
-    return (int)(want < 1024 ? (want < 1 ? 1 : want) : 1024);
+// The grid of each persistent launch, decided here and nowhere else (mcamd_stem_block_plan_info reports the same).
+// A work item is a unit (32 columns x 2 conv rows) or, for the Gram pass, a step (32 columns x 1 row); a workgroup
+// takes `per_wg` items per pass and the grid is what one pass over `div`-item shares needs, up to `cap` workgroups.
+struct LaunchPlan {
+    int grid;
+    long long items;
+    int per_pass;       // items all workgroups take in one pass: grid * per_wg
+    int per_wave;       // items the busiest wave takes over all passes
+};
+LaunchPlan launch_plan(int which, int B, int H, int W) {
+    static const struct { int div, cap, per_wg, waves; } k[MCAMD_STEM_PLAN_LAUNCHES] = {
+        {8, 2048, 16, 4},           // MCAMD_STEM_PLAN_FWD: 4 waves x UN = 4 (sized for one pass of 2 units per wave)
+        {8, 2048, 8, 4},            // _FWD_PLANES: planes >= 2 or split operands, 4 waves x UN = 2
+        {8, 1024, 8, 4},            // _STATS: 4 waves x UN = 2
+        {32, kGramWgs, 32, 8},      // _GRAM: 8 waves x a batch of 4 steps; 2 workgroups per CU: 223 vs 239 us
+        {32, kBwdWgs, 8, 8},        // _BWD: 8 waves x 1 unit (sized for 4 units per wave)
+    };
+    LaunchPlan p;
+    p.items = which == MCAMD_STEM_PLAN_GRAM ? (long long)B * H * (W / 32) : (long long)B * (H / 2) * (W / 32);
+    const long long want = (p.items + k[which].div - 1) / k[which].div;
+    p.grid = (int)(want < k[which].cap ? (want < 1 ? 1 : want) : k[which].cap);
+    p.per_pass = p.grid * k[which].per_wg;
+    const long long passes = (p.items + p.per_pass - 1) / p.per_pass;
+    p.per_wave = (int)(passes * (k[which].per_wg / k[which].waves));
+    return p;
 }
 
 }  // namespace
+
+extern "C" int mcamd_stem_block_plan_info(const mcamd_stem_block_desc* d, int32_t out[MCAMD_STEM_PLAN_INFO_N]) {
+    MCAMD_REQUIRE(d && out, "stem_block_plan_info: null argument");
+    MCAMD_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0, "stem_block_plan_info: non-positive dimension");
+    MCAMD_REQUIRE(d->W % 32 == 0 && d->H % 2 == 0, "stem_block_plan_info: needs W %% 32 == 0 and an even H (got %d x %d)", d->H, d->W);
+    MCAMD_REQUIRE((long long)d->B * d->H * d->W < (1ll << 31), "stem_block_plan_info: more than 2^31 output pixels");
+    for (int which = 0; which < MCAMD_STEM_PLAN_LAUNCHES; ++which) {
+        const LaunchPlan p = launch_plan(which, d->B, d->H, d->W);
+        out[4 * which] = p.grid, out[4 * which + 1] = (int32_t)p.items, out[4 * which + 2] = p.per_pass, out[4 * which + 3] = p.per_wave;
+    }
+    return MCAMD_OK;
+}
 
 extern "C" size_t mcamd_stem_block_workspace_bytes(void) { return carve().total; }
 
@@ -757,9 +793,7 @@ extern "C" int mcamd_stem_block_fwd(const mcamd_stem_block_desc* d, void* worksp
         StemBlockArgs g = a;
         g.nunits = (long long)d->B * d->H * g.Wb;
         g.slab = (float*)(ws + c.gram_slab);
-        long long want = (g.nunits + 31) / 32;    // >= one batch of 4 steps per wave
-        const int gmax = kGramWgs;   // 2 workgroups per CU: 223 vs 239 us
-        const int grid = (int)(want < gmax ? (want < 1 ? 1 : want) : gmax);
+        const int grid = launch_plan(MCAMD_STEM_PLAN_GRAM, d->B, d->H, d->W).grid;
         hipLaunchKernelGGL(stem_gram_kernel, dim3(grid), dim3(512), 0, st, g);
         MCAMD_LAUNCH_CHECK("stem_gram");
         hipLaunchKernelGGL(slab_sum_kernel, dim3(2304 / 16), dim3(256), 0, st, (const float*)g.slab, grid, 2304,
@@ -773,8 +807,7 @@ extern "C" int mcamd_stem_block_fwd(const mcamd_stem_block_desc* d, void* worksp
     a.out = (half_t*)d->dst;
     a.out_ld = d->dst_ld, a.out_choff = d->dst_choff;
     a.nunits = (long long)d->B * a.H2 * a.Wb;
-    long long want = (a.nunits + 7) / 8;          // >= one pass of 2 units per wave
-    const int grid = (int)(want < 2048 ? (want < 1 ? 1 : want) : 2048);
+    const int grid = launch_plan(split || d->planes >= 2 ? MCAMD_STEM_PLAN_FWD_PLANES : MCAMD_STEM_PLAN_FWD, d->B, d->H, d->W).grid;
     if (split) {
         if (d->planes == 3) hipLaunchKernelGGL((stem_block_fwd_kernel<2, 3, true>), dim3(grid), dim3(256), 0, st, a);
         else if (d->planes == 2) hipLaunchKernelGGL((stem_block_fwd_kernel<2, 2, true>), dim3(grid), dim3(256), 0, st, a);
@@ -801,7 +834,7 @@ extern "C" int mcamd_nchw_f32_to_nhwc4_split(const float* src, int32_t B, int32_
 
 extern "C" int32_t mcamd_stem_block_stats_rows(const mcamd_stem_block_desc* d) {
     if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0) return 0;
-    return stats_grid(d);
+    return launch_plan(MCAMD_STEM_PLAN_STATS, d->B, d->H, d->W).grid;
 }
 
 extern "C" int mcamd_stem_block_stats(const mcamd_stem_block_desc* d, float* stats, int32_t stats_rows, int32_t stats_ld,
@@ -819,7 +852,7 @@ extern "C" int mcamd_stem_block_stats(const mcamd_stem_block_desc* d, float* sta
     MCAMD_REQUIRE(d->cout == 0 || d->cout == 32, "stem_block_stats: 32 filters (got %d)", d->cout);
     const bool split = d->x_lo != nullptr || d->wp_lo != nullptr;
     MCAMD_REQUIRE(!split || (d->x_lo && d->wp_lo), "stem_block_stats: split operands need both x_lo and wp_lo");
-    const int grid = stats_grid(d);
+    const int grid = launch_plan(MCAMD_STEM_PLAN_STATS, d->B, d->H, d->W).grid;
     MCAMD_REQUIRE(stats_rows == grid && stats_ld >= 32, "stem_block_stats: slab must be [%d][2][>= 32] (got %d rows, ld %d)",
                   grid, stats_rows, stats_ld);
     StemBlockArgs a;
@@ -858,8 +891,7 @@ extern "C" int mcamd_stem_block_bwd(const mcamd_stem_block_desc* d, void* worksp
     a.g_ld = d->g_ld, a.g_choff = d->g_choff;
     a.nunits = (long long)d->B * a.H2 * a.Wb;
     a.slab = (float*)(ws + c.bwd_slab);
-    long long want = (a.nunits + 31) / 32;        // >= 4 units per wave
-    const int grid = (int)(want < kBwdWgs ? (want < 1 ? 1 : want) : kBwdWgs);
+    const int grid = launch_plan(MCAMD_STEM_PLAN_BWD, d->B, d->H, d->W).grid;
     hipLaunchKernelGGL(stem_block_bwd_kernel, dim3(grid), dim3(512), 0, st, a);
     MCAMD_LAUNCH_CHECK("stem_block_bwd");
     hipLaunchKernelGGL(slab_sum_kernel, dim3(3104 / 16), dim3(256), 0, st, (const float*)a.slab, grid, 3104,

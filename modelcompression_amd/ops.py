@@ -533,6 +533,20 @@ def stem_block_stats_rows(B, H, W):
     return int(L.lib().mcamd_stem_block_stats_rows(C.byref(d)))
 
 
+StemLaunchInfo = collections.namedtuple("StemLaunchInfo", "grid items per_pass per_wave passes")
+StemPlanInfo = collections.namedtuple("StemPlanInfo", "fwd fwd_planes stats gram bwd")
+
+
+def stem_block_plan_info(B, H, W):
+    """How the first block's five persistent launches divide B x H x W (workgroups, work items, items per pass, items of
+    the busiest wave, passes): mcamd_stem_block_plan_info, the launches' own grid function.  Needs no GPU."""
+    d = StemBlockDesc()
+    d.B, d.H, d.W = B, H, W
+    out = (C.c_int32 * L.STEM_PLAN_INFO_N)()
+    check(L.lib().mcamd_stem_block_plan_info(C.byref(d), out), "mcamd_stem_block_plan_info")
+    return StemPlanInfo(*(StemLaunchInfo(*out[4 * i:4 * i + 4], -(-out[4 * i + 1] // out[4 * i + 2])) for i in range(5)))
+
+
 def stem_block_stats(B, H, W, x, wp, stats, x_lo=None, wp_lo=None):
     """Per-channel partial sums / sums of squares of the first block's conv output (split operands with `x_lo` /
     `wp_lo`) into the fp32 slab `stats` [stem_block_stats_rows][2][ld]: what bn_coeffs takes.  Nothing else is written."""
