@@ -1114,10 +1114,23 @@ int mcamd_block_mask(const int32_t* keep, const float* old_mask, int32_t cout, i
  *   MCAMD_WZ_FP8   the e4m3 code mcamd_pack_q8 stores, with that packer's exponent per filter,   1 byte
  * and every other weight reads back as +0.  A record has bit words iff 8 ceil(n / 64) + kept elem < n elem; otherwise
  * all n values are stored (0 for a weight that is not kept).  Reading: fp32 as is, fp16 widened, e4m3 as
- * value(code) 2^-exponent (exact in fp32 whenever that is a normal number). */
+ * value(code) 2^-exponent (exact in fp32 whenever that is a normal number).
+ *
+ * A fourth kind stores a layer tied by weight sharing (below):
+ *   MCAMD_WZ_CODE  the codebook index of the weight, 1 byte in the passes, `width` bits in the file
+ * A weight of this kind is KEPT iff its MASK value is non-zero (every weight when there is no mask): a shared value may
+ * be exactly 0, so the bits cannot come from the values.  Its record carries `bits` (1..8) in the uint32 behind the flags
+ * (0 for the other kinds) and, behind the per-channel arrays, float32 codebook[2^bits]; then the bit words, then the codes
+ * of the kept weights (or of all n, 0 where not kept) in flat order, `width` bits each, code i in bits
+ * [width (i % (8 / width)), +width) of byte i / (8 / width), width = the smallest of 1, 2, 4, 8 that is >= bits.  It has
+ * bit words iff kept < n (a code cannot say "not kept", so the size rule of the other kinds does not apply).  The passes
+ * see one byte per code: pack reads w = uint8 codes[n] and stores the kept ones by the same rule; unpack writes
+ * w = uint8 codes[n] (0 where the bit is clear) and the mask.  A file whose header payload is MCAMD_WZ_CODE stores its
+ * untied layers as MCAMD_WZ_FP32. */
 #define MCAMD_WZ_FP32 0
 #define MCAMD_WZ_FP16 1
 #define MCAMD_WZ_FP8 2
+#define MCAMD_WZ_CODE 4 /* (3 is not a kind) */
 #define MCAMD_WZ_F_BN 1u
 #define MCAMD_WZ_F_BITS 2u
 #define MCAMD_WZ_BLOCK_WORDS 64 /* bit words (of 64 weights) per workgroup of both passes */
@@ -1131,14 +1144,15 @@ int mcamd_block_mask(const int32_t* keep, const float* old_mask, int32_t cout, i
  * and val0 are any offsets whose range lies inside the arrays given (checked).  All three arrays may be one buffer
  * holding the file as it is, since every array of a record starts at a multiple of 8 bytes. */
 typedef struct mcamd_wz_seg {
-    void* w;         /* fp32 OIHW [cout][n / cout]: the master (pack, read) or the weights to fill (unpack, written) */
+    void* w;         /* fp32 OIHW [cout][n / cout]: the master (pack, read) or the weights to fill (unpack, written);
+                        MCAMD_WZ_CODE: uint8 codes [n] */
     void* mask;      /* fp32 0/1 mask: read by pack (NULL = all ones); written by unpack unless NULL */
     int64_t n;       /* weights, > 0, a multiple of cout */
     int64_t word0;   /* first bit word of the segment in `words` */
     int64_t val0;    /* unpack: byte offset of the segment's values in `values`, a multiple of 8.  pack: unused */
     int64_t kept;    /* unpack, dense == 0: number of values stored (<= n).  pack: unused */
     int32_t cout;
-    int32_t kind;    /* MCAMD_WZ_FP32 / _FP16 / _FP8 */
+    int32_t kind;    /* MCAMD_WZ_FP32 / _FP16 / _FP8 / _CODE */
     int32_t exp0;    /* first exponent of the segment in `exps` */
     int32_t dense;   /* unpack: 1 = the record has no bit words, all n values are stored.  pack: unused */
     int32_t block0;  /* first workgroup of the segment */
@@ -1166,6 +1180,73 @@ int mcamd_wz_pack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_
 int mcamd_wz_unpack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, const uint64_t* words,
                     int64_t words_cap, const int32_t* exps, int64_t exps_cap, const void* values, int64_t values_bytes,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Weight sharing (trained quantisation by k-means; an addition beyond the reference).
+ * ------------------------------------------------------------------------- */
+/* Per layer, over its KEPT weights (mask value != 0; every weight when the layer has no mask), K = 2^bits, bits 1..8.
+ * The arithmetic, operation by operation (float64 unless said otherwise, no contraction):
+ *   range    lo, hi = minimum and maximum of the kept fp32 weights.  A layer with no kept weight gets a codebook of K
+ *            zeros; its codes are never read.
+ *   init     c[k] = fp32(lo + ((hi - lo) * k) / (K - 1)), k = 0..K-1, in exactly that order (the linear initialisation).
+ *   assign   code = the number of j in 0..K-2 with mid[j] < w, mid[j] = (double(c[j]) + double(c[j+1])) / 2, w widened to
+ *            double: ties go to the lower index, equal centroids are harmless.  The codebook is non-decreasing (init
+ *            makes it so and update keeps it so), so the count is found by bisection: np.searchsorted(mid, w, "left").
+ *            Every operation is exact, so the codes are bit-exact given the centroids.
+ *   update   per cluster, sum = the float64 sum of its members, count = their number; c[k] = fp32(sum / count); an empty
+ *            cluster keeps its centroid.  No floating-point atomics: the layer is cut into slabs of MCAMD_WS_SLAB
+ *            consecutive weights, one workgroup sums one slab in a fixed order, and the slab sums are added in slab
+ *            order.  Order inside a slab, for cluster k: the slab is cut into S = 256 / K sub-slabs of MCAMD_WS_SLAB / S
+ *            consecutive weights; each sub-slab's members are added in index order starting from 0.0, then the S sub-slab
+ *            sums are added in sub-slab order starting from 0.0.  The result is bit-reproducible from run to run.
+ *   kmeans   init, `iters` rounds of assign then update, and one last assign against the codebook returned.
+ *   project  with the codes fixed: update, then w = c[code] on every kept weight.  Weights that are not kept are not
+ *            written; an empty cluster changes nothing.  `count` copies of one fp32 value sum exactly in float64 for
+ *            count <= 2^29 whatever the order, so on a layer that is already tied the projection is the identity, bit
+ *            for bit.
+ *   expand   w = c[code] on kept weights and +0 elsewhere.
+ * tests/wshare_ref.py restates this in numpy. */
+#define MCAMD_WS_SLAB 4096 /* weights per workgroup */
+
+/* One layer of a pass.  All layers go through ONE table: a HOST array for the checks and the grid size and its DEVICE
+ * copy for the kernels.  Running sums over the table, in order (checked):
+ *   slab0  += ceil(n / MCAMD_WS_SLAB)
+ *   cb0    += K                             the layer's K entries in `codebook`, `sums` and `counts`
+ *   part0  += ceil(n / MCAMD_WS_SLAB) * K   the layer's slab sums in the workspace
+ * w and mask are 16-byte aligned, codes 4-byte aligned (checked). */
+typedef struct mcamd_ws_seg {
+    void* w;        /* fp32 [n]: read by init / iterate / assign, read and written by project, written by expand */
+    void* mask;     /* fp32 0/1 mask, or NULL = every weight is kept */
+    void* codes;    /* uint8 [n]: written by iterate / assign, read by project / expand; codes of weights that are not
+                       kept are written as 0 and never read.  init alone takes NULL */
+    int64_t n;      /* weights, > 0 */
+    int64_t part0;
+    int32_t K;      /* 2, 4, 8, ..., 256 */
+    int32_t cb0;
+    int32_t slab0;
+    int32_t reserved;
+} mcamd_ws_seg;
+
+/* workspace of every pass below for a table of `nseg` layers, `nslabs` slabs and `parts` slab sums (the final sums) */
+size_t mcamd_ws_workspace_bytes(int64_t nslabs, int64_t parts, int32_t nseg);
+
+/* range + init: codebook[cb0 + k] of every layer.  cb_cap = entries of `codebook` (and of `sums` / `counts` below). */
+int mcamd_ws_init(const mcamd_ws_seg* segs, const mcamd_ws_seg* segs_dev, int32_t nseg, float* codebook, int64_t cb_cap,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* One round: assign against `codebook` (codes written), then update `codebook` in place.  sums[cb0 + k] (float64) and
+ * counts[cb0 + k] (int64) receive the cluster sums and sizes of the round.  Called `iters` times with nothing read back. */
+int mcamd_ws_iterate(const mcamd_ws_seg* segs, const mcamd_ws_seg* segs_dev, int32_t nseg, float* codebook, int64_t cb_cap,
+                     double* sums, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* assign alone: the codes against `codebook`. */
+int mcamd_ws_assign(const mcamd_ws_seg* segs, const mcamd_ws_seg* segs_dev, int32_t nseg, const float* codebook, int64_t cb_cap,
+                    void* stream);
+/* project: `codebook` is updated in place to the cluster means and written back to the kept weights.  One call for the
+ * whole model, no read-back: the training step calls it behind every optimizer step. */
+int mcamd_ws_project(const mcamd_ws_seg* segs, const mcamd_ws_seg* segs_dev, int32_t nseg, float* codebook, int64_t cb_cap,
+                     double* sums, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* expand: w = codebook[code] on kept weights, +0 elsewhere.  A code >= K reads entry K - 1 (never outside the layer's). */
+int mcamd_ws_expand(const mcamd_ws_seg* segs, const mcamd_ws_seg* segs_dev, int32_t nseg, const float* codebook, int64_t cb_cap,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,3 +32,11 @@ def _materialise_cfg():
 YOLOV2_VOC_CFG = _materialise_cfg()
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # weight sharing (share.py, an addition beyond the reference), re-exported without importing torch with the package
+    if name in ("kmeans_share", "are_codebooks_consistent"):
+        from . import share
+        return getattr(share, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -166,6 +166,12 @@ class WzSeg(C.Structure):
                 ("block0", C.c_int32), ("reserved", C.c_int32)]
 
 
+class WsSeg(C.Structure):
+    """mcamd_ws_seg (include/mcamd.h)."""
+    _fields_ = [("w", C.c_void_p), ("mask", C.c_void_p), ("codes", C.c_void_p), ("n", C.c_int64), ("part0", C.c_int64),
+                ("K", C.c_int32), ("cb0", C.c_int32), ("slab0", C.c_int32), ("reserved", C.c_int32)]
+
+
 EPI_RAW_F16, EPI_NCHW_F32, EPI_PAD_F16, EPI_RAW_F32 = 0, 1, 2, 3
 DST_PLAIN, DST_POOL, DST_REORG = 0, 1, 2
 WGRAD_GENERIC, WGRAD_STEM, WGRAD_WIN, WGRAD_NINE, WGRAD_NINE_WIDE = 0, 1, 2, 3, 4      # mcamd_conv_wgrad_plan_info: family
@@ -173,9 +179,10 @@ WFIN_ROW, WFIN_VEC, WFIN_GENERIC = 0, 1, 2                                      
 WGRAD_PLAN_INFO_N = 13
 STEM_PLAN_FWD, STEM_PLAN_FWD_PLANES, STEM_PLAN_STATS, STEM_PLAN_GRAM, STEM_PLAN_BWD = 0, 1, 2, 3, 4    # mcamd_stem_block_plan_info
 STEM_PLAN_INFO_N = 20
-WZ_FP32, WZ_FP16, WZ_FP8 = 0, 1, 2                                                     # mcamd_wz_seg.kind
+WZ_FP32, WZ_FP16, WZ_FP8, WZ_CODE = 0, 1, 2, 4                                         # mcamd_wz_seg.kind
 WZ_F_BN, WZ_F_BITS = 1, 2                                                              # record flags of a .mcz file
 WZ_BLOCK_WORDS = 64
+WS_SLAB = 4096                                                                         # MCAMD_WS_SLAB
 
 # name -> (restype, argtypes); the complete list of symbols include/mcamd.h declares.
 _P, _I32, _I64, _F, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -288,6 +295,12 @@ SIGNATURES = {
     "mcamd_wz_workspace_bytes": (_SZ, [_I64, _I32]),
     "mcamd_wz_pack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P, _SZ, _P]),
     "mcamd_wz_unpack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "mcamd_ws_workspace_bytes": (_SZ, [_I64, _I64, _I32]),
+    "mcamd_ws_init": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _SZ, _P]),
+    "mcamd_ws_iterate": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "mcamd_ws_assign": (C.c_int, [_P, _P, _I32, _P, _I64, _P]),
+    "mcamd_ws_project": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "mcamd_ws_expand": (C.c_int, [_P, _P, _I32, _P, _I64, _P]),
 }
 
 _lib = None

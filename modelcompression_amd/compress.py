@@ -4,9 +4,13 @@ A Darknet .weights file stores every conv weight as a dense float32, zeros inclu
 a bitmask of the non-zero weights and only those weights, as fp32, fp16 or e4m3 codes -- exactly what the engine the file
 is written for consumes, so the file is lossless for that engine:
 
-    save_compressed(model, path, payload="fp16", layers=None)
+    save_compressed(model, path, payload="fp16", layers=None)       # payload "shared": codebooks + narrow codes (below)
     load_compressed(model, path, set_masks=True) -> masks
     compressed_info(path) -> dict
+
+Payload "shared"  stores every layer Darknet.set_codebooks tied as the bitmask of its MASK, its fp32 codebook
+and one code of 1, 2, 4 or 8 bits per kept weight, and every other layer as fp32; reading it gives back the tied model's
+fp32 weights exactly, with its masks and codebooks.
 
 A model on the GPU is packed and expanded by the device passes of csrc/wpack.hip (ops.wz_pack / ops.wz_unpack: all layers
 through one segment table); a model on the CPU takes the torch / numpy path below, which writes and reads the same bytes.
@@ -22,13 +26,13 @@ from ._lib import McamdError
 
 MAGIC = b"MCZW"
 VERSION = 1
-PAYLOADS = {"fp32": L.WZ_FP32, "fp16": L.WZ_FP16, "fp8": L.WZ_FP8}
+PAYLOADS = {"fp32": L.WZ_FP32, "fp16": L.WZ_FP16, "fp8": L.WZ_FP8, "shared": L.WZ_CODE}
 KIND_NAMES = {v: k for k, v in PAYLOADS.items()}
-ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1}
-_CODE_DTYPE = {L.WZ_FP32: "<u4", L.WZ_FP16: "<u2", L.WZ_FP8: "u1"}
+ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1, L.WZ_CODE: 1}      # (WZ_CODE: in the device passes; `width` bits in the file)
+_CODE_DTYPE = {L.WZ_FP32: "<u4", L.WZ_FP16: "<u2", L.WZ_FP8: "u1", L.WZ_CODE: "u1"}
 _MAG_BITS = {L.WZ_FP32: 0x7FFFFFFF, L.WZ_FP16: 0x7FFF, L.WZ_FP8: 0x7F}
 _HEADER = struct.Struct("<4sIIIq")          # magic, version, payload, records, seen
-_RECORD = struct.Struct("<4iIIQ")           # cout, cin, kh, kw, flags, 0, kept
+_RECORD = struct.Struct("<4iIIQ")           # cout, cin, kh, kw, flags, bits (WZ_CODE; 0 otherwise), kept
 
 
 def _pad8(nbytes):
@@ -36,8 +40,39 @@ def _pad8(nbytes):
 
 
 def has_bits(n, kept, kind):
-    """The bitmask-or-dense rule: a record carries bit words only when that is smaller."""
+    """The bitmask-or-dense rule: a record carries bit words only when that is smaller.  A record of codes carries them
+    whenever a weight is not kept: a code cannot say so."""
+    if kind == L.WZ_CODE:
+        return kept < n
     return 8 * ((n + 63) // 64) + kept * ELEM[kind] < n * ELEM[kind]
+
+
+def code_width(bits):
+    """Bits per stored code: the smallest of 1, 2, 4, 8 that holds `bits`."""
+    return next(w for w in (1, 2, 4, 8) if w >= bits)
+
+
+def _pack_codes(codes, width):
+    """uint8 codes -> bytes: code i in bits [width (i % per), +width) of byte i // per, per = 8 // width."""
+    per = 8 // width
+    if per == 1:
+        return np.ascontiguousarray(codes, dtype=np.uint8)
+    padded = np.zeros((codes.size + per - 1) // per * per, dtype=np.uint8)
+    padded[:codes.size] = codes
+    out = np.zeros(padded.size // per, dtype=np.uint8)
+    for j in range(per):
+        out |= (padded[j::per] << np.uint8(width * j)).astype(np.uint8)
+    return out
+
+
+def _unpack_codes(packed, width, count):
+    per = 8 // width
+    if per == 1:
+        return np.ascontiguousarray(packed[:count], dtype=np.uint8)
+    out = np.empty(packed.size * per, dtype=np.uint8)
+    for j in range(per):
+        out[j::per] = (packed >> np.uint8(width * j)) & np.uint8((1 << width) - 1)
+    return out[:count]
 
 
 def is_compressed(path):
@@ -95,6 +130,19 @@ def _codes_cpu(w, mask, kind):
     return scaled.to(torch.float8_e4m3fn).contiguous().view(torch.uint8).numpy().reshape(-1), e.numpy().astype("<i4")
 
 
+def _encode_shared_cpu(codes, mask):
+    codes = codes.detach().cpu().numpy().reshape(-1)
+    n = codes.size
+    keep = np.ones(n, dtype=bool) if mask is None else (mask.detach().cpu().numpy().reshape(-1) != 0)
+    kept, words = int(keep.sum()), None
+    if has_bits(n, kept, L.WZ_CODE):
+        bits = np.zeros((n + 63) // 64 * 64, dtype=np.uint8)
+        bits[:n] = keep
+        words = np.packbits(bits, bitorder="little").view("<u8")
+        codes = codes[keep]
+    return dict(kept=kept, exps=None, words=words, values=np.ascontiguousarray(codes))
+
+
 def _encode_cpu(w, mask, kind):
     codes, exps = _codes_cpu(w, mask, kind)
     n = codes.size
@@ -128,6 +176,14 @@ def _decode_cpu(rec, what):
     """(fp32 weights, fp32 mask) as flat numpy arrays from a parsed record with its payload."""
     n, kind = rec["n"], rec["kind"]
     dt = np.dtype(_CODE_DTYPE[kind])
+    if kind == L.WZ_CODE:
+        keep = np.ones(n, dtype=bool)
+        if rec["words"] is not None:
+            keep = np.unpackbits(rec["words"].view(np.uint8), bitorder="little")[:n].astype(bool)
+        codes = np.zeros(n, dtype=np.uint8)
+        codes[keep] = rec["codes"]
+        rec["codes_full"] = codes
+        return np.where(keep, rec["codebook"][codes], np.float32(0.0)).astype(np.float32), keep.astype(np.float32)
     if rec["words"] is not None:
         bits = np.unpackbits(rec["words"].view(np.uint8), bitorder="little")
         keep = bits[:n].astype(bool)
@@ -155,6 +211,8 @@ def _kinds(model, payload, layers):
         raise McamdError("payload must be one of %r (got %r)" % (sorted(PAYLOADS), payload))
     convs = _conv_blocks(model)
     kind = PAYLOADS[payload]
+    if kind == L.WZ_CODE:         # the layers set_codebooks tied as codes, every other layer as it is
+        return convs, [L.WZ_CODE if getattr(conv, "share_flag", False) else L.WZ_FP32 for _, conv, _ in convs]
     if kind != L.WZ_FP8:
         return convs, [kind] * len(convs)
     chosen = set(default_fp8_layers(model) if layers is None else [int(i) for i in layers])
@@ -175,6 +233,9 @@ def _encode_device(convs, kinds):
     items = []
     for (_, conv, _), kind in zip(convs, kinds):
         w, m = conv.weight.data, _mask_of(conv)
+        if kind == L.WZ_CODE:
+            items.append(dict(w=conv.codes.contiguous(), mask=m.contiguous().float() if m is not None else None, kind=kind))
+            continue
         if w.dtype != torch.float32:
             raise McamdError("compressed model files are written from fp32 master weights")
         items.append(dict(w=w.contiguous(), mask=m.contiguous().float() if m is not None else None, kind=kind))
@@ -219,21 +280,27 @@ def save_compressed(model, path, payload="fp16", layers=None):
     if all(conv.weight.is_cuda for _, conv, _ in convs):
         encoded = _encode_device(convs, kinds)
     else:
-        encoded = [_encode_cpu(conv.weight.data.cpu(), (_mask_of(conv).cpu() if _mask_of(conv) is not None else None), kind)
+        encoded = [_encode_shared_cpu(conv.codes, _mask_of(conv)) if kind == L.WZ_CODE else
+                   _encode_cpu(conv.weight.data.cpu(), (_mask_of(conv).cpu() if _mask_of(conv) is not None else None), kind)
                    for (_, conv, _), kind in zip(convs, kinds)]
     with open(path, "wb") as f:
         f.write(_HEADER.pack(MAGIC, VERSION, PAYLOADS[payload], len(convs), int(model.seen)))
         for (_, conv, bn), kind, rec in zip(convs, kinds, encoded):
             cout, cin, kh, kw = conv.weight.shape
             flags = (L.WZ_F_BN if bn is not None else 0) | (L.WZ_F_BITS if rec["words"] is not None else 0) | (kind << 8)
-            f.write(_RECORD.pack(cout, cin, kh, kw, flags, 0, rec["kept"]))
+            bits = 0
+            if kind == L.WZ_CODE:
+                bits = int(conv.codebook.numel()).bit_length() - 1
+            f.write(_RECORD.pack(cout, cin, kh, kw, flags, bits, rec["kept"]))
             for a in _small_arrays(conv, bn):
                 _write_array(f, a)
             if kind == L.WZ_FP8:
                 _write_array(f, rec["exps"].astype("<i4", copy=False))
+            if kind == L.WZ_CODE:
+                _write_array(f, conv.codebook.detach().cpu().numpy().astype("<f4", copy=False))
             if rec["words"] is not None:
                 _write_array(f, rec["words"])
-            _write_array(f, rec["values"])
+            _write_array(f, _pack_codes(rec["values"], code_width(bits)) if kind == L.WZ_CODE else rec["values"])
 
 
 def _parse(path, payload=True):
@@ -272,16 +339,18 @@ def _parse_open(f, path, size, payload):
     for r in range(nrec):
         what = "conv%d" % (r + 1)
         start = pos
-        cout, cin, kh, kw, flags, _, kept = _RECORD.unpack(head(_RECORD.size, what))
+        cout, cin, kh, kw, flags, cbits, kept = _RECORD.unpack(head(_RECORD.size, what))
         kind = (flags >> 8) & 0xFF
         if min(cout, cin, kh, kw) <= 0 or kind not in KIND_NAMES or flags & ~(0xFF00 | L.WZ_F_BN | L.WZ_F_BITS):
             raise McamdError("%s: %s: damaged record header" % (path, what))
+        if kind == L.WZ_CODE and (pay != L.WZ_CODE or not 1 <= cbits <= 8):
+            raise McamdError("%s: %s: damaged record header (codes of %d bits in a %r file)" % (path, what, cbits, KIND_NAMES[pay]))
         n = cout * cin * kh * kw
         bits = bool(flags & L.WZ_F_BITS)
         if kept > n or bits != has_bits(n, kept, kind):
             raise McamdError("%s: %s: damaged record header (kept %d of %d weights)" % (path, what, kept, n))
         rec = dict(shape=(cout, cin, kh, kw), cout=cout, n=n, bn=bool(flags & L.WZ_F_BN), bits=bits, kind=kind, kept=kept,
-                   small=[], exps=None, words=None, values=None, exp0=0, word0=0)
+                   small=[], exps=None, words=None, values=None, exp0=0, word0=0, code_bits=None, codebook=None, codes=None)
         for _ in range(4 if rec["bn"] else 1):
             o = take(_pad8(4 * cout), what + " per-channel arrays")
             if raw is not None:
@@ -290,14 +359,30 @@ def _parse_open(f, path, size, payload):
             o = rec["exp0"] = take(_pad8(4 * cout), what + " exponents")
             if raw is not None:
                 rec["exps"] = np.frombuffer(raw, "<i4", cout, o)
+        if kind == L.WZ_CODE:
+            rec["code_bits"] = cbits
+            o = take(_pad8(4 << cbits), what + " codebook")
+            if raw is not None:
+                rec["codebook"] = np.frombuffer(raw, "<f4", 1 << cbits, o)
         if bits:
             o = rec["word0"] = take(8 * ((n + 63) // 64), what + " bit words")
             if raw is not None:
                 rec["words"] = np.frombuffer(raw, "<u8", (n + 63) // 64, o)
         stored = kept if bits else n
-        rec["val0"] = take(_pad8(stored * ELEM[kind]), what + " values")
-        if raw is not None:
-            rec["values"] = np.frombuffer(raw, _CODE_DTYPE[kind], stored, rec["val0"])
+        if kind == L.WZ_CODE:
+            width = code_width(cbits)
+            nbytes = (stored * width + 7) // 8
+            rec["val0"] = take(_pad8(nbytes), what + " codes")
+            if raw is not None:
+                rec["values"] = np.frombuffer(raw, "u1", nbytes, rec["val0"])
+                rec["codes"] = _unpack_codes(rec["values"], width, stored)
+                if stored and int(rec["codes"].max()) >= 1 << cbits:
+                    raise McamdError("%s: %s: a code of %d with a codebook of %d entries" % (path, what, int(rec["codes"].max()),
+                                                                                          1 << cbits))
+        else:
+            rec["val0"] = take(_pad8(stored * ELEM[kind]), what + " values")
+            if raw is not None:
+                rec["values"] = np.frombuffer(raw, _CODE_DTYPE[kind], stored, rec["val0"])
         rec["bytes"] = pos - start
         recs.append(rec)
     if pos != size:
@@ -309,7 +394,9 @@ def load_compressed(model, path, set_masks=True):
     """Fill `model` from an .mcz file: fp32 master weights (fp32 as is, fp16 widened, e4m3 as value 2^-exponent), BatchNorm
     tensors, biases and `seen`.  Every record's shape is checked against the cfg before anything is written.  Returns the
     list of kept-bit masks (all ones for a record without a bitmask) and, when `set_masks` and at least one record has a
-    bitmask, hands it to model.set_masks."""
+    bitmask, hands it to model.set_masks.  A "shared" file: the codes are widened on the host, expanded
+    through the codebooks on the device (ops.WsTable.expand), and -- with `set_masks` -- the codebooks are set as
+    Darknet.set_codebooks sets them, so that retraining and save_compressed(payload="shared") go on from the file."""
     convs = _conv_blocks(model)
     info = _parse(path)
     recs = info["records"]
@@ -322,29 +409,46 @@ def load_compressed(model, path, set_masks=True):
                 " with BatchNorm" if bn is not None else ""))
     for (i, _, _), rec in zip(convs, recs):           # on the host, where the words are: the same refusal on either path
         _check_words(rec, "%s: conv%d" % (path, i))
-    masks = []
+    masks, books = [], [None] * len(recs)
     if all(conv.weight.is_cuda for _, conv, _ in convs):
         from . import ops
         dev = convs[0][1].weight.device
-        items = []
-        for (_, conv, _), rec in zip(convs, recs):
+        items, shared = [], []
+        buf = bytearray(info["raw"])
+        for s, ((_, conv, _), rec) in enumerate(zip(convs, recs)):
             if conv.weight.dtype != torch.float32 or not conv.weight.data.is_contiguous():
                 raise McamdError("compressed model files are read into contiguous fp32 master weights")
             masks.append(torch.empty_like(conv.weight.data))
-            items.append(dict(w=conv.weight.data, mask=masks[-1], kind=rec["kind"], dense=not rec["bits"], kept=rec["kept"],
-                              val0=rec["val0"], word0=rec["word0"] // 8, exp0=rec["exp0"] // 4))
-        if info["bytes"] >= 1 << 33:
+            target, val0 = conv.weight.data, rec["val0"]
+            if rec["kind"] == L.WZ_CODE:
+                # one byte per code for the device pass, behind the file's own bytes (the sub-byte widening is a host pass)
+                target, val0 = torch.empty(rec["shape"], dtype=torch.uint8, device=dev), len(buf)
+                b = rec["codes"].tobytes()
+                buf += b + b"\0" * (_pad8(len(b)) - len(b))
+                shared.append(s)
+                books[s] = (torch.from_numpy(rec["codebook"].astype(np.float32)).to(dev), target)
+            items.append(dict(w=target, mask=masks[-1], kind=rec["kind"], dense=not rec["bits"], kept=rec["kept"],
+                              val0=val0, word0=rec["word0"] // 8, exp0=rec["exp0"] // 4))
+        if len(buf) >= 1 << 33:
             raise McamdError("%s: a file of 8 GiB or more is not read on the device" % path)
         # the file's bytes go up once, as they are, and are expanded next to the weights: a record's bit words, exponents
         # and values are read in place (every array of the file starts at a multiple of 8 bytes)
-        values = torch.frombuffer(bytearray(info["raw"]), dtype=torch.uint8).to(dev)
+        values = torch.frombuffer(buf, dtype=torch.uint8).to(dev)
         words, exps = values.view(torch.int64), values.view(torch.int32)
         ops.wz_unpack(items, words, exps, values)
+        if shared:
+            table = ops.WsTable([dict(w=convs[s][1].weight.data, mask=masks[s] if recs[s]["bits"] else None, codes=books[s][1],
+                                      K=1 << recs[s]["code_bits"]) for s in shared],
+                                codebook=torch.cat([books[s][0] for s in shared]))
+            table.expand()
     else:
-        for (i, conv, _), rec in zip(convs, recs):
+        for s, ((i, conv, _), rec) in enumerate(zip(convs, recs)):
             w, m = _decode_cpu(rec, "%s: conv%d" % (path, i))
             conv.weight.data.copy_(torch.from_numpy(w).view(rec["shape"]))
             masks.append(torch.from_numpy(m).view(rec["shape"]).to(conv.weight.device))
+            if rec["kind"] == L.WZ_CODE:
+                books[s] = (torch.from_numpy(rec["codebook"].astype(np.float32)),
+                            torch.from_numpy(rec["codes_full"]).view(rec["shape"]))
     for (_, conv, bn), rec in zip(convs, recs):
         for t, a in zip(_small_targets(conv, bn), rec["small"]):
             t.copy_(torch.from_numpy(a.astype(np.float32)))
@@ -352,6 +456,9 @@ def load_compressed(model, path, set_masks=True):
     model._weights_dirty = True
     if set_masks and any(rec["bits"] for rec in recs):
         model.set_masks(masks)
+    if set_masks and any(b is not None for b in books):
+        from . import share
+        share.set_codebooks(model, books, expand_weights=False)      # (the weights above are the expansion already)
     return masks
 
 
@@ -363,6 +470,8 @@ def compressed_info(path):
     for i, rec in enumerate(info["records"]):
         layers.append(dict(conv=i + 1, shape=rec["shape"], kind=KIND_NAMES[rec["kind"]], bitmask=rec["bits"], kept=rec["kept"],
                            weights=rec["n"], bytes=rec["bytes"]))
+        if rec["kind"] == L.WZ_CODE:      # a tied layer: its code bits, their width in the file and the codebook's entries
+            layers[-1].update(bits=rec["code_bits"], width=code_width(rec["code_bits"]), codebook=1 << rec["code_bits"])
         dense += 4 * (rec["n"] + rec["cout"] * (4 if rec["bn"] else 1))
     return dict(payload=info["payload"], seen=info["seen"], layers=layers, weights=sum(l["weights"] for l in layers),
                 kept=sum(l["kept"] for l in layers), bytes=info["bytes"], dense_bytes=dense, ratio=dense / info["bytes"])

@@ -90,6 +90,19 @@ __device__ __forceinline__ float wz_masked(const mcamd_wz_seg& g, long long i) {
     return ((const float*)g.w)[i] * (m ? m[i] : 1.f);
 }
 
+// pack: the stored code of weight i and whether it is kept.  MCAMD_WZ_CODE: the byte at w[i], kept by the MASK (a shared
+// value may be exactly 0); every other kind: the code of weight * mask, kept iff it is non-zero
+__device__ __forceinline__ unsigned wz_pack_code(const mcamd_wz_seg& g, long long i, int e, bool* keep) {
+    if (g.kind == MCAMD_WZ_CODE) {
+        const float* m = (const float*)g.mask;
+        *keep = !m || m[i] != 0.f;
+        return ((const unsigned char*)g.w)[i];
+    }
+    const unsigned code = wz_code(g.kind, wz_masked(g, i), e);
+    *keep = wz_kept(g.kind, code);
+    return code;
+}
+
 // ---------------------------------------------------------------------------------------
 // pack
 // ---------------------------------------------------------------------------------------
@@ -129,7 +142,7 @@ __global__ __launch_bounds__(256) void wz_words_kernel(const mcamd_wz_seg* __res
         bool keep = false;
         if (i < g.n) {
             const int e = g.kind == MCAMD_WZ_FP8 ? exps[g.exp0 + (int)(i / per)] : 0;
-            keep = wz_kept(g.kind, wz_code(g.kind, wz_masked(g, i), e));
+            (void)wz_pack_code(g, i, e, &keep);
         }
         const u64 word = __ballot(keep);
         if (lane == 0) words[g.word0 + wi] = word;
@@ -167,7 +180,7 @@ __global__ __launch_bounds__(64) void wz_scan_kernel(const mcamd_wz_seg* __restr
         }
         if (PACK) {
             const u64 elem = (u64)wz_elem(g.kind);
-            const bool bits = 8ull * (u64)nwords + carry * elem < (u64)g.n * elem;
+            const bool bits = g.kind == MCAMD_WZ_CODE ? carry < (u64)g.n : 8ull * (u64)nwords + carry * elem < (u64)g.n * elem;
             if (lane == 0) {
                 counts[s] = carry;
                 dense[s] = bits ? 0 : 1;
@@ -225,7 +238,8 @@ __global__ __launch_bounds__(256) void wz_scatter_kernel(const mcamd_wz_seg* __r
         unsigned code = 0u;
         if (bit) {
             const int e = g.kind == MCAMD_WZ_FP8 ? exps[g.exp0 + (int)(i / per)] : 0;
-            code = wz_code(g.kind, wz_masked(g, i), e);
+            bool keep;
+            code = wz_pack_code(g, i, e, &keep);
         }
         const long long pos = all ? i : (long long)(boff + osh[k] + (u64)__popcll(word & ((1ull << lane) - 1ull)));
         wz_store(base, g.kind, pos, code);
@@ -276,6 +290,11 @@ __global__ __launch_bounds__(256) void wz_expand_kernel(const mcamd_wz_seg* __re
             const u64 pos = boff + osh[k] + (u64)__popcll(word & ((1ull << lane) - 1ull));
             if (pos < (u64)g.kept) code = wz_load(base, g.kind, (long long)pos);      // a damaged file reads as +0
         }
+        if (g.kind == MCAMD_WZ_CODE) {                    // the codes themselves; the caller expands them (mcamd_ws_expand)
+            ((unsigned char*)g.w)[i] = bit ? (unsigned char)code : (unsigned char)0;
+            if (mask) mask[i] = bit ? 1.f : 0.f;
+            continue;
+        }
         float v = 0.f;
         if (wz_kept(g.kind, code)) {
             const int e = g.kind == MCAMD_WZ_FP8 ? exps[g.exp0 + (int)(i / per)] : 0;
@@ -300,8 +319,8 @@ static int wz_check_table(const char* what, const mcamd_wz_seg* segs, int nseg, 
         const mcamd_wz_seg& g = segs[s];
         MCAMD_REQUIRE(g.w && g.n > 0 && g.cout > 0 && g.n % g.cout == 0, "%s: segment %d: bad tensor (n %lld, cout %d)", what, s,
                       (long long)g.n, g.cout);
-        MCAMD_REQUIRE(g.kind == MCAMD_WZ_FP32 || g.kind == MCAMD_WZ_FP16 || g.kind == MCAMD_WZ_FP8, "%s: segment %d: bad value kind %d",
-                      what, s, g.kind);
+        MCAMD_REQUIRE(g.kind == MCAMD_WZ_FP32 || g.kind == MCAMD_WZ_FP16 || g.kind == MCAMD_WZ_FP8 || g.kind == MCAMD_WZ_CODE,
+                      "%s: segment %d: bad value kind %d", what, s, g.kind);
         const long long elem = g.kind == MCAMD_WZ_FP32 ? 4 : g.kind == MCAMD_WZ_FP16 ? 2 : 1;
         const long long nwords = (g.n + 63) / 64;
         MCAMD_REQUIRE(g.block0 == blocks, "%s: segment %d: block0 %d is not the running sum %lld", what, s, g.block0, blocks);

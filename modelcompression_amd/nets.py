@@ -282,6 +282,7 @@ class Darknet(nn.Module):
         # engine state (not part of the reference surface)
         self._engines = {}
         self._weights_dirty = True
+        self._ws_table = None           # project_codebooks: the cached table over the tied layers (share.py)
         self._grad_hook = None          # callable(flat_grad) run at the end of backward (data parallel)
         self._grad_ready_hook = None    # callable(flat_grad, lo, hi[, fence]): that slice is final (overlapped all-reduce; Engine.backward)
         self._last_flat_grad = None
@@ -325,6 +326,7 @@ class Darknet(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         self._engines = {}
         self._weights_dirty = True
+        self._ws_table = None
         return super(Darknet, self)._apply(fn, *args, **kwargs)
 
     def grad_overflowed(self, reset=True):
@@ -547,14 +549,30 @@ class Darknet(nn.Module):
                     save_fc(fp, model[0] if block['activation'] != 'linear' else model)
 
     def save_compressed(self, outfile, payload="fp16", layers=None):
-        """Write a compressed model file (an addition beyond the reference; compress.save_compressed)."""
+        """Write a compressed model file (an addition beyond the reference; compress.save_compressed).
+        payload "shared": codebooks + narrow codes of the layers set_codebooks tied."""
         from . import compress
         compress.save_compressed(self, outfile, payload, layers)
 
     def load_compressed(self, weightfile, set_masks=True):
-        """Read a compressed model file; returns the kept-bit masks (compress.load_compressed)."""
+        """Read a compressed model file; returns the kept-bit masks (compress.load_compressed).  A "shared" file also
+        sets the codebooks."""
         from . import compress
         return compress.load_compressed(self, weightfile, set_masks)
+
+    def set_codebooks(self, codebooks):
+        """Tie the weights (an addition beyond the reference; share.py): `codebooks` is what
+        share.kmeans_share returns, one (codebook, codes) or None per conv block in set_masks order.  Registers the buffers
+        `codebook` and `codes` on each MaskedConv2d named -- only here, like set_mask: an untied model's state_dict is
+        unchanged --, sets its weights to codebook[codes] on kept positions and raises its share_flag."""
+        from . import share
+        share.set_codebooks(self, codebooks)
+
+    def project_codebooks(self):
+        """Put every cluster of every tied layer back on its mean (share.py): call it behind optimizer.step().  On the GPU one
+        library call over all tied layers with no host synchronisation; every engine re-packs before its next forward."""
+        from . import share
+        share.project_codebooks(self)
 
     def set_masks(self, masks):
         """nets.py:1053-1061: hand masks[count] to every MaskedConv2d in module order.  Like the

@@ -1275,7 +1275,7 @@ def conv_fwd_q8_sparse24(g, x8, wq, idx, wexp, y, y_ld, y_choff=0, scale=None, s
 
 
 # ----------------------------------------------------------------------------- compressed model files (.mcz)
-WZ_ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1}
+WZ_ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1, L.WZ_CODE: 1}
 
 
 def _wz_table(items, device, unpack):
@@ -1286,7 +1286,9 @@ def _wz_table(items, device, unpack):
     for a, it in zip(arr, items):
         w, mask, kind = it["w"], it.get("mask"), int(it["kind"])
         _need_cuda(w, mask)
-        if w.dtype != torch.float32 or not w.is_contiguous() or w.numel() == 0 or kind not in WZ_ELEM:
+        if kind == L.WZ_CODE and (w.dtype != torch.uint8 or not w.is_contiguous() or w.numel() == 0):
+            raise L.McamdError("wz: the codes of a WZ_CODE item must be a non-empty contiguous uint8 tensor of the weight's shape")
+        if kind != L.WZ_CODE and (w.dtype != torch.float32 or not w.is_contiguous() or w.numel() == 0 or kind not in WZ_ELEM):
             raise L.McamdError("wz: weights must be non-empty contiguous fp32 tensors and kind one of %r" % sorted(WZ_ELEM))
         if mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous() or mask.shape != w.shape):
             raise L.McamdError("wz: a mask must be a contiguous fp32 tensor of the weight's shape")
@@ -1343,3 +1345,71 @@ def wz_unpack(items, words, exps, values):
     check(L.lib().mcamd_wz_unpack(arr, ptr(table), len(items), ptr(words), words.numel() if words is not None else 0, ptr(exps),
                                   exps.numel() if exps is not None else 0, ptr(values), values.numel(), ptr(ws), ws.numel(),
                                   stream_ptr()), "mcamd_wz_unpack")
+
+
+# ----------------------------------------------------------------------------- weight sharing
+class WsTable:
+    """Every layer of a weight-sharing pass through one mcamd_ws_seg table (include/mcamd.h), with the arrays the passes
+    share: `codebook` fp32 [sum K], `sums` float64 and `counts` int64 of the same length, and the workspace.
+
+    items: one dict(w=fp32 tensor, mask=fp32 tensor of its shape or None, codes=uint8 tensor of its shape, K=2^bits) per
+    layer.  codebook: the flat fp32 tensor to work on (layer s at the running sum of K), allocated when None.  Built once;
+    every method is one library call on the current stream with no host read."""
+
+    def __init__(self, items, codebook=None):
+        if not items:
+            raise L.McamdError("ws: no layer given")
+        dev = items[0]["w"].device
+        arr = (L.WsSeg * len(items))()
+        slabs = parts = cb = 0
+        self.offsets = []
+        for a, it in zip(arr, items):
+            w, mask, codes, K = it["w"], it.get("mask"), it["codes"], int(it["K"])
+            _need_cuda(w, mask, codes)
+            if w.dtype != torch.float32 or not w.is_contiguous() or w.numel() == 0:
+                raise L.McamdError("ws: weights must be non-empty contiguous fp32 tensors")
+            if mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous() or mask.shape != w.shape):
+                raise L.McamdError("ws: a mask must be a contiguous fp32 tensor of the weight's shape")
+            if codes.dtype != torch.uint8 or not codes.is_contiguous() or codes.numel() != w.numel():
+                raise L.McamdError("ws: codes must be a contiguous uint8 tensor with one entry per weight")
+            n = w.numel()
+            nsl = (n + L.WS_SLAB - 1) // L.WS_SLAB
+            a.w, a.mask, a.codes = w.data_ptr(), (mask.data_ptr() if mask is not None else None), codes.data_ptr()
+            a.n, a.K, a.cb0, a.slab0, a.part0 = n, K, cb, slabs, parts
+            self.offsets.append(cb)
+            slabs, parts, cb = slabs + nsl, parts + nsl * K, cb + K
+        self.items, self.arr, self.nseg, self.cb = items, arr, len(items), cb
+        # (pinned and non-blocking: building a table is no host synchronisation either)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory().to(dev, non_blocking=True)
+        if codebook is None:
+            codebook = torch.zeros(cb, dtype=torch.float32, device=dev)
+        _need_cuda(codebook)
+        if codebook.dtype != torch.float32 or not codebook.is_contiguous() or codebook.numel() < cb:
+            raise L.McamdError("ws: the codebook must be a contiguous fp32 tensor of at least %d entries" % cb)
+        self.codebook = codebook
+        self.sums = torch.zeros(cb, dtype=torch.float64, device=dev)
+        self.counts = torch.zeros(cb, dtype=torch.int64, device=dev)
+        self.ws = torch.empty(int(L.lib().mcamd_ws_workspace_bytes(slabs, parts, len(items))), dtype=torch.uint8, device=dev)
+
+    def layer_codebook(self, s):
+        return self.codebook[self.offsets[s]:self.offsets[s] + int(self.items[s]["K"])]
+
+    def init(self):
+        check(L.lib().mcamd_ws_init(self.arr, ptr(self.table), self.nseg, ptr(self.codebook), self.codebook.numel(), ptr(self.ws),
+                                    self.ws.numel(), stream_ptr()), "mcamd_ws_init")
+
+    def iterate(self):
+        check(L.lib().mcamd_ws_iterate(self.arr, ptr(self.table), self.nseg, ptr(self.codebook), self.codebook.numel(), ptr(self.sums),
+                                       ptr(self.counts), ptr(self.ws), self.ws.numel(), stream_ptr()), "mcamd_ws_iterate")
+
+    def assign(self):
+        check(L.lib().mcamd_ws_assign(self.arr, ptr(self.table), self.nseg, ptr(self.codebook), self.codebook.numel(), stream_ptr()),
+              "mcamd_ws_assign")
+
+    def project(self):
+        check(L.lib().mcamd_ws_project(self.arr, ptr(self.table), self.nseg, ptr(self.codebook), self.codebook.numel(), ptr(self.sums),
+                                       ptr(self.counts), ptr(self.ws), self.ws.numel(), stream_ptr()), "mcamd_ws_project")
+
+    def expand(self):
+        check(L.lib().mcamd_ws_expand(self.arr, ptr(self.table), self.nseg, ptr(self.codebook), self.codebook.numel(), stream_ptr()),
+              "mcamd_ws_expand")

@@ -74,6 +74,7 @@ class MaskedConv2d(nn.Conv2d):
         super(MaskedConv2d, self).__init__(in_channels, out_channels,
                                            kernel_size, stride, padding, dilation, groups, bias)
         self.mask_flag = False
+        self.share_flag = False     # Darknet.set_codebooks: the weights are tied to a `codebook` through `codes` (share.py)
         self.name = 'MaskedConv2d'
 
     def set_mask(self, mask):

@@ -14,6 +14,7 @@ import torch
 from ... import ops
 from ..._lib import McamdError
 from .utils import prune_rate, arg_nonzero_min
+from ...share import kmeans_share  # noqa: F401  (the stage behind pruning: weight sharing, share.py)
 
 
 def _virtual_index(n, perc, ftype):

@@ -27,7 +27,14 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     optimizer entry or gradient hook; every step runs its forward under no_grad in front of the student's and adds
     DISTILL(output, teacher_output) -- a distill.DistillLoss, by default DistillLoss.from_model(model) -- to the region
     loss.  Off by default: the same launches and results as without the keywords.
-  * YOLOv2Train.SAVE_COMPRESSED = "fp32" / "fp16" / "fp8" (an attribute, set on the class or on the object before
+  * SHARE=4 (bits), or a dict of share.kmeans_share keywords, adds weight sharing to the retraining (share.py, DESIGN.md
+    3u): behind pruning and set_masks every conv layer's kept weights are clustered into 2^bits shared values
+    (kmeans_share + Darknet.set_codebooks), and Darknet.project_codebooks() behind every optimizer.step() puts each
+    cluster back on its mean -- SGD on the shared values with the mean member gradient.  Each epoch prints whether every
+    tied layer still holds at most 2^bits distinct kept values.  Given by keyword only (the positional parameters of train()
+    stay as they were: a wrapper takes the keyword off), or set as the attribute YOLOv2Train.SHARE, which the keyword
+    overrides.  Off by default: the same launches and results as without it.
+  * YOLOv2Train.SAVE_COMPRESSED = "fp32" / "fp16" / "fp8" / "shared" (an attribute, set on the class or on the object before
     train() is called: the signature of train() stays the reference's plus the keywords above) writes a compressed model
     file of that payload (compress.py) beside every .weights file saved, with the extension .mcz.
     MODEL_WEIGHT and a TEACHER path may name such a file: Darknet.load_weights recognises it, and train() resumes at the
@@ -38,6 +45,7 @@ import os
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC for RCCL: read when HIP initialises (dp.init_from_env)
 
+import functools  # noqa: E402
 import time  # noqa: E402
 
 import torch  # noqa: E402
@@ -52,6 +60,7 @@ from .data import (VOCList, SyntheticDetection, VOCAugment, SyntheticAugment, Re
 from .nets import Darknet, cfg_shapes, parse_cfg  # noqa: E402
 from .pruning.weightPruning.methods import block_prune, quick_filter_prune, weight_prune  # noqa: E402
 from .pruning.weightPruning.utils import prune_rate, are_masks_consistent  # noqa: E402
+from .share import kmeans_share, are_codebooks_consistent, _bits_of  # noqa: E402
 
 
 def logging(message):
@@ -194,10 +203,27 @@ class StepGuard:
         return self.consume()
 
 
+def _share_keyword(train):
+    """train(..., SHARE=...): the keyword is taken off here and handed to the call as an attribute.  The parameter list of
+    train() itself stays the reference's plus the earlier keywords, positions included (callers pass it positionally up to
+    RESIDENT, and its end is pinned by tests/test_distill_cpu.py), so SHARE can only be given by keyword."""
+    @functools.wraps(train)
+    def with_share(self, *args, SHARE=None, **kwargs):
+        self._share_arg = SHARE
+        try:
+            return train(self, *args, **kwargs)
+        finally:
+            self._share_arg = None
+    return with_share
+
+
 class YOLOv2Train():
     # "fp32" / "fp16" / "fp8": train() writes a compressed model file of that payload (compress.py) beside every .weights file
     # it saves.  An attribute, like PASCALVOCEval.fused, not a keyword: train() keeps its signature.
     SAVE_COMPRESSED = None
+    # bits, or a dict of share.kmeans_share keywords: the default of train()'s SHARE keyword (module docstring)
+    SHARE = None
+    _share_arg = None
 
     def __init__(self):
         self.model = ''
@@ -210,15 +236,21 @@ class YOLOv2Train():
         self.teacher = None       # train(TEACHER=...): the frozen Darknet and the distill.DistillLoss of the last call
         self.distill = None
 
+    @_share_keyword
     def train(self, PASCAL_DIR, PASCAL_TRAIN, PASCAL_VALID, TRAIN_LOGDIR, VAL_LOGDIR, VAL_OUTPUTDIR_PKL, VAL_PREFIX,
               MODEL_CFG, MODEL_WEIGHT,
               BATCH_SIZE, SAVE_INTERNAL,
               LOGGER='', DEBUG_EPOCHS=-1, verbose=0, pruning_perc=0., pruning_method="weight",
               MAX_EPOCHS=135, SYNTHETIC_SAMPLES=256, EVAL=False, AUGMENT=False, RESIDENT=False, TEACHER=None,
               DISTILL=None):
+        SHARE = self.SHARE if self._share_arg is None else self._share_arg
         SAVE_COMPRESSED = self.SAVE_COMPRESSED
-        if SAVE_COMPRESSED not in (None, "fp32", "fp16", "fp8"):
-            raise ValueError('train: SAVE_COMPRESSED must be None, "fp32", "fp16" or "fp8", got %r' % (SAVE_COMPRESSED,))
+        if SAVE_COMPRESSED not in (None, "fp32", "fp16", "fp8", "shared"):
+            raise ValueError('train: SAVE_COMPRESSED must be None, "fp32", "fp16", "fp8" or "shared", got %r' % (SAVE_COMPRESSED,))
+        if SHARE is not None and not isinstance(SHARE, dict):
+            SHARE = dict(bits=SHARE)
+        if SHARE is not None and not isinstance(SHARE.get("bits", 4), dict):
+            _bits_of(SHARE.get("bits", 4), [1])       # a bad width is refused here, before the model is built
         if DISTILL is not None and TEACHER is None:
             raise ValueError("train: DISTILL needs a TEACHER (True, a .weights path or a Darknet)")
         rank, world = dp.init_from_env()
@@ -301,6 +333,9 @@ class YOLOv2Train():
         if world > 1:
             # static weight masks: only the kept gradient entries travel (dp.py); filter masks keep the dense transport
             reducer = dp.attach(self.model, masks=masks if (masks is not None and pruning_method != "filter") else None)
+        if SHARE is not None:
+            # every rank clusters the same broadcast weights under the same masks: the codebooks agree, nothing travels
+            self.model.set_codebooks(kmeans_share(self.model, **SHARE))
         if masks is not None:
             p_rate = prune_rate(self.model, rank == 0)
             if rank == 0:
@@ -354,6 +389,10 @@ class YOLOv2Train():
                 # together, and the host learns of it one step late (StepGuard)
                 guard.decide(train_loss)
                 optimizer.step()
+                if SHARE is not None:
+                    # By linearity, SGD on the shared values with the mean member gradient (momentum and weight decay
+                    # included).  A step StepGuard skipped left the weights tied: the projection is then the identity.
+                    self.model.project_codebooks()
                 steps_here += 1
                 if verbose and rank == 0:
                     print(' - loss : ', float(train_loss.detach()))
@@ -370,6 +409,8 @@ class YOLOv2Train():
             if pruning_perc > 0 and rank == 0:
                 print(' pruned: %s' % prune_rate(self.model, False))
                 print(' pruned weights consistent after retraining: %s ' % are_masks_consistent(self.model, masks))
+                if SHARE is not None:
+                    print(' shared weights consistent after retraining: %s ' % are_codebooks_consistent(self.model))
                 if (epoch + 1) % 5 == 0 and TRAIN_LOGDIR:
                     name = '%s/%s-pruned-%s-retrained_%06d.weights' % (TRAIN_LOGDIR, pruning_method, pruning_perc, epoch + 1)
                     logging('save weights to %s' % name)
