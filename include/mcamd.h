@@ -226,6 +226,11 @@ int mcamd_conv_fwd(const mcamd_conv_geom* g, const void* x, const void* wp_fwd,
 int32_t mcamd_conv_fwd_sparse24_ok(const mcamd_conv_geom* g);
 /* Sizes of the packed 2:4 operands: out[0] = fp16 kept values, out[1] = 16-bit index words. */
 int mcamd_sparse24_elems(const mcamd_conv_geom* g, int64_t out[2]);
+/* The kernel instance mcamd_conv_fwd_sparse24 launches for this geometry, from the launch's own choice (host logic only, no
+ * GPU): out = {bmw, bnp, bk, stages, mtiles, ntiles, grid} -- a workgroup tile of bmw filters x bnp pixels, K chunks of bk
+ * (the channel block of the packed K order), LDS ring stages, the tiles along the pixels and the filters, and the blocks
+ * launched (whole rounds of 8 pixel tiles).  MCAMD_SPARSE_WIDE=0 removes the 256-filter tile. */
+int mcamd_conv_fwd_sparse24_info(const mcamd_conv_geom* g, int32_t out[7]);
 /* OIHW fp32 master (* mask, may be NULL) -> the 2:4 packing the sparse forward stages:
  *   wsp: fp16 [Npad][ktot / 2], Npad = round_up(cout, 256), ktot = k*k * round_up(cin, 32): the dense forward row
  *        (K order of mcamd_pack_weights) with each group of 4 consecutive k reduced to its 2 kept values, in k order;

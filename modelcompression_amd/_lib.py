@@ -203,6 +203,7 @@ SIGNATURES = {
     "mcamd_conv_fwd": (C.c_int, [C.POINTER(ConvGeom), _P, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_fwd_sparse24_ok": (_I32, [C.POINTER(ConvGeom)]),
     "mcamd_sparse24_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
+    "mcamd_conv_fwd_sparse24_info": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I32)]),
     "mcamd_pack_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
     "mcamd_conv_fwd_sparse24": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_fwd_bsparse_ok": (_I32, [C.POINTER(ConvGeom)]),

@@ -673,6 +673,15 @@ extern "C" int mcamd_sparse24_elems(const mcamd_conv_geom* g, int64_t out[2]) {
     return MCAMD_OK;
 }
 
+// mcamd_sparse24_choice()'s answer: what mcamd_conv_fwd_sparse24 launches for this geometry (host logic only)
+extern "C" int mcamd_conv_fwd_sparse24_info(const mcamd_conv_geom* g, int32_t out[7]) {
+    MCAMD_REQUIRE(g && out, "conv_fwd_sparse24_info: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_sparse24_ok(g), "conv_fwd_sparse24_info: geometry has no 2:4 form (mcamd_conv_fwd_sparse24_ok)");
+    const Sparse24Choice c = mcamd_sparse24_choice((long long)g->B * g->H * g->W, g->cout, kblock_of(cin_tap_of(g)));
+    out[0] = c.bmw, out[1] = c.bnp, out[2] = c.bk, out[3] = c.stages, out[4] = c.mtiles, out[5] = c.ntiles, out[6] = c.grid;
+    return MCAMD_OK;
+}
+
 extern "C" int mcamd_pack_sparse24(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* wsp, void* idx,
                                    void* stream) {
     if (mcamd_recording()) {

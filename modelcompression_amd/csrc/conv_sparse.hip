@@ -166,35 +166,50 @@ void sparse24_kernel(IgemmArgs a, const unsigned short* __restrict__ idx, int np
 }
 
 template <int BMW, int BNP, int WM, int WN, int BK, int NSTAGE>
-static int sparse24_launch_t(IgemmArgs& a, const unsigned short* idx, int npad, hipStream_t st) {
+static int sparse24_launch_t(IgemmArgs& a, const Sparse24Choice& c, const unsigned short* idx, int npad, hipStream_t st) {
     constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
     constexpr int I_BYTES = (BK / 32) * BMW * 4 > 1024 ? (BK / 32) * BMW * 4 : 1024;
     constexpr int STAGE_BYTES = (BMW * (BK / 16) + BNP * (BK / 8)) * 16 + I_BYTES;
     constexpr int LDS = NSTAGE * STAGE_BYTES > BNP * BMW * 2 ? NSTAGE * STAGE_BYTES : BNP * BMW * 2;   // ring / epilogue tile
     auto kern = sparse24_kernel<BMW, BNP, WM, WN, BK, NSTAGE>;
     MCAMD_LDS_OPT_IN(kern, LDS);
-    a.num_mtiles = (a.M + BNP - 1) / BNP;
-    a.num_ntiles = (a.N + BMW - 1) / BMW;
-    const int grid = (a.num_mtiles + 7) / 8 * 8 * a.num_ntiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), LDS, st, a, idx, npad);
+    a.num_mtiles = c.mtiles;
+    a.num_ntiles = c.ntiles;
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), LDS, st, a, idx, npad);
     MCAMD_LAUNCH_CHECK("conv_fwd_sparse24");
     return MCAMD_OK;
 }
 
 // Tile: 256 channels x 128 pixels (8 waves of 64 x 64) for layers with >= 256 filters and 64-channel blocks -- the weight
 // half of a staged chunk is cheap with 2:4, so the taller tile halves the activation bytes per MFMA --, 128 x 128 (4 waves)
-// for >= 128 filters, 64 x 128 below.  MCAMD_SPARSE_WIDE=0: no 256-channel tile (A/B switch).
+// for >= 128 filters, 64 x 128 below.  MCAMD_SPARSE_WIDE=0: no 256-channel tile (A/B switch).  K chunks of
+// the channel block kb, two ring stages.  The grid is whole rounds of 8 pixel tiles (xcd_tile).
+Sparse24Choice mcamd_sparse24_choice(long long M, int N, int kb) {
+    Sparse24Choice c;
+    c.bk = kb == 64 ? 64 : 32;
+    c.bnp = 128;
+    c.stages = 2;
+    if (c.bk == 64 && N >= 256 && MCAMD_ENV_INT("MCAMD_SPARSE_WIDE", 1)) c.bmw = 256;
+    else c.bmw = N >= 128 ? 128 : 64;
+    c.mtiles = (int)((M + c.bnp - 1) / c.bnp);
+    c.ntiles = (N + c.bmw - 1) / c.bmw;
+    c.grid = (c.mtiles + 7) / 8 * 8 * c.ntiles;
+    return c;
+}
+
 int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st) {
     const unsigned short* ix = (const unsigned short*)idx;
     const int npad = round_up_int(a.N, 256);
-    const bool wide = a.N >= 128;
-    if (a.kb == 64) {
-        if (a.N >= 256 && MCAMD_ENV_INT("MCAMD_SPARSE_WIDE", 1)) return sparse24_launch_t<256, 128, 64, 64, 64, 2>(a, ix, npad, st);
-        return wide ? sparse24_launch_t<128, 128, 64, 64, 64, 2>(a, ix, npad, st)
-                    : sparse24_launch_t<64, 128, 32, 64, 64, 2>(a, ix, npad, st);
+    const Sparse24Choice c = mcamd_sparse24_choice(a.M, a.N, a.kb);
+    if (c.bnp == 128 && c.stages == 2) {
+        if (c.bmw == 256 && c.bk == 64) return sparse24_launch_t<256, 128, 64, 64, 64, 2>(a, c, ix, npad, st);
+        if (c.bmw == 128 && c.bk == 64) return sparse24_launch_t<128, 128, 64, 64, 64, 2>(a, c, ix, npad, st);
+        if (c.bmw == 64 && c.bk == 64) return sparse24_launch_t<64, 128, 32, 64, 64, 2>(a, c, ix, npad, st);
+        if (c.bmw == 128 && c.bk == 32) return sparse24_launch_t<128, 128, 64, 64, 32, 2>(a, c, ix, npad, st);
+        if (c.bmw == 64 && c.bk == 32) return sparse24_launch_t<64, 128, 32, 64, 32, 2>(a, c, ix, npad, st);
     }
-    return wide ? sparse24_launch_t<128, 128, 64, 64, 32, 2>(a, ix, npad, st)
-                : sparse24_launch_t<64, 128, 32, 64, 32, 2>(a, ix, npad, st);
+    mcamd_set_error("conv_fwd_sparse24: no kernel instance %d x %d, K %d, %d stages", c.bmw, c.bnp, c.bk, c.stages);
+    return MCAMD_EINVAL;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -130,7 +130,14 @@ int mcamd_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, float* ws, hipS
 #define MCAMD_BSPARSE_BM_DEFAULT 128
 int mcamd_bsparse_launch(IgemmArgs& a, const int* count, const int* list, hipStream_t st);
 int mcamd_bsparse_lists_launch(const void* wp, int cout, int cin_tap, int ntaps, int* count, int* list, hipStream_t st);
-int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);   // conv_sparse.hip: 2:4 weights, mode 2 epilogue
+// conv_sparse.hip: 2:4 weights, mode 2 epilogue.  mcamd_sparse24_choice names the sparse24_kernel instance (bmw filters x
+// bnp pixels, K chunks of bk, LDS ring stages) and its grid for M pixels x N filters with channel blocks of kb; the launch
+// dispatches on it
+struct Sparse24Choice {
+    int bmw, bnp, bk, stages, mtiles, ntiles, grid;
+};
+Sparse24Choice mcamd_sparse24_choice(long long M, int N, int kb);
+int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);
 int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
                                int cin_tap, int kb, hipStream_t st);
 // conv_q8.hip: e4m3 operands (byte strides in `a`), mode 2 epilogue with a format per destination; packer; cast pass

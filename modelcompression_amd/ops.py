@@ -966,6 +966,18 @@ def sparse24_elems(g):
     return int(out[0]), int(out[1])
 
 
+Sparse24Info = collections.namedtuple("Sparse24Info", "bmw bnp bk stages mtiles ntiles grid")
+
+
+def conv_fwd_sparse24_info(g):
+    """The sparse24_kernel instance conv_fwd_sparse24 launches for `g` (a tile of bmw filters x bnp pixels, K chunks of bk,
+    LDS ring stages), its tiles along the pixels and the filters and its grid: mcamd_conv_fwd_sparse24_info, the launch's
+    own choice.  Needs no GPU."""
+    out = (C.c_int32 * 7)()
+    check(L.lib().mcamd_conv_fwd_sparse24_info(C.byref(g), out), "mcamd_conv_fwd_sparse24_info")
+    return Sparse24Info(*out)
+
+
 def pack_sparse24(g, w, mask=None, out_vals=None, out_idx=None):
     """fp32 OIHW master (* mask) -> (fp16 kept values, int16 index words) of the 2:4 forward (mcamd_pack_sparse24)."""
     _need_cuda(w, mask)
@@ -983,10 +995,11 @@ def pack_sparse24(g, w, mask=None, out_vals=None, out_idx=None):
 
 
 def conv_fwd_sparse24(g, x, wsp, idx, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
-                      y2_choff=0):
-    """conv_fwd_padded on 2:4-packed weights (v_smfmac): the same inference epilogue, arguments and output."""
+                      y2_choff=0, overflow=None):
+    """conv_fwd_padded on 2:4-packed weights (v_smfmac): the same inference epilogue, arguments and output.
+    `overflow`: optional int32 flag, set to 1 when an output was clamped to +-65504."""
     e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
-             y2_choff=y2_choff)
+             y2_choff=y2_choff, overflow=overflow)
     check(L.lib().mcamd_conv_fwd_sparse24(C.byref(g), ptr(x), ptr(wsp), ptr(idx), C.byref(e), stream_ptr()),
           "mcamd_conv_fwd_sparse24")
 

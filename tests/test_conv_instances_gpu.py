@@ -18,7 +18,7 @@ store outside the slice and a slab row nobody wrote all show.
 
 Out of scope: the split-operand and fp8-correction operand forms (x_wrap, x_f8, small3x3_split_kernel); the dgrad
 instances that take BatchNorm sums (test_dgrad_bn_sums_gpu.py); the split-K, sparse and q8 kernels, each of which has its
-own exact tests; the MCAMD_PP_MFMA=32 instances, which are off by default and selected by a switch the library reads once
+own exact tests (the 2:4 fp16 forward: test_sparse_instances_gpu.py); the MCAMD_PP_MFMA=32 instances, which are off by default and selected by a switch the library reads once
 per process."""
 import os
 import sys
@@ -29,28 +29,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from modelcompression_amd import ops, _lib as L  # noqa: E402
 import conv_cases as CC  # noqa: E402
+from util import NAN, whole as _whole, fill_padded as _fill, padded_split as _padded_to_nchw  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-NAN = float("nan")
-
-
-def _whole(buf):
-    """The buffer with the guard bands in front of and behind it: everything a stray store could reach."""
-    return torch.empty(0, dtype=buf.dtype, device=buf.device).set_(buf.untyped_storage())
-
-
-def _fill(dev, c, t, ld, choff, width, pad):
-    """[B][C][H][W] (cpu, fp16-exact values) -> padded NHWC fp16 device buffer of `ld` channels with the tensor at channel
-    `choff`; the slice [choff, choff + width) is zero beyond the tensor and around the image, every other channel is NaN."""
-    buf = ops.alloc_padded(c.B, c.H, c.W, ld, dev, pad=pad)
-    npix = c.B * (c.H + 1) * (c.W + 1) + c.W + 2 if pad else c.B * (c.H + 2) * (c.W + 2)
-    flat = buf[:npix * ld].view(npix, ld)
-    flat[:, :choff] = NAN
-    flat[:, choff + width:] = NAN
-    C_ = t.shape[1]
-    ops.padded_view(buf, c.B, c.H, c.W, ld, pad)[:, 1:-1, 1:-1, choff:choff + C_] = t.permute(0, 2, 3, 1).to(dev).half()
-    return buf
 
 
 def _rows_to_nchw(y, c, ld, choff, n):
@@ -58,16 +39,6 @@ def _rows_to_nchw(y, c, ld, choff, n):
     v = y.view(c.B, c.H, c.W, ld)
     rest = torch.cat([v[..., :choff].reshape(-1), v[..., choff + n:].reshape(-1)])
     return v[..., choff:choff + n].permute(0, 3, 1, 2).cpu(), rest.cpu()
-
-
-def _padded_to_nchw(buf, B, H, W, ld, choff, n):
-    """padded NHWC destination (guards included) -> the interior slice as [B][n][H][W]; everything else as a flat vector"""
-    all_ = _whole(buf).clone()
-    lo = buf.storage_offset()
-    v = all_[lo:lo + B * (H + 2) * (W + 2) * ld].view(B, H + 2, W + 2, ld)
-    got = v[:, 1:-1, 1:-1, choff:choff + n].permute(0, 3, 1, 2).clone().cpu()
-    v[:, 1:-1, 1:-1, choff:choff + n] = NAN
-    return got, all_.cpu()
 
 
 def _launch(dev, c, r, o):

@@ -3,6 +3,8 @@ import torch
 
 from modelcompression_amd import ops
 
+NAN = float("nan")
+
 
 def rel_l2(a, b):
     a, b = a.double(), b.double()
@@ -46,3 +48,32 @@ def nchw_to_raw(x, ld, choff=0):
 def q16(t):
     """Round to fp16 and back (what the kernels see)."""
     return t.half().float()
+
+
+# ---- NaN sentinels around operand and output slices (the exact kernel-instance tests)
+def whole(buf):
+    """The buffer with the guard bands in front of and behind it: everything a stray store could reach."""
+    return torch.empty(0, dtype=buf.dtype, device=buf.device).set_(buf.untyped_storage())
+
+
+def fill_padded(dev, c, t, ld, choff, width, pad):
+    """[B][C][H][W] (cpu, fp16-exact values) -> padded NHWC fp16 device buffer of `ld` channels with the tensor at channel
+    `choff`; the slice [choff, choff + width) is zero beyond the tensor and around the image, every other channel is NaN."""
+    buf = ops.alloc_padded(c.B, c.H, c.W, ld, dev, pad=pad)
+    npix = c.B * (c.H + 1) * (c.W + 1) + c.W + 2 if pad else c.B * (c.H + 2) * (c.W + 2)
+    flat = buf[:npix * ld].view(npix, ld)
+    flat[:, :choff] = NAN
+    flat[:, choff + width:] = NAN
+    C_ = t.shape[1]
+    ops.padded_view(buf, c.B, c.H, c.W, ld, pad)[:, 1:-1, 1:-1, choff:choff + C_] = t.permute(0, 2, 3, 1).to(dev).half()
+    return buf
+
+
+def padded_split(buf, B, H, W, ld, choff, n):
+    """padded NHWC destination (guards included) -> the interior slice as [B][n][H][W]; everything else as a flat vector"""
+    all_ = whole(buf).clone()
+    lo = buf.storage_offset()
+    v = all_[lo:lo + B * (H + 2) * (W + 2) * ld].view(B, H + 2, W + 2, ld)
+    got = v[:, 1:-1, 1:-1, choff:choff + n].permute(0, 3, 1, 2).clone().cpu()
+    v[:, 1:-1, 1:-1, choff:choff + n] = NAN
+    return got, all_.cpu()
