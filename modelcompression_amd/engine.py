@@ -43,8 +43,51 @@ class _T:
         self.ps0 = ps          # (a folded producer's planes move closer together: Engine._plan_folds)
 
 
+_LAYER_FIELDS = dict(
+    # geometry: the block, its place in the plan, the shapes of its launches
+    index=0, li=0, conv=None, bn=None, slope=1.0, src=0, tin=None, cin=0, cout=0, cout_p=0, H=0, W=0, k=0, M=0, stem=0, pad=0,
+    level=1, mode=0, out_id=None, out2_id=None, out_t=None, out2_t=None, is_last=False, train_ok=True, border=None,
+    border_map=None, geom=None, geom_f=None, p_lo=0, p_hi=0,
+    # buffers: packed weights (forward / dgrad), raw output + statistics, BatchNorm coefficients, gradients
+    wp=None, wd=None, y=None, stats=None, scale=None, shift=None, mean=None, invstd=None, dy=None, gin=None, act_full=None,
+    # compaction / fold (_update_compaction, _plan_folds)
+    keep=None, perm=None, perm32=None, in_perm=None, g_rows=None, g_cols=None, n_act=0, geom_act=None, gather=False,
+    fold=None, fold_cin=0, fold_aug=0, fold_consumers=None, ones_idx=-1, skip_dead=False, bn_width=0, waug=None, dwaug=None,
+    # first-block variants, and the fp8 correction form of a split-operand block
+    fused_stem=False, fused_stem_eval=False, stem_shadow=False, stem_split=False, stem_f32=False, stem_ws=None, weff=None,
+    sh_img=None, sh_img_lo=None, sh_geom=None, sh_wp=None, sh_wp_lo=None, sh_coef=None,
+    f8=False, f8_wexp=ops.F8_WEXP_DEFAULT, f8_wexp_eff=ops.F8_WEXP_DEFAULT,
+    # inference form (Engine._choose_forms, _FORMS) and what belongs to one: split-K slices, 2:4 values + index words,
+    # block-sparse chunk lists
+    form="dense", sk_slices=1, wsp=None, widx=None, bs_count=None, bs_list=None,
+    # fp8: launch geometry on the byte buffer, byte destinations, private input copy, packed operands; "fp8-qat" training:
+    # the fp32 raw output + statistics that stand in for the fp16 ones, and the values the weight bytes stand for
+    geom_q8=None, q8_y=False, q8_y2=False, xq=None, _xq=None, _xq_key=None, wq=None, wqs=None, widx8=None, wexp=None,
+    y_f16=None, stats_f16=None, y_f32=None, stats_q8=None, w_q=None)
+
+
 class _Layer:
-    pass
+    """One [convolutional] block of the plan.  Every field it can carry is declared above with its default: a misspelt one
+    raises instead of reading as "off"."""
+    __slots__ = tuple(_LAYER_FIELDS)
+
+    def __init__(self):
+        for name, default in _LAYER_FIELDS.items():
+            setattr(self, name, default)
+        self.fold_consumers = []
+
+    # exactly one inference form per block; the flags of the single forms are read-only views of it
+    sp_on = property(lambda self: self.form == "sparse24")
+    bs_on = property(lambda self: self.form == "bsparse")
+    sk_on = property(lambda self: self.form == "splitk")
+    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24"))
+    q8s_on = property(lambda self: self.form == "q8_sparse24")
+    q8_slim = property(lambda self: self.form == "q8_slim")
+
+
+def _momentum(bn):
+    """BatchNorm momentum as the coefficient kernels take it (None reads as torch's default, 0.1)."""
+    return bn.momentum if bn.momentum is not None else 0.1
 
 
 def _resolve_routes(blocks):
@@ -91,6 +134,147 @@ TRAIN_GAIN = 1.1
 # is at least 10 % faster than the dense launch on every layer of conv9 .. conv22 at B = 128 (worst layer 1.15x at 0.375;
 # at 0.5 conv9 / 11 / 13 gain 4-9 % only, and from 0.625 up the 3x3 layers lose).
 BSPARSE_MAX_KEPT = 0.375
+
+
+class _Dense:
+    """One inference form of a block (`_Layer.form`, chosen by Engine._choose_forms): what it allocates, how it packs and
+    what it launches.  This one is the dense fp16 launch off the packed weights every block has; a form with packed
+    operands of its own names them once.  `ops` functions are named, not bound, and looked up when they are called."""
+    fwd = "conv_fwd_padded"              # ops: the forward with the fused inference epilogue
+    geom = "geom_act"                    # layer field of its geometry
+    bufs = (("wp", torch.float16),)      # (layer field, dtype) of its weight operands, in the order elems / packer / fwd take them
+    elems = packer = None                # ops: their sizes, and the pass that fills them from the fp32 master * mask (None:
+                                         # `wp` is the pack table's)
+
+    def alloc(self, eng, lays):
+        """Buffers of the blocks that took this form (behind every choice): kept where the size already matches."""
+        for lay in lays if self.elems else ():
+            for (name, dtype), n in zip(self.bufs, getattr(ops, self.elems)(getattr(lay, self.geom))):
+                if getattr(lay, name) is None or getattr(lay, name).numel() != n:
+                    setattr(lay, name, torch.zeros(n, dtype=dtype, device=eng.device))
+
+    def pack(self, eng, lay, w, mask):
+        """This form's operands (every re-pack, in front of the pack table's launch)."""
+        if self.packer:
+            getattr(ops, self.packer)(getattr(lay, self.geom), w, mask, *(getattr(lay, name) for name, _ in self.bufs))
+
+    def repacked(self, eng, lay):
+        """... and what it derives from the packed weights (every re-pack, behind that launch)."""
+
+    def operands(self, eng, lay, xin):
+        """(geometry, input, weights...) of the fused launch and its extra keywords."""
+        return (getattr(lay, self.geom), xin, *(getattr(lay, name) for name, _ in self.bufs)), {}
+
+    def raw(self, eng, lay, xin, training):
+        """The launch of a block that does not take the fused path: raw fp16 output (+ batch statistics in training)."""
+        eng._timed('fwd', lay, ops.conv_fwd_raw, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0, lay.stats if training else None)
+
+
+class _SplitK(_Dense):
+    """Few pixels: K cut into slices over the whole chip (Darknet.splitk, csrc/conv_splitk.hip)."""
+    fwd = "conv_fwd_splitk"
+
+    def alloc(self, eng, lays):
+        # one workspace of the largest requirement: the layers run one after another on the launch stream
+        need = max(ops.conv_fwd_splitk_info(lay.geom_act, *eng._splitk_form(lay)).workspace_bytes for lay in lays)
+        if eng._splitk_ws is None or eng._splitk_ws.numel() * 4 < need:
+            eng._splitk_ws = torch.empty(need // 4, dtype=torch.float32, device=eng.device)
+
+    def operands(self, eng, lay, xin):
+        return _Dense.operands(self, eng, lay, xin)[0], dict(slices=lay.sk_slices, workspace=eng._splitk_ws)
+
+    def raw(self, eng, lay, xin, training):
+        if training:
+            return _Dense.raw(self, eng, lay, xin, training)
+        eng._timed('fwd', lay, ops.conv_fwd_raw_splitk, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0,
+                   slices=lay.sk_slices, workspace=eng._splitk_ws)
+
+
+class _Sparse24(_Dense):
+    """2:4 weights on the sparse MFMA (Darknet.sparse = "2:4", csrc/conv_sparse.hip): kept values + index words."""
+    fwd, elems, packer = "conv_fwd_sparse24", "sparse24_elems", "pack_sparse24"
+    bufs = (("wsp", torch.float16), ("widx", torch.int16))
+
+
+class _BSparse(_Dense):
+    """The non-zero K chunks of each 64-filter tile only (Darknet.sparse = "block", csrc/conv_bsparse.hip).  Two phases:
+    `policy` reads the masked weights in front of the filter compaction (the blocks it picks are exempt from it),
+    `repacked` rebuilds the chunk lists of the blocks that kept the form from the weights the launch reads."""
+    fwd = "conv_fwd_bsparse"
+    bufs = (("wp", torch.float16), ("bs_count", torch.int32), ("bs_list", torch.int32))
+
+    def policy(self, eng, max_kept):
+        """Taken in front of every re-pack (masks, weights, the mode or Darknet.sparse_max_kept changed): every candidate's
+        chunk lists from its packed weights in their own filter and channel order (mcamd_bsparse_lists on a temporary
+        packing), ONE host read of all counts, and a candidate is chosen when its kept-chunk fraction, sum(count) /
+        (tiles x chunks), is at most `max_kept`.  Returns (the chosen layer indices, conv number -> kept fraction of every
+        candidate): pack() keeps the chosen blocks out of the filter compaction, whose physical channel order would scatter
+        the zero blocks over the K chunks."""
+        def masked(lay):
+            m = lay.conv.mask if lay.conv.mask_flag else None
+            return m is not None and m.is_cuda and m.dtype == torch.float32 and m.shape == lay.conv.weight.shape
+        cand = [lay for lay in eng.layers if masked(lay) and not eng.q8 and eng._eligible(lay, compacted=False)
+                and ops.conv_fwd_bsparse_ok(lay.geom)]
+        sums = []
+        for lay in cand:
+            wp, _ = ops.pack_weights(lay.geom, lay.conv.weight.data, lay.conv.mask.contiguous(), want_dgrad=False)
+            sums.append(ops.bsparse_lists(lay.geom, wp)[0].sum())
+        chosen, kept = [], {}
+        for lay, s_ in zip(cand, torch.stack(sums).cpu().tolist() if cand else []):
+            kept[lay.li + 1] = s_ / float(ops.bsparse_elems(lay.geom)[1])       # conv number (conv1 = the first block)
+            if kept[lay.li + 1] <= max_kept:
+                chosen.append(lay.li)
+        return frozenset(chosen), kept
+
+    def alloc(self, eng, lays):
+        for lay in lays:
+            nc, nl = ops.bsparse_elems(lay.geom_act)
+            if lay.bs_count is None or lay.bs_count.numel() != nc or lay.bs_list.numel() != nl:
+                lay.bs_count = torch.zeros(nc, dtype=torch.int32, device=eng.device)
+                lay.bs_list = torch.zeros(nc, nl // nc, dtype=torch.int32, device=eng.device)
+
+    def repacked(self, eng, lay):
+        ops.bsparse_lists(lay.geom_act, lay.wp, lay.bs_count, lay.bs_list)
+
+
+class _Q8(_Dense):
+    """e4m3 activations x e4m3 weights (Darknet.precision = "fp8", csrc/conv_q8.hip): bytes + one exponent per filter,
+    computed on the device."""
+    fwd, elems, packer, geom = "conv_fwd_q8", "q8_elems", "pack_q8", "geom_q8"
+    bufs = (("wq", torch.uint8), ("wexp", torch.int32))
+
+    def pack(self, eng, lay, w, mask):
+        _Dense.pack(self, eng, lay, w, mask)
+        if eng._qat_train(lay):     # the values those bytes stand for, fp32 OIHW: the dgrad packing's source
+            ops.fakequant_q8(lay.geom_act, w, mask, lay.wexp, lay.w_q)
+
+    def operands(self, eng, lay, xin):
+        x8 = eng.qbufs.get(lay.tin.buf)
+        if lay.xq is not None:      # the fp16 -> fp8 edge: cast pass over the padded input slice into a private byte copy
+            ti, x8 = lay.tin, lay.xq
+            eng._timed('cast', lay, ops.cast_q8, xin, eng.B * (ti.H + 2) * (ti.W + 2), ti.ld, ti.choff, lay.cin,
+                       x8, lay.geom_q8.x_ld, ti.choff)
+        return _Dense.operands(self, eng, lay, x8)[0], dict(y_f8=lay.q8_y, y2_f8=lay.q8_y2)
+
+
+class _Q8Slim(_Q8):
+    """A slim model's fp8 block: rows of round_up(cin, 64) channels with zero bytes behind the real ones, border table in
+    the epilogue."""
+    fwd, elems, packer = "conv_fwd_q8_slim", "q8_slim_elems", "pack_q8_slim"
+
+    def operands(self, eng, lay, xin):
+        args, kw = _Q8.operands(self, eng, lay, xin)
+        return args, dict(kw, border=lay.border, border_ld=lay.cout)
+
+
+class _Q8Sparse24(_Q8):
+    """2:4-compressed e4m3 weights with their index words on the sparse MFMA ("fp8-2:4", csrc/conv_q8_sparse.hip)."""
+    fwd, elems, packer = "conv_fwd_q8_sparse24", "q8_sparse24_elems", "pack_q8_sparse24"
+    bufs = (("wqs", torch.uint8), ("widx8", torch.int32), ("wexp", torch.int32))
+
+
+_FORMS = {"dense": _Dense(), "splitk": _SplitK(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "q8": _Q8(),
+          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24()}
 
 
 def _probe_side_stream(device, tries=8):
@@ -148,7 +332,7 @@ class Engine:
         plain (MIXED_BUDGET; `for_training`: the budget of the training-mode forward, MIXED_BUDGET_TRAIN, under which the
         first block is split as well).  The backward pass uses plain fp16 operands in every mode.
         "fp8" -- inference only: the "fp16" engine with every eligible block on e4m3 activations and weights
-        (csrc/conv_q8.hip, `fp8_layers`, _update_q8); a training-mode forward raises.
+        (csrc/conv_q8.hip, `fp8_layers`, _choose_q8); a training-mode forward raises.
         "fp8-2:4" -- the "fp8" engine with every fp8 block whose mask conforms to 2:4 on the sparse fp8 kernel
         (csrc/conv_q8_sparse.hip, `fp8_sparse_layers`); every other block runs what "fp8" runs.
         "fp8-qat" -- fp8 quantisation-aware training: in training mode every block of `fp8_layers` runs its
@@ -163,7 +347,7 @@ class Engine:
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
         self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-qat")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
-        # when the masks change (_update_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
+        # when the masks change (_choose_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
         self.q8 = precision in ("fp8", "fp8-2:4", "fp8-qat")
         self.qat = precision == "fp8-qat"      # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
@@ -171,12 +355,12 @@ class Engine:
         self.q8_sparse = precision == "fp8-2:4"
         self.fp8_sparse_layers = []
         self.qbufs = {}
-        self._qld = {}                         # buffer id -> bytes per pixel of its byte buffer (_update_q8)
-        self._q8_keys = None
+        self._qld = {}                         # buffer id -> bytes per pixel of its byte buffer (_choose_q8)
         self.grad_scale = float(grad_scale)
         self.serial = 0
         self._packed_sig = None
         self.events = None            # list of (tag, layer, start, end) HIP events while profiling
+        self.event_pool = None        # ... and reusable timing events a caller may hand in for them (_timed)
         # weight-gradient kernels on a second HIP stream beside the dgrad / BN-backward chain (they fill each other's
         # tails: +3.5 % images/s at B=64); MCAMD_OVERLAP_WGRAD=0 serialises everything on the launch stream (per-kernel
         # timing passes do that, bench.py)
@@ -192,19 +376,21 @@ class Engine:
         self._logits = self._gout = self._flat = None
         self._pack_on_side = False
         # 2:4 sparse inference (Darknet.sparse = "2:4", plain-fp16 eval engines only): conv indices of the blocks that run
-        # mcamd_conv_fwd_sparse24, chosen when the masks change (_update_sparse); empty = every block dense
+        # mcamd_conv_fwd_sparse24, chosen when the masks or the mode change (_choose_forms); empty = every block dense
         self.sparse_layers = []
-        self._sparse_mode, self._sparse_keys = None, None
         # block-sparse inference (Darknet.sparse = "block", plain-fp16 eval engines only): conv numbers of the blocks that run
-        # mcamd_conv_fwd_bsparse, chosen when the masks, the weights or Darknet.sparse_max_kept change (_refresh_bsparse)
+        # mcamd_conv_fwd_bsparse, chosen when the masks, the weights or Darknet.sparse_max_kept change (_choose_forms)
         self.bsparse_layers = []
         self.bsparse_kept = {}           # conv number -> kept-chunk fraction of every candidate block
-        self._bs_max_kept = None
-        self._bs_exempt = frozenset()    # layer indices the policy chose: their filters are not compacted (_plan_bsparse)
+        self._bs_exempt = frozenset()    # layer indices the policy chose: their filters are not compacted (_BSparse.policy)
         # split-K low-batch inference (Darknet.splitk, plain-fp16 eval engines only): conv numbers of the blocks that run
-        # mcamd_conv_fwd_splitk, chosen when the flag or the masks change (_update_splitk); one workspace for all of them
+        # mcamd_conv_fwd_splitk, chosen when the flag or the masks change (_choose_forms); one workspace for all of them
         self.splitk_layers = []
-        self._splitk_on, self._splitk_keys, self._splitk_ws = False, None, None
+        self._splitk_ws = None
+        # what every block's form was last chosen for (pack): mask keys, block-sparse choice, sparse mode, sparse_max_kept,
+        # split-K flag
+        self._form_key = (None, None, None, None, None)
+        self._training, self._fold_key = None, None
         self.fold_dead = os.environ.get("MCAMD_FOLD_DEAD", "1") == "1"
         # "mixed": the two correction products of the split-operand forward from e4m3 copies on the block-scaled fp8 MFMAs
         # (csrc/conv_igemm_pp.hip, F8).  "fp16x3" keeps all three products on fp16 operands: it is the tests' tight reference.
@@ -410,7 +596,6 @@ class Engine:
             lay.train_ok = lay.is_last or (lay.cout // 8 <= 256 and 256 % (lay.cout // 8) == 0)
             # slim models (slim.py): constant contribution of physically removed input channels, by border class
             lay.border = getattr(lay.conv, "border_bias", None)
-            lay.border_map = None
             if lay.border is not None:
                 lay.border = lay.border.detach().to(device=dev, dtype=torch.float32).contiguous()
                 if tuple(lay.border.shape) != (16, lay.cout):
@@ -433,7 +618,6 @@ class Engine:
                 self.producer_of[lay.out_id] = lay
                 if lay.out2_id is not None:
                     self.producer_of[lay.out2_id] = lay
-            lay.fold, lay.ones_idx, lay.skip_dead, lay.fold_consumers, lay.bn_width = None, -1, False, [], 0
         # a concat tensor's members are consumed through the concat's consumer
         self.consumer_of = {}
         for lay in self.layers:
@@ -481,7 +665,6 @@ class Engine:
             lay.geom_f = g if lay.level == 1 else ops.geom(B, lay.H, lay.W, lay.k, lay.level * lay.cin, lay.cout,
                                                            lay.tin.ld, 0, 0, lay.pad, wrap)
             nf, _ = ops.packed_elems(lay.geom_f)
-            lay.f8, lay.f8_wexp, lay.f8_wexp_eff = False, ops.F8_WEXP_DEFAULT, ops.F8_WEXP_DEFAULT
             if self.precise:
                 lay.n_act, lay.geom_act = lay.cout, g
                 self._set_geom_f(lay)
@@ -515,16 +698,11 @@ class Engine:
                 lay.sh_coef = [torch.empty(lay.cout, **f32) for _ in range(4)]             # scale, shift, mean, invstd
                 lay.stem_ws = torch.empty(ops.stem_block_workspace_bytes(), dtype=torch.uint8, device=dev)
             lay.dy = None if (lay.fused_stem or lay.stem_shadow) else ops.alloc_padded(B, lay.H, lay.W, lay.cout_p, dev, pad=lay.pad)
-            lay.keep, lay.keep_key = None, None
-            lay.gin = None
-            lay.stem_f32 = False
             if lay.li > 0:
                 lay.gin = torch.empty(lay.M * lay.tin.ld, dtype=ops.HALF, device=dev)
-            lay.perm = lay.perm32 = lay.in_perm = lay.g_rows = lay.g_cols = None
-            lay.n_act, lay.geom_act, lay.gather = lay.cout, lay.geom, False
+            lay.n_act, lay.geom_act = lay.cout, lay.geom
             if not lay.is_last:
                 if lay.fused_stem:
-                    lay.y = lay.stats = None
                     lay.stem_ws = torch.empty(ops.stem_block_workspace_bytes(), dtype=torch.uint8, device=dev)
                 else:
                     # The first convolution of the split-operand modes: fp32 on the vector ALUs straight from the fp32 image
@@ -544,7 +722,6 @@ class Engine:
                     # compaction (self.pool_act_on, _update_compaction): there the weight-gradient stream is the longer one of
                     # the backward pass, the bytes saved on the launch stream buy nothing and the forward's extra write is paid
                     # (filter40: 8.29 -> 8.37 ms with it, same box)
-                    lay.act_full = None
                     if (self.bwd_from_act and self.precise and self.train_layout and lay.y is not None and lay.mode == L.DST_POOL
                             and lay.border is None and lay.slope > 0.0):
                         lay.act_full = ops.alloc_padded(B, lay.H, lay.W, ops.round_up(lay.cout, 8), dev, pad=pad_for(lay.W))
@@ -562,7 +739,6 @@ class Engine:
                 if lay.out_t is None:
                     raise NotImplementedError("conv block %d output is never consumed" % lay.index)
         self.wgrad_ws = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
-        self._mask_keys = None
         self._pack_key, self._pack_table, self._pack_keep = None, None, []
         # filter compaction + dead-input folding; since round 4 also in the split-operand engines (two-plane storage)
         self.compact = os.environ.get("MCAMD_COMPACT", "1") == "1" and (not self.precise or self.act_planes == 2)
@@ -623,7 +799,7 @@ class Engine:
         # (events come from a pool the caller may hand in -- `self.event_pool`, a list of reusable timing events -- so that a
         # long instrumented pass does not keep hundreds of profiling signals alive; the host-side seconds of the three
         # parts [record, call, record] are kept next to the pair: a GPU-side gap with a long host part is a HOST stall)
-        pool = getattr(self, "event_pool", None)
+        pool = self.event_pool
         if pool:
             e0, e1 = pool.pop(), pool.pop()
         else:
@@ -650,7 +826,7 @@ class Engine:
             w = lay.conv.weight
             m = lay.conv.mask if lay.conv.mask_flag else None
             bnv = None
-            if lay.fold is not None and not getattr(self, "_training", True):
+            if lay.fold is not None and self._training is False:
                 # eval: the folded constants beta - running_mean * gamma / sqrt(running_var + eps) are baked into the
                 # augmented weights -- an in-place change of the producer's BatchNorm tensors (dp.sync_buffers,
                 # running_mean.copy_, load_state_dict) must trigger a re-pack
@@ -659,13 +835,16 @@ class Engine:
             sig.append((w.data_ptr(), w._version, None if m is None else (m.data_ptr(), m._version), bnv))
         return tuple(sig)
 
-    def pack(self, force=False, training=True):
-        """fp32 master * mask -> fp16 kernel layouts (replaces layers.py:59's per-forward multiply)."""
-        if any(lay.fold is not None for lay in self.layers) and training != getattr(self, "_training", None):
+    def pack(self, force=False, training=True, sparse=None, splitk=False, max_kept=None):
+        """fp32 master * mask -> fp16 kernel layouts (replaces layers.py:59's per-forward multiply).
+        `sparse`, `splitk`, `max_kept`: the inference options forward() validated (Darknet.sparse / splitk /
+        sparse_max_kept; off in training mode); every block's form is chosen again when they or the masks change."""
+        if any(lay.fold is not None for lay in self.layers) and training != self._training:
             force = True          # the folded constants differ between batch and running statistics
         self._training = training
         sig = self._signature()
-        if not force and sig == self._packed_sig and not self.model._weights_dirty:
+        if (not force and sig == self._packed_sig and (sparse, max_kept, splitk) == self._form_key[2:]
+                and not self.model._weights_dirty):
             return
         if self.model._weights_dirty or (self.f8 and self.serial % 1000 == 999):      # (and every 1 000th forward: slow drift)
             self._refresh_f8_wexp()
@@ -673,24 +852,17 @@ class Engine:
                       for lay in self.layers)
         # (Darknet.sparse = "block": the blocks the policy chose keep their dense filter layout, so the compaction plan
         # depends on that choice too; it is the empty set in every other mode)
-        exempt = self._plan_bsparse() if self._sparse_mode == "block" else frozenset()
-        if (mkeys, exempt) != self._mask_keys:         # masks are static during retraining: planned once
-            self._bs_exempt = exempt
-            self._update_compaction()
-            self._mask_keys = (mkeys, exempt)
-            self._pack_key = None
-            for lay in self.layers:          # the packed shapes may have shrunk: stale entries must not survive
-                lay.wp.zero_()
-                if lay.wd is not None:
-                    lay.wd.zero_()
+        exempt = frozenset()
+        if sparse == "block":
+            exempt, self.bsparse_kept = _FORMS["bsparse"].policy(self, max_kept)
+        key = (mkeys, exempt, sparse, max_kept, splitk)
+        if key != self._form_key:          # masks are static during retraining: planned once
+            self._choose_forms(key)
         # geom_act / g_rows / g_cols: physical channel order (kept filters first, permuted inputs); identity = None.
         # Split-operand engines: forward = fp16 of [w_hi | w_hi | w_lo] along the input channels (w_hi = fp16(w * mask),
         # w_lo = fp16(w * mask - w_hi)), matching the [x_hi | x_lo | x_hi] activation planes, written by the one-launch
         # packer itself (mcamd_pack_job.split); dgrad = the plain fp16 packing (the backward pass multiplies plain operands)
-        if self.q8 and mkeys != self._q8_keys:      # (in front of the job table: it names the fp8 blocks' w_q)
-            self._update_q8()
-            self._q8_keys = mkeys
-            self._pack_key = None
+        # (the forms are chosen in front of the job table: it names the fp8 blocks' w_q)
         tkey = tuple((s_[0], None if s_[2] is None else s_[2][0]) for s_ in sig)
         if tkey != self._pack_key:          # weight / mask storage moved, or the compaction changed: new job table
             jobs, self._pack_keep = [], []
@@ -717,30 +889,13 @@ class Engine:
                                  dst_fwd=lay.wp, dst_dgrad=lay.wd, split=split, f8_wexp=lay.f8_wexp_eff))
             self._pack_table = ops.pack_table(jobs, self.device) if jobs else None
             self._pack_key = tkey
-        skeys = (mkeys, self._sparse_mode)
-        if skeys != self._sparse_keys:
-            self._update_sparse()
-            self._sparse_keys = skeys
-        kkeys = (mkeys, self._sparse_mode, self._splitk_on)      # (behind _update_sparse: sparse blocks are never split)
-        if kkeys != self._splitk_keys:
-            self._update_splitk()
-            self._splitk_keys = kkeys
         for lay in self.layers:
             mask = lay.conv.mask.contiguous() if lay.conv.mask_flag else None
-            if lay.sp_on:
-                ops.pack_sparse24(lay.geom_act, lay.conv.weight.data, mask, lay.wsp, lay.widx)
-            if self.q8 and lay.q8_on:      # e4m3 bytes + one exponent per filter, computed on the device
-                if lay.q8s_on:             # ... 2:4-compressed, with their index words
-                    ops.pack_q8_sparse24(lay.geom_q8, lay.conv.weight.data, mask, lay.wqs, lay.widx8, lay.wexp)
-                elif lay.q8_slim:          # ... rows of round_up(cin, 64) channels, zero bytes behind the real ones
-                    ops.pack_q8_slim(lay.geom_q8, lay.conv.weight.data, mask, lay.wq, lay.wexp)
-                else:
-                    ops.pack_q8(lay.geom_q8, lay.conv.weight.data, mask, lay.wq, lay.wexp)
-                    if self._qat_train(lay):   # the values those bytes stand for, fp32 OIHW: the dgrad packing's source
-                        ops.fakequant_q8(lay.geom_act, lay.conv.weight.data, mask, lay.wexp, lay.w_q)
+            if lay.form != "dense":
+                _FORMS[lay.form].pack(self, lay, lay.conv.weight.data, mask)
             if lay.stem:
                 ops.pack_weights(lay.geom_act, lay.conv.weight.data, mask, True, False, lay.wp, None, rows=lay.g_rows)
-            if getattr(lay, "stem_split", False):          # hi and lo stem packings of the split-operand fused first block
+            if lay.stem_split:          # hi and lo stem packings of the split-operand fused first block
                 ops.pack_stem_split(lay.conv.weight.data, mask, lay.sh_wp, lay.sh_wp_lo)
         # The layers behind the first block are not needed until that block's forward is done: with folded layers
         # (filter masks) their fold + re-pack runs on the second stream under the first block's Gram / forward kernels and
@@ -761,7 +916,7 @@ class Engine:
                 # all layers through a cached job table (the table holds pointers: rebuilt when a tensor moved)
                 fkey = tuple((lay.conv.weight.data_ptr(), lay.fold.bn.bias.data_ptr(),
                               lay.conv.mask.data_ptr() if lay.conv.mask_flag else 0) for lay in folds)
-                if fkey != getattr(self, "_fold_key", None):
+                if fkey != self._fold_key:
                     self._fold_table = ops.fold_table([dict(w=lay.conv.weight.data, mask=lay.conv.mask if lay.conv.mask_flag else None,
                                                             rows=lay.g_rows, cols=lay.g_cols, beta=lay.fold.bn.bias.data,
                                                             slope=lay.fold.slope, n=lay.n_act, cin_k=lay.fold_cin, waug=lay.waug)
@@ -777,159 +932,125 @@ class Engine:
                 ops.pack_many(*self._pack_table)
             if side is not None:
                 self._pack_on_side = True      # forward() makes the launch stream wait for the second one before block 2
-        if self._sparse_mode == "block":       # (eval only: a training-mode forward has _sparse_mode None)
-            self._refresh_bsparse()
+        for lay in self.layers:                # (what a form derives from the weights the forward launch reads)
+            if lay.form != "dense":
+                _FORMS[lay.form].repacked(self, lay)
         self._packed_sig = sig
         self.model._weights_dirty = False
 
-    # ------------------------------------------------------------------ 2:4 sparsity
-    def _fused_eval(self, lay, border_ok=False):
+    # ------------------------------------------------------------------ inference forms
+    def _fused_eval(self, lay, border_ok=False, compacted=True):
         """Does this block take the fused inference path (BN + LeakyReLU [+ pool / reorg] in the conv epilogue)?
-        `border_ok`: also with a border table (slim models) -- the fp8 epilogue adds it (_update_q8), the fp16 ones do not."""
-        return (self.fuse_eval and not self.precise and not lay.is_last and lay.perm is None
+        `border_ok`: also with a border table (slim models) -- the fp8 epilogue adds it (_choose_q8), the fp16 ones do not.
+        `compacted=False`: whatever the filter compaction made of it (_eligible)."""
+        return (self.fuse_eval and not self.precise and not lay.is_last and (lay.perm is None or not compacted)
                 and (border_ok or lay.border is None)
                 and (lay.out2_t is None or lay.mode == L.DST_POOL)
                 and (lay.mode == L.DST_PLAIN or (lay.H % 2 == 0 and lay.W % 2 == 0)))
 
-    def _update_sparse(self):
-        """Which blocks run the 2:4 forward (called when the masks or Darknet.sparse change): a block does when its mask
-        keeps at most 2 of every 4 consecutive input channels at each (filter, tap) -- checked on the device, one host
-        read for all blocks --, it takes the fused inference path without filter compaction or folding, it is neither the
-        first nor the last block, and mcamd_conv_fwd_sparse24_ok accepts its geometry.  Every other block stays dense."""
-        self._plan_epoch += 1             # recorded forward plans name the dense or the sparse launch of a block
-        for lay in self.layers:
-            lay.sp_on = lay.bs_on = False
-        self.sparse_layers, self.bsparse_layers = [], []
-        if self._sparse_mode != "block":
-            self.bsparse_kept = {}
-        if self._sparse_mode is None:
-            return
-        if self._sparse_mode == "block":
-            return                        # (chosen per re-pack: _plan_bsparse / _refresh_bsparse)
-        if self._sparse_mode != "2:4":
-            raise McamdError("sparse must be None, '2:4' or 'block' (got %r)" % (self._sparse_mode,))
-        cand = [lay for lay in self.layers
-                if lay.li > 0 and not lay.stem and not lay.is_last and lay.conv.mask_flag and lay.fold is None
-                and lay.g_cols is None and lay.cin % 4 == 0 and self._fused_eval(lay)
-                and lay.conv.mask.shape == lay.conv.weight.shape and ops.conv_fwd_sparse24_ok(lay.geom_act)]
+    def _inner(self, lay):
+        """Neither the first block (nor a stem in any form) nor the last one."""
+        return lay.li > 0 and not lay.stem and not lay.is_last
+
+    def _eligible(self, lay, border_ok=False, compacted=True):
+        """Can this block leave the dense launch?  It is neither the first nor the last block, takes the fused inference
+        path, and its filters are not compacted, its inputs neither permuted nor folded.
+        `border_ok`: a border table is acceptable (slim fp8).  `compacted=False`: the compaction state is ignored -- for the
+        block-sparse policy, which runs in front of the compaction and exempts the blocks it picks from it."""
+        return (self._inner(lay) and self._fused_eval(lay, border_ok, compacted)
+                and (not compacted or (lay.fold is None and lay.g_cols is None)))
+
+    def _conforming(self, cand):
+        """The blocks of `cand` whose mask keeps at most 2 of every 4 consecutive input channels at each (filter, tap):
+        checked on the device, one pass per candidate and ONE host read for all."""
         if not cand:
-            return
+            return []
         counts = torch.zeros(len(cand), dtype=torch.int32, device=self.device)
         for i, lay in enumerate(cand):
             ops.nm_violations(lay.conv.mask.contiguous(), counts[i:i + 1])
-        bad = counts.cpu().tolist()
-        for lay, b in zip(cand, bad):
-            if b:
-                continue
-            nv, ni = ops.sparse24_elems(lay.geom_act)
-            if getattr(lay, "wsp", None) is None or lay.wsp.numel() != nv:
-                lay.wsp = torch.zeros(nv, dtype=torch.float16, device=self.device)
-                lay.widx = torch.zeros(ni, dtype=torch.int16, device=self.device)
-            lay.sp_on = True
-            self.sparse_layers.append(lay.li + 1)      # conv number (conv1 = the first block)
+        return [lay for lay, bad in zip(cand, counts.cpu().tolist()) if not bad]
 
-    # ------------------------------------------------------------------ block sparsity
-    def _bsparse_candidate(self, lay):
-        """Could this block run mcamd_conv_fwd_bsparse?  It has a mask of its weight's shape, is neither the first nor the
-        last block, takes the fused inference path when its filters are not compacted, has no border table (slim_export
-        models) and a geometry mcamd_conv_fwd_bsparse_ok accepts."""
-        m = lay.conv.mask if lay.conv.mask_flag else None
-        return (m is not None and m.is_cuda and m.dtype == torch.float32 and m.shape == lay.conv.weight.shape
-                and lay.li > 0 and not lay.stem and not lay.is_last and lay.bn is not None and lay.border is None
-                and self.fuse_eval and not self.precise and not self.q8
-                and (lay.out2_t is None or lay.mode == L.DST_POOL)
-                and (lay.mode == L.DST_PLAIN or (lay.H % 2 == 0 and lay.W % 2 == 0))
-                and ops.conv_fwd_bsparse_ok(lay.geom))
-
-    def _plan_bsparse(self):
-        """The policy of Darknet.sparse = "block", taken in front of every re-pack (masks, weights, the mode or
-        Darknet.sparse_max_kept changed): every candidate's chunk lists from its packed weights in their own filter and
-        channel order (mcamd_bsparse_lists on a temporary packing), ONE host read of all counts, and a candidate is chosen
-        when its kept-chunk fraction, sum(count) / (tiles x chunks), is at most sparse_max_kept.  Returns the chosen
-        layer indices: pack() keeps those blocks out of the filter compaction, whose physical channel order would scatter
-        the zero blocks over the K chunks."""
-        cand = [lay for lay in self.layers if self._bsparse_candidate(lay)]
-        sums = []
-        for lay in cand:
-            wp, _ = ops.pack_weights(lay.geom, lay.conv.weight.data, lay.conv.mask.contiguous(), want_dgrad=False)
-            sums.append(ops.bsparse_lists(lay.geom, wp)[0].sum())
-        self.bsparse_kept = {}
-        if not cand:
-            return frozenset()
-        chosen = []
-        for lay, s_ in zip(cand, torch.stack(sums).cpu().tolist()):
-            kept = s_ / float(ops.bsparse_elems(lay.geom)[1])
-            self.bsparse_kept[lay.li + 1] = kept       # conv number (conv1 = the first block)
-            if kept <= self._bs_max_kept:
-                chosen.append(lay.li)
-        return frozenset(chosen)
-
-    def _refresh_bsparse(self):
-        """Behind every re-pack under Darknet.sparse = "block": the chunk lists of the chosen blocks from the weights the
-        forward launch reads.  A chosen block whose producer was compacted after all (its input channels are permuted)
-        stays on the dense launch."""
-        on = []
+    def _choose_forms(self, key):
+        """Every block's inference form (`_Layer.form`, exactly one of _FORMS), chosen when `key` changes: the mask keys,
+        the block-sparse policy's choice, Darknet.sparse, sparse_max_kept and Darknet.splitk (pack).  In this order:
+          1. (pack) the block-sparse policy has read the masked weights; the blocks it chose are exempt from
+          2. filter compaction and folding, planned again when the masks or that choice changed;
+          3. then fp8 (every eligible block of an fp8 engine), 2:4 (sparse = "2:4": every eligible block whose mask conforms
+             and whose geometry mcamd_conv_fwd_sparse24_ok accepts) or block-sparse (sparse = "block": the chosen blocks that
+             are still eligible -- one whose producer was compacted after all, so that its input channels are permuted, stays
+             dense), which depend on perm / g_cols / fold -- and all of it in front of the pack job table, which names w_q of
+             an fp8-qat training block;
+          4. split-K last: it only takes blocks that are still dense -- sparse and block-sparse blocks are never split --
+             and does when the library's policy gives the block's eval-mode launch two slices or more
+             (mcamd_conv_fwd_splitk_info).
+        Every other block stays dense.  The `*_layers` lists are the conv numbers (conv1 = the first block) per form."""
+        mkeys, exempt, sparse, max_kept, splitk = key
+        self._plan_epoch += 1             # recorded plans name each block's launch and hold its operands' addresses
+        if (mkeys, exempt) != self._form_key[:2]:
+            self._bs_exempt = exempt
+            self._update_compaction()
+            self._pack_key = None
+            for lay in self.layers:          # the packed shapes may have shrunk: stale entries must not survive
+                lay.wp.zero_()
+                if lay.wd is not None:
+                    lay.wd.zero_()
         for lay in self.layers:
-            lay_on = (lay.li in self._bs_exempt and lay.perm is None and lay.g_cols is None and lay.fold is None
-                      and self._fused_eval(lay))
-            if lay_on:
-                nc, nl = ops.bsparse_elems(lay.geom_act)
-                if getattr(lay, "bs_count", None) is None or lay.bs_count.numel() != nc or lay.bs_list.numel() != nl:
-                    lay.bs_count = torch.zeros(nc, dtype=torch.int32, device=self.device)
-                    lay.bs_list = torch.zeros(nc, nl // nc, dtype=torch.int32, device=self.device)
-                    self._plan_epoch += 1     # recorded forward plans hold the lists' addresses
-                ops.bsparse_lists(lay.geom_act, lay.wp, lay.bs_count, lay.bs_list)
-                on.append(lay.li + 1)
-            if lay_on != lay.bs_on:
-                self._plan_epoch += 1         # recorded forward plans name the dense or the block-sparse launch of a block
-                lay.bs_on = lay_on
-        if on != self.bsparse_layers:
-            self.bsparse_layers = on
-            if self._splitk_on:
-                self._update_splitk()         # block-sparse blocks are never split
+            lay.form, lay.sk_slices = "dense", 1
+            lay.q8_y, lay.q8_y2, lay.xq, lay.geom_q8 = False, False, None, lay.geom_act
+            if lay.y_f16 is not None:        # (an fp8-qat training block: back to its fp16 raw output and statistics)
+                lay.y, lay.stats = lay.y_f16, lay.stats_f16
+        if sparse != "block":
+            self.bsparse_kept = {}
+        if self.q8:
+            self._choose_q8()
+            self._pack_key = None
+        elif sparse == "2:4":
+            for lay in self._conforming([lay for lay in self.layers
+                                         if self._eligible(lay) and lay.conv.mask_flag and lay.cin % 4 == 0
+                                         and lay.conv.mask.shape == lay.conv.weight.shape
+                                         and ops.conv_fwd_sparse24_ok(lay.geom_act)]):
+                lay.form = "sparse24"
+        elif sparse == "block":
+            for lay in self.layers:
+                if lay.li in exempt and self._eligible(lay):
+                    lay.form = "bsparse"
+        if splitk:
+            for lay in self.layers:
+                launch = self._splitk_form(lay)
+                if launch is None or lay.geom_act.pad:
+                    continue
+                info = ops.conv_fwd_splitk_info(lay.geom_act, launch[0], launch[1])
+                if info.slices >= 2:
+                    lay.form, lay.sk_slices = "splitk", info.slices
+        by_form = {}
+        for lay in self.layers:
+            by_form.setdefault(lay.form, []).append(lay)
+        for name, lays in by_form.items():
+            _FORMS[name].alloc(self, lays)
+        nums = lambda *names: [lay.li + 1 for lay in self.layers if lay.form in names]
+        self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
+        self.fp8_layers, self.fp8_sparse_layers = nums("q8", "q8_slim", "q8_sparse24"), nums("q8_sparse24")
+        self._form_key = key
 
-    # ------------------------------------------------------------------ split-K low-batch inference
     def _splitk_form(self, lay):
         """(epilogue mode, dst_mode) of the eval-mode launch of a block the split-K pair can stand in for, or None: the fused
         inference launch (ops.conv_fwd_padded) or the raw one without statistics (ops.conv_fwd_raw: blocks with a border
         table, a permutation or folding -- how slim_export models run in fp16)."""
-        if (lay.li == 0 or lay.stem or lay.is_last or lay.sp_on or lay.bs_on or self.precise or self.q8
-                or lay.fused_stem or lay.fused_stem_eval or getattr(lay, "stem_split", False)):
+        if not self._inner(lay) or lay.form not in ("dense", "splitk") or self.precise or self.q8:
             return None
         return (L.EPI_PAD_F16, lay.mode) if self._fused_eval(lay) else (L.EPI_RAW_F16, L.DST_PLAIN)
 
-    def _update_splitk(self):
-        """Which blocks run the split-K forward (called when Darknet.splitk, Darknet.sparse or the masks change, and when
-        the engine is built): a block does when the library's policy gives its eval-mode launch two slices or more
-        (mcamd_conv_fwd_splitk_info); blocks on the 2:4 kernel, the first and the last block never do."""
-        self._plan_epoch += 1             # recorded forward plans name the unsplit or the split launch of a block
-        self.splitk_layers = []
-        need = 0
-        for lay in self.layers:
-            lay.sk_on, lay.sk_slices = False, 1
-            form = self._splitk_form(lay) if self._splitk_on else None
-            if form is None or lay.geom_act.pad:
-                continue
-            info = ops.conv_fwd_splitk_info(lay.geom_act, form[0], form[1])
-            if info.slices >= 2:
-                lay.sk_on, lay.sk_slices = True, info.slices
-                need = max(need, info.workspace_bytes)
-                self.splitk_layers.append(lay.li + 1)      # conv number (conv1 = the first block)
-        # one workspace of the largest requirement: the layers run one after another on the launch stream
-        if need and (self._splitk_ws is None or self._splitk_ws.numel() * 4 < need):
-            self._splitk_ws = torch.empty(need // 4, dtype=torch.float32, device=self.device)
-
     # ------------------------------------------------------------------ fp8 quantised inference
-    def _update_q8(self):
-        """Which blocks run the fp8 forward (called when the masks change): a block does when it is neither the first nor
-        the last one, has a multiple of 64 input channels, takes the fused inference path without filter compaction,
-        folding or a border table, and mcamd_conv_fwd_q8_ok accepts its geometry.  Every other block runs what the "fp16"
+    def _choose_q8(self):
+        """Which blocks of an fp8 engine run an fp8 forward, and which tensors are held as bytes (step 3 of _choose_forms): a
+        block does when it is eligible (_eligible), has a multiple of 64 input channels and no border table, and
+        mcamd_conv_fwd_q8_ok accepts its geometry.  Every other block runs what the "fp16"
         engine runs.  An activation buffer holds e4m3 bytes when EVERY block that reads it (a concat member can have a
         reader of its own beside the concat's) and every block that writes into it are fp8 blocks: one format per tensor.
         Otherwise the buffer stays fp16 and an fp8 block that reads it takes a private byte copy that a cast pass
         (mcamd_cast_q8) writes in front of it.
         Precision "fp8-2:4": an fp8 block whose mask is present with the weight's shape and keeps at most 2 of every 4
-        consecutive input channels at each (filter, tap) -- checked on the device, one host read for all blocks -- runs
+        consecutive input channels at each (filter, tap) (_conforming) runs
         the sparse fp8 kernel (`fp8_sparse_layers`); formats and buffers do not depend on that.
         Slim models (a model some conv of which carries a border table; not under "fp8-qat"): a block with a
         border table and / or an input channel count that is
@@ -938,13 +1059,6 @@ class Engine:
         loop reads round_up(cin, 64) bytes per pixel and tap, so a byte buffer's leading dimension (`_qld`, the private
         copies' too) is raised until that span lies inside it for every fp8 reader; the bytes behind a tensor's channels are
         allocated 0x00 and never written."""
-        self._plan_epoch += 1             # recorded forward plans name the fp16, the fp8 or the sparse fp8 launch of a block
-        for lay in self.layers:
-            lay.q8_on, lay.q8_y, lay.q8_y2, lay.xq, lay.q8s_on = False, False, False, None, False
-            lay.q8_slim, lay.geom_q8 = False, lay.geom_act
-            if getattr(lay, "y_f16", None) is not None:
-                lay.y, lay.stats = lay.y_f16, lay.stats_f16
-        self.fp8_layers, self.fp8_sparse_layers = [], []
         dev = self.device
         # "fp8-qat" training engines keep their small images in the shared-halo form (both kernels read it); the set of
         # blocks is the inference engine's: the same predicate on everything that does not depend on the layout
@@ -953,28 +1067,19 @@ class Engine:
         # had -- conv2 of the dense YOLOv2 (32 input channels, no table) stays an fp16 block
         slim_model = not self.qat and any(lay.border is not None for lay in self.layers)
         for lay in self.layers:
-            if not (lay.li > 0 and not lay.stem and not lay.is_last and lay.fold is None and lay.g_cols is None
-                    and lay.g_rows is None and lay.n_act == lay.cout and (qat_train or not lay.pad)):
+            if lay.pad and not qat_train:
                 continue
-            if lay.cin % 64 == 0 and self._fused_eval(lay) and ops.conv_fwd_q8_ok(lay.geom_act):
-                lay.q8_on = True
-            elif (slim_model and (lay.border is not None or lay.cin % 64 != 0) and self._fused_eval(lay, border_ok=True)
+            if lay.cin % 64 == 0 and self._eligible(lay) and ops.conv_fwd_q8_ok(lay.geom_act):
+                lay.form = "q8"
+            elif (slim_model and (lay.border is not None or lay.cin % 64 != 0) and self._eligible(lay, border_ok=True)
                   and ops.round_up(lay.cin, 64) <= 2 * lay.cin and ops.conv_fwd_q8_slim_ok(self._q8_geom(lay))):
-                lay.q8_on = lay.q8_slim = True
-            if lay.q8_on:
-                self.fp8_layers.append(lay.li + 1)     # conv number (conv1 = the first block)
-        cand = [lay for lay in self.layers
-                if self.q8_sparse and lay.q8_on and not lay.q8_slim and lay.conv.mask_flag
-                and lay.conv.mask.shape == lay.conv.weight.shape
-                and ops.conv_fwd_q8_sparse24_ok(lay.geom_act)]
-        if cand:
-            counts = torch.zeros(len(cand), dtype=torch.int32, device=dev)
-            for i, lay in enumerate(cand):
-                ops.nm_violations(lay.conv.mask.contiguous(), counts[i:i + 1])
-            for lay, bad in zip(cand, counts.cpu().tolist()):
-                if not bad:
-                    lay.q8s_on = True
-                    self.fp8_sparse_layers.append(lay.li + 1)
+                lay.form = "q8_slim"
+        if self.q8_sparse:
+            for lay in self._conforming([lay for lay in self.layers
+                                         if lay.form == "q8" and lay.conv.mask_flag
+                                         and lay.conv.mask.shape == lay.conv.weight.shape
+                                         and ops.conv_fwd_q8_sparse24_ok(lay.geom_act)]):
+                lay.form = "q8_sparse24"
         writers = {}                      # buffer id -> the blocks that write into it
         for lay in self.layers:
             if not lay.is_last:
@@ -996,17 +1101,6 @@ class Engine:
             qld = max(self._q8_ld(r) for r in readers[t.buf]) if shared else self._q8_ld(lay)
             if qld != t.ld or lay.q8_slim:
                 lay.geom_q8 = self._q8_geom(lay, qld)
-            if lay.q8s_on:
-                nw, ni, ne = ops.q8_sparse24_elems(lay.geom_q8)
-                if getattr(lay, "wqs", None) is None or lay.wqs.numel() != nw:
-                    lay.wqs = torch.zeros(nw, dtype=torch.uint8, device=dev)
-                    lay.widx8 = torch.zeros(ni, dtype=torch.int32, device=dev)
-            else:
-                nw, ne = ops.q8_slim_elems(lay.geom_q8) if lay.q8_slim else ops.q8_elems(lay.geom_q8)
-                if getattr(lay, "wq", None) is None or lay.wq.numel() != nw:
-                    lay.wq = torch.zeros(nw, dtype=torch.uint8, device=dev)
-            if getattr(lay, "wexp", None) is None or lay.wexp.numel() != ne:
-                lay.wexp = torch.zeros(ne, dtype=torch.int32, device=dev)
             if shared:
                 live.add(t.buf)
                 if t.buf not in self.qbufs or self._qld.get(t.buf) != qld:
@@ -1019,12 +1113,12 @@ class Engine:
                     raise NotImplementedError("fp8-qat: conv%d reads an fp16 tensor that another block reads too"
                                               % (lay.li + 1))
                 key = (self.B, t.H, t.W, qld)
-                if getattr(lay, "_xq_key", None) != key:
+                if lay._xq_key != key:
                     lay._xq, lay._xq_key = ops.alloc_padded_q8(self.B, t.H, t.W, qld, dev, pad=self._pad_for(t.W)), key
                 lay.xq = lay._xq
             if qat_train:
                 # fp32 raw output + its statistics slab (the fp16 ones come back when the block leaves the set), and w_q
-                if getattr(lay, "y_f16", None) is None:
+                if lay.y_f16 is None:
                     lay.y_f16, lay.stats_f16 = lay.y, lay.stats
                     lay.y_f32 = torch.zeros(lay.M * lay.cout, dtype=torch.float32, device=dev)
                     lay.stats_q8 = torch.zeros(ops.conv_fwd_q8_stats_rows(lay.geom_act), 2, ops.round_up(lay.cout, 256),
@@ -1055,7 +1149,7 @@ class Engine:
 
     def _qat_train(self, lay):
         """Does this block train in the fp8 arithmetic (a block of fp8_layers in an "fp8-qat" training engine)?"""
-        return self.qat and self.train_layout and getattr(lay, "q8_on", False)
+        return self.qat and self.train_layout and lay.q8_on
 
     def qat_block_io(self, conv_number):
         """Debug accessor of an "fp8-qat" training engine: what fp8 block `conv_number` read and wrote in the last training
@@ -1068,16 +1162,10 @@ class Engine:
         if not self._qat_train(lay):
             raise McamdError("conv%d is not an fp8 block of an fp8-qat training engine (fp8_layers = %r)"
                              % (conv_number, self.fp8_layers))
-        B = self.B
-
-        def interior(buf, f8, t, C):
-            pad = self._pad_for(t.W)
-            v = ops.padded_view_q8(buf, B, t.H, t.W, t.ld, pad) if f8 else ops.padded_view(buf, B, t.H, t.W, t.ld, pad)
-            v = v[:, 1:-1, 1:-1, t.choff:t.choff + C].permute(0, 3, 1, 2).contiguous().cpu()
-            return v if f8 else v.float()
+        B, interior = self.B, self._interior
         t, t2, ti = lay.out_t, lay.out2_t, lay.tin
         cdst = 4 * lay.cout if lay.mode == L.DST_REORG else lay.cout
-        out = dict(x8=interior(lay.xq if lay.xq is not None else self.qbufs[ti.buf], True, ti, lay.cin),
+        out = dict(x8=interior(lay.xq if lay.xq is not None else self.qbufs[ti.buf], True, ti, lay.cin, lay.geom_q8.x_ld),
                    x16=interior(self.bufs[ti.buf], False, ti, lay.cin),
                    y=lay.y.view(B, lay.H, lay.W, lay.cout).permute(0, 3, 1, 2).contiguous().cpu(),
                    scale=lay.scale.cpu(), shift=lay.shift.cpu(), mean=lay.mean.cpu(), invstd=lay.invstd.cpu(), slope=lay.slope,
@@ -1094,24 +1182,26 @@ class Engine:
             out["out2_16"] = interior(self.bufs[t2.buf], False, t2, lay.cout)
         return out
 
+    def _interior(self, buf, f8, t, C, ld=None):
+        """The C channels of tensor `t` in `buf` -- its byte buffer of `ld` bytes per pixel (`f8`; default: the engine's
+        buffer of that tensor) or its fp16 one -- without the halo, as a CPU NCHW tensor: codes (uint8) or fp32 values."""
+        pad = self._pad_for(t.W)
+        if f8:
+            v = ops.padded_view_q8(buf, self.B, t.H, t.W, ld or self._qld[t.buf], pad)
+        else:
+            v = ops.padded_view(buf, self.B, t.H, t.W, t.ld, pad)
+        v = v[:, 1:-1, 1:-1, t.choff:t.choff + C].permute(0, 3, 1, 2).contiguous().cpu()
+        return v if f8 else v.float()
+
     def q8_block_io(self, conv_number):
         """Debug accessor: what fp8 block `conv_number` read and wrote in the last forward, from the engine's own buffers,
         as CPU NCHW tensors -- `x8` e4m3 codes of the input; `y` (and `y2`, the full-resolution copy, or None) as codes
         (uint8) where `y_f8` (`y2_f8`) else fp16 values; `dst` "plain" / "pool" / "reorg"; the epilogue's `scale`, `shift`,
         `slope`."""
         lay = self.layers[conv_number - 1]
-        if not getattr(lay, "q8_on", False):
+        if not lay.q8_on:
             raise McamdError("conv%d is not an fp8 block (fp8_layers = %r)" % (conv_number, self.fp8_layers))
-        B = self.B
-
-        def read(buf, f8, t, C, ld=None):
-            if f8:
-                ld = ld or self._qld[t.buf]
-                v = buf[: B * (t.H + 2) * (t.W + 2) * ld].view(B, t.H + 2, t.W + 2, ld)
-            else:
-                v = ops.padded_view(buf, B, t.H, t.W, t.ld)
-            v = v[:, 1:-1, 1:-1, t.choff:t.choff + C].permute(0, 3, 1, 2).contiguous().cpu()
-            return v if f8 else v.float()
+        read = self._interior
         t, t2, ti = lay.out_t, lay.out2_t, lay.tin
         cdst = 4 * lay.cout if lay.mode == L.DST_REORG else lay.cout
         out = dict(x8=read(lay.xq if lay.xq is not None else self.qbufs[ti.buf], True, ti, lay.cin, lay.geom_q8.x_ld),
@@ -1196,7 +1286,8 @@ class Engine:
         through `chan_perm`.  Pool / reorg / route keep or compose permutations.  Called when a mask
         object changes (one host sync for the kept counts)."""
         dev = self.device
-        self._plan_epoch += 1            # every recorded plan is stale: buffers / maps / geometries below change
+        # (every recorded plan is stale, buffers / maps / geometries below change: _choose_forms, the one caller, has bumped
+        # _plan_epoch)
         tperm = {-1: None}               # tensor id -> LongTensor physical position -> original channel (None = identity)
         by_ci = {lay.index: lay for lay in self.layers}
         wbytes = 16
@@ -1281,7 +1372,7 @@ class Engine:
             self._fold_key = None
             if lay.gin is not None:
                 lay.gin.zero_()       # a folding consumer's dgrad leaves the dead channels of G untouched: they must be finite
-            for t in (lay.tin, getattr(lay, "out_t", None), getattr(lay, "out2_t", None)):
+            for t in (lay.tin, lay.out_t, lay.out2_t):
                 if t is not None and t.ps != t.ps0:      # planes of a formerly folded producer: back to the full width
                     t.ps = t.ps0
                     v = ops.padded_view(self.bufs[t.buf], self.B, t.H, t.W, t.ld)[:, 1:-1, 1:-1]
@@ -1422,10 +1513,10 @@ class Engine:
         if splitk and (self.precise or self.q8):
             raise McamdError("splitk=True runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r"
                              % (self.precision,))
+        if mode not in (None, "2:4", "block"):
+            raise McamdError("sparse must be None, '2:4' or 'block' (got %r)" % (mode,))
         max_kept = float(getattr(self.model, "sparse_max_kept", BSPARSE_MAX_KEPT)) if mode == "block" else None
-        force = bool(training) or mode != self._sparse_mode or splitk != self._splitk_on or max_kept != self._bs_max_kept
-        self._sparse_mode, self._splitk_on, self._bs_max_kept = mode, splitk, max_kept
-        self.pack(force=force, training=training)
+        self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept)
         self.serial += 1
         tin = self.layers[0].tin
         xs = x.detach().contiguous().float()
@@ -1498,7 +1589,7 @@ class Engine:
                 self._timed('fwd', lay, ops.stem_block_fwd, B, lay.H, lay.W, xin, lay.wp, bn.weight.data, bn.bias.data,
                             bn.running_mean, bn.running_var, training, lay.scale, lay.shift, lay.mean, lay.invstd, lay.slope,
                             self.bufs[t.buf], t.ld, t.choff, lay.stem_ws if lay.fused_stem else None,
-                            momentum=bn.momentum if bn.momentum is not None else 0.1, eps=bn.eps, cout=lay.cout,
+                            momentum=_momentum(bn), eps=bn.eps, cout=lay.cout,
                             planes=self.act_planes)
                 continue
             if training and lay.stem_split:
@@ -1518,8 +1609,7 @@ class Engine:
                                 lay.stats if training else None)
                 ops.bn_coeffs(lay.stats if training else None, lay.cout, lay.M, bn.weight.data, bn.bias.data,
                               bn.running_mean, bn.running_var, training, lay.scale, lay.shift, lay.mean, lay.invstd,
-                              momentum=bn.momentum if bn.momentum is not None else 0.1, eps=bn.eps, perm=lay.perm32,
-                              ones_channel=lay.ones_idx)
+                              momentum=_momentum(bn), eps=bn.eps, perm=lay.perm32, ones_channel=lay.ones_idx)
                 t, t2 = lay.out_t, lay.out2_t
                 cons = self._fused_1x1(lay)
                 if cons is not None:
@@ -1529,81 +1619,51 @@ class Engine:
                     fused_done.add(cons.li)
                     self.fused_1x1_launches += 1
                     continue
-                af = getattr(lay, "act_full", None) if (training and self.pool_act_on) else None
+                af = lay.act_full if (training and self.pool_act_on) else None
+                dst2, dst2_pad = self._dst2(t2)
                 ops.bn_act_fwd(B, lay.H, lay.W, lay.bn_width or lay.cout, lay.y, lay.cout, 0, lay.scale, lay.shift,
-                               lay.slope, lay.mode, self.bufs[t.buf], t.ld, t.choff,
-                               self.bufs[t2.buf] if t2 is not None else None,
-                               t2.ld if t2 is not None else 0, t2.choff if t2 is not None else 0, border=lay.border,
+                               lay.slope, lay.mode, self.bufs[t.buf], t.ld, t.choff, *dst2, border=lay.border,
                                planes=self._planes_for(lay.out_id), dst_plane=t.ps, dst2_plane=t2.ps if t2 is not None else 0,
-                               dst_pad=self._pad_for(t.W), dst2_pad=self._pad_for(t2.W) if t2 is not None else 0,
+                               dst_pad=self._pad_for(t.W), dst2_pad=dst2_pad,
                                planes2=self._planes_for(lay.out2_id) if t2 is not None else 0,
                                pool_act=af, pool_act_ld=ops.round_up(lay.cout, 8) if af is not None else 0,
                                pool_act_pad=self._pad_for(lay.W) if af is not None else 0)
                 continue
-            if not training and (self._fused_eval(lay) or (self.q8 and lay.q8_on)):
+            if not training and (self._fused_eval(lay) or lay.q8_on):
                 # inference: BN (running statistics) + LeakyReLU -- and the MaxPool / Reorg that follows the block -- in the
                 # conv epilogue, written straight into the consumer's padded buffer: the raw output is never stored (one
                 # fp16 rounding per layer, no second pass)
                 ops.bn_coeffs(None, lay.cout, lay.M, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, False,
                               lay.scale, lay.shift, lay.mean, lay.invstd, eps=bn.eps)
-                t, t2 = lay.out_t, lay.out2_t
-                q8 = self.q8 and lay.q8_on
-                # destination form of the epilogue: plain / pool (+ the full-resolution copy y2, bytes or fp16) / reorg
-                y2 = None if t2 is None else (self.qbufs if q8 and lay.q8_y2 else self.bufs)[t2.buf]
-                dst = dict(dst_mode=lay.mode, y2=y2, y2_ld=self._q8_tld(t2, q8 and lay.q8_y2) if t2 is not None else 0,
-                           y2_choff=t2.choff if t2 is not None else 0)
-                if q8:                      # e4m3 activations x e4m3 weights (Darknet.precision = "fp8", _update_q8)
-                    x8 = self.qbufs.get(lay.tin.buf)
-                    if lay.xq is not None:  # the fp16 -> fp8 edge: cast pass over the padded input slice
-                        ti, x8 = lay.tin, lay.xq
-                        self._timed('cast', lay, ops.cast_q8, xin, B * (ti.H + 2) * (ti.W + 2), ti.ld, ti.choff, lay.cin,
-                                    x8, lay.geom_q8.x_ld, ti.choff)
-                    y, y_ld = (self.qbufs[t.buf] if lay.q8_y else self.bufs[t.buf]), self._q8_tld(t, lay.q8_y)
-                    if lay.q8s_on:          # ... 2:4-compressed weights on the sparse MFMA ("fp8-2:4")
-                        self._timed('fwd', lay, ops.conv_fwd_q8_sparse24, lay.geom_q8, x8, lay.wqs, lay.widx8, lay.wexp, y,
-                                    y_ld, t.choff, lay.scale, lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
-                        continue
-                    if lay.q8_slim:         # ... a slim model's block: zero-padded K, border table in the epilogue
-                        self._timed('fwd', lay, ops.conv_fwd_q8_slim, lay.geom_q8, x8, lay.wq, lay.wexp, y, y_ld, t.choff,
-                                    lay.scale, lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, border=lay.border,
-                                    border_ld=lay.cout, **dst)
-                        continue
-                    self._timed('fwd', lay, ops.conv_fwd_q8, lay.geom_q8, x8, lay.wq, lay.wexp, y, y_ld, t.choff, lay.scale,
-                                lay.shift, lay.slope, y_f8=lay.q8_y, y2_f8=lay.q8_y2, **dst)
-                    continue
-                if lay.sp_on:       # 2:4 weights on the sparse MFMA (Darknet.sparse, _update_sparse)
-                    self._timed('fwd', lay, ops.conv_fwd_sparse24, lay.geom_act, xin, lay.wsp, lay.widx, self.bufs[t.buf], t.ld,
-                                t.choff, lay.scale, lay.shift, lay.slope, **dst)
-                    continue
-                if lay.bs_on:       # the non-zero K chunks of each 64-filter tile only (Darknet.sparse = "block", _refresh_bsparse)
-                    self._timed('fwd', lay, ops.conv_fwd_bsparse, lay.geom_act, xin, lay.wp, lay.bs_count, lay.bs_list,
-                                self.bufs[t.buf], t.ld, t.choff, lay.scale, lay.shift, lay.slope, **dst)
-                    continue
-                if lay.sk_on:       # few pixels: K cut into slices over the whole chip (Darknet.splitk, _update_splitk)
-                    self._timed('fwd', lay, ops.conv_fwd_splitk, lay.geom_act, xin, lay.wp, self.bufs[t.buf], t.ld, t.choff,
-                                lay.scale, lay.shift, lay.slope, slices=lay.sk_slices, workspace=self._splitk_ws, **dst)
-                    continue
-                self._timed('fwd', lay, ops.conv_fwd_padded, lay.geom_act, xin, lay.wp, self.bufs[t.buf], t.ld, t.choff,
-                            lay.scale, lay.shift, lay.slope, **dst)
+                t = lay.out_t
+                # destination form of the epilogue: plain / pool (+ the full-resolution copy y2) / reorg, each as bytes where
+                # the engine holds the tensor as e4m3 (fp8 forms only) and as fp16 elsewhere
+                y, y_ld = (self.qbufs if lay.q8_y else self.bufs)[t.buf], self._q8_tld(t, lay.q8_y)
+                (y2, y2_ld, y2_choff), _ = self._dst2(lay.out2_t, lay.q8_y2)
+                form = _FORMS[lay.form]
+                args, kw = form.operands(self, lay, xin)
+                self._timed('fwd', lay, getattr(ops, form.fwd), *args, y, y_ld, t.choff, lay.scale, lay.shift, lay.slope,
+                            dst_mode=lay.mode, y2=y2, y2_ld=y2_ld, y2_choff=y2_choff, **kw)
                 continue
             if training and self._qat_train(lay):
                 self._qat_forward(lay, xin)
                 continue
-            if lay.sk_on and not training:
-                self._timed('fwd', lay, ops.conv_fwd_raw_splitk, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0,
-                            slices=lay.sk_slices, workspace=self._splitk_ws)
-            else:
-                self._timed('fwd', lay, ops.conv_fwd_raw, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0, lay.stats if training else None)
+            _FORMS[lay.form].raw(self, lay, xin, training)
             ops.bn_coeffs(lay.stats if training else None, lay.cout, lay.M, bn.weight.data, bn.bias.data,
                           bn.running_mean, bn.running_var, training, lay.scale, lay.shift, lay.mean, lay.invstd,
-                          momentum=bn.momentum if bn.momentum is not None else 0.1, eps=bn.eps, perm=lay.perm32,
-                          ones_channel=lay.ones_idx)
-            t, t2 = lay.out_t, lay.out2_t
+                          momentum=_momentum(bn), eps=bn.eps, perm=lay.perm32, ones_channel=lay.ones_idx)
+            t = lay.out_t
+            dst2, dst2_pad = self._dst2(lay.out2_t)
             ops.bn_act_fwd(B, lay.H, lay.W, lay.bn_width or lay.cout, lay.y, lay.cout, 0, lay.scale, lay.shift,
-                           lay.slope, lay.mode, self.bufs[t.buf], t.ld, t.choff,
-                           self.bufs[t2.buf] if t2 is not None else None,
-                           t2.ld if t2 is not None else 0, t2.choff if t2 is not None else 0, border=lay.border,
-                           dst_pad=self._pad_for(t.W), dst2_pad=self._pad_for(t2.W) if t2 is not None else 0)
+                           lay.slope, lay.mode, self.bufs[t.buf], t.ld, t.choff, *dst2, border=lay.border,
+                           dst_pad=self._pad_for(t.W), dst2_pad=dst2_pad)
+
+    def _dst2(self, t2, f8=False):
+        """The second destination of a block (the full-resolution copy beside a pooled output): ((buffer, leading dimension,
+        channel offset), pad form), all None / 0 where the block has none.  `f8`: the tensor's byte buffer."""
+        if t2 is None:
+            return (None, 0, 0), 0
+        return ((self.qbufs if f8 else self.bufs)[t2.buf], self._q8_tld(t2, f8), t2.choff), self._pad_for(t2.W)
 
     def _fused_1x1_act(self, lay):
         """(positional, keyword) arguments of the activation pass of the PLAIN block `lay` in hi | lo storage, as
@@ -1659,13 +1719,11 @@ class Engine:
                         lay.cin, x8, ti.ld, ti.choff, write_back=True)
         self._timed('fwd', lay, ops.conv_fwd_q8_raw, lay.geom_act, x8, lay.wq, lay.wexp, lay.y, lay.cout, 0, lay.stats)
         ops.bn_coeffs(lay.stats, lay.cout, lay.M, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, True,
-                      lay.scale, lay.shift, lay.mean, lay.invstd, momentum=bn.momentum if bn.momentum is not None else 0.1,
-                      eps=bn.eps)
+                      lay.scale, lay.shift, lay.mean, lay.invstd, momentum=_momentum(bn), eps=bn.eps)
         t, t2 = lay.out_t, lay.out2_t
+        dst2, dst2_pad = self._dst2(t2)
         ops.bn_act_fwd(B, lay.H, lay.W, lay.cout, lay.y, lay.cout, 0, lay.scale, lay.shift, lay.slope, lay.mode,
-                       self.bufs[t.buf], t.ld, t.choff, self.bufs[t2.buf] if t2 is not None else None,
-                       t2.ld if t2 is not None else 0, t2.choff if t2 is not None else 0,
-                       dst_pad=self._pad_for(t.W), dst2_pad=self._pad_for(t2.W) if t2 is not None else 0,
+                       self.bufs[t.buf], t.ld, t.choff, *dst2, dst_pad=self._pad_for(t.W), dst2_pad=dst2_pad,
                        dst_q8=self.qbufs[t.buf] if lay.q8_y else None,
                        dst2_q8=self.qbufs[t2.buf] if (t2 is not None and lay.q8_y2) else None)
 
@@ -1675,8 +1733,7 @@ class Engine:
         bn, t = lay.bn, lay.out_t
         ops.stem_block_stats(self.B, lay.H, lay.W, lay.sh_img, lay.sh_wp, lay.stats, x_lo=lay.sh_img_lo, wp_lo=lay.sh_wp_lo)
         ops.bn_coeffs(lay.stats, lay.cout, lay.M, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, True,
-                      lay.scale, lay.shift, lay.mean, lay.invstd, momentum=bn.momentum if bn.momentum is not None else 0.1,
-                      eps=bn.eps)
+                      lay.scale, lay.shift, lay.mean, lay.invstd, momentum=_momentum(bn), eps=bn.eps)
         ops.stem_block_fwd(self.B, lay.H, lay.W, lay.sh_img, lay.sh_wp, bn.weight.data, bn.bias.data, None, None, False,
                            lay.scale, lay.shift, lay.mean, lay.invstd, lay.slope, self.bufs[t.buf], t.ld, t.choff, None,
                            eps=bn.eps, cout=lay.cout, planes=self.act_planes, x_lo=lay.sh_img_lo, wp_lo=lay.sh_wp_lo)
@@ -1738,7 +1795,7 @@ class Engine:
             act = dict(act=self.bufs[t.buf], act_ld=t.ld, act_choff=t.choff, act_pad=self._pad_for(t.W))
         elif self.bwd_from_act and self.precise and self.train_layout and lay.mode == L.DST_POOL and lay.slope > 0.0:
             # ... and a MaxPool block's read the full-resolution fp16 copy of its activation (mcamd_act_desc.pool_act)
-            if self.pool_act_on and getattr(lay, "act_full", None) is not None:
+            if self.pool_act_on and lay.act_full is not None:
                 act = dict(act=lay.act_full, act_ld=ops.round_up(lay.cout, 8), act_choff=0, act_pad=self._pad_for(lay.W))
             if g2 is None and lay.y is not None:
                 # ... and the pass that forms the sums needs the pooled element only: the hi plane of the consumer's

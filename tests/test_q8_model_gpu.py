@@ -1,4 +1,4 @@
-"""Darknet.precision = "fp8": post-training e4m3 inference of YOLOv2-VOC (csrc/conv_q8.hip, Engine._update_q8) -- which
+"""Darknet.precision = "fp8": post-training e4m3 inference of YOLOv2-VOC (csrc/conv_q8.hip, Engine._choose_q8) -- which
 blocks are quantised, every block recomputed exactly from the input the engine gave it, the end-to-end error LEVEL against
 the CPU restatement (two correct 8-bit engines differ from each other at the level of their own quantisation noise, so
 outputs are never compared directly), re-packing, the precision rules and no allocation in a warm forward."""

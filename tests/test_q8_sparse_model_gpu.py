@@ -1,5 +1,5 @@
 """Darknet.precision = "fp8-2:4": the fp8 engine with the nm_prune masks on the sparse fp8 kernel (csrc/conv_q8_sparse.hip,
-Engine._update_q8) -- which blocks go sparse, every block recomputed from the input the engine gave it, the end-to-end
+Engine._choose_q8) -- which blocks go sparse, every block recomputed from the input the engine gave it, the end-to-end
 error LEVEL against the CPU restatement (q8_ref.forward with the 2:4 masks: a 2:4 mask is just a mask), the per-block
 fallback to the dense fp8 kernel, engine separation, the precision rules and no allocation in a warm forward."""
 import pytest
