@@ -322,6 +322,13 @@ int mcamd_pack_q8(const mcamd_conv_geom* g, const float* w_oihw, const float* ma
  * 0: fp16 as mcamd_conv_fwd writes it.  Both `pad` forms of x. */
 int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
                       const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream);
+/* The kernel instance an fp8 block launches for this geometry, from the launches' own choice (host logic only, no GPU).
+ * form: 0 mcamd_conv_fwd_q8 with the inference epilogue, 1 mcamd_conv_fwd_q8 with MCAMD_EPI_RAW_F32, 2 mcamd_conv_fwd_q8_slim
+ * with a border table (without one it launches form 0's kernel on the same tile; the geometry is held to
+ * mcamd_conv_fwd_q8_slim_ok), 3 mcamd_conv_fwd_q8_sparse24.  out = {bmw, bnp, f8mfma, stages, mtiles, ntiles, grid} -- a
+ * workgroup tile of bmw filters x bnp pixels, whether MCAMD_Q8_MFMA selects the fp8 MFMA, LDS ring stages, the tiles along
+ * the pixels and the filters, and the blocks launched (whole rounds of 8 pixel tiles). */
+int mcamd_conv_fwd_q8_info(const mcamd_conv_geom* g, int32_t form, int32_t out[7]);
 /* The cast pass of an fp16 -> fp8 edge: fp16 [pixels][src_ld] channels [src_choff, +C) -> bytes q(2 x) [pixels][dst_ld]
  * channels [dst_choff, +C); C, the leading dimensions and offsets multiples of 8.  Halo pixels are pixels like any other. */
 int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst, int32_t dst_ld,

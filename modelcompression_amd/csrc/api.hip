@@ -1001,6 +1001,18 @@ extern "C" int mcamd_conv_fwd_q8_sparse24(const mcamd_conv_geom* g, const void* 
     return mcamd_conv_q8_sparse_launch(a, idx, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
 }
 
+// mcamd_q8_choice()'s answer: what mcamd_conv_fwd_q8 (forms 0, 1), mcamd_conv_fwd_q8_slim (form 2) and
+// mcamd_conv_fwd_q8_sparse24 (form 3) launch for this geometry (host logic only)
+extern "C" int mcamd_conv_fwd_q8_info(const mcamd_conv_geom* g, int32_t form, int32_t out[7]) {
+    MCAMD_REQUIRE(g && out, "conv_fwd_q8_info: null argument");
+    MCAMD_REQUIRE(form >= MCAMD_Q8_FORM_INFER && form <= MCAMD_Q8_FORM_SPARSE, "conv_fwd_q8_info: form %d is none of 0 .. 3", form);
+    MCAMD_REQUIRE(form == MCAMD_Q8_FORM_BORDER ? mcamd_conv_fwd_q8_slim_ok(g) : mcamd_conv_fwd_q8_ok(g),
+                  "conv_fwd_q8_info: geometry has no fp8 form of this kind (mcamd_conv_fwd_q8_ok / mcamd_conv_fwd_q8_slim_ok)");
+    const Q8Choice c = mcamd_q8_choice((long long)g->B * g->H * g->W, g->cout, form);
+    out[0] = c.bmw, out[1] = c.bnp, out[2] = c.f8mfma, out[3] = c.stages, out[4] = c.mtiles, out[5] = c.ntiles, out[6] = c.grid;
+    return MCAMD_OK;
+}
+
 static int cast_q8_any(const void* src, int64_t pixels, int32_t src_ld, int32_t src_choff, int32_t C, void* dst, int32_t dst_ld,
                        int32_t dst_choff, int back, void* stream) {
     MCAMD_REQUIRE(src && dst && pixels > 0 && C > 0, "cast_q8: null pointer / empty");

@@ -268,8 +268,8 @@ void conv_q8_border_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, 
 }
 
 template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW = false>
-static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, hipStream_t st, const float* border = nullptr,
-                            int border_ld = 0) {
+static int conv_q8_launch_t(IgemmArgs& a, const Q8Choice& c, const int* wexp, int y_f8, int y2_f8, hipStream_t st,
+                            const float* border = nullptr, int border_ld = 0) {
     constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
     constexpr int RING = NSTAGE * (BMW + BNP) * 64;
     constexpr int PB = BMW + 8;                    // tile row pitch (conv_q8_kernel)
@@ -278,49 +278,69 @@ static int conv_q8_launch_t(IgemmArgs& a, const int* wexp, int y_f8, int y2_f8, 
     const bool has2 = a.y2 != nullptr;
     const bool mixed = (y_f8 || (has2 && y2_f8)) && (!y_f8 || (has2 && !y2_f8));
     const int lds = (mixed && !RAW) ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);   // (RAW: its tiles lie inside the ring)
-    a.num_mtiles = (a.M + BNP - 1) / BNP;
-    a.num_ntiles = (a.N + BMW - 1) / BMW;
-    const int grid = (a.num_mtiles + 7) / 8 * 8 * a.num_ntiles;
+    a.num_mtiles = c.mtiles;
+    a.num_ntiles = c.ntiles;
     if constexpr (!RAW) {
         if (border) {                              // (the same tile, ring and LDS as the launch without a table)
             auto kern = conv_q8_border_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
             MCAMD_LDS_OPT_IN(kern, LDS);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8, border, border_ld);
+            hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8, border, border_ld);
             MCAMD_LAUNCH_CHECK("conv_fwd_q8_slim");
             return MCAMD_OK;
         }
     }
     auto kern = conv_q8_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA, RAW>;
     MCAMD_LDS_OPT_IN(kern, LDS);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8);
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8);
     MCAMD_LAUNCH_CHECK("conv_fwd_q8");
     return MCAMD_OK;
 }
 
 // Tiles as conv_sparse.hip's: 256 channels x 128 pixels (8 waves of 64 x 64) from 256 filters, 128 x 128 (4 waves) from
-// 128, 64 x 128 below; a 3-deep ring of 64-byte rows (72 / 48 / 36 KB: two workgroups per CU).
-// MCAMD_Q8_MFMA: 0 = fp16 MFMAs on converted bytes, 1 = the block-scaled fp8 MFMA.
+// 128, 64 x 128 below; a 3-deep ring of 64-byte rows (72 / 48 / 36 KB: two workgroups per CU).  The same rule in all four
+// forms (inference, raw fp32, border table, 2:4 -- `form` is there so that a form can get a rule of its own).
+// MCAMD_Q8_MFMA: 0 = fp16 MFMAs on converted bytes, 1 = the (block-scaled / sparse) fp8 MFMA: faster, not
+// byte-exact (see the kernels' comments).
+// No 256-channel tile in the default form: with the converted fragments it needs 136 registers (133 with 2:4 weights), one
+// workgroup per CU, and measured 0.87-0.92 x the fp16 kernels on the 256- and 512-filter layers (2:4: 0.73-0.84 x the
+// 128 x 128 tile there, 0.94 x over the whole forward).
+// The grid is whole rounds of 8 pixel tiles (xcd_tile).
+Q8Choice mcamd_q8_choice(long long M, int N, int form) {
+    (void)form;
+    Q8Choice c;
+    c.f8mfma = MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0) ? 1 : 0;
+    c.bnp = 128;
+    c.stages = 3;
+    if (c.f8mfma && N >= 256) c.bmw = 256;
+    else c.bmw = N >= 128 ? 128 : 64;
+    c.mtiles = (int)((M + c.bnp - 1) / c.bnp);
+    c.ntiles = (N + c.bmw - 1) / c.bmw;
+    c.grid = (c.mtiles + 7) / 8 * 8 * c.ntiles;
+    return c;
+}
+
 // `border` (mcamd_conv_fwd_q8_slim; inference epilogue only): fp32 [16][border_ld] table added by pixel class, or NULL.
 int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st, const float* border, int border_ld) {
     const int* we = (const int*)wexp;
-    if (a.mode == MCAMD_EPI_RAW_F32) {             // training: fp32 y + statistics, the same tile per filter count
-        if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {
-            if (a.N >= 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true, true>(a, we, 0, 0, st);
-            if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true, true>(a, we, 0, 0, st);
-            return conv_q8_launch_t<64, 128, 32, 64, 3, true, true>(a, we, 0, 0, st);
+    const bool raw = a.mode == MCAMD_EPI_RAW_F32;  // training: fp32 y + statistics, the same tile per filter count
+    const Q8Choice c = mcamd_q8_choice(a.M, a.N, raw ? MCAMD_Q8_FORM_RAW : border ? MCAMD_Q8_FORM_BORDER : MCAMD_Q8_FORM_INFER);
+    if (c.bnp == 128 && c.stages == 3) {
+        if (raw) {
+            if (c.f8mfma && c.bmw == 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true, true>(a, c, we, 0, 0, st);
+            if (c.f8mfma && c.bmw == 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true, true>(a, c, we, 0, 0, st);
+            if (c.f8mfma && c.bmw == 64) return conv_q8_launch_t<64, 128, 32, 64, 3, true, true>(a, c, we, 0, 0, st);
+            if (!c.f8mfma && c.bmw == 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false, true>(a, c, we, 0, 0, st);
+            if (!c.f8mfma && c.bmw == 64) return conv_q8_launch_t<64, 128, 32, 64, 3, false, true>(a, c, we, 0, 0, st);
+        } else {
+            if (c.f8mfma && c.bmw == 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true>(a, c, we, y_f8, y2_f8, st, border, border_ld);
+            if (c.f8mfma && c.bmw == 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true>(a, c, we, y_f8, y2_f8, st, border, border_ld);
+            if (c.f8mfma && c.bmw == 64) return conv_q8_launch_t<64, 128, 32, 64, 3, true>(a, c, we, y_f8, y2_f8, st, border, border_ld);
+            if (!c.f8mfma && c.bmw == 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false>(a, c, we, y_f8, y2_f8, st, border, border_ld);
+            if (!c.f8mfma && c.bmw == 64) return conv_q8_launch_t<64, 128, 32, 64, 3, false>(a, c, we, y_f8, y2_f8, st, border, border_ld);
         }
-        if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false, true>(a, we, 0, 0, st);
-        return conv_q8_launch_t<64, 128, 32, 64, 3, false, true>(a, we, 0, 0, st);
     }
-    if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {       // the fp8 MFMA: faster, not byte-exact (see the kernel's comment)
-        if (a.N >= 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st, border, border_ld);
-        if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true>(a, we, y_f8, y2_f8, st, border, border_ld);
-        return conv_q8_launch_t<64, 128, 32, 64, 3, true>(a, we, y_f8, y2_f8, st, border, border_ld);
-    }
-    // (no 256-channel tile here: with the converted fragments it needs 136 registers, one workgroup per CU, and measured
-    // 0.87-0.92 x the fp16 kernels on the 256- and 512-filter layers)
-    if (a.N >= 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false>(a, we, y_f8, y2_f8, st, border, border_ld);
-    return conv_q8_launch_t<64, 128, 32, 64, 3, false>(a, we, y_f8, y2_f8, st, border, border_ld);
+    mcamd_set_error("conv_fwd_q8: no kernel instance %d x %d, fp8 MFMA %d, %d stages", c.bmw, c.bnp, c.f8mfma, c.stages);
+    return MCAMD_EINVAL;
 }
 
 // ---------------------------------------------------------------------------------------

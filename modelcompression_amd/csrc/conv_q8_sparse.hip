@@ -187,7 +187,8 @@ void conv_q8_sparse_kernel(IgemmArgs a, const unsigned* __restrict__ idx, int np
 }
 
 template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
-static int conv_q8_sparse_launch_t(IgemmArgs& a, const unsigned* idx, int npad, const int* wexp, int y_f8, int y2_f8, hipStream_t st) {
+static int conv_q8_sparse_launch_t(IgemmArgs& a, const Q8Choice& c, const unsigned* idx, int npad, const int* wexp, int y_f8, int y2_f8,
+                                   hipStream_t st) {
     constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
     constexpr int I_BYTES = BMW * 8 > 1024 ? BMW * 8 : 1024;
     constexpr int RING = NSTAGE * (BMW * 32 + BNP * 64 + I_BYTES);
@@ -199,31 +200,30 @@ static int conv_q8_sparse_launch_t(IgemmArgs& a, const unsigned* idx, int npad, 
     const int lds = mixed ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);
     auto kern = conv_q8_sparse_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
     MCAMD_LDS_OPT_IN(kern, LDS);
-    a.num_mtiles = (a.M + BNP - 1) / BNP;
-    a.num_ntiles = (a.N + BMW - 1) / BMW;
-    const int grid = (a.num_mtiles + 7) / 8 * 8 * a.num_ntiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a, idx, npad, wexp, y_f8, y2_f8);
+    a.num_mtiles = c.mtiles;
+    a.num_ntiles = c.ntiles;
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), lds, st, a, idx, npad, wexp, y_f8, y2_f8);
     MCAMD_LAUNCH_CHECK("conv_fwd_q8_sparse24");
     return MCAMD_OK;
 }
 
-// Tiles as conv_q8.hip's: 256 channels x 128 pixels (8 waves of 64 x 64) from 256 filters with the fp8 MFMA, 128 x 128
-// (4 waves) from 128, 64 x 128 below; a 3-deep ring (54 / 39 / 33 KB).
+// The tile is mcamd_q8_choice's (conv_q8.hip: 256 channels x 128 pixels from 256 filters with the fp8 MFMA, 128 x 128 from
+// 128, 64 x 128 below); a 3-deep ring (54 / 39 / 33 KB).
 // MCAMD_Q8_MFMA: 0 = fp16 sparse MFMAs on converted bytes, 1 = the fp8 sparse MFMA.
 int mcamd_conv_q8_sparse_launch(IgemmArgs& a, const void* idx, const void* wexp, int y_f8, int y2_f8, hipStream_t st) {
     const int* we = (const int*)wexp;
     const unsigned* ix = (const unsigned*)idx;
     const int npad = round_up_int(a.N, 256);
-    if (MCAMD_ENV_INT("MCAMD_Q8_MFMA", 0)) {       // the fp8 sparse MFMA: faster, not byte-exact (see the kernel's comment)
-        if (a.N >= 256) return conv_q8_sparse_launch_t<256, 128, 64, 64, 3, true>(a, ix, npad, we, y_f8, y2_f8, st);
-        if (a.N >= 128) return conv_q8_sparse_launch_t<128, 128, 64, 64, 3, true>(a, ix, npad, we, y_f8, y2_f8, st);
-        return conv_q8_sparse_launch_t<64, 128, 32, 64, 3, true>(a, ix, npad, we, y_f8, y2_f8, st);
+    const Q8Choice c = mcamd_q8_choice(a.M, a.N, MCAMD_Q8_FORM_SPARSE);
+    if (c.bnp == 128 && c.stages == 3) {
+        if (c.f8mfma && c.bmw == 256) return conv_q8_sparse_launch_t<256, 128, 64, 64, 3, true>(a, c, ix, npad, we, y_f8, y2_f8, st);
+        if (c.f8mfma && c.bmw == 128) return conv_q8_sparse_launch_t<128, 128, 64, 64, 3, true>(a, c, ix, npad, we, y_f8, y2_f8, st);
+        if (c.f8mfma && c.bmw == 64) return conv_q8_sparse_launch_t<64, 128, 32, 64, 3, true>(a, c, ix, npad, we, y_f8, y2_f8, st);
+        if (!c.f8mfma && c.bmw == 128) return conv_q8_sparse_launch_t<128, 128, 64, 64, 3, false>(a, c, ix, npad, we, y_f8, y2_f8, st);
+        if (!c.f8mfma && c.bmw == 64) return conv_q8_sparse_launch_t<64, 128, 32, 64, 3, false>(a, c, ix, npad, we, y_f8, y2_f8, st);
     }
-    // (no 256-channel tile here either: the A fragments are half the dense ones, but with the converted fragments it still
-    // needs 133 registers -- one workgroup per CU; held to 128 it spills -- and measured 0.94 x the 128 x 128 tile over the
-    // whole forward, 0.73-0.84 x on the 256- and 512-filter layers: DESIGN.md 3k)
-    if (a.N >= 128) return conv_q8_sparse_launch_t<128, 128, 64, 64, 3, false>(a, ix, npad, we, y_f8, y2_f8, st);
-    return conv_q8_sparse_launch_t<64, 128, 32, 64, 3, false>(a, ix, npad, we, y_f8, y2_f8, st);
+    mcamd_set_error("conv_fwd_q8_sparse24: no kernel instance %d x %d, fp8 MFMA %d, %d stages", c.bmw, c.bnp, c.f8mfma, c.stages);
+    return MCAMD_EINVAL;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -140,6 +140,17 @@ Sparse24Choice mcamd_sparse24_choice(long long M, int N, int kb);
 int mcamd_sparse24_launch(IgemmArgs& a, const void* idx, hipStream_t st);
 int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, void* idx, int cout, int cin, int ntaps,
                                int cin_tap, int kb, hipStream_t st);
+// conv_q8.hip / conv_q8_sparse.hip: mcamd_q8_choice names the conv_q8_kernel / conv_q8_border_kernel / conv_q8_sparse_kernel
+// instance (bmw filters x bnp pixels, the MFMA form MCAMD_Q8_MFMA selects, LDS ring stages) and its grid for M pixels x N
+// filters in one of the four forms; both launches dispatch on it
+#define MCAMD_Q8_FORM_INFER 0    // conv_q8_kernel, inference epilogue
+#define MCAMD_Q8_FORM_RAW 1      // conv_q8_kernel, raw fp32 epilogue + statistics (fp8-qat)
+#define MCAMD_Q8_FORM_BORDER 2   // conv_q8_border_kernel (slim models with a border table)
+#define MCAMD_Q8_FORM_SPARSE 3   // conv_q8_sparse_kernel (2:4)
+struct Q8Choice {
+    int bmw, bnp, f8mfma, stages, mtiles, ntiles, grid;
+};
+Q8Choice mcamd_q8_choice(long long M, int N, int form);
 // conv_q8.hip: e4m3 operands (byte strides in `a`), mode 2 epilogue with a format per destination; packer; cast pass
 // (`border`: fp32 [16][border_ld] table the inference epilogue adds by pixel class, mcamd_conv_fwd_q8_slim; NULL = none)
 int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hipStream_t st, const float* border = nullptr,

@@ -1163,12 +1163,27 @@ def pack_q8(g, w, mask=None, out_w=None, out_exp=None):
     return out_w, out_exp
 
 
+Q8_FORM_INFER, Q8_FORM_RAW, Q8_FORM_BORDER, Q8_FORM_SPARSE = 0, 1, 2, 3
+Q8Info = collections.namedtuple("Q8Info", "bmw bnp f8mfma stages mtiles ntiles grid")
+
+
+def conv_fwd_q8_info(g, form=Q8_FORM_INFER):
+    """The kernel instance an fp8 block launches for `g` in `form` (Q8_FORM_INFER: conv_fwd_q8; Q8_FORM_RAW: conv_fwd_q8_raw;
+    Q8_FORM_BORDER: conv_fwd_q8_slim with a table; Q8_FORM_SPARSE: conv_fwd_q8_sparse24): a tile of bmw filters x bnp pixels,
+    whether MCAMD_Q8_MFMA selects the fp8 MFMA, LDS ring stages, its tiles along the pixels and the filters and its grid:
+    mcamd_conv_fwd_q8_info, the launches' own choice.  Needs no GPU."""
+    out = (C.c_int32 * 7)()
+    check(L.lib().mcamd_conv_fwd_q8_info(C.byref(g), int(form), out), "mcamd_conv_fwd_q8_info")
+    return Q8Info(*out)
+
+
 def conv_fwd_q8(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
-                y2_choff=0, y_f8=False, y2_f8=False):
+                y2_choff=0, y_f8=False, y2_f8=False, overflow=None):
     """The quantised block (mcamd_conv_fwd_q8): e4m3 activations x e4m3 weights, the inference epilogue of conv_fwd_padded
-    with `y` / `y2` written as e4m3 bytes (y_f8 / y2_f8) or fp16."""
+    with `y` / `y2` written as e4m3 bytes (y_f8 / y2_f8) or fp16.
+    `overflow`: optional int32 flag, set to 1 when an fp16 output was clamped to +-65504 (bytes saturate silently)."""
     e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
-             y2_choff=y2_choff)
+             y2_choff=y2_choff, overflow=overflow)
     check(L.lib().mcamd_conv_fwd_q8(C.byref(g), ptr(x8), ptr(wq), ptr(wexp), C.byref(e), int(bool(y_f8)), int(bool(y2_f8)),
                                     stream_ptr()), "mcamd_conv_fwd_q8")
 
@@ -1201,11 +1216,11 @@ def pack_q8_slim(g, w, mask=None, out_w=None, out_exp=None):
 
 
 def conv_fwd_q8_slim(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
-                     y2_choff=0, y_f8=False, y2_f8=False, border=None, border_ld=0):
+                     y2_choff=0, y_f8=False, y2_f8=False, border=None, border_ld=0, overflow=None):
     """conv_fwd_q8 for cin % 8 == 0 from pack_q8_slim's rows, with the fp32 [16][border_ld] table `border` (or None) added to
-    the raw value by pixel class in the epilogue (mcamd_conv_fwd_q8_slim)."""
+    the raw value by pixel class in the epilogue (mcamd_conv_fwd_q8_slim).  `overflow`: as conv_fwd_q8."""
     e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
-             y2_choff=y2_choff)
+             y2_choff=y2_choff, overflow=overflow)
     if border is not None:
         assert border.dtype == torch.float32 and border.is_contiguous()
         border_ld = border_ld or border.shape[-1]
@@ -1278,11 +1293,11 @@ def pack_q8_sparse24(g, w, mask=None, out_w=None, out_idx=None, out_exp=None):
 
 
 def conv_fwd_q8_sparse24(g, x8, wq, idx, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None,
-                         y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False):
+                         y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None):
     """conv_fwd_q8 on 2:4-compressed e4m3 weights (mcamd_conv_fwd_q8_sparse24): the same arguments plus the index words,
-    the same arithmetic and output."""
+    the same arithmetic and output.  `overflow`: as conv_fwd_q8."""
     e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
-             y2_choff=y2_choff)
+             y2_choff=y2_choff, overflow=overflow)
     check(L.lib().mcamd_conv_fwd_q8_sparse24(C.byref(g), ptr(x8), ptr(wq), ptr(idx), ptr(wexp), C.byref(e), int(bool(y_f8)),
                                              int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q8_sparse24")
 

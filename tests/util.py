@@ -69,11 +69,41 @@ def fill_padded(dev, c, t, ld, choff, width, pad):
     return buf
 
 
-def padded_split(buf, B, H, W, ld, choff, n):
-    """padded NHWC destination (guards included) -> the interior slice as [B][n][H][W]; everything else as a flat vector"""
+def padded_split(buf, B, H, W, ld, choff, n, sentinel=NAN):
+    """padded NHWC destination (guards included; fp16, or bytes with the sentinel NAN8) -> the interior slice as
+    [B][n][H][W]; everything else as a flat vector, the slice's place filled with the sentinel"""
     all_ = whole(buf).clone()
     lo = buf.storage_offset()
     v = all_[lo:lo + B * (H + 2) * (W + 2) * ld].view(B, H + 2, W + 2, ld)
     got = v[:, 1:-1, 1:-1, choff:choff + n].permute(0, 3, 1, 2).clone().cpu()
-    v[:, 1:-1, 1:-1, choff:choff + n] = NAN
+    v[:, 1:-1, 1:-1, choff:choff + n] = sentinel
     return got, all_.cpu()
+
+
+# ---- the same for e4m3 byte buffers: the sentinel is the NaN code 0x7F, which no store of q() ever writes
+NAN8 = 0x7F
+
+
+def is_sentinel(t):
+    """elementwise: does the element still hold its sentinel (NaN for floating point, NAN8 for bytes)?"""
+    return t == NAN8 if t.dtype == torch.uint8 else torch.isnan(t)
+
+
+def has_nan_code(b):
+    """does a tensor of e4m3 codes hold a NaN code (0x7F / 0xFF)?"""
+    return bool(((b & 0x7F) == 0x7F).any())
+
+
+def fill_padded_q8(dev, c, a8, ld, choff, width, pad, fill=None):
+    """[B][C][H][W] codes (cpu uint8) -> padded NHWC byte device buffer of `ld` channels with the tensor at channel `choff`;
+    the slice [choff, choff + width) is 0x00 around the image and, beyond the tensor's channels, 0x00 or the codes `fill`
+    [B][width - C][H][W] inside the image; every other byte is the NaN code."""
+    npix = ops.padded_pixels(c.B, c.H, c.W, pad)
+    buf = torch.full((npix * ld,), NAN8, dtype=torch.uint8, device=dev)
+    buf.view(npix, ld)[:, choff:choff + width] = 0
+    inner = ops.padded_view_q8(buf, c.B, c.H, c.W, ld, pad)[:, 1:-1, 1:-1]
+    C_ = a8.shape[1]
+    inner[..., choff:choff + C_] = a8.permute(0, 2, 3, 1).to(dev)
+    if fill is not None:
+        inner[..., choff + C_:choff + width] = fill.permute(0, 2, 3, 1).to(dev)
+    return buf
