@@ -335,6 +335,31 @@ int mcamd_cast_q8(const void* src, int64_t pixels, int32_t src_ld, int32_t src_c
                   int32_t dst_choff, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Split-K form of the quantised block for low-batch inference (an addition beyond the reference; conv_q8_splitk.hip,
+ * Darknet.precision = "fp8-splitk"): mcamd_conv_fwd_splitk's launch design on mcamd_conv_fwd_q8's operands.
+ * Workgroup (tile of 64 filters x 64 pixels, slice s) of a first launch multiplies the 64-byte K chunks
+ * [floor(s n / S), floor((s + 1) n / S)) of the tile's n = k*k * cin / 64 chunks -- in the MFMA form MCAMD_Q8_MFMA selects --
+ * and stores its unrounded fp32 accumulators to slab s of `workspace` ([S][Mpad][Npad] fp32, whole tiles); a second launch on
+ * the same stream sums the S slabs of every element in slice order in fp32 and applies mcamd_conv_fwd_q8's epilogue,
+ * v = leaky(scale_f * 2^-(e_f + 1) * S + shift_f), written as q(2 v) bytes or saturated fp16 per destination.  No atomics,
+ * no workgroup waits for another: the result is a function of the operands, the MFMA form and S only; with S = 1 it is
+ * mcamd_conv_fwd_q8's result code for code, and it differs from it by the order of the fp32 sum only for any S.
+ *
+ * Geometries: mcamd_conv_fwd_q8_ok and pad == 0.  Epilogue: MCAMD_EPI_PAD_F16 (dst_mode PLAIN / POOL (+ y2) / REORG) with
+ * stats == NULL.  Operands: exactly mcamd_conv_fwd_q8's (mcamd_pack_q8's bytes and exponents, the same byte buffer).
+ * ------------------------------------------------------------------------- */
+/* Host logic only.  The policy is mcamd_conv_fwd_splitk_info's (MCAMD_SPLITK_CUS, MCAMD_SPLITK_MIN_CHUNKS, the clamp to 16)
+ * on chunks of 64 k: slices = 0 asks it, slices > 0 sizes a forced count in [1, chunks].  out->bm = pixels, bn = filters,
+ * bk = 64 of the partial kernel's tile. */
+int mcamd_conv_fwd_q8_splitk_info(const mcamd_conv_geom* g, int32_t dst_mode, int32_t slices, mcamd_splitk_info* out);
+/* The two launches.  y_f8 / y2_f8 as mcamd_conv_fwd_q8; slices as above; workspace: at least the workspace_bytes the query
+ * returns for the same arguments, 16-byte aligned, free again once the call's launches have run.  Everything refused is
+ * refused before the first launch. */
+int mcamd_conv_fwd_q8_splitk(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
+                             const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, int32_t slices, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * fp8 inference of slim_export models (an addition beyond the reference): the fp8 block above for an input
  * channel count that is a multiple of 8 only, and with the border table of a conv that lost input channels (slim.py) in
  * the epilogue.  With cin_pad = round_up(cin, 64):

@@ -26,6 +26,7 @@ SOURCES = {
     "conv_splitk.hip": [],
     "conv_q8.hip": [],
     "conv_q8_sparse.hip": [],
+    "conv_q8_splitk.hip": [],             # conv_q8.hip's flags: the epilogue expression contracts the way the unsplit kernel's does
     "conv_stem.hip": [],
     "conv_stem_block.hip": [],
     "conv_stem_f32.hip": [],

@@ -881,6 +881,66 @@ extern "C" int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const
 }
 
 // ---------------------------------------------------------------------------------------
+// split-K fp8 forward for low-batch inference (conv_q8_splitk.hip; Darknet.precision = "fp8-splitk")
+// ---------------------------------------------------------------------------------------
+// what both entries refuse, then the plan for `slices` (0 = the policy: mcamd_splitk_plan, the fp16 pair's, on 64-byte chunks)
+static int q8_splitk_plan_for(const mcamd_conv_geom* g, int dst_mode, int slices, const char* what, SplitkPlan* p) {
+    MCAMD_REQUIRE(g, "%s: null geometry", what);
+    MCAMD_REQUIRE(g->stem == 0, "%s: stem %d: the first layer has no fp8 split-K form", what, g->stem);
+    MCAMD_REQUIRE(g->pad == 0, "%s: pad %d: the shared-halo form is not accepted (pad must be 0)", what, g->pad);
+    MCAMD_REQUIRE(g->cin > 0 && g->cin % 64 == 0, "%s: cin %d: the byte K loop needs cin %% 64 == 0", what, g->cin);
+    if (check_geom(g, what)) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_ok(g), "%s: geometry has no fp8 form (mcamd_conv_fwd_q8_ok)", what);
+    MCAMD_REQUIRE(dst_mode == MCAMD_DST_PLAIN || dst_mode == MCAMD_DST_POOL || dst_mode == MCAMD_DST_REORG, "%s: bad dst_mode %d", what,
+                  dst_mode);
+    MCAMD_REQUIRE(slices >= 0, "%s: slices %d is negative", what, slices);
+    *p = mcamd_splitk_plan((long long)g->B * g->H * g->W, g->cout, g->cin, ntaps_of(g) * g->cin, slices);
+    MCAMD_REQUIRE(p->slices >= 1 && p->slices <= p->chunks, "%s: slices %d outside [1, chunks = %d]", what, p->slices, p->chunks);
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_conv_fwd_q8_splitk_info(const mcamd_conv_geom* g, int32_t dst_mode, int32_t slices, mcamd_splitk_info* out) {
+    MCAMD_REQUIRE(out, "conv_fwd_q8_splitk_info: null output");
+    SplitkPlan p;
+    if (q8_splitk_plan_for(g, dst_mode, slices, "conv_fwd_q8_splitk_info", &p)) return MCAMD_EINVAL;
+    out->slices = p.slices;
+    out->bm = p.bm, out->bn = p.bn, out->bk = p.bk;
+    out->chunks = p.chunks;
+    out->tiles = p.tiles;
+    out->workspace_bytes = (int64_t)p.slices * p.slab_elems * (int64_t)sizeof(float);
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_conv_fwd_q8_splitk(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
+                                        const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, int32_t slices, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_splitk: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) {
+            return mcamd_conv_fwd_q8_splitk(&g_, x8, wq, wexp, &e_, y_f8, y2_f8, slices, workspace, workspace_bytes, s);
+        });
+    }
+    MCAMD_REQUIRE(g, "conv_fwd_q8_splitk: null geometry");
+    MCAMD_REQUIRE(epi, "conv_fwd_q8_splitk: null epilogue");
+    MCAMD_REQUIRE(epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8_splitk: epilogue mode %d: mode 2 (MCAMD_EPI_PAD_F16) only", epi->mode);
+    SplitkPlan p;
+    if (q8_splitk_plan_for(g, epi->dst_mode, slices, "conv_fwd_q8_splitk", &p)) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(epi->stats == nullptr, "conv_fwd_q8_splitk: stats must be NULL (no statistics slab in the split-K form)");
+    MCAMD_REQUIRE(x8 && wq && wexp, "conv_fwd_q8_splitk: null input");
+    const size_t need = (size_t)p.slices * (size_t)p.slab_elems * sizeof(float);
+    MCAMD_REQUIRE(workspace, "conv_fwd_q8_splitk: null workspace (%zu bytes needed)", need);
+    MCAMD_REQUIRE(workspace_bytes >= need, "conv_fwd_q8_splitk: workspace_bytes %zu is short of the %zu bytes %d slices need",
+                  workspace_bytes, need, p.slices);
+    MCAMD_REQUIRE(((uintptr_t)workspace & 15) == 0, "conv_fwd_q8_splitk: workspace must be 16-byte aligned (%zu bytes needed)", need);
+    IgemmArgs a;
+    fill_operand(a, g, x8, wq, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_splitk", 0)) return MCAMD_EINVAL;
+    return mcamd_q8_splitk_launch(a, p, wexp, y_f8 != 0, y2_f8 != 0, (float*)workspace, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------
 // fp8 inference of slim_export models: cin a multiple of 8 on zero-padded weight rows, border tables
 // ---------------------------------------------------------------------------------------
 extern "C" int32_t mcamd_conv_fwd_q8_slim_ok(const mcamd_conv_geom* g) {

@@ -164,6 +164,9 @@ int mcamd_cast_q8_launch(const void* src, long long pixels, int src_ld, int src_
                          int dst_choff, int back, hipStream_t st);
 int mcamd_fakequant_q8_launch(const float* w, const float* mask, const void* wexp, float* out, int cout, int cin, int ntaps,
                               hipStream_t st);
+// conv_q8_splitk.hip: split-K pair on conv_q8.hip's operands (partial + finish launch, mode 2 epilogue).  `p`: mcamd_splitk_plan
+// for 64-wide chunks (cin % 64 == 0); ws: p.slices * p.slab_elems floats; the MFMA form is mcamd_q8_choice's
+int mcamd_q8_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* wexp, int y_f8, int y2_f8, float* ws, hipStream_t st);
 // conv_q8_sparse.hip: conv_q8.hip's block on 2:4-compressed e4m3 weights (sparse MFMA); packer
 int mcamd_conv_q8_sparse_launch(IgemmArgs& a, const void* idx, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
 int mcamd_pack_q8_sparse24_launch(const float* w, const float* mask, void* wq, void* idx, void* wexp, int cout, int cin,

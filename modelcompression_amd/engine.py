@@ -57,8 +57,8 @@ _LAYER_FIELDS = dict(
     fused_stem=False, fused_stem_eval=False, stem_shadow=False, stem_split=False, stem_f32=False, stem_ws=None, weff=None,
     sh_img=None, sh_img_lo=None, sh_geom=None, sh_wp=None, sh_wp_lo=None, sh_coef=None,
     f8=False, f8_wexp=ops.F8_WEXP_DEFAULT, f8_wexp_eff=ops.F8_WEXP_DEFAULT,
-    # inference form (Engine._choose_forms, _FORMS) and what belongs to one: split-K slices, 2:4 values + index words,
-    # block-sparse chunk lists
+    # inference form (Engine._choose_forms, _FORMS) and what belongs to one: split-K slices (forms "splitk" and "q8_splitk"),
+    # 2:4 values + index words, block-sparse chunk lists
     form="dense", sk_slices=1, wsp=None, widx=None, bs_count=None, bs_list=None,
     # fp8: launch geometry on the byte buffer, byte destinations, private input copy, packed operands; "fp8-qat" training:
     # the fp32 raw output + statistics that stand in for the fp16 ones, and the values the weight bytes stand for
@@ -80,7 +80,7 @@ class _Layer:
     sp_on = property(lambda self: self.form == "sparse24")
     bs_on = property(lambda self: self.form == "bsparse")
     sk_on = property(lambda self: self.form == "splitk")
-    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24"))
+    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk"))
     q8s_on = property(lambda self: self.form == "q8_sparse24")
     q8_slim = property(lambda self: self.form == "q8_slim")
 
@@ -273,8 +273,24 @@ class _Q8Sparse24(_Q8):
     bufs = (("wqs", torch.uint8), ("widx8", torch.int32), ("wexp", torch.int32))
 
 
+class _Q8SplitK(_Q8):
+    """An fp8 block of few pixels: the byte K loop cut into slices over the whole chip ("fp8-splitk", csrc/conv_q8_splitk.hip).
+    The operands are _Q8's; the workspace is the engine's one split-K workspace."""
+    fwd = "conv_fwd_q8_splitk"
+
+    def alloc(self, eng, lays):
+        _Q8.alloc(self, eng, lays)
+        need = max(ops.conv_fwd_q8_splitk_info(lay.geom_q8, lay.mode, lay.sk_slices).workspace_bytes for lay in lays)
+        if eng._splitk_ws is None or eng._splitk_ws.numel() * 4 < need:
+            eng._splitk_ws = torch.empty(need // 4, dtype=torch.float32, device=eng.device)
+
+    def operands(self, eng, lay, xin):
+        args, kw = _Q8.operands(self, eng, lay, xin)
+        return args, dict(kw, slices=lay.sk_slices, workspace=eng._splitk_ws)
+
+
 _FORMS = {"dense": _Dense(), "splitk": _SplitK(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "q8": _Q8(),
-          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24()}
+          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK()}
 
 
 def _probe_side_stream(device, tries=8):
@@ -335,25 +351,34 @@ class Engine:
         (csrc/conv_q8.hip, `fp8_layers`, _choose_q8); a training-mode forward raises.
         "fp8-2:4" -- the "fp8" engine with every fp8 block whose mask conforms to 2:4 on the sparse fp8 kernel
         (csrc/conv_q8_sparse.hip, `fp8_sparse_layers`); every other block runs what "fp8" runs.
+        "fp8-splitk" -- the "fp8" engine for low batches: every block of form "q8" whose launch the split-K
+        policy gives two slices or more runs the fp8 split-K pair (csrc/conv_q8_splitk.hip, `fp8_splitk_layers`); every other
+        block, and every batch the policy does not split, runs exactly what "fp8" runs.  Differs from "fp8" by the order of
+        the fp32 sums only.
         "fp8-qat" -- fp8 quantisation-aware training: in training mode every block of `fp8_layers` runs its
         forward in the "fp8" arithmetic on batch statistics (mcamd_conv_fwd_q8 with the fp32 raw epilogue, byte + dequantised
         fp16 destinations) and a straight-through backward on the fp16 kernels; every other block trains as in "fp16".  An
         inference-mode forward is the "fp8" engine's, bit for bit."""
-        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-qat"):
-            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4' or 'fp8-qat' (got %r)" % (precision,))
+        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat"):
+            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk' or 'fp8-qat' (got %r)"
+                             % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-qat")
+        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_choose_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-qat")
+        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat")
         self.qat = precision == "fp8-qat"      # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
         # "fp8-2:4": the subset of fp8_layers whose masks conform to 2:4 and that run mcamd_conv_fwd_q8_sparse24
         self.q8_sparse = precision == "fp8-2:4"
         self.fp8_sparse_layers = []
+        # "fp8-splitk": the subset of fp8_layers the split-K policy gives two slices or more and that run
+        # mcamd_conv_fwd_q8_splitk (they share `_splitk_ws` below)
+        self.q8_splitk = precision == "fp8-splitk"
+        self.fp8_splitk_layers = []
         self.qbufs = {}
         self._qld = {}                         # buffer id -> bytes per pixel of its byte buffer (_choose_q8)
         self.grad_scale = float(grad_scale)
@@ -975,8 +1000,10 @@ class Engine:
         the block-sparse policy's choice, Darknet.sparse, sparse_max_kept and Darknet.splitk (pack).  In this order:
           1. (pack) the block-sparse policy has read the masked weights; the blocks it chose are exempt from
           2. filter compaction and folding, planned again when the masks or that choice changed;
-          3. then fp8 (every eligible block of an fp8 engine), 2:4 (sparse = "2:4": every eligible block whose mask conforms
-             and whose geometry mcamd_conv_fwd_sparse24_ok accepts) or block-sparse (sparse = "block": the chosen blocks that
+          3. then fp8 (every eligible block of an fp8 engine; under "fp8-splitk" behind it: every block of form "q8" -- not the
+             slim ones -- whose launch the split-K policy gives two slices or more, mcamd_conv_fwd_q8_splitk_info), 2:4
+             (sparse = "2:4": every eligible block whose mask conforms and whose geometry mcamd_conv_fwd_sparse24_ok accepts)
+             or block-sparse (sparse = "block": the chosen blocks that
              are still eligible -- one whose producer was compacted after all, so that its input channels are permuted, stays
              dense), which depend on perm / g_cols / fold -- and all of it in front of the pack job table, which names w_q of
              an fp8-qat training block;
@@ -1004,6 +1031,13 @@ class Engine:
         if self.q8:
             self._choose_q8()
             self._pack_key = None
+            if self.q8_splitk:
+                for lay in self.layers:
+                    if lay.form != "q8" or lay.geom_q8.pad:
+                        continue
+                    info = ops.conv_fwd_q8_splitk_info(lay.geom_q8, lay.mode)
+                    if info.slices >= 2:
+                        lay.form, lay.sk_slices = "q8_splitk", info.slices
         elif sparse == "2:4":
             for lay in self._conforming([lay for lay in self.layers
                                          if self._eligible(lay) and lay.conv.mask_flag and lay.cin % 4 == 0
@@ -1029,7 +1063,8 @@ class Engine:
             _FORMS[name].alloc(self, lays)
         nums = lambda *names: [lay.li + 1 for lay in self.layers if lay.form in names]
         self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
-        self.fp8_layers, self.fp8_sparse_layers = nums("q8", "q8_slim", "q8_sparse24"), nums("q8_sparse24")
+        self.fp8_layers, self.fp8_sparse_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk"), nums("q8_sparse24")
+        self.fp8_splitk_layers = nums("q8_splitk")
         self._form_key = key
 
     def _splitk_form(self, lay):
@@ -1511,8 +1546,9 @@ class Engine:
                                 "model.sparse = None" if self.q8 and mode == "2:4" else ""))
         splitk = bool(getattr(self.model, "splitk", False)) and not training
         if splitk and (self.precise or self.q8):
-            raise McamdError("splitk=True runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r"
-                             % (self.precision,))
+            raise McamdError("splitk=True runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r%s"
+                             % (self.precision, "; split-K on the fp8 engine: model.precision = 'fp8-splitk' with "
+                                "model.splitk = False" if self.q8 else ""))
         if mode not in (None, "2:4", "block"):
             raise McamdError("sparse must be None, '2:4' or 'block' (got %r)" % (mode,))
         max_kept = float(getattr(self.model, "sparse_max_kept", BSPARSE_MAX_KEPT)) if mode == "block" else None

@@ -301,6 +301,9 @@ class Darknet(nn.Module):
         # accumulation, no calibration data (csrc/conv_q8.hip; MCAMD_Q8_MFMA picks the MFMA form).  A training-mode
         # forward raises.  "fp8-2:4": the "fp8" engine with every fp8 block whose mask conforms to 2:4 (nm_prune) on the sparse
         # fp8 MFMA kernel (engine.Engine.fp8_sparse_layers, csrc/conv_q8_sparse.hip); `sparse` stays None with it.
+        # "fp8-splitk" (eval only): the "fp8" engine for one image at a time -- every fp8 block whose launch would leave most CUs
+        # idle runs as a split-K pair on the same byte operands (engine.Engine.fp8_splitk_layers, csrc/conv_q8_splitk.hip,
+        # DESIGN.md 3v); batches the policy does not split run exactly what "fp8" runs; `splitk` stays False with it.
         # "fp8-qat" (an addition beyond the reference): fp8 quantisation-aware training -- in training mode the blocks of
         # engine.Engine.fp8_layers run their forward in the "fp8" arithmetic on batch statistics and a straight-through backward
         # on the fp16 kernels, every other block trains as in "fp16"; in eval mode it is the "fp8" engine, bit for bit

@@ -1188,6 +1188,32 @@ def conv_fwd_q8(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slo
                                     stream_ptr()), "mcamd_conv_fwd_q8")
 
 
+# ... with the K axis cut into slices for low-batch inference (csrc/conv_q8_splitk.hip)
+def conv_fwd_q8_splitk_info(g, dst_mode=0, slices=0):
+    """mcamd_splitk_info of a split-K fp8 forward of `g`: host logic only.  slices = 0 asks the policy -- conv_fwd_splitk_info's,
+    on chunks of 64 k (info.slices == 1: it does not split this launch); > 0 sizes a forced slice count."""
+    info = SplitkInfo()
+    check(L.lib().mcamd_conv_fwd_q8_splitk_info(C.byref(g), dst_mode, slices, C.byref(info)), "mcamd_conv_fwd_q8_splitk_info")
+    return info
+
+
+def conv_fwd_q8_splitk(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
+                       y2_choff=0, y_f8=False, y2_f8=False, overflow=None, slices=0, workspace=None):
+    """conv_fwd_q8 with the K axis cut into `slices` slices (0 = the policy's count): a partial launch into `workspace` (fp32,
+    conv_fwd_q8_splitk_info(...).workspace_bytes; None allocates one) and a finish launch with the same epilogue and
+    destination formats.  Returns the workspace."""
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff, overflow=overflow)
+    if workspace is None:
+        info = conv_fwd_q8_splitk_info(g, dst_mode, slices)
+        workspace = torch.empty(info.workspace_bytes // 4, dtype=torch.float32, device=x8.device)
+    _need_cuda(x8, workspace)
+    check(L.lib().mcamd_conv_fwd_q8_splitk(C.byref(g), ptr(x8), ptr(wq), ptr(wexp), C.byref(e), int(bool(y_f8)), int(bool(y2_f8)),
+                                           slices, ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr()),
+          "mcamd_conv_fwd_q8_splitk")
+    return workspace
+
+
 # ... of slim_export models (DESIGN.md 3m): cin a multiple of 8 on zero-padded weight rows, border table in the epilogue
 def conv_fwd_q8_slim_ok(g):
     """Does mcamd_conv_fwd_q8_slim accept this geometry?  (Shared by the engine and the tests; needs no device.)"""

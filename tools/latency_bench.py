@@ -1,6 +1,8 @@
-"""Low-batch inference latency of YOLOv2-VOC at 416x416, precision "fp16": the eval forward and model.detect in milliseconds
-per call at B = 1, 2, 4 and 8 with Darknet.splitk off and on, for the dense model and (B = 1) for a
-quick_filter_prune(60) -> slim_export model.
+"""Low-batch inference latency of YOLOv2-VOC at 416x416: the eval forward and model.detect in milliseconds per call at
+B = 1, 2, 4 and 8 with split-K off and on, for the dense model and (B = 1) for a quick_filter_prune(60) -> slim_export model.
+--precision fp16 (the default): precision "fp16" with Darknet.splitk off / on.  --precision fp8: the off leg is precision "fp8",
+the on leg "fp8-splitk" (MCAMD_Q8_MFMA picks the MFMA form of both), and the fp16 legs of the dense model are
+measured in the same process beside them.
 
 Method: both settings alternate in one process, PAIRS pairs; each sample is a loop of CALLS calls after warm-up with a device
 synchronise only around the whole loop (host clock), so a sample is the sustained time per call, launch overhead included;
@@ -9,7 +11,8 @@ instrumented pass (the engine's HIP events around every conv launch, plan replay
 tiles, slices, us unsplit, us split (partial + finish launch).  Launch counts: the library calls of the recorded forward plan
 (a split block is one call and two kernels), the eval-mode bn_coeffs launches among them and the layout pass in front.
 
-usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N]        (--json: one JSON document on stdout)"""
+usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8]
+                                                                             (--json: one JSON document on stdout)"""
 import json
 import os
 import sys
@@ -29,13 +32,29 @@ def arg(name, dflt):
 
 
 CALLS, PAIRS, PASSES = max(200, arg("--calls", 200)), max(4, arg("--pairs", 4)), 7
+PRECISION = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp16"
+if PRECISION not in ("fp16", "fp8"):
+    raise SystemExit("--precision must be fp16 or fp8 (got %r)" % PRECISION)
 if not torch.cuda.is_available():
     raise SystemExit("latency_bench needs the GPU")
 dev = torch.device("cuda", 0)
 
 
 def engine(m, x):
-    return [e for k, e in m._engines.items() if k[0] == tuple(x.shape) and not e.train_layout][0]
+    """The inference engine of this input shape in the model's current precision."""
+    return [e for k, e in m._engines.items() if k[0] == tuple(x.shape) and not e.train_layout and e.precision == m.precision][0]
+
+
+def leg(m, flag):
+    """Split-K off / on: Darknet.splitk of a "fp16" model; the precisions "fp8" / "fp8-splitk" of an fp8 one."""
+    if m.precision == "fp16":
+        m.splitk = flag
+    else:
+        m.precision = "fp8-splitk" if flag else "fp8"
+
+
+def split_layers(eng):
+    return list(eng.fp8_splitk_layers if eng.q8 else eng.splitk_layers)
 
 
 def median(v):
@@ -59,7 +78,7 @@ def latencies(m, x):
     out = {"forward": {"off": [], "on": []}, "detect": {"off": [], "on": []}}
     for _ in range(PAIRS):
         for flag in (False, True):
-            m.splitk = flag
+            leg(m, flag)
             out["forward"]["on" if flag else "off"].append(sample(lambda: m(x)))
             out["detect"]["on" if flag else "off"].append(sample(lambda: m.detect(x)))
     return out
@@ -68,7 +87,7 @@ def latencies(m, x):
 def layer_table(m, x):
     per = {}
     for flag in (False, True):
-        m.splitk = flag
+        leg(m, flag)
         m(x)
         torch.cuda.synchronize()
         eng = engine(m, x)
@@ -78,27 +97,35 @@ def layer_table(m, x):
             m(x)
             torch.cuda.synchronize()
             for tag, lay, e0, e1, _host in eng.events:
-                acc.setdefault(lay.li + 1, []).append(e0.elapsed_time(e1) * 1e3)
+                if tag == 'fwd':      # (the conv launches; an fp8 engine also times the cast pass of an fp16 -> fp8 edge)
+                    acc.setdefault(lay.li + 1, []).append(e0.elapsed_time(e1) * 1e3)
             eng.events = None
         per[flag] = {k: median(v) for k, v in acc.items()}
     eng = engine(m, x)
     rows = []
     for lay in eng.layers:
-        form = eng._splitk_form(lay)
         tiles = slices = None
-        if form is not None and not lay.geom_act.pad:
-            info = ops.conv_fwd_splitk_info(lay.geom_act, form[0], form[1])
-            tiles, slices = info.tiles, info.slices
+        if eng.q8:              # the fp8 blocks the pair can stand in for: forms "q8" and "q8_splitk"
+            split = lay.form == "q8_splitk"
+            if lay.form in ("q8", "q8_splitk") and not lay.geom_q8.pad:
+                info = ops.conv_fwd_q8_splitk_info(lay.geom_q8, lay.mode)
+                tiles, slices = info.tiles, info.slices
+        else:
+            split = bool(lay.sk_on)
+            form = eng._splitk_form(lay)
+            if form is not None and not lay.geom_act.pad:
+                info = ops.conv_fwd_splitk_info(lay.geom_act, form[0], form[1])
+                tiles, slices = info.tiles, info.slices
         n = lay.li + 1
-        rows.append({"conv": n, "tiles": tiles, "slices": slices, "split": bool(lay.sk_on),
-                     "us_unsplit": per[False].get(n), "us_split": per[True].get(n) if lay.sk_on else None})
+        rows.append({"conv": n, "tiles": tiles, "slices": slices, "split": split, "form": lay.form,
+                     "us_unsplit": per[False].get(n), "us_split": per[True].get(n) if split else None})
     return rows
 
 
 def launches(m, x):
     out = {}
     for flag in (False, True):
-        m.splitk = flag
+        leg(m, flag)
         m(x)
         eng = engine(m, x)
         plan = eng._fwd_plans.get(False)
@@ -106,31 +133,31 @@ def launches(m, x):
             "plan_calls": plan.launches if plan is not None else None,
             "bn_coeffs": sum(1 for lay in eng.layers if lay.bn is not None),
             "layout_pass": 1,
-            "splitk_finish_kernels": len(eng.splitk_layers),
-            "splitk_layers": list(eng.splitk_layers)}
+            "splitk_finish_kernels": len(split_layers(eng)),
+            "splitk_layers": split_layers(eng)}
     return out
 
 
 def bench_model(m, batches, name):
-    res = {"model": name, "batches": {}}
+    res = {"model": name, "precision": m.precision, "batches": {}}
     for B in batches:
         x = synthetic_batch(B, 416, 416, seed=0, device=dev)
         r = latencies(m, x)
         r["launches"] = launches(m, x)
         if B == 1:
             r["layers"] = layer_table(m, x)
-        m.splitk = False
+        leg(m, False)
         a = m(x).clone()
-        m.splitk = True
+        leg(m, True)
         b = m(x)
         r["rel_l2_on_vs_off"] = float((b.double() - a.double()).norm() / a.double().norm())
         res["batches"][str(B)] = r
-    m.splitk = False
+    leg(m, False)
     return res
 
 
 def show(res):
-    print("== %s" % res["model"])
+    print("== %s, precision %s" % (res["model"], res["precision"]))
     for B, r in res["batches"].items():
         for what in ("forward", "detect"):
             off, on = r[what]["off"], r[what]["on"]
@@ -151,7 +178,7 @@ def show(res):
 with torch.no_grad():
     dense = init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
     dense.eval()
-    dense.precision = "fp16"
+    dense.precision = PRECISION
     results = [bench_model(dense, (1, 2, 4, 8), "yolov2-voc")]
     pruned = init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
     pruned.set_masks(quick_filter_prune(pruned, 60.0))
@@ -159,10 +186,14 @@ with torch.no_grad():
     with tempfile.TemporaryDirectory() as tmp:
         thin = slim.slim_export(pruned, os.path.join(tmp, "slim.cfg"))
         thin.eval()
-        thin.precision = "fp16"
+        thin.precision = PRECISION
         results.append(bench_model(thin, (1,), "yolov2-voc slim60"))
+    if PRECISION == "fp8":      # the fp16 split-K figures of the same run, beside the fp8 ones
+        dense.precision = "fp16"
+        results.append(bench_model(dense, (1, 2, 4, 8), "yolov2-voc"))
 
-doc = {"calls": CALLS, "pairs": PAIRS, "passes": PASSES, "arch": L.lib().mcamd_arch().decode(),
+doc = {"calls": CALLS, "pairs": PAIRS, "passes": PASSES, "arch": L.lib().mcamd_arch().decode(), "precision": PRECISION,
+       "q8_mfma": int(os.environ.get("MCAMD_Q8_MFMA", 0)),
        "min_chunks": int(os.environ.get("MCAMD_SPLITK_MIN_CHUNKS", 8)), "cus": int(os.environ.get("MCAMD_SPLITK_CUS", 256)),
        "results": results}
 if "--json" in sys.argv:
