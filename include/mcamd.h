@@ -451,6 +451,52 @@ int mcamd_pack_q8_sparse24(const mcamd_conv_geom* g, const float* w_oihw, const 
 int mcamd_conv_fwd_q8_sparse24(const mcamd_conv_geom* g, const void* x8, const void* wq, const void* idx, const int32_t* wexp,
                                const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * 4-bit weight inference on the fp8 engine (an addition beyond the reference; conv_q8_w4.hip, Darknet.precision =
+ * "fp8-w4"): the fp8 block above -- same activations, q(), output formula and destinations -- with the weights
+ * held as 4-bit e2m1 codes and one shift per group of 32 input channels: 4.25 bits per weight.  Per filter f of
+ * w = weight * mask, with e_f as mcamd_pack_q8 computes it:
+ *   filter exponent  e4_f = e_f - 1 (0 for an all-zero filter); s = w * 2^e4_f: the filter's largest |s| lies in (112, 224];
+ *   groups           the 32 consecutive input channels [32 j, 32 j + 32) at one tap of one filter (cin % 64 == 0: every 64-k
+ *                    chunk of the packed order holds exactly two);
+ *   group shift      the smallest integer g in [-5, 6] with max |s| over the group <= 6 * 2^g ((m, x) = frexp(max): x - 3 if
+ *                    m <= 0.75 else x - 2, clamped); -5 for an all-zero group;
+ *   code             bit 3 = sign, bits 0-2 = index into {0, 0.5, 1, 1.5, 2, 3, 4, 6} of |s| / 2^g rounded to nearest, ties to
+ *                    the index with the even mantissa bit (2.5 -> 2, 3.5 -> 4, 5 -> 4, 0.25 -> 0); a zero magnitude has no sign
+ *                    bit (the packer writes no -0; the kernels read one as 0).  Groups below 0.25 * 2^-5 come out as zeros;
+ *   value            grid[code] * 2^g.  Every such value is an e4m3 number (one mantissa bit, 2^-6 <= |value| <= 384 <= 448), so
+ *                    its byte W8x = q(value) is exact, and
+ *   output           v = leaky(scale_f * 2^-(e4_f + 1) * S + shift_f), S = sum a8 * W8x: mcamd_conv_fwd_q8 on the bytes W8x
+ *                    with the exponents e4_f, bit for bit, in both MCAMD_Q8_MFMA forms (the kernel expands the codes to those
+ *                    bytes in registers and issues that kernel's MFMA sequence).
+ * ------------------------------------------------------------------------- */
+/* mcamd_conv_fwd_q8_ok's predicate. */
+int32_t mcamd_conv_fwd_q8_w4_ok(const mcamd_conv_geom* g);
+/* Sizes of the packed operands: out[0] = code bytes (Npad * ktot / 2; Npad = round_up(cout, 256), ktot = k*k * cin),
+ * out[1] = shift bytes (Npad * ktot / 32), out[2] = int32 exponents (Npad). */
+int mcamd_q8_w4_elems(const mcamd_conv_geom* g, int64_t out[3]);
+/* OIHW fp32 master (* mask, may be NULL) -> the 4-bit packing, everything computed on the device, no atomics:
+ *   wexp:   int32 [Npad], e4_f (pad rows 0);
+ *   gshift: bytes [ktot / 64][Npad][2]: gshift[(q * Npad + n) * 2 + j] = g + 5 of group j of chunk q of row n -- the positions
+ *           kpos in [64 q + 32 j, +32) of mcamd_pack_q8's order kpos(t, c) = (c / 64) * k*k*64 + t * 64 + c % 64; pad rows 0;
+ *   codes:  bytes [Npad][ktot / 2]; chunk q of row n is the 32 bytes [32 q, 32 q + 32), two 16-byte pieces h = 0, 1 (one lane's
+ *           operand each).  Piece h holds the chunk's positions p(h, t), t in [0, 32): p = 16 h + t for t < 16 (group 0),
+ *           32 + 16 h + (t - 16) otherwise (group 1).  Byte i of the piece, with d = i / 4, b = i % 4: the low nibble is the
+ *           code of t = 8 d + b, the high nibble the code of t = 8 d + 4 + b.  Pad rows: zero codes.
+ * Every row up to Npad is written. */
+int mcamd_pack_q8_w4(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* codes, void* gshift,
+                     int32_t* wexp, void* stream);
+/* codes + gshift -> wq: the e4m3 bytes W8x, [Npad][ktot] in exactly mcamd_pack_q8's layout (pad rows zero bytes):
+ * mcamd_conv_fwd_q8(.., wq, wexp = e4_f, ..) then computes what mcamd_conv_fwd_q8_w4 computes. */
+int mcamd_unpack_q8_w4(const mcamd_conv_geom* g, const void* codes, const void* gshift, void* wq, void* stream);
+/* mcamd_conv_fwd_q8 from that packing: epi->mode MCAMD_EPI_PAD_F16 only; dst_mode, y2, y_f8 / y2_f8 as there.  Both
+ * MCAMD_Q8_MFMA forms, both `pad` forms of x, any batch size. */
+int mcamd_conv_fwd_q8_w4(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* gshift, const int32_t* wexp,
+                         const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream);
+/* The kernel instance mcamd_conv_fwd_q8_w4 launches for this geometry (host logic only): out as mcamd_conv_fwd_q8_info's --
+ * the tile mcamd_conv_fwd_q8 takes for the same geometry (no instance needs scratch memory, none is left out). */
+int mcamd_conv_fwd_q8_w4_info(const mcamd_conv_geom* g, int32_t out[7]);
+
 /* dx = conv_transpose(dy, w) -- autograd's input gradient of the same call.
  * `dy` is padded NHWC fp16 [B][H+2][W+2][dy_ld] (zero halo); g->cin/cout keep their forward
  * meaning; the result has g->cin channels.  epi->mode 0 (fp16 [M][y_ld]) or 1 (fp32 NCHW). */

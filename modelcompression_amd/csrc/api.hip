@@ -1061,6 +1061,74 @@ extern "C" int mcamd_conv_fwd_q8_sparse24(const mcamd_conv_geom* g, const void* 
     return mcamd_conv_q8_sparse_launch(a, idx, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------
+// 4-bit weight inference on the fp8 engine (conv_q8_w4.hip; Darknet.precision = "fp8-w4")
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_q8_w4_ok(const mcamd_conv_geom* g) {
+    return mcamd_conv_fwd_q8_ok(g);                // (cin % 64 == 0: two whole groups of 32 per chunk)
+}
+
+extern "C" int mcamd_q8_w4_elems(const mcamd_conv_geom* g, int64_t out[3]) {
+    MCAMD_REQUIRE(g && out, "q8_w4_elems: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_w4_ok(g), "q8_w4_elems: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_ok)");
+    const long long npad = round_up_int(g->cout, 256), ktot = (long long)ntaps_of(g) * g->cin;
+    out[0] = npad * ktot / 2;      // code bytes
+    out[1] = npad * ktot / 32;     // shift bytes
+    out[2] = npad;                 // int32 exponents
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_pack_q8_w4(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* codes, void* gshift,
+                                int32_t* wexp, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "pack_q8_w4: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_pack_q8_w4(&g_, w_oihw, mask_oihw, codes, gshift, wexp, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_w4_ok(g), "pack_q8_w4: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_ok)");
+    MCAMD_REQUIRE(w_oihw && codes && gshift && wexp, "pack_q8_w4: null pointer");
+    return mcamd_pack_q8_w4_launch(w_oihw, mask_oihw, codes, gshift, wexp, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
+}
+
+extern "C" int mcamd_unpack_q8_w4(const mcamd_conv_geom* g, const void* codes, const void* gshift, void* wq, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "unpack_q8_w4: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_unpack_q8_w4(&g_, codes, gshift, wq, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_w4_ok(g), "unpack_q8_w4: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_ok)");
+    MCAMD_REQUIRE(codes && gshift && wq, "unpack_q8_w4: null pointer");
+    return mcamd_unpack_q8_w4_launch(codes, gshift, wq, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_q8_w4(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* gshift,
+                                    const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8,
+                                    void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_w4: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_q8_w4(&g_, x8, codes, gshift, wexp, &e_, y_f8, y2_f8, s); });
+    }
+    if (check_geom(g, "conv_fwd_q8_w4")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_w4_ok(g), "conv_fwd_q8_w4: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_ok)");
+    MCAMD_REQUIRE(x8 && codes && gshift && wexp, "conv_fwd_q8_w4: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8_w4: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x8, codes, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_w4", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    return mcamd_conv_q8_w4_launch(a, gshift, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
+}
+
+// mcamd_q8_w4_choice()'s answer: what mcamd_conv_fwd_q8_w4 launches for this geometry (host logic only)
+extern "C" int mcamd_conv_fwd_q8_w4_info(const mcamd_conv_geom* g, int32_t out[7]) {
+    MCAMD_REQUIRE(g && out, "conv_fwd_q8_w4_info: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_w4_ok(g), "conv_fwd_q8_w4_info: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_ok)");
+    const Q8Choice c = mcamd_q8_w4_choice((long long)g->B * g->H * g->W, g->cout);
+    out[0] = c.bmw, out[1] = c.bnp, out[2] = c.f8mfma, out[3] = c.stages, out[4] = c.mtiles, out[5] = c.ntiles, out[6] = c.grid;
+    return MCAMD_OK;
+}
+
 // mcamd_q8_choice()'s answer: what mcamd_conv_fwd_q8 (forms 0, 1), mcamd_conv_fwd_q8_slim (form 2) and
 // mcamd_conv_fwd_q8_sparse24 (form 3) launch for this geometry (host logic only)
 extern "C" int mcamd_conv_fwd_q8_info(const mcamd_conv_geom* g, int32_t form, int32_t out[7]) {

@@ -1,0 +1,381 @@
+// 4-bit weight inference on the fp8 engine (an addition beyond the reference: Darknet.precision = "fp8-w4"):
+// conv_q8.hip's block with the weight operand held as e2m1 codes + one shift per group of 32 input channels, staged as
+// nibbles and expanded to e4m3 bytes IN REGISTERS in front of the MFMAs.
+//
+//   S[n][m] = sum_{tap, c} W8x[n][kpos(tap, c)] * X8[pixel(m) + tap][c]       (fp32 accumulation of exact products)
+//   v       = leaky(scale[n] * 2^-(e4[n] + 1) * S + shift[n])
+//
+// The format, per filter f of w = weight * mask (mcamd.h states it in full): e4_f = e_f - 1 with e_f mcamd_pack_q8's exponent
+// (0 for an all-zero filter), s = w 2^e4_f; per group -- the 32 consecutive input channels [32 j, 32 j + 32) at one tap -- the
+// smallest shift g in [-5, 6] with max |s| <= 6 * 2^g; a code = sign + |s| / 2^g rounded to nearest (ties to the even
+// mantissa bit) onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}.  Every value grid[code] * 2^g is an e4m3 number (one mantissa bit, 2^-6
+// <= |value| <= 384), so W8x, the byte of that value, is exact, and this kernel is conv_q8_kernel on a restricted set of weight
+// bytes: the decoded fragment of lane (r, h) holds the bytes [16 h, 16 h + 16) and [32 + 16 h, +16) of row r's chunk, as
+// conv_q8_kernel's does, and the MFMA sequence per accumulator is the same in both MFMA forms (MCAMD_Q8_MFMA).
+//
+// One K chunk = 64 k: per weight row 32 code bytes (half of conv_q8.hip's A traffic) + 2 shift bytes, per pixel one 64-byte
+// row, all staged by global_load_lds_dwordx4 with conv_q8_sparse.hip's ring (32-byte weight rows read 16 bytes per lane,
+// contiguously over the wave: no swizzle; the shift bytes of a tile's chunk are one wave-wide DMA, lanes repeating).
+//
+// Decode (w4_decode): code dword d of a lane's 16 bytes holds the lane's k 8 d .. 8 d + 7 -- byte b: low nibble k 8 d + b,
+// high nibble k 8 d + 4 + b -- so `x & 0x0f0f0f0f` and `(x >> 4) & 0x0f0f0f0f` are the four codes of two output dwords.  The
+// magnitude byte comes from an 8-entry table by v_perm_b32 (entry c: 0 for c = 0, else the e4m3 magnitude of grid[c] 2^g --
+// the group's table is the g = -5 one, {0x00, 0x08, 0x10, 0x14, 0x18, 0x1c, 0x20, 0x24}, plus (g + 5) << 3 on its non-zero
+// entries: two additions per group and lane), the sign bit is moved up from bit 3.  A lane's first 16 k lie in the chunk's
+// first group, its second 16 in the second.
+#include "kernels.h"
+#include "conv_epi.h"
+#include "q8_exp.h"
+
+// e4m3 magnitudes of the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6} * 2^-5: entries 0-3 (v_perm's second source), 4-7 (its first)
+constexpr unsigned W4_TLO = 0x14100800u, W4_THI = 0x24201c18u;
+
+struct W4Table {
+    unsigned lo, hi;
+};
+
+// the table of a group with shift byte G = g + 5: every non-zero entry's exponent field raised by G (no carry: <= 0x7c)
+__device__ __forceinline__ W4Table w4_table(unsigned G) {
+    W4Table t;
+    t.lo = W4_TLO + (G << 3) * 0x01010100u;
+    t.hi = W4_THI + (G << 3) * 0x01010101u;
+    return t;
+}
+
+// four codes, one per byte (bits 0-2 magnitude, bit 3 sign) -> their four e4m3 bytes
+__device__ __forceinline__ int w4_bytes4(unsigned c4, const W4Table& t) {
+    const unsigned mag = __builtin_amdgcn_perm(t.hi, t.lo, c4 & 0x07070707u);
+    return (int)(((c4 & 0x08080808u) << 4) | mag);
+}
+
+// a lane's 16 code bytes + the two shift bytes of its row's chunk -> its 32 e4m3 weight bytes (conv_q8_kernel's fragment)
+__device__ __forceinline__ i32x8_t w4_decode(i32x4_t codes, unsigned shifts) {
+    const W4Table t0 = w4_table(shifts & 0xffu), t1 = w4_table((shifts >> 8) & 0xffu);
+    i32x8_t o;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const unsigned x = (unsigned)codes[d];
+        o[2 * d] = w4_bytes4(x & 0x0f0f0f0fu, d < 2 ? t0 : t1);
+        o[2 * d + 1] = w4_bytes4((x >> 4) & 0x0f0f0f0fu, d < 2 ? t0 : t1);
+    }
+    return o;
+}
+
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
+void conv_q8_w4_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad, const int* __restrict__ wexp, int y_f8, int y2_f8) {
+    constexpr int WAVES_N = BNP / WN;
+    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
+    constexpr int BK = 64, CPRA = 2, CPRB = 4;     // 16-byte pieces per code row / per pixel row
+    constexpr int A_SLOTS = BMW * CPRA, B_SLOTS = BNP * CPRB;
+    constexpr int A_IT = (A_SLOTS + NT - 1) / NT, B_IT = B_SLOTS / NT;
+    constexpr int G_BYTES = 1024;                  // shift region: one wave-wide DMA (BMW * 2 bytes used)
+    constexpr int G_PIECES = BMW * 2 / 16;         // 16-byte pieces of a tile's shift bytes
+    constexpr int TM = WM / 32, TN = WN / 32;
+    constexpr int STAGE_BYTES = (A_SLOTS + B_SLOTS) * 16 + G_BYTES;
+    constexpr int DMIN = A_SLOTS / NT + B_IT;      // DMA instructions every wave issues per stage
+    static_assert(A_SLOTS % 64 == 0 && B_SLOTS % NT == 0, "whole waves per DMA instruction");
+    static_assert(BMW * 2 <= G_BYTES && G_PIECES >= 1 && G_PIECES <= 64, "shift region");
+    static_assert(NSTAGE >= 2 && NSTAGE <= 3, "LDS ring depth");
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    int nt, mt;
+    if (!xcd_tile(a.num_ntiles, a.num_mtiles, nt, mt)) return;
+    const int nchunks = a.ktot / BK;
+    const int krow = a.ktot / 2;                   // code row length (bytes)
+    const char* xg = (const char*)a.x;             // byte operands: every stride of `a` counts bytes
+    const char* wg = (const char*)a.w;
+
+    long long wbase[A_IT];
+#pragma unroll
+    for (int it = 0; it < A_IT; ++it) {
+        const int slot = (it * NT + tid) % A_SLOTS;              // (a wave past A_SLOTS issues nothing: stage())
+        wbase[it] = (long long)(nt * BMW + slot / CPRA) * krow + (slot % CPRA) * 16;   // rows < Npad = round_up(N, 256)
+    }
+    long long xbase[B_IT];
+#pragma unroll
+    for (int it = 0; it < B_IT; ++it) {
+        const int slot = it * NT + tid;
+        const int row = slot / CPRB, phys = slot % CPRB;
+        xbase[it] = tile_x_base(a, a.dst_mode != 0, mt * BNP + row) + (phys ^ swz<CPRB>(row)) * 16;
+    }
+    // shift DMA (wave 0): lane l fetches 16 bytes = the shift pairs of 8 rows of the tile (lanes past the tile repeat)
+    const long long gbase = (long long)nt * BMW * 2 + (lane % G_PIECES) * 16;
+
+    f32x16_t acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    auto stage = [&](int q, int buf) {
+        const int cb = q / a.ntaps, tap = q - cb * a.ntaps;      // one chunk per tap of a 64-channel block
+        const int koff = a.tap_off[tap] + cb * BK;
+        char* sa = smem + buf * STAGE_BYTES;
+        char* sg = sa + A_SLOTS * 16;
+        char* sb = sg + G_BYTES;
+#pragma unroll
+        for (int it = 0; it < A_IT; ++it) {
+            const int wslot = it * NT + wave * 64;
+            if (wslot < A_SLOTS) glds16(wg + wbase[it] + (long long)q * (BK / 2), sa + wslot * 16);
+        }
+        if (wave == 0) glds16(gshift + gbase + (long long)q * npad * 2, sg);
+#pragma unroll
+        for (int it = 0; it < B_IT; ++it) glds16(xg + xbase[it] + koff, sb + (it * NT + wave * 64) * 16);
+    };
+
+    const int lrow = lane & 31, hh = lane >> 5;
+    const int SC = 127 * 0x01010101;               // e8m0 1.0 in all four scale bytes
+
+#pragma unroll
+    for (int p = 0; p < NSTAGE - 1; ++p)
+        if (p < nchunks) stage(p, p);
+    int sidx = 0;
+    for (int q = 0; q < nchunks; ++q) {
+        int issued = q + NSTAGE - 1;
+        if (issued > nchunks) issued = nchunks;
+        const int inflight = issued - q - 1;
+        if (NSTAGE == 2 || inflight == 0) wait_vmcnt<0>();
+        else wait_vmcnt<DMIN>();                   // (a wave that issues more per stage waits for more: in-order completion)
+        __builtin_amdgcn_s_barrier();              // chunk q landed for every wave; every wave is done with chunk q-1
+        if (q + NSTAGE - 1 < nchunks) {
+            int ns = sidx + NSTAGE - 1;
+            if (ns >= NSTAGE) ns -= NSTAGE;
+            stage(q + NSTAGE - 1, ns);
+        }
+        const char* sa = smem + sidx * STAGE_BYTES;
+        const char* sg = sa + A_SLOTS * 16;
+        const char* sb = sg + G_BYTES;
+        sidx = sidx + 1 == NSTAGE ? 0 : sidx + 1;
+        i32x8_t af[TM], bf[TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int row = wm * WM + i * 32 + lrow;
+            const i32x4_t codes = *(const i32x4_t*)(sa + (row * CPRA + hh) * 16);
+            af[i] = w4_decode(codes, *(const unsigned short*)(sg + row * 2));
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int row = wn * WN + j * 32 + lrow;
+            const i32x4_t lo = *(const i32x4_t*)(sb + (row * CPRB + (hh ^ swz<CPRB>(row))) * 16);
+            const i32x4_t hi = *(const i32x4_t*)(sb + (row * CPRB + ((2 + hh) ^ swz<CPRB>(row))) * 16);
+            bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+        // conv_q8_block's MFMA sequence on the decoded bytes.  Unlike there, the A operand (and possibly the scale register) was
+        // just written by VALU instructions, and hipcc pads no hazard in front of inline assembly: every string opens with
+        // `s_nop 1`, the two wait states a VALU write of an MFMA source operand needs on gfx950.
+        if constexpr (F8MFMA) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    asm volatile("s_nop 1\n\tv_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"
+                                 : "+v"(acc[i][j])
+                                 : "v"(af[i]), "v"(bf[j]), "v"(SC), "v"(SC));
+        } else {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                h8_t a16[TM], b16[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) a16[i] = q8_to_f16(af[i][2 * s4], af[i][2 * s4 + 1]);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) b16[j] = q8_to_f16(bf[j][2 * s4], bf[j][2 * s4 + 1]);
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a16[i], b16[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    }
+    if constexpr (F8MFMA) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // last (assembly) MFMA -> VALU reads of the accumulators
+
+    // ------------------------------- epilogue (conv_q8_kernel's, e4_f in place of e_f) -------------------------------
+    __syncthreads();                               // every wave is done with the stage buffers
+    const bool has2 = a.y2 != nullptr;
+    const bool need_b = y_f8 || (has2 && y2_f8), need_h = !y_f8 || (has2 && !y2_f8);
+    constexpr int PB = BMW + 8;                    // tile row pitch: a wave's 32 pixels on 32 LDS banks
+    char* bt = smem;                               // [BNP][PB] e4m3 tile
+    half_t* ht = (half_t*)(smem + (need_b ? BNP * PB : 0));   // [BNP][PB] fp16 tile
+    const float* scale = a.scale;
+    const bool sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale, wexp](int n) { return ldexpf(scale ? scale[n] : 1.f, -(wexp[n] + 1)); },
+                                                    need_b, need_h, bt, ht, nt, wm, wn, lane);
+    __syncthreads();
+    store_pad_tile<BNP, BMW, PB, NT>(a, bt, ht, y_f8 != 0, y2_f8 != 0, mt, nt, tid);
+    if (sat && a.overflow) atomicOr(a.overflow, 1);
+}
+
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+static int conv_q8_w4_launch_t(IgemmArgs& a, const Q8Choice& c, const char* gshift, int npad, const int* wexp, int y_f8, int y2_f8,
+                               hipStream_t st) {
+    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
+    constexpr int RING = NSTAGE * (BMW * 32 + BNP * 64 + 1024);
+    constexpr int PB = BMW + 8;                    // tile row pitch (conv_q8_w4_kernel)
+    constexpr int TILES = BNP * PB * 3;            // a byte and an fp16 tile (destinations of both formats)
+    constexpr int LDS = RING > TILES ? RING : TILES;
+    const bool has2 = a.y2 != nullptr;
+    const bool mixed = (y_f8 || (has2 && y2_f8)) && (!y_f8 || (has2 && !y2_f8));
+    const int lds = mixed ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);
+    auto kern = conv_q8_w4_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
+    MCAMD_LDS_OPT_IN(kern, LDS);
+    a.num_mtiles = c.mtiles;
+    a.num_ntiles = c.ntiles;
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), lds, st, a, gshift, npad, wexp, y_f8, y2_f8);
+    MCAMD_LAUNCH_CHECK("conv_fwd_q8_w4");
+    return MCAMD_OK;
+}
+
+// The tile is mcamd_q8_choice's for the fp8 block (conv_q8.hip: 256 filters x 128 pixels from 256 filters with the fp8 MFMA,
+// 128 x 128 from 128, 64 x 128 below; 3 stages): every one of the five instances compiles without scratch memory
+// (profiles/q8_w4_resources.txt), so none is left out.
+Q8Choice mcamd_q8_w4_choice(long long M, int N) { return mcamd_q8_choice(M, N, MCAMD_Q8_FORM_INFER); }
+
+int mcamd_conv_q8_w4_launch(IgemmArgs& a, const void* gshift, const void* wexp, int y_f8, int y2_f8, hipStream_t st) {
+    const int* we = (const int*)wexp;
+    const char* gs = (const char*)gshift;
+    const int npad = round_up_int(a.N, 256);
+    const Q8Choice c = mcamd_q8_w4_choice(a.M, a.N);
+    if (c.bnp == 128 && c.stages == 3) {
+        if (c.f8mfma && c.bmw == 256) return conv_q8_w4_launch_t<256, 128, 64, 64, 3, true>(a, c, gs, npad, we, y_f8, y2_f8, st);
+        if (c.f8mfma && c.bmw == 128) return conv_q8_w4_launch_t<128, 128, 64, 64, 3, true>(a, c, gs, npad, we, y_f8, y2_f8, st);
+        if (c.f8mfma && c.bmw == 64) return conv_q8_w4_launch_t<64, 128, 32, 64, 3, true>(a, c, gs, npad, we, y_f8, y2_f8, st);
+        if (!c.f8mfma && c.bmw == 128) return conv_q8_w4_launch_t<128, 128, 64, 64, 3, false>(a, c, gs, npad, we, y_f8, y2_f8, st);
+        if (!c.f8mfma && c.bmw == 64) return conv_q8_w4_launch_t<64, 128, 32, 64, 3, false>(a, c, gs, npad, we, y_f8, y2_f8, st);
+    }
+    mcamd_set_error("conv_fwd_q8_w4: no kernel instance %d x %d, fp8 MFMA %d, %d stages", c.bmw, c.bnp, c.f8mfma, c.stages);
+    return MCAMD_EINVAL;
+}
+
+// ---------------------------------------------------------------------------------------
+// packer: fp32 OIHW master * mask -> codes [Npad][ktot / 2] + shift bytes [ktot / 64][Npad][2] + exponents [Npad]
+// ---------------------------------------------------------------------------------------
+// the lane-local order of a chunk's k: piece h (16 code bytes), t in [0, 32) -> position in the 64-k chunk
+__device__ __forceinline__ int w4_kk(int h, int t) { return t < 16 ? 16 * h + t : 32 + 16 * h + (t - 16); }
+
+// Smallest g in [-5, 6] with amax <= 6 * 2^g (-5 for amax == 0), integer steps as q8_filter_exponent: (m, x) = frexp(amax),
+// 6 * 2^g = 0.75 * 2^(g + 3), so g = x - 3 if m <= 0.75 else x - 2.
+__device__ __forceinline__ int w4_group_shift(float amax) {
+    if (!(amax > 0.f)) return -5;
+    int x;
+    const float m = frexpf(amax, &x);
+    const int g = m <= 0.75f ? x - 3 : x - 2;
+    return g < -5 ? -5 : g > 6 ? 6 : g;
+}
+
+// s (the scaled weight) -> its 4-bit code under shift g: round to nearest onto the e2m1 grid, ties to the even mantissa bit
+// (rintf on 2 v / v / v / 2: an even integer there is a code with mantissa bit 0); above 6 saturates; a zero magnitude
+// carries no sign bit.
+__device__ __forceinline__ unsigned w4_code(float s, int g) {
+    const float v = fminf(ldexpf(fabsf(s), -g), 6.f);
+    unsigned c;
+    if (v < 2.f) c = (unsigned)rintf(2.f * v);               // 0, 0.5, 1, 1.5, (2)
+    else if (v < 4.f) c = (unsigned)rintf(v) + 2u;           // 2, 3, (4)
+    else c = (unsigned)rintf(0.5f * v) + 4u;                 // 4, 6
+    return (c != 0u && s < 0.f) ? (c | 8u) : c;
+}
+
+// One workgroup per row n < Npad.  The exponent is pack_q8_kernel's minus one (0 for an all-zero filter).  Then the row is
+// walked four chunks at a time, every weight read once: thread t stages the scaled w * mask of position t of the 256 (packed
+// order [cb][tap][64]) in LDS; eight threads take the maxima and shifts of the eight groups; 128 threads write one code byte
+// (two weights) each.  Pad rows: zero codes, shift byte 0, exponent 0.
+__global__ __launch_bounds__(256) void pack_q8_w4_kernel(const float* __restrict__ w, const float* __restrict__ mask,
+                                                         char* __restrict__ codes, char* __restrict__ gshift,
+                                                         int* __restrict__ wexp, int cout, int cin, int ntaps, int npad) {
+    __shared__ float red[256];
+    __shared__ float sv[256];                                    // scaled weights of four chunks
+    __shared__ int sg[8];                                        // their group shifts
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int ktot = cin * ntaps, nchunks = ktot / 64;
+    float amax = 0.f;
+    if (n < cout)
+        for (int o = tid; o < ktot; o += 256) {
+            const long long s = (long long)n * ktot + o;
+            amax = fmaxf(amax, fabsf(w[s] * (mask ? mask[s] : 1.f)));
+        }
+    red[tid] = amax;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    amax = red[0];
+    const int e4 = amax > 0.f ? q8_filter_exponent(amax) - 1 : 0;
+    if (tid == 0) wexp[n] = e4;
+    for (int q0 = 0; q0 < nchunks; q0 += 4) {                    // (uniform over the workgroup: the barriers below)
+        {
+            const int q = q0 + tid / 64, kk = tid % 64;
+            float v = 0.f;
+            if (n < cout && q < nchunks) {
+                const int cb = q / ntaps, tap = q - cb * ntaps;
+                const long long s = ((long long)n * cin + cb * 64 + kk) * ntaps + tap;
+                v = ldexpf(w[s] * (mask ? mask[s] : 1.f), e4);   // exact: a power of two
+            }
+            sv[tid] = v;
+        }
+        __syncthreads();
+        if (tid < 8) {                                           // group tid % 2 of chunk q0 + tid / 2
+            float m = 0.f;
+            for (int k = 0; k < 32; ++k) m = fmaxf(m, fabsf(sv[tid * 32 + k]));
+            const int g = w4_group_shift(m);
+            sg[tid] = g;
+            const int q = q0 + tid / 2;
+            if (q < nchunks) gshift[((long long)q * npad + n) * 2 + (tid & 1)] = (char)(n < cout ? g + 5 : 0);
+        }
+        __syncthreads();
+        if (tid < 128) {                                         // code byte i of chunk q0 + tid / 32
+            const int c = tid / 32, i = tid % 32, q = q0 + c;
+            const int h = i / 16, d = (i % 16) / 4, b = i % 4;
+            const int g = sg[2 * c + (d >= 2)];
+            const unsigned lo = w4_code(sv[c * 64 + w4_kk(h, 8 * d + b)], g), hi = w4_code(sv[c * 64 + w4_kk(h, 8 * d + 4 + b)], g);
+            if (q < nchunks) codes[(long long)n * (ktot / 2) + (long long)q * 32 + i] = (char)(lo | hi << 4);
+        }
+        __syncthreads();                                         // before the next four chunks overwrite sv / sg
+    }
+}
+
+int mcamd_pack_q8_w4_launch(const float* w, const float* mask, void* codes, void* gshift, void* wexp, int cout, int cin, int ntaps,
+                            hipStream_t st) {
+    const int npad = round_up_int(cout, 256);
+    hipLaunchKernelGGL(pack_q8_w4_kernel, dim3(npad), dim3(256), 0, st, w, mask, (char*)codes, (char*)gshift, (int*)wexp, cout, cin,
+                       ntaps, npad);
+    MCAMD_LAUNCH_CHECK("pack_q8_w4");
+    return MCAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// expander: codes + shift bytes -> the e4m3 bytes [Npad][ktot] in mcamd_pack_q8's layout (the forward's own decode)
+// ---------------------------------------------------------------------------------------
+// One thread per (row, chunk, piece): 16 code bytes -> the two 16-byte runs [16 h, +16) and [32 + 16 h, +16) of the chunk.
+__global__ __launch_bounds__(256) void unpack_q8_w4_kernel(const char* __restrict__ codes, const char* __restrict__ gshift,
+                                                           char* __restrict__ wq, long long total, int ktot, int npad) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int upr = ktot / 32;                                   // pieces per row
+    const long long n = t / upr;
+    const int u = (int)(t - n * upr), q = u >> 1, h = u & 1;
+    const i32x4_t c = *(const i32x4_t*)(codes + n * (ktot / 2) + 16 * u);
+    const unsigned char* gp = (const unsigned char*)gshift + ((long long)q * npad + n) * 2;
+    const i32x8_t o = w4_decode(c, (unsigned)gp[0] | (unsigned)gp[1] << 8);
+    i32x4_t lo, hi;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) lo[i] = o[i], hi[i] = o[4 + i];
+    char* row = wq + n * ktot + (long long)q * 64;
+    *(i32x4_t*)(row + 16 * h) = lo;
+    *(i32x4_t*)(row + 32 + 16 * h) = hi;
+}
+
+int mcamd_unpack_q8_w4_launch(const void* codes, const void* gshift, void* wq, int cout, int cin, int ntaps, hipStream_t st) {
+    const int npad = round_up_int(cout, 256), ktot = cin * ntaps;
+    const long long total = (long long)npad * (ktot / 32);
+    hipLaunchKernelGGL(unpack_q8_w4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const char*)codes,
+                       (const char*)gshift, (char*)wq, total, ktot, npad);
+    MCAMD_LAUNCH_CHECK("unpack_q8_w4");
+    return MCAMD_OK;
+}

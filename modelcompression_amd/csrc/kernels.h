@@ -171,6 +171,13 @@ int mcamd_q8_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* 
 int mcamd_conv_q8_sparse_launch(IgemmArgs& a, const void* idx, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
 int mcamd_pack_q8_sparse24_launch(const float* w, const float* mask, void* wq, void* idx, void* wexp, int cout, int cin,
                                   int ntaps, hipStream_t st);
+// conv_q8_w4.hip: conv_q8.hip's block on e2m1 codes + group shifts expanded to e4m3 bytes in registers (a.w = the codes);
+// its choice of instance (the fp8 block's), packer, expander to mcamd_pack_q8's bytes
+Q8Choice mcamd_q8_w4_choice(long long M, int N);
+int mcamd_conv_q8_w4_launch(IgemmArgs& a, const void* gshift, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
+int mcamd_pack_q8_w4_launch(const float* w, const float* mask, void* codes, void* gshift, void* wexp, int cout, int cin, int ntaps,
+                            hipStream_t st);
+int mcamd_unpack_q8_w4_launch(const void* codes, const void* gshift, void* wq, int cout, int cin, int ntaps, hipStream_t st);
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps);
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);

@@ -63,6 +63,7 @@ _LAYER_FIELDS = dict(
     # fp8: launch geometry on the byte buffer, byte destinations, private input copy, packed operands; "fp8-qat" training:
     # the fp32 raw output + statistics that stand in for the fp16 ones, and the values the weight bytes stand for
     geom_q8=None, q8_y=False, q8_y2=False, xq=None, _xq=None, _xq_key=None, wq=None, wqs=None, widx8=None, wexp=None,
+    w4c=None, w4g=None, wexp4=None,
     y_f16=None, stats_f16=None, y_f32=None, stats_q8=None, w_q=None)
 
 
@@ -80,7 +81,7 @@ class _Layer:
     sp_on = property(lambda self: self.form == "sparse24")
     bs_on = property(lambda self: self.form == "bsparse")
     sk_on = property(lambda self: self.form == "splitk")
-    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk"))
+    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4"))
     q8s_on = property(lambda self: self.form == "q8_sparse24")
     q8_slim = property(lambda self: self.form == "q8_slim")
 
@@ -289,8 +290,16 @@ class _Q8SplitK(_Q8):
         return args, dict(kw, slices=lay.sk_slices, workspace=eng._splitk_ws)
 
 
+class _Q8W4(_Q8):
+    """An fp8 block on 4-bit weights ("fp8-w4", csrc/conv_q8_w4.hip): e2m1 nibble codes, one shift byte per group
+    of 32 input channels and one exponent per filter -- 4.25 bits per weight, expanded to e4m3 bytes in the kernel's registers.
+    No weight bytes (`wq`) are held."""
+    fwd, elems, packer = "conv_fwd_q8_w4", "q8_w4_elems", "pack_q8_w4"
+    bufs = (("w4c", torch.uint8), ("w4g", torch.uint8), ("wexp4", torch.int32))
+
+
 _FORMS = {"dense": _Dense(), "splitk": _SplitK(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "q8": _Q8(),
-          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK()}
+          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4()}
 
 
 def _probe_side_stream(device, tries=8):
@@ -358,18 +367,22 @@ class Engine:
         "fp8-qat" -- fp8 quantisation-aware training: in training mode every block of `fp8_layers` runs its
         forward in the "fp8" arithmetic on batch statistics (mcamd_conv_fwd_q8 with the fp32 raw epilogue, byte + dequantised
         fp16 destinations) and a straight-through backward on the fp16 kernels; every other block trains as in "fp16".  An
-        inference-mode forward is the "fp8" engine's, bit for bit."""
-        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat"):
-            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk' or 'fp8-qat' (got %r)"
-                             % (precision,))
+        inference-mode forward is the "fp8" engine's, bit for bit.
+        "fp8-w4" -- the "fp8" engine on 4-bit weights, inference only: every block "fp8" runs in form "q8" holds
+        its weights as e2m1 codes with a shift per group of 32 input channels (csrc/conv_q8_w4.hip, `fp8_w4_layers`) and
+        computes what the fp8 block computes on the e4m3 bytes those codes stand for; the slim blocks and every other block
+        run what "fp8" runs."""
+        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4"):
+            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk', 'fp8-qat' or 'fp8-w4' "
+                             "(got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat")
+        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_choose_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat")
+        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4")
         self.qat = precision == "fp8-qat"      # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
         # "fp8-2:4": the subset of fp8_layers whose masks conform to 2:4 and that run mcamd_conv_fwd_q8_sparse24
@@ -379,6 +392,9 @@ class Engine:
         # mcamd_conv_fwd_q8_splitk (they share `_splitk_ws` below)
         self.q8_splitk = precision == "fp8-splitk"
         self.fp8_splitk_layers = []
+        # "fp8-w4": the subset of fp8_layers that run mcamd_conv_fwd_q8_w4 on 4-bit weights (every block of form "q8")
+        self.q8_w4 = precision == "fp8-w4"
+        self.fp8_w4_layers = []
         self.qbufs = {}
         self._qld = {}                         # buffer id -> bytes per pixel of its byte buffer (_choose_q8)
         self.grad_scale = float(grad_scale)
@@ -1001,7 +1017,8 @@ class Engine:
           1. (pack) the block-sparse policy has read the masked weights; the blocks it chose are exempt from
           2. filter compaction and folding, planned again when the masks or that choice changed;
           3. then fp8 (every eligible block of an fp8 engine; under "fp8-splitk" behind it: every block of form "q8" -- not the
-             slim ones -- whose launch the split-K policy gives two slices or more, mcamd_conv_fwd_q8_splitk_info), 2:4
+             slim ones -- whose launch the split-K policy gives two slices or more, mcamd_conv_fwd_q8_splitk_info; under
+             "fp8-w4" every block of form "q8" takes the 4-bit form "q8_w4"), 2:4
              (sparse = "2:4": every eligible block whose mask conforms and whose geometry mcamd_conv_fwd_sparse24_ok accepts)
              or block-sparse (sparse = "block": the chosen blocks that
              are still eligible -- one whose producer was compacted after all, so that its input channels are permuted, stays
@@ -1038,6 +1055,10 @@ class Engine:
                     info = ops.conv_fwd_q8_splitk_info(lay.geom_q8, lay.mode)
                     if info.slices >= 2:
                         lay.form, lay.sk_slices = "q8_splitk", info.slices
+            if self.q8_w4:               # (the slim blocks keep their form, as under "fp8-splitk")
+                for lay in self.layers:
+                    if lay.form == "q8" and ops.conv_fwd_q8_w4_ok(lay.geom_q8):
+                        lay.form = "q8_w4"
         elif sparse == "2:4":
             for lay in self._conforming([lay for lay in self.layers
                                          if self._eligible(lay) and lay.conv.mask_flag and lay.cin % 4 == 0
@@ -1063,8 +1084,8 @@ class Engine:
             _FORMS[name].alloc(self, lays)
         nums = lambda *names: [lay.li + 1 for lay in self.layers if lay.form in names]
         self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
-        self.fp8_layers, self.fp8_sparse_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk"), nums("q8_sparse24")
-        self.fp8_splitk_layers = nums("q8_splitk")
+        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4")
+        self.fp8_sparse_layers, self.fp8_splitk_layers, self.fp8_w4_layers = nums("q8_sparse24"), nums("q8_splitk"), nums("q8_w4")
         self._form_key = key
 
     def _splitk_form(self, lay):

@@ -308,6 +308,9 @@ class Darknet(nn.Module):
         # engine.Engine.fp8_layers run their forward in the "fp8" arithmetic on batch statistics and a straight-through backward
         # on the fp16 kernels, every other block trains as in "fp16"; in eval mode it is the "fp8" engine, bit for bit
         # (DESIGN.md 3l).  The fine-tuning step between pruning / retraining and deployment under "fp8" or "fp8-2:4".
+        # "fp8-w4" (eval only, an opt-in): the "fp8" engine with the weights of every dense fp8 block held as 4-bit e2m1 codes
+        # + one shift per group of 32 input channels, 4.25 bits per weight resident, expanded to e4m3 bytes in the kernel's
+        # registers (engine.Engine.fp8_w4_layers, csrc/conv_q8_w4.hip); `sparse` and `splitk` stay off with it.
         self.precision = os.environ.get("MCAMD_PRECISION", "auto")
         # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA

@@ -1328,6 +1328,70 @@ def conv_fwd_q8_sparse24(g, x8, wq, idx, wexp, y, y_ld, y_choff=0, scale=None, s
                                              int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q8_sparse24")
 
 
+# ----------------------------------------------------------------------------- 4-bit weights on the fp8 engine
+def conv_fwd_q8_w4_ok(g):
+    """Does mcamd_conv_fwd_q8_w4 accept this geometry?  (mcamd_conv_fwd_q8_ok's predicate; needs no device.)"""
+    return bool(L.lib().mcamd_conv_fwd_q8_w4_ok(C.byref(g)))
+
+
+def q8_w4_elems(g):
+    """(code bytes, shift bytes, int32 exponents) of the 4-bit packing: 4.25 bits per weight."""
+    out = (C.c_int64 * 3)()
+    check(L.lib().mcamd_q8_w4_elems(C.byref(g), out), "mcamd_q8_w4_elems")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def pack_q8_w4(g, w, mask=None, out_codes=None, out_shift=None, out_exp=None):
+    """fp32 OIHW master (* mask) -> (e2m1 nibble codes, one shift byte per group of 32 input channels, int32 exponent per
+    filter) of the 4-bit forward (mcamd_pack_q8_w4; the layout is stated in include/mcamd.h)."""
+    _need_cuda(w, mask)
+    assert w.dtype == torch.float32 and w.is_contiguous()
+    nc, ng, ne = q8_w4_elems(g)
+    if out_codes is None:
+        out_codes = torch.empty(nc, dtype=torch.uint8, device=w.device)
+    if out_shift is None:
+        out_shift = torch.empty(ng, dtype=torch.uint8, device=w.device)
+    if out_exp is None:
+        out_exp = torch.empty(ne, dtype=torch.int32, device=w.device)
+    if out_codes.numel() < nc or out_shift.numel() < ng or out_exp.numel() < ne:
+        raise L.McamdError("pack_q8_w4: destination too small")
+    check(L.lib().mcamd_pack_q8_w4(C.byref(g), ptr(w), ptr(mask), ptr(out_codes), ptr(out_shift), ptr(out_exp), stream_ptr()),
+          "mcamd_pack_q8_w4")
+    return out_codes, out_shift, out_exp
+
+
+def unpack_q8_w4(g, codes, gshift, out_w=None):
+    """The e4m3 bytes the 4-bit packing stands for, in pack_q8's layout (mcamd_unpack_q8_w4): conv_fwd_q8 on them with
+    pack_q8_w4's exponents computes what conv_fwd_q8_w4 computes."""
+    _need_cuda(codes, gshift)
+    nw = q8_elems(g)[0]
+    if out_w is None:
+        out_w = torch.empty(nw, dtype=torch.uint8, device=codes.device)
+    nc, ng, _ = q8_w4_elems(g)
+    if out_w.numel() < nw or codes.numel() < nc or gshift.numel() < ng:
+        raise L.McamdError("unpack_q8_w4: operand too small")
+    check(L.lib().mcamd_unpack_q8_w4(C.byref(g), ptr(codes), ptr(gshift), ptr(out_w), stream_ptr()), "mcamd_unpack_q8_w4")
+    return out_w
+
+
+def conv_fwd_q8_w4_info(g):
+    """The kernel instance conv_fwd_q8_w4 launches for `g`, as conv_fwd_q8_info reports the fp8 block's
+    (mcamd_conv_fwd_q8_w4_info, the launch's own choice).  Needs no GPU."""
+    out = (C.c_int32 * 7)()
+    check(L.lib().mcamd_conv_fwd_q8_w4_info(C.byref(g), out), "mcamd_conv_fwd_q8_w4_info")
+    return Q8Info(*out)
+
+
+def conv_fwd_q8_w4(g, x8, codes, gshift, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None,
+                   y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None):
+    """conv_fwd_q8 on 4-bit weights (mcamd_conv_fwd_q8_w4): the same arguments with pack_q8_w4's codes and shift bytes in
+    place of the weight bytes, the arithmetic of conv_fwd_q8 on unpack_q8_w4's bytes.  `overflow`: as conv_fwd_q8."""
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff, overflow=overflow)
+    check(L.lib().mcamd_conv_fwd_q8_w4(C.byref(g), ptr(x8), ptr(codes), ptr(gshift), ptr(wexp), C.byref(e), int(bool(y_f8)),
+                                       int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q8_w4")
+
+
 # ----------------------------------------------------------------------------- compressed model files (.mcz, DESIGN.md 3s)
 WZ_ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1, L.WZ_CODE: 1}
 

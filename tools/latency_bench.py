@@ -2,7 +2,9 @@
 B = 1, 2, 4 and 8 with split-K off and on, for the dense model and (B = 1) for a quick_filter_prune(60) -> slim_export model.
 --precision fp16 (the default): precision "fp16" with Darknet.splitk off / on.  --precision fp8: the off leg is precision "fp8",
 the on leg "fp8-splitk" (MCAMD_Q8_MFMA picks the MFMA form of both), and the fp16 legs of the dense model are
-measured in the same process beside them.
+measured in the same process beside them.  --precision fp8-w4: the off leg is precision "fp8", the on leg "fp8-w4" (4-bit
+weights) on the dense model only; nothing is split there, and the launch record and the per-layer table carry
+fields of their own (`w4_layers`; `w4`, `us_fp8`, `us_fp8_w4`) in place of the split-K ones.
 
 Method: both settings alternate in one process, PAIRS pairs; each sample is a loop of CALLS calls after warm-up with a device
 synchronise only around the whole loop (host clock), so a sample is the sustained time per call, launch overhead included;
@@ -11,7 +13,7 @@ instrumented pass (the engine's HIP events around every conv launch, plan replay
 tiles, slices, us unsplit, us split (partial + finish launch).  Launch counts: the library calls of the recorded forward plan
 (a split block is one call and two kernels), the eval-mode bn_coeffs launches among them and the layout pass in front.
 
-usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8]
+usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8|fp8-w4]
                                                                              (--json: one JSON document on stdout)"""
 import json
 import os
@@ -33,8 +35,10 @@ def arg(name, dflt):
 
 CALLS, PAIRS, PASSES = max(200, arg("--calls", 200)), max(4, arg("--pairs", 4)), 7
 PRECISION = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp16"
-if PRECISION not in ("fp16", "fp8"):
-    raise SystemExit("--precision must be fp16 or fp8 (got %r)" % PRECISION)
+if PRECISION not in ("fp16", "fp8", "fp8-w4"):
+    raise SystemExit("--precision must be fp16, fp8 or fp8-w4 (got %r)" % PRECISION)
+W4 = PRECISION == "fp8-w4"
+ON_LEG = "fp8-w4" if W4 else "fp8-splitk"      # the on leg of an fp8 model
 if not torch.cuda.is_available():
     raise SystemExit("latency_bench needs the GPU")
 dev = torch.device("cuda", 0)
@@ -46,11 +50,11 @@ def engine(m, x):
 
 
 def leg(m, flag):
-    """Split-K off / on: Darknet.splitk of a "fp16" model; the precisions "fp8" / "fp8-splitk" of an fp8 one."""
+    """Split-K off / on: Darknet.splitk of a "fp16" model; the precisions "fp8" / "fp8-splitk" (or "fp8-w4") of an fp8 one."""
     if m.precision == "fp16":
         m.splitk = flag
     else:
-        m.precision = "fp8-splitk" if flag else "fp8"
+        m.precision = ON_LEG if flag else "fp8"
 
 
 def split_layers(eng):
@@ -102,6 +106,9 @@ def layer_table(m, x):
             eng.events = None
         per[flag] = {k: median(v) for k, v in acc.items()}
     eng = engine(m, x)
+    if W4:                      # nothing is split: the block's form on the "fp8-w4" leg and its time on either leg
+        return [{"conv": lay.li + 1, "form": lay.form, "w4": lay.form == "q8_w4", "us_fp8": per[False].get(lay.li + 1),
+                 "us_fp8_w4": per[True].get(lay.li + 1)} for lay in eng.layers]
     rows = []
     for lay in eng.layers:
         tiles = slices = None
@@ -132,9 +139,11 @@ def launches(m, x):
         out["on" if flag else "off"] = {
             "plan_calls": plan.launches if plan is not None else None,
             "bn_coeffs": sum(1 for lay in eng.layers if lay.bn is not None),
-            "layout_pass": 1,
-            "splitk_finish_kernels": len(split_layers(eng)),
-            "splitk_layers": split_layers(eng)}
+            "layout_pass": 1}
+        if W4:                  # (a w4 block is one launch, like the fp8 block it stands in for)
+            out["on" if flag else "off"]["w4_layers"] = list(eng.fp8_w4_layers)
+        else:
+            out["on" if flag else "off"].update(splitk_finish_kernels=len(split_layers(eng)), splitk_layers=split_layers(eng))
     return out
 
 
@@ -164,6 +173,14 @@ def show(res):
             print("B=%s %-7s ms/call: off %.3f (%.3f .. %.3f)  on %.3f (%.3f .. %.3f)  x%.3f"
                   % (B, what, median(off), min(off), max(off), median(on), min(on), max(on), median(off) / median(on)))
         la = r["launches"]
+        if W4:
+            print("B=%s plan calls: fp8 %s, fp8-w4 %s; bn_coeffs launches %d, layout pass 1; w4 layers %s; logits rel-L2 fp8-w4 vs fp8 %.2e"
+                  % (B, la["off"]["plan_calls"], la["on"]["plan_calls"], la["on"]["bn_coeffs"], la["on"]["w4_layers"], r["rel_l2_on_vs_off"]))
+            for row in r.get("layers", ()):
+                print("conv%-3d %-8s us fp8 %s  us fp8-w4 %s" % (row["conv"], row["form"],
+                      "%.1f" % row["us_fp8"] if row["us_fp8"] is not None else "-",
+                      "%.1f" % row["us_fp8_w4"] if row["us_fp8_w4"] is not None else "-"))
+            continue
         print("B=%s plan calls: off %s, on %s (+%d finish kernels); bn_coeffs launches %d, layout pass 1; split layers %s; "
               "logits rel-L2 on vs off %.2e" % (B, la["off"]["plan_calls"], la["on"]["plan_calls"], la["on"]["splitk_finish_kernels"],
                                                 la["on"]["bn_coeffs"], la["on"]["splitk_layers"], r["rel_l2_on_vs_off"]))
@@ -178,22 +195,23 @@ def show(res):
 with torch.no_grad():
     dense = init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
     dense.eval()
-    dense.precision = PRECISION
+    dense.precision = "fp8" if PRECISION == "fp8-w4" else PRECISION
     results = [bench_model(dense, (1, 2, 4, 8), "yolov2-voc")]
-    pruned = init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
-    pruned.set_masks(quick_filter_prune(pruned, 60.0))
-    pruned.eval()
-    with tempfile.TemporaryDirectory() as tmp:
-        thin = slim.slim_export(pruned, os.path.join(tmp, "slim.cfg"))
-        thin.eval()
-        thin.precision = PRECISION
-        results.append(bench_model(thin, (1,), "yolov2-voc slim60"))
+    pruned = None if PRECISION == "fp8-w4" else init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
+    if pruned is not None:
+        pruned.set_masks(quick_filter_prune(pruned, 60.0))
+        pruned.eval()
+        with tempfile.TemporaryDirectory() as tmp:
+            thin = slim.slim_export(pruned, os.path.join(tmp, "slim.cfg"))
+            thin.eval()
+            thin.precision = PRECISION
+            results.append(bench_model(thin, (1,), "yolov2-voc slim60"))
     if PRECISION == "fp8":      # the fp16 split-K figures of the same run, beside the fp8 ones
         dense.precision = "fp16"
         results.append(bench_model(dense, (1, 2, 4, 8), "yolov2-voc"))
 
 doc = {"calls": CALLS, "pairs": PAIRS, "passes": PASSES, "arch": L.lib().mcamd_arch().decode(), "precision": PRECISION,
-       "q8_mfma": int(os.environ.get("MCAMD_Q8_MFMA", 0)),
+       "on_leg": ON_LEG if PRECISION != "fp16" else "splitk", "q8_mfma": int(os.environ.get("MCAMD_Q8_MFMA", 0)),
        "min_chunks": int(os.environ.get("MCAMD_SPLITK_MIN_CHUNKS", 8)), "cus": int(os.environ.get("MCAMD_SPLITK_CUS", 256)),
        "results": results}
 if "--json" in sys.argv:

@@ -8,7 +8,10 @@ fp16 with sparse = "2:4", fp8 and fp8-2:4 (windows alternated over all four).
 unfused border path) and fp8 the same way, and the table names per layer cin -> round_up(cin, 64), which blocks are fp8
 blocks (`slim`: on mcamd_conv_fwd_q8_slim, `table`: with a border table) and the time of each cast pass.  Run it once
 without and once with MCAMD_Q8_MFMA=1 for the two forms of the fp8 kernel.
-usage: python tools/q8_bench.py [batch] [forwards per window] [--sparse | --slim PCT] [--json PATH]"""
+--w4: "fp8" against "fp8-w4" (4-bit weights) on the same weights, the two alternated in one process, with the
+resident weight-operand bytes of the fp8 blocks under both -- once per MCAMD_Q8_MFMA form, each form in a child process of its
+own started with that switch; the merged report goes to profiles/q8_w4_bench.json unless --json names another file.
+usage: python tools/q8_bench.py [batch] [forwards per window] [--sparse | --slim PCT | --w4] [--json PATH]"""
 import json
 import os
 import sys
@@ -27,11 +30,16 @@ def parse(argv):
         raise SystemExit("q8_bench: batch and forwards per window must be positive")
     if slim_pct is not None and ("--sparse" in argv or not 0.0 < slim_pct < 100.0):
         raise SystemExit("q8_bench: --slim takes a percentage in (0, 100) and does not combine with --sparse")
+    if "--w4" in argv and ("--sparse" in argv or slim_pct is not None):
+        raise SystemExit("q8_bench: --w4 does not combine with --sparse or --slim")
     return B, K, out_json, "--sparse" in argv, slim_pct
 
 
 def main(argv):
     B, K, out_json, sparse, slim_pct = parse(argv)
+    w4 = "--w4" in argv
+    if w4 and "--w4-form" not in argv:
+        return run_w4_forms(argv, B, K, out_json)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("q8_bench needs the GPU")
@@ -53,6 +61,8 @@ def main(argv):
         from modelcompression_amd.pruning.weightPruning.methods import nm_prune
         m.set_masks(nm_prune(m))
         modes = ("fp16", "fp16+2:4", "fp8", "fp8-2:4")
+    if w4:
+        modes = ("fp8", "fp8-w4")
 
     def select(mode):
         m.precision, m.sparse = mode.split("+")[0], "2:4" if mode.endswith("+2:4") else None
@@ -77,7 +87,7 @@ def main(argv):
             eng.events = None
         return {k: sorted(v)[len(v) // 2] for k, v in per.items()}
 
-    with torch.no_grad():
+    def measure():
         res = {}
         for prec in modes:
             select(prec)
@@ -102,6 +112,18 @@ def main(argv):
                     m(x)
                 torch.cuda.synchronize()
                 rates[prec].append(B * K / (time.perf_counter() - t0))
+        return res, rates, fp8_layers, sparse_layers if sparse else None
+
+    if w4:                                     # (one MFMA form: the caller's MCAMD_Q8_MFMA, as in every other mode)
+        from modelcompression_amd.engine import _FORMS
+        with torch.no_grad():
+            res, rates, fp8_layers, _ = measure()
+        nbytes = {p: sum(getattr(lay, name).numel() * getattr(lay, name).element_size()
+                         for lay in engine(p).layers if lay.li + 1 in fp8_layers for name, _ in _FORMS[lay.form].bufs) for p in modes}
+        return report_w4(B, K, out_json, os.environ.get("MCAMD_Q8_MFMA", "0"), res, rates, fp8_layers,
+                         list(engine("fp8-w4").fp8_w4_layers), nbytes)
+    with torch.no_grad():
+        res, rates, fp8_layers, sparse_layers = measure()
 
     if slim_pct is not None:
         return report_slim(B, K, out_json, slim_pct, engine("fp8"), res, rates)
@@ -124,6 +146,54 @@ def main(argv):
         with open(out_json, "w") as f:
             json.dump({"B": B, "forwards_per_window": K, "fp8_layers": fp8_layers, "fp16_ms": d["layers"], "fp8_ms": s["layers"],
                        "fp16_img_s": rates["fp16"], "fp8_img_s": rates["fp8"], "pairs": pairs, "rel_l2": rel}, f, indent=1)
+
+
+def run_w4_forms(argv, B, K, out_json):
+    """--w4: one child process per MCAMD_Q8_MFMA form (the library reads the switch once per process), their reports merged."""
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {"B": B, "forwards_per_window": K, "forms": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for mfma in ("0", "1"):
+            part = os.path.join(tmp, "form%s.json" % mfma)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), str(B), str(K), "--w4", "--w4-form", "--json", part],
+                               env=dict(os.environ, MCAMD_Q8_MFMA=mfma))
+            if r.returncode != 0:
+                raise SystemExit("q8_bench --w4: the MCAMD_Q8_MFMA=%s run failed (exit %d)" % (mfma, r.returncode))
+            with open(part) as f:
+                out["forms"][mfma] = json.load(f)
+    out_json = out_json or os.path.join(root, "profiles", "q8_w4_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out_json)), exist_ok=True)
+    with open(out_json, "w") as f:
+        json.dump(out, f, indent=1)
+
+
+def report_w4(B, K, out_json, mfma, res, rates, fp8_layers, w4_layers, nbytes):
+    d, s = res["fp8"], res["fp8-w4"]
+    rel = float((s["logits"].double() - d["logits"].double()).norm() / d["logits"].double().norm())
+    print("MCAMD_Q8_MFMA=%s; fp8 layers %s; w4 layers %s" % (mfma, fp8_layers, w4_layers))
+    print("%-6s %10s %10s %9s" % ("conv", "fp8 ms", "fp8-w4 ms", "w4 / fp8"))
+    for k in sorted(d["layers"]):
+        dm, sm = d["layers"][k], s["layers"].get(k, float("nan"))
+        print("%-6s %10.3f %10.3f %9.2f%s" % ("conv%d" % k, dm, sm, sm / dm, "" if k in w4_layers else "  (not w4)"))
+    td, ts = sum(d["layers"].values()), sum(s["layers"].values())
+    print("%-6s %10.3f %10.3f %9.2f" % ("sum", td, ts, ts / td))
+    for p in ("fp8", "fp8-w4"):
+        r = rates[p]
+        print("whole forward B=%d, %d forwards per window, %-7s %s img/s (spread %.2f %%)"
+              % (B, K, p + ":", ["%.0f" % v for v in r], 100.0 * (max(r) - min(r)) / min(r)))
+    pairs = [b / a for a, b in zip(rates["fp8"], rates["fp8-w4"])]
+    print("pairs fp8-w4 / fp8 (img/s): %s" % ["%.3f" % p for p in pairs])
+    print("resident weight-operand bytes of the fp8 blocks: fp8 %d, fp8-w4 %d (%.4f x)"
+          % (nbytes["fp8"], nbytes["fp8-w4"], nbytes["fp8-w4"] / nbytes["fp8"]))
+    print("logits rel-L2 (fp8-w4 vs fp8 engine, same weights): %.3e" % rel)
+    sys.stdout.flush()
+    if out_json:
+        with open(out_json, "w") as f:
+            json.dump({"fp8_layers": fp8_layers, "fp8_w4_layers": w4_layers, "fp8_ms": d["layers"], "fp8_w4_ms": s["layers"],
+                       "fp8_img_s": rates["fp8"], "fp8_w4_img_s": rates["fp8-w4"], "pairs_w4_over_fp8": pairs,
+                       "weight_operand_bytes": nbytes, "rel_l2_w4_vs_fp8": rel}, f, indent=1)
 
 
 def report_slim(B, K, out_json, pct, eng, res, rates):
