@@ -497,6 +497,35 @@ int mcamd_conv_fwd_q8_w4(const mcamd_conv_geom* g, const void* x8, const void* c
  * the tile mcamd_conv_fwd_q8 takes for the same geometry (no instance needs scratch memory, none is left out). */
 int mcamd_conv_fwd_q8_w4_info(const mcamd_conv_geom* g, int32_t out[7]);
 
+/* ---------------------------------------------------------------------------
+ * 4-bit quantisation-aware training (an addition beyond the reference; Darknet.precision = "fp8-w4-qat"): the
+ * fp8 quantisation-aware training above with the weights of every fp8 block in the 4-bit format above -- the training-mode
+ * forward of a block runs on the codes it would be deployed with under "fp8-w4".
+ *   forward   a8 = q(2 x) input codes, as there; every step w = weight * mask is re-quantised on the device by
+ *             mcamd_pack_q8_w4 into codes, group shifts g and filter exponents e4_f (the format is unchanged);
+ *             raw output y[m][f] = 2^-(e4_f + 1) * sum a8 * W8x, fp32 [B*H*W][y_ld], W8x the e4m3 bytes the codes stand for --
+ *             the convolution of x_q = deq(a8) / 2 with w_q = grid[code] * 2^g * 2^-e4_f (the powers of two are exact);
+ *             the BatchNorm statistics of those fp32 values, the coefficients, the byte and fp16-twin stores and the
+ *             fp16 -> fp8 edge are exactly those of "fp8-qat".
+ *   backward  straight-through, WITHOUT a clipping mask: dX = dgrad(dY, fp16(w_q)), dW = wgrad(dY, x_q) * mask, master
+ *             weights fp32.  A weight its group rounds to code 0 still receives its gradient.  fp16(w_q) is exact whenever
+ *             w_q stays in fp16's normal range (one mantissa bit).
+ *   An inference-mode forward under "fp8-w4-qat" is the "fp8-w4" engine's, bit for bit.
+ * ------------------------------------------------------------------------- */
+/* mcamd_conv_fwd_q8_w4's K loop (staging, register decode, both MCAMD_Q8_MFMA forms) with mcamd_conv_fwd_q8's
+ * MCAMD_EPI_RAW_F32 epilogue -- the only mode accepted: y as above and, with epi->stats, the per-channel sums and sums of squares
+ * of the fp32 values, row p over the pixels [128 p, 128 p + 128) -- every row written, fixed summation order, no atomics;
+ * stats_rows must equal mcamd_conv_fwd_q8_stats_rows(g), stats_ld >= round_up(cout, 256).  Bit-equal to mcamd_conv_fwd_q8 in that
+ * mode on mcamd_unpack_q8_w4's bytes with the exponents e4_f.  The tile is the one mcamd_conv_fwd_q8 takes in that mode
+ * (mcamd_conv_fwd_q8_info, form 1).  Both `pad` forms of x, any batch size. */
+int mcamd_conv_fwd_q8_w4_raw(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* gshift, const int32_t* wexp,
+                             const mcamd_conv_epilogue* epi, void* stream);
+/* w_q = grid[code] * 2^g * 2^-e4_f as fp32 OIHW [cout][cin][k][k], decoded from mcamd_pack_q8_w4's operands through the layout
+ * stated above: the values the forward multiplied.  A masked weight has code 0 and comes out as exactly 0.
+ * mcamd_pack_weights(_many) builds the dgrad operand from it (with no mask). */
+int mcamd_fakequant_q8_w4(const mcamd_conv_geom* g, const void* codes, const void* gshift, const int32_t* wexp, float* wq_oihw,
+                          void* stream);
+
 /* dx = conv_transpose(dy, w) -- autograd's input gradient of the same call.
  * `dy` is padded NHWC fp16 [B][H+2][W+2][dy_ld] (zero halo); g->cin/cout keep their forward
  * meaning; the result has g->cin channels.  epi->mode 0 (fp16 [M][y_ld]) or 1 (fp32 NCHW). */

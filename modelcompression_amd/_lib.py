@@ -233,6 +233,8 @@ SIGNATURES = {
     "mcamd_unpack_q8_w4": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P]),
     "mcamd_conv_fwd_q8_w4": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _P]),
     "mcamd_conv_fwd_q8_w4_info": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I32)]),
+    "mcamd_conv_fwd_q8_w4_raw": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
+    "mcamd_fakequant_q8_w4": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
     "mcamd_cast_q8": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _I32, _I32, _P]),
     "mcamd_conv_fwd_q8_stats_rows": (_I32, [C.POINTER(ConvGeom)]),
     "mcamd_fakequant_q8": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),

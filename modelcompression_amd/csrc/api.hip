@@ -1120,6 +1120,38 @@ extern "C" int mcamd_conv_fwd_q8_w4(const mcamd_conv_geom* g, const void* x8, co
     return mcamd_conv_q8_w4_launch(a, gshift, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
 }
 
+// the training form (Darknet.precision = "fp8-w4-qat"): raw fp32 output + statistics, and the values the codes
+// stand for
+extern "C" int mcamd_conv_fwd_q8_w4_raw(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* gshift,
+                                        const int32_t* wexp, const mcamd_conv_epilogue* epi, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_w4_raw: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_q8_w4_raw(&g_, x8, codes, gshift, wexp, &e_, s); });
+    }
+    if (check_geom(g, "conv_fwd_q8_w4_raw")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_w4_ok(g), "conv_fwd_q8_w4_raw: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_ok)");
+    MCAMD_REQUIRE(x8 && codes && gshift && wexp, "conv_fwd_q8_w4_raw: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_RAW_F32, "conv_fwd_q8_w4_raw: epilogue mode 3 (MCAMD_EPI_RAW_F32) only");
+    IgemmArgs a;
+    fill_operand(a, g, x8, codes, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_w4_raw", mcamd_conv_fwd_q8_stats_rows(g))) return MCAMD_EINVAL;
+    return mcamd_conv_q8_w4_raw_launch(a, gshift, wexp, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_fakequant_q8_w4(const mcamd_conv_geom* g, const void* codes, const void* gshift, const int32_t* wexp,
+                                     float* wq_oihw, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "fakequant_q8_w4: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_fakequant_q8_w4(&g_, codes, gshift, wexp, wq_oihw, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_w4_ok(g), "fakequant_q8_w4: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_ok)");
+    MCAMD_REQUIRE(codes && gshift && wexp && wq_oihw, "fakequant_q8_w4: null pointer");
+    return mcamd_fakequant_q8_w4_launch(codes, gshift, wexp, wq_oihw, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
+}
+
 // mcamd_q8_w4_choice()'s answer: what mcamd_conv_fwd_q8_w4 launches for this geometry (host logic only)
 extern "C" int mcamd_conv_fwd_q8_w4_info(const mcamd_conv_geom* g, int32_t out[7]) {
     MCAMD_REQUIRE(g && out, "conv_fwd_q8_w4_info: null argument");

@@ -1,6 +1,7 @@
 // Addressing and epilogues shared by the forward implicit-GEMM kernels (conv_igemm.hip, conv_igemm_pp.hip,
-// conv_sparse.hip, conv_q8.hip): GEMM row -> pixel, the store of a finished LDS tile into the consumer's padded buffer,
-// and the accumulators -> LDS tile step of the two weights-as-A kernels.
+// conv_sparse.hip, conv_q8.hip, conv_q8_w4.hip): GEMM row -> pixel, the store of a finished LDS tile into the consumer's padded
+// buffer, the accumulators -> LDS tile step of the weights-as-A kernels, and the raw fp32 epilogue + BatchNorm partial sums of
+// the byte kernels' training forms.
 //
 // Inference blocks whose activation pass is fused with MaxPool(2,2) / Reorg(2) (reference src/nets.py:802-821 conv ->
 // BatchNorm -> LeakyReLU -> MaxPool, nets.py:648-667 Reorg): the conv epilogue has applied leaky(acc * scale + shift) and
@@ -523,4 +524,79 @@ __device__ __forceinline__ bool write_ch_tile(const IgemmArgs& __restrict__ a, c
         }
     }
     return sat;
+}
+
+// ---------------------------------------------------------------------------------------
+// MCAMD_EPI_RAW_F32 of the byte weights-as-A kernels (conv_q8.hip, conv_q8_w4.hip; training): y[m][n] =
+// 2^-(wexp[n] + 1) * acc as fp32 [M][y_ld] (the power of two is exact) plus, with a.stats, per channel the sum and the sum of
+// squares of those fp32 values over the workgroup's pixel tile: slab row = the pixel tile mt, every row written, fixed order,
+// no atomics.  Each wave transposes its accumulators through a private LDS region, 32 pixels at a time ([pixel][channel], rows
+// WM + 4 floats apart: the 16-byte writes of 8 pixels fall on 8 different bank slots), stores whole channel runs and adds the
+// 32 rows of a column in order; pixels past M go down as zeros and are not stored.  Every wave of the workgroup calls it, behind
+// a barrier that ends the K loop's use of `smem`, of which it uses the first raw32_ch_lds_bytes().
+// ---------------------------------------------------------------------------------------
+__host__ __device__ constexpr int raw32_ch_lds_bytes(int bmw, int bnp, int wm, int wn) {
+    return (bmw / wm) * (bnp / wn) * 32 * (wm + 4) * 4 + (bnp / wn) * bmw * 2 * 4;
+}
+
+template <int BMW, int BNP, int WM, int WN, int TM, int TN>
+__device__ __forceinline__ void store_raw32_ch_tile(const IgemmArgs& __restrict__ a, const f32x16_t (&acc)[TM][TN],
+                                                    const int* __restrict__ wexp, char* smem, int mt, int nt, int wm, int wn, int wave,
+                                                    int lane, int tid) {
+    constexpr int WAVES_N = BNP / WN, NWAVES = (BMW / WM) * WAVES_N;
+    constexpr int PF = WM + 4, C4 = WM / 4;    // floats between the pixel rows of a wave's region; float4 pieces per row
+    constexpr int REGION = 32 * PF;            // floats per wave
+    float* tile = (float*)smem + wave * REGION;
+    float* comb = (float*)smem + NWAVES * REGION;             // [WAVES_N][BMW][2] partial sums of the pixel waves
+    float* y = (float*)a.y;
+    float s1 = 0.f, s2 = 0.f;                  // lane c < WM: channel wm * WM + c over this wave's WN pixels
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int m0 = mt * BNP + wn * WN + j * 32;
+        const bool live = m0 + (lane & 31) < a.M;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int ch0 = i * 32 + 8 * g + 4 * (lane >> 5);
+                f32x4_t v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)    // (rows up to Npad = round_up(N, 256) exist: zero bytes, exponent 0)
+                    v[e] = live ? ldexpf(acc[i][j][4 * g + e], -(wexp[nt * BMW + wm * WM + ch0 + e] + 1)) : 0.f;
+                *(f32x4_t*)(tile + (lane & 31) * PF + ch0) = v;
+            }
+        __syncthreads();
+        for (int slot = lane; slot < 32 * C4; slot += 64) {
+            const int row = slot / C4, c4 = slot - row * C4;
+            const int m = m0 + row, n0 = nt * BMW + wm * WM + c4 * 4;
+            if (m < a.M && n0 < a.N) *(f32x4_t*)(y + (long long)m * a.y_ld + a.y_choff + n0) = *(const f32x4_t*)(tile + row * PF + c4 * 4);
+        }
+        if (a.stats && lane < WM) {
+#pragma unroll 8
+            for (int p = 0; p < 32; ++p) {
+                const float v = tile[p * PF + lane];
+                s1 += v;
+                s2 += v * v;
+            }
+        }
+        __syncthreads();
+    }
+    if (a.stats) {                             // (wave-uniform)
+        if (lane < WM) {
+            comb[(wn * BMW + wm * WM + lane) * 2] = s1;
+            comb[(wn * BMW + wm * WM + lane) * 2 + 1] = s2;
+        }
+        __syncthreads();
+        if (tid < BMW) {
+            float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+            for (int k = 0; k < WAVES_N; ++k) {
+                t1 += comb[(k * BMW + tid) * 2];
+                t2 += comb[(k * BMW + tid) * 2 + 1];
+            }
+            // channels in [N, round_up(N, BMW)) come out as zeros: stats_ld >= round_up(N, 256) holds them
+            a.stats[((long long)mt * 2 + 0) * a.stats_ld + nt * BMW + tid] = t1;
+            a.stats[((long long)mt * 2 + 1) * a.stats_ld + nt * BMW + tid] = t2;
+        }
+    }
 }

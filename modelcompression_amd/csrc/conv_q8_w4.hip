@@ -1,4 +1,5 @@
-// 4-bit weight inference on the fp8 engine (an addition beyond the reference: Darknet.precision = "fp8-w4"):
+// 4-bit weight inference on the fp8 engine (an addition beyond the reference: Darknet.precision = "fp8-w4") --
+// and its training form (Darknet.precision = "fp8-w4-qat"; DESIGN.md 3x: the raw fp32 epilogue + the fake quantisation below):
 // conv_q8.hip's block with the weight operand held as e2m1 codes + one shift per group of 32 input channels, staged as
 // nibbles and expanded to e4m3 bytes IN REGISTERS in front of the MFMAs.
 //
@@ -61,9 +62,14 @@ __device__ __forceinline__ i32x8_t w4_decode(i32x4_t codes, unsigned shifts) {
     return o;
 }
 
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
-__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
-void conv_q8_w4_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad, const int* __restrict__ wexp, int y_f8, int y2_f8) {
+// RAW (training, Darknet.precision = "fp8-w4-qat"): the same K loop -- staging, register decode, both MFMA forms
+// and their s_nop spacing -- with conv_q8_block's MCAMD_EPI_RAW_F32 epilogue (conv_epi.h: store_raw32_ch_tile): y[m][n] =
+// 2^-(e4[n] + 1) * S as fp32 [M][y_ld] and, with a.stats, the per-channel sums and sums of squares of those values, slab row =
+// the pixel tile.  That epilogue's LDS need (72 / 36 / 19 KB) is not the ring's (51 / 39 / 33 KB -- the code rows are half the
+// fp8 kernel's): the launch asks for the larger of the two.
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW>
+__device__ __forceinline__ void conv_q8_w4_block(const IgemmArgs& __restrict__ a, const char* __restrict__ gshift, int npad,
+                                                 const int* __restrict__ wexp, int y_f8, int y2_f8) {
     constexpr int WAVES_N = BNP / WN;
     constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
     constexpr int BK = 64, CPRA = 2, CPRB = 4;     // 16-byte pieces per code row / per pixel row
@@ -199,6 +205,10 @@ void conv_q8_w4_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad, c
 
     // ------------------------------- epilogue (conv_q8_kernel's, e4_f in place of e_f) -------------------------------
     __syncthreads();                               // every wave is done with the stage buffers
+    if constexpr (RAW) {                           // (the launch requested raw32_ch_lds_bytes() or the ring, whichever is larger)
+        store_raw32_ch_tile<BMW, BNP, WM, WN>(a, acc, wexp, smem, mt, nt, wm, wn, wave, lane, tid);
+        return;
+    }
     const bool has2 = a.y2 != nullptr;
     const bool need_b = y_f8 || (has2 && y2_f8), need_h = !y_f8 || (has2 && !y2_f8);
     constexpr int PB = BMW + 8;                    // tile row pitch: a wave's 32 pixels on 32 LDS banks
@@ -210,6 +220,35 @@ void conv_q8_w4_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad, c
     __syncthreads();
     store_pad_tile<BNP, BMW, PB, NT>(a, bt, ht, y_f8 != 0, y2_f8 != 0, mt, nt, tid);
     if (sat && a.overflow) atomicOr(a.overflow, 1);
+}
+
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
+void conv_q8_w4_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad, const int* __restrict__ wexp, int y_f8, int y2_f8) {
+    conv_q8_w4_block<BMW, BNP, WM, WN, NSTAGE, F8MFMA, false>(a, gshift, npad, wexp, y_f8, y2_f8);
+}
+
+// ... with the raw fp32 epilogue + statistics (training)
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
+void conv_q8_w4_raw_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad, const int* __restrict__ wexp) {
+    conv_q8_w4_block<BMW, BNP, WM, WN, NSTAGE, F8MFMA, true>(a, gshift, npad, wexp, 0, 0);
+}
+
+template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+static int conv_q8_w4_raw_launch_t(IgemmArgs& a, const Q8Choice& c, const char* gshift, int npad, const int* wexp, hipStream_t st) {
+    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
+    constexpr int RING = NSTAGE * (BMW * 32 + BNP * 64 + 1024);
+    constexpr int EPI = raw32_ch_lds_bytes(BMW, BNP, WM, WN);
+    constexpr int LDS = RING > EPI ? RING : EPI;   // (256 x 128: the epilogue's 72 KB over a 51 KB ring)
+    static_assert(EPI <= LDS && RING <= LDS && LDS <= 160 * 1024, "raw epilogue and ring inside the requested LDS");
+    auto kern = conv_q8_w4_raw_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
+    MCAMD_LDS_OPT_IN(kern, LDS);
+    a.num_mtiles = c.mtiles;
+    a.num_ntiles = c.ntiles;
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), LDS, st, a, gshift, npad, wexp);
+    MCAMD_LAUNCH_CHECK("conv_fwd_q8_w4_raw");
+    return MCAMD_OK;
 }
 
 template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
@@ -250,6 +289,24 @@ int mcamd_conv_q8_w4_launch(IgemmArgs& a, const void* gshift, const void* wexp, 
         if (!c.f8mfma && c.bmw == 64) return conv_q8_w4_launch_t<64, 128, 32, 64, 3, false>(a, c, gs, npad, we, y_f8, y2_f8, st);
     }
     mcamd_set_error("conv_fwd_q8_w4: no kernel instance %d x %d, fp8 MFMA %d, %d stages", c.bmw, c.bnp, c.f8mfma, c.stages);
+    return MCAMD_EINVAL;
+}
+
+// The training launch: the same tile per filter count (mcamd_q8_choice's for the raw fp8 block, as the engine's statistics
+// slab and mcamd_conv_fwd_q8_stats_rows assume).
+int mcamd_conv_q8_w4_raw_launch(IgemmArgs& a, const void* gshift, const void* wexp, hipStream_t st) {
+    const int* we = (const int*)wexp;
+    const char* gs = (const char*)gshift;
+    const int npad = round_up_int(a.N, 256);
+    const Q8Choice c = mcamd_q8_choice(a.M, a.N, MCAMD_Q8_FORM_RAW);
+    if (c.bnp == 128 && c.stages == 3) {
+        if (c.f8mfma && c.bmw == 256) return conv_q8_w4_raw_launch_t<256, 128, 64, 64, 3, true>(a, c, gs, npad, we, st);
+        if (c.f8mfma && c.bmw == 128) return conv_q8_w4_raw_launch_t<128, 128, 64, 64, 3, true>(a, c, gs, npad, we, st);
+        if (c.f8mfma && c.bmw == 64) return conv_q8_w4_raw_launch_t<64, 128, 32, 64, 3, true>(a, c, gs, npad, we, st);
+        if (!c.f8mfma && c.bmw == 128) return conv_q8_w4_raw_launch_t<128, 128, 64, 64, 3, false>(a, c, gs, npad, we, st);
+        if (!c.f8mfma && c.bmw == 64) return conv_q8_w4_raw_launch_t<64, 128, 32, 64, 3, false>(a, c, gs, npad, we, st);
+    }
+    mcamd_set_error("conv_fwd_q8_w4_raw: no kernel instance %d x %d, fp8 MFMA %d, %d stages", c.bmw, c.bnp, c.f8mfma, c.stages);
     return MCAMD_EINVAL;
 }
 
@@ -377,5 +434,40 @@ int mcamd_unpack_q8_w4_launch(const void* codes, const void* gshift, void* wq, i
     hipLaunchKernelGGL(unpack_q8_w4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const char*)codes,
                        (const char*)gshift, (char*)wq, total, ktot, npad);
     MCAMD_LAUNCH_CHECK("unpack_q8_w4");
+    return MCAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// fake quantisation (training): codes + shift bytes + exponents -> fp32 OIHW w_q = grid[code] * 2^g * 2^-e4_f, the
+// values the forward's decoded bytes stand for, read back through the documented layout.  The fp16 packers build the dgrad
+// operand from it.  One thread per weight (the stores are contiguous; a code byte is shared by two threads, a shift byte by 32).
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fakequant_q8_w4_kernel(const unsigned char* __restrict__ codes,
+                                                              const unsigned char* __restrict__ gshift, const int* __restrict__ wexp,
+                                                              float* __restrict__ out, long long total, int cin, int ntaps, int npad) {
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;         // OIHW: ((n * cin + c) * ntaps + tap)
+    if (s >= total) return;
+    const int tap = (int)(s % ntaps);
+    const long long nc = s / ntaps;
+    const int c = (int)(nc % cin), n = (int)(nc / cin);
+    const int q = (c / 64) * ntaps + tap, kk = c % 64;                     // chunk and position in it (mcamd_pack_q8's order)
+    const int j = kk >> 5, h = (kk >> 4) & 1, t = (kk & 15) + 16 * j;      // group, piece, t: kk = w4_kk(h, t)
+    const int d = t >> 3, r = t & 7;                                       // byte i = 4 d + r % 4, high nibble for r >= 4
+    const unsigned byte = codes[(long long)n * (cin * ntaps / 2) + (long long)q * 32 + 16 * h + 4 * d + (r & 3)];
+    const unsigned code = r >= 4 ? byte >> 4 : byte & 15u;
+    const int g = (int)gshift[((long long)q * npad + n) * 2 + j] - 5;
+    const unsigned m = code & 7u;
+    // grid[m]: {0, 0.5, 1, 1.5} = m / 2, {2, 3, 4, 6} = (2 + m % 2) << (m - 4) / 2
+    const float mag = m < 4u ? 0.5f * (float)m : (float)((2u + (m & 1u)) << ((m - 4u) >> 1));
+    const float v = ldexpf(mag, g - wexp[n]);                              // exact: a power of two
+    out[s] = m == 0u ? 0.f : ((code & 8u) ? -v : v);
+}
+
+int mcamd_fakequant_q8_w4_launch(const void* codes, const void* gshift, const void* wexp, float* out, int cout, int cin, int ntaps,
+                                 hipStream_t st) {
+    const long long total = (long long)cout * cin * ntaps;
+    hipLaunchKernelGGL(fakequant_q8_w4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const unsigned char*)codes,
+                       (const unsigned char*)gshift, (const int*)wexp, out, total, cin, ntaps, round_up_int(cout, 256));
+    MCAMD_LAUNCH_CHECK("fakequant_q8_w4");
     return MCAMD_OK;
 }

@@ -144,7 +144,7 @@ int mcamd_pack_sparse24_launch(const float* w, const float* mask, void* vals, vo
 // instance (bmw filters x bnp pixels, the MFMA form MCAMD_Q8_MFMA selects, LDS ring stages) and its grid for M pixels x N
 // filters in one of the four forms; both launches dispatch on it
 #define MCAMD_Q8_FORM_INFER 0    // conv_q8_kernel, inference epilogue
-#define MCAMD_Q8_FORM_RAW 1      // conv_q8_kernel, raw fp32 epilogue + statistics (fp8-qat)
+#define MCAMD_Q8_FORM_RAW 1      // conv_q8_kernel, raw fp32 epilogue + statistics (fp8-qat; conv_q8_w4_raw_kernel under fp8-w4-qat)
 #define MCAMD_Q8_FORM_BORDER 2   // conv_q8_border_kernel (slim models with a border table)
 #define MCAMD_Q8_FORM_SPARSE 3   // conv_q8_sparse_kernel (2:4)
 struct Q8Choice {
@@ -178,6 +178,11 @@ int mcamd_conv_q8_w4_launch(IgemmArgs& a, const void* gshift, const void* wexp, 
 int mcamd_pack_q8_w4_launch(const float* w, const float* mask, void* codes, void* gshift, void* wexp, int cout, int cin, int ntaps,
                             hipStream_t st);
 int mcamd_unpack_q8_w4_launch(const void* codes, const void* gshift, void* wq, int cout, int cin, int ntaps, hipStream_t st);
+// ... its training form (a.mode MCAMD_EPI_RAW_F32: the raw fp8 block's tile, fp32 y + one statistics row per pixel tile), and the
+// fp32 OIHW values the codes stand for
+int mcamd_conv_q8_w4_raw_launch(IgemmArgs& a, const void* gshift, const void* wexp, hipStream_t st);
+int mcamd_fakequant_q8_w4_launch(const void* codes, const void* gshift, const void* wexp, float* out, int cout, int cin, int ntaps,
+                                 hipStream_t st);
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps);
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);

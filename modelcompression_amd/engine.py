@@ -249,6 +249,10 @@ class _Q8(_Dense):
         if eng._qat_train(lay):     # the values those bytes stand for, fp32 OIHW: the dgrad packing's source
             ops.fakequant_q8(lay.geom_act, w, mask, lay.wexp, lay.w_q)
 
+    def qat_raw(self, eng, lay, x8):
+        """The training-mode launch of a quantisation-aware training block (Engine._qat_forward): fp32 raw output + statistics."""
+        eng._timed('fwd', lay, ops.conv_fwd_q8_raw, lay.geom_act, x8, lay.wq, lay.wexp, lay.y, lay.cout, 0, lay.stats)
+
     def operands(self, eng, lay, xin):
         x8 = eng.qbufs.get(lay.tin.buf)
         if lay.xq is not None:      # the fp16 -> fp8 edge: cast pass over the padded input slice into a private byte copy
@@ -293,9 +297,18 @@ class _Q8SplitK(_Q8):
 class _Q8W4(_Q8):
     """An fp8 block on 4-bit weights ("fp8-w4", csrc/conv_q8_w4.hip): e2m1 nibble codes, one shift byte per group
     of 32 input channels and one exponent per filter -- 4.25 bits per weight, expanded to e4m3 bytes in the kernel's registers.
-    No weight bytes (`wq`) are held."""
+    No weight bytes (`wq`) are held.  Under "fp8-w4-qat"  the training-mode forward runs on the same operands,
+    re-quantised every step, and `w_q` -- the values the codes stand for -- is decoded from them for the dgrad packing."""
     fwd, elems, packer = "conv_fwd_q8_w4", "q8_w4_elems", "pack_q8_w4"
     bufs = (("w4c", torch.uint8), ("w4g", torch.uint8), ("wexp4", torch.int32))
+
+    def pack(self, eng, lay, w, mask):
+        _Dense.pack(self, eng, lay, w, mask)
+        if eng._qat_train(lay):
+            ops.fakequant_q8_w4(lay.geom_act, lay.w4c, lay.w4g, lay.wexp4, lay.w_q)
+
+    def qat_raw(self, eng, lay, x8):
+        eng._timed('fwd', lay, ops.conv_fwd_q8_w4_raw, lay.geom_act, x8, lay.w4c, lay.w4g, lay.wexp4, lay.y, lay.cout, 0, lay.stats)
 
 
 _FORMS = {"dense": _Dense(), "splitk": _SplitK(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "q8": _Q8(),
@@ -371,19 +384,23 @@ class Engine:
         "fp8-w4" -- the "fp8" engine on 4-bit weights, inference only: every block "fp8" runs in form "q8" holds
         its weights as e2m1 codes with a shift per group of 32 input channels (csrc/conv_q8_w4.hip, `fp8_w4_layers`) and
         computes what the fp8 block computes on the e4m3 bytes those codes stand for; the slim blocks and every other block
-        run what "fp8" runs."""
-        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4"):
-            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk', 'fp8-qat' or 'fp8-w4' "
-                             "(got %r)" % (precision,))
+        run what "fp8" runs.
+        "fp8-w4-qat" -- 4-bit quantisation-aware training: "fp8-qat" with the weights of every fp8 block in the
+        4-bit format -- in training mode every block of `fp8_layers` (`fp8_w4_layers` is the same list) re-quantises its weights
+        to codes, shifts and exponents every step and runs its forward on them (mcamd_conv_fwd_q8_w4_raw); the backward is
+        "fp8-qat"'s on the values the codes stand for.  An inference-mode forward is the "fp8-w4" engine's, bit for bit."""
+        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat"):
+            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk', 'fp8-qat', 'fp8-w4' or "
+                             "'fp8-w4-qat' (got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4")
+        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_choose_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4")
-        self.qat = precision == "fp8-qat"      # ... and their training-mode forward / straight-through backward
+        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat")
+        self.qat = precision in ("fp8-qat", "fp8-w4-qat")   # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
         # "fp8-2:4": the subset of fp8_layers whose masks conform to 2:4 and that run mcamd_conv_fwd_q8_sparse24
         self.q8_sparse = precision == "fp8-2:4"
@@ -392,8 +409,9 @@ class Engine:
         # mcamd_conv_fwd_q8_splitk (they share `_splitk_ws` below)
         self.q8_splitk = precision == "fp8-splitk"
         self.fp8_splitk_layers = []
-        # "fp8-w4": the subset of fp8_layers that run mcamd_conv_fwd_q8_w4 on 4-bit weights (every block of form "q8")
-        self.q8_w4 = precision == "fp8-w4"
+        # "fp8-w4" / "fp8-w4-qat": the subset of fp8_layers that run on 4-bit weights (every block of form "q8": all of them in
+        # a training engine, which has no slim blocks)
+        self.q8_w4 = precision in ("fp8-w4", "fp8-w4-qat")
         self.fp8_w4_layers = []
         self.qbufs = {}
         self._qld = {}                         # buffer id -> bytes per pixel of its byte buffer (_choose_q8)
@@ -1204,7 +1222,7 @@ class Engine:
         return self._qld[t.buf] if f8 else t.ld
 
     def _qat_train(self, lay):
-        """Does this block train in the fp8 arithmetic (a block of fp8_layers in an "fp8-qat" training engine)?"""
+        """Does this block train in the fp8 arithmetic (a block of fp8_layers in an "fp8-qat" / "fp8-w4-qat" training engine)?"""
         return self.qat and self.train_layout and lay.q8_on
 
     def qat_block_io(self, conv_number):
@@ -1213,7 +1231,8 @@ class Engine:
         `y` the fp32 raw output; batch `scale` / `shift` / `mean` / `invstd`; `out8` (`out2_8`) output codes where the
         destination is held as bytes, else None, and `out16` (`out2_16`) the fp16 buffer of the same tensor; `dst`;
         `dy` the gradient wrt y times grad_scale (after a backward); `w_q` the weights the dgrad operand was packed from,
-        `wexp` their exponents; `gin` the gradient wrt the block's input slice times grad_scale."""
+        `wexp` their exponents; `gin` the gradient wrt the block's input slice times grad_scale.  A 4-bit block ("fp8-w4-qat")
+        adds `codes` [cout][ktot / 2] and `gshift` [ktot / 64][cout][2], the packed operands of its forward (`wexp` = e4_f)."""
         lay = self.layers[conv_number - 1]
         if not self._qat_train(lay):
             raise McamdError("conv%d is not an fp8 block of an fp8-qat training engine (fp8_layers = %r)"
@@ -1230,9 +1249,13 @@ class Engine:
                    dst={L.DST_PLAIN: "plain", L.DST_POOL: "pool", L.DST_REORG: "reorg"}[lay.mode],
                    dy=ops.padded_view(lay.dy, B, lay.H, lay.W, lay.cout_p, lay.pad)[:, 1:-1, 1:-1, :lay.cout]
                    .permute(0, 3, 1, 2).contiguous().float().cpu(),
-                   w_q=lay.w_q.cpu(), wexp=lay.wexp[:lay.cout].cpu(),
+                   w_q=lay.w_q.cpu(), wexp=(lay.wexp4 if lay.form == "q8_w4" else lay.wexp)[:lay.cout].cpu(),
                    gin=lay.gin.view(B, lay.H, lay.W, ti.ld)[..., ti.choff:ti.choff + lay.cin].permute(0, 3, 1, 2)
                    .contiguous().float().cpu())
+        if lay.form == "q8_w4":
+            ktot, npad = lay.cin * lay.k * lay.k, ops.round_up(lay.cout, 256)
+            out["codes"] = lay.w4c.view(npad, ktot // 2)[:lay.cout].cpu()
+            out["gshift"] = lay.w4g.view(ktot // 64, npad, 2)[:, :lay.cout].contiguous().cpu()
         if t2 is not None:
             out["out2_8"] = interior(self.qbufs[t2.buf], True, t2, lay.cout) if lay.q8_y2 else None
             out["out2_16"] = interior(self.bufs[t2.buf], False, t2, lay.cout)
@@ -1764,8 +1787,8 @@ class Engine:
         return res
 
     def _qat_forward(self, lay, xin):
-        """Training-mode forward of an fp8 block ("fp8-qat"): the fp8 convolution's fp32 raw output and its
-        batch statistics, coefficients, then BatchNorm + LeakyReLU (+ pool / reorg / route) written as e4m3 codes into the
+        """Training-mode forward of an fp8 block ("fp8-qat"; "fp8-w4-qat", 3x): the fp8 convolution's fp32 raw
+        output and its batch statistics, coefficients, then BatchNorm + LeakyReLU (+ pool / reorg / route) written as e4m3 codes into the
         tensors the engine holds as bytes -- with the dequantised values in their fp16 buffers, which the backward pass
         reads -- and as fp16 elsewhere."""
         B, bn = self.B, lay.bn
@@ -1774,7 +1797,7 @@ class Engine:
             ti, x8 = lay.tin, lay.xq
             self._timed('cast', lay, ops.cast_q8, xin, ops.padded_pixels(B, ti.H, ti.W, self._pad_for(ti.W)), ti.ld, ti.choff,
                         lay.cin, x8, ti.ld, ti.choff, write_back=True)
-        self._timed('fwd', lay, ops.conv_fwd_q8_raw, lay.geom_act, x8, lay.wq, lay.wexp, lay.y, lay.cout, 0, lay.stats)
+        _FORMS[lay.form].qat_raw(self, lay, x8)     # (the raw forward of the block's form: fp8 bytes, or 4-bit codes)
         ops.bn_coeffs(lay.stats, lay.cout, lay.M, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, True,
                       lay.scale, lay.shift, lay.mean, lay.invstd, momentum=_momentum(bn), eps=bn.eps)
         t, t2 = lay.out_t, lay.out2_t

@@ -311,6 +311,10 @@ class Darknet(nn.Module):
         # "fp8-w4" (eval only, an opt-in): the "fp8" engine with the weights of every dense fp8 block held as 4-bit e2m1 codes
         # + one shift per group of 32 input channels, 4.25 bits per weight resident, expanded to e4m3 bytes in the kernel's
         # registers (engine.Engine.fp8_w4_layers, csrc/conv_q8_w4.hip); `sparse` and `splitk` stay off with it.
+        # "fp8-w4-qat" (an addition beyond the reference): 4-bit quantisation-aware training -- "fp8-qat" with the weights of every
+        # fp8 block re-quantised to the "fp8-w4" format every step: the training-mode forward multiplies the codes the block would
+        # be deployed with, the backward is straight-through on the values they stand for; in eval mode it is the "fp8-w4" engine,
+        # bit for bit.  The fine-tuning step in front of deployment under "fp8-w4"; `sparse` and `splitk` stay off.
         self.precision = os.environ.get("MCAMD_PRECISION", "auto")
         # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA

@@ -1392,6 +1392,33 @@ def conv_fwd_q8_w4(g, x8, codes, gshift, wexp, y, y_ld, y_choff=0, scale=None, s
                                        int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q8_w4")
 
 
+def conv_fwd_q8_w4_raw(g, x8, codes, gshift, wexp, y, y_ld, y_choff=0, stats=None):
+    """The training form of the 4-bit block (mcamd_conv_fwd_q8_w4_raw): conv_fwd_q8_raw's arguments with
+    pack_q8_w4's codes, shift bytes and exponents in place of the weight bytes; y[M][y_ld] fp32 = 2^-(e4_f + 1) x the sum of byte
+    products, `stats`: fp32 [conv_fwd_q8_stats_rows(g)][2][stats_ld] slab of the fp32 values, or None."""
+    e = _epi(L.EPI_RAW_F32, y, y_ld, y_choff, stats=stats,
+             stats_rows_=stats.shape[0] if stats is not None else 0,
+             stats_ld=stats.shape[2] if stats is not None else 0)
+    check(L.lib().mcamd_conv_fwd_q8_w4_raw(C.byref(g), ptr(x8), ptr(codes), ptr(gshift), ptr(wexp), C.byref(e), stream_ptr()),
+          "mcamd_conv_fwd_q8_w4_raw")
+
+
+def fakequant_q8_w4(g, codes, gshift, wexp, out=None):
+    """fp32 OIHW w_q = grid[code] * 2^g * 2^-e4_f decoded from pack_q8_w4's operands (mcamd_fakequant_q8_w4): the values the
+    4-bit forward multiplies."""
+    _need_cuda(codes, gshift, wexp)
+    nc, ng, ne = q8_w4_elems(g)
+    if codes.numel() < nc or gshift.numel() < ng or wexp.numel() < ne:
+        raise L.McamdError("fakequant_q8_w4: operand too small")
+    if out is None:
+        out = torch.empty(g.cout, g.cin, g.ksize, g.ksize, dtype=torch.float32, device=codes.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != g.cout * g.cin * g.ksize * g.ksize:
+        raise L.McamdError("fakequant_q8_w4: destination must be contiguous fp32 [cout][cin][k][k]")
+    check(L.lib().mcamd_fakequant_q8_w4(C.byref(g), ptr(codes), ptr(gshift), ptr(wexp), ptr(out), stream_ptr()),
+          "mcamd_fakequant_q8_w4")
+    return out
+
+
 # ----------------------------------------------------------------------------- compressed model files (.mcz, DESIGN.md 3s)
 WZ_ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1, L.WZ_CODE: 1}
 
