@@ -1238,11 +1238,29 @@ int mcamd_block_mask(const int32_t* keep, const float* old_mask, int32_t cout, i
  * bit words iff kept < n (a code cannot say "not kept", so the size rule of the other kinds does not apply).  The passes
  * see one byte per code: pack reads w = uint8 codes[n] and stores the kept ones by the same rule; unpack writes
  * w = uint8 codes[n] (0 where the bit is clear) and the mask.  A file whose header payload is MCAMD_WZ_CODE stores its
- * untied layers as MCAMD_WZ_FP32. */
+ * untied layers as MCAMD_WZ_FP32.
+ *
+ * A fifth kind stores a layer as the 4-bit engine consumes it (mcamd_pack_q8_w4 above), cin % 32 == 0:
+ *   MCAMD_WZ_W4    the 4-bit code of the weight (bit 3 sign, bits 0-2 grid index, never -0), 1 byte in the passes, one
+ *                  nibble in the file
+ * Behind the per-channel arrays its record carries int32 e4[cout], the filter exponents of mcamd_pack_q8_w4, and
+ * uint8 shift[n / 32], g + 5 (0..11) of every group of 32 input channels at one tap in the order [cout][cin / 32][kh][kw]
+ * (an all-zero group: byte 0); then the bit words, then the codes of the kept weights (or of all n, 0 where not kept) in
+ * flat OIHW order, code i in bits [4 (i % 2), +4) of byte i / 2, the unused nibble of the last byte 0.  Codes, shifts and
+ * exponents are exactly those of mcamd_pack_q8_w4 on the same weight * mask, in OIHW order instead of the kernel's tile
+ * layout.  A weight is KEPT iff code & 7 != 0; the record has bit words iff
+ * 8 ceil(n / 64) + ceil(kept / 2) < ceil(n / 2).  Reading: grid[code & 7] 2^(shift - 5 - e4) with the code's sign (exact
+ * in fp32 whenever that is a normal number); a shift byte above 11 reads as +0.  A file whose header payload is
+ * MCAMD_WZ_W4 stores its other layers as MCAMD_WZ_FP16.  The passes see one byte per code, as for MCAMD_WZ_CODE, through
+ * mcamd_wz_pack_w4 / mcamd_wz_unpack_w4 (below), which take the shift bytes as one more array. */
 #define MCAMD_WZ_FP32 0
 #define MCAMD_WZ_FP16 1
 #define MCAMD_WZ_FP8 2
 #define MCAMD_WZ_CODE 4 /* (3 is not a kind) */
+#define MCAMD_WZ_W4 5
+/* mcamd_wz_seg.kind of an MCAMD_WZ_W4 segment also carries the taps kh kw of its tensor (a group of 32 input channels is
+ * strided by them in OIHW); every other kind is the bare value */
+#define MCAMD_WZ_W4_KIND(taps) (MCAMD_WZ_W4 | (taps) << 8)
 #define MCAMD_WZ_F_BN 1u
 #define MCAMD_WZ_F_BITS 2u
 #define MCAMD_WZ_BLOCK_WORDS 64 /* bit words (of 64 weights) per workgroup of both passes */
@@ -1251,10 +1269,12 @@ int mcamd_block_mask(const int32_t* keep, const float* old_mask, int32_t cout, i
  * sizes and its DEVICE copy for the kernels.  Running sums over the table, in order (checked):
  *   block0  += ceil(ceil(n / 64) / MCAMD_WZ_BLOCK_WORDS)
  *   word0   += ceil(n / 64)     pack only
- *   exp0    += cout             pack only, the segments of kind MCAMD_WZ_FP8
- * Unpack reads the bit words, exponents and values where the caller has them: word0 (dense == 0), exp0 (MCAMD_WZ_FP8)
- * and val0 are any offsets whose range lies inside the arrays given (checked).  All three arrays may be one buffer
- * holding the file as it is, since every array of a record starts at a multiple of 8 bytes. */
+ *   exp0    += cout             pack only, the segments of kind MCAMD_WZ_FP8 and MCAMD_WZ_W4
+ *   shift0  += ceil(n / 256)    pack only, the segments of kind MCAMD_WZ_W4 (its n / 32 shift bytes, padded to 8)
+ * Unpack reads the bit words, exponents, shift bytes and values where the caller has them: word0 (dense == 0), exp0
+ * (MCAMD_WZ_FP8, MCAMD_WZ_W4), shift0 (MCAMD_WZ_W4) and val0 are any offsets whose range lies inside the arrays given
+ * (checked).  All the arrays may be one buffer holding the file as it is, since every array of a record starts at a
+ * multiple of 8 bytes. */
 typedef struct mcamd_wz_seg {
     void* w;         /* fp32 OIHW [cout][n / cout]: the master (pack, read) or the weights to fill (unpack, written);
                         MCAMD_WZ_CODE: uint8 codes [n] */
@@ -1264,11 +1284,11 @@ typedef struct mcamd_wz_seg {
     int64_t val0;    /* unpack: byte offset of the segment's values in `values`, a multiple of 8.  pack: unused */
     int64_t kept;    /* unpack, dense == 0: number of values stored (<= n).  pack: unused */
     int32_t cout;
-    int32_t kind;    /* MCAMD_WZ_FP32 / _FP16 / _FP8 / _CODE */
+    int32_t kind;    /* MCAMD_WZ_FP32 / _FP16 / _FP8 / _CODE, or MCAMD_WZ_W4_KIND(kh kw) */
     int32_t exp0;    /* first exponent of the segment in `exps` */
     int32_t dense;   /* unpack: 1 = the record has no bit words, all n values are stored.  pack: unused */
     int32_t block0;  /* first workgroup of the segment */
-    int32_t reserved;
+    int32_t shift0;  /* MCAMD_WZ_W4: first shift byte of the segment in `shifts`, in units of 8 bytes.  Otherwise unused */
 } mcamd_wz_seg;
 
 /* workspace of either pass for a table of `nseg` segments and `nblocks` workgroups (the final block0 sum) */
@@ -1292,6 +1312,24 @@ int mcamd_wz_pack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_
 int mcamd_wz_unpack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, const uint64_t* words,
                     int64_t words_cap, const int32_t* exps, int64_t exps_cap, const void* values, int64_t values_bytes,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* The two passes for a table that may hold MCAMD_WZ_W4 segments (any other kind as above, and a table without one gives
+ * the bytes of mcamd_wz_pack / mcamd_wz_unpack).  `shifts` holds the shift bytes, segment s at byte 8 shift0.
+ * Pack: a pre-pass (one workgroup per filter) takes the filter maximum and from it e4_f (exps[exp0 ...]), then the maxima
+ * of the filter's groups and from them the shift bytes; in the word and scatter passes each lane derives its own code from
+ * its weight, its filter's e4_f and its group's shift by the rule of mcamd_pack_q8_w4 (csrc/w4_quant.h, one statement for
+ * both).  The values of an MCAMD_WZ_W4 segment are one byte per code, bytes(t) = (bit words ? kept : n), bit words iff
+ * 8 ceil(n / 64) + ceil(kept / 2) < ceil(n / 2); the caller packs two codes into a byte for the file.  shifts_cap >= the
+ * final shift0 sum * 8 (checked); the padding bytes are not written: zero `shifts` first.
+ * Unpack: w[i] = grid[code & 7] 2^(shift - 5 - e4_f) with the code's sign and the mask as above, from one byte per code at
+ * val0 (the caller widens the file's nibbles).  A shift byte above 11 and a code position past `kept` read as +0; every
+ * offset is checked against the capacities given before the launch. */
+int mcamd_wz_pack_w4(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, uint64_t* words, int64_t words_cap,
+                     uint64_t* counts, int32_t* exps, int64_t exps_cap, void* values, int64_t values_bytes, void* workspace,
+                     size_t workspace_bytes, void* stream, uint8_t* shifts, int64_t shifts_cap);
+int mcamd_wz_unpack_w4(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, const uint64_t* words,
+                       int64_t words_cap, const int32_t* exps, int64_t exps_cap, const void* values, int64_t values_bytes,
+                       void* workspace, size_t workspace_bytes, void* stream, const uint8_t* shifts, int64_t shifts_cap);
 
 /* ------------------------------------------------------------------------- *
  * Weight sharing (trained quantisation by k-means; an addition beyond the reference).

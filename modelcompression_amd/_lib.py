@@ -163,7 +163,7 @@ class WzSeg(C.Structure):
     """mcamd_wz_seg (include/mcamd.h)."""
     _fields_ = [("w", C.c_void_p), ("mask", C.c_void_p), ("n", C.c_int64), ("word0", C.c_int64), ("val0", C.c_int64),
                 ("kept", C.c_int64), ("cout", C.c_int32), ("kind", C.c_int32), ("exp0", C.c_int32), ("dense", C.c_int32),
-                ("block0", C.c_int32), ("reserved", C.c_int32)]
+                ("block0", C.c_int32), ("shift0", C.c_int32)]
 
 
 class WsSeg(C.Structure):
@@ -179,7 +179,7 @@ WFIN_ROW, WFIN_VEC, WFIN_GENERIC = 0, 1, 2                                      
 WGRAD_PLAN_INFO_N = 13
 STEM_PLAN_FWD, STEM_PLAN_FWD_PLANES, STEM_PLAN_STATS, STEM_PLAN_GRAM, STEM_PLAN_BWD = 0, 1, 2, 3, 4    # mcamd_stem_block_plan_info
 STEM_PLAN_INFO_N = 20
-WZ_FP32, WZ_FP16, WZ_FP8, WZ_CODE = 0, 1, 2, 4                                         # mcamd_wz_seg.kind
+WZ_FP32, WZ_FP16, WZ_FP8, WZ_CODE, WZ_W4 = 0, 1, 2, 4, 5                               # mcamd_wz_seg.kind (WZ_W4: | taps << 8)
 WZ_F_BN, WZ_F_BITS = 1, 2                                                              # record flags of a .mcz file
 WZ_BLOCK_WORDS = 64
 WS_SLAB = 4096                                                                         # MCAMD_WS_SLAB
@@ -307,6 +307,8 @@ SIGNATURES = {
     "mcamd_wz_workspace_bytes": (_SZ, [_I64, _I32]),
     "mcamd_wz_pack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P, _SZ, _P]),
     "mcamd_wz_unpack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "mcamd_wz_pack_w4": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P, _SZ, _P, _P, _I64]),
+    "mcamd_wz_unpack_w4": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P, _P, _I64]),
     "mcamd_ws_workspace_bytes": (_SZ, [_I64, _I64, _I32]),
     "mcamd_ws_init": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _SZ, _P]),
     "mcamd_ws_iterate": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _SZ, _P]),

@@ -5,12 +5,18 @@ a bitmask of the non-zero weights and only those weights, as fp32, fp16 or e4m3 
 is written for consumes, so the file is lossless for that engine:
 
     save_compressed(model, path, payload="fp16", layers=None)       # payload "shared": codebooks + narrow codes (below)
+                                                                    # payload "w4": what the "fp8-w4" engine consumes (below)
     load_compressed(model, path, set_masks=True) -> masks
     compressed_info(path) -> dict
 
 Payload "shared"  stores every layer Darknet.set_codebooks tied as the bitmask of its MASK, its fp32 codebook
 and one code of 1, 2, 4 or 8 bits per kept weight, and every other layer as fp32; reading it gives back the tied model's
 fp32 weights exactly, with its masks and codebooks.
+
+Payload "w4"  stores the layers the "fp8-w4" engine runs in its 4-bit format as that format: one exponent per
+filter, one shift byte per group of 32 input channels at one tap and one 4-bit code per weight -- the codes, shifts and exponents
+of mcamd_pack_q8_w4, in OIHW order -- and every other layer as fp16.  Reading it gives fp32 masters grid[code] 2^g 2^-e4_f, which
+the engine's packer turns back into the same expanded e4m3 bytes: the file is lossless for that engine.
 
 A model on the GPU is packed and expanded by the device passes of csrc/wpack.hip (ops.wz_pack / ops.wz_unpack: all layers
 through one segment table); a model on the CPU takes the torch / numpy path below, which writes and reads the same bytes.
@@ -26,11 +32,14 @@ from ._lib import McamdError
 
 MAGIC = b"MCZW"
 VERSION = 1
-PAYLOADS = {"fp32": L.WZ_FP32, "fp16": L.WZ_FP16, "fp8": L.WZ_FP8, "shared": L.WZ_CODE}
+PAYLOADS = {"fp32": L.WZ_FP32, "fp16": L.WZ_FP16, "fp8": L.WZ_FP8, "shared": L.WZ_CODE, "w4": L.WZ_W4}
 KIND_NAMES = {v: k for k, v in PAYLOADS.items()}
-ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1, L.WZ_CODE: 1}      # (WZ_CODE: in the device passes; `width` bits in the file)
-_CODE_DTYPE = {L.WZ_FP32: "<u4", L.WZ_FP16: "<u2", L.WZ_FP8: "u1", L.WZ_CODE: "u1"}
-_MAG_BITS = {L.WZ_FP32: 0x7FFFFFFF, L.WZ_FP16: 0x7FFF, L.WZ_FP8: 0x7F}
+# (WZ_CODE, WZ_W4: one byte per code in the device passes; `width` / 4 bits in the file)
+ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1, L.WZ_CODE: 1, L.WZ_W4: 1}
+_CODE_DTYPE = {L.WZ_FP32: "<u4", L.WZ_FP16: "<u2", L.WZ_FP8: "u1", L.WZ_CODE: "u1", L.WZ_W4: "u1"}
+_MAG_BITS = {L.WZ_FP32: 0x7FFFFFFF, L.WZ_FP16: 0x7FFF, L.WZ_FP8: 0x7F, L.WZ_W4: 0x7}
+_W4_GRID = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=np.float64)
+_W4_SHIFT_MAX = 11                           # shift bytes are g + 5, g in [-5, 6]
 _HEADER = struct.Struct("<4sIIIq")          # magic, version, payload, records, seen
 _RECORD = struct.Struct("<4iIIQ")           # cout, cin, kh, kw, flags, bits (WZ_CODE; 0 otherwise), kept
 
@@ -41,9 +50,11 @@ def _pad8(nbytes):
 
 def has_bits(n, kept, kind):
     """The bitmask-or-dense rule: a record carries bit words only when that is smaller.  A record of codes carries them
-    whenever a weight is not kept: a code cannot say so."""
+    whenever a weight is not kept: a code cannot say so.  A 4-bit record counts its nibbles."""
     if kind == L.WZ_CODE:
         return kept < n
+    if kind == L.WZ_W4:
+        return 8 * ((n + 63) // 64) + (kept + 1) // 2 < (n + 1) // 2
     return 8 * ((n + 63) // 64) + kept * ELEM[kind] < n * ELEM[kind]
 
 
@@ -130,6 +141,28 @@ def _codes_cpu(w, mask, kind):
     return scaled.to(torch.float8_e4m3fn).contiguous().view(torch.uint8).numpy().reshape(-1), e.numpy().astype("<i4")
 
 
+def _codes_w4_cpu(w, mask):
+    """(codes uint8 flat OIHW, e4 int32 [cout], shift bytes uint8 flat [cout][cin / 32][kh][kw]) of weight * mask: the steps of
+    mcamd_pack_q8_w4 (csrc/w4_quant.h) on exact float64 values."""
+    wm = w.detach().float() * mask.float() if mask is not None else w.detach().float() * 1.0
+    cout, cin, kh, kw = wm.shape
+    a = wm.abs().flatten(1).amax(1)
+    m, x = torch.frexp(a)
+    e = torch.where(m <= 0.875, 9 - x, 8 - x) - 1
+    e = torch.where(a == 0, torch.zeros_like(e), e).to(torch.int32)
+    s = wm.double() * torch.pow(2.0, e.double()).view(-1, 1, 1, 1)
+    amax = s.abs().view(cout, cin // 32, 32, kh, kw).amax(2)
+    gm, gx = torch.frexp(amax)
+    g = torch.where(gm <= 0.75, gx - 3, gx - 2).clamp(-5, 6)
+    g = torch.where(amax == 0, torch.full_like(g, -5), g)
+    step = torch.pow(2.0, g.double()).unsqueeze(2).expand(cout, cin // 32, 32, kh, kw).reshape(cout, cin, kh, kw)
+    v = (s.abs() / step).clamp(max=6.0)
+    # round to nearest onto the grid, ties to the even code (torch.round: half to even)
+    c = torch.where(v < 2, torch.round(2 * v), torch.where(v < 4, torch.round(v) + 2, torch.round(0.5 * v) + 4)).long()
+    c = c | (((s < 0) & (c != 0)).long() << 3)
+    return (c.to(torch.uint8).numpy().reshape(-1), e.numpy().astype("<i4"), (g + 5).to(torch.uint8).numpy().reshape(-1))
+
+
 def _encode_shared_cpu(codes, mask):
     codes = codes.detach().cpu().numpy().reshape(-1)
     n = codes.size
@@ -144,7 +177,11 @@ def _encode_shared_cpu(codes, mask):
 
 
 def _encode_cpu(w, mask, kind):
-    codes, exps = _codes_cpu(w, mask, kind)
+    shifts = None
+    if kind == L.WZ_W4:
+        codes, exps, shifts = _codes_w4_cpu(w, mask)
+    else:
+        codes, exps = _codes_cpu(w, mask, kind)
     n = codes.size
     keep = (codes & codes.dtype.type(_MAG_BITS[kind])) != 0
     kept = int(keep.sum())
@@ -156,7 +193,7 @@ def _encode_cpu(w, mask, kind):
     else:
         words = None
         values = np.where(keep, codes, codes.dtype.type(0))
-    return dict(kept=kept, exps=exps, words=words, values=np.ascontiguousarray(values))
+    return dict(kept=kept, exps=exps, shifts=shifts, words=words, values=np.ascontiguousarray(values))
 
 
 def _check_words(rec, what):
@@ -188,12 +225,19 @@ def _decode_cpu(rec, what):
         bits = np.unpackbits(rec["words"].view(np.uint8), bitorder="little")
         keep = bits[:n].astype(bool)
         codes = np.zeros(n, dtype=dt)
-        codes[keep] = rec["values"]
+        codes[keep] = rec["codes"] if kind == L.WZ_W4 else rec["values"]
         mask = keep.astype(np.float32)
     else:
-        codes = rec["values"]
+        codes = rec["codes"] if kind == L.WZ_W4 else rec["values"]
         mask = np.ones(n, dtype=np.float32)
     nz = (codes & dt.type(_MAG_BITS[kind])) != 0
+    if kind == L.WZ_W4:                       # grid[code & 7] 2^(shift - 5 - e4_f), signed by bit 3: exact in float64, then in fp32
+        cout, cin, kh, kw = rec["shape"]
+        g = rec["shifts"].astype(np.int64).reshape(cout, cin // 32, 1, kh, kw) - 5
+        g = np.broadcast_to(g, (cout, cin // 32, 32, kh, kw)).reshape(cout, -1)
+        c = codes.reshape(cout, -1)
+        w = np.ldexp(_W4_GRID[c & 7], g - rec["exps"].astype(np.int64).reshape(-1, 1)) * np.where(c & 8, -1.0, 1.0)
+        return np.where(nz, w.reshape(-1), 0.0).astype(np.float32), mask
     if kind == L.WZ_FP32:
         w = codes.view("<f4")
     elif kind == L.WZ_FP16:
@@ -213,14 +257,19 @@ def _kinds(model, payload, layers):
     kind = PAYLOADS[payload]
     if kind == L.WZ_CODE:         # the layers set_codebooks tied as codes, every other layer as it is
         return convs, [L.WZ_CODE if getattr(conv, "share_flag", False) else L.WZ_FP32 for _, conv, _ in convs]
-    if kind != L.WZ_FP8:
+    if kind not in (L.WZ_FP8, L.WZ_W4):
         return convs, [kind] * len(convs)
     chosen = set(default_fp8_layers(model) if layers is None else [int(i) for i in layers])
     bad = sorted(chosen - set(i for i, _, _ in convs))
     if bad:
         raise McamdError("layers names conv numbers the model does not have: %r" % bad)
-    # every other layer of an fp8 file is what the "fp8" engine runs there: fp16
-    return convs, [L.WZ_FP8 if i in chosen else L.WZ_FP16 for i, _, _ in convs]
+    if kind == L.WZ_W4:
+        for i, conv, _ in convs:
+            if i in chosen and conv.weight.shape[1] % 32:
+                raise McamdError("conv%d has %d input channels: a layer of a \"w4\" file is stored in groups of 32 input channels"
+                                 % (i, conv.weight.shape[1]))
+    # every other layer of an fp8 / w4 file is what the "fp8" / "fp8-w4" engine runs there: fp16
+    return convs, [kind if i in chosen else L.WZ_FP16 for i, _, _ in convs]
 
 
 def _mask_of(conv):
@@ -239,24 +288,28 @@ def _encode_device(convs, kinds):
         if w.dtype != torch.float32:
             raise McamdError("compressed model files are written from fp32 master weights")
         items.append(dict(w=w.contiguous(), mask=m.contiguous().float() if m is not None else None, kind=kind))
-    words, counts, exps, values = ops.wz_pack(items)
+    words, counts, exps, values, *shifts = ops.wz_pack(items)
     counts = [int(c) for c in counts.cpu().numpy().view("<u8")]                # the one synchronising read
     words, exps = words.cpu().numpy().view("<u8"), exps.cpu().numpy().astype("<i4", copy=False)
+    shifts = shifts[0].cpu().numpy() if shifts else None
     sizes = []
     for it, kind, kept in zip(items, kinds, counts):
         n = it["w"].numel()
         sizes.append((kept if has_bits(n, kept, kind) else n) * ELEM[kind])
     values = values[:sum(_pad8(s) for s in sizes)].cpu().numpy()
-    out, w0, e0, v0 = [], 0, 0, 0
+    out, w0, e0, v0, s0 = [], 0, 0, 0, 0
     for it, kind, kept, size in zip(items, kinds, counts, sizes):
         n, cout = it["w"].numel(), it["w"].shape[0]
         nwords = (n + 63) // 64
-        rec = dict(kept=kept, exps=None, words=None, values=values[v0:v0 + size].view(_CODE_DTYPE[kind]))
+        rec = dict(kept=kept, exps=None, shifts=None, words=None, values=values[v0:v0 + size].view(_CODE_DTYPE[kind]))
         if has_bits(n, kept, kind):
             rec["words"] = words[w0:w0 + nwords]
-        if kind == L.WZ_FP8:
+        if kind in (L.WZ_FP8, L.WZ_W4):
             rec["exps"] = exps[e0:e0 + cout]
             e0 += cout
+        if kind == L.WZ_W4:
+            rec["shifts"] = shifts[s0:s0 + n // 32]
+            s0 += _pad8(n // 32)
         w0 += nwords
         v0 += _pad8(size)
         out.append(rec)
@@ -271,9 +324,11 @@ def _write_array(f, a):
 
 def save_compressed(model, path, payload="fp16", layers=None):
     """Write `model` as an .mcz file.  payload: "fp32" (bit patterns of weight * mask), "fp16" (what the fp16 engines
-    consume) or "fp8" (the conv numbers in `layers` as e4m3 codes + one exponent per filter, every other layer as fp16;
-    `layers` defaults to default_fp8_layers(model), pass Engine.fp8_layers to be exact for any cfg).  A weight is stored
-    iff its value in the payload is non-zero."""
+    consume), "fp8" (the conv numbers in `layers` as e4m3 codes + one exponent per filter, every other layer as fp16;
+    `layers` defaults to default_fp8_layers(model), pass Engine.fp8_layers to be exact for any cfg) or "w4" (the conv numbers
+    in `layers` as 4-bit codes + one shift byte per group of 32 input channels + one exponent per filter, every other layer
+    as fp16; the same default, pass Engine.fp8_w4_layers to be exact for any cfg; a chosen layer needs cin % 32 == 0).  A weight
+    is stored iff its value in the payload is non-zero."""
     convs, kinds = _kinds(model, payload, layers)
     if not convs:
         raise McamdError("the model has no convolutional block to store")
@@ -294,13 +349,16 @@ def save_compressed(model, path, payload="fp16", layers=None):
             f.write(_RECORD.pack(cout, cin, kh, kw, flags, bits, rec["kept"]))
             for a in _small_arrays(conv, bn):
                 _write_array(f, a)
-            if kind == L.WZ_FP8:
+            if kind in (L.WZ_FP8, L.WZ_W4):
                 _write_array(f, rec["exps"].astype("<i4", copy=False))
+            if kind == L.WZ_W4:
+                _write_array(f, rec["shifts"])
             if kind == L.WZ_CODE:
                 _write_array(f, conv.codebook.detach().cpu().numpy().astype("<f4", copy=False))
             if rec["words"] is not None:
                 _write_array(f, rec["words"])
-            _write_array(f, _pack_codes(rec["values"], code_width(bits)) if kind == L.WZ_CODE else rec["values"])
+            width = code_width(bits) if kind == L.WZ_CODE else 4 if kind == L.WZ_W4 else 8
+            _write_array(f, _pack_codes(rec["values"], width) if width < 8 else rec["values"])
 
 
 def _parse(path, payload=True):
@@ -345,20 +403,30 @@ def _parse_open(f, path, size, payload):
             raise McamdError("%s: %s: damaged record header" % (path, what))
         if kind == L.WZ_CODE and (pay != L.WZ_CODE or not 1 <= cbits <= 8):
             raise McamdError("%s: %s: damaged record header (codes of %d bits in a %r file)" % (path, what, cbits, KIND_NAMES[pay]))
+        if kind == L.WZ_W4 and (pay != L.WZ_W4 or cin % 32):
+            raise McamdError("%s: %s: damaged record header (4-bit codes of %d input channels in a %r file)" % (path, what, cin,
+                                                                                                            KIND_NAMES[pay]))
         n = cout * cin * kh * kw
         bits = bool(flags & L.WZ_F_BITS)
         if kept > n or bits != has_bits(n, kept, kind):
             raise McamdError("%s: %s: damaged record header (kept %d of %d weights)" % (path, what, kept, n))
         rec = dict(shape=(cout, cin, kh, kw), cout=cout, n=n, bn=bool(flags & L.WZ_F_BN), bits=bits, kind=kind, kept=kept,
-                   small=[], exps=None, words=None, values=None, exp0=0, word0=0, code_bits=None, codebook=None, codes=None)
+                   small=[], exps=None, words=None, values=None, exp0=0, word0=0, code_bits=None, codebook=None, codes=None,
+                   shifts=None, shift0=0)
         for _ in range(4 if rec["bn"] else 1):
             o = take(_pad8(4 * cout), what + " per-channel arrays")
             if raw is not None:
                 rec["small"].append(np.frombuffer(raw, "<f4", cout, o))
-        if kind == L.WZ_FP8:
+        if kind in (L.WZ_FP8, L.WZ_W4):
             o = rec["exp0"] = take(_pad8(4 * cout), what + " exponents")
             if raw is not None:
                 rec["exps"] = np.frombuffer(raw, "<i4", cout, o)
+        if kind == L.WZ_W4:
+            o = rec["shift0"] = take(_pad8(n // 32), what + " group shifts")
+            if raw is not None:
+                rec["shifts"] = np.frombuffer(raw, "u1", n // 32, o)
+                if int(rec["shifts"].max()) > _W4_SHIFT_MAX:
+                    raise McamdError("%s: %s: a group shift byte of %d (0..%d)" % (path, what, int(rec["shifts"].max()), _W4_SHIFT_MAX))
         if kind == L.WZ_CODE:
             rec["code_bits"] = cbits
             o = take(_pad8(4 << cbits), what + " codebook")
@@ -379,6 +447,17 @@ def _parse_open(f, path, size, payload):
                 if stored and int(rec["codes"].max()) >= 1 << cbits:
                     raise McamdError("%s: %s: a code of %d with a codebook of %d entries" % (path, what, int(rec["codes"].max()),
                                                                                           1 << cbits))
+        elif kind == L.WZ_W4:
+            nbytes = (stored + 1) // 2
+            rec["val0"] = take(_pad8(nbytes), what + " codes")
+            if raw is not None:
+                rec["values"] = np.frombuffer(raw, "u1", nbytes, rec["val0"])
+                rec["codes"] = _unpack_codes(rec["values"], 4, stored)
+                if stored % 2 and int(rec["values"][-1]) >> 4:
+                    raise McamdError("%s: %s: the unused nibble behind the last code is not 0" % (path, what))
+                # a kept weight has a non-zero grid index, every other stored code is +0
+                if int(np.count_nonzero(rec["codes"] & 7)) != kept or bool((rec["codes"] == 8).any()):
+                    raise McamdError("%s: %s: the codes stored do not hold the %d kept weights" % (path, what, kept))
         else:
             rec["val0"] = take(_pad8(stored * ELEM[kind]), what + " values")
             if raw is not None:
@@ -391,9 +470,9 @@ def _parse_open(f, path, size, payload):
 
 
 def load_compressed(model, path, set_masks=True):
-    """Fill `model` from an .mcz file: fp32 master weights (fp32 as is, fp16 widened, e4m3 as value 2^-exponent), BatchNorm
-    tensors, biases and `seen`.  Every record's shape is checked against the cfg before anything is written.  Returns the
-    list of kept-bit masks (all ones for a record without a bitmask) and, when `set_masks` and at least one record has a
+    """Fill `model` from an .mcz file: fp32 master weights (fp32 as is, fp16 widened, e4m3 as value 2^-exponent,
+    4-bit codes as grid[code] 2^g 2^-e4_f), BatchNorm tensors, biases and `seen`.  Every record's shape is checked against
+    the cfg before anything is written.  Returns the list of kept-bit masks (all ones for a record without a bitmask) and, when `set_masks` and at least one record has a
     bitmask, hands it to model.set_masks.  A "shared" file: the codes are widened on the host, expanded
     through the codebooks on the device (ops.WsTable.expand), and -- with `set_masks` -- the codebooks are set as
     Darknet.set_codebooks sets them, so that retraining and save_compressed(payload="shared") go on from the file."""
@@ -427,15 +506,19 @@ def load_compressed(model, path, set_masks=True):
                 buf += b + b"\0" * (_pad8(len(b)) - len(b))
                 shared.append(s)
                 books[s] = (torch.from_numpy(rec["codebook"].astype(np.float32)).to(dev), target)
+            if rec["kind"] == L.WZ_W4:               # one byte per code too; the exponents and shift bytes are read in place
+                val0 = len(buf)
+                b = rec["codes"].tobytes()
+                buf += b + b"\0" * (_pad8(len(b)) - len(b))
             items.append(dict(w=target, mask=masks[-1], kind=rec["kind"], dense=not rec["bits"], kept=rec["kept"],
-                              val0=val0, word0=rec["word0"] // 8, exp0=rec["exp0"] // 4))
+                              val0=val0, word0=rec["word0"] // 8, exp0=rec["exp0"] // 4, shift0=rec["shift0"] // 8))
         if len(buf) >= 1 << 33:
             raise McamdError("%s: a file of 8 GiB or more is not read on the device" % path)
         # the file's bytes go up once, as they are, and are expanded next to the weights: a record's bit words, exponents
         # and values are read in place (every array of the file starts at a multiple of 8 bytes)
         values = torch.frombuffer(buf, dtype=torch.uint8).to(dev)
         words, exps = values.view(torch.int64), values.view(torch.int32)
-        ops.wz_unpack(items, words, exps, values)
+        ops.wz_unpack(items, words, exps, values, values)
         if shared:
             table = ops.WsTable([dict(w=convs[s][1].weight.data, mask=masks[s] if recs[s]["bits"] else None, codes=books[s][1],
                                       K=1 << recs[s]["code_bits"]) for s in shared],

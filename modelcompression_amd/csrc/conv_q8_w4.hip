@@ -27,6 +27,7 @@
 #include "kernels.h"
 #include "conv_epi.h"
 #include "q8_exp.h"
+#include "w4_quant.h"
 
 // e4m3 magnitudes of the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6} * 2^-5: entries 0-3 (v_perm's second source), 4-7 (its first)
 constexpr unsigned W4_TLO = 0x14100800u, W4_THI = 0x24201c18u;
@@ -316,27 +317,7 @@ int mcamd_conv_q8_w4_raw_launch(IgemmArgs& a, const void* gshift, const void* we
 // the lane-local order of a chunk's k: piece h (16 code bytes), t in [0, 32) -> position in the 64-k chunk
 __device__ __forceinline__ int w4_kk(int h, int t) { return t < 16 ? 16 * h + t : 32 + 16 * h + (t - 16); }
 
-// Smallest g in [-5, 6] with amax <= 6 * 2^g (-5 for amax == 0), integer steps as q8_filter_exponent: (m, x) = frexp(amax),
-// 6 * 2^g = 0.75 * 2^(g + 3), so g = x - 3 if m <= 0.75 else x - 2.
-__device__ __forceinline__ int w4_group_shift(float amax) {
-    if (!(amax > 0.f)) return -5;
-    int x;
-    const float m = frexpf(amax, &x);
-    const int g = m <= 0.75f ? x - 3 : x - 2;
-    return g < -5 ? -5 : g > 6 ? 6 : g;
-}
-
-// s (the scaled weight) -> its 4-bit code under shift g: round to nearest onto the e2m1 grid, ties to the even mantissa bit
-// (rintf on 2 v / v / v / 2: an even integer there is a code with mantissa bit 0); above 6 saturates; a zero magnitude
-// carries no sign bit.
-__device__ __forceinline__ unsigned w4_code(float s, int g) {
-    const float v = fminf(ldexpf(fabsf(s), -g), 6.f);
-    unsigned c;
-    if (v < 2.f) c = (unsigned)rintf(2.f * v);               // 0, 0.5, 1, 1.5, (2)
-    else if (v < 4.f) c = (unsigned)rintf(v) + 2u;           // 2, 3, (4)
-    else c = (unsigned)rintf(0.5f * v) + 4u;                 // 4, 6
-    return (c != 0u && s < 0.f) ? (c | 8u) : c;
-}
+// (the shift rule w4_group_shift and the round-to-grid step w4_code: w4_quant.h, shared with wpack.hip)
 
 // One workgroup per row n < Npad.  The exponent is pack_q8_kernel's minus one (0 for an all-zero filter).  Then the row is
 // walked four chunks at a time, every weight read once: thread t stages the scaled w * mask of position t of the 256 (packed
@@ -363,7 +344,7 @@ __global__ __launch_bounds__(256) void pack_q8_w4_kernel(const float* __restrict
         __syncthreads();
     }
     amax = red[0];
-    const int e4 = amax > 0.f ? q8_filter_exponent(amax) - 1 : 0;
+    const int e4 = w4_filter_exponent(amax);
     if (tid == 0) wexp[n] = e4;
     for (int q0 = 0; q0 < nchunks; q0 += 4) {                    // (uniform over the workgroup: the barriers below)
         {
@@ -457,9 +438,7 @@ __global__ __launch_bounds__(256) void fakequant_q8_w4_kernel(const unsigned cha
     const unsigned code = r >= 4 ? byte >> 4 : byte & 15u;
     const int g = (int)gshift[((long long)q * npad + n) * 2 + j] - 5;
     const unsigned m = code & 7u;
-    // grid[m]: {0, 0.5, 1, 1.5} = m / 2, {2, 3, 4, 6} = (2 + m % 2) << (m - 4) / 2
-    const float mag = m < 4u ? 0.5f * (float)m : (float)((2u + (m & 1u)) << ((m - 4u) >> 1));
-    const float v = ldexpf(mag, g - wexp[n]);                              // exact: a power of two
+    const float v = ldexpf(w4_grid(m), g - wexp[n]);                       // exact: a power of two
     out[s] = m == 0u ? 0.f : ((code & 8u) ? -v : v);
 }
 

@@ -1,10 +1,11 @@
-// The two device passes around a compressed model file (.mcz, include/mcamd.h, DESIGN.md 3s) for gfx950, wave64.
+// The two device passes around a compressed model file (.mcz, include/mcamd.h, DESIGN.md 3s, 3y) for gfx950, wave64.
 //
-// pack    fp32 OIHW masters (* masks) of ALL layers, one segment table -> bit words, kept counts, fp8 exponents and the
-//         compacted values in the file's own layout.  Launches: [exponents] -> words + workgroup counts -> scan -> scatter.
-// unpack  bit words + compacted values (+ exponents) -> fp32 OIHW weights and, optionally, the fp32 0/1 masks.
-//         Launches: workgroup counts -> scan -> expand.  The words, exponents and values are read where the caller has
-//         them (word0 / exp0 / val0 are offsets it gives), so a whole file uploaded once serves as all three arrays.
+// pack    fp32 OIHW masters (* masks) of ALL layers, one segment table -> bit words, kept counts, fp8 / 4-bit exponents, 4-bit
+//         group shifts and the compacted values in the file's own layout.  Launches: [exponents + shifts] -> words +
+//         workgroup counts -> scan -> scatter.
+// unpack  bit words + compacted values (+ exponents, shifts) -> fp32 OIHW weights and, optionally, the fp32 0/1 masks.
+//         Launches: workgroup counts -> scan -> expand.  The words, exponents, shifts and values are read where the caller
+//         has them (word0 / exp0 / shift0 / val0 are offsets it gives), so a whole file uploaded once serves as every array.
 //
 // One wave handles one word of 64 consecutive weights: each lane converts its weight, the wave ballot of "my code is
 // non-zero" IS the word, and a lane's rank among the kept values of the word is the population count of the word below the
@@ -14,6 +15,7 @@
 // throughout; 64-bit element offsets.
 #include "common.h"
 #include "q8_exp.h"
+#include "w4_quant.h"
 
 constexpr int WZ_BW = MCAMD_WZ_BLOCK_WORDS;      // words per workgroup
 constexpr int WZ_WAVES = 4;                      // 256 threads
@@ -43,6 +45,19 @@ extern "C" size_t mcamd_wz_workspace_bytes(int64_t nblocks, int32_t nseg) {
     return (size_t)nblocks * (sizeof(u64) + sizeof(unsigned)) + (size_t)nseg * (sizeof(u64) + sizeof(int)) + 16;
 }
 
+// an MCAMD_WZ_W4 segment's kind carries its taps (MCAMD_WZ_W4_KIND): take them off, leaving the bare kind in the copy
+__device__ __forceinline__ int wz_taps(mcamd_wz_seg& g) {
+    const int taps = g.kind >> 8;
+    g.kind &= 0xff;
+    return taps;
+}
+
+// MCAMD_WZ_W4: the group of weight i in the order [cout][cin / 32][kh][kw] (per = cin * taps weights per filter)
+__device__ __forceinline__ long long wz_w4_group(long long i, long long per, int taps) {
+    const long long f = i / per, r = i - f * per, c = r / taps, tap = r - c * taps;
+    return f * (per / 32) + (c >> 5) * taps + tap;
+}
+
 __device__ __forceinline__ int wz_elem(int kind) { return kind == MCAMD_WZ_FP32 ? 4 : kind == MCAMD_WZ_FP16 ? 2 : 1; }
 
 // the code of weight * mask in the segment's value kind (e: the filter's exponent, fp8 only)
@@ -57,7 +72,7 @@ __device__ __forceinline__ unsigned wz_code(int kind, float wm, int e) {
 
 // kept: any bit outside the sign bit
 __device__ __forceinline__ bool wz_kept(int kind, unsigned code) {
-    return (code & (kind == MCAMD_WZ_FP32 ? 0x7fffffffu : kind == MCAMD_WZ_FP16 ? 0x7fffu : 0x7fu)) != 0u;
+    return (code & (kind == MCAMD_WZ_FP32 ? 0x7fffffffu : kind == MCAMD_WZ_FP16 ? 0x7fffu : kind == MCAMD_WZ_W4 ? 0x7u : 0x7fu)) != 0u;
 }
 
 __device__ __forceinline__ float wz_value(int kind, unsigned code, int e) {
@@ -90,15 +105,24 @@ __device__ __forceinline__ float wz_masked(const mcamd_wz_seg& g, long long i) {
     return ((const float*)g.w)[i] * (m ? m[i] : 1.f);
 }
 
+// the exponent of weight i's filter (MCAMD_WZ_FP8, MCAMD_WZ_W4) and the shift byte of its group (MCAMD_WZ_W4); 0 otherwise
+__device__ __forceinline__ void wz_scales(const mcamd_wz_seg& g, int taps, long long per, long long i, const int* __restrict__ exps,
+                                          const unsigned char* __restrict__ shifts, int* e, int* sh) {
+    const bool w4 = g.kind == MCAMD_WZ_W4;
+    *e = (w4 || g.kind == MCAMD_WZ_FP8) ? exps[g.exp0 + (int)(i / per)] : 0;
+    *sh = w4 ? (int)shifts[8ll * g.shift0 + wz_w4_group(i, per, taps)] : 0;
+}
+
 // pack: the stored code of weight i and whether it is kept.  MCAMD_WZ_CODE: the byte at w[i], kept by the MASK (a shared
-// value may be exactly 0); every other kind: the code of weight * mask, kept iff it is non-zero
-__device__ __forceinline__ unsigned wz_pack_code(const mcamd_wz_seg& g, long long i, int e, bool* keep) {
+// value may be exactly 0); every other kind: the code of weight * mask, kept iff it is non-zero.  MCAMD_WZ_W4: pack_q8_w4_kernel's
+// code of the weight scaled by its filter's e4_f under its group's shift byte `sh`
+__device__ __forceinline__ unsigned wz_pack_code(const mcamd_wz_seg& g, long long i, int e, int sh, bool* keep) {
     if (g.kind == MCAMD_WZ_CODE) {
         const float* m = (const float*)g.mask;
         *keep = !m || m[i] != 0.f;
         return ((const unsigned char*)g.w)[i];
     }
-    const unsigned code = wz_code(g.kind, wz_masked(g, i), e);
+    const unsigned code = g.kind == MCAMD_WZ_W4 ? w4_code(ldexpf(wz_masked(g, i), e), sh - 5) : wz_code(g.kind, wz_masked(g, i), e);
     *keep = wz_kept(g.kind, code);
     return code;
 }
@@ -106,15 +130,21 @@ __device__ __forceinline__ unsigned wz_pack_code(const mcamd_wz_seg& g, long lon
 // ---------------------------------------------------------------------------------------
 // pack
 // ---------------------------------------------------------------------------------------
-// One workgroup per filter of the MCAMD_WZ_FP8 segments: exps[f] = the packers' exponent of max |w * mask|.
-__global__ __launch_bounds__(256) void wz_exponent_kernel(const mcamd_wz_seg* __restrict__ segs, int nseg, int* __restrict__ exps) {
+// One workgroup per filter of the MCAMD_WZ_FP8 and MCAMD_WZ_W4 segments: exps[f] = the packers' exponent of max |w * mask|
+// (fp8: e_f; 4-bit: e4_f).  MCAMD_WZ_W4: then one thread per group of 32 input channels at one tap (32 weights strided by the
+// taps in OIHW): the maximum of the scaled magnitudes and from it the shift byte, pack_q8_w4_kernel's steps in its order.
+__global__ __launch_bounds__(256) void wz_exponent_kernel(const mcamd_wz_seg* __restrict__ segs, int nseg, int* __restrict__ exps,
+                                                          unsigned char* __restrict__ shifts) {
     __shared__ float red[256];
     const int f = blockIdx.x, tid = threadIdx.x;
     int s = -1;
-    for (int t = 0; t < nseg; ++t)
-        if (segs[t].kind == MCAMD_WZ_FP8 && f >= segs[t].exp0 && f < segs[t].exp0 + segs[t].cout) s = t;
-    if (s < 0) return;                                   // (uniform; the host sizes the grid to the fp8 filters)
-    const mcamd_wz_seg g = segs[s];
+    for (int t = 0; t < nseg; ++t) {
+        const int kind = segs[t].kind & 0xff;
+        if ((kind == MCAMD_WZ_FP8 || kind == MCAMD_WZ_W4) && f >= segs[t].exp0 && f < segs[t].exp0 + segs[t].cout) s = t;
+    }
+    if (s < 0) return;                                   // (uniform; the host sizes the grid to the fp8 and 4-bit filters)
+    mcamd_wz_seg g = segs[s];
+    const int taps = wz_taps(g);
     const long long per = g.n / g.cout, first = (long long)(f - g.exp0) * per;
     float amax = 0.f;
     for (long long o = tid; o < per; o += 256) amax = fmaxf(amax, fabsf(wz_masked(g, first + o)));
@@ -124,14 +154,30 @@ __global__ __launch_bounds__(256) void wz_exponent_kernel(const mcamd_wz_seg* __
         if (tid < h) red[tid] = fmaxf(red[tid], red[tid + h]);
         __syncthreads();
     }
-    if (tid == 0) exps[f] = q8_filter_exponent(red[0]);
+    if (g.kind == MCAMD_WZ_FP8) {
+        if (tid == 0) exps[f] = q8_filter_exponent(red[0]);
+        return;
+    }
+    const int e4 = w4_filter_exponent(red[0]);
+    if (tid == 0) exps[f] = e4;
+    const int ngrp = (int)(per / 32);                    // groups of the filter, [cin / 32][taps]
+    unsigned char* out = shifts + 8ll * g.shift0 + (long long)(f - g.exp0) * ngrp;
+    for (int q = tid; q < ngrp; q += 256) {
+        const int j = q / taps, tap = q - j * taps;
+        const long long base = first + (long long)j * 32 * taps + tap;
+        float m = 0.f;
+        for (int k = 0; k < 32; ++k) m = fmaxf(m, fabsf(ldexpf(wz_masked(g, base + (long long)k * taps), e4)));
+        out[q] = (unsigned char)(w4_group_shift(m) + 5);
+    }
 }
 
 __global__ __launch_bounds__(256) void wz_words_kernel(const mcamd_wz_seg* __restrict__ segs, int nseg, const int* __restrict__ exps,
-                                                       u64* __restrict__ words, unsigned* __restrict__ blocksum) {
+                                                       const unsigned char* __restrict__ shifts, u64* __restrict__ words,
+                                                       unsigned* __restrict__ blocksum) {
     __shared__ unsigned cnt[WZ_WAVES];
     const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const mcamd_wz_seg g = segs[wz_seg_of_block(segs, nseg, b)];
+    mcamd_wz_seg g = segs[wz_seg_of_block(segs, nseg, b)];
+    const int taps = wz_taps(g);
     const long long nwords = (g.n + 63) / 64, per = g.n / g.cout;
     const long long w0 = (long long)(b - g.block0) * WZ_BW + wave * WZ_WPW;
     unsigned c = 0;
@@ -141,8 +187,9 @@ __global__ __launch_bounds__(256) void wz_words_kernel(const mcamd_wz_seg* __res
         const long long i = wi * 64 + lane;
         bool keep = false;
         if (i < g.n) {
-            const int e = g.kind == MCAMD_WZ_FP8 ? exps[g.exp0 + (int)(i / per)] : 0;
-            (void)wz_pack_code(g, i, e, &keep);
+            int e, sh;
+            wz_scales(g, taps, per, i, exps, shifts, &e, &sh);
+            (void)wz_pack_code(g, i, e, sh, &keep);
         }
         const u64 word = __ballot(keep);
         if (lane == 0) words[g.word0 + wi] = word;
@@ -162,7 +209,8 @@ __global__ __launch_bounds__(64) void wz_scan_kernel(const mcamd_wz_seg* __restr
     const int lane = threadIdx.x;
     u64 vb = 0;
     for (int s = 0; s < nseg; ++s) {
-        const mcamd_wz_seg g = segs[s];
+        mcamd_wz_seg g = segs[s];
+        (void)wz_taps(g);
         const long long nwords = (g.n + 63) / 64;
         const int nb = (int)((nwords + WZ_BW - 1) / WZ_BW);
         u64 carry = 0;
@@ -180,7 +228,10 @@ __global__ __launch_bounds__(64) void wz_scan_kernel(const mcamd_wz_seg* __restr
         }
         if (PACK) {
             const u64 elem = (u64)wz_elem(g.kind);
-            const bool bits = g.kind == MCAMD_WZ_CODE ? carry < (u64)g.n : 8ull * (u64)nwords + carry * elem < (u64)g.n * elem;
+            // (MCAMD_WZ_W4: the rule counts the file's nibbles, the pass stores one byte per code)
+            const bool bits = g.kind == MCAMD_WZ_CODE ? carry < (u64)g.n
+                            : g.kind == MCAMD_WZ_W4   ? 8ull * (u64)nwords + (carry + 1ull) / 2ull < ((u64)g.n + 1ull) / 2ull
+                                                      : 8ull * (u64)nwords + carry * elem < (u64)g.n * elem;
             if (lane == 0) {
                 counts[s] = carry;
                 dense[s] = bits ? 0 : 1;
@@ -212,6 +263,7 @@ __device__ __forceinline__ void wz_block_words(const u64* __restrict__ words, bo
 }
 
 __global__ __launch_bounds__(256) void wz_scatter_kernel(const mcamd_wz_seg* __restrict__ segs, int nseg, const int* __restrict__ exps,
+                                                         const unsigned char* __restrict__ shifts,
                                                          const u64* __restrict__ words, const u64* __restrict__ blockoff,
                                                          const u64* __restrict__ segbase, const int* __restrict__ dense,
                                                          char* __restrict__ values) {
@@ -219,7 +271,8 @@ __global__ __launch_bounds__(256) void wz_scatter_kernel(const mcamd_wz_seg* __r
     __shared__ unsigned osh[WZ_BW];
     const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int s = wz_seg_of_block(segs, nseg, b);
-    const mcamd_wz_seg g = segs[s];
+    mcamd_wz_seg g = segs[s];
+    const int taps = wz_taps(g);
     const long long nwords = (g.n + 63) / 64, per = g.n / g.cout;
     const long long first = (long long)(b - g.block0) * WZ_BW;
     wz_block_words(words, true, g.word0, first, nwords, wsh, osh);
@@ -237,9 +290,10 @@ __global__ __launch_bounds__(256) void wz_scatter_kernel(const mcamd_wz_seg* __r
         if (!bit && !all) continue;
         unsigned code = 0u;
         if (bit) {
-            const int e = g.kind == MCAMD_WZ_FP8 ? exps[g.exp0 + (int)(i / per)] : 0;
+            int e, sh;
+            wz_scales(g, taps, per, i, exps, shifts, &e, &sh);
             bool keep;
-            code = wz_pack_code(g, i, e, &keep);
+            code = wz_pack_code(g, i, e, sh, &keep);
         }
         const long long pos = all ? i : (long long)(boff + osh[k] + (u64)__popcll(word & ((1ull << lane) - 1ull)));
         wz_store(base, g.kind, pos, code);
@@ -253,7 +307,7 @@ __global__ __launch_bounds__(256) void wz_scatter_kernel(const mcamd_wz_seg* __r
 __global__ __launch_bounds__(64) void wz_popc_kernel(const mcamd_wz_seg* __restrict__ segs, int nseg, const u64* __restrict__ words,
                                                      unsigned* __restrict__ blocksum) {
     const int b = blockIdx.x, lane = threadIdx.x;
-    const mcamd_wz_seg g = segs[wz_seg_of_block(segs, nseg, b)];
+    const mcamd_wz_seg g = segs[wz_seg_of_block(segs, nseg, b)];      // (kind is not read)
     const long long nwords = (g.n + 63) / 64, first = (long long)(b - g.block0) * WZ_BW;
     unsigned c = (!g.dense && first + lane < nwords) ? (unsigned)__popcll(words[g.word0 + first + lane]) : 0u;
 #pragma unroll
@@ -262,12 +316,14 @@ __global__ __launch_bounds__(64) void wz_popc_kernel(const mcamd_wz_seg* __restr
 }
 
 __global__ __launch_bounds__(256) void wz_expand_kernel(const mcamd_wz_seg* __restrict__ segs, int nseg, const int* __restrict__ exps,
+                                                        const unsigned char* __restrict__ shifts,
                                                         const u64* __restrict__ words, const u64* __restrict__ blockoff,
                                                         const char* __restrict__ values) {
     __shared__ u64 wsh[WZ_BW];
     __shared__ unsigned osh[WZ_BW];
     const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const mcamd_wz_seg g = segs[wz_seg_of_block(segs, nseg, b)];
+    mcamd_wz_seg g = segs[wz_seg_of_block(segs, nseg, b)];
+    const int taps = wz_taps(g);
     const long long nwords = (g.n + 63) / 64, per = g.n / g.cout;
     const long long first = (long long)(b - g.block0) * WZ_BW;
     wz_block_words(words, !g.dense, g.word0, first, nwords, wsh, osh);
@@ -297,8 +353,14 @@ __global__ __launch_bounds__(256) void wz_expand_kernel(const mcamd_wz_seg* __re
         }
         float v = 0.f;
         if (wz_kept(g.kind, code)) {
-            const int e = g.kind == MCAMD_WZ_FP8 ? exps[g.exp0 + (int)(i / per)] : 0;
-            v = wz_value(g.kind, code, e);
+            int e, sh;
+            wz_scales(g, taps, per, i, exps, shifts, &e, &sh);
+            if (g.kind != MCAMD_WZ_W4) {
+                v = wz_value(g.kind, code, e);
+            } else if (sh <= 11) {                        // (a damaged file's shift byte reads as +0)
+                v = ldexpf(w4_grid(code & 7u), sh - 5 - e);
+                if (code & 8u) v = -v;
+            }
         }
         w[i] = v;
         if (mask) mask[i] = bit ? 1.f : 0.f;
@@ -309,33 +371,49 @@ __global__ __launch_bounds__(256) void wz_expand_kernel(const mcamd_wz_seg* __re
 // entry points
 // ---------------------------------------------------------------------------------------
 struct WzTotals {
-    long long blocks, words, exps, cap_bytes;
+    long long blocks, words, exps, shifts, cap_bytes;     // (shifts: in units of 8 bytes)
 };
 
+// `shifts_cap` < 0: the entry point takes no shift bytes and refuses an MCAMD_WZ_W4 segment
 static int wz_check_table(const char* what, const mcamd_wz_seg* segs, int nseg, bool unpack, long long words_cap, long long exps_cap,
-                          long long values_bytes, WzTotals* t) {
-    long long blocks = 0, words = 0, exps = 0, cap = 0;
+                          long long shifts_cap, long long values_bytes, WzTotals* t) {
+    long long blocks = 0, words = 0, exps = 0, shifts = 0, cap = 0;
     for (int s = 0; s < nseg; ++s) {
         const mcamd_wz_seg& g = segs[s];
         MCAMD_REQUIRE(g.w && g.n > 0 && g.cout > 0 && g.n % g.cout == 0, "%s: segment %d: bad tensor (n %lld, cout %d)", what, s,
                       (long long)g.n, g.cout);
-        MCAMD_REQUIRE(g.kind == MCAMD_WZ_FP32 || g.kind == MCAMD_WZ_FP16 || g.kind == MCAMD_WZ_FP8 || g.kind == MCAMD_WZ_CODE,
+        const bool w4 = (g.kind & 0xff) == MCAMD_WZ_W4 && g.kind >= 0;
+        MCAMD_REQUIRE(g.kind == MCAMD_WZ_FP32 || g.kind == MCAMD_WZ_FP16 || g.kind == MCAMD_WZ_FP8 || g.kind == MCAMD_WZ_CODE || w4,
                       "%s: segment %d: bad value kind %d", what, s, g.kind);
+        const bool scaled = w4 || g.kind == MCAMD_WZ_FP8;  // one exponent per filter
+        if (w4) {
+            const long long taps = g.kind >> 8, per = g.n / g.cout;
+            MCAMD_REQUIRE(shifts_cap >= 0, "%s: segment %d: an MCAMD_WZ_W4 segment goes through %s_w4", what, s, what);
+            MCAMD_REQUIRE(taps > 0 && per % taps == 0 && (per / taps) % 32 == 0,
+                          "%s: segment %d: MCAMD_WZ_W4 needs cin %% 32 == 0 (%lld weights per filter, %lld taps)", what, s, per, taps);
+        }
         const long long elem = g.kind == MCAMD_WZ_FP32 ? 4 : g.kind == MCAMD_WZ_FP16 ? 2 : 1;
         const long long nwords = (g.n + 63) / 64;
         MCAMD_REQUIRE(g.block0 == blocks, "%s: segment %d: block0 %d is not the running sum %lld", what, s, g.block0, blocks);
         if (!unpack) {                                    // pack lays the arrays out itself: running sums
             MCAMD_REQUIRE(g.word0 == words, "%s: segment %d: word0 %lld is not the running sum %lld", what, s, (long long)g.word0, words);
             words += nwords;
-            if (g.kind == MCAMD_WZ_FP8) {
+            if (scaled) {
                 MCAMD_REQUIRE(g.exp0 == exps, "%s: segment %d: exp0 %d is not the running sum %lld", what, s, g.exp0, exps);
                 exps += g.cout;
+            }
+            if (w4) {
+                MCAMD_REQUIRE(g.shift0 == shifts, "%s: segment %d: shift0 %d is not the running sum %lld", what, s, g.shift0, shifts);
+                shifts += (g.n / 32 + 7) / 8;
             }
         } else {                                          // unpack reads them where the caller has them
             MCAMD_REQUIRE(g.dense == 1 || (g.word0 >= 0 && g.word0 + nwords <= words_cap),
                           "%s: segment %d: bit words [%lld, +%lld) outside the %lld given", what, s, (long long)g.word0, nwords, words_cap);
-            MCAMD_REQUIRE(g.kind != MCAMD_WZ_FP8 || (g.exp0 >= 0 && (long long)g.exp0 + g.cout <= exps_cap),
+            MCAMD_REQUIRE(!scaled || (g.exp0 >= 0 && (long long)g.exp0 + g.cout <= exps_cap),
                           "%s: segment %d: exponents [%d, +%d) outside the %lld given", what, s, g.exp0, g.cout, exps_cap);
+            MCAMD_REQUIRE(!w4 || (g.shift0 >= 0 && 8ll * g.shift0 + g.n / 32 <= shifts_cap),
+                          "%s: segment %d: shift bytes [%lld, +%lld) outside the %lld given", what, s, 8ll * g.shift0,
+                          (long long)(g.n / 32), shifts_cap);
         }
         if (unpack) {
             MCAMD_REQUIRE(g.dense == 0 || g.dense == 1, "%s: segment %d: bad dense flag", what, s);
@@ -348,51 +426,57 @@ static int wz_check_table(const char* what, const mcamd_wz_seg* segs, int nseg, 
         }
         cap += (g.n * elem + 7) / 8 * 8;
         blocks += (nwords + WZ_BW - 1) / WZ_BW;
-        MCAMD_REQUIRE(blocks < (1ll << 31) && exps < (1ll << 31), "%s: too many weights", what);
+        MCAMD_REQUIRE(blocks < (1ll << 31) && exps < (1ll << 31) && shifts < (1ll << 31), "%s: too many weights", what);
     }
-    t->blocks = blocks, t->words = words, t->exps = exps, t->cap_bytes = cap;
+    t->blocks = blocks, t->words = words, t->exps = exps, t->shifts = shifts, t->cap_bytes = cap;
     return MCAMD_OK;
 }
 
-extern "C" int mcamd_wz_pack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, uint64_t* words, int64_t words_cap,
-                             uint64_t* counts, int32_t* exps, int64_t exps_cap, void* values, int64_t values_bytes, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-    MCAMD_REQUIRE(!mcamd_recording(), "wz_pack: not recordable into a launch plan");
-    MCAMD_REQUIRE(segs && segs_dev && nseg > 0 && words && counts && values && workspace, "wz_pack: null argument");
+// (shifts_cap < 0: mcamd_wz_pack, which has no shift bytes)
+static int wz_pack_impl(const char* what, const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, uint64_t* words,
+                        int64_t words_cap, uint64_t* counts, int32_t* exps, int64_t exps_cap, void* values, int64_t values_bytes,
+                        void* workspace, size_t workspace_bytes, void* stream, uint8_t* shifts, int64_t shifts_cap) {
+    MCAMD_REQUIRE(!mcamd_recording(), "%s: not recordable into a launch plan", what);
+    MCAMD_REQUIRE(segs && segs_dev && nseg > 0 && words && counts && values && workspace, "%s: null argument", what);
     WzTotals t;
-    const int rc = wz_check_table("wz_pack", segs, nseg, false, words_cap, exps_cap, values_bytes, &t);
+    const int rc = wz_check_table(what, segs, nseg, false, words_cap, exps_cap, shifts_cap, values_bytes, &t);
     if (rc) return rc;
-    MCAMD_REQUIRE(words_cap >= t.words, "wz_pack: %lld bit words needed, room for %lld", t.words, (long long)words_cap);
-    MCAMD_REQUIRE(t.exps == 0 || (exps && exps_cap >= t.exps), "wz_pack: %lld exponents needed, room for %lld", t.exps,
+    MCAMD_REQUIRE(words_cap >= t.words, "%s: %lld bit words needed, room for %lld", what, t.words, (long long)words_cap);
+    MCAMD_REQUIRE(t.exps == 0 || (exps && exps_cap >= t.exps), "%s: %lld exponents needed, room for %lld", what, t.exps,
                   exps ? (long long)exps_cap : 0ll);
-    MCAMD_REQUIRE(values_bytes >= t.cap_bytes, "wz_pack: values need room for %lld bytes (every weight kept), got %lld", t.cap_bytes,
+    MCAMD_REQUIRE(t.shifts == 0 || (shifts && shifts_cap >= 8 * t.shifts), "%s: %lld shift bytes needed, room for %lld", what,
+                  8 * t.shifts, shifts ? (long long)shifts_cap : 0ll);
+    MCAMD_REQUIRE(values_bytes >= t.cap_bytes, "%s: values need room for %lld bytes (every weight kept), got %lld", what, t.cap_bytes,
                   (long long)values_bytes);
     if (workspace_bytes < mcamd_wz_workspace_bytes(t.blocks, nseg)) {
-        mcamd_set_error("wz_pack: workspace too small");
+        mcamd_set_error("%s: workspace too small", what);
         return MCAMD_EWORKSPACE;
     }
     const WzWork k = wz_work(workspace, t.blocks, nseg);
     hipStream_t st = (hipStream_t)stream;
-    if (t.exps) hipLaunchKernelGGL(wz_exponent_kernel, dim3((int)t.exps), dim3(256), 0, st, segs_dev, nseg, exps);
-    hipLaunchKernelGGL(wz_words_kernel, dim3((int)t.blocks), dim3(256), 0, st, segs_dev, nseg, (const int*)exps, (u64*)words, k.blocksum);
+    if (t.exps) hipLaunchKernelGGL(wz_exponent_kernel, dim3((int)t.exps), dim3(256), 0, st, segs_dev, nseg, exps, (unsigned char*)shifts);
+    hipLaunchKernelGGL(wz_words_kernel, dim3((int)t.blocks), dim3(256), 0, st, segs_dev, nseg, (const int*)exps,
+                       (const unsigned char*)shifts, (u64*)words, k.blocksum);
     hipLaunchKernelGGL(wz_scan_kernel<true>, dim3(1), dim3(64), 0, st, segs_dev, nseg, (const unsigned*)k.blocksum, k.blockoff,
                        (u64*)counts, k.segbase, k.dense);
-    hipLaunchKernelGGL(wz_scatter_kernel, dim3((int)t.blocks), dim3(256), 0, st, segs_dev, nseg, (const int*)exps, (const u64*)words,
-                       (const u64*)k.blockoff, (const u64*)k.segbase, (const int*)k.dense, (char*)values);
-    MCAMD_LAUNCH_CHECK("wz_pack");
+    hipLaunchKernelGGL(wz_scatter_kernel, dim3((int)t.blocks), dim3(256), 0, st, segs_dev, nseg, (const int*)exps,
+                       (const unsigned char*)shifts, (const u64*)words, (const u64*)k.blockoff, (const u64*)k.segbase,
+                       (const int*)k.dense, (char*)values);
+    MCAMD_LAUNCH_CHECK(what);
     return MCAMD_OK;
 }
 
-extern "C" int mcamd_wz_unpack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, const uint64_t* words,
-                               int64_t words_cap, const int32_t* exps, int64_t exps_cap, const void* values, int64_t values_bytes,
-                               void* workspace, size_t workspace_bytes, void* stream) {
-    MCAMD_REQUIRE(!mcamd_recording(), "wz_unpack: not recordable into a launch plan");
-    MCAMD_REQUIRE(segs && segs_dev && nseg > 0 && values && values_bytes >= 0 && workspace, "wz_unpack: null argument");
+static int wz_unpack_impl(const char* what, const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, const uint64_t* words,
+                          int64_t words_cap, const int32_t* exps, int64_t exps_cap, const void* values, int64_t values_bytes,
+                          void* workspace, size_t workspace_bytes, void* stream, const uint8_t* shifts, int64_t shifts_cap) {
+    MCAMD_REQUIRE(!mcamd_recording(), "%s: not recordable into a launch plan", what);
+    MCAMD_REQUIRE(segs && segs_dev && nseg > 0 && values && values_bytes >= 0 && workspace, "%s: null argument", what);
     WzTotals t;
-    const int rc = wz_check_table("wz_unpack", segs, nseg, true, words ? words_cap : 0, exps ? exps_cap : 0, values_bytes, &t);
+    const int rc = wz_check_table(what, segs, nseg, true, words ? words_cap : 0, exps ? exps_cap : 0,
+                                  shifts_cap < 0 ? -1 : shifts ? shifts_cap : 0, values_bytes, &t);
     if (rc) return rc;
     if (workspace_bytes < mcamd_wz_workspace_bytes(t.blocks, nseg)) {
-        mcamd_set_error("wz_unpack: workspace too small");
+        mcamd_set_error("%s: workspace too small", what);
         return MCAMD_EWORKSPACE;
     }
     const WzWork k = wz_work(workspace, t.blocks, nseg);
@@ -400,8 +484,39 @@ extern "C" int mcamd_wz_unpack(const mcamd_wz_seg* segs, const mcamd_wz_seg* seg
     hipLaunchKernelGGL(wz_popc_kernel, dim3((int)t.blocks), dim3(64), 0, st, segs_dev, nseg, (const u64*)words, k.blocksum);
     hipLaunchKernelGGL(wz_scan_kernel<false>, dim3(1), dim3(64), 0, st, segs_dev, nseg, (const unsigned*)k.blocksum, k.blockoff,
                        (u64*)nullptr, (u64*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(wz_expand_kernel, dim3((int)t.blocks), dim3(256), 0, st, segs_dev, nseg, (const int*)exps, (const u64*)words,
-                       (const u64*)k.blockoff, (const char*)values);
-    MCAMD_LAUNCH_CHECK("wz_unpack");
+    hipLaunchKernelGGL(wz_expand_kernel, dim3((int)t.blocks), dim3(256), 0, st, segs_dev, nseg, (const int*)exps,
+                       (const unsigned char*)shifts, (const u64*)words, (const u64*)k.blockoff, (const char*)values);
+    MCAMD_LAUNCH_CHECK(what);
     return MCAMD_OK;
+}
+
+extern "C" int mcamd_wz_pack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, uint64_t* words, int64_t words_cap,
+                             uint64_t* counts, int32_t* exps, int64_t exps_cap, void* values, int64_t values_bytes, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    return wz_pack_impl("wz_pack", segs, segs_dev, nseg, words, words_cap, counts, exps, exps_cap, values, values_bytes, workspace,
+                        workspace_bytes, stream, nullptr, -1);
+}
+
+extern "C" int mcamd_wz_unpack(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, const uint64_t* words,
+                               int64_t words_cap, const int32_t* exps, int64_t exps_cap, const void* values, int64_t values_bytes,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    return wz_unpack_impl("wz_unpack", segs, segs_dev, nseg, words, words_cap, exps, exps_cap, values, values_bytes, workspace,
+                          workspace_bytes, stream, nullptr, -1);
+}
+
+extern "C" int mcamd_wz_pack_w4(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, uint64_t* words,
+                                int64_t words_cap, uint64_t* counts, int32_t* exps, int64_t exps_cap, void* values,
+                                int64_t values_bytes, void* workspace, size_t workspace_bytes, void* stream, uint8_t* shifts,
+                                int64_t shifts_cap) {
+    MCAMD_REQUIRE(shifts_cap >= 0, "wz_pack_w4: negative shifts_cap");
+    return wz_pack_impl("wz_pack_w4", segs, segs_dev, nseg, words, words_cap, counts, exps, exps_cap, values, values_bytes, workspace,
+                        workspace_bytes, stream, shifts, shifts_cap);
+}
+
+extern "C" int mcamd_wz_unpack_w4(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, int32_t nseg, const uint64_t* words,
+                                  int64_t words_cap, const int32_t* exps, int64_t exps_cap, const void* values, int64_t values_bytes,
+                                  void* workspace, size_t workspace_bytes, void* stream, const uint8_t* shifts, int64_t shifts_cap) {
+    MCAMD_REQUIRE(shifts_cap >= 0, "wz_unpack_w4: negative shifts_cap");
+    return wz_unpack_impl("wz_unpack_w4", segs, segs_dev, nseg, words, words_cap, exps, exps_cap, values, values_bytes, workspace,
+                          workspace_bytes, stream, shifts, shifts_cap);
 }

@@ -560,7 +560,8 @@ class Darknet(nn.Module):
 
     def save_compressed(self, outfile, payload="fp16", layers=None):
         """Write a compressed model file (an addition beyond the reference; compress.save_compressed).
-        payload "shared": codebooks + narrow codes of the layers set_codebooks tied."""
+        payload "shared": codebooks + narrow codes of the layers set_codebooks tied; payload "w4": the 4-bit
+        codes, group shifts and filter exponents the "fp8-w4" engine consumes."""
         from . import compress
         compress.save_compressed(self, outfile, payload, layers)
 

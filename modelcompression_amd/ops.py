@@ -1420,14 +1420,15 @@ def fakequant_q8_w4(g, codes, gshift, wexp, out=None):
 
 
 # ----------------------------------------------------------------------------- compressed model files (.mcz)
-WZ_ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1, L.WZ_CODE: 1}
+WZ_ELEM = {L.WZ_FP32: 4, L.WZ_FP16: 2, L.WZ_FP8: 1, L.WZ_CODE: 1, L.WZ_W4: 1}
 
 
 def _wz_table(items, device, unpack):
-    """items: dicts(w, mask, kind[, dense, kept, val0, word0, exp0]) -> (host mcamd_wz_seg array, its device copy, blocks, words, exps,
-    bytes of every value array were every weight kept).  The running sums are the header's (include/mcamd.h)."""
+    """items: dicts(w, mask, kind[, dense, kept, val0, word0, exp0, shift0]) -> (host mcamd_wz_seg array, its device copy, blocks,
+    words, exps, bytes of every value array were every weight kept, shift bytes).  The running sums are the header's
+    (include/mcamd.h)."""
     arr = (L.WzSeg * len(items))()
-    blocks = words = exps = cap = 0
+    blocks = words = exps = cap = shifts = 0
     for a, it in zip(arr, items):
         w, mask, kind = it["w"], it.get("mask"), int(it["kind"])
         _need_cuda(w, mask)
@@ -1435,51 +1436,64 @@ def _wz_table(items, device, unpack):
             raise L.McamdError("wz: the codes of a WZ_CODE item must be a non-empty contiguous uint8 tensor of the weight's shape")
         if kind != L.WZ_CODE and (w.dtype != torch.float32 or not w.is_contiguous() or w.numel() == 0 or kind not in WZ_ELEM):
             raise L.McamdError("wz: weights must be non-empty contiguous fp32 tensors and kind one of %r" % sorted(WZ_ELEM))
+        if kind == L.WZ_W4 and (w.dim() != 4 or w.shape[1] % 32):
+            raise L.McamdError("wz: a WZ_W4 item must be an OIHW tensor with cin %% 32 == 0, got %r" % (tuple(w.shape),))
         if mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous() or mask.shape != w.shape):
             raise L.McamdError("wz: a mask must be a contiguous fp32 tensor of the weight's shape")
         n, nwords = w.numel(), (w.numel() + 63) // 64
-        a.w, a.mask, a.n, a.cout, a.kind = w.data_ptr(), (mask.data_ptr() if mask is not None else None), n, w.shape[0], kind
+        a.w, a.mask, a.n, a.cout = w.data_ptr(), (mask.data_ptr() if mask is not None else None), n, w.shape[0]
+        a.kind = kind | (w.shape[2] * w.shape[3]) << 8 if kind == L.WZ_W4 else kind          # MCAMD_WZ_W4_KIND(taps)
         a.block0 = blocks
         a.word0, a.exp0 = (int(it.get("word0", words)), int(it.get("exp0", exps))) if unpack else (words, exps)
+        a.shift0 = (int(it.get("shift0", shifts // 8)) if unpack else shifts // 8) if kind == L.WZ_W4 else 0
         a.dense = int(bool(it.get("dense", 0))) if unpack else 0
         a.kept, a.val0 = (int(it["kept"]), int(it["val0"])) if unpack else (0, 0)
         if not a.dense:
             words += nwords
-        if kind == L.WZ_FP8:
+        if kind in (L.WZ_FP8, L.WZ_W4):
             exps += w.shape[0]
+        if kind == L.WZ_W4:
+            shifts += round_up(n // 32, 8)
         blocks += (nwords + L.WZ_BLOCK_WORDS - 1) // L.WZ_BLOCK_WORDS
         cap += round_up(n * WZ_ELEM[kind], 8)
     dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
-    return arr, dev, blocks, words, exps, cap
+    return arr, dev, blocks, words, exps, cap, shifts
 
 
 def wz_pack(items):
     """items: one dict(w=fp32 OIHW master, mask=fp32 mask or None, kind=L.WZ_*) per layer, all through one table
-    (mcamd_wz_pack) -> device tensors (words int64 [sum ceil(n / 64)], counts int64 [len(items)], exps int32 [fp8 filters],
-    values uint8): the bit words of segment s start at the running sum of ceil(n / 64), its exponents at the running sum of
-    the fp8 segments' cout, its values at the byte offset the header's rule gives from the counts."""
+    (mcamd_wz_pack_w4) -> device tensors (words int64 [sum ceil(n / 64)], counts int64 [len(items)], exps int32 [fp8 and 4-bit
+    filters], values uint8): the bit words of segment s start at the running sum of ceil(n / 64), its exponents at the running
+    sum of the fp8 and 4-bit segments' cout, its values at the byte offset the header's rule gives from the counts.  A table
+    that holds a WZ_W4 item returns a fifth tensor, shifts uint8: the n / 32 shift bytes of each such segment, padded to 8, in
+    order; its values are one byte per code."""
     dev = items[0]["w"].device
-    arr, table, blocks, nwords, nexps, cap = _wz_table(items, dev, False)
+    arr, table, blocks, nwords, nexps, cap, nshifts = _wz_table(items, dev, False)
     words = torch.empty(nwords, dtype=torch.int64, device=dev)
     counts = torch.empty(len(items), dtype=torch.int64, device=dev)
     exps = torch.empty(max(nexps, 1), dtype=torch.int32, device=dev)
     values = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    shifts = torch.zeros(max(nshifts, 8), dtype=torch.uint8, device=dev)
     ws = torch.empty(int(L.lib().mcamd_wz_workspace_bytes(blocks, len(items))), dtype=torch.uint8, device=dev)
-    check(L.lib().mcamd_wz_pack(arr, ptr(table), len(items), ptr(words), nwords, ptr(counts), ptr(exps), nexps, ptr(values), cap,
-                                ptr(ws), ws.numel(), stream_ptr()), "mcamd_wz_pack")
+    check(L.lib().mcamd_wz_pack_w4(arr, ptr(table), len(items), ptr(words), nwords, ptr(counts), ptr(exps), nexps, ptr(values), cap,
+                                   ptr(ws), ws.numel(), stream_ptr(), ptr(shifts), nshifts), "mcamd_wz_pack_w4")
+    if nshifts:
+        return words, counts, exps[:nexps], values, shifts[:nshifts]
     return words, counts, exps[:nexps], values
 
 
-def wz_unpack(items, words, exps, values):
+def wz_unpack(items, words, exps, values, shifts=None):
     """items: one dict(w=fp32 OIHW tensor to fill, mask=fp32 tensor to fill or None, kind, dense, kept, val0) per layer;
-    words (int64, the bit words of the non-dense items in order), exps (int32, the fp8 items' exponents in order) and
-    values (uint8, item s at byte val0) are device tensors or None when no item needs them (mcamd_wz_unpack).  An item
-    may name where its bit words and exponents start (word0, exp0: element offsets into `words` / `exps`) in place of the
-    running sums, which lets views of one uploaded file serve as all three arrays."""
+    words (int64, the bit words of the non-dense items in order), exps (int32, the fp8 and 4-bit items' exponents in order),
+    values (uint8, item s at byte val0; a WZ_W4 item: one byte per code) and shifts (uint8, the WZ_W4 items' shift bytes, each
+    item's padded to 8) are device tensors or None when no item needs them (mcamd_wz_unpack_w4).  An item may name where its
+    bit words, exponents and shift bytes start (word0, exp0: element offsets into `words` / `exps`; shift0: the byte offset
+    into `shifts` divided by 8) in place of the running sums, which lets views of one uploaded file serve as every array."""
     dev = items[0]["w"].device
-    _need_cuda(words, exps, values)
-    arr, table, blocks, nwords, nexps, _ = _wz_table(items, dev, True)
-    for t, dt, need, name in ((words, torch.int64, nwords, "words"), (exps, torch.int32, nexps, "exps"), (values, torch.uint8, 0, "values")):
+    _need_cuda(words, exps, values, shifts)
+    arr, table, blocks, nwords, nexps, _, nshifts = _wz_table(items, dev, True)
+    for t, dt, need, name in ((words, torch.int64, nwords, "words"), (exps, torch.int32, nexps, "exps"), (values, torch.uint8, 0, "values"),
+                              (shifts, torch.uint8, nshifts, "shifts")):
         if t is not None and (t.dtype != dt or not t.is_contiguous()):
             raise L.McamdError("wz_unpack: `%s` must be a contiguous %s tensor" % (name, dt))
         if need and t is None:
@@ -1487,9 +1501,9 @@ def wz_unpack(items, words, exps, values):
     if values is None:
         values = torch.zeros(8, dtype=torch.uint8, device=dev)
     ws = torch.empty(int(L.lib().mcamd_wz_workspace_bytes(blocks, len(items))), dtype=torch.uint8, device=dev)
-    check(L.lib().mcamd_wz_unpack(arr, ptr(table), len(items), ptr(words), words.numel() if words is not None else 0, ptr(exps),
-                                  exps.numel() if exps is not None else 0, ptr(values), values.numel(), ptr(ws), ws.numel(),
-                                  stream_ptr()), "mcamd_wz_unpack")
+    check(L.lib().mcamd_wz_unpack_w4(arr, ptr(table), len(items), ptr(words), words.numel() if words is not None else 0, ptr(exps),
+                                     exps.numel() if exps is not None else 0, ptr(values), values.numel(), ptr(ws), ws.numel(),
+                                     stream_ptr(), ptr(shifts), shifts.numel() if shifts is not None else 0), "mcamd_wz_unpack_w4")
 
 
 # ----------------------------------------------------------------------------- weight sharing

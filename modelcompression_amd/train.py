@@ -34,7 +34,7 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     tied layer still holds at most 2^bits distinct kept values.  Given by keyword only (the positional parameters of train()
     stay as they were: a wrapper takes the keyword off), or set as the attribute YOLOv2Train.SHARE, which the keyword
     overrides.  Off by default: the same launches and results as without it.
-  * YOLOv2Train.SAVE_COMPRESSED = "fp32" / "fp16" / "fp8" / "shared" (an attribute, set on the class or on the object before
+  * YOLOv2Train.SAVE_COMPRESSED = "fp32" / "fp16" / "w4" / "fp8" / "shared" (an attribute, set on the class or on the object before
     train() is called: the signature of train() stays the reference's plus the keywords above) writes a compressed model
     file of that payload (compress.py) beside every .weights file saved, with the extension .mcz.
     MODEL_WEIGHT and a TEACHER path may name such a file: Darknet.load_weights recognises it, and train() resumes at the
@@ -245,8 +245,8 @@ class YOLOv2Train():
               DISTILL=None):
         SHARE = self.SHARE if self._share_arg is None else self._share_arg
         SAVE_COMPRESSED = self.SAVE_COMPRESSED
-        if SAVE_COMPRESSED not in (None, "fp32", "fp16", "fp8", "shared"):
-            raise ValueError('train: SAVE_COMPRESSED must be None, "fp32", "fp16", "fp8" or "shared", got %r' % (SAVE_COMPRESSED,))
+        if SAVE_COMPRESSED not in (None, "fp32", "fp16", "w4", "fp8", "shared"):
+            raise ValueError('train: SAVE_COMPRESSED must be None, "fp32", "fp16", "w4", "fp8" or "shared", got %r' % (SAVE_COMPRESSED,))
         if SHARE is not None and not isinstance(SHARE, dict):
             SHARE = dict(bits=SHARE)
         if SHARE is not None and not isinstance(SHARE.get("bits", 4), dict):

@@ -1,14 +1,15 @@
 """Compressed model files (modelcompression_amd/compress.py) of a seeded YOLOv2-VOC: bytes on disk and the
 time to write and read them.
 
-  bytes  for the dense model, weight_prune(80) and nm_prune, and each payload (fp32, fp16, fp8 with the default layers):
+  bytes  for the dense model, weight_prune(80) and nm_prune, and each payload (fp32, fp16, fp8 and w4 with the default layers):
          the size of the .mcz file and its ratio against the dense float32 .weights file.  Exact, not timed: the sizes follow
          from the kept counts.
   time   on the weight_prune(80) model, fp16 payload: save_compressed against save_weights, and load-to-device
          (a fresh Darknet on the device + load_compressed, the device expanding the file's bytes) against the Darknet path
-         (load_weights on the host + .to(device)).  The four legs alternate in one process, ROUNDS rounds after one warm-up
-         round; every sample is wall time around the call with a device synchronise on both sides, files in a temporary
-         directory (page cache warm for every leg alike).  Quoted: the median of the samples and their spread.
+         (load_weights on the host + .to(device)); and the "w4" payload against the "fp8" payload, save and
+         load-to-device.  All legs alternate in one process, ROUNDS rounds after one warm-up round; every sample is wall
+         time around the call with a device synchronise on both sides, files in a temporary directory (page cache warm for
+         every leg alike).  Quoted: the median of the samples and their spread.
 
 usage: python tools/compress_bench.py [--json]
 --json writes the result to profiles/compress_bench.json."""
@@ -22,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 JSON_PATH = os.path.join(ROOT, "profiles", "compress_bench.json")
 ROUNDS = 5
-PAYLOADS = ("fp32", "fp16", "fp8")
+PAYLOADS = ("fp32", "fp16", "fp8", "w4")
 
 
 def median(v):
@@ -69,19 +70,24 @@ def main(argv):
 
         m = models["weight_prune(80)"]
         plain, packed = os.path.join(tmp, "t.weights"), os.path.join(tmp, "t.mcz")
+        packed8, packed4 = os.path.join(tmp, "t8.mcz"), os.path.join(tmp, "t4.mcz")
 
         def load_plain():
             r = nets.Darknet(YOLOV2_VOC_CFG)
             r.load_weights(plain)
             return r.to(dev)
 
-        def load_packed():
+        def load_packed(path=None):
             r = nets.Darknet(YOLOV2_VOC_CFG).to(dev)
-            r.load_weights(packed)
+            r.load_weights(path or packed)
             return r
 
         legs = {"save_weights": lambda: m.save_weights(plain), "save_compressed fp16": lambda: m.save_compressed(packed, "fp16"),
-                "load_weights + to(device)": load_plain, "load_compressed on the device": load_packed}
+                "load_weights + to(device)": load_plain, "load_compressed on the device": load_packed,
+                "save_compressed fp8": lambda: m.save_compressed(packed8, "fp8"),
+                "save_compressed w4": lambda: m.save_compressed(packed4, "w4"),
+                "load_compressed fp8 on the device": lambda: load_packed(packed8),
+                "load_compressed w4 on the device": lambda: load_packed(packed4)}
         samples = {k: [] for k in legs}
         for rnd in range(ROUNDS + 1):
             for k, fn in legs.items():
