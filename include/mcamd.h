@@ -680,6 +680,21 @@ typedef struct mcamd_act_desc {
 } mcamd_act_desc;
 int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream);
 
+/* Which kernel instance mcamd_bn_act_fwd launches for a descriptor (host logic only: no GPU work, the pointers are compared
+ * with NULL and never read).  The launch and this query ask one function (`act_route` in csrc/bn_act.hip), so the query
+ * returns MCAMD_OK exactly where the launch would, and the launch's error (code and mcamd_last_error text) where it refuses.
+ *   mode             : MCAMD_DST_* as given
+ *   fixed            : 1 when C / 8 divides 256 (a thread keeps one channel group and its coefficients in registers), else 0
+ *                      (any C % 8 == 0: coefficients re-read per item)
+ *   y32              : 1 for an fp32 y
+ *   planes, planes2  : the storage forms of dst and dst2 with the zeros resolved (planes 0 -> 1, planes2 0 -> planes)
+ *   q8               : 1 when a byte twin (dst_q8 / dst2_q8) is given
+ *   items            : 8-channel groups x pixels at the mode's resolution; grid: workgroups of 256 threads, at most 4096 --
+ *                      beyond that a thread takes more than one item
+ * The library holds 48 instances: 3 modes x fixed 0/1 x {fp16 y: planes 1, 2, 3; fp32 y: planes 1, 2, 3, 4; q8}. */
+typedef struct mcamd_act_instance { int32_t mode, fixed, y32, planes, planes2, q8; int64_t items; int32_t grid; } mcamd_act_instance;
+int mcamd_bn_act_fwd_instance(const mcamd_act_desc* d, mcamd_act_instance* out);
+
 /* mcamd_bn_act_fwd(d) followed by mcamd_conv_fwd(g, d->dst, wp_fwd, epi) in ONE launch, for a PLAIN block whose only
  * consumer is a 1x1 convolution on split operands (csrc/bn_conv1x1.hip): a workgroup reads the producer's fp32 raw output
  * d->y once, applies leaky(y * scale + shift), splits into hi = fp16(v) saturated and lo = fp16(v - hi) in registers and

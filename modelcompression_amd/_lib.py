@@ -78,6 +78,12 @@ class DgradSums(C.Structure):
                 ("ch_lo", C.c_int32), ("C", C.c_int32)]
 
 
+class ActInstance(C.Structure):
+    """mcamd_act_instance (include/mcamd.h)."""
+    _fields_ = [("mode", C.c_int32), ("fixed", C.c_int32), ("y32", C.c_int32), ("planes", C.c_int32),
+                ("planes2", C.c_int32), ("q8", C.c_int32), ("items", C.c_int64), ("grid", C.c_int32)]
+
+
 class SplitkInfo(C.Structure):
     """mcamd_splitk_info (include/mcamd.h)."""
     _fields_ = [("slices", C.c_int32), ("bm", C.c_int32), ("bn", C.c_int32), ("bk", C.c_int32),
@@ -252,6 +258,7 @@ SIGNATURES = {
     "mcamd_fold_weights_many": (C.c_int, [_P, _I32, _I64, _P]),
     "mcamd_unfold_wgrad": (C.c_int, [C.POINTER(FoldDesc), _P, _P, _P, _P, _I32, _P]),
     "mcamd_bn_act_fwd": (C.c_int, [C.POINTER(ActDesc), _P]),
+    "mcamd_bn_act_fwd_instance": (C.c_int, [C.POINTER(ActDesc), C.POINTER(ActInstance)]),
     "mcamd_bn_act_conv1x1_ok": (_I32, [C.POINTER(ActDesc), C.POINTER(ConvGeom)]),
     "mcamd_bn_act_conv1x1_stats_rows": (_I32, [C.POINTER(ActDesc), C.POINTER(ConvGeom)]),
     "mcamd_bn_act_conv1x1_fwd": (C.c_int, [C.POINTER(ActDesc), C.POINTER(ConvGeom), _P, C.POINTER(ConvEpilogue), _P]),

@@ -1244,12 +1244,10 @@ static int check_c(int C, const char* what) {
     return MCAMD_OK;
 }
 
-extern "C" int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream) {
-    if (mcamd_recording()) {
-        MCAMD_REQUIRE(d, "bn_act_fwd: null descriptor");
-        const mcamd_act_desc d_ = *d;
-        return mcamd_rec_push(stream, [=](void* s) { return mcamd_bn_act_fwd(&d_, s); });
-    }
+// Which bn_act_fwd_kernel<MODE, FIXED, Y32, PL, Q8> instance a descriptor gets, its grid and its arguments: the ONE place
+// that validates a descriptor and decides, for the launch and for the host-only query mcamd_bn_act_fwd_instance (what
+// the exact per-instance tests ask), so the two cannot disagree.
+static int act_route(const mcamd_act_desc* d, ActArgs* out, mcamd_act_instance* r) {
     MCAMD_REQUIRE(d && d->y && d->dst && d->scale && d->shift, "bn_act_fwd: null argument");
     MCAMD_REQUIRE(d->C > 0 && d->C % 8 == 0, "bn_act_fwd: channel count %d must be a positive multiple of 8", d->C);
     MCAMD_REQUIRE(d->y_ld % 8 == 0 && d->y_choff % 8 == 0 && d->dst_ld % 8 == 0 && d->dst_choff % 8 == 0 &&
@@ -1290,8 +1288,6 @@ extern "C" int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream) {
     long long pixels = (long long)d->B * d->H * d->W;
     if (d->mode != MCAMD_DST_PLAIN) pixels /= 4;
     a.items = pixels * (d->C / 8);
-    int grid = stream_grid(a.items);
-    hipStream_t st = (hipStream_t)stream;
     a.border = d->border;
     MCAMD_REQUIRE(!d->pool_act || (d->mode == MCAMD_DST_POOL && d->pool_act_ld % 8 == 0 && d->pool_act_ld >= d->C &&
                                    (d->pool_act_pad == 0 || d->pool_act_pad == 1)),
@@ -1306,6 +1302,30 @@ extern "C" int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream) {
     MCAMD_REQUIRE(!q8 || (y32 && planes == 1 && planes2 == 1 && !d->pool_act && (!d->dst2_q8 || d->dst2)),
                   "bn_act_fwd: byte destinations (dst_q8 / dst2_q8) go with an fp32 y, one plane, no pool_act, and dst2_q8 with dst2");
     a.dst_q8 = (char*)d->dst_q8, a.dst2_q8 = (char*)d->dst2_q8;
+    MCAMD_REQUIRE(d->mode == MCAMD_DST_PLAIN || d->mode == MCAMD_DST_POOL || d->mode == MCAMD_DST_REORG, "bn_act_fwd: bad mode %d", d->mode);
+    r->mode = d->mode, r->fixed = fixed, r->y32 = y32, r->planes = planes, r->planes2 = planes2, r->q8 = q8;
+    r->items = a.items, r->grid = stream_grid(a.items);
+    if (out) *out = a;
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_bn_act_fwd_instance(const mcamd_act_desc* d, mcamd_act_instance* out) {
+    MCAMD_REQUIRE(out, "bn_act_fwd_instance: null output");
+    return act_route(d, nullptr, out);
+}
+
+extern "C" int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(d, "bn_act_fwd: null descriptor");
+        const mcamd_act_desc d_ = *d;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_bn_act_fwd(&d_, s); });
+    }
+    ActArgs a;
+    mcamd_act_instance r;
+    if (int rc = act_route(d, &a, &r)) return rc;
+    const int grid = r.grid, planes = r.planes;
+    const bool fixed = r.fixed, y32 = r.y32, q8 = r.q8;
+    hipStream_t st = (hipStream_t)stream;
 #define ACT_INST(MODE_, FIXED_)                                                                                         \
     do {                                                                                                                \
         if (q8) hipLaunchKernelGGL((bn_act_fwd_kernel<MODE_, FIXED_, true, 1, true>), dim3(grid), dim3(256), 0, st, a);                 \
@@ -1324,8 +1344,7 @@ extern "C" int mcamd_bn_act_fwd(const mcamd_act_desc* d, void* stream) {
     } while (0)
     if (d->mode == MCAMD_DST_PLAIN) ACT_CASE(MCAMD_DST_PLAIN);
     else if (d->mode == MCAMD_DST_POOL) ACT_CASE(MCAMD_DST_POOL);
-    else if (d->mode == MCAMD_DST_REORG) ACT_CASE(MCAMD_DST_REORG);
-    else MCAMD_REQUIRE(false, "bn_act_fwd: bad mode %d", d->mode);
+    else ACT_CASE(MCAMD_DST_REORG);
 #undef ACT_CASE
 #undef ACT_INST
     MCAMD_LAUNCH_CHECK("bn_act_fwd");

@@ -408,6 +408,20 @@ def bn_act_fwd(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, ds
     check(L.lib().mcamd_bn_act_fwd(C.byref(d), stream_ptr()), "mcamd_bn_act_fwd")
 
 
+ActInstance = collections.namedtuple("ActInstance", "mode fixed y32 planes planes2 q8 items grid")
+
+
+def bn_act_fwd_instance(B, H, W, C_, y, y_ld, y_choff, scale, shift, slope, mode, dst, dst_ld, dst_choff=0, dst2=None,
+                        dst2_ld=0, dst2_choff=0, border=None, planes=1, dst_plane=0, dst2_plane=0, dst_pad=0, dst2_pad=0,
+                        planes2=0, pool_act=None, pool_act_ld=0, pool_act_pad=0, dst_q8=None, dst2_q8=None):
+    """The kernel instance bn_act_fwd launches for these arguments (mcamd_bn_act_fwd_instance: host logic only, needs no
+    GPU -- the tensors only say which pointers are given and whether y is fp32); raises what bn_act_fwd would raise."""
+    d = _act_desc(**locals())
+    r = L.ActInstance()
+    check(L.lib().mcamd_bn_act_fwd_instance(C.byref(d), C.byref(r)), "mcamd_bn_act_fwd_instance")
+    return ActInstance(r.mode, bool(r.fixed), bool(r.y32), r.planes, r.planes2, bool(r.q8), r.items, r.grid)
+
+
 class _NoPtr:
     """Stands for a device buffer where only the geometry is asked (bn_act_conv1x1_ok needs no GPU)."""
     dtype = torch.float32
