@@ -1347,6 +1347,87 @@ int mcamd_wz_unpack_w4(const mcamd_wz_seg* segs, const mcamd_wz_seg* segs_dev, i
                        void* workspace, size_t workspace_bytes, void* stream, const uint8_t* shifts, int64_t shifts_cap);
 
 /* ------------------------------------------------------------------------- *
+ * Huffman-coded model files ("MCZH"; an addition beyond the reference): the device passes around the file.
+ * ------------------------------------------------------------------------- */
+/* The coded file is the "MCZW" file above with every uint8-symbol array replaced by a STREAM; it is a container of its own:
+ *   header   char magic[4] = "MCZH"; uint32 version = 1; then payload, nrec, seen as above
+ *   record   the 32-byte record header, the per-channel float arrays, the int32 exponents and the fp32 codebook byte for
+ *            byte as above (same flags, `bits`, `kept`, same rule for bit words); in the place of
+ *              the shift bytes (MCAMD_WZ_W4)     a stream of the n / 32 bytes,                        alphabet A = 12
+ *              the bit words (MCAMD_WZ_F_BITS)   a stream of the 8 ceil(n / 64) bytes of the words,   A = 256
+ *              the values, MCAMD_WZ_FP8          a stream of the stored e4m3 bytes,                   A = 256
+ *              the values, MCAMD_WZ_CODE         a stream of one symbol per stored code,              A = 2^bits
+ *              the values, MCAMD_WZ_W4           a stream of one symbol per stored nibble code,       A = 16
+ *            MCAMD_WZ_FP16 and MCAMD_WZ_FP32 values stay the raw arrays of the "MCZW" file.
+ *   stream   uint32 mode (0 raw, 1 Huffman); uint32 A; uint64 nsym; then
+ *     mode 0   the array exactly as the "MCZW" file stores it (codes packed at their width), padded to 8 bytes
+ *     mode 1   uint64 nbits
+ *              uint8  length[A]                                 0 = symbol absent, else 1..MCAMD_HZ_MAXLEN; padded to 8 bytes
+ *              uint32 chunk_bit0[ceil(nsym / MCAMD_HZ_CHUNK)]   bit position of each chunk's first code; padded to 8 bytes
+ *              uint64 bits[ceil(nbits / 64)]
+ * Codes are canonical (RFC 1951, 3.2.2): the symbols with a non-zero length, in (length, symbol) order, take increasing
+ * code values.  A code's bits go most significant first into successive bit positions; position p is bit p % 64 of word
+ * p / 64; the tail bits of the last word are 0.  A stream with one distinct symbol gives it length 1 and code 0; a stream
+ * with nsym == 0 is mode 0 with no body.  The writer chooses mode 1 iff the mode-1 body, padding included, is strictly
+ * smaller than the mode-0 body and nbits < 2^32: a coded file exceeds its "MCZW" twin by at most 16 bytes per stream.
+ * The lengths are in the file (a length-limited Huffman code of the stream's histogram, compress.huffman_lengths): no
+ * reader recomputes them.  A reader refuses lengths whose Kraft sum is not 1 (1/2 for a single symbol). */
+#define MCAMD_HZ_MAXLEN 12
+#define MCAMD_HZ_CHUNK 1024 /* symbols per chunk: one chunk_bit0 entry each */
+#define MCAMD_HZ_GROUP 64   /* chunks per workgroup of the histogram and decode passes */
+
+/* One stream of a pass.  All streams of a file go through ONE table: a HOST array for the checks and the grid sizes and
+ * its DEVICE copy for the kernels.  Running sums over the table, in order (checked):
+ *   block0 += ceil(ceil(nsym / MCAMD_HZ_CHUNK) / MCAMD_HZ_GROUP)
+ *   chunk0 += ceil(nsym / MCAMD_HZ_CHUNK)        encode only
+ * sym0, word0 and (decode) chunk0 are any offsets whose range lies inside the arrays given (checked before any launch). */
+typedef struct mcamd_hz_seg {
+    int64_t sym0;      /* byte offset of the stream's symbols in `syms` (histogram, encode: read) or `out` (decode: written),
+                          a multiple of 8 */
+    int64_t nsym;      /* symbols, >= 0.  histogram with `dyn`: the most the stream can have */
+    int64_t nbits;     /* encode, decode: code bits of the stream, < 2^32 and <= MCAMD_HZ_MAXLEN nsym.  histogram: unused */
+    int64_t word0;     /* encode, decode: first uint64 of the stream's code bits in `bits` */
+    int64_t chunk0;    /* encode, decode: first entry of the stream in `chunk_bit0` */
+    int64_t popc_bits; /* decode: > 0: the symbols are bit words (nsym a multiple of 8) of which the first popc_bits bits
+                          stand for weights: stats gets their population count.  0: not counted.  Otherwise unused */
+    int32_t block0;    /* first workgroup of the stream */
+    int32_t A;         /* alphabet, 1..256: a symbol >= A has no code */
+} mcamd_hz_seg;
+
+/* workspace of histogram and encode for a table of `nseg` streams and `nblocks` workgroups (the final block0 sum) */
+size_t mcamd_hz_workspace_bytes(int64_t nblocks, int32_t nseg);
+
+/* hist[s][v] (uint64 [nseg][256]) = how many symbols of stream s are v.  Each workgroup counts its MCAMD_HZ_GROUP chunks in
+ * LDS counters of its own; a second launch adds a stream's workgroups in workgroup order: integer counts in a fixed order,
+ * a function of the input only.  `dyn` (device int64 [nseg][2], or NULL) gives sym0 and nsym of every stream from the
+ * device, for symbols whose place a device pass before decided (mcamd_wz_pack's values): a pair that is negative, not a
+ * multiple of 8, longer than the table's nsym or outside syms_bytes counts as an empty stream.  Not recordable. */
+int mcamd_hz_histogram(const mcamd_hz_seg* segs, const mcamd_hz_seg* segs_dev, int32_t nseg, const uint8_t* syms,
+                       int64_t syms_bytes, const int64_t* dyn, uint64_t* hist, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* Encode: from the symbols and length (device uint8 [nseg][256], 0 = absent; a length above MCAMD_HZ_MAXLEN and a symbol
+ * >= A count as absent and take no bits) the chunk_bit0 of every stream (chunk_bit0[chunk0 ...], chunk0 the running sum)
+ * and its code bits (bits[word0 ...], ZERO `bits` first).  nbits is the caller's sum of hist[v] length[v]; no word behind
+ * ceil(nbits / 64) is written.  Launches: per-chunk bit sums -> an exclusive scan per stream, which is the file's index
+ * table -> the bits: a workgroup ORs its chunk's codes into LDS words and stores them, the first and last 32-bit word of a
+ * chunk by an integer atomic OR.  Nothing floating-point, nothing order-dependent.  Not recordable. */
+int mcamd_hz_encode(const mcamd_hz_seg* segs, const mcamd_hz_seg* segs_dev, int32_t nseg, const uint8_t* syms,
+                    int64_t syms_bytes, const uint8_t* length, uint32_t* chunk_bit0, int64_t chunk_cap, uint64_t* bits,
+                    int64_t bits_cap, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Decode: the symbols of stream s to out[sym0 ...], one lane per chunk through a 2^MCAMD_HZ_MAXLEN entry table of the stream
+ * in LDS.  chunk_bit0 and bits are read where the caller has them (chunk0 in uint32, word0 in uint64 units: an uploaded
+ * file serves as both).  A lane takes no bit at or past the end of its chunk (the next chunk's chunk_bit0; nbits for the
+ * last chunk), loads no word behind ceil(nbits / 64) and stores nothing outside its chunk's min(1024, rest) symbols.
+ * stats (device uint64 [nseg][2], cleared by the call): stats[s][0] bit 0 = a chunk of the stream did not end exactly at its
+ * end or met an unassigned code (its remaining symbols are not written), bit 1 = a decoded bit word has a bit set at or
+ * past popc_bits; stats[s][1] = the population count of the first popc_bits decoded bits.  Not recordable. */
+int mcamd_hz_decode(const mcamd_hz_seg* segs, const mcamd_hz_seg* segs_dev, int32_t nseg, const uint8_t* length,
+                    const uint32_t* chunk_bit0, int64_t chunk_cap, const uint64_t* bits, int64_t bits_cap, uint8_t* out,
+                    int64_t out_bytes, uint64_t* stats, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Weight sharing (trained quantisation by k-means; an addition beyond the reference).
  * ------------------------------------------------------------------------- */
 /* Per layer, over its KEPT weights (mask value != 0; every weight when the layer has no mask), K = 2^bits, bits 1..8.

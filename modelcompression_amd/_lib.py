@@ -172,6 +172,12 @@ class WzSeg(C.Structure):
                 ("block0", C.c_int32), ("shift0", C.c_int32)]
 
 
+class HzSeg(C.Structure):
+    """mcamd_hz_seg (include/mcamd.h)."""
+    _fields_ = [("sym0", C.c_int64), ("nsym", C.c_int64), ("nbits", C.c_int64), ("word0", C.c_int64), ("chunk0", C.c_int64),
+                ("popc_bits", C.c_int64), ("block0", C.c_int32), ("A", C.c_int32)]
+
+
 class WsSeg(C.Structure):
     """mcamd_ws_seg (include/mcamd.h)."""
     _fields_ = [("w", C.c_void_p), ("mask", C.c_void_p), ("codes", C.c_void_p), ("n", C.c_int64), ("part0", C.c_int64),
@@ -188,6 +194,7 @@ STEM_PLAN_INFO_N = 20
 WZ_FP32, WZ_FP16, WZ_FP8, WZ_CODE, WZ_W4 = 0, 1, 2, 4, 5                               # mcamd_wz_seg.kind (WZ_W4: | taps << 8)
 WZ_F_BN, WZ_F_BITS = 1, 2                                                              # record flags of a .mcz file
 WZ_BLOCK_WORDS = 64
+HZ_MAXLEN, HZ_CHUNK, HZ_GROUP = 12, 1024, 64                                            # MCAMD_HZ_*
 WS_SLAB = 4096                                                                         # MCAMD_WS_SLAB
 
 # name -> (restype, argtypes); the complete list of symbols include/mcamd.h declares.
@@ -316,6 +323,10 @@ SIGNATURES = {
     "mcamd_wz_unpack": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),
     "mcamd_wz_pack_w4": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P, _SZ, _P, _P, _I64]),
     "mcamd_wz_unpack_w4": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P, _P, _I64]),
+    "mcamd_hz_workspace_bytes": (_SZ, [_I64, _I32]),
+    "mcamd_hz_histogram": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "mcamd_hz_encode": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "mcamd_hz_decode": (C.c_int, [_P, _P, _I32, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     "mcamd_ws_workspace_bytes": (_SZ, [_I64, _I64, _I32]),
     "mcamd_ws_init": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _SZ, _P]),
     "mcamd_ws_iterate": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _SZ, _P]),

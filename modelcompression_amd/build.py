@@ -48,6 +48,7 @@ SOURCES = {
     "voc_eval.hip": ["-ffp-contract=off"],  # voc_eval's float64 arithmetic, operation by operation
     "wpack.hip": ["-ffp-contract=off"],   # compressed model files: the stored codes are pinned conversions of weight * mask
     "wshare.hip": ["-ffp-contract=off"],  # weight sharing: float64 sums and divisions, operation by operation
+    "huff.hip": [],                       # Huffman-coded model files: integer passes only
 }
 
 

@@ -558,12 +558,13 @@ class Darknet(nn.Module):
                     model = self.models[ind]
                     save_fc(fp, model[0] if block['activation'] != 'linear' else model)
 
-    def save_compressed(self, outfile, payload="fp16", layers=None):
+    def save_compressed(self, outfile, payload="fp16", layers=None, entropy=None):
         """Write a compressed model file (an addition beyond the reference; compress.save_compressed).
         payload "shared": codebooks + narrow codes of the layers set_codebooks tied; payload "w4": the 4-bit
-        codes, group shifts and filter exponents the "fp8-w4" engine consumes."""
+        codes, group shifts and filter exponents the "fp8-w4" engine consumes.  entropy "huffman": the coded
+        container, which load_weights and load_compressed read like the plain one."""
         from . import compress
-        compress.save_compressed(self, outfile, payload, layers)
+        compress.save_compressed(self, outfile, payload, layers, entropy)
 
     def load_compressed(self, weightfile, set_masks=True):
         """Read a compressed model file; returns the kept-bit masks (compress.load_compressed).  A "shared" file also

@@ -1520,6 +1520,156 @@ def wz_unpack(items, words, exps, values, shifts=None):
                                      stream_ptr(), ptr(shifts), shifts.numel() if shifts is not None else 0), "mcamd_wz_unpack_w4")
 
 
+# ----------------------------------------------------------------------------- Huffman-coded model files
+def _hz_table(spans, device, encode=False):
+    """spans: dicts(sym0, nsym, A[, nbits, word0, chunk0, popc_bits]) -> (host mcamd_hz_seg array, its device copy, workgroups,
+    chunks, code words).  block0 is the header's running sum; word0 and chunk0 default to their running sums (encode lays both
+    out that way)."""
+    arr = (L.HzSeg * len(spans))()
+    blocks = chunks = words = 0
+    for a, sp in zip(arr, spans):
+        nsym, nbits = int(sp["nsym"]), int(sp.get("nbits", 0))
+        nc = (nsym + L.HZ_CHUNK - 1) // L.HZ_CHUNK
+        a.sym0, a.nsym, a.nbits, a.A, a.popc_bits = int(sp["sym0"]), nsym, nbits, int(sp["A"]), int(sp.get("popc_bits", 0))
+        a.block0 = blocks
+        a.word0, a.chunk0 = (words, chunks) if encode else (int(sp.get("word0", words)), int(sp.get("chunk0", chunks)))
+        blocks += (nc + L.HZ_GROUP - 1) // L.HZ_GROUP
+        chunks += nc
+        words += (nbits + 63) // 64
+    dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return arr, dev, blocks, chunks, words
+
+
+def _hz_lengths(lengths, device):
+    """A list of per-stream code lengths (uint8 arrays of up to 256 entries) -> uint8 [nseg][256] on the device."""
+    import numpy as np
+    table = np.zeros((len(lengths), 256), dtype=np.uint8)
+    for row, l in zip(table, lengths):
+        l = l.cpu().numpy() if isinstance(l, torch.Tensor) else np.asarray(l)
+        row[:l.size] = l.reshape(-1)
+    return torch.from_numpy(table).to(device)
+
+
+def _hz_buffer(buf, name):
+    _need_cuda(buf)
+    if buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.dim() != 1:
+        raise L.McamdError("%s: the symbols must be a contiguous 1-d uint8 tensor" % name)
+
+
+def hz_histogram_at(buf, spans, dyn=None):
+    """int64 [len(spans)][256]: how often every byte value occurs in each stream of the uint8 device tensor `buf`
+    (mcamd_hz_histogram).  spans: dicts(sym0, nsym, A).  dyn (int64 [len(spans)][2] on the device, optional): sym0 and nsym of
+    every stream as a device pass left them; a span's nsym is then the most the stream can have."""
+    _hz_buffer(buf, "hz_histogram")
+    arr, table, blocks, _, _ = _hz_table(spans, buf.device)
+    if dyn is not None and (dyn.dtype != torch.int64 or not dyn.is_contiguous() or tuple(dyn.shape) != (len(spans), 2)
+                            or dyn.device != buf.device):
+        raise L.McamdError("hz_histogram: `dyn` must be a contiguous int64 [streams][2] tensor on the symbols' device")
+    hist = torch.empty(len(spans), 256, dtype=torch.int64, device=buf.device)
+    ws = torch.empty(int(L.lib().mcamd_hz_workspace_bytes(blocks, len(spans))), dtype=torch.uint8, device=buf.device)
+    check(L.lib().mcamd_hz_histogram(arr, ptr(table), len(spans), ptr(buf), buf.numel(), ptr(dyn), ptr(hist), ptr(ws), ws.numel(),
+                                     stream_ptr()), "mcamd_hz_histogram")
+    return hist
+
+
+def hz_encode_at(buf, spans, lengths):
+    """(chunk_bit0 int32 [sum of chunks], bits int64 [sum of ceil(nbits / 64)]) of the streams of `buf` under `lengths` (one
+    uint8 array per stream), both in span order (mcamd_hz_encode).  spans: dicts(sym0, nsym, A, nbits), nbits the sum of
+    count * length over the stream's histogram."""
+    _hz_buffer(buf, "hz_encode")
+    arr, table, blocks, chunks, words = _hz_table(spans, buf.device, encode=True)
+    ctab = torch.empty(max(chunks, 1), dtype=torch.int32, device=buf.device)
+    bits = torch.zeros(max(words, 1), dtype=torch.int64, device=buf.device)
+    lens = _hz_lengths(lengths, buf.device)
+    ws = torch.empty(int(L.lib().mcamd_hz_workspace_bytes(blocks, len(spans))), dtype=torch.uint8, device=buf.device)
+    check(L.lib().mcamd_hz_encode(arr, ptr(table), len(spans), ptr(buf), buf.numel(), ptr(lens), ptr(ctab), chunks, ptr(bits), words,
+                                  ptr(ws), ws.numel(), stream_ptr()), "mcamd_hz_encode")
+    return ctab[:chunks], bits[:words]
+
+
+def hz_decode_at(spans, lengths, chunk_bit0, bits, out):
+    """Decode the streams into the uint8 device tensor `out` (mcamd_hz_decode) -> stats int64 [len(spans)][2] on the device:
+    [s][0] bit 0 = the stream is damaged, bit 1 = a decoded bit word has a bit set at or past popc_bits; [s][1] = the set
+    bits among the first popc_bits.  spans: dicts(sym0, nsym, A, nbits, word0, chunk0[, popc_bits]): where the stream's
+    symbols go in `out`, its code words lie in `bits` (int64) and its chunk table lies in `chunk_bit0` (int32)."""
+    _hz_buffer(out, "hz_decode")
+    _need_cuda(chunk_bit0, bits)
+    if chunk_bit0.dtype != torch.int32 or bits.dtype != torch.int64 or not chunk_bit0.is_contiguous() or not bits.is_contiguous():
+        raise L.McamdError("hz_decode: chunk_bit0 must be a contiguous int32 and bits a contiguous int64 tensor")
+    arr, table, _, _, _ = _hz_table(spans, out.device)
+    lens = _hz_lengths(lengths, out.device)
+    stats = torch.empty(len(spans), 2, dtype=torch.int64, device=out.device)
+    check(L.lib().mcamd_hz_decode(arr, ptr(table), len(spans), ptr(lens), ptr(chunk_bit0), chunk_bit0.numel(), ptr(bits), bits.numel(),
+                                  ptr(out), out.numel(), ptr(stats), stream_ptr()), "mcamd_hz_decode")
+    return stats
+
+
+def _hz_cat(tensors, name):
+    """A list of uint8 device tensors -> (one buffer with every tensor at a multiple of 8 bytes, the byte offsets)."""
+    if not tensors:
+        raise L.McamdError("%s: no stream" % name)
+    for t in tensors:
+        _hz_buffer(t, name)
+    offs, total = [], 0
+    for t in tensors:
+        offs.append(total)
+        total += round_up(t.numel(), 8)
+    buf = torch.zeros(max(total, 8), dtype=torch.uint8, device=tensors[0].device)
+    for t, o in zip(tensors, offs):
+        buf[o:o + t.numel()] = t
+    return buf, offs
+
+
+def hz_histogram(streams):
+    """streams: a list of 1-d uint8 device tensors -> int64 [len(streams)][256] on the device, their byte histograms."""
+    buf, offs = _hz_cat(streams, "hz_histogram")
+    return hz_histogram_at(buf, [dict(sym0=o, nsym=t.numel(), A=256) for t, o in zip(streams, offs)])
+
+
+def hz_encode(streams, lengths, alphabets=None):
+    """streams: a list of 1-d uint8 device tensors; lengths: per stream the uint8 code lengths of its alphabet (0 = absent,
+    1..12; compress.huffman_lengths of its histogram) -> per stream dict(nsym, A, nbits, lengths, chunk_bit0 int32, bits
+    int64), device tensors.  nbits comes from one read of the streams' histograms."""
+    buf, offs = _hz_cat(streams, "hz_encode")
+    alphabets = alphabets or [256] * len(streams)
+    spans = [dict(sym0=o, nsym=t.numel(), A=int(A)) for t, o, A in zip(streams, offs, alphabets)]
+    hist = hz_histogram_at(buf, spans).cpu().numpy()
+    for sp, h, l in zip(spans, hist, lengths):
+        l = (l.cpu().numpy() if isinstance(l, torch.Tensor) else l).reshape(-1)
+        sp["nbits"] = int(sum(int(c) * int(x) for c, x in zip(h[:l.size], l)))
+    ctab, bits = hz_encode_at(buf, spans, lengths)
+    out, c0, b0 = [], 0, 0
+    for sp, l in zip(spans, lengths):
+        nc, nw = (sp["nsym"] + L.HZ_CHUNK - 1) // L.HZ_CHUNK, (sp["nbits"] + 63) // 64
+        out.append(dict(nsym=sp["nsym"], A=sp["A"], nbits=sp["nbits"], lengths=l, chunk_bit0=ctab[c0:c0 + nc], bits=bits[b0:b0 + nw]))
+        c0, b0 = c0 + nc, b0 + nw
+    return out
+
+
+def hz_decode(coded, out=None, offsets=None):
+    """coded: a list of dict(nsym, A, nbits, lengths, chunk_bit0, bits) as hz_encode returns -> (the decoded streams, uint8
+    device tensors; stats int64 [len(coded)][2] as hz_decode_at returns).  out / offsets: decode into the uint8 device tensor
+    `out`, stream s at byte offsets[s] (a multiple of 8), instead of a fresh buffer."""
+    if not coded:
+        raise L.McamdError("hz_decode: no stream")
+    dev = coded[0]["bits"].device
+    ctab = torch.cat([c["chunk_bit0"].to(torch.int32).reshape(-1) for c in coded] + [torch.zeros(1, dtype=torch.int32, device=dev)])
+    bits = torch.cat([c["bits"].to(torch.int64).reshape(-1) for c in coded] + [torch.zeros(1, dtype=torch.int64, device=dev)])
+    if out is None:
+        offsets, total = [], 0
+        for c in coded:
+            offsets.append(total)
+            total += round_up(int(c["nsym"]), 8)
+        out = torch.zeros(max(total, 8), dtype=torch.uint8, device=dev)
+    spans, c0, b0 = [], 0, 0
+    for c, o in zip(coded, offsets):
+        spans.append(dict(sym0=int(o), nsym=int(c["nsym"]), A=int(c["A"]), nbits=int(c["nbits"]), word0=b0, chunk0=c0,
+                          popc_bits=int(c.get("popc_bits", 0))))
+        c0, b0 = c0 + c["chunk_bit0"].numel(), b0 + c["bits"].numel()
+    stats = hz_decode_at(spans, [c["lengths"] for c in coded], ctab, bits, out)
+    return [out[int(o):int(o) + int(c["nsym"])] for c, o in zip(coded, offsets)], stats
+
+
 # ----------------------------------------------------------------------------- weight sharing (DESIGN.md 3u)
 class WsTable:
     """Every layer of a weight-sharing pass through one mcamd_ws_seg table (include/mcamd.h), with the arrays the passes

@@ -39,7 +39,8 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     file of that payload (compress.py) beside every .weights file saved, with the extension .mcz.
     MODEL_WEIGHT and a TEACHER path may name such a file: Darknet.load_weights recognises it, and train() resumes at the
     epoch the file's `seen` stands for (a .weights file drops `seen`, as in the reference).  None by default: the same
-    files as before.
+    files as before.  YOLOv2Train.SAVE_COMPRESSED_ENTROPY = "huffman" (an attribute too) makes that file a Huffman-coded one
+    (DESIGN.md 3z), which load_weights reads the same way; None by default.
 """
 import os
 
@@ -221,6 +222,8 @@ class YOLOv2Train():
     # "fp32" / "fp16" / "fp8": train() writes a compressed model file of that payload (compress.py) beside every .weights file
     # it saves.  An attribute, like PASCALVOCEval.fused, not a keyword: train() keeps its signature.
     SAVE_COMPRESSED = None
+    # None / "huffman": the entropy keyword of that save_compressed call ("huffman": a coded "MCZH" file)
+    SAVE_COMPRESSED_ENTROPY = None
     # bits, or a dict of share.kmeans_share keywords: the default of train()'s SHARE keyword (module docstring)
     SHARE = None
     _share_arg = None
@@ -247,6 +250,8 @@ class YOLOv2Train():
         SAVE_COMPRESSED = self.SAVE_COMPRESSED
         if SAVE_COMPRESSED not in (None, "fp32", "fp16", "w4", "fp8", "shared"):
             raise ValueError('train: SAVE_COMPRESSED must be None, "fp32", "fp16", "w4", "fp8" or "shared", got %r' % (SAVE_COMPRESSED,))
+        if self.SAVE_COMPRESSED_ENTROPY not in (None, "huffman"):
+            raise ValueError('train: SAVE_COMPRESSED_ENTROPY must be None or "huffman", got %r' % (self.SAVE_COMPRESSED_ENTROPY,))
         if SHARE is not None and not isinstance(SHARE, dict):
             SHARE = dict(bits=SHARE)
         if SHARE is not None and not isinstance(SHARE.get("bits", 4), dict):
@@ -436,7 +441,7 @@ class YOLOv2Train():
             return
         name = os.path.splitext(weights_name)[0] + '.mcz'
         logging('save compressed weights (%s) to %s' % (payload, name))
-        self.model.save_compressed(name, payload)
+        self.model.save_compressed(name, payload, entropy=self.SAVE_COMPRESSED_ENTROPY)
 
     def _make_teacher(self, TEACHER, DISTILL, MODEL_CFG, dev):
         """(teacher, loss) of the TEACHER / DISTILL keywords, (None, None) without a teacher.  Called after the model is

@@ -11,8 +11,14 @@ time to write and read them.
          time around the call with a device synchronise on both sides, files in a temporary directory (page cache warm for
          every leg alike).  Quoted: the median of the samples and their spread.
 
+  huffman  the Huffman-coded container: for the same three models and every payload, the "shared" payload at 4
+         and 8 bits included, the exact size of the plain file and of its coded twin (the bytes mode lists the coded size too);
+         and on the weight_prune(80) model save_compressed and load-to-device with entropy=None against "huffman" for the
+         "fp16", "fp8" and "shared" (4 bits) payloads, legs alternated as above.
+
 usage: python tools/compress_bench.py [--json]
---json writes the result to profiles/compress_bench.json."""
+       python tools/compress_bench.py huffman [--json]
+--json writes the result to profiles/compress_bench.json (huffman: profiles/huffman_bench.json)."""
 import json
 import os
 import sys
@@ -35,7 +41,97 @@ def spread(v):
     return 100.0 * (max(v) - min(v)) / min(v)
 
 
+def huffman(argv):
+    """The Huffman-coded container beside the plain one: exact bytes of every model and payload, and on the
+    weight_prune(80) model the time of save_compressed and of load-to-device with entropy=None against "huffman"."""
+    import copy
+    import torch
+    from modelcompression_amd import compress, nets, share, YOLOV2_VOC_CFG
+    from modelcompression_amd.pruning.weightPruning.methods import nm_prune, weight_prune
+    from modelcompression_amd.synthetic import init_synthetic
+
+    dev = torch.device("cuda", 0)
+    result = {"model": "YOLOv2-VOC, seeded synthetic weights", "bytes": {}, "streams": {}, "time": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        timed = {}
+        for name, prune in (("dense", None), ("weight_prune(80)", lambda m: weight_prune(m, 80.0)), ("nm_prune", nm_prune)):
+            m = init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), seed=0).to(dev)
+            if prune is not None:
+                m.set_masks(prune(m))
+            plain = os.path.join(tmp, "m.weights")
+            m.save_weights(plain)
+            row = {"float32 .weights": os.path.getsize(plain)}
+            variants = [(p, m, p) for p in PAYLOADS]
+            for bits in (4, 8):
+                t = copy.deepcopy(m)
+                t.set_codebooks(share.kmeans_share(t, bits=bits))
+                variants.append(("shared %d bits" % bits, t, "shared"))
+            for label, model, payload in variants:
+                a, b = os.path.join(tmp, "a.mcz"), os.path.join(tmp, "b.mcz")
+                model.save_compressed(a, payload)
+                model.save_compressed(b, payload, entropy="huffman")
+                info = compress.compressed_info(b)
+                assert info["plain_bytes"] == os.path.getsize(a) and info["bytes"] == os.path.getsize(b)
+                check = os.path.join(tmp, "c.mcz")
+                compress.transcode(b, check, None)               # the coded file holds the plain one, byte for byte
+                assert open(check, "rb").read() == open(a, "rb").read(), (name, label)
+                row[label] = {"bytes": info["plain_bytes"], "huffman_bytes": info["bytes"],
+                              "ratio": round(info["dense_bytes"] / info["plain_bytes"], 3), "huffman_ratio": round(info["ratio"], 3)}
+                per = {}
+                for l in info["layers"]:
+                    for s in l["streams"]:
+                        e = per.setdefault(s["name"] if s["name"] != "codes" else l["kind"] + " codes",
+                                           {"symbols": 0, "raw_bytes": 0, "bytes": 0})
+                        e["symbols"] += s["nsym"]
+                        e["raw_bytes"] += s["raw_bytes"]
+                        e["bytes"] += s["bytes"]
+                for e in per.values():
+                    e["bits_per_symbol"] = round(8.0 * e["bytes"] / max(e["symbols"], 1), 3)
+                result["streams"]["%s, %s" % (name, label)] = per
+                if name == "weight_prune(80)" and label in ("fp16", "fp8", "shared 4 bits"):
+                    timed[label] = (model, payload)
+            result["bytes"][name] = row
+            print("%-18s %12d bytes dense float32; " % (name, row["float32 .weights"])
+                  + ", ".join("%s %d -> %d (%.2fx -> %.2fx)" % (k, v["bytes"], v["huffman_bytes"], v["ratio"], v["huffman_ratio"])
+                              for k, v in row.items() if isinstance(v, dict)))
+
+        def load(path):
+            r = nets.Darknet(YOLOV2_VOC_CFG).to(dev)
+            r.load_weights(path)
+            return r
+
+        legs = {}
+        for label, (model, payload) in timed.items():
+            for entropy in (None, "huffman"):
+                path = os.path.join(tmp, "t_%s_%s.mcz" % (label.replace(" ", ""), entropy))
+                tag = "%s, entropy=%r" % (label, entropy)
+                legs["save_compressed " + tag] = lambda model=model, payload=payload, path=path, entropy=entropy: \
+                    model.save_compressed(path, payload, entropy=entropy)
+                legs["load to device " + tag] = lambda path=path: load(path)
+        samples = {k: [] for k in legs}
+        for rnd in range(ROUNDS + 1):
+            for k, fn in legs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if rnd:
+                    samples[k].append(1e3 * (time.perf_counter() - t0))
+        for k, v in samples.items():
+            result["time"][k] = {"ms": v, "median_ms": median(v), "spread_percent": spread(v)}
+            print("%-52s median %9.1f ms (spread %.0f %%)" % (k, median(v), spread(v)))
+        result["time"]["rounds"] = ROUNDS
+        result["time"]["model"] = "weight_prune(80); legs alternate in one process, one warm-up round"
+    if "--json" in argv:
+        with open(os.path.join(ROOT, "profiles", "huffman_bench.json"), "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print("wrote profiles/huffman_bench.json")
+
+
 def main(argv):
+    if "huffman" in argv:
+        return huffman(argv)
     import torch
     from modelcompression_amd import compress, nets, YOLOV2_VOC_CFG
     from modelcompression_amd.pruning.weightPruning.methods import nm_prune, weight_prune
@@ -64,9 +160,14 @@ def main(argv):
                 assert info["bytes"] == os.path.getsize(path) and info["dense_bytes"] == row["float32 .weights"]
                 row[payload] = {"bytes": info["bytes"], "ratio": round(info["ratio"], 3), "kept": info["kept"],
                                 "weights": info["weights"]}
+                m.save_compressed(path, payload, entropy="huffman")          # the coded container
+                coded = compress.compressed_info(path)
+                assert coded["plain_bytes"] == info["bytes"]
+                row[payload].update(huffman_bytes=coded["bytes"], huffman_ratio=round(coded["ratio"], 3))
             result["bytes"][name] = row
             print("%-18s %12d bytes dense float32; " % (name, row["float32 .weights"])
-                  + ", ".join("%s %d (%.2fx)" % (p, row[p]["bytes"], row[p]["ratio"]) for p in PAYLOADS))
+                  + ", ".join("%s %d (%.2fx), coded %d (%.2fx)" % (p, row[p]["bytes"], row[p]["ratio"], row[p]["huffman_bytes"],
+                                                                   row[p]["huffman_ratio"]) for p in PAYLOADS))
 
         m = models["weight_prune(80)"]
         plain, packed = os.path.join(tmp, "t.weights"), os.path.join(tmp, "t.mcz")

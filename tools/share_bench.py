@@ -9,7 +9,8 @@ and the per-step projection cost, what the "shared" compressed model file weighs
             plain and followed by project_codebooks() as train(SHARE=4) runs it: alternated windows of STEPS steps after
             their own warm-up.  Quoted: medians and spreads.
   bytes     the dense, weight_prune(80) and nm_prune models tied at 4 and 8 bits: the exact size of the "shared" file beside
-            the fp16 and fp8 payloads, and each ratio against the dense float32 .weights file.  Not timed.
+            the fp16 and fp8 payloads, each also as its Huffman-coded twin (entropy="huffman"), and each ratio
+            against the dense float32 .weights file.  Not timed.
   accuracy  a weight_prune(80) model against itself tied at 4 bits: rel-L2 of the eval-mode logits on held-out synthetic
             images, before and after STEPS tied training steps (train()'s SGD rule + project_codebooks) on one synthetic
             batch; the untied model takes the same steps for comparison.  A RANDOM-INIT network on synthetic images: an
@@ -206,6 +207,8 @@ def run_bytes(want_json):
             for payload in ("fp16", "fp8"):
                 m.save_compressed(path, payload)
                 row[payload] = os.path.getsize(path)
+                m.save_compressed(path, payload, entropy="huffman")          # the coded container
+                row[payload + " huffman"] = os.path.getsize(path)
             for bits in (4, 8):
                 t = copy.deepcopy(m)
                 t.set_codebooks(share.kmeans_share(t, bits=bits))
@@ -217,6 +220,10 @@ def run_bytes(want_json):
                 assert all(torch.equal(a.weight.data, b.weight.data)
                            for (_, a), (_, b) in zip(share._blocks(t), share._blocks(r))), "the file is not lossless"
                 row["shared %d bits" % bits] = info["bytes"]
+                t.save_compressed(path, "shared", entropy="huffman")
+                coded = compress.compressed_info(path)
+                assert coded["plain_bytes"] == info["bytes"] and coded["bytes"] == os.path.getsize(path)
+                row["shared %d bits huffman" % bits] = coded["bytes"]
                 del t, r
             row["ratio"] = {k: round(row["float32 .weights"] / v, 3) for k, v in row.items() if k != "float32 .weights"}
             doc[name] = row
