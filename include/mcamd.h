@@ -360,6 +360,38 @@ int mcamd_conv_fwd_q8_splitk(const mcamd_conv_geom* g, const void* x8, const voi
                              size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Block-sparse form of the quantised block (an addition beyond the reference; conv_q8_bsparse.hip, Darknet.precision =
+ * "fp8-block"): mcamd_conv_fwd_q8 on its 64-filter x 128-pixel tile, taking the 64-byte K chunks of each N
+ * tile from a list as mcamd_conv_fwd_bsparse does.  The fp8 K order [channel block of 64][tap][64 channels] makes chunk q one
+ * (channel block, tap) pair of 64 filters: one block of block_prune's masks (cin % 64 == 0, so kb = 64).
+ *   lists     count: int32 [ntiles], ntiles = ceil(cout / 64); list: int32 [ntiles][nchunks], nchunks = k*k * cin / 64.
+ *             Entries [0, count[nt]) of row nt are the chunks tile nt multiplies, ascending.
+ *   operands  exactly mcamd_conv_fwd_q8's: mcamd_pack_q8's bytes [Npad][k*k * cin] and exponents, the same byte buffer.
+ * A chunk whose 64 x 64 weight bytes are all zero codes (0x00 or 0x80) adds +-0 to accumulators that start at +0: in the
+ * default MFMA form a launch on mcamd_q8_bsparse_lists' lists equals the same launch on full lists bit for bit, and that one
+ * feeds every accumulator mcamd_conv_fwd_q8's instruction sequence, so it equals that entry bit for bit.  The same holds
+ * on the fp8 MFMA (MCAMD_Q8_MFMA=1), by measurement: all-zero A bytes leave C as it is (the tests assert it).
+ * ------------------------------------------------------------------------- */
+/* 1: the entries below accept this geometry: what mcamd_conv_fwd_q8_ok accepts, with cin % 64 == 0 and pad == 0. */
+int32_t mcamd_conv_fwd_q8_bsparse_ok(const mcamd_conv_geom* g);
+/* Sizes of the lists (int32 entries): out[0] = ntiles = ceil(cout / 64) counts, out[1] = ntiles * nchunks list entries,
+ * nchunks = k*k * cin / 64. */
+int mcamd_q8_bsparse_elems(const mcamd_conv_geom* g, int64_t out[2]);
+/* count[nt] and list[nt][0 .. count[nt]) from mcamd_pack_q8's bytes wq [Npad][k*k * cin]: the chunks q with any byte b,
+ * b & 0x7f != 0 (both e4m3 zeros are zeros), in rows [64 nt, 64 nt + 64), columns [64 q, 64 q + 64), ascending.  One wave
+ * ballot per (tile, chunk) and a scan in q order: no atomics, no host synchronisation.  Entries behind the count are written
+ * as 0.  Refused above 8192 chunks.  From the bytes, not the mask: a kept weight that rounds to a zero byte is skipped too. */
+int mcamd_q8_bsparse_lists(const mcamd_conv_geom* g, const void* wq, int32_t* count, int32_t* list, void* stream);
+/* mcamd_conv_fwd_q8 over the listed chunks: epilogue mode MCAMD_EPI_PAD_F16 only; dst_mode PLAIN / POOL / REORG, y2, y_f8 /
+ * y2_f8 and the overflow flag as there.  A count outside [0, nchunks] or an index outside [0, nchunks) is clamped into its
+ * range.  count == 0: the tile's outputs are leaky(shift_f). */
+int mcamd_conv_fwd_q8_bsparse(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp, const int32_t* count,
+                              const int32_t* list, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream);
+/* The kernel instance mcamd_conv_fwd_q8_bsparse launches for this geometry (host logic only, no GPU): out as
+ * mcamd_conv_fwd_q8_info's -- always the 64 x 128 tile with a 3-stage ring, in the MFMA form MCAMD_Q8_MFMA selects. */
+int mcamd_conv_fwd_q8_bsparse_info(const mcamd_conv_geom* g, int32_t out[7]);
+
+/* ---------------------------------------------------------------------------
  * fp8 inference of slim_export models (an addition beyond the reference): the fp8 block above for an input
  * channel count that is a multiple of 8 only, and with the border table of a conv that lost input channels (slim.py) in
  * the epilogue.  With cin_pad = round_up(cin, 64):

@@ -232,6 +232,11 @@ SIGNATURES = {
     "mcamd_conv_fwd_q8_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I32)]),
     "mcamd_conv_fwd_q8_splitk_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, C.POINTER(SplitkInfo)]),
     "mcamd_conv_fwd_q8_splitk": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _I32, _P, _SZ, _P]),
+    "mcamd_conv_fwd_q8_bsparse_ok": (_I32, [C.POINTER(ConvGeom)]),
+    "mcamd_q8_bsparse_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
+    "mcamd_q8_bsparse_lists": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P]),
+    "mcamd_conv_fwd_q8_bsparse": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _P]),
+    "mcamd_conv_fwd_q8_bsparse_info": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I32)]),
     "mcamd_conv_fwd_q8_slim_ok": (_I32, [C.POINTER(ConvGeom)]),
     "mcamd_q8_slim_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
     "mcamd_pack_q8_slim": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),

@@ -27,6 +27,7 @@ SOURCES = {
     "conv_q8.hip": [],
     "conv_q8_sparse.hip": [],
     "conv_q8_splitk.hip": [],             # conv_q8.hip's flags: the epilogue expression contracts the way the unsplit kernel's does
+    "conv_q8_bsparse.hip": [],            # conv_q8.hip's flags: bit-equal to that kernel on full lists
     "conv_q8_w4.hip": [],                 # conv_q8.hip's flags: bit-equal to that kernel on the expanded bytes
     "conv_stem.hip": [],
     "conv_stem_block.hip": [],

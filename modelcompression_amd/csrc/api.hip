@@ -881,6 +881,62 @@ extern "C" int mcamd_conv_fwd_q8(const mcamd_conv_geom* g, const void* x8, const
 }
 
 // ---------------------------------------------------------------------------------------
+// block-sparse fp8 forward (conv_q8_bsparse.hip; Darknet.precision = "fp8-block")
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_q8_bsparse_ok(const mcamd_conv_geom* g) {
+    return mcamd_conv_fwd_q8_ok(g) && g->cin % 64 == 0 && g->pad == 0;
+}
+
+extern "C" int mcamd_q8_bsparse_elems(const mcamd_conv_geom* g, int64_t out[2]) {
+    MCAMD_REQUIRE(g && out, "q8_bsparse_elems: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_bsparse_ok(g), "q8_bsparse_elems: geometry has no block-sparse fp8 form (mcamd_conv_fwd_q8_bsparse_ok)");
+    const long long ntiles = (g->cout + 63) / 64, nchunks = (long long)ntaps_of(g) * g->cin / 64;
+    out[0] = ntiles;             // counts
+    out[1] = ntiles * nchunks;   // list entries
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_q8_bsparse_lists(const mcamd_conv_geom* g, const void* wq, int32_t* count, int32_t* list, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "q8_bsparse_lists: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_q8_bsparse_lists(&g_, wq, count, list, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_bsparse_ok(g), "q8_bsparse_lists: geometry has no block-sparse fp8 form (mcamd_conv_fwd_q8_bsparse_ok)");
+    MCAMD_REQUIRE(wq && count && list, "q8_bsparse_lists: null pointer");
+    MCAMD_REQUIRE(((uintptr_t)wq & 15) == 0, "q8_bsparse_lists: packed weights must be 16-byte aligned");
+    return mcamd_q8_bsparse_lists_launch(wq, g->cout, g->cin, ntaps_of(g), count, list, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_q8_bsparse(const mcamd_conv_geom* g, const void* x8, const void* wq, const int32_t* wexp,
+                                         const int32_t* count, const int32_t* list, const mcamd_conv_epilogue* epi, int32_t y_f8,
+                                         int32_t y2_f8, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_bsparse: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_q8_bsparse(&g_, x8, wq, wexp, count, list, &e_, y_f8, y2_f8, s); });
+    }
+    if (check_geom(g, "conv_fwd_q8_bsparse")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_bsparse_ok(g), "conv_fwd_q8_bsparse: geometry has no block-sparse fp8 form (mcamd_conv_fwd_q8_bsparse_ok)");
+    MCAMD_REQUIRE(x8 && wq && wexp && count && list, "conv_fwd_q8_bsparse: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8_bsparse: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x8, wq, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_bsparse", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    return mcamd_conv_q8_bsparse_launch(a, wexp, count, list, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
+}
+
+// mcamd_q8_bsparse_choice()'s answer: what mcamd_conv_fwd_q8_bsparse launches for this geometry (host logic only)
+extern "C" int mcamd_conv_fwd_q8_bsparse_info(const mcamd_conv_geom* g, int32_t out[7]) {
+    MCAMD_REQUIRE(g && out, "conv_fwd_q8_bsparse_info: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_bsparse_ok(g), "conv_fwd_q8_bsparse_info: geometry has no block-sparse fp8 form (mcamd_conv_fwd_q8_bsparse_ok)");
+    const Q8Choice c = mcamd_q8_bsparse_choice((long long)g->B * g->H * g->W, g->cout);
+    out[0] = c.bmw, out[1] = c.bnp, out[2] = c.f8mfma, out[3] = c.stages, out[4] = c.mtiles, out[5] = c.ntiles, out[6] = c.grid;
+    return MCAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // split-K fp8 forward for low-batch inference (conv_q8_splitk.hip; Darknet.precision = "fp8-splitk")
 // ---------------------------------------------------------------------------------------
 // what both entries refuse, then the plan for `slices` (0 = the policy: mcamd_splitk_plan, the fp16 pair's, on 64-byte chunks)

@@ -81,7 +81,7 @@ class _Layer:
     sp_on = property(lambda self: self.form == "sparse24")
     bs_on = property(lambda self: self.form == "bsparse")
     sk_on = property(lambda self: self.form == "splitk")
-    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4"))
+    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_bsparse"))
     q8s_on = property(lambda self: self.form == "q8_sparse24")
     q8_slim = property(lambda self: self.form == "q8_slim")
 
@@ -135,6 +135,14 @@ TRAIN_GAIN = 1.1
 # is at least 10 % faster than the dense launch on every layer of conv9 .. conv22 at B = 128 (worst layer 1.15x at 0.375;
 # at 0.5 conv9 / 11 / 13 gain 4-9 % only, and from 0.625 up the 3x3 layers lose).
 BSPARSE_MAX_KEPT = 0.375
+# Darknet.precision = "fp8-block": a masked fp8 block leaves the dense fp8 launch for the block-sparse fp8 kernel
+# (csrc/conv_q8_bsparse.hip) when the kept fraction of its (64-filter tile, 64-byte K chunk) pairs is at most
+# this -- the default of Darknet.fp8_block_max_kept.  Measured by the rule of DESIGN.md 3t against the same commit's "fp8"
+# engine (tools/bsparse_bench.py --precision fp8, profiles/q8_bsparse_bench.json and q8_bsparse_bench_mfma.json):
+# the largest kept fraction at which the kernel is at least 10 % faster than the fp8 launch on every layer of conv9 .. conv22
+# at B = 128 is 0.375 in both MFMA forms (worst layer 1.16x on converted bytes, 1.15x on the fp8 MFMA; at 0.5 conv15 / conv22
+# gain 5-7 % only, and from 0.625 up the fp8-MFMA form loses on the 13x13 3x3 layers).
+Q8_BSPARSE_MAX_KEPT = 0.375
 
 
 class _Dense:
@@ -294,6 +302,53 @@ class _Q8SplitK(_Q8):
         return args, dict(kw, slices=lay.sk_slices, workspace=eng._splitk_ws)
 
 
+class _Q8BSparse(_Q8):
+    """The non-zero 64-byte K chunks of each 64-filter tile only ("fp8-block", csrc/conv_q8_bsparse.hip): _Q8's
+    bytes and exponents plus the chunk lists.  Two phases, as _BSparse: `policy` reads the packed bytes of the masked weights
+    in front of the filter compaction (the blocks it picks are exempt from it), `repacked` rebuilds the lists of the blocks
+    that took the form from the bytes the launch reads."""
+    fwd = "conv_fwd_q8_bsparse"
+    bufs = (("wq", torch.uint8), ("wexp", torch.int32), ("bs_count", torch.int32), ("bs_list", torch.int32))
+
+    def policy(self, eng, max_kept):
+        """Taken in front of every re-pack of an "fp8-block" engine: the candidates are the masked blocks _choose_q8 would give
+        form "q8" if their filters stayed uncompacted; each one's chunk lists from a temporary mcamd_pack_q8 in the layer's
+        own order (mcamd_q8_bsparse_lists), ONE host read of all counts, and a candidate is chosen when its kept-chunk
+        fraction is at most `max_kept` (0.0 chooses nothing).  Returns (the chosen layer indices, conv number -> kept
+        fraction of every candidate)."""
+        def masked(lay):
+            m = lay.conv.mask if lay.conv.mask_flag else None
+            return m is not None and m.is_cuda and m.dtype == torch.float32 and m.shape == lay.conv.weight.shape
+        cand = [lay for lay in eng.layers if masked(lay) and not lay.pad and lay.cin % 64 == 0 and lay.border is None
+                and eng._eligible(lay, compacted=False) and ops.conv_fwd_q8_bsparse_ok(lay.geom)]
+        sums = []
+        for lay in cand:
+            wq, _ = ops.pack_q8(lay.geom, lay.conv.weight.data, lay.conv.mask.contiguous())
+            sums.append(ops.q8_bsparse_lists(lay.geom, wq)[0].sum())
+        chosen, kept = [], {}
+        for lay, s_ in zip(cand, torch.stack(sums).cpu().tolist() if cand else []):
+            kept[lay.li + 1] = s_ / float(ops.q8_bsparse_elems(lay.geom)[1])    # conv number (conv1 = the first block)
+            if max_kept > 0.0 and kept[lay.li + 1] <= max_kept:
+                chosen.append(lay.li)
+        return frozenset(chosen), kept
+
+    def alloc(self, eng, lays):
+        for lay in lays:
+            for (name, dtype), n in zip(self.bufs[:2], ops.q8_elems(lay.geom_q8)):
+                if getattr(lay, name) is None or getattr(lay, name).numel() != n:
+                    setattr(lay, name, torch.zeros(n, dtype=dtype, device=eng.device))
+            nc, nl = ops.q8_bsparse_elems(lay.geom_q8)
+            if lay.bs_count is None or lay.bs_count.numel() != nc or lay.bs_list.numel() != nl:
+                lay.bs_count = torch.zeros(nc, dtype=torch.int32, device=eng.device)
+                lay.bs_list = torch.zeros(nc, nl // nc, dtype=torch.int32, device=eng.device)
+
+    def pack(self, eng, lay, w, mask):
+        ops.pack_q8(lay.geom_q8, w, mask, lay.wq, lay.wexp)
+
+    def repacked(self, eng, lay):
+        ops.q8_bsparse_lists(lay.geom_q8, lay.wq, lay.bs_count, lay.bs_list)
+
+
 class _Q8W4(_Q8):
     """An fp8 block on 4-bit weights ("fp8-w4", csrc/conv_q8_w4.hip): e2m1 nibble codes, one shift byte per group
     of 32 input channels and one exponent per filter -- 4.25 bits per weight, expanded to e4m3 bytes in the kernel's registers.
@@ -312,7 +367,7 @@ class _Q8W4(_Q8):
 
 
 _FORMS = {"dense": _Dense(), "splitk": _SplitK(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "q8": _Q8(),
-          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4()}
+          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4(), "q8_bsparse": _Q8BSparse()}
 
 
 def _probe_side_stream(device, tries=8):
@@ -388,18 +443,24 @@ class Engine:
         "fp8-w4-qat" -- 4-bit quantisation-aware training: "fp8-qat" with the weights of every fp8 block in the
         4-bit format -- in training mode every block of `fp8_layers` (`fp8_w4_layers` is the same list) re-quantises its weights
         to codes, shifts and exponents every step and runs its forward on them (mcamd_conv_fwd_q8_w4_raw); the backward is
-        "fp8-qat"'s on the values the codes stand for.  An inference-mode forward is the "fp8-w4" engine's, bit for bit."""
-        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat"):
-            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk', 'fp8-qat', 'fp8-w4' or "
-                             "'fp8-w4-qat' (got %r)" % (precision,))
+        "fp8-qat"'s on the values the codes stand for.  An inference-mode forward is the "fp8-w4" engine's, bit for bit.
+        "fp8-block" -- the "fp8" engine for block-pruned models, inference only: every masked block "fp8" would
+        run in form "q8" with its filters uncompacted, and whose kept fraction of (64-filter tile, 64-byte K chunk) pairs is at
+        most Darknet.fp8_block_max_kept, keeps its filters out of the compaction and runs the block-sparse fp8 kernel on the
+        chunks that hold a non-zero weight byte (csrc/conv_q8_bsparse.hip, `fp8_block_layers`, `fp8_block_kept`); every
+        other block runs what "fp8" runs, and with nothing chosen it is the "fp8" engine bit for bit."""
+        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat",
+                             "fp8-block"):
+            raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk', 'fp8-qat', 'fp8-w4', "
+                             "'fp8-w4-qat' or 'fp8-block' (got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat")
+        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat", "fp8-block")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_choose_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat")
+        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat", "fp8-block")
         self.qat = precision in ("fp8-qat", "fp8-w4-qat")   # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
         # "fp8-2:4": the subset of fp8_layers whose masks conform to 2:4 and that run mcamd_conv_fwd_q8_sparse24
@@ -413,6 +474,12 @@ class Engine:
         # a training engine, which has no slim blocks)
         self.q8_w4 = precision in ("fp8-w4", "fp8-w4-qat")
         self.fp8_w4_layers = []
+        # "fp8-block": the subset of fp8_layers the block policy chose and that run mcamd_conv_fwd_q8_bsparse, and the kept-chunk
+        # fraction of every candidate (conv number -> fraction); chosen when the masks, the weights or
+        # Darknet.fp8_block_max_kept change (_Q8BSparse.policy; the chosen blocks share `_bs_exempt` with sparse = "block")
+        self.q8_bsparse = precision == "fp8-block"
+        self.fp8_block_layers = []
+        self.fp8_block_kept = {}
         self.qbufs = {}
         self._qld = {}                         # buffer id -> bytes per pixel of its byte buffer (_choose_q8)
         self.grad_scale = float(grad_scale)
@@ -914,6 +981,8 @@ class Engine:
         exempt = frozenset()
         if sparse == "block":
             exempt, self.bsparse_kept = _FORMS["bsparse"].policy(self, max_kept)
+        elif self.q8_bsparse and max_kept is not None:
+            exempt, self.fp8_block_kept = _FORMS["q8_bsparse"].policy(self, max_kept)
         key = (mkeys, exempt, sparse, max_kept, splitk)
         if key != self._form_key:          # masks are static during retraining: planned once
             self._choose_forms(key)
@@ -1032,7 +1101,8 @@ class Engine:
     def _choose_forms(self, key):
         """Every block's inference form (`_Layer.form`, exactly one of _FORMS), chosen when `key` changes: the mask keys,
         the block-sparse policy's choice, Darknet.sparse, sparse_max_kept and Darknet.splitk (pack).  In this order:
-          1. (pack) the block-sparse policy has read the masked weights; the blocks it chose are exempt from
+          1. (pack) the block-sparse policy (sparse = "block", or _Q8BSparse.policy under "fp8-block": there a chosen block that
+             _choose_q8 then gives form "q8" takes "q8_bsparse") has read the masked weights; the blocks it chose are exempt from
           2. filter compaction and folding, planned again when the masks or that choice changed;
           3. then fp8 (every eligible block of an fp8 engine; under "fp8-splitk" behind it: every block of form "q8" -- not the
              slim ones -- whose launch the split-K policy gives two slices or more, mcamd_conv_fwd_q8_splitk_info; under
@@ -1073,6 +1143,10 @@ class Engine:
                     info = ops.conv_fwd_q8_splitk_info(lay.geom_q8, lay.mode)
                     if info.slices >= 2:
                         lay.form, lay.sk_slices = "q8_splitk", info.slices
+            if self.q8_bsparse:          # (a chosen block whose input was permuted or folded after all did not get form "q8")
+                for lay in self.layers:
+                    if lay.li in exempt and lay.form == "q8" and ops.conv_fwd_q8_bsparse_ok(lay.geom_q8):
+                        lay.form = "q8_bsparse"
             if self.q8_w4:               # (the slim blocks keep their form, as under "fp8-splitk")
                 for lay in self.layers:
                     if lay.form == "q8" and ops.conv_fwd_q8_w4_ok(lay.geom_q8):
@@ -1102,7 +1176,8 @@ class Engine:
             _FORMS[name].alloc(self, lays)
         nums = lambda *names: [lay.li + 1 for lay in self.layers if lay.form in names]
         self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
-        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4")
+        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_bsparse")
+        self.fp8_block_layers = nums("q8_bsparse")
         self.fp8_sparse_layers, self.fp8_splitk_layers, self.fp8_w4_layers = nums("q8_sparse24"), nums("q8_splitk"), nums("q8_w4")
         self._form_key = key
 
@@ -1587,7 +1662,9 @@ class Engine:
         if mode is not None and (self.precise or self.q8):
             raise McamdError("sparse=%r runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r%s"
                              % (mode, self.precision, "; 2:4 masks on the fp8 engine: model.precision = 'fp8-2:4' with "
-                                "model.sparse = None" if self.q8 and mode == "2:4" else ""))
+                                "model.sparse = None" if self.q8 and mode == "2:4" else
+                                "; block masks on the fp8 engine: model.precision = 'fp8-block' with model.sparse = None"
+                                if self.q8 and mode == "block" else ""))
         splitk = bool(getattr(self.model, "splitk", False)) and not training
         if splitk and (self.precise or self.q8):
             raise McamdError("splitk=True runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r%s"
@@ -1596,6 +1673,8 @@ class Engine:
         if mode not in (None, "2:4", "block"):
             raise McamdError("sparse must be None, '2:4' or 'block' (got %r)" % (mode,))
         max_kept = float(getattr(self.model, "sparse_max_kept", BSPARSE_MAX_KEPT)) if mode == "block" else None
+        if self.q8_bsparse and not training:
+            max_kept = float(getattr(self.model, "fp8_block_max_kept", Q8_BSPARSE_MAX_KEPT))
         self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept)
         self.serial += 1
         tin = self.layers[0].tin

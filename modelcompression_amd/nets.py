@@ -315,7 +315,14 @@ class Darknet(nn.Module):
         # fp8 block re-quantised to the "fp8-w4" format every step: the training-mode forward multiplies the codes the block would
         # be deployed with, the backward is straight-through on the values they stand for; in eval mode it is the "fp8-w4" engine,
         # bit for bit.  The fine-tuning step in front of deployment under "fp8-w4"; `sparse` and `splitk` stay off.
+        # "fp8-block" (eval only, an addition beyond the reference): the "fp8" engine for block-pruned models -- every masked fp8
+        # block whose kept fraction of (64-filter tile, 64-byte K chunk) pairs is at most `fp8_block_max_kept` keeps its filters
+        # out of the compaction and multiplies only the chunks that hold a non-zero weight byte
+        # (engine.Engine.fp8_block_layers / fp8_block_kept, csrc/conv_q8_bsparse.hip); with nothing chosen it is
+        # the "fp8" engine bit for bit.  What block_prune + "fp8-qat" fine-tuning deploy to; `sparse` and `splitk` stay off.
         self.precision = os.environ.get("MCAMD_PRECISION", "auto")
+        from .engine import Q8_BSPARSE_MAX_KEPT
+        self.fp8_block_max_kept = Q8_BSPARSE_MAX_KEPT    # the policy constant of "fp8-block" (engine.py)
         # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA
         # (engine.Engine.sparse_layers).  "block" runs every eligible masked block on the block-sparse kernel

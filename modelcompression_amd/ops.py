@@ -1228,6 +1228,60 @@ def conv_fwd_q8_splitk(g, x8, wq, wexp, y, y_ld, y_choff=0, scale=None, shift=No
     return workspace
 
 
+# ... over the non-zero K chunks of each 64-filter tile only (csrc/conv_q8_bsparse.hip)
+def conv_fwd_q8_bsparse_ok(g):
+    """Does mcamd_conv_fwd_q8_bsparse accept this geometry?  (Shared by the engine and the tests; needs no device.)"""
+    return bool(L.lib().mcamd_conv_fwd_q8_bsparse_ok(C.byref(g)))
+
+
+def q8_bsparse_elems(g):
+    """(ntiles, ntiles * nchunks): int32 entries of the counts and of the lists (64-filter tiles, 64-byte chunks)."""
+    out = (C.c_int64 * 2)()
+    check(L.lib().mcamd_q8_bsparse_elems(C.byref(g), out), "mcamd_q8_bsparse_elems")
+    return int(out[0]), int(out[1])
+
+
+def q8_bsparse_lists(g, wq, out_count=None, out_list=None):
+    """pack_q8's weight bytes -> (count int32[ntiles], list int32[ntiles][nchunks]): per 64-filter tile the 64-byte K chunks
+    holding a non-zero e4m3 code, ascending (mcamd_q8_bsparse_lists; no host synchronisation)."""
+    _need_cuda(wq)
+    nc, nl = q8_bsparse_elems(g)
+    if out_count is None:
+        out_count = torch.empty(nc, dtype=torch.int32, device=wq.device)
+    if out_list is None:
+        out_list = torch.empty(nc, nl // nc, dtype=torch.int32, device=wq.device)
+    if out_count.numel() != nc or out_list.numel() != nl or wq.dtype != torch.uint8 or wq.numel() < q8_elems(g)[0]:
+        raise L.McamdError("q8_bsparse_lists: operand sizes do not fit the geometry")
+    check(L.lib().mcamd_q8_bsparse_lists(C.byref(g), ptr(wq), ptr(out_count), ptr(out_list), stream_ptr()), "mcamd_q8_bsparse_lists")
+    return out_count, out_list
+
+
+def conv_fwd_q8_bsparse_info(g):
+    """The kernel instance conv_fwd_q8_bsparse launches for `g` (Q8Info: always the 64 x 128 tile, 3 stages, the MFMA form
+    MCAMD_Q8_MFMA selects): mcamd_conv_fwd_q8_bsparse_info.  Needs no GPU."""
+    out = (C.c_int32 * 7)()
+    check(L.lib().mcamd_conv_fwd_q8_bsparse_info(C.byref(g), out), "mcamd_conv_fwd_q8_bsparse_info")
+    return Q8Info(*out)
+
+
+def conv_fwd_q8_bsparse(g, x8, wq, wexp, count, lst, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None,
+                        y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None, all_chunks=False):
+    """conv_fwd_q8 over the listed K chunks of each 64-filter tile (q8_bsparse_lists): the same operands, epilogue,
+    destination formats and output.  all_chunks=True (tests, tools/bsparse_bench.py) runs the same launch with full lists."""
+    nc, nl = q8_bsparse_elems(g)
+    if all_chunks:
+        nch = nl // nc
+        count = torch.full((nc,), nch, dtype=torch.int32, device=x8.device)
+        lst = torch.arange(nch, dtype=torch.int32, device=x8.device).repeat(nc, 1).contiguous()
+    _need_cuda(x8, count, lst)
+    if count.dtype != torch.int32 or lst.dtype != torch.int32 or count.numel() != nc or lst.numel() != nl or not lst.is_contiguous():
+        raise L.McamdError("conv_fwd_q8_bsparse: count / list must be contiguous int32 of %d / %d entries" % (nc, nl))
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff, overflow=overflow)
+    check(L.lib().mcamd_conv_fwd_q8_bsparse(C.byref(g), ptr(x8), ptr(wq), ptr(wexp), ptr(count), ptr(lst), C.byref(e),
+                                            int(bool(y_f8)), int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q8_bsparse")
+
+
 # ... of slim_export models (DESIGN.md 3m): cin a multiple of 8 on zero-padded weight rows, border table in the epilogue
 def conv_fwd_q8_slim_ok(g):
     """Does mcamd_conv_fwd_q8_slim accept this geometry?  (Shared by the engine and the tests; needs no device.)"""
