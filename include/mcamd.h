@@ -1526,6 +1526,63 @@ int mcamd_ws_project(const mcamd_ws_seg* segs, const mcamd_ws_seg* segs_dev, int
 int mcamd_ws_expand(const mcamd_ws_seg* segs, const mcamd_ws_seg* segs_dev, int32_t nseg, const float* codebook, int64_t cb_cap,
                     void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * First-order Taylor importance (taylor_prune; an addition beyond the reference; Molchanov et al. 2019,
+ * arXiv:1906.10771): the importance of a group S of parameters is (sum over S of g w)^2, summed over training steps.  One
+ * call between backward() and optimizer.step() adds one step's term to every accumulator of every layer: one launch over
+ * a segment table, nothing read back, no atomics, every result a function of the operands alone.
+ * ------------------------------------------------------------------------- */
+/* A CONV segment is one conv layer: w and g (its gradient) fp32 OIHW [cout][cin][khw], optionally its bias and the bias's
+ * gradient fp32 [cout] (both or neither).  With p_i = g_i * w_i rounded to fp32 (one multiply, no contraction), its three
+ * optional outputs -- a NULL one is neither computed nor written -- are
+ *   acc_w  fp32 [cout cin khw]   acc_w[i] = acc_w[i] + p_i * p_i, both operations rounded to fp32
+ *   acc_b  float64 [blocks]      cin % 32 == 0 only; the blocks and the block index of mcamd_block_scores (64 filters x kb
+ *                                channels x one tap, kb = 64 when cin % 64 == 0 else 32, ragged last filter block, index
+ *                                (fb * (cin / kb) + cb) * khw + tap).  S_b = the float64 sum of (double)p_i over the block in
+ *                                that function's order: elements numbered e = r * kb + c, lane l adds e = l, l + 64, ... in
+ *                                ascending order starting from 0.0, the 64 lane sums are combined by s[l] += s[l ^ d],
+ *                                d = 32, 16, 8, 4, 2, 1.  Then acc_b[b] = acc_b[b] + S_b * S_b: one rounded multiply, one
+ *                                rounded add.
+ *   acc_f  float64 [cout]        for a conv WITHOUT BatchNorm.  S_f = the float64 sum of (double)p_i over filter f with the
+ *                                elements in memory order, e = c * khw + tap, and the same lane and butterfly order; then
+ *                                S_f = S_f + (double)(gbias_f * bias_f) (the product rounded to fp32) when there is a bias;
+ *                                acc_f[f] = acc_f[f] + S_f * S_f.
+ * A GATE segment is one BatchNorm: w = gamma, g = dgamma, bias = beta, gbias = dbeta, fp32 [cout], cin = khw = 1, acc_f only:
+ *   t = (double)gamma * (double)dgamma + (double)beta * (double)dbeta (the products are exact, the sum is rounded once);
+ *   acc_f[c] = acc_f[c] + t * t.
+ * A conv followed by BatchNorm on batch statistics takes its filter scores from the gate: the loss does not change when
+ * such a filter is rescaled, so its own sum of g w is zero up to rounding (Euler's theorem).
+ * fp32 arrays are 4-byte aligned (a gradient may be a view into a flat buffer), float64 arrays 8-byte aligned (checked).
+ * tests/taylor_ref.py restates this in numpy. */
+#define MCAMD_TAYLOR_CONV 0
+#define MCAMD_TAYLOR_GATE 1
+typedef struct mcamd_taylor_seg {
+    void* w;        /* conv: weights; gate: gamma */
+    void* g;        /* conv: weight gradient; gate: dgamma */
+    void* bias;     /* conv: bias or NULL; gate: beta */
+    void* gbias;    /* conv: bias gradient or NULL; gate: dbeta */
+    void* acc_w;    /* read and written; NULL = not wanted */
+    void* acc_b;
+    void* acc_f;
+    int64_t wg0;    /* running sum over the table of mcamd_taylor_seg_workgroups (checked) */
+    int32_t kind;   /* MCAMD_TAYLOR_CONV / MCAMD_TAYLOR_GATE */
+    int32_t cout;   /* gate: channels */
+    int32_t cin;    /* gate: 1 */
+    int32_t khw;    /* gate: 1 */
+} mcamd_taylor_seg;
+
+/* workgroups the launch spends on one segment (wg0 is ignored); 0 for a segment mcamd_taylor_accum refuses by its shape */
+int64_t mcamd_taylor_seg_workgroups(const mcamd_taylor_seg* seg);
+
+/* One step of every segment.  `segs` is a HOST array for the checks and the grid size, `segs_dev` its DEVICE copy for the
+ * kernel.  skip: device fp32 scalar or NULL; when *skip != 0 nothing is accumulated and *steps is left alone (train.StepGuard's
+ * `found`: an overflowed or non-finite step adds nothing).  Otherwise *steps (device int32) = *steps + 1.  Launch-type:
+ * recorded into a launch plan while one is being recorded.  Refused without a launch (MCAMD_EINVAL): NULL or misaligned
+ * pointers, acc_b with cin % 32 != 0, a gate with acc_w / acc_b, a conv segment without any output, a wg0 that is not the
+ * running sum. */
+int mcamd_taylor_accum(const mcamd_taylor_seg* segs, const mcamd_taylor_seg* segs_dev, int32_t nseg, const float* skip,
+                       int32_t* steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

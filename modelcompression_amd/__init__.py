@@ -39,4 +39,8 @@ def __getattr__(name):
     if name in ("kmeans_share", "are_codebooks_consistent"):
         from . import share
         return getattr(share, name)
+    # Taylor-importance pruning (importance.py, an addition beyond the reference), the same way
+    if name in ("TaylorImportance", "taylor_prune"):
+        from . import importance
+        return getattr(importance, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -50,6 +50,7 @@ SOURCES = {
     "wpack.hip": ["-ffp-contract=off"],   # compressed model files: the stored codes are pinned conversions of weight * mask
     "wshare.hip": ["-ffp-contract=off"],  # weight sharing: float64 sums and divisions, operation by operation
     "huff.hip": [],                       # Huffman-coded model files: integer passes only
+    "taylor.hip": ["-ffp-contract=off"],  # Taylor importance: pinned fp32 / float64 products and sums
 }
 
 

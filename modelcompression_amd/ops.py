@@ -1790,3 +1790,57 @@ class WsTable:
     def expand(self):
         check(L.lib().mcamd_ws_expand(self.arr, ptr(self.table), self.nseg, ptr(self.codebook), self.codebook.numel(), stream_ptr()),
               "mcamd_ws_expand")
+
+
+# ----------------------------------------------------------------------------- Taylor importance
+class TaylorTable:
+    """Every layer of a Taylor-importance step through one mcamd_taylor_seg table (include/mcamd.h).
+
+    items: one dict per segment.  A conv segment: w, g (fp32, the weight's shape, [cout][cin]...), optional bias and gbias
+    (fp32 [cout]) and the optional outputs acc_w (fp32, the weight's shape), acc_b (float64 [blocks]), acc_f (float64 [cout]).
+    A gate segment (gate=True): w = gamma, g = dgamma, bias = beta, gbias = dbeta (fp32 [C]) and acc_f (float64 [C]).
+    steps: device int32 [1].  Built once; accumulate() is one library call on the current stream with no host read."""
+
+    def __init__(self, items, steps):
+        if not items:
+            raise L.McamdError("taylor: no segment given")
+        dev = items[0]["w"].device
+        arr = (L.TaylorSeg * len(items))()
+        wgs = 0
+        for a, it in zip(arr, items):
+            w, g, gate = it["w"], it["g"], bool(it.get("gate"))
+            f32 = [w, g, it.get("bias"), it.get("gbias"), it.get("acc_w")]
+            f64 = [it.get("acc_b"), it.get("acc_f")]
+            _need_cuda(*f32, *f64)
+            for t, dt in [(t, torch.float32) for t in f32] + [(t, torch.float64) for t in f64]:
+                if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != dev):
+                    raise L.McamdError("taylor: every array must be a contiguous %s tensor on one device" % dt)
+            cout = w.shape[0]
+            cin = 1 if gate or w.dim() < 2 else w.shape[1]
+            khw = w.numel() // (cout * cin)
+            want = {"g": w.numel(), "bias": cout, "gbias": cout, "acc_w": w.numel(), "acc_f": cout}
+            if not gate and cin % 32 == 0:
+                want["acc_b"] = ((cout + BLOCK_FILTERS - 1) // BLOCK_FILTERS) * (cin // block_kb(cin)) * khw
+            for name, n in want.items():
+                if it.get(name) is not None and it[name].numel() != n:
+                    raise L.McamdError("taylor: %s holds %d entries, %d expected" % (name, it[name].numel(), n))
+            a.w, a.g = w.data_ptr(), g.data_ptr()
+            for name in ("bias", "gbias", "acc_w", "acc_b", "acc_f"):
+                setattr(a, name, it[name].data_ptr() if it.get(name) is not None else None)
+            a.kind, a.cout, a.cin, a.khw, a.wg0 = (L.TAYLOR_GATE if gate else L.TAYLOR_CONV), cout, cin, khw, wgs
+            wgs += int(L.lib().mcamd_taylor_seg_workgroups(C.byref(a)))
+        _need_cuda(steps)
+        if steps.dtype != torch.int32 or steps.numel() != 1:
+            raise L.McamdError("taylor: steps must be a device int32 scalar")
+        self.items, self.arr, self.nseg, self.steps, self.workgroups = items, arr, len(items), steps, wgs
+        # (pinned and non-blocking: building a table is no host synchronisation)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory().to(dev, non_blocking=True)
+
+    def accumulate(self, skip=None):
+        """One step: every accumulator += this step's term, steps += 1; nothing at all when *skip != 0 (device fp32 scalar)."""
+        if skip is not None:
+            _need_cuda(skip)
+            if skip.dtype != torch.float32 or skip.numel() != 1:
+                raise L.McamdError("taylor: skip must be a device fp32 scalar")
+        check(L.lib().mcamd_taylor_accum(self.arr, ptr(self.table), self.nseg, ptr(skip), ptr(self.steps), stream_ptr()),
+              "mcamd_taylor_accum")

@@ -41,6 +41,12 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     epoch the file's `seen` stands for (a .weights file drops `seen`, as in the reference).  None by default: the same
     files as before.  YOLOv2Train.SAVE_COMPRESSED_ENTROPY = "huffman" (an attribute too) makes that file a Huffman-coded one
     (DESIGN.md 3z), which load_weights reads the same way; None by default.
+  * pruning_method = "taylor-weight" / "taylor-block" / "taylor-filter" ranks by first-order Taylor importance instead of
+    magnitude (importance.py): before pruning, YOLOv2Train.TAYLOR_STEPS batches of the training loader go
+    through forward, loss (with the distillation term when there is a TEACHER) and backward in training mode, WITHOUT an
+    optimizer step; importance.TaylorImportance.accumulate adds each step's scores in one launch, skipped on the device
+    when StepGuard flags the step.  The BatchNorm running statistics are put back afterwards.  With several ranks each
+    scores its own shard and the accumulators are all-reduced.  Every other method value behaves as before.
 """
 import os
 
@@ -62,6 +68,9 @@ from .nets import Darknet, cfg_shapes, parse_cfg  # noqa: E402
 from .pruning.weightPruning.methods import block_prune, quick_filter_prune, weight_prune  # noqa: E402
 from .pruning.weightPruning.utils import prune_rate, are_masks_consistent  # noqa: E402
 from .share import kmeans_share, are_codebooks_consistent, _bits_of  # noqa: E402
+from .importance import TaylorImportance, taylor_prune  # noqa: E402
+
+TAYLOR_METHODS = {"taylor-weight": "weight", "taylor-block": "block", "taylor-filter": "filter"}
 
 
 def logging(message):
@@ -227,6 +236,8 @@ class YOLOv2Train():
     # bits, or a dict of share.kmeans_share keywords: the default of train()'s SHARE keyword (module docstring)
     SHARE = None
     _share_arg = None
+    # batches scored before pruning by pruning_method = "taylor-*" (an attribute: train() keeps its signature)
+    TAYLOR_STEPS = 16
 
     def __init__(self):
         self.model = ''
@@ -327,7 +338,10 @@ class YOLOv2Train():
 
         masks = None
         if pruning_perc > 0:
-            if pruning_method == "filter":
+            if pruning_method in TAYLOR_METHODS:
+                masks = self._taylor_masks(TAYLOR_METHODS[pruning_method], pruning_perc, dataset, resident, shape, AUGMENT,
+                                           init_epoch, rank, world, dev, region_loss, optimizer)
+            elif pruning_method == "filter":
                 masks = quick_filter_prune(self.model, pruning_perc)
             elif pruning_method == "block":
                 masks = block_prune(self.model, pruning_perc)
@@ -337,7 +351,7 @@ class YOLOv2Train():
             self.model.set_masks(masks)
         if world > 1:
             # static weight masks: only the kept gradient entries travel (dp.py); filter masks keep the dense transport
-            reducer = dp.attach(self.model, masks=masks if (masks is not None and pruning_method != "filter") else None)
+            reducer = dp.attach(self.model, masks=masks if (masks is not None and pruning_method not in ("filter", "taylor-filter")) else None)
         if SHARE is not None:
             # every rank clusters the same broadcast weights under the same masks: the codebooks agree, nothing travels
             self.model.set_codebooks(kmeans_share(self.model, **SHARE))
@@ -434,6 +448,65 @@ class YOLOv2Train():
             self.model.save_weights(name)
             self._save_compressed(name, SAVE_COMPRESSED)
         return self.model
+
+    def _taylor_masks(self, granularity, pruning_perc, dataset, resident, shape, AUGMENT, epoch, rank, world, dev, region_loss,
+                      optimizer):
+        """pruning_method = "taylor-*": score TAYLOR_STEPS batches (no optimizer step), then taylor_prune.  The loader is
+        built the way the training loop builds its own; the model's buffers (BatchNorm running statistics) are restored."""
+        nsteps = int(self.TAYLOR_STEPS)
+        if nsteps < 1:
+            raise ValueError("train: TAYLOR_STEPS must be at least 1, got %r" % (self.TAYLOR_STEPS,))
+        per_rank = max(1, self.batch_size // world)
+        sampler = torch.utils.data.distributed.DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 else None
+        if sampler is not None:
+            sampler.set_epoch(epoch)
+        if AUGMENT:
+            dataset.set_epoch(epoch)
+        augmenter = DeviceAugmenter(shape, dev, resident) if AUGMENT or resident is not None else None
+        loader = torch.utils.data.DataLoader(dataset, batch_size=per_rank, shuffle=(sampler is None), sampler=sampler,
+                                             num_workers=4 if isinstance(dataset, (VOCList, VOCAugment, SyntheticAugment)) else 0,
+                                             pin_memory=True, drop_last=True,
+                                             collate_fn=dataset.collate if resident is not None
+                                             else collate_fn(shape) if AUGMENT else None)
+        if len(loader) == 0:
+            raise ValueError("train: the training set holds no full batch to score")
+        imp = TaylorImportance(self.model, weight=granularity == "weight", block=granularity == "block",
+                               filter=granularity == "filter")
+        saved = [(b, b.detach().clone()) for b in self.model.buffers()]
+        guard = StepGuard(self.model, optimizer, dev, log=logging if rank == 0 else None)
+        self.model.train()
+        done, t0 = 0, time.time()
+        while done < nsteps:
+            for batch in loader:
+                data, target = augmenter(batch) if augmenter is not None else batch
+                data = data.to(dev, non_blocking=True)
+                target = target.float().to(dev, non_blocking=True)
+                if self.teacher is not None:
+                    with torch.no_grad():
+                        t_out = self.teacher(data)
+                output = self.model(data)
+                loss = region_loss(output, target)
+                if self.teacher is not None:
+                    loss = loss + self.distill(output, t_out)
+                optimizer.zero_grad()
+                loss.backward()
+                guard.decide(loss)
+                imp.accumulate(skip=guard.found)          # a flagged step adds nothing, on the device
+                done += 1
+                if done == nsteps:
+                    break
+        guard.finish()
+        optimizer.zero_grad()
+        with torch.no_grad():
+            for b, v in saved:
+                b.copy_(v)
+        imp.all_reduce()
+        scored = imp.steps()
+        masks = taylor_prune(self.model, pruning_perc, imp, granularity)
+        if rank == 0:
+            logging('taylor-%s: %d of %d scoring steps accumulated (over all ranks) in %.2f s' % (
+                granularity, scored, nsteps * world, time.time() - t0))
+        return masks
 
     def _save_compressed(self, weights_name, payload):
         """YOLOv2Train.SAVE_COMPRESSED = payload: the compressed model file (compress.py) beside a .weights file just saved."""
