@@ -16,7 +16,8 @@ the real channels and the halo hold zero; every output starts as NaN everywhere 
 bands included) and the statistics slab starts as NaN, so a leak from a neighbour's channels, an unwritten element, a
 store outside the slice and a slab row nobody wrote all show.
 
-Out of scope: the split-operand and fp8-correction operand forms (x_wrap, x_f8, small3x3_split_kernel); the dgrad
+The split-operand and fp8-correction operand forms (x_wrap, x_f8, small3x3_split_kernel) have the same kind of test in
+test_split_instances_gpu.py (cases: split_cases.py, proven on the CPU by test_split_cases_cpu.py).  Out of scope: the dgrad
 instances that take BatchNorm sums (test_dgrad_bn_sums_gpu.py); the split-K, sparse and q8 kernels, each of which has its
 own exact tests (the 2:4 fp16 forward: test_sparse_instances_gpu.py); the MCAMD_PP_MFMA=32 instances, which are off by default and selected by a switch the library reads once
 per process."""
