@@ -268,6 +268,11 @@ int mcamd_bsparse_lists(const mcamd_conv_geom* g, const void* wp_fwd, int32_t* c
  * outside [0, nchunks] or an index outside [0, nchunks) is clamped into its range. */
 int mcamd_conv_fwd_bsparse(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const int32_t* count,
                            const int32_t* list, const mcamd_conv_epilogue* epi, void* stream);
+/* The kernel instance mcamd_conv_fwd_bsparse launches for this geometry, from the launch's own choice (host logic only, no
+ * GPU): out = {bm, bn, bk, stages, mtiles, ntiles, grid} -- a workgroup tile of bm pixels (MCAMD_BSPARSE_BM: 64, else 128) x
+ * bn = 64 filters, K chunks of bk = kb, LDS ring stages, the tiles along the pixels and the filters, and the blocks launched
+ * (whole rounds of 8 pixel tiles). */
+int mcamd_conv_fwd_bsparse_info(const mcamd_conv_geom* g, int32_t out[7]);
 
 /* ------------------------------------------------------------------------- *
  * Split-K forward for low-batch fp16 inference (an addition beyond the reference; conv_splitk.hip, Darknet.splitk).
@@ -287,6 +292,9 @@ typedef struct mcamd_splitk_info {
     int32_t chunks;          /* ktot / bk */
     int32_t tiles;           /* M tiles x N tiles */
     int64_t workspace_bytes; /* what mcamd_conv_fwd_splitk needs for `slices` */
+    int32_t stages;          /* LDS ring depth of the partial kernel instance */
+    int32_t mtiles, ntiles;  /* partial tiles along the pixels and the filters (tiles = mtiles x ntiles) */
+    int32_t finish_rows, finish_cols; /* the finish kernel's tile: pixels x channels */
 } mcamd_splitk_info;
 /* Host logic only.  slices = 0 asks the policy (the largest S <= MCAMD_SPLITK_CUS / tiles that leaves every slice at
  * least MCAMD_SPLITK_MIN_CHUNKS chunks, clamped to [1, 16]); slices > 0 sizes a forced count in [1, chunks]. */

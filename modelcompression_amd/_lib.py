@@ -87,7 +87,9 @@ class ActInstance(C.Structure):
 class SplitkInfo(C.Structure):
     """mcamd_splitk_info (include/mcamd.h)."""
     _fields_ = [("slices", C.c_int32), ("bm", C.c_int32), ("bn", C.c_int32), ("bk", C.c_int32),
-                ("chunks", C.c_int32), ("tiles", C.c_int32), ("workspace_bytes", C.c_int64)]
+                ("chunks", C.c_int32), ("tiles", C.c_int32), ("workspace_bytes", C.c_int64),
+                ("stages", C.c_int32), ("mtiles", C.c_int32), ("ntiles", C.c_int32),
+                ("finish_rows", C.c_int32), ("finish_cols", C.c_int32)]
 
 
 class FoldDesc(C.Structure):
@@ -231,6 +233,7 @@ SIGNATURES = {
     "mcamd_bsparse_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
     "mcamd_bsparse_lists": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P]),
     "mcamd_conv_fwd_bsparse": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
+    "mcamd_conv_fwd_bsparse_info": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I32)]),
     "mcamd_conv_fwd_splitk_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, _I32, C.POINTER(SplitkInfo)]),
     "mcamd_conv_fwd_splitk": (C.c_int, [C.POINTER(ConvGeom), _P, _P, C.POINTER(ConvEpilogue), _I32, _P, _SZ, _P]),
     "mcamd_conv_fwd_q8_ok": (_I32, [C.POINTER(ConvGeom)]),

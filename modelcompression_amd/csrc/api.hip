@@ -766,6 +766,15 @@ extern "C" int mcamd_conv_fwd_bsparse(const mcamd_conv_geom* g, const void* x, c
     return mcamd_bsparse_launch(a, count, list, (hipStream_t)stream);
 }
 
+// mcamd_bsparse_choice()'s answer: what mcamd_conv_fwd_bsparse launches for this geometry (host logic only)
+extern "C" int mcamd_conv_fwd_bsparse_info(const mcamd_conv_geom* g, int32_t out[7]) {
+    MCAMD_REQUIRE(g && out, "conv_fwd_bsparse_info: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_bsparse_ok(g), "conv_fwd_bsparse_info: geometry has no block-sparse form (mcamd_conv_fwd_bsparse_ok)");
+    const BsparseChoice c = mcamd_bsparse_choice((long long)g->B * g->H * g->W, g->cout, kblock_of(cin_tap_of(g)));
+    out[0] = c.bm, out[1] = c.bn, out[2] = c.bk, out[3] = c.stages, out[4] = c.mtiles, out[5] = c.ntiles, out[6] = c.grid;
+    return MCAMD_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // split-K forward for low-batch inference (conv_splitk.hip; an addition beyond the reference)
 // ---------------------------------------------------------------------------------------
@@ -788,16 +797,23 @@ static int splitk_plan_for(const mcamd_conv_geom* g, int mode, int dst_mode, int
     return MCAMD_OK;
 }
 
-extern "C" int mcamd_conv_fwd_splitk_info(const mcamd_conv_geom* g, int32_t mode, int32_t dst_mode, int32_t slices,
-                                          mcamd_splitk_info* out) {
-    MCAMD_REQUIRE(out, "conv_fwd_splitk_info: null output");
-    SplitkPlan p;
-    if (splitk_plan_for(g, mode, dst_mode, slices, "conv_fwd_splitk_info", &p)) return MCAMD_EINVAL;
+static void splitk_info_of(const SplitkPlan& p, mcamd_splitk_info* out) {
     out->slices = p.slices;
     out->bm = p.bm, out->bn = p.bn, out->bk = p.bk;
     out->chunks = p.chunks;
     out->tiles = p.tiles;
     out->workspace_bytes = (int64_t)p.slices * p.slab_elems * (int64_t)sizeof(float);
+    out->stages = p.stages;
+    out->mtiles = p.mtiles, out->ntiles = p.ntiles;
+    out->finish_rows = p.fr, out->finish_cols = p.fc;
+}
+
+extern "C" int mcamd_conv_fwd_splitk_info(const mcamd_conv_geom* g, int32_t mode, int32_t dst_mode, int32_t slices,
+                                          mcamd_splitk_info* out) {
+    MCAMD_REQUIRE(out, "conv_fwd_splitk_info: null output");
+    SplitkPlan p;
+    if (splitk_plan_for(g, mode, dst_mode, slices, "conv_fwd_splitk_info", &p)) return MCAMD_EINVAL;
+    splitk_info_of(p, out);
     return MCAMD_OK;
 }
 
@@ -959,11 +975,7 @@ extern "C" int mcamd_conv_fwd_q8_splitk_info(const mcamd_conv_geom* g, int32_t d
     MCAMD_REQUIRE(out, "conv_fwd_q8_splitk_info: null output");
     SplitkPlan p;
     if (q8_splitk_plan_for(g, dst_mode, slices, "conv_fwd_q8_splitk_info", &p)) return MCAMD_EINVAL;
-    out->slices = p.slices;
-    out->bm = p.bm, out->bn = p.bn, out->bk = p.bk;
-    out->chunks = p.chunks;
-    out->tiles = p.tiles;
-    out->workspace_bytes = (int64_t)p.slices * p.slab_elems * (int64_t)sizeof(float);
+    splitk_info_of(p, out);
     return MCAMD_OK;
 }
 

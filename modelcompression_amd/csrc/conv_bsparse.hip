@@ -212,22 +212,34 @@ int mcamd_bsparse_lists_launch(const void* wp, int cout, int cin_tap, int ntaps,
 }
 
 template <int BM, int BK, int NSTAGE>
-static int bsparse_launch_t(IgemmArgs& a, const int* count, const int* list, hipStream_t st) {
+static int bsparse_launch_t(IgemmArgs& a, const BsparseChoice& c, const int* count, const int* list, hipStream_t st) {
     constexpr int STAGE_BYTES = (BM + BS_BN) * (BK / 8) * 16;
     constexpr int LDS = NSTAGE * STAGE_BYTES > BM * BS_BN * 2 ? NSTAGE * STAGE_BYTES : BM * BS_BN * 2;   // ring / epilogue tile
     auto kern = bsparse_kernel<BM, BK, NSTAGE>;
     if (LDS > 64 * 1024) MCAMD_LDS_OPT_IN(kern, LDS);
-    a.num_mtiles = (a.M + BM - 1) / BM;
-    a.num_ntiles = (a.N + BS_BN - 1) / BS_BN;
-    const int grid = (a.num_mtiles + 7) / 8 * 8 * a.num_ntiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, st, a, count, list);
+    a.num_mtiles = c.mtiles;
+    a.num_ntiles = c.ntiles;
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), LDS, st, a, count, list);
     MCAMD_LAUNCH_CHECK("conv_fwd_bsparse");
     return MCAMD_OK;
 }
 
-// M tile: MCAMD_BSPARSE_BM_DEFAULT rows (MCAMD_BSPARSE_BM = 64 / 128: A/B switch of tools/bsparse_bench.py)
+// The instance, in one place.  M tile: MCAMD_BSPARSE_BM_DEFAULT rows (MCAMD_BSPARSE_BM = 64 selects 64, anything else 128:
+// A/B switch of tools/bsparse_bench.py); K chunk = the channel block kb, 3 ring stages of 64 or 4 of 32
+BsparseChoice mcamd_bsparse_choice(long long M, int N, int kb) {
+    BsparseChoice c;
+    c.bm = MCAMD_ENV_INT("MCAMD_BSPARSE_BM", MCAMD_BSPARSE_BM_DEFAULT) == 64 ? 64 : 128;
+    c.bn = BS_BN;
+    c.bk = kb == 64 ? 64 : 32;
+    c.stages = c.bk == 64 ? 3 : 4;
+    c.mtiles = (int)((M + c.bm - 1) / c.bm);
+    c.ntiles = (N + BS_BN - 1) / BS_BN;
+    c.grid = (c.mtiles + 7) / 8 * 8 * c.ntiles;
+    return c;
+}
+
 int mcamd_bsparse_launch(IgemmArgs& a, const int* count, const int* list, hipStream_t st) {
-    const int bm = MCAMD_ENV_INT("MCAMD_BSPARSE_BM", MCAMD_BSPARSE_BM_DEFAULT);
-    if (a.kb == 64) return bm == 64 ? bsparse_launch_t<64, 64, 3>(a, count, list, st) : bsparse_launch_t<128, 64, 3>(a, count, list, st);
-    return bm == 64 ? bsparse_launch_t<64, 32, 4>(a, count, list, st) : bsparse_launch_t<128, 32, 4>(a, count, list, st);
+    const BsparseChoice c = mcamd_bsparse_choice(a.M, a.N, a.kb);
+    if (c.bk == 64) return c.bm == 64 ? bsparse_launch_t<64, 64, 3>(a, c, count, list, st) : bsparse_launch_t<128, 64, 3>(a, c, count, list, st);
+    return c.bm == 64 ? bsparse_launch_t<64, 32, 4>(a, c, count, list, st) : bsparse_launch_t<128, 32, 4>(a, c, count, list, st);
 }

@@ -193,6 +193,8 @@ SplitkPlan mcamd_splitk_plan(long long M, int n, int cin_tap, int ktot, int forc
     SplitkPlan p;
     p.bm = SK_BM, p.bn = SK_BN;
     p.bk = cin_tap % 64 == 0 ? 64 : 32;
+    p.stages = p.bk == 64 ? 3 : 4;   // splitk_partial_kernel<64, 3> / <32, 4>
+    p.fr = SK_FR, p.fc = SK_FC;
     p.chunks = ktot / p.bk;
     p.mtiles = (int)((M + SK_BM - 1) / SK_BM);
     p.ntiles = (n + SK_BN - 1) / SK_BN;
@@ -229,10 +231,14 @@ int mcamd_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, float* ws, hipS
     k.mtiles = p.mtiles, k.ntiles = p.ntiles;
     const int groups = p.ntiles * p.slices;
     const dim3 grid((unsigned)(round_up_int(groups, 8) * p.mtiles));
-    if (p.bk == 64) hipLaunchKernelGGL((splitk_partial_kernel<64, 3>), grid, dim3(256), 3 * (SK_BM + SK_BN) * 8 * 16, st, k);
-    else hipLaunchKernelGGL((splitk_partial_kernel<32, 4>), grid, dim3(256), 4 * (SK_BM + SK_BN) * 4 * 16, st, k);
+    if (p.bk == 64 && p.stages == 3) hipLaunchKernelGGL((splitk_partial_kernel<64, 3>), grid, dim3(256), 3 * (SK_BM + SK_BN) * 8 * 16, st, k);
+    else if (p.bk == 32 && p.stages == 4) hipLaunchKernelGGL((splitk_partial_kernel<32, 4>), grid, dim3(256), 4 * (SK_BM + SK_BN) * 4 * 16, st, k);
+    else {
+        mcamd_set_error("conv_fwd_splitk: no partial kernel instance for chunks of %d with %d stages", p.bk, p.stages);
+        return MCAMD_EINVAL;
+    }
     MCAMD_LAUNCH_CHECK("conv_fwd_splitk (partial)");
-    const dim3 fgrid((unsigned)(((a.M + SK_FR - 1) / SK_FR) * p.ntiles));
+    const dim3 fgrid((unsigned)(((a.M + p.fr - 1) / p.fr) * p.ntiles));
     if (a.mode == MCAMD_EPI_PAD_F16) hipLaunchKernelGGL((splitk_finish_kernel<MCAMD_EPI_PAD_F16>), fgrid, dim3(256), 0, st, k);
     else hipLaunchKernelGGL((splitk_finish_kernel<MCAMD_EPI_RAW_F16>), fgrid, dim3(256), 0, st, k);
     MCAMD_LAUNCH_CHECK("conv_fwd_splitk (finish)");

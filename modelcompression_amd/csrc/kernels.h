@@ -121,6 +121,8 @@ bool mcamd_igemm_sums_ok(const ConvRoute& r);   // the route's kernel has a MCAM
 // (forced > 0: that slice count instead of the policy's); slab_elems = floats per slice of the workspace
 struct SplitkPlan {
     int bm, bn, bk, chunks, mtiles, ntiles, tiles, slices;
+    int stages;   // LDS ring depth of the partial kernel instance
+    int fr, fc;   // finish tile: pixels x channels
     long long slab_elems;
 };
 SplitkPlan mcamd_splitk_plan(long long M, int n, int cin_tap, int ktot, int forced);
@@ -128,6 +130,12 @@ int mcamd_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, float* ws, hipS
 // conv_bsparse.hip: the K chunks of each 64-filter N tile from a list (count[ntiles], list[ntiles][ktot / kb]), mode 2
 // epilogue; and the lists of a packed forward weight matrix
 #define MCAMD_BSPARSE_BM_DEFAULT 128
+// mcamd_bsparse_choice names the bsparse_kernel instance (bm pixels x bn filters, K chunks of bk, LDS ring stages) and its
+// grid (whole rounds of 8 pixel tiles) for M pixels x N filters with channel blocks of kb; the launch dispatches on it
+struct BsparseChoice {
+    int bm, bn, bk, stages, mtiles, ntiles, grid;
+};
+BsparseChoice mcamd_bsparse_choice(long long M, int N, int kb);
 int mcamd_bsparse_launch(IgemmArgs& a, const int* count, const int* list, hipStream_t st);
 int mcamd_bsparse_lists_launch(const void* wp, int cout, int cin_tap, int ntaps, int* count, int* list, hipStream_t st);
 // conv_sparse.hip: 2:4 weights, mode 2 epilogue.  mcamd_sparse24_choice names the sparse24_kernel instance (bmw filters x

@@ -1081,10 +1081,23 @@ def bsparse_lists(g, wp, out_count=None, out_list=None):
     return out_count, out_list
 
 
+BsparseInfo = collections.namedtuple("BsparseInfo", "bm bn bk stages mtiles ntiles grid")
+
+
+def conv_fwd_bsparse_info(g):
+    """The kernel instance conv_fwd_bsparse launches for `g`: a tile of bm pixels (MCAMD_BSPARSE_BM) x bn filters, K chunks
+    of bk, LDS ring stages, its tiles along the pixels and the filters and its grid: mcamd_conv_fwd_bsparse_info, the
+    launch's own choice.  Needs no GPU."""
+    out = (C.c_int32 * 7)()
+    check(L.lib().mcamd_conv_fwd_bsparse_info(C.byref(g), out), "mcamd_conv_fwd_bsparse_info")
+    return BsparseInfo(*out)
+
+
 def conv_fwd_bsparse(g, x, wp, count, lst, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
-                     y2_choff=0, all_chunks=False):
+                     y2_choff=0, all_chunks=False, overflow=None):
     """conv_fwd_padded over the listed K chunks of each 64-filter tile (bsparse_lists): the same inference epilogue,
-    arguments and output.  all_chunks=True (tests, tools/bsparse_bench.py) runs the same launch with full lists."""
+    arguments and output.  all_chunks=True (tests, tools/bsparse_bench.py) runs the same launch with full lists.
+    `overflow`: optional int32 flag, set to 1 when an output was clamped to +-65504."""
     nc, nl = bsparse_elems(g)
     if all_chunks:
         nch = nl // nc
@@ -1094,7 +1107,7 @@ def conv_fwd_bsparse(g, x, wp, count, lst, y, y_ld, y_choff=0, scale=None, shift
     if count.dtype != torch.int32 or lst.dtype != torch.int32 or count.numel() != nc or lst.numel() != nl or not lst.is_contiguous():
         raise L.McamdError("conv_fwd_bsparse: count / list must be contiguous int32 of %d / %d entries" % (nc, nl))
     e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
-             y2_choff=y2_choff)
+             y2_choff=y2_choff, overflow=overflow)
     check(L.lib().mcamd_conv_fwd_bsparse(C.byref(g), ptr(x), ptr(wp), ptr(count), ptr(lst), C.byref(e), stream_ptr()),
           "mcamd_conv_fwd_bsparse")
 
@@ -1119,17 +1132,19 @@ def _splitk(g, x, wp, e, slices, workspace):
 
 
 def conv_fwd_splitk(g, x, wp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0, y2_choff=0,
-                    slices=0, workspace=None):
+                    slices=0, workspace=None, overflow=None):
     """conv_fwd_padded with the K axis cut into `slices` slices (0 = the policy's count): a partial launch into `workspace`
-    (fp32, conv_fwd_splitk_info(...).workspace_bytes; None allocates one) and a finish launch with the same epilogue."""
+    (fp32, conv_fwd_splitk_info(...).workspace_bytes; None allocates one) and a finish launch with the same epilogue.
+    `overflow`: optional int32 flag, set to 1 when an output was clamped to +-65504."""
     e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
-             y2_choff=y2_choff)
+             y2_choff=y2_choff, overflow=overflow)
     return _splitk(g, x, wp, e, slices, workspace)
 
 
-def conv_fwd_raw_splitk(g, x, wp, y, y_ld, y_choff=0, slices=0, workspace=None):
-    """conv_fwd_raw(..., stats=None) with the K axis cut into `slices` slices: y[M][y_ld] fp16 raw conv output."""
-    return _splitk(g, x, wp, _epi(L.EPI_RAW_F16, y, y_ld, y_choff), slices, workspace)
+def conv_fwd_raw_splitk(g, x, wp, y, y_ld, y_choff=0, slices=0, workspace=None, overflow=None):
+    """conv_fwd_raw(..., stats=None) with the K axis cut into `slices` slices: y[M][y_ld] fp16 raw conv output.
+    `overflow`: as conv_fwd_splitk."""
+    return _splitk(g, x, wp, _epi(L.EPI_RAW_F16, y, y_ld, y_choff, overflow=overflow), slices, workspace)
 
 
 # ----------------------------------------------------------------------------- fp8 (e4m3) quantised inference

@@ -1,6 +1,7 @@
 """Block pruning and the block-sparse forward, kernel by kernel (csrc/prune.hip: mcamd_block_scores / mcamd_block_mask;
 csrc/conv_bsparse.hip: mcamd_bsparse_lists / mcamd_conv_fwd_bsparse) against the numpy restatement bsparse_ref.py and the
-dense kernels."""
+dense kernels.  (These are the Gaussian checks on the network's shapes; test_bsparse_instances_gpu.py holds every
+bsparse_kernel instance and the list kernel to an exact reference, in both `pad` forms.)"""
 import numpy as np
 import pytest
 import torch

@@ -1,4 +1,5 @@
 """The split-K forward pair (csrc/conv_splitk.hip, mcamd_conv_fwd_splitk) per element.
+(These are the Gaussian checks on real shapes; test_splitk_instances_gpu.py holds every instance to an exact reference.)
 
 Reference: float64 conv2d on the fp16-rounded operands, r = leaky(scale * conv + shift) (raw form: r = conv).
 
