@@ -759,6 +759,19 @@ int32_t mcamd_bn_act_conv1x1_stats_rows(const mcamd_act_desc* d, const mcamd_con
 int mcamd_bn_act_conv1x1_fwd(const mcamd_act_desc* d, const mcamd_conv_geom* g, const void* wp_fwd,
                              const mcamd_conv_epilogue* epi, void* stream);
 
+/* Which kernel instance mcamd_bn_act_conv1x1_fwd launches for a pair, and with which dimensions (host logic only: no GPU
+ * work, pointers are not read).  The launch and this query ask one refusal function and one choice function, so the query
+ * returns MCAMD_OK exactly where mcamd_bn_act_conv1x1_ok returns 1, and MCAMD_EINVAL with the launch's reason elsewhere.
+ *   bn, cb      : bn_conv1x1_kernel<bn, cb> -- the column tile (64 for cout <= 64, else 128) and the 64-channel blocks of
+ *                 the producer's C; the library holds <64,1> <64,2> <128,1> <128,2> <128,3> <128,4>
+ *   threads     : per workgroup, 4 * bn
+ *   rows        : persistent slots = rows of the statistics slab (mcamd_bn_act_conv1x1_stats_rows)
+ *   num_mtiles  : tiles of 128 pixels; more tiles than rows: a workgroup takes several
+ *   grid        : workgroups launched (rows rounded up to the 8 XCDs, plus one per XCD; the surplus returns at once)
+ *   lds_bytes   : dynamic LDS per workgroup */
+typedef struct mcamd_bn_conv1x1_instance { int32_t bn, cb, threads, rows, num_mtiles, grid, lds_bytes; } mcamd_bn_conv1x1_instance;
+int mcamd_bn_act_conv1x1_info(const mcamd_act_desc* d, const mcamd_conv_geom* g, mcamd_bn_conv1x1_instance* out);
+
 typedef struct mcamd_act_bwd_desc {
     int32_t B, H, W, C;
     const void* y; int32_t y_ld, y_choff;   /* saved raw conv output */

@@ -78,6 +78,11 @@ class DgradSums(C.Structure):
                 ("ch_lo", C.c_int32), ("C", C.c_int32)]
 
 
+class BnConv1x1Instance(C.Structure):
+    """mcamd_bn_conv1x1_instance (include/mcamd.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("bn", "cb", "threads", "rows", "num_mtiles", "grid", "lds_bytes")]
+
+
 class ActInstance(C.Structure):
     """mcamd_act_instance (include/mcamd.h)."""
     _fields_ = [("mode", C.c_int32), ("fixed", C.c_int32), ("y32", C.c_int32), ("planes", C.c_int32),
@@ -284,6 +289,7 @@ SIGNATURES = {
     "mcamd_bn_act_fwd_instance": (C.c_int, [C.POINTER(ActDesc), C.POINTER(ActInstance)]),
     "mcamd_bn_act_conv1x1_ok": (_I32, [C.POINTER(ActDesc), C.POINTER(ConvGeom)]),
     "mcamd_bn_act_conv1x1_stats_rows": (_I32, [C.POINTER(ActDesc), C.POINTER(ConvGeom)]),
+    "mcamd_bn_act_conv1x1_info": (C.c_int, [C.POINTER(ActDesc), C.POINTER(ConvGeom), C.POINTER(BnConv1x1Instance)]),
     "mcamd_bn_act_conv1x1_fwd": (C.c_int, [C.POINTER(ActDesc), C.POINTER(ConvGeom), _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_bn_act_bwd_workspace_bytes": (_SZ, [C.POINTER(ActBwdDesc)]),
     "mcamd_bn_act_bwd": (C.c_int, [C.POINTER(ActBwdDesc), _P, _SZ, _P]),

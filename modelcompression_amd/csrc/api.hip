@@ -626,6 +626,24 @@ extern "C" int32_t mcamd_bn_act_conv1x1_stats_rows(const mcamd_act_desc* d, cons
     return bn_conv1x1_refusal(d, g, &r) ? 0 : r.rows;
 }
 
+// what the launch below will choose: the same refusal function, the same choice function (bn_conv1x1.hip)
+extern "C" int mcamd_bn_act_conv1x1_info(const mcamd_act_desc* d, const mcamd_conv_geom* g, mcamd_bn_conv1x1_instance* out) {
+    ConvRoute r;
+    const char* why = bn_conv1x1_refusal(d, g, &r);
+    if (why) {
+        const std::string w(why);   // (may be the error buffer itself)
+        mcamd_set_error("bn_act_conv1x1_info: %s (mcamd_bn_act_conv1x1_ok)", w.c_str());
+        return MCAMD_EINVAL;
+    }
+    MCAMD_REQUIRE(out, "bn_act_conv1x1_info: null output");
+    BnConv1x1Choice c;
+    MCAMD_REQUIRE(mcamd_bn_conv1x1_choice(g->x_wrap / 2, g->cout, (long long)g->B * g->H * g->W, r.rows, &c),
+                  "bn_act_conv1x1_info: no kernel instance for %d -> %d channels", g->x_wrap / 2, g->cout);
+    out->bn = c.bn, out->cb = c.cb, out->threads = c.threads, out->rows = c.rows;
+    out->num_mtiles = c.num_mtiles, out->grid = c.grid, out->lds_bytes = c.lds_bytes;
+    return MCAMD_OK;
+}
+
 extern "C" int mcamd_bn_act_conv1x1_fwd(const mcamd_act_desc* d, const mcamd_conv_geom* g, const void* wp_fwd,
                                         const mcamd_conv_epilogue* epi, void* stream) {
     if (mcamd_recording()) {

@@ -173,34 +173,49 @@ bool mcamd_bn_conv1x1_shape_ok(int P, int cout) {
     return P <= 2 * (cout <= 64 ? 64 : 128);
 }
 
+// The instance a pair takes and its launch dimensions: the launch and mcamd_bn_act_conv1x1_info both ask here.  The column
+// tile is the narrower one that holds cout; the grid is the persistent slots (statistics rows) rounded up to the 8 XCDs
+// plus one workgroup per XCD (xcd_tile); LDS: two stages of A and B rows of 64 halfs (>= the statistics scratch).
+bool mcamd_bn_conv1x1_choice(int P, int cout, long long M, int rows, BnConv1x1Choice* c) {
+    if (!mcamd_bn_conv1x1_shape_ok(P, cout) || M <= 0 || rows <= 0) return false;
+    c->bn = cout <= 64 ? 64 : 128;
+    c->cb = P / 64;
+    c->threads = 4 * c->bn;
+    c->rows = rows;
+    c->num_mtiles = (int)((M + 127) / 128);
+    c->grid = round_up_int(rows, 8) + 8;
+    c->lds_bytes = 2 * (128 + c->bn) * 8 * 16;
+    return true;
+}
+
 template <int BN, int CB>
-static void launch_bc(const IgemmArgs& a, const float* py, int py_ld, int py_choff, hipStream_t st) {
-    constexpr int NT = 4 * BN;
-    const size_t lds = 2 * (size_t)(128 + BN) * 8 * 16;   // two stages of A and B rows of 64 halfs (>= the statistics scratch)
-    if (lds > 64 * 1024) MCAMD_LDS_OPT_IN((bn_conv1x1_kernel<BN, CB>), lds);
-    hipLaunchKernelGGL((bn_conv1x1_kernel<BN, CB>), dim3(round_up_int(a.num_pslots, 8) + 8), dim3(NT), lds, st, a, py, py_ld, py_choff);
+static void launch_bc(const IgemmArgs& a, const BnConv1x1Choice& c, const float* py, int py_ld, int py_choff, hipStream_t st) {
+    if (c.lds_bytes > 64 * 1024) MCAMD_LDS_OPT_IN((bn_conv1x1_kernel<BN, CB>), c.lds_bytes);
+    hipLaunchKernelGGL((bn_conv1x1_kernel<BN, CB>), dim3(c.grid), dim3(c.threads), c.lds_bytes, st, a, py, py_ld, py_choff);
 }
 
 // a: filled as for the consumer's igemm launch (x = the consumer's padded input, whose hi plane is written), plus the
 // producer's scale / shift / slope; P = the producer's channels; rows = persistent workgroups (statistics slab rows)
 int mcamd_bn_conv1x1_launch(IgemmArgs& a, const float* py, int py_ld, int py_choff, int P, int rows, hipStream_t st) {
-    if (!mcamd_bn_conv1x1_shape_ok(P, a.N) || a.ktot != 3 * P) {
+    BnConv1x1Choice c;
+    if (a.ktot != 3 * P || !mcamd_bn_conv1x1_choice(P, a.N, a.M, rows, &c)) {
         mcamd_set_error("bn_act_conv1x1: no kernel instance for %d -> %d channels", P, a.N);
         return MCAMD_EINVAL;
     }
-    a.num_mtiles = (a.M + 127) / 128;
-    a.num_pslots = rows;
+    a.num_mtiles = c.num_mtiles;
+    a.num_pslots = c.rows;
     a.num_ntiles = 1;
     a.xcd_order = 1;
-    const int cb = P / 64;
-    if (a.N <= 64) {
-        if (cb == 1) launch_bc<64, 1>(a, py, py_ld, py_choff, st);
-        else launch_bc<64, 2>(a, py, py_ld, py_choff, st);
-    } else {
-        if (cb == 1) launch_bc<128, 1>(a, py, py_ld, py_choff, st);
-        else if (cb == 2) launch_bc<128, 2>(a, py, py_ld, py_choff, st);
-        else if (cb == 3) launch_bc<128, 3>(a, py, py_ld, py_choff, st);
-        else launch_bc<128, 4>(a, py, py_ld, py_choff, st);
+    switch (c.bn * 8 + c.cb) {
+    case 64 * 8 + 1: launch_bc<64, 1>(a, c, py, py_ld, py_choff, st); break;
+    case 64 * 8 + 2: launch_bc<64, 2>(a, c, py, py_ld, py_choff, st); break;
+    case 128 * 8 + 1: launch_bc<128, 1>(a, c, py, py_ld, py_choff, st); break;
+    case 128 * 8 + 2: launch_bc<128, 2>(a, c, py, py_ld, py_choff, st); break;
+    case 128 * 8 + 3: launch_bc<128, 3>(a, c, py, py_ld, py_choff, st); break;
+    case 128 * 8 + 4: launch_bc<128, 4>(a, c, py, py_ld, py_choff, st); break;
+    default:
+        mcamd_set_error("bn_act_conv1x1: no kernel instance <%d, %d>", c.bn, c.cb);
+        return MCAMD_EINVAL;
     }
     MCAMD_LAUNCH_CHECK("bn_act_conv1x1");
     return MCAMD_OK;

@@ -229,6 +229,9 @@ int mcamd_small3x3_split_launch(const IgemmArgs& a, int rows, hipStream_t st);
 // conv_route(): its own entry point (mcamd_bn_act_conv1x1_fwd).  `a` as for the consumer's igemm launch + the producer's
 // scale / shift / slope; py = the producer's fp32 raw output, P its channels
 bool mcamd_bn_conv1x1_shape_ok(int P, int cout);
+// the instance bn_conv1x1_kernel<bn, cb> and the launch dimensions of a pair (M pixels, `rows` persistent slots); false: none
+struct BnConv1x1Choice { int bn, cb, threads, rows, num_mtiles, grid, lds_bytes; };
+bool mcamd_bn_conv1x1_choice(int P, int cout, long long M, int rows, BnConv1x1Choice* c);
 int mcamd_bn_conv1x1_launch(IgemmArgs& a, const float* py, int py_ld, int py_choff, int P, int rows, hipStream_t st);
 
 bool mcamd_wres_ok(int ksize, int stem, int n, int cin_tap, int ktot, int B, int H, int W, int mode);   // conv_wres.hip

@@ -447,6 +447,17 @@ def bn_act_conv1x1_stats_rows(d, g):
     return int(L.lib().mcamd_bn_act_conv1x1_stats_rows(C.byref(d), C.byref(g)))
 
 
+BnConv1x1Info = collections.namedtuple("BnConv1x1Info", "bn cb threads rows num_mtiles grid lds_bytes")
+
+
+def bn_act_conv1x1_info(d, g):
+    """The bn_conv1x1_kernel<bn, cb> instance and launch dimensions bn_act_conv1x1_fwd takes for the pair
+    (mcamd_bn_act_conv1x1_info: host logic only, needs no GPU); raises what the launch would raise for a refused pair."""
+    r = L.BnConv1x1Instance()
+    check(L.lib().mcamd_bn_act_conv1x1_info(C.byref(d), C.byref(g), C.byref(r)), "mcamd_bn_act_conv1x1_info")
+    return BnConv1x1Info(r.bn, r.cb, r.threads, r.rows, r.num_mtiles, r.grid, r.lds_bytes)
+
+
 def bn_act_conv1x1_fwd(act_args, act_kw, g, wp, y, y_ld, y_choff=0, stats=None):
     """bn_act_fwd(*act_args, **act_kw) and conv_fwd_raw32(g, dst, wp, y, y_ld, y_choff, stats) in one launch
     (mcamd_bn_act_conv1x1_fwd): bit-equal y and stats; of the activation only the hi plane is stored."""

@@ -12,7 +12,8 @@ fp8-correction form (split_cases.stats_bounds: its outputs are multiples of 2^-1
 
 The accuracy of both forms against the unrounded product is what the four Gaussian tests of test_kernels_gpu.py check
 (test_split_forward_two_planes_equals_three, test_f8_correction_forward, test_small3x3_split_kernel,
-test_split_conv2_at_channel_offset); bn_conv1x1.hip has its own bit-equality tests."""
+test_split_conv2_at_channel_offset); bn_conv1x1.hip has its own bit-equality tests
+(test_bn_conv1x1_gpu.py) and its own exact per-instance tests (test_bn1x1_instances_gpu.py)."""
 import os
 import sys
 
