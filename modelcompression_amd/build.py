@@ -24,11 +24,14 @@ SOURCES = {
     "conv_sparse.hip": [],
     "conv_bsparse.hip": [],
     "conv_splitk.hip": [],
+    # The fp8 forward family runs one K loop and one epilogue (csrc/conv_q8_loop.h): their results are bit-equal where the
+    # tests say so because the same functions run.  The five files must still be compiled with EQUAL flags, so that the
+    # shared epilogue expression (and the split-K finish kernel's restatement of it) contracts the same way in each.
     "conv_q8.hip": [],
     "conv_q8_sparse.hip": [],
-    "conv_q8_splitk.hip": [],             # conv_q8.hip's flags: the epilogue expression contracts the way the unsplit kernel's does
-    "conv_q8_bsparse.hip": [],            # conv_q8.hip's flags: bit-equal to that kernel on full lists
-    "conv_q8_w4.hip": [],                 # conv_q8.hip's flags: bit-equal to that kernel on the expanded bytes
+    "conv_q8_splitk.hip": [],
+    "conv_q8_bsparse.hip": [],
+    "conv_q8_w4.hip": [],
     "conv_stem.hip": [],
     "conv_stem_block.hip": [],
     "conv_stem_f32.hip": [],

@@ -8,33 +8,17 @@
 //
 // X8 = e4m3(2 x) bytes in a padded NHWC BYTE buffer (halo bytes 0x00), W8 = e4m3(w * 2^e[n]) with one exponent per
 // filter (mcamd_pack_q8 below).  The MFMA: by default v_mfma_f32_32x32x16_f16 on the bytes converted to fp16 in registers
-// (byte-exact against the contract), or v_mfma_scale_f32_32x32x64_f8f6f4 with both e8m0 scales 1.0 (MCAMD_Q8_MFMA=1: half
-// the MFMA time, not byte-exact; see conv_q8_kernel).  The power of two goes into the epilogue's per-filter scale (exact).
-// As in conv_sparse.hip the weights are the A operand (rows = output channels)
-// and the pixels the columns, so that a lane's four accumulator rows are four consecutive channels of one pixel: one
-// 32-bit word of output bytes.
+// (byte-exact against the contract), or the block-scaled fp8 MFMA with both e8m0 scales 1.0 (MCAMD_Q8_MFMA=1: half the MFMA
+// time, not byte-exact; conv_q8_loop.h: q8_mma).  The power of two goes into the epilogue's per-filter scale (exact).
+// As in conv_sparse.hip the weights are the A operand (rows = output channels) and the pixels the columns, so that a lane's
+// four accumulator rows are four consecutive channels of one pixel: one 32-bit word of output bytes.
 //
-// Operand form: K order [channel block of 64][tap][64 channels]; one K chunk = 64 k = one 64-byte LDS row per weight row /
-// pixel, staged by global_load_lds_dwordx4 (source address swizzled as in conv_igemm.hip).  Lane (r, h) of an MFMA reads
-// bytes [16 h, 16 h + 16) and [32 + 16 h, 32 + 16 h + 16) of row r for BOTH operands: a k permutation common to A and B
-// (tools/f8_probe.hip; the F8 phase of conv_igemm_pp.hip reads the same way).  Against the fp16 kernels a chunk carries
-// twice the k per staged byte (and, with the fp8 MFMA, per MFMA cycle).
-//
-// Epilogue: the tile is laid down in LDS as [pixel][channel] in the format of each destination -- e4m3(2 v) bytes for a
-// destination an fp8 block reads (ONE rounding from fp32), fp16 otherwise (conv_epi.h: write_ch_tile) -- and stored PLAIN /
-// POOL (+ the optional full-resolution copy y2) / REORG by the store every forward implicit-GEMM kernel uses
-// (store_pad_tile).  MaxPool of bytes is taken on the order-preserving key of the code (q is monotone: the maximum of the
-// bytes is the byte of the maximum; -0 sorts below +0).
-#include "kernels.h"
-#include "conv_epi.h"
+// The K loop (operand form, LDS-DMA staging, ring, fragments, both MFMA forms) and the inference epilogue are
+// conv_q8_loop.h's, here over all K chunks of 64-byte weight rows.  MaxPool of bytes is taken on the order-preserving key of
+// the code (q is monotone: the maximum of the bytes is the byte of the maximum; -0 sorts below +0).
+#include "conv_q8_loop.h"
 #include "q8_exp.h"
 
-// F8MFMA = false (the default): the staged bytes are converted to fp16 in registers and multiplied by
-// v_mfma_f32_32x32x16_f16, whose sum of the (exact) products is an fp32 sum -- the arithmetic of the contract, byte for
-// byte.  F8MFMA = true (MCAMD_Q8_MFMA=1): one v_mfma_scale_f32_32x32x64_f8f6f4 per block and chunk, half the MFMA time --
-// but that instruction (and the non-scaled fp8 one) drops products more than ~14 bits below the largest of their group
-// of 8, which flips ~6e-4 of the output bytes to the adjacent code.
-//
 // RAW (training, Darknet.precision = "fp8-qat"): the same main loop with the MCAMD_EPI_RAW_F32 epilogue --
 // y[m][n] = 2^-(e[n] + 1) * S as fp32 [M][y_ld] (the power of two is exact) plus, per channel, the sum and the sum of squares
 // of those fp32 values over the workgroup's pixel tile: slab row = the pixel tile mt, every row written, fixed order, no
@@ -42,200 +26,65 @@
 //
 // BORDER (slim models; conv_q8_border_kernel below): the epilogue adds the fp32 table entry of the pixel's
 // border class to the raw value 2^-(e[n] + 1) * S in front of the affine step (conv_epi.h: Q8Border).
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW, bool BORDER>
+template <class T, bool F8MFMA, bool RAW, bool BORDER>
 __device__ __forceinline__ void conv_q8_block(const IgemmArgs& __restrict__ a, const int* __restrict__ wexp, int y_f8, int y2_f8,
                                               const float* __restrict__ border, int border_ld) {
-    constexpr int WAVES_N = BNP / WN;
-    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
-    constexpr int BK = 64, CPR = 4;                // 64 e4m3 k per 64-byte LDS row: four 16-byte chunks
-    constexpr int A_SLOTS = BMW * CPR, B_SLOTS = BNP * CPR;
-    constexpr int A_IT = A_SLOTS / NT, B_IT = B_SLOTS / NT;
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int STAGE_BYTES = (A_SLOTS + B_SLOTS) * 16;
-    constexpr int DPS = A_IT + B_IT;               // DMA instructions per stage and wave
-    static_assert(A_SLOTS % NT == 0 && B_SLOTS % NT == 0, "whole workgroups per DMA round");
-    static_assert(NSTAGE >= 2 && NSTAGE <= 3, "LDS ring depth");
-
+    using A = Q8RowsA<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    const Q8Wave w = q8_wave<T>();
     int nt, mt;
     if (!xcd_tile(a.num_ntiles, a.num_mtiles, nt, mt)) return;
-    const int nchunks = a.ktot / BK;
-    const char* xg = (const char*)a.x;             // byte operands: every stride of `a` counts bytes
-    const char* wg = (const char*)a.w;
-
-    long long wbase[A_IT];
-#pragma unroll
-    for (int it = 0; it < A_IT; ++it) {
-        const int slot = it * NT + tid;
-        const int row = slot / CPR, phys = slot % CPR;
-        wbase[it] = (long long)(nt * BMW + row) * a.ktot + (phys ^ swz<CPR>(row)) * 16;   // rows < Npad = round_up(N, 256)
-    }
-    long long xbase[B_IT];
-#pragma unroll
-    for (int it = 0; it < B_IT; ++it) {
-        const int slot = it * NT + tid;
-        const int row = slot / CPR, phys = slot % CPR;
-        xbase[it] = tile_x_base(a, a.dst_mode != 0, mt * BNP + row) + (phys ^ swz<CPR>(row)) * 16;
-    }
-
-    f32x16_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    auto stage = [&](int q, int buf) {
-        const int cb = q / a.ntaps, tap = q - cb * a.ntaps;      // one chunk per tap of a 64-channel block
-        const int koff = a.tap_off[tap] + cb * BK;
-        char* sa = smem + buf * STAGE_BYTES;
-        char* sb = sa + A_SLOTS * 16;
-#pragma unroll
-        for (int it = 0; it < A_IT; ++it) glds16(wg + wbase[it] + (long long)q * BK, sa + (it * NT + wave * 64) * 16);
-#pragma unroll
-        for (int it = 0; it < B_IT; ++it) glds16(xg + xbase[it] + koff, sb + (it * NT + wave * 64) * 16);
-    };
-
-    // fragment addresses: row = block row + (lane & 31), 16-byte chunks h and 2 + h of the row (swizzled)
-    const int lrow = lane & 31, hh = lane >> 5;
-    const int SC = 127 * 0x01010101;               // e8m0 1.0 in all four scale bytes
-
-#pragma unroll
-    for (int p = 0; p < NSTAGE - 1; ++p)
-        if (p < nchunks) stage(p, p);
-    int sidx = 0;
-    for (int q = 0; q < nchunks; ++q) {
-        int issued = q + NSTAGE - 1;
-        if (issued > nchunks) issued = nchunks;
-        const int inflight = issued - q - 1;
-        if (NSTAGE == 2 || inflight == 0) wait_vmcnt<0>();
-        else wait_vmcnt<DPS>();
-        __builtin_amdgcn_s_barrier();              // chunk q landed for every wave; every wave is done with chunk q-1
-        if (q + NSTAGE - 1 < nchunks) {
-            int ns = sidx + NSTAGE - 1;
-            if (ns >= NSTAGE) ns -= NSTAGE;
-            stage(q + NSTAGE - 1, ns);
-        }
-        const char* sa = smem + sidx * STAGE_BYTES;
-        const char* sb = sa + A_SLOTS * 16;
-        sidx = sidx + 1 == NSTAGE ? 0 : sidx + 1;
-        i32x8_t af[TM], bf[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int row = wm * WM + i * 32 + lrow;
-            const i32x4_t lo = *(const i32x4_t*)(sa + (row * CPR + (hh ^ swz<CPR>(row))) * 16);
-            const i32x4_t hi = *(const i32x4_t*)(sa + (row * CPR + ((2 + hh) ^ swz<CPR>(row))) * 16);
-            af[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int row = wn * WN + j * 32 + lrow;
-            const i32x4_t lo = *(const i32x4_t*)(sb + (row * CPR + (hh ^ swz<CPR>(row))) * 16);
-            const i32x4_t hi = *(const i32x4_t*)(sb + (row * CPR + ((2 + hh) ^ swz<CPR>(row))) * 16);
-            bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-        // Inline assembly as in conv_igemm_pp.hip (through the builtin hipcc does not accumulate in place).  The operands
-        // come from LDS reads the compiler waits for; the blocks are independent; the epilogue's reads are padded below.
-        if constexpr (F8MFMA) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"
-                                 : "+v"(acc[i][j])
-                                 : "v"(af[i]), "v"(bf[j]), "v"(SC), "v"(SC));
-        } else {
-            // four 16-k steps: 8-byte piece s of the lane's 32 bytes of both operands (lanes h = 0 / 1 hold disjoint k)
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                h8_t a16[TM], b16[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) a16[i] = q8_to_f16(af[i][2 * s4], af[i][2 * s4 + 1]);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b16[j] = q8_to_f16(bf[j][2 * s4], bf[j][2 * s4 + 1]);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a16[i], b16[j], acc[i][j], 0, 0, 0);
-            }
-        }
-    }
-    if constexpr (F8MFMA) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // last (assembly) MFMA -> VALU reads of the accumulators
-
-    // ------------------------------- epilogue -------------------------------
+    A aop;
+    aop.setup(a, nt, w.tid);                       // rows < Npad = round_up(N, 256)
+    f32x16_t acc[T::TM][T::TN];
+    q8_zero(acc);
+    const Q8Lane<T> ln(w);
+    q8_ring<T>(a, aop, Q8SeqDense{a.ktot / T::BK}, mt, smem, w, [&](const char* sa, const char* sb) {
+        q8_dense_step<T, F8MFMA, false>(acc, sb, ln, [&](int i) { return q8_row_frag(sa, ln.a[i]); });
+    });
+    q8_mma_drain<F8MFMA>();
     __syncthreads();                               // every wave is done with the stage buffers
     if constexpr (RAW) {
-        static_assert(raw32_ch_lds_bytes(BMW, BNP, WM, WN) <= NSTAGE * STAGE_BYTES, "raw epilogue inside the ring");
-        store_raw32_ch_tile<BMW, BNP, WM, WN>(a, acc, wexp, smem, mt, nt, wm, wn, wave, lane, tid);   // (conv_epi.h)
-        return;
+        static_assert(raw32_ch_lds_bytes(T::BMW, T::BNP, T::WM, T::WN) <= A::RING, "raw epilogue inside the ring");
+        store_raw32_ch_tile<T::BMW, T::BNP, T::WM, T::WN>(a, acc, wexp, smem, mt, nt, w.wm, w.wn, w.wave, w.lane, w.tid);   // (conv_epi.h)
+    } else if constexpr (BORDER) {
+        q8_infer_epilogue<T>(a, acc, wexp, y_f8, y2_f8, smem, mt, nt, w, Q8Border{border, wexp, border_ld, mt * T::BNP});
+    } else {
+        q8_infer_epilogue<T>(a, acc, wexp, y_f8, y2_f8, smem, mt, nt, w);
     }
-    const bool has2 = a.y2 != nullptr;
-    const bool need_b = y_f8 || (has2 && y2_f8), need_h = !y_f8 || (has2 && !y2_f8);
-    // tile rows are PB = BMW + 8 elements apart: the 32 pixels of a wave's write then fall on 32 different LDS banks (a
-    // pitch of BMW puts them all on one or two)
-    constexpr int PB = BMW + 8;
-    char* bt = smem;                               // [BNP][PB] e4m3 tile
-    half_t* ht = (half_t*)(smem + (need_b ? BNP * PB : 0));   // [BNP][PB] fp16 tile
-    // the per-filter scale with the power of two of the packed weights and of the 2 x activations taken back (exact)
-    const float* scale = a.scale;
-    bool sat;
-    if constexpr (BORDER)
-        sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale](int n) { return scale ? scale[n] : 1.f; }, need_b, need_h, bt, ht, nt, wm,
-                                             wn, lane, Q8Border{border, wexp, border_ld, mt * BNP});
-    else
-        sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale, wexp](int n) { return ldexpf(scale ? scale[n] : 1.f, -(wexp[n] + 1)); },
-                                             need_b, need_h, bt, ht, nt, wm, wn, lane);
-    __syncthreads();
-    store_pad_tile<BNP, BMW, PB, NT>(a, bt, ht, y_f8 != 0, y2_f8 != 0, mt, nt, tid);
-    if (sat && a.overflow) atomicOr(a.overflow, 1);
 }
 
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW>
-__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
-void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8) {
-    conv_q8_block<BMW, BNP, WM, WN, NSTAGE, F8MFMA, RAW, false>(a, wexp, y_f8, y2_f8, nullptr, 0);
+template <class T, bool F8MFMA, bool RAW>
+__global__ __launch_bounds__(T::NT) void conv_q8_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8) {
+    conv_q8_block<T, F8MFMA, RAW, false>(a, wexp, y_f8, y2_f8, nullptr, 0);
 }
 
 // ... with a border table (inference epilogue only)
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
-__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
-void conv_q8_border_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8, const float* __restrict__ border,
-                           int border_ld) {
-    conv_q8_block<BMW, BNP, WM, WN, NSTAGE, F8MFMA, false, true>(a, wexp, y_f8, y2_f8, border, border_ld);
+template <class T, bool F8MFMA>
+__global__ __launch_bounds__(T::NT) void conv_q8_border_kernel(IgemmArgs a, const int* __restrict__ wexp, int y_f8, int y2_f8,
+                                                               const float* __restrict__ border, int border_ld) {
+    conv_q8_block<T, F8MFMA, false, true>(a, wexp, y_f8, y2_f8, border, border_ld);
 }
 
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW = false>
-static int conv_q8_launch_t(IgemmArgs& a, const Q8Choice& c, const int* wexp, int y_f8, int y2_f8, hipStream_t st,
-                            const float* border = nullptr, int border_ld = 0) {
-    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
-    constexpr int RING = NSTAGE * (BMW + BNP) * 64;
-    constexpr int PB = BMW + 8;                    // tile row pitch (conv_q8_kernel)
-    constexpr int TILES = BNP * PB * 3;            // a byte and an fp16 tile (destinations of both formats)
-    constexpr int LDS = RING > TILES ? RING : TILES;
-    const bool has2 = a.y2 != nullptr;
-    const bool mixed = (y_f8 || (has2 && y2_f8)) && (!y_f8 || (has2 && !y2_f8));
-    const int lds = (mixed && !RAW) ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);   // (RAW: its tiles lie inside the ring)
+template <class T, bool F8MFMA, bool RAW>
+static int conv_q8_launch_t(IgemmArgs& a, const Q8Choice& c, const int* wexp, int y_f8, int y2_f8, hipStream_t st, const float* border,
+                            int border_ld) {
+    constexpr int RING = Q8RowsA<T>::RING, LDS = q8_infer_lds_max(RING, T::TILE_BYTES);
+    const int lds = q8_infer_lds(RING, T::TILE_BYTES, a, y_f8, y2_f8);   // (RAW: y_f8 = y2_f8 = 0, its tiles lie inside the ring)
     a.num_mtiles = c.mtiles;
     a.num_ntiles = c.ntiles;
     if constexpr (!RAW) {
         if (border) {                              // (the same tile, ring and LDS as the launch without a table)
-            auto kern = conv_q8_border_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
+            auto kern = conv_q8_border_kernel<T, F8MFMA>;
             MCAMD_LDS_OPT_IN(kern, LDS);
-            hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8, border, border_ld);
+            hipLaunchKernelGGL(kern, dim3(c.grid), dim3(T::NT), lds, st, a, wexp, y_f8, y2_f8, border, border_ld);
             MCAMD_LAUNCH_CHECK("conv_fwd_q8_slim");
             return MCAMD_OK;
         }
     }
-    auto kern = conv_q8_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA, RAW>;
+    auto kern = conv_q8_kernel<T, F8MFMA, RAW>;
     MCAMD_LDS_OPT_IN(kern, LDS);
-    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), lds, st, a, wexp, y_f8, y2_f8);
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(T::NT), lds, st, a, wexp, y_f8, y2_f8);
     MCAMD_LAUNCH_CHECK("conv_fwd_q8");
     return MCAMD_OK;
 }
@@ -248,7 +97,7 @@ static int conv_q8_launch_t(IgemmArgs& a, const Q8Choice& c, const int* wexp, in
 // No 256-channel tile in the default form: with the converted fragments it needs 136 registers (133 with 2:4 weights), one
 // workgroup per CU, and measured 0.87-0.92 x the fp16 kernels on the 256- and 512-filter layers (2:4: 0.73-0.84 x the
 // 128 x 128 tile there, 0.94 x over the whole forward).
-// The grid is whole rounds of 8 pixel tiles (xcd_tile).
+// The grid is whole rounds of 8 pixel tiles (q8_choice_grid).
 Q8Choice mcamd_q8_choice(long long M, int N, int form) {
     (void)form;
     Q8Choice c;
@@ -257,9 +106,7 @@ Q8Choice mcamd_q8_choice(long long M, int N, int form) {
     c.stages = 3;
     if (c.f8mfma && N >= 256) c.bmw = 256;
     else c.bmw = N >= 128 ? 128 : 64;
-    c.mtiles = (int)((M + c.bnp - 1) / c.bnp);
-    c.ntiles = (N + c.bmw - 1) / c.bmw;
-    c.grid = (c.mtiles + 7) / 8 * 8 * c.ntiles;
+    q8_choice_grid(c, M, N);
     return c;
 }
 
@@ -268,23 +115,10 @@ int mcamd_conv_q8_launch(IgemmArgs& a, const void* wexp, int y_f8, int y2_f8, hi
     const int* we = (const int*)wexp;
     const bool raw = a.mode == MCAMD_EPI_RAW_F32;  // training: fp32 y + statistics, the same tile per filter count
     const Q8Choice c = mcamd_q8_choice(a.M, a.N, raw ? MCAMD_Q8_FORM_RAW : border ? MCAMD_Q8_FORM_BORDER : MCAMD_Q8_FORM_INFER);
-    if (c.bnp == 128 && c.stages == 3) {
-        if (raw) {
-            if (c.f8mfma && c.bmw == 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true, true>(a, c, we, 0, 0, st);
-            if (c.f8mfma && c.bmw == 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true, true>(a, c, we, 0, 0, st);
-            if (c.f8mfma && c.bmw == 64) return conv_q8_launch_t<64, 128, 32, 64, 3, true, true>(a, c, we, 0, 0, st);
-            if (!c.f8mfma && c.bmw == 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false, true>(a, c, we, 0, 0, st);
-            if (!c.f8mfma && c.bmw == 64) return conv_q8_launch_t<64, 128, 32, 64, 3, false, true>(a, c, we, 0, 0, st);
-        } else {
-            if (c.f8mfma && c.bmw == 256) return conv_q8_launch_t<256, 128, 64, 64, 3, true>(a, c, we, y_f8, y2_f8, st, border, border_ld);
-            if (c.f8mfma && c.bmw == 128) return conv_q8_launch_t<128, 128, 64, 64, 3, true>(a, c, we, y_f8, y2_f8, st, border, border_ld);
-            if (c.f8mfma && c.bmw == 64) return conv_q8_launch_t<64, 128, 32, 64, 3, true>(a, c, we, y_f8, y2_f8, st, border, border_ld);
-            if (!c.f8mfma && c.bmw == 128) return conv_q8_launch_t<128, 128, 64, 64, 3, false>(a, c, we, y_f8, y2_f8, st, border, border_ld);
-            if (!c.f8mfma && c.bmw == 64) return conv_q8_launch_t<64, 128, 32, 64, 3, false>(a, c, we, y_f8, y2_f8, st, border, border_ld);
-        }
-    }
-    mcamd_set_error("conv_fwd_q8: no kernel instance %d x %d, fp8 MFMA %d, %d stages", c.bmw, c.bnp, c.f8mfma, c.stages);
-    return MCAMD_EINVAL;
+    return q8_dispatch(c, "conv_fwd_q8", [&](auto t, auto f8) {
+        if (raw) return conv_q8_launch_t<decltype(t), decltype(f8)::value, true>(a, c, we, 0, 0, st, nullptr, 0);
+        return conv_q8_launch_t<decltype(t), decltype(f8)::value, false>(a, c, we, y_f8, y2_f8, st, border, border_ld);
+    });
 }
 
 // ---------------------------------------------------------------------------------------

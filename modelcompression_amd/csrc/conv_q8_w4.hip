@@ -1,7 +1,7 @@
 // 4-bit weight inference on the fp8 engine (an addition beyond the reference: Darknet.precision = "fp8-w4") --
 // and its training form (Darknet.precision = "fp8-w4-qat"; DESIGN.md 3x: the raw fp32 epilogue + the fake quantisation below):
-// conv_q8.hip's block with the weight operand held as e2m1 codes + one shift per group of 32 input channels, staged as
-// nibbles and expanded to e4m3 bytes IN REGISTERS in front of the MFMAs.
+// conv_q8_loop.h's K loop and epilogue with the weight operand held as e2m1 codes + one shift per group of 32 input channels,
+// staged as nibbles and expanded to e4m3 bytes IN REGISTERS in front of the MFMAs.
 //
 //   S[n][m] = sum_{tap, c} W8x[n][kpos(tap, c)] * X8[pixel(m) + tap][c]       (fp32 accumulation of exact products)
 //   v       = leaky(scale[n] * 2^-(e4[n] + 1) * S + shift[n])
@@ -12,11 +12,11 @@
 // mantissa bit) onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}.  Every value grid[code] * 2^g is an e4m3 number (one mantissa bit, 2^-6
 // <= |value| <= 384), so W8x, the byte of that value, is exact, and this kernel is conv_q8_kernel on a restricted set of weight
 // bytes: the decoded fragment of lane (r, h) holds the bytes [16 h, 16 h + 16) and [32 + 16 h, +16) of row r's chunk, as
-// conv_q8_kernel's does, and the MFMA sequence per accumulator is the same in both MFMA forms (MCAMD_Q8_MFMA).
+// conv_q8_kernel's does, and both kernels hand their fragments to the same step function (q8_dense_step) in both MFMA forms
+// (MCAMD_Q8_MFMA).
 //
-// One K chunk = 64 k: per weight row 32 code bytes (half of conv_q8.hip's A traffic) + 2 shift bytes, per pixel one 64-byte
-// row, all staged by global_load_lds_dwordx4 with conv_q8_sparse.hip's ring (32-byte weight rows read 16 bytes per lane,
-// contiguously over the wave: no swizzle; the shift bytes of a tile's chunk are one wave-wide DMA, lanes repeating).
+// One K chunk = 64 k: per weight row 32 code bytes (half of conv_q8.hip's A traffic) + 2 shift bytes (Q8HalfRowsA: the shift
+// bytes of a tile's chunk are one wave-wide DMA), per pixel one 64-byte row.
 //
 // Decode (w4_decode): code dword d of a lane's 16 bytes holds the lane's k 8 d .. 8 d + 7 -- byte b: low nibble k 8 d + b,
 // high nibble k 8 d + 4 + b -- so `x & 0x0f0f0f0f` and `(x >> 4) & 0x0f0f0f0f` are the four codes of two output dwords.  The
@@ -24,10 +24,12 @@
 // the group's table is the g = -5 one, {0x00, 0x08, 0x10, 0x14, 0x18, 0x1c, 0x20, 0x24}, plus (g + 5) << 3 on its non-zero
 // entries: two additions per group and lane), the sign bit is moved up from bit 3.  A lane's first 16 k lie in the chunk's
 // first group, its second 16 in the second.
-#include "kernels.h"
-#include "conv_epi.h"
+#include "conv_q8_loop.h"
 #include "q8_exp.h"
 #include "w4_quant.h"
+
+template <class T>
+using Q8W4RowsA = Q8HalfRowsA<T, 2>;             // 32 code bytes + the two group shifts per row and chunk
 
 // e4m3 magnitudes of the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6} * 2^-5: entries 0-3 (v_perm's second source), 4-7 (its first)
 constexpr unsigned W4_TLO = 0x14100800u, W4_THI = 0x24201c18u;
@@ -64,210 +66,74 @@ __device__ __forceinline__ i32x8_t w4_decode(i32x4_t codes, unsigned shifts) {
 }
 
 // RAW (training, Darknet.precision = "fp8-w4-qat"): the same K loop -- staging, register decode, both MFMA forms
-// and their s_nop spacing -- with conv_q8_block's MCAMD_EPI_RAW_F32 epilogue (conv_epi.h: store_raw32_ch_tile): y[m][n] =
+// and their s_nop spacing -- with the MCAMD_EPI_RAW_F32 epilogue conv_q8_block uses (conv_epi.h: store_raw32_ch_tile): y[m][n] =
 // 2^-(e4[n] + 1) * S as fp32 [M][y_ld] and, with a.stats, the per-channel sums and sums of squares of those values, slab row =
 // the pixel tile.  That epilogue's LDS need (72 / 36 / 19 KB) is not the ring's (51 / 39 / 33 KB -- the code rows are half the
 // fp8 kernel's): the launch asks for the larger of the two.
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA, bool RAW>
+template <class T, bool F8MFMA, bool RAW>
 __device__ __forceinline__ void conv_q8_w4_block(const IgemmArgs& __restrict__ a, const char* __restrict__ gshift, int npad,
                                                  const int* __restrict__ wexp, int y_f8, int y2_f8) {
-    constexpr int WAVES_N = BNP / WN;
-    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
-    constexpr int BK = 64, CPRA = 2, CPRB = 4;     // 16-byte pieces per code row / per pixel row
-    constexpr int A_SLOTS = BMW * CPRA, B_SLOTS = BNP * CPRB;
-    constexpr int A_IT = (A_SLOTS + NT - 1) / NT, B_IT = B_SLOTS / NT;
-    constexpr int G_BYTES = 1024;                  // shift region: one wave-wide DMA (BMW * 2 bytes used)
-    constexpr int G_PIECES = BMW * 2 / 16;         // 16-byte pieces of a tile's shift bytes
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int STAGE_BYTES = (A_SLOTS + B_SLOTS) * 16 + G_BYTES;
-    constexpr int DMIN = A_SLOTS / NT + B_IT;      // DMA instructions every wave issues per stage
-    static_assert(A_SLOTS % 64 == 0 && B_SLOTS % NT == 0, "whole waves per DMA instruction");
-    static_assert(BMW * 2 <= G_BYTES && G_PIECES >= 1 && G_PIECES <= 64, "shift region");
-    static_assert(NSTAGE >= 2 && NSTAGE <= 3, "LDS ring depth");
-
+    using A = Q8W4RowsA<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    const Q8Wave w = q8_wave<T>();
     int nt, mt;
     if (!xcd_tile(a.num_ntiles, a.num_mtiles, nt, mt)) return;
-    const int nchunks = a.ktot / BK;
-    const int krow = a.ktot / 2;                   // code row length (bytes)
-    const char* xg = (const char*)a.x;             // byte operands: every stride of `a` counts bytes
-    const char* wg = (const char*)a.w;
-
-    long long wbase[A_IT];
-#pragma unroll
-    for (int it = 0; it < A_IT; ++it) {
-        const int slot = (it * NT + tid) % A_SLOTS;              // (a wave past A_SLOTS issues nothing: stage())
-        wbase[it] = (long long)(nt * BMW + slot / CPRA) * krow + (slot % CPRA) * 16;   // rows < Npad = round_up(N, 256)
-    }
-    long long xbase[B_IT];
-#pragma unroll
-    for (int it = 0; it < B_IT; ++it) {
-        const int slot = it * NT + tid;
-        const int row = slot / CPRB, phys = slot % CPRB;
-        xbase[it] = tile_x_base(a, a.dst_mode != 0, mt * BNP + row) + (phys ^ swz<CPRB>(row)) * 16;
-    }
-    // shift DMA (wave 0): lane l fetches 16 bytes = the shift pairs of 8 rows of the tile (lanes past the tile repeat)
-    const long long gbase = (long long)nt * BMW * 2 + (lane % G_PIECES) * 16;
-
-    f32x16_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    auto stage = [&](int q, int buf) {
-        const int cb = q / a.ntaps, tap = q - cb * a.ntaps;      // one chunk per tap of a 64-channel block
-        const int koff = a.tap_off[tap] + cb * BK;
-        char* sa = smem + buf * STAGE_BYTES;
-        char* sg = sa + A_SLOTS * 16;
-        char* sb = sg + G_BYTES;
-#pragma unroll
-        for (int it = 0; it < A_IT; ++it) {
-            const int wslot = it * NT + wave * 64;
-            if (wslot < A_SLOTS) glds16(wg + wbase[it] + (long long)q * (BK / 2), sa + wslot * 16);
-        }
-        if (wave == 0) glds16(gshift + gbase + (long long)q * npad * 2, sg);
-#pragma unroll
-        for (int it = 0; it < B_IT; ++it) glds16(xg + xbase[it] + koff, sb + (it * NT + wave * 64) * 16);
-    };
-
-    const int lrow = lane & 31, hh = lane >> 5;
-    const int SC = 127 * 0x01010101;               // e8m0 1.0 in all four scale bytes
-
-#pragma unroll
-    for (int p = 0; p < NSTAGE - 1; ++p)
-        if (p < nchunks) stage(p, p);
-    int sidx = 0;
-    for (int q = 0; q < nchunks; ++q) {
-        int issued = q + NSTAGE - 1;
-        if (issued > nchunks) issued = nchunks;
-        const int inflight = issued - q - 1;
-        if (NSTAGE == 2 || inflight == 0) wait_vmcnt<0>();
-        else wait_vmcnt<DMIN>();                   // (a wave that issues more per stage waits for more: in-order completion)
-        __builtin_amdgcn_s_barrier();              // chunk q landed for every wave; every wave is done with chunk q-1
-        if (q + NSTAGE - 1 < nchunks) {
-            int ns = sidx + NSTAGE - 1;
-            if (ns >= NSTAGE) ns -= NSTAGE;
-            stage(q + NSTAGE - 1, ns);
-        }
-        const char* sa = smem + sidx * STAGE_BYTES;
-        const char* sg = sa + A_SLOTS * 16;
-        const char* sb = sg + G_BYTES;
-        sidx = sidx + 1 == NSTAGE ? 0 : sidx + 1;
-        i32x8_t af[TM], bf[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int row = wm * WM + i * 32 + lrow;
-            const i32x4_t codes = *(const i32x4_t*)(sa + (row * CPRA + hh) * 16);
-            af[i] = w4_decode(codes, *(const unsigned short*)(sg + row * 2));
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int row = wn * WN + j * 32 + lrow;
-            const i32x4_t lo = *(const i32x4_t*)(sb + (row * CPRB + (hh ^ swz<CPRB>(row))) * 16);
-            const i32x4_t hi = *(const i32x4_t*)(sb + (row * CPRB + ((2 + hh) ^ swz<CPRB>(row))) * 16);
-            bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-        // conv_q8_block's MFMA sequence on the decoded bytes.  Unlike there, the A operand (and possibly the scale register) was
-        // just written by VALU instructions, and hipcc pads no hazard in front of inline assembly: every string opens with
-        // `s_nop 1`, the two wait states a VALU write of an MFMA source operand needs on gfx950.
-        if constexpr (F8MFMA) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    asm volatile("s_nop 1\n\tv_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"
-                                 : "+v"(acc[i][j])
-                                 : "v"(af[i]), "v"(bf[j]), "v"(SC), "v"(SC));
-        } else {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                h8_t a16[TM], b16[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) a16[i] = q8_to_f16(af[i][2 * s4], af[i][2 * s4 + 1]);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b16[j] = q8_to_f16(bf[j][2 * s4], bf[j][2 * s4 + 1]);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a16[i], b16[j], acc[i][j], 0, 0, 0);
-            }
-        }
-    }
-    if constexpr (F8MFMA) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // last (assembly) MFMA -> VALU reads of the accumulators
-
-    // ------------------------------- epilogue (conv_q8_kernel's, e4_f in place of e_f) -------------------------------
+    A aop;
+    aop.setup(a, gshift, npad, nt, w.tid);
+    f32x16_t acc[T::TM][T::TN];
+    q8_zero(acc);
+    const Q8Lane<T> ln(w);
+    // the shared MFMA sequence on the decoded bytes; the A fragment was just written by VALU instructions (VALU_A)
+    q8_ring<T>(a, aop, Q8SeqDense{a.ktot / T::BK}, mt, smem, w, [&](const char* sa, const char* sb) {
+        q8_dense_step<T, F8MFMA, true>(acc, sb, ln, [&](int i) {
+            return w4_decode(*(const i32x4_t*)(sa + ln.ahalf[i]), *(const unsigned short*)(A::band(sa) + ln.arow[i] * 2));
+        });
+    });
+    q8_mma_drain<F8MFMA>();
     __syncthreads();                               // every wave is done with the stage buffers
-    if constexpr (RAW) {                           // (the launch requested raw32_ch_lds_bytes() or the ring, whichever is larger)
-        store_raw32_ch_tile<BMW, BNP, WM, WN>(a, acc, wexp, smem, mt, nt, wm, wn, wave, lane, tid);
-        return;
-    }
-    const bool has2 = a.y2 != nullptr;
-    const bool need_b = y_f8 || (has2 && y2_f8), need_h = !y_f8 || (has2 && !y2_f8);
-    constexpr int PB = BMW + 8;                    // tile row pitch: a wave's 32 pixels on 32 LDS banks
-    char* bt = smem;                               // [BNP][PB] e4m3 tile
-    half_t* ht = (half_t*)(smem + (need_b ? BNP * PB : 0));   // [BNP][PB] fp16 tile
-    const float* scale = a.scale;
-    const bool sat = write_ch_tile<BMW, PB, WM, WN>(a, acc, [scale, wexp](int n) { return ldexpf(scale ? scale[n] : 1.f, -(wexp[n] + 1)); },
-                                                    need_b, need_h, bt, ht, nt, wm, wn, lane);
-    __syncthreads();
-    store_pad_tile<BNP, BMW, PB, NT>(a, bt, ht, y_f8 != 0, y2_f8 != 0, mt, nt, tid);
-    if (sat && a.overflow) atomicOr(a.overflow, 1);
+    // the shared epilogues, e4_f in place of e_f (RAW: the launch requested raw32_ch_lds_bytes() or the ring, whichever is larger)
+    if constexpr (RAW) store_raw32_ch_tile<T::BMW, T::BNP, T::WM, T::WN>(a, acc, wexp, smem, mt, nt, w.wm, w.wn, w.wave, w.lane, w.tid);
+    else q8_infer_epilogue<T>(a, acc, wexp, y_f8, y2_f8, smem, mt, nt, w);
 }
 
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
-__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
-void conv_q8_w4_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad, const int* __restrict__ wexp, int y_f8, int y2_f8) {
-    conv_q8_w4_block<BMW, BNP, WM, WN, NSTAGE, F8MFMA, false>(a, gshift, npad, wexp, y_f8, y2_f8);
+template <class T, bool F8MFMA>
+__global__ __launch_bounds__(T::NT) void conv_q8_w4_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad,
+                                                           const int* __restrict__ wexp, int y_f8, int y2_f8) {
+    conv_q8_w4_block<T, F8MFMA, false>(a, gshift, npad, wexp, y_f8, y2_f8);
 }
 
 // ... with the raw fp32 epilogue + statistics (training)
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
-__global__ __launch_bounds__((BMW / WM) * (BNP / WN) * 64)
-void conv_q8_w4_raw_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad, const int* __restrict__ wexp) {
-    conv_q8_w4_block<BMW, BNP, WM, WN, NSTAGE, F8MFMA, true>(a, gshift, npad, wexp, 0, 0);
+template <class T, bool F8MFMA>
+__global__ __launch_bounds__(T::NT) void conv_q8_w4_raw_kernel(IgemmArgs a, const char* __restrict__ gshift, int npad,
+                                                               const int* __restrict__ wexp) {
+    conv_q8_w4_block<T, F8MFMA, true>(a, gshift, npad, wexp, 0, 0);
 }
 
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+template <class T, bool F8MFMA>
 static int conv_q8_w4_raw_launch_t(IgemmArgs& a, const Q8Choice& c, const char* gshift, int npad, const int* wexp, hipStream_t st) {
-    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
-    constexpr int RING = NSTAGE * (BMW * 32 + BNP * 64 + 1024);
-    constexpr int EPI = raw32_ch_lds_bytes(BMW, BNP, WM, WN);
+    constexpr int RING = Q8W4RowsA<T>::RING;
+    constexpr int EPI = raw32_ch_lds_bytes(T::BMW, T::BNP, T::WM, T::WN);
     constexpr int LDS = RING > EPI ? RING : EPI;   // (256 x 128: the epilogue's 72 KB over a 51 KB ring)
     static_assert(EPI <= LDS && RING <= LDS && LDS <= 160 * 1024, "raw epilogue and ring inside the requested LDS");
-    auto kern = conv_q8_w4_raw_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
+    auto kern = conv_q8_w4_raw_kernel<T, F8MFMA>;
     MCAMD_LDS_OPT_IN(kern, LDS);
     a.num_mtiles = c.mtiles;
     a.num_ntiles = c.ntiles;
-    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), LDS, st, a, gshift, npad, wexp);
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(T::NT), LDS, st, a, gshift, npad, wexp);
     MCAMD_LAUNCH_CHECK("conv_fwd_q8_w4_raw");
     return MCAMD_OK;
 }
 
-template <int BMW, int BNP, int WM, int WN, int NSTAGE, bool F8MFMA>
+template <class T, bool F8MFMA>
 static int conv_q8_w4_launch_t(IgemmArgs& a, const Q8Choice& c, const char* gshift, int npad, const int* wexp, int y_f8, int y2_f8,
                                hipStream_t st) {
-    constexpr int NT = (BMW / WM) * (BNP / WN) * 64;
-    constexpr int RING = NSTAGE * (BMW * 32 + BNP * 64 + 1024);
-    constexpr int PB = BMW + 8;                    // tile row pitch (conv_q8_w4_kernel)
-    constexpr int TILES = BNP * PB * 3;            // a byte and an fp16 tile (destinations of both formats)
-    constexpr int LDS = RING > TILES ? RING : TILES;
-    const bool has2 = a.y2 != nullptr;
-    const bool mixed = (y_f8 || (has2 && y2_f8)) && (!y_f8 || (has2 && !y2_f8));
-    const int lds = mixed ? LDS : (RING > BNP * PB * 2 ? RING : BNP * PB * 2);
-    auto kern = conv_q8_w4_kernel<BMW, BNP, WM, WN, NSTAGE, F8MFMA>;
-    MCAMD_LDS_OPT_IN(kern, LDS);
+    constexpr int RING = Q8W4RowsA<T>::RING;
+    auto kern = conv_q8_w4_kernel<T, F8MFMA>;
+    MCAMD_LDS_OPT_IN(kern, q8_infer_lds_max(RING, T::TILE_BYTES));
     a.num_mtiles = c.mtiles;
     a.num_ntiles = c.ntiles;
-    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(NT), lds, st, a, gshift, npad, wexp, y_f8, y2_f8);
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(T::NT), q8_infer_lds(RING, T::TILE_BYTES, a, y_f8, y2_f8), st, a, gshift, npad, wexp, y_f8,
+                       y2_f8);
     MCAMD_LAUNCH_CHECK("conv_fwd_q8_w4");
     return MCAMD_OK;
 }
@@ -278,37 +144,21 @@ static int conv_q8_w4_launch_t(IgemmArgs& a, const Q8Choice& c, const char* gshi
 Q8Choice mcamd_q8_w4_choice(long long M, int N) { return mcamd_q8_choice(M, N, MCAMD_Q8_FORM_INFER); }
 
 int mcamd_conv_q8_w4_launch(IgemmArgs& a, const void* gshift, const void* wexp, int y_f8, int y2_f8, hipStream_t st) {
-    const int* we = (const int*)wexp;
-    const char* gs = (const char*)gshift;
     const int npad = round_up_int(a.N, 256);
     const Q8Choice c = mcamd_q8_w4_choice(a.M, a.N);
-    if (c.bnp == 128 && c.stages == 3) {
-        if (c.f8mfma && c.bmw == 256) return conv_q8_w4_launch_t<256, 128, 64, 64, 3, true>(a, c, gs, npad, we, y_f8, y2_f8, st);
-        if (c.f8mfma && c.bmw == 128) return conv_q8_w4_launch_t<128, 128, 64, 64, 3, true>(a, c, gs, npad, we, y_f8, y2_f8, st);
-        if (c.f8mfma && c.bmw == 64) return conv_q8_w4_launch_t<64, 128, 32, 64, 3, true>(a, c, gs, npad, we, y_f8, y2_f8, st);
-        if (!c.f8mfma && c.bmw == 128) return conv_q8_w4_launch_t<128, 128, 64, 64, 3, false>(a, c, gs, npad, we, y_f8, y2_f8, st);
-        if (!c.f8mfma && c.bmw == 64) return conv_q8_w4_launch_t<64, 128, 32, 64, 3, false>(a, c, gs, npad, we, y_f8, y2_f8, st);
-    }
-    mcamd_set_error("conv_fwd_q8_w4: no kernel instance %d x %d, fp8 MFMA %d, %d stages", c.bmw, c.bnp, c.f8mfma, c.stages);
-    return MCAMD_EINVAL;
+    return q8_dispatch(c, "conv_fwd_q8_w4", [&](auto t, auto f8) {
+        return conv_q8_w4_launch_t<decltype(t), decltype(f8)::value>(a, c, (const char*)gshift, npad, (const int*)wexp, y_f8, y2_f8, st);
+    });
 }
 
 // The training launch: the same tile per filter count (mcamd_q8_choice's for the raw fp8 block, as the engine's statistics
 // slab and mcamd_conv_fwd_q8_stats_rows assume).
 int mcamd_conv_q8_w4_raw_launch(IgemmArgs& a, const void* gshift, const void* wexp, hipStream_t st) {
-    const int* we = (const int*)wexp;
-    const char* gs = (const char*)gshift;
     const int npad = round_up_int(a.N, 256);
     const Q8Choice c = mcamd_q8_choice(a.M, a.N, MCAMD_Q8_FORM_RAW);
-    if (c.bnp == 128 && c.stages == 3) {
-        if (c.f8mfma && c.bmw == 256) return conv_q8_w4_raw_launch_t<256, 128, 64, 64, 3, true>(a, c, gs, npad, we, st);
-        if (c.f8mfma && c.bmw == 128) return conv_q8_w4_raw_launch_t<128, 128, 64, 64, 3, true>(a, c, gs, npad, we, st);
-        if (c.f8mfma && c.bmw == 64) return conv_q8_w4_raw_launch_t<64, 128, 32, 64, 3, true>(a, c, gs, npad, we, st);
-        if (!c.f8mfma && c.bmw == 128) return conv_q8_w4_raw_launch_t<128, 128, 64, 64, 3, false>(a, c, gs, npad, we, st);
-        if (!c.f8mfma && c.bmw == 64) return conv_q8_w4_raw_launch_t<64, 128, 32, 64, 3, false>(a, c, gs, npad, we, st);
-    }
-    mcamd_set_error("conv_fwd_q8_w4_raw: no kernel instance %d x %d, fp8 MFMA %d, %d stages", c.bmw, c.bnp, c.f8mfma, c.stages);
-    return MCAMD_EINVAL;
+    return q8_dispatch(c, "conv_fwd_q8_w4_raw", [&](auto t, auto f8) {
+        return conv_q8_w4_raw_launch_t<decltype(t), decltype(f8)::value>(a, c, (const char*)gshift, npad, (const int*)wexp, st);
+    });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -175,16 +175,17 @@ int mcamd_fakequant_q8_launch(const float* w, const float* mask, const void* wex
 // conv_q8_splitk.hip: split-K pair on conv_q8.hip's operands (partial + finish launch, mode 2 epilogue).  `p`: mcamd_splitk_plan
 // for 64-wide chunks (cin % 64 == 0); ws: p.slices * p.slab_elems floats; the MFMA form is mcamd_q8_choice's
 int mcamd_q8_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* wexp, int y_f8, int y2_f8, float* ws, hipStream_t st);
-// conv_q8_bsparse.hip: conv_q8.hip's 64 x 128 block over the K chunks each 64-filter tile lists (count[ntiles],
+// conv_q8_bsparse.hip: conv_q8.hip's K loop (conv_q8_loop.h) on a 64 x 128 tile over the K chunks each 64-filter tile lists (count[ntiles],
 // list[ntiles][ktot / 64]); its instance and grid; the lists of mcamd_pack_q8's bytes
 Q8Choice mcamd_q8_bsparse_choice(long long M, int N);
 int mcamd_conv_q8_bsparse_launch(IgemmArgs& a, const void* wexp, const int* count, const int* list, int y_f8, int y2_f8, hipStream_t st);
 int mcamd_q8_bsparse_lists_launch(const void* wq, int cout, int cin, int ntaps, int* count, int* list, hipStream_t st);
-// conv_q8_sparse.hip: conv_q8.hip's block on 2:4-compressed e4m3 weights (sparse MFMA); packer
+// conv_q8_sparse.hip: conv_q8.hip's K loop and epilogue (conv_q8_loop.h) on 2:4-compressed e4m3 weights (sparse MFMA); packer
 int mcamd_conv_q8_sparse_launch(IgemmArgs& a, const void* idx, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
 int mcamd_pack_q8_sparse24_launch(const float* w, const float* mask, void* wq, void* idx, void* wexp, int cout, int cin,
                                   int ntaps, hipStream_t st);
-// conv_q8_w4.hip: conv_q8.hip's block on e2m1 codes + group shifts expanded to e4m3 bytes in registers (a.w = the codes);
+// conv_q8_w4.hip: conv_q8.hip's K loop and epilogue (conv_q8_loop.h) on e2m1 codes + group shifts expanded to e4m3 bytes in
+// registers (a.w = the codes);
 // its choice of instance (the fp8 block's), packer, expander to mcamd_pack_q8's bytes
 Q8Choice mcamd_q8_w4_choice(long long M, int N);
 int mcamd_conv_q8_w4_launch(IgemmArgs& a, const void* gshift, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
