@@ -638,6 +638,32 @@ int mcamd_conv_wgrad_plan_info(const mcamd_conv_geom* g, int32_t has_cmap, int32
  * written (out may be NULL with cap 0); returns their number.  Any other tuple is an MCAMD_EINVAL of the launch. */
 int32_t mcamd_wgrad_generic_instances(int32_t* out, int32_t cap);
 
+/* The whole backward of a dense 1x1 block in ONE launch plus the weight gradient's finish pass: what mcamd_conv_dgrad_sums
+ * (epilogue mode 0) and mcamd_conv_wgrad compute for the same arguments, from one pass over dY and x.
+ *   gin[m][g_choff + c] = sum_n dy[m][n] w[n][c] as fp16 [B*H*W][g_ld], saturated to +-65504 with `overflow` (may be NULL)
+ *                          set to 1 where a value was clamped, exactly as mcamd_conv_dgrad stores it; nothing else of gin is
+ *                          written;
+ *   `sums` (may be NULL): the BatchNorm-backward sums of the PLAIN block that produced x, as mcamd_conv_dgrad_sums forms them
+ *                          -- sums->rows = mcamd_conv_bwd1x1_sums_rows(g), every row and every producer channel written; the
+ *                          producer's stored activation must BE this block's input (act == x, act_ld == g->x_ld, act_choff ==
+ *                          g->x_choff + ch_lo, act_pad == g->pad): the launch reads it from the tile of x it holds on chip;
+ *   dw_oihw = dy^T x * mask / grad_scale, dbias as mcamd_conv_wgrad (no channel map); workspace >=
+ *                          mcamd_conv_bwd1x1_workspace_bytes(g): one fp32 [cout][cin] split per workgroup
+ *                          (mcamd_conv_bwd1x1_wgrad_splits of them), summed by mcamd_conv_wgrad's finish kernel.
+ * A persistent launch of a fixed grid; no workgroup waits for another, no atomics on results: two runs give the same bits.
+ * mcamd_conv_bwd1x1_ok (host logic only): 1 when the geometry has such a launch -- ksize 1, no stem / x_wrap / x_f8, an
+ * existing (cout, cin) instance: (64, 128), (128, 256), x slice in whole groups of 8 -- else 0 with *reason (may be NULL)
+ * pointing at a static string that says why; the launch returns MCAMD_EINVAL with the same reason.  The three queries
+ * return 0 for a refused geometry.  Both `pad` forms of x and dy. */
+int32_t mcamd_conv_bwd1x1_ok(const mcamd_conv_geom* g, const char** reason);
+int32_t mcamd_conv_bwd1x1_sums_rows(const mcamd_conv_geom* g);
+int32_t mcamd_conv_bwd1x1_wgrad_splits(const mcamd_conv_geom* g);
+size_t mcamd_conv_bwd1x1_workspace_bytes(const mcamd_conv_geom* g);
+int mcamd_conv_bwd1x1(const mcamd_conv_geom* g, const void* x, const void* dy, int32_t dy_ld, int32_t dy_choff,
+                      const void* wp_dgrad, void* gin, int32_t g_ld, int32_t g_choff, int32_t* overflow,
+                      const mcamd_dgrad_sums* sums, const float* mask_oihw, float grad_scale, float* dw_oihw, float* dbias,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * BatchNorm2d (eps, momentum as given; torch defaults 1e-5 / 0.1 at nets.py:802)
  * + LeakyReLU(0.1) (nets.py:809) + MaxPool2d(2,2) (nets.py:821) + Reorg(2)

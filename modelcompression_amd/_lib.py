@@ -280,6 +280,12 @@ SIGNATURES = {
     "mcamd_conv_wgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _I32, _I32, _P, C.POINTER(ChanMap), _F, _P, _P, _P, _SZ, _P]),
     "mcamd_conv_wgrad_plan_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I32)]),
     "mcamd_wgrad_generic_instances": (_I32, [C.POINTER(_I32), _I32]),
+    "mcamd_conv_bwd1x1_ok": (_I32, [C.POINTER(ConvGeom), C.POINTER(C.c_char_p)]),
+    "mcamd_conv_bwd1x1_sums_rows": (_I32, [C.POINTER(ConvGeom)]),
+    "mcamd_conv_bwd1x1_wgrad_splits": (_I32, [C.POINTER(ConvGeom)]),
+    "mcamd_conv_bwd1x1_workspace_bytes": (_SZ, [C.POINTER(ConvGeom)]),
+    "mcamd_conv_bwd1x1": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _I32, _I32, _P, _P, _I32, _I32, _P, C.POINTER(DgradSums), _P, _F,
+                                    _P, _P, _P, _SZ, _P]),
     "mcamd_bn_coeffs": (C.c_int, [_P, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _F, _F, _I32, _P, _P, _P, _P, _P, _P]),
     "mcamd_bn_coeffs_ex": (C.c_int, [_P, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _F, _F, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "mcamd_fold_weights": (C.c_int, [C.POINTER(FoldDesc), _P, _P]),

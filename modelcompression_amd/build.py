@@ -40,6 +40,7 @@ SOURCES = {
     "conv_wres.hip": [],
     "conv_wgrad.hip": [],
     "conv_wgrad_stem.hip": [],
+    "conv_bwd1x1.hip": [],
     "bn_act.hip": [],
     "bn_conv1x1.hip": [],
     "fold.hip": [],

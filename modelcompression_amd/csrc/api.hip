@@ -1457,3 +1457,100 @@ extern "C" int mcamd_conv_wgrad(const mcamd_conv_geom* g, const void* x, const v
     }
     return rc;
 }
+
+// ---------------------------------------------------------------------------------------
+// dgrad + producer sums + wgrad of a dense 1x1 block in one launch (conv_bwd1x1.hip)
+// ---------------------------------------------------------------------------------------
+static const char* bwd1x1_refusal(const mcamd_conv_geom* g) {
+    if (!g) return "null geometry";
+    if (g->pad != 0 && g->pad != 1) return "pad must be 0 or 1";
+    const char* why = mcamd_bwd1x1_refusal(g->ksize, g->stem, g->x_wrap, g->x_f8, g->cout, g->cin);
+    if (why) return why;
+    if (g->x_ld % 8 != 0 || g->x_choff % 8 != 0 || g->x_choff < 0 || g->x_choff + g->cin > g->x_ld)
+        return "x channel slice must be whole groups of 8 inside x_ld";
+    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || (long long)g->B * g->H * g->W >= (1ll << 31)) return "pixel count out of range";
+    return nullptr;
+}
+
+extern "C" int32_t mcamd_conv_bwd1x1_ok(const mcamd_conv_geom* g, const char** reason) {
+    const char* why = bwd1x1_refusal(g);
+    if (reason) *reason = why;
+    return why ? 0 : 1;
+}
+
+extern "C" int32_t mcamd_conv_bwd1x1_sums_rows(const mcamd_conv_geom* g) { return bwd1x1_refusal(g) ? 0 : MCAMD_BWD1X1_GRID; }
+extern "C" int32_t mcamd_conv_bwd1x1_wgrad_splits(const mcamd_conv_geom* g) { return bwd1x1_refusal(g) ? 0 : MCAMD_BWD1X1_GRID; }
+extern "C" size_t mcamd_conv_bwd1x1_workspace_bytes(const mcamd_conv_geom* g) {
+    return bwd1x1_refusal(g) ? 0 : (size_t)MCAMD_BWD1X1_GRID * g->cout * g->cin * sizeof(float);
+}
+
+extern "C" int mcamd_conv_bwd1x1(const mcamd_conv_geom* g, const void* x, const void* dy, int32_t dy_ld, int32_t dy_choff,
+                                 const void* wp_dgrad, void* gin, int32_t g_ld, int32_t g_choff, int32_t* overflow,
+                                 const mcamd_dgrad_sums* sums, const float* mask_oihw, float grad_scale, float* dw_oihw,
+                                 float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "conv_bwd1x1: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        const bool has_sums = sums != nullptr;
+        const mcamd_dgrad_sums s_ = has_sums ? *sums : mcamd_dgrad_sums{};
+        return mcamd_rec_push(stream, [=](void* s) {
+            return mcamd_conv_bwd1x1(&g_, x, dy, dy_ld, dy_choff, wp_dgrad, gin, g_ld, g_choff, overflow, has_sums ? &s_ : nullptr,
+                                     mask_oihw, grad_scale, dw_oihw, dbias, workspace, workspace_bytes, s);
+        });
+    }
+    const char* why = bwd1x1_refusal(g);
+    MCAMD_REQUIRE(!why, "conv_bwd1x1: %s", why);
+    MCAMD_REQUIRE(x && dy && wp_dgrad && gin && dw_oihw && workspace, "conv_bwd1x1: null argument");
+    MCAMD_REQUIRE(grad_scale > 0.f, "conv_bwd1x1: grad_scale must be positive");
+    MCAMD_REQUIRE(dy_ld % 8 == 0 && dy_choff % 8 == 0 && dy_choff >= 0 && dy_choff + g->cout <= dy_ld,
+                  "conv_bwd1x1: dy slice [%d, %d) does not fit dy_ld %d", dy_choff, dy_choff + g->cout, dy_ld);
+    MCAMD_REQUIRE(g_ld % 8 == 0 && g_choff % 8 == 0 && g_choff >= 0 && g_choff + g->cin <= g_ld,
+                  "conv_bwd1x1: G slice [%d, %d) does not fit g_ld %d", g_choff, g_choff + g->cin, g_ld);
+    const size_t need = mcamd_conv_bwd1x1_workspace_bytes(g);
+    if (workspace_bytes < need) {
+        mcamd_set_error("conv_bwd1x1: workspace %zu < %zu bytes", workspace_bytes, need);
+        return MCAMD_EWORKSPACE;
+    }
+    Bwd1x1Launch q;
+    memset(&q, 0, sizeof(q));
+    q.dy = (const half_t*)dy, q.x = (const half_t*)x, q.w = (const half_t*)wp_dgrad, q.g = (half_t*)gin;
+    q.slab = (float*)workspace, q.overflow = (int*)overflow;
+    q.dy_ld = dy_ld, q.dy_choff = dy_choff, q.x_ld = g->x_ld, q.x_choff = g->x_choff, q.g_ld = g_ld, q.g_choff = g_choff;
+    q.H = g->H, q.W = g->W, q.M = g->B * g->H * g->W, q.pw = pw_of(g), q.cout = g->cout, q.cin = g->cin;
+    if (sums && sums->slab) {
+        const mcamd_dgrad_sums* s = sums;
+        MCAMD_REQUIRE(s->rows == MCAMD_BWD1X1_GRID, "conv_bwd1x1: sums.rows must be mcamd_conv_bwd1x1_sums_rows() = %d (got %d)",
+                      MCAMD_BWD1X1_GRID, s->rows);
+        MCAMD_REQUIRE(s->scale && s->shift && s->mean && s->invstd, "conv_bwd1x1: sums: null argument");
+        MCAMD_REQUIRE(s->C > 0 && s->C % 8 == 0 && s->ch_lo >= 0 && s->ch_lo % 8 == 0 && s->ch_lo + s->C <= g->cin,
+                      "conv_bwd1x1: sums: producer columns [%d, %d) must be whole groups of 8 inside the %d channels of G",
+                      s->ch_lo, s->ch_lo + s->C, g->cin);
+        MCAMD_REQUIRE(s->ld >= s->C, "conv_bwd1x1: sums.ld (%d) must be >= C (%d)", s->ld, s->C);
+        // the producer's stored activation IS this block's input: the launch takes it from the X tile it has staged
+        MCAMD_REQUIRE(s->act == x && s->act_ld == g->x_ld && s->act_choff == g->x_choff + s->ch_lo && (s->act_pad != 0) == (g->pad != 0),
+                      "conv_bwd1x1: sums: the producer's activation must be the block's input x (same buffer, ld, form; act_choff = "
+                      "x_choff + ch_lo)");
+        MCAMD_REQUIRE(!s->y || (s->y_ld % 4 == 0 && s->y_choff % 4 == 0 && s->y_choff >= 0 && s->y_choff + s->C <= s->y_ld),
+                      "conv_bwd1x1: sums: fp32 y slice [%d, %d) does not fit y_ld %d", s->y_choff, s->y_choff + s->C, s->y_ld);
+        MCAMD_REQUIRE(s->slope > 0.f, "conv_bwd1x1: sums need an invertible activation (slope > 0)");
+        q.bsum.slab = s->slab, q.bsum.ld = s->ld;
+        q.bsum.scale = s->scale, q.bsum.shift = s->shift, q.bsum.mean = s->mean, q.bsum.invstd = s->invstd;
+        q.bsum.y = s->y, q.bsum.y_ld = s->y_ld, q.bsum.y_choff = s->y_choff;
+        q.bsum.ch_lo = s->ch_lo, q.bsum.C = s->C;
+        q.bsum.slope = s->slope;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = mcamd_bwd1x1_launch(q, st);
+    if (rc) return rc;
+    // the workgroups' accumulators are the splits of the weight gradient's slab layout: the same finish pass
+    WgradPlan p;
+    memset(&p, 0, sizeof(p));
+    p.nsplit = MCAMD_BWD1X1_GRID, p.rows_pad = g->cout;
+    rc = mcamd_wgrad_finish_launch((const float*)workspace, p, g->cin, g->cin, 0, g->cout, g->cin, 1, mask_oihw, 1.0f / grad_scale,
+                                   dw_oihw, nullptr, nullptr, st);
+    if (rc) return rc;
+    if (dbias)
+        rc = mcamd_colsum_launch((const half_t*)dy, padded_pixels(g), dy_ld, dy_choff, g->cout, 1.0f / grad_scale, dbias, st, workspace,
+                                 workspace_bytes);
+    return rc;
+}

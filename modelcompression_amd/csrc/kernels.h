@@ -217,6 +217,23 @@ int mcamd_wgrad_finish_launch(const float* slab, const WgradPlan& p, int ktot, i
 int mcamd_colsum_launch(const half_t* dy, long long rows, int ld, int choff, int C, float inv_scale, float* out,
                         hipStream_t st, void* scratch, size_t scratch_bytes);   // scratch: reusable once the finish pass is enqueued
 
+// conv_bwd1x1.hip: dgrad + producer sums + wgrad of a dense 1x1 block in one persistent launch (mcamd_conv_bwd1x1).  The grid
+// is fixed: it is the number of sums rows and of dW splits, and one workgroup fits a CU.
+#define MCAMD_BWD1X1_GRID 256
+struct Bwd1x1Launch {
+    const half_t* dy;
+    const half_t* x;
+    const half_t* w;     // dgrad packing [cin][cout]
+    half_t* g;           // raw [M][g_ld]
+    float* slab;         // [MCAMD_BWD1X1_GRID][cout][cin]
+    int* overflow;
+    int dy_ld, dy_choff, x_ld, x_choff, g_ld, g_choff;
+    int H, W, M, pw, cout, cin;
+    DgradSums bsum;      // slab NULL = none; the activation fields are not read (the activation is x)
+};
+const char* mcamd_bwd1x1_refusal(int ksize, int stem, int x_wrap, int x_f8, int cout, int cin);   // NULL: an instance exists
+int mcamd_bwd1x1_launch(const Bwd1x1Launch& q, hipStream_t st);
+
 // the per-kernel eligibility rules and slab rows conv_route() asks, each once; the launches take `rows` from the route
 bool mcamd_win3x3_ok(int mode, bool stats, long long M, int n, int cin_tap, int ktot, int H, int W);   // conv_win.hip
 int mcamd_win3x3_launch(const IgemmArgs& a, hipStream_t st);

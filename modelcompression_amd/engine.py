@@ -533,6 +533,12 @@ class Engine:
         self.fuse_bn_1x1 = os.environ.get("MCAMD_FUSE_BN_1X1", "1") == "1"
         self.fused_1x1_launches = 0
         self._fused_1x1_cache = {}
+        # ... and the whole backward of a narrow dense 1x1 block -- dgrad, its producer's BatchNorm sums, wgrad -- in one launch
+        # on the launch stream (mcamd_conv_bwd1x1, _bwd1x1_route; MCAMD_BWD1X1=0: a dgrad launch + a wgrad launch on the
+        # second stream).  One workspace for the blocks' weight-gradient splits, allocated once: plans hold its address.
+        self.bwd1x1 = os.environ.get("MCAMD_BWD1X1", "1") == "1"
+        self._bwd1x1_cache = {}
+        self._bwd1x1_ws = None
         self._dgrad_sums_cache = {}
         self._side_stream = None
         self._side_concurrent = True
@@ -1898,15 +1904,34 @@ class Engine:
                            eps=bn.eps, cout=lay.cout, planes=self.act_planes, x_lo=lay.sh_img_lo, wp_lo=lay.sh_wp_lo)
 
     # ------------------------------------------------------------------ backward
-    def _dgrad_sums(self, lay, concurrent):
+    def _bwd1x1_route(self, lay):
+        """Does block `lay` run its backward as ONE launch (ops.conv_bwd1x1)?  The library has an instance for its dense
+        geometry (ops.conv_bwd1x1_ok) and the block runs that geometry: no fold, no gather, no in_perm -- the conditions
+        _dgrad_sums puts on the consumer."""
+        if not self.bwd1x1 or lay.li == 0 or lay.gin is None or lay.fused_stem or lay.stem_shadow:
+            return False
+        key = (lay.li, self._plan_epoch)
+        hit = self._bwd1x1_cache.get(key)
+        if hit is None:
+            hit = (lay.fold is None and not lay.gather and lay.in_perm is None and lay.geom_act is lay.geom
+                   and ops.conv_bwd1x1_ok(lay.geom)[0])
+            self._bwd1x1_cache = {k: v for k, v in self._bwd1x1_cache.items() if k[1] == self._plan_epoch}
+            self._bwd1x1_cache[key] = hit
+        if hit and self._bwd1x1_ws is None:
+            need = max(ops.conv_bwd1x1_workspace_bytes(l.geom) for l in self.layers if l.geom is not None)
+            self._bwd1x1_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return hit
+
+    def _dgrad_sums(self, lay, concurrent, fused=False):
         """(descriptor, slab, producer) when the dgrad launch of block `lay` can take the BatchNorm-backward sums of the
         block that produced its input (ops.dgrad_sums), else None.  The producer must be a PLAIN block of a split-operand
         engine read from its stored activation (bwd_from_act), with this block as its only consumer and none of keep / perm /
         fold / skip_dead / a narrowed BatchNorm pass; this block must run its dense geometry (no gather / fold of its own),
-        and the kernel its dgrad gets must have the sums-taking form (ops.dgrad_sums_rows > 0)."""
+        and the kernel its dgrad gets must have the sums-taking form (ops.dgrad_sums_rows > 0).
+        `fused`: the launch is the block's one-launch backward (_bwd1x1_route), whose slab has ops.conv_bwd1x1_sums_rows rows."""
         if not (self.dgrad_bn_sums and self.bwd_from_act and self.precise) or lay.gin is None:
             return None
-        key = (lay.li, bool(concurrent), self._plan_epoch)
+        key = (lay.li, "fused" if fused else bool(concurrent), self._plan_epoch)
         hit = self._dgrad_sums_cache.get(key, False)
         if hit is not False:
             return hit
@@ -1926,7 +1951,7 @@ class Engine:
                 ch_lo = t.choff - lay.tin.choff
                 if t.buf != lay.tin.buf or t.ld != lay.tin.ld or ch_lo < 0 or ch_lo % 8 != 0 or ch_lo + prod.cout > lay.geom.cin:
                     continue
-                rows = ops.dgrad_sums_rows(lay.geom_act, concurrent)
+                rows = ops.conv_bwd1x1_sums_rows(lay.geom) if fused else ops.dgrad_sums_rows(lay.geom_act, concurrent)
                 if rows <= 0:
                     continue
                 slab = torch.empty(rows, 2, prod.cout, dtype=torch.float32, device=self.device)
@@ -2033,8 +2058,10 @@ class Engine:
             if side is None:
                 on_ready(flat, lay.p_lo, lay.p_hi)
             elif getattr(on_ready, "takes_fence", False):
-                # (the fused first block writes its whole slice on the launch stream: it needs the real fence)
-                on_ready(flat, lay.p_lo, lay.p_hi, fence if (lay.fused_stem or lay.stem_shadow) else on_side)
+                # (the fused first block writes its whole slice on the launch stream: it needs the real fence; so does a
+                # block whose weight gradient comes out of its one-launch backward, _bwd1x1_route)
+                on_ready(flat, lay.p_lo, lay.p_hi,
+                         fence if (lay.fused_stem or lay.stem_shadow or self._bwd1x1_route(lay)) else on_side)
             else:
                 with fence():
                     on_ready(flat, lay.p_lo, lay.p_hi)
@@ -2125,6 +2152,18 @@ class Engine:
                                       gmap[id(lay.bn.weight)], gmap[id(lay.bn.bias)], D, sums=sums_of.pop(lay.li, None))
             mask = lay.conv.mask.contiguous() if lay.conv.mask_flag else None
             dbias = gmap[id(lay.conv.bias)] if lay.conv.bias is not None else None
+            if self._bwd1x1_route(lay):
+                # a narrow dense 1x1 block: G, the sums of the PLAIN block that produced its input and dW from ONE pass over
+                # dY and the input, on the launch stream (timed under 'dgrad': the block has no 'wgrad' launch)
+                flush()
+                ds = self._dgrad_sums(lay, False, fused=True)
+                if ds is not None:
+                    sums_of[ds[2].li] = ds[1]
+                self._timed('dgrad', lay, ops.conv_bwd1x1, lay.geom, self.bufs[lay.tin.buf], lay.dy, lay.cout_p, 0, lay.wd,
+                            lay.gin, lay.tin.ld, lay.tin.choff, gmap[id(lay.conv.weight)], mask=mask, grad_scale=D, dbias=dbias,
+                            workspace=self._bwd1x1_ws, overflow=self.overflow, sums=ds[0] if ds is not None else None)
+                ready(lay)
+                continue
             def wgrad_of(ws, lay=lay, mask=mask, dbias=dbias):
                 """This block's weight gradient (nothing in the backward chain depends on it)."""
                 if lay.fold is not None:

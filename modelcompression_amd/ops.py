@@ -298,6 +298,39 @@ def conv_wgrad(g, x, dy, dy_ld, dy_choff, dw, mask=None, grad_scale=1.0, dbias=N
                                    ptr(dbias), ptr(workspace), workspace.numel(), stream_ptr()), "mcamd_conv_wgrad")
 
 
+def conv_bwd1x1_ok(g):
+    """(ok, reason): does `g` have the one-launch backward (mcamd_conv_bwd1x1)?  `reason` says why not.  Needs no GPU."""
+    why = C.c_char_p()
+    ok = bool(L.lib().mcamd_conv_bwd1x1_ok(C.byref(g), C.byref(why)))
+    return ok, (None if ok else why.value.decode())
+
+
+def conv_bwd1x1_sums_rows(g):
+    """Rows of the sums slab a conv_bwd1x1 launch of `g` writes (dgrad_sums(...) with that many rows); 0: refused geometry."""
+    return int(L.lib().mcamd_conv_bwd1x1_sums_rows(C.byref(g)))
+
+
+def conv_bwd1x1_wgrad_splits(g):
+    """fp32 [cout][cin] splits of the weight gradient a conv_bwd1x1 launch of `g` leaves in its workspace; 0: refused."""
+    return int(L.lib().mcamd_conv_bwd1x1_wgrad_splits(C.byref(g)))
+
+
+def conv_bwd1x1_workspace_bytes(g):
+    return int(L.lib().mcamd_conv_bwd1x1_workspace_bytes(C.byref(g)))
+
+
+def conv_bwd1x1(g, x, dy, dy_ld, dy_choff, wpd, gin, g_ld, g_choff, dw, mask=None, grad_scale=1.0, dbias=None, workspace=None,
+                overflow=None, sums=None):
+    """The whole backward of a dense 1x1 block in one launch + the finish pass: gin as conv_dgrad_raw stores it (with
+    `overflow`), dw / dbias as conv_wgrad, and with `sums` (dgrad_sums(...) over x itself, conv_bwd1x1_sums_rows(g) rows) the
+    producer's BatchNorm-backward sums."""
+    if workspace is None:
+        workspace = torch.empty(conv_bwd1x1_workspace_bytes(g), dtype=torch.uint8, device=dw.device)
+    check(L.lib().mcamd_conv_bwd1x1(C.byref(g), ptr(x), ptr(dy), dy_ld, dy_choff, ptr(wpd), ptr(gin), g_ld, g_choff, ptr(overflow),
+                                    C.byref(sums) if sums is not None else None, ptr(mask), grad_scale, ptr(dw), ptr(dbias),
+                                    ptr(workspace), workspace.numel(), stream_ptr()), "mcamd_conv_bwd1x1")
+
+
 def _perm_ptr(perm, C_):
     if perm is None:
         return None
