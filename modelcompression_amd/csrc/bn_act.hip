@@ -335,7 +335,7 @@ struct ActBwdArgs {
     float slope;
     long long items;
     int dy_pw;             // 2: dy in the padded form, 1: shared-halo form
-    const half_t* act;     // optional (bn_plain_bwd_act_kernel): the block's stored activation, padded NHWC fp16
+    const half_t* act;     // optional (source BN_SRC_ACT): the block's stored activation, padded NHWC fp16
     int act_ld, act_choff, act_pw;
     const half_t* pool_out;  // optional (bn_pool_sums_kernel): the block's POOLED activation, padded NHWC fp16 at H/2 x W/2
     int pool_out_ld, pool_out_choff, pool_out_pw;
@@ -368,29 +368,127 @@ __device__ __forceinline__ void block_partials_to_slab(const float (&sb)[8], con
     }
 }
 
+// The end of every backward kernel: pass 1 reports a clamped dY, pass 0 hands the thread's sums to the slab.
+template <int PHASE>
+__device__ __forceinline__ void bn_bwd_finish(const ActBwdArgs& a, const float (&sb)[8], const float (&sg)[8], bool overflowed, int CH) {
+    if (PHASE == 1 && overflowed && a.overflow) atomicOr(a.overflow, 1);
+    if (PHASE == 0) block_partials_to_slab(sb, sg, CH, a.slab, a.C);
+}
+
+// The shared pieces of the backward kernels: one prologue (BnBwdChan), one position type (PixPos), the 2x2 window
+// load / store, and the source parameter SRC of the specialised kernels -- where an element's value `u` in the linear
+// term, its LeakyReLU side and (MaxPool) its argmax key come from:
+//   BN_SRC_Y16 / BN_SRC_Y32: the saved raw conv output y, fp16 / fp32.  u = y, side = sign of z = y scale + shift, key =
+//                            leaky(z) as the forward pass stored it (compared as fp16 / as fp32: unrounded with the split
+//                            hi | lo storage that goes with an fp32 y).
+//   BN_SRC_ACT:              the activation the forward pass stored (fp16).  u = z = a > 0 ? a : a / slope -- or the saved
+//                            fp32 y on an ill-conditioned channel, below -- side = sign of a, key = a.
+enum { BN_SRC_Y16 = 0, BN_SRC_Y32 = 1, BN_SRC_ACT = 2 };
+
+// The constants of a thread's 8 channels, filled once per thread (bn_bwd_chan).  xhat = (u - off) mul:
+//   a y source: off = mean, mul = invstd, no channel `usey` (nothing to choose);
+//   the stored activation: act_xhat_source (common.h) -- off = beta, mul = 1 / gamma, and on the ILL-CONDITIONED
+//   channels, |gamma| < BN_ACT_T max(|beta|, 1), the y form again with usey set (need_y: the thread holds one).
+// Pass 1, with dm = scale (0 where dy_keep says the filter is pruned: its dY is not needed and is zeroed):
+//     out = dm (g_z - c1 - xhat c2) = dm g_z - (P u + Q),   P = dm c2 mul,  Q = dm c1 - P off     (per channel, hoisted)
+// The generic kernel takes the first form from c1 / c2 (it rounds differently), the specialised kernels the second.
+typedef float f32x8_t __attribute__((ext_vector_type(8)));
+struct BnBwdChan {
+    float sc[8], sh[8], mu[8], is[8];
+    float off[8], mul[8];
+    bool usey[8], need_y;
+    float c1[8], c2[8];                          // pass 1 only, and so are dm, P, Q
+    // The three constants of pass 1's element loop are 8-wide vector values, not arrays: the compiler splits a struct's
+    // arrays into 24 scalars and then pairs them for the packed fp32 instructions inside the loop (8-9 more VGPRs and
+    // an occupancy step in bn_plain_bwd_kernel<1, BN_SRC_Y16 | BN_SRC_Y32>); as vectors every instance keeps the
+    // registers it had with per-kernel arrays (profiles/bn_bwd_shared_pieces.txt).  Elements are read and written as [i].
+    f32x8_t dm, P, Q;
+};
+template <int PHASE, bool FROM_ACT>
+__device__ __forceinline__ void bn_bwd_chan(const ActBwdArgs& a, int c8, BnBwdChan& ch) {
+    loadf8(a.scale + c8, ch.sc);
+    loadf8(a.shift + c8, ch.sh);
+    loadf8(a.mean + c8, ch.mu);
+    loadf8(a.invstd + c8, ch.is);
+    if (FROM_ACT) {
+        ch.need_y = act_xhat_source(ch.sc, ch.sh, ch.mu, ch.is, a.y != nullptr, ch.off, ch.mul, ch.usey);
+    } else {
+        ch.need_y = false;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ch.off[i] = ch.mu[i], ch.mul[i] = ch.is[i], ch.usey[i] = false;
+    }
+    if (PHASE == 1) {
+        loadf8(a.coef + c8, ch.c1);
+        loadf8(a.coef + a.C + c8, ch.c2);
+        if (a.dy_keep) {
+            float kp[8];
+            loadf8(a.dy_keep + c8, kp);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ch.dm[i] = kp[i] != 0.f ? ch.sc[i] : 0.f;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ch.dm[i] = ch.sc[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            ch.P[i] = ch.dm[i] * ch.c2[i] * ch.mul[i];
+            ch.Q[i] = ch.dm[i] * ch.c1[i] - ch.P[i] * ch.off[i];
+        }
+    }
+}
+
+// (b, h, w) of the 32-bit pixel index `pix` of a [B][H][W] tensor (full resolution, or H/2 x W/2 for the windows of a
+// MaxPool block), stepped without a division: the specialised kernels decompose their start and their grid stride once.
+struct PixPos {
+    unsigned pix;
+    int b, h, w;
+};
+__device__ __forceinline__ PixPos pix_pos(unsigned pix, int H, int W) {
+    const int HW = H * W;
+    PixPos p;
+    p.pix = pix;
+    p.b = (int)(pix / (unsigned)HW);
+    const int rem = (int)(pix - (unsigned)p.b * (unsigned)HW);
+    p.h = rem / W, p.w = rem - p.h * W;
+    return p;
+}
+// p += s (s.pix pixels, decomposed once), with carries
+__device__ __forceinline__ void pix_pos_step(PixPos& p, const PixPos& s, int H, int W) {
+    p.pix += s.pix;
+    p.w += s.w;
+    if (p.w >= W) p.w -= W, ++p.h;
+    p.h += s.h;
+    if (p.h >= H) p.h -= H, ++p.b;
+    p.b += s.b;
+}
+
+// The 2x2 window of 8-channel groups whose first pixel is element `i0` of `base` (fp32 or fp16), `ld` elements per pixel
+// and `row` per image row, in (h, w) scan order; and its fp16 store.
+template <bool F32>
+__device__ __forceinline__ void load_win(const void* base, long long i0, long long ld, long long row, float (&v)[4][8]) {
+    typedef typename std::conditional<F32, float, half_t>::type elem_t;
+    const elem_t* p = (const elem_t*)base + i0;
+    load_y<F32>(p, 0, v[0]);
+    load_y<F32>(p + ld, 0, v[1]);
+    load_y<F32>(p + row, 0, v[2]);
+    load_y<F32>(p + row + ld, 0, v[3]);
+}
+__device__ __forceinline__ void store_win(half_t* p, long long ld, long long row, const float (&v)[4][8]) {
+    store8(p, v[0]);
+    store8(p + ld, v[1]);
+    store8(p + row, v[2]);
+    store8(p + row + ld, v[3]);
+}
+
 template <int MODE, int PHASE, bool Y32>
 __global__ __launch_bounds__(256) void bn_act_bwd_kernel(ActBwdArgs a) {
     constexpr int NP = MODE == MCAMD_DST_PLAIN ? 1 : 4;
     const int CH = a.C >> 3;
     const int c8 = (threadIdx.x % CH) * 8;
-    float sc[8], sh[8], mu[8], is[8], c1[8], c2[8], dm[8];
-    loadf8(a.scale + c8, sc);
-    loadf8(a.shift + c8, sh);
-    loadf8(a.mean + c8, mu);
-    loadf8(a.invstd + c8, is);
-    if (PHASE == 1) {
-        loadf8(a.coef + c8, c1);
-        loadf8(a.coef + a.C + c8, c2);
-        if (a.dy_keep) {
-            float kp[8];
-            loadf8(a.dy_keep + c8, kp);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = kp[i] != 0.f ? sc[i] : 0.f;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = sc[i];
-        }
-    }
+    BnBwdChan ch;
+    bn_bwd_chan<PHASE, false>(a, c8, ch);
+    const auto &sc = ch.sc, &sh = ch.sh, &mu = ch.mu, &is = ch.is, &c1 = ch.c1, &c2 = ch.c2;
+    const f32x8_t& dm = ch.dm;
     float sb[8], sg[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) sb[i] = sg[i] = 0.f;
@@ -489,543 +587,222 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(ActBwdArgs a) {
             }
         }
     }
-    if (PHASE == 1 && sat && a.overflow) atomicOr(a.overflow, 1);
-
-    if (PHASE == 0) {
-        block_partials_to_slab(sb, sg, CH, a.slab, a.C);
-    }
+    bn_bwd_finish<PHASE>(a, sb, sg, sat, CH);
 }
 
-// PLAIN blocks (16 of YOLOv2's 21 BatchNorm blocks) without a second gradient: the same hoisted form as bn_pool_bwd_kernel
-// below, and no position arithmetic beyond one incremental (b, h, w) for the padded dY address.  The generic kernel's two
-// 64-bit divisions per 48-byte item made its loop 450-640 instructions long; on the 13x13 layers (5 items per thread,
+// PLAIN blocks (16 of YOLOv2's 21 BatchNorm blocks) without a second gradient: the hoisted form out = dm g_z - (P u + Q)
+// (BnBwdChan), and no position arithmetic beyond one incremental (b, h, w) for the padded addresses.  The generic kernel's
+// two 64-bit divisions per 48-byte item made its loop 450-640 instructions long; on the 13x13 layers (5 items per thread,
 // 4 waves per SIMD) that is ~17 us of pure instruction issue for a pass that moves 44 MB -- 14.7 us measured against
 // 9 us for the forward pass over the same bytes.
-template <int PHASE, bool Y32>
-__global__ __launch_bounds__(256) void bn_plain_bwd_kernel(ActBwdArgs a) {
-    const int CH = a.C >> 3, lg = __ffs(CH) - 1;        // C / 8 is a power of two (check_c)
-    const int c8 = (threadIdx.x & (CH - 1)) * 8;
-    float sc[8], sh[8], mu[8], is[8], A[8], Bc[8], dm[8];
-    loadf8(a.scale + c8, sc);
-    loadf8(a.shift + c8, sh);
-    loadf8(a.mean + c8, mu);
-    loadf8(a.invstd + c8, is);
-    if (PHASE == 1) {
-        float c1[8], c2[8];
-        loadf8(a.coef + c8, c1);
-        loadf8(a.coef + a.C + c8, c2);
-        if (a.dy_keep) {
-            float kp[8];
-            loadf8(a.dy_keep + c8, kp);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = kp[i] != 0.f ? sc[i] : 0.f;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = sc[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            Bc[i] = dm[i] * c2[i] * is[i];
-            A[i] = dm[i] * c1[i] - Bc[i] * mu[i];
-        }
-    }
-    float sb[8], sg[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sb[i] = sg[i] = 0.f;
-    float satmax = 0.f;
-    const int HW = a.H * a.W;
-    const unsigned npix = (unsigned)(a.items >> lg);
-    const unsigned stride = (gridDim.x * 256u) >> lg;                      // pixels per grid stride
-    unsigned pix = (blockIdx.x * 256u + threadIdx.x) >> lg;
-    int b = (int)(pix / (unsigned)HW), rem = (int)(pix - (unsigned)b * (unsigned)HW);
-    int h = rem / a.W, w = rem - h * a.W;
-    const int sb_ = (int)(stride / (unsigned)HW), srem = (int)(stride - (unsigned)sb_ * (unsigned)HW);
-    const int sh_ = srem / a.W, sw_ = srem - sh_ * a.W;
-    for (; pix < npix; pix += stride) {
-        float yv[8], gv[8];
-        load_y<Y32>(a.y, (long long)pix * a.y_ld + a.y_choff + c8, yv);
-        load8(a.g + (long long)pix * a.g_ld + a.g_choff + c8, gv);
-        float out[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float z = yv[i] * sc[i] + sh[i];
-            const float gz = z > 0.f ? gv[i] : gv[i] * a.slope;
-            if (PHASE == 0) {
-                sb[i] += gz;
-                sg[i] += gz * ((yv[i] - mu[i]) * is[i]);
-            } else {
-                const float o = dm[i] * gz - (Bc[i] * yv[i] + A[i]);
-                out[i] = o;
-                satmax = fmaxf(satmax, fabsf(o));
-            }
-        }
-        if (PHASE == 1) {
-            store8(a.dy + pad_off(b, h, w, a.H, a.W, a.dy_ld, a.dy_pw) + a.dy_choff + c8, out);
-            w += sw_;
-            if (w >= a.W) w -= a.W, ++h;
-            h += sh_;
-            if (h >= a.H) h -= a.H, ++b;
-            b += sb_;
-        }
-    }
-    if (PHASE == 1 && satmax > 65504.f && a.overflow) atomicOr(a.overflow, 1);
-    if (PHASE == 0) {
-        block_partials_to_slab(sb, sg, CH, a.slab, a.C);
-    }
-}
-
-// Backward passes from the stored activation (bn_plain_bwd_act_kernel, bn_pool_bwd_act_kernel): a channel is
-// ILL-CONDITIONED when |gamma| < BN_ACT_T max(|beta|, 1).  Recovering xhat = (z - beta) / gamma from an fp16 activation
-// costs up to 2^-11 (|xhat| + |beta / gamma|); on the other channels that is at most 2^-11 (1 / BN_ACT_T + |xhat|).  With
-// |gamma| = |scale| / invstd the test is |scale| < BN_ACT_T max(|beta|, 1) invstd (gamma == 0 always included).
-// (BN_ACT_T and act_xhat_source: common.h -- the dgrad epilogue that takes a PLAIN block's sums applies the same rule)
-
-// The same two passes WITHOUT the saved raw output: LeakyReLU is invertible, so a PLAIN block's pre-activation is
-// recovered from the activation the forward pass stored for the consumer (fp16, the hi plane of split storage):
-// z = a > 0 ? a : a / slope, xhat = (z - beta) / gamma.  With the split-operand precisions the saved y is fp32: the two
-// passes read 2 instead of 4 bytes per element for it (0.89 -> 0.65 ms per "mixed" B=64 step), at the operand precision
-// every backward pass has anyway (G and dY are fp16).  With dm = gamma invstd (0 for a pruned filter):
+//
+// SRC == BN_SRC_ACT: the same two passes WITHOUT the saved raw output.  LeakyReLU is invertible, so a PLAIN block's
+// pre-activation is recovered from the activation the forward pass stored for the consumer (fp16, the hi plane of split
+// storage): z = a > 0 ? a : a / slope, xhat = (z - beta) / gamma.  With the split-operand precisions the saved y is fp32:
+// the two passes read 2 instead of 4 bytes per element for it (0.89 -> 0.65 ms per "mixed" B=64 step), at the operand
+// precision every backward pass has anyway (G and dY are fp16).  With dm = gamma invstd (0 for a pruned filter):
 //     out = dm g_z - (P z + Q),   P = dm c2 / gamma,  Q = dm c1 - P beta     (per channel, hoisted)
 // The stored activation carries an fp16 rounding of up to 2^-11 |z|, so xhat = (z - beta) / gamma is off by up to
-// 2^-11 (|xhat| + |beta / gamma|): useless where |gamma| << |beta| (at gamma = 1e-4, beta = 1 every z rounds to beta).
-// Channels with |gamma| < BN_ACT_T max(|beta|, 1) (act_xhat_source, gamma = 0 included) take xhat = (y - mu) invstd from the
-// saved fp32 y in BOTH passes instead, with the y kernels' P = dm c2 invstd, Q = dm c1 - P mu; the LeakyReLU side stays
-// the sign of the stored activation.  Only the threads that hold such a channel read y: a healthy network's backward
-// pass reads what it read without the rule.  y = NULL: those channels use the activation as every other channel does
-// (gamma == 0: xhat 0, so dgamma 0; dY is 0 there either way, dm = 0).
-template <int PHASE>
-__global__ __launch_bounds__(256) void bn_plain_bwd_act_kernel(ActBwdArgs a) {
+// 2^-11 (|xhat| + |beta / gamma|): useless where |gamma| << |beta| (at gamma = 1e-4, beta = 1 every z rounds to beta); on
+// the other channels that is at most 2^-11 (1 / BN_ACT_T + |xhat|).  A channel is ILL-CONDITIONED when |gamma| <
+// BN_ACT_T max(|beta|, 1); with |gamma| = |scale| / invstd the test is |scale| < BN_ACT_T max(|beta|, 1) invstd (gamma == 0
+// always included).  (BN_ACT_T and act_xhat_source: common.h -- the dgrad epilogue that takes a PLAIN block's sums
+// applies the same rule.)  Those channels take xhat = (y - mu) invstd from the saved fp32 y in BOTH passes instead, with
+// the y sources' P = dm c2 invstd, Q = dm c1 - P mu; the LeakyReLU side stays the sign of the stored activation.  Only the
+// threads that hold such a channel read y: a healthy network's backward pass reads what it read without the rule.
+// y = NULL: those channels use the activation as every other channel does (gamma == 0: xhat 0, so dgamma 0; dY is 0 there
+// either way, dm = 0).
+template <int PHASE, int SRC>
+__global__ __launch_bounds__(256) void bn_plain_bwd_kernel(ActBwdArgs a) {
+    constexpr bool ACT = SRC == BN_SRC_ACT;
     const int CH = a.C >> 3, lg = __ffs(CH) - 1;        // C / 8 is a power of two (check_c)
     const int c8 = (threadIdx.x & (CH - 1)) * 8;
-    float sc[8], sh[8], mu[8], is[8], off[8], mul[8], P[8], Q[8], dm[8];
-    bool usey[8];
-    loadf8(a.scale + c8, sc);
-    loadf8(a.shift + c8, sh);
-    loadf8(a.mean + c8, mu);
-    loadf8(a.invstd + c8, is);
-    const bool need_y = act_xhat_source(sc, sh, mu, is, a.y != nullptr, off, mul, usey);
-    if (PHASE == 1) {
-        float c1[8], c2[8];
-        loadf8(a.coef + c8, c1);
-        loadf8(a.coef + a.C + c8, c2);
-        if (a.dy_keep) {
-            float kp[8];
-            loadf8(a.dy_keep + c8, kp);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = kp[i] != 0.f ? sc[i] : 0.f;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = sc[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            P[i] = dm[i] * c2[i] * mul[i];
-            Q[i] = dm[i] * c1[i] - P[i] * off[i];
-        }
-    }
+    BnBwdChan ch;
+    bn_bwd_chan<PHASE, ACT>(a, c8, ch);
     float sb[8], sg[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) sb[i] = sg[i] = 0.f;
     float satmax = 0.f;
     const float inv_slope = 1.0f / a.slope;
-    const int HW = a.H * a.W;
     const unsigned npix = (unsigned)(a.items >> lg);
     const unsigned stride = (gridDim.x * 256u) >> lg;                      // pixels per grid stride
-    unsigned pix = (blockIdx.x * 256u + threadIdx.x) >> lg;
-    int b = (int)(pix / (unsigned)HW), rem = (int)(pix - (unsigned)b * (unsigned)HW);
-    int h = rem / a.W, w = rem - h * a.W;
-    const int sb_ = (int)(stride / (unsigned)HW), srem = (int)(stride - (unsigned)sb_ * (unsigned)HW);
-    const int sh_ = srem / a.W, sw_ = srem - sh_ * a.W;
-    for (; pix < npix; pix += stride) {
-        float av[8], gv[8];
-        load8(a.act + pad_off(b, h, w, a.H, a.W, a.act_ld, a.act_pw) + a.act_choff + c8, av);
-        load8(a.g + (long long)pix * a.g_ld + a.g_choff + c8, gv);
-        float out[8], z[8];
+    PixPos p = pix_pos((blockIdx.x * 256u + threadIdx.x) >> lg, a.H, a.W);
+    const PixPos step = pix_pos(stride, a.H, a.W);
+    for (; p.pix < npix; pix_pos_step(p, step, a.H, a.W)) {
+        float sv[8], gv[8], u[8];                        // sv: the source's value, y or the stored activation
+        if (ACT) load8(a.act + pad_off(p.b, p.h, p.w, a.H, a.W, a.act_ld, a.act_pw) + a.act_choff + c8, sv);
+        else load_y<SRC == BN_SRC_Y32>(a.y, (long long)p.pix * a.y_ld + a.y_choff + c8, sv);
+        load8(a.g + (long long)p.pix * a.g_ld + a.g_choff + c8, gv);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) z[i] = av[i] > 0.f ? av[i] : av[i] * inv_slope;
-        if (need_y) {                                    // ill-conditioned channels: the saved y in place of z
+        for (int i = 0; i < 8; ++i) u[i] = !ACT ? sv[i] : sv[i] > 0.f ? sv[i] : sv[i] * inv_slope;
+        if (ACT && ch.need_y) {                          // ill-conditioned channels: the saved y in place of z
             float yv[8];
-            load_y<true>(a.y, (long long)pix * a.y_ld + a.y_choff + c8, yv);
+            load_y<true>(a.y, (long long)p.pix * a.y_ld + a.y_choff + c8, yv);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) z[i] = usey[i] ? yv[i] : z[i];
+            for (int i = 0; i < 8; ++i) u[i] = ch.usey[i] ? yv[i] : u[i];
         }
+        float out[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const float gz = av[i] > 0.f ? gv[i] : gv[i] * a.slope;
+            const float side = ACT ? sv[i] : sv[i] * ch.sc[i] + ch.sh[i];
+            const float gz = side > 0.f ? gv[i] : gv[i] * a.slope;
             if (PHASE == 0) {
                 sb[i] += gz;
-                sg[i] += gz * ((z[i] - off[i]) * mul[i]);
+                sg[i] += gz * ((u[i] - ch.off[i]) * ch.mul[i]);
             } else {
-                const float o = dm[i] * gz - (P[i] * z[i] + Q[i]);
+                const float o = ch.dm[i] * gz - (ch.P[i] * u[i] + ch.Q[i]);
                 out[i] = o;
                 satmax = fmaxf(satmax, fabsf(o));
             }
         }
-        if (PHASE == 1) store8(a.dy + pad_off(b, h, w, a.H, a.W, a.dy_ld, a.dy_pw) + a.dy_choff + c8, out);
-        w += sw_;
-        if (w >= a.W) w -= a.W, ++h;
-        h += sh_;
-        if (h >= a.H) h -= a.H, ++b;
-        b += sb_;
+        if (PHASE == 1) store8(a.dy + pad_off(p.b, p.h, p.w, a.H, a.W, a.dy_ld, a.dy_pw) + a.dy_choff + c8, out);
     }
-    if (PHASE == 1 && satmax > 65504.f && a.overflow) atomicOr(a.overflow, 1);
-    if (PHASE == 0) {
-        block_partials_to_slab(sb, sg, CH, a.slab, a.C);
-    }
+    bn_bwd_finish<PHASE>(a, sb, sg, satmax > 65504.f, CH);
 }
 
 // MaxPool blocks (conv2 / conv5 / conv8 / conv13 of YOLOv2: 0.7 of the 1.5 ms of BatchNorm backward).
 // The generic kernel above spends ~1 300 instructions per item there (SQ_ACTIVE_INST_ANY 0.62 of the wave cycles, 3.6 TB/s:
 // it is issue-bound, not HBM-bound) because it treats the four window pixels as four full backward elements.  Only the
-// argmax pixel receives a gradient, so with  out = dm (g_z - c1 - xhat c2),  xhat = (y - mu) is:
-//     out_k = [k == arg] dm g_z  -  (Bc y_k + A),      Bc = dm c2 is,  A = dm c1 - Bc mu     (per channel, hoisted)
+// argmax pixel receives a gradient, so with  out = dm (g_z - c1 - xhat c2),  xhat = (u - off) mul:
+//     out_k = [k == arg] dm g_z  -  (P u_k + Q)       (P, Q per channel, hoisted: BnBwdChan)
 // i.e. one multiply-add per non-argmax element; the sums of pass 0 need the argmax element only.  The argmax itself is
-// taken exactly as the generic kernel takes it (first maximum of the activations AS STORED by the forward pass, compared
-// as fp16 values here instead of converting them back).  32-bit positions stepped incrementally (no division in the loop).
+// taken exactly as the generic kernel takes it (first maximum of the activations AS STORED by the forward pass; a y16
+// source compares them as fp16 values instead of converting them back).  32-bit positions stepped incrementally (no
+// division in the loop).
 // G2: a second gradient at full resolution (the route that reads conv13 beside its pool) is added to every window pixel,
 // so every pixel has a g_z -- still without the generic kernel's per-pixel xhat / select chains.
-template <int PHASE, bool Y32, bool G2>
-__global__ __launch_bounds__(256) void bn_pool_bwd_kernel(ActBwdArgs a) {
-    const int CH = a.C >> 3, lg = __ffs(CH) - 1;        // C / 8 is a power of two (check_c)
-    const int c8 = (threadIdx.x & (CH - 1)) * 8;
-    float sc[8], sh[8], mu[8], is[8], A[8], Bc[8], dm[8];
-    loadf8(a.scale + c8, sc);
-    loadf8(a.shift + c8, sh);
-    loadf8(a.mean + c8, mu);
-    loadf8(a.invstd + c8, is);
-    if (PHASE == 1) {
-        float c1[8], c2[8];
-        loadf8(a.coef + c8, c1);
-        loadf8(a.coef + a.C + c8, c2);
-        if (a.dy_keep) {
-            float kp[8];
-            loadf8(a.dy_keep + c8, kp);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = kp[i] != 0.f ? sc[i] : 0.f;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = sc[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            Bc[i] = dm[i] * c2[i] * is[i];
-            A[i] = dm[i] * c1[i] - Bc[i] * mu[i];
-        }
-    }
-    float sb[8], sg[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sb[i] = sg[i] = 0.f;
-    float satmax = 0.f;
-    const int Ho = a.H >> 1, Wo = a.W >> 1, HoWo = Ho * Wo;
-    const unsigned npix = (unsigned)(a.items >> lg);                       // pooled pixels
-    const unsigned stride = (gridDim.x * 256u) >> lg;                      // pooled pixels per grid stride
-    unsigned pix = (blockIdx.x * 256u + threadIdx.x) >> lg;
-    // (b, ho, wo) of `pix` and of the stride, advanced with carries
-    int b = (int)(pix / (unsigned)HoWo), rem = (int)(pix - (unsigned)b * (unsigned)HoWo);
-    int ho = rem / Wo, wo = rem - ho * Wo;
-    const int sb_ = (int)(stride / (unsigned)HoWo), srem = (int)(stride - (unsigned)sb_ * (unsigned)HoWo);
-    const int sho = srem / Wo, swo = srem - sho * Wo;
-    const long long yrow = (long long)a.W * a.y_ld;                         // elements per image row of y
-    for (; pix < npix; pix += stride) {
-        const half_t* yp = (const half_t*)a.y;
-        const long long y0 = (((long long)b * a.H + 2 * ho) * a.W + 2 * wo) * a.y_ld + a.y_choff + c8;
-        float yv[4][8], gv[8];
-        if (Y32) {
-            const float* yf = (const float*)a.y;
-            loadf8(yf + y0, yv[0]);
-            loadf8(yf + y0 + a.y_ld, yv[1]);
-            loadf8(yf + y0 + yrow, yv[2]);
-            loadf8(yf + y0 + yrow + a.y_ld, yv[3]);
-        } else {
-            load8(yp + y0, yv[0]);
-            load8(yp + y0 + a.y_ld, yv[1]);
-            load8(yp + y0 + yrow, yv[2]);
-            load8(yp + y0 + yrow + a.y_ld, yv[3]);
-        }
-        load8(a.g + (long long)pix * a.g_ld + a.g_choff + c8, gv);
-        float g2v[G2 ? 4 : 1][8];
-        if (G2) {
-            const half_t* q0 = a.g2 + (((long long)b * a.H + 2 * ho) * a.W + 2 * wo) * a.g2_ld + a.g2_choff + c8;
-            const long long g2row = (long long)a.W * a.g2_ld;
-            load8(q0, g2v[0]);
-            load8(q0 + a.g2_ld, g2v[G2 ? 1 : 0]);
-            load8(q0 + g2row, g2v[G2 ? 2 : 0]);
-            load8(q0 + g2row + a.g2_ld, g2v[G2 ? 3 : 0]);
-        }
-        float out[4][8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            float z[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) z[k] = yv[k][i] * sc[i] + sh[i];
-            // first maximum in (h, w) scan order of the activations as the forward pass stored them
-            int arg = 0;
-            float zs = z[0], ys = yv[0][i];
-            if (Y32) {
-                float best = z[0] > 0.f ? z[0] : z[0] * a.slope;
-#pragma unroll
-                for (int k = 1; k < 4; ++k) {
-                    const float av = z[k] > 0.f ? z[k] : z[k] * a.slope;
-                    const bool gt = av > best;
-                    best = gt ? av : best, arg = gt ? k : arg, zs = gt ? z[k] : zs, ys = gt ? yv[k][i] : ys;
-                }
-            } else {
-                half_t best = (half_t)(z[0] > 0.f ? z[0] : z[0] * a.slope);
-#pragma unroll
-                for (int k = 1; k < 4; ++k) {
-                    const half_t av = (half_t)(z[k] > 0.f ? z[k] : z[k] * a.slope);
-                    const bool gt = av > best;
-                    best = gt ? av : best, arg = gt ? k : arg, zs = gt ? z[k] : zs, ys = gt ? yv[k][i] : ys;
-                }
-            }
-            if (G2) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float ga = (k == arg ? gv[i] : 0.f) + g2v[G2 ? k : 0][i];
-                    const float gzk = z[k] > 0.f ? ga : ga * a.slope;
-                    if (PHASE == 0) {
-                        sb[i] += gzk;
-                        sg[i] += gzk * ((yv[k][i] - mu[i]) * is[i]);
-                    } else {
-                        const float o = dm[i] * gzk - (Bc[i] * yv[k][i] + A[i]);
-                        out[k][i] = o;
-                        satmax = fmaxf(satmax, fabsf(o));
-                    }
-                }
-            } else {
-                const float gz = zs > 0.f ? gv[i] : gv[i] * a.slope;
-                if (PHASE == 0) {
-                    sb[i] += gz;
-                    sg[i] += gz * ((ys - mu[i]) * is[i]);
-                } else {
-                    const float t = dm[i] * gz;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float o = (k == arg ? t : 0.f) - (Bc[i] * yv[k][i] + A[i]);
-                        out[k][i] = o;
-                        satmax = fmaxf(satmax, fabsf(o));
-                    }
-                }
-            }
-        }
-        if (PHASE == 1) {
-            half_t* d0 = a.dy + pad_off(b, 2 * ho, 2 * wo, a.H, a.W, a.dy_ld, a.dy_pw) + a.dy_choff + c8;
-            const long long drow = (long long)(a.W + a.dy_pw) * a.dy_ld;
-            store8(d0, out[0]);
-            store8(d0 + a.dy_ld, out[1]);
-            store8(d0 + drow, out[2]);
-            store8(d0 + drow + a.dy_ld, out[3]);
-        }
-        wo += swo;
-        if (wo >= Wo) wo -= Wo, ++ho;
-        ho += sho;
-        if (ho >= Ho) ho -= Ho, ++b;
-        b += sb_;
-    }
-    if (PHASE == 1 && satmax > 65504.f && a.overflow) atomicOr(a.overflow, 1);
-    if (PHASE == 0) {
-        block_partials_to_slab(sb, sg, CH, a.slab, a.C);
-    }
-}
-
-// MaxPool blocks WITHOUT the saved raw output (second session of round 4): as bn_plain_bwd_act_kernel recovers a PLAIN block's
-// pre-activation from the stored activation, a MaxPool block's comes from a FULL-RESOLUTION fp16 copy of its activation
-// (the forward pass writes one beside the pooled output: mcamd_act_desc.pool_act).  z = a > 0 ? a : a / slope, xhat =
+//
+// SRC == BN_SRC_ACT: MaxPool blocks WITHOUT the saved raw output.  As a PLAIN block's pre-activation is recovered from the
+// stored activation (bn_plain_bwd_kernel), a MaxPool block's comes from a FULL-RESOLUTION fp16 copy of its activation (the
+// forward pass writes one beside the pooled output: mcamd_act_desc.pool_act).  z = a > 0 ? a : a / slope, xhat =
 // (z - beta) / gamma; the window's argmax is the maximum of the four STORED values -- the forward pass stores them so that
 // the element it pooled (first maximum of the unrounded activations) is their strict maximum -- and the LeakyReLU side of
-// every element is the sign of its stored value (rounding keeps the sign).  Split-operand engines save y as fp32: the two passes read 2 instead of 4 bytes per
-// element (conv2 / 5 / 8 / 13 at B = 64: 0.66 GB less per step) for 2 bytes more written by the forward pass where the copy
-// did not exist.  out_k = [k == arg] dm g_z - (P z_k + Q) with P, Q of bn_plain_bwd_act_kernel; ill-conditioned channels
-// (act_xhat_source) take z_k from the saved fp32 y in both passes, as there, while the argmax and the LeakyReLU sides still come
-// from the stored activation.
-template <int PHASE, bool G2>
-__global__ __launch_bounds__(256) void bn_pool_bwd_act_kernel(ActBwdArgs a) {
+// every element is the sign of its stored value (rounding keeps the sign).  Split-operand engines save y as fp32: the two
+// passes read 2 instead of 4 bytes per element (conv2 / 5 / 8 / 13 at B = 64: 0.66 GB less per step) for 2 bytes more
+// written by the forward pass where the copy did not exist.  Ill-conditioned channels (act_xhat_source) take u_k from the
+// saved fp32 y in both passes, as in the PLAIN kernel, while the argmax and the LeakyReLU sides still come from the stored
+// activation.
+template <int PHASE, int SRC, bool G2>
+__global__ __launch_bounds__(256) void bn_pool_bwd_kernel(ActBwdArgs a) {
+    constexpr bool ACT = SRC == BN_SRC_ACT;
     const int CH = a.C >> 3, lg = __ffs(CH) - 1;        // C / 8 is a power of two (check_c)
     const int c8 = (threadIdx.x & (CH - 1)) * 8;
-    float sc[8], sh[8], mu[8], is[8], off[8], mul[8], P[8], Q[8], dm[8];
-    bool usey[8];
-    loadf8(a.scale + c8, sc);
-    loadf8(a.shift + c8, sh);
-    loadf8(a.mean + c8, mu);
-    loadf8(a.invstd + c8, is);
-    const bool need_y = act_xhat_source(sc, sh, mu, is, a.y != nullptr, off, mul, usey);
-    if (PHASE == 1) {
-        float c1[8], c2[8];
-        loadf8(a.coef + c8, c1);
-        loadf8(a.coef + a.C + c8, c2);
-        if (a.dy_keep) {
-            float kp[8];
-            loadf8(a.dy_keep + c8, kp);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = kp[i] != 0.f ? sc[i] : 0.f;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dm[i] = sc[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            P[i] = dm[i] * c2[i] * mul[i];
-            Q[i] = dm[i] * c1[i] - P[i] * off[i];
-        }
-    }
+    BnBwdChan ch;
+    bn_bwd_chan<PHASE, ACT>(a, c8, ch);
     float sb[8], sg[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) sb[i] = sg[i] = 0.f;
     float satmax = 0.f;
     const float inv_slope = 1.0f / a.slope;
-    const int Ho = a.H >> 1, Wo = a.W >> 1, HoWo = Ho * Wo;
+    const int Ho = a.H >> 1, Wo = a.W >> 1;
     const unsigned npix = (unsigned)(a.items >> lg);                       // pooled pixels
     const unsigned stride = (gridDim.x * 256u) >> lg;                      // pooled pixels per grid stride
-    unsigned pix = (blockIdx.x * 256u + threadIdx.x) >> lg;
-    int b = (int)(pix / (unsigned)HoWo), rem = (int)(pix - (unsigned)b * (unsigned)HoWo);
-    int ho = rem / Wo, wo = rem - ho * Wo;
-    const int sb_ = (int)(stride / (unsigned)HoWo), srem = (int)(stride - (unsigned)sb_ * (unsigned)HoWo);
-    const int sho = srem / Wo, swo = srem - sho * Wo;
-    const long long arow = (long long)(a.W + a.act_pw) * a.act_ld;          // elements per padded image row of the activation
-    const long long yrow = (long long)a.W * a.y_ld;
-    for (; pix < npix; pix += stride) {
-        const half_t* ap = a.act + pad_off(b, 2 * ho, 2 * wo, a.H, a.W, a.act_ld, a.act_pw) + a.act_choff + c8;
-        float av[4][8], gv[8];
-        load8(ap, av[0]);
-        load8(ap + a.act_ld, av[1]);
-        load8(ap + arow, av[2]);
-        load8(ap + arow + a.act_ld, av[3]);
-        load8(a.g + (long long)pix * a.g_ld + a.g_choff + c8, gv);
-        float g2v[G2 ? 4 : 1][8];
-        if (G2) {
-            const half_t* q0 = a.g2 + (((long long)b * a.H + 2 * ho) * a.W + 2 * wo) * a.g2_ld + a.g2_choff + c8;
-            const long long g2row = (long long)a.W * a.g2_ld;
-            load8(q0, g2v[0]);
-            load8(q0 + a.g2_ld, g2v[G2 ? 1 : 0]);
-            load8(q0 + g2row, g2v[G2 ? 2 : 0]);
-            load8(q0 + g2row + a.g2_ld, g2v[G2 ? 3 : 0]);
-        }
-        float z[4][8];
+    PixPos p = pix_pos((blockIdx.x * 256u + threadIdx.x) >> lg, Ho, Wo);
+    const PixPos step = pix_pos(stride, Ho, Wo);
+    // elements per image row: y and g2 are unpadded, the activation copy and dY padded
+    const long long yrow = (long long)a.W * a.y_ld, g2row = (long long)a.W * a.g2_ld;
+    const long long arow = (long long)(a.W + a.act_pw) * a.act_ld, drow = (long long)(a.W + a.dy_pw) * a.dy_ld;
+    for (; p.pix < npix; pix_pos_step(p, step, Ho, Wo)) {
+        const long long fp = ((long long)p.b * a.H + 2 * p.h) * a.W + 2 * p.w;   // the window's first pixel, unpadded
+        float sv[4][8], gv[8], g2v[4][8], u[4][8];       // sv: the source's values, y or the stored activation
+        if (ACT) load_win<false>(a.act, pad_off(p.b, 2 * p.h, 2 * p.w, a.H, a.W, a.act_ld, a.act_pw) + a.act_choff + c8, a.act_ld, arow, sv);
+        else load_win<SRC == BN_SRC_Y32>(a.y, fp * a.y_ld + a.y_choff + c8, a.y_ld, yrow, sv);
+        load8(a.g + (long long)p.pix * a.g_ld + a.g_choff + c8, gv);
+        if (G2) load_win<false>(a.g2, fp * a.g2_ld + a.g2_choff + c8, a.g2_ld, g2row, g2v);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int i = 0; i < 8; ++i) z[k][i] = av[k][i] > 0.f ? av[k][i] : av[k][i] * inv_slope;
-        if (need_y) {                                    // ill-conditioned channels: the saved y in place of z
-            const float* yf = (const float*)a.y;
-            const long long y0 = (((long long)b * a.H + 2 * ho) * a.W + 2 * wo) * a.y_ld + a.y_choff + c8;
+            for (int i = 0; i < 8; ++i) u[k][i] = !ACT ? sv[k][i] : sv[k][i] > 0.f ? sv[k][i] : sv[k][i] * inv_slope;
+        if (ACT && ch.need_y) {                          // ill-conditioned channels: the saved y in place of z
             float yv[4][8];
-            loadf8(yf + y0, yv[0]);
-            loadf8(yf + y0 + a.y_ld, yv[1]);
-            loadf8(yf + y0 + yrow, yv[2]);
-            loadf8(yf + y0 + yrow + a.y_ld, yv[3]);
+            load_win<true>(a.y, fp * a.y_ld + a.y_choff + c8, a.y_ld, yrow, yv);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) z[k][i] = usey[i] ? yv[k][i] : z[k][i];
+                for (int i = 0; i < 8; ++i) u[k][i] = ch.usey[i] ? yv[k][i] : u[k][i];
         }
         float out[4][8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            // first maximum in (h, w) scan order of the activations as the forward pass stored them
+            float side[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) side[k] = ACT ? sv[k][i] : sv[k][i] * ch.sc[i] + ch.sh[i];
+            // the activation of element k as the forward pass stored it
+            auto key = [&](int k) {
+                if constexpr (ACT) return side[k];
+                else if constexpr (SRC == BN_SRC_Y32) return side[k] > 0.f ? side[k] : side[k] * a.slope;
+                else return (half_t)(side[k] > 0.f ? side[k] : side[k] * a.slope);
+            };
+            // first maximum in (h, w) scan order; ss, us: side and u of that element
             int arg = 0;
-            float best = av[0][i];
+            auto best = key(0);
+            float ss = side[0], us = u[0][i];
 #pragma unroll
             for (int k = 1; k < 4; ++k) {
-                const bool gt = av[k][i] > best;
-                best = gt ? av[k][i] : best, arg = gt ? k : arg;
+                const auto av = key(k);
+                const bool gt = av > best;
+                best = gt ? av : best, arg = gt ? k : arg, ss = gt ? side[k] : ss, us = gt ? u[k][i] : us;
             }
             if (G2) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float ga = (k == arg ? gv[i] : 0.f) + g2v[G2 ? k : 0][i];
-                    const float gzk = av[k][i] > 0.f ? ga : ga * a.slope;
+                    const float ga = (k == arg ? gv[i] : 0.f) + g2v[k][i];
+                    const float gzk = side[k] > 0.f ? ga : ga * a.slope;
                     if (PHASE == 0) {
                         sb[i] += gzk;
-                        sg[i] += gzk * ((z[k][i] - off[i]) * mul[i]);
+                        sg[i] += gzk * ((u[k][i] - ch.off[i]) * ch.mul[i]);
                     } else {
-                        const float o = dm[i] * gzk - (P[i] * z[k][i] + Q[i]);
+                        const float o = ch.dm[i] * gzk - (ch.P[i] * u[k][i] + ch.Q[i]);
                         out[k][i] = o;
                         satmax = fmaxf(satmax, fabsf(o));
                     }
                 }
             } else {
-                const float gz = best > 0.f ? gv[i] : gv[i] * a.slope;
+                const float gz = ss > 0.f ? gv[i] : gv[i] * a.slope;
                 if (PHASE == 0) {
-                    float zs = z[0][i];
-#pragma unroll
-                    for (int k = 1; k < 4; ++k) zs = k == arg ? z[k][i] : zs;
                     sb[i] += gz;
-                    sg[i] += gz * ((zs - off[i]) * mul[i]);
+                    sg[i] += gz * ((us - ch.off[i]) * ch.mul[i]);
                 } else {
-                    const float t = dm[i] * gz;
+                    const float t = ch.dm[i] * gz;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const float o = (k == arg ? t : 0.f) - (P[i] * z[k][i] + Q[i]);
+                        const float o = (k == arg ? t : 0.f) - (ch.P[i] * u[k][i] + ch.Q[i]);
                         out[k][i] = o;
                         satmax = fmaxf(satmax, fabsf(o));
                     }
                 }
             }
         }
-        if (PHASE == 1) {
-            half_t* d0 = a.dy + pad_off(b, 2 * ho, 2 * wo, a.H, a.W, a.dy_ld, a.dy_pw) + a.dy_choff + c8;
-            const long long drow = (long long)(a.W + a.dy_pw) * a.dy_ld;
-            store8(d0, out[0]);
-            store8(d0 + a.dy_ld, out[1]);
-            store8(d0 + drow, out[2]);
-            store8(d0 + drow + a.dy_ld, out[3]);
-        }
-        wo += swo;
-        if (wo >= Wo) wo -= Wo, ++ho;
-        ho += sho;
-        if (ho >= Ho) ho -= Ho, ++b;
-        b += sb_;
+        if (PHASE == 1) store_win(a.dy + pad_off(p.b, 2 * p.h, 2 * p.w, a.H, a.W, a.dy_ld, a.dy_pw) + a.dy_choff + c8, a.dy_ld, drow, out);
     }
-    if (PHASE == 1 && satmax > 65504.f && a.overflow) atomicOr(a.overflow, 1);
-    if (PHASE == 0) {
-        block_partials_to_slab(sb, sg, CH, a.slab, a.C);
-    }
+    bn_bwd_finish<PHASE>(a, sb, sg, satmax > 65504.f, CH);
 }
 
 // Pass 0 of a MaxPool block without a second gradient, from the POOLED tensors (mcamd_act_bwd_desc.pool_out).  Only the
 // pooled element of a window has a g_z, so the two sums need that element's activation and nothing of the other three.
 // bn_act_fwd_kernel writes it twice: as the pooled output, sat_half(max of the four unrounded activations), and into the
-// full-resolution copy as the window's strict maximum, sat_half of the same value.  max(av[0..3]) of
-// bn_pool_bwd_act_kernel<0, false> is therefore the pooled value bit for bit (tests/test_bn_pool_sums_gpu.py pins it), and
-// this pass reads pooled G + pooled activation, 4 bytes per window and channel, where that one reads 10.  The terms are
-// the same fp32 values and a thread adds them in the same order (its windows pix, pix + stride, ...; two per loop trip,
-// four 16-byte loads in flight), so at the same grid the slab is bit-equal to that pass's.  conv2 / 5 / 8 at B = 64:
-// 61 -> 22 us per launch, FETCH_SIZE 2.5 : 1.
+// full-resolution copy as the window's strict maximum, sat_half of the same value.  The maximum of the four stored values
+// in bn_pool_bwd_kernel<0, BN_SRC_ACT, false> is therefore the pooled value bit for bit (tests/test_bn_pool_sums_gpu.py
+// pins it), and this pass reads pooled G + pooled activation, 4 bytes per window and channel, where that one reads 10.
+// The terms are the same fp32 values and a thread adds them in the same order (its windows pix, pix + stride, ...; two per
+// loop trip, four 16-byte loads in flight), so at the same grid the slab is bit-equal to that pass's.  conv2 / 5 / 8 at
+// B = 64: 61 -> 22 us per launch, FETCH_SIZE 2.5 : 1.
 // Threads that hold an ill-conditioned channel (act_xhat_source) need z from the saved fp32 y AT THE ARGMAX, which the
 // pooled tensor does not locate: they load the window of the copy and of y as the other kernel does, one window per
 // trip.  A healthy network has no such thread.
 // ACT == false: an engine without the copy (filter compaction) -- pass 0 read the four fp32 y values of a window, 18 bytes
-// with G.  The pooled activation gives xhat = (z - beta) / gamma at fp16 accuracy, the trade bn_plain_bwd_act_kernel made;
-// the ill-conditioned channels take the argmax from the unrounded activations of y, as bn_pool_bwd_kernel<., true, .>.
-struct PoolPos {
-    unsigned pix;
-    int b, ho, wo;
-};
-__device__ __forceinline__ PoolPos pool_pos(unsigned pix, int HoWo, int Wo) {
-    PoolPos p;
-    p.pix = pix;
-    p.b = (int)(pix / (unsigned)HoWo);
-    const int rem = (int)(pix - (unsigned)p.b * (unsigned)HoWo);
-    p.ho = rem / Wo, p.wo = rem - p.ho * Wo;
-    return p;
-}
-// p += s (s.pix pixels, decomposed once), without a division
-__device__ __forceinline__ void pool_pos_step(PoolPos& p, const PoolPos& s, int Ho, int Wo) {
-    p.pix += s.pix;
-    p.wo += s.wo;
-    if (p.wo >= Wo) p.wo -= Wo, ++p.ho;
-    p.ho += s.ho;
-    if (p.ho >= Ho) p.ho -= Ho, ++p.b;
-    p.b += s.b;
-}
+// with G.  The pooled activation gives xhat = (z - beta) / gamma at fp16 accuracy, the trade the PLAIN blocks' activation
+// source made; the ill-conditioned channels take the argmax from the unrounded activations of y, as
+// bn_pool_bwd_kernel<., BN_SRC_Y32, .>.
+
 // z of the argmax element from the saved y, for the ill-conditioned channels of one window (one image row of the window at
 // a time: 32 values in flight)
 template <bool ACT>
-__device__ __forceinline__ void pool_sums_z_from_y(const ActBwdArgs& a, const PoolPos& p, int c8, const bool (&usey)[8],
+__device__ __forceinline__ void pool_sums_z_from_y(const ActBwdArgs& a, const PixPos& p, int c8, const bool (&usey)[8],
                                                    const float (&sc)[8], const float (&sh)[8], float (&z)[8]) {
-    const half_t* ap = ACT ? a.act + pad_off(p.b, 2 * p.ho, 2 * p.wo, a.H, a.W, a.act_ld, a.act_pw) + a.act_choff + c8 : nullptr;
+    const half_t* ap = ACT ? a.act + pad_off(p.b, 2 * p.h, 2 * p.w, a.H, a.W, a.act_ld, a.act_pw) + a.act_choff + c8 : nullptr;
     const long long arow = (long long)(a.W + a.act_pw) * a.act_ld;
-    const float* yf = (const float*)a.y + (((long long)p.b * a.H + 2 * p.ho) * a.W + 2 * p.wo) * a.y_ld + a.y_choff + c8;
+    const float* yf = (const float*)a.y + (((long long)p.b * a.H + 2 * p.h) * a.W + 2 * p.w) * a.y_ld + a.y_choff + c8;
     const long long yrow = (long long)a.W * a.y_ld;
     float best[8], ys[8];
 #pragma unroll 1
@@ -1036,7 +813,7 @@ __device__ __forceinline__ void pool_sums_z_from_y(const ActBwdArgs& a, const Po
         if (ACT) {
             load8(ap + r * arow, av[0]);
             load8(ap + r * arow + a.act_ld, av[1]);
-        } else {                                         // no copy: the unrounded activations, as bn_pool_bwd_kernel<., true, .>
+        } else {                                         // no copy: the unrounded activations, as the BN_SRC_Y32 source
 #pragma unroll
             for (int k = 0; k < 2; ++k)
 #pragma unroll
@@ -1063,21 +840,16 @@ template <bool ACT>
 __global__ __launch_bounds__(256) void bn_pool_sums_kernel(ActBwdArgs a) {
     const int CH = a.C >> 3, lg = __ffs(CH) - 1;        // C / 8 is a power of two (check_c)
     const int c8 = (threadIdx.x & (CH - 1)) * 8;
-    float sc[8], sh[8], mu[8], is[8], off[8], mul[8];
-    bool usey[8];
-    loadf8(a.scale + c8, sc);
-    loadf8(a.shift + c8, sh);
-    loadf8(a.mean + c8, mu);
-    loadf8(a.invstd + c8, is);
-    const bool need_y = act_xhat_source(sc, sh, mu, is, a.y != nullptr, off, mul, usey);
+    BnBwdChan ch;
+    bn_bwd_chan<0, true>(a, c8, ch);                     // xhat from the pooled activation, with or without the copy
     float sb[8], sg[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) sb[i] = sg[i] = 0.f;
     const float inv_slope = 1.0f / a.slope;
-    const int Ho = a.H >> 1, Wo = a.W >> 1, HoWo = Ho * Wo;
+    const int Ho = a.H >> 1, Wo = a.W >> 1;
     const unsigned npix = (unsigned)(a.items >> lg);                       // pooled pixels
     const unsigned stride = (gridDim.x * 256u) >> lg;                      // pooled pixels per grid stride
-    PoolPos p0 = pool_pos((blockIdx.x * 256u + threadIdx.x) >> lg, HoWo, Wo);
+    PixPos p0 = pix_pos((blockIdx.x * 256u + threadIdx.x) >> lg, Ho, Wo);
     const half_t* pout = a.pool_out + a.pool_out_choff + c8;
     const half_t* gp = a.g + a.g_choff + c8;
     auto add = [&](const float (&z)[8], const float (&pv)[8], const float (&gv)[8]) {
@@ -1085,30 +857,30 @@ __global__ __launch_bounds__(256) void bn_pool_sums_kernel(ActBwdArgs a) {
         for (int i = 0; i < 8; ++i) {
             const float gz = pv[i] > 0.f ? gv[i] : gv[i] * a.slope;
             sb[i] += gz;
-            sg[i] += gz * ((z[i] - off[i]) * mul[i]);
+            sg[i] += gz * ((z[i] - ch.off[i]) * ch.mul[i]);
         }
     };
-    auto window = [&](const PoolPos& p, float (&pv)[8], float (&gv)[8]) {
-        load8(pout + pad_off(p.b, p.ho, p.wo, Ho, Wo, a.pool_out_ld, a.pool_out_pw), pv);
+    auto window = [&](const PixPos& p, float (&pv)[8], float (&gv)[8]) {
+        load8(pout + pad_off(p.b, p.h, p.w, Ho, Wo, a.pool_out_ld, a.pool_out_pw), pv);
         load8(gp + (long long)p.pix * a.g_ld, gv);
     };
     auto z_of = [&](const float (&pv)[8], float (&z)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) z[i] = pv[i] > 0.f ? pv[i] : pv[i] * inv_slope;
     };
-    if (need_y) {                                        // a thread with an ill-conditioned channel: one window per trip
-        const PoolPos step = pool_pos(stride, HoWo, Wo);
-        for (; p0.pix < npix; pool_pos_step(p0, step, Ho, Wo)) {
+    if (ch.need_y) {                                     // a thread with an ill-conditioned channel: one window per trip
+        const PixPos step = pix_pos(stride, Ho, Wo);
+        for (; p0.pix < npix; pix_pos_step(p0, step, Ho, Wo)) {
             float pv[8], gv[8], z[8];
             window(p0, pv, gv);
             z_of(pv, z);
-            pool_sums_z_from_y<ACT>(a, p0, c8, usey, sc, sh, z);
+            pool_sums_z_from_y<ACT>(a, p0, c8, ch.usey, ch.sc, ch.sh, z);
             add(z, pv, gv);
         }
     } else {
-        const PoolPos step2 = pool_pos(2u * stride, HoWo, Wo);
-        PoolPos p1 = pool_pos(p0.pix + stride, HoWo, Wo);
-        for (; p1.pix < npix; pool_pos_step(p0, step2, Ho, Wo), pool_pos_step(p1, step2, Ho, Wo)) {
+        const PixPos step2 = pix_pos(2u * stride, Ho, Wo);
+        PixPos p1 = pix_pos(p0.pix + stride, Ho, Wo);
+        for (; p1.pix < npix; pix_pos_step(p0, step2, Ho, Wo), pix_pos_step(p1, step2, Ho, Wo)) {
             float pv0[8], gv0[8], pv1[8], gv1[8], z[8];
             window(p0, pv0, gv0);
             window(p1, pv1, gv1);
@@ -1124,7 +896,7 @@ __global__ __launch_bounds__(256) void bn_pool_sums_kernel(ActBwdArgs a) {
             add(z, pv, gv);
         }
     }
-    block_partials_to_slab(sb, sg, CH, a.slab, a.C);
+    bn_bwd_finish<0>(a, sb, sg, false, CH);
 }
 
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* slab, int nblocks, int ld, int C, double count,
@@ -1357,6 +1129,34 @@ extern "C" size_t mcamd_bn_act_bwd_workspace_bytes(const mcamd_act_bwd_desc* d) 
     return ((size_t)kBwdBlocks * 2 * d->C + 2 * (size_t)d->C) * sizeof(float);
 }
 
+// Which kernel runs pass 0 (the sums) and pass 1 (dY) of a backward call: the ONE place that decides.  pool_fast /
+// plain_fast: the specialised kernels apply (the mode, no second gradient for PLAIN, 32-bit positions, the environment
+// switches); otherwise the generic kernel of the mode, nullptr for a mode that does not exist.  pool_out: pass 0 of a
+// MaxPool block from the pooled tensors.
+typedef void (*BwdKernel)(ActBwdArgs);
+struct BwdRoute {
+    BwdKernel pass0, pass1;
+};
+static BwdRoute bwd_route(int mode, bool y32, bool act, bool g2, bool pool_out, bool pool_fast, bool plain_fast) {
+    auto pass = [&](auto phase) -> BwdKernel {
+        constexpr int PH = decltype(phase)::value;
+        if (pool_fast) {
+            if (act) return g2 ? bn_pool_bwd_kernel<PH, BN_SRC_ACT, true> : bn_pool_bwd_kernel<PH, BN_SRC_ACT, false>;
+            if (y32) return g2 ? bn_pool_bwd_kernel<PH, BN_SRC_Y32, true> : bn_pool_bwd_kernel<PH, BN_SRC_Y32, false>;
+            return g2 ? bn_pool_bwd_kernel<PH, BN_SRC_Y16, true> : bn_pool_bwd_kernel<PH, BN_SRC_Y16, false>;
+        }
+        if (plain_fast)
+            return act ? bn_plain_bwd_kernel<PH, BN_SRC_ACT> : y32 ? bn_plain_bwd_kernel<PH, BN_SRC_Y32> : bn_plain_bwd_kernel<PH, BN_SRC_Y16>;
+        if (mode == MCAMD_DST_PLAIN) return y32 ? bn_act_bwd_kernel<MCAMD_DST_PLAIN, PH, true> : bn_act_bwd_kernel<MCAMD_DST_PLAIN, PH, false>;
+        if (mode == MCAMD_DST_POOL) return y32 ? bn_act_bwd_kernel<MCAMD_DST_POOL, PH, true> : bn_act_bwd_kernel<MCAMD_DST_POOL, PH, false>;
+        if (mode == MCAMD_DST_REORG) return y32 ? bn_act_bwd_kernel<MCAMD_DST_REORG, PH, true> : bn_act_bwd_kernel<MCAMD_DST_REORG, PH, false>;
+        return nullptr;
+    };
+    BwdRoute r = {pass(std::integral_constant<int, 0>()), pass(std::integral_constant<int, 1>())};
+    if (pool_fast && pool_out) r.pass0 = act ? bn_pool_sums_kernel<true> : bn_pool_sums_kernel<false>;
+    return r;
+}
+
 extern "C" int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
     if (mcamd_recording()) {
         MCAMD_REQUIRE(d, "bn_act_bwd: null descriptor");
@@ -1431,46 +1231,16 @@ extern "C" int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, si
     if (grid > kBwdBlocks) grid = kBwdBlocks;
     if (max_blocks >= 1 && grid > max_blocks) grid = max_blocks;
     hipStream_t st = (hipStream_t)stream;
-#define BWD_INST(MODE_, PHASE)                                                                                     \
-    do {                                                                                                          \
-        if (y32) hipLaunchKernelGGL((bn_act_bwd_kernel<MODE_, PHASE, true>), dim3(grid), dim3(256), 0, st, a);    \
-        else hipLaunchKernelGGL((bn_act_bwd_kernel<MODE_, PHASE, false>), dim3(grid), dim3(256), 0, st, a);       \
-    } while (0)
-#define BWD_LAUNCH(PHASE)                                                                                         \
-    if (d->mode == MCAMD_DST_PLAIN)                                                                               \
-        BWD_INST(MCAMD_DST_PLAIN, PHASE);                                                                         \
-    else if (d->mode == MCAMD_DST_POOL)                                                                           \
-        BWD_INST(MCAMD_DST_POOL, PHASE);                                                                          \
-    else if (d->mode == MCAMD_DST_REORG)                                                                          \
-        BWD_INST(MCAMD_DST_REORG, PHASE);                                                                         \
-    else                                                                                                          \
-        MCAMD_REQUIRE(false, "bn_act_bwd: bad mode %d", d->mode);
     // MaxPool blocks: the argmax form (bn_pool_bwd_kernel); MCAMD_BN_POOL_FAST=0: generic kernel
     const bool pool_fast_on = MCAMD_ENV_INT("MCAMD_BN_POOL_FAST", 1) != 0;
     const bool pool_fast = pool_fast_on && d->mode == MCAMD_DST_POOL && a.items < (1ll << 31) &&
                            (unsigned long long)grid * 256ull < (1ull << 31);
-#define POOL_INST(PHASE, Y32_, G2_) hipLaunchKernelGGL((bn_pool_bwd_kernel<PHASE, Y32_, G2_>), dim3(grid), dim3(256), 0, st, a)
-#define POOL_LAUNCH(PHASE)                                                                                        \
-    do {                                                                                                          \
-        if (a.act && d->g2) hipLaunchKernelGGL((bn_pool_bwd_act_kernel<PHASE, true>), dim3(grid), dim3(256), 0, st, a);   \
-        else if (a.act) hipLaunchKernelGGL((bn_pool_bwd_act_kernel<PHASE, false>), dim3(grid), dim3(256), 0, st, a);      \
-        else if (y32 && d->g2) POOL_INST(PHASE, true, true);                                                      \
-        else if (y32) POOL_INST(PHASE, true, false);                                                              \
-        else if (d->g2) POOL_INST(PHASE, false, true);                                                            \
-        else POOL_INST(PHASE, false, false);                                                                      \
-    } while (0)
     // PLAIN blocks without a second gradient: bn_plain_bwd_kernel (MCAMD_BN_PLAIN_FAST=0: generic kernel)
     const bool plain_fast = MCAMD_ENV_INT("MCAMD_BN_PLAIN_FAST", 1) != 0 &&
                             d->mode == MCAMD_DST_PLAIN && !d->g2 && a.items < (1ll << 31) &&
                             (unsigned long long)grid * 256ull < (1ull << 31);
     MCAMD_REQUIRE(!d->act || plain_fast || pool_fast, "bn_act_bwd: `act` needs the plain / pool fast path (fewer than 2^31 items, "
                                                       "MCAMD_BN_POOL_FAST / MCAMD_BN_PLAIN_FAST not 0)");
-#define PLAIN_LAUNCH(PHASE)                                                                                       \
-    do {                                                                                                          \
-        if (a.act) hipLaunchKernelGGL((bn_plain_bwd_act_kernel<PHASE>), dim3(grid), dim3(256), 0, st, a);         \
-        else if (y32) hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE, true>), dim3(grid), dim3(256), 0, st, a);    \
-        else hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE, false>), dim3(grid), dim3(256), 0, st, a);            \
-    } while (0)
     // sums already taken (mcamd_act_bwd_desc.sums: the dgrad launch that wrote G formed them, mcamd_conv_dgrad_sums): no pass 0
     const float* fin_slab = (const float*)a.slab;
     int fin_rows = grid, fin_ld = d->C;
@@ -1480,30 +1250,16 @@ extern "C" int mcamd_bn_act_bwd(const mcamd_act_bwd_desc* d, void* workspace, si
                       d->sums_rows, d->sums_ld);
         fin_slab = d->sums, fin_rows = d->sums_rows, fin_ld = d->sums_ld;
     }
-    if (d->sums) {   // pass 0 ran in that dgrad's epilogue
-    } else if (pool_fast && a.pool_out && a.act) hipLaunchKernelGGL(bn_pool_sums_kernel<true>, dim3(grid), dim3(256), 0, st, a);
-    else if (pool_fast && a.pool_out) hipLaunchKernelGGL(bn_pool_sums_kernel<false>, dim3(grid), dim3(256), 0, st, a);
-    else if (pool_fast) POOL_LAUNCH(0);
-    else if (plain_fast) PLAIN_LAUNCH(0);
-    else {
-        BWD_LAUNCH(0)
-    }
+    const BwdRoute route = bwd_route(d->mode, y32, a.act != nullptr, d->g2 != nullptr, a.pool_out != nullptr, pool_fast, plain_fast);
+    MCAMD_REQUIRE(route.pass0 && route.pass1, "bn_act_bwd: bad mode %d", d->mode);
+    if (!d->sums) hipLaunchKernelGGL(route.pass0, dim3(grid), dim3(256), 0, st, a);   // (`sums`: pass 0 ran in that dgrad's epilogue)
     MCAMD_LAUNCH_CHECK("bn_act_bwd reduce");
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((d->C + RED_CPB - 1) / RED_CPB), dim3(1024), 0, st, fin_slab, fin_rows, fin_ld, d->C,
                        count, 1.0f / d->grad_scale, d->dgamma, d->dbeta, coef, (const int*)d->chan_perm,
                        d->skip_dead_param_grads);
     MCAMD_LAUNCH_CHECK("bn_act_bwd finalize");
-    if (pool_fast) POOL_LAUNCH(1);
-    else if (plain_fast) PLAIN_LAUNCH(1);
-    else {
-        BWD_LAUNCH(1)
-    }
+    hipLaunchKernelGGL(route.pass1, dim3(grid), dim3(256), 0, st, a);
     MCAMD_LAUNCH_CHECK("bn_act_bwd apply");
-#undef POOL_LAUNCH
-#undef PLAIN_LAUNCH
-#undef POOL_INST
-#undef BWD_LAUNCH
-#undef BWD_INST
     return MCAMD_OK;
 }
 

@@ -270,7 +270,7 @@ __device__ __forceinline__ void split_hi_lo(const float* v, h8_t& hi, h8_t& lo) 
 // ---------------------------------------------------------------------------------------
 // store_raw_tile for a dgrad launch whose output is the gradient G of a PLAIN BatchNorm + LeakyReLU block (a.bsum,
 // MCAMD_EPI_RAW_F16_SUMS instances): while the tile goes out, pass 0 of that block's BatchNorm backward
-// (bn_plain_bwd_act_kernel<0>, bn_act.hip) is taken on it -- per producer channel sum g_z and sum g_z xhat, from G AS
+// (bn_plain_bwd_kernel<0, BN_SRC_ACT>, bn_act.hip) is taken on it -- per producer channel sum g_z and sum g_z xhat, from G AS
 // STORED (fp16, saturated: what pass 1 reads) and the 16 bytes of the producer's stored activation at the same pixel and
 // channels.  Same element formulas, same ill-conditioned-channel rule (act_xhat_source: only threads that hold such a
 // channel read the saved fp32 y).  Rows >= M and columns outside [ch_lo, ch_lo + C) contribute nothing.

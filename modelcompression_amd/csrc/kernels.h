@@ -3,7 +3,7 @@
 #include "common.h"
 
 // BatchNorm-backward sums of the PLAIN block whose output gradient G a dgrad launch stores (mcamd_dgrad_sums, mcamd.h;
-// conv_epi.h store_raw_tile_sums): pass 0 of bn_plain_bwd_act_kernel taken on the fp16 tile on its way out.
+// conv_epi.h store_raw_tile_sums): pass 0 of bn_plain_bwd_kernel<., BN_SRC_ACT> taken on the fp16 tile on its way out.
 struct DgradSums {
     float* slab;             // [num_pslots][2][ld]: sum g_z, sum g_z xhat per producer channel; NULL = none
     const half_t* act;       // the producer's stored activation (padded NHWC / shared-halo form per act_pw)

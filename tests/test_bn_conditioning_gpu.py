@@ -97,19 +97,19 @@ def _decisions(y32, scale, shift, slope, B, H, W, mode, y16):
 
 # (name, mode, y dtype, act storage form (None: y kernel; 0 padded, 1 shared-halo), g2, environment, slope)
 VARIANTS = [
-    ("plain-y16", L.DST_PLAIN, 16, None, False, {}, 0.1),              # bn_plain_bwd_kernel<., false>
-    ("plain-y32", L.DST_PLAIN, 32, None, False, {}, 1.0),              # bn_plain_bwd_kernel<., true>
-    ("plain-act", L.DST_PLAIN, 32, 0, False, {}, 0.1),                 # bn_plain_bwd_act_kernel
+    ("plain-y16", L.DST_PLAIN, 16, None, False, {}, 0.1),              # bn_plain_bwd_kernel<., BN_SRC_Y16>
+    ("plain-y32", L.DST_PLAIN, 32, None, False, {}, 1.0),              # bn_plain_bwd_kernel<., BN_SRC_Y32>
+    ("plain-act", L.DST_PLAIN, 32, 0, False, {}, 0.1),                 # bn_plain_bwd_kernel<., BN_SRC_ACT>
     ("plain-act-halo", L.DST_PLAIN, 32, 1, False, {}, 1.0),
     ("plain-generic-y16", L.DST_PLAIN, 16, None, False, {"MCAMD_BN_PLAIN_FAST": "0"}, 0.1),   # bn_act_bwd_kernel
     ("plain-generic-y32", L.DST_PLAIN, 32, None, False, {"MCAMD_BN_PLAIN_FAST": "0"}, 0.1),
     ("plain-g2-y16", L.DST_PLAIN, 16, None, True, {}, 0.1),            # PLAIN with g2: the generic kernel
     ("plain-g2-y32", L.DST_PLAIN, 32, None, True, {}, 0.1),
-    ("pool-y16", L.DST_POOL, 16, None, False, {}, 0.1),                # bn_pool_bwd_kernel<., Y32, G2>
+    ("pool-y16", L.DST_POOL, 16, None, False, {}, 0.1),                # bn_pool_bwd_kernel<., SRC, G2>
     ("pool-y16-g2", L.DST_POOL, 16, None, True, {}, 0.1),
     ("pool-y32", L.DST_POOL, 32, None, False, {}, 1.0),
     ("pool-y32-g2", L.DST_POOL, 32, None, True, {}, 0.1),
-    ("pool-act", L.DST_POOL, 32, 0, False, {}, 0.1),                   # bn_pool_bwd_act_kernel<., G2>
+    ("pool-act", L.DST_POOL, 32, 0, False, {}, 0.1),                   # bn_pool_bwd_kernel<., BN_SRC_ACT, G2>
     ("pool-act-g2-halo", L.DST_POOL, 32, 1, True, {}, 0.1),
     ("pool-generic-y16", L.DST_POOL, 16, None, False, {"MCAMD_BN_POOL_FAST": "0"}, 0.1),
     ("pool-generic-y32-g2", L.DST_POOL, 32, None, True, {"MCAMD_BN_POOL_FAST": "0"}, 0.1),

@@ -17,7 +17,7 @@ conv5 / conv8 (the MaxPool blocks with one consumer), B reduced and one at B = 6
 5. two runs are bit-equal.
 
 Every case also runs WITHOUT the full-resolution copy (engines with filter compaction switch it off): the present pass 0
-is then bn_pool_bwd_kernel<0, true, false> on the saved fp32 y, the pooled route bn_pool_sums_kernel<false>, whose
+is then bn_pool_bwd_kernel<0, BN_SRC_Y32, false> on the saved fp32 y, the pooled route bn_pool_sums_kernel<false>, whose
 ill-conditioned channels take the argmax from the unrounded activations of y.  There the two routes differ by the fp16
 rounding of the pooled activation (the trade the PLAIN blocks made), not by summation order: check 2 does not apply and
 its figures are only printed; the premise is checked against the unrounded activations, and 3 - 5 hold with the y
@@ -46,7 +46,7 @@ CASES = [
     ("conv8-b8", 256, 8, 52, 52, 0, 248),
     ("conv8-b64", 256, 64, 52, 52, 1, 0),
 ]
-# Summation-order noise of the PRESENT pass 0 (bn_pool_bwd_act_kernel<0, false>): 1024 against 384 workgroups on the inputs
+# Summation-order noise of the PRESENT pass 0 (bn_pool_bwd_kernel<0, BN_SRC_ACT, false>): 1024 against 384 workgroups on the inputs
 # of each case with the copy, as measured on an MI355X (the test prints the figures of its own run beside them):
 #   dgamma: max over channels of |difference| / sum|g_z xhat|,  dbeta: of |difference| / sum|g_z|,  dY: rel-L2.
 # The new route may differ from the present one by 4x these.  (Measured difference: 0 in all three, at every case -- at the
@@ -196,7 +196,7 @@ def test_pool_sums_from_pooled_tensors(dev, setenv, case, copy):
     new2 = run(True)
     old = run(False)
     old_b = run(False, BLOCKS_B)
-    ykern = run(False, with_act=False)                               # bn_pool_bwd_kernel<., true, false>: the fp32-y kernel
+    ykern = run(False, with_act=False)                               # bn_pool_bwd_kernel<., BN_SRC_Y32, false>: the fp32-y kernel
 
     written = torch.ones(C, dtype=torch.bool)
     if skip_from:

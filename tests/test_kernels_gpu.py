@@ -971,7 +971,7 @@ def test_bn_pool_bwd_fast_equals_generic(dev, setenv, C, y_ld, keep_n, mode, dua
 
 @pytest.mark.parametrize("C,B,H,W,pad,slope", [(64, 3, 20, 12, 0, 0.1), (512, 5, 13, 13, 1, 0.1), (128, 2, 26, 26, 1, 1.0)])
 def test_bn_plain_bwd_from_stored_activation(dev, C, B, H, W, pad, slope):
-    """mcamd_act_bwd_desc.act (bn_plain_bwd_act_kernel): the BatchNorm + LeakyReLU backward of a PLAIN block from the
+    """mcamd_act_bwd_desc.act (bn_plain_bwd_kernel<., BN_SRC_ACT>): the BatchNorm + LeakyReLU backward of a PLAIN block from the
     fp16 activation the forward pass stored (hi plane of split storage, padded or shared-halo buffer, a channel slice of a
     wider buffer) instead of the saved fp32 raw output: z = act > 0 ? act : act / slope, xhat = (z - beta) / gamma.
     Against the fp32-y kernel on the same inputs (dY within 2e-3 -- the fp16 rounding of the activation -- dgamma / dbeta
@@ -1030,7 +1030,7 @@ def test_bn_plain_bwd_from_stored_activation(dev, C, B, H, W, pad, slope):
 
 @pytest.mark.parametrize("C,B,H,W,pad,dual", [(64, 3, 20, 12, 0, False), (128, 2, 26, 26, 1, True), (32, 2, 8, 8, 1, False)])
 def test_bn_pool_bwd_from_stored_activation(dev, C, B, H, W, pad, dual):
-    """mcamd_act_desc.pool_act + mcamd_act_bwd_desc.act in mode POOL (bn_pool_bwd_act_kernel): the BatchNorm + LeakyReLU +
+    """mcamd_act_desc.pool_act + mcamd_act_bwd_desc.act in mode POOL (bn_pool_bwd_kernel<., BN_SRC_ACT, .>): the BatchNorm + LeakyReLU +
     MaxPool(2,2) backward of a block from a full-resolution fp16 copy of its activation instead of the saved fp32 raw
     output.  The forward pass stores the copy so that the element it pooled -- the first maximum of the UNROUNDED
     activations -- is the window's strict maximum (a neighbour that rounds to the same fp16 value goes one step lower):
