@@ -275,6 +275,39 @@ int mcamd_conv_fwd_bsparse(const mcamd_conv_geom* g, const void* x, const void* 
 int mcamd_conv_fwd_bsparse_info(const mcamd_conv_geom* g, int32_t out[7]);
 
 /* ------------------------------------------------------------------------- *
+ * The training form of the block-sparse kernel (Darknet.sparse_train = "block"): the same K loop over the
+ * listed chunks with the raw fp16 epilogue (MCAMD_EPI_RAW_F16), for the forward GEMM and for the dgrad GEMM.  The dgrad
+ * packing of mcamd_pack_weights is [Cpad][k*k * cout_p] with the forward's K order [channel block][tap][kb] over cout_p
+ * (kb_d = 64 when cout_p % 64 == 0, else 32), so a K chunk of a 64-row N tile (64 input channels) is one (cout block,
+ * flipped tap) pair: when cout_p % 64 == 0, exactly one block of block_prune's masks, seen from the other side.  The
+ * lists are read from the packed values, so any mask is correct.  `dgrad` below: 0 the forward launch, 1 the dgrad launch.
+ * ------------------------------------------------------------------------- */
+/* 1: the launch of that direction accepts the geometry.  Forward: as mcamd_conv_fwd_bsparse_ok.  dgrad: stem == 0, x_wrap ==
+ * 0, x_f8 == 0, ksize 1 or 3, cin % 8 == 0 (the launch also wants the slice of dy inside dy_ld).  Host logic only. */
+int32_t mcamd_conv_bsparse_train_ok(const mcamd_conv_geom* g, int32_t dgrad);
+/* The instance the launch of that direction takes, from its own choice (host logic only): out as
+ * mcamd_conv_fwd_bsparse_info's {bm, bn, bk, stages, mtiles, ntiles, grid}; dgrad: ntiles over cin, bk = kb_d. */
+int mcamd_conv_bsparse_train_info(const mcamd_conv_geom* g, int32_t dgrad, int32_t out[7]);
+/* Rows of the statistics slab of mcamd_conv_fwd_bsparse_raw: one per pixel tile (= mtiles; the grid is not persistent).
+ * 0: the geometry is refused. */
+int32_t mcamd_conv_bsparse_raw_stats_rows(const mcamd_conv_geom* g, int32_t dgrad);
+/* mcamd_bsparse_elems / mcamd_bsparse_lists on the dgrad packing: ntiles = ceil(cin / 64), nchunks = k*k * cout_p / kb_d. */
+int mcamd_bsparse_elems_dgrad(const mcamd_conv_geom* g, int64_t out[2]);
+int mcamd_bsparse_lists_dgrad(const mcamd_conv_geom* g, const void* wp_dgrad, int32_t* count, int32_t* list, void* stream);
+/* y[M][y_ld] (at y_choff) = conv(x, w) over the listed chunks, fp16 saturated at +-65504 (never inf; epi->overflow is set
+ * where a value was clamped).  epi->mode must be MCAMD_EPI_RAW_F16 (else MCAMD_EINVAL); both `pad` forms of x.  With
+ * epi->stats: per channel the sum and the sum of squares of the values AS STORED (mcamd_conv_fwd's convention for this
+ * mode), one slab row [2][stats_ld] per pixel tile, stats_rows = mcamd_conv_bsparse_raw_stats_rows(g, 0).  A tile whose
+ * count is 0 stores zeros and zero sums; foreign counts and indices are clamped as in mcamd_conv_fwd_bsparse. */
+int mcamd_conv_fwd_bsparse_raw(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const int32_t* count,
+                               const int32_t* list, const mcamd_conv_epilogue* epi, void* stream);
+/* gin[M][y_ld] (at y_choff) = mcamd_conv_dgrad's result over the listed chunks of mcamd_bsparse_lists_dgrad: the same
+ * operands and geometry set-up; MCAMD_EPI_RAW_F16 without statistics only, with the overflow flag.  epi->concurrent is
+ * accepted and ignored (one tile shape). */
+int mcamd_conv_dgrad_bsparse(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff, const void* wp_dgrad,
+                             const int32_t* count, const int32_t* list, const mcamd_conv_epilogue* epi, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Split-K forward for low-batch fp16 inference (an addition beyond the reference; conv_splitk.hip, Darknet.splitk).
  * A layer of few output pixels gives mcamd_conv_fwd a handful of workgroups that each walk the whole K axis; here
  * workgroup (tile, slice s) of a first launch multiplies the K chunks [floor(s n / S), floor((s + 1) n / S)) of the

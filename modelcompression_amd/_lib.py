@@ -239,6 +239,13 @@ SIGNATURES = {
     "mcamd_bsparse_lists": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P]),
     "mcamd_conv_fwd_bsparse": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_fwd_bsparse_info": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I32)]),
+    "mcamd_conv_bsparse_train_ok": (_I32, [C.POINTER(ConvGeom), _I32]),
+    "mcamd_conv_bsparse_train_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I32)]),
+    "mcamd_conv_bsparse_raw_stats_rows": (_I32, [C.POINTER(ConvGeom), _I32]),
+    "mcamd_bsparse_elems_dgrad": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
+    "mcamd_bsparse_lists_dgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P]),
+    "mcamd_conv_fwd_bsparse_raw": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
+    "mcamd_conv_dgrad_bsparse": (C.c_int, [C.POINTER(ConvGeom), _P, _I32, _I32, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_fwd_splitk_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, _I32, C.POINTER(SplitkInfo)]),
     "mcamd_conv_fwd_splitk": (C.c_int, [C.POINTER(ConvGeom), _P, _P, C.POINTER(ConvEpilogue), _I32, _P, _SZ, _P]),
     "mcamd_conv_fwd_q8_ok": (_I32, [C.POINTER(ConvGeom)]),

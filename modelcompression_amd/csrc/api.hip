@@ -793,6 +793,99 @@ extern "C" int mcamd_conv_fwd_bsparse_info(const mcamd_conv_geom* g, int32_t out
     return MCAMD_OK;
 }
 
+// ... and its training form (Darknet.sparse_train = "block"): the raw fp16 epilogue, for the forward GEMM and
+// for the dgrad GEMM -- N = cin, K = k*k * cout_p over the dgrad packing [Cpad][kpos(t, n)], whose K order is the forward's
+// [channel block][tap][kb] over cout_p, so a K chunk is one (cout block, flipped tap) pair there too.
+extern "C" int32_t mcamd_conv_bsparse_train_ok(const mcamd_conv_geom* g, int32_t dgrad) {
+    if (!dgrad) return mcamd_conv_fwd_bsparse_ok(g);   // (refuses stem, x_wrap and x_f8)
+    if (!g || g->stem || g->x_wrap != 0 || g->x_f8 != 0 || (g->ksize != 1 && g->ksize != 3)) return 0;
+    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->cin <= 0 || g->cout <= 0) return 0;
+    if (g->cin % 8 != 0 || (long long)g->B * g->H * g->W >= (1ll << 31)) return 0;
+    if (g->pad != 0 && g->pad != 1) return 0;
+    return 1;   // (the slice of dy inside dy_ld: checked by the launch, which is given them)
+}
+
+// the launch's own choice for either direction
+static BsparseChoice bsparse_train_choice(const mcamd_conv_geom* g, int dgrad) {
+    const long long M = (long long)g->B * g->H * g->W;
+    return dgrad ? mcamd_bsparse_choice(M, g->cin, kblock_of(cout_p_of(g))) : mcamd_bsparse_choice(M, g->cout, kblock_of(cin_tap_of(g)));
+}
+
+extern "C" int mcamd_conv_bsparse_train_info(const mcamd_conv_geom* g, int32_t dgrad, int32_t out[7]) {
+    MCAMD_REQUIRE(g && out, "conv_bsparse_train_info: null argument");
+    MCAMD_REQUIRE(mcamd_conv_bsparse_train_ok(g, dgrad), "conv_bsparse_train_info: geometry has no block-sparse training form (mcamd_conv_bsparse_train_ok)");
+    const BsparseChoice c = bsparse_train_choice(g, dgrad);
+    out[0] = c.bm, out[1] = c.bn, out[2] = c.bk, out[3] = c.stages, out[4] = c.mtiles, out[5] = c.ntiles, out[6] = c.grid;
+    return MCAMD_OK;
+}
+
+extern "C" int32_t mcamd_conv_bsparse_raw_stats_rows(const mcamd_conv_geom* g, int32_t dgrad) {
+    if (!g || !mcamd_conv_bsparse_train_ok(g, dgrad)) return 0;
+    return bsparse_train_choice(g, dgrad).mtiles;   // one row per pixel tile: the grid is not persistent
+}
+
+extern "C" int mcamd_bsparse_elems_dgrad(const mcamd_conv_geom* g, int64_t out[2]) {
+    MCAMD_REQUIRE(g && out, "bsparse_elems_dgrad: null argument");
+    MCAMD_REQUIRE(mcamd_conv_bsparse_train_ok(g, 1), "bsparse_elems_dgrad: geometry has no block-sparse dgrad (mcamd_conv_bsparse_train_ok)");
+    const int cp = cout_p_of(g);
+    const long long ntiles = (g->cin + 63) / 64, nchunks = (long long)g->ksize * g->ksize * cp / kblock_of(cp);
+    out[0] = ntiles;             // counts
+    out[1] = ntiles * nchunks;   // list entries
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_bsparse_lists_dgrad(const mcamd_conv_geom* g, const void* wp_dgrad, int32_t* count, int32_t* list, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "bsparse_lists_dgrad: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_bsparse_lists_dgrad(&g_, wp_dgrad, count, list, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_bsparse_train_ok(g, 1), "bsparse_lists_dgrad: geometry has no block-sparse dgrad (mcamd_conv_bsparse_train_ok)");
+    MCAMD_REQUIRE(wp_dgrad && count && list, "bsparse_lists_dgrad: null pointer");
+    MCAMD_REQUIRE(((uintptr_t)wp_dgrad & 15) == 0, "bsparse_lists_dgrad: packed weights must be 16-byte aligned");
+    return mcamd_bsparse_lists_launch(wp_dgrad, g->cin, cout_p_of(g), g->ksize * g->ksize, count, list, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_bsparse_raw(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const int32_t* count,
+                                          const int32_t* list, const mcamd_conv_epilogue* epi, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_bsparse_raw: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_bsparse_raw(&g_, x, wp_fwd, count, list, &e_, s); });
+    }
+    if (check_geom(g, "conv_fwd_bsparse_raw")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_bsparse_train_ok(g, 0), "conv_fwd_bsparse_raw: geometry has no block-sparse training form (mcamd_conv_bsparse_train_ok)");
+    MCAMD_REQUIRE(x && wp_fwd && count && list, "conv_fwd_bsparse_raw: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_RAW_F16, "conv_fwd_bsparse_raw: epilogue mode 0 (MCAMD_EPI_RAW_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x, wp_fwd, g->x_ld, g->x_choff, g->cout, cin_tap_of(g), 0);
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_bsparse_raw", bsparse_train_choice(g, 0).mtiles)) return MCAMD_EINVAL;
+    return mcamd_bsparse_launch(a, count, list, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_dgrad_bsparse(const mcamd_conv_geom* g, const void* dy, int32_t dy_ld, int32_t dy_choff, const void* wp_dgrad,
+                                        const int32_t* count, const int32_t* list, const mcamd_conv_epilogue* epi, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_dgrad_bsparse: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_dgrad_bsparse(&g_, dy, dy_ld, dy_choff, wp_dgrad, count, list, &e_, s); });
+    }
+    if (check_geom(g, "conv_dgrad_bsparse")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_bsparse_train_ok(g, 1), "conv_dgrad_bsparse: geometry has no block-sparse dgrad (mcamd_conv_bsparse_train_ok)");
+    MCAMD_REQUIRE(dy && wp_dgrad && count && list, "conv_dgrad_bsparse: null input");
+    const int cout_p = cout_p_of(g);
+    MCAMD_REQUIRE(dy_ld % 8 == 0 && dy_choff % 8 == 0 && dy_choff >= 0 && dy_choff + cout_p <= dy_ld,
+                  "conv_dgrad_bsparse: dy slice [%d, %d) does not fit dy_ld %d", dy_choff, dy_choff + cout_p, dy_ld);
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_RAW_F16 && !epi->stats && epi->dst_mode == 0 && !epi->y2,
+                  "conv_dgrad_bsparse: epilogue mode 0 (MCAMD_EPI_RAW_F16) without statistics only");
+    IgemmArgs a;
+    fill_operand(a, g, dy, wp_dgrad, dy_ld, dy_choff, g->cin, cout_p, 0);   // (the set-up of mcamd_conv_dgrad; one tile shape:
+    if (fill_epilogue(a, epi, g->cin, "conv_dgrad_bsparse", 0)) return MCAMD_EINVAL;   //  epilogue.concurrent changes nothing)
+    return mcamd_bsparse_launch(a, count, list, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------
 // split-K forward for low-batch inference (conv_splitk.hip; an addition beyond the reference)
 // ---------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
-// Block-sparse fp16 inference forward for gfx950 (MI355X): the implicit GEMM of conv_igemm.hip on 64-filter N tiles that
-// takes its K chunks from a list instead of 0 .. nchunks-1 (an addition beyond the reference; Darknet.sparse = "block",
-// DESIGN.md 3t).
+// Block-sparse fp16 forward (inference; forward and dgrad in training) for gfx950 (MI355X): the implicit GEMM of conv_igemm.hip
+// on 64-filter N tiles that takes its K chunks from a list instead of 0 .. nchunks-1 (an addition beyond the reference;
+// Darknet.sparse = "block"; Darknet.sparse_train = "block").
 //
 //   D[m][n] = sum_{q in list[n / 64]} sum_{k in chunk q} X[pixel(m) + tap(q)][c(q, k)] * Wp[n][q kb + k]
 //
@@ -14,13 +14,20 @@
 // Operands, LDS-DMA staging with swizzled source addresses, the NSTAGE ring with counted vmcnt waits and the
 // v_mfma_f32_32x32x16_f16 walk in K order are igemm_kernel's; the epilogue is its MCAMD_EPI_PAD_F16 branch with the shared
 // stores of conv_epi.h.  With full lists every accumulator sees igemm_kernel's MFMA sequence.
+//
+// The training form (Darknet.sparse_train = "block") is the same K loop with igemm_kernel's MCAMD_EPI_RAW_F16
+// branch: the tile to y[M][y_ld] through store_raw_tile and, with a.stats, the BatchNorm partial sums of the stored values to
+// one slab row per pixel tile through store_stats_slab.  It serves the forward GEMM and the dgrad GEMM alike -- the dgrad
+// packing [Cpad][kpos(t, n)] has the same K order over cout_p, so its chunk q is one (cout block, flipped tap) pair and
+// bsparse_lists_kernel reads its lists from it unchanged.
 #include "kernels.h"
 #include "conv_epi.h"
 
 constexpr int BS_BN = 64;   // N tile = the pruning grain (filters per block of block_prune)
 
-// count[ntiles], list[ntiles][nchunks]: entries [0, count[nt]) of row nt are the tile's chunk indices, ascending
-template <int BM, int BK, int NSTAGE>
+// count[ntiles], list[ntiles][nchunks]: entries [0, count[nt]) of row nt are the tile's chunk indices, ascending.
+// EPI: MCAMD_EPI_PAD_F16 (inference) or MCAMD_EPI_RAW_F16 (the training form, forward and dgrad: DESIGN.md 3zc)
+template <int BM, int BK, int NSTAGE, int EPI>
 __global__ __launch_bounds__(256) void bsparse_kernel(IgemmArgs a, const int* __restrict__ count, const int* __restrict__ list) {
     constexpr int BN = BS_BN, NT = 256, WAVES_N = 2;
     constexpr int WM = BM / 2, WN = BN / WAVES_N;      // 2 x 2 waves of (BM / 2) x 32
@@ -57,7 +64,7 @@ __global__ __launch_bounds__(256) void bsparse_kernel(IgemmArgs a, const int* __
         const int slot = it * NT + tid;
         const int row = slot / CPR, phys = slot % CPR;
         // (pooled order when the epilogue pools: four consecutive rows = one 2x2 window)
-        abase[it] = tile_x_base(a, a.dst_mode != 0, mt * BM + row) + (phys ^ swz<CPR>(row)) * 8;
+        abase[it] = tile_x_base(a, EPI == MCAMD_EPI_PAD_F16 && a.dst_mode != 0, mt * BM + row) + (phys ^ swz<CPR>(row)) * 8;
     }
 #pragma unroll
     for (int it = 0; it < B_IT; ++it) {
@@ -125,11 +132,11 @@ __global__ __launch_bounds__(256) void bsparse_kernel(IgemmArgs a, const int* __
             for (int t = 0; t < TM; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[k][t], bf[k], acc[t], 0, 0, 0);
     }
 
-    // ------------------------------- epilogue (igemm_kernel, MCAMD_EPI_PAD_F16) -------------------------------
+    // ------------------------------- epilogue (igemm_kernel's MCAMD_EPI_PAD_F16 / MCAMD_EPI_RAW_F16 branches) -------------------------------
     __syncthreads();   // every wave is done with the stage buffers
     half_t* ct = (half_t*)smem;   // [BM][BN] fp16 output tile
     bool sat = false;
-    {
+    if constexpr (EPI == MCAMD_EPI_PAD_F16) {
         const int col = wn * WN + (lane & 31);
         const int n = nt * BN + col;
         float sc = 1.f, sh = 0.f;
@@ -147,10 +154,37 @@ __global__ __launch_bounds__(256) void bsparse_kernel(IgemmArgs a, const int* __
                 ct[row * BN + col] = (half_t)fminf(fmaxf(v, -65504.f), 65504.f);   // saturate, never inf
                 sat |= fabsf(v) > 65504.f;
             }
+        __syncthreads();
+        store_pad_tile<BM, BN, BN, NT>(a, nullptr, ct, false, false, mt, nt, tid);
+        if (sat && a.overflow) atomicOr(a.overflow, 1);
+    } else {
+        // the raw tile to y[M][y_ld], and (a.stats) the BatchNorm partial sums of the values AS STORED -- fp16, saturated, rows
+        // past the last pixel as zeros: igemm_kernel's convention -- to the slab row of this pixel tile (the grid is not
+        // persistent: one row per M tile).  An empty list leaves the accumulators zero: zeros stored, zero sums.
+        static_assert(EPI == MCAMD_EPI_RAW_F16, "bsparse_kernel: epilogue modes 0 and 2");
+        float s1[1] = {0.f}, s2[1] = {0.f};
+        const int col = wn * WN + (lane & 31);
+        const int mlim = a.M - mt * BM;   // rows of this tile that are real pixels
+#pragma unroll
+        for (int t = 0; t < TM; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = wm * WM + t * 32 + mfma32_row(r, lane);
+                const float v = acc[t][r];
+                const half_t hv = (half_t)fminf(fmaxf(v, -65504.f), 65504.f);   // saturate, never inf
+                sat |= fabsf(v) > 65504.f;
+                ct[row * BN + col] = hv;
+                if (a.stats) {
+                    const float fv = row < mlim ? (float)hv : 0.f;
+                    s1[0] += fv;
+                    s2[0] += fv * fv;
+                }
+            }
+        __syncthreads();
+        store_raw_tile<BM, BN, NT>(a, ct, mt, nt, tid);
+        if (sat && a.overflow) atomicOr(a.overflow, 1);
+        if (a.stats) store_stats_slab<BM, BN, WM, WN, NT>(a, smem, s1, s2, mt, nt, wm, wn, lane, tid);   // (uniform; its barrier ends the tile's use)
     }
-    __syncthreads();
-    store_pad_tile<BM, BN, BN, NT>(a, nullptr, ct, false, false, mt, nt, tid);
-    if (sat && a.overflow) atomicOr(a.overflow, 1);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -211,17 +245,25 @@ int mcamd_bsparse_lists_launch(const void* wp, int cout, int cin_tap, int ntaps,
     return MCAMD_OK;
 }
 
-template <int BM, int BK, int NSTAGE>
-static int bsparse_launch_t(IgemmArgs& a, const BsparseChoice& c, const int* count, const int* list, hipStream_t st) {
+template <int BM, int BK, int NSTAGE, int EPI>
+static int bsparse_launch_e(IgemmArgs& a, const BsparseChoice& c, const int* count, const int* list, hipStream_t st) {
     constexpr int STAGE_BYTES = (BM + BS_BN) * (BK / 8) * 16;
-    constexpr int LDS = NSTAGE * STAGE_BYTES > BM * BS_BN * 2 ? NSTAGE * STAGE_BYTES : BM * BS_BN * 2;   // ring / epilogue tile
-    auto kern = bsparse_kernel<BM, BK, NSTAGE>;
+    // ring / epilogue tile (the statistics reduction of the raw form, 2 x 2 x 64 floats, fits either)
+    constexpr int LDS = NSTAGE * STAGE_BYTES > BM * BS_BN * 2 ? NSTAGE * STAGE_BYTES : BM * BS_BN * 2;
+    auto kern = bsparse_kernel<BM, BK, NSTAGE, EPI>;
     if (LDS > 64 * 1024) MCAMD_LDS_OPT_IN(kern, LDS);
     a.num_mtiles = c.mtiles;
     a.num_ntiles = c.ntiles;
     hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), LDS, st, a, count, list);
-    MCAMD_LAUNCH_CHECK("conv_fwd_bsparse");
+    // (the raw form serves mcamd_conv_fwd_bsparse_raw and mcamd_conv_dgrad_bsparse)
+    MCAMD_LAUNCH_CHECK(EPI == MCAMD_EPI_RAW_F16 ? "conv_fwd_bsparse_raw / conv_dgrad_bsparse" : "conv_fwd_bsparse");
     return MCAMD_OK;
+}
+
+template <int BM, int BK, int NSTAGE>
+static int bsparse_launch_t(IgemmArgs& a, const BsparseChoice& c, const int* count, const int* list, hipStream_t st) {
+    if (a.mode == MCAMD_EPI_RAW_F16) return bsparse_launch_e<BM, BK, NSTAGE, MCAMD_EPI_RAW_F16>(a, c, count, list, st);
+    return bsparse_launch_e<BM, BK, NSTAGE, MCAMD_EPI_PAD_F16>(a, c, count, list, st);
 }
 
 // The instance, in one place.  M tile: MCAMD_BSPARSE_BM_DEFAULT rows (MCAMD_BSPARSE_BM = 64 selects 64, anything else 128:

@@ -128,7 +128,8 @@ struct SplitkPlan {
 SplitkPlan mcamd_splitk_plan(long long M, int n, int cin_tap, int ktot, int forced);
 int mcamd_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, float* ws, hipStream_t st);
 // conv_bsparse.hip: the K chunks of each 64-filter N tile from a list (count[ntiles], list[ntiles][ktot / kb]), mode 2
-// epilogue; and the lists of a packed forward weight matrix
+// epilogue (inference) or mode 0 (a.mode == MCAMD_EPI_RAW_F16: the training form, forward and dgrad; a.stats: one slab row
+// per pixel tile); and the lists of a packed forward or dgrad weight matrix
 #define MCAMD_BSPARSE_BM_DEFAULT 128
 // mcamd_bsparse_choice names the bsparse_kernel instance (bm pixels x bn filters, K chunks of bk, LDS ring stages) and its
 // grid (whole rounds of 8 pixel tiles) for M pixels x N filters with channel blocks of kb; the launch dispatches on it

@@ -60,6 +60,9 @@ _LAYER_FIELDS = dict(
     # inference form (Engine._choose_forms, _FORMS) and what belongs to one: split-K slices (forms "splitk" and "q8_splitk"),
     # 2:4 values + index words, block-sparse chunk lists
     form="dense", sk_slices=1, wsp=None, widx=None, bs_count=None, bs_list=None,
+    # the training form of the block-sparse kernel (form "bsparse_train"): its statistics slab (one row per pixel tile), the
+    # chunk lists over the dgrad packing, whether the dgrad launch takes it too, and full lists (Engine.bsparse_train_full_lists)
+    bs_stats=None, bs_dcount=None, bs_dlist=None, bs_dgrad=False, bs_full=None,
     # fp8: launch geometry on the byte buffer, byte destinations, private input copy, packed operands; "fp8-qat" training:
     # the fp32 raw output + statistics that stand in for the fp16 ones, and the values the weight bytes stand for
     geom_q8=None, q8_y=False, q8_y2=False, xq=None, _xq=None, _xq_key=None, wq=None, wqs=None, widx8=None, wexp=None,
@@ -143,6 +146,14 @@ BSPARSE_MAX_KEPT = 0.375
 # at B = 128 is 0.375 in both MFMA forms (worst layer 1.16x on converted bytes, 1.15x on the fp8 MFMA; at 0.5 conv15 / conv22
 # gain 5-7 % only, and from 0.625 up the fp8-MFMA form loses on the 13x13 3x3 layers).
 Q8_BSPARSE_MAX_KEPT = 0.375
+# Darknet.sparse_train = "block": a masked block of the fp16 TRAINING step leaves the dense forward and dgrad launches for the
+# raw-epilogue form of the block-sparse kernel when its kept-chunk fraction is at most this -- the default of
+# Darknet.sparse_train_max_kept.  The rule of DESIGN.md 3t on tools/bsparse_train_bench.py (profiles/bsparse_train_bench.json):
+# the largest measured kept fraction at which BOTH the forward and the dgrad launch of every layer of conv9 .. conv22 are at
+# least 10 % faster than the dense training launches they replace (0.0 would mean: no level passes).  Measured at B = 64: 0.375
+# (worst launch 1.11x, conv21's dgrad; at 0.5 conv9's dgrad loses 3 %).  The rule looks at the launches it replaces: the two list
+# launches per chosen block and step (0.9 ms per step in all) are not in it -- the whole step only gains below kept 0.3.
+BSPARSE_TRAIN_MAX_KEPT = 0.375
 
 
 class _Dense:
@@ -244,6 +255,73 @@ class _BSparse(_Dense):
 
     def repacked(self, eng, lay):
         ops.bsparse_lists(lay.geom_act, lay.wp, lay.bs_count, lay.bs_list)
+
+
+class _BSparseTrain(_BSparse):
+    """The training form (Darknet.sparse_train = "block"): the same kernel with the raw fp16 epilogue, for the
+    forward launch (statistics slab of one row per pixel tile) and -- on chunk lists built from the dgrad packing, whose K
+    order is the forward's over cout_p -- for the dgrad launch.  Both lists are rebuilt behind every re-pack."""
+    fwd = None                           # (no fused inference launch: an eval pass chooses its forms by Darknet.sparse)
+
+    def policy(self, eng, max_kept):
+        """_BSparse.policy for the training step: the candidates are the masked inner blocks the training launches accept
+        (Engine._bst_eligible); planned once while the masks are static (pack caches the answer by the mask keys)."""
+        def masked(lay):
+            m = lay.conv.mask if lay.conv.mask_flag else None
+            return m is not None and m.is_cuda and m.dtype == torch.float32 and m.shape == lay.conv.weight.shape
+        cand = [lay for lay in eng.layers if masked(lay) and eng._bst_eligible(lay, compacted=False)]
+        sums = []
+        for lay in cand:
+            wp, _ = ops.pack_weights(lay.geom, lay.conv.weight.data, lay.conv.mask.contiguous(), want_dgrad=False)
+            sums.append(ops.bsparse_lists(lay.geom, wp)[0].sum())
+        chosen, kept = [], {}
+        for lay, s_ in zip(cand, torch.stack(sums).cpu().tolist() if cand else []):
+            kept[lay.li + 1] = s_ / float(ops.bsparse_elems(lay.geom)[1])       # conv number (conv1 = the first block)
+            if kept[lay.li + 1] <= max_kept:
+                chosen.append(lay.li)
+        return frozenset(chosen), kept
+
+    def alloc(self, eng, lays):
+        _BSparse.alloc(self, eng, lays)
+        dev = eng.device
+        for lay in lays:
+            rows = ops.bsparse_raw_stats_rows(lay.geom_act)
+            if lay.bs_stats is None or lay.bs_stats.shape[0] != rows:
+                lay.bs_stats = torch.zeros(rows, 2, ops.round_up(lay.cout, 256), dtype=torch.float32, device=dev)
+            # a block on the one-launch 1x1 backward keeps that backward: only its forward is chosen
+            lay.bs_dgrad = (lay.gin is not None and lay.wd is not None and not eng._bwd1x1_route(lay)
+                            and ops.conv_bsparse_train_ok(lay.geom_act, True))
+            nc, nl = ops.bsparse_elems_dgrad(lay.geom_act) if lay.bs_dgrad else (0, 0)
+            if lay.bs_dgrad and (lay.bs_dcount is None or lay.bs_dcount.numel() != nc or lay.bs_dlist.numel() != nl):
+                lay.bs_dcount = torch.zeros(nc, dtype=torch.int32, device=dev)
+                lay.bs_dlist = torch.zeros(nc, nl // nc, dtype=torch.int32, device=dev)
+            lay.bs_full = None               # (Engine.bsparse_train_full_lists: built when a launch asks for them)
+
+    def repacked(self, eng, lay):
+        eng._timed('lists', lay, ops.bsparse_lists, lay.geom_act, lay.wp, lay.bs_count, lay.bs_list)
+        if lay.bs_dgrad:
+            eng._timed('lists', lay, ops.bsparse_lists_dgrad, lay.geom_act, lay.wd, lay.bs_dcount, lay.bs_dlist)
+
+    def full(self, eng, lay):
+        """(count, list, dgrad count, dgrad list) naming every chunk: the test switch Engine.bsparse_train_full_lists"""
+        if lay.bs_full is None:
+            full = ops.bsparse_full_lists(*ops.bsparse_elems(lay.geom_act), eng.device)
+            lay.bs_full = full + (ops.bsparse_full_lists(*ops.bsparse_elems_dgrad(lay.geom_act), eng.device) if lay.bs_dgrad
+                                  else (None, None))
+        return lay.bs_full
+
+    def raw(self, eng, lay, xin, training):
+        if not training:
+            return _Dense.raw(self, eng, lay, xin, training)
+        count, lst = self.full(eng, lay)[:2] if eng.bsparse_train_full_lists else (lay.bs_count, lay.bs_list)
+        eng._timed('fwd', lay, ops.conv_fwd_bsparse_raw, lay.geom_act, xin, lay.wp, count, lst, lay.y, lay.cout, 0, stats=lay.bs_stats)
+
+    def dgrad(self, eng, lay, concurrent):
+        """The dgrad launch of a chosen block (Engine._backward_body): no producer sums -- its producer's BatchNorm backward
+        runs its own pass 0."""
+        count, lst = self.full(eng, lay)[2:] if eng.bsparse_train_full_lists else (lay.bs_dcount, lay.bs_dlist)
+        eng._timed('dgrad', lay, ops.conv_dgrad_bsparse, lay.geom_act, lay.dy, lay.cout_p, 0, lay.wd, count, lst, lay.gin,
+                   lay.tin.ld, lay.tin.choff, overflow=eng.overflow, concurrent=concurrent)
 
 
 class _Q8(_Dense):
@@ -366,7 +444,7 @@ class _Q8W4(_Q8):
         eng._timed('fwd', lay, ops.conv_fwd_q8_w4_raw, lay.geom_act, x8, lay.w4c, lay.w4g, lay.wexp4, lay.y, lay.cout, 0, lay.stats)
 
 
-_FORMS = {"dense": _Dense(), "splitk": _SplitK(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "q8": _Q8(),
+_FORMS = {"dense": _Dense(), "splitk": _SplitK(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "bsparse_train": _BSparseTrain(), "q8": _Q8(),
           "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4(), "q8_bsparse": _Q8BSparse()}
 
 
@@ -509,6 +587,15 @@ class Engine:
         self.bsparse_layers = []
         self.bsparse_kept = {}           # conv number -> kept-chunk fraction of every candidate block
         self._bs_exempt = frozenset()    # layer indices the policy chose: their filters are not compacted (_BSparse.policy)
+        # block-sparse TRAINING (Darknet.sparse_train = "block", plain-fp16 training passes only): conv numbers of
+        # the blocks whose forward runs mcamd_conv_fwd_bsparse_raw, of those whose dgrad runs mcamd_conv_dgrad_bsparse too, and
+        # the kept-chunk fraction of every candidate; planned once while the masks are static (`_bst_policy` caches the
+        # policy's answer by mask keys and bound).  `bsparse_train_full_lists` (tests): the same kernels on full lists.
+        self.bsparse_train_layers = []
+        self.bsparse_train_dgrad_layers = []
+        self.bsparse_train_kept = {}
+        self._bst_policy = None
+        self._bst_full = False
         # split-K low-batch inference (Darknet.splitk, plain-fp16 eval engines only): conv numbers of the blocks that run
         # mcamd_conv_fwd_splitk, chosen when the flag or the masks change (_choose_forms); one workspace for all of them
         self.splitk_layers = []
@@ -987,6 +1074,10 @@ class Engine:
         exempt = frozenset()
         if sparse == "block":
             exempt, self.bsparse_kept = _FORMS["bsparse"].policy(self, max_kept)
+        elif sparse == "block-train":       # (Darknet.sparse_train; re-packed every step: one host read per set of masks)
+            if self._bst_policy is None or self._bst_policy[0] != (mkeys, max_kept):
+                self._bst_policy = ((mkeys, max_kept),) + _FORMS["bsparse_train"].policy(self, max_kept)
+            exempt, self.bsparse_train_kept = self._bst_policy[1:]
         elif self.q8_bsparse and max_kept is not None:
             exempt, self.fp8_block_kept = _FORMS["q8_bsparse"].policy(self, max_kept)
         key = (mkeys, exempt, sparse, max_kept, splitk)
@@ -1066,9 +1157,12 @@ class Engine:
                 ops.pack_many(*self._pack_table)
             if side is not None:
                 self._pack_on_side = True      # forward() makes the launch stream wait for the second one before block 2
-        for lay in self.layers:                # (what a form derives from the weights the forward launch reads)
-            if lay.form != "dense":
-                _FORMS[lay.form].repacked(self, lay)
+            # what a form derives from the packed weights (the chunk lists): on the stream the re-pack ran on, behind it.
+            # Only blocks behind the first one take such a form, so the wait in front of block 2 orders their launches
+            # behind these as it orders them behind the re-pack.
+            for lay in self.layers:
+                if lay.form != "dense":       # (_inner: lay.li > 0)
+                    _FORMS[lay.form].repacked(self, lay)
         self._packed_sig = sig
         self.model._weights_dirty = False
 
@@ -1093,6 +1187,25 @@ class Engine:
         block-sparse policy, which runs in front of the compaction and exempts the blocks it picks from it."""
         return (self._inner(lay) and self._fused_eval(lay, border_ok, compacted)
                 and (not compacted or (lay.fold is None and lay.g_cols is None)))
+
+    def _bst_eligible(self, lay, compacted=True):
+        """Can this block train on the block-sparse kernel (form "bsparse_train")?  An inner block of the plain-fp16 engine
+        with a BatchNorm and a raw fp16 output whose geometry mcamd_conv_bsparse_train_ok accepts; `compacted` (behind the
+        compaction plan): and no fold, gather or perm, on itself or forced on it by its producer."""
+        ok = (self.precision == "fp16" and self._inner(lay) and lay.bn is not None and lay.y is not None
+              and lay.y.dtype == torch.float16 and lay.geom is not None and ops.conv_bsparse_train_ok(lay.geom))
+        if ok and compacted:
+            ok = (lay.fold is None and not lay.gather and lay.perm is None and lay.in_perm is None and lay.geom_act is lay.geom
+                  and not lay.fold_consumers and not lay.skip_dead)
+        return ok
+
+    bsparse_train_full_lists = property(lambda self: self._bst_full)
+
+    @bsparse_train_full_lists.setter
+    def bsparse_train_full_lists(self, on):
+        if bool(on) != self._bst_full:
+            self._bst_full = bool(on)
+            self._plan_epoch += 1            # recorded plans hold the lists' addresses
 
     def _conforming(self, cand):
         """The blocks of `cand` whose mask keeps at most 2 of every 4 consecutive input channels at each (filter, tap):
@@ -1167,6 +1280,10 @@ class Engine:
             for lay in self.layers:
                 if lay.li in exempt and self._eligible(lay):
                     lay.form = "bsparse"
+        elif sparse == "block-train":
+            for lay in self.layers:          # (a chosen block whose producer was compacted after all stays dense)
+                if lay.li in exempt and self._bst_eligible(lay):
+                    lay.form = "bsparse_train"
         if splitk:
             for lay in self.layers:
                 launch = self._splitk_form(lay)
@@ -1184,6 +1301,11 @@ class Engine:
         self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
         self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_bsparse")
         self.fp8_block_layers = nums("q8_bsparse")
+        if self._training:                   # (what the last training-mode choice was; an eval pass in between keeps it)
+            self.bsparse_train_layers = nums("bsparse_train")
+            self.bsparse_train_dgrad_layers = [lay.li + 1 for lay in self.layers if lay.form == "bsparse_train" and lay.bs_dgrad]
+            if sparse != "block-train":
+                self.bsparse_train_kept = {}
         self.fp8_sparse_layers, self.fp8_splitk_layers, self.fp8_w4_layers = nums("q8_sparse24"), nums("q8_splitk"), nums("q8_w4")
         self._form_key = key
 
@@ -1665,6 +1787,12 @@ class Engine:
             raise McamdError("precision %r is inference only (there is no fp8 training path): call model.eval() or "
                              "pick another precision for training" % (self.precision,))
         mode = None if training else getattr(self.model, "sparse", None)
+        st = getattr(self.model, "sparse_train", None) if training else None
+        if st not in (None, "block"):
+            raise McamdError("sparse_train must be None or 'block' (got %r)" % (st,))
+        if st == "block" and self.precision != "fp16":
+            raise McamdError("sparse_train=%r trains in the plain-fp16 engine only (model.precision = 'fp16'), not precision=%r"
+                             % (st, self.precision))
         if mode is not None and (self.precise or self.q8):
             raise McamdError("sparse=%r runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r%s"
                              % (mode, self.precision, "; 2:4 masks on the fp8 engine: model.precision = 'fp8-2:4' with "
@@ -1681,6 +1809,9 @@ class Engine:
         max_kept = float(getattr(self.model, "sparse_max_kept", BSPARSE_MAX_KEPT)) if mode == "block" else None
         if self.q8_bsparse and not training:
             max_kept = float(getattr(self.model, "fp8_block_max_kept", Q8_BSPARSE_MAX_KEPT))
+        if st == "block" and float(getattr(self.model, "sparse_train_max_kept", BSPARSE_TRAIN_MAX_KEPT)) > 0.0:
+            # (a bound of 0.0 chooses nothing: the sparse_train = None engine, bit for bit)
+            mode, max_kept = "block-train", float(getattr(self.model, "sparse_train_max_kept", BSPARSE_TRAIN_MAX_KEPT))
         self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept)
         self.serial += 1
         tin = self.layers[0].tin
@@ -1814,7 +1945,8 @@ class Engine:
                 self._qat_forward(lay, xin)
                 continue
             _FORMS[lay.form].raw(self, lay, xin, training)
-            ops.bn_coeffs(lay.stats if training else None, lay.cout, lay.M, bn.weight.data, bn.bias.data,
+            stats = lay.bs_stats if lay.form == "bsparse_train" else lay.stats      # (one row per pixel tile of that kernel)
+            ops.bn_coeffs(stats if training else None, lay.cout, lay.M, bn.weight.data, bn.bias.data,
                           bn.running_mean, bn.running_var, training, lay.scale, lay.shift, lay.mean, lay.invstd,
                           momentum=_momentum(bn), eps=bn.eps, perm=lay.perm32, ones_channel=lay.ones_idx)
             t = lay.out_t
@@ -2206,6 +2338,9 @@ class Engine:
                 # (... and where the input comes from a PLAIN block, the launch takes that block's BatchNorm-backward sums
                 # from the tile it stores: _dgrad_sums)
                 conc = side is not None and self._side_concurrent
+                if lay.form == "bsparse_train" and lay.bs_dgrad:
+                    _FORMS[lay.form].dgrad(self, lay, conc)
+                    continue
                 ds = self._dgrad_sums(lay, conc)
                 if ds is not None:
                     sums_of[ds[2].li] = ds[1]

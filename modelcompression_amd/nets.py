@@ -333,6 +333,16 @@ class Darknet(nn.Module):
         self.sparse = None
         from .engine import BSPARSE_MAX_KEPT
         self.sparse_max_kept = BSPARSE_MAX_KEPT      # the measured policy constant (engine.py)
+        # Block-sparse TRAINING (an addition beyond the reference): "block" runs the forward and the dgrad launch
+        # of every masked inner block whose kept-chunk fraction is at most `sparse_train_max_kept` on the raw-epilogue form of
+        # the block-sparse kernel (engine.Engine.bsparse_train_layers / bsparse_train_dgrad_layers / bsparse_train_kept): the
+        # zero blocks of block_prune / taylor_prune(granularity="block") masks are skipped, bit-identically to multiplying
+        # them.  The weight gradient stays dense.  Training-mode passes with precision "fp16" only -- any other training
+        # precision raises; eval ignores it (`sparse` is the eval switch, and training keeps ignoring that one).  A bound of
+        # 0.0, or a model without masks, is the engine of sparse_train = None bit for bit.
+        self.sparse_train = None
+        from .engine import BSPARSE_TRAIN_MAX_KEPT
+        self.sparse_train_max_kept = BSPARSE_TRAIN_MAX_KEPT      # the measured policy constant (engine.py)
         # Low-batch inference (an addition beyond the reference): True runs every block whose forward launch would leave most
         # CUs idle -- the 13x13 and 26x26 layers at B = 1 -- as a split-K pair (csrc/conv_splitk.hip, DESIGN.md 3p,
         # engine.Engine.splitk_layers); batches the policy does not split run exactly what they run without it.  Eval with

@@ -1156,6 +1156,87 @@ def conv_fwd_bsparse(g, x, wp, count, lst, y, y_ld, y_choff=0, scale=None, shift
           "mcamd_conv_fwd_bsparse")
 
 
+# ... the training form: raw fp16 epilogue, forward and dgrad (Darknet.sparse_train = "block")
+def conv_bsparse_train_ok(g, dgrad=False):
+    """Does conv_fwd_bsparse_raw (dgrad=False) / conv_dgrad_bsparse (dgrad=True) accept this geometry?  Needs no GPU."""
+    return bool(L.lib().mcamd_conv_bsparse_train_ok(C.byref(g), 1 if dgrad else 0))
+
+
+def conv_bsparse_train_info(g, dgrad=False):
+    """BsparseInfo of the instance that launch takes (mcamd_conv_bsparse_train_info, the launch's own choice).  Needs no GPU."""
+    out = (C.c_int32 * 7)()
+    check(L.lib().mcamd_conv_bsparse_train_info(C.byref(g), 1 if dgrad else 0, out), "mcamd_conv_bsparse_train_info")
+    return BsparseInfo(*out)
+
+
+def bsparse_raw_stats_rows(g, dgrad=False):
+    """Rows of the statistics slab of conv_fwd_bsparse_raw: one per pixel tile (0: geometry refused)."""
+    return int(L.lib().mcamd_conv_bsparse_raw_stats_rows(C.byref(g), 1 if dgrad else 0))
+
+
+def bsparse_elems_dgrad(g):
+    """(ntiles, ntiles * nchunks) of the lists over the dgrad packing: ntiles = ceil(cin / 64), nchunks = k*k * cout_p / kb_d."""
+    out = (C.c_int64 * 2)()
+    check(L.lib().mcamd_bsparse_elems_dgrad(C.byref(g), out), "mcamd_bsparse_elems_dgrad")
+    return int(out[0]), int(out[1])
+
+
+def bsparse_lists_dgrad(g, wpd, out_count=None, out_list=None):
+    """bsparse_lists on the packed dgrad weights: per 64-input-channel tile the K chunks (cout block, flipped tap) holding a
+    non-zero weight, ascending (mcamd_bsparse_lists_dgrad; no host synchronisation)."""
+    _need_cuda(wpd)
+    nc, nl = bsparse_elems_dgrad(g)
+    if out_count is None:
+        out_count = torch.empty(nc, dtype=torch.int32, device=wpd.device)
+    if out_list is None:
+        out_list = torch.empty(nc, nl // nc, dtype=torch.int32, device=wpd.device)
+    if out_count.numel() != nc or out_list.numel() != nl or wpd.numel() < packed_elems(g)[1]:
+        raise L.McamdError("bsparse_lists_dgrad: operand sizes do not fit the geometry")
+    check(L.lib().mcamd_bsparse_lists_dgrad(C.byref(g), ptr(wpd), ptr(out_count), ptr(out_list), stream_ptr()),
+          "mcamd_bsparse_lists_dgrad")
+    return out_count, out_list
+
+
+def bsparse_full_lists(nc, nl, device):
+    """(count, list) naming every chunk of every tile: what all_chunks=True launches on."""
+    nch = nl // nc
+    return (torch.full((nc,), nch, dtype=torch.int32, device=device),
+            torch.arange(nch, dtype=torch.int32, device=device).repeat(nc, 1).contiguous())
+
+
+def _check_lists(what, x, count, lst, nc, nl):
+    _need_cuda(x, count, lst)
+    if count.dtype != torch.int32 or lst.dtype != torch.int32 or count.numel() != nc or lst.numel() != nl or not lst.is_contiguous():
+        raise L.McamdError("%s: count / list must be contiguous int32 of %d / %d entries" % (what, nc, nl))
+
+
+def conv_fwd_bsparse_raw(g, x, wp, count, lst, y, y_ld, y_choff=0, stats=None, all_chunks=False, overflow=None):
+    """conv_fwd_raw over the listed K chunks of each 64-filter tile: y[M][y_ld] fp16 raw (saturated, `overflow` flag);
+    `stats`: fp32 [bsparse_raw_stats_rows(g)][2][stats_ld] slab or None.  all_chunks=True: the same launch on full lists."""
+    nc, nl = bsparse_elems(g)
+    if all_chunks:
+        count, lst = bsparse_full_lists(nc, nl, x.device)
+    _check_lists("conv_fwd_bsparse_raw", x, count, lst, nc, nl)
+    e = _epi(L.EPI_RAW_F16, y, y_ld, y_choff, stats=stats, stats_rows_=stats.shape[0] if stats is not None else 0,
+             stats_ld=stats.shape[2] if stats is not None else 0, overflow=overflow)
+    check(L.lib().mcamd_conv_fwd_bsparse_raw(C.byref(g), ptr(x), ptr(wp), ptr(count), ptr(lst), C.byref(e), stream_ptr()),
+          "mcamd_conv_fwd_bsparse_raw")
+
+
+def conv_dgrad_bsparse(g, dy, dy_ld, dy_choff, wpd, count, lst, out, out_ld, out_choff=0, overflow=None, concurrent=False,
+                       all_chunks=False):
+    """conv_dgrad_raw over the listed K chunks of each 64-input-channel tile (bsparse_lists_dgrad).  `concurrent` is passed
+    on and ignored by the library (one tile shape).  all_chunks=True: the same launch on full lists."""
+    nc, nl = bsparse_elems_dgrad(g)
+    if all_chunks:
+        count, lst = bsparse_full_lists(nc, nl, dy.device)
+    _check_lists("conv_dgrad_bsparse", dy, count, lst, nc, nl)
+    e = _epi(L.EPI_RAW_F16, out, out_ld, out_choff, overflow=overflow)
+    e.concurrent = 1 if concurrent else 0
+    check(L.lib().mcamd_conv_dgrad_bsparse(C.byref(g), ptr(dy), dy_ld, dy_choff, ptr(wpd), ptr(count), ptr(lst), C.byref(e),
+                                           stream_ptr()), "mcamd_conv_dgrad_bsparse")
+
+
 # ----------------------------------------------------------------------------- split-K forward (low-batch inference)
 def conv_fwd_splitk_info(g, mode, dst_mode=0, slices=0):
     """mcamd_splitk_info of a split-K forward of `g` with epilogue `mode` (L.EPI_PAD_F16 / L.EPI_RAW_F16): host logic only.

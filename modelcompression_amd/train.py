@@ -47,6 +47,10 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     optimizer step; importance.TaylorImportance.accumulate adds each step's scores in one launch, skipped on the device
     when StepGuard flags the step.  The BatchNorm running statistics are put back afterwards.  With several ranks each
     scores its own shard and the accumulators are all-reduced.  Every other method value behaves as before.
+  * YOLOv2Train.SPARSE_TRAIN = "block" (an attribute; None by default: train() is what it was) sets Darknet.sparse_train on the
+    model behind set_masks: with pruning_method "block" or "taylor-block" and the training precision "fp16", the forward and
+    dgrad launches of the retraining steps skip the zeroed blocks of every layer whose kept fraction is at most the model's
+    default bound (engine.BSPARSE_TRAIN_MAX_KEPT).
 """
 import os
 
@@ -238,6 +242,11 @@ class YOLOv2Train():
     _share_arg = None
     # batches scored before pruning by pruning_method = "taylor-*" (an attribute: train() keeps its signature)
     TAYLOR_STEPS = 16
+    # None / "block": Darknet.sparse_train of the model train() builds, set behind set_masks (an attribute too).  "block" skips
+    # the zero blocks of pruning_method "block" / "taylor-block" masks in the forward and dgrad launches of the fp16 training
+    # step; it needs the training precision "fp16" (MCAMD_PRECISION) and, for blocks to be chosen, a bound
+    # Darknet.sparse_train_max_kept above the layers' kept fractions.
+    SPARSE_TRAIN = None
 
     def __init__(self):
         self.model = ''
@@ -349,6 +358,8 @@ class YOLOv2Train():
                 masks = weight_prune(self.model, pruning_perc)
             dp.broadcast_masks(masks, src=0)
             self.model.set_masks(masks)
+        if self.SPARSE_TRAIN is not None:      # (the engine checks the value and the training precision: "fp16" only)
+            self.model.sparse_train = self.SPARSE_TRAIN
         if world > 1:
             # static weight masks: only the kept gradient entries travel (dp.py); filter masks keep the dense transport
             reducer = dp.attach(self.model, masks=masks if (masks is not None and pruning_method not in ("filter", "taylor-filter")) else None)
