@@ -949,7 +949,7 @@ def load_compressed(model, path, set_masks=True):
         for t, a in zip(_small_targets(conv, bn), rec["small"]):
             t.copy_(torch.from_numpy(a.astype(np.float32)))
     model.seen = int(info["seen"])
-    model._weights_dirty = True
+    model._mark_weights_replaced()
     if set_masks and any(rec["bits"] for rec in recs):
         model.set_masks(masks)
     if set_masks and any(b is not None for b in books):

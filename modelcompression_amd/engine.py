@@ -563,6 +563,7 @@ class Engine:
         self.grad_scale = float(grad_scale)
         self.serial = 0
         self._packed_sig = None
+        self._weights_seen = None     # Darknet._weights_serial at the last pack (None: never packed)
         self.events = None            # list of (tag, layer, start, end) HIP events while profiling
         self.event_pool = None        # ... and reusable timing events a caller may hand in for them (_timed)
         # weight-gradient kernels on a second HIP stream beside the dgrad / BN-backward chain (they fill each other's
@@ -1062,10 +1063,15 @@ class Engine:
             force = True          # the folded constants differ between batch and running statistics
         self._training = training
         sig = self._signature()
-        if (not force and sig == self._packed_sig and (sparse, max_kept, splitk) == self._form_key[2:]
-                and not self.model._weights_dirty):
+        # "the model says its weights were replaced" is per engine: Darknet._weights_dirty is cleared by the first engine
+        # that packs, Darknet._weights_serial counts every time it was raised -- an eval engine must re-pack after
+        # invalidate_packed() although the training engine packed first, and an engine's first pack (a second training
+        # engine after grad_scale was halved) must not keep the static default exponents
+        serial = self.model._weights_serial
+        dirty = self.model._weights_dirty or serial != self._weights_seen
+        if not force and sig == self._packed_sig and (sparse, max_kept, splitk) == self._form_key[2:] and not dirty:
             return
-        if self.model._weights_dirty or (self.f8 and self.serial % 1000 == 999):      # (and every 1 000th forward: slow drift)
+        if dirty or (self.f8 and self.serial % 1000 == 999):      # (and every 1 000th forward: slow drift)
             self._refresh_f8_wexp()
         mkeys = tuple(None if not lay.conv.mask_flag else (lay.conv.mask.data_ptr(), lay.conv.mask._version)
                       for lay in self.layers)
@@ -1164,6 +1170,7 @@ class Engine:
                 if lay.form != "dense":       # (_inner: lay.li > 0)
                     _FORMS[lay.form].repacked(self, lay)
         self._packed_sig = sig
+        self._weights_seen = serial
         self.model._weights_dirty = False
 
     # ------------------------------------------------------------------ inference forms

@@ -281,7 +281,8 @@ class Darknet(nn.Module):
         self.seen = 0
         # engine state (not part of the reference surface)
         self._engines = {}
-        self._weights_dirty = True
+        self._weights_dirty = True      # raised by _mark_weights_replaced(), cleared by the first engine that packs
+        self._weights_serial = 0        # ... and how often it was raised: what every further engine goes by
         self._ws_table = None           # project_codebooks: the cached table over the tied layers (share.py)
         self._grad_hook = None          # callable(flat_grad) run at the end of backward (data parallel)
         self._grad_ready_hook = None    # callable(flat_grad, lo, hi[, fence]): that slice is final (overlapped all-reduce; Engine.backward)
@@ -350,9 +351,17 @@ class Darknet(nn.Module):
         self.splitk = os.environ.get("MCAMD_SPLITK", "0") == "1"
 
     # ---- engine plumbing
+    def _mark_weights_replaced(self):
+        """The weights (or masks) were replaced behind the engines' backs: every engine re-packs, and reads what it derives
+        from the weights on the host again, before its next forward.  `_weights_dirty` is the flag the first engine that
+        packs clears; `_weights_serial` counts the calls, and each engine compares it with the count it last packed at
+        (Engine.pack) -- a model has up to three engines, and the flag alone reaches only the first of them."""
+        self._weights_dirty = True
+        self._weights_serial += 1
+
     def _apply(self, fn, *args, **kwargs):
         self._engines = {}
-        self._weights_dirty = True
+        self._mark_weights_replaced()
         self._ws_table = None
         return super(Darknet, self)._apply(fn, *args, **kwargs)
 
@@ -370,10 +379,10 @@ class Darknet(nn.Module):
 
     def invalidate_packed(self):
         """Call after modifying weights through `.data` outside optimizer.step / set_masks / load_weights."""
-        self._weights_dirty = True
+        self._mark_weights_replaced()
 
     def load_state_dict(self, *args, **kwargs):
-        self._weights_dirty = True
+        self._mark_weights_replaced()
         return super(Darknet, self).load_state_dict(*args, **kwargs)
 
     def _engine_for(self, x):
@@ -531,7 +540,7 @@ class Darknet(nn.Module):
                 elif block['type'] == 'connected':
                     model = self.models[ind]
                     load_fc(f, model[0] if block['activation'] != 'linear' else model)
-        self._weights_dirty = True
+        self._mark_weights_replaced()
 
     def load_weights_old(self, weightfile):
         """nets.py:950-1005: 4 x int32 header (kept in self.header, seen = header[3]), then floats."""
@@ -551,7 +560,7 @@ class Darknet(nn.Module):
                 elif block['type'] == 'connected':
                     model = self.models[ind]
                     load_fc(f, model[0] if block['activation'] != 'linear' else model)
-        self._weights_dirty = True
+        self._mark_weights_replaced()
 
     def save_weights(self, outfile, cutoff=0):
         """nets.py:1007-1051: header int32 [major, minor, revision, seen] (so a saved file always
@@ -614,7 +623,7 @@ class Darknet(nn.Module):
                     count += 1
             except Exception:
                 pass
-        self._weights_dirty = True
+        self._mark_weights_replaced()
 
 
 def debug_weights(model):

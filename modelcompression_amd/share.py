@@ -182,7 +182,7 @@ def set_codebooks(model, codebooks, expand_weights=True):
             conv.weight.data = expand(conv.codebook, conv.codes, _mask_of(conv)).to(conv.weight.dtype)
         conv.share_flag = True
     model._ws_table = None
-    model._weights_dirty = True
+    model._mark_weights_replaced()
 
 
 def _device_table(model, tied):
@@ -216,9 +216,10 @@ def project_codebooks(model):
     if all(conv.weight.is_cuda for _, conv in tied):
         _device_table(model, tied).project()
         # The kernel wrote through raw pointers.  Bumping the version counters is what an in-place torch write would have
-        # done: EVERY engine of the model compares them before its next forward and re-packs (Darknet._weights_dirty is
-        # cleared by the first engine that packs).  The per-layer fp8 exponents of a "mixed" engine are not re-read on a
-        # version-only change; none is needed here: a mean never exceeds its largest member, so no layer's largest |w| grows.
+        # done: EVERY engine of the model compares them before its next forward and re-packs.  (Darknet._mark_weights_replaced()
+        # reaches every engine too, and has each read its per-layer fp8 exponents on the host again.)  A "mixed" engine does
+        # not re-read them on a version-only change; none is needed here: a mean never exceeds its largest member, so no
+        # layer's largest |w| grows.
         for _, conv in tied:
             torch.autograd.graph.increment_version(conv.weight)
     else:
@@ -229,7 +230,7 @@ def project_codebooks(model):
                        conv.codes.detach().cpu().numpy().reshape(-1), c.numpy())
             conv.weight.data.copy_(w)
             conv.codebook.copy_(c)
-        model._weights_dirty = True
+        model._mark_weights_replaced()
 
 
 def are_codebooks_consistent(model):
