@@ -671,6 +671,44 @@ int mcamd_conv_wgrad_plan_info(const mcamd_conv_geom* g, int32_t has_cmap, int32
  * written (out may be NULL with cap 0); returns their number.  Any other tuple is an MCAMD_EINVAL of the launch. */
 int32_t mcamd_wgrad_generic_instances(int32_t* out, int32_t cap);
 
+/* ------------------------------------------------------------------------- *
+ * The list launch of the weight gradient (Darknet.sparse_train = "block-wgrad").  For a block mask the zero
+ * blocks of dW are OUTPUT tiles of the two 64 x 64 weight-gradient kernels: a block of 64 filters x 64 input channels x one
+ * tap (block_prune) is one tap of a wgrad9_kernel workgroup tile (3x3 layers) or a whole tile of wgrad_kernel<64, 64, 1, 64>
+ * (1x1 layers).  The launch runs the listed tiles only, and of a 3x3 tile the taps whose bit is set in its tap word; the
+ * finish pass writes exactly 0.0f wherever the mask is zero WITHOUT reading the slabs there (skipped tiles and taps leave
+ * their part of the workspace as it was), and sum * (1 / grad_scale) * mask elsewhere, in mcamd_conv_wgrad's order of
+ * additions.  The lists come from the MASK, never from weight values: a kept weight that is zero still has a gradient.  Any
+ * mask is correct, block-aligned or not: a tile or tap is kept when any of its mask elements is non-zero (-0 counts as
+ * zero), and an elementwise hole inside a kept block is the finish pass's select.  Deterministic; no atomics on floats.
+ * ------------------------------------------------------------------------- */
+/* 1: ksize 1 or 3, stem == 0, x_wrap == 0, x_f8 == 0, cin % 64 == 0, cout % 64 == 0, the input slice inside x_ld, and for
+ * ksize 3 the geometries of the padded-pixel 9-tap kernel (W <= 208 and the MCAMD_WGRAD9 switch on).  Host logic only. */
+int32_t mcamd_conv_wgrad_bsparse_ok(const mcamd_conv_geom* g);
+/* int32 entries of the lists: out[0] = the tiles nt = (cout / 64) * (cin / 64) (tile list), out[1] = 2 nt (tap words). */
+int mcamd_wgrad_bsparse_elems(const mcamd_conv_geom* g, int64_t out[2]);
+/* From the fp32 OIHW mask: the word of tile (ot, ct), index ot * (cin / 64) + ct, has bit t set iff any mask element of
+ * filters [64 ot, 64 ot + 64) x channels [64 ct, 64 ct + 64) x tap t is non-zero (ksize 1: bit 0).  tiles[0 .. counts[0]):
+ * the tiles with a non-zero word, ascending; words[0 .. counts[0]): their words; counts[1]: the kept (tile, tap) pairs.
+ * Entries behind counts[0] are written as 0; words[nt .. 2 nt) holds the word of EVERY tile.  No host synchronisation. */
+int mcamd_wgrad_bsparse_lists(const mcamd_conv_geom* g, const float* mask_oihw, int32_t* tiles, int32_t* words, int32_t* counts,
+                              void* stream);
+/* What a list launch of `kept_tiles` tiles runs (host logic only, the launch's own plan function): out = {family
+ * (MCAMD_WGRAD_NINE wgrad9_kernel<KP>, never the wide form; MCAMD_WGRAD_GENERIC wgrad_kernel<64, 64, 1, 64>), KP, LDS ring
+ * stages, nsplit, pix_per_split, finish kernel (MCAMD_WFIN_VEC: its select form), SG, workspace bytes}.  nsplit is
+ * mcamd_conv_wgrad's cost rule applied to the kept tile count (0 tiles count as one). */
+#define MCAMD_WGRAD_BSPARSE_PLAN_N 8
+int mcamd_conv_wgrad_bsparse_plan(const mcamd_conv_geom* g, int32_t kept_tiles, int64_t out[MCAMD_WGRAD_BSPARSE_PLAN_N]);
+/* dw_oihw and dbias as mcamd_conv_wgrad computes them with the same mask (no channel map), on the `ntiles` listed tiles.
+ * `nsplit` is the caller's (from the plan query: 1 .. the steps of the kernel), so that a launch on full lists -- every tile,
+ * word 0x1ff or 1 -- runs at the split count of the short ones and gives the same bits; workspace >= nsplit * cout * k*k *
+ * cin floats (out[7] above).  ntiles == 0 launches the finish pass only: all zeros.  `words` may be NULL for ksize 1.  A
+ * tile index outside [0, nt) is skipped.  The mask must be the one the lists were built from: a kept element outside the
+ * listed tiles and taps would read slab that nobody wrote. */
+int mcamd_conv_wgrad_bsparse(const mcamd_conv_geom* g, const void* x, const void* dy, int32_t dy_ld, int32_t dy_choff,
+                             const float* mask_oihw, const int32_t* tiles, const int32_t* words, int32_t ntiles, int32_t nsplit,
+                             float grad_scale, float* dw_oihw, float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The whole backward of a dense 1x1 block in ONE launch plus the weight gradient's finish pass: what mcamd_conv_dgrad_sums
  * (epilogue mode 0) and mcamd_conv_wgrad compute for the same arguments, from one pass over dY and x.
  *   gin[m][g_choff + c] = sum_n dy[m][n] w[n][c] as fp16 [B*H*W][g_ld], saturated to +-65504 with `overflow` (may be NULL)

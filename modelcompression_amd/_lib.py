@@ -203,6 +203,7 @@ DST_PLAIN, DST_POOL, DST_REORG = 0, 1, 2
 WGRAD_GENERIC, WGRAD_STEM, WGRAD_WIN, WGRAD_NINE, WGRAD_NINE_WIDE = 0, 1, 2, 3, 4      # mcamd_conv_wgrad_plan_info: family
 WFIN_ROW, WFIN_VEC, WFIN_GENERIC = 0, 1, 2                                             # ... and finish kernel
 WGRAD_PLAN_INFO_N = 13
+WGRAD_BSPARSE_PLAN_N = 8                                                               # mcamd_conv_wgrad_bsparse_plan
 STEM_PLAN_FWD, STEM_PLAN_FWD_PLANES, STEM_PLAN_STATS, STEM_PLAN_GRAM, STEM_PLAN_BWD = 0, 1, 2, 3, 4    # mcamd_stem_block_plan_info
 STEM_PLAN_INFO_N = 20
 WZ_FP32, WZ_FP16, WZ_FP8, WZ_CODE, WZ_W4 = 0, 1, 2, 4, 5                               # mcamd_wz_seg.kind (WZ_W4: | taps << 8)
@@ -287,6 +288,11 @@ SIGNATURES = {
     "mcamd_conv_wgrad": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _I32, _I32, _P, C.POINTER(ChanMap), _F, _P, _P, _P, _SZ, _P]),
     "mcamd_conv_wgrad_plan_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I32)]),
     "mcamd_wgrad_generic_instances": (_I32, [C.POINTER(_I32), _I32]),
+    "mcamd_conv_wgrad_bsparse_ok": (_I32, [C.POINTER(ConvGeom)]),
+    "mcamd_wgrad_bsparse_elems": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I64)]),
+    "mcamd_wgrad_bsparse_lists": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
+    "mcamd_conv_wgrad_bsparse_plan": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I64)]),
+    "mcamd_conv_wgrad_bsparse": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _I32, _I32, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _SZ, _P]),
     "mcamd_conv_bwd1x1_ok": (_I32, [C.POINTER(ConvGeom), C.POINTER(C.c_char_p)]),
     "mcamd_conv_bwd1x1_sums_rows": (_I32, [C.POINTER(ConvGeom)]),
     "mcamd_conv_bwd1x1_wgrad_splits": (_I32, [C.POINTER(ConvGeom)]),

@@ -1484,6 +1484,31 @@ extern "C" int32_t mcamd_wgrad_generic_instances(int32_t* out, int32_t cap) {
     return mcamd_wgrad_instances((int (*)[4])out, out ? cap : 0);
 }
 
+// the operands of a weight-gradient launch as the compute kernels address them (mcamd_conv_wgrad and its list form)
+static WgradArgs wgrad_args_of(const mcamd_conv_geom* g, const void* x, const void* dy, int dy_ld, int dy_choff, void* workspace) {
+    WgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const half_t*)x;
+    a.dy = (const half_t*)dy;
+    a.slab = (float*)workspace;
+    a.x_ld = g->x_ld;
+    a.x_row_stride = (g->W + pw_of(g)) * g->x_ld;
+    a.x_img_stride = (long long)(g->H + pw_of(g)) * a.x_row_stride;
+    a.x_off = g->x_choff;
+    a.dy_ld = dy_ld;
+    a.dy_row_stride = (g->W + pw_of(g)) * dy_ld;
+    a.dy_img_stride = (long long)(g->H + pw_of(g)) * a.dy_row_stride;
+    a.dy_off = dy_choff + a.dy_row_stride + dy_ld;
+    a.dy_zero_off = dy_choff;
+    a.H = g->H, a.W = g->W, a.HW = g->H * g->W;
+    a.M = (int)((long long)g->B * g->H * g->W);
+    a.cin_tap = cin_tap_of(g);
+    a.ntaps = ntaps_of(g);
+    a.ktot = a.ntaps * a.cin_tap;
+    fill_taps(g->ksize, g->stem, a.x_row_stride, g->x_ld, a.tap_off);
+    return a;
+}
+
 extern "C" int mcamd_conv_wgrad(const mcamd_conv_geom* g, const void* x, const void* dy, int32_t dy_ld, int32_t dy_choff,
                                 const float* mask_oihw, const mcamd_chan_map* map, float grad_scale, float* dw_oihw,
                                 float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1514,26 +1539,7 @@ extern "C" int mcamd_conv_wgrad(const mcamd_conv_geom* g, const void* x, const v
         return MCAMD_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = (const half_t*)x;
-    a.dy = (const half_t*)dy;
-    a.slab = (float*)workspace;
-    a.x_ld = g->x_ld;
-    a.x_row_stride = (g->W + pw_of(g)) * g->x_ld;
-    a.x_img_stride = (long long)(g->H + pw_of(g)) * a.x_row_stride;
-    a.x_off = g->x_choff;
-    a.dy_ld = dy_ld;
-    a.dy_row_stride = (g->W + pw_of(g)) * dy_ld;
-    a.dy_img_stride = (long long)(g->H + pw_of(g)) * a.dy_row_stride;
-    a.dy_off = dy_choff + a.dy_row_stride + dy_ld;
-    a.dy_zero_off = dy_choff;
-    a.H = g->H, a.W = g->W, a.HW = g->H * g->W;
-    a.M = (int)M;
-    a.cin_tap = cin_tap;
-    a.ntaps = ntaps;
-    a.ktot = ntaps * cin_tap;
-    fill_taps(g->ksize, g->stem, a.x_row_stride, g->x_ld, a.tap_off);
+    WgradArgs a = wgrad_args_of(g, x, dy, dy_ld, dy_choff, workspace);
     int rc = p.nine    ? mcamd_wgrad9_launch(a, p, g->W + pw_of(g), padded_pixels(g), st)
              : p.stemw == 1 ? mcamd_wgrad_stem_launch(a, p, st)
              : p.stemw == 2 ? mcamd_wgrad_win_launch(a, p, st)
@@ -1548,6 +1554,100 @@ extern "C" int mcamd_conv_wgrad(const mcamd_conv_geom* g, const void* x, const v
         rc = mcamd_colsum_launch((const half_t*)dy, rows, dy_ld, dy_choff, g->cout, 1.0f / grad_scale, dbias, st, workspace,
                                  workspace_bytes);
     }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------
+// the list launch of the weight gradient (conv_wgrad.hip; Darknet.sparse_train = "block-wgrad")
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_wgrad_bsparse_ok(const mcamd_conv_geom* g) {
+    if (!g || g->B <= 0 || g->H <= 0 || g->W <= 0 || g->cin <= 0 || g->cout <= 0) return 0;
+    if (g->x_wrap || g->x_f8 || (g->pad != 0 && g->pad != 1)) return 0;
+    if (g->x_choff < 0 || g->x_choff % 8 || g->x_choff + g->cin > g->x_ld) return 0;
+    return mcamd_wgrad_bsparse_ok(g->ksize, g->stem, g->cout, g->cin, g->W) ? 1 : 0;
+}
+
+extern "C" int mcamd_wgrad_bsparse_elems(const mcamd_conv_geom* g, int64_t out[2]) {
+    MCAMD_REQUIRE(g && out, "wgrad_bsparse_elems: null argument");
+    MCAMD_REQUIRE(mcamd_conv_wgrad_bsparse_ok(g), "wgrad_bsparse_elems: geometry has no list weight gradient (mcamd_conv_wgrad_bsparse_ok)");
+    const int64_t nt = (int64_t)(g->cout / 64) * (g->cin / 64);
+    out[0] = nt;
+    out[1] = 2 * nt;
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_wgrad_bsparse_lists(const mcamd_conv_geom* g, const float* mask_oihw, int32_t* tiles, int32_t* words,
+                                         int32_t* counts, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "wgrad_bsparse_lists: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_wgrad_bsparse_lists(&g_, mask_oihw, tiles, words, counts, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_wgrad_bsparse_ok(g), "wgrad_bsparse_lists: geometry has no list weight gradient (mcamd_conv_wgrad_bsparse_ok)");
+    MCAMD_REQUIRE(mask_oihw && tiles && words && counts, "wgrad_bsparse_lists: null pointer");
+    return mcamd_wgrad_bsparse_lists_launch(mask_oihw, g->cout, g->cin, ntaps_of(g), tiles, words, counts, (hipStream_t)stream);
+}
+
+static WgradPlan wgrad_bsparse_plan_for(const mcamd_conv_geom* g, int kept_tiles, int nsplit) {
+    return mcamd_wgrad_bsparse_plan(g->ksize, (long long)g->B * g->H * g->W, padded_pixels(g), g->cout, g->cin, g->W + pw_of(g),
+                                    kept_tiles, nsplit);
+}
+
+extern "C" int mcamd_conv_wgrad_bsparse_plan(const mcamd_conv_geom* g, int32_t kept_tiles, int64_t out[MCAMD_WGRAD_BSPARSE_PLAN_N]) {
+    if (check_geom(g, "conv_wgrad_bsparse_plan")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(out, "conv_wgrad_bsparse_plan: null output");
+    MCAMD_REQUIRE(mcamd_conv_wgrad_bsparse_ok(g), "conv_wgrad_bsparse_plan: geometry has no list weight gradient (mcamd_conv_wgrad_bsparse_ok)");
+    MCAMD_REQUIRE(kept_tiles >= 0 && kept_tiles <= (g->cout / 64) * (g->cin / 64),
+                  "conv_wgrad_bsparse_plan: %d kept tiles of %d", kept_tiles, (g->cout / 64) * (g->cin / 64));
+    const WgradPlan p = wgrad_bsparse_plan_for(g, kept_tiles, 0);
+    const WgradFinish f = mcamd_wgrad_finish_pick(p.nsplit, 0, g->cin, g->ksize, false);
+    out[0] = p.nine ? MCAMD_WGRAD_NINE : MCAMD_WGRAD_GENERIC;
+    out[1] = p.kp, out[2] = p.ns, out[3] = p.nsplit, out[4] = p.pix_per_split;
+    out[5] = f.kernel, out[6] = f.sg;
+    out[7] = (int64_t)p.bytes;
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_conv_wgrad_bsparse(const mcamd_conv_geom* g, const void* x, const void* dy, int32_t dy_ld, int32_t dy_choff,
+                                        const float* mask_oihw, const int32_t* tiles, const int32_t* words, int32_t ntiles,
+                                        int32_t nsplit, float grad_scale, float* dw_oihw, float* dbias, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "conv_wgrad_bsparse: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) {
+            return mcamd_conv_wgrad_bsparse(&g_, x, dy, dy_ld, dy_choff, mask_oihw, tiles, words, ntiles, nsplit, grad_scale, dw_oihw,
+                                            dbias, workspace, workspace_bytes, s);
+        });
+    }
+    if (check_geom(g, "conv_wgrad_bsparse")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_wgrad_bsparse_ok(g), "conv_wgrad_bsparse: geometry has no list weight gradient (mcamd_conv_wgrad_bsparse_ok)");
+    MCAMD_REQUIRE(x && dy && mask_oihw && dw_oihw && workspace, "conv_wgrad_bsparse: null argument");
+    MCAMD_REQUIRE(grad_scale > 0.f, "conv_wgrad_bsparse: grad_scale must be positive");
+    const int all_tiles = (g->cout / 64) * (g->cin / 64);
+    MCAMD_REQUIRE(ntiles >= 0 && ntiles <= all_tiles, "conv_wgrad_bsparse: %d listed tiles of %d", ntiles, all_tiles);
+    MCAMD_REQUIRE(ntiles == 0 || (tiles && (words || g->ksize == 1)), "conv_wgrad_bsparse: null list");
+    // (a split holds at least one step of the kernel: more splits than steps would only sum slabs of zeros)
+    const long long max_split = g->ksize == 3 ? (padded_pixels(g) + 31) / 32 : ((long long)g->B * g->H * g->W + 63) / 64;
+    MCAMD_REQUIRE(nsplit >= 1 && nsplit <= max_split, "conv_wgrad_bsparse: nsplit %d outside [1, %lld]", nsplit, max_split);
+    const WgradPlan p = wgrad_bsparse_plan_for(g, ntiles, nsplit);
+    MCAMD_REQUIRE(dy_ld % 8 == 0 && dy_choff % 8 == 0 && dy_choff + p.rows_pad <= dy_ld,
+                  "conv_wgrad_bsparse: dy slice [%d, %d) does not fit dy_ld %d", dy_choff, dy_choff + p.rows_pad, dy_ld);
+    if (workspace_bytes < p.bytes) {
+        mcamd_set_error("conv_wgrad_bsparse: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
+        return MCAMD_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    WgradArgs a = wgrad_args_of(g, x, dy, dy_ld, dy_choff, workspace);
+    int rc = MCAMD_OK;
+    if (ntiles > 0) rc = mcamd_wgrad_bsparse_launch(a, p, g->W + pw_of(g), padded_pixels(g), tiles, words, ntiles, st);
+    if (rc) return rc;
+    rc = mcamd_wgrad_finish_launch((const float*)workspace, p, a.ktot, a.cin_tap, 0, g->cout, g->cin, g->ksize, mask_oihw,
+                                   1.0f / grad_scale, dw_oihw, nullptr, nullptr, st, true);
+    if (rc) return rc;
+    if (dbias)     // (as mcamd_conv_wgrad: the slabs are consumed, the workspace is free again in stream order)
+        rc = mcamd_colsum_launch((const half_t*)dy, padded_pixels(g), dy_ld, dy_choff, g->cout, 1.0f / grad_scale, dbias, st,
+                                 workspace, workspace_bytes);
     return rc;
 }
 

@@ -47,7 +47,9 @@ __device__ __forceinline__ void wait_vm_dyn(int n) {
     }
 }
 
-template <int TMo, int TNc, int TAPS, int KP, int NS>
+// LIST (mcamd_conv_wgrad_bsparse, the 64 x 64 one-tap instance only): the workgroup takes its tile from a.tile_list instead of
+// enumerating all of them; everything behind the tile index is the dense kernel's.
+template <int TMo, int TNc, int TAPS, int KP, int NS, bool LIST = false>
 __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
     constexpr int NT = 256;
     constexpr int NI = TMo / 32, WPI = 4 / NI, NJ = TNc / 32;
@@ -71,13 +73,14 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
     // XCD-aware order: work items are numbered split-major (all tiles of a split stream the same
     // dY / X pixel range); blocks are dealt round-robin to the 8 XCDs, so XCD x takes the
     // contiguous chunk [x*chunk, (x+1)*chunk) and neighbouring items share its L2.
-    const int ntiles = a.n_otiles * a.n_tapgroups * a.n_ctiles;
+    const int ntiles = LIST ? a.n_list : a.n_otiles * a.n_tapgroups * a.n_ctiles;
     const int total_items = ntiles * a.nsplit;
     const int chunk = (total_items + 7) >> 3;
     const int item = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
     if ((int)(blockIdx.x >> 3) >= chunk || item >= total_items) return;
     const int split = item / ntiles;
-    const int tile = item - split * ntiles;
+    const int tile = LIST ? a.tile_list[item - split * ntiles] : item - split * ntiles;
+    if (LIST && (unsigned)tile >= (unsigned)(a.n_otiles * a.n_tapgroups * a.n_ctiles)) return;   // a foreign list entry: no tile
     const int per_o = a.n_tapgroups * a.n_ctiles;
     const int ot = tile / per_o;
     const int rem = tile - ot * per_o;
@@ -275,10 +278,17 @@ struct Wgrad9Args {
     int P;               // number of padded pixels B*(H+2)*(W+2)
     int rows_pad, ktot, cin_tap;
     int n_ctiles, n_otiles, nsplit, steps_per_split, nsteps_total;
+    // list launch (mcamd_conv_wgrad_bsparse): n_list tiles, their indices ot * n_ctiles + ct and their 9-bit tap words
+    const int* tile_list;
+    const int* tap_words;
+    int n_list;
 };
 
 // KP = pixels per step (32 or 64; steps_per_split / nsteps_total are in units of 32 pixels)
-template <int KP>
+// LIST: the workgroup takes its tile and a tap word from the lists.  A tap whose bit is clear costs the wave neither its B
+// fragment nor its MFMA nor its part of the slab store (wave-uniform scalar branches, as the 4-tap waves of the wide form
+// take them); staging, the MFMA order over the pixels of a kept tap and the store are the dense kernel's: the same lines.
+template <int KP, bool LIST = false>
 __global__ __launch_bounds__(256, 2) void wgrad9_kernel(Wgrad9Args a) {
     constexpr int RB = 128, CH = 8;   // 64 channels = 128 bytes = 8 chunks per row
     constexpr int U = KP / 32;        // 32-pixel units per step
@@ -289,13 +299,16 @@ __global__ __launch_bounds__(256, 2) void wgrad9_kernel(Wgrad9Args a) {
     const int R = KP + 2 * a.S;                 // window rows (multiple of 8)
     const int a_bytes = KP * RB, x_bytes = R * RB, stage_bytes = a_bytes + x_bytes;
 
-    const int ntiles = a.n_otiles * a.n_ctiles;
+    const int ntiles = LIST ? a.n_list : a.n_otiles * a.n_ctiles;
     const int total_items = ntiles * a.nsplit;
     const int chunk = (total_items + 7) >> 3;
     const int item = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
     if ((int)(blockIdx.x >> 3) >= chunk || item >= total_items) return;
     const int split = item / ntiles;
-    const int tile = item - split * ntiles;
+    const int tile = LIST ? a.tile_list[item - split * ntiles] : item - split * ntiles;
+    const int word = LIST ? a.tap_words[item - split * ntiles] : 0x1ff;      // (scalar loads: the index is wave-uniform)
+    if (LIST && (unsigned)tile >= (unsigned)(a.n_otiles * a.n_ctiles)) return;   // a foreign list entry: no tile
+    auto kept = [&](int t) { return !LIST || ((word >> t) & 1) != 0; };
     const int ot = tile / a.n_ctiles, ct = tile - ot * a.n_ctiles;
     // steps of KP pixels; the split boundaries are in 32-pixel units (the host makes steps_per_split a multiple of U)
     const int st0 = split * a.steps_per_split / U;
@@ -349,22 +362,25 @@ __global__ __launch_bounds__(256, 2) void wgrad9_kernel(Wgrad9Args a) {
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int shift = (t / 3 - 1) * a.W2 + (t % 3 - 1);
-                bf[t] = tr_frag_rows_builtin<RB>(sx, 16 * s + a.S + shift, wj * 32, lane);
+                if (kept(t)) bf[t] = tr_frag_rows_builtin<RB>(sx, 16 * s + a.S + shift, wj * 32, lane);
             }
 #pragma unroll
-            for (int t = 0; t < 9; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf[t], acc[t], 0, 0, 0);
+            for (int t = 0; t < 9; ++t)
+                if (kept(t)) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf[t], acc[t], 0, 0, 0);
         }
     }
 
     float* out = a.slab + (long long)split * a.rows_pad * a.ktot;
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+    for (int t = 0; t < 9; ++t) {
+        if (!kept(t)) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             int n = ot * 64 + wi * 32 + mfma32_row(r, lane);
             int k = t * a.cin_tap + ct * 64 + wj * 32 + (lane & 31);
             out[(long long)n * a.ktot + k] = acc[t][r];
         }
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -562,7 +578,31 @@ __global__ __launch_bounds__(512, 1) void wgrad9w_kernel(Wgrad9Args a) {
 // Vector form (Cin % 4 == 0): an item = 4 consecutive input channels of one filter = 4*KK
 // contiguous OIHW floats; per tap it sums float4 slab reads (coalesced across the block) and the
 // transposition [tap][c] -> [c][tap] happens in registers.
-template <int KK, int SG>
+//
+// SEL (the list launch only, mcamd_conv_wgrad_bsparse: a mask, no maps): the parts of the slabs that belong to skipped tiles and
+// taps hold whatever an earlier layer left there, NaN and Inf bit patterns included, and NaN * 0 is NaN.  So a slab element
+// whose mask value is zero is never read and its dW is the constant 0.0f: a select, not a product.  Where the mask is
+// non-zero: the same loads, the same order of additions and the same two products as without SEL.
+template <bool SEL, int KK>
+__device__ __forceinline__ f32x4_t slab_ld4(const float* p, const float (&mk)[SEL ? 4 * KK : 1], int t) {
+    if constexpr (!SEL) {
+        return *(const f32x4_t*)p;
+    } else {
+        const bool k0 = mk[t] != 0.f, k1 = mk[KK + t] != 0.f, k2 = mk[2 * KK + t] != 0.f, k3 = mk[3 * KK + t] != 0.f;
+        f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+        if (k0 && k1 && k2 && k3) {
+            v = *(const f32x4_t*)p;
+        } else {       // an elementwise hole, or a whole cleared tap: the kept elements one by one
+            if (k0) v[0] = p[0];
+            if (k1) v[1] = p[1];
+            if (k2) v[2] = p[2];
+            if (k3) v[3] = p[3];
+        }
+        return v;
+    }
+}
+
+template <int KK, int SG, bool SEL = false>
 __global__ __launch_bounds__(256) void wgrad_finish_vec_kernel(const float* slab, int nsplit, int rows_pad, int ktot,
                                                                int cin_tap, int Cout, int Cin, const float* mask,
                                                                float inv_scale, float* dw, const int* rmap,
@@ -584,6 +624,15 @@ __global__ __launch_bounds__(256) void wgrad_finish_vec_kernel(const float* slab
     f32x4_t acc[KK];
 #pragma unroll
     for (int t = 0; t < KK; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float mk[SEL ? 4 * KK : 1];                   // SEL: the item's 4 * KK mask values, OIHW order ([channel][tap])
+    if (SEL) {
+#pragma unroll
+        for (int e = 0; e < (SEL ? KK : 0); ++e) {
+            const f32x4_t m = live ? *(const f32x4_t*)(mask + ((long long)n * Cin + c) * KK + 4 * e) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mk[SEL ? 4 * e + i : 0] = m[i];
+        }
+    }
     if (live) {
         const float* p = slab + (long long)n * ktot + c;
         constexpr int U = KK == 1 ? 8 : 2;        // splits issued together: 8 (1x1 layers) or 2 x 9 loads in flight
@@ -593,7 +642,7 @@ __global__ __launch_bounds__(256) void wgrad_finish_vec_kernel(const float* slab
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int t = 0; t < KK; ++t) l[u][t] = *(const f32x4_t*)(p + t * cin_tap + (s + u * SG) * split_stride);
+                for (int t = 0; t < KK; ++t) l[u][t] = slab_ld4<SEL, KK>(p + t * cin_tap + (s + u * SG) * split_stride, mk, t);
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -601,7 +650,7 @@ __global__ __launch_bounds__(256) void wgrad_finish_vec_kernel(const float* slab
         }
         for (; s < nsplit; s += SG) {
 #pragma unroll
-            for (int t = 0; t < KK; ++t) acc[t] += *(const f32x4_t*)(p + t * cin_tap + s * split_stride);
+            for (int t = 0; t < KK; ++t) acc[t] += slab_ld4<SEL, KK>(p + t * cin_tap + s * split_stride, mk, t);
         }
     }
     if (SG > 1) {
@@ -636,7 +685,12 @@ __global__ __launch_bounds__(256) void wgrad_finish_vec_kernel(const float* slab
 #pragma unroll
     for (int e = 0; e < KK; ++e) {
         f32x4_t ov = {out[4 * e], out[4 * e + 1], out[4 * e + 2], out[4 * e + 3]};
-        if (mask) ov *= *(const f32x4_t*)(mask + base + 4 * e);
+        if (SEL) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ov[i] = mk[SEL ? 4 * e + i : 0] != 0.f ? ov[i] * mk[SEL ? 4 * e + i : 0] : 0.0f;
+        } else if (mask) {
+            ov *= *(const f32x4_t*)(mask + base + 4 * e);
+        }
         *(f32x4_t*)(dw + base + 4 * e) = ov;
     }
 }
@@ -765,6 +819,32 @@ static int wgrad9_S(int pitch) { return round_up_int(pitch + 1, 4); }   // pitch
 static size_t wgrad9w_stage(int pitch) { return (size_t)64 * 256 + (size_t)(64 + 2 * wgrad9_S(pitch)) * 128; }
 static int wgrad9w_ring(int pitch) { return 3 * wgrad9w_stage(pitch) <= 160 * 1024 ? 3 : 2; }
 
+// pixels per step of wgrad9_kernel: 64 (half the barriers, 17-25 % fewer staged bytes per flop) while two double-buffered
+// workgroups still fit the LDS; the big-image layers (window of 64 + 2(W+3) rows) stay at 32
+// (128 pixels per step (13x13 layers only) measured 1.8x SLOWER: wgrad9_kernel exists for 32 and 64)
+static int wgrad9_kp(int pitch) {
+    return 2 * (size_t)(64 + 64 + 2 * wgrad9_S(pitch)) * 128 <= 72 * 1024 ? 64 : 32;   // two workgroups per CU: 2 x 72 KB
+}
+
+// Pixel splits of the 9-tap kernels: whole rounds of the `slots` workgroups that run at once, time ~ rounds(ns) / ns plus the
+// slab traffic that grows with ns; at least 8 steps of 32 pixels per split.  `tiles`: workgroups per split.
+static long long wgrad9_pick_splits(long long tiles, long long nsteps, long long slots) {
+    long long cap = 2048 / tiles;
+    if (cap < 1) cap = 1;
+    if (cap > nsteps / 8) cap = nsteps / 8 > 0 ? nsteps / 8 : 1;
+    long long ns = 1;
+    double best = 1e30;
+    for (long long c = 1; c <= cap; ++c) {
+        double rounds = (double)((tiles * c + slots - 1) / slots);
+        double cost = rounds / (double)c * (1.0 + 0.004 * (double)c);
+        if (cost < best - 1e-12) {
+            best = cost;
+            ns = c;
+        }
+    }
+    return ns;
+}
+
 // plan of the padded-pixel 9-tap kernel (see wgrad9_kernel); P = padded pixels
 static WgradPlan wgrad9_plan(long long P, int cout, int cin_tap, int W, int pitch, int B) {
     WgradPlan p;
@@ -773,12 +853,8 @@ static WgradPlan wgrad9_plan(long long P, int cout, int cin_tap, int W, int pitc
     p.stemw = 0;
     p.tmo = p.tnc = 64;
     p.taps = 9;
-    // 64 pixels per step (half the barriers, 17-25 % fewer staged bytes per flop) while two double-buffered
-    // workgroups still fit the LDS; the big-image layers (window of 64 + 2(W+3) rows) stay at 32
-    p.kp = 32;
+    p.kp = wgrad9_kp(pitch);
     p.ns = 2;
-    // 128 pixels per step (13x13 layers only) measured 1.8x SLOWER: wgrad9_kernel exists for 32 and 64
-    if (2 * (size_t)(64 + 64 + 2 * wgrad9_S(pitch)) * 128 <= 72 * 1024) p.kp = 64;   // two workgroups per CU: 2 x 72 KB
     p.rows_pad = round_up_int(cout, 64);
     p.n_otiles = p.rows_pad / 64;
     p.n_ctiles = cin_tap / 64;
@@ -799,20 +875,7 @@ static WgradPlan wgrad9_plan(long long P, int cout, int cin_tap, int W, int pitc
     }
     long long tiles = (long long)p.n_otiles * p.n_ctiles;
     long long nsteps = (P + 31) / 32;   // in 32-pixel units
-    const long long slots = wide ? 256 : 512;
-    long long cap = 2048 / tiles;
-    if (cap < 1) cap = 1;
-    if (cap > nsteps / 8) cap = nsteps / 8 > 0 ? nsteps / 8 : 1;
-    long long ns = 1;
-    double best = 1e30;
-    for (long long c = 1; c <= cap; ++c) {
-        double rounds = (double)((tiles * c + slots - 1) / slots);
-        double cost = rounds / (double)c * (1.0 + 0.004 * (double)c);
-        if (cost < best - 1e-12) {
-            best = cost;
-            ns = c;
-        }
-    }
+    long long ns = wgrad9_pick_splits(tiles, nsteps, wide ? 256 : 512);
     long long sps = (nsteps + ns - 1) / ns;
     sps = (sps + p.kp / 32 - 1) / (p.kp / 32) * (p.kp / 32);      // whole steps of kp pixels per split
     ns = (nsteps + sps - 1) / sps;
@@ -830,7 +893,7 @@ bool mcamd_wgrad_use9(int ksize, int stem, int cout, int cin_tap, int W) {
 WgradPlan mcamd_wgrad_plan9(long long P, int cout, int cin_tap, int W, int pitch, int B) { return wgrad9_plan(P, cout, cin_tap, W, pitch, B); }
 
 // pitch: padded pixels per image row; P: padded pixels enumerated (both follow the operands' form, include/mcamd.h)
-int mcamd_wgrad9_launch(const WgradArgs& w, const WgradPlan& p, int pitch, long long P, hipStream_t st) {
+static Wgrad9Args wgrad9_args(const WgradArgs& w, const WgradPlan& p, int pitch, long long P) {
     Wgrad9Args a;
     memset(&a, 0, sizeof(a));
     a.x = w.x;
@@ -851,7 +914,14 @@ int mcamd_wgrad9_launch(const WgradArgs& w, const WgradPlan& p, int pitch, long 
     a.nsplit = p.nsplit;
     a.steps_per_split = p.pix_per_split / 32;
     a.nsteps_total = (int)((P + 31) / 32);
-    const int R = 32 + 2 * a.S;
+    return a;
+}
+
+// dynamic LDS of wgrad9_kernel<KP>: two stages of the dY tile and the X window
+static size_t wgrad9_lds(int kp, int S) { return 2 * (size_t)(kp * 128 + (kp + 2 * S) * 128); }
+
+int mcamd_wgrad9_launch(const WgradArgs& w, const WgradPlan& p, int pitch, long long P, hipStream_t st) {
+    const Wgrad9Args a = wgrad9_args(w, p, pitch, P);
     const int grid = round_up_int(p.n_otiles * p.n_ctiles * p.nsplit, 8);
     if (p.nine == 2 && p.kp == 64 && (p.ns == 2 || p.ns == 3)) {
         const size_t stage = wgrad9w_stage(pitch);
@@ -860,17 +930,37 @@ int mcamd_wgrad9_launch(const WgradArgs& w, const WgradPlan& p, int pitch, long 
         if (p.ns == 3) hipLaunchKernelGGL((wgrad9w_kernel<64, 3>), dim3(grid), dim3(512), 3 * stage, st, a);
         else hipLaunchKernelGGL((wgrad9w_kernel<64, 2>), dim3(grid), dim3(512), 2 * stage, st, a);
     } else if (p.nine == 1 && p.kp == 64) {
-        const size_t lds = 2 * (size_t)(64 * 128 + (R + 32) * 128);
-        hipLaunchKernelGGL(wgrad9_kernel<64>, dim3(grid), dim3(256), lds, st, a);
+        hipLaunchKernelGGL(wgrad9_kernel<64>, dim3(grid), dim3(256), wgrad9_lds(64, a.S), st, a);
     } else if (p.nine == 1 && p.kp == 32) {
-        const size_t lds = 2 * (size_t)(32 * 128 + R * 128);
-        hipLaunchKernelGGL(wgrad9_kernel<32>, dim3(grid), dim3(256), lds, st, a);
+        hipLaunchKernelGGL(wgrad9_kernel<32>, dim3(grid), dim3(256), wgrad9_lds(32, a.S), st, a);
     } else {
         mcamd_set_error("wgrad9: no kernel instance for form %d kp %d stages %d", p.nine, p.kp, p.ns);
         return MCAMD_EINVAL;
     }
     MCAMD_LAUNCH_CHECK("wgrad9");
     return MCAMD_OK;
+}
+
+// Pixel splits of wgrad_kernel: fill whole rounds of the machine.  `slots` workgroups run at once (3 per CU at the
+// default 48 KB of LDS); time ~ rounds(ns) / ns, plus the slab traffic that grows with ns.  `tiles`: workgroups per split.
+static long long wgrad_pick_splits(long long tiles, long long M, int kp) {
+    const long long slots = 768;
+    long long max_by_work = (M + 8 * kp - 1) / (8 * kp);  // at least 8 steps per split
+    if (max_by_work < 1) max_by_work = 1;
+    long long cap = 3072 / tiles;
+    if (cap < 1) cap = 1;
+    if (cap > max_by_work) cap = max_by_work;
+    long long ns = 1;
+    double best = 1e30;
+    for (long long c = 1; c <= cap; ++c) {
+        double rounds = (double)((tiles * c + slots - 1) / slots);
+        double cost = rounds / (double)c * (1.0 + 0.004 * (double)c);
+        if (cost < best - 1e-12) {
+            best = cost;
+            ns = c;
+        }
+    }
+    return ns;
 }
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps) {
@@ -887,24 +977,7 @@ WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps) {
     p.n_ctiles = cin_tap / p.tnc;
     p.n_tapgroups = ntaps / p.taps;
     long long tiles = (long long)p.n_otiles * p.n_tapgroups * p.n_ctiles;
-    // Pixel splits: fill whole rounds of the machine.  `slots` workgroups run at once (3 per CU at the
-    // default 48 KB of LDS); time ~ rounds(ns) / ns, plus the slab traffic that grows with ns.
-    const long long slots = 768;
-    long long max_by_work = (M + 8 * p.kp - 1) / (8 * p.kp);  // at least 8 steps per split
-    if (max_by_work < 1) max_by_work = 1;
-    long long cap = 3072 / tiles;
-    if (cap < 1) cap = 1;
-    if (cap > max_by_work) cap = max_by_work;
-    long long ns = 1;
-    double best = 1e30;
-    for (long long c = 1; c <= cap; ++c) {
-        double rounds = (double)((tiles * c + slots - 1) / slots);
-        double cost = rounds / (double)c * (1.0 + 0.004 * (double)c);
-        if (cost < best - 1e-12) {
-            best = cost;
-            ns = c;
-        }
-    }
+    long long ns = wgrad_pick_splits(tiles, M, p.kp);
     long long pps = ((M + ns - 1) / ns + p.kp - 1) / p.kp * p.kp;
     ns = (M + pps - 1) / pps;
     p.nsplit = (int)ns;
@@ -969,12 +1042,12 @@ int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st) {
     return MCAMD_OK;
 }
 
-template <int KK>
+template <int KK, bool SEL = false>
 static void launch_finish_vec(int sg, long long total, const float* slab, const WgradPlan& p, int ktot, int cin_tap, int Cout,
                               int Cin, const float* mask, float inv_scale, float* dw, const int* rmap, const int* cmap,
                               hipStream_t st) {
-#define F_CASE(SG_)                                                                                               \
-    hipLaunchKernelGGL((wgrad_finish_vec_kernel<KK, SG_>), dim3((unsigned)((total + 256 / SG_ - 1) / (256 / SG_))), \
+#define F_CASE(SG_)                                                                                                    \
+    hipLaunchKernelGGL((wgrad_finish_vec_kernel<KK, SG_, SEL>), dim3((unsigned)((total + 256 / SG_ - 1) / (256 / SG_))), \
                        dim3(256), 0, st, slab, p.nsplit, p.rows_pad, ktot, cin_tap, Cout, Cin, mask, inv_scale, dw, rmap, cmap)
     if (sg == 1) F_CASE(1);
     else if (sg == 8) F_CASE(8);
@@ -993,10 +1066,18 @@ WgradFinish mcamd_wgrad_finish_pick(int nsplit, int stem, int Cin, int ksize, bo
 
 int mcamd_wgrad_finish_launch(const float* slab, const WgradPlan& p, int ktot, int cin_tap, int stem, int Cout, int Cin,
                               int ksize, const float* mask, float inv_scale, float* dw, const int* rmap, const int* cmap,
-                              hipStream_t st) {
+                              hipStream_t st, bool select) {
     const WgradFinish f = mcamd_wgrad_finish_pick(p.nsplit, stem, Cin, ksize, cmap != nullptr);
     const int sg = f.sg;
-    if (f.kernel == MCAMD_WFIN_ROW) {
+    if (select) {     // the list launch: the vector kernel's select form (wgrad_finish_vec_kernel<.., SEL>), a mask and no maps
+        if (f.kernel != MCAMD_WFIN_VEC || !mask || rmap || cmap) {
+            mcamd_set_error("wgrad_finish: the select form takes the vector kernel with a mask and without channel maps");
+            return MCAMD_EINVAL;
+        }
+        long long total = (long long)Cout * (Cin / 4);
+        if (ksize == 3) launch_finish_vec<9, true>(sg, total, slab, p, ktot, cin_tap, Cout, Cin, mask, inv_scale, dw, rmap, cmap, st);
+        else launch_finish_vec<1, true>(sg, total, slab, p, ktot, cin_tap, Cout, Cin, mask, inv_scale, dw, rmap, cmap, st);
+    } else if (f.kernel == MCAMD_WFIN_ROW) {
         const size_t lds = (size_t)Cin * ksize * ksize * sizeof(float);
         if (ksize == 3)
             hipLaunchKernelGGL(wgrad_finish_row_kernel<9>, dim3(Cout), dim3(256), lds, st, slab, p.nsplit, p.rows_pad, ktot,
@@ -1019,6 +1100,156 @@ int mcamd_wgrad_finish_launch(const float* slab, const WgradPlan& p, int ktot, i
 #undef S_CASE
     }
     MCAMD_LAUNCH_CHECK("wgrad_finish");
+    return MCAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The list launch (mcamd_conv_wgrad_bsparse): for a block mask the zero blocks of dW are OUTPUT tiles of the
+// two 64 x 64 kernels -- a block of 64 filters x 64 input channels x one tap is one tap of a wgrad9_kernel tile, or a whole
+// tile of wgrad_kernel<64, 64, 1, 64> -- so they are dropped before they are computed: a tile list in ascending tile index,
+// for the 3x3 kernel a 9-bit tap word per listed tile, and the finish pass's select form for everything that was skipped.
+// ---------------------------------------------------------------------------------------
+// One workgroup per (ot, ct) tile: bit t of raw[tile] is set iff any mask element of filters [64 ot, 64 ot + 64) x channels
+// [64 ct, 64 ct + 64) x tap t is non-zero (-0 counts as zero, as in the finish pass's select).  OIHW: a filter's part of the
+// tile is 64 * KK contiguous floats.
+template <int KK>
+__global__ __launch_bounds__(256) void wgrad_bs_words_kernel(const float* mask, int cin, int n_ctiles, int* raw) {
+    __shared__ int word;
+    const int tile = blockIdx.x, ot = tile / n_ctiles, ct = tile - ot * n_ctiles;
+    if (threadIdx.x == 0) word = 0;
+    __syncthreads();
+    int bits = 0;
+    for (int e = threadIdx.x; e < 64 * 64 * KK; e += 256) {
+        const int r = e / (64 * KK), q = e - r * (64 * KK);
+        if (mask[((long long)(ot * 64 + r) * cin + ct * 64) * KK + q] != 0.f) bits |= 1 << (q % KK);
+    }
+    if (bits) atomicOr(&word, bits);        // (an integer OR in LDS: any order gives the same word)
+    __syncthreads();
+    if (threadIdx.x == 0) raw[tile] = word;
+}
+
+// One workgroup: the tiles with a non-zero word, ascending, with their words; counts[0] = kept tiles, counts[1] = kept
+// (tile, tap) pairs.  Entries behind the count are written as 0.  A block scan per 256 tiles: no atomics.
+__global__ __launch_bounds__(256) void wgrad_bs_compact_kernel(const int* raw, int nt, int* tiles, int* words, int* counts) {
+    __shared__ int scan[256];
+    int base = 0, pairs = 0;
+    for (int i0 = 0; i0 < nt; i0 += 256) {
+        const int i = i0 + threadIdx.x;
+        const int w = i < nt ? raw[i] : 0;
+        scan[threadIdx.x] = w != 0;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {
+            const int v = (int)threadIdx.x >= o ? scan[threadIdx.x - o] : 0;
+            __syncthreads();
+            scan[threadIdx.x] += v;
+            __syncthreads();
+        }
+        if (w != 0) {
+            tiles[base + scan[threadIdx.x] - 1] = i;
+            words[base + scan[threadIdx.x] - 1] = w;
+        }
+        pairs += __popc((unsigned)w);
+        base += scan[255];
+        __syncthreads();
+    }
+    for (int i = base + threadIdx.x; i < nt; i += 256) tiles[i] = 0, words[i] = 0;
+    scan[threadIdx.x] = pairs;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) scan[threadIdx.x] += scan[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) counts[0] = base, counts[1] = scan[0];
+}
+
+// tiles[nt], words[2 nt] (the compacted words in front, the word of EVERY tile behind them), counts[2]
+int mcamd_wgrad_bsparse_lists_launch(const float* mask, int cout, int cin, int kk, int* tiles, int* words, int* counts,
+                                     hipStream_t st) {
+    const int n_ctiles = cin / 64, nt = (cout / 64) * n_ctiles;
+    int* raw = words + nt;
+    if (kk == 9) hipLaunchKernelGGL(wgrad_bs_words_kernel<9>, dim3(nt), dim3(256), 0, st, mask, cin, n_ctiles, raw);
+    else hipLaunchKernelGGL(wgrad_bs_words_kernel<1>, dim3(nt), dim3(256), 0, st, mask, cin, n_ctiles, raw);
+    hipLaunchKernelGGL(wgrad_bs_compact_kernel, dim3(1), dim3(256), 0, st, (const int*)raw, nt, tiles, words, counts);
+    MCAMD_LAUNCH_CHECK("wgrad_bsparse_lists");
+    return MCAMD_OK;
+}
+
+bool mcamd_wgrad_bsparse_ok(int ksize, int stem, int cout, int cin, int W) {
+    if (stem || (ksize != 1 && ksize != 3) || cin % 64 || cout % 64) return false;
+    return ksize == 1 || mcamd_wgrad_use9(ksize, stem, cout, cin, W);
+}
+
+// The plan of a list launch of `kept_tiles` tiles: always the 64 x 64 tile (3x3: wgrad9_kernel<KP>, never the wide form;
+// 1x1: wgrad_kernel<64, 64, 1, 64>).  nsplit == 0: the dense plans' cost rule on the kept tile count; nsplit > 0: that many
+// splits (a launch on full lists at the split count of the short ones).  pix_per_split follows from nsplit alone.
+WgradPlan mcamd_wgrad_bsparse_plan(int ksize, long long M, long long P, int cout, int cin, int pitch, int kept_tiles, int nsplit) {
+    WgradPlan p;
+    memset(&p, 0, sizeof(p));
+    p.tmo = p.tnc = 64;
+    p.rows_pad = cout;
+    p.n_otiles = cout / 64;
+    p.n_ctiles = cin / 64;
+    p.n_tapgroups = 1;
+    const long long tiles = kept_tiles > 0 ? kept_tiles : 1;
+    if (ksize == 3) {
+        p.nine = 1;
+        p.taps = 9;
+        p.kp = wgrad9_kp(pitch);
+        p.ns = 2;
+        const long long nsteps = (P + 31) / 32, u = p.kp / 32;   // in 32-pixel units
+        long long ns = nsplit > 0 ? nsplit : wgrad9_pick_splits(tiles, nsteps, 512);
+        long long sps = ((nsteps + ns - 1) / ns + u - 1) / u * u;      // whole steps of kp pixels per split
+        if (nsplit <= 0) ns = (nsteps + sps - 1) / sps;
+        p.nsplit = (int)ns;
+        p.pix_per_split = (int)(sps * 32);
+    } else {
+        p.taps = 1;
+        p.kp = pick_kp(64, 64, 1);
+        p.ns = wgrad_ring(64, 64, 1, p.kp);
+        long long ns = nsplit > 0 ? nsplit : wgrad_pick_splits(tiles, M, p.kp);
+        const long long pps = ((M + ns - 1) / ns + p.kp - 1) / p.kp * p.kp;
+        if (nsplit <= 0) ns = (M + pps - 1) / pps;
+        p.nsplit = (int)ns;
+        p.pix_per_split = (int)pps;
+    }
+    p.bytes = (size_t)p.nsplit * p.rows_pad * ((size_t)ksize * ksize * cin) * sizeof(float);
+    return p;
+}
+
+int mcamd_wgrad_bsparse_launch(WgradArgs& w, const WgradPlan& p, int pitch, long long P, const int* tiles, const int* words,
+                               int ntiles, hipStream_t st) {
+    const int grid = round_up_int(ntiles * p.nsplit, 8);
+    if (p.nine == 1 && (p.kp == 64 || p.kp == 32)) {
+        Wgrad9Args a = wgrad9_args(w, p, pitch, P);
+        a.tile_list = tiles;
+        a.tap_words = words;
+        a.n_list = ntiles;
+        const size_t lds = wgrad9_lds(p.kp, a.S);
+        if (p.kp == 64) {
+            if (lds > 64 * 1024) MCAMD_LDS_OPT_IN((wgrad9_kernel<64, true>), 72 * 1024);
+            hipLaunchKernelGGL((wgrad9_kernel<64, true>), dim3(grid), dim3(256), lds, st, a);
+        } else {
+            if (lds > 64 * 1024) MCAMD_LDS_OPT_IN((wgrad9_kernel<32, true>), 160 * 1024);
+            hipLaunchKernelGGL((wgrad9_kernel<32, true>), dim3(grid), dim3(256), lds, st, a);
+        }
+    } else if (p.nine == 0 && p.tmo == 64 && p.tnc == 64 && p.taps == 1 && p.kp == 64) {
+        w.rows_pad = p.rows_pad;
+        w.n_ctiles = p.n_ctiles;
+        w.n_otiles = p.n_otiles;
+        w.n_tapgroups = p.n_tapgroups;
+        w.nsplit = p.nsplit;
+        w.pix_per_split = p.pix_per_split;
+        w.tile_list = tiles;
+        w.n_list = ntiles;
+        constexpr int NS = wgrad_ring(64, 64, 1, 64);
+        constexpr size_t lds = NS * wgrad_stage(64, 64, 1, 64);
+        static_assert(lds <= 64 * 1024, "no LDS opt-in needed");
+        hipLaunchKernelGGL((wgrad_kernel<64, 64, 1, 64, NS, true>), dim3(grid), dim3(256), lds, st, w);
+    } else {
+        mcamd_set_error("wgrad_bsparse: no list instance for form %d tile %dx%d taps %d kp %d", p.nine, p.tmo, p.tnc, p.taps, p.kp);
+        return MCAMD_EINVAL;
+    }
+    MCAMD_LAUNCH_CHECK("wgrad_bsparse");
     return MCAMD_OK;
 }
 

@@ -86,6 +86,8 @@ struct WgradArgs {
     int n_ctiles;     // cin tiles per tap
     int n_otiles, n_tapgroups, nsplit;
     int pix_per_split;
+    const int* tile_list;   // list launch (mcamd_conv_wgrad_bsparse): the tile indices ot * n_ctiles + ct to run, n_list of them
+    int n_list;
 };
 
 struct WgradPlan {
@@ -214,7 +216,13 @@ WgradFinish mcamd_wgrad_finish_pick(int nsplit, int stem, int Cin, int ksize, bo
 int mcamd_wgrad_instances(int (*out)[4], int cap);   // the (TMo, TNc, TAPS, KP) of every wgrad_kernel instance; returns their number
 int mcamd_wgrad_finish_launch(const float* slab, const WgradPlan& p, int ktot, int cin_tap, int stem, int Cout, int Cin,
                               int ksize, const float* mask, float inv_scale, float* dw, const int* rmap, const int* cmap,
-                              hipStream_t st);
+                              hipStream_t st, bool select = false);
+// the list launch of the two 64 x 64 kernels (mcamd_conv_wgrad_bsparse): `nsplit` 0 asks the cost rule for `kept_tiles` tiles
+bool mcamd_wgrad_bsparse_ok(int ksize, int stem, int cout, int cin, int W);
+WgradPlan mcamd_wgrad_bsparse_plan(int ksize, long long M, long long P, int cout, int cin, int pitch, int kept_tiles, int nsplit);
+int mcamd_wgrad_bsparse_lists_launch(const float* mask, int cout, int cin, int kk, int* tiles, int* words, int* counts, hipStream_t st);
+int mcamd_wgrad_bsparse_launch(WgradArgs& a, const WgradPlan& p, int pitch, long long P, const int* tiles, const int* words,
+                               int ntiles, hipStream_t st);
 int mcamd_colsum_launch(const half_t* dy, long long rows, int ld, int choff, int C, float inv_scale, float* out,
                         hipStream_t st, void* scratch, size_t scratch_bytes);   // scratch: reusable once the finish pass is enqueued
 

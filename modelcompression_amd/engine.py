@@ -63,6 +63,10 @@ _LAYER_FIELDS = dict(
     # the training form of the block-sparse kernel (form "bsparse_train"): its statistics slab (one row per pixel tile), the
     # chunk lists over the dgrad packing, whether the dgrad launch takes it too, and full lists (Engine.bsparse_train_full_lists)
     bs_stats=None, bs_dcount=None, bs_dlist=None, bs_dgrad=False, bs_full=None,
+    # ... and its weight gradient on tile lists (Darknet.sparse_train = "block-wgrad"): the lists built from the
+    # mask when the policy ran with their two counters as host integers (kept tiles, kept (tile, tap) pairs), whether the
+    # launch takes them, its split count and workspace bytes, and full lists at that split count
+    bw_tiles=None, bw_words=None, bw_dev_counts=None, bw_counts=None, bw_on=False, bw_nsplit=0, bw_bytes=0, bw_full=None,
     # fp8: launch geometry on the byte buffer, byte destinations, private input copy, packed operands; "fp8-qat" training:
     # the fp32 raw output + statistics that stand in for the fp16 ones, and the values the weight bytes stand for
     geom_q8=None, q8_y=False, q8_y2=False, xq=None, _xq=None, _xq_key=None, wq=None, wqs=None, widx8=None, wexp=None,
@@ -154,6 +158,15 @@ Q8_BSPARSE_MAX_KEPT = 0.375
 # (worst launch 1.11x, conv21's dgrad; at 0.5 conv9's dgrad loses 3 %).  The rule looks at the launches it replaces: the two list
 # launches per chosen block and step (0.9 ms per step in all) are not in it -- the whole step only gains below kept 0.3.
 BSPARSE_TRAIN_MAX_KEPT = 0.375
+# Darknet.sparse_train = "block-wgrad": a block that trains on the block-sparse kernel also sends its weight gradient through
+# the list launch (mcamd_conv_wgrad_bsparse) when the kept fraction of its (64 x 64 tile, tap) pairs is at most
+# this -- the default of Darknet.sparse_train_wgrad_max_kept.  The rule of DESIGN.md 3t on tools/bsparse_train_bench.py
+# (profiles/bsparse_train_wgrad_bench.json): the largest measured kept level at which the list launch of EVERY chosen layer of
+# conv9 .. conv22 is at least 10 % faster than the dense weight-gradient launch it replaces; 0.0: no level passes.
+# Measured at B = 64: 0.1 (worst layer 1.15x, conv18; at 0.25 the 13x13 3x3 layers lose 2-18 %: a 9-tap tile stages its whole
+# window for however few taps it keeps, and nearly every tile keeps some).  Whole step at kept 0.1: dense 9.15, "block" 7.89,
+# "block-wgrad" 7.13 ms.  A block_prune level of 90 % leaves layers at 0.100 .. 0.125: a caller who wants them all sets 0.125.
+BSPARSE_TRAIN_WGRAD_MAX_KEPT = 0.1
 
 
 class _Dense:
@@ -263,9 +276,12 @@ class _BSparseTrain(_BSparse):
     order is the forward's over cout_p -- for the dgrad launch.  Both lists are rebuilt behind every re-pack."""
     fwd = None                           # (no fused inference launch: an eval pass chooses its forms by Darknet.sparse)
 
-    def policy(self, eng, max_kept):
+    def policy(self, eng, max_kept, wgrad=False):
         """_BSparse.policy for the training step: the candidates are the masked inner blocks the training launches accept
-        (Engine._bst_eligible); planned once while the masks are static (pack caches the answer by the mask keys)."""
+        (Engine._bst_eligible); planned once while the masks are static (pack caches the answer by the mask keys).
+        `wgrad` ("block-wgrad"): the tile lists of the weight gradient's list launch are built here too, from the MASK of
+        every candidate whose geometry mcamd_conv_wgrad_bsparse_ok accepts, and their two counters come back in the same
+        host read: a step never builds them, and never reads anything back (Engine._choose_bst_wgrad decides from them)."""
         def masked(lay):
             m = lay.conv.mask if lay.conv.mask_flag else None
             return m is not None and m.is_cuda and m.dtype == torch.float32 and m.shape == lay.conv.weight.shape
@@ -274,11 +290,24 @@ class _BSparseTrain(_BSparse):
         for lay in cand:
             wp, _ = ops.pack_weights(lay.geom, lay.conv.weight.data, lay.conv.mask.contiguous(), want_dgrad=False)
             sums.append(ops.bsparse_lists(lay.geom, wp)[0].sum())
+        for lay in eng.layers:
+            lay.bw_counts, lay.bw_full = None, None
+        wcand = [lay for lay in cand if wgrad and ops.conv_wgrad_bsparse_ok(lay.geom)]
+        for lay in wcand:
+            nt, nw = ops.wgrad_bsparse_elems(lay.geom)
+            if lay.bw_tiles is None or lay.bw_tiles.numel() != nt:
+                lay.bw_tiles = torch.zeros(nt, dtype=torch.int32, device=eng.device)
+                lay.bw_words = torch.zeros(nw, dtype=torch.int32, device=eng.device)
+                lay.bw_dev_counts = torch.zeros(2, dtype=torch.int32, device=eng.device)
+            ops.wgrad_bsparse_lists(lay.geom, lay.conv.mask.contiguous(), lay.bw_tiles, lay.bw_words, lay.bw_dev_counts)
+        host = (torch.cat([torch.stack(sums)] + [lay.bw_dev_counts.long() for lay in wcand]).cpu().tolist() if cand else [])
         chosen, kept = [], {}
-        for lay, s_ in zip(cand, torch.stack(sums).cpu().tolist() if cand else []):
+        for lay, s_ in zip(cand, host):
             kept[lay.li + 1] = s_ / float(ops.bsparse_elems(lay.geom)[1])       # conv number (conv1 = the first block)
             if kept[lay.li + 1] <= max_kept:
                 chosen.append(lay.li)
+        for i, lay in enumerate(wcand):
+            lay.bw_counts = tuple(host[len(cand) + 2 * i:len(cand) + 2 * i + 2])
         return frozenset(chosen), kept
 
     def alloc(self, eng, lays):
@@ -322,6 +351,17 @@ class _BSparseTrain(_BSparse):
         count, lst = self.full(eng, lay)[2:] if eng.bsparse_train_full_lists else (lay.bs_dcount, lay.bs_dlist)
         eng._timed('dgrad', lay, ops.conv_dgrad_bsparse, lay.geom_act, lay.dy, lay.cout_p, 0, lay.wd, count, lst, lay.gin,
                    lay.tin.ld, lay.tin.choff, overflow=eng.overflow, concurrent=concurrent)
+
+    def wgrad(self, eng, lay, gw, mask, D, dbias, ws):
+        """The weight gradient of a block on the list launch (lay.bw_on, Engine._choose_bst_wgrad): the lists and the host
+        integers the policy left; under Engine.bsparse_train_full_lists every tile with every tap at the SAME split count."""
+        tiles, words, n = lay.bw_tiles, lay.bw_words, lay.bw_counts[0]
+        if eng.bsparse_train_full_lists:
+            if lay.bw_full is None:
+                lay.bw_full = ops.wgrad_bsparse_full_lists(lay.geom, eng.device)
+            (tiles, words), n = lay.bw_full, lay.bw_full[0].numel()
+        eng._timed('wgrad', lay, ops.conv_wgrad_bsparse, lay.geom, eng.bufs[lay.tin.buf], lay.dy, lay.cout_p, 0, gw, mask, tiles,
+                   words, n, lay.bw_nsplit, D, dbias, ws)
 
 
 class _Q8(_Dense):
@@ -597,6 +637,11 @@ class Engine:
         self.bsparse_train_kept = {}
         self._bst_policy = None
         self._bst_full = False
+        # ... "block-wgrad" (DESIGN.md 3zd): conv numbers of the chosen blocks whose weight gradient runs the list launch
+        # mcamd_conv_wgrad_bsparse, and the kept (tile, tap) fraction of every candidate (_choose_bst_wgrad)
+        self.bsparse_train_wgrad_layers = []
+        self.bsparse_train_wgrad_kept = {}
+        self._bst_wgrad_key = None
         # split-K low-batch inference (Darknet.splitk, plain-fp16 eval engines only): conv numbers of the blocks that run
         # mcamd_conv_fwd_splitk, chosen when the flag or the masks change (_choose_forms); one workspace for all of them
         self.splitk_layers = []
@@ -1055,10 +1100,11 @@ class Engine:
             sig.append((w.data_ptr(), w._version, None if m is None else (m.data_ptr(), m._version), bnv))
         return tuple(sig)
 
-    def pack(self, force=False, training=True, sparse=None, splitk=False, max_kept=None):
+    def pack(self, force=False, training=True, sparse=None, splitk=False, max_kept=None, wgrad_max_kept=None):
         """fp32 master * mask -> fp16 kernel layouts (replaces layers.py:59's per-forward multiply).
         `sparse`, `splitk`, `max_kept`: the inference options forward() validated (Darknet.sparse / splitk /
-        sparse_max_kept; off in training mode); every block's form is chosen again when they or the masks change."""
+        sparse_max_kept; off in training mode); every block's form is chosen again when they or the masks change.
+        `wgrad_max_kept` (sparse = "block-train" only; None: off): Darknet.sparse_train = "block-wgrad"."""
         if any(lay.fold is not None for lay in self.layers) and training != self._training:
             force = True          # the folded constants differ between batch and running statistics
         self._training = training
@@ -1081,14 +1127,21 @@ class Engine:
         if sparse == "block":
             exempt, self.bsparse_kept = _FORMS["bsparse"].policy(self, max_kept)
         elif sparse == "block-train":       # (Darknet.sparse_train; re-packed every step: one host read per set of masks)
-            if self._bst_policy is None or self._bst_policy[0] != (mkeys, max_kept):
-                self._bst_policy = ((mkeys, max_kept),) + _FORMS["bsparse_train"].policy(self, max_kept)
+            pkey = (mkeys, max_kept) + ((True,) if wgrad_max_kept is not None else ())
+            if self._bst_policy is None or self._bst_policy[0] != pkey:
+                self._bst_policy = (pkey,) + _FORMS["bsparse_train"].policy(self, max_kept, wgrad=wgrad_max_kept is not None)
             exempt, self.bsparse_train_kept = self._bst_policy[1:]
         elif self.q8_bsparse and max_kept is not None:
             exempt, self.fp8_block_kept = _FORMS["q8_bsparse"].policy(self, max_kept)
         key = (mkeys, exempt, sparse, max_kept, splitk)
         if key != self._form_key:          # masks are static during retraining: planned once
             self._choose_forms(key)
+        # (the list weight gradient follows the forms: chosen again when they, the masks -- part of the form key -- or its
+        # bound change, from the counters the policy read; None in every mode but "block-wgrad")
+        wkey = (key, wgrad_max_kept) if sparse == "block-train" and wgrad_max_kept is not None else None
+        if wkey != self._bst_wgrad_key:
+            self._choose_bst_wgrad(None if wkey is None else wgrad_max_kept)
+            self._bst_wgrad_key = wkey
         # geom_act / g_rows / g_cols: physical channel order (kept filters first, permuted inputs); identity = None.
         # Split-operand engines: forward = fp16 of [w_hi | w_hi | w_lo] along the input channels (w_hi = fp16(w * mask),
         # w_lo = fp16(w * mask - w_hi)), matching the [x_hi | x_lo | x_hi] activation planes, written by the one-launch
@@ -1213,6 +1266,34 @@ class Engine:
         if bool(on) != self._bst_full:
             self._bst_full = bool(on)
             self._plan_epoch += 1            # recorded plans hold the lists' addresses
+
+    def _choose_bst_wgrad(self, bound):
+        """Which blocks send their weight gradient through the list launch (Darknet.sparse_train = "block-wgrad", DESIGN.md
+        3zd), behind _choose_forms and from the counters _BSparseTrain.policy read: no launch and no host read here.  A block
+        is chosen when it took form "bsparse_train", has no gather, perm or fold, is not on the one-launch 1x1 backward, its
+        geometry has a list launch and its kept (tile, tap) fraction is at most `bound`.  The split count of each plan and the
+        split-K workspaces (this stream's and the second one's) are settled here.  bound None: nothing is chosen."""
+        self._plan_epoch += 1
+        chosen, kept, wbytes = [], {}, 0
+        for lay in self.layers:
+            lay.bw_on = False
+            if bound is None or lay.bw_counts is None:
+                continue
+            ntiles, npairs = lay.bw_counts
+            kept[lay.li + 1] = npairs / float(ops.wgrad_bsparse_elems(lay.geom)[0] * lay.k * lay.k)
+            if (lay.form == "bsparse_train" and not lay.gather and lay.perm is None and lay.fold is None
+                    and not self._bwd1x1_route(lay) and kept[lay.li + 1] <= bound):
+                plan = ops.conv_wgrad_bsparse_plan(lay.geom, ntiles)
+                lay.bw_on, lay.bw_nsplit, lay.bw_bytes = True, plan.nsplit, plan.bytes
+                wbytes = max(wbytes, plan.bytes)
+                chosen.append(lay.li + 1)
+        if wbytes > self.wgrad_ws.numel():
+            self.wgrad_ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+        if self._side_ws is not None and self._side_ws.numel() < self.wgrad_ws.numel():
+            self._side_ws = torch.empty(self.wgrad_ws.numel(), dtype=torch.uint8, device=self.device)
+            self._side_ws.record_stream(self._get_side_stream())
+        if self._training:
+            self.bsparse_train_wgrad_layers, self.bsparse_train_wgrad_kept = chosen, kept
 
     def _conforming(self, cand):
         """The blocks of `cand` whose mask keeps at most 2 of every 4 consecutive input channels at each (filter, tap):
@@ -1795,9 +1876,9 @@ class Engine:
                              "pick another precision for training" % (self.precision,))
         mode = None if training else getattr(self.model, "sparse", None)
         st = getattr(self.model, "sparse_train", None) if training else None
-        if st not in (None, "block"):
-            raise McamdError("sparse_train must be None or 'block' (got %r)" % (st,))
-        if st == "block" and self.precision != "fp16":
+        if st not in (None, "block", "block-wgrad"):
+            raise McamdError("sparse_train must be None, 'block' or 'block-wgrad' (got %r)" % (st,))
+        if st is not None and self.precision != "fp16":
             raise McamdError("sparse_train=%r trains in the plain-fp16 engine only (model.precision = 'fp16'), not precision=%r"
                              % (st, self.precision))
         if mode is not None and (self.precise or self.q8):
@@ -1816,10 +1897,14 @@ class Engine:
         max_kept = float(getattr(self.model, "sparse_max_kept", BSPARSE_MAX_KEPT)) if mode == "block" else None
         if self.q8_bsparse and not training:
             max_kept = float(getattr(self.model, "fp8_block_max_kept", Q8_BSPARSE_MAX_KEPT))
-        if st == "block" and float(getattr(self.model, "sparse_train_max_kept", BSPARSE_TRAIN_MAX_KEPT)) > 0.0:
+        wgrad_max = None
+        if st is not None and float(getattr(self.model, "sparse_train_max_kept", BSPARSE_TRAIN_MAX_KEPT)) > 0.0:
             # (a bound of 0.0 chooses nothing: the sparse_train = None engine, bit for bit)
             mode, max_kept = "block-train", float(getattr(self.model, "sparse_train_max_kept", BSPARSE_TRAIN_MAX_KEPT))
-        self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept)
+            if st == "block-wgrad" and float(getattr(self.model, "sparse_train_wgrad_max_kept", BSPARSE_TRAIN_WGRAD_MAX_KEPT)) > 0.0:
+                # (again 0.0 chooses nothing: sparse_train = "block", bit for bit, and no list is built)
+                wgrad_max = float(getattr(self.model, "sparse_train_wgrad_max_kept", BSPARSE_TRAIN_WGRAD_MAX_KEPT))
+        self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept, wgrad_max_kept=wgrad_max)
         self.serial += 1
         tin = self.layers[0].tin
         xs = x.detach().contiguous().float()
@@ -2324,6 +2409,9 @@ class Engine:
                         ops.memset_zero(gw)
                     self._timed('wgrad', lay, ops.conv_wgrad, lay.geom_act, self.bufs[lay.tin.buf], lay.dy, lay.cout_p, 0,
                                 gw, mask, D, dbias, ws, rows=lay.g_rows, cols=lay.g_cols)
+                elif lay.bw_on:
+                    # the tiles and taps the block mask keeps only (Darknet.sparse_train = "block-wgrad")
+                    _FORMS["bsparse_train"].wgrad(self, lay, gmap[id(lay.conv.weight)], mask, D, dbias, ws)
                 else:
                     self._timed('wgrad', lay, ops.conv_wgrad, lay.geom, self.bufs[lay.tin.buf], lay.dy, lay.cout_p, 0,
                                 gmap[id(lay.conv.weight)], mask, D, dbias, ws)

@@ -341,9 +341,16 @@ class Darknet(nn.Module):
         # them.  The weight gradient stays dense.  Training-mode passes with precision "fp16" only -- any other training
         # precision raises; eval ignores it (`sparse` is the eval switch, and training keeps ignoring that one).  A bound of
         # 0.0, or a model without masks, is the engine of sparse_train = None bit for bit.
+        # "block-wgrad"  does everything "block" does and also sends the weight gradient of the chosen blocks
+        # that are neither compacted nor on the one-launch 1x1 backward through the list launch mcamd_conv_wgrad_bsparse when
+        # the kept fraction of their (64 x 64 tile, tap) pairs is at most `sparse_train_wgrad_max_kept`
+        # (engine.Engine.bsparse_train_wgrad_layers / bsparse_train_wgrad_kept): masked tiles and taps are never computed and
+        # their gradient is exactly 0.  The lists come from the masks when the masks change, never per step.  A bound of 0.0
+        # is "block" bit for bit.
         self.sparse_train = None
-        from .engine import BSPARSE_TRAIN_MAX_KEPT
+        from .engine import BSPARSE_TRAIN_MAX_KEPT, BSPARSE_TRAIN_WGRAD_MAX_KEPT
         self.sparse_train_max_kept = BSPARSE_TRAIN_MAX_KEPT      # the measured policy constant (engine.py)
+        self.sparse_train_wgrad_max_kept = BSPARSE_TRAIN_WGRAD_MAX_KEPT      # ... and the weight gradient's
         # Low-batch inference (an addition beyond the reference): True runs every block whose forward launch would leave most
         # CUs idle -- the 13x13 and 26x26 layers at B = 1 -- as a split-K pair (csrc/conv_splitk.hip, DESIGN.md 3p,
         # engine.Engine.splitk_layers); batches the policy does not split run exactly what they run without it.  Eval with

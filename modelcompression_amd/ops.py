@@ -298,6 +298,70 @@ def conv_wgrad(g, x, dy, dy_ld, dy_choff, dw, mask=None, grad_scale=1.0, dbias=N
                                    ptr(dbias), ptr(workspace), workspace.numel(), stream_ptr()), "mcamd_conv_wgrad")
 
 
+# ... its list launch: the tiles and taps a block mask keeps (Darknet.sparse_train = "block-wgrad")
+def conv_wgrad_bsparse_ok(g):
+    """Does conv_wgrad_bsparse accept this geometry?  Needs no GPU."""
+    return bool(L.lib().mcamd_conv_wgrad_bsparse_ok(C.byref(g)))
+
+
+def wgrad_bsparse_elems(g):
+    """(nt, 2 nt): int32 entries of the tile list and of the tap words, nt = (cout / 64) * (cin / 64)."""
+    out = (C.c_int64 * 2)()
+    check(L.lib().mcamd_wgrad_bsparse_elems(C.byref(g), out), "mcamd_wgrad_bsparse_elems")
+    return int(out[0]), int(out[1])
+
+
+def wgrad_bsparse_lists(g, mask, tiles=None, words=None, counts=None):
+    """fp32 OIHW mask -> (tiles int32[nt], words int32[2 nt], counts int32[2]): the 64 x 64 tiles with any non-zero mask
+    element, ascending, their tap words, and (kept tiles, kept (tile, tap) pairs): mcamd_wgrad_bsparse_lists; no host
+    synchronisation."""
+    _need_cuda(mask)
+    nt, nw = wgrad_bsparse_elems(g)
+    if mask.dtype != torch.float32 or not mask.is_contiguous() or mask.numel() != g.cout * g.cin * g.ksize * g.ksize:
+        raise L.McamdError("wgrad_bsparse_lists: mask must be contiguous fp32 OIHW of the geometry's shape")
+    tiles = torch.empty(nt, dtype=torch.int32, device=mask.device) if tiles is None else tiles
+    words = torch.empty(nw, dtype=torch.int32, device=mask.device) if words is None else words
+    counts = torch.empty(2, dtype=torch.int32, device=mask.device) if counts is None else counts
+    if tiles.numel() != nt or words.numel() != nw or counts.numel() != 2:
+        raise L.McamdError("wgrad_bsparse_lists: list sizes do not fit the geometry")
+    check(L.lib().mcamd_wgrad_bsparse_lists(C.byref(g), ptr(mask), ptr(tiles), ptr(words), ptr(counts), stream_ptr()),
+          "mcamd_wgrad_bsparse_lists")
+    return tiles, words, counts
+
+
+def wgrad_bsparse_full_lists(g, device):
+    """(tiles, words) naming every tile with every tap: what a full-list launch runs on."""
+    nt, nw = wgrad_bsparse_elems(g)
+    return (torch.arange(nt, dtype=torch.int32, device=device),
+            torch.full((nw,), 0x1ff if g.ksize == 3 else 1, dtype=torch.int32, device=device))
+
+
+WgradBsparsePlan = collections.namedtuple("WgradBsparsePlan", "family kp ns nsplit pix_per_split finish sg bytes")
+
+
+def conv_wgrad_bsparse_plan(g, kept_tiles):
+    """What conv_wgrad_bsparse runs for `kept_tiles` listed tiles (mcamd_conv_wgrad_bsparse_plan).  Needs no GPU."""
+    out = (C.c_int64 * L.WGRAD_BSPARSE_PLAN_N)()
+    check(L.lib().mcamd_conv_wgrad_bsparse_plan(C.byref(g), int(kept_tiles), out), "mcamd_conv_wgrad_bsparse_plan")
+    return WgradBsparsePlan(*(int(v) for v in out))
+
+
+def conv_wgrad_bsparse(g, x, dy, dy_ld, dy_choff, dw, mask, tiles, words, ntiles, nsplit, grad_scale=1.0, dbias=None,
+                       workspace=None):
+    """conv_wgrad on the `ntiles` listed tiles (wgrad_bsparse_lists of the same mask) at `nsplit` pixel splits
+    (conv_wgrad_bsparse_plan(g, ntiles).nsplit; a full-list launch takes the short lists' split count).  `ntiles` and
+    `nsplit` are host integers: the launch never reads the counters back."""
+    nt, nw = wgrad_bsparse_elems(g)
+    _need_cuda(x, dy, mask, tiles, words)
+    if tiles.dtype != torch.int32 or words.dtype != torch.int32 or tiles.numel() < ntiles or words.numel() < ntiles:
+        raise L.McamdError("conv_wgrad_bsparse: tiles / words must be int32 lists of at least %d entries" % ntiles)
+    if workspace is None:
+        workspace = torch.empty(nsplit * g.cout * g.cin * g.ksize * g.ksize * 4, dtype=torch.uint8, device=dw.device)
+    check(L.lib().mcamd_conv_wgrad_bsparse(C.byref(g), ptr(x), ptr(dy), dy_ld, dy_choff, ptr(mask), ptr(tiles), ptr(words),
+                                           int(ntiles), int(nsplit), grad_scale, ptr(dw), ptr(dbias), ptr(workspace),
+                                           workspace.numel(), stream_ptr()), "mcamd_conv_wgrad_bsparse")
+
+
 def conv_bwd1x1_ok(g):
     """(ok, reason): does `g` have the one-launch backward (mcamd_conv_bwd1x1)?  `reason` says why not.  Needs no GPU."""
     why = C.c_char_p()

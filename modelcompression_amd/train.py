@@ -50,7 +50,8 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
   * YOLOv2Train.SPARSE_TRAIN = "block" (an attribute; None by default: train() is what it was) sets Darknet.sparse_train on the
     model behind set_masks: with pruning_method "block" or "taylor-block" and the training precision "fp16", the forward and
     dgrad launches of the retraining steps skip the zeroed blocks of every layer whose kept fraction is at most the model's
-    default bound (engine.BSPARSE_TRAIN_MAX_KEPT).
+    default bound (engine.BSPARSE_TRAIN_MAX_KEPT).  SPARSE_TRAIN = "block-wgrad" also runs their weight
+    gradient on the tiles and taps the masks keep (engine.BSPARSE_TRAIN_WGRAD_MAX_KEPT).
 """
 import os
 
@@ -245,7 +246,8 @@ class YOLOv2Train():
     # None / "block": Darknet.sparse_train of the model train() builds, set behind set_masks (an attribute too).  "block" skips
     # the zero blocks of pruning_method "block" / "taylor-block" masks in the forward and dgrad launches of the fp16 training
     # step; it needs the training precision "fp16" (MCAMD_PRECISION) and, for blocks to be chosen, a bound
-    # Darknet.sparse_train_max_kept above the layers' kept fractions.
+    # Darknet.sparse_train_max_kept above the layers' kept fractions.  "block-wgrad"  also skips them in the
+    # weight gradient of the layers below Darknet.sparse_train_wgrad_max_kept.
     SPARSE_TRAIN = None
 
     def __init__(self):

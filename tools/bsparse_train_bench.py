@@ -9,7 +9,11 @@ included: the baseline) and sparse_train = "block" with every candidate chosen (
 From the table it derives engine.BSPARSE_TRAIN_MAX_KEPT by the rule of 3t: the largest kept fraction of a level at which BOTH
 the forward and the dgrad launch of every layer of conv9 .. conv22 are at least 10 % faster than the dense training launches
 they replace (0.0 when no level passes).
-usage: python tools/bsparse_train_bench.py [B] [STEPS] [--levels 50,75,90] [--json [PATH]]"""
+--wgrad adds the leg sparse_train = "block-wgrad" (sparse_train_wgrad_max_kept = 1.0: every candidate's weight
+gradient on the list launch), alternated with the other two in the same process, and reports per layer the weight-gradient
+launch of the "block" leg (dense: compute + finish + dbias) against the list launch, the three whole steps, and
+engine.BSPARSE_TRAIN_WGRAD_MAX_KEPT by the same rule on the weight-gradient launches (profiles/bsparse_train_wgrad_bench.json).
+usage: python tools/bsparse_train_bench.py [B] [STEPS] [--levels 50,75,90] [--json [PATH]] [--wgrad [PATH]]"""
 import json
 import os
 import sys
@@ -20,11 +24,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 POLICY_LAYERS = range(9, 23)
 POLICY_GAIN = 1.10
 LEGS = ("dense", "block")
+WGRAD_LEG = "block-wgrad"
 DEFAULT_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "bsparse_train_bench.json")
+DEFAULT_WGRAD_JSON = os.path.join(os.path.dirname(DEFAULT_JSON), "bsparse_train_wgrad_bench.json")
 
 
 def parse(argv):
-    levels, out_json, pos = [10.0, 25.0, 37.5, 50.0, 62.5, 75.0, 90.0], None, []
+    levels, out_json, wgrad_json, pos = [10.0, 25.0, 37.5, 50.0, 62.5, 75.0, 90.0], None, None, []
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -37,6 +43,12 @@ def parse(argv):
                 i += 1
             else:
                 out_json = DEFAULT_JSON
+        elif a == "--wgrad":
+            if i + 1 < len(argv) and not argv[i + 1].startswith("--") and not argv[i + 1].replace(".", "").isdigit():
+                wgrad_json = argv[i + 1]
+                i += 1
+            else:
+                wgrad_json = DEFAULT_WGRAD_JSON
         elif not a.startswith("--"):
             pos.append(a)
         i += 1
@@ -44,7 +56,24 @@ def parse(argv):
     K = int(pos[1]) if len(pos) > 1 else 30
     if B < 1 or K < 1 or not levels or not all(0.0 < v < 100.0 for v in levels):
         raise SystemExit("bsparse_train_bench: B and STEPS must be positive, levels percentages in (0, 100)")
-    return B, K, out_json, levels
+    return B, K, out_json, levels, wgrad_json
+
+
+def wgrad_policy(rows):
+    """rows: dicts(level, conv, kept, wgrad_dense_ms, wgrad_list_ms) -> (constant, per-level table): policy()'s rule on the
+    weight-gradient launch of every chosen layer of POLICY_LAYERS."""
+    table, const = {}, 0.0
+    for level in sorted({r["level"] for r in rows}):
+        pts = [(r["wgrad_dense_ms"] / r["wgrad_list_ms"], r["conv"], r["kept"]) for r in rows
+               if r["level"] == level and r["conv"] in POLICY_LAYERS]
+        if not pts:
+            continue
+        gain, worst, _ = min(pts)
+        kept = min(p[2] for p in pts)
+        table["%g" % level] = {"kept": kept, "min_gain": gain, "min_gain_conv": worst, "passes": gain >= POLICY_GAIN}
+        if gain >= POLICY_GAIN and kept > const:
+            const = kept
+    return const, table
 
 
 def median(v):
@@ -80,7 +109,8 @@ def policy(rows):
 
 
 def main(argv):
-    B, K, out_json, levels = parse(argv)
+    B, K, out_json, levels, wgrad_json = parse(argv)
+    LEGS = globals()["LEGS"] + ((WGRAD_LEG,) if wgrad_json else ())
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bsparse_train_bench needs the GPU")
@@ -90,7 +120,7 @@ def main(argv):
     dev = torch.device("cuda", 0)
     x = synthetic_batch(B, 416, 416, seed=0, device=dev)
     gout = torch.randn(B, 125, 13, 13, generator=torch.Generator().manual_seed(1)).to(dev) * 0.01
-    rows, wholes = [], []
+    rows, wholes, wrows, wwholes = [], [], [], []
 
     for level in levels:
         m = init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
@@ -98,10 +128,11 @@ def main(argv):
         m.train()
         m.precision = "fp16"
         m.sparse_train_max_kept = 1.0
+        m.sparse_train_wgrad_max_kept = 1.0
         opt = torch.optim.SGD(m.parameters(), lr=1e-6, momentum=0.9, weight_decay=5e-4, fused=True)
 
         def select(leg):
-            m.sparse_train = None if leg == "dense" else "block"
+            m.sparse_train = None if leg == "dense" else leg
 
         def engine():
             return [e for e in m._engines.values() if e.train_layout][0]
@@ -184,6 +215,28 @@ def main(argv):
                        "step_ms_median": {leg: median(step_ms[leg]) for leg in LEGS},
                        "step_spread_pct": {leg: spread(step_ms[leg]) for leg in LEGS}, "dense_over_block": pairs,
                        "launch_ms_sums": tot, "lists_ms_per_step": tot["block"]["lists"], "finite": finite})
+        if wgrad_json:
+            select(WGRAD_LEG)
+            step()
+            torch.cuda.synchronize()
+            eng = engine()
+            won, wkept = list(eng.bsparse_train_wgrad_layers), dict(eng.bsparse_train_wgrad_kept)
+            wfinite = all(bool(torch.isfinite(p).all()) for p in m.parameters())
+            print("weight gradient on the list launch (conv numbers): %s" % won)
+            print("%-6s %7s %9s %9s %6s   spread %% (dense / list)" % ("conv", "kept", "wgr d ms", "wgr l ms", "d/l"))
+            for k in won:
+                wd, wl = t["block"].get(("wgrad", k), 0.0), t[WGRAD_LEG].get(("wgrad", k), 0.0)
+                wrows.append({"level": level, "conv": k, "kept": wkept[k], "wgrad_dense_ms": wd, "wgrad_list_ms": wl,
+                              "spread_pct": [sp["block"].get(("wgrad", k), 0.0), sp[WGRAD_LEG].get(("wgrad", k), 0.0)]})
+                print("%-6s %7.3f %9.3f %9.3f %6.2f   %.1f / %.1f" % ("conv%d" % k, wkept[k], wd, wl, wd / wl if wl else 0.0,
+                                                                     wrows[-1]["spread_pct"][0], wrows[-1]["spread_pct"][1]))
+            print("pairs block / block-wgrad: %s; dense / block-wgrad: %s; parameters finite: %s\n"
+                  % (["%.3f" % (a / b) for a, b in zip(step_ms["block"], step_ms[WGRAD_LEG])],
+                     ["%.3f" % (a / b) for a, b in zip(step_ms["dense"], step_ms[WGRAD_LEG])], wfinite))
+            wwholes.append({"level": level, "wgrad_layers": won, "step_ms": step_ms,
+                            "step_ms_median": {leg: median(step_ms[leg]) for leg in LEGS},
+                            "step_spread_pct": {leg: spread(step_ms[leg]) for leg in LEGS},
+                            "wgrad_ms_sums": {leg: tot[leg]["wgrad"] for leg in LEGS}, "finite": wfinite})
         del m, opt, eng
         torch.cuda.empty_cache()
 
@@ -196,6 +249,16 @@ def main(argv):
             json.dump({"B": B, "steps_per_window": K, "levels": levels, "per_layer": True, "precision": "fp16", "layers": rows,
                        "whole_step": wholes, "policy_gain": POLICY_GAIN, "policy_layers": list(POLICY_LAYERS), "max_kept": const,
                        "levels_table": per}, f, indent=1)
+    if wgrad_json:
+        wconst, wper = wgrad_policy(wrows)
+        print("weight-gradient policy (conv9 .. conv22, the list launch of every chosen layer >= %.2f x the dense launch): max kept "
+              "%.3f; per level %s" % (POLICY_GAIN, wconst, {k: "%.3f: %.2f (conv%d)%s" % (v["kept"], v["min_gain"], v["min_gain_conv"],
+                                                                                        "" if v["passes"] else " -")
+                                                            for k, v in wper.items()}))
+        with open(wgrad_json, "w") as f:
+            json.dump({"B": B, "steps_per_window": K, "levels": levels, "per_layer": True, "precision": "fp16", "layers": wrows,
+                       "whole_step": wwholes, "policy_gain": POLICY_GAIN, "policy_layers": list(POLICY_LAYERS),
+                       "wgrad_max_kept": wconst, "levels_table": wper}, f, indent=1)
 
 
 if __name__ == "__main__":
