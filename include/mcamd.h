@@ -1064,7 +1064,8 @@ int mcamd_stem_block_plan_info(const mcamd_stem_block_desc* d, int32_t out[MCAMD
  * nets.py:720-774).
  * ------------------------------------------------------------------------- */
 /* src fp32 [B][C][H][W] * mul -> dst padded NHWC fp16 channels [choff, choff+C).  `overflow` (may be NULL): device
- * flag set to 1 when a value was clamped to +-65504 (the incoming logit gradient x grad_scale). */
+ * flag set to 1 when a value was clamped to +-65504 (the incoming logit gradient x grad_scale) -- and when the source
+ * value is not finite: +-inf is stored as +-65504 and a NaN as -65504, finite gradients that must not pass for real ones. */
 int mcamd_nchw_f32_to_padded_nhwc_f16(const float* src, int32_t B, int32_t C, int32_t H, int32_t W,
                                       float mul, void* dst, int32_t dst_ld, int32_t dst_choff, int32_t* overflow,
                                       void* stream);

@@ -942,8 +942,9 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* src, int
         half_t* d = dst + pad_off(b, h, w, H, W, ld, pw) + choff + c0;
         const float* s = src + ((long long)b * C + c0) * HW + rem;
         int nc = C - c0 < 8 ? C - c0 : 8;
+        // not "|v| > 65504": that is false for a NaN, which sat_half turns into -65504 -- a finite gradient without a flag
         if (overflow)
-            for (int i = 0; i < nc; ++i) sat |= fabsf(s[i * HW] * mul) > 65504.f;
+            for (int i = 0; i < nc; ++i) sat |= !(fabsf(s[i * HW] * mul) <= 65504.f);
         if (plane > 0) {  // split storage: hi | lo | hi planes, `plane` channels apart (mcamd_act_desc.planes)
             for (int i = 0; i < nc; ++i) {
                 const float v = s[i * HW] * mul;
