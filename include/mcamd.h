@@ -1702,6 +1702,55 @@ int64_t mcamd_taylor_seg_workgroups(const mcamd_taylor_seg* seg);
 int mcamd_taylor_accum(const mcamd_taylor_seg* segs, const mcamd_taylor_seg* segs_dev, int32_t nseg, const float* skip,
                        int32_t* steps, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Proximal group lasso (sparsify.GroupLasso; an addition beyond the reference; Wen et al. 2016,
+ * arXiv:1608.03665, for weight groups; Liu et al. 2017, arXiv:1708.06519, for BatchNorm gates): the proximal step of a
+ * group-lasso penalty, taken behind optimizer.step().  A group the loss does not need shrinks to exactly zero over the
+ * steps.  One launch over a segment table for the whole model, nothing read back, no atomics, every written element has
+ * one owner, every result a function of the operands alone.
+ * ------------------------------------------------------------------------- */
+/* A BLOCK segment is one conv weight, fp32 OIHW [cout][cin][khw], cin % 32 == 0.  Its groups are the blocks of
+ * mcamd_block_scores with that function's block index: filters [64 fb, min(64 fb + 64, cout)) x kb channels x one tap, kb = 64
+ * when cin % 64 == 0 else 32, index (fb * (cin / kb) + cb) * khw + tap.  For a block of n_g elements:
+ *   n2    the float64 sum of (double)w_i * (double)w_i (each product is exact) in that function's order: elements numbered
+ *         e = r * kb + c, lane l adds e = l, l + 64, ... in ascending order starting from 0.0, the 64 lane sums are
+ *         combined by s[l] += s[l ^ d], d = 32, 16, 8, 4, 2, 1
+ *   thr2  = tau2 * (double)n_g, one rounded multiply
+ *   n2 <= thr2:  every element of the block becomes +0.0f
+ *   otherwise:   s = 1.0 - sqrt(thr2 / n2) in float64 (one divide, one square root, one subtract), and
+ *                w_i = (float)((double)w_i * s)
+ * which is the proximal operator of lam * sqrt(n_g) * ||w_g||_2 at step lr when tau2 = (lr * lam)^2.  Non-finite values
+ * are not hidden: a block that holds an Inf keeps its values (n2 = Inf, s = 1), a block that holds a NaN becomes NaN
+ * (n2 <= thr2 is false, s is NaN).  nz (int32 [blocks], or NULL = not written): 0 when n2 <= thr2, else 1.
+ * A GATE segment is one BatchNorm weight, fp32 [cout], cin = khw = 1:
+ *   a = fabsf(gamma) - tau_gate, one fp32 subtract; gamma = copysignf(a, gamma) when a > 0, +0.0f when a <= 0, and
+ *   gamma is left alone when a is NaN.  nz (int32 [cout] or NULL): 0 when a <= 0, else 1.
+ * No |w| and no |gamma| grows.  All arrays are 4-byte aligned (checked).  tests/gprox_ref.py restates this in numpy. */
+#define MCAMD_GPROX_BLOCK 0
+#define MCAMD_GPROX_GATE 1
+typedef struct mcamd_gprox_seg {
+    void* w;        /* block: weights; gate: gamma.  Read and written */
+    void* nz;       /* int32, one entry per group; NULL = not wanted */
+    int64_t wg0;    /* running sum over the table of mcamd_gprox_seg_workgroups (checked) */
+    int32_t kind;   /* MCAMD_GPROX_BLOCK / MCAMD_GPROX_GATE */
+    int32_t cout;   /* gate: channels */
+    int32_t cin;    /* gate: 1 */
+    int32_t khw;    /* gate: 1 */
+} mcamd_gprox_seg;
+
+/* workgroups the launch spends on one segment (wg0 is ignored); 0 for a segment mcamd_group_prox refuses by its shape */
+int64_t mcamd_gprox_seg_workgroups(const mcamd_gprox_seg* seg);
+
+/* One proximal step of every segment.  `segs` is a HOST array for the checks and the grid size, `segs_dev` its DEVICE copy
+ * for the kernel.  tau2 applies to the BLOCK segments, tau_gate to the GATE segments; the caller passes (lr * lam)^2 and
+ * (float)(lr * lam).  skip: device fp32 scalar or NULL; when *skip != 0 nothing is written at all, neither weights nor
+ * flags (train.StepGuard's `found`: a skipped optimizer step leaves the weights as they were).  Launch-type: recorded into a
+ * launch plan while one is being recorded.  Refused without a launch (MCAMD_EINVAL): NULL or misaligned pointers, a BLOCK
+ * segment with cin % 32 != 0, a GATE segment that is not [C][1][1], a wg0 that is not the running sum, a negative or
+ * non-finite tau2 or tau_gate. */
+int mcamd_group_prox(const mcamd_gprox_seg* segs, const mcamd_gprox_seg* segs_dev, int32_t nseg, double tau2, float tau_gate,
+                     const float* skip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,4 +43,8 @@ def __getattr__(name):
     if name in ("TaylorImportance", "taylor_prune"):
         from . import importance
         return getattr(importance, name)
+    # structured sparsity learned while training (sparsify.py, an addition beyond the reference), the same way
+    if name == "GroupLasso":
+        from . import sparsify
+        return sparsify.GroupLasso
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

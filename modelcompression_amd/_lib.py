@@ -198,6 +198,12 @@ class TaylorSeg(C.Structure):
                 ("cin", C.c_int32), ("khw", C.c_int32)]
 
 
+class GproxSeg(C.Structure):
+    """mcamd_gprox_seg (include/mcamd.h)."""
+    _fields_ = [("w", C.c_void_p), ("nz", C.c_void_p), ("wg0", C.c_int64), ("kind", C.c_int32), ("cout", C.c_int32),
+                ("cin", C.c_int32), ("khw", C.c_int32)]
+
+
 EPI_RAW_F16, EPI_NCHW_F32, EPI_PAD_F16, EPI_RAW_F32 = 0, 1, 2, 3
 DST_PLAIN, DST_POOL, DST_REORG = 0, 1, 2
 WGRAD_GENERIC, WGRAD_STEM, WGRAD_WIN, WGRAD_NINE, WGRAD_NINE_WIDE = 0, 1, 2, 3, 4      # mcamd_conv_wgrad_plan_info: family
@@ -212,6 +218,7 @@ WZ_BLOCK_WORDS = 64
 HZ_MAXLEN, HZ_CHUNK, HZ_GROUP = 12, 1024, 64                                            # MCAMD_HZ_*
 WS_SLAB = 4096                                                                         # MCAMD_WS_SLAB
 TAYLOR_CONV, TAYLOR_GATE = 0, 1                                                        # mcamd_taylor_seg.kind
+GPROX_BLOCK, GPROX_GATE = 0, 1                                                         # mcamd_gprox_seg.kind
 
 # name -> (restype, argtypes); the complete list of symbols include/mcamd.h declares.
 _P, _I32, _I64, _F, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -376,6 +383,8 @@ SIGNATURES = {
     "mcamd_ws_expand": (C.c_int, [_P, _P, _I32, _P, _I64, _P]),
     "mcamd_taylor_seg_workgroups": (_I64, [C.POINTER(TaylorSeg)]),
     "mcamd_taylor_accum": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
+    "mcamd_gprox_seg_workgroups": (_I64, [C.POINTER(GproxSeg)]),
+    "mcamd_group_prox": (C.c_int, [_P, _P, _I32, C.c_double, _F, _P, _P]),
 }
 
 _lib = None

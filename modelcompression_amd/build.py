@@ -55,6 +55,7 @@ SOURCES = {
     "wshare.hip": ["-ffp-contract=off"],  # weight sharing: float64 sums and divisions, operation by operation
     "huff.hip": [],                       # Huffman-coded model files: integer passes only
     "taylor.hip": ["-ffp-contract=off"],  # Taylor importance: pinned fp32 / float64 products and sums
+    "group_prox.hip": ["-ffp-contract=off"],  # proximal group lasso: pinned float64 sums, one scale per block
 }
 
 

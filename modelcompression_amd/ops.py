@@ -2048,3 +2048,52 @@ class TaylorTable:
                 raise L.McamdError("taylor: skip must be a device fp32 scalar")
         check(L.lib().mcamd_taylor_accum(self.arr, ptr(self.table), self.nseg, ptr(skip), ptr(self.steps), stream_ptr()),
               "mcamd_taylor_accum")
+
+
+# ----------------------------------------------------------------------------- proximal group lasso
+class GroupProxTable:
+    """Every layer of a proximal group-lasso step through one mcamd_gprox_seg table (include/mcamd.h).
+
+    items: one dict per segment.  A block segment: w (fp32, [cout][cin]..., cin % 32 == 0) and optionally nz (int32
+    [blocks]).  A gate segment (gate=True): w = gamma (fp32 [C]) and optionally nz (int32 [C]).  Built once; step() is one
+    library call on the current stream with no host read and no allocation."""
+
+    def __init__(self, items):
+        if not items:
+            raise L.McamdError("group_prox: no segment given")
+        dev = items[0]["w"].device
+        arr = (L.GproxSeg * len(items))()
+        wgs = 0
+        for a, it in zip(arr, items):
+            w, nz, gate = it["w"], it.get("nz"), bool(it.get("gate"))
+            _need_cuda(w, nz)
+            if w.dtype != torch.float32 or not w.is_contiguous() or w.device != dev or w.numel() == 0:
+                raise L.McamdError("group_prox: weights must be non-empty contiguous fp32 tensors on one device")
+            cout = w.shape[0]
+            cin = 1 if gate or w.dim() < 2 else w.shape[1]
+            khw = w.numel() // (cout * cin)
+            if gate:
+                groups = cout
+            else:
+                if cin % 32 != 0:
+                    raise L.McamdError("group_prox: blocks need cin %% 32 == 0 (cin %d)" % cin)
+                groups = ((cout + BLOCK_FILTERS - 1) // BLOCK_FILTERS) * (cin // block_kb(cin)) * khw
+            if nz is not None and (nz.dtype != torch.int32 or not nz.is_contiguous() or nz.device != dev or nz.numel() != groups):
+                raise L.McamdError("group_prox: nz must be a contiguous int32 tensor of %d entries on the weights' device" % groups)
+            a.w, a.nz = w.data_ptr(), (nz.data_ptr() if nz is not None else None)
+            a.kind, a.cout, a.cin, a.khw, a.wg0 = (L.GPROX_GATE if gate else L.GPROX_BLOCK), cout, cin, khw, wgs
+            wgs += int(L.lib().mcamd_gprox_seg_workgroups(C.byref(a)))
+        self.items, self.arr, self.nseg, self.workgroups = items, arr, len(items), wgs
+        # (pinned and non-blocking: building a table is no host synchronisation)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory().to(dev, non_blocking=True)
+
+    def step(self, tau, skip=None):
+        """One proximal step at tau = lr * lam: blocks take tau2 = tau * tau (float64), gates (float)tau; nothing at all is
+        written when *skip != 0 (device fp32 scalar)."""
+        if skip is not None:
+            _need_cuda(skip)
+            if skip.dtype != torch.float32 or skip.numel() != 1:
+                raise L.McamdError("group_prox: skip must be a device fp32 scalar")
+        tau = float(tau)
+        check(L.lib().mcamd_group_prox(self.arr, ptr(self.table), self.nseg, tau * tau, tau, ptr(skip), stream_ptr()),
+              "mcamd_group_prox")

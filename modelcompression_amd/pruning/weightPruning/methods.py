@@ -16,6 +16,7 @@ from ..._lib import McamdError
 from .utils import prune_rate, arg_nonzero_min
 from ...share import kmeans_share  # noqa: F401  (the stage behind pruning: weight sharing, share.py)
 from ...importance import taylor_prune  # noqa: F401  (ranking by first-order Taylor importance, importance.py)
+from ...sparsify import GroupLasso  # noqa: F401  (block and filter sparsity learned while training, sparsify.py)
 
 
 def _virtual_index(n, perc, ftype):

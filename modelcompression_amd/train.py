@@ -52,6 +52,16 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     dgrad launches of the retraining steps skip the zeroed blocks of every layer whose kept fraction is at most the model's
     default bound (engine.BSPARSE_TRAIN_MAX_KEPT).  SPARSE_TRAIN = "block-wgrad" also runs their weight
     gradient on the tiles and taps the masks keep (engine.BSPARSE_TRAIN_WGRAD_MAX_KEPT).
+  * YOLOv2Train.GROUP_LASSO = {"lam": float, "granularity": "block" | "filter"} (an attribute; None by default: train()
+    issues the launches it issued before and nothing more) learns structured sparsity while training (sparsify.py, DESIGN.md
+    3ze): a sparsify.GroupLasso is built behind set_masks, and its proximal step -- one launch over all layers, at the
+    optimizer's learning rate, skipped on the device when StepGuard flags the step -- runs behind every optimizer.step().
+    "block" shrinks block_prune's blocks of the conv weights, "filter" the BatchNorm gammas.  Each epoch logs the fraction of
+    zero groups; before every checkpoint and at the end model.set_masks(gl.masks()) turns the zero groups into ordinary
+    masks, so the .weights / .mcz files and the later engines see them as any pruner's.  Data-parallel ranks hold identical
+    weights after the all-reduced step and the proximal step is a deterministic function of the weights: nothing travels.
+    SHARE together with GROUP_LASSO raises (the projection and the proximal step would undo each other).  The object is kept
+    as YOLOv2Train.group_lasso.
 """
 import os
 
@@ -74,6 +84,7 @@ from .pruning.weightPruning.methods import block_prune, quick_filter_prune, weig
 from .pruning.weightPruning.utils import prune_rate, are_masks_consistent  # noqa: E402
 from .share import kmeans_share, are_codebooks_consistent, _bits_of  # noqa: E402
 from .importance import TaylorImportance, taylor_prune  # noqa: E402
+from .sparsify import GroupLasso, check_config as _group_lasso_config  # noqa: E402
 
 TAYLOR_METHODS = {"taylor-weight": "weight", "taylor-block": "block", "taylor-filter": "filter"}
 
@@ -249,6 +260,9 @@ class YOLOv2Train():
     # Darknet.sparse_train_max_kept above the layers' kept fractions.  "block-wgrad"  also skips them in the
     # weight gradient of the layers below Darknet.sparse_train_wgrad_max_kept.
     SPARSE_TRAIN = None
+    # None, or {"lam": float, "granularity": "block" | "filter"}: a proximal group-lasso step (sparsify.GroupLasso, DESIGN.md
+    # 3ze) behind every optimizer.step(); the learned zero groups become masks before every file is saved (an attribute too)
+    GROUP_LASSO = None
 
     def __init__(self):
         self.model = ''
@@ -260,6 +274,7 @@ class YOLOv2Train():
         self.batch_size = ''
         self.teacher = None       # train(TEACHER=...): the frozen Darknet and the distill.DistillLoss of the last call
         self.distill = None
+        self.group_lasso = None   # GROUP_LASSO: the sparsify.GroupLasso of the last call
 
     @_share_keyword
     def train(self, PASCAL_DIR, PASCAL_TRAIN, PASCAL_VALID, TRAIN_LOGDIR, VAL_LOGDIR, VAL_OUTPUTDIR_PKL, VAL_PREFIX,
@@ -278,6 +293,15 @@ class YOLOv2Train():
             SHARE = dict(bits=SHARE)
         if SHARE is not None and not isinstance(SHARE.get("bits", 4), dict):
             _bits_of(SHARE.get("bits", 4), [1])       # a bad width is refused here, before the model is built
+        GROUP_LASSO = self.GROUP_LASSO
+        if GROUP_LASSO is not None:
+            if not isinstance(GROUP_LASSO, dict) or set(GROUP_LASSO) != {"lam", "granularity"}:
+                raise ValueError('train: GROUP_LASSO must be None or a dict {"lam": float, "granularity": "block" | "filter"}, '
+                                 'got %r' % (GROUP_LASSO,))
+            _group_lasso_config(GROUP_LASSO["lam"], GROUP_LASSO["granularity"], who="train: GROUP_LASSO")
+            if SHARE is not None:
+                raise ValueError("train: SHARE and GROUP_LASSO cannot be combined: the projection onto the codebooks and the "
+                                 "proximal step would undo each other")
         if DISTILL is not None and TEACHER is None:
             raise ValueError("train: DISTILL needs a TEACHER (True, a .weights path or a Darknet)")
         rank, world = dp.init_from_env()
@@ -368,6 +392,9 @@ class YOLOv2Train():
         if SHARE is not None:
             # every rank clusters the same broadcast weights under the same masks: the codebooks agree, nothing travels
             self.model.set_codebooks(kmeans_share(self.model, **SHARE))
+        self.group_lasso = gl = None
+        if GROUP_LASSO is not None:
+            gl = self.group_lasso = GroupLasso(self.model, GROUP_LASSO["lam"], GROUP_LASSO["granularity"])
         if masks is not None:
             p_rate = prune_rate(self.model, rank == 0)
             if rank == 0:
@@ -421,6 +448,10 @@ class YOLOv2Train():
                 # together, and the host learns of it one step late (StepGuard)
                 guard.decide(train_loss)
                 optimizer.step()
+                if gl is not None:
+                    # the proximal step of the penalty, at the step size SGD just used; a step StepGuard skipped leaves the
+                    # weights exactly as they were, decided on the device
+                    gl.step(optimizer.param_groups[0]["lr"], skip=guard.found)
                 if SHARE is not None:
                     # By linearity, SGD on the shared values with the mean member gradient (momentum and weight decay
                     # included).  A step StepGuard skipped left the weights tied: the projection is then the identity.
@@ -437,7 +468,13 @@ class YOLOv2Train():
                     seen_here / max(time.time() - t0, 1e-9), train_loss_total / max(len(loader), 1),
                     '' if distill_loss_total is None else
                     ', of it distillation %.4f' % (float(distill_loss_total) / max(len(loader), 1))))
+            if gl is not None and rank == 0:
+                logging('group lasso (%s, lam %g): %.4f of the groups are zero' % (gl.granularity, gl.lam, gl.zero_fraction()))
             dp.sync_buffers(self.model)     # BatchNorm running statistics are rank-local: average before checkpoint / eval
+            if gl is not None and pruning_perc > 0 and (epoch + 1) % 5 == 0 and TRAIN_LOGDIR:
+                # a checkpoint follows: the zero groups become ordinary masks first, on every rank alike
+                masks = gl.masks()
+                self.model.set_masks(masks)
             if pruning_perc > 0 and rank == 0:
                 print(' pruned: %s' % prune_rate(self.model, False))
                 print(' pruned weights consistent after retraining: %s ' % are_masks_consistent(self.model, masks))
@@ -455,6 +492,10 @@ class YOLOv2Train():
                 from .predict import PASCALVOCEval
                 PASCALVOCEval(self.model, MODEL_CFG, MODEL_WEIGHT, region_loss, PASCAL_DIR, PASCAL_VALID, VAL_LOGDIR,
                               VAL_PREFIX, VAL_OUTPUTDIR_PKL, LOGGER, epoch).predict(BATCH_SIZE, RESIDENT=eval_resident)
+        if gl is not None:
+            # the learned structure as ordinary masks: what the .weights / .mcz files and the later engines see
+            masks = gl.masks()
+            self.model.set_masks(masks)
         if TRAIN_LOGDIR and rank == 0:
             name = '%s/%s-pruned-%s-retrained-final_%06d.weights' % (TRAIN_LOGDIR, pruning_method, pruning_perc, epoch + 1)
             logging('save weights to %s' % name)
