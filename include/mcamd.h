@@ -338,6 +338,43 @@ int mcamd_conv_fwd_splitk_info(const mcamd_conv_geom* g, int32_t mode, int32_t d
 int mcamd_conv_fwd_splitk(const mcamd_conv_geom* g, const void* x, const void* wp_fwd, const mcamd_conv_epilogue* epi,
                           int32_t slices, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Low-rank (factored) forward for fp16 inference (an addition beyond the reference; conv_lowrank.hip, Darknet.lowrank,
+ * DESIGN.md 3zf).  A block whose weight is the product V U of U [rank][cin][k][k] and V [cout][rank] runs as a k x k
+ * convolution to `rank` channels and a 1 x 1 convolution to cout filters in ONE launch; the intermediate lives in LDS:
+ *
+ *   H[m][j] = sat_half( fp32 sum over (tap, c) of x[m][tap, c] * U[j][tap, c] )        j < rank
+ *   Y[m][n] = epilogue( fp32 sum over j < rank of H[m][j] * V[n][j] )
+ *
+ * sat_half: mode 0's saturating round-to-nearest-even; epilogue: MCAMD_EPI_PAD_F16's (leaky(acc * scale + shift),
+ * saturating fp16, overflow flag -- also set when an H value was clamped), dst_mode PLAIN / POOL (+ y2) / REORG.  That is
+ * mcamd_conv_fwd in mode 0 with the geometry's cout = rank followed by mcamd_conv_fwd in mode 2 of the 1 x 1 block, up to the
+ * order of the fp32 sums.
+ *
+ * Geometries: ksize 1 or 3, stem == 0, pad == 0, x_wrap == 0, x_f8 == 0, cout % 8 == 0; rank a multiple of 32 in [32, 256].
+ * Operands: `up` = U in mcamd_pack_weights' forward layout for `rank` filters ([round_up(rank, 256)][k*k * round_up(cin, 32)],
+ * packed K order), `vp` = V in the layout of a 1 x 1 block over `rank` channels ([round_up(cout, 256)][rank]); pad rows and
+ * pad channels are zeros.  mcamd_pack_lowrank fills both from the fp32 factors.
+ * ------------------------------------------------------------------------- */
+typedef struct mcamd_lowrank_info {
+    int32_t rank_padded;     /* intermediate columns of the kernel instance: round_up(rank, 64) */
+    int32_t bm, bn, bk;      /* pixels per workgroup; filters per N tile of the second GEMM; K chunk of both GEMMs */
+    int32_t stages;          /* LDS ring depth */
+    int32_t mtiles, ntiles;  /* workgroups that do work; N tiles each of them walks */
+    int32_t grid;            /* launched workgroups: round_up(mtiles, 8) */
+    int32_t lds_bytes;       /* dynamic LDS of the instance: intermediate tile + ring (+ output tile) */
+    int64_t up_elems, vp_elems; /* fp16 elements of the two packed operands */
+} mcamd_lowrank_info;
+/* Host logic only: 1 when (geometry, rank) has a low-rank form; the instance the launch takes and the operand sizes. */
+int32_t mcamd_conv_fwd_lowrank_ok(const mcamd_conv_geom* g, int32_t rank);
+int mcamd_conv_fwd_lowrank_info(const mcamd_conv_geom* g, int32_t rank, mcamd_lowrank_info* out);
+/* u_oihw: fp32 [rank][cin][k][k], v_oi: fp32 [cout][rank] (device); up / vp: up_elems / vp_elems fp16 values. */
+int mcamd_pack_lowrank(const mcamd_conv_geom* g, int32_t rank, const float* u_oihw, const float* v_oi, void* up, void* vp,
+                       void* stream);
+/* The launch.  epi->mode must be MCAMD_EPI_PAD_F16. */
+int mcamd_conv_fwd_lowrank(const mcamd_conv_geom* g, int32_t rank, const void* x, const void* up, const void* vp,
+                           const mcamd_conv_epilogue* epi, void* stream);
+
 /* ---------------------------------------------------------------------------
  * fp8 (OCP e4m3) quantised inference (an addition beyond the reference; conv_q8.hip, Darknet.precision = "fp8").
  *   q(v) = round-to-nearest-even to e4m3 of v clamped to [-448, 448].

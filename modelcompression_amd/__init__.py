@@ -47,4 +47,8 @@ def __getattr__(name):
     if name == "GroupLasso":
         from . import sparsify
         return sparsify.GroupLasso
+    # low-rank factorisation (lowrank.py, an addition beyond the reference), the same way
+    if name == "lowrank_factor":
+        from . import lowrank
+        return lowrank.lowrank_factor
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

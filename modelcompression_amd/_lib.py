@@ -97,6 +97,12 @@ class SplitkInfo(C.Structure):
                 ("finish_rows", C.c_int32), ("finish_cols", C.c_int32)]
 
 
+class LowrankInfo(C.Structure):
+    """mcamd_lowrank_info (include/mcamd.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("rank_padded", "bm", "bn", "bk", "stages", "mtiles", "ntiles", "grid", "lds_bytes")] + \
+               [("up_elems", C.c_int64), ("vp_elems", C.c_int64)]
+
+
 class FoldDesc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("mask", C.c_void_p), ("rows", C.c_void_p), ("cols", C.c_void_p),
                 ("beta", C.c_void_p), ("slope", C.c_float),
@@ -261,6 +267,10 @@ SIGNATURES = {
     "mcamd_pack_q8": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P]),
     "mcamd_conv_fwd_q8": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _P]),
     "mcamd_conv_fwd_q8_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(_I32)]),
+    "mcamd_conv_fwd_lowrank_ok": (_I32, [C.POINTER(ConvGeom), _I32]),
+    "mcamd_conv_fwd_lowrank_info": (C.c_int, [C.POINTER(ConvGeom), _I32, C.POINTER(LowrankInfo)]),
+    "mcamd_pack_lowrank": (C.c_int, [C.POINTER(ConvGeom), _I32, _P, _P, _P, _P, _P]),
+    "mcamd_conv_fwd_lowrank": (C.c_int, [C.POINTER(ConvGeom), _I32, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),
     "mcamd_conv_fwd_q8_splitk_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, C.POINTER(SplitkInfo)]),
     "mcamd_conv_fwd_q8_splitk": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _I32, _P, _SZ, _P]),
     "mcamd_conv_fwd_q8_bsparse_ok": (_I32, [C.POINTER(ConvGeom)]),

@@ -24,6 +24,8 @@ SOURCES = {
     "conv_sparse.hip": [],
     "conv_bsparse.hip": [],
     "conv_splitk.hip": [],
+    # (no packed-fp32 instructions in the epilogue arithmetic: some of their forms round differently)
+    "conv_lowrank.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # The fp8 forward family runs one K loop and one epilogue (csrc/conv_q8_loop.h): their results are bit-equal where the
     # tests say so because the same functions run.  The five files must still be compiled with EQUAL flags, so that the
     # shared epilogue expression (and the split-K finish kernel's restatement of it) contracts the same way in each.

@@ -954,6 +954,91 @@ extern "C" int mcamd_conv_fwd_splitk(const mcamd_conv_geom* g, const void* x, co
 }
 
 // ---------------------------------------------------------------------------------------
+// low-rank (factored) forward for fp16 inference (conv_lowrank.hip; an addition beyond the reference)
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_lowrank_ok(const mcamd_conv_geom* g, int32_t rank) {
+    if (!g || g->stem || g->pad != 0 || g->x_wrap != 0 || g->x_f8 != 0 || (g->ksize != 1 && g->ksize != 3)) return 0;
+    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->cin <= 0 || g->cout <= 0) return 0;
+    if (rank < 32 || rank > 256 || rank % 32 != 0 || g->cout % 8 != 0 || (long long)g->B * g->H * g->W >= (1ll << 31)) return 0;
+    if (g->x_ld % 8 != 0 || g->x_choff % 8 != 0 || g->x_choff < 0 || g->x_choff + cin_tap_of(g) > g->x_ld) return 0;
+    return 1;
+}
+
+// the two geometries the operands are packed for: U as the forward weights of `rank` filters, V as those of a 1 x 1 block
+// over `rank` channels
+static void lowrank_geoms(const mcamd_conv_geom* g, int rank, mcamd_conv_geom* gu, mcamd_conv_geom* gv) {
+    *gu = *g;
+    gu->cout = rank;
+    *gv = *g;
+    gv->ksize = 1, gv->cin = rank, gv->x_ld = rank, gv->x_choff = 0;
+}
+
+extern "C" int mcamd_conv_fwd_lowrank_info(const mcamd_conv_geom* g, int32_t rank, mcamd_lowrank_info* out) {
+    MCAMD_REQUIRE(g && out, "conv_fwd_lowrank_info: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_lowrank_ok(g, rank), "conv_fwd_lowrank_info: geometry / rank %d has no low-rank form (mcamd_conv_fwd_lowrank_ok)", rank);
+    const LowrankChoice c = mcamd_lowrank_choice((long long)g->B * g->H * g->W, g->cout, rank);
+    mcamd_conv_geom gu, gv;
+    lowrank_geoms(g, rank, &gu, &gv);
+    out->rank_padded = c.rp;
+    out->bm = c.bm, out->bn = c.bn, out->bk = c.bk;
+    out->stages = c.stages;
+    out->mtiles = c.mtiles, out->ntiles = c.ntiles;
+    out->grid = c.grid;
+    out->lds_bytes = c.lds_bytes;
+    out->up_elems = mcamd_packed_elems_fwd(&gu);
+    out->vp_elems = mcamd_packed_elems_fwd(&gv);
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_pack_lowrank(const mcamd_conv_geom* g, int32_t rank, const float* u_oihw, const float* v_oi, void* up, void* vp,
+                                  void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "pack_lowrank: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_pack_lowrank(&g_, rank, u_oihw, v_oi, up, vp, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_lowrank_ok(g, rank), "pack_lowrank: geometry / rank %d has no low-rank form (mcamd_conv_fwd_lowrank_ok)", rank);
+    MCAMD_REQUIRE(u_oihw && v_oi && up && vp, "pack_lowrank: null pointer");
+    mcamd_conv_geom gu, gv;
+    lowrank_geoms(g, rank, &gu, &gv);
+    hipStream_t st = (hipStream_t)stream;
+    const mcamd_conv_geom* gs[2] = {&gu, &gv};
+    const float* src[2] = {u_oihw, v_oi};
+    void* dst[2] = {up, vp};
+    for (int i = 0; i < 2; ++i) {   // pack_weights' forward kernel: rows past the last filter and channels past the last one are zeros
+        const long long total = mcamd_packed_elems_fwd(gs[i]);
+        long long grid = (total + 256 * 4 - 1) / (256 * 4);
+        if (grid > 4096) grid = 4096;
+        hipLaunchKernelGGL(pack_fwd_kernel, dim3((int)grid), dim3(256), 0, st, src[i], (const float*)nullptr, (half_t*)dst[i], gs[i]->cout,
+                           gs[i]->cin, gs[i]->ksize, cin_tap_of(gs[i]), 0, total, ntaps_of(gs[i]) * cin_tap_of(gs[i]),
+                           (const int*)nullptr, (const int*)nullptr, (half_t*)nullptr);
+    }
+    MCAMD_LAUNCH_CHECK("pack_lowrank");
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_conv_fwd_lowrank(const mcamd_conv_geom* g, int32_t rank, const void* x, const void* up, const void* vp,
+                                      const mcamd_conv_epilogue* epi, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_lowrank: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_lowrank(&g_, rank, x, up, vp, &e_, s); });
+    }
+    MCAMD_REQUIRE(g, "conv_fwd_lowrank: null geometry");
+    MCAMD_REQUIRE(mcamd_conv_fwd_lowrank_ok(g, rank),
+                  "conv_fwd_lowrank: geometry / rank %d has no low-rank form: ksize 1 or 3, rank a multiple of 32 in [32, 256], "
+                  "cout %% 8 == 0, no stem / pad / x_wrap / x_f8 (mcamd_conv_fwd_lowrank_ok)", rank);
+    if (check_geom(g, "conv_fwd_lowrank")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(x && up && vp, "conv_fwd_lowrank: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_lowrank: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x, up, g->x_ld, g->x_choff, g->cout, cin_tap_of(g), 0);
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_lowrank", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    return mcamd_lowrank_launch(a, vp, rank, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------
 // fp8 (e4m3) quantised inference (conv_q8.hip; an addition beyond the reference)
 // ---------------------------------------------------------------------------------------
 extern "C" int32_t mcamd_conv_fwd_q8_ok(const mcamd_conv_geom* g) {

@@ -129,6 +129,14 @@ struct SplitkPlan {
 };
 SplitkPlan mcamd_splitk_plan(long long M, int n, int cin_tap, int ktot, int forced);
 int mcamd_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, float* ws, hipStream_t st);
+// conv_lowrank.hip: a factored block (k x k to `rank` channels, then 1 x 1 to N filters) in one launch, mode 2 epilogue.
+// mcamd_lowrank_choice names the lowrank_kernel<rp> instance (rp = round_up(rank, 64) intermediate columns), its tiles
+// (bm pixels; bn filters per N tile of the second GEMM; K chunks of bk), its grid and its dynamic LDS
+struct LowrankChoice {
+    int rp, bm, bn, bk, stages, mtiles, ntiles, grid, lds_bytes;
+};
+LowrankChoice mcamd_lowrank_choice(long long M, int n, int rank);
+int mcamd_lowrank_launch(const IgemmArgs& a, const void* vp, int rank, hipStream_t st);
 // conv_bsparse.hip: the K chunks of each 64-filter N tile from a list (count[ntiles], list[ntiles][ktot / kb]), mode 2
 // epilogue (inference) or mode 0 (a.mode == MCAMD_EPI_RAW_F16: the training form, forward and dgrad; a.stats: one slab row
 // per pixel tile); and the lists of a packed forward or dgrad weight matrix

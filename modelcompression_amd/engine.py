@@ -29,6 +29,7 @@ import torch
 
 from . import ops
 from . import _lib as L
+from . import lowrank as _lowrank
 from ._lib import McamdError
 
 
@@ -60,6 +61,8 @@ _LAYER_FIELDS = dict(
     # inference form (Engine._choose_forms, _FORMS) and what belongs to one: split-K slices (forms "splitk" and "q8_splitk"),
     # 2:4 values + index words, block-sparse chunk lists
     form="dense", sk_slices=1, wsp=None, widx=None, bs_count=None, bs_list=None,
+    # the packed factors of form "lowrank" and their rank
+    up=None, vp=None, lr_rank=0,
     # the training form of the block-sparse kernel (form "bsparse_train"): its statistics slab (one row per pixel tile), the
     # chunk lists over the dgrad packing, whether the dgrad launch takes it too, and full lists (Engine.bsparse_train_full_lists)
     bs_stats=None, bs_dcount=None, bs_dlist=None, bs_dgrad=False, bs_full=None,
@@ -167,6 +170,22 @@ BSPARSE_TRAIN_MAX_KEPT = 0.375
 # window for however few taps it keeps, and nearly every tile keeps some).  Whole step at kept 0.1: dense 9.15, "block" 7.89,
 # "block-wgrad" 7.13 ms.  A block_prune level of 90 % leaves layers at 0.100 .. 0.125: a caller who wants them all sets 0.125.
 BSPARSE_TRAIN_WGRAD_MAX_KEPT = 0.1
+# Darknet.lowrank: a block with fresh factors of rank r leaves the dense fp16 launch for the fused two-GEMM kernel
+# (csrc/conv_lowrank.hip) when its cost ratio r (Cin k k + Cout) / (Cin k k Cout) is at most this -- the default of
+# Darknet.lowrank_max_cost.  The rule of DESIGN.md 3t on tools/lowrank_bench.py (profiles/lowrank_bench.json): the largest
+# measured cost ratio at which every chosen layer of conv9 .. conv22 is at least 10 % faster than the dense launch it replaces
+# at B = 128; 0.0: no level passes.  Measured (ranks 64 / 128 / 192 / 256 on every accepted block, points sorted by ratio, us dense ->
+# fused): 0.068-0.076 (r 64, conv14-22 3x3) 1.89-2.68x; 0.136-0.153 (r 128 conv14-22; r 64 conv9 / 11 / 13) 1.58-2.17x, worst
+# 209.7 -> 132.6 (conv18); then 0.188 (r 64 on the 1x1 conv15 / 17) 47.9 -> 47.6 = 1.01x fails, so the constant is 0.153 although
+# 0.204-0.229 (r 192, 3x3) still gain 1.34-1.79x; from 0.272 (r 256) the 3x3 layers lose (0.74-1.04x), the 1x1 layers lose at
+# every rank (0.42-1.01x).  The unfused pair of dense launches was FASTER than the fused launch at every point (conv18, r 128:
+# 84.7 us against 132.6): the fusion does not pay yet, the factorisation does.
+LOWRANK_MAX_COST = 0.153
+# ... and a launch of fewer pixel tiles than this (the default of Darknet.lowrank_min_tiles) stays dense whatever its ratio: one workgroup per 64 pixels walks the
+# whole K axis alone, so a launch that cannot put a workgroup on every CU once is bound by that walk, not by the work saved.
+# Measured at B = 8 and B = 1 (3 .. 169 tiles): 0.31-0.94x of the dense launch on every layer of conv9 .. conv22 but conv19 / 20 /
+# 22 at r 64 and B = 8 (22 tiles, 1.04-1.11x); at 338 tiles (B = 128) the table above holds.  Nothing between 169 and 338 was tried.
+LOWRANK_MIN_TILES = 256
 
 
 class _Dense:
@@ -221,6 +240,26 @@ class _SplitK(_Dense):
             return _Dense.raw(self, eng, lay, xin, training)
         eng._timed('fwd', lay, ops.conv_fwd_raw_splitk, lay.geom_act, xin, lay.wp, lay.y, lay.cout, 0,
                    slices=lay.sk_slices, workspace=eng._splitk_ws)
+
+
+class _LowRank(_Dense):
+    """Fresh low-rank factors: both factor GEMMs in one launch, the intermediate in LDS (Darknet.lowrank,
+    csrc/conv_lowrank.hip).  The dense `wp` stays packed beside them: it is what the block runs when the factors go stale."""
+    fwd = "conv_fwd_lowrank"
+    bufs = (("up", torch.float16), ("vp", torch.float16))
+
+    def alloc(self, eng, lays):
+        for lay in lays:
+            info = ops.conv_fwd_lowrank_info(lay.geom_act, lay.lr_rank)
+            for name, n in (("up", info.up_elems), ("vp", info.vp_elems)):
+                if getattr(lay, name) is None or getattr(lay, name).numel() != n:
+                    setattr(lay, name, torch.zeros(n, dtype=torch.float16, device=eng.device))
+
+    def pack(self, eng, lay, w, mask):
+        ops.pack_lowrank(lay.geom_act, lay.conv.factor_u, lay.conv.factor_v, lay.up, lay.vp)
+
+    def operands(self, eng, lay, xin):
+        return (lay.geom_act, lay.lr_rank, xin, lay.up, lay.vp), {}
 
 
 class _Sparse24(_Dense):
@@ -484,7 +523,7 @@ class _Q8W4(_Q8):
         eng._timed('fwd', lay, ops.conv_fwd_q8_w4_raw, lay.geom_act, x8, lay.w4c, lay.w4g, lay.wexp4, lay.y, lay.cout, 0, lay.stats)
 
 
-_FORMS = {"dense": _Dense(), "splitk": _SplitK(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "bsparse_train": _BSparseTrain(), "q8": _Q8(),
+_FORMS = {"dense": _Dense(), "splitk": _SplitK(), "lowrank": _LowRank(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "bsparse_train": _BSparseTrain(), "q8": _Q8(),
           "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4(), "q8_bsparse": _Q8BSparse()}
 
 
@@ -646,9 +685,15 @@ class Engine:
         # mcamd_conv_fwd_splitk, chosen when the flag or the masks change (_choose_forms); one workspace for all of them
         self.splitk_layers = []
         self._splitk_ws = None
+        # low-rank inference (Darknet.lowrank, plain-fp16 eval engines only): conv numbers of the blocks that run
+        # mcamd_conv_fwd_lowrank; {conv number: rank} of every block that carries factors; conv numbers of those whose weight was
+        # written after set_factors (they run dense).  Read again in every forward, from host state only.
+        self.lowrank_layers = []
+        self.lowrank_ranks = {}
+        self.lowrank_stale = []
         # what every block's form was last chosen for (pack): mask keys, block-sparse choice, sparse mode, sparse_max_kept,
         # split-K flag
-        self._form_key = (None, None, None, None, None)
+        self._form_key = (None, None, None, None, None, None)
         self._training, self._fold_key = None, None
         self.fold_dead = os.environ.get("MCAMD_FOLD_DEAD", "1") == "1"
         # "mixed": the two correction products of the split-operand forward from e4m3 copies on the block-scaled fp8 MFMAs
@@ -1100,11 +1145,13 @@ class Engine:
             sig.append((w.data_ptr(), w._version, None if m is None else (m.data_ptr(), m._version), bnv))
         return tuple(sig)
 
-    def pack(self, force=False, training=True, sparse=None, splitk=False, max_kept=None, wgrad_max_kept=None):
+    def pack(self, force=False, training=True, sparse=None, splitk=False, max_kept=None, wgrad_max_kept=None, lowrank=None):
         """fp32 master * mask -> fp16 kernel layouts (replaces layers.py:59's per-forward multiply).
         `sparse`, `splitk`, `max_kept`: the inference options forward() validated (Darknet.sparse / splitk /
         sparse_max_kept; off in training mode); every block's form is chosen again when they or the masks change.
-        `wgrad_max_kept` (sparse = "block-train" only; None: off): Darknet.sparse_train = "block-wgrad"."""
+        `wgrad_max_kept` (sparse = "block-train" only; None: off): Darknet.sparse_train = "block-wgrad".
+        `lowrank` (None: off): (Darknet.lowrank_max_cost, Darknet.lowrank_min_tiles, ((layer index, rank) of every block
+        with fresh factors))."""
         if any(lay.fold is not None for lay in self.layers) and training != self._training:
             force = True          # the folded constants differ between batch and running statistics
         self._training = training
@@ -1115,7 +1162,7 @@ class Engine:
         # engine after grad_scale was halved) must not keep the static default exponents
         serial = self.model._weights_serial
         dirty = self.model._weights_dirty or serial != self._weights_seen
-        if not force and sig == self._packed_sig and (sparse, max_kept, splitk) == self._form_key[2:] and not dirty:
+        if not force and sig == self._packed_sig and (sparse, max_kept, splitk, lowrank) == self._form_key[2:] and not dirty:
             return
         if dirty or (self.f8 and self.serial % 1000 == 999):      # (and every 1 000th forward: slow drift)
             self._refresh_f8_wexp()
@@ -1133,7 +1180,7 @@ class Engine:
             exempt, self.bsparse_train_kept = self._bst_policy[1:]
         elif self.q8_bsparse and max_kept is not None:
             exempt, self.fp8_block_kept = _FORMS["q8_bsparse"].policy(self, max_kept)
-        key = (mkeys, exempt, sparse, max_kept, splitk)
+        key = (mkeys, exempt, sparse, max_kept, splitk, lowrank)
         if key != self._form_key:          # masks are static during retraining: planned once
             self._choose_forms(key)
         # (the list weight gradient follows the forms: chosen again when they, the masks -- part of the form key -- or its
@@ -1323,7 +1370,7 @@ class Engine:
              and does when the library's policy gives the block's eval-mode launch two slices or more
              (mcamd_conv_fwd_splitk_info).
         Every other block stays dense.  The `*_layers` lists are the conv numbers (conv1 = the first block) per form."""
-        mkeys, exempt, sparse, max_kept, splitk = key
+        mkeys, exempt, sparse, max_kept, splitk, lowrank = key
         self._plan_epoch += 1             # recorded plans name each block's launch and hold its operands' addresses
         if (mkeys, exempt) != self._form_key[:2]:
             self._bs_exempt = exempt
@@ -1372,6 +1419,14 @@ class Engine:
             for lay in self.layers:          # (a chosen block whose producer was compacted after all stays dense)
                 if lay.li in exempt and self._bst_eligible(lay):
                     lay.form = "bsparse_train"
+        if lowrank is not None:              # (in front of split-K, which is off with it)
+            max_cost, min_tiles, fresh = lowrank[0], lowrank[1], dict(lowrank[2])
+            for lay in self.layers:
+                r, K = fresh.get(lay.li, 0), lay.cin * lay.k * lay.k
+                if (r and lay.form == "dense" and self._eligible(lay) and not lay.conv.mask_flag and not lay.geom_act.pad
+                        and ops.conv_fwd_lowrank_ok(lay.geom_act, r) and r * (K + lay.cout) <= max_cost * K * lay.cout
+                        and ops.conv_fwd_lowrank_info(lay.geom_act, r).mtiles >= min_tiles):
+                    lay.form, lay.lr_rank = "lowrank", r
         if splitk:
             for lay in self.layers:
                 launch = self._splitk_form(lay)
@@ -1387,6 +1442,7 @@ class Engine:
             _FORMS[name].alloc(self, lays)
         nums = lambda *names: [lay.li + 1 for lay in self.layers if lay.form in names]
         self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
+        self.lowrank_layers = nums("lowrank")
         self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_bsparse")
         self.fp8_block_layers = nums("q8_bsparse")
         if self._training:                   # (what the last training-mode choice was; an eval pass in between keeps it)
@@ -1892,6 +1948,20 @@ class Engine:
             raise McamdError("splitk=True runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not %r%s"
                              % (self.precision, "; split-K on the fp8 engine: model.precision = 'fp8-splitk' with "
                                 "model.splitk = False" if self.q8 else ""))
+        lowrank = None
+        facts = [(lay, lay.conv.factor_u.shape[0]) for lay in self.layers if getattr(lay.conv, "factor_u", None) is not None]
+        self.lowrank_ranks = {lay.li + 1: int(r) for lay, r in facts}
+        self.lowrank_stale = [lay.li + 1 for lay, _ in facts if not _lowrank.is_fresh(self.model, lay.conv)]
+        if bool(getattr(self.model, "lowrank", False)) and not training:
+            if self.precise or self.q8:
+                raise McamdError("lowrank=True runs in the plain-fp16 inference engine only (model.precision = 'fp16'), not "
+                                 "precision=%r" % (self.precision,))
+            if splitk or mode is not None:
+                raise McamdError("lowrank=True does not combine with %s: a factored block has no sparse or split-K form"
+                                 % ("splitk=True" if splitk else "sparse=%r" % (mode,)))
+            lowrank = (float(getattr(self.model, "lowrank_max_cost", LOWRANK_MAX_COST)),
+                       int(getattr(self.model, "lowrank_min_tiles", LOWRANK_MIN_TILES)),
+                       tuple((lay.li, int(r)) for lay, r in facts if lay.li + 1 not in self.lowrank_stale))
         if mode not in (None, "2:4", "block"):
             raise McamdError("sparse must be None, '2:4' or 'block' (got %r)" % (mode,))
         max_kept = float(getattr(self.model, "sparse_max_kept", BSPARSE_MAX_KEPT)) if mode == "block" else None
@@ -1904,7 +1974,8 @@ class Engine:
             if st == "block-wgrad" and float(getattr(self.model, "sparse_train_wgrad_max_kept", BSPARSE_TRAIN_WGRAD_MAX_KEPT)) > 0.0:
                 # (again 0.0 chooses nothing: sparse_train = "block", bit for bit, and no list is built)
                 wgrad_max = float(getattr(self.model, "sparse_train_wgrad_max_kept", BSPARSE_TRAIN_WGRAD_MAX_KEPT))
-        self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept, wgrad_max_kept=wgrad_max)
+        self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept, wgrad_max_kept=wgrad_max,
+                  lowrank=lowrank)
         self.serial += 1
         tin = self.layers[0].tin
         xs = x.detach().contiguous().float()

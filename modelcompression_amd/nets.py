@@ -356,6 +356,16 @@ class Darknet(nn.Module):
         # engine.Engine.splitk_layers); batches the policy does not split run exactly what they run without it.  Eval with
         # precision "fp16" only -- other eval precisions raise; training ignores it.  MCAMD_SPLITK=1 sets the default.
         self.splitk = os.environ.get("MCAMD_SPLITK", "0") == "1"
+        # Low-rank inference (an addition beyond the reference; lowrank.py): True runs every eligible block whose
+        # factors (set_factors) are fresh, whose geometry and rank mcamd_conv_fwd_lowrank_ok accepts and whose cost ratio
+        # r (Cin k k + Cout) / (Cin k k Cout) is at most `lowrank_max_cost` as ONE launch of both factor GEMMs with the r-channel
+        # intermediate in LDS (csrc/conv_lowrank.hip, engine.Engine.lowrank_layers / lowrank_ranks / lowrank_stale).  A block
+        # whose weight was written after set_factors is stale and runs dense on its current weights.  Eval with precision
+        # "fp16" only -- other eval precisions raise; training ignores it; `sparse` and `splitk` stay off with it.
+        self.lowrank = False
+        from .engine import LOWRANK_MAX_COST, LOWRANK_MIN_TILES
+        self.lowrank_max_cost = LOWRANK_MAX_COST     # the measured policy constant (engine.py)
+        self.lowrank_min_tiles = LOWRANK_MIN_TILES   # launches of fewer 64-pixel tiles stay dense (engine.py)
 
     # ---- engine plumbing
     def _mark_weights_replaced(self):
@@ -367,10 +377,15 @@ class Darknet(nn.Module):
         self._weights_serial += 1
 
     def _apply(self, fn, *args, **kwargs):
+        from . import lowrank
+        fresh = [m for m in self.modules() if lowrank.is_fresh(self, m)]
         self._engines = {}
         self._mark_weights_replaced()
         self._ws_table = None
-        return super(Darknet, self)._apply(fn, *args, **kwargs)
+        out = super(Darknet, self)._apply(fn, *args, **kwargs)
+        for conv in fresh:          # moved or cast with their factors, not rewritten: the factors still describe them
+            lowrank.stamp(self, conv)
+        return out
 
     def grad_overflowed(self, reset=True):
         """True when a backward pass since the last call had to clamp a scaled gradient (grad_scale x dY / dX) to the
@@ -618,6 +633,15 @@ class Darknet(nn.Module):
         library call over all tied layers with no host synchronisation; every engine re-packs before its next forward."""
         from . import share
         share.project_codebooks(self)
+
+    def set_factors(self, factors):
+        """Tie the weights to low-rank factors (an addition beyond the reference; lowrank.py): `factors` is what
+        lowrank.lowrank_factor returns, one (U, V) or None per conv block in set_masks order.  Registers the buffers
+        `factor_u` and `factor_v` on each MaskedConv2d named -- only here, like set_codebooks: an unfactored model's
+        state_dict is unchanged -- and sets its weight to V @ U.  Raises, naming the block, if it carries a mask or a
+        codebook.  All None removes the factors."""
+        from . import lowrank
+        lowrank.set_factors(self, factors)
 
     def set_masks(self, masks):
         """nets.py:1053-1061: hand masks[count] to every MaskedConv2d in module order.  Like the

@@ -10,7 +10,7 @@ import weakref
 import torch
 
 from . import _lib as L
-from ._lib import (ConvGeom, ConvEpilogue, SplitkInfo, ActDesc, ActBwdDesc, DgradSums, ChanMap, PackJob, StemBlockDesc, FoldDesc, FoldJob, check, ptr,
+from ._lib import (ConvGeom, ConvEpilogue, SplitkInfo, LowrankInfo, ActDesc, ActBwdDesc, DgradSums, ChanMap, PackJob, StemBlockDesc, FoldDesc, FoldJob, check, ptr,
                    stream_ptr)
 
 HALF = torch.float16
@@ -1334,6 +1334,52 @@ def conv_fwd_raw_splitk(g, x, wp, y, y_ld, y_choff=0, slices=0, workspace=None, 
     """conv_fwd_raw(..., stats=None) with the K axis cut into `slices` slices: y[M][y_ld] fp16 raw conv output.
     `overflow`: as conv_fwd_splitk."""
     return _splitk(g, x, wp, _epi(L.EPI_RAW_F16, y, y_ld, y_choff, overflow=overflow), slices, workspace)
+
+
+# ----------------------------------------------------------------------------- low-rank (factored) forward
+def conv_fwd_lowrank_ok(g, rank):
+    """Does mcamd_conv_fwd_lowrank accept this geometry with this rank (ksize 1 or 3, rank a multiple of 32 in [32, 256],
+    cout % 8 == 0)?  Needs no GPU."""
+    return bool(L.lib().mcamd_conv_fwd_lowrank_ok(C.byref(g), int(rank)))
+
+
+def conv_fwd_lowrank_info(g, rank):
+    """mcamd_lowrank_info of the launch conv_fwd_lowrank takes for (`g`, rank): the kernel instance (rank_padded), its tiles,
+    grid and LDS bytes, and the fp16 elements of the two packed operands.  Host logic only; raises where _ok refuses."""
+    info = LowrankInfo()
+    check(L.lib().mcamd_conv_fwd_lowrank_info(C.byref(g), int(rank), C.byref(info)), "mcamd_conv_fwd_lowrank_info")
+    return info
+
+
+def pack_lowrank(g, u, v, out_up=None, out_vp=None):
+    """fp32 factors U [r][cin][k][k] and V [cout][r] -> (up, vp), the fp16 operands of conv_fwd_lowrank: U in the packed K
+    order of an r-filter forward, V as a 1 x 1 operand over r channels, pad rows and channels zero (mcamd_pack_lowrank)."""
+    _need_cuda(u, v)
+    assert u.dtype == torch.float32 and v.dtype == torch.float32 and u.is_contiguous() and v.is_contiguous()
+    rank = int(u.shape[0])
+    if tuple(u.shape) != (rank, g.cin, g.ksize, g.ksize) or tuple(v.shape) != (g.cout, rank):
+        raise L.McamdError("pack_lowrank: factors %s / %s do not fit the geometry" % (tuple(u.shape), tuple(v.shape)))
+    info = conv_fwd_lowrank_info(g, rank)
+    if out_up is None:
+        out_up = torch.empty(info.up_elems, dtype=HALF, device=u.device)
+    if out_vp is None:
+        out_vp = torch.empty(info.vp_elems, dtype=HALF, device=u.device)
+    if out_up.numel() < info.up_elems or out_vp.numel() < info.vp_elems:
+        raise L.McamdError("pack_lowrank: destination too small")
+    check(L.lib().mcamd_pack_lowrank(C.byref(g), rank, ptr(u), ptr(v), ptr(out_up), ptr(out_vp), stream_ptr()), "mcamd_pack_lowrank")
+    return out_up, out_vp
+
+
+def conv_fwd_lowrank(g, rank, x, up, vp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None, y2_ld=0,
+                     y2_choff=0, overflow=None):
+    """A factored block in one launch: conv_fwd_raw of `g` to `rank` channels (fp16, saturated) and conv_fwd_padded of the
+    1 x 1 block over them, the intermediate kept in LDS (csrc/conv_lowrank.hip).  Epilogue arguments and output as
+    conv_fwd_padded; `overflow`: optional int32 flag, set to 1 when an intermediate or an output was clamped to +-65504."""
+    _need_cuda(x, up, vp)
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff, overflow=overflow)
+    check(L.lib().mcamd_conv_fwd_lowrank(C.byref(g), int(rank), ptr(x), ptr(up), ptr(vp), C.byref(e), stream_ptr()),
+          "mcamd_conv_fwd_lowrank")
 
 
 # ----------------------------------------------------------------------------- fp8 (e4m3) quantised inference

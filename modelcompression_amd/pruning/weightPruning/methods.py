@@ -15,6 +15,7 @@ from ... import ops
 from ..._lib import McamdError
 from .utils import prune_rate, arg_nonzero_min
 from ...share import kmeans_share  # noqa: F401  (the stage behind pruning: weight sharing, share.py)
+from ...lowrank import lowrank_factor  # noqa: F401  (low-rank factorisation of the dense layers, lowrank.py)
 from ...importance import taylor_prune  # noqa: F401  (ranking by first-order Taylor importance, importance.py)
 from ...sparsify import GroupLasso  # noqa: F401  (block and filter sparsity learned while training, sparsify.py)
 
