@@ -608,6 +608,42 @@ int mcamd_conv_fwd_q8_w4(const mcamd_conv_geom* g, const void* x8, const void* c
 int mcamd_conv_fwd_q8_w4_info(const mcamd_conv_geom* g, int32_t out[7]);
 
 /* ---------------------------------------------------------------------------
+ * ... with the codes fed to the matrix instruction AS fp4 (an addition beyond the reference; conv_q8_w4_mx.hip,
+ * Darknet.precision = "fp8-w4-mx").  The quantisation is the one above, unchanged -- e4_f, the groups, the
+ * shifts g, the codes and their rounding.  The grid with the sign in bit 3 is OCP e2m1, a group is one lane's 32 k of a 64-k
+ * chunk and 2^g is the e8m0 byte 127 + g, so v_mfma_scale_f32_32x32x64_f8f6f4 multiplies the codes (A, 4 bits, one scale per
+ * lane) with the e4m3 activations (B) directly: no expansion to bytes in registers.  Only the layout differs from
+ * mcamd_pack_q8_w4's -- it is what the instruction consumes without a shuffle:
+ *   wexp:   int32 [Npad], e4_f (pad rows 0), as above;
+ *   scales: bytes [ktot / 64][Npad][2]: scales[(q * Npad + n) * 2 + j] = 127 + g of group j of chunk q of row n (the positions
+ *           [64 q + 32 j, +32) of mcamd_pack_q8's order); pad rows 127;
+ *   codes:  bytes [Npad][ktot / 2]; chunk q of row n is the 32 bytes [32 q, 32 q + 32); piece h = 0, 1 is 16 bytes and holds
+ *           group h, the chunk's positions [32 h, 32 h + 32): byte i of the piece has position 32 h + 2 i in its LOW nibble and
+ *           32 h + 2 i + 1 in its HIGH nibble -- the order the instruction reads an fp4 operand in: element e of lane (r, h), bits
+ *           [4 e, 4 e + 4) of its four registers, is k = 32 h + e of row r (measured by tools/f4_probe.hip; the 8-bit operand
+ *           it meets holds k = 16 h + e for e < 16 and 32 + 16 h + (e - 16) above).  Pad rows: zero codes.
+ *   output  v = leaky(scale_f * 2^-(e4_f + 1) * S + shift_f), S = sum over groups of 2^g * sum a8 * grid[code]: the S above
+ *           in the arithmetic of the block-scaled fp8 MFMA (MCAMD_Q8_MFMA=1's), whatever MCAMD_Q8_MFMA says: not byte-exact
+ *           (that instruction drops products far below the largest of their group).
+ * The operand sizes are mcamd_q8_w4_elems's.
+ * ------------------------------------------------------------------------- */
+/* mcamd_conv_fwd_q8_w4_ok's predicate. */
+int32_t mcamd_conv_fwd_q8_w4_mx_ok(const mcamd_conv_geom* g);
+/* OIHW fp32 master (* mask, may be NULL) -> that packing, on the device, no atomics.  Every row up to Npad is written. */
+int mcamd_pack_q8_w4_mx(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* codes, void* scales,
+                        int32_t* wexp, void* stream);
+/* codes + scales -> wq: the e4m3 bytes W8x, [Npad][ktot] in exactly mcamd_pack_q8's layout (pad rows zero bytes) -- equal to
+ * mcamd_unpack_q8_w4 of mcamd_pack_q8_w4 on the same weights. */
+int mcamd_unpack_q8_w4_mx(const mcamd_conv_geom* g, const void* codes, const void* scales, void* wq, void* stream);
+/* The forward from that packing: epi->mode MCAMD_EPI_PAD_F16 only; dst_mode, y2, y_f8 / y2_f8, both `pad` forms of x and the
+ * overflow flag as mcamd_conv_fwd_q8_w4.  Any batch size. */
+int mcamd_conv_fwd_q8_w4_mx(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* scales, const int32_t* wexp,
+                            const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream);
+/* The kernel instance it launches (host logic only), out as mcamd_conv_fwd_q8_info's: the tile mcamd_conv_fwd_q8 takes for the
+ * geometry under MCAMD_Q8_MFMA=1 (256 x 128 from 256 filters, 128 x 128 from 128, 64 x 128 below), out[2] = 1 always. */
+int mcamd_conv_fwd_q8_w4_mx_info(const mcamd_conv_geom* g, int32_t out[7]);
+
+/* ---------------------------------------------------------------------------
  * 4-bit quantisation-aware training (an addition beyond the reference; Darknet.precision = "fp8-w4-qat"): the
  * fp8 quantisation-aware training above with the weights of every fp8 block in the 4-bit format above -- the training-mode
  * forward of a block runs on the codes it would be deployed with under "fp8-w4".

@@ -1425,6 +1425,63 @@ extern "C" int mcamd_conv_fwd_q8_w4_info(const mcamd_conv_geom* g, int32_t out[7
     return MCAMD_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// ... with the codes fed to the block-scaled MFMA as fp4 (conv_q8_w4_mx.hip; Darknet.precision = "fp8-w4-mx"):
+// mcamd_pack_q8_w4's quantisation in the instruction's layout; the operand sizes are mcamd_q8_w4_elems's
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t mcamd_conv_fwd_q8_w4_mx_ok(const mcamd_conv_geom* g) { return mcamd_conv_fwd_q8_w4_ok(g); }
+
+extern "C" int mcamd_pack_q8_w4_mx(const mcamd_conv_geom* g, const float* w_oihw, const float* mask_oihw, void* codes, void* scales,
+                                   int32_t* wexp, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "pack_q8_w4_mx: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_pack_q8_w4_mx(&g_, w_oihw, mask_oihw, codes, scales, wexp, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_w4_mx_ok(g), "pack_q8_w4_mx: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_mx_ok)");
+    MCAMD_REQUIRE(w_oihw && codes && scales && wexp, "pack_q8_w4_mx: null pointer");
+    return mcamd_pack_q8_w4_mx_launch(w_oihw, mask_oihw, codes, scales, wexp, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
+}
+
+extern "C" int mcamd_unpack_q8_w4_mx(const mcamd_conv_geom* g, const void* codes, const void* scales, void* wq, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g, "unpack_q8_w4_mx: null geometry");
+        const mcamd_conv_geom g_ = *g;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_unpack_q8_w4_mx(&g_, codes, scales, wq, s); });
+    }
+    MCAMD_REQUIRE(g && mcamd_conv_fwd_q8_w4_mx_ok(g), "unpack_q8_w4_mx: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_mx_ok)");
+    MCAMD_REQUIRE(codes && scales && wq, "unpack_q8_w4_mx: null pointer");
+    return mcamd_unpack_q8_w4_mx_launch(codes, scales, wq, g->cout, g->cin, ntaps_of(g), (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_q8_w4_mx(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* scales,
+                                       const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8,
+                                       void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_w4_mx: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_conv_fwd_q8_w4_mx(&g_, x8, codes, scales, wexp, &e_, y_f8, y2_f8, s); });
+    }
+    if (check_geom(g, "conv_fwd_q8_w4_mx")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_w4_mx_ok(g), "conv_fwd_q8_w4_mx: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_mx_ok)");
+    MCAMD_REQUIRE(x8 && codes && scales && wexp, "conv_fwd_q8_w4_mx: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8_w4_mx: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x8, codes, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_w4_mx", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    return mcamd_conv_q8_w4_mx_launch(a, scales, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
+}
+
+// mcamd_q8_w4_mx_choice()'s answer: what mcamd_conv_fwd_q8_w4_mx launches for this geometry (host logic only)
+extern "C" int mcamd_conv_fwd_q8_w4_mx_info(const mcamd_conv_geom* g, int32_t out[7]) {
+    MCAMD_REQUIRE(g && out, "conv_fwd_q8_w4_mx_info: null argument");
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_w4_mx_ok(g), "conv_fwd_q8_w4_mx_info: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_mx_ok)");
+    const Q8Choice c = mcamd_q8_w4_mx_choice((long long)g->B * g->H * g->W, g->cout);
+    out[0] = c.bmw, out[1] = c.bnp, out[2] = c.f8mfma, out[3] = c.stages, out[4] = c.mtiles, out[5] = c.ntiles, out[6] = c.grid;
+    return MCAMD_OK;
+}
+
 // mcamd_q8_choice()'s answer: what mcamd_conv_fwd_q8 (forms 0, 1), mcamd_conv_fwd_q8_slim (form 2) and
 // mcamd_conv_fwd_q8_sparse24 (form 3) launch for this geometry (host logic only)
 extern "C" int mcamd_conv_fwd_q8_info(const mcamd_conv_geom* g, int32_t form, int32_t out[7]) {

@@ -208,6 +208,13 @@ int mcamd_unpack_q8_w4_launch(const void* codes, const void* gshift, void* wq, i
 int mcamd_conv_q8_w4_raw_launch(IgemmArgs& a, const void* gshift, const void* wexp, hipStream_t st);
 int mcamd_fakequant_q8_w4_launch(const void* codes, const void* gshift, const void* wexp, float* out, int cout, int cin, int ntaps,
                                  hipStream_t st);
+// conv_q8_w4_mx.hip: the same quantisation in the layout the block-scaled MFMA consumes as an fp4 operand (a.w = the codes,
+// `scales` = e8m0 bytes 127 + g); its choice (the three fp8-MFMA tiles, whatever MCAMD_Q8_MFMA says), packer and expander
+Q8Choice mcamd_q8_w4_mx_choice(long long M, int N);
+int mcamd_conv_q8_w4_mx_launch(IgemmArgs& a, const void* scales, const void* wexp, int y_f8, int y2_f8, hipStream_t st);
+int mcamd_pack_q8_w4_mx_launch(const float* w, const float* mask, void* codes, void* scales, void* wexp, int cout, int cin, int ntaps,
+                               hipStream_t st);
+int mcamd_unpack_q8_w4_mx_launch(const void* codes, const void* scales, void* wq, int cout, int cin, int ntaps, hipStream_t st);
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps);
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);

@@ -91,7 +91,7 @@ class _Layer:
     sp_on = property(lambda self: self.form == "sparse24")
     bs_on = property(lambda self: self.form == "bsparse")
     sk_on = property(lambda self: self.form == "splitk")
-    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_bsparse"))
+    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_bsparse"))
     q8s_on = property(lambda self: self.form == "q8_sparse24")
     q8_slim = property(lambda self: self.form == "q8_slim")
 
@@ -523,8 +523,27 @@ class _Q8W4(_Q8):
         eng._timed('fwd', lay, ops.conv_fwd_q8_w4_raw, lay.geom_act, x8, lay.w4c, lay.w4g, lay.wexp4, lay.y, lay.cout, 0, lay.stats)
 
 
+class _Q8W4Mx(_Q8):
+    """An fp8 block whose 4-bit codes go to the block-scaled MFMA as its fp4 operand ("fp8-w4-mx", csrc/conv_q8_w4_mx.hip,
+    DESIGN.md 3zg): _Q8W4's quantisation and buffer sizes in the instruction's layout, the group shifts as e8m0 scale bytes.
+    The buffers are _Q8W4's fields: an engine has one precision, so a block only ever holds one of the two layouts.
+    The block packs the VALUES its codes stand for, not the weights themselves: a group whose largest weight rounds down to 3
+    2^g re-quantises to the same values under the shift g - 1 (22 % of the groups of a Gaussian layer), and the instruction's
+    truncation depends on which (code, scale) pair stands for a value (one fp16 step in ~1 % of the outputs).
+    Packed this way a model and its "w4" model file -- whose masters ARE those values -- run on equal operands."""
+    fwd, elems, packer = "conv_fwd_q8_w4_mx", "q8_w4_elems", "pack_q8_w4_mx"
+    bufs = _Q8W4.bufs
+
+    def pack(self, eng, lay, w, mask):
+        g, ops_ = lay.geom_q8, (lay.w4c, lay.w4g, lay.wexp4)
+        ops.pack_q8_w4(g, w, mask, *ops_)
+        values = ops.fakequant_q8_w4(g, *ops_)      # (fp32 OIHW, one layer at a time, freed behind the pack)
+        ops.pack_q8_w4_mx(g, values, None, *ops_)
+
+
 _FORMS = {"dense": _Dense(), "splitk": _SplitK(), "lowrank": _LowRank(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "bsparse_train": _BSparseTrain(), "q8": _Q8(),
-          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4(), "q8_bsparse": _Q8BSparse()}
+          "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4(), "q8_w4_mx": _Q8W4Mx(),
+          "q8_bsparse": _Q8BSparse()}
 
 
 def _probe_side_stream(device, tries=8):
@@ -597,6 +616,10 @@ class Engine:
         its weights as e2m1 codes with a shift per group of 32 input channels (csrc/conv_q8_w4.hip, `fp8_w4_layers`) and
         computes what the fp8 block computes on the e4m3 bytes those codes stand for; the slim blocks and every other block
         run what "fp8" runs.
+        "fp8-w4-mx" -- the "fp8-w4" engine with every block that would take form "q8_w4" on form "q8_w4_mx" (DESIGN.md 3zg),
+        inference only: the same codes, shifts and exponents in the layout v_mfma_scale_f32_32x32x64_f8f6f4 takes as an fp4
+        operand with per-lane e8m0 scales (csrc/conv_q8_w4_mx.hip, `fp8_w4_mx_layers`) -- no expansion in registers, the
+        arithmetic of MCAMD_Q8_MFMA=1 whatever that switch says; every other block runs what "fp8-w4" runs.
         "fp8-w4-qat" -- 4-bit quantisation-aware training: "fp8-qat" with the weights of every fp8 block in the
         4-bit format -- in training mode every block of `fp8_layers` (`fp8_w4_layers` is the same list) re-quantises its weights
         to codes, shifts and exponents every step and runs its forward on them (mcamd_conv_fwd_q8_w4_raw); the backward is
@@ -606,18 +629,19 @@ class Engine:
         most Darknet.fp8_block_max_kept, keeps its filters out of the compaction and runs the block-sparse fp8 kernel on the
         chunks that hold a non-zero weight byte (csrc/conv_q8_bsparse.hip, `fp8_block_layers`, `fp8_block_kept`); every
         other block runs what "fp8" runs, and with nothing chosen it is the "fp8" engine bit for bit."""
-        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat",
-                             "fp8-block"):
+        if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx",
+                             "fp8-w4-qat", "fp8-block"):
             raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk', 'fp8-qat', 'fp8-w4', "
-                             "'fp8-w4-qat' or 'fp8-block' (got %r)" % (precision,))
+                             "'fp8-w4-mx', 'fp8-w4-qat' or 'fp8-block' (got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat", "fp8-block")
+        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx", "fp8-w4-qat",
+                                         "fp8-block")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_choose_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-qat", "fp8-block")
+        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx", "fp8-w4-qat", "fp8-block")
         self.qat = precision in ("fp8-qat", "fp8-w4-qat")   # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
         # "fp8-2:4": the subset of fp8_layers whose masks conform to 2:4 and that run mcamd_conv_fwd_q8_sparse24
@@ -631,6 +655,9 @@ class Engine:
         # a training engine, which has no slim blocks)
         self.q8_w4 = precision in ("fp8-w4", "fp8-w4-qat")
         self.fp8_w4_layers = []
+        # "fp8-w4-mx": the blocks "fp8-w4" runs on 4-bit weights, on the fp4-operand kernel instead (form "q8_w4_mx")
+        self.q8_w4_mx = precision == "fp8-w4-mx"
+        self.fp8_w4_mx_layers = []
         # "fp8-block": the subset of fp8_layers the block policy chose and that run mcamd_conv_fwd_q8_bsparse, and the kept-chunk
         # fraction of every candidate (conv number -> fraction); chosen when the masks, the weights or
         # Darknet.fp8_block_max_kept change (_Q8BSparse.policy; the chosen blocks share `_bs_exempt` with sparse = "block")
@@ -1360,7 +1387,7 @@ class Engine:
           2. filter compaction and folding, planned again when the masks or that choice changed;
           3. then fp8 (every eligible block of an fp8 engine; under "fp8-splitk" behind it: every block of form "q8" -- not the
              slim ones -- whose launch the split-K policy gives two slices or more, mcamd_conv_fwd_q8_splitk_info; under
-             "fp8-w4" every block of form "q8" takes the 4-bit form "q8_w4"), 2:4
+             "fp8-w4" every block of form "q8" takes the 4-bit form "q8_w4", under "fp8-w4-mx" the form "q8_w4_mx"), 2:4
              (sparse = "2:4": every eligible block whose mask conforms and whose geometry mcamd_conv_fwd_sparse24_ok accepts)
              or block-sparse (sparse = "block": the chosen blocks that
              are still eligible -- one whose producer was compacted after all, so that its input channels are permuted, stays
@@ -1401,10 +1428,10 @@ class Engine:
                 for lay in self.layers:
                     if lay.li in exempt and lay.form == "q8" and ops.conv_fwd_q8_bsparse_ok(lay.geom_q8):
                         lay.form = "q8_bsparse"
-            if self.q8_w4:               # (the slim blocks keep their form, as under "fp8-splitk")
+            if self.q8_w4 or self.q8_w4_mx:   # (the slim blocks keep their form, as under "fp8-splitk")
                 for lay in self.layers:
                     if lay.form == "q8" and ops.conv_fwd_q8_w4_ok(lay.geom_q8):
-                        lay.form = "q8_w4"
+                        lay.form = "q8_w4_mx" if self.q8_w4_mx else "q8_w4"
         elif sparse == "2:4":
             for lay in self._conforming([lay for lay in self.layers
                                          if self._eligible(lay) and lay.conv.mask_flag and lay.cin % 4 == 0
@@ -1443,7 +1470,8 @@ class Engine:
         nums = lambda *names: [lay.li + 1 for lay in self.layers if lay.form in names]
         self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
         self.lowrank_layers = nums("lowrank")
-        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_bsparse")
+        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_bsparse")
+        self.fp8_w4_mx_layers = nums("q8_w4_mx")
         self.fp8_block_layers = nums("q8_bsparse")
         if self._training:                   # (what the last training-mode choice was; an eval pass in between keeps it)
             self.bsparse_train_layers = nums("bsparse_train")

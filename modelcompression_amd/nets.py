@@ -312,6 +312,10 @@ class Darknet(nn.Module):
         # "fp8-w4" (eval only, an opt-in): the "fp8" engine with the weights of every dense fp8 block held as 4-bit e2m1 codes
         # + one shift per group of 32 input channels, 4.25 bits per weight resident, expanded to e4m3 bytes in the kernel's
         # registers (engine.Engine.fp8_w4_layers, csrc/conv_q8_w4.hip); `sparse` and `splitk` stay off with it.
+        # "fp8-w4-mx" (eval only, an opt-in): the "fp8-w4" engine with those codes fed to the block-scaled MFMA as its fp4 operand
+        # and the group shifts as its per-lane e8m0 scales -- the same quantisation and resident bytes, no expansion in registers,
+        # the arithmetic of MCAMD_Q8_MFMA=1 (engine.Engine.fp8_w4_mx_layers, csrc/conv_q8_w4_mx.hip); `sparse` and
+        # `splitk` stay off with it.
         # "fp8-w4-qat" (an addition beyond the reference): 4-bit quantisation-aware training -- "fp8-qat" with the weights of every
         # fp8 block re-quantised to the "fp8-w4" format every step: the training-mode forward multiplies the codes the block would
         # be deployed with, the backward is straight-through on the values they stand for; in eval mode it is the "fp8-w4" engine,

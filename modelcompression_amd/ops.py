@@ -1659,7 +1659,7 @@ def q8_w4_elems(g):
     return int(out[0]), int(out[1]), int(out[2])
 
 
-def pack_q8_w4(g, w, mask=None, out_codes=None, out_shift=None, out_exp=None):
+def pack_q8_w4(g, w, mask=None, out_codes=None, out_shift=None, out_exp=None, _entry="mcamd_pack_q8_w4"):
     """fp32 OIHW master (* mask) -> (e2m1 nibble codes, one shift byte per group of 32 input channels, int32 exponent per
     filter) of the 4-bit forward (mcamd_pack_q8_w4; the layout is stated in include/mcamd.h)."""
     _need_cuda(w, mask)
@@ -1672,13 +1672,12 @@ def pack_q8_w4(g, w, mask=None, out_codes=None, out_shift=None, out_exp=None):
     if out_exp is None:
         out_exp = torch.empty(ne, dtype=torch.int32, device=w.device)
     if out_codes.numel() < nc or out_shift.numel() < ng or out_exp.numel() < ne:
-        raise L.McamdError("pack_q8_w4: destination too small")
-    check(L.lib().mcamd_pack_q8_w4(C.byref(g), ptr(w), ptr(mask), ptr(out_codes), ptr(out_shift), ptr(out_exp), stream_ptr()),
-          "mcamd_pack_q8_w4")
+        raise L.McamdError("%s: destination too small" % _entry[6:])
+    check(getattr(L.lib(), _entry)(C.byref(g), ptr(w), ptr(mask), ptr(out_codes), ptr(out_shift), ptr(out_exp), stream_ptr()), _entry)
     return out_codes, out_shift, out_exp
 
 
-def unpack_q8_w4(g, codes, gshift, out_w=None):
+def unpack_q8_w4(g, codes, gshift, out_w=None, _entry="mcamd_unpack_q8_w4"):
     """The e4m3 bytes the 4-bit packing stands for, in pack_q8's layout (mcamd_unpack_q8_w4): conv_fwd_q8 on them with
     pack_q8_w4's exponents computes what conv_fwd_q8_w4 computes."""
     _need_cuda(codes, gshift)
@@ -1687,8 +1686,8 @@ def unpack_q8_w4(g, codes, gshift, out_w=None):
         out_w = torch.empty(nw, dtype=torch.uint8, device=codes.device)
     nc, ng, _ = q8_w4_elems(g)
     if out_w.numel() < nw or codes.numel() < nc or gshift.numel() < ng:
-        raise L.McamdError("unpack_q8_w4: operand too small")
-    check(L.lib().mcamd_unpack_q8_w4(C.byref(g), ptr(codes), ptr(gshift), ptr(out_w), stream_ptr()), "mcamd_unpack_q8_w4")
+        raise L.McamdError("%s: operand too small" % _entry[6:])
+    check(getattr(L.lib(), _entry)(C.byref(g), ptr(codes), ptr(gshift), ptr(out_w), stream_ptr()), _entry)
     return out_w
 
 
@@ -1701,13 +1700,46 @@ def conv_fwd_q8_w4_info(g):
 
 
 def conv_fwd_q8_w4(g, x8, codes, gshift, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None,
-                   y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None):
+                   y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None, _entry="mcamd_conv_fwd_q8_w4"):
     """conv_fwd_q8 on 4-bit weights (mcamd_conv_fwd_q8_w4): the same arguments with pack_q8_w4's codes and shift bytes in
     place of the weight bytes, the arithmetic of conv_fwd_q8 on unpack_q8_w4's bytes.  `overflow`: as conv_fwd_q8."""
     e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
              y2_choff=y2_choff, overflow=overflow)
-    check(L.lib().mcamd_conv_fwd_q8_w4(C.byref(g), ptr(x8), ptr(codes), ptr(gshift), ptr(wexp), C.byref(e), int(bool(y_f8)),
-                                       int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q8_w4")
+    check(getattr(L.lib(), _entry)(C.byref(g), ptr(x8), ptr(codes), ptr(gshift), ptr(wexp), C.byref(e), int(bool(y_f8)),
+                                   int(bool(y2_f8)), stream_ptr()), _entry)
+
+
+# ... fed to the block-scaled MFMA as fp4 (DESIGN.md 3zg): the same quantisation and operand sizes, the instruction's layout
+def conv_fwd_q8_w4_mx_ok(g):
+    """Does mcamd_conv_fwd_q8_w4_mx accept this geometry?  (conv_fwd_q8_w4_ok's predicate; needs no device.)"""
+    return bool(L.lib().mcamd_conv_fwd_q8_w4_mx_ok(C.byref(g)))
+
+
+def pack_q8_w4_mx(g, w, mask=None, out_codes=None, out_scales=None, out_exp=None):
+    """pack_q8_w4's codes and exponents with the codes in the order the fp4 MFMA operand takes them and the group shifts as
+    e8m0 bytes 127 + g (mcamd_pack_q8_w4_mx; the layout is stated in include/mcamd.h)."""
+    return pack_q8_w4(g, w, mask, out_codes, out_scales, out_exp, _entry="mcamd_pack_q8_w4_mx")
+
+
+def unpack_q8_w4_mx(g, codes, scales, out_w=None):
+    """The e4m3 bytes that packing stands for, in pack_q8's layout (mcamd_unpack_q8_w4_mx): unpack_q8_w4's of pack_q8_w4."""
+    return unpack_q8_w4(g, codes, scales, out_w, _entry="mcamd_unpack_q8_w4_mx")
+
+
+def conv_fwd_q8_w4_mx_info(g):
+    """The kernel instance conv_fwd_q8_w4_mx launches for `g` (mcamd_conv_fwd_q8_w4_mx_info): one of the three fp8-MFMA tiles,
+    whatever MCAMD_Q8_MFMA says.  Needs no GPU."""
+    out = (C.c_int32 * 7)()
+    check(L.lib().mcamd_conv_fwd_q8_w4_mx_info(C.byref(g), out), "mcamd_conv_fwd_q8_w4_mx_info")
+    return Q8Info(*out)
+
+
+def conv_fwd_q8_w4_mx(g, x8, codes, scales, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None,
+                      y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None):
+    """conv_fwd_q8_w4's arguments on pack_q8_w4_mx's operands (mcamd_conv_fwd_q8_w4_mx): the codes go to the block-scaled MFMA
+    as its fp4 operand, the group shifts as its per-lane scales -- the arithmetic of MCAMD_Q8_MFMA=1, not byte-exact."""
+    conv_fwd_q8_w4(g, x8, codes, scales, wexp, y, y_ld, y_choff, scale, shift, slope, dst_mode, y2, y2_ld, y2_choff, y_f8, y2_f8,
+                   overflow, _entry="mcamd_conv_fwd_q8_w4_mx")
 
 
 def conv_fwd_q8_w4_raw(g, x8, codes, gshift, wexp, y, y_ld, y_choff=0, stats=None):

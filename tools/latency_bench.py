@@ -4,7 +4,8 @@ B = 1, 2, 4 and 8 with split-K off and on, for the dense model and (B = 1) for a
 the on leg "fp8-splitk" (MCAMD_Q8_MFMA picks the MFMA form of both), and the fp16 legs of the dense model are
 measured in the same process beside them.  --precision fp8-w4: the off leg is precision "fp8", the on leg "fp8-w4" (4-bit
 weights) on the dense model only; nothing is split there, and the launch record and the per-layer table carry
-fields of their own (`w4_layers`; `w4`, `us_fp8`, `us_fp8_w4`) in place of the split-K ones.
+fields of their own (`w4_layers`; `w4`, `us_fp8`, `us_fp8_w4`) in place of the split-K ones.  --precision fp8-w4-mx: the same with
+the on leg "fp8-w4-mx" (the codes as the MFMA's fp4 operand; `w4_layers` is its fp8_w4_mx_layers).
 
 Method: both settings alternate in one process, PAIRS pairs; each sample is a loop of CALLS calls after warm-up with a device
 synchronise only around the whole loop (host clock), so a sample is the sustained time per call, launch overhead included;
@@ -13,7 +14,7 @@ instrumented pass (the engine's HIP events around every conv launch, plan replay
 tiles, slices, us unsplit, us split (partial + finish launch).  Launch counts: the library calls of the recorded forward plan
 (a split block is one call and two kernels), the eval-mode bn_coeffs launches among them and the layout pass in front.
 
-usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8|fp8-w4]
+usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8|fp8-w4|fp8-w4-mx]
                                                                              (--json: one JSON document on stdout)"""
 import json
 import os
@@ -35,10 +36,10 @@ def arg(name, dflt):
 
 CALLS, PAIRS, PASSES = max(200, arg("--calls", 200)), max(4, arg("--pairs", 4)), 7
 PRECISION = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp16"
-if PRECISION not in ("fp16", "fp8", "fp8-w4"):
-    raise SystemExit("--precision must be fp16, fp8 or fp8-w4 (got %r)" % PRECISION)
-W4 = PRECISION == "fp8-w4"
-ON_LEG = "fp8-w4" if W4 else "fp8-splitk"      # the on leg of an fp8 model
+if PRECISION not in ("fp16", "fp8", "fp8-w4", "fp8-w4-mx"):
+    raise SystemExit("--precision must be fp16, fp8, fp8-w4 or fp8-w4-mx (got %r)" % PRECISION)
+W4 = PRECISION in ("fp8-w4", "fp8-w4-mx")
+ON_LEG = PRECISION if W4 else "fp8-splitk"     # the on leg of an fp8 model
 if not torch.cuda.is_available():
     raise SystemExit("latency_bench needs the GPU")
 dev = torch.device("cuda", 0)
@@ -107,7 +108,7 @@ def layer_table(m, x):
         per[flag] = {k: median(v) for k, v in acc.items()}
     eng = engine(m, x)
     if W4:                      # nothing is split: the block's form on the "fp8-w4" leg and its time on either leg
-        return [{"conv": lay.li + 1, "form": lay.form, "w4": lay.form == "q8_w4", "us_fp8": per[False].get(lay.li + 1),
+        return [{"conv": lay.li + 1, "form": lay.form, "w4": lay.form in ("q8_w4", "q8_w4_mx"), "us_fp8": per[False].get(lay.li + 1),
                  "us_fp8_w4": per[True].get(lay.li + 1)} for lay in eng.layers]
     rows = []
     for lay in eng.layers:
@@ -141,7 +142,7 @@ def launches(m, x):
             "bn_coeffs": sum(1 for lay in eng.layers if lay.bn is not None),
             "layout_pass": 1}
         if W4:                  # (a w4 block is one launch, like the fp8 block it stands in for)
-            out["on" if flag else "off"]["w4_layers"] = list(eng.fp8_w4_layers)
+            out["on" if flag else "off"]["w4_layers"] = list(eng.fp8_w4_mx_layers if eng.precision == "fp8-w4-mx" else eng.fp8_w4_layers)
         else:
             out["on" if flag else "off"].update(splitk_finish_kernels=len(split_layers(eng)), splitk_layers=split_layers(eng))
     return out
@@ -174,11 +175,12 @@ def show(res):
                   % (B, what, median(off), min(off), max(off), median(on), min(on), max(on), median(off) / median(on)))
         la = r["launches"]
         if W4:
-            print("B=%s plan calls: fp8 %s, fp8-w4 %s; bn_coeffs launches %d, layout pass 1; w4 layers %s; logits rel-L2 fp8-w4 vs fp8 %.2e"
-                  % (B, la["off"]["plan_calls"], la["on"]["plan_calls"], la["on"]["bn_coeffs"], la["on"]["w4_layers"], r["rel_l2_on_vs_off"]))
+            print("B=%s plan calls: fp8 %s, %s %s; bn_coeffs launches %d, layout pass 1; w4 layers %s; logits rel-L2 %s vs fp8 %.2e"
+                  % (B, la["off"]["plan_calls"], ON_LEG, la["on"]["plan_calls"], la["on"]["bn_coeffs"], la["on"]["w4_layers"], ON_LEG,
+                     r["rel_l2_on_vs_off"]))
             for row in r.get("layers", ()):
-                print("conv%-3d %-8s us fp8 %s  us fp8-w4 %s" % (row["conv"], row["form"],
-                      "%.1f" % row["us_fp8"] if row["us_fp8"] is not None else "-",
+                print("conv%-3d %-8s us fp8 %s  us %s %s" % (row["conv"], row["form"],
+                      "%.1f" % row["us_fp8"] if row["us_fp8"] is not None else "-", ON_LEG,
                       "%.1f" % row["us_fp8_w4"] if row["us_fp8_w4"] is not None else "-"))
             continue
         print("B=%s plan calls: off %s, on %s (+%d finish kernels); bn_coeffs launches %d, layout pass 1; split layers %s; "
@@ -195,9 +197,9 @@ def show(res):
 with torch.no_grad():
     dense = init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
     dense.eval()
-    dense.precision = "fp8" if PRECISION == "fp8-w4" else PRECISION
+    dense.precision = "fp8" if W4 else PRECISION
     results = [bench_model(dense, (1, 2, 4, 8), "yolov2-voc")]
-    pruned = None if PRECISION == "fp8-w4" else init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
+    pruned = None if W4 else init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
     if pruned is not None:
         pruned.set_masks(quick_filter_prune(pruned, 60.0))
         pruned.eval()

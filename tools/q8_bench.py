@@ -8,8 +8,9 @@ fp16 with sparse = "2:4", fp8 and fp8-2:4 (windows alternated over all four).
 unfused border path) and fp8 the same way, and the table names per layer cin -> round_up(cin, 64), which blocks are fp8
 blocks (`slim`: on mcamd_conv_fwd_q8_slim, `table`: with a border table) and the time of each cast pass.  Run it once
 without and once with MCAMD_Q8_MFMA=1 for the two forms of the fp8 kernel.
---w4: "fp8" against "fp8-w4" (4-bit weights) on the same weights, the two alternated in one process, with the
-resident weight-operand bytes of the fp8 blocks under both -- once per MCAMD_Q8_MFMA form, each form in a child process of its
+--w4: "fp8" against "fp8-w4" (4-bit weights) and "fp8-w4-mx" (the codes as the MFMA's fp4 operand, 3zg; it does
+not read MCAMD_Q8_MFMA) on the same weights, the three alternated in one process, with the
+resident weight-operand bytes of the fp8 blocks under each -- once per MCAMD_Q8_MFMA form, each form in a child process of its
 own started with that switch; the merged report goes to profiles/q8_w4_bench.json unless --json names another file.
 usage: python tools/q8_bench.py [batch] [forwards per window] [--sparse | --slim PCT | --w4] [--json PATH]"""
 import json
@@ -62,7 +63,7 @@ def main(argv):
         m.set_masks(nm_prune(m))
         modes = ("fp16", "fp16+2:4", "fp8", "fp8-2:4")
     if w4:
-        modes = ("fp8", "fp8-w4")
+        modes = ("fp8", "fp8-w4", "fp8-w4-mx")
 
     def select(mode):
         m.precision, m.sparse = mode.split("+")[0], "2:4" if mode.endswith("+2:4") else None
@@ -121,7 +122,7 @@ def main(argv):
         nbytes = {p: sum(getattr(lay, name).numel() * getattr(lay, name).element_size()
                          for lay in engine(p).layers if lay.li + 1 in fp8_layers for name, _ in _FORMS[lay.form].bufs) for p in modes}
         return report_w4(B, K, out_json, os.environ.get("MCAMD_Q8_MFMA", "0"), res, rates, fp8_layers,
-                         list(engine("fp8-w4").fp8_w4_layers), nbytes)
+                         list(engine("fp8-w4").fp8_w4_layers), nbytes, list(engine("fp8-w4-mx").fp8_w4_mx_layers))
     with torch.no_grad():
         res, rates, fp8_layers, sparse_layers = measure()
 
@@ -169,31 +170,39 @@ def run_w4_forms(argv, B, K, out_json):
         json.dump(out, f, indent=1)
 
 
-def report_w4(B, K, out_json, mfma, res, rates, fp8_layers, w4_layers, nbytes):
-    d, s = res["fp8"], res["fp8-w4"]
-    rel = float((s["logits"].double() - d["logits"].double()).norm() / d["logits"].double().norm())
-    print("MCAMD_Q8_MFMA=%s; fp8 layers %s; w4 layers %s" % (mfma, fp8_layers, w4_layers))
-    print("%-6s %10s %10s %9s" % ("conv", "fp8 ms", "fp8-w4 ms", "w4 / fp8"))
+def report_w4(B, K, out_json, mfma, res, rates, fp8_layers, w4_layers, nbytes, mx_layers):
+    d, s, x = res["fp8"], res["fp8-w4"], res["fp8-w4-mx"]
+
+    def rel(a):
+        return float((a["logits"].double() - d["logits"].double()).norm() / d["logits"].double().norm())
+    print("MCAMD_Q8_MFMA=%s; fp8 layers %s; w4 layers %s; w4-mx layers %s" % (mfma, fp8_layers, w4_layers, mx_layers))
+    print("%-6s %10s %10s %12s %9s %9s %9s" % ("conv", "fp8 ms", "fp8-w4 ms", "fp8-w4-mx ms", "w4 / fp8", "mx / fp8", "mx / w4"))
     for k in sorted(d["layers"]):
-        dm, sm = d["layers"][k], s["layers"].get(k, float("nan"))
-        print("%-6s %10.3f %10.3f %9.2f%s" % ("conv%d" % k, dm, sm, sm / dm, "" if k in w4_layers else "  (not w4)"))
-    td, ts = sum(d["layers"].values()), sum(s["layers"].values())
-    print("%-6s %10.3f %10.3f %9.2f" % ("sum", td, ts, ts / td))
-    for p in ("fp8", "fp8-w4"):
+        dm, sm, xm = d["layers"][k], s["layers"].get(k, float("nan")), x["layers"].get(k, float("nan"))
+        print("%-6s %10.3f %10.3f %12.3f %9.2f %9.2f %9.2f%s" % ("conv%d" % k, dm, sm, xm, sm / dm, xm / dm, xm / sm,
+                                                             "" if k in w4_layers else "  (not w4)"))
+    td, ts, tx = sum(d["layers"].values()), sum(s["layers"].values()), sum(x["layers"].values())
+    print("%-6s %10.3f %10.3f %12.3f %9.2f %9.2f %9.2f" % ("sum", td, ts, tx, ts / td, tx / td, tx / ts))
+    for p in ("fp8", "fp8-w4", "fp8-w4-mx"):
         r = rates[p]
-        print("whole forward B=%d, %d forwards per window, %-7s %s img/s (spread %.2f %%)"
+        print("whole forward B=%d, %d forwards per window, %-10s %s img/s (spread %.2f %%)"
               % (B, K, p + ":", ["%.0f" % v for v in r], 100.0 * (max(r) - min(r)) / min(r)))
     pairs = [b / a for a, b in zip(rates["fp8"], rates["fp8-w4"])]
+    pairs_mx = [b / a for a, b in zip(rates["fp8"], rates["fp8-w4-mx"])]
+    pairs_mx_w4 = [b / a for a, b in zip(rates["fp8-w4"], rates["fp8-w4-mx"])]
     print("pairs fp8-w4 / fp8 (img/s): %s" % ["%.3f" % p for p in pairs])
-    print("resident weight-operand bytes of the fp8 blocks: fp8 %d, fp8-w4 %d (%.4f x)"
-          % (nbytes["fp8"], nbytes["fp8-w4"], nbytes["fp8-w4"] / nbytes["fp8"]))
-    print("logits rel-L2 (fp8-w4 vs fp8 engine, same weights): %.3e" % rel)
+    print("pairs fp8-w4-mx / fp8 (img/s): %s; fp8-w4-mx / fp8-w4: %s" % (["%.3f" % p for p in pairs_mx], ["%.3f" % p for p in pairs_mx_w4]))
+    print("resident weight-operand bytes of the fp8 blocks: fp8 %d, fp8-w4 %d (%.4f x), fp8-w4-mx %d"
+          % (nbytes["fp8"], nbytes["fp8-w4"], nbytes["fp8-w4"] / nbytes["fp8"], nbytes["fp8-w4-mx"]))
+    print("logits rel-L2 against the fp8 engine, same weights: fp8-w4 %.3e, fp8-w4-mx %.3e" % (rel(s), rel(x)))
     sys.stdout.flush()
     if out_json:
         with open(out_json, "w") as f:
             json.dump({"fp8_layers": fp8_layers, "fp8_w4_layers": w4_layers, "fp8_ms": d["layers"], "fp8_w4_ms": s["layers"],
                        "fp8_img_s": rates["fp8"], "fp8_w4_img_s": rates["fp8-w4"], "pairs_w4_over_fp8": pairs,
-                       "weight_operand_bytes": nbytes, "rel_l2_w4_vs_fp8": rel}, f, indent=1)
+                       "weight_operand_bytes": nbytes, "rel_l2_w4_vs_fp8": rel(s),
+                       "fp8_w4_mx_layers": mx_layers, "fp8_w4_mx_ms": x["layers"], "fp8_w4_mx_img_s": rates["fp8-w4-mx"],
+                       "pairs_w4_mx_over_fp8": pairs_mx, "pairs_w4_mx_over_w4": pairs_mx_w4, "rel_l2_w4_mx_vs_fp8": rel(x)}, f, indent=1)
 
 
 def report_slim(B, K, out_json, pct, eng, res, rates):
