@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 
 from modelcompression_amd import ops, _lib as L  # noqa: E402
 from conv_cases import _draw, DRAWS, SLOPE, reorg  # noqa: E402
+from lowrank_cases import reference  # noqa: E402
 from util import fill_padded, padded_split, whole, rel_l2  # noqa: E402
 
 DST = {"plain": L.DST_PLAIN, "pool": L.DST_POOL, "pool+y2": L.DST_POOL, "reorg": L.DST_REORG}
@@ -51,17 +52,10 @@ def case(name):
                                  shift=shift, x_ld=x_ld, x_choff=x_choff, y_ld=y_ld, y_choff=y_choff)
 
 
-def reference(c, x=None):
-    """(full-resolution fp16 output, the float64 intermediate before its rounding, whether either had to be clamped)"""
-    h = F.conv2d((c.x if x is None else x).double(), c.u.double(), padding=c.k // 2)
-    hh = h.clamp(-65504.0, 65504.0).half().double()
-    z = F.conv2d(hh, c.v.double().view(c.cout, c.r, 1, 1)) * c.scale.double().view(1, -1, 1, 1) + c.shift.double().view(1, -1, 1, 1)
-    z = torch.where(z > 0, z, z * SLOPE)
-    return z.clamp(-65504.0, 65504.0).half(), h, bool((z.abs() > 65504).any() or (h.abs() > 65504).any())
-
-
-def launch(dev, c, u=None, v=None):
-    """One fused launch into NaN-filled destinations; returns the [(slice, everything else)] of y and, when present, y2."""
+def launch(dev, c, u=None, v=None, overflow=True):
+    """One fused launch into NaN-filled destinations; returns the [(slice, everything else)] of y and, when present, y2, and the
+    overflow flag (cleared before the launch; overflow=False: the launch gets none, and None is returned).  The full-resolution
+    copy lies in y's slice unless the case names one of its own (y2_ld, y2_choff); scale / shift may be None."""
     u, v = (c.u if u is None else u), (c.v if v is None else v)
     r = u.shape[0]
     g = ops.geom(c.B, c.H, c.W, c.k, c.cin, c.cout, c.x_ld, c.x_choff)
@@ -71,18 +65,20 @@ def launch(dev, c, u=None, v=None):
     nch = 4 * c.cout if c.dst == "reorg" else c.cout
     y = ops.alloc_padded(c.B, ho, wo, c.y_ld, dev)
     whole(y).fill_(float("nan"))
-    y2 = None
+    y2, y2_ld, y2_choff = None, 0, 0
     if c.dst == "pool+y2":
-        y2 = ops.alloc_padded(c.B, c.H, c.W, c.y_ld, dev)
+        y2_ld, y2_choff = getattr(c, "y2_ld", 0) or c.y_ld, (c.y2_choff if getattr(c, "y2_ld", 0) else c.y_choff)
+        y2 = ops.alloc_padded(c.B, c.H, c.W, y2_ld, dev)
         whole(y2).fill_(float("nan"))
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    ops.conv_fwd_lowrank(g, r, xbuf, up, vp, y, c.y_ld, c.y_choff, c.scale.to(dev), c.shift.to(dev), SLOPE, dst_mode=DST[c.dst],
-                         y2=y2, y2_ld=c.y_ld if y2 is not None else 0, y2_choff=c.y_choff if y2 is not None else 0, overflow=flag)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if overflow else None
+    scale, shift = (None if t is None else t.to(dev) for t in (c.scale, c.shift))
+    ops.conv_fwd_lowrank(g, r, xbuf, up, vp, y, c.y_ld, c.y_choff, scale, shift, SLOPE, dst_mode=DST[c.dst],
+                         y2=y2, y2_ld=y2_ld, y2_choff=y2_choff, overflow=flag)
     torch.cuda.synchronize()
     out = [padded_split(y, c.B, ho, wo, c.y_ld, c.y_choff, nch)]
     if y2 is not None:
-        out.append(padded_split(y2, c.B, c.H, c.W, c.y_ld, c.y_choff, c.cout))
-    return out, int(flag.item())
+        out.append(padded_split(y2, c.B, c.H, c.W, y2_ld, y2_choff, c.cout))
+    return out, (int(flag.item()) if overflow else None)
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -121,3 +121,63 @@ def test_staleness_and_rules(dev):
     m.train()                                    # training ignores the switch
     m(x)
     assert [e for e in m._engines.values() if e.train_layout][0].lowrank_layers == []
+
+
+def test_decision_rule_at_its_boundaries(dev):
+    """r (K + Cout) <= max_cost K Cout and mtiles >= min_tiles, each at its boundary: conv9 (10 x 10 at this input, 4 tiles) is
+    chosen at lowrank_min_tiles = 4 and left dense at 5; conv13 is chosen at its own ratio times (1 + 1e-6) and left dense at
+    (1 - 1e-6) -- every other block follows the same inequality -- and the blocks a rule leaves dense run the dense launch:
+    the logits equal those of a model that carries the same weights and factors for the chosen blocks only."""
+    from modelcompression_amd import ops
+    m, x, off, on = shared(dev)
+    cs = convs(m)
+    K = {n: cs[n - 1].weight[0].numel() for n in RANKS}
+    cout = {n: cs[n - 1].weight.shape[0] for n in RANKS}
+    ratio = {n: RANKS[n] * (K[n] + cout[n]) / (K[n] * cout[n]) for n in RANKS}
+
+    def mtiles(n):
+        lay = [lay for lay in engine_for(m, x).layers if lay.li + 1 == n][0]
+        return ops.conv_fwd_lowrank_info(lay.geom_act, RANKS[n]).mtiles
+
+    def run(max_cost, min_tiles):
+        m.lowrank_max_cost, m.lowrank_min_tiles = max_cost, min_tiles
+        with torch.no_grad():
+            y = m(x).clone()
+        return y, engine_for(m, x).lowrank_layers
+
+    def only(chosen):
+        """the logits of a model with m's weights whose factors cover `chosen` alone, every one of them forced on"""
+        p = fresh_model(dev, factored=False)
+        for a, b in zip(convs(p), cs):
+            a.weight.data.copy_(b.weight.data)
+        p.set_factors([(b.factor_u, b.factor_v) if n in chosen else None for n, b in enumerate(cs, 1)])
+        assert all(torch.equal(a.weight.data, b.weight.data) for a, b in zip(convs(p), cs))
+        p.lowrank, p.lowrank_max_cost, p.lowrank_min_tiles = True, 1.0, 1
+        with torch.no_grad():
+            y = p(x).clone()
+        assert engine_for(p, x).lowrank_layers == sorted(chosen)
+        return y
+
+    try:
+        tiles = {n: mtiles(n) for n in RANKS}
+        assert tiles[9] == 2 * 10 * 10 // 64 + 1 and tiles[15] < tiles[9]
+        y, chosen = run(1.0, tiles[9])
+        assert 9 in chosen and chosen == [n for n in sorted(RANKS) if tiles[n] >= tiles[9]] and chosen != sorted(RANKS)
+        assert torch.equal(y, only(chosen))
+        y, chosen = run(1.0, tiles[9] + 1)
+        assert 9 not in chosen and chosen == [n for n in sorted(RANKS) if tiles[n] >= tiles[9] + 1]
+        assert chosen or torch.equal(y, off)
+        for sign, inside in ((1.0, True), (-1.0, False)):
+            cost = ratio[13] * (1.0 + sign * 1e-6)
+            y, chosen = run(cost, 1)
+            assert (13 in chosen) == inside
+            assert chosen == [n for n in sorted(RANKS) if RANKS[n] * (K[n] + cout[n]) <= cost * K[n] * cout[n]]
+            if inside:
+                assert 0 < len(chosen) < len(RANKS) and torch.equal(y, only(chosen))
+            else:
+                assert not any(abs(ratio[n] - ratio[13]) < 1e-9 for n in chosen)
+                assert chosen or torch.equal(y, off)
+    finally:
+        m.lowrank_max_cost, m.lowrank_min_tiles = 1.0, 1
+    with torch.no_grad():
+        assert torch.equal(m(x), on)
