@@ -1824,6 +1824,67 @@ int64_t mcamd_gprox_seg_workgroups(const mcamd_gprox_seg* seg);
 int mcamd_group_prox(const mcamd_gprox_seg* segs, const mcamd_gprox_seg* segs_dev, int32_t nseg, double tau2, float tau_gate,
                      const float* skip, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Factor SGD (lowrank.FactorSGD; an addition beyond the reference): retraining a low-rank block in factored
+ * form.  The training step runs the dense kernels on W = V U; behind optimizer.step() ONE call takes the dense weight
+ * gradient of every factored block onto its factors, steps them with momentum SGD and recomposes W.  Three launches over a
+ * segment table for the whole model, nothing read back, no allocation, no floating-point atomics.
+ * ------------------------------------------------------------------------- */
+/* One segment is one factored block, K = Cin k k; every tensor fp32, contiguous and 16-byte aligned except g, which may be a
+ * 4-byte aligned view (a gradient inside a flat buffer):
+ *   g [cout][K] read;  u [r][K], v [cout][r], mu [r][K], mv [cout][r] read and written;  w [cout][K] written.
+ * With lr, mom, wd fp32 and every product and sum fp32:
+ *   aU = V^T G and aV = G U^T from the OLD u and v, on the fp32 MFMA (v_mfma_f32_32x32x2_f32, round to nearest): an element of
+ *        aU accumulates its cout terms in ascending order, one accumulator.  An element of aV accumulates the terms of each K
+ *        slice [MCAMD_LRSGD_SLICE s, min(K, MCAMD_LRSGD_SLICE (s + 1))) in ascending order into a slab of its own, and
+ *        aV = ((slab_0 + slab_1) + slab_2) + ... in slice order.
+ *   gU = fmaf(wd, U, aU)          gV = fmaf(wd, V, aV)
+ *   MU = fmaf(mom, MU, gU)        MV = fmaf(mom, MV, gV)        (zero buffers: the first step gives M = g, as torch SGD)
+ *   U  = fmaf(-lr, MU, U)         V  = fmaf(-lr, MV, V)
+ *   W  = V U from the NEW u and v, r terms in ascending order, one accumulator.
+ * Every order depends on the shapes and on the constants below only: two calls on equal operands give equal bits.
+ * Accepted: r % 32 == 0 in [32, 256], cout % 32 == 0, K % 32 == 0, cout K < 2^31. */
+#define MCAMD_LRSGD_SLICE 1024    /* reduction steps of one aV slab */
+#define MCAMD_LRSGD_TILE 64       /* output tile edge of the three products (a workgroup of 256 threads) */
+#define MCAMD_LRSGD_ITEM 1024     /* elements one workgroup of the update launch steps */
+typedef struct mcamd_lrsgd_seg {
+    void* g;
+    void* u;
+    void* v;
+    void* mu;
+    void* mv;
+    void* w;
+    int64_t ws0;          /* first float of the block's slabs in the workspace: the running sum of slices * cout * r (checked) */
+    int32_t cout, K, r;
+    int32_t tile0_grad;   /* first workgroup of the block in each of the three launches: the running sums of */
+    int32_t tile0_update; /*   mcamd_lowrank_sgd_info's tiles_grad / tiles_update / tiles_compose (checked) */
+    int32_t tile0_compose;
+} mcamd_lrsgd_seg;
+
+typedef struct mcamd_lrsgd_info {
+    int32_t tile, tile_k, slice, slices;                  /* MCAMD_LRSGD_TILE, reduction steps per LDS stage, MCAMD_LRSGD_SLICE, ceil(K / slice) */
+    int32_t threads, lds_bytes;                           /* of the two GEMM launches */
+    int32_t tiles_grad, tiles_update, tiles_compose;      /* workgroups the block adds to each launch */
+    int32_t reserved;
+    int64_t workspace_bytes;                              /* slices * cout * r * 4: the aV slabs */
+} mcamd_lrsgd_info;
+
+/* 1 when a block of this shape is accepted, else 0 */
+int32_t mcamd_lowrank_sgd_ok(int32_t cout, int32_t K, int32_t r);
+/* the figures above; MCAMD_EINVAL, with the refused dimension named in mcamd_last_error, for a shape that is not accepted */
+int mcamd_lowrank_sgd_info(int32_t cout, int32_t K, int32_t r, mcamd_lrsgd_info* info);
+
+/* One step of every segment: the gradient launch (aU tiles with MU updated in the epilogue -- each MU element belongs to one
+ * tile, and no tile of this launch writes u or v, which other tiles still read -- and aV slabs into `workspace`), the update
+ * launch (slabs summed, MV, then U and V) and the compose launch (W).  `segs` is a HOST array for the checks and the grid
+ * sizes, `segs_dev` its DEVICE copy.  skip: device fp32 scalar or NULL; when *skip != 0 nothing at all is written, neither u,
+ * v, mu, mv nor w (train.StepGuard's `found`), decided on the device.  workspace: 16-byte aligned, at least the sum of the
+ * blocks' workspace_bytes.  Launch-type: recorded into a launch plan while one is being recorded.  Refused without a launch
+ * (MCAMD_EINVAL): NULL or misaligned pointers, a shape that is not accepted, offsets that are not the running sums, a
+ * workspace that is too small, non-finite lr, mom or wd. */
+int mcamd_lowrank_sgd(const mcamd_lrsgd_seg* segs, const mcamd_lrsgd_seg* segs_dev, int32_t nseg, float lr, float mom, float wd,
+                      const float* skip, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,4 +51,7 @@ def __getattr__(name):
     if name == "lowrank_factor":
         from . import lowrank
         return lowrank.lowrank_factor
+    if name == "FactorSGD":
+        from . import lowrank
+        return lowrank.FactorSGD
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

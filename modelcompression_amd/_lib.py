@@ -210,6 +210,19 @@ class GproxSeg(C.Structure):
                 ("cin", C.c_int32), ("khw", C.c_int32)]
 
 
+class LrsgdSeg(C.Structure):
+    """mcamd_lrsgd_seg (include/mcamd.h)."""
+    _fields_ = [("g", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("mu", C.c_void_p), ("mv", C.c_void_p), ("w", C.c_void_p),
+                ("ws0", C.c_int64), ("cout", C.c_int32), ("K", C.c_int32), ("r", C.c_int32),
+                ("tile0_grad", C.c_int32), ("tile0_update", C.c_int32), ("tile0_compose", C.c_int32)]
+
+
+class LrsgdInfo(C.Structure):
+    """mcamd_lrsgd_info (include/mcamd.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("tile", "tile_k", "slice", "slices", "threads", "lds_bytes", "tiles_grad", "tiles_update",
+                                         "tiles_compose", "reserved")] + [("workspace_bytes", C.c_int64)]
+
+
 EPI_RAW_F16, EPI_NCHW_F32, EPI_PAD_F16, EPI_RAW_F32 = 0, 1, 2, 3
 DST_PLAIN, DST_POOL, DST_REORG = 0, 1, 2
 WGRAD_GENERIC, WGRAD_STEM, WGRAD_WIN, WGRAD_NINE, WGRAD_NINE_WIDE = 0, 1, 2, 3, 4      # mcamd_conv_wgrad_plan_info: family
@@ -400,6 +413,9 @@ SIGNATURES = {
     "mcamd_taylor_accum": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
     "mcamd_gprox_seg_workgroups": (_I64, [C.POINTER(GproxSeg)]),
     "mcamd_group_prox": (C.c_int, [_P, _P, _I32, C.c_double, _F, _P, _P]),
+    "mcamd_lowrank_sgd_ok": (_I32, [_I32, _I32, _I32]),
+    "mcamd_lowrank_sgd_info": (C.c_int, [_I32, _I32, _I32, C.POINTER(LrsgdInfo)]),
+    "mcamd_lowrank_sgd": (C.c_int, [_P, _P, _I32, _F, _F, _F, _P, _P, _SZ, _P]),
 }
 
 _lib = None

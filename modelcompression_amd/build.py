@@ -60,6 +60,7 @@ SOURCES = {
     "huff.hip": [],                       # Huffman-coded model files: integer passes only
     "taylor.hip": ["-ffp-contract=off"],  # Taylor importance: pinned fp32 / float64 products and sums
     "group_prox.hip": ["-ffp-contract=off"],  # proximal group lasso: pinned float64 sums, one scale per block
+    "lowrank_train.hip": ["-ffp-contract=off"],  # factor SGD: fp32 MFMA products, every fused multiply-add written out
 }
 
 

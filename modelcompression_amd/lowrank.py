@@ -12,6 +12,11 @@ A factored model is ordinary fp32 master weights of rank r, so every engine, pre
 it as it is; only the fp16 inference engine multiplies the factors themselves.  Factors are FRESH while the weight still is
 the product set_factors wrote: any later write (optimizer.step, load_weights, set_masks, invalidate_packed) makes them
 stale, and a stale block runs dense on its current weights.
+
+    fs = FactorSGD(model, momentum, weight_decay); ...; optimizer.step(); fs.step(lr)    # retraining in factored form
+
+keeps them fresh through training: the dense gradient goes onto the factors, they take the SGD step and W = V U is written
+back (csrc/lowrank_train.hip).
 """
 import torch
 
@@ -118,3 +123,79 @@ def set_factors(model, factors):
 def fresh_blocks(model):
     """[(conv number, MaskedConv2d)] whose factors still describe the weight."""
     return [(i, conv) for i, conv in _blocks(model) if is_fresh(model, conv)]
+
+
+# ----------------------------------------------------------------------------- retraining in factored form
+class FactorSGD:
+    """Momentum SGD on the factors of `model`'s fresh factored blocks (include/mcamd.h).
+
+        fs = FactorSGD(model, momentum=0.9, weight_decay=0.0)
+        loss.backward(); optimizer.step(); fs.step(lr)
+
+    The training step stays the dense one on W = V U.  step() reads the dense weight.grad the backward left, takes it onto the
+    factors (gU = V^T G + wd U, gV = G U^T + wd V, both from the old factors), steps them as torch's SGD would (M = mom M + g,
+    x = x - lr M; the momentum buffers live here, not in the state_dict) and writes W = V U over whatever the dense optimizer
+    wrote: this object owns the weights of its blocks.  On the GPU that is one library call over all blocks -- three launches,
+    no allocation, no host synchronisation, bit-reproducible -- on a table built once and rebuilt when a tensor it names has
+    moved (weight.grad included).  Afterwards the weights' version counters are bumped and the blocks are stamped fresh, so
+    model.lowrank = True runs the trained factors.
+    `skip` (a one-element fp32 tensor on the model's device) non-zero leaves factors, momentum and weights as they were,
+    decided on the device.  It MUST be the flag the optimizer itself honours (train.StepGuard.found): then the dense step
+    left W alone as well, W = V U still holds and the stamp stays valid.
+    CPU tensors take a torch fp32 restatement of the same formulas; its sums run in another order, so it is not bit-equal
+    to the device."""
+
+    def __init__(self, model, momentum=0.9, weight_decay=0.0):
+        self.model, self.momentum, self.weight_decay = model, float(momentum), float(weight_decay)
+        self.blocks = fresh_blocks(model)
+        if not self.blocks:
+            raise McamdError("FactorSGD: the model has no fresh factored block (lowrank_factor, then set_factors)")
+        from . import _lib
+        for i, conv in self.blocks:
+            cout, r = conv.factor_v.shape
+            if conv.weight.dtype != torch.float32:
+                raise McamdError("FactorSGD: conv%d: the weight must be fp32" % i)
+            info = _lib.LrsgdInfo()       # (the CPU restatement keeps the kernel's shapes: one rule for both)
+            if _lib.lib().mcamd_lowrank_sgd_info(cout, conv.weight[0].numel(), r, _lib.C.byref(info)) != 0:
+                raise McamdError("FactorSGD: conv%d: %s" % (i, _lib.lib().mcamd_last_error().decode()))
+        self.mu = [torch.zeros_like(conv.factor_u) for _, conv in self.blocks]
+        self.mv = [torch.zeros_like(conv.factor_v) for _, conv in self.blocks]
+        self._table, self._key = None, None
+        self.tables_built = 0
+
+    def step(self, lr, skip=None):
+        lr = float(lr)
+        for i, conv in self.blocks:
+            if conv.weight.grad is None:
+                raise McamdError("FactorSGD.step: conv%d has no weight.grad: call it behind backward() and optimizer.step()" % i)
+        if not self.blocks[0][1].weight.is_cuda:
+            if skip is not None and float(skip.reshape(-1)[0]) != 0.0:
+                return
+            mom, wd = self.momentum, self.weight_decay
+            for (_, conv), mu, mv in zip(self.blocks, self.mu, self.mv):
+                u4, v = conv.factor_u, conv.factor_v
+                u, g = u4.reshape(u4.shape[0], -1), conv.weight.grad.reshape(v.shape[0], -1).float()
+                gu, gv = v.t() @ g + wd * u, g @ u.t() + wd * v
+                mu.mul_(mom).add_(gu.reshape(mu.shape))
+                mv.mul_(mom).add_(gv)
+                u4.sub_(lr * mu)
+                v.sub_(lr * mv)
+                with torch.no_grad():
+                    conv.weight.copy_((v @ u4.reshape(u4.shape[0], -1)).reshape(conv.weight.shape))
+                stamp(self.model, conv)
+            return
+        from . import ops
+        tensors = [(conv.weight.grad, conv.factor_u, conv.factor_v, mu, mv, conv.weight.data)
+                   for (_, conv), mu, mv in zip(self.blocks, self.mu, self.mv)]
+        key = tuple(t.data_ptr() for ts in tensors for t in ts)
+        if self._table is None or key != self._key:
+            self._table = ops.LowRankSgdTable([dict(zip(("g", "u", "v", "mu", "mv", "w"), ts)) for ts in tensors])
+            self._key = key
+            self.tables_built += 1
+        self._table.step(lr, self.momentum, self.weight_decay, skip)
+        # The kernel wrote through raw pointers.  Bumping the version counters is what an in-place torch write would have done:
+        # every engine of the model compares them before its next forward and re-packs (share.project_codebooks); the stamp
+        # behind it says the factors describe the weight again.
+        for _, conv in self.blocks:
+            torch.autograd.graph.increment_version(conv.weight)
+            stamp(self.model, conv)

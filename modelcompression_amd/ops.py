@@ -2175,3 +2175,60 @@ class GroupProxTable:
         tau = float(tau)
         check(L.lib().mcamd_group_prox(self.arr, ptr(self.table), self.nseg, tau * tau, tau, ptr(skip), stream_ptr()),
               "mcamd_group_prox")
+
+
+def lowrank_sgd_info(cout, K, r):
+    """mcamd_lowrank_sgd_info of one block [cout][K] at rank r: the tile constants, the workgroups it adds to each of the three
+    launches and its workspace bytes.  Raises McamdError naming the refused dimension."""
+    info = L.LrsgdInfo()
+    check(L.lib().mcamd_lowrank_sgd_info(int(cout), int(K), int(r), C.byref(info)), "mcamd_lowrank_sgd_info")
+    return info
+
+
+class LowRankSgdTable:
+    """Every factored block of a factor-SGD step through one mcamd_lrsgd_seg table (include/mcamd.h).
+
+    items: one dict per block with fp32 tensors g [cout, K...] (the dense weight gradient), u [r, K...], v [cout, r], mu, mv
+    (momentum, shaped like u and v) and w [cout, K...].  Built once: the table is uploaded pinned and non-blocking and the
+    slab workspace is allocated here; step() is one library call on the current stream with no host read and no allocation."""
+
+    def __init__(self, items):
+        if not items:
+            raise L.McamdError("lowrank_sgd: no block given")
+        dev = items[0]["w"].device
+        arr = (L.LrsgdSeg * len(items))()
+        grad = update = compose = ws = 0
+        self.infos = []
+        for a, it in zip(arr, items):
+            ts = [it[k] for k in ("g", "u", "v", "mu", "mv", "w")]
+            _need_cuda(*ts)
+            if any(t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev for t in ts):
+                raise L.McamdError("lowrank_sgd: every tensor must be a contiguous fp32 tensor on one device")
+            g, u, v, mu, mv, w = ts
+            cout, r = v.shape
+            K = w.numel() // cout
+            if u.numel() != r * K or g.numel() != w.numel() or mu.numel() != u.numel() or mv.numel() != v.numel():
+                raise L.McamdError("lowrank_sgd: g and w are [cout, K], u and mu [r, K], v and mv [cout, r] (got %s)"
+                                   % ", ".join(str(tuple(t.shape)) for t in ts))
+            info = lowrank_sgd_info(cout, K, r)
+            a.g, a.u, a.v, a.mu, a.mv, a.w = (t.data_ptr() for t in ts)
+            a.cout, a.K, a.r, a.ws0 = cout, K, r, ws // 4
+            a.tile0_grad, a.tile0_update, a.tile0_compose = grad, update, compose
+            grad, update, compose, ws = grad + info.tiles_grad, update + info.tiles_update, compose + info.tiles_compose, \
+                ws + info.workspace_bytes
+            self.infos.append(info)
+        self.items, self.arr, self.nseg = items, arr, len(items)
+        self.workgroups = (grad, update, compose)
+        self.workspace = torch.empty(ws // 4, dtype=torch.float32, device=dev)
+        # (pinned and non-blocking: building a table is no host synchronisation)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory().to(dev, non_blocking=True)
+
+    def step(self, lr, mom, wd, skip=None):
+        """U, V, MU, MV and W of every block, by the header's formulas; nothing at all is written when *skip != 0 (device
+        fp32 scalar)."""
+        if skip is not None:
+            _need_cuda(skip)
+            if skip.dtype != torch.float32 or skip.numel() != 1:
+                raise L.McamdError("lowrank_sgd: skip must be a device fp32 scalar")
+        check(L.lib().mcamd_lowrank_sgd(self.arr, ptr(self.table), self.nseg, float(lr), float(mom), float(wd), ptr(skip),
+                                        ptr(self.workspace), self.workspace.numel() * 4, stream_ptr()), "mcamd_lowrank_sgd")

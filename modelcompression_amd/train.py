@@ -62,6 +62,13 @@ per-epoch prune_rate + are_masks_consistent and a checkpoint every 5th epoch whe
     weights after the all-reduced step and the proximal step is a deterministic function of the weights: nothing travels.
     SHARE together with GROUP_LASSO raises (the projection and the proximal step would undo each other).  The object is kept
     as YOLOv2Train.group_lasso.
+  * YOLOv2Train.LOWRANK = {"rank": int | dict} or {"energy": float}, optionally with "layers" (an attribute; None by default:
+    train() issues the launches it issued before and nothing more) retrains low-rank layers in factored form (lowrank.py,
+    DESIGN.md 3zh): the loaded model goes through lowrank_factor and set_factors -- every rank factors the same broadcast
+    weights -- and a lowrank.FactorSGD with the optimizer's momentum and weight decay steps the factors behind every
+    optimizer.step(), at its learning rate, skipped on the device when StepGuard flags the step.  The factors end fresh, so
+    model.lowrank = True runs them.  LOWRANK together with pruning_perc > 0, SHARE or GROUP_LASSO raises: a factored block
+    carries neither masks nor codebooks.  The object is kept as YOLOv2Train.factor_sgd.
 """
 import os
 
@@ -85,6 +92,7 @@ from .pruning.weightPruning.utils import prune_rate, are_masks_consistent  # noq
 from .share import kmeans_share, are_codebooks_consistent, _bits_of  # noqa: E402
 from .importance import TaylorImportance, taylor_prune  # noqa: E402
 from .sparsify import GroupLasso, check_config as _group_lasso_config  # noqa: E402
+from .lowrank import FactorSGD, lowrank_factor  # noqa: E402
 
 TAYLOR_METHODS = {"taylor-weight": "weight", "taylor-block": "block", "taylor-filter": "filter"}
 
@@ -263,6 +271,9 @@ class YOLOv2Train():
     # None, or {"lam": float, "granularity": "block" | "filter"}: a proximal group-lasso step (sparsify.GroupLasso, DESIGN.md
     # 3ze) behind every optimizer.step(); the learned zero groups become masks before every file is saved (an attribute too)
     GROUP_LASSO = None
+    # None, or {"rank": ...} / {"energy": ...} with optional "layers": the arguments of lowrank.lowrank_factor; the factored
+    # blocks are then retrained in factored form by a lowrank.FactorSGD (an attribute too)
+    LOWRANK = None
 
     def __init__(self):
         self.model = ''
@@ -275,6 +286,7 @@ class YOLOv2Train():
         self.teacher = None       # train(TEACHER=...): the frozen Darknet and the distill.DistillLoss of the last call
         self.distill = None
         self.group_lasso = None   # GROUP_LASSO: the sparsify.GroupLasso of the last call
+        self.factor_sgd = None    # LOWRANK: the lowrank.FactorSGD of the last call
 
     @_share_keyword
     def train(self, PASCAL_DIR, PASCAL_TRAIN, PASCAL_VALID, TRAIN_LOGDIR, VAL_LOGDIR, VAL_OUTPUTDIR_PKL, VAL_PREFIX,
@@ -302,6 +314,17 @@ class YOLOv2Train():
             if SHARE is not None:
                 raise ValueError("train: SHARE and GROUP_LASSO cannot be combined: the projection onto the codebooks and the "
                                  "proximal step would undo each other")
+        LOWRANK = self.LOWRANK
+        if LOWRANK is not None:
+            if (not isinstance(LOWRANK, dict) or not set(LOWRANK) <= {"rank", "energy", "layers"}
+                    or ("rank" in LOWRANK) == ("energy" in LOWRANK)):
+                raise ValueError('train: LOWRANK must be None or a dict {"rank": ...} or {"energy": ...}, optionally with '
+                                 '"layers", got %r' % (LOWRANK,))
+            for name, on in (("pruning_perc > 0", pruning_perc > 0), ("SHARE", SHARE is not None),
+                             ("GROUP_LASSO", GROUP_LASSO is not None)):
+                if on:
+                    raise ValueError("train: LOWRANK and %s cannot be combined: a factored block carries neither masks nor "
+                                     "codebooks" % name)
         if DISTILL is not None and TEACHER is None:
             raise ValueError("train: DISTILL needs a TEACHER (True, a .weights path or a Darknet)")
         rank, world = dp.init_from_env()
@@ -392,6 +415,14 @@ class YOLOv2Train():
         if SHARE is not None:
             # every rank clusters the same broadcast weights under the same masks: the codebooks agree, nothing travels
             self.model.set_codebooks(kmeans_share(self.model, **SHARE))
+        self.factor_sgd = fs = None
+        if LOWRANK is not None:
+            # every rank factors the same broadcast weights: the factors agree, nothing travels.  In a data-parallel run
+            # weight.grad is already reduced when fs.step reads it, so the ranks' factors stay equal.
+            self.model.set_factors(lowrank_factor(self.model, **LOWRANK))
+            fs = self.factor_sgd = FactorSGD(self.model, momentum=momentum, weight_decay=decay * self.batch_size)
+            if rank == 0:
+                logging('low-rank retraining: %s' % ', '.join('conv%d r=%d' % (i, c.factor_u.shape[0]) for i, c in fs.blocks))
         self.group_lasso = gl = None
         if GROUP_LASSO is not None:
             gl = self.group_lasso = GroupLasso(self.model, GROUP_LASSO["lam"], GROUP_LASSO["granularity"])
@@ -448,6 +479,10 @@ class YOLOv2Train():
                 # together, and the host learns of it one step late (StepGuard)
                 guard.decide(train_loss)
                 optimizer.step()
+                if fs is not None:
+                    # the step of the factors, which overwrites the dense step of their weights with V U; a step StepGuard
+                    # skipped leaves all of them exactly as they were, decided on the device
+                    fs.step(optimizer.param_groups[0]["lr"], skip=guard.found)
                 if gl is not None:
                     # the proximal step of the penalty, at the step size SGD just used; a step StepGuard skipped leaves the
                     # weights exactly as they were, decided on the device
