@@ -644,6 +644,30 @@ int mcamd_conv_fwd_q8_w4_mx(const mcamd_conv_geom* g, const void* x8, const void
 int mcamd_conv_fwd_q8_w4_mx_info(const mcamd_conv_geom* g, int32_t out[7]);
 
 /* ---------------------------------------------------------------------------
+ * Split-K form of that block for low-batch inference (an addition beyond the reference; conv_q8_w4_mx.hip,
+ * Darknet.precision = "fp8-w4-mx-splitk"): mcamd_conv_fwd_q8_splitk's launch design on mcamd_pack_q8_w4_mx's
+ * operands.  Workgroup (tile of 64 filters x 64 pixels, slice s) of a first launch multiplies the chunks
+ * [floor(s n / S), floor((s + 1) n / S)) of the tile's n = k*k * cin / 64 chunks -- per chunk 32 code bytes and two scale bytes
+ * per filter, the matrix step of mcamd_conv_fwd_q8_w4_mx -- and stores its unrounded fp32 accumulators to slab s of `workspace`
+ * ([S][Mpad][Npad] fp32, whole tiles); mcamd_conv_fwd_q8_splitk's second launch sums the S slabs of every element in slice
+ * order in fp32 and applies v = leaky(scale_f * 2^-(e4_f + 1) * S + shift_f), written as q(2 v) bytes or saturated fp16 per
+ * destination.  No atomics, no workgroup waits for another: the result is a function of the operands and S only; with S = 1
+ * it is mcamd_conv_fwd_q8_w4_mx's result code for code, and it differs from it by the order of the fp32 sum only for any S.
+ *
+ * Geometries: mcamd_conv_fwd_q8_w4_mx_ok and pad == 0.  Epilogue: MCAMD_EPI_PAD_F16 (dst_mode PLAIN / POOL (+ y2) / REORG) with
+ * stats == NULL.  Operands: exactly mcamd_conv_fwd_q8_w4_mx's (the same codes, scales and exponents, the same byte buffer).
+ * ------------------------------------------------------------------------- */
+/* Host logic only: mcamd_conv_fwd_q8_splitk_info's answer for the same arguments (one policy, one tile: the two pairs and the
+ * fp16 pair size one workspace).  slices = 0 asks the policy, slices > 0 sizes a forced count in [1, chunks]. */
+int mcamd_conv_fwd_q8_w4_mx_splitk_info(const mcamd_conv_geom* g, int32_t dst_mode, int32_t slices, mcamd_splitk_info* out);
+/* The two launches.  y_f8 / y2_f8 as mcamd_conv_fwd_q8; slices as above; workspace: at least the workspace_bytes the query
+ * returns for the same arguments, 16-byte aligned, free again once the call's launches have run.  Everything refused is
+ * refused before the first launch. */
+int mcamd_conv_fwd_q8_w4_mx_splitk(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* scales,
+                                   const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8,
+                                   int32_t slices, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * 4-bit quantisation-aware training (an addition beyond the reference; Darknet.precision = "fp8-w4-qat"): the
  * fp8 quantisation-aware training above with the weights of every fp8 block in the 4-bit format above -- the training-mode
  * forward of a block runs on the codes it would be deployed with under "fp8-w4".

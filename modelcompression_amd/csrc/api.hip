@@ -1482,6 +1482,48 @@ extern "C" int mcamd_conv_fwd_q8_w4_mx_info(const mcamd_conv_geom* g, int32_t ou
     return MCAMD_OK;
 }
 
+// ... and its split-K pair for low-batch inference (conv_q8_w4_mx.hip's partial kernel + conv_q8_splitk.hip's finish kernel,
+// DESIGN.md 3zi; Darknet.precision = "fp8-w4-mx-splitk"): the fp8 split-K entries' refusals and plan (q8_splitk_plan_for:
+// mcamd_conv_fwd_q8_w4_mx_ok is mcamd_conv_fwd_q8_ok) on mcamd_pack_q8_w4_mx's operands
+extern "C" int mcamd_conv_fwd_q8_w4_mx_splitk_info(const mcamd_conv_geom* g, int32_t dst_mode, int32_t slices, mcamd_splitk_info* out) {
+    MCAMD_REQUIRE(out, "conv_fwd_q8_w4_mx_splitk_info: null output");
+    SplitkPlan p;
+    if (q8_splitk_plan_for(g, dst_mode, slices, "conv_fwd_q8_w4_mx_splitk_info", &p)) return MCAMD_EINVAL;
+    splitk_info_of(p, out);
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_conv_fwd_q8_w4_mx_splitk(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* scales,
+                                              const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8,
+                                              int32_t slices, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_w4_mx_splitk: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) {
+            return mcamd_conv_fwd_q8_w4_mx_splitk(&g_, x8, codes, scales, wexp, &e_, y_f8, y2_f8, slices, workspace, workspace_bytes, s);
+        });
+    }
+    MCAMD_REQUIRE(g, "conv_fwd_q8_w4_mx_splitk: null geometry");
+    MCAMD_REQUIRE(epi, "conv_fwd_q8_w4_mx_splitk: null epilogue");
+    MCAMD_REQUIRE(epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8_w4_mx_splitk: epilogue mode %d: mode 2 (MCAMD_EPI_PAD_F16) only",
+                  epi->mode);
+    SplitkPlan p;
+    if (q8_splitk_plan_for(g, epi->dst_mode, slices, "conv_fwd_q8_w4_mx_splitk", &p)) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(epi->stats == nullptr, "conv_fwd_q8_w4_mx_splitk: stats must be NULL (no statistics slab in the split-K form)");
+    MCAMD_REQUIRE(x8 && codes && scales && wexp, "conv_fwd_q8_w4_mx_splitk: null input");
+    const size_t need = (size_t)p.slices * (size_t)p.slab_elems * sizeof(float);
+    MCAMD_REQUIRE(workspace, "conv_fwd_q8_w4_mx_splitk: null workspace (%zu bytes needed)", need);
+    MCAMD_REQUIRE(workspace_bytes >= need, "conv_fwd_q8_w4_mx_splitk: workspace_bytes %zu is short of the %zu bytes %d slices need",
+                  workspace_bytes, need, p.slices);
+    MCAMD_REQUIRE(((uintptr_t)workspace & 15) == 0, "conv_fwd_q8_w4_mx_splitk: workspace must be 16-byte aligned (%zu bytes needed)",
+                  need);
+    IgemmArgs a;
+    fill_operand(a, g, x8, codes, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_w4_mx_splitk", 0)) return MCAMD_EINVAL;
+    return mcamd_q8_w4_mx_splitk_launch(a, p, scales, wexp, y_f8 != 0, y2_f8 != 0, (float*)workspace, (hipStream_t)stream);
+}
+
 // mcamd_q8_choice()'s answer: what mcamd_conv_fwd_q8 (forms 0, 1), mcamd_conv_fwd_q8_slim (form 2) and
 // mcamd_conv_fwd_q8_sparse24 (form 3) launch for this geometry (host logic only)
 extern "C" int mcamd_conv_fwd_q8_info(const mcamd_conv_geom* g, int32_t form, int32_t out[7]) {

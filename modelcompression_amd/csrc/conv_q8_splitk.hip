@@ -121,14 +121,7 @@ __global__ __launch_bounds__(256) void q8_splitk_finish_kernel(Q8SplitkArgs p) {
     if (sat && a.overflow) atomicOr(a.overflow, 1);
 }
 
-// a.* geometry and epilogue fields filled by the caller (mode MCAMD_EPI_PAD_F16, byte strides); p: mcamd_splitk_plan with
-// 64-wide chunks (cin % 64 == 0); ws: p.slices * p.slab_elems floats.  The MFMA form is mcamd_q8_choice's (MCAMD_Q8_MFMA).
-int mcamd_q8_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* wexp, int y_f8, int y2_f8, float* ws, hipStream_t st) {
-    if (p.bk != 64 || p.bm != QSK_BNP || p.bn != QSK_BMW || a.cin_tap % 64 != 0 || a.ktot % 64 != 0 || p.slices < 1 ||
-        p.slices > p.chunks) {
-        mcamd_set_error("conv_fwd_q8_splitk: K per tap %d / slices %d do not fit %d chunks of %d", a.cin_tap, p.slices, p.chunks, p.bk);
-        return MCAMD_EINVAL;
-    }
+static Q8SplitkArgs q8_splitk_args(const IgemmArgs& a, const SplitkPlan& p, const void* wexp, int y_f8, int y2_f8, float* ws) {
     Q8SplitkArgs k;
     k.a = a;
     k.wexp = (const int*)wexp;
@@ -138,14 +131,37 @@ int mcamd_q8_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* 
     k.npad = p.ntiles * QSK_BMW;
     k.mtiles = p.mtiles, k.ntiles = p.ntiles;
     k.y_f8 = y_f8, k.y2_f8 = y2_f8;
+    return k;
+}
+
+static int q8_splitk_finish(const Q8SplitkArgs& k, hipStream_t st, const char* what) {
+    const dim3 fgrid((unsigned)(((k.a.M + QSK_FR - 1) / QSK_FR) * k.ntiles));
+    hipLaunchKernelGGL(q8_splitk_finish_kernel, fgrid, dim3(256), 0, st, k);
+    MCAMD_LAUNCH_CHECK(what);
+    return MCAMD_OK;
+}
+
+// a.* geometry and epilogue fields filled by the caller (mode MCAMD_EPI_PAD_F16, byte strides); p: mcamd_splitk_plan with
+// 64-wide chunks (cin % 64 == 0); ws: p.slices * p.slab_elems floats.  The MFMA form is mcamd_q8_choice's (MCAMD_Q8_MFMA).
+int mcamd_q8_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* wexp, int y_f8, int y2_f8, float* ws, hipStream_t st) {
+    if (p.bk != 64 || p.bm != QSK_BNP || p.bn != QSK_BMW || a.cin_tap % 64 != 0 || a.ktot % 64 != 0 || p.slices < 1 ||
+        p.slices > p.chunks) {
+        mcamd_set_error("conv_fwd_q8_splitk: K per tap %d / slices %d do not fit %d chunks of %d", a.cin_tap, p.slices, p.chunks, p.bk);
+        return MCAMD_EINVAL;
+    }
+    const Q8SplitkArgs k = q8_splitk_args(a, p, wexp, y_f8, y2_f8, ws);
     const int groups = p.ntiles * p.slices;
     const dim3 grid((unsigned)(round_up_int(groups, 8) * p.mtiles));
     const int lds = Q8RowsA<QskTile>::RING;
     if (mcamd_q8_choice(a.M, a.N, MCAMD_Q8_FORM_INFER).f8mfma) hipLaunchKernelGGL(q8_splitk_partial_kernel<true>, grid, dim3(256), lds, st, k);
     else hipLaunchKernelGGL(q8_splitk_partial_kernel<false>, grid, dim3(256), lds, st, k);
     MCAMD_LAUNCH_CHECK("conv_fwd_q8_splitk (partial)");
-    const dim3 fgrid((unsigned)(((a.M + QSK_FR - 1) / QSK_FR) * p.ntiles));
-    hipLaunchKernelGGL(q8_splitk_finish_kernel, fgrid, dim3(256), 0, st, k);
-    MCAMD_LAUNCH_CHECK("conv_fwd_q8_splitk (finish)");
-    return MCAMD_OK;
+    return q8_splitk_finish(k, st, "conv_fwd_q8_splitk (finish)");
+}
+
+// The finish launch alone, for a partial kernel of another file that filled ws = [p.slices][p.slab_elems] in this file's slab
+// layout (64 x 64 tiles, rows of p.ntiles * 64 floats): conv_q8_w4_mx.hip's.  a.w is not read.
+int mcamd_q8_splitk_finish_launch(const IgemmArgs& a, const SplitkPlan& p, const void* wexp, int y_f8, int y2_f8, float* ws,
+                                  hipStream_t st, const char* what) {
+    return q8_splitk_finish(q8_splitk_args(a, p, wexp, y_f8, y2_f8, ws), st, what);
 }

@@ -137,6 +137,92 @@ int mcamd_conv_q8_w4_mx_launch(IgemmArgs& a, const void* scales, const void* wex
 }
 
 // ---------------------------------------------------------------------------------------
+// split-K partial kernel for low-batch inference (Darknet.precision = "fp8-w4-mx-splitk")
+// ---------------------------------------------------------------------------------------
+// conv_q8_splitk.hip's launch design on this file's operands and matrix step.  Workgroup (pixel tile, filter tile, slice s) of
+// a 64-filter x 64-pixel tile -- four waves, one 32 x 32 accumulator block each -- runs the chunks [floor(s n / S),
+// floor((s + 1) n / S)) of the n = ktot / 64 chunks through the ring and stores its fp32 accumulators, unrounded, to slab s of
+// the workspace [S][Mpad][Npad]; q8_splitk_finish_kernel (conv_q8_splitk.hip, unchanged) sums the slabs in slice order and
+// applies the epilogue.  No workgroup waits for another: the launch boundary is the reduction.
+//   staging  per chunk and workgroup: 64 rows x 32 code bytes (waves 0 and 1: one DMA instruction each), the tile's 128 scale
+//            bytes of plane q of [ktot / 64][Npad][2] (wave 0: one more; the 64 lanes repeat the 8 pieces) and 64 pixel rows
+//            x 64 bytes (every wave: one) -- 7 KB a stage, 21 KB for the three.  Half the weight bytes of the byte kernel
+//            in the regime where every workgroup of a (filter tile, slice) waits for the same weight chunks: xcd_tile puts
+//            the pixel tiles of one (filter tile, slice) on one XCD, so they stage those chunks out of one L2.
+//   step     w4mx_step<T> with TM = TN = 1: one ds_read_b128 (A), one ds_read_u8 (scale), two ds_read_b128 (B), one MFMA.
+//   store    a lane's accumulator rows 4 g .. 4 g + 3 are four consecutive channels of one pixel: one 16-byte store per g,
+//            whole 128-byte lines per wave; the slab is padded to whole tiles, so nothing is masked (the finish kernel's
+//            stores are).
+struct W4MxSplitkArgs {
+    IgemmArgs a;            // byte operands, a.w = the codes
+    const char* scales;     // [ktot / 64][wnpad][2]
+    float* ws;              // [slices][slab_elems]
+    long long slab_elems;   // mtiles * 64 * npad
+    int slices;
+    int wnpad;              // rows of a scale plane: round_up(N, 256)
+    int npad;               // ntiles * 64: floats per slab row
+    int mtiles, ntiles;
+};
+
+using W4SkTile = Q8Tile<64, 64, 32, 32, 3>;
+
+__global__ __launch_bounds__(W4SkTile::NT) void q8_w4_mx_splitk_partial_kernel(W4MxSplitkArgs p) {
+    using T = W4SkTile;
+    static_assert(T::TM == 1 && T::TN == 1, "one accumulator block per wave (the slab store below)");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const IgemmArgs& a = p.a;
+    const Q8Wave w = q8_wave<T>();
+    int mt, grp;
+    if (!xcd_tile(p.mtiles, p.ntiles * p.slices, mt, grp)) return;
+    const int s = grp / p.ntiles, nt = grp - s * p.ntiles;
+    const int nchunks = a.ktot / T::BK;
+    const int q0 = (int)((long long)s * nchunks / p.slices), q1 = (int)((long long)(s + 1) * nchunks / p.slices);
+    Q8W4MxRowsA<T> aop;
+    aop.setup(a, p.scales, p.wnpad, nt, w.tid);
+    f32x16_t acc[1][1];
+    q8_zero(acc);
+    const W4MxLane<T> ln(w);
+    q8_ring<T>(a, aop, Q8SeqSlice{q1 - q0, q0}, mt, smem, w, [&](const char* sa, const char* sb) { w4mx_step<T>(acc, sa, sb, ln); });
+    q8_mma_drain<true>();
+
+    float* slab = p.ws + (long long)s * p.slab_elems;
+    const int lrow = w.lane & 31, hh = w.lane >> 5;
+    const long long prow = (long long)(mt * T::BNP + w.wn * 32 + lrow) * p.npad + nt * T::BMW + w.wm * 32 + 4 * hh;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        f32x4_t v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = acc[0][0][4 * g + e];
+        *(f32x4_t*)(slab + prow + 8 * g) = v;
+    }
+}
+
+// a.* geometry and epilogue fields filled by the caller (mode MCAMD_EPI_PAD_F16, byte strides, a.w = the codes); p:
+// mcamd_splitk_plan with 64-wide chunks (cin % 64 == 0); ws: p.slices * p.slab_elems floats
+int mcamd_q8_w4_mx_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* scales, const void* wexp, int y_f8, int y2_f8,
+                                 float* ws, hipStream_t st) {
+    if (p.bk != 64 || p.bm != W4SkTile::BNP || p.bn != W4SkTile::BMW || a.cin_tap % 64 != 0 || a.ktot % 64 != 0 || p.slices < 1 ||
+        p.slices > p.chunks) {
+        mcamd_set_error("conv_fwd_q8_w4_mx_splitk: K per tap %d / slices %d do not fit %d chunks of %d", a.cin_tap, p.slices, p.chunks,
+                        p.bk);
+        return MCAMD_EINVAL;
+    }
+    W4MxSplitkArgs k;
+    k.a = a;
+    k.scales = (const char*)scales;
+    k.ws = ws;
+    k.slab_elems = p.slab_elems;
+    k.slices = p.slices;
+    k.wnpad = round_up_int(a.N, 256);
+    k.npad = p.ntiles * W4SkTile::BMW;
+    k.mtiles = p.mtiles, k.ntiles = p.ntiles;
+    const dim3 grid((unsigned)(round_up_int(p.ntiles * p.slices, 8) * p.mtiles));
+    hipLaunchKernelGGL(q8_w4_mx_splitk_partial_kernel, grid, dim3(W4SkTile::NT), Q8W4MxRowsA<W4SkTile>::RING, st, k);
+    MCAMD_LAUNCH_CHECK("conv_fwd_q8_w4_mx_splitk (partial)");
+    return mcamd_q8_splitk_finish_launch(a, p, wexp, y_f8, y2_f8, ws, st, "conv_fwd_q8_w4_mx_splitk (finish)");
+}
+
+// ---------------------------------------------------------------------------------------
 // packer: fp32 OIHW master * mask -> codes [Npad][ktot / 2] + e8m0 scales [ktot / 64][Npad][2] + exponents [Npad]
 // ---------------------------------------------------------------------------------------
 // pack_q8_w4_kernel's steps in its order (one workgroup per row n < Npad, four chunks at a time, every weight read once; the

@@ -186,6 +186,10 @@ int mcamd_fakequant_q8_launch(const float* w, const float* mask, const void* wex
 // conv_q8_splitk.hip: split-K pair on conv_q8.hip's operands (partial + finish launch, mode 2 epilogue).  `p`: mcamd_splitk_plan
 // for 64-wide chunks (cin % 64 == 0); ws: p.slices * p.slab_elems floats; the MFMA form is mcamd_q8_choice's
 int mcamd_q8_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* wexp, int y_f8, int y2_f8, float* ws, hipStream_t st);
+// ... its finish launch alone, behind a partial kernel of another file that filled `ws` in the same slab layout (`what`
+// names the caller in a launch error)
+int mcamd_q8_splitk_finish_launch(const IgemmArgs& a, const SplitkPlan& p, const void* wexp, int y_f8, int y2_f8, float* ws,
+                                  hipStream_t st, const char* what);
 // conv_q8_bsparse.hip: conv_q8.hip's K loop (conv_q8_loop.h) on a 64 x 128 tile over the K chunks each 64-filter tile lists (count[ntiles],
 // list[ntiles][ktot / 64]); its instance and grid; the lists of mcamd_pack_q8's bytes
 Q8Choice mcamd_q8_bsparse_choice(long long M, int N);
@@ -215,6 +219,10 @@ int mcamd_conv_q8_w4_mx_launch(IgemmArgs& a, const void* scales, const void* wex
 int mcamd_pack_q8_w4_mx_launch(const float* w, const float* mask, void* codes, void* scales, void* wexp, int cout, int cin, int ntaps,
                                hipStream_t st);
 int mcamd_unpack_q8_w4_mx_launch(const void* codes, const void* scales, void* wq, int cout, int cin, int ntaps, hipStream_t st);
+// ... and its split-K pair: a partial launch on those operands (64 x 64 tiles, `p` and `ws` as mcamd_q8_splitk_launch's) and
+// mcamd_q8_splitk_finish_launch
+int mcamd_q8_w4_mx_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* scales, const void* wexp, int y_f8, int y2_f8,
+                                 float* ws, hipStream_t st);
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps);
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);

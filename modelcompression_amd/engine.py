@@ -58,7 +58,8 @@ _LAYER_FIELDS = dict(
     fused_stem=False, fused_stem_eval=False, stem_shadow=False, stem_split=False, stem_f32=False, stem_ws=None, weff=None,
     sh_img=None, sh_img_lo=None, sh_geom=None, sh_wp=None, sh_wp_lo=None, sh_coef=None,
     f8=False, f8_wexp=ops.F8_WEXP_DEFAULT, f8_wexp_eff=ops.F8_WEXP_DEFAULT,
-    # inference form (Engine._choose_forms, _FORMS) and what belongs to one: split-K slices (forms "splitk" and "q8_splitk"),
+    # inference form (Engine._choose_forms, _FORMS) and what belongs to one: split-K slices (forms "splitk", "q8_splitk" and
+    # "q8_w4_mx_splitk"),
     # 2:4 values + index words, block-sparse chunk lists
     form="dense", sk_slices=1, wsp=None, widx=None, bs_count=None, bs_list=None,
     # the packed factors of form "lowrank" and their rank
@@ -91,7 +92,8 @@ class _Layer:
     sp_on = property(lambda self: self.form == "sparse24")
     bs_on = property(lambda self: self.form == "bsparse")
     sk_on = property(lambda self: self.form == "splitk")
-    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_bsparse"))
+    q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_w4_mx_splitk",
+                                                "q8_bsparse"))
     q8s_on = property(lambda self: self.form == "q8_sparse24")
     q8_slim = property(lambda self: self.form == "q8_slim")
 
@@ -541,9 +543,26 @@ class _Q8W4Mx(_Q8):
         ops.pack_q8_w4_mx(g, values, None, *ops_)
 
 
+class _Q8W4MxSplitK(_Q8W4Mx):
+    """An fp4-operand block of few pixels: its K loop cut into slices over the whole chip ("fp8-w4-mx-splitk",
+    csrc/conv_q8_w4_mx.hip).  The operands and their packing are _Q8W4Mx's; the workspace is the engine's one
+    split-K workspace, as _Q8SplitK's."""
+    fwd = "conv_fwd_q8_w4_mx_splitk"
+
+    def alloc(self, eng, lays):
+        _Q8W4Mx.alloc(self, eng, lays)
+        need = max(ops.conv_fwd_q8_w4_mx_splitk_info(lay.geom_q8, lay.mode, lay.sk_slices).workspace_bytes for lay in lays)
+        if eng._splitk_ws is None or eng._splitk_ws.numel() * 4 < need:
+            eng._splitk_ws = torch.empty(need // 4, dtype=torch.float32, device=eng.device)
+
+    def operands(self, eng, lay, xin):
+        args, kw = _Q8W4Mx.operands(self, eng, lay, xin)
+        return args, dict(kw, slices=lay.sk_slices, workspace=eng._splitk_ws)
+
+
 _FORMS = {"dense": _Dense(), "splitk": _SplitK(), "lowrank": _LowRank(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "bsparse_train": _BSparseTrain(), "q8": _Q8(),
           "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4(), "q8_w4_mx": _Q8W4Mx(),
-          "q8_bsparse": _Q8BSparse()}
+          "q8_w4_mx_splitk": _Q8W4MxSplitK(), "q8_bsparse": _Q8BSparse()}
 
 
 def _probe_side_stream(device, tries=8):
@@ -620,6 +639,11 @@ class Engine:
         inference only: the same codes, shifts and exponents in the layout v_mfma_scale_f32_32x32x64_f8f6f4 takes as an fp4
         operand with per-lane e8m0 scales (csrc/conv_q8_w4_mx.hip, `fp8_w4_mx_layers`) -- no expansion in registers, the
         arithmetic of MCAMD_Q8_MFMA=1 whatever that switch says; every other block runs what "fp8-w4" runs.
+        "fp8-w4-mx-splitk" -- the "fp8-w4-mx" engine for low batches, inference only: every block of form
+        "q8_w4_mx" on an unpadded geometry whose launch the split-K policy gives two slices or more runs the fp4-operand
+        split-K pair on the same packed operands (`fp8_w4_mx_splitk_layers`; `fp8_w4_mx_layers` lists every block on fp4
+        operands, split or not); every other block, and every batch the policy does not split, runs exactly what "fp8-w4-mx"
+        runs.  Differs from "fp8-w4-mx" by the order of the fp32 sums only.
         "fp8-w4-qat" -- 4-bit quantisation-aware training: "fp8-qat" with the weights of every fp8 block in the
         4-bit format -- in training mode every block of `fp8_layers` (`fp8_w4_layers` is the same list) re-quantises its weights
         to codes, shifts and exponents every step and runs its forward on them (mcamd_conv_fwd_q8_w4_raw); the backward is
@@ -630,18 +654,19 @@ class Engine:
         chunks that hold a non-zero weight byte (csrc/conv_q8_bsparse.hip, `fp8_block_layers`, `fp8_block_kept`); every
         other block runs what "fp8" runs, and with nothing chosen it is the "fp8" engine bit for bit."""
         if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx",
-                             "fp8-w4-qat", "fp8-block"):
+                             "fp8-w4-mx-splitk", "fp8-w4-qat", "fp8-block"):
             raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk', 'fp8-qat', 'fp8-w4', "
-                             "'fp8-w4-mx', 'fp8-w4-qat' or 'fp8-block' (got %r)" % (precision,))
+                             "'fp8-w4-mx', 'fp8-w4-mx-splitk', 'fp8-w4-qat' or 'fp8-block' (got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
-        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx", "fp8-w4-qat",
-                                         "fp8-block")
+        self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx",
+                                         "fp8-w4-mx-splitk", "fp8-w4-qat", "fp8-block")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_choose_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx", "fp8-w4-qat", "fp8-block")
+        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx", "fp8-w4-mx-splitk", "fp8-w4-qat",
+                                "fp8-block")
         self.qat = precision in ("fp8-qat", "fp8-w4-qat")   # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
         # "fp8-2:4": the subset of fp8_layers whose masks conform to 2:4 and that run mcamd_conv_fwd_q8_sparse24
@@ -656,8 +681,12 @@ class Engine:
         self.q8_w4 = precision in ("fp8-w4", "fp8-w4-qat")
         self.fp8_w4_layers = []
         # "fp8-w4-mx": the blocks "fp8-w4" runs on 4-bit weights, on the fp4-operand kernel instead (form "q8_w4_mx")
-        self.q8_w4_mx = precision == "fp8-w4-mx"
+        self.q8_w4_mx = precision in ("fp8-w4-mx", "fp8-w4-mx-splitk")
         self.fp8_w4_mx_layers = []
+        # "fp8-w4-mx-splitk": the subset of fp8_w4_mx_layers -- unpadded geometries only -- the split-K policy gives two slices
+        # or more and that run mcamd_conv_fwd_q8_w4_mx_splitk (form "q8_w4_mx_splitk"; they share `_splitk_ws` below)
+        self.q8_w4_mx_splitk = precision == "fp8-w4-mx-splitk"
+        self.fp8_w4_mx_splitk_layers = []
         # "fp8-block": the subset of fp8_layers the block policy chose and that run mcamd_conv_fwd_q8_bsparse, and the kept-chunk
         # fraction of every candidate (conv number -> fraction); chosen when the masks, the weights or
         # Darknet.fp8_block_max_kept change (_Q8BSparse.policy; the chosen blocks share `_bs_exempt` with sparse = "block")
@@ -1387,7 +1416,9 @@ class Engine:
           2. filter compaction and folding, planned again when the masks or that choice changed;
           3. then fp8 (every eligible block of an fp8 engine; under "fp8-splitk" behind it: every block of form "q8" -- not the
              slim ones -- whose launch the split-K policy gives two slices or more, mcamd_conv_fwd_q8_splitk_info; under
-             "fp8-w4" every block of form "q8" takes the 4-bit form "q8_w4", under "fp8-w4-mx" the form "q8_w4_mx"), 2:4
+             "fp8-w4" every block of form "q8" takes the 4-bit form "q8_w4", under "fp8-w4-mx" the form "q8_w4_mx", and under
+             "fp8-w4-mx-splitk" an unpadded one of those that mcamd_conv_fwd_q8_w4_mx_splitk_info gives two slices or more the form
+             "q8_w4_mx_splitk"), 2:4
              (sparse = "2:4": every eligible block whose mask conforms and whose geometry mcamd_conv_fwd_sparse24_ok accepts)
              or block-sparse (sparse = "block": the chosen blocks that
              are still eligible -- one whose producer was compacted after all, so that its input channels are permuted, stays
@@ -1432,6 +1463,13 @@ class Engine:
                 for lay in self.layers:
                     if lay.form == "q8" and ops.conv_fwd_q8_w4_ok(lay.geom_q8):
                         lay.form = "q8_w4_mx" if self.q8_w4_mx else "q8_w4"
+            if self.q8_w4_mx_splitk:
+                for lay in self.layers:
+                    if lay.form != "q8_w4_mx" or lay.geom_q8.pad:
+                        continue
+                    info = ops.conv_fwd_q8_w4_mx_splitk_info(lay.geom_q8, lay.mode)
+                    if info.slices >= 2:
+                        lay.form, lay.sk_slices = "q8_w4_mx_splitk", info.slices
         elif sparse == "2:4":
             for lay in self._conforming([lay for lay in self.layers
                                          if self._eligible(lay) and lay.conv.mask_flag and lay.cin % 4 == 0
@@ -1470,8 +1508,9 @@ class Engine:
         nums = lambda *names: [lay.li + 1 for lay in self.layers if lay.form in names]
         self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
         self.lowrank_layers = nums("lowrank")
-        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_bsparse")
-        self.fp8_w4_mx_layers = nums("q8_w4_mx")
+        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_w4_mx_splitk", "q8_bsparse")
+        self.fp8_w4_mx_layers = nums("q8_w4_mx", "q8_w4_mx_splitk")
+        self.fp8_w4_mx_splitk_layers = nums("q8_w4_mx_splitk")
         self.fp8_block_layers = nums("q8_bsparse")
         if self._training:                   # (what the last training-mode choice was; an eval pass in between keeps it)
             self.bsparse_train_layers = nums("bsparse_train")

@@ -316,6 +316,10 @@ class Darknet(nn.Module):
         # and the group shifts as its per-lane e8m0 scales -- the same quantisation and resident bytes, no expansion in registers,
         # the arithmetic of MCAMD_Q8_MFMA=1 (engine.Engine.fp8_w4_mx_layers, csrc/conv_q8_w4_mx.hip); `sparse` and
         # `splitk` stay off with it.
+        # "fp8-w4-mx-splitk" (eval only, an opt-in): the "fp8-w4-mx" engine for one image at a time -- every fp4-operand block whose
+        # launch would leave most CUs idle runs as a split-K pair on the same packed operands
+        # (engine.Engine.fp8_w4_mx_splitk_layers, csrc/conv_q8_w4_mx.hip); batches the policy does not split run
+        # exactly what "fp8-w4-mx" runs; `sparse` and `splitk` stay off with it.
         # "fp8-w4-qat" (an addition beyond the reference): 4-bit quantisation-aware training -- "fp8-qat" with the weights of every
         # fp8 block re-quantised to the "fp8-w4" format every step: the training-mode forward multiplies the codes the block would
         # be deployed with, the backward is straight-through on the values they stand for; in eval mode it is the "fp8-w4" engine,

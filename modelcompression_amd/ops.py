@@ -1742,6 +1742,33 @@ def conv_fwd_q8_w4_mx(g, x8, codes, scales, wexp, y, y_ld, y_choff=0, scale=None
                    overflow, _entry="mcamd_conv_fwd_q8_w4_mx")
 
 
+# ... with the K axis cut into slices for low-batch inference
+def conv_fwd_q8_w4_mx_splitk_info(g, dst_mode=0, slices=0):
+    """mcamd_splitk_info of a split-K fp4-operand forward of `g` (mcamd_conv_fwd_q8_w4_mx_splitk_info): host logic only, and
+    conv_fwd_q8_splitk_info's answer -- one policy, one tile.  slices = 0 asks the policy; > 0 sizes a forced slice count."""
+    info = SplitkInfo()
+    check(L.lib().mcamd_conv_fwd_q8_w4_mx_splitk_info(C.byref(g), dst_mode, slices, C.byref(info)), "mcamd_conv_fwd_q8_w4_mx_splitk_info")
+    return info
+
+
+def conv_fwd_q8_w4_mx_splitk(g, x8, codes, scales, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0, y2=None,
+                             y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None, slices=0, workspace=None):
+    """conv_fwd_q8_w4_mx with the K axis cut into `slices` slices (0 = the policy's count): a partial launch on pack_q8_w4_mx's
+    operands into `workspace` (fp32, conv_fwd_q8_w4_mx_splitk_info(...).workspace_bytes; None allocates one) and
+    conv_fwd_q8_splitk's finish launch.  Returns the workspace."""
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff, overflow=overflow)
+    if workspace is None:
+        info = conv_fwd_q8_w4_mx_splitk_info(g, dst_mode, slices)
+        workspace = torch.empty(info.workspace_bytes // 4, dtype=torch.float32, device=x8.device)
+    _need_cuda(x8, workspace)
+    check(L.lib().mcamd_conv_fwd_q8_w4_mx_splitk(C.byref(g), ptr(x8), ptr(codes), ptr(scales), ptr(wexp), C.byref(e), int(bool(y_f8)),
+                                                 int(bool(y2_f8)), slices, ptr(workspace),
+                                                 workspace.numel() * workspace.element_size(), stream_ptr()),
+          "mcamd_conv_fwd_q8_w4_mx_splitk")
+    return workspace
+
+
 def conv_fwd_q8_w4_raw(g, x8, codes, gshift, wexp, y, y_ld, y_choff=0, stats=None):
     """The training form of the 4-bit block (mcamd_conv_fwd_q8_w4_raw): conv_fwd_q8_raw's arguments with
     pack_q8_w4's codes, shift bytes and exponents in place of the weight bytes; y[M][y_ld] fp32 = 2^-(e4_f + 1) x the sum of byte

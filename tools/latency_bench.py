@@ -6,6 +6,9 @@ measured in the same process beside them.  --precision fp8-w4: the off leg is pr
 weights) on the dense model only; nothing is split there, and the launch record and the per-layer table carry
 fields of their own (`w4_layers`; `w4`, `us_fp8`, `us_fp8_w4`) in place of the split-K ones.  --precision fp8-w4-mx: the same with
 the on leg "fp8-w4-mx" (the codes as the MFMA's fp4 operand; `w4_layers` is its fp8_w4_mx_layers).
+--precision fp8-w4-mx-splitk: the off leg is precision "fp8-w4-mx", the on leg "fp8-w4-mx-splitk"  on the dense
+model, with the split-K fields and per-layer table of the fp8 pair; the "fp8" / "fp8-splitk" legs and the fp16 split-K legs of
+the same model are measured in the same process beside them.
 
 Method: both settings alternate in one process, PAIRS pairs; each sample is a loop of CALLS calls after warm-up with a device
 synchronise only around the whole loop (host clock), so a sample is the sustained time per call, launch overhead included;
@@ -14,7 +17,7 @@ instrumented pass (the engine's HIP events around every conv launch, plan replay
 tiles, slices, us unsplit, us split (partial + finish launch).  Launch counts: the library calls of the recorded forward plan
 (a split block is one call and two kernels), the eval-mode bn_coeffs launches among them and the layout pass in front.
 
-usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8|fp8-w4|fp8-w4-mx]
+usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8|fp8-w4|fp8-w4-mx|fp8-w4-mx-splitk]
                                                                              (--json: one JSON document on stdout)"""
 import json
 import os
@@ -36,10 +39,12 @@ def arg(name, dflt):
 
 CALLS, PAIRS, PASSES = max(200, arg("--calls", 200)), max(4, arg("--pairs", 4)), 7
 PRECISION = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp16"
-if PRECISION not in ("fp16", "fp8", "fp8-w4", "fp8-w4-mx"):
-    raise SystemExit("--precision must be fp16, fp8, fp8-w4 or fp8-w4-mx (got %r)" % PRECISION)
+if PRECISION not in ("fp16", "fp8", "fp8-w4", "fp8-w4-mx", "fp8-w4-mx-splitk"):
+    raise SystemExit("--precision must be fp16, fp8, fp8-w4, fp8-w4-mx or fp8-w4-mx-splitk (got %r)" % PRECISION)
 W4 = PRECISION in ("fp8-w4", "fp8-w4-mx")
-ON_LEG = PRECISION if W4 else "fp8-splitk"     # the on leg of an fp8 model
+MXSK = PRECISION == "fp8-w4-mx-splitk"
+ON_LEG = PRECISION if W4 or MXSK else "fp8-splitk"     # the on leg of an fp8 model
+LEGS = ["fp8-w4-mx" if MXSK else "fp8", ON_LEG]         # [off, on] precisions of an fp8 model (main swaps in the fp8 pair)
 if not torch.cuda.is_available():
     raise SystemExit("latency_bench needs the GPU")
 dev = torch.device("cuda", 0)
@@ -55,10 +60,12 @@ def leg(m, flag):
     if m.precision == "fp16":
         m.splitk = flag
     else:
-        m.precision = ON_LEG if flag else "fp8"
+        m.precision = LEGS[flag]
 
 
 def split_layers(eng):
+    if eng.precision == "fp8-w4-mx-splitk":
+        return list(eng.fp8_w4_mx_splitk_layers)
     return list(eng.fp8_splitk_layers if eng.q8 else eng.splitk_layers)
 
 
@@ -113,9 +120,9 @@ def layer_table(m, x):
     rows = []
     for lay in eng.layers:
         tiles = slices = None
-        if eng.q8:              # the fp8 blocks the pair can stand in for: forms "q8" and "q8_splitk"
-            split = lay.form == "q8_splitk"
-            if lay.form in ("q8", "q8_splitk") and not lay.geom_q8.pad:
+        if eng.q8:              # the fp8 blocks a pair can stand in for: forms "q8" / "q8_splitk", "q8_w4_mx" / "q8_w4_mx_splitk"
+            split = lay.form in ("q8_splitk", "q8_w4_mx_splitk")     # (one policy: the fp8 query answers for both pairs)
+            if lay.form in ("q8", "q8_splitk", "q8_w4_mx", "q8_w4_mx_splitk") and not lay.geom_q8.pad:
                 info = ops.conv_fwd_q8_splitk_info(lay.geom_q8, lay.mode)
                 tiles, slices = info.tiles, info.slices
         else:
@@ -197,9 +204,9 @@ def show(res):
 with torch.no_grad():
     dense = init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
     dense.eval()
-    dense.precision = "fp8" if W4 else PRECISION
+    dense.precision = "fp8" if W4 else LEGS[0] if MXSK else PRECISION
     results = [bench_model(dense, (1, 2, 4, 8), "yolov2-voc")]
-    pruned = None if W4 else init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
+    pruned = None if W4 or MXSK else init_synthetic(nets.Darknet(YOLOV2_VOC_CFG), 0).to(dev)
     if pruned is not None:
         pruned.set_masks(quick_filter_prune(pruned, 60.0))
         pruned.eval()
@@ -208,7 +215,11 @@ with torch.no_grad():
             thin.eval()
             thin.precision = PRECISION
             results.append(bench_model(thin, (1,), "yolov2-voc slim60"))
-    if PRECISION == "fp8":      # the fp16 split-K figures of the same run, beside the fp8 ones
+    if MXSK:                    # the fp8 pair of the same run, beside the fp4-operand one
+        LEGS[:] = ["fp8", "fp8-splitk"]
+        dense.precision = "fp8"
+        results.append(bench_model(dense, (1, 2, 4, 8), "yolov2-voc"))
+    if PRECISION == "fp8" or MXSK:      # the fp16 split-K figures of the same run, beside the fp8 ones
         dense.precision = "fp16"
         results.append(bench_model(dense, (1, 2, 4, 8), "yolov2-voc"))
 
