@@ -668,6 +668,49 @@ int mcamd_conv_fwd_q8_w4_mx_splitk(const mcamd_conv_geom* g, const void* x8, con
                                    int32_t slices, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * MXFP4 activations: the fp4 x fp4 forward (an addition beyond the reference; conv_q4_mx.hip, Darknet.precision = "fp4-mx",
+ * DESIGN.md 3zj).  The block above with its pixel operand in 4 bits too: the instruction runs with cbsz:4 and blgp:4, four
+ * registers and one e8m0 scale byte per lane on both sides.  The activation format, written by mcamd_cast_a4_mx from the
+ * engine's padded e4m3 buffer (rows = B (H + 2) (W + 2) padded pixels of `ld` bytes, channels [choff, choff + cin), the bytes
+ * standing for 2 x as everywhere):
+ *   groups  the 32 consecutive channels [32 j, 32 j + 32) of one row;
+ *   shift   the smallest integer s with max |value| over the group <= 6 * 2^s -- mcamd_pack_q8_w4's frexp rule WITHOUT its
+ *           clamp: s in [-11, 7] for e4m3 inputs, so nothing saturates; 0 for an all-zero group (halo rows included);
+ *   code    as mcamd_pack_q8_w4's: bit 3 = sign, bits 0-2 = index into {0, 0.5, 1, 1.5, 2, 3, 4, 6} of |value| / 2^s rounded to
+ *           nearest, ties to the even mantissa bit; a zero magnitude carries no sign;
+ *   value   grid[code] * 2^s, within half a grid step of the input: an e4m3 number (the inputs are multiples of 2^-9) -- but for
+ *           the format's maximum: +-448 = 3.5 * 2^7 is a tie and goes to the even 4 * 2^7 = +-512;
+ *   NaN     the producers never write one; a byte 0x7f / 0xff is read as +-480, the value its bit pattern continues the format
+ *           to, and quantised like any magnitude (512 where it is its group's largest): no NaN comes out;
+ *   codes   bytes [rows][cin / 2]: byte i of a row holds channel 2 i in its LOW nibble and 2 i + 1 in its HIGH nibble -- the 16
+ *           bytes at 32 b + 16 h are channels [64 b + 32 h, + 32), one lane's four registers of the B operand (measured by
+ *           tools/f4x4_probe.hip: B's lane (c, h) holds k = 32 h + e, low nibble first, as A's);
+ *   scales  32-bit words [rows][cin / 64]: byte h = 127 + s of group h of the row's 64-channel block b, bytes 2-3 zero (a word
+ *           so that the kernel stages it with one aligned 4-byte LDS-DMA per pixel and chunk).
+ *   output  v = leaky(scale_f * 2^-(e4_f + 1) * S + shift_f), S = sum over group pairs of 2^g 2^s sum grid[wcode] grid[acode]:
+ *           mcamd_conv_fwd_q8_w4_mx's S on the e4m3 bytes the activation codes stand for, in the arithmetic of the block-scaled
+ *           MFMA (products far below the largest of their group are dropped): not byte-exact on Gaussian operands.
+ * ------------------------------------------------------------------------- */
+/* out[0] = code bytes (rows * cin / 2), out[1] = scale bytes (rows * cin / 16); cin % 64 == 0. */
+int mcamd_a4_mx_elems(int64_t rows, int32_t cin, int64_t out[2]);
+/* The cast pass: one pass, no atomics, deterministic; every byte of both destinations is written.  ld % 16 == 0,
+ * choff % 16 == 0, cin % 64 == 0; x8 and codes 16-byte aligned, scales 4-byte aligned. */
+int mcamd_cast_a4_mx(const void* x8, int64_t rows, int32_t ld, int32_t choff, int32_t cin, void* codes, void* scales,
+                     void* stream);
+/* mcamd_conv_fwd_q8_w4_mx_ok and pad == 0: 3x3 pad 1 or 1x1, stride 1, cin % 64 == 0, the padded NHWC form (no shared-halo
+ * form of the codes, no border table). */
+int32_t mcamd_conv_fwd_q4_mx_ok(const mcamd_conv_geom* g);
+/* The forward: xcodes / xscales from mcamd_cast_a4_mx over the block's whole padded input (g->x_ld / x_choff describe the byte
+ * buffer they were cast from and are not read), codes / scales / wexp from mcamd_pack_q8_w4_mx, unchanged.  epi->mode
+ * MCAMD_EPI_PAD_F16 only; dst_mode, y2, y_f8 / y2_f8 and the overflow flag as mcamd_conv_fwd_q8_w4_mx.  Any batch size.
+ * Anything else returns MCAMD_EINVAL with a message. */
+int mcamd_conv_fwd_q4_mx(const mcamd_conv_geom* g, const void* xcodes, const void* xscales, const void* codes, const void* scales,
+                         const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, void* stream);
+/* The kernel instance it launches (host logic only), out as mcamd_conv_fwd_q8_info's: mcamd_conv_fwd_q8_w4_mx_info's tile
+ * (256 x 128 from 256 filters, 128 x 128 from 128, 64 x 128 below) on a four-stage ring: out[2] = 1, out[3] = 4. */
+int mcamd_conv_fwd_q4_mx_info(const mcamd_conv_geom* g, int32_t out[7]);
+
+/* ---------------------------------------------------------------------------
  * 4-bit quantisation-aware training (an addition beyond the reference; Darknet.precision = "fp8-w4-qat"): the
  * fp8 quantisation-aware training above with the weights of every fp8 block in the 4-bit format above -- the training-mode
  * forward of a block runs on the codes it would be deployed with under "fp8-w4".

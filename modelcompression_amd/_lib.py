@@ -310,6 +310,11 @@ SIGNATURES = {
     "mcamd_unpack_q8_w4_mx": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P]),
     "mcamd_conv_fwd_q8_w4_mx": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _P]),
     "mcamd_conv_fwd_q8_w4_mx_info": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I32)]),
+    "mcamd_a4_mx_elems": (C.c_int, [C.c_int64, _I32, C.POINTER(C.c_int64)]),
+    "mcamd_cast_a4_mx": (C.c_int, [_P, C.c_int64, _I32, _I32, _I32, _P, _P, _P]),
+    "mcamd_conv_fwd_q4_mx_ok": (_I32, [C.POINTER(ConvGeom)]),
+    "mcamd_conv_fwd_q4_mx": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _P]),
+    "mcamd_conv_fwd_q4_mx_info": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I32)]),
     "mcamd_conv_fwd_q8_w4_mx_splitk_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, C.POINTER(SplitkInfo)]),
     "mcamd_conv_fwd_q8_w4_mx_splitk": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _I32, _P, _SZ, _P]),
     "mcamd_conv_fwd_q8_w4_raw": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),

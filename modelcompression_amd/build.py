@@ -36,6 +36,8 @@ SOURCES = {
     "conv_q8_w4.hip": [],
     # (shares the family's loop and epilogue; its matrix step is its own, and it claims bit-equality with none of them)
     "conv_q8_w4_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # (the same: conv_q8_w4_mx.hip's flags, whose weight operands and epilogue it shares)
+    "conv_q4_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "conv_stem.hip": [],
     "conv_stem_block.hip": [],
     "conv_stem_f32.hip": [],

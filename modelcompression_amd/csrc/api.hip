@@ -1524,6 +1524,71 @@ extern "C" int mcamd_conv_fwd_q8_w4_mx_splitk(const mcamd_conv_geom* g, const vo
     return mcamd_q8_w4_mx_splitk_launch(a, p, scales, wexp, y_f8 != 0, y2_f8 != 0, (float*)workspace, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------
+// MXFP4 activations: the cast pass and the fp4 x fp4 forward (conv_q4_mx.hip; Darknet.precision = "fp4-mx")
+// ---------------------------------------------------------------------------------------
+extern "C" int mcamd_a4_mx_elems(int64_t rows, int32_t cin, int64_t out[2]) {
+    MCAMD_REQUIRE(out && rows > 0 && cin > 0 && cin % 64 == 0, "a4_mx_elems: rows %lld / cin %d: cin must be a positive multiple of 64",
+                  (long long)rows, cin);
+    out[0] = rows * (cin / 2);     // code bytes
+    out[1] = rows * (cin / 16);    // scale bytes: one 32-bit word per row and 64 channels
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_cast_a4_mx(const void* x8, int64_t rows, int32_t ld, int32_t choff, int32_t cin, void* codes, void* scales,
+                                void* stream) {
+    if (mcamd_recording())
+        return mcamd_rec_push(stream, [=](void* s) { return mcamd_cast_a4_mx(x8, rows, ld, choff, cin, codes, scales, s); });
+    MCAMD_REQUIRE(x8 && codes && scales && rows > 0, "cast_a4_mx: null pointer / no rows");
+    MCAMD_REQUIRE(cin > 0 && cin % 64 == 0, "cast_a4_mx: cin %d must be a positive multiple of 64 (whole scale words)", cin);
+    MCAMD_REQUIRE(ld % 16 == 0 && choff % 16 == 0 && choff >= 0 && (long long)choff + cin <= ld,
+                  "cast_a4_mx: channel slice [%d, %d) must start at a multiple of 16 inside a leading dimension (%d) that is one", choff,
+                  choff + cin, ld);
+    MCAMD_REQUIRE((((uintptr_t)x8 | (uintptr_t)codes) & 15) == 0 && ((uintptr_t)scales & 3) == 0, "cast_a4_mx: misaligned buffer");
+    return mcamd_cast_a4_mx_launch(x8, rows, ld, choff, cin, codes, scales, (hipStream_t)stream);
+}
+
+// the geometries the forward takes: the fp8 block's, on the padded-NHWC form only (the activation codes have no shared-halo form)
+static int q4_mx_refuse(const mcamd_conv_geom* g, const char* what) {
+    MCAMD_REQUIRE(g, "%s: null geometry", what);
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_w4_mx_ok(g), "%s: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_mx_ok: 3x3 pad 1 or 1x1, "
+                  "stride 1, cin %% 64 == 0)", what);
+    MCAMD_REQUIRE(g->pad == 0, "%s: pad %d: the activation codes are rows of the padded NHWC form (pad 0) only", what, g->pad);
+    return MCAMD_OK;
+}
+
+extern "C" int32_t mcamd_conv_fwd_q4_mx_ok(const mcamd_conv_geom* g) { return g && mcamd_conv_fwd_q8_w4_mx_ok(g) && g->pad == 0; }
+
+extern "C" int mcamd_conv_fwd_q4_mx(const mcamd_conv_geom* g, const void* xcodes, const void* xscales, const void* codes,
+                                    const void* scales, const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8,
+                                    int32_t y2_f8, void* stream) {
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q4_mx: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        return mcamd_rec_push(stream, [=](void* s) {
+            return mcamd_conv_fwd_q4_mx(&g_, xcodes, xscales, codes, scales, wexp, &e_, y_f8, y2_f8, s);
+        });
+    }
+    if (check_geom(g, "conv_fwd_q4_mx") || q4_mx_refuse(g, "conv_fwd_q4_mx")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(xcodes && xscales && codes && scales && wexp, "conv_fwd_q4_mx: null input");
+    MCAMD_REQUIRE((((uintptr_t)xcodes) & 15) == 0 && ((uintptr_t)xscales & 3) == 0, "conv_fwd_q4_mx: misaligned activation codes / scales");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q4_mx: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, xcodes, codes, 1, 0, g->cout, g->cin, 0);     // (strides in buffer rows: a row is cin / 2 code bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q4_mx", 0)) return MCAMD_EINVAL;   // (mode 2: no statistics)
+    return mcamd_conv_q4_mx_launch(a, xscales, scales, wexp, y_f8 != 0, y2_f8 != 0, (hipStream_t)stream);
+}
+
+// mcamd_q4_mx_choice()'s answer: what mcamd_conv_fwd_q4_mx launches for this geometry (host logic only)
+extern "C" int mcamd_conv_fwd_q4_mx_info(const mcamd_conv_geom* g, int32_t out[7]) {
+    MCAMD_REQUIRE(out, "conv_fwd_q4_mx_info: null argument");
+    if (q4_mx_refuse(g, "conv_fwd_q4_mx_info")) return MCAMD_EINVAL;
+    const Q8Choice c = mcamd_q4_mx_choice((long long)g->B * g->H * g->W, g->cout);
+    out[0] = c.bmw, out[1] = c.bnp, out[2] = c.f8mfma, out[3] = c.stages, out[4] = c.mtiles, out[5] = c.ntiles, out[6] = c.grid;
+    return MCAMD_OK;
+}
+
 // mcamd_q8_choice()'s answer: what mcamd_conv_fwd_q8 (forms 0, 1), mcamd_conv_fwd_q8_slim (form 2) and
 // mcamd_conv_fwd_q8_sparse24 (form 3) launch for this geometry (host logic only)
 extern "C" int mcamd_conv_fwd_q8_info(const mcamd_conv_geom* g, int32_t form, int32_t out[7]) {

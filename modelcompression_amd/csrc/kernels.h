@@ -223,6 +223,13 @@ int mcamd_unpack_q8_w4_mx_launch(const void* codes, const void* scales, void* wq
 // mcamd_q8_splitk_finish_launch
 int mcamd_q8_w4_mx_splitk_launch(const IgemmArgs& a, const SplitkPlan& p, const void* scales, const void* wexp, int y_f8, int y2_f8,
                                  float* ws, hipStream_t st);
+// conv_q4_mx.hip: MXFP4 activations -- the cast pass from the padded e4m3 buffer to codes [rows][cin / 2] + scale
+// words [rows][cin / 64], and the fp4 x fp4 forward on them and conv_q8_w4_mx.hip's weight operands (`a` addresses buffer rows:
+// x_ld 1, x_off 0; a.x = the activation codes, a.w = the weight codes); its choice: mcamd_q8_w4_mx_choice's tiles, four stages
+int mcamd_cast_a4_mx_launch(const void* x8, long long rows, int ld, int choff, int cin, void* codes, void* scales, hipStream_t st);
+Q8Choice mcamd_q4_mx_choice(long long M, int N);
+int mcamd_conv_q4_mx_launch(IgemmArgs& a, const void* xscales, const void* wscales, const void* wexp, int y_f8, int y2_f8,
+                            hipStream_t st);
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps);
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);

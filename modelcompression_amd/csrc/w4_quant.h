@@ -7,13 +7,20 @@
 // e4_f of a filter from max |w * mask|: the fp8 packers' exponent minus one, 0 for an all-zero filter
 __device__ __forceinline__ int w4_filter_exponent(float amax) { return amax > 0.f ? q8_filter_exponent(amax) - 1 : 0; }
 
-// Smallest g in [-5, 6] with amax <= 6 * 2^g (-5 for amax == 0), integer steps as q8_filter_exponent: (m, x) = frexp(amax),
-// 6 * 2^g = 0.75 * 2^(g + 3), so g = x - 3 if m <= 0.75 else x - 2.
-__device__ __forceinline__ int w4_group_shift(float amax) {
-    if (!(amax > 0.f)) return -5;
+// Smallest integer g with amax <= 6 * 2^g for amax > 0 (0 for amax == 0), integer steps as q8_filter_exponent: (m, x) =
+// frexp(amax), 6 * 2^g = 0.75 * 2^(g + 3), so g = x - 3 if m <= 0.75 else x - 2.  Unclamped: under it nothing saturates in
+// w4_code.  The MXFP4 activation cast (conv_q4_mx.hip) uses it as it stands: g in [-11, 7] for e4m3 inputs.
+__device__ __forceinline__ int w4_group_shift_free(float amax) {
+    if (!(amax > 0.f)) return 0;
     int x;
     const float m = frexpf(amax, &x);
-    const int g = m <= 0.75f ? x - 3 : x - 2;
+    return m <= 0.75f ? x - 3 : x - 2;
+}
+
+// ... clamped to the weight format's [-5, 6] (-5 for amax == 0)
+__device__ __forceinline__ int w4_group_shift(float amax) {
+    if (!(amax > 0.f)) return -5;
+    const int g = w4_group_shift_free(amax);
     return g < -5 ? -5 : g > 6 ? 6 : g;
 }
 

@@ -93,7 +93,7 @@ class _Layer:
     bs_on = property(lambda self: self.form == "bsparse")
     sk_on = property(lambda self: self.form == "splitk")
     q8_on = property(lambda self: self.form in ("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_w4_mx_splitk",
-                                                "q8_bsparse"))
+                                                "q4_mx", "q8_bsparse"))
     q8s_on = property(lambda self: self.form == "q8_sparse24")
     q8_slim = property(lambda self: self.form == "q8_slim")
 
@@ -560,9 +560,31 @@ class _Q8W4MxSplitK(_Q8W4Mx):
         return args, dict(kw, slices=lay.sk_slices, workspace=eng._splitk_ws)
 
 
+class _Q4Mx(_Q8W4Mx):
+    """An fp4-operand block whose ACTIVATIONS are MXFP4 too ("fp4-mx", csrc/conv_q4_mx.hip): the block-scaled MFMA
+    with four registers and one e8m0 scale per lane on both sides.  The weight operands and their packing are _Q8W4Mx's; the
+    block's byte input -- the engine's e4m3 buffer, or the private copy behind the fp16 -> fp8 edge cast -- goes through the cast
+    pass mcamd_cast_a4_mx into the engine's one scratch pair of codes and scale words, sized for the largest such block (the
+    blocks run one after another on the launch stream), and the launch reads that pair."""
+    fwd = "conv_fwd_q4_mx"
+
+    def alloc(self, eng, lays):
+        _Q8W4Mx.alloc(self, eng, lays)
+        need = [max(n) for n in zip(*(ops.a4_mx_elems(eng.B * (lay.tin.H + 2) * (lay.tin.W + 2), lay.cin) for lay in lays))]
+        if eng._a4_codes is None or eng._a4_codes.numel() < need[0] or eng._a4_scales.numel() < need[1]:
+            eng._a4_codes = torch.zeros(need[0], dtype=torch.uint8, device=eng.device)
+            eng._a4_scales = torch.zeros(need[1], dtype=torch.uint8, device=eng.device)
+
+    def operands(self, eng, lay, xin):
+        (g, x8, *w), kw = _Q8W4Mx.operands(self, eng, lay, xin)
+        eng._timed('cast4', lay, ops.cast_a4_mx, x8, eng.B * (lay.tin.H + 2) * (lay.tin.W + 2), g.x_ld, g.x_choff, lay.cin,
+                   eng._a4_codes, eng._a4_scales)
+        return (g, eng._a4_codes, eng._a4_scales, *w), kw
+
+
 _FORMS = {"dense": _Dense(), "splitk": _SplitK(), "lowrank": _LowRank(), "sparse24": _Sparse24(), "bsparse": _BSparse(), "bsparse_train": _BSparseTrain(), "q8": _Q8(),
           "q8_slim": _Q8Slim(), "q8_sparse24": _Q8Sparse24(), "q8_splitk": _Q8SplitK(), "q8_w4": _Q8W4(), "q8_w4_mx": _Q8W4Mx(),
-          "q8_w4_mx_splitk": _Q8W4MxSplitK(), "q8_bsparse": _Q8BSparse()}
+          "q8_w4_mx_splitk": _Q8W4MxSplitK(), "q4_mx": _Q4Mx(), "q8_bsparse": _Q8BSparse()}
 
 
 def _probe_side_stream(device, tries=8):
@@ -644,6 +666,11 @@ class Engine:
         split-K pair on the same packed operands (`fp8_w4_mx_splitk_layers`; `fp8_w4_mx_layers` lists every block on fp4
         operands, split or not); every other block, and every batch the policy does not split, runs exactly what "fp8-w4-mx"
         runs.  Differs from "fp8-w4-mx" by the order of the fp32 sums only.
+        "fp4-mx" -- the "fp8-w4-mx" engine with MXFP4 activations, inference only: every block of form
+        "q8_w4_mx" whose geometry mcamd_conv_fwd_q4_mx_ok accepts and whose conv number is not in Darknet.fp4_skip takes form
+        "q4_mx" (`fp4_layers`; `fp8_w4_mx_layers` keeps listing every block on 4-bit weights): a cast pass turns its e4m3 input
+        into e2m1 codes with one e8m0 scale per 32 channels and the kernel multiplies fp4 x fp4 (csrc/conv_q4_mx.hip); every other
+        block, the slim ones included, runs what "fp8-w4-mx" runs.  MCAMD_Q8_MFMA does not reach the form.
         "fp8-w4-qat" -- 4-bit quantisation-aware training: "fp8-qat" with the weights of every fp8 block in the
         4-bit format -- in training mode every block of `fp8_layers` (`fp8_w4_layers` is the same list) re-quantises its weights
         to codes, shifts and exponents every step and runs its forward on them (mcamd_conv_fwd_q8_w4_raw); the backward is
@@ -654,18 +681,18 @@ class Engine:
         chunks that hold a non-zero weight byte (csrc/conv_q8_bsparse.hip, `fp8_block_layers`, `fp8_block_kept`); every
         other block runs what "fp8" runs, and with nothing chosen it is the "fp8" engine bit for bit."""
         if precision not in ("fp16", "fp16x3", "mixed", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx",
-                             "fp8-w4-mx-splitk", "fp8-w4-qat", "fp8-block"):
+                             "fp8-w4-mx-splitk", "fp4-mx", "fp8-w4-qat", "fp8-block"):
             raise McamdError("precision must be 'fp16', 'fp16x3', 'mixed', 'fp8', 'fp8-2:4', 'fp8-splitk', 'fp8-qat', 'fp8-w4', "
-                             "'fp8-w4-mx', 'fp8-w4-mx-splitk', 'fp8-w4-qat' or 'fp8-block' (got %r)" % (precision,))
+                             "'fp8-w4-mx', 'fp8-w4-mx-splitk', 'fp4-mx', 'fp8-w4-qat' or 'fp8-block' (got %r)" % (precision,))
         self.model, self.B, self.device = model, B, device
         self.precision = precision
         self.for_training = bool(for_training)
         self.train_layout = bool(train_layout)     # built by a model in training mode: forward(training=True) only
         self.precise = precision not in ("fp16", "fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx",
-                                         "fp8-w4-mx-splitk", "fp8-w4-qat", "fp8-block")
+                                         "fp8-w4-mx-splitk", "fp4-mx", "fp8-w4-qat", "fp8-block")
         # fp8 quantised inference (Darknet.precision = "fp8"): conv numbers of the blocks that run mcamd_conv_fwd_q8, chosen
         # when the masks change (_choose_q8); `qbufs`: buffer id -> the BYTE buffer of an activation tensor stored as e4m3
-        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx", "fp8-w4-mx-splitk", "fp8-w4-qat",
+        self.q8 = precision in ("fp8", "fp8-2:4", "fp8-splitk", "fp8-qat", "fp8-w4", "fp8-w4-mx", "fp8-w4-mx-splitk", "fp4-mx", "fp8-w4-qat",
                                 "fp8-block")
         self.qat = precision in ("fp8-qat", "fp8-w4-qat")   # ... and their training-mode forward / straight-through backward
         self.fp8_layers = []
@@ -681,8 +708,13 @@ class Engine:
         self.q8_w4 = precision in ("fp8-w4", "fp8-w4-qat")
         self.fp8_w4_layers = []
         # "fp8-w4-mx": the blocks "fp8-w4" runs on 4-bit weights, on the fp4-operand kernel instead (form "q8_w4_mx")
-        self.q8_w4_mx = precision in ("fp8-w4-mx", "fp8-w4-mx-splitk")
+        self.q8_w4_mx = precision in ("fp8-w4-mx", "fp8-w4-mx-splitk", "fp4-mx")
         self.fp8_w4_mx_layers = []
+        # "fp4-mx": the subset of fp8_w4_mx_layers -- unpadded geometries outside Darknet.fp4_skip -- whose activations go through
+        # mcamd_cast_a4_mx into the scratch pair below and that run mcamd_conv_fwd_q4_mx (form "q4_mx")
+        self.q4_mx = precision == "fp4-mx"
+        self.fp4_layers = []
+        self._a4_codes = self._a4_scales = None
         # "fp8-w4-mx-splitk": the subset of fp8_w4_mx_layers -- unpadded geometries only -- the split-K policy gives two slices
         # or more and that run mcamd_conv_fwd_q8_w4_mx_splitk (form "q8_w4_mx_splitk"; they share `_splitk_ws` below)
         self.q8_w4_mx_splitk = precision == "fp8-w4-mx-splitk"
@@ -749,7 +781,7 @@ class Engine:
         self.lowrank_stale = []
         # what every block's form was last chosen for (pack): mask keys, block-sparse choice, sparse mode, sparse_max_kept,
         # split-K flag
-        self._form_key = (None, None, None, None, None, None)
+        self._form_key = (None, None, None, None, None, None, None)
         self._training, self._fold_key = None, None
         self.fold_dead = os.environ.get("MCAMD_FOLD_DEAD", "1") == "1"
         # "mixed": the two correction products of the split-operand forward from e4m3 copies on the block-scaled fp8 MFMAs
@@ -1201,13 +1233,15 @@ class Engine:
             sig.append((w.data_ptr(), w._version, None if m is None else (m.data_ptr(), m._version), bnv))
         return tuple(sig)
 
-    def pack(self, force=False, training=True, sparse=None, splitk=False, max_kept=None, wgrad_max_kept=None, lowrank=None):
+    def pack(self, force=False, training=True, sparse=None, splitk=False, max_kept=None, wgrad_max_kept=None, lowrank=None,
+             fp4_skip=None):
         """fp32 master * mask -> fp16 kernel layouts (replaces layers.py:59's per-forward multiply).
         `sparse`, `splitk`, `max_kept`: the inference options forward() validated (Darknet.sparse / splitk /
         sparse_max_kept; off in training mode); every block's form is chosen again when they or the masks change.
         `wgrad_max_kept` (sparse = "block-train" only; None: off): Darknet.sparse_train = "block-wgrad".
         `lowrank` (None: off): (Darknet.lowrank_max_cost, Darknet.lowrank_min_tiles, ((layer index, rank) of every block
-        with fresh factors))."""
+        with fresh factors)).
+        `fp4_skip` ("fp4-mx" only; None elsewhere): Darknet.fp4_skip as a sorted tuple of conv numbers."""
         if any(lay.fold is not None for lay in self.layers) and training != self._training:
             force = True          # the folded constants differ between batch and running statistics
         self._training = training
@@ -1218,7 +1252,7 @@ class Engine:
         # engine after grad_scale was halved) must not keep the static default exponents
         serial = self.model._weights_serial
         dirty = self.model._weights_dirty or serial != self._weights_seen
-        if not force and sig == self._packed_sig and (sparse, max_kept, splitk, lowrank) == self._form_key[2:] and not dirty:
+        if not force and sig == self._packed_sig and (sparse, max_kept, splitk, lowrank, fp4_skip) == self._form_key[2:] and not dirty:
             return
         if dirty or (self.f8 and self.serial % 1000 == 999):      # (and every 1 000th forward: slow drift)
             self._refresh_f8_wexp()
@@ -1236,7 +1270,7 @@ class Engine:
             exempt, self.bsparse_train_kept = self._bst_policy[1:]
         elif self.q8_bsparse and max_kept is not None:
             exempt, self.fp8_block_kept = _FORMS["q8_bsparse"].policy(self, max_kept)
-        key = (mkeys, exempt, sparse, max_kept, splitk, lowrank)
+        key = (mkeys, exempt, sparse, max_kept, splitk, lowrank, fp4_skip)
         if key != self._form_key:          # masks are static during retraining: planned once
             self._choose_forms(key)
         # (the list weight gradient follows the forms: chosen again when they, the masks -- part of the form key -- or its
@@ -1418,7 +1452,8 @@ class Engine:
              slim ones -- whose launch the split-K policy gives two slices or more, mcamd_conv_fwd_q8_splitk_info; under
              "fp8-w4" every block of form "q8" takes the 4-bit form "q8_w4", under "fp8-w4-mx" the form "q8_w4_mx", and under
              "fp8-w4-mx-splitk" an unpadded one of those that mcamd_conv_fwd_q8_w4_mx_splitk_info gives two slices or more the form
-             "q8_w4_mx_splitk"), 2:4
+             "q8_w4_mx_splitk"; under "fp4-mx" every block of form "q8_w4_mx" that mcamd_conv_fwd_q4_mx_ok accepts and
+             Darknet.fp4_skip does not name the form "q4_mx"), 2:4
              (sparse = "2:4": every eligible block whose mask conforms and whose geometry mcamd_conv_fwd_sparse24_ok accepts)
              or block-sparse (sparse = "block": the chosen blocks that
              are still eligible -- one whose producer was compacted after all, so that its input channels are permuted, stays
@@ -1428,7 +1463,7 @@ class Engine:
              and does when the library's policy gives the block's eval-mode launch two slices or more
              (mcamd_conv_fwd_splitk_info).
         Every other block stays dense.  The `*_layers` lists are the conv numbers (conv1 = the first block) per form."""
-        mkeys, exempt, sparse, max_kept, splitk, lowrank = key
+        mkeys, exempt, sparse, max_kept, splitk, lowrank, fp4_skip = key
         self._plan_epoch += 1             # recorded plans name each block's launch and hold its operands' addresses
         if (mkeys, exempt) != self._form_key[:2]:
             self._bs_exempt = exempt
@@ -1470,6 +1505,10 @@ class Engine:
                     info = ops.conv_fwd_q8_w4_mx_splitk_info(lay.geom_q8, lay.mode)
                     if info.slices >= 2:
                         lay.form, lay.sk_slices = "q8_w4_mx_splitk", info.slices
+            if self.q4_mx:
+                for lay in self.layers:
+                    if lay.form == "q8_w4_mx" and lay.li + 1 not in (fp4_skip or ()) and ops.conv_fwd_q4_mx_ok(lay.geom_q8):
+                        lay.form = "q4_mx"
         elif sparse == "2:4":
             for lay in self._conforming([lay for lay in self.layers
                                          if self._eligible(lay) and lay.conv.mask_flag and lay.cin % 4 == 0
@@ -1508,8 +1547,10 @@ class Engine:
         nums = lambda *names: [lay.li + 1 for lay in self.layers if lay.form in names]
         self.sparse_layers, self.bsparse_layers, self.splitk_layers = nums("sparse24"), nums("bsparse"), nums("splitk")
         self.lowrank_layers = nums("lowrank")
-        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_w4_mx_splitk", "q8_bsparse")
-        self.fp8_w4_mx_layers = nums("q8_w4_mx", "q8_w4_mx_splitk")
+        self.fp8_layers = nums("q8", "q8_slim", "q8_sparse24", "q8_splitk", "q8_w4", "q8_w4_mx", "q8_w4_mx_splitk", "q4_mx",
+                               "q8_bsparse")
+        self.fp8_w4_mx_layers = nums("q8_w4_mx", "q8_w4_mx_splitk", "q4_mx")
+        self.fp4_layers = nums("q4_mx")
         self.fp8_w4_mx_splitk_layers = nums("q8_w4_mx_splitk")
         self.fp8_block_layers = nums("q8_bsparse")
         if self._training:                   # (what the last training-mode choice was; an eval pass in between keeps it)
@@ -2041,8 +2082,15 @@ class Engine:
             if st == "block-wgrad" and float(getattr(self.model, "sparse_train_wgrad_max_kept", BSPARSE_TRAIN_WGRAD_MAX_KEPT)) > 0.0:
                 # (again 0.0 chooses nothing: sparse_train = "block", bit for bit, and no list is built)
                 wgrad_max = float(getattr(self.model, "sparse_train_wgrad_max_kept", BSPARSE_TRAIN_WGRAD_MAX_KEPT))
+        fp4_skip = None
+        if self.q4_mx and not training:
+            try:
+                fp4_skip = tuple(sorted(set(int(n) for n in getattr(self.model, "fp4_skip", ()))))
+            except (TypeError, ValueError):
+                raise McamdError("fp4_skip must be a collection of conv numbers (conv1 = the first block), got %r"
+                                 % (getattr(self.model, "fp4_skip", ()),))
         self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept, wgrad_max_kept=wgrad_max,
-                  lowrank=lowrank)
+                  lowrank=lowrank, fp4_skip=fp4_skip)
         self.serial += 1
         tin = self.layers[0].tin
         xs = x.detach().contiguous().float()

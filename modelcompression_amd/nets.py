@@ -320,6 +320,11 @@ class Darknet(nn.Module):
         # launch would leave most CUs idle runs as a split-K pair on the same packed operands
         # (engine.Engine.fp8_w4_mx_splitk_layers, csrc/conv_q8_w4_mx.hip); batches the policy does not split run
         # exactly what "fp8-w4-mx" runs; `sparse` and `splitk` stay off with it.
+        # "fp4-mx" (eval only, an opt-in): the "fp8-w4-mx" engine with MXFP4 ACTIVATIONS -- every fp4-operand block on an unpadded
+        # geometry whose conv number `fp4_skip` does not name casts its e4m3 input to e2m1 codes with one e8m0 scale per 32
+        # channels and multiplies fp4 x fp4, the form of the block-scaled MFMA that issues at 1.56x the fp8 rate
+        # (engine.Engine.fp4_layers, csrc/conv_q4_mx.hip); slim blocks and every other block run what "fp8-w4-mx"
+        # runs; a training-mode forward raises, and `sparse`, `splitk` and `lowrank` stay off with it.
         # "fp8-w4-qat" (an addition beyond the reference): 4-bit quantisation-aware training -- "fp8-qat" with the weights of every
         # fp8 block re-quantised to the "fp8-w4" format every step: the training-mode forward multiplies the codes the block would
         # be deployed with, the backward is straight-through on the values they stand for; in eval mode it is the "fp8-w4" engine,
@@ -332,6 +337,9 @@ class Darknet(nn.Module):
         self.precision = os.environ.get("MCAMD_PRECISION", "auto")
         from .engine import Q8_BSPARSE_MAX_KEPT
         self.fp8_block_max_kept = Q8_BSPARSE_MAX_KEPT    # the policy constant of "fp8-block" (engine.py)
+        # "fp4-mx": conv numbers (conv1 = the first block) that keep e4m3 activations -- form "q8_w4_mx" -- because early layers are
+        # where 4-bit activations cost most; changing it re-chooses the forms at the next forward
+        self.fp4_skip = ()
         # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA
         # (engine.Engine.sparse_layers).  "block" runs every eligible masked block on the block-sparse kernel

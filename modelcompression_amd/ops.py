@@ -1743,6 +1743,57 @@ def conv_fwd_q8_w4_mx(g, x8, codes, scales, wexp, y, y_ld, y_choff=0, scale=None
 
 
 # ... with the K axis cut into slices for low-batch inference
+# ... and with MXFP4 activations: the cast pass and the fp4 x fp4 forward
+def a4_mx_elems(rows, cin):
+    """(code bytes, scale bytes) of the MXFP4 activation format for `rows` buffer rows of `cin` channels (mcamd_a4_mx_elems)."""
+    out = (C.c_int64 * 2)()
+    check(L.lib().mcamd_a4_mx_elems(int(rows), int(cin), out), "mcamd_a4_mx_elems")
+    return int(out[0]), int(out[1])
+
+
+def cast_a4_mx(x8, rows, ld, choff, cin, out_codes=None, out_scales=None):
+    """e4m3 bytes [rows][ld], channels [choff, choff + cin) -> (e2m1 codes [rows][cin / 2], scale words [rows][cin / 64] as
+    bytes) of the fp4 x fp4 forward (mcamd_cast_a4_mx; the format is stated in include/mcamd.h)."""
+    _need_cuda(x8)
+    nc, ns = a4_mx_elems(rows, cin)
+    if out_codes is None:
+        out_codes = torch.empty(nc, dtype=torch.uint8, device=x8.device)
+    if out_scales is None:
+        out_scales = torch.empty(ns, dtype=torch.uint8, device=x8.device)
+    if out_codes.numel() < nc or out_scales.numel() < ns or x8.numel() < rows * ld:
+        raise L.McamdError("cast_a4_mx: operand too small")
+    check(L.lib().mcamd_cast_a4_mx(ptr(x8), int(rows), int(ld), int(choff), int(cin), ptr(out_codes), ptr(out_scales), stream_ptr()),
+          "mcamd_cast_a4_mx")
+    return out_codes, out_scales
+
+
+def conv_fwd_q4_mx_ok(g):
+    """Does mcamd_conv_fwd_q4_mx accept this geometry?  (conv_fwd_q8_w4_mx_ok's predicate and pad == 0; needs no device.)"""
+    return bool(L.lib().mcamd_conv_fwd_q4_mx_ok(C.byref(g)))
+
+
+def conv_fwd_q4_mx_info(g):
+    """The kernel instance conv_fwd_q4_mx launches for `g` (mcamd_conv_fwd_q4_mx_info): conv_fwd_q8_w4_mx_info's tile on a
+    four-stage ring.  Needs no GPU."""
+    out = (C.c_int32 * 7)()
+    check(L.lib().mcamd_conv_fwd_q4_mx_info(C.byref(g), out), "mcamd_conv_fwd_q4_mx_info")
+    return Q8Info(*out)
+
+
+def conv_fwd_q4_mx(g, xcodes, xscales, codes, scales, wexp, y, y_ld, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0,
+                   y2=None, y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None):
+    """conv_fwd_q8_w4_mx with cast_a4_mx's codes and scale words of the block's padded input in place of its bytes
+    (mcamd_conv_fwd_q4_mx): fp4 x fp4 on the block-scaled MFMA, the weight operands and the epilogue unchanged."""
+    rows = g.B * (g.H + 2) * (g.W + 2)
+    nc, ns = a4_mx_elems(rows, g.cin)
+    if xcodes.numel() < nc or xscales.numel() < ns:
+        raise L.McamdError("conv_fwd_q4_mx: activation codes / scales too small for %d rows of %d channels" % (rows, g.cin))
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff, overflow=overflow)
+    check(L.lib().mcamd_conv_fwd_q4_mx(C.byref(g), ptr(xcodes), ptr(xscales), ptr(codes), ptr(scales), ptr(wexp), C.byref(e),
+                                       int(bool(y_f8)), int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q4_mx")
+
+
 def conv_fwd_q8_w4_mx_splitk_info(g, dst_mode=0, slices=0):
     """mcamd_splitk_info of a split-K fp4-operand forward of `g` (mcamd_conv_fwd_q8_w4_mx_splitk_info): host logic only, and
     conv_fwd_q8_splitk_info's answer -- one policy, one tile.  slices = 0 asks the policy; > 0 sizes a forced slice count."""

@@ -5,7 +5,9 @@ the on leg "fp8-splitk" (MCAMD_Q8_MFMA picks the MFMA form of both
 measured in the same process beside them.  --precision fp8-w4: the off leg is precision "fp8", the on leg "fp8-w4" (4-bit
 weights) on the dense model only; nothing is split there, and the launch record and the per-layer table carry
 fields of their own (`w4_layers`; `w4`, `us_fp8`, `us_fp8_w4`) in place of the split-K ones.  --precision fp8-w4-mx: the same with
-the on leg "fp8-w4-mx" (the codes as the MFMA's fp4 operand; `w4_layers` is its fp8_w4_mx_layers).
+the on leg "fp8-w4-mx" (the codes as the MFMA's fp4 operand; `w4_layers` is its fp8_w4_mx_layers).  --precision
+fp4-mx: the same with the on leg "fp4-mx" (MXFP4 activations too; the layer table times the conv launches, the
+cast pass in front of each is in the whole-forward figures only).
 --precision fp8-w4-mx-splitk: the off leg is precision "fp8-w4-mx", the on leg "fp8-w4-mx-splitk"  on the dense
 model, with the split-K fields and per-layer table of the fp8 pair; the "fp8" / "fp8-splitk" legs and the fp16 split-K legs of
 the same model are measured in the same process beside them.
@@ -17,7 +19,7 @@ instrumented pass (the engine's HIP events around every conv launch, plan replay
 tiles, slices, us unsplit, us split (partial + finish launch).  Launch counts: the library calls of the recorded forward plan
 (a split block is one call and two kernels), the eval-mode bn_coeffs launches among them and the layout pass in front.
 
-usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8|fp8-w4|fp8-w4-mx|fp8-w4-mx-splitk]
+usage: python tools/latency_bench.py [--json] [--calls N] [--pairs N] [--precision fp16|fp8|fp8-w4|fp8-w4-mx|fp8-w4-mx-splitk|fp4-mx]
                                                                              (--json: one JSON document on stdout)"""
 import json
 import os
@@ -39,9 +41,9 @@ def arg(name, dflt):
 
 CALLS, PAIRS, PASSES = max(200, arg("--calls", 200)), max(4, arg("--pairs", 4)), 7
 PRECISION = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp16"
-if PRECISION not in ("fp16", "fp8", "fp8-w4", "fp8-w4-mx", "fp8-w4-mx-splitk"):
-    raise SystemExit("--precision must be fp16, fp8, fp8-w4, fp8-w4-mx or fp8-w4-mx-splitk (got %r)" % PRECISION)
-W4 = PRECISION in ("fp8-w4", "fp8-w4-mx")
+if PRECISION not in ("fp16", "fp8", "fp8-w4", "fp8-w4-mx", "fp8-w4-mx-splitk", "fp4-mx"):
+    raise SystemExit("--precision must be fp16, fp8, fp8-w4, fp8-w4-mx, fp8-w4-mx-splitk or fp4-mx (got %r)" % PRECISION)
+W4 = PRECISION in ("fp8-w4", "fp8-w4-mx", "fp4-mx")
 MXSK = PRECISION == "fp8-w4-mx-splitk"
 ON_LEG = PRECISION if W4 or MXSK else "fp8-splitk"     # the on leg of an fp8 model
 LEGS = ["fp8-w4-mx" if MXSK else "fp8", ON_LEG]         # [off, on] precisions of an fp8 model (main swaps in the fp8 pair)
@@ -115,7 +117,7 @@ def layer_table(m, x):
         per[flag] = {k: median(v) for k, v in acc.items()}
     eng = engine(m, x)
     if W4:                      # nothing is split: the block's form on the "fp8-w4" leg and its time on either leg
-        return [{"conv": lay.li + 1, "form": lay.form, "w4": lay.form in ("q8_w4", "q8_w4_mx"), "us_fp8": per[False].get(lay.li + 1),
+        return [{"conv": lay.li + 1, "form": lay.form, "w4": lay.form in ("q8_w4", "q8_w4_mx", "q4_mx"), "us_fp8": per[False].get(lay.li + 1),
                  "us_fp8_w4": per[True].get(lay.li + 1)} for lay in eng.layers]
     rows = []
     for lay in eng.layers:
@@ -149,7 +151,7 @@ def launches(m, x):
             "bn_coeffs": sum(1 for lay in eng.layers if lay.bn is not None),
             "layout_pass": 1}
         if W4:                  # (a w4 block is one launch, like the fp8 block it stands in for)
-            out["on" if flag else "off"]["w4_layers"] = list(eng.fp8_w4_mx_layers if eng.precision == "fp8-w4-mx" else eng.fp8_w4_layers)
+            out["on" if flag else "off"]["w4_layers"] = list(eng.fp8_w4_mx_layers if eng.precision in ("fp8-w4-mx", "fp4-mx") else eng.fp8_w4_layers)
         else:
             out["on" if flag else "off"].update(splitk_finish_kernels=len(split_layers(eng)), splitk_layers=split_layers(eng))
     return out

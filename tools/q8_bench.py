@@ -8,7 +8,8 @@ fp16 with sparse = "2:4", fp8 and fp8-2:4 (windows alternated over all four).
 unfused border path) and fp8 the same way, and the table names per layer cin -> round_up(cin, 64), which blocks are fp8
 blocks (`slim`: on mcamd_conv_fwd_q8_slim, `table`: with a border table) and the time of each cast pass.  Run it once
 without and once with MCAMD_Q8_MFMA=1 for the two forms of the fp8 kernel.
---w4: "fp8" against "fp8-w4" (4-bit weights) and "fp8-w4-mx" (the codes as the MFMA's fp4 operand, 3zg; it does
+--w4: "fp8" against "fp8-w4" (4-bit weights), "fp8-w4-mx" (the codes as the MFMA's fp4 operand, 3zg) and "fp4-mx"
+(MXFP4 activations too, 3zj: its cast pass in a column of its own, the kernel's TFLOP/s on conv22) ("fp8-w4-mx" does
 not read MCAMD_Q8_MFMA) on the same weights, the three alternated in one process, with the
 resident weight-operand bytes of the fp8 blocks under each -- once per MCAMD_Q8_MFMA form, each form in a child process of its
 own started with that switch; the merged report goes to profiles/q8_w4_bench.json unless --json names another file.
@@ -63,7 +64,7 @@ def main(argv):
         m.set_masks(nm_prune(m))
         modes = ("fp16", "fp16+2:4", "fp8", "fp8-2:4")
     if w4:
-        modes = ("fp8", "fp8-w4", "fp8-w4-mx")
+        modes = ("fp8", "fp8-w4", "fp8-w4-mx", "fp4-mx")
 
     def select(mode):
         m.precision, m.sparse = mode.split("+")[0], "2:4" if mode.endswith("+2:4") else None
@@ -98,9 +99,20 @@ def main(argv):
             res[prec] = {"logits": y.clone(), "layers": layer_times(prec)}
             if slim_pct is not None and prec == "fp8":
                 res[prec]["casts"] = layer_times(prec, only="cast")
+            if prec == "fp4-mx":                # (the MXFP4 activation cast in front of each fp4 x fp4 block)
+                res[prec]["casts"] = layer_times(prec, only="cast4")
+            if prec == "fp8":
+                fp8_layers = list(engine("fp8").fp8_layers)
+            if w4:                              # (a model keeps three engines: read what the report needs while this one lives)
+                from modelcompression_amd.engine import _FORMS
+                e = engine(prec)
+                res[prec]["snap"] = {
+                    "w4": list(e.fp8_w4_layers), "mx": list(e.fp8_w4_mx_layers), "fp4": list(e.fp4_layers),
+                    "flop": {lay.li + 1: 2.0 * lay.M * lay.cout * lay.cin * lay.k * lay.k for lay in e.layers},
+                    "nbytes": sum(getattr(lay, name).numel() * getattr(lay, name).element_size()
+                                  for lay in e.layers if lay.li + 1 in e.fp8_layers for name, _ in _FORMS[lay.form].bufs)}
             if prec == "fp16+2:4":
                 sparse_layers = list(engine(prec).sparse_layers)
-        fp8_layers = list(engine("fp8").fp8_layers)
         rates = {p: [] for p in modes}
         for rep in range(3):                   # alternated: the two engines see the same host / GPU conditions
             for prec in modes:
@@ -116,13 +128,11 @@ def main(argv):
         return res, rates, fp8_layers, sparse_layers if sparse else None
 
     if w4:                                     # (one MFMA form: the caller's MCAMD_Q8_MFMA, as in every other mode)
-        from modelcompression_amd.engine import _FORMS
         with torch.no_grad():
             res, rates, fp8_layers, _ = measure()
-        nbytes = {p: sum(getattr(lay, name).numel() * getattr(lay, name).element_size()
-                         for lay in engine(p).layers if lay.li + 1 in fp8_layers for name, _ in _FORMS[lay.form].bufs) for p in modes}
-        return report_w4(B, K, out_json, os.environ.get("MCAMD_Q8_MFMA", "0"), res, rates, fp8_layers,
-                         list(engine("fp8-w4").fp8_w4_layers), nbytes, list(engine("fp8-w4-mx").fp8_w4_mx_layers))
+        snap = {p: res[p]["snap"] for p in modes}
+        return report_w4(B, K, out_json, os.environ.get("MCAMD_Q8_MFMA", "0"), res, rates, fp8_layers, snap["fp8-w4"]["w4"],
+                         {p: snap[p]["nbytes"] for p in modes}, snap["fp8-w4-mx"]["mx"], snap["fp4-mx"]["fp4"], snap["fp4-mx"]["flop"])
     with torch.no_grad():
         res, rates, fp8_layers, sparse_layers = measure()
 
@@ -170,7 +180,34 @@ def run_w4_forms(argv, B, K, out_json):
         json.dump(out, f, indent=1)
 
 
-def report_w4(B, K, out_json, mfma, res, rates, fp8_layers, w4_layers, nbytes, mx_layers):
+def report_fp4(B, K, res, rates, fp4_layers, flop):
+    """The "fp4-mx" leg of --w4 beside "fp8-w4-mx": per layer the block's launches with the cast pass in its own column, the
+    layers where the form loses, the whole forward, and the fp4 x fp4 kernel's rate on conv22.  Returns its JSON fields."""
+    x, q = res["fp8-w4-mx"], res["fp4-mx"]
+    print("fp4 layers %s" % fp4_layers)
+    print("%-6s %12s %12s %10s %10s %9s" % ("conv", "fp8-w4-mx ms", "fp4-mx ms", "cast ms", "kernel ms", "fp4 / mx"))
+    loses = []
+    for k in sorted(x["layers"]):
+        xm, qm, cm = x["layers"][k], q["layers"].get(k, float("nan")), q["casts"].get(k, 0.0)
+        if k in fp4_layers and qm > xm:
+            loses.append(k)
+        print("%-6s %12.3f %12.3f %10.3f %10.3f %9.2f%s" % ("conv%d" % k, xm, qm, cm, qm - cm, qm / xm, "" if k in fp4_layers else "  (not fp4)"))
+    tx, tq, tc = sum(x["layers"].values()), sum(q["layers"].values()), sum(q["casts"].values())
+    print("%-6s %12.3f %12.3f %10.3f %10.3f %9.2f" % ("sum", tx, tq, tc, tq - tc, tq / tx))
+    r = rates["fp4-mx"]
+    pairs = [b / a for a, b in zip(rates["fp8-w4-mx"], r)]
+    print("whole forward B=%d, %d forwards per window, fp4-mx: %s img/s (spread %.2f %%); pairs fp4-mx / fp8-w4-mx %s; / fp8 %s"
+          % (B, K, ["%.0f" % v for v in r], 100.0 * (max(r) - min(r)) / min(r), ["%.3f" % p for p in pairs],
+             ["%.3f" % (b / a) for a, b in zip(rates["fp8"], r)]))
+    tf = {p: flop[22] / (res[p]["layers"][22] - (q["casts"].get(22, 0.0) if p == "fp4-mx" else 0.0)) * 1e-9 for p in ("fp8-w4-mx", "fp4-mx")}
+    print("conv22 kernel: fp8-w4-mx %.0f TFLOP/s, fp4-mx %.0f TFLOP/s (tools/f4_probe.hip issue rates: 4 974 / 7 738); fp4 layers slower "
+          "than fp8-w4-mx, cast included: %s" % (tf["fp8-w4-mx"], tf["fp4-mx"], loses))
+    return {"fp4_layers": fp4_layers, "fp4_mx_ms": q["layers"], "fp4_mx_cast_ms": q["casts"], "fp4_mx_img_s": r,
+            "pairs_fp4_mx_over_w4_mx": pairs, "conv22_tflops": tf, "fp4_layers_slower_than_w4_mx": loses,
+            "rel_l2_fp4_mx_vs_fp8": float((q["logits"].double() - res["fp8"]["logits"].double()).norm() / res["fp8"]["logits"].double().norm())}
+
+
+def report_w4(B, K, out_json, mfma, res, rates, fp8_layers, w4_layers, nbytes, mx_layers, fp4_layers, flop):
     d, s, x = res["fp8"], res["fp8-w4"], res["fp8-w4-mx"]
 
     def rel(a):
@@ -195,10 +232,11 @@ def report_w4(B, K, out_json, mfma, res, rates, fp8_layers, w4_layers, nbytes, m
     print("resident weight-operand bytes of the fp8 blocks: fp8 %d, fp8-w4 %d (%.4f x), fp8-w4-mx %d"
           % (nbytes["fp8"], nbytes["fp8-w4"], nbytes["fp8-w4"] / nbytes["fp8"], nbytes["fp8-w4-mx"]))
     print("logits rel-L2 against the fp8 engine, same weights: fp8-w4 %.3e, fp8-w4-mx %.3e" % (rel(s), rel(x)))
+    fp4 = report_fp4(B, K, res, rates, fp4_layers, flop)
     sys.stdout.flush()
     if out_json:
         with open(out_json, "w") as f:
-            json.dump({"fp8_layers": fp8_layers, "fp8_w4_layers": w4_layers, "fp8_ms": d["layers"], "fp8_w4_ms": s["layers"],
+            json.dump({"fp4_mx": fp4, "fp8_layers": fp8_layers, "fp8_w4_layers": w4_layers, "fp8_ms": d["layers"], "fp8_w4_ms": s["layers"],
                        "fp8_img_s": rates["fp8"], "fp8_w4_img_s": rates["fp8-w4"], "pairs_w4_over_fp8": pairs,
                        "weight_operand_bytes": nbytes, "rel_l2_w4_vs_fp8": rel(s),
                        "fp8_w4_mx_layers": mx_layers, "fp8_w4_mx_ms": x["layers"], "fp8_w4_mx_img_s": rates["fp8-w4-mx"],
