@@ -711,6 +711,40 @@ int mcamd_conv_fwd_q4_mx(const mcamd_conv_geom* g, const void* xcodes, const voi
 int mcamd_conv_fwd_q4_mx_info(const mcamd_conv_geom* g, int32_t out[7]);
 
 /* ---------------------------------------------------------------------------
+ * ... written by the PRODUCER's epilogue (an addition beyond the reference; DESIGN.md 3zk, Darknet.fp4_fused): both fp4-operand
+ * forwards with MXFP4 destinations.  The epilogue has the finished tile as e4m3(2 v) bytes; a destination described by a
+ * mcamd_a4_dst receives mcamd_cast_a4_mx's codes and scale words of those bytes -- the format above to the letter (group
+ * maximum on the low seven bits, byte 127 and zero codes for an all-zero group, +-448 -> 512, a NaN byte read as +-480, no sign
+ * on a zero code) -- so the result is byte for byte what the same call into an e4m3 destination followed by mcamd_cast_a4_mx
+ * over it writes, and the consumer's mcamd_conv_fwd_q4_mx reads it with no pass in between.
+ *   codes / scales  the destination tensor's [rows][channels / 2] code bytes and [rows][channels / 64] scale words over its
+ *                   PADDED rows (B (Ho + 2) (Wo + 2), Ho x Wo = the destination's resolution: pooled for y under POOL / REORG);
+ *   choff           the call writes channels [choff, choff + cout) -- REORG: [choff, choff + 4 cout), out channel (dy * 2 + dx) *
+ *                   cout + n -- of the INTERIOR pixels' codes and scale words and nothing else: the halo rows must already hold
+ *                   the halo's contents (zero codes, scale words 0x00007f7f).
+ * dst_mode POOL takes the 2x2 maximum of the bytes first and quantises the pooled bytes; its copy y2 quantises the unpooled ones.
+ * Rules (anything else returns MCAMD_EINVAL with a message): cout % 64 == 0; channels > 0, channels % 64 == 0, choff >= 0,
+ * choff % 64 == 0 and the written slice inside `channels`; codes 16-byte aligned, scales 4-byte aligned; y2_a4 needs epi->y2 != NULL.
+ * ------------------------------------------------------------------------- */
+typedef struct mcamd_a4_dst {
+    void* codes;
+    void* scales;
+    int32_t channels;
+    int32_t choff;
+} mcamd_a4_dst;
+/* mcamd_conv_fwd_q4_mx's arguments + y_a4 / y2_a4: a non-NULL entry overrides that destination's format (epi->y / epi->y2 of
+ * such a destination are not written but must still describe a valid slice -- pass the codes, `channels` and `choff`); NULL
+ * leaves y_f8 / y2_f8 in force, so y and y2 independently take fp16, e4m3 or MXFP4.  With both NULL the call IS
+ * mcamd_conv_fwd_q4_mx. */
+int mcamd_conv_fwd_q4_mx_a4(const mcamd_conv_geom* g, const void* xcodes, const void* xscales, const void* codes, const void* scales,
+                            const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8,
+                            const mcamd_a4_dst* y_a4, const mcamd_a4_dst* y2_a4, void* stream);
+/* The same for mcamd_conv_fwd_q8_w4_mx (e4m3 activations in, MXFP4 out: the producer in front of the first fp4 x fp4 block). */
+int mcamd_conv_fwd_q8_w4_mx_a4(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* scales, const int32_t* wexp,
+                               const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8, const mcamd_a4_dst* y_a4,
+                               const mcamd_a4_dst* y2_a4, void* stream);
+
+/* ---------------------------------------------------------------------------
  * 4-bit quantisation-aware training (an addition beyond the reference; Darknet.precision = "fp8-w4-qat"): the
  * fp8 quantisation-aware training above with the weights of every fp8 block in the 4-bit format above -- the training-mode
  * forward of a block runs on the codes it would be deployed with under "fp8-w4".

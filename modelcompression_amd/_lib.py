@@ -29,6 +29,10 @@ class ConvEpilogue(C.Structure):
                 ("concurrent", C.c_int32)]
 
 
+class A4Dst(C.Structure):
+    _fields_ = [("codes", C.c_void_p), ("scales", C.c_void_p), ("channels", C.c_int32), ("choff", C.c_int32)]
+
+
 class ActDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
                 ("y", C.c_void_p), ("y_ld", C.c_int32), ("y_choff", C.c_int32),
@@ -315,6 +319,10 @@ SIGNATURES = {
     "mcamd_conv_fwd_q4_mx_ok": (_I32, [C.POINTER(ConvGeom)]),
     "mcamd_conv_fwd_q4_mx": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _P]),
     "mcamd_conv_fwd_q4_mx_info": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(_I32)]),
+    "mcamd_conv_fwd_q4_mx_a4": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32,
+                                          C.POINTER(A4Dst), C.POINTER(A4Dst), _P]),
+    "mcamd_conv_fwd_q8_w4_mx_a4": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32,
+                                             C.POINTER(A4Dst), C.POINTER(A4Dst), _P]),
     "mcamd_conv_fwd_q8_w4_mx_splitk_info": (C.c_int, [C.POINTER(ConvGeom), _I32, _I32, C.POINTER(SplitkInfo)]),
     "mcamd_conv_fwd_q8_w4_mx_splitk": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _I32, _I32, _I32, _P, _SZ, _P]),
     "mcamd_conv_fwd_q8_w4_raw": (C.c_int, [C.POINTER(ConvGeom), _P, _P, _P, _P, C.POINTER(ConvEpilogue), _P]),

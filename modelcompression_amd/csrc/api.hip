@@ -1589,6 +1589,92 @@ extern "C" int mcamd_conv_fwd_q4_mx_info(const mcamd_conv_geom* g, int32_t out[7
     return MCAMD_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// ... and both fp4-operand forwards with MXFP4 DESTINATIONS: the producer's epilogue writes the consumer's
+// activation format, no cast pass in between
+// ---------------------------------------------------------------------------------------
+// one destination: mcamd.h's rules for `span` channels from in->choff; NULL leaves `out` empty
+static int a4_dst_fill(const mcamd_a4_dst* in, int n_out, int span, const char* what, const char* which, A4Dst& out) {
+    out = A4Dst{nullptr, nullptr, 0, 0, 0};
+    if (!in) return MCAMD_OK;
+    MCAMD_REQUIRE(n_out % 64 == 0, "%s: an MXFP4 destination needs cout %% 64 == 0 (whole groups and scale words), got %d", what, n_out);
+    MCAMD_REQUIRE(in->codes && in->scales, "%s: %s: null codes / scales", what, which);
+    MCAMD_REQUIRE(in->channels > 0 && in->channels % 64 == 0 && in->choff >= 0 && in->choff % 64 == 0 && in->choff + span <= in->channels,
+                  "%s: %s: channel slice [%d, %d) must start at a multiple of 64 inside a channel count (%d) that is one", what, which,
+                  in->choff, in->choff + span, in->channels);
+    MCAMD_REQUIRE(((uintptr_t)in->codes & 15) == 0 && ((uintptr_t)in->scales & 3) == 0,
+                  "%s: %s: codes must be 16-byte aligned and scale words 4-byte aligned", what, which);
+    out = A4Dst{(char*)in->codes, (int*)in->scales, in->channels / 2, in->channels / 64, in->choff};
+    return MCAMD_OK;
+}
+
+// both destinations and their formats, behind fill_epilogue
+static int a4_dsts(const mcamd_conv_geom* g, const mcamd_conv_epilogue* epi, const mcamd_a4_dst* y_a4, const mcamd_a4_dst* y2_a4, int y_f8,
+                   int y2_f8, const char* what, int& fy, int& fy2, A4Dst& d, A4Dst& d2) {
+    MCAMD_REQUIRE(!y2_a4 || epi->y2, "%s: y2_a4 without a full-resolution copy (epi->y2 NULL)", what);
+    if (a4_dst_fill(y_a4, g->cout, epi->dst_mode == MCAMD_DST_REORG ? 4 * g->cout : g->cout, what, "y_a4", d) ||
+        a4_dst_fill(y2_a4, g->cout, g->cout, what, "y2_a4", d2))
+        return MCAMD_EINVAL;
+    fy = y_a4 ? MCAMD_FMT_A4 : y_f8 ? MCAMD_FMT_F8 : MCAMD_FMT_F16;
+    fy2 = y2_a4 ? MCAMD_FMT_A4 : y2_f8 ? MCAMD_FMT_F8 : MCAMD_FMT_F16;
+    return MCAMD_OK;
+}
+
+extern "C" int mcamd_conv_fwd_q4_mx_a4(const mcamd_conv_geom* g, const void* xcodes, const void* xscales, const void* codes,
+                                       const void* scales, const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8,
+                                       int32_t y2_f8, const mcamd_a4_dst* y_a4, const mcamd_a4_dst* y2_a4, void* stream) {
+    if (!y_a4 && !y2_a4) return mcamd_conv_fwd_q4_mx(g, xcodes, xscales, codes, scales, wexp, epi, y_f8, y2_f8, stream);
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q4_mx_a4: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        const mcamd_a4_dst d_ = y_a4 ? *y_a4 : mcamd_a4_dst{}, d2_ = y2_a4 ? *y2_a4 : mcamd_a4_dst{};
+        const bool has = y_a4 != nullptr, has2 = y2_a4 != nullptr;
+        return mcamd_rec_push(stream, [=](void* s) {
+            return mcamd_conv_fwd_q4_mx_a4(&g_, xcodes, xscales, codes, scales, wexp, &e_, y_f8, y2_f8, has ? &d_ : nullptr,
+                                           has2 ? &d2_ : nullptr, s);
+        });
+    }
+    if (check_geom(g, "conv_fwd_q4_mx_a4") || q4_mx_refuse(g, "conv_fwd_q4_mx_a4")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(xcodes && xscales && codes && scales && wexp, "conv_fwd_q4_mx_a4: null input");
+    MCAMD_REQUIRE((((uintptr_t)xcodes) & 15) == 0 && ((uintptr_t)xscales & 3) == 0, "conv_fwd_q4_mx_a4: misaligned activation codes / scales");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q4_mx_a4: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, xcodes, codes, 1, 0, g->cout, g->cin, 0);     // (strides in buffer rows: a row is cin / 2 code bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q4_mx_a4", 0)) return MCAMD_EINVAL;
+    int fy, fy2;
+    A4Dst d, d2;
+    if (a4_dsts(g, epi, y_a4, y2_a4, y_f8, y2_f8, "conv_fwd_q4_mx_a4", fy, fy2, d, d2)) return MCAMD_EINVAL;
+    return mcamd_conv_q4_mx_a4_launch(a, xscales, scales, wexp, fy, fy2, d, d2, (hipStream_t)stream);
+}
+
+extern "C" int mcamd_conv_fwd_q8_w4_mx_a4(const mcamd_conv_geom* g, const void* x8, const void* codes, const void* scales,
+                                          const int32_t* wexp, const mcamd_conv_epilogue* epi, int32_t y_f8, int32_t y2_f8,
+                                          const mcamd_a4_dst* y_a4, const mcamd_a4_dst* y2_a4, void* stream) {
+    if (!y_a4 && !y2_a4) return mcamd_conv_fwd_q8_w4_mx(g, x8, codes, scales, wexp, epi, y_f8, y2_f8, stream);
+    if (mcamd_recording()) {
+        MCAMD_REQUIRE(g && epi, "conv_fwd_q8_w4_mx_a4: null geometry / epilogue");
+        const mcamd_conv_geom g_ = *g;
+        const mcamd_conv_epilogue e_ = *epi;
+        const mcamd_a4_dst d_ = y_a4 ? *y_a4 : mcamd_a4_dst{}, d2_ = y2_a4 ? *y2_a4 : mcamd_a4_dst{};
+        const bool has = y_a4 != nullptr, has2 = y2_a4 != nullptr;
+        return mcamd_rec_push(stream, [=](void* s) {
+            return mcamd_conv_fwd_q8_w4_mx_a4(&g_, x8, codes, scales, wexp, &e_, y_f8, y2_f8, has ? &d_ : nullptr, has2 ? &d2_ : nullptr, s);
+        });
+    }
+    if (check_geom(g, "conv_fwd_q8_w4_mx_a4")) return MCAMD_EINVAL;
+    MCAMD_REQUIRE(mcamd_conv_fwd_q8_w4_mx_ok(g), "conv_fwd_q8_w4_mx_a4: geometry has no 4-bit fp8 form (mcamd_conv_fwd_q8_w4_mx_ok)");
+    MCAMD_REQUIRE(x8 && codes && scales && wexp, "conv_fwd_q8_w4_mx_a4: null input");
+    MCAMD_REQUIRE(epi && epi->mode == MCAMD_EPI_PAD_F16, "conv_fwd_q8_w4_mx_a4: epilogue mode 2 (MCAMD_EPI_PAD_F16) only");
+    IgemmArgs a;
+    fill_operand(a, g, x8, codes, g->x_ld, g->x_choff, g->cout, g->cin, 0);   // (strides in elements = bytes)
+    if (fill_epilogue(a, epi, g->cout, "conv_fwd_q8_w4_mx_a4", 0)) return MCAMD_EINVAL;
+    int fy, fy2;
+    A4Dst d, d2;
+    if (a4_dsts(g, epi, y_a4, y2_a4, y_f8, y2_f8, "conv_fwd_q8_w4_mx_a4", fy, fy2, d, d2)) return MCAMD_EINVAL;
+    return mcamd_conv_q8_w4_mx_a4_launch(a, scales, wexp, fy, fy2, d, d2, (hipStream_t)stream);
+}
+
 // mcamd_q8_choice()'s answer: what mcamd_conv_fwd_q8 (forms 0, 1), mcamd_conv_fwd_q8_slim (form 2) and
 // mcamd_conv_fwd_q8_sparse24 (form 3) launch for this geometry (host logic only)
 extern "C" int mcamd_conv_fwd_q8_info(const mcamd_conv_geom* g, int32_t form, int32_t out[7]) {

@@ -11,6 +11,7 @@
 // padded buffer: the raw output never exists and no activation pass runs.
 #pragma once
 #include "kernels.h"
+#include "w4_quant.h"
 
 // row-major pixel index p of images of HW = H * W pixels -> (image b, pixel hw of it) -> (b, h, w)
 __device__ __forceinline__ void split_image(int p, int HW, int& b, int& hw) {
@@ -172,6 +173,133 @@ __device__ __forceinline__ void store_pad_tile(const IgemmArgs& __restrict__ a, 
                 put8(a.y, y_f8, pad_off(b, ho, wo, Ho, Wo, a.y_ld) + a.y_choff + (m & 3) * a.N + n0, bt, ht, row * PITCH + ch * 8);
             }
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// The sibling whose destinations can be MXFP4 (mcamd.h "MXFP4 activations"): the e4m3 bytes of the byte tile
+// are quantised on their way out by mcamd_cast_a4_mx's rule -- w4_quant.h's shift and code on the low seven bits' group
+// maximum -- so the consumer's fp4 x fp4 forward reads them with no cast pass in between.  Format per destination (fy / fy2):
+// MCAMD_FMT_F16, MCAMD_FMT_F8 (store_pad_tile's paths) or MCAMD_FMT_A4.
+//
+// Work split of an MXFP4 destination: thread (tile row r = tid % ROWS, 64-channel block tid / ROWS) -- at most one per thread.
+// The lanes of a wave hold CONSECUTIVE rows of one block, so each ds_read_b64 of a lane's bytes (rows are PITCH = COLS + 8
+// bytes apart: 8-byte aligned, not 16, hence eight 8-byte reads where 16-byte alignment would allow four) reads 32 rows
+// 2 (PITCH / 8) banks apart -- PITCH / 8 is odd, every bank once.  One group of 32 channels at a time (eight registers; both
+// groups at once cost the kernels a wave per SIMD): its maximum in the lane's registers, one 16-byte code store; then ONE
+// aligned scale word (byte h = 127 + s of group h, bytes 2-3 zero).  POOL: the tile is in pooled order, so the four rows of a
+// window are the four lanes of a quad -- the 2x2 maximum is taken on the order-preserving keys by two DPP quad_perm exchanges
+// (no LDS traffic), lanes 0 / 1 of the quad quantise group 0 / 1 of the pooled bytes and lane 0 stores the word.  Halo rows and
+// channels outside [choff, choff + N) are never written: the engine initialises them once.
+// ---------------------------------------------------------------------------------------
+// (MCAMD_FMT_*, A4Dst: kernels.h)
+// the 32 e4m3 bytes of one group (8 registers) -> its 16 code bytes; returns the e8m0 byte 127 + s
+__device__ __forceinline__ int a4_quant32(const unsigned (&v)[8], i32x4_t& out) {
+    unsigned top = 0;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        const unsigned m7 = v[d] & 0x7f7f7f7fu;
+        top = max(max(top, m7 & 0xffu), max((m7 >> 8) & 0xffu, max((m7 >> 16) & 0xffu, m7 >> 24)));
+    }
+    const int s = w4_group_shift_free(a4_mag(top));
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        unsigned word = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const unsigned b = (v[2 * d + e / 4] >> (8 * (e & 3))) & 0xffu;
+            const float x = a4_mag(b);
+            word |= w4_code((b & 0x80u) ? -x : x, s) << (4 * e);
+        }
+        out[d] = (int)word;
+        __builtin_amdgcn_sched_barrier(0);         // (one code register at a time: interleaved, the 32 channels' temporaries pile up)
+    }
+    return 127 + s;
+}
+
+// group h of the 64 bytes at tile address p
+__device__ __forceinline__ void a4_read32(const char* p, int h, unsigned (&g)[8]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const i32x2_t t = *(const i32x2_t*)(p + h * 32 + i * 8);
+        g[2 * i] = (unsigned)t[0], g[2 * i + 1] = (unsigned)t[1];
+    }
+}
+
+// the 64 bytes at tile address p to buffer row `prow`, channels [ch, ch + 64), of one MXFP4 destination
+__device__ __forceinline__ void a4_put64(const A4Dst& d, long long prow, int ch, const char* p, bool live) {
+    int word = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        unsigned g[8];
+        i32x4_t c;
+        a4_read32(p, h, g);
+        word |= a4_quant32(g, c) << (8 * h);
+        if (live) *(i32x4_t*)(d.codes + prow * d.cbytes + ch / 2 + h * 16) = c;
+    }
+    if (live) d.scales[prow * d.swords + ch / 64] = word;
+}
+
+template <int ROWS, int COLS, int PITCH, int NT>
+__device__ __forceinline__ void store_pad_tile_a4(const IgemmArgs& __restrict__ a, const char* bt, const half_t* ht, int fy, int fy2,
+                                                  const A4Dst& d, const A4Dst& d2, int mt, int nt, int tid) {
+    constexpr int CB = COLS / 64, CH = COLS / 8;
+    static_assert(COLS % 64 == 0 && ROWS % 64 == 0 && ROWS * CB <= NT && (PITCH / 8) % 2 == 1, "one (row, block) per thread, whole waves");
+    // (a.y2 is NULL when the copy is MXFP4 -- d2.codes says that it exists -- so store_pad_tile below writes the pooled y alone)
+    if (a.dst_mode == MCAMD_DST_POOL) {            // the destination in another format: store_pad_tile's pooled y, or the copy y2
+        if (fy != MCAMD_FMT_A4) {
+            store_pad_tile<ROWS, COLS, PITCH, NT>(a, bt, ht, fy == MCAMD_FMT_F8, false, mt, nt, tid);
+        } else if (a.y2 != nullptr) {
+            for (int slot = tid; slot < ROWS * CH; slot += NT) {
+                const int row = slot / CH, ch = slot - row * CH;
+                const int m = mt * ROWS + row, n0 = nt * COLS + ch * 8;
+                if (m < a.M && n0 < a.N) {
+                    int b, h, w;
+                    tile_pixel(a, true, m, b, h, w);
+                    put8(a.y2, fy2 == MCAMD_FMT_F8, pad_off(b, h, w, a.H, a.W, a.y2_ld) + a.y2_choff + n0, bt, ht, row * PITCH + ch * 8);
+                }
+            }
+        }
+    }
+    if (tid >= ROWS * CB) return;                  // (whole waves)
+    const int row = tid % ROWS, blk = tid / ROWS;
+    const int m = mt * ROWS + row, n0 = nt * COLS + blk * 64;
+    const bool live = m < a.M && n0 < a.N;         // (N % 64 == 0: whole blocks; POOL / REORG: M % 4 == 0, whole windows)
+    const char* p = bt + row * PITCH + blk * 64;
+    int b, h, w;
+    tile_pixel(a, a.dst_mode != 0, m < a.M ? m : a.M - 1, b, h, w);
+    if (a.dst_mode == MCAMD_DST_PLAIN) {
+        a4_put64(d, pad_off(b, h, w, a.H, a.W, 1), d.choff + n0, p, live);
+        return;
+    }
+    const long long prow = pad_off(b, h >> 1, w >> 1, a.H >> 1, a.W >> 1, 1);     // the pooled pixel's buffer row
+    if (a.dst_mode == MCAMD_DST_REORG) {           // out channel = (dy * 2 + dx) * N + n
+        a4_put64(d, prow, d.choff + (m & 3) * a.N + n0, p, live);
+        return;
+    }
+    if (fy2 == MCAMD_FMT_A4 && d2.codes != nullptr) a4_put64(d2, pad_off(b, h, w, a.H, a.W, 1), d2.choff + n0, p, live);
+    if (fy != MCAMD_FMT_A4) return;                // (uniform over the launch)
+    const int q = row & 3, hg = q & 1;             // lane q of the window's quad; the group it quantises
+    unsigned g[8];
+#pragma unroll
+    for (int grp = 0; grp < 2; ++grp) {            // every lane pools both groups (the exchange needs all four rows) and keeps its own
+        unsigned v[8];
+        a4_read32(p, grp, v);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            unsigned k = e4m3_key(v[i]);
+            k = e4m3_max4(k, (unsigned)__builtin_amdgcn_update_dpp(0, (int)k, 0xb1, 0xf, 0xf, true));   // quad_perm [1, 0, 3, 2]
+            k = e4m3_max4(k, (unsigned)__builtin_amdgcn_update_dpp(0, (int)k, 0x4e, 0xf, 0xf, true));   // quad_perm [2, 3, 0, 1]
+            g[i] = grp == 0 || hg ? e4m3_unkey(k) : g[i];
+        }
+    }
+    i32x4_t c;
+    const int sb = a4_quant32(g, c);
+    const int sb1 = __builtin_amdgcn_update_dpp(0, sb, 0xb1, 0xf, 0xf, true);     // lane 0: group 1's byte from lane 1
+    if (live && q < 2) {
+        const int ch = d.choff + n0;
+        *(i32x4_t*)(d.codes + prow * d.cbytes + ch / 2 + hg * 16) = c;
+        if (q == 0) d.scales[prow * d.swords + ch / 64] = sb | sb1 << 8;
     }
 }
 

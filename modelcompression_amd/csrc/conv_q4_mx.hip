@@ -44,12 +44,7 @@
 // ---------------------------------------------------------------------------------------
 // cast pass: e4m3 bytes [rows][ld], channels [choff, choff + cin) -> codes + scale words
 // ---------------------------------------------------------------------------------------
-// the value of an e4m3 byte's low seven bits; the NaN pattern 0x7f continues the format to 480 (mcamd.h)
-__device__ __forceinline__ float a4_mag(unsigned b) {
-    const unsigned e = (b >> 3) & 15u, m = b & 7u;
-    return e ? ldexpf((float)(8u + m), (int)e - 10) : ldexpf((float)m, -9);
-}
-
+// (a4_mag, the value of an e4m3 byte's low seven bits: w4_quant.h)
 // One thread per 16 channels: one 16-byte load, the group maximum from the pair's other lane (DPP quad_perm [1, 0, 3, 2]; e4m3
 // is monotone in its low seven bits, so the maximum is taken on them), 8 code bytes stored; lane 0 of a quad -- 64 channels --
 // takes group 1's scale byte from lane 2 (quad_perm [2, 2, 2, 2]) and stores the block's scale word.  cin % 64 == 0: a quad
@@ -249,6 +244,58 @@ static int conv_q4_mx_launch_t(IgemmArgs& a, const Q8Choice& c, const char* wsca
                        xscales, y_f8, y2_f8);
     MCAMD_LAUNCH_CHECK("conv_fwd_q4_mx");
     return MCAMD_OK;
+}
+
+// The same kernel with MXFP4 destinations (mcamd_conv_fwd_q4_mx_a4): conv_q4_mx_kernel's K loop, then the
+// epilogue whose store quantises the byte tile on its way out (conv_epi.h store_pad_tile_a4) -- its consumer reads the codes
+// and scale words with no cast pass.  fy / fy2: MCAMD_FMT_* per destination.  A kernel of its own, so that every instance
+// above stays what it was.
+template <class T>
+__global__ __launch_bounds__(T::NT) void conv_q4_mx_a4_kernel(IgemmArgs a, const char* __restrict__ wscales, int npad,
+                                                              const int* __restrict__ wexp, const char* __restrict__ xscales, int fy,
+                                                              int fy2, A4Dst d, A4Dst d2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const Q8Wave w = q8_wave<T>();
+    int nt, mt;
+    if (!xcd_tile(a.num_ntiles, a.num_mtiles, nt, mt)) return;
+    Q4RowsA<T> aop;
+    aop.setup(a, wscales, npad, nt, w.tid);
+    Q4PixelsB<T> bop;
+    bop.setup(a, xscales, mt, w.tid);
+    f32x16_t acc[T::TM][T::TN];
+    q8_zero(acc);
+    const Q4Lane<T> ln(w);
+    q4_ring<T>(a, aop, bop, a.ktot / T::BK, smem, w, [&](const char* sa, const char* sb) { q4mx_step<T>(acc, sa, sb, ln); });
+    q8_mma_drain<true>();
+    __syncthreads();                               // every wave is done with the stage buffers
+    q8_infer_epilogue_a4<T>(a, acc, wexp, fy, fy2, d, d2, smem, mt, nt, w);
+}
+
+template <class T>
+static int conv_q4_mx_a4_launch_t(IgemmArgs& a, const Q8Choice& c, const char* wscales, int npad, const int* wexp, const char* xscales,
+                                  int fy, int fy2, const A4Dst& d, const A4Dst& d2, hipStream_t st) {
+    constexpr int RING = T::RING_STAGES * (Q4RowsA<T>::BYTES + T::B4_BYTES);
+    auto kern = conv_q4_mx_a4_kernel<T>;
+    MCAMD_LDS_OPT_IN(kern, q8_infer_lds_max(RING, T::TILE_BYTES));
+    a.num_mtiles = c.mtiles;
+    a.num_ntiles = c.ntiles;
+    // (an MXFP4 destination is quantised from the byte tile: sized as an e4m3 one; the kernel sees an MXFP4 copy in d2 alone)
+    const int lds = q8_infer_lds(RING, T::TILE_BYTES, a, fy != MCAMD_FMT_F16, fy2 != MCAMD_FMT_F16);
+    if (fy2 == MCAMD_FMT_A4) a.y2 = nullptr;
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(T::NT), lds, st, a, wscales, npad, wexp, xscales, fy, fy2, d, d2);
+    MCAMD_LAUNCH_CHECK("conv_fwd_q4_mx_a4");
+    return MCAMD_OK;
+}
+
+int mcamd_conv_q4_mx_a4_launch(IgemmArgs& a, const void* xscales, const void* wscales, const void* wexp, int fy, int fy2,
+                               const A4Dst& d, const A4Dst& d2, hipStream_t st) {
+    const int npad = round_up_int(a.N, 256);
+    const Q8Choice c = mcamd_q4_mx_choice(a.M, a.N);
+    const char *ws = (const char*)wscales, *xs = (const char*)xscales;
+    const int* we = (const int*)wexp;
+    if (c.bmw == 256) return conv_q4_mx_a4_launch_t<Q4Tile<256, 128, 64, 64>>(a, c, ws, npad, we, xs, fy, fy2, d, d2, st);
+    if (c.bmw == 128) return conv_q4_mx_a4_launch_t<Q4Tile<128, 128, 64, 64>>(a, c, ws, npad, we, xs, fy, fy2, d, d2, st);
+    return conv_q4_mx_a4_launch_t<Q4Tile<64, 128, 32, 64>>(a, c, ws, npad, we, xs, fy, fy2, d, d2, st);
 }
 
 // mcamd_q8_w4_mx_choice's three tiles (256 / 128 / 64 filters x 128 pixels) on a four-stage ring.  Every instance compiles

@@ -332,6 +332,26 @@ __device__ __forceinline__ void q8_infer_epilogue(const IgemmArgs& __restrict__ 
     if (sat && a.overflow) atomicOr(a.overflow, 1);
 }
 
+// ... with destinations that can be MXFP4 (conv_q4_mx.hip's and conv_q8_w4_mx.hip's *_a4 kernels): the same
+// tile expression -- the bytes an MXFP4 destination is quantised from ARE the bytes q8_infer_epilogue would store, so the
+// result equals that store followed by mcamd_cast_a4_mx byte for byte -- behind store_pad_tile_a4.  An MXFP4 destination
+// needs the byte tile as an e4m3 one does.
+template <class T>
+__device__ __forceinline__ void q8_infer_epilogue_a4(const IgemmArgs& __restrict__ a, const f32x16_t (&acc)[T::TM][T::TN],
+                                                     const int* __restrict__ wexp, int fy, int fy2, const A4Dst& d, const A4Dst& d2,
+                                                     char* smem, int mt, int nt, const Q8Wave& w) {
+    // (one destination at least is MXFP4: the byte tile always; a.y2 is NULL when the copy is MXFP4, d2.codes says it exists)
+    const bool need_b = true, need_h = fy == MCAMD_FMT_F16 || (a.y2 != nullptr && fy2 == MCAMD_FMT_F16);
+    char* bt = smem;
+    half_t* ht = (half_t*)(smem + T::TILE_BYTES);
+    const float* scale = a.scale;
+    const bool sat = write_ch_tile<T::BMW, T::PB, T::WM, T::WN>(a, acc, [scale, wexp](int n) { return ldexpf(scale ? scale[n] : 1.f, -(wexp[n] + 1)); },
+                                                                need_b, need_h, bt, ht, nt, w.wm, w.wn, w.lane);
+    __syncthreads();
+    store_pad_tile_a4<T::BNP, T::BMW, T::PB, T::NT>(a, bt, ht, fy, fy2, d, d2, mt, nt, w.tid);
+    if (sat && a.overflow) atomicOr(a.overflow, 1);
+}
+
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------

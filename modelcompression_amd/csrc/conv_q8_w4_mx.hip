@@ -136,6 +136,55 @@ int mcamd_conv_q8_w4_mx_launch(IgemmArgs& a, const void* scales, const void* wex
     return conv_q8_w4_mx_launch_t<Q8Tile<64, 128, 32, 64, 3>>(a, c, sc, npad, we, y_f8, y2_f8, st);
 }
 
+// The same kernel with MXFP4 destinations (mcamd_conv_fwd_q8_w4_mx_a4): the producer in front of an fp4 x fp4
+// block where the engine's e4m3 activations end (Darknet.fp4_skip).  conv_q8_w4_mx_kernel's K loop, then the epilogue whose
+// store quantises the byte tile on its way out (conv_epi.h store_pad_tile_a4); fy / fy2: MCAMD_FMT_* per destination.
+template <class T>
+__global__ __launch_bounds__(T::NT) void conv_q8_w4_mx_a4_kernel(IgemmArgs a, const char* __restrict__ scales, int npad,
+                                                                 const int* __restrict__ wexp, int fy, int fy2, A4Dst d, A4Dst d2) {
+    using A = Q8W4MxRowsA<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const Q8Wave w = q8_wave<T>();
+    int nt, mt;
+    if (!xcd_tile(a.num_ntiles, a.num_mtiles, nt, mt)) return;
+    A aop;
+    aop.setup(a, scales, npad, nt, w.tid);
+    f32x16_t acc[T::TM][T::TN];
+    q8_zero(acc);
+    const W4MxLane<T> ln(w);
+    q8_ring<T>(a, aop, Q8SeqDense{a.ktot / T::BK}, mt, smem, w, [&](const char* sa, const char* sb) { w4mx_step<T>(acc, sa, sb, ln); });
+    q8_mma_drain<true>();
+    __syncthreads();                               // every wave is done with the stage buffers
+    q8_infer_epilogue_a4<T>(a, acc, wexp, fy, fy2, d, d2, smem, mt, nt, w);
+}
+
+template <class T>
+static int conv_q8_w4_mx_a4_launch_t(IgemmArgs& a, const Q8Choice& c, const char* scales, int npad, const int* wexp, int fy, int fy2,
+                                     const A4Dst& d, const A4Dst& d2, hipStream_t st) {
+    constexpr int RING = Q8W4MxRowsA<T>::RING;
+    auto kern = conv_q8_w4_mx_a4_kernel<T>;
+    MCAMD_LDS_OPT_IN(kern, q8_infer_lds_max(RING, T::TILE_BYTES));
+    a.num_mtiles = c.mtiles;
+    a.num_ntiles = c.ntiles;
+    // (an MXFP4 destination is quantised from the byte tile: sized as an e4m3 one; the kernel sees an MXFP4 copy in d2 alone)
+    const int lds = q8_infer_lds(RING, T::TILE_BYTES, a, fy != MCAMD_FMT_F16, fy2 != MCAMD_FMT_F16);
+    if (fy2 == MCAMD_FMT_A4) a.y2 = nullptr;
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(T::NT), lds, st, a, scales, npad, wexp, fy, fy2, d, d2);
+    MCAMD_LAUNCH_CHECK("conv_fwd_q8_w4_mx_a4");
+    return MCAMD_OK;
+}
+
+int mcamd_conv_q8_w4_mx_a4_launch(IgemmArgs& a, const void* scales, const void* wexp, int fy, int fy2, const A4Dst& d, const A4Dst& d2,
+                                  hipStream_t st) {
+    const int npad = round_up_int(a.N, 256);
+    const Q8Choice c = mcamd_q8_w4_mx_choice(a.M, a.N);
+    const char* sc = (const char*)scales;
+    const int* we = (const int*)wexp;
+    if (c.bmw == 256) return conv_q8_w4_mx_a4_launch_t<Q8Tile<256, 128, 64, 64, 3>>(a, c, sc, npad, we, fy, fy2, d, d2, st);
+    if (c.bmw == 128) return conv_q8_w4_mx_a4_launch_t<Q8Tile<128, 128, 64, 64, 3>>(a, c, sc, npad, we, fy, fy2, d, d2, st);
+    return conv_q8_w4_mx_a4_launch_t<Q8Tile<64, 128, 32, 64, 3>>(a, c, sc, npad, we, fy, fy2, d, d2, st);
+}
+
 // ---------------------------------------------------------------------------------------
 // split-K partial kernel for low-batch inference (Darknet.precision = "fp8-w4-mx-splitk")
 // ---------------------------------------------------------------------------------------

@@ -230,6 +230,20 @@ int mcamd_cast_a4_mx_launch(const void* x8, long long rows, int ld, int choff, i
 Q8Choice mcamd_q4_mx_choice(long long M, int N);
 int mcamd_conv_q4_mx_launch(IgemmArgs& a, const void* xscales, const void* wscales, const void* wexp, int y_f8, int y2_f8,
                             hipStream_t st);
+// ... and both forwards with MXFP4 DESTINATIONS (conv_epi.h store_pad_tile_a4): fy / fy2 = the format of y / y2,
+// d / d2 = mcamd_a4_dst in the store's units for a destination of format MCAMD_FMT_A4 (a.y / a.y2 are then not written; a copy
+// exists when a.y2 != NULL on entry -- the launch hands the kernel a.y2 = NULL for an MXFP4 copy, which d2.codes announces)
+enum { MCAMD_FMT_F16 = 0, MCAMD_FMT_F8 = 1, MCAMD_FMT_A4 = 2 };
+struct A4Dst {
+    char* codes;           // [rows][cbytes]
+    int* scales;           // [rows][swords]
+    int cbytes, swords;    // channels / 2, channels / 64
+    int choff;
+};
+int mcamd_conv_q4_mx_a4_launch(IgemmArgs& a, const void* xscales, const void* wscales, const void* wexp, int fy, int fy2,
+                               const A4Dst& d, const A4Dst& d2, hipStream_t st);
+int mcamd_conv_q8_w4_mx_a4_launch(IgemmArgs& a, const void* scales, const void* wexp, int fy, int fy2, const A4Dst& d, const A4Dst& d2,
+                                  hipStream_t st);
 
 WgradPlan mcamd_wgrad_plan(long long M, int cout, int cin_tap, int ntaps);
 int mcamd_wgrad_launch(WgradArgs& a, const WgradPlan& p, hipStream_t st);

@@ -75,6 +75,9 @@ _LAYER_FIELDS = dict(
     # the fp32 raw output + statistics that stand in for the fp16 ones, and the values the weight bytes stand for
     geom_q8=None, q8_y=False, q8_y2=False, xq=None, _xq=None, _xq_key=None, wq=None, wqs=None, widx8=None, wexp=None,
     w4c=None, w4g=None, wexp4=None,
+    # "fp4-mx" with Darknet.fp4_fused: the block reads its input tensor's MXFP4 pair (no cast pass); its epilogue
+    # writes the pair of its output tensor / of the full-resolution copy
+    a4_in=False, a4_y=False, a4_y2=False,
     y_f16=None, stats_f16=None, y_f32=None, stats_q8=None, w_q=None)
 
 
@@ -542,6 +545,11 @@ class _Q8W4Mx(_Q8):
         values = ops.fakequant_q8_w4(g, *ops_)      # (fp32 OIHW, one layer at a time, freed behind the pack)
         ops.pack_q8_w4_mx(g, values, None, *ops_)
 
+    def operands(self, eng, lay, xin):
+        # (Darknet.fp4_fused: y_a4 / y2_a4 of a block whose epilogue writes MXFP4 -- the launch is then this form's `fwd` + "_a4")
+        args, kw = _Q8.operands(self, eng, lay, xin)
+        return args, dict(kw, **eng._a4_dsts(lay))
+
 
 class _Q8W4MxSplitK(_Q8W4Mx):
     """An fp4-operand block of few pixels: its K loop cut into slices over the whole chip ("fp8-w4-mx-splitk",
@@ -565,18 +573,23 @@ class _Q4Mx(_Q8W4Mx):
     with four registers and one e8m0 scale per lane on both sides.  The weight operands and their packing are _Q8W4Mx's; the
     block's byte input -- the engine's e4m3 buffer, or the private copy behind the fp16 -> fp8 edge cast -- goes through the cast
     pass mcamd_cast_a4_mx into the engine's one scratch pair of codes and scale words, sized for the largest such block (the
-    blocks run one after another on the launch stream), and the launch reads that pair."""
+    blocks run one after another on the launch stream), and the launch reads that pair.  Under Darknet.fp4_fused
+    a block whose producers' epilogues wrote its input tensor's own MXFP4 pair (`a4_in`, Engine._choose_a4) reads that pair:
+    no cast pass."""
     fwd = "conv_fwd_q4_mx"
 
     def alloc(self, eng, lays):
         _Q8W4Mx.alloc(self, eng, lays)
-        need = [max(n) for n in zip(*(ops.a4_mx_elems(eng.B * (lay.tin.H + 2) * (lay.tin.W + 2), lay.cin) for lay in lays))]
+        lays = [lay for lay in lays if not lay.a4_in]        # (the blocks that still cast into the scratch pair)
+        need = [max(n) for n in zip(*(ops.a4_mx_elems(eng.B * (lay.tin.H + 2) * (lay.tin.W + 2), lay.cin) for lay in lays))] or [0, 0]
         if eng._a4_codes is None or eng._a4_codes.numel() < need[0] or eng._a4_scales.numel() < need[1]:
             eng._a4_codes = torch.zeros(need[0], dtype=torch.uint8, device=eng.device)
             eng._a4_scales = torch.zeros(need[1], dtype=torch.uint8, device=eng.device)
 
     def operands(self, eng, lay, xin):
         (g, x8, *w), kw = _Q8W4Mx.operands(self, eng, lay, xin)
+        if lay.a4_in:
+            return (g, *eng.a4bufs[lay.tin.buf], *w), kw
         eng._timed('cast4', lay, ops.cast_a4_mx, x8, eng.B * (lay.tin.H + 2) * (lay.tin.W + 2), g.x_ld, g.x_choff, lay.cin,
                    eng._a4_codes, eng._a4_scales)
         return (g, eng._a4_codes, eng._a4_scales, *w), kw
@@ -715,6 +728,10 @@ class Engine:
         self.q4_mx = precision == "fp4-mx"
         self.fp4_layers = []
         self._a4_codes = self._a4_scales = None
+        # ... with Darknet.fp4_fused: buffer id -> the (codes, scale bytes) of an activation tensor its producers'
+        # epilogues write as MXFP4 (_choose_a4), and the conv numbers of the fp4 x fp4 blocks that read one -- no cast pass
+        self.a4bufs, self._a4_key = {}, {}
+        self.fp4_fused_layers = []
         # "fp8-w4-mx-splitk": the subset of fp8_w4_mx_layers -- unpadded geometries only -- the split-K policy gives two slices
         # or more and that run mcamd_conv_fwd_q8_w4_mx_splitk (form "q8_w4_mx_splitk"; they share `_splitk_ws` below)
         self.q8_w4_mx_splitk = precision == "fp8-w4-mx-splitk"
@@ -781,7 +798,7 @@ class Engine:
         self.lowrank_stale = []
         # what every block's form was last chosen for (pack): mask keys, block-sparse choice, sparse mode, sparse_max_kept,
         # split-K flag
-        self._form_key = (None, None, None, None, None, None, None)
+        self._form_key = (None, None, None, None, None, None, None, None)
         self._training, self._fold_key = None, None
         self.fold_dead = os.environ.get("MCAMD_FOLD_DEAD", "1") == "1"
         # "mixed": the two correction products of the split-operand forward from e4m3 copies on the block-scaled fp8 MFMAs
@@ -1234,14 +1251,14 @@ class Engine:
         return tuple(sig)
 
     def pack(self, force=False, training=True, sparse=None, splitk=False, max_kept=None, wgrad_max_kept=None, lowrank=None,
-             fp4_skip=None):
+             fp4_skip=None, fp4_fused=False):
         """fp32 master * mask -> fp16 kernel layouts (replaces layers.py:59's per-forward multiply).
         `sparse`, `splitk`, `max_kept`: the inference options forward() validated (Darknet.sparse / splitk /
         sparse_max_kept; off in training mode); every block's form is chosen again when they or the masks change.
         `wgrad_max_kept` (sparse = "block-train" only; None: off): Darknet.sparse_train = "block-wgrad".
         `lowrank` (None: off): (Darknet.lowrank_max_cost, Darknet.lowrank_min_tiles, ((layer index, rank) of every block
         with fresh factors)).
-        `fp4_skip` ("fp4-mx" only; None elsewhere): Darknet.fp4_skip as a sorted tuple of conv numbers."""
+        `fp4_skip` ("fp4-mx" only; None elsewhere): Darknet.fp4_skip as a sorted tuple of conv numbers; `fp4_fused`: Darknet.fp4_fused."""
         if any(lay.fold is not None for lay in self.layers) and training != self._training:
             force = True          # the folded constants differ between batch and running statistics
         self._training = training
@@ -1252,7 +1269,8 @@ class Engine:
         # engine after grad_scale was halved) must not keep the static default exponents
         serial = self.model._weights_serial
         dirty = self.model._weights_dirty or serial != self._weights_seen
-        if not force and sig == self._packed_sig and (sparse, max_kept, splitk, lowrank, fp4_skip) == self._form_key[2:] and not dirty:
+        if (not force and sig == self._packed_sig and (sparse, max_kept, splitk, lowrank, fp4_skip, fp4_fused) == self._form_key[2:]
+                and not dirty):
             return
         if dirty or (self.f8 and self.serial % 1000 == 999):      # (and every 1 000th forward: slow drift)
             self._refresh_f8_wexp()
@@ -1270,7 +1288,7 @@ class Engine:
             exempt, self.bsparse_train_kept = self._bst_policy[1:]
         elif self.q8_bsparse and max_kept is not None:
             exempt, self.fp8_block_kept = _FORMS["q8_bsparse"].policy(self, max_kept)
-        key = (mkeys, exempt, sparse, max_kept, splitk, lowrank, fp4_skip)
+        key = (mkeys, exempt, sparse, max_kept, splitk, lowrank, fp4_skip, fp4_fused)
         if key != self._form_key:          # masks are static during retraining: planned once
             self._choose_forms(key)
         # (the list weight gradient follows the forms: chosen again when they, the masks -- part of the form key -- or its
@@ -1463,7 +1481,7 @@ class Engine:
              and does when the library's policy gives the block's eval-mode launch two slices or more
              (mcamd_conv_fwd_splitk_info).
         Every other block stays dense.  The `*_layers` lists are the conv numbers (conv1 = the first block) per form."""
-        mkeys, exempt, sparse, max_kept, splitk, lowrank, fp4_skip = key
+        mkeys, exempt, sparse, max_kept, splitk, lowrank, fp4_skip, fp4_fused = key
         self._plan_epoch += 1             # recorded plans name each block's launch and hold its operands' addresses
         if (mkeys, exempt) != self._form_key[:2]:
             self._bs_exempt = exempt
@@ -1476,6 +1494,7 @@ class Engine:
         for lay in self.layers:
             lay.form, lay.sk_slices = "dense", 1
             lay.q8_y, lay.q8_y2, lay.xq, lay.geom_q8 = False, False, None, lay.geom_act
+            lay.a4_in = lay.a4_y = lay.a4_y2 = False
             if lay.y_f16 is not None:        # (an fp8-qat training block: back to its fp16 raw output and statistics)
                 lay.y, lay.stats = lay.y_f16, lay.stats_f16
         if sparse != "block":
@@ -1509,6 +1528,7 @@ class Engine:
                 for lay in self.layers:
                     if lay.form == "q8_w4_mx" and lay.li + 1 not in (fp4_skip or ()) and ops.conv_fwd_q4_mx_ok(lay.geom_q8):
                         lay.form = "q4_mx"
+            self._choose_a4(self.q4_mx and fp4_fused)
         elif sparse == "2:4":
             for lay in self._conforming([lay for lay in self.layers
                                          if self._eligible(lay) and lay.conv.mask_flag and lay.cin % 4 == 0
@@ -1551,6 +1571,7 @@ class Engine:
                                "q8_bsparse")
         self.fp8_w4_mx_layers = nums("q8_w4_mx", "q8_w4_mx_splitk", "q4_mx")
         self.fp4_layers = nums("q4_mx")
+        self.fp4_fused_layers = [lay.li + 1 for lay in self.layers if lay.a4_in]
         self.fp8_w4_mx_splitk_layers = nums("q8_w4_mx_splitk")
         self.fp8_block_layers = nums("q8_bsparse")
         if self._training:                   # (what the last training-mode choice was; an eval pass in between keeps it)
@@ -1661,6 +1682,62 @@ class Engine:
             if lay.q8_on:
                 lay.q8_y = lay.out_t.buf in self.qbufs
                 lay.q8_y2 = lay.out2_t is not None and lay.out2_t.buf in self.qbufs
+
+    def _choose_a4(self, fused):
+        """Darknet.fp4_fused, behind the forms: which activation tensors their producers' conv epilogues write as
+        MXFP4 codes and scale words (mcamd_conv_fwd_q4_mx_a4 / mcamd_conv_fwd_q8_w4_mx_a4), so that the fp4 x fp4 blocks behind them
+        read them with no cast pass.  A tensor is when it is held as e4m3 bytes today (_choose_q8: every reader and writer an fp8
+        block), EVERY reader is a "q4_mx" block that reads exactly the tensor's channels (x_choff 0, leading dimension cin -- a
+        reader of a slice, or an fp4_skip reader beside an fp4 one, keeps the tensor in e4m3 and the cast pass), every writer is
+        an unsplit "q4_mx" / "q8_w4_mx" block and the entries' rules hold (cout, offsets and channel count multiples of 64).  Its
+        e4m3 buffer is then no longer written at all.  The pair of a tensor is sized by mcamd_a4_mx_elems over its padded rows,
+        made again when B or the geometry changes and initialised ONCE to the halo's contents -- zero codes, scale words
+        0x00007f7f -- which no epilogue ever writes; nothing is allocated inside a forward."""
+        writers, readers = {}, {}
+        for lay in self.layers:
+            readers.setdefault(lay.tin.buf, []).append(lay)
+            if not lay.is_last:
+                for t in (lay.out_t, lay.out2_t):
+                    if t is not None:
+                        writers.setdefault(t.buf, []).append((lay, t))
+        live = set()
+        for buf, ws in writers.items() if fused else ():
+            rs = readers.get(buf, [])
+            ld = self._qld.get(buf)
+            if buf not in self.qbufs or not rs or ld % 64:
+                continue
+            if not all(r.form == "q4_mx" and r.tin.choff == 0 and r.cin == ld for r in rs):
+                continue
+            span = lambda w, t: w.cout * (4 if (w.mode == L.DST_REORG and t is w.out_t) else 1)
+            if not all(w.form in ("q4_mx", "q8_w4_mx") and w.cout % 64 == 0 and t.choff % 64 == 0 and t.choff + span(w, t) <= ld
+                       for w, t in ws):
+                continue
+            t = rs[0].tin
+            key = (self.B, t.H, t.W, ld)
+            if self._a4_key.get(buf) != key:
+                nc, ns = ops.a4_mx_elems(self.B * (t.H + 2) * (t.W + 2), ld)
+                halo = torch.tensor([127, 127, 0, 0], dtype=torch.uint8, device=self.device)
+                self.a4bufs[buf] = (torch.zeros(nc, dtype=torch.uint8, device=self.device), halo.repeat(ns // 4))
+                self._a4_key[buf] = key
+            live.add(buf)
+            for r in rs:
+                r.a4_in = True
+            for w, t in ws:
+                if t is w.out_t:
+                    w.a4_y = True
+                else:
+                    w.a4_y2 = True
+        for b in [b for b in self.a4bufs if b not in live]:
+            del self.a4bufs[b], self._a4_key[b]
+
+    def _a4_dsts(self, lay):
+        """The y_a4 / y2_a4 keywords of a block whose epilogue writes MXFP4 (_choose_a4): (codes, scale bytes, channels, choff)
+        of its output tensor's pair; empty for every other block."""
+        kw = {}
+        for flag, name, t in ((lay.a4_y, "y_a4", lay.out_t), (lay.a4_y2, "y2_a4", lay.out2_t)):
+            if flag:
+                kw[name] = (*self.a4bufs[t.buf], self._qld[t.buf], t.choff)
+        return kw
 
     def _q8_ld(self, lay):
         """Bytes per pixel a byte buffer needs for this block to read its input from it: the fp16 buffer's leading dimension,
@@ -2089,8 +2166,12 @@ class Engine:
             except (TypeError, ValueError):
                 raise McamdError("fp4_skip must be a collection of conv numbers (conv1 = the first block), got %r"
                                  % (getattr(self.model, "fp4_skip", ()),))
+        fp4_fused = bool(getattr(self.model, "fp4_fused", False)) and not training
+        if fp4_fused and not self.q4_mx:
+            raise McamdError("fp4_fused=True runs under model.precision = 'fp4-mx' only (its producers' epilogues write the MXFP4 "
+                             "activations of that engine), not precision=%r" % (self.precision,))
         self.pack(force=bool(training), training=training, sparse=mode, splitk=splitk, max_kept=max_kept, wgrad_max_kept=wgrad_max,
-                  lowrank=lowrank, fp4_skip=fp4_skip)
+                  lowrank=lowrank, fp4_skip=fp4_skip, fp4_fused=fp4_fused)
         self.serial += 1
         tin = self.layers[0].tin
         xs = x.detach().contiguous().float()
@@ -2216,7 +2297,9 @@ class Engine:
                 (y2, y2_ld, y2_choff), _ = self._dst2(lay.out2_t, lay.q8_y2)
                 form = _FORMS[lay.form]
                 args, kw = form.operands(self, lay, xin)
-                self._timed('fwd', lay, getattr(ops, form.fwd), *args, y, y_ld, t.choff, lay.scale, lay.shift, lay.slope,
+                # (a block whose epilogue writes MXFP4, Darknet.fp4_fused: the form's launch with MXFP4 destinations)
+                fwd = form.fwd + "_a4" if ("y_a4" in kw or "y2_a4" in kw) else form.fwd
+                self._timed('fwd', lay, getattr(ops, fwd), *args, y, y_ld, t.choff, lay.scale, lay.shift, lay.slope,
                             dst_mode=lay.mode, y2=y2, y2_ld=y2_ld, y2_choff=y2_choff, **kw)
                 continue
             if training and self._qat_train(lay):

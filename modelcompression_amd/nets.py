@@ -340,6 +340,11 @@ class Darknet(nn.Module):
         # "fp4-mx": conv numbers (conv1 = the first block) that keep e4m3 activations -- form "q8_w4_mx" -- because early layers are
         # where 4-bit activations cost most; changing it re-chooses the forms at the next forward
         self.fp4_skip = ()
+        # "fp4-mx": True lets every fp4 x fp4 block whose producer is an fp4-operand block read MXFP4 codes and scale words that
+        # the producer's conv epilogue wrote -- no e4m3 tensor and no cast pass in between (engine.Engine.fp4_fused_layers,
+        # csrc/conv_epi.h store_pad_tile_a4); the logits are bit-equal to False's.  Any other eval precision
+        # raises with it set.  MCAMD_FP4_FUSED=1 sets the default.
+        self.fp4_fused = os.environ.get("MCAMD_FP4_FUSED", "0") == "1"
         # 2:4 structured-sparse inference (an addition beyond the reference): "2:4" runs every eligible block whose mask
         # keeps at most 2 of every 4 consecutive input channels (pruning.weightPruning.methods.nm_prune) on the sparse MFMA
         # (engine.Engine.sparse_layers).  "block" runs every eligible masked block on the block-sparse kernel

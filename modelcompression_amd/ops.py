@@ -1794,6 +1794,58 @@ def conv_fwd_q4_mx(g, xcodes, xscales, codes, scales, wexp, y, y_ld, y_choff=0, 
                                        int(bool(y_f8)), int(bool(y2_f8)), stream_ptr()), "mcamd_conv_fwd_q4_mx")
 
 
+# ... written by the producer's epilogue: both fp4-operand forwards with MXFP4 destinations
+def _a4_dst(what, dst, rows, span):
+    """(codes, scale bytes, channels, choff) of one MXFP4 destination over `rows` padded rows -> L.A4Dst, or None; the tensors
+    must hold a4_mx_elems(rows, channels) and the written slice [choff, choff + span) must lie inside `channels`."""
+    if dst is None:
+        return None
+    codes, scales, channels, choff = dst
+    _need_cuda(codes, scales)
+    if channels <= 0 or channels % 64 or choff < 0 or choff + span > channels:
+        raise L.McamdError("%s: MXFP4 destination slice [%d, %d) does not fit %d channels" % (what, choff, choff + span, channels))
+    nc, ns = a4_mx_elems(rows, channels)
+    if codes.numel() * codes.element_size() < nc or scales.numel() * scales.element_size() < ns:
+        raise L.McamdError("%s: MXFP4 destination too small for %d rows of %d channels" % (what, rows, channels))
+    return L.A4Dst(ptr(codes), ptr(scales), int(channels), int(choff))
+
+
+def _conv_fwd_a4(entry, g, operands, y, y_ld, y_choff, scale, shift, slope, dst_mode, y2, y2_ld, y2_choff, y_f8, y2_f8, overflow,
+                 y_a4, y2_a4):
+    Ho, Wo = (g.H, g.W) if dst_mode == L.DST_PLAIN else (g.H // 2, g.W // 2)
+    d = _a4_dst(entry, y_a4, g.B * (Ho + 2) * (Wo + 2), g.cout * (4 if dst_mode == L.DST_REORG else 1))
+    d2 = _a4_dst(entry, y2_a4, g.B * (g.H + 2) * (g.W + 2), g.cout)
+    if d is not None:            # (an MXFP4 destination's epilogue slice: its codes, channel count and offset)
+        y, y_ld, y_choff = y_a4[0], y_a4[2], y_a4[3]
+    if d2 is not None:
+        y2, y2_ld, y2_choff = y2_a4[0], y2_a4[2], y2_a4[3]
+    e = _epi(L.EPI_PAD_F16, y, y_ld, y_choff, scale=scale, shift=shift, slope=slope, dst_mode=dst_mode, y2=y2, y2_ld=y2_ld,
+             y2_choff=y2_choff, overflow=overflow)
+    check(getattr(L.lib(), entry)(C.byref(g), *(ptr(t) for t in operands), C.byref(e), int(bool(y_f8)), int(bool(y2_f8)),
+                                  C.byref(d) if d is not None else None, C.byref(d2) if d2 is not None else None, stream_ptr()), entry)
+
+
+def conv_fwd_q4_mx_a4(g, xcodes, xscales, codes, scales, wexp, y=None, y_ld=0, y_choff=0, scale=None, shift=None, slope=1.0,
+                      dst_mode=0, y2=None, y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None, y_a4=None, y2_a4=None):
+    """conv_fwd_q4_mx whose destinations can be MXFP4 (mcamd_conv_fwd_q4_mx_a4): `y_a4` / `y2_a4` = (codes, scale bytes,
+    channels, choff) of the destination tensor's padded rows override that destination's format -- the epilogue writes
+    cast_a4_mx's codes and scale words of the e4m3 bytes it would have stored, interior pixels and [choff, choff + cout) only.
+    With both None this is conv_fwd_q4_mx."""
+    rows = g.B * (g.H + 2) * (g.W + 2)
+    nc, ns = a4_mx_elems(rows, g.cin)
+    if xcodes.numel() < nc or xscales.numel() < ns:
+        raise L.McamdError("conv_fwd_q4_mx_a4: activation codes / scales too small for %d rows of %d channels" % (rows, g.cin))
+    _conv_fwd_a4("mcamd_conv_fwd_q4_mx_a4", g, (xcodes, xscales, codes, scales, wexp), y, y_ld, y_choff, scale, shift, slope,
+                 dst_mode, y2, y2_ld, y2_choff, y_f8, y2_f8, overflow, y_a4, y2_a4)
+
+
+def conv_fwd_q8_w4_mx_a4(g, x8, codes, scales, wexp, y=None, y_ld=0, y_choff=0, scale=None, shift=None, slope=1.0, dst_mode=0,
+                         y2=None, y2_ld=0, y2_choff=0, y_f8=False, y2_f8=False, overflow=None, y_a4=None, y2_a4=None):
+    """conv_fwd_q8_w4_mx whose destinations can be MXFP4 (mcamd_conv_fwd_q8_w4_mx_a4): `y_a4` / `y2_a4` as conv_fwd_q4_mx_a4's."""
+    _conv_fwd_a4("mcamd_conv_fwd_q8_w4_mx_a4", g, (x8, codes, scales, wexp), y, y_ld, y_choff, scale, shift, slope, dst_mode, y2,
+                 y2_ld, y2_choff, y_f8, y2_f8, overflow, y_a4, y2_a4)
+
+
 def conv_fwd_q8_w4_mx_splitk_info(g, dst_mode=0, slices=0):
     """mcamd_splitk_info of a split-K fp4-operand forward of `g` (mcamd_conv_fwd_q8_w4_mx_splitk_info): host logic only, and
     conv_fwd_q8_splitk_info's answer -- one policy, one tile.  slices = 0 asks the policy; > 0 sizes a forced slice count."""

@@ -7,7 +7,8 @@ weights) on the dense model only; nothing is split there, and the 
 fields of their own (`w4_layers`; `w4`, `us_fp8`, `us_fp8_w4`) in place of the split-K ones.  --precision fp8-w4-mx: the same with
 the on leg "fp8-w4-mx" (the codes as the MFMA's fp4 operand; `w4_layers` is its fp8_w4_mx_layers).  --precision
 fp4-mx: the same with the on leg "fp4-mx" (MXFP4 activations too; the layer table times the conv launches, the
-cast pass in front of each is in the whole-forward figures only).
+cast pass in front of each is in the whole-forward figures only); with --fused its on leg sets Darknet.fp4_fused (DESIGN.md 3zk:
+the producers' epilogues write the MXFP4 activations, `plan_calls` drops by one per fused block).
 --precision fp8-w4-mx-splitk: the off leg is precision "fp8-w4-mx", the on leg "fp8-w4-mx-splitk"  on the dense
 model, with the split-K fields and per-layer table of the fp8 pair; the "fp8" / "fp8-splitk" legs and the fp16 split-K legs of
 the same model are measured in the same process beside them.
@@ -45,6 +46,7 @@ if PRECISION not in ("fp16", "fp8", "fp8-w4", "fp8-w4-mx", "fp8-w4-mx-splitk", "
     raise SystemExit("--precision must be fp16, fp8, fp8-w4, fp8-w4-mx, fp8-w4-mx-splitk or fp4-mx (got %r)" % PRECISION)
 W4 = PRECISION in ("fp8-w4", "fp8-w4-mx", "fp4-mx")
 MXSK = PRECISION == "fp8-w4-mx-splitk"
+FUSED = PRECISION == "fp4-mx" and "--fused" in sys.argv      # the on leg with Darknet.fp4_fused
 ON_LEG = PRECISION if W4 or MXSK else "fp8-splitk"     # the on leg of an fp8 model
 LEGS = ["fp8-w4-mx" if MXSK else "fp8", ON_LEG]         # [off, on] precisions of an fp8 model (main swaps in the fp8 pair)
 if not torch.cuda.is_available():
@@ -63,6 +65,7 @@ def leg(m, flag):
         m.splitk = flag
     else:
         m.precision = LEGS[flag]
+        m.fp4_fused = FUSED and bool(flag)
 
 
 def split_layers(eng):

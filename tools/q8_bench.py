@@ -10,7 +10,8 @@ blocks (`slim`: on mcamd_conv_fwd_q8_slim, `table`: with a border table) and the
 without and once with MCAMD_Q8_MFMA=1 for the two forms of the fp8 kernel.
 --w4: "fp8" against "fp8-w4" (4-bit weights), "fp8-w4-mx" (the codes as the MFMA's fp4 operand, 3zg) and "fp4-mx"
 (MXFP4 activations too, 3zj: its cast pass in a column of its own, the kernel's TFLOP/s on conv22) ("fp8-w4-mx" does
-not read MCAMD_Q8_MFMA) on the same weights, the three alternated in one process, with the
+not read MCAMD_Q8_MFMA) and a fifth leg, "fp4-mx" with Darknet.fp4_fused (3zk: the producers' epilogues write the MXFP4
+activations; reported beside the unfused leg) on the same weights, the five alternated in one process, with the
 resident weight-operand bytes of the fp8 blocks under each -- once per MCAMD_Q8_MFMA form, each form in a child process of its
 own started with that switch; the merged report goes to profiles/q8_w4_bench.json unless --json names another file.
 usage: python tools/q8_bench.py [batch] [forwards per window] [--sparse | --slim PCT | --w4] [--json PATH]"""
@@ -64,10 +65,11 @@ def main(argv):
         m.set_masks(nm_prune(m))
         modes = ("fp16", "fp16+2:4", "fp8", "fp8-2:4")
     if w4:
-        modes = ("fp8", "fp8-w4", "fp8-w4-mx", "fp4-mx")
+        modes = ("fp8", "fp8-w4", "fp8-w4-mx", "fp4-mx", "fp4-mx+fused")   # (the fifth: Darknet.fp4_fused)
 
     def select(mode):
         m.precision, m.sparse = mode.split("+")[0], "2:4" if mode.endswith("+2:4") else None
+        m.fp4_fused = mode.endswith("+fused")
 
     def engine(mode):
         return [e for k, e in m._engines.items() if k[3] == mode.split("+")[0] and not e.train_layout][0]
@@ -99,7 +101,7 @@ def main(argv):
             res[prec] = {"logits": y.clone(), "layers": layer_times(prec)}
             if slim_pct is not None and prec == "fp8":
                 res[prec]["casts"] = layer_times(prec, only="cast")
-            if prec == "fp4-mx":                # (the MXFP4 activation cast in front of each fp4 x fp4 block)
+            if prec.startswith("fp4-mx"):       # (the MXFP4 activation cast in front of each unfused fp4 x fp4 block)
                 res[prec]["casts"] = layer_times(prec, only="cast4")
             if prec == "fp8":
                 fp8_layers = list(engine("fp8").fp8_layers)
@@ -207,6 +209,26 @@ def report_fp4(B, K, res, rates, fp4_layers, flop):
             "rel_l2_fp4_mx_vs_fp8": float((q["logits"].double() - res["fp8"]["logits"].double()).norm() / res["fp8"]["logits"].double().norm())}
 
 
+def report_fused(B, K, res, rates):
+    """The fifth leg of --w4, "fp4-mx" with Darknet.fp4_fused, beside the unfused one of the same process: per
+    layer the conv launch of either leg (the fused one carries the MXFP4 store of its consumer's cast), the cast launches that
+    are left, and the whole forward against every other leg.  Returns its JSON fields."""
+    q, f = res["fp4-mx"], res["fp4-mx+fused"]
+    print("%-6s %12s %12s %12s %12s" % ("conv", "unfused conv", "+ its cast", "fused conv", "+ its cast"))
+    for k in sorted(q["layers"]):
+        qc, fc = q["casts"].get(k, 0.0), f["casts"].get(k, 0.0)
+        print("%-6s %12.3f %12.3f %12.3f %12.3f" % ("conv%d" % k, q["layers"][k] - qc, qc, f["layers"].get(k, float("nan")) - fc, fc))
+    tq, tf = sum(q["layers"].values()), sum(f["layers"].values())
+    print("%-6s launches: unfused %.3f ms (casts %.3f), fused %.3f ms (casts %.3f)" % ("sum", tq, sum(q["casts"].values()), tf, sum(f["casts"].values())))
+    r = rates["fp4-mx+fused"]
+    pairs = {p: [b / a for a, b in zip(rates[p], r)] for p in ("fp4-mx", "fp8-w4-mx", "fp8")}
+    print("whole forward B=%d, %d forwards per window, fp4-mx fused: %s img/s (spread %.2f %%); pairs fused / %s"
+          % (B, K, ["%.0f" % v for v in r], 100.0 * (max(r) - min(r)) / min(r),
+             "; / ".join("%s %s" % (p, ["%.3f" % v for v in pairs[p]]) for p in pairs)))
+    return {"ms": f["layers"], "cast_ms": f["casts"], "img_s": r, "pairs_fused_over": pairs,
+            "logits_equal_unfused": bool((f["logits"] == q["logits"]).all())}
+
+
 def report_w4(B, K, out_json, mfma, res, rates, fp8_layers, w4_layers, nbytes, mx_layers, fp4_layers, flop):
     d, s, x = res["fp8"], res["fp8-w4"], res["fp8-w4-mx"]
 
@@ -233,6 +255,7 @@ def report_w4(B, K, out_json, mfma, res, rates, fp8_layers, w4_layers, nbytes, m
           % (nbytes["fp8"], nbytes["fp8-w4"], nbytes["fp8-w4"] / nbytes["fp8"], nbytes["fp8-w4-mx"]))
     print("logits rel-L2 against the fp8 engine, same weights: fp8-w4 %.3e, fp8-w4-mx %.3e" % (rel(s), rel(x)))
     fp4 = report_fp4(B, K, res, rates, fp4_layers, flop)
+    fp4["fused"] = report_fused(B, K, res, rates)
     sys.stdout.flush()
     if out_json:
         with open(out_json, "w") as f:
